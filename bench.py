@@ -39,6 +39,18 @@ value(N) / value(1) is the strong-scaling speed-up:
   --config c1|c3|c4 selects another headline; --config weak reproduces round
   1's weak-scaling series (10000 sqrt(N) samples x 100k sites).
 
+A plain run does only what the headline needs: set-up, warm-up, the timed
+steps, and the result line (`value`, `ms_per_step` and the `roofline` of those
+steps).  Everything measured or checked beside it takes --full: the planted-
+relatives check, `value_layout_reused`, `value_including_h2d`, the clock pass,
+`roofline.filter_worst_case`, `cpu_baseline`, `other_configs`, and for N > 1 the
+unpipelined gather, `with_broadcast` and `single_gpu_same_run` / `speedup`.
+
+--dump-outputs DIR writes the records of the last timed step (what a caller of
+compute_king receives, sorted as cuking.cu:761-765 sorts them) as DIR/<field>.npy:
+sample_i, sample_j, ibs0, ibs1, ibs2 in float64, kin in float32, and
+num_results.  The inputs are seeded (--seed), so two builds compare field by field.
+
 Prints ONE JSON line on rank 0.
 """
 from __future__ import annotations
@@ -106,9 +118,14 @@ def parse_args():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--config", default="", choices=["", "c1", "c2", "c3", "c4", "weak"],
                     help="workload behind `value`; default c2 at every N (strong scaling)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline (see the "
+                         "module docstring); a plain run times the headline steps only")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the records of the last timed step to DIR/<field>.npy")
     ap.add_argument("--extra-configs", default=None,
-                    help="comma list of further configs measured after the headline and "
-                         "reported under other_configs (default c0,c1,c3 with the default "
+                    help="--full: comma list of further configs measured after the headline "
+                         "and reported under other_configs (default c0,c1,c3 with the default "
                          "headline -- c0 = the real-input path through the C++ host, N = 1 "
                          "only --, + c4 from 4 GPUs on; 'none' disables)")
     ap.add_argument("--samples", type=int, default=0, help="override N samples")
@@ -127,7 +144,7 @@ def parse_args():
                     help="-1 automatic, 0 lean form (4 sums + recount of emitted pairs), "
                          "1 full form (5 sums)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0,
-                    help="target CPU-baseline time (0 disables it)")
+                    help="--full: target CPU-baseline time (0 disables it)")
     ap.add_argument("--cpu-threads", type=int, default=0,
                     help="OpenMP threads of the CPU baseline (0 = min(16, available))")
     ap.add_argument("--dist-mode", default="resident",
@@ -170,7 +187,12 @@ def parse_args():
                     help="library option set on the context (cuking_ctx_set_option), e.g. "
                          "filter_check1=0; repeatable (A/B runs)")
     ap.add_argument("--seed", type=int, default=20240229)
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.extra_configs not in (None, "none") and not args.full:
+        ap.error("--extra-configs measures beside the headline: it needs --full")
+    return args
 
 
 def cpu_model():
@@ -365,6 +387,28 @@ def records_of(results, count):
     return cuking_amd.sort_results(recs)
 
 
+DUMP_LIMIT_BYTES = 64_000_000        # all files, .npy headers included
+
+
+def dump_outputs(out_dir, recs):
+    """The sorted KingResult records of the last timed step, one .npy per field: kin in
+    float32 (its own type), the u32 fields in float64 (exact).  Beyond 64 MB a fixed,
+    seeded sample of the records (in sorted order) is written; num_results is the full
+    count either way."""
+    import numpy as np
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    row_bytes = 4 + 5 * 8
+    count = len(recs)
+    keep = (DUMP_LIMIT_BYTES - 4096) // row_bytes
+    if count > keep:
+        recs = recs[np.sort(np.random.default_rng(0).choice(count, keep, replace=False))]
+    np.save(d / "num_results.npy", np.array([count], dtype=np.float64))
+    for name in recs.dtype.names:
+        np.save(d / f"{name}.npy",
+                recs[name].astype(np.float32 if name == "kin" else np.float64))
+
+
 def check_planted(recs, cohort, thr, no_check):
     """Every planted relative the threshold admits must be reported (half
     siblings sit near 0.125: only asked for below 0.06)."""
@@ -421,12 +465,13 @@ def single_gpu_workload(args, ctx, n, m, thr, steps, warmup, local_rank, clock_p
     if ovf:
         raise SystemExit("result overflow: raise --max-results")
     recs = records_of(results, count)
-    check_planted(recs, cohort, thr, args.no_check)
+    # (what follows is measured or checked beside the headline: --full only)
+    check_planted(recs, cohort, thr, args.no_check or not args.full)
 
     # The same steps once more with the layout converted once and reused (round 3's
     # `value`): what a host that runs several passes over one cohort would see.
     reused = None
-    if not args.reuse_layout:
+    if args.full and not args.reuse_layout:
         ctx.set_option("reuse_prepared", 1)
         step()                                   # (converts if the workspace is stale)
         torch.cuda.synchronize()
@@ -441,7 +486,7 @@ def single_gpu_workload(args, ctx, n, m, thr, steps, warmup, local_rank, clock_p
     # The boundary hands over host buffers (cuking_copy_to_device): the copy of the
     # packed bitset from page-locked host memory, timed with events, best of three.
     h2d_ms = None
-    if h2d_pass and not args.no_h2d_pass:
+    if h2d_pass and args.full and not args.no_h2d_pass:
         host = torch.empty(bits.shape, dtype=bits.dtype, pin_memory=True)
         host.copy_(bits)
         back = torch.empty_like(bits)
@@ -458,7 +503,7 @@ def single_gpu_workload(args, ctx, n, m, thr, steps, warmup, local_rank, clock_p
         del host, back
 
     clock = None
-    if clock_pass and not args.no_clock_pass:
+    if clock_pass and args.full and not args.no_clock_pass:
         # the same steps once more with the one-wave clock probe beside them
         # (it holds a wave slot of one CU, so it stays out of the timed region)
         span_us = max(2000, int(0.8 * elapsed * 1e6))
@@ -715,7 +760,7 @@ def dist_workload(args, env, ctx, key, n, m, thr, steps, warmup, headline):
 
     gather_ms = None
     with_broadcast = None
-    if headline:
+    if headline and args.full:
         # the gather alone: one unpipelined pass, timed from "my kernel is done"
         barrier()
         out_tiles = compute_tiles(bits, *my_tiles)
@@ -759,7 +804,7 @@ def dist_workload(args, env, ctx, key, n, m, thr, steps, warmup, headline):
     # (the others wait), so that the strong-scaling ratio can be read off one JSON
     # line instead of two runs on possibly different boxes.
     single = None
-    if not args.no_single_gpu_pass and args.kernel == "tiled":
+    if args.full and not args.no_single_gpu_pass and args.kernel == "tiled":
         barrier()
         if rank == 0:
             reps = 3 if pairs < 10**9 else 1          # (short passes: take the best of three)
@@ -784,7 +829,7 @@ def dist_workload(args, env, ctx, key, n, m, thr, steps, warmup, headline):
 
     out = None
     if rank == 0:
-        check_planted(recs, cohort, thr, args.no_check)
+        check_planted(recs, cohort, thr, args.no_check or not args.full)
         if args.dist_mode == "staged":
             share = rank_tile_share((n + tile - 1) // tile, world, 0)
         else:
@@ -1129,13 +1174,14 @@ def main():
                      "between steps); roofline.prepare_ms is that one conversion" if reuse else
                      "every timed step converts the bitset into the kernel-internal layout "
                      "(roofline.prepare_ms, inside ms_per_step and `value`), as a one-pass job "
-                     "does; value_layout_reused is the rate with the layout converted once")
+                     "does; value_layout_reused (--full) is the rate with the layout converted "
+                     "once")
     ctx.timing_enable(True)
     dtype_of = lambda roof: ("fp4 products, f32 accumulate (exact integers)"
                              if roof["bound"] == "mfma" else "u32")
     extras = args.extra_configs
     if extras is None:
-        if config == "c2" and not custom:
+        if config == "c2" and not custom and args.full:
             extras = "c1,c3,c4" if (use_dist and world >= 4) else "c1,c3" if use_dist else "c0,c1,c3"
         else:
             extras = "none"
@@ -1148,13 +1194,15 @@ def main():
     if not use_dist:
         r = single_gpu_workload(args, ctx, n, m, thr, args.steps, args.warmup, local_rank,
                                 h2d_pass=True)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, r["recs"])
         roofline = roofline_block(
             args, ctx, launch_pairs=r["pairs"], sites=m, wps=r["wps"], thr=thr,
             king_ms=r["king_ms"], prepare_ms=r["prepare_ms"], launches=r["launches"],
             workload_key=f"{n}x{m}", clock_mhz=r["clock_mhz"])
         if r["filter"] is not None:
             roofline["filter"] = r["filter"]
-            if not custom and config == "c2" and not args.no_worst_case:
+            if args.full and not custom and config == "c2" and not args.no_worst_case:
                 roofline["filter_worst_case"] = filter_worst_case(args, ctx, r["bits"], n, m, thr,
                                                                   local_rank)
         out = {
@@ -1188,7 +1236,7 @@ def main():
                 "h2d_GBps": r["bits"].numel() * 8 / (r["h2d_ms"] * 1e-3) / 1e9,
                 "what": "ms_per_step + one host-to-device copy of the packed bitset from "
                         "page-locked memory (HIP events, best of three); never `value`"}
-        if args.cpu_seconds > 0:
+        if args.full and args.cpu_seconds > 0:
             bits = r["bits"]
 
             def host_bits(s):
@@ -1243,6 +1291,8 @@ def main():
     env = dict(world=world, rank=rank, local_rank=local_rank, dev=dev,
                host_or_dev="cpu" if rehearsal else dev)
     h = dist_workload(args, env, ctx, config, n, m, thr, args.steps, args.warmup, headline=True)
+    if h is not None and args.dump_outputs:
+        dump_outputs(args.dump_outputs, h["recs"])
     others = {}
     for key in extra_keys:
         c = CONFIGS[key]

@@ -76,7 +76,8 @@ def test_bench_refuses_a_world_size_that_does_not_match():
 
 
 # --------------------------------------------------- one GPU (rehearsal) ----
-SMALL = ["--samples", "3000", "--sites", "20000", "--steps", "2", "--warmup", "1",
+# (--full: the single-GPU pass and the broadcast-inclusive passes the tests read)
+SMALL = ["--samples", "3000", "--sites", "20000", "--steps", "2", "--warmup", "1", "--full",
          "--extra-configs", "none", "--cpu-seconds", "0", "--no-clock-pass"]
 
 

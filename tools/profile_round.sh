@@ -21,7 +21,7 @@ echo "$TS $TW" > $OUT/trace_steps.txt
 if [ $LIGHT = 1 ]; then
   python3 $REPO/bench.py $LEAN --steps $TS --warmup $TW "$@" > $OUT/bench.json 2> $OUT/bench.err
 else
-  python3 $REPO/bench.py --extra-configs none "$@" > $OUT/bench.json 2> $OUT/bench.err
+  python3 $REPO/bench.py --full --extra-configs none "$@" > $OUT/bench.json 2> $OUT/bench.err
 fi
 # per-dispatch durations (kernel_trace.csv) as well as the stats table: the first
 # launches of a process are cold, so the summary reports the median and the mean
