@@ -60,16 +60,12 @@ def _newer(target: Path, deps) -> bool:
     return all(Path(d).stat().st_mtime <= t for d in deps)
 
 
-def build_library(force: bool = False, save_temps: bool = False,
-                  tuning: bool = False) -> Path:
-    """tuning=True adds timing-only experiment kernels (-DCUKING_TUNING); never
-    the shipped configuration (build() and the tests use the default)."""
+def build_library(force: bool = False, save_temps: bool = False) -> Path:
     srcs = [CSRC / s for s in HIP_SOURCES + HOST_ABI_SOURCES]
     deps = srcs + [CSRC / "king_common.h", CSRC / "king_device.h", CSRC / "king_host.h",
                    CSRC / "king_submatrix.h", INCLUDE / "cuking_amd.h",
                    Path(__file__)]
-    extra = (["-DCUKING_TUNING"] if tuning else []) + \
-        os.environ.get("CUKING_EXTRA_HIPFLAGS", "").split()
+    extra = os.environ.get("CUKING_EXTRA_HIPFLAGS", "").split()
     wanted = " ".join(extra)
     # (no stamp = a library from before stamps existed, or a box the stamp did not
     #  travel to: trusted; a stamp that says something else = somebody's experiment)
@@ -78,7 +74,7 @@ def build_library(force: bool = False, save_temps: bool = False,
         return LIB_PATH
     cmd = [_hipcc(), *HIP_FLAGS, "-shared", f"-I{INCLUDE}", f"-I{CSRC}",
            *map(str, srcs), "-o", str(LIB_PATH)]
-    # experiments: extra -D flags, e.g. CUKING_EXTRA_HIPFLAGS="-DCUKING_MFMA_STAGES=3"
+    # experiments: extra compiler flags, e.g. CUKING_EXTRA_HIPFLAGS="-DMY_EXPERIMENT=1"
     for flag in extra:
         cmd.insert(1, flag)
     # Always with -save-temps (in build_tmp/): the assembly of the matrix-core
@@ -98,7 +94,7 @@ def build_library(force: bool = False, save_temps: bool = False,
             raise subprocess.CalledProcessError(r.returncode, cmd)
     problems = check_mfma_loops(cwd / "king_mfma-hip-amdgcn-amd-amdhsa-gfx950.s")
     problems += check_filter_loop(cwd / "king_filter-hip-amdgcn-amd-amdhsa-gfx950.s")
-    if problems and not (tuning or os.environ.get("CUKING_EXTRA_HIPFLAGS")):
+    if problems and not extra:
         LIB_PATH.unlink(missing_ok=True)
         raise RuntimeError("matrix-core kernel: the compiler put vector-memory waits or scratch "
                            "accesses inside an LDS-DMA loop:\n  " + "\n  ".join(problems))
@@ -110,8 +106,8 @@ def build_library(force: bool = False, save_temps: bool = False,
 
 def check_filter_loop(asm_path: Path, verbose: bool = False):
     """The same check for king_filter_kernel (king_filter.hip): its k-loops hold LDS-DMA
-    requests and hand-counted waits (22 in flight at a hand-over; 30 with
-    -DCUKING_FILTER_FINE=1) and must hold no scratch access and no other vmcnt wait."""
+    requests and a hand-counted wait (22 in flight at a hand-over) and must hold no
+    scratch access and no other vmcnt wait."""
     import re
     text = Path(asm_path).read_text()
     bodies = [m.group(1) for m in re.finditer(
@@ -133,7 +129,7 @@ def check_filter_loop(asm_path: Path, verbose: bool = False):
         seen += 1
         scratch = [l.strip() for l in loop if "scratch_" in l]
         waits = [l.strip() for l in loop if re.search(r"s_waitcnt.*vmcnt\(\d+\)", l)]
-        foreign = [w for w in waits if not any(f"vmcnt({n})" in w for n in (22, 30))]
+        foreign = [w for w in waits if "vmcnt(22)" not in w]
         if verbose:
             print(f"king_filter_kernel: loop {head} ({mfma} MFMAs): scratch {len(scratch)}, "
                   f"vmcnt waits {waits}")
@@ -159,9 +155,8 @@ def check_mfma_loops(asm_path: Path, verbose: bool = False):
         return [f"no king_mfma_kernel in {asm_path}"]
     problems = []
     for f in funcs:
-        m = re.match(r"_ZN6cuking12_GLOBAL__N_116king_mfma_kernelILb(\d)ELb(\d)ELi(\d)ELb(\d)", f)
-        label = (f"king_mfma_kernel<FULL={m.group(1)}, SPLIT={m.group(2)}, ABLATE={m.group(3)}, "
-                 f"N4={m.group(4)}>")
+        m = re.match(r"_ZN6cuking12_GLOBAL__N_116king_mfma_kernelILb(\d)ELb(\d)ELb(\d)", f)
+        label = f"king_mfma_kernel<FULL={m.group(1)}, SPLIT={m.group(2)}, N4={m.group(3)}>"
         body = f.split(".Lfunc_end")[0]
         seen = 0
         for block in re.split(r"\n(?=\.LBB\d+_\d+:)", body):
@@ -180,8 +175,8 @@ def check_mfma_loops(asm_path: Path, verbose: bool = False):
             seen += 1
             scratch = [l.strip() for l in loop if "scratch_" in l]
             waits = [l.strip() for l in loop if re.search(r"s_waitcnt.*vmcnt\(\d+\)", l)]
-            # (hand-counted: 16 = four stages in flight; 24 with CUKING_MFMA_PAIRED_STAGES=10;
-            #  20 = the four-product form's hand-over)
+            # (hand-counted: 16 = four stages in flight (full form); 24 = six (lean form,
+            #  paired hand-over); 20 = the four-product form's hand-over)
             foreign = [w for w in waits
                        if not any(f"vmcnt({n})" in w for n in (16, 20, 24))]
             if verbose:
@@ -234,10 +229,8 @@ def main(argv=None) -> int:
     ap.add_argument("--lib", action="store_true", help="library only")
     ap.add_argument("--force", action="store_true")
     ap.add_argument("--save-temps", action="store_true")
-    ap.add_argument("--tuning", action="store_true")
     args = ap.parse_args(argv)
-    print(build_library(force=args.force or args.tuning, save_temps=args.save_temps,
-                        tuning=args.tuning))
+    print(build_library(force=args.force, save_temps=args.save_temps))
     if not args.lib:
         print(build_cli(force=args.force))
     return 0

@@ -1287,24 +1287,6 @@ cuking_status cuking_ctx_get_option(const cuking_ctx *ctx, const char *key,
     }
     *value = (int64_t)(total + ctx->filter_totals_retired[word]);
   }
-  else if (strncmp(key, "filter_total_", 13) == 0) {
-    // Diagnostic (WAITS for the device): word N < 32 of the filter's running totals, summed
-    // over the context's streams -- the words behind the named ones are the timing build's
-    // (-DCUKING_FILTER_TIMING=1, king_filter.hip).
-    const int word = atoi(key + 13);
-    if (word < 0 || word >= 32) return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "unknown option %s", key);
-    if (hipSetDevice(ctx->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess)
-      return cuking_fail(CUKING_ERR_DEVICE, "device wait failed");
-    unsigned long long total = 0;
-    for (auto &e : ctx->filter_scratch) {
-      unsigned long long v = 0;
-      if (hipMemcpy(&v, e.base + filter_scratch_layout(e.tiles).totals + (size_t)word * 8, 8,
-                    hipMemcpyDeviceToHost) != hipSuccess)
-        return cuking_fail(CUKING_ERR_DEVICE, "reading the filter counters failed");
-      total += v;
-    }
-    *value = (int64_t)total;
-  }
   else if (strcmp(key, "filter_step_ticks16") == 0) {
     // Diagnostic (WAITS for the device): the 100 MHz counter's ticks per k-step x 16 as the
     // tiles of the last launch chunk measured them (rotated tiles, king_filter.hip), averaged
@@ -1688,63 +1670,6 @@ cuking_status cuking_timing_collect(cuking_ctx *ctx, double *king_ms,
   uint64_t na = 0, nb = 0;
   HIP_TRY(ctx->king_timer.collect(&a, &na));
   HIP_TRY(ctx->prepare_timer.collect(&b, &nb));
-#ifdef CUKING_MFMA_TIMELINE
-  mfma_timeline_dump();  // diagnostic build: the last matrix-core launch
-#endif
-#ifdef CUKING_MFMA_STAMPS
-  // diagnostic build: per-phase cycles of the matrix-core kernel's k-step, for
-  // k-steps without (row 0) and with (row 1) a stage hand-over
-  for (auto &e : ctx->split_scratch) {
-    std::vector<unsigned long long> h(1024 * 16);
-    uint32_t *scratch = e.second + mfma_split_counter_bytes(ctx->split_wgs) / sizeof(uint32_t);
-    if (hipMemcpy(h.data(), scratch, h.size() * 8, hipMemcpyDeviceToHost) != hipSuccess) break;
-    double sum[2][6] = {}, steps = 0;
-    int n = 0;
-    for (int b = 0; b < 1024; ++b)
-      if (h[b * 16 + 7] == 0x5354414D50ull) {
-        for (int k = 0; k < 6; ++k) sum[0][k] += (double)h[b * 16 + k];
-        for (int k = 0; k < 6; ++k) sum[1][k] += (double)h[b * 16 + 8 + k];
-        steps += (double)h[b * 16 + 6];
-        ++n;
-      }
-    if (n) {
-      // five-product loop: alternating k-steps without / with a hand-over (6 phases);
-      // four-product loop: per k-step three slices without and one with (4 groups)
-      for (int r = 0; r < 2; ++r) {
-        double t = 0;
-        for (int k = 0; k < 6; ++k) t += sum[r][k];
-        if (t == 0) continue;
-        fprintf(stderr,
-                "mfma stamps (%d workgroups, row %d = %s hand-over): cycles per k-step of the "
-                "tile  p0 %.0f | p1 %.0f | p2 %.0f | p3 %.0f | p4 %.0f | p5 %.0f | total %.0f\n",
-                n, r, r ? "with" : "without", sum[r][0] / steps, sum[r][1] / steps,
-                sum[r][2] / steps, sum[r][3] / steps, sum[r][4] / steps, sum[r][5] / steps,
-                t / steps);
-      }
-    }
-  }
-  // four-product loop: 4 slices x 4 groups (hi | hj + reads | dd + requests | q)
-  for (auto &e : ctx->split_scratch) {
-    std::vector<unsigned long long> h(1024 * 32);
-    uint32_t *scratch = e.second + mfma_split_counter_bytes(ctx->split_wgs) / sizeof(uint32_t);
-    if (hipMemcpy(h.data(), scratch, h.size() * 8, hipMemcpyDeviceToHost) != hipSuccess) break;
-    double sum[16] = {}, steps = 0;
-    int n = 0;
-    for (int b = 0; b < 1024; ++b)
-      if (h[b * 32 + 25] == 0x5354414D5034ull) {
-        for (int k = 0; k < 16; ++k) sum[k] += (double)h[b * 32 + (k < 7 ? k : k + 1)];
-        steps += (double)h[b * 32 + 24];
-        ++n;
-      }
-    if (n)
-      for (int c = 0; c < 4; ++c)
-        fprintf(stderr,
-                "mfma4 stamps (%d workgroups) slice %d: cycles per k-step  hi %.0f | hj+reads%s %.0f | "
-                "dd+requests %.0f | q %.0f\n",
-                n, c, sum[4 * c] / steps, c == 2 ? "+hand-over" : "", sum[4 * c + 1] / steps,
-                sum[4 * c + 2] / steps, sum[4 * c + 3] / steps);
-  }
-#endif
   if (king_ms) *king_ms = a;
   if (king_launches) *king_launches = na;
   if (prepare_ms) *prepare_ms = b;

@@ -351,11 +351,7 @@ struct TiledVariant {
 // below 2^24.
 constexpr uint32_t kMfmaMaxSites = 1u << 24;
 
-#ifdef CUKING_TUNING
-constexpr int kNumTiledVariants = 14;  // + timing-only experiments
-#else
 constexpr int kNumTiledVariants = 8;
-#endif
 constexpr int kMfmaVariant = 5;    // five plane products, quad layout
 constexpr int kMfmaN4Variant = 6;  // four plane products, nibble layout (king_mfma.hip)
 // The four-product variant decides kinship on the integer num = hi + hj - 2 dd
@@ -461,10 +457,11 @@ inline FilterScratchLayout filter_scratch_layout(uint64_t tiles) {
 inline bool is_mfma_variant(int v) {
   return v == kMfmaVariant || v == kMfmaN4Variant || v == kMfmaFilterVariant;
 }
-#ifndef CUKING_MFMA_STAGES
-#define CUKING_MFMA_STAGES 6
-#endif
-constexpr uint32_t kMfmaLdsBytes = CUKING_MFMA_STAGES * 2 * 2 * 2 * 128 * 16;
+// LDS stages of the five-product kernel's full form (16 KiB each, king_mfma.hip; the
+// lean form has kStagesPaired): stage s + kMfmaStages - 1 is requested while stage s is
+// multiplied, i.e. kMfmaStages - 2 k-steps (~1.4 us each) of HBM latency are covered.
+constexpr int kMfmaStages = 6;
+constexpr uint32_t kMfmaLdsBytes = kMfmaStages * 2 * 2 * 2 * 128 * 16;
 // The full form parks its fifth sum (64 registers per lane) behind the stages.
 constexpr uint32_t kMfmaParkBytes = 4 * 64 * 64 * 4;
 static_assert(kMfmaLdsBytes + kMfmaParkBytes <= 160 * 1024, "LDS of one CU");
@@ -516,9 +513,6 @@ hipError_t launch_mark_codes_ready(const uint32_t *gate, uint32_t *ready, hipStr
 // the counter part alone (the only part that must start out zero).
 size_t mfma_split_scratch_bytes(uint32_t wgs);
 size_t mfma_split_counter_bytes(uint32_t wgs);
-#ifdef CUKING_MFMA_TIMELINE
-void mfma_timeline_dump();  // diagnostic build (king_mfma.hip)
-#endif
 
 // Converts plane-sample tiles [s_tile_begin, s_tile_end) (units of 64 plane
 // samples) of the block.

@@ -72,14 +72,11 @@ typedef int v8i __attribute__((ext_vector_type(8)));
 typedef float v16f __attribute__((ext_vector_type(16)));
 
 constexpr int kT = (int)kFilterTile;
-// LDS stages: 5 of 32 KiB (two units of 64 sites per k-half: a k-step of 256 sites), or
-// -DCUKING_FILTER_FINE=1: 10 of 16 KiB (one unit: 128 sites per k-step, a hand-over per
-// 32 MFMAs, 8 instead of 3 k-steps between a request and the hand-over that needs it).
-#ifndef CUKING_FILTER_FINE
-#define CUKING_FILTER_FINE 0
-#endif
-constexpr int kUnits = CUKING_FILTER_FINE ? 1 : 2;   // units per k-half and stage
-constexpr int kStages = CUKING_FILTER_FINE ? 10 : 5;
+// LDS stages: 5 of 32 KiB (two units of 64 sites per k-half: a k-step of 256 sites).
+// 10 of 16 KiB (one unit, 8 instead of 3 k-steps of lead) measured the same: configs[2]
+// 148.1 -> 148.2 ms (profiles/r03_ablation.txt).
+constexpr int kUnits = 2;                             // units per k-half and stage
+constexpr int kStages = 5;
 constexpr int kSliceU4 = kT;                          // one (side, k-half, unit): 256 samples
 constexpr int kStageU4 = 2 * 2 * kUnits * kSliceU4;   // uint4 per stage
 constexpr int kStageReqs = 4 * kUnits;                // requests per wavefront and stage
@@ -211,17 +208,6 @@ __device__ __forceinline__ v8i tfrag(const uint4 w, uint32_t mask) {
   return r;
 }
 
-// Timing-only builds (wrong results, never shipped; tools/ab_flags.sh):
-// -DCUKING_FILTER_ABLATE=1 no LDS-DMA requests, =2 no stage barrier either,
-// =3 the shipped loop without the epilogue, =4 the shipped kernel with every tile
-// reading tile (0, 0)'s operands.
-#ifndef CUKING_FILTER_ABLATE
-#define CUKING_FILTER_ABLATE 0
-#endif
-#ifndef CUKING_FILTER_TIMING
-#define CUKING_FILTER_TIMING 0
-#endif
-
 __device__ __forceinline__ uint4 shl2(const uint4 w) {
   return make_uint4(w.x << 2, w.y << 2, w.z << 2, w.w << 2);
 }
@@ -229,7 +215,6 @@ __device__ __forceinline__ uint4 shl2(const uint4 w) {
 // One LDS-DMA request: lane l's 16 bytes of SRC + OFF land at DST + OFF + 16 l
 // (the immediate offset moves source and destination alike).
 #define F_ISSUE(SRC, DST, OFF)                                                 \
-  if (CUKING_FILTER_ABLATE != 1 && CUKING_FILTER_ABLATE != 2)                  \
   asm volatile("s_mov_b32 m0, %0\n\t"                                          \
                "s_nop 0\n\t"                                                   \
                "global_load_lds_dwordx4 %1, %2 offset:" #OFF                   \
@@ -242,32 +227,6 @@ __device__ __forceinline__ uint4 shl2(const uint4 w) {
 // dynamic tail is through: uniform, before anything else), 0 otherwise -- wavefronts return
 // from the epilogue one by one.  lds: [kStages][side][k-half][unit][256].
 __device__ __forceinline__ int filter_tile(const TiledArgs &a, const uint32_t wg, uint4 *const lds) {
-
-#if CUKING_FILTER_TIMING
-  // Timing build (tools/tile_gaps.sh): how long a CU waits for its next workgroup, and how
-  // long a workgroup takes to its first request.  Totals 8 .. 11 (100 MHz ticks, summed by
-  // thread 0): gaps between a workgroup's exit at the check point and the entry of the next
-  // workgroup on the same CU, their number, entry -> first request, their number.  The
-  // table of last exits per CU sits in the (idle) slabs of the remainder pieces.
-  const uint32_t t_entry = (uint32_t)__builtin_amdgcn_s_memrealtime();
-  uint32_t cu_key;
-  {
-    uint32_t hw, xcc;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-    cu_key = ((xcc & 15u) << 8) | ((hw >> 8) & 255u);  // XCC | SE, SH, CU
-  }
-  uint32_t *const cu_last_exit = reinterpret_cast<uint32_t *>(a.fsplit_slabs);
-  if (threadIdx.x == 0 && cu_last_exit != nullptr && a.tile_done != nullptr) {
-    const uint32_t last = __hip_atomic_load(cu_last_exit + cu_key, __ATOMIC_RELAXED,
-                                            __HIP_MEMORY_SCOPE_AGENT);
-    if (last != 0) {
-      __hip_atomic_fetch_add(a.filter_totals + 8, (unsigned long long)(t_entry - last),
-                             __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_fetch_add(a.filter_totals + 9, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-  }
-#endif
   uint32_t bid = wg;
   // Remainder of a short launch (king_common.h, fsplit_*): piece `part` of the k
   // range of one of the launch's last tiles.
@@ -315,15 +274,8 @@ __device__ __forceinline__ int filter_tile(const TiledArgs &a, const uint32_t wg
   // over the chunk in its own order, king_mfma.hip persistent mode) computes every tile
   // that has not set its tile_done flag.  The worst case costs the exact kernel's time
   // plus the first round of this one (short launches: plus an eighth of it, check 0).
-// (A/B: k-steps a new tile starts ahead of where the tiles of its XCD are)
-#ifndef CUKING_ROTATE_LEAD
-#define CUKING_ROTATE_LEAD 0
-#endif
-#ifndef CUKING_FILTER_GIVE_UP
-#define CUKING_FILTER_GIVE_UP 1  // (A/B: 0 = tiles never give up)
-#endif
   uint32_t xcd_pos = 0;  // the k-step the tiles of this XCD are at (rotated tiles)
-  if (CUKING_FILTER_GIVE_UP && !split && a.tile_done != nullptr) {
+  if (!split && a.tile_done != nullptr) {
     // ONE decision per workgroup (the counters move while the wavefronts read them,
     // and a wavefront that left alone would take its quarter of every stage's
     // requests with it): thread 0 reads, the stage memory carries the verdict.
@@ -381,7 +333,7 @@ __device__ __forceinline__ int filter_tile(const TiledArgs &a, const uint32_t wg
       uint32_t pos = (uint32_t)(said >> 32);
       const uint32_t ago = (uint32_t)__builtin_amdgcn_s_memrealtime() - (uint32_t)said;
       if (said != 0 && ticks16 != 0 && ago < 16384u)
-        pos += ago * 16u / ticks16 + CUKING_ROTATE_LEAD;
+        pos += ago * 16u / ticks16;
       verdict[1 + threadIdx.x] = pos;
     }
     __syncthreads();
@@ -412,9 +364,8 @@ __device__ __forceinline__ int filter_tile(const TiledArgs &a, const uint32_t wg
       split ? part * all_steps / a.fsplit_parts : 0u);
   const uint32_t num_steps = __builtin_amdgcn_readfirstlane(
       split ? (part + 1) * all_steps / a.fsplit_parts - k_first : all_steps);
-  // (=4: every tile reads the operands of tile (0, 0) -- all requests hit the L2)
-  const uint4 *g_rows = a.t2 + (CUKING_FILTER_ABLATE == 4 ? 0u : (uint64_t)tr * kT);
-  const uint4 *g_cols = a.t2 + a.geo.col_base + (CUKING_FILTER_ABLATE == 4 ? 0u : (uint64_t)tc * kT);
+  const uint4 *g_rows = a.t2 + (uint64_t)tr * kT;
+  const uint4 *g_cols = a.t2 + a.geo.col_base + (uint64_t)tc * kT;
 
   uint32_t mT;
   asm volatile("s_mov_b32 %0, 0xcccccccc" : "=s"(mT));
@@ -547,8 +498,8 @@ __device__ __forceinline__ int filter_tile(const TiledArgs &a, const uint32_t wg
   // in the gaps of the last eight that unit's set-B fragments.
 #define F_SLICE_A(CUR, NXT, RBUF, RC, SYNC, PA, DC, OFF0, OFF1)                \
   {                                                                            \
-    if ((SYNC) && CUKING_FILTER_ABLATE != 2) {                                 \
-      if (CUKING_FILTER_ABLATE != 1) __builtin_amdgcn_s_waitcnt(vmcnt_imm(kSyncVm)); \
+    if (SYNC) {                                                                \
+      __builtin_amdgcn_s_waitcnt(vmcnt_imm(kSyncVm));                          \
       __syncthreads();                                                         \
     }                                                                          \
     const char *src_ = (PA).src + (DC) * row_bytes;                            \
@@ -577,17 +528,6 @@ __device__ __forceinline__ int filter_tile(const TiledArgs &a, const uint32_t wg
   // hand-over of k-step s (stage s + 1 must have landed) comes in its last slice:
   // in flight then may be the stages after s + 1 and the requests of the newest one
   // that the slices before the last have issued (kSyncVm: 2 x 8 + 6 = 22).
-#if CUKING_FILTER_FINE
-#define F_KSTEP                                                                \
-  {                                                                            \
-    const uint32_t nbuf = buf == kStages - 1 ? 0 : buf + 1;                    \
-    F_SLICE_B(0, 1, pa, 0, 0, 1024)                                            \
-    F_SLICE_A(1, 0, nbuf, 0, true, pa, 0, 2048, 3072)                          \
-    pa = addr_next(pa, step + kStages, buf);                                   \
-    buf = nbuf;                                                                \
-    ++step;                                                                    \
-  }
-#else
 #define F_KSTEP                                                                \
   {                                                                            \
     const uint32_t nbuf = buf == kStages - 1 ? 0 : buf + 1;                    \
@@ -599,7 +539,6 @@ __device__ __forceinline__ int filter_tile(const TiledArgs &a, const uint32_t wg
     buf = nbuf;                                                                \
     ++step;                                                                    \
   }
-#endif
 
   // --- Check points (king_common.h).  X = sum over the sites of (g_i - g_j)^2 has only
   // non-negative terms, so its sum over a PREFIX of the sites is a lower bound of X, and
@@ -636,7 +575,7 @@ __device__ __forceinline__ int filter_tile(const TiledArgs &a, const uint32_t wg
   // differences of the cumulative counts sample_stats_kernel leaves.
   uint32_t chk0 = 0, chk1 = 0, entry1 = 0, share1 = 0;
   uint32_t phase = 0, k0 = 0, wrap = 0, start_abs = 0;
-  if (!CUKING_FILTER_FINE && !split && a.check_steps != nullptr && a.tile_done != nullptr) {
+  if (!split && a.check_steps != nullptr && a.tile_done != nullptr) {
     if (a.rotate != 0 && all_steps >= a.rotate_min_steps) {
       uint32_t base = 0;
       if (a.rotate == 1) {
@@ -735,14 +674,6 @@ __device__ __forceinline__ int filter_tile(const TiledArgs &a, const uint32_t wg
   uint32_t *const ticks_word = a.filter_ctrl + kCtrlStepTicks + (wg & 7);
   // (the first request of the tile goes out about now)
   const uint32_t t_start = a.rotate == 1 ? (uint32_t)__builtin_amdgcn_s_memrealtime() : 0u;
-#if CUKING_FILTER_TIMING
-  if (threadIdx.x == 0 && a.tile_done != nullptr && !split) {
-    __hip_atomic_fetch_add(a.filter_totals + 10,
-                           (unsigned long long)((uint32_t)__builtin_amdgcn_s_memrealtime() - t_entry),
-                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_fetch_add(a.filter_totals + 11, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-#endif
 #define F_PUBLISH(STEPS)                                                       \
   if (a.rotate == 1 && wave == 0) {                                            \
     const uint32_t now_ = (uint32_t)__builtin_amdgcn_s_memrealtime();          \
@@ -794,10 +725,9 @@ __device__ __forceinline__ int filter_tile(const TiledArgs &a, const uint32_t wg
     for (int st = 0; st < kStages - 1; ++st) {
       const Addr p0 = addr_of(st, st);
       F_ISSUE4(p0, 0)
-      if (kUnits == 2) F_ISSUE4(p0, 1)
+      F_ISSUE4(p0, 1)
     }
-    if (CUKING_FILTER_ABLATE != 1 && CUKING_FILTER_ABLATE != 2)
-      __builtin_amdgcn_s_waitcnt(vmcnt_imm((kStages - 2) * kStageReqs));
+    __builtin_amdgcn_s_waitcnt(vmcnt_imm((kStages - 2) * kStageReqs));
     __syncthreads();
     // unit 0 of stage 0, set B
 #pragma unroll
@@ -811,21 +741,11 @@ __device__ __forceinline__ int filter_tile(const TiledArgs &a, const uint32_t wg
     uint32_t buf = 0;  // buffer of the k-step being multiplied
     Addr pa = addr_of(kStages - 1, kStages - 1);
     uint32_t step = 0;
-#if CUKING_FILTER_FINE
-    while (step + 3 < seg_steps) {
-      F_KSTEP
-      F_KSTEP
-      F_KSTEP
-      F_KSTEP
-    }
-    while (step < seg_steps) F_KSTEP
-#else
     while (step + 1 < seg_steps) {
       F_KSTEP
       F_KSTEP
     }
     if (step < seg_steps) F_KSTEP
-#endif
     // The clamped repeats of the last stage must have landed before the stages
     // become the check's or the epilogue's scratch.
     __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
@@ -943,11 +863,6 @@ __device__ __forceinline__ int filter_tile(const TiledArgs &a, const uint32_t wg
         __hip_atomic_fetch_add(
             a.filter_totals + kTotalEarly, 1ull,
             __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#if CUKING_FILTER_TIMING
-        if (cu_last_exit != nullptr)
-          __hip_atomic_store(cu_last_exit + cu_key, (uint32_t)__builtin_amdgcn_s_memrealtime() | 1u,
-                             __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#endif
       }
     }
     return 0;
@@ -1019,18 +934,6 @@ __device__ __forceinline__ int filter_tile(const TiledArgs &a, const uint32_t wg
             acc[bi][bj][4 * r4 + 3] += v.w;
           }
     }
-  }
-
-  if (CUKING_FILTER_ABLATE != 0) {
-    float sum = 0.f;
-#pragma unroll
-    for (int bi = 0; bi < 4; ++bi)
-#pragma unroll
-      for (int bj = 0; bj < 4; ++bj)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) sum += acc[bi][bj][r];
-    if (sum == -1.f) a.results[0].kin = sum;  // never true, keeps the sums alive
-    return 0;
   }
 
   // --- epilogue: the bound, per pair.  C layout of the 32 x 32 MFMA: column =
@@ -1166,7 +1069,7 @@ __global__ __launch_bounds__(256, 1) void king_filter_kernel(const TiledArgs a) 
 // The same launch from ONE workgroup per CU that takes tile after tile (king_common.h
 // persist_wgs; option "filter_persistent", OFF by default).  A CU waits 32 us of a 430 us tile
 // for the dispatcher between two workgroups of the one-tile-per-workgroup grid
-// (tools/tile_gaps.sh: exit at the check point -> entry of the next workgroup on the same
+// (profiles/r04_tile_gaps.txt: exit at the check point -> entry of the next workgroup on the same
 // CU; 160 KiB of LDS and 512 registers per workgroup) -- and yet this kernel, which does not
 // wait, runs configs[2] in 135.9-136.0 ms against 134.3-134.4 (same box, interleaved): the chip
 // is power-bound under the matrix pipes, and what an idle CU does not draw the others clock
@@ -1323,12 +1226,6 @@ hipError_t launch_filter(const TiledArgs &args, uint64_t num_tiles, hipStream_t 
     const bool checks = args.tile_done != nullptr;
     hipError_t e = hipMemsetAsync(args.filter_ctrl, 0, kCtrlChunkBytes + (checks ? n : 0), stream);
     if (e != hipSuccess) return e;
-#if CUKING_FILTER_TIMING
-    if (args.fsplit_slabs != nullptr) {  // (the timing build's table of last exits per CU)
-      e = hipMemsetAsync(args.fsplit_slabs, 0, 4096 * sizeof(uint32_t), stream);
-      if (e != hipSuccess) return e;
-    }
-#endif
     TiledArgs a = args;
     a.tile_begin = args.tile_begin + done;
     a.quad = 0;

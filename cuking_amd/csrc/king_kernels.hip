@@ -160,10 +160,7 @@ __device__ __forceinline__ uint32_t spread8(uint32_t b) {
 // rows of the reference layout are words_per_sample x 8 bytes apart, so longer
 // runs mean fewer DRAM pages per byte), transposed through LDS, written 1 KiB
 // per k-row (64 consecutive samples).
-#ifndef CUKING_NIB_WORDS
-#define CUKING_NIB_WORDS 32  // (A/B: 16, 64)
-#endif
-constexpr int kNibWords = CUKING_NIB_WORDS;
+constexpr int kNibWords = 32;
 
 // CODES: the fp4 codes and the het-only copy; T2: the filter kernel's two-bit layout
 // (king_common.h, kLayoutNibbleStats).  `perm` (or nullptr): which stored sample sits at
@@ -324,10 +321,9 @@ __global__ __launch_bounds__(256) void prepare_nibbles_kernel(
 // the two kinds and every instruction costs ~4 cycles; two waves of one
 // workgroup on the same SIMD that enter their logic phases together pair
 // their full-rate instructions up, and the stream costs the sum of its parts
-// (~3.05 cycles per instruction for this mix).  (PHASED 2 / 3: barrier
-// placements that measured slower, tuning builds only.)
+// (~3.05 cycles per instruction for this mix).
 template <int TIT, int TJT, int RI, int RJ, int KC, int KU, int MINW, bool FULL,
-          int ABLATE = 0, int PHASED = 0>  // ABLATE bit 2: one column operand at a time
+          bool PHASED = false>
 __global__ __launch_bounds__(TIT *TJT, MINW) void king_tiled_kernel(
     const TiledArgs a) {
   constexpr int TILE = TIT * RI;
@@ -403,13 +399,9 @@ __global__ __launch_bounds__(TIT *TJT, MINW) void king_tiled_kernel(
     const uint32_t buf = chunk & 1;
     // Chunk `chunk` has landed (vmcnt) for every wave, and every wave is done
     // reading the other buffer.
-    // (ABLATE: timing-only experiments of the tuning build; results are
-    // wrong.  bit 0 = no per-step LDS reads, bit 1 = no DMA and no barrier.)
-    if (!(ABLATE & 2)) {
-      __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0), leaves lgkmcnt/expcnt
-      __syncthreads();
-      if (chunk + 1 < num_chunks) issue_chunk(chunk + 1, buf ^ 1);
-    }
+    __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0), leaves lgkmcnt/expcnt
+    __syncthreads();
+    if (chunk + 1 < num_chunks) issue_chunk(chunk + 1, buf ^ 1);
 
     const uint4 *l_rows = lds + (buf * 2 + 0) * KC * TILE;
     const uint4 *l_cols = lds + (buf * 2 + 1) * KC * TILE;
@@ -447,8 +439,7 @@ __global__ __launch_bounds__(TIT *TJT, MINW) void king_tiled_kernel(
           for (int y = 0; y < RJ; ++y) cj[y] = l_cols[(kc + 1) * TILE + y * TJT + tj];
         }
         __builtin_amdgcn_sched_barrier(0);
-        if (PHASED >= 2) __builtin_amdgcn_s_barrier();  // tuning only: measured slower
-        __builtin_amdgcn_sched_barrier(0);
+        __builtin_amdgcn_sched_barrier(0);  // (twice: one alone changes the register assignment)
         // --- popcount phase: half-rate instructions only.  Inline asm keeps
         // the accumulate fused (v_bcnt d, s, d): left to itself the compiler
         // re-associates two k-steps into bcnt + bcnt + v_add3. ---
@@ -465,7 +456,7 @@ __global__ __launch_bounds__(TIT *TJT, MINW) void king_tiled_kernel(
           }
         }
         __builtin_amdgcn_sched_barrier(0);
-        if (PHASED != 3) __builtin_amdgcn_s_barrier();  // aligns the next logic phase
+        __builtin_amdgcn_s_barrier();  // aligns the next logic phase
         __builtin_amdgcn_sched_barrier(0);
       }
       continue;
@@ -475,39 +466,10 @@ __global__ __launch_bounds__(TIT *TJT, MINW) void king_tiled_kernel(
 #pragma unroll KU
     for (int kc = 0; kc < KC; ++kc) {
       uint4 ri[RI], cj[RJ];
-      const int kr = (ABLATE & 1) ? 0 : kc;
 #pragma unroll
-      for (int x = 0; x < RI; ++x) ri[x] = l_rows[kr * TILE + x * TIT + ti];
-      if (!(ABLATE & 4)) {
+      for (int x = 0; x < RI; ++x) ri[x] = l_rows[kc * TILE + x * TIT + ti];
 #pragma unroll
-        for (int y = 0; y < RJ; ++y) cj[y] = l_cols[kr * TILE + y * TJT + tj];
-      }
-      if (ABLATE & 1) {  // keep the logic ops from being hoisted
-#pragma unroll
-        for (int x = 0; x < RI; ++x)
-          asm volatile("" : "+v"(ri[x].x), "+v"(ri[x].y), "+v"(ri[x].z), "+v"(ri[x].w));
-#pragma unroll
-        for (int y = 0; y < RJ; ++y)
-          asm volatile("" : "+v"(cj[y].x), "+v"(cj[y].y), "+v"(cj[y].z), "+v"(cj[y].w));
-      }
-      if (ABLATE & 4) {
-        // Register-lean order: one column operand live at a time.
-#pragma unroll
-        for (int y = 0; y < RJ; ++y) {
-          const uint4 c = l_cols[kr * TILE + y * TJT + tj];
-#pragma unroll
-          for (int x = 0; x < RI; ++x) {
-            const uint32_t hom_both = ri[x].z & c.z;
-            if (FULL) c_hh[x][y] += __builtin_popcount(hom_both);
-            c_opp[x][y] += __builtin_popcount(
-                __builtin_amdgcn_bitop3_b32(ri[x].y, c.y, hom_both, 0x28));
-            c_bh[x][y] += __builtin_popcount(ri[x].x & c.x);
-            c_hi[x][y] += __builtin_popcount(ri[x].x & c.w);
-            c_hj[x][y] += __builtin_popcount(ri[x].w & c.x);
-          }
-        }
-        continue;
-      }
+      for (int y = 0; y < RJ; ++y) cj[y] = l_cols[kc * TILE + y * TJT + tj];
 #pragma unroll
       for (int x = 0; x < RI; ++x) {
 #pragma unroll
@@ -701,10 +663,10 @@ __global__ __launch_bounds__(256) void pack_compact_kernel(
 uint64_t g_max_blocks_override = 0;  // tests: force splitting at small sizes
 
 template <int TIT, int TJT, int RI, int RJ, int KC, int KU, int MINW, bool FULL,
-          int ABLATE = 0, int PHASED = 0>
+          bool PHASED = false>
 hipError_t launch_variant(const TiledArgs &args, uint64_t num_tiles,
                           uint32_t lds_bytes, hipStream_t stream) {
-  auto kernel = king_tiled_kernel<TIT, TJT, RI, RJ, KC, KU, MINW, FULL, ABLATE, PHASED>;
+  auto kernel = king_tiled_kernel<TIT, TJT, RI, RJ, KC, KU, MINW, FULL, PHASED>;
   // The attribute belongs to the function object of ONE device: a host with
   // contexts on several GPUs has to set it on each of them.
   static DeviceOnce attr_set;
@@ -747,14 +709,6 @@ const TiledVariant kVariants[kNumTiledVariants] = {
     // what it lets through: 256 x 256 pairs per workgroup, 128 sites per k-step
     // (king_filter.hip).
     {"t256_mfma_fp4_filter", kFilterTile, 8, 256, kFilterLdsBytes, kLayoutNibbleStats},
-#ifdef CUKING_TUNING
-    {"phased_both_barriers", 64, 16, 512, 2 * 2 * 16 * 64 * 16, kLayoutWord},
-    {"phased_bar_before_popcount_only", 64, 16, 512, 2 * 2 * 16 * 64 * 16, kLayoutWord},
-    {"phased_k8", 64, 8, 512, 2 * 2 * 8 * 64 * 16, kLayoutWord},
-    {"unphased_noldsread", 64, 8, 256, 2 * 2 * 8 * 64 * 16, kLayoutWord},
-    {"unphased_nodma_nobarrier", 64, 8, 256, 2 * 2 * 8 * 64 * 16, kLayoutWord},
-    {"unphased_w5", 64, 8, 256, 2 * 2 * 8 * 64 * 16, kLayoutWord},
-#endif
 };
 
 
@@ -776,11 +730,10 @@ hipError_t launch_tiled(int variant, bool full, const TiledArgs &args,
 #define CUKING_SHAPE(...)                                                      \
   (full ? launch_variant<__VA_ARGS__, true>(args, num_tiles, lds, stream)      \
         : launch_variant<__VA_ARGS__, false>(args, num_tiles, lds, stream))
-#define CUKING_PHASED(KC_, MODE_)                                              \
-  (full ? launch_variant<16, 32, 4, 2, KC_, KC_, 4, true, 0, MODE_>(args, num_tiles, lds, stream) \
-        : launch_variant<16, 32, 4, 2, KC_, KC_, 4, false, 0, MODE_>(args, num_tiles, lds, stream))
   switch (variant) {
-    case 0: return CUKING_PHASED(16, 1);
+    case 0:
+      return full ? launch_variant<16, 32, 4, 2, 16, 16, 4, true, true>(args, num_tiles, lds, stream)
+                  : launch_variant<16, 32, 4, 2, 16, 16, 4, false, true>(args, num_tiles, lds, stream);
     case 1: return CUKING_SHAPE(16, 16, 4, 4, 8, 2, 4);
     case 2: return CUKING_SHAPE(16, 32, 8, 4, 8, 2, 2);
     case 3: return CUKING_SHAPE(32, 32, 4, 4, 8, 2, 4);
@@ -803,18 +756,9 @@ hipError_t launch_tiled(int variant, bool full, const TiledArgs &args,
       }
       return launch_mfma(full, true, a, num_tiles, kMfmaN4LdsBytes, stream);
     }
-#ifdef CUKING_TUNING
-    case 8: return CUKING_PHASED(16, 2);
-    case 9: return CUKING_PHASED(16, 3);
-    case 10: return CUKING_PHASED(8, 1);
-    case 11: return launch_variant<16, 16, 4, 4, 8, 2, 4, false, 1>(args, num_tiles, lds, stream);
-    case 12: return launch_variant<16, 16, 4, 4, 8, 2, 4, false, 2>(args, num_tiles, lds, stream);
-    case 13: return launch_variant<16, 16, 4, 4, 8, 1, 5, false, 4>(args, num_tiles, lds, stream);
-#endif
     default: return hipErrorInvalidValue;
   }
 #undef CUKING_SHAPE
-#undef CUKING_PHASED
 }
 
 hipError_t launch_prepare_planes(uint32_t layout, const uint64_t *d_bit_sets,

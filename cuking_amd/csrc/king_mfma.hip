@@ -29,15 +29,12 @@
 // (four 32-site words) per plane and block, read from LDS with ds_read_b128
 // and expanded four times (f = 0..3): 80 MFMAs per k-step and wavefront.  The
 // planes come from the quad layout (king_common.h) by LDS-DMA, 16 KiB per
-// k-step, kStages stages deep.  DESIGN.md 4.1 has the measurements behind the
-// choices; archive/profiles/r01_mfma_microbench.txt the raw numbers.
+// k-step, kMfmaStages stages deep (king_common.h).  DESIGN.md 4.1 has the
+// measurements behind the choices; archive/profiles/r01_mfma_microbench.txt the
+// raw numbers.
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <stdlib.h>
-#ifdef CUKING_MFMA_TIMELINE
-#include <algorithm>
-#include <vector>
-#endif
 
 #include "king_common.h"
 #include "king_device.h"
@@ -45,13 +42,6 @@
 // The LDS-DMA statements below write M0 and say so in their clobber lists; the
 // compiler notes that it keeps no value of its own there (M0 is reserved).
 #pragma clang diagnostic ignored "-Winline-asm"
-
-#ifndef CUKING_MFMA_STAGES
-#define CUKING_MFMA_STAGES 6
-#endif
-#ifndef CUKING_MFMA_PREFILTER
-#define CUKING_MFMA_PREFILTER 1  // 0: exact kinship for every pair (A/B experiments)
-#endif
 
 namespace cuking {
 
@@ -63,25 +53,13 @@ typedef float v16f __attribute__((ext_vector_type(16)));
 constexpr int kTile = 128;
 constexpr int kStageU4 = 2 * 2 * 2 * kTile;  // sides x k-groups x planes x samples
 constexpr int kPiecesPerWave = 4;            // 16 x 1 KiB per stage, 4 wavefronts
-// LDS stages (16 KiB each): stage s + kStages - 1 is requested while stage s
-// is multiplied, i.e. kStages - 2 k-steps (~1.4 us each) of HBM latency are
-// covered.
-constexpr int kStages = CUKING_MFMA_STAGES;
 // Lean form (no LDS needed for a parked sum): more stages, at least the two it
 // takes to hand stages over with one barrier per TWO k-steps.
-#ifndef CUKING_MFMA_PAIRED
-#define CUKING_MFMA_PAIRED 1
-#endif
-constexpr bool kPairedSync = CUKING_MFMA_PAIRED != 0 && kStages == 6;
-#ifndef CUKING_MFMA_PAIRED_STAGES
-// even, 8 or 10.  10 x 16 KiB is the CU's whole LDS and puts 5.5 instead of 3.5
-// k-steps between a request and the hand-over that needs it: configs[2] 593 ->
-// 590 ms, 40k x 100k 95.2 -> 94.7 ms, configs[1] (bitset in the Infinity Cache) equal
+// 10 x 16 KiB is the CU's whole LDS and puts 5.5 instead of 3.5 k-steps (8 stages)
+// between a request and the hand-over that needs it: configs[2] 593 -> 590 ms,
+// 40k x 100k 95.2 -> 94.7 ms, configs[1] (bitset in the Infinity Cache) equal
 // (archive/experiments/exp25.sh).
-#define CUKING_MFMA_PAIRED_STAGES 10
-#endif
-constexpr int kStagesPaired = CUKING_MFMA_PAIRED_STAGES;
-static_assert(kStagesPaired % 2 == 0 && kStagesPaired >= 8 && kStagesPaired <= 10, "stages");
+constexpr int kStagesPaired = 10;
 // s_waitcnt vmcnt(N) immediate for N requests that may stay in flight.
 constexpr int vmcnt_imm(int n) { return 0x0F70 | (n & 15) | ((n >> 4) << 14); }
 
@@ -189,47 +167,6 @@ __device__ __attribute__((noinline)) uint32_t reserve_slots(uint32_t *result_ind
     if ((v) > 0) __builtin_amdgcn_sched_group_barrier(0x002, (v), 0);          \
   }
 
-// Diagnostic build (-DCUKING_MFMA_TIMELINE, never shipped): when the workgroups
-// of a launch start and finish, and where a piece's time goes (100 MHz
-// s_memrealtime, comparable across the chip).  [workgroup][12]: 0 entry,
-// per segment s (0, 1): 1+5s start, 2+5s loop entered, 3+5s loop done,
-// 4+5s slab / totals done, 5+5s epilogue done, 11 exit.
-#ifdef CUKING_MFMA_TIMELINE
-__device__ unsigned long long *g_timeline;
-constexpr uint32_t kTimelineBlocks = 1u << 19;
-void timeline_arm(uint32_t whole, uint32_t blocks);
-#define CUKING_TL(K)                                                           \
-  if (threadIdx.x == 0 && g_timeline != nullptr && blockIdx.x < kTimelineBlocks) { \
-    unsigned long long t_;                                                     \
-    asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory"); \
-    g_timeline[(size_t)blockIdx.x * 12 + (K)] = t_;                            \
-  }
-#else
-#define CUKING_TL(K)
-#endif
-
-// Diagnostic build (-DCUKING_MFMA_STAMPS, never shipped): where a wavefront's
-// time goes inside a k-step.  One s_memtime per phase boundary (ONE asm statement
-// with its own lgkmcnt(0), MI355X guide, In-kernel stamps), summed per phase and
-// written by wave 0 of the first 1024 workgroups into the (otherwise unused)
-// split scratch; cuking_timing_collect prints the averages.  The stamps cost
-// ~40 cycles each.
-#ifdef CUKING_MFMA_STAMPS
-#define CUKING_STAMP(K)                                                        \
-  {                                                                            \
-    unsigned long long now_;                                                   \
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(now_)::"memory"); \
-    stamp_sum[(K) + stamp_row] += now_ - stamp_last;                           \
-    stamp_last = now_;                                                         \
-  }
-#define CUKING_STAMP_ROW(SYNC) stamp_row = (SYNC) ? 6 : 0;
-#define CUKING_STAMP_SLICE(C) stamp_row = 4 * (C);
-#else
-#define CUKING_STAMP(K)
-#define CUKING_STAMP_ROW(SYNC)
-#define CUKING_STAMP_SLICE(C)
-#endif
-
 // Tickets: one per workgroup and pass (the full form makes two).
 __host__ __device__ inline size_t split_counter_bytes(uint32_t wgs) {
   return ((size_t)wgs * 2 * sizeof(uint32_t) + 255) / 256 * 256 + 256;
@@ -259,17 +196,15 @@ __device__ __forceinline__ uint32_t split_owner(uint64_t u, uint64_t units,
 // each partial result (exact integers) is parked in a scratch slab, and the
 // workgroup that delivers a tile's last part adds the others to its own and
 // runs the epilogue.
-// ABLATE (tuning builds, wrong results): 1 = no LDS-DMA, 2 = no barrier either,
-// 3 = epilogue reduced to one store per lane (prices the kinship/threshold pass).
 // N4 = the four-product form on the nibble layout (below, "Four products").
-template <bool FULL, bool SPLIT, int ABLATE = 0, bool N4 = false>
+template <bool FULL, bool SPLIT, bool N4 = false>
 __global__ __launch_bounds__(256, 1) void king_mfma_kernel(const TiledArgs a) {
   // Five-product form: the lean form has 10 LDS stages and ONE stage barrier per
   // two k-steps (below); the full form parks its fifth sum in the LDS behind the
   // stages and keeps 6 stages with a barrier per k-step.  Four-product form:
   // 5 stages of 32 KiB, every sum in registers.
-  constexpr bool PAIRED = !N4 && !FULL && kPairedSync;
-  constexpr int NSTAGE = N4 ? kMfmaN4Stages : PAIRED ? kStagesPaired : kStages;
+  constexpr bool PAIRED = !N4 && !FULL;
+  constexpr int NSTAGE = N4 ? kMfmaN4Stages : PAIRED ? kStagesPaired : kMfmaStages;
   constexpr int NSUM = FULL ? 5 : 4; // sums per pair
   // ... of which the main loop keeps NQ = 4 in its accumulators (five products:
   // opp, bh, hi, hj; four products: hi / 2, hj / 2, dd, 4 q).  The full form's
@@ -312,10 +247,7 @@ __global__ __launch_bounds__(256, 1) void king_mfma_kernel(const TiledArgs a) {
     // xcd_chunk == 1: patches of 32 consecutive tiles dealt round-robin to the
     // XCDs (XCD x takes patches x, x + 8, ...); otherwise one contiguous chunk
     // of xcd_chunk tiles per XCD.
-#ifndef CUKING_XCD_XOR
-#define CUKING_XCD_XOR 0  // (experiment: which patches an XCD takes, archive/profiles/r02_tail.txt)
-#endif
-    bid = a.xcd_chunk == 1 ? (((j >> 5) * 8 + (x ^ CUKING_XCD_XOR)) << 5) + (j & 31)
+    bid = a.xcd_chunk == 1 ? (((j >> 5) * 8 + x) << 5) + (j & 31)
                            : x * a.xcd_chunk + j;
     if (bid >= a.launch_tiles) return;  // padding (uniform)
   }
@@ -362,8 +294,6 @@ __global__ __launch_bounds__(256, 1) void king_mfma_kernel(const TiledArgs a) {
   // SPLIT launches: the first split_whole workgroups take one whole tile each,
   // the remaining split_wgs ones cut the units of the last split_tiles tiles
   // into equal pieces (piece index `piece`).
-  CUKING_TL(0)
-  [[maybe_unused]] uint32_t tl_seg = 0;  // (timeline build) segment of this workgroup
   const uint64_t units = (uint64_t)a.split_tiles * tile_steps;      // of the cut-up tiles
   const uint64_t whole_units = SPLIT ? (uint64_t)a.split_whole * tile_steps : 0;
   const bool whole_wg = !SPLIT || blockIdx.x < a.split_whole;
@@ -372,16 +302,6 @@ __global__ __launch_bounds__(256, 1) void king_mfma_kernel(const TiledArgs a) {
                               : whole_units + split_bound(piece, units, a.split_wgs);
   uint64_t unit_hi = whole_wg ? unit_lo + tile_steps
                               : whole_units + split_bound(piece + 1, units, a.split_wgs);
-#ifdef CUKING_TUNING
-  // experiment (split_wgs with the top bit set): persistent workgroups, whole
-  // tiles blockIdx.x, blockIdx.x + grid, ... of the launch's split_tiles.
-  const bool strided = SPLIT && (a.split_wgs & 0x80000000u) != 0;
-  uint64_t next_tile = blockIdx.x;
-  if (strided) unit_lo = unit_hi = 0;
-#else
-  constexpr bool strided = false;
-  uint64_t next_tile = 0;
-#endif
   while (true) {
   if (listed && unit_lo >= unit_hi) {
     bid += gridDim.x;
@@ -390,12 +310,7 @@ __global__ __launch_bounds__(256, 1) void king_mfma_kernel(const TiledArgs a) {
     unit_lo = (uint64_t)bid * tile_steps;
     unit_hi = unit_lo + tile_steps;
   }
-  if (unit_lo >= unit_hi) {
-    if (!strided || next_tile >= a.split_tiles) break;
-    unit_lo = next_tile * tile_steps;
-    unit_hi = unit_lo + tile_steps;
-    next_tile += gridDim.x;
-  }
+  if (unit_lo >= unit_hi) break;
   // Everything about the piece is wave-uniform; the 64-bit divisions behind it
   // are computed in vector registers, so pin the results to SGPRs (the SPLIT
   // instantiation otherwise runs out of VGPRs in the main loop and spills).
@@ -419,7 +334,6 @@ __global__ __launch_bounds__(256, 1) void king_mfma_kernel(const TiledArgs a) {
   tr = __builtin_amdgcn_readfirstlane(tr);
   tc = __builtin_amdgcn_readfirstlane(tc);
 
-  CUKING_TL(1 + 5 * tl_seg)
   const uint4 *g_rows = a.planes + (uint64_t)tr * kTile;
   const uint4 *g_cols = a.planes + a.geo.col_base + (uint64_t)tc * kTile;
 
@@ -457,7 +371,6 @@ __global__ __launch_bounds__(256, 1) void king_mfma_kernel(const TiledArgs a) {
   // Inline asm keeps it out of the compiler's wait-count bookkeeping
   // (king_kernels.hip).
   auto issue_piece = [&](const PieceAddr &pa, int r) {
-    if (ABLATE == 1 || ABLATE == 2) return;
     if (r & 1)
       asm volatile(
           "s_mov_b32 m0, %0\n\t"
@@ -480,12 +393,11 @@ __global__ __launch_bounds__(256, 1) void king_mfma_kernel(const TiledArgs a) {
 #pragma unroll
     for (int r = 0; r < kPiecesPerWave; ++r) issue_piece(pa, r);
   };
-  // All but the kStages - 2 youngest stages requested so far have landed, for
+  // All but the NSTAGE - 2 youngest stages requested so far have landed, for
   // this wavefront (counted wait) and, after the barrier, for all of them;
   // every wavefront is also done reading the buffer the next request
   // overwrites.
   auto stage_sync = [&]() {
-    if (ABLATE == 2) return;
     // unpaired: the NSTAGE - 2 younger stages; paired: NSTAGE - 4 (see below)
     constexpr int younger = (PAIRED ? NSTAGE - 4 : NSTAGE - 2) * kPiecesPerWave;
     static_assert(younger < 64, "vmcnt is a 6-bit counter");
@@ -711,72 +623,22 @@ __global__ __launch_bounds__(256, 1) void king_mfma_kernel(const TiledArgs a) {
     // reload whose first use is inside the loop would put the compiler's
     // s_waitcnt vmcnt(0) there, draining the DMA pipeline in every iteration.
     asm volatile("" : "+v"(row_off), "+v"(col_off), "+v"(lane16));
-#ifdef CUKING_MFMA_STAMPS
-    // rows: k-steps without / with a stage hand-over
-    unsigned long long stamp_sum[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, stamp_last;
-    [[maybe_unused]] int stamp_row = 0;
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(stamp_last)::"memory");
-#endif
-    // Where a k-step's LDS reads of the NEXT k-step go (archive/experiments/exp14.sh, one box,
-    // archive/profiles/r02_mfma_stamps.txt): 0 = all eight in front of phase f = 3 (round
-    // 1), 1 = in front of phase f = 2, 2 = phase f = 2, one behind each of its
-    // first eight MFMAs (default), 3 = one per two MFMAs.
-#ifndef CUKING_RD_MODE
-#define CUKING_RD_MODE 2
-#endif
-#if CUKING_RD_MODE == 0
-    // f = 2 multiplies, f = 3 is built from the shifted words
-#define CUKING_PHASE_F2(SYNC)                                                  \
-      CUKING_EXPAND(Y, As, Bs, m1)                                             \
-      CUKING_MMA16(2, X)                                                       \
-      CUKING_MMA4(2, X)                                                        \
-      CUKING_PACE(16, 4) CUKING_PACE(4, 0)                                     \
-      __builtin_amdgcn_sched_barrier(0);
-    // f = 3 multiplies; next k-step: hand-over, LDS reads, f = 0
-#define CUKING_PHASE_F3(SYNC)                                                  \
-      if (SYNC) stage_sync();                                                  \
-      CUKING_STAMP(4)                                                          \
-      CUKING_LOAD_RAW(nbuf)                                                    \
-      CUKING_EXPAND(X, A, B, m1)                                               \
-      CUKING_MMA16(3, Y)                                                       \
-      CUKING_MMA4(3, Y)                                                        \
-      __builtin_amdgcn_sched_group_barrier(0x100, 8, 0);                       \
-      CUKING_PACE(4, 0) CUKING_PACE(16, 4)                                     \
-      __builtin_amdgcn_sched_barrier(0);
-#else
     // The raw words are dead after f = 1 (f = 2 and f = 3 read the shifted
-    // copies): hand-over and LDS reads of the next k-step in phase f = 2.
-#if CUKING_RD_MODE == 1
-#define CUKING_RD_PACE                                                         \
-      __builtin_amdgcn_sched_group_barrier(0x100, 8, 0);                       \
-      CUKING_PACE(16, 4) CUKING_PACE(4, 0)
-#elif CUKING_RD_MODE == 2
-#define CUKING_RD_PACE                                                         \
-      _Pragma("unroll") for (int i_ = 0; i_ < 8; ++i_) {                       \
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                     \
-        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);                     \
-        __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);                     \
-      }                                                                        \
-      CUKING_PACE(8, 4) CUKING_PACE(4, 0)
-#else
-#define CUKING_RD_PACE                                                         \
-      _Pragma("unroll") for (int i_ = 0; i_ < 8; ++i_) {                       \
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                     \
-        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);                     \
-        __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);                     \
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                     \
-        __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);                     \
-      }                                                                        \
-      CUKING_PACE(4, 0)
-#endif
+    // copies): hand-over and LDS reads of the next k-step in phase f = 2, one
+    // read behind each of its first eight MFMAs: configs[2] 594.5 ms; one per two
+    // MFMAs 600.1, all in front of the phase 608.8 (archive/profiles/r02_mfma_stamps.txt).
 #define CUKING_PHASE_F2(SYNC)                                                  \
       if (SYNC) stage_sync();                                                  \
-      CUKING_STAMP(4)                                                          \
       CUKING_LOAD_RAW(nbuf)                                                    \
       CUKING_EXPAND(Y, As, Bs, m1)                                             \
       CUKING_MMA16(2, X)                                                       \
       CUKING_MMA4(2, X)                                                        \
-      CUKING_RD_PACE                                                           \
+      _Pragma("unroll") for (int i_ = 0; i_ < 8; ++i_) {                       \
+        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                     \
+        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);                     \
+        __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);                     \
+      }                                                                        \
+      CUKING_PACE(8, 4) CUKING_PACE(4, 0)                                      \
       __builtin_amdgcn_sched_barrier(0);
 #define CUKING_PHASE_F3(SYNC)                                                  \
       CUKING_EXPAND(X, A, B, m1)                                               \
@@ -784,7 +646,6 @@ __global__ __launch_bounds__(256, 1) void king_mfma_kernel(const TiledArgs a) {
       CUKING_MMA4(3, Y)                                                        \
       CUKING_PACE(4, 0) CUKING_PACE(16, 4)                                     \
       __builtin_amdgcn_sched_barrier(0);
-#endif
     // One k-step.  Its four requests go to the addresses the k-step before it
     // worked out (`pa`); in phase f = 3, where the MFMA gaps have room for scalar
     // instructions, it works out those of the NEXT k-step, which requests stage
@@ -794,20 +655,17 @@ __global__ __launch_bounds__(256, 1) void king_mfma_kernel(const TiledArgs a) {
     {                                                                          \
       const uint32_t nbuf = buf == NSTAGE - 1 ? 0 : buf + 1;                   \
       const PieceAddr pa_ = pa;                                                \
-      CUKING_STAMP_ROW(SYNC)                                                   \
       /* f = 0 multiplies, f = 1 is built */                                   \
       CUKING_EXPAND(Y, A, B, m2)                                               \
       CUKING_MMA16(0, X)                                                       \
       CUKING_PACE(16, 4)                                                       \
       __builtin_amdgcn_sched_barrier(0);                                       \
-      CUKING_STAMP(0)                                                          \
       _Pragma("unroll") for (int r = 0; r < 4; ++r) {                          \
         issue_piece(pa_, r);                                                   \
         acc[r >> 1][r & 1][0] =                                                \
             mma<0>(Xa[r >> 1][1], Xb[r & 1][0], acc[r >> 1][r & 1][0]);        \
         __builtin_amdgcn_sched_barrier(0);                                     \
       }                                                                        \
-      CUKING_STAMP(1)                                                          \
       /* f = 1 multiplies (unscaled), f = 2 and the shifted words are built */ \
       CUKING_EXPAND(X, A, B, m4)                                               \
       _Pragma("unroll") for (int b = 0; b < 2; ++b)                            \
@@ -819,16 +677,12 @@ __global__ __launch_bounds__(256, 1) void king_mfma_kernel(const TiledArgs a) {
       CUKING_MMA4(1, Y)                                                        \
       CUKING_PACE(20, 5)                                                       \
       __builtin_amdgcn_sched_barrier(0);                                       \
-      CUKING_STAMP(2)                                                          \
       CUKING_PHASE_F2(SYNC)                                                    \
-      CUKING_STAMP(3)                                                          \
       pa = piece_addr((STEP) + 1 + (NAHEAD),                                   \
                       nbuf >= (NBACK) ? nbuf - (NBACK) : nbuf + NSTAGE - (NBACK)); \
       CUKING_PHASE_F3(SYNC)                                                    \
-      CUKING_STAMP(5)                                                          \
       buf = nbuf;                                                              \
     }
-    CUKING_TL(2 + 5 * tl_seg)
     // (the first k-step requests stage NSTAGE - 1 into the buffer behind its own)
     PieceAddr pa = piece_addr(NSTAGE - 1, buf >= 1 ? buf - 1 : buf + NSTAGE - 1);
     if constexpr (PAIRED) {
@@ -847,16 +701,6 @@ __global__ __launch_bounds__(256, 1) void king_mfma_kernel(const TiledArgs a) {
 #undef CUKING_KSTEP
 #undef CUKING_PHASE_F2
 #undef CUKING_PHASE_F3
-#ifdef CUKING_MFMA_STAMPS
-    if (!SPLIT && a.split_scratch != nullptr && blockIdx.x < 1024 && threadIdx.x == 0) {
-      unsigned long long *dbg =
-          reinterpret_cast<unsigned long long *>(a.split_scratch) + (size_t)blockIdx.x * 16;
-      for (int k = 0; k < 6; ++k) dbg[k] = stamp_sum[k];
-      for (int k = 0; k < 6; ++k) dbg[8 + k] = stamp_sum[6 + k];
-      dbg[6] = num_steps - 1;
-      dbg[7] = 0x5354414D50ull;  // "STAMP"
-    }
-#endif
     // last k-step: nothing left to fetch
     CUKING_EXPAND(Y, A, B, m2)
     CUKING_MMA16(0, X)
@@ -935,9 +779,6 @@ __global__ __launch_bounds__(256, 1) void king_mfma_kernel(const TiledArgs a) {
     // (65 cycles of a k-step in the stamps, profiles/r03_stamps_n4.txt).
     const uint32_t kstep_bytes = 8 * s_stride * 16;  // (< 2^32: 128 B x stored samples)
     auto n4_next = [&](const N4Addr &cur, uint32_t step, uint32_t buf) {
-#ifdef CUKING_N4_ADDR_MUL  // (A/B)
-      return n4_addr(step, buf);
-#endif
       N4Addr pa;
       const uint32_t adv = step < num_steps ? kstep_bytes : 0u;
       pa.src = reinterpret_cast<const uint4 *>(reinterpret_cast<const char *>(cur.src) + adv);
@@ -946,7 +787,6 @@ __global__ __launch_bounds__(256, 1) void king_mfma_kernel(const TiledArgs a) {
       return pa;
     };
     auto n4_issue = [&](const N4Addr &pa, int c, int half) {
-      if (ABLATE == 1 || ABLATE == 2) return;
       const uint4 *src = pa.src + (uint64_t)c * s_stride;
       const uint32_t dst = pa.dst + c * (kSliceU4 * 16);
       if (half)
@@ -971,7 +811,6 @@ __global__ __launch_bounds__(256, 1) void king_mfma_kernel(const TiledArgs a) {
     // stages s + 1 .. s + 3 and the 4 requests of stage s + 4 that slices 0 and 1
     // have issued; stage s + 1 has landed when all but the 20 youngest have.
     auto n4_sync = [&]() {
-      if (ABLATE == 2) return;
       __builtin_amdgcn_s_waitcnt(vmcnt_imm(2 * 8 + 4));
       __syncthreads();
     };
@@ -983,10 +822,8 @@ __global__ __launch_bounds__(256, 1) void king_mfma_kernel(const TiledArgs a) {
 #pragma unroll
         for (int r = 0; r < 8; ++r) n4_issue(pa0, r >> 1, r & 1);
       }
-      if (ABLATE != 2) {
-        __builtin_amdgcn_s_waitcnt(vmcnt_imm(3 * 8));
-        __syncthreads();
-      }
+      __builtin_amdgcn_s_waitcnt(vmcnt_imm(3 * 8));
+      __syncthreads();
     };
 
     // This lane's operand rows inside a stage (uint4 units): rows / columns.
@@ -1069,7 +906,6 @@ __global__ __launch_bounds__(256, 1) void king_mfma_kernel(const TiledArgs a) {
 // go out; SYNC: stage hand-over in front of the reads.
 #define N4_SLICE(CUR, NXT, RBUF, RSLICE, SYNC, C)                              \
     {                                                                          \
-      CUKING_STAMP_SLICE(C)                                                    \
       /* hi = H_i.D_j; T of this slice from its own raw words */               \
       N4_PIN_RAW_A(CUR) N4_PIN_RAW_B(CUR)                                      \
       N4_BUILD_A(2, CUR, mT) N4_BUILD_B(2, CUR, mT)                            \
@@ -1077,20 +913,16 @@ __global__ __launch_bounds__(256, 1) void king_mfma_kernel(const TiledArgs a) {
       /* (last slice: the next k-step's request addresses -- a dependent chain  \
          of ~10 scalar instructions -- among this group's MFMAs, not behind the \
          k-step where nothing covers them) */                                  \
-      if ((C) == 3 && !CUKING_N4_ADDR_LATE) pa_next = n4_next(pa, step + NSTAGE, buf); \
+      if ((C) == 3) pa_next = n4_next(pa, step + NSTAGE, buf);                 \
       CUKING_PACE(4, 4)                                                        \
       N4_PIN_A(2) N4_PIN_B(2)                                                  \
       __builtin_amdgcn_sched_barrier(0);                                       \
-      CUKING_STAMP(0)                                                          \
       /* hj = D_i.H_j */                                                       \
       N4_READ_GROUP(1, 1, 0, CUR, NXT, RBUF, RSLICE, SYNC)                     \
-      CUKING_STAMP(1)                                                          \
       /* dd = D_i.D_j */                                                       \
       N4_DMA_GROUP(2, 1, NXT, C)                                               \
-      CUKING_STAMP(2)                                                          \
       /* q = T_i.T_j */                                                        \
       N4_LAST_GROUP(3, 2, 2, NXT)                                              \
-      CUKING_STAMP(3)                                                          \
     }
     zero_acc();
     if constexpr (HH5) {
@@ -1116,22 +948,9 @@ __global__ __launch_bounds__(256, 1) void king_mfma_kernel(const TiledArgs a) {
     // k-step s requests stage s + NSTAGE - 1 into the buffer stage s - 1 left
     // (all its reads were issued before the hand-over of k-step s - 1)
     N4Addr pa = n4_addr(NSTAGE - 1, NSTAGE - 1);
-    CUKING_TL(2 + 5 * tl_seg)
-#ifdef CUKING_MFMA_STAMPS
-    // groups hi | hj + reads (+ hand-over in slice 2) | dd + requests | q of each of
-    // the four slices of a k-step
-    unsigned long long stamp_sum[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, stamp_last;
-    [[maybe_unused]] int stamp_row = 0;
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(stamp_last)::"memory");
-#endif
     // One k-step; four per loop trip (the trip's back edge and counter updates cost
-    // ~100 cycles with nothing to cover them: stamps, profiles/r03_stamps_n4.txt).
-#ifndef CUKING_N4_KSTEPS_PER_TRIP
-#define CUKING_N4_KSTEPS_PER_TRIP 4  // (A/B: 1, 2: configs[2] 540 -> 529 -> 526 ms)
-#endif
-#ifndef CUKING_N4_ADDR_LATE
-#define CUKING_N4_ADDR_LATE 0        // (A/B: 1 = next k-step's addresses behind the k-step)
-#endif
+    // ~100 cycles with nothing to cover them: stamps, profiles/r03_stamps_n4.txt;
+    // 1, 2, 4 k-steps per trip: configs[2] 540 -> 529 -> 526 ms).
 #define N4_KSTEP                                                               \
     {                                                                          \
       const uint32_t nbuf = buf == NSTAGE - 1 ? 0 : buf + 1;                   \
@@ -1140,13 +959,11 @@ __global__ __launch_bounds__(256, 1) void king_mfma_kernel(const TiledArgs a) {
       N4_SLICE(1, 0, buf, 3, false, 1)                                         \
       N4_SLICE(0, 1, nbuf, 0, true, 2)                                         \
       N4_SLICE(1, 0, nbuf, 1, false, 3)                                        \
-      if (CUKING_N4_ADDR_LATE) pa_next = n4_next(pa, step + NSTAGE, buf);      \
       pa = pa_next;                                                            \
       buf = nbuf;                                                              \
       ++step;                                                                  \
     }
     uint32_t step = 0;
-#if CUKING_N4_KSTEPS_PER_TRIP == 4
     while (step + 3 < num_steps) {
       N4_KSTEP
       N4_KSTEP
@@ -1154,27 +971,7 @@ __global__ __launch_bounds__(256, 1) void king_mfma_kernel(const TiledArgs a) {
       N4_KSTEP
     }
     while (step < num_steps) N4_KSTEP
-#elif CUKING_N4_KSTEPS_PER_TRIP == 2
-    while (step + 1 < num_steps) {
-      N4_KSTEP
-      N4_KSTEP
-    }
-    if (step < num_steps) N4_KSTEP
-#else
-    while (step < num_steps) N4_KSTEP
-#endif
 #undef N4_KSTEP
-#ifdef CUKING_MFMA_STAMPS
-    if (!SPLIT && a.split_scratch != nullptr && blockIdx.x < 1024 && threadIdx.x == 0) {
-      // (32 words per workgroup; word 7 stays clear of the five-product loop's mark)
-      unsigned long long *dbg =
-          reinterpret_cast<unsigned long long *>(a.split_scratch) + (size_t)blockIdx.x * 32;
-      for (int k = 0; k < 16; ++k) dbg[k < 7 ? k : k + 1] = stamp_sum[k];
-      dbg[7] = 0;
-      dbg[24] = num_steps;
-      dbg[25] = 0x5354414D5034ull;  // "STAMP4"
-    }
-#endif
 #undef N4_READ
 #undef N4_PIN4
 #undef N4_PINF
@@ -1194,7 +991,6 @@ __global__ __launch_bounds__(256, 1) void king_mfma_kernel(const TiledArgs a) {
   // workgroup's LDS goes away.
   __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
   if (SPLIT) __syncthreads();  // ... and nobody reads the stages any more
-  CUKING_TL(3 + 5 * tl_seg)
 
   // Full form: the fifth sum stays where the pass in front of the main loop
   // parked it (this lane's 16-byte slots) and is read block by block.
@@ -1285,11 +1081,7 @@ __global__ __launch_bounds__(256, 1) void king_mfma_kernel(const TiledArgs a) {
     __syncthreads();
     const bool last = *flag != 0;
     __syncthreads();  // the flag word is stage memory again after this
-    if (!last) {
-      CUKING_TL(4 + 5 * tl_seg)
-      tl_seg = 1;
-      continue;
-    }
+    if (!last) continue;
     // Totals: this part is still in registers, the others come from their slabs.
     for (uint32_t w = w_first; w <= w_last; ++w) {
       if (w == piece) continue;
@@ -1324,22 +1116,6 @@ __global__ __launch_bounds__(256, 1) void king_mfma_kernel(const TiledArgs a) {
     }
   }
 
-  CUKING_TL(4 + 5 * tl_seg)
-  if (ABLATE == 3) {
-    float sum = 0.f;
-#pragma unroll
-    for (int bi = 0; bi < BI; ++bi)
-#pragma unroll
-      for (int bj = 0; bj < 2; ++bj)
-#pragma unroll
-        for (int q = 0; q < NQ; ++q)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) sum += acc[bi][bj][q][r];
-    if (PARKED) sum += park[0].x;
-    if (HH5) sum += hh5[0][0][0];
-    if (sum == -1.f) a.results[0].kin = sum;  // never true, keeps the sums alive
-    continue;
-  }
   // --- epilogue: kinship, threshold, append (cuking.cu:284-313).  C layout of
   // the 32 x 32 MFMA: column = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5).
   const auto emit_ctx = [&]() {
@@ -1463,9 +1239,8 @@ __global__ __launch_bounds__(256, 1) void king_mfma_kernel(const TiledArgs a) {
           // the recount of hom_hom (king_device.h).
           const float f_hi = 2.f * acc[bi][bj][0][r], f_hj = 2.f * acc[bi][bj][1][r];
           const float f_num = f_hi + f_hj - 2.f * acc[bi][bj][2][r] + 0.5f * acc[bi][bj][3][r];
-          const bool maybe = !CUKING_MFMA_PREFILTER ||
-                             (valid && kinship_may_pass_num(f_num, fminf(f_hi, f_hj),
-                                                            a.kin_threshold));
+          const bool maybe =
+              valid && kinship_may_pass_num(f_num, fminf(f_hi, f_hj), a.kin_threshold);
           if (__ballot(maybe) != 0)
             lean_epilogue_call_n4(emit_ctx, valid, li, lj, (uint32_t)f_hi, (uint32_t)f_hj,
                                   (uint32_t)acc[bi][bj][2][r],
@@ -1475,10 +1250,8 @@ __global__ __launch_bounds__(256, 1) void king_mfma_kernel(const TiledArgs a) {
           // sums without the IEEE divide, and only when some lane of the
           // wavefront may pass run the exact epilogue (wave-uniform branch).
           const bool maybe =
-              !CUKING_MFMA_PREFILTER ||
-              (valid && kinship_may_pass(acc[bi][bj][2][r], acc[bi][bj][3][r],
-                                        acc[bi][bj][1][r], acc[bi][bj][0][r],
-                                        a.kin_threshold));
+              valid && kinship_may_pass(acc[bi][bj][2][r], acc[bi][bj][3][r],
+                                        acc[bi][bj][1][r], acc[bi][bj][0][r], a.kin_threshold);
           if (__ballot(maybe) != 0)
             lean_epilogue_call(emit_ctx, valid, li, lj, (uint32_t)acc[bi][bj][2][r],
                                (uint32_t)acc[bi][bj][3][r], (uint32_t)acc[bi][bj][1][r],
@@ -1489,20 +1262,17 @@ __global__ __launch_bounds__(256, 1) void king_mfma_kernel(const TiledArgs a) {
   }
   }
   if (SPLIT) __syncthreads();  // LDS is reused by the next piece
-  CUKING_TL(5 + 5 * tl_seg)
-  tl_seg = 1;
   }  // pieces of this workgroup
-  CUKING_TL(11)
 }
 
-template <bool FULL, bool SPLIT, int ABLATE = 0, bool N4 = false>
+template <bool FULL, bool SPLIT, bool N4 = false>
 hipError_t launch_shape(const TiledArgs &args, uint64_t num_blocks,
                         uint32_t lds_bytes, hipStream_t stream) {
-  auto kernel = king_mfma_kernel<FULL, SPLIT, ABLATE, N4>;
+  auto kernel = king_mfma_kernel<FULL, SPLIT, N4>;
   // (five products: the caller's figure is the 6-stage one of the variant table)
   if (N4) lds_bytes = kMfmaN4LdsBytes;
   else if (FULL) lds_bytes += kMfmaParkBytes;  // the parked fifth sum, behind the stages
-  else if (kPairedSync) lds_bytes = kStagesPaired * kStageU4 * sizeof(uint4);
+  else lds_bytes = kStagesPaired * kStageU4 * sizeof(uint4);
   static DeviceOnce attr_set;  // per device, see king_device.h
   if (!attr_set.done()) {
     hipError_t e = hipFuncSetAttribute(
@@ -1517,17 +1287,9 @@ hipError_t launch_shape(const TiledArgs &args, uint64_t num_blocks,
     a.launch_tiles = args.split_whole;
     // the pieces are taken from the counter as well (an XCD that finishes its
     // whole tiles early takes more of them): half as many workgroups again
-    if ((args.split_wgs & 0x80000000u) == 0) {
-      a.dyn_tiles = args.split_wgs;
-      a.dyn_wgs = args.split_wgs + args.split_wgs / 2;
-      num_blocks = (uint64_t)args.split_whole + a.dyn_wgs;
-    } else {
-      a.dyn_tiles = a.dyn_wgs = 0;  // (tuning builds: persistent workgroups)
-    }
-#ifdef CUKING_MFMA_TIMELINE
-    (void)hipStreamSynchronize(stream);
-    timeline_arm(args.split_whole, (uint32_t)num_blocks);
-#endif
+    a.dyn_tiles = args.split_wgs;
+    a.dyn_wgs = args.split_wgs + args.split_wgs / 2;
+    num_blocks = (uint64_t)args.split_whole + a.dyn_wgs;
     kernel<<<dim3((uint32_t)num_blocks), dim3(256), lds_bytes, stream>>>(a);
     return hipGetLastError();
   }
@@ -1576,10 +1338,6 @@ hipError_t launch_shape(const TiledArgs &args, uint64_t num_blocks,
     } else {
       a.xcd_chunk = 0;
     }
-#ifdef CUKING_MFMA_TIMELINE
-    (void)hipStreamSynchronize(stream);
-    timeline_arm((uint32_t)grid, (uint32_t)grid);
-#endif
     kernel<<<dim3((uint32_t)grid), dim3(256), lds_bytes, stream>>>(a);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
@@ -1590,125 +1348,6 @@ hipError_t launch_shape(const TiledArgs &args, uint64_t num_blocks,
 
 }  // namespace
 
-#ifdef CUKING_MFMA_TIMELINE
-static unsigned long long *g_timeline_host = nullptr;
-static uint32_t g_timeline_whole = 0, g_timeline_blocks = 0;
-namespace {
-void timeline_arm(uint32_t whole, uint32_t blocks) {
-  if (g_timeline_host == nullptr) {
-    if (hipMalloc(&g_timeline_host, (size_t)kTimelineBlocks * 12 * 8) != hipSuccess) return;
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(g_timeline), &g_timeline_host, sizeof(g_timeline_host));
-  }
-  (void)hipMemset(g_timeline_host, 0, (size_t)kTimelineBlocks * 12 * 8);
-  g_timeline_whole = whole;
-  g_timeline_blocks = blocks < kTimelineBlocks ? blocks : kTimelineBlocks;
-}
-}  // namespace
-void mfma_timeline_dump() {
-  if (g_timeline_host == nullptr || g_timeline_blocks == 0) return;
-  std::vector<unsigned long long> h((size_t)g_timeline_blocks * 12);
-  if (hipMemcpy(h.data(), g_timeline_host, h.size() * 8, hipMemcpyDeviceToHost) != hipSuccess)
-    return;
-  unsigned long long t0 = ~0ull;
-  for (uint32_t b = 0; b < g_timeline_blocks; ++b)
-    if (h[b * 12] != 0 && h[b * 12] < t0) t0 = h[b * 12];
-  auto us = [&](unsigned long long t) { return t == 0 ? -1.0 : (double)(t - t0) / 100.0; };
-  double whole_end_max = 0, whole_end_min = 1e30, whole_dur = 0;
-  uint32_t nw = 0;
-  for (uint32_t b = 0; b < g_timeline_whole && b < g_timeline_blocks; ++b) {
-    if (h[b * 12 + 11] == 0 || h[b * 12 + 1] == 0) continue;
-    const double e = us(h[b * 12 + 11]);
-    whole_end_max = e > whole_end_max ? e : whole_end_max;
-    whole_dur += e - us(h[b * 12]);
-    ++nw;
-  }
-  // the last 256 whole tiles to finish
-  std::vector<double> ends;
-  for (uint32_t b = 0; b < g_timeline_whole && b < g_timeline_blocks; ++b)
-    if (h[b * 12 + 11] != 0 && h[b * 12 + 1] != 0) ends.push_back(us(h[b * 12 + 11]));
-  std::sort(ends.begin(), ends.end());
-  if (ends.size() >= 256) whole_end_min = ends[ends.size() - 256];
-  fprintf(stderr, "timeline: %u whole tiles, mean %.1f us each; the last 256 end %.1f .. %.1f us\n",
-          nw, nw ? whole_dur / nw : 0.0, whole_end_min, whole_end_max);
-  {  // per XCD (workgroup b runs on XCD b % 8): tiles, mean tile time, last exit
-    double dur[8] = {}, last[8] = {};
-    uint32_t cnt[8] = {};
-    for (uint32_t b = 0; b < g_timeline_whole && b < g_timeline_blocks; ++b) {
-      if (h[b * 12 + 11] == 0 || h[b * 12 + 1] == 0) continue;
-      const double e = us(h[b * 12 + 11]);
-      dur[b & 7] += e - us(h[b * 12]);
-      ++cnt[b & 7];
-      last[b & 7] = e > last[b & 7] ? e : last[b & 7];
-    }
-    for (int x = 0; x < 8; ++x)
-      fprintf(stderr, "timeline: XCD %d: %u tiles, mean %.1f us, last exit %.1f us\n", x, cnt[x],
-              cnt[x] ? dur[x] / cnt[x] : 0.0, last[x]);
-  }
-  double st_min = 1e30, st_max = 0, en_min = 1e30, en_max = 0;
-  double seg[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
-  uint32_t nseg[2] = {0, 0}, np = 0;
-  for (uint32_t b = g_timeline_whole; b < g_timeline_blocks; ++b) {
-    if (h[b * 12] == 0) continue;
-    const double st = us(h[b * 12]), en = us(h[b * 12 + 11]);
-    st_min = st < st_min ? st : st_min; st_max = st > st_max ? st : st_max;
-    en_min = en < en_min ? en : en_min; en_max = en > en_max ? en : en_max;
-    ++np;
-    for (int sgm = 0; sgm < 2; ++sgm) {
-      const unsigned long long *q = &h[b * 12 + 1 + 5 * sgm];
-      if (q[0] == 0 || q[2] == 0) continue;
-      ++nseg[sgm];
-      seg[sgm][0] += us(q[1]) - us(q[0]);
-      seg[sgm][1] += us(q[2]) - us(q[1]);
-      if (q[3] != 0) seg[sgm][2] += us(q[3]) - us(q[2]);
-      if (q[4] != 0 && q[3] != 0) seg[sgm][3] += us(q[4]) - us(q[3]);
-    }
-  }
-  if (np != 0) {
-    fprintf(stderr, "timeline: %u pieces start %.1f .. %.1f us, end %.1f .. %.1f us\n", np, st_min,
-            st_max, en_min, en_max);
-    for (int sgm = 0; sgm < 2; ++sgm)
-      if (nseg[sgm])
-        fprintf(stderr,
-                "timeline: segment %d of a piece (%u): fill %.1f | loop %.1f | slab+ticket/totals %.1f "
-                "| epilogue %.1f us (sums over pieces / pieces with the segment)\n",
-                sgm, nseg[sgm], seg[sgm][0] / nseg[sgm], seg[sgm][1] / nseg[sgm],
-                seg[sgm][2] / nseg[sgm], seg[sgm][3] / nseg[sgm]);
-  }
-  // start of every 16th piece (dispatch order) and the sorted starts
-  {
-    std::vector<double> st;
-    fprintf(stderr, "timeline: piece starts by index (every 16th):");
-    for (uint32_t b = g_timeline_whole; b < g_timeline_blocks; ++b) {
-      if (h[b * 12] == 0) continue;
-      st.push_back(us(h[b * 12]));
-      if ((b - g_timeline_whole) % 16 == 0) fprintf(stderr, " %.0f", us(h[b * 12]));
-    }
-    std::sort(st.begin(), st.end());
-    fprintf(stderr, "\ntimeline: piece starts sorted (every 16th):");
-    for (size_t k = 0; k < st.size(); k += 16) fprintf(stderr, " %.0f", st[k]);
-    fprintf(stderr, "\n");
-  }
-  // the pieces that finish last, stamp by stamp
-  std::vector<std::pair<double, uint32_t>> order;
-  for (uint32_t b = g_timeline_whole; b < g_timeline_blocks; ++b)
-    if (h[b * 12] != 0) order.emplace_back(us(h[b * 12 + 11]), b);
-  std::sort(order.begin(), order.end());
-  for (size_t k = order.size() > 6 ? order.size() - 6 : 0; k < order.size(); ++k) {
-    const uint32_t b = order[k].second;
-    fprintf(stderr, "timeline: piece %u:", b - g_timeline_whole);
-    for (int q = 0; q < 12; ++q) fprintf(stderr, " %.1f", us(h[b * 12 + q]));
-    fprintf(stderr, "\n");
-  }
-  for (size_t k = 0; k < 3 && k < order.size(); ++k) {
-    const uint32_t b = order[k].second;
-    fprintf(stderr, "timeline: (early) piece %u:", b - g_timeline_whole);
-    for (int q = 0; q < 12; ++q) fprintf(stderr, " %.1f", us(h[b * 12 + q]));
-    fprintf(stderr, "\n");
-  }
-  g_timeline_blocks = 0;
-}
-#endif
-
 size_t mfma_split_scratch_bytes(uint32_t wgs) {
   // one counter per tile (padded to 16 bytes), then two slabs of five sums per
   // workgroup
@@ -1717,15 +1356,15 @@ size_t mfma_split_scratch_bytes(uint32_t wgs) {
 size_t mfma_split_counter_bytes(uint32_t wgs) { return split_counter_bytes(wgs); }
 
 namespace {
-// launch_shape<FULL, SPLIT, 0, N4> by run-time flags
+// launch_shape<FULL, SPLIT, N4> by run-time flags
 hipError_t launch_form(bool full, bool split, bool nibble, const TiledArgs &a, uint64_t blocks,
                        uint32_t lds_bytes, hipStream_t stream) {
   if (nibble) {
     if (split)
-      return full ? launch_shape<true, true, 0, true>(a, blocks, lds_bytes, stream)
-                  : launch_shape<false, true, 0, true>(a, blocks, lds_bytes, stream);
-    return full ? launch_shape<true, false, 0, true>(a, blocks, lds_bytes, stream)
-                : launch_shape<false, false, 0, true>(a, blocks, lds_bytes, stream);
+      return full ? launch_shape<true, true, true>(a, blocks, lds_bytes, stream)
+                  : launch_shape<false, true, true>(a, blocks, lds_bytes, stream);
+    return full ? launch_shape<true, false, true>(a, blocks, lds_bytes, stream)
+                : launch_shape<false, false, true>(a, blocks, lds_bytes, stream);
   }
   if (split)
     return full ? launch_shape<true, true>(a, blocks, lds_bytes, stream)
@@ -1752,7 +1391,7 @@ hipError_t launch_mfma_list(const TiledArgs &args, uint32_t grid, hipStream_t st
   const uint64_t cap = max_blocks_per_launch(256);
   if (grid > cap) grid = (uint32_t)cap;
   if (grid == 0) return hipErrorInvalidValue;
-  auto kernel = king_mfma_kernel<false, false, 0, true>;
+  auto kernel = king_mfma_kernel<false, false, true>;
   static DeviceOnce attr_set;  // per device, see king_device.h
   if (!attr_set.done()) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel),
@@ -1780,7 +1419,7 @@ hipError_t launch_mfma_gated(const TiledArgs &args, uint64_t num_units, uint32_t
   const uint64_t cap = max_blocks_per_launch(256);  // (ONE launch, see launch_mfma_list)
   if (grid > cap) grid = (uint32_t)cap;
   if (grid == 0) return hipErrorInvalidValue;
-  auto kernel = king_mfma_kernel<false, false, 0, true>;
+  auto kernel = king_mfma_kernel<false, false, true>;
   static DeviceOnce attr_set;  // per device, see king_device.h
   if (!attr_set.done()) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel),
@@ -1797,25 +1436,11 @@ hipError_t launch_mfma(bool full, bool nibble, const TiledArgs &args, uint64_t n
                        uint32_t lds_bytes, hipStream_t stream) {
   if ((uint64_t)args.geo.k_words * 32 > (nibble ? kMfmaN4MaxSites : kMfmaMaxSites))
     return hipErrorInvalidValue;
-#ifdef CUKING_TUNING
-  // Timing-only experiments (wrong results): CUKING_MFMA_ABLATE=1 no LDS-DMA,
-  // =2 no stage barrier either.
-  if (const char *e = getenv("CUKING_MFMA_ABLATE")) {
-    if (nibble) {
-      if (e[0] == '1') return launch_shape<false, false, 1, true>(args, num_tiles, lds_bytes, stream);
-      if (e[0] == '2') return launch_shape<false, false, 2, true>(args, num_tiles, lds_bytes, stream);
-      if (e[0] == '3') return launch_shape<false, false, 3, true>(args, num_tiles, lds_bytes, stream);
-    }
-    if (e[0] == '1') return launch_shape<false, false, 1>(args, num_tiles, lds_bytes, stream);
-    if (e[0] == '2') return launch_shape<false, false, 2>(args, num_tiles, lds_bytes, stream);
-    if (e[0] == '3') return launch_shape<false, false, 3>(args, num_tiles, lds_bytes, stream);
-  }
-#endif
   // Whole rounds of one tile per workgroup, then the remainder (the tiles that
   // would leave most CUs idle for a whole tile time) cut into equal pieces of
   // k-steps over all CUs, in the SAME launch: a CU that finishes its last
   // whole tile goes straight on to a piece.  For launches of fewer than
-  // CUKING_SPLIT_ROUNDS tiles per CU: 36 tiles 0.57 -> 0.25 ms, 300 tiles
+  // kSplitRounds tiles per CU: 36 tiles 0.57 -> 0.25 ms, 300 tiles
   // 1.26 -> 0.91 ms, 820 tiles 2.40 -> 2.15 ms; configs[1] (3160 tiles = 12.3
   // rounds, the dispatcher's back-filling does not hide the 13th: time follows
   // ceil(rounds), archive/experiments/exp15.sh) 6.93 -> 6.75 ms and 7.12 -> 6.84 ms on two
@@ -1823,39 +1448,18 @@ hipError_t launch_mfma(bool full, bool nibble, const TiledArgs &args, uint64_t n
   // pieces end as far apart as the whole tiles before them did (~0.3 ms after
   // 12 rounds), which is what is left of the ideal 0.66 x 0.53 ms
   // (archive/profiles/r02_tail.txt); beyond 64 rounds the gain is under 1 %.
+  constexpr uint64_t kSplitRounds = 64;
   const uint32_t wgs = args.split_wgs;
   const uint32_t tile_steps = args.geo.k_words / 8;
   uint64_t whole = num_tiles;
   uint32_t rest = 0;
-#ifndef CUKING_SPLIT_ROUNDS
-#define CUKING_SPLIT_ROUNDS 64
-#endif
-  if (wgs != 0 && args.split_scratch != nullptr &&
-      num_tiles < (uint64_t)CUKING_SPLIT_ROUNDS * wgs) {
+  if (wgs != 0 && args.split_scratch != nullptr && num_tiles < kSplitRounds * wgs) {
     // under two tiles per CU everything goes out as pieces (300 tiles:
     // 0.98 -> 0.91 ms); otherwise the remainder after whole rounds
     rest = num_tiles < 2ull * wgs ? (uint32_t)num_tiles : (uint32_t)(num_tiles % wgs);
     if ((uint64_t)rest * tile_steps < 8ull * wgs) rest = 0;  // too little work to cut up
     whole = num_tiles - rest;
   }
-#ifdef CUKING_TUNING
-  // experiment: every launch as one persistent stream-k launch (20k samples:
-  // 26.2 -> 29.9 ms, the contiguous tile ranges lose the L2 sharing of the
-  // band order)
-  if (getenv("CUKING_MFMA_SPLIT_ALL") && wgs != 0 && args.split_scratch != nullptr &&
-      num_tiles < 0xFFFFFFFFull && num_tiles * tile_steps >= 8ull * wgs) {
-    rest = (uint32_t)num_tiles;
-    whole = 0;
-  }
-  // experiment: persistent workgroups striding over whole tiles
-  if (getenv("CUKING_MFMA_PERSIST") && wgs != 0 && args.split_scratch != nullptr &&
-      num_tiles < 0x7FFFFFFFull && num_tiles > wgs) {
-    TiledArgs pa = args;
-    pa.split_tiles = (uint32_t)num_tiles;
-    pa.split_wgs = wgs | 0x80000000u;
-    return launch_form(full, true, nibble, pa, wgs, lds_bytes, stream);
-  }
-#endif
   if (getenv("CUKING_AMD_DEBUG"))
     fprintf(stderr, "launch_mfma: tiles %llu whole %llu rest %u wgs %u scratch %p\n",
             (unsigned long long)num_tiles, (unsigned long long)whole, rest, wgs,
