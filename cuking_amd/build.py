@@ -111,9 +111,9 @@ def check_filter_loop(asm_path: Path, verbose: bool = False):
     import re
     text = Path(asm_path).read_text()
     bodies = [m.group(1) for m in re.finditer(
-        r"\n_ZN6cuking12_GLOBAL__N_1\d+king_filter(?:_persistent)?_kernelE\w+:(.*?)\.Lfunc_end", text, re.S)]
-    if len(bodies) < 2:
-        return [f"king_filter_kernel / king_filter_persistent_kernel not both in {asm_path}"]
+        r"\n_ZN6cuking12_GLOBAL__N_1\d+king_filter_kernelE\w+:(.*?)\.Lfunc_end", text, re.S)]
+    if not bodies:
+        return [f"no king_filter_kernel in {asm_path}"]
     problems, seen = [], 0
     for block in (b for body in bodies for b in re.split(r"\n(?=\.LBB\d+_\d+:)", body)):
         lines = block.split("\n")
@@ -135,8 +135,8 @@ def check_filter_loop(asm_path: Path, verbose: bool = False):
                   f"vmcnt waits {waits}")
         if scratch or foreign:
             problems.append(f"king_filter_kernel, loop {head}: scratch {scratch[:2]}, waits {foreign}")
-    if seen < 2:
-        problems.append("king_filter kernels: an LDS-DMA loop is missing (listing format changed?)")
+    if seen == 0:
+        problems.append("king_filter_kernel: no LDS-DMA loop found (listing format changed?)")
     return problems
 
 

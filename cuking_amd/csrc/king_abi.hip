@@ -5,13 +5,9 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <atomic>
-#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <string>
-#include <tuple>
 #include <vector>
 
 #include "king_common.h"
@@ -101,26 +97,28 @@ struct cuking_ctx {
   uint4 *planes = nullptr;
   size_t planes_bytes = 0;
   uint64_t *band_prefix = nullptr;
-  size_t band_prefix_entries = 0;
+  size_t band_prefix_bytes = 0;
   TileSpace prefix_for = {0, 0, 0, 0};  // tile space the prefix was built for
 
-  // Remainder splitting of the matrix-core kernel (king_mfma.hip): one zeroed
-  // scratch slab per stream that launches it (launches on different streams
-  // may overlap), split_wgs workgroups = one per CU.  0 = never split.
+  // Remainder splitting of the matrix-core kernel (king_mfma.hip): split_wgs
+  // workgroups = one per CU.  0 = never split.
   uint32_t split_wgs = 0;
-  std::vector<std::pair<hipStream_t, uint32_t *>> split_scratch;
-  // Filter variant (king_filter.hip): control words, candidate list and dense-
-  // quadrant list, one set per stream like the split scratch.  The two caps are
-  // options so that tests can force the dense and the list-full paths.
-  struct FilterScratch {
+  // Scratch of one stream that launches pair kernels (launches on different streams may
+  // overlap): the matrix-core kernel's zeroed remainder slab, and the filter variant's
+  // control words, candidate list, dense-quadrant list and slabs (king_filter.hip), sized
+  // for a block of `filter_tiles` tiles (of its enumeration).  Each is allocated on first
+  // use; at most kMaxStreams streams, the oldest makes room.
+  struct StreamScratch {
     hipStream_t stream;
-    uint8_t *base;
-    uint64_t tiles;  // the block size (tiles of its enumeration) the lists are sized for
+    uint32_t *split = nullptr;
+    uint8_t *filter = nullptr;
+    uint64_t filter_tiles = 0;
   };
-  std::vector<FilterScratch> filter_scratch;
-  // The running totals of scratch blocks that have been freed since (a larger block took
-  // their place, their stream made room): the diagnostics count over the context's life.
+  std::vector<StreamScratch> scratch;
+  // The running totals of filter scratch that has been freed since (a larger block took
+  // its place, its stream made room): the diagnostics count over the context's life.
   unsigned long long filter_totals_retired[kNumTotals] = {};
+  // (the two caps are options so that tests can force the dense and the list-full paths)
   uint32_t filter_quadrant_cap = kFilterQuadrantCap;
   uint32_t filter_cand_cap = kFilterCandCap;
   uint32_t filter_split_min_steps = 8;  // k-steps per remainder piece, at least
@@ -133,11 +131,6 @@ struct cuking_ctx {
   int filter_rotate = 1;
   uint32_t filter_rotate_min_steps = 128;
   uint32_t filter_rotate_min_tiles = 2048;  // 8 rounds of one tile per CU
-  // one resident workgroup per CU takes tile after tile (king_filter.hip): measured 1.2 % behind
-  // one workgroup per tile at configs[2] -- the chip is power-bound, a CU that waits for the
-  // dispatcher lends its share to the others -- so off unless asked for
-  bool filter_persistent = false;
-  uint32_t filter_persistent_min_tiles = 2048;
   // The kernel layout's samples sorted by their share of missing calls (king_sort.hip);
   // the four-product kernel's codes converted only when the filter needs them
   // (0: with every conversion).
@@ -299,157 +292,185 @@ uint64_t total_tiles(const TileSpace &t) {
   return n;
 }
 
-// Split scratch of `stream` (allocated and zeroed on first use), or nullptr
-// when splitting is off / does not apply to the variant.
-cuking_status split_scratch_for(cuking_ctx *ctx, hipStream_t stream,
-                                uint32_t **scratch, uint32_t **counters) {
-  *scratch = *counters = nullptr;
-  if (ctx->split_wgs == 0 || !is_mfma_variant(ctx->variant)) return CUKING_OK;
-  const size_t bytes = mfma_split_scratch_bytes(ctx->split_wgs);
-  uint32_t *base = nullptr;
-  for (auto &e : ctx->split_scratch)
-    if (e.first == stream) base = e.second;
-  if (base == nullptr) {
-    if (ctx->split_scratch.size() >= 8) {
-      // Streams come and go (torch hands out new handles): keep the cache
-      // small.  Nothing may still be using a slab we free.
-      ++ctx->host_syncs;
-      HIP_TRY(hipDeviceSynchronize());
-      for (auto &e : ctx->split_scratch) (void)hipFree(e.second);
-      ctx->split_scratch.clear();
-    }
-    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&base), bytes));
-    ++ctx->workspace_allocations;
-    // The tickets must read zero when the first launch on this stream starts:
-    // zero them ON that stream (a null-stream memset is not ordered against a
-    // non-blocking stream, and fresh memory holds whatever was there before).
-    hipError_t e = hipMemsetAsync(base, 0, mfma_split_counter_bytes(ctx->split_wgs), stream);
-    if (e != hipSuccess) {
-      (void)hipFree(base);
-      HIP_TRY(e);
-    }
-    ctx->split_scratch.emplace_back(stream, base);
+// Streams whose scratch a context keeps (torch hands out new stream handles: the cache
+// stays small).
+constexpr size_t kMaxStreams = 8;
+
+// Frees the filter scratch of a stream on which nothing runs any more; its running totals
+// join the context's.
+void free_filter_scratch(cuking_ctx *ctx, cuking_ctx::StreamScratch &e) {
+  if (e.filter == nullptr) return;
+  unsigned long long v[kNumTotals] = {};
+  if (hipMemcpy(v, e.filter + filter_scratch_layout(e.filter_tiles).totals, sizeof v,
+                hipMemcpyDeviceToHost) == hipSuccess) {
+    for (uint32_t k = 0; k < kNumTotals; ++k) ctx->filter_totals_retired[k] += v[k];
   }
-  *counters = base;
-  *scratch = base + mfma_split_counter_bytes(ctx->split_wgs) / sizeof(uint32_t);
+  (void)hipGetLastError();
+  (void)hipFree(e.filter);
+  e.filter = nullptr;
+}
+
+// Waits for the stream of ctx->scratch[k] and drops its entry.  A stream its owner has
+// destroyed meanwhile cannot be waited for, but work it held may still run: then the
+// whole device is waited for.
+void evict_scratch(cuking_ctx *ctx, size_t k) {
+  cuking_ctx::StreamScratch &e = ctx->scratch[k];
+  ++ctx->host_syncs;
+  if (hipStreamSynchronize(e.stream) != hipSuccess) {
+    (void)hipGetLastError();
+    (void)hipDeviceSynchronize();
+    (void)hipGetLastError();
+  }
+  free_filter_scratch(ctx, e);
+  if (e.split != nullptr) (void)hipFree(e.split);
+  ctx->scratch.erase(ctx->scratch.begin() + (ptrdiff_t)k);
+}
+
+// What a launch of the context's variant needs per stream.
+bool uses_split_slab(const cuking_ctx *ctx) {
+  return ctx->split_wgs != 0 && is_mfma_variant(ctx->variant);
+}
+bool uses_filter_scratch(const cuking_ctx *ctx) { return ctx->variant == kMfmaFilterVariant; }
+
+// A device buffer of `bytes` whose bytes [zero_at, zero_at + zero_bytes) read zero when
+// the first kernel on `stream` starts: zeroed ON that stream (a null-stream memset is not
+// ordered against a non-blocking stream, and fresh memory holds whatever was there before).
+cuking_status alloc_scratch(cuking_ctx *ctx, void **p, size_t bytes, size_t zero_at,
+                            size_t zero_bytes, hipStream_t stream) {
+  HIP_TRY(hipMalloc(p, bytes));
+  ++ctx->workspace_allocations;
+  const hipError_t e = hipMemsetAsync(static_cast<uint8_t *>(*p) + zero_at, 0, zero_bytes, stream);
+  if (e != hipSuccess) {
+    (void)hipFree(*p);
+    *p = nullptr;
+    HIP_TRY(e);
+  }
   return CUKING_OK;
 }
 
-// Filter scratch of `stream` for a block of `tiles` tiles (allocated on first use, again
-// when a larger block comes; the control words are zeroed by every launch chunk), or
-// nothing when the context's variant is not the filter variant.  Fills the filter
-// fields of `a`.
-// Before a scratch block is freed (nothing runs on its stream any more): its running totals
-// join the context's.
-static void retire_filter_totals(cuking_ctx *ctx, const cuking_ctx::FilterScratch &e) {
-  if (e.base == nullptr) return;
-  unsigned long long v[kNumTotals] = {};
-  if (hipMemcpy(v, e.base + filter_scratch_layout(e.tiles).totals, sizeof v,
-                hipMemcpyDeviceToHost) != hipSuccess) {
-    (void)hipGetLastError();
-    return;
+// The scratch of `stream` for a block of `tiles` tiles (of its enumeration), allocated on
+// first use -- the filter scratch again when a larger block comes --, or nullptr when the
+// context's variant needs none.
+cuking_status scratch_for(cuking_ctx *ctx, hipStream_t stream, uint64_t tiles,
+                          cuking_ctx::StreamScratch **out) {
+  *out = nullptr;
+  const bool split = uses_split_slab(ctx), filter = uses_filter_scratch(ctx);
+  if (!split && !filter) return CUKING_OK;
+  cuking_ctx::StreamScratch *e = nullptr;
+  for (auto &x : ctx->scratch)
+    if (x.stream == stream) e = &x;
+  if (e == nullptr) {
+    if (ctx->scratch.size() >= kMaxStreams) evict_scratch(ctx, 0);
+    ctx->scratch.push_back({stream});
+    e = &ctx->scratch.back();
   }
-  for (uint32_t k = 0; k < kNumTotals; ++k) ctx->filter_totals_retired[k] += v[k];
-}
-
-cuking_status filter_scratch_for(cuking_ctx *ctx, hipStream_t stream, const PlaneGeometry &geo,
-                                 uint64_t tiles, TiledArgs *a) {
-  a->sample_stats = nullptr;
-  a->t2 = nullptr;
-  a->filter_ctrl = nullptr;
-  a->cand_list = nullptr;
-  a->dense_list = nullptr;
-  a->cand_cap = a->dense_cap = a->quadrant_cap = 0;
-  a->fsplit_parts = a->fsplit_first = a->fsplit_tile0 = 0;
-  a->fsplit_slabs = nullptr;
-  a->fsplit_tickets = nullptr;
-  a->filter_totals = nullptr;
-  a->tile_done = nullptr;
-  a->prefix_u = nullptr;
-  a->cohort_sums = nullptr;
-  a->check_steps = nullptr;
-  a->check0 = a->check1 = 0;
-  a->rotate = a->rotate_min_steps = a->rotate_min_tiles = 0;
-  a->persist_wgs = a->persist_min_tiles = 0;
-  if (ctx->variant != kMfmaFilterVariant) return CUKING_OK;
+  cuking_status st;
+  if (split && e->split == nullptr) {
+    // (the tickets in front of the slab)
+    st = alloc_scratch(ctx, reinterpret_cast<void **>(&e->split),
+                       mfma_split_scratch_bytes(ctx->split_wgs), 0,
+                       mfma_split_counter_bytes(ctx->split_wgs), stream);
+    if (st != CUKING_OK) return st;
+  }
   const FilterScratchLayout want = filter_scratch_layout(tiles);
-  cuking_ctx::FilterScratch *entry = nullptr;
-  for (auto &e : ctx->filter_scratch)
-    if (e.stream == stream) entry = &e;
-  if (entry != nullptr && filter_scratch_layout(entry->tiles).bytes < want.bytes) {
+  if (filter && e->filter != nullptr && filter_scratch_layout(e->filter_tiles).bytes < want.bytes) {
     // a larger block: kernels of this stream may still use the old lists
     ++ctx->host_syncs;
     HIP_TRY(hipStreamSynchronize(stream));
-    retire_filter_totals(ctx, *entry);
-    (void)hipFree(entry->base);
-    entry->base = nullptr;
+    free_filter_scratch(ctx, *e);
   }
-  if (entry == nullptr || entry->base == nullptr) {
-    if (entry == nullptr && ctx->filter_scratch.size() >= 8) {
-      // Streams come and go (torch hands out new handles): the oldest entry makes room.
-      ++ctx->host_syncs;
-      HIP_TRY(hipStreamSynchronize(ctx->filter_scratch.front().stream));
-      (void)hipGetLastError();  // (a stream its owner has destroyed meanwhile: nothing runs on it)
-      retire_filter_totals(ctx, ctx->filter_scratch.front());
-      (void)hipFree(ctx->filter_scratch.front().base);
-      ctx->filter_scratch.erase(ctx->filter_scratch.begin());
-    }
-    uint8_t *base = nullptr;
-    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&base), want.bytes));
-    ++ctx->workspace_allocations;
-    // (the running totals behind "filter_candidates" / "filter_dense_quadrants")
-    // ... and the tickets of the remainder pieces, zero between launches
-    hipError_t e = hipMemsetAsync(base + want.totals, 0, kFilterCtrlBytes + kFilterTicketBytes, stream);
-    if (e != hipSuccess) {
-      (void)hipFree(base);
-      HIP_TRY(e);
-    }
-    if (entry == nullptr) {
-      ctx->filter_scratch.push_back({stream, base, tiles});
-      entry = &ctx->filter_scratch.back();
-    } else {
-      entry->base = base;
-      entry->tiles = tiles;
-    }
+  if (filter && e->filter == nullptr) {
+    // (the running totals behind "filter_candidates" / "filter_dense_quadrants" and the
+    //  tickets of the remainder pieces, zero between launches)
+    st = alloc_scratch(ctx, reinterpret_cast<void **>(&e->filter), want.bytes, want.totals,
+                       kFilterCtrlBytes + kFilterTicketBytes, stream);
+    if (st != CUKING_OK) return st;
+    e->filter_tiles = tiles;
   }
-  uint8_t *base = entry->base;
-  const FilterScratchLayout l = filter_scratch_layout(entry->tiles);
-  a->sample_stats = plane_stats(ctx->planes, geo);
-  a->t2 = plane_t2(ctx->planes, geo);
-  a->prefix_u = plane_prefix_u(ctx->planes, geo);
-  a->cohort_sums = plane_cohort_sums(ctx->planes, geo);
-  a->filter_ctrl = reinterpret_cast<uint32_t *>(base);
-  a->filter_totals = reinterpret_cast<unsigned long long *>(base + l.totals);
-  a->fsplit_tickets = reinterpret_cast<uint32_t *>(base + l.tickets);
-  a->tile_done = base + l.tile_done;
-  a->cand_list = reinterpret_cast<uint2 *>(base + l.cand);
-  a->cand_cap = ctx->filter_cand_cap < l.cand_entries ? ctx->filter_cand_cap : l.cand_entries;
-  a->quadrant_cap = ctx->filter_quadrant_cap;
-  a->dense_list = reinterpret_cast<uint2 *>(base + l.dense);
-  a->dense_cap = l.chunk_tiles * 4;
-  // (remainder splitting follows the matrix-core kernels' switch: "split_wgs" 0 = never)
-  a->fsplit_first = ctx->filter_split_min_steps;  // (on entry: launch_filter)
-  a->fsplit_slabs = ctx->split_wgs != 0 ? reinterpret_cast<float4 *>(base + l.slabs) : nullptr;
-  a->check0 = (uint32_t)ctx->filter_check0;  // (switches on entry: launch_filter)
-  a->check1 = (uint32_t)ctx->filter_check1 | ((uint32_t)ctx->filter_check_emit << 8) |
-              (ctx->filter_check0 != 0 ? 1u << 16 : 0u);
-  a->rotate = (uint32_t)ctx->filter_rotate;
-  a->rotate_min_steps = ctx->filter_rotate_min_steps;
-  a->rotate_min_tiles = ctx->filter_rotate_min_tiles;
-  a->persist_wgs = ctx->filter_persistent ? 1u : 0u;
-  a->persist_min_tiles = ctx->filter_persistent_min_tiles;
-  a->check_steps = plane_check_steps(ctx->planes, geo);
+  *out = e;
   return CUKING_OK;
 }
 
-// The sample order of the workspace's layout, and the lazy-codes word, for the launch.
-void layout_order_for(const cuking_ctx *ctx, uint32_t words_per_sample, const PlaneGeometry &geo,
-                      TiledArgs *a) {
-  a->perm = nullptr;
-  a->codes_ready = nullptr;
-  if (plan_variant(ctx, words_per_sample).layout != kLayoutNibbleStats) return;
-  a->perm = plane_perm(ctx->planes, geo);
-  if (!ctx->prepared.codes) a->codes_ready = plane_flags(ctx->planes, geo);
+// The launch arguments of the pair kernels for the block `sm` of the prepared workspace
+// (geometry `geo`, enumeration `tiles`; the stream's filter scratch sized for
+// `block_tiles`), with the context's switches.  Callers fill in the tile range.
+struct Outputs {
+  uint32_t max_results;
+  cuking_result *results;
+  uint32_t *result_index, *result_overflow;
+  cuking_counts *counts;
+};
+cuking_status launch_args(cuking_ctx *ctx, hipStream_t stream, const cuking_submatrix &sm,
+                          uint32_t words_per_sample, const uint64_t *d_bit_sets,
+                          const PlaneGeometry &geo, const TileSpace &tiles,
+                          uint64_t block_tiles, float kin_threshold, const Outputs &out,
+                          TiledArgs *args) {
+  TiledArgs &a = *args;
+  a = {};
+  a.planes = ctx->planes;
+  a.geo = geo;
+  a.tiles = tiles;
+  a.band_prefix = ctx->band_prefix;
+  a.i_begin = sm.i_begin;
+  a.j_begin = sm.j_begin;
+  a.kin_threshold = kin_threshold;
+  a.max_results = out.max_results;
+  a.results = out.results;
+  a.result_index = out.result_index;
+  a.result_overflow = out.result_overflow;
+  a.dense_counts = out.counts;
+  a.rect_row_stride = 1;
+  a.bits = d_bit_sets;
+  a.words_per_sample = words_per_sample;
+  a.split_wgs = ctx->split_wgs;
+  a.xcd_chunk = (uint32_t)ctx->xcd_swizzle;  // (switch: 1 chunks, 2 patches; the launch sets the value)
+  a.dyn_tiles = ctx->dyn_tail_tiles;         // (threshold; the launch sets the count)
+  // the sample order of the workspace's layout, and the lazy-codes word
+  if (plan_variant(ctx, words_per_sample).layout == kLayoutNibbleStats) {
+    a.perm = plane_perm(ctx->planes, geo);
+    if (!ctx->prepared.codes) a.codes_ready = plane_flags(ctx->planes, geo);
+  }
+  cuking_ctx::StreamScratch *e;
+  const cuking_status st = scratch_for(ctx, stream, block_tiles, &e);
+  if (st != CUKING_OK || e == nullptr) return st;
+  if (uses_split_slab(ctx)) {
+    a.split_counters = e->split;
+    a.split_scratch = e->split + mfma_split_counter_bytes(ctx->split_wgs) / sizeof(uint32_t);
+  }
+  if (!uses_filter_scratch(ctx)) return CUKING_OK;
+  uint8_t *base = e->filter;
+  const FilterScratchLayout l = filter_scratch_layout(e->filter_tiles);
+  a.sample_stats = plane_stats(ctx->planes, geo);
+  a.t2 = plane_t2(ctx->planes, geo);
+  a.prefix_u = plane_prefix_u(ctx->planes, geo);
+  a.cohort_sums = plane_cohort_sums(ctx->planes, geo);
+  a.filter_ctrl = reinterpret_cast<uint32_t *>(base);
+  a.filter_totals = reinterpret_cast<unsigned long long *>(base + l.totals);
+  a.fsplit_tickets = reinterpret_cast<uint32_t *>(base + l.tickets);
+  a.tile_done = base + l.tile_done;
+  a.cand_list = reinterpret_cast<uint2 *>(base + l.cand);
+  a.cand_cap = ctx->filter_cand_cap < l.cand_entries ? ctx->filter_cand_cap : l.cand_entries;
+  a.quadrant_cap = ctx->filter_quadrant_cap;
+  a.dense_list = reinterpret_cast<uint2 *>(base + l.dense);
+  a.dense_cap = l.chunk_tiles * 4;
+  // (remainder splitting follows the matrix-core kernels' switch: "split_wgs" 0 = never)
+  a.fsplit_first = ctx->filter_split_min_steps;  // (on entry: launch_filter)
+  a.fsplit_slabs = ctx->split_wgs != 0 ? reinterpret_cast<float4 *>(base + l.slabs) : nullptr;
+  a.check0 = (uint32_t)ctx->filter_check0;  // (switches on entry: launch_filter)
+  a.check1 = (uint32_t)ctx->filter_check1 | ((uint32_t)ctx->filter_check_emit << 8) |
+             (ctx->filter_check0 != 0 ? 1u << 16 : 0u);
+  a.rotate = (uint32_t)ctx->filter_rotate;
+  a.rotate_min_steps = ctx->filter_rotate_min_steps;
+  a.rotate_min_tiles = ctx->filter_rotate_min_tiles;
+  a.check_steps = plane_check_steps(ctx->planes, geo);
+  return CUKING_OK;
+}
+
+// The filter's bound applies to a call: the four-product kernel's codes may stay
+// unconverted.
+bool filter_runs(const cuking_ctx *ctx, uint32_t words_per_sample, bool full, float kin_threshold) {
+  return effective_variant(ctx, words_per_sample) == kMfmaFilterVariant && !full &&
+         kin_threshold > 0.f && kin_threshold < 0.5f;
 }
 
 // Enqueues `num_tiles` tiles of the planned geometry: as they are when the
@@ -531,48 +552,35 @@ bool same_block(const cuking_ctx::Prepared &p, const cuking_submatrix &sm,
          p.tile == tile && p.bits == bits;
 }
 
-// Makes the plane workspace at least `need` bytes and the band prefix at least
-// `entries` long.  Replacing either waits for the whole device first: kernels
-// of earlier calls (possibly on other streams) may still read the old one.
-cuking_status ensure_workspace(cuking_ctx *ctx, size_t need, size_t entries) {
-  if (need > ctx->planes_bytes) {
-    ++ctx->host_syncs;
-    HIP_TRY(hipDeviceSynchronize());
-    if (ctx->planes) HIP_TRY(hipFree(ctx->planes));
-    ctx->planes = nullptr;
-    ctx->planes_bytes = 0;
-    ctx->prepared.valid = false;
-    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&ctx->planes), need));
-    ++ctx->workspace_allocations;
-    ctx->planes_bytes = need;
-  }
-  if (entries > ctx->band_prefix_entries) {
-    ++ctx->host_syncs;
-    HIP_TRY(hipDeviceSynchronize());
-    if (ctx->band_prefix) HIP_TRY(hipFree(ctx->band_prefix));
-    ctx->band_prefix = nullptr;
-    ctx->band_prefix_entries = 0;
-    ctx->prefix_for = TileSpace{0, 0, 0, 0};
-    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&ctx->band_prefix), entries * sizeof(uint64_t)));
-    ++ctx->workspace_allocations;
-    ctx->band_prefix_entries = entries;
-  }
+// Makes the device buffer *buf (*bytes long) at least `need` bytes.  Replacing it waits
+// for the whole device first: kernels of earlier calls (possibly on other streams) may
+// still read the old one.
+cuking_status grow(cuking_ctx *ctx, void **buf, size_t *bytes, size_t need) {
+  if (need <= *bytes) return CUKING_OK;
+  ++ctx->host_syncs;
+  HIP_TRY(hipDeviceSynchronize());
+  if (*buf) HIP_TRY(hipFree(*buf));
+  *buf = nullptr;
+  *bytes = 0;
+  HIP_TRY(hipMalloc(buf, need));
+  ++ctx->workspace_allocations;
+  *bytes = need;
   return CUKING_OK;
 }
 
-// Device scratch of the sample sort for ranges of up to `n` samples.
-cuking_status ensure_sort_temp(cuking_ctx *ctx, uint32_t n) {
-  const size_t need = sort_temp_bytes_for(n);
-  if (need <= ctx->sort_temp_bytes) return CUKING_OK;
-  ++ctx->host_syncs;
-  HIP_TRY(hipDeviceSynchronize());
-  if (ctx->sort_temp) HIP_TRY(hipFree(ctx->sort_temp));
-  ctx->sort_temp = nullptr;
-  ctx->sort_temp_bytes = 0;
-  HIP_TRY(hipMalloc(&ctx->sort_temp, need));
-  ++ctx->workspace_allocations;
-  ctx->sort_temp_bytes = need;
-  return CUKING_OK;
+// The workspace of the tiled kernel for `geo` / `tiles`: the planes, the band prefix
+// and the sample sort's scratch.
+cuking_status ensure_workspace(cuking_ctx *ctx, const PlaneGeometry &geo, const TiledVariant &v,
+                               const TileSpace &tiles) {
+  const size_t planes = plane_bytes(geo, v.layout);
+  if (planes > ctx->planes_bytes) ctx->prepared.valid = false;
+  cuking_status st = grow(ctx, reinterpret_cast<void **>(&ctx->planes), &ctx->planes_bytes, planes);
+  if (st != CUKING_OK) return st;
+  const size_t prefix = ((size_t)tiles.num_bands() + 1) * sizeof(uint64_t);
+  if (prefix > ctx->band_prefix_bytes) ctx->prefix_for = TileSpace{0, 0, 0, 0};
+  st = grow(ctx, reinterpret_cast<void **>(&ctx->band_prefix), &ctx->band_prefix_bytes, prefix);
+  if (st != CUKING_OK || v.layout != kLayoutNibbleStats || ctx->filter_sort == 0) return st;
+  return grow(ctx, &ctx->sort_temp, &ctx->sort_temp_bytes, sort_temp_bytes_for(geo.s_stride));
 }
 
 bool same_tile_space(const TileSpace &a, const TileSpace &b) {
@@ -632,14 +640,8 @@ cuking_status prepare(cuking_ctx *ctx, const cuking_submatrix &sm,
   *geo_out = geo;
   *tiles_out = tiles;
 
-  const size_t need = plane_bytes(geo, v.layout);
-  const uint32_t nb = tiles.num_bands();
-  cuking_status st = ensure_workspace(ctx, need, (size_t)nb + 1);
+  cuking_status st = ensure_workspace(ctx, geo, v, tiles);
   if (st != CUKING_OK) return st;
-  if (v.layout == kLayoutNibbleStats && ctx->filter_sort != 0) {
-    st = ensure_sort_temp(ctx, geo.s_stride);
-    if (st != CUKING_OK) return st;
-  }
   // Book-keeping of what the workspace holds, and ordering against kernels on
   // other streams that still read what is about to be overwritten -- the planes
   // AND the band prefix below, so this comes before either is touched.
@@ -690,7 +692,7 @@ cuking_status prepare(cuking_ctx *ctx, const cuking_submatrix &sm,
     if (st != CUKING_OK) return st;
   }
 
-  if (need == 0) return CUKING_OK;
+  if (plane_bytes(geo, v.layout) == 0) return CUKING_OK;
   EventPair *ev = nullptr;
   if (ctx->timing) HIP_TRY(ctx->prepare_timer.begin(stream, &ev));
   if (v.layout == kLayoutNibbleStats) {
@@ -734,18 +736,12 @@ cuking_status prepare(cuking_ctx *ctx, const cuking_submatrix &sm,
 cuking_status run_tiled(cuking_ctx *ctx, const cuking_submatrix &sm,
                         uint32_t words_per_sample, const uint64_t *d_bit_sets,
                         uint64_t tile_begin, uint64_t tile_end, bool whole,
-                        float kin_threshold, uint32_t max_results,
-                        cuking_result *d_results, uint32_t *d_result_index,
-                        uint32_t *d_result_overflow, cuking_counts *d_counts,
-                        hipStream_t stream) {
+                        float kin_threshold, const Outputs &out, hipStream_t stream) {
   PlaneGeometry geo;
   TileSpace tiles;
-  const bool full = use_full_counts(ctx, kin_threshold, d_counts != nullptr, words_per_sample);
-  // (the filter's bound applies: the four-product kernel's codes may stay unconverted)
-  const bool filter_runs = effective_variant(ctx, words_per_sample) == kMfmaFilterVariant &&
-                           !full && kin_threshold > 0.f && kin_threshold < 0.5f;
-  cuking_status st =
-      prepare(ctx, sm, words_per_sample, d_bit_sets, stream, &geo, &tiles, !filter_runs);
+  const bool full = use_full_counts(ctx, kin_threshold, out.counts != nullptr, words_per_sample);
+  cuking_status st = prepare(ctx, sm, words_per_sample, d_bit_sets, stream, &geo, &tiles,
+                             !filter_runs(ctx, words_per_sample, full, kin_threshold));
   if (st != CUKING_OK) return st;
   const uint64_t n_tiles = total_tiles(tiles);
   if (whole) {
@@ -759,36 +755,11 @@ cuking_status run_tiled(cuking_ctx *ctx, const cuking_submatrix &sm,
                 (unsigned long long)n_tiles);
   if (tile_begin == tile_end) return CUKING_OK;
 
-  TiledArgs a = {};
-  a.planes = ctx->planes;
-  a.geo = geo;
-  a.tiles = tiles;
-  a.band_prefix = ctx->band_prefix;
+  TiledArgs a;
+  st = launch_args(ctx, stream, sm, words_per_sample, d_bit_sets, geo, tiles, n_tiles,
+                   kin_threshold, out, &a);
+  if (st != CUKING_OK) return st;
   a.tile_begin = tile_begin;
-  a.i_begin = sm.i_begin;
-  a.j_begin = sm.j_begin;
-  a.kin_threshold = kin_threshold;
-  a.max_results = max_results;
-  a.results = d_results;
-  a.result_index = d_result_index;
-  a.result_overflow = d_result_overflow;
-  a.dense_counts = d_counts;
-  a.rect_rows = a.rect_cols = a.rect_row0 = a.rect_col0 = 0;
-  a.rect_row_stride = 1;
-  a.bits = d_bit_sets;
-  a.words_per_sample = words_per_sample;
-  a.split_tiles = 0;
-  a.split_whole = 0;
-  a.split_wgs = ctx->split_wgs;
-  a.xcd_chunk = (uint32_t)ctx->xcd_swizzle;  // (switch: 1 chunks, 2 patches; the launch sets the value)
-  a.launch_tiles = 0;
-  a.dyn_tiles = ctx->dyn_tail_tiles;  // (threshold; the launch sets the count)
-  a.dyn_wgs = 0;
-  st = split_scratch_for(ctx, stream, &a.split_scratch, &a.split_counters);
-  if (st != CUKING_OK) return st;
-  st = filter_scratch_for(ctx, stream, geo, n_tiles, &a);
-  if (st != CUKING_OK) return st;
-  layout_order_for(ctx, words_per_sample, geo, &a);
 
   EventPair *ev = nullptr;
   if (ctx->timing) HIP_TRY(ctx->king_timer.begin(stream, &ev));
@@ -811,6 +782,136 @@ cuking_status run_stream(cuking_ctx *ctx, const cuking_submatrix &sm,
                         max_results, d_results, d_result_index,
                         d_result_overflow, d_counts, stream));
   if (ev) HIP_TRY(hipEventRecord(ev->stop, stream));
+  return CUKING_OK;
+}
+
+// ---- options ---------------------------------------------------------------
+
+// What setting an option does besides storing the value.
+enum : uint8_t {
+  kInvalidatesLayout = 1,  // the prepared layout was built under the old value
+  kResizesSlabs = 2,       // split slabs are sized by it: a change frees them (waits for the device)
+};
+
+struct Option {
+  const char *key;
+  int64_t lo, hi;          // accepted values, inclusive ...
+  const char *error;       // ... and the message for any other (%u: error_arg)
+  uint32_t error_arg;
+  uint8_t effects;
+  int64_t (*get)(const cuking_ctx *);
+  void (*set)(cuking_ctx *, int64_t);
+  int64_t hole = INT64_MIN;  // a value inside the bounds that is refused as well
+};
+
+// Reads and stores a field of the context.
+#define CTX_FIELD(f)                                                     \
+  [](const cuking_ctx *c) -> int64_t { return (int64_t)c->f; },          \
+  [](cuking_ctx *c, int64_t v) { c->f = (decltype(c->f))v; }
+
+// The settable options (include/cuking_amd.h documents them in this order).  None of them
+// changes any record.
+const Option kOptions[] = {
+    {"variant", 0, kNumTiledVariants - 1, "variant outside [0, %u)", kNumTiledVariants, 0,
+     CTX_FIELD(variant)},
+    {"band_rows", 0, 64, "band_rows outside [0, 64]", 0, 0, CTX_FIELD(band_rows)},
+    {"counts_mode", -1, 1, "counts_mode outside [-1, 1]", 0, 0, CTX_FIELD(counts_mode)},
+    {"split_wgs", 0, 4096, "split_wgs outside [0, 4096]", 0, kResizesSlabs, CTX_FIELD(split_wgs)},
+    {"xcd_swizzle", 0, 2, "xcd_swizzle outside [0, 2]", 0, 0, CTX_FIELD(xcd_swizzle)},
+    {"dyn_tail_tiles", 0, 0x7FFFFFFF, "dyn_tail_tiles outside [0, 2^31)", 0, 0,
+     CTX_FIELD(dyn_tail_tiles)},
+    {"reuse_prepared", 0, 1, "reuse_prepared outside [0, 1]", 0, 0, CTX_FIELD(reuse_prepared)},
+    {"filter_sort", 0, 2, "filter_sort outside [0, 2]", 0, kInvalidatesLayout,
+     CTX_FIELD(filter_sort)},
+    {"filter_lazy_codes", 0, 1, "filter_lazy_codes outside [0, 1]", 0, kInvalidatesLayout,
+     CTX_FIELD(filter_lazy_codes)},
+    {"filter_check0", 0, 2, "filter_check0 outside [0, 2]", 0, 0, CTX_FIELD(filter_check0)},
+    {"filter_check1", 0, 1 + kNumCheckShares, "filter_check1 outside {0, 1, 3 .. %u}",
+     1 + kNumCheckShares, 0, CTX_FIELD(filter_check1), /*hole=*/2},
+    {"filter_check_emit", 0, 255, "filter_check_emit outside [0, 255]", 0, 0,
+     CTX_FIELD(filter_check_emit)},
+    {"filter_rotate", 0, 2 + kNumPhases, "filter_rotate outside [0, %u]", 2 + kNumPhases, 0,
+     CTX_FIELD(filter_rotate)},
+    {"filter_rotate_min_steps", 1, 1 << 20, "filter_rotate_min_steps outside [1, 2^20]", 0, 0,
+     CTX_FIELD(filter_rotate_min_steps)},
+    {"filter_rotate_min_tiles", 0, 1 << 30, "filter_rotate_min_tiles outside [0, 2^30]", 0, 0,
+     CTX_FIELD(filter_rotate_min_tiles)},
+    // test hooks: force the paths of the filter variant that ordinary cohorts do not take
+    {"filter_quadrant_cap", 0, 16384, "filter_quadrant_cap outside [0, 16384]", 0, 0,
+     CTX_FIELD(filter_quadrant_cap)},
+    {"filter_cand_cap", 0, kFilterCandCap, "filter_cand_cap outside [0, %u]", kFilterCandCap, 0,
+     CTX_FIELD(filter_cand_cap)},
+    {"filter_split_min_steps", 1, 4096, "filter_split_min_steps outside [1, 4096]", 0, 0,
+     CTX_FIELD(filter_split_min_steps)},
+    // test hooks of the whole process, not of the context
+    {"max_launch_blocks", 0, INT64_MAX, "negative block cap", 0, 0,
+     [](const cuking_ctx *) -> int64_t { return (int64_t)max_blocks_override(); },
+     [](cuking_ctx *, int64_t v) { set_max_blocks_per_launch((uint64_t)v); }},
+    {"filter_check_min_steps", 4, 1 << 20, "filter_check_min_steps outside [4, 2^20]", 0,
+     kInvalidatesLayout,  // (the prefix counts of the workspace belong to the old value)
+     [](const cuking_ctx *) -> int64_t { return filter_check_min_steps(); },
+     [](cuking_ctx *, int64_t v) { set_filter_check_min_steps((uint32_t)v); }},
+};
+#undef CTX_FIELD
+
+const Option *find_option(const char *key) {
+  for (const Option &o : kOptions)
+    if (strcmp(o.key, key) == 0) return &o;
+  return nullptr;
+}
+
+// The read-only keys of cuking_ctx_get_option.
+cuking_status read_diagnostic(const cuking_ctx *ctx, const char *key, int64_t *value) {
+  const std::pair<const char *, uint64_t> counters[] = {
+      {"workspace_allocations", ctx->workspace_allocations},
+      {"host_syncs", ctx->host_syncs},
+      {"conversions_skipped", ctx->conversions_skipped}};
+  for (const auto &c : counters)
+    if (strcmp(c.first, key) == 0) {
+      *value = (int64_t)c.second;
+      return CUKING_OK;
+    }
+  // Diagnostics of the filter variant, summed over the context's streams (they WAIT for the
+  // device): pairs the bound let through, quadrants handed to the exact kernel, tiles that
+  // left at the rigorous check point and tiles that started at another phase, since the
+  // context was created ...
+  const char *const totals[kNumTotals] = {"filter_candidates", "filter_dense_quadrants",
+                                          "filter_early_exits", "filter_rotated_tiles"};
+  static_assert(kTotalCand == 0 && kTotalDense == 1 && kTotalEarly == 2 && kTotalRotated == 3,
+                "totals[] in the order of the running totals");
+  uint32_t word = 0;
+  while (word < kNumTotals && strcmp(totals[word], key) != 0) ++word;
+  // ... and the 100 MHz counter's ticks per k-step x 16 as the tiles of the last launch chunk
+  // measured them (rotated tiles, king_filter.hip), averaged over the XCDs that said so and
+  // the context's streams; 0 = nobody did.
+  const bool ticks = strcmp(key, "filter_step_ticks16") == 0;
+  if (word == kNumTotals && !ticks)
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "unknown option %s", key);
+  if (hipSetDevice(ctx->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess)
+    return cuking_fail(CUKING_ERR_DEVICE, "device wait failed");
+  unsigned long long sum = 0;
+  uint64_t count = 0;
+  for (const auto &e : ctx->scratch) {
+    if (e.filter == nullptr) continue;
+    if (ticks) {
+      uint32_t w[8];
+      if (hipMemcpy(w, e.filter + kCtrlStepTicks * 4, sizeof w, hipMemcpyDeviceToHost) != hipSuccess)
+        return cuking_fail(CUKING_ERR_DEVICE, "reading the filter counters failed");
+      for (uint32_t v : w)
+        if (v != 0) {
+          sum += v;
+          ++count;
+        }
+    } else {
+      unsigned long long v = 0;
+      if (hipMemcpy(&v, e.filter + filter_scratch_layout(e.filter_tiles).totals + word * 8, 8,
+                    hipMemcpyDeviceToHost) != hipSuccess)
+        return cuking_fail(CUKING_ERR_DEVICE, "reading the filter counters failed");
+      sum += v;
+    }
+  }
+  if (ticks) *value = count != 0 ? (int64_t)(sum / count) : 0;
+  else *value = (int64_t)(sum + ctx->filter_totals_retired[word]);
   return CUKING_OK;
 }
 
@@ -848,22 +949,6 @@ cuking_status cuking_ctx_create(int device, cuking_ctx **out) {
   ctx->device = device;
   ctx->variant = default_variant();
   ctx->split_wgs = (uint32_t)prop.multiProcessorCount;
-  if (const char *v = getenv("CUKING_AMD_SPLIT_WGS")) {
-    const int k = atoi(v);
-    if (k >= 0 && k <= 4096) ctx->split_wgs = (uint32_t)k;
-  }
-  if (const char *v = getenv("CUKING_AMD_XCD_SWIZZLE")) {
-    const int k = atoi(v);
-    if (k >= 0 && k <= 2) ctx->xcd_swizzle = k;
-  }
-  if (const char *v = getenv("CUKING_AMD_DYN_TAIL_TILES")) {
-    const long long k = atoll(v);
-    if (k >= 0 && k <= 0x7FFFFFFF) ctx->dyn_tail_tiles = (uint32_t)k;
-  }
-  if (const char *v = getenv("CUKING_AMD_BAND_ROWS")) {
-    const int k = atoi(v);
-    if (k >= 1 && k <= 64) ctx->band_rows = (uint32_t)k;
-  }
   *out = ctx;
   return CUKING_OK;
 }
@@ -874,8 +959,10 @@ void cuking_ctx_destroy(cuking_ctx *ctx) {
   if (ctx->planes) (void)hipFree(ctx->planes);
   if (ctx->band_prefix) (void)hipFree(ctx->band_prefix);
   if (ctx->sort_temp) (void)hipFree(ctx->sort_temp);
-  for (auto &e : ctx->split_scratch) (void)hipFree(e.second);
-  for (auto &e : ctx->filter_scratch) (void)hipFree(e.base);
+  for (auto &e : ctx->scratch) {
+    if (e.split) (void)hipFree(e.split);
+    if (e.filter) (void)hipFree(e.filter);
+  }
   for (auto &r : ctx->readers)
     if (r.second) (void)hipEventDestroy(r.second);
   ctx->king_timer.destroy();
@@ -895,147 +982,20 @@ cuking_status cuking_ctx_set_option(cuking_ctx *ctx, const char *key,
                                     int64_t value) {
   if (ctx == nullptr || key == nullptr)
     return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "null argument");
-  if (strcmp(key, "variant") == 0) {
-    if (value < 0 || value >= kNumTiledVariants)
-      return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "variant outside [0, %d)",
-                  kNumTiledVariants);
-    ctx->variant = (int)value;
-    return CUKING_OK;
-  }
-  if (strcmp(key, "band_rows") == 0) {
-    if (value < 0 || value > 64)
-      return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "band_rows outside [0, 64]");
-    ctx->band_rows = (uint32_t)value;
-    return CUKING_OK;
-  }
-  if (strcmp(key, "split_wgs") == 0) {  // 0 = never split the remainder
-    if (value < 0 || value > 4096)
-      return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "split_wgs outside [0, 4096]");
-    if ((uint32_t)value != ctx->split_wgs) {
-      // slabs are sized by the workgroup count
-      HIP_TRY(hipDeviceSynchronize());
-      for (auto &e : ctx->split_scratch) (void)hipFree(e.second);
-      ctx->split_scratch.clear();
+  const Option *o = find_option(key);
+  if (o == nullptr) return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "unknown option %s", key);
+  if (value < o->lo || value > o->hi || value == o->hole)
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, o->error, o->error_arg);
+  if ((o->effects & kResizesSlabs) && value != o->get(ctx)) {
+    HIP_TRY(hipDeviceSynchronize());
+    for (auto &e : ctx->scratch) {
+      if (e.split) (void)hipFree(e.split);
+      e.split = nullptr;
     }
-    ctx->split_wgs = (uint32_t)value;
-    return CUKING_OK;
   }
-  if (strcmp(key, "max_launch_blocks") == 0) {  // test hook, process-wide
-    if (value < 0) return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "negative block cap");
-    set_max_blocks_per_launch((uint64_t)value);
-    return CUKING_OK;
-  }
-  if (strcmp(key, "dyn_tail_tiles") == 0) {  // 0 = never; tests lower it
-    if (value < 0 || value > 0x7FFFFFFF)
-      return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "dyn_tail_tiles outside [0, 2^31)");
-    ctx->dyn_tail_tiles = (uint32_t)value;
-    return CUKING_OK;
-  }
-  if (strcmp(key, "xcd_swizzle") == 0) {
-    if (value < 0 || value > 2)
-      return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "xcd_swizzle outside [0, 2]");
-    ctx->xcd_swizzle = (int)value;
-    return CUKING_OK;
-  }
-  if (strcmp(key, "counts_mode") == 0) {
-    if (value < -1 || value > 1)
-      return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "counts_mode outside [-1, 1]");
-    ctx->counts_mode = (int)value;
-    return CUKING_OK;
-  }
-  if (strcmp(key, "filter_quadrant_cap") == 0) {  // tests: 0 sends every quadrant with a candidate to the exact kernel
-    if (value < 0 || value > 16384)
-      return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "filter_quadrant_cap outside [0, 16384]");
-    ctx->filter_quadrant_cap = (uint32_t)value;
-    return CUKING_OK;
-  }
-  if (strcmp(key, "filter_split_min_steps") == 0) {  // tests: remainder pieces of short bitsets
-    if (value < 1 || value > 4096)
-      return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "filter_split_min_steps outside [1, 4096]");
-    ctx->filter_split_min_steps = (uint32_t)value;
-    return CUKING_OK;
-  }
-  if (strcmp(key, "filter_check_min_steps") == 0) {  // test hook, process-wide: checks for short bitsets
-    if (value < 4 || value > 1 << 20)
-      return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "filter_check_min_steps outside [4, 2^20]");
-    set_filter_check_min_steps((uint32_t)value);
-    ctx->prepared.valid = false;  // (prefix counts of the workspace belong to the old value)
-    return CUKING_OK;
-  }
-  if (strcmp(key, "filter_sort") == 0) {
-    if (value < 0 || value > 2)
-      return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "filter_sort outside [0, 2]");
-    ctx->filter_sort = (int)value;
-    ctx->prepared.valid = false;  // (the workspace was laid out under the old setting)
-    return CUKING_OK;
-  }
-  if (strcmp(key, "filter_lazy_codes") == 0) {
-    if (value < 0 || value > 1)
-      return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "filter_lazy_codes outside [0, 1]");
-    ctx->filter_lazy_codes = value != 0;
-    ctx->prepared.valid = false;
-    return CUKING_OK;
-  }
-  if (strcmp(key, "filter_check0") == 0) {  // forecast check: 0 off, 1 short launches, 2 always
-    if (value < 0 || value > 2)
-      return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "filter_check0 outside [0, 2]");
-    ctx->filter_check0 = (int)value;
-    return CUKING_OK;
-  }
-  if (strcmp(key, "filter_rotate") == 0) {  // rotated tiles: 0 off, 1 on, 2 / 3 + phase: test hooks
-    if (value < 0 || value > 2 + (int64_t)kNumPhases)
-      return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "filter_rotate outside [0, %u]", 2 + kNumPhases);
-    ctx->filter_rotate = (int)value;
-    return CUKING_OK;
-  }
-  if (strcmp(key, "filter_persistent_min_tiles") == 0) {
-    if (value < 0 || value > (1 << 30))
-      return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "filter_persistent_min_tiles outside [0, 2^30]");
-    ctx->filter_persistent_min_tiles = (uint32_t)value;
-    return CUKING_OK;
-  }
-  if (strcmp(key, "filter_persistent") == 0) {
-    ctx->filter_persistent = value != 0;
-    return CUKING_OK;
-  }
-  if (strcmp(key, "filter_rotate_min_tiles") == 0) {
-    if (value < 0 || value > (1 << 30))
-      return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "filter_rotate_min_tiles outside [0, 2^30]");
-    ctx->filter_rotate_min_tiles = (uint32_t)value;
-    return CUKING_OK;
-  }
-  if (strcmp(key, "filter_rotate_min_steps") == 0) {
-    if (value < 1 || value > (1 << 20))
-      return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "filter_rotate_min_steps outside [1, 2^20]");
-    ctx->filter_rotate_min_steps = (uint32_t)value;
-    return CUKING_OK;
-  }
-  if (strcmp(key, "filter_check_emit") == 0) {  // live pairs per quadrant handed over at the check
-    if (value < 0 || value > 255)
-      return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "filter_check_emit outside [0, 255]");
-    ctx->filter_check_emit = (int)value;
-    return CUKING_OK;
-  }
-  if (strcmp(key, "filter_check1") == 0) {  // rigorous check: 0 off, 1 automatic, 2 + k entry k
-    if (value < 0 || value > 1 + (int64_t)kNumCheckShares || value == 2)
-      return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "filter_check1 outside {0, 1, 3 .. %u}",
-                  1 + kNumCheckShares);
-    ctx->filter_check1 = (int)value;
-    return CUKING_OK;
-  }
-  if (strcmp(key, "filter_cand_cap") == 0) {  // tests: a short candidate list
-    if (value < 0 || value > (int64_t)kFilterCandCap)
-      return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "filter_cand_cap outside [0, %u]", kFilterCandCap);
-    ctx->filter_cand_cap = (uint32_t)value;
-    return CUKING_OK;
-  }
-  if (strcmp(key, "reuse_prepared") == 0) {
-    if (value < 0 || value > 1)
-      return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "reuse_prepared outside [0, 1]");
-    ctx->reuse_prepared = value != 0;
-    return CUKING_OK;
-  }
-  return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "unknown option %s", key);
+  o->set(ctx, value);
+  if (o->effects & kInvalidatesLayout) ctx->prepared.valid = false;
+  return CUKING_OK;
 }
 
 cuking_status cuking_device_alloc(cuking_ctx *ctx, size_t bytes, void **d_ptr) {
@@ -1246,71 +1206,11 @@ cuking_status cuking_ctx_get_option(const cuking_ctx *ctx, const char *key,
                                     int64_t *value) {
   if (ctx == nullptr || key == nullptr || value == nullptr)
     return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "null argument");
-  if (strcmp(key, "variant") == 0) *value = ctx->variant;
-  else if (strcmp(key, "split_wgs") == 0) *value = ctx->split_wgs;
-  else if (strcmp(key, "band_rows") == 0) *value = ctx->band_rows;
-  else if (strcmp(key, "counts_mode") == 0) *value = ctx->counts_mode;
-  else if (strcmp(key, "xcd_swizzle") == 0) *value = ctx->xcd_swizzle;
-  else if (strcmp(key, "dyn_tail_tiles") == 0) *value = ctx->dyn_tail_tiles;
-  else if (strcmp(key, "reuse_prepared") == 0) *value = ctx->reuse_prepared ? 1 : 0;
-  else if (strcmp(key, "filter_quadrant_cap") == 0) *value = ctx->filter_quadrant_cap;
-  else if (strcmp(key, "filter_cand_cap") == 0) *value = ctx->filter_cand_cap;
-  else if (strcmp(key, "filter_split_min_steps") == 0) *value = ctx->filter_split_min_steps;
-  else if (strcmp(key, "filter_sort") == 0) *value = ctx->filter_sort;
-  else if (strcmp(key, "filter_lazy_codes") == 0) *value = ctx->filter_lazy_codes ? 1 : 0;
-  else if (strcmp(key, "filter_check0") == 0) *value = ctx->filter_check0;
-  else if (strcmp(key, "filter_check1") == 0) *value = ctx->filter_check1;
-  else if (strcmp(key, "filter_check_emit") == 0) *value = ctx->filter_check_emit;
-  else if (strcmp(key, "filter_rotate") == 0) *value = ctx->filter_rotate;
-  else if (strcmp(key, "filter_rotate_min_steps") == 0) *value = ctx->filter_rotate_min_steps;
-  else if (strcmp(key, "filter_rotate_min_tiles") == 0) *value = ctx->filter_rotate_min_tiles;
-  else if (strcmp(key, "filter_persistent") == 0) *value = ctx->filter_persistent ? 1 : 0;
-  else if (strcmp(key, "filter_persistent_min_tiles") == 0) *value = ctx->filter_persistent_min_tiles;
-  else if (strcmp(key, "filter_candidates") == 0 || strcmp(key, "filter_dense_quadrants") == 0 ||
-           strcmp(key, "filter_early_exits") == 0 || strcmp(key, "filter_rotated_tiles") == 0) {
-    // Diagnostics (they WAIT for the device): pairs the bound let through, quadrants
-    // handed to the exact kernel, and tiles that left at the rigorous check point, summed
-    // over the context's streams, since the context was created.
-    const size_t word = strcmp(key, "filter_candidates") == 0        ? kTotalCand
-                        : strcmp(key, "filter_dense_quadrants") == 0 ? kTotalDense
-                        : strcmp(key, "filter_early_exits") == 0     ? kTotalEarly
-                                                                     : kTotalRotated;
-    unsigned long long total = 0;
-    if (hipSetDevice(ctx->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess)
-      return cuking_fail(CUKING_ERR_DEVICE, "device wait failed");
-    for (auto &e : ctx->filter_scratch) {
-      unsigned long long v = 0;
-      if (hipMemcpy(&v, e.base + filter_scratch_layout(e.tiles).totals + word * 8, 8,
-                    hipMemcpyDeviceToHost) != hipSuccess)
-        return cuking_fail(CUKING_ERR_DEVICE, "reading the filter counters failed");
-      total += v;
-    }
-    *value = (int64_t)(total + ctx->filter_totals_retired[word]);
+  if (const Option *o = find_option(key)) {
+    *value = o->get(ctx);
+    return CUKING_OK;
   }
-  else if (strcmp(key, "filter_step_ticks16") == 0) {
-    // Diagnostic (WAITS for the device): the 100 MHz counter's ticks per k-step x 16 as the
-    // tiles of the last launch chunk measured them (rotated tiles, king_filter.hip), averaged
-    // over the XCDs that said so and the context's streams; 0 = nobody did.
-    if (hipSetDevice(ctx->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess)
-      return cuking_fail(CUKING_ERR_DEVICE, "device wait failed");
-    uint64_t sum = 0, count = 0;
-    for (auto &e : ctx->filter_scratch) {
-      uint32_t w[8];
-      if (hipMemcpy(w, e.base + kCtrlStepTicks * 4, sizeof w, hipMemcpyDeviceToHost) != hipSuccess)
-        return cuking_fail(CUKING_ERR_DEVICE, "reading the filter counters failed");
-      for (uint32_t v : w)
-        if (v != 0) {
-          sum += v;
-          ++count;
-        }
-    }
-    *value = count != 0 ? (int64_t)(sum / count) : 0;
-  }
-  else if (strcmp(key, "workspace_allocations") == 0) *value = (int64_t)ctx->workspace_allocations;
-  else if (strcmp(key, "host_syncs") == 0) *value = (int64_t)ctx->host_syncs;
-  else if (strcmp(key, "conversions_skipped") == 0) *value = (int64_t)ctx->conversions_skipped;
-  else return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "unknown option %s", key);
-  return CUKING_OK;
+  return read_diagnostic(ctx, key, value);
 }
 
 int cuking_num_variants(void) { return kNumTiledVariants; }
@@ -1347,9 +1247,9 @@ cuking_status cuking_compute_king(cuking_ctx *ctx, const cuking_submatrix *sm,
     return run_stream(ctx, *sm, words_per_sample, d_bit_sets, kin_threshold,
                       max_results, d_results, d_result_index, d_result_overflow,
                       nullptr, (hipStream_t)stream);
-  return run_tiled(ctx, *sm, words_per_sample, d_bit_sets, 0, 0, true,
-                   kin_threshold, max_results, d_results, d_result_index,
-                   d_result_overflow, nullptr, (hipStream_t)stream);
+  return run_tiled(ctx, *sm, words_per_sample, d_bit_sets, 0, 0, true, kin_threshold,
+                   {max_results, d_results, d_result_index, d_result_overflow, nullptr},
+                   (hipStream_t)stream);
 }
 
 cuking_status cuking_compute_king_tiles(
@@ -1368,9 +1268,10 @@ cuking_status cuking_compute_king_tiles(
       return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "empty block has no tiles");
     return CUKING_OK;
   }
-  return run_tiled(ctx, *sm, words_per_sample, d_bit_sets, tile_begin, tile_end,
-                   false, kin_threshold, max_results, d_results, d_result_index,
-                   d_result_overflow, nullptr, (hipStream_t)stream);
+  return run_tiled(ctx, *sm, words_per_sample, d_bit_sets, tile_begin, tile_end, false,
+                   kin_threshold,
+                   {max_results, d_results, d_result_index, d_result_overflow, nullptr},
+                   (hipStream_t)stream);
 }
 
 // Offsets of a sample range inside a diagonal block, in tiles.
@@ -1479,42 +1380,20 @@ cuking_status cuking_compute_king_rect(
                     sm->i_begin + c * v.tile);
   }
 
-  TiledArgs a = {};
-  a.planes = ctx->planes;
-  a.geo = geo;
-  a.tiles = tiles;
-  a.band_prefix = ctx->band_prefix;  // unused in rectangle mode
-  a.tile_begin = 0;
+  TiledArgs a;
+  st = launch_args(ctx, (hipStream_t)stream, *sm, words_per_sample, d_bit_sets, geo, tiles,
+                   total_tiles(make_tiles(geo, v, ctx->band_rows)), kin_threshold,
+                   {max_results, d_results, d_result_index, d_result_overflow, nullptr}, &a);
+  if (st != CUKING_OK) return st;
   a.rect_rows = n_rows;
   a.rect_cols = c1 - c0;
   a.rect_row0 = r0;
   a.rect_col0 = c0;
   a.rect_row_stride = stride;
-  a.i_begin = sm->i_begin;
-  a.j_begin = sm->j_begin;
-  a.kin_threshold = kin_threshold;
-  a.max_results = max_results;
-  a.results = d_results;
-  a.result_index = d_result_index;
-  a.result_overflow = d_result_overflow;
-  a.dense_counts = nullptr;
-  a.bits = d_bit_sets;
-  a.words_per_sample = words_per_sample;
-  a.split_tiles = 0;
-  a.split_whole = 0;
-  a.split_wgs = ctx->split_wgs;
   a.xcd_chunk = ctx->xcd_swizzle == 2 ? 2u : 0u;  // (see above; patches keep the balance)
-  a.launch_tiles = 0;
-  a.dyn_tiles = ctx->dyn_tail_tiles;
-  a.dyn_wgs = 0;
-  st = split_scratch_for(ctx, (hipStream_t)stream, &a.split_scratch, &a.split_counters);
-  if (st != CUKING_OK) return st;
-  st = filter_scratch_for(ctx, (hipStream_t)stream, geo, total_tiles(make_tiles(geo, v, ctx->band_rows)), &a);
-  if (st != CUKING_OK) return st;
-  layout_order_for(ctx, words_per_sample, geo, &a);
   const bool full = use_full_counts(ctx, kin_threshold, false, words_per_sample);
   if (v.layout == kLayoutNibbleStats && !ctx->prepared.codes &&
-      !(variant == kMfmaFilterVariant && !full && kin_threshold > 0.f && kin_threshold < 0.5f)) {
+      !filter_runs(ctx, words_per_sample, full, kin_threshold)) {
     // (a block converted without the four-product kernel's codes, and a call that runs
     //  that kernel directly)
     st = convert_codes_now(ctx, geo, words_per_sample, d_bit_sets, (hipStream_t)stream);
@@ -1548,12 +1427,8 @@ cuking_status cuking_ctx_reserve(cuking_ctx *ctx, const cuking_submatrix *sm,
   const TiledVariant v = plan_variant(ctx, words_per_sample);
   const PlaneGeometry geo = make_geometry(*sm, words_per_sample, v);
   const TileSpace tiles = make_tiles(geo, v, ctx->band_rows);
-  st = ensure_workspace(ctx, plane_bytes(geo, v.layout), (size_t)tiles.num_bands() + 1);
+  st = ensure_workspace(ctx, geo, v, tiles);
   if (st != CUKING_OK) return st;
-  if (v.layout == kLayoutNibbleStats && ctx->filter_sort != 0) {
-    st = ensure_sort_temp(ctx, geo.s_stride);
-    if (st != CUKING_OK) return st;
-  }
   if (!same_tile_space(ctx->prefix_for, tiles)) {
     // (nothing may be reading another block's prefix: the caller reserves
     //  before it enqueues work for this block)
@@ -1564,57 +1439,29 @@ cuking_status cuking_ctx_reserve(cuking_ctx *ctx, const cuking_submatrix *sm,
     st = upload_prefix(ctx, tiles, nullptr);
     if (st != CUKING_OK) return st;
   }
-  if (num_streams > 8)
-    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "at most 8 streams per context can be reserved");
-  if (ctx->split_wgs != 0 && is_mfma_variant(ctx->variant)) {
-    // (the slab cache holds 8 streams and drops ALL of them when a ninth comes:
-    //  make room now rather than lose a slab reserved a moment ago)
-    size_t missing = 0;
-    for (size_t k = 0; k < num_streams; ++k) {
-      bool have = false;
-      for (auto &e : ctx->split_scratch) have = have || e.first == (hipStream_t)streams[k];
-      missing += have ? 0 : 1;
-    }
-    if (missing != 0 && ctx->split_scratch.size() + missing > 8) {
-      ++ctx->host_syncs;
-      HIP_TRY(hipDeviceSynchronize());
-      for (auto &e : ctx->split_scratch) (void)hipFree(e.second);
-      ctx->split_scratch.clear();
-    }
-  }
-  if (ctx->variant == kMfmaFilterVariant) {
-    // (the scratch cache holds 8 streams and evicts the oldest for a ninth: make room
-    //  now, so that nothing reserved here is the one evicted)
-    size_t missing = 0;
-    for (size_t k = 0; k < num_streams; ++k) {
-      bool have = false;
-      for (auto &e : ctx->filter_scratch) have = have || e.stream == (hipStream_t)streams[k];
-      missing += have ? 0 : 1;
-    }
-    if (missing != 0 && ctx->filter_scratch.size() + missing > 8) {
-      // drop what this reservation does not name
-      ++ctx->host_syncs;
-      HIP_TRY(hipDeviceSynchronize());
-      std::vector<cuking_ctx::FilterScratch> keep;
-      for (auto &e : ctx->filter_scratch) {
-        bool named = false;
-        for (size_t k = 0; k < num_streams; ++k) named = named || e.stream == (hipStream_t)streams[k];
-        if (named) {
-          keep.push_back(e);
-        } else {
-          retire_filter_totals(ctx, e);
-          (void)hipFree(e.base);
-        }
-      }
-      ctx->filter_scratch.swap(keep);
+  if (num_streams > kMaxStreams)
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT,
+                       "at most %zu streams per context can be reserved", kMaxStreams);
+  auto named = [&](hipStream_t s) {
+    for (size_t k = 0; k < num_streams; ++k)
+      if ((hipStream_t)streams[k] == s) return true;
+    return false;
+  };
+  if (uses_split_slab(ctx) || uses_filter_scratch(ctx)) {
+    // Make room now, so that no stream reserved here is the one evicted for a later one:
+    // the oldest entries this reservation does not name go.
+    size_t missing = num_streams;
+    for (const auto &e : ctx->scratch) missing -= named(e.stream) ? 1 : 0;
+    for (size_t k = 0; ctx->scratch.size() + missing > kMaxStreams;) {
+      if (named(ctx->scratch[k].stream))
+        ++k;
+      else
+        evict_scratch(ctx, k);
     }
   }
   for (size_t k = 0; k < num_streams; ++k) {
-    uint32_t *scratch, *counters;
-    st = split_scratch_for(ctx, (hipStream_t)streams[k], &scratch, &counters);
-    if (st != CUKING_OK) return st;
-    TiledArgs unused = {};
-    st = filter_scratch_for(ctx, (hipStream_t)streams[k], geo, total_tiles(tiles), &unused);
+    cuking_ctx::StreamScratch *e;
+    st = scratch_for(ctx, (hipStream_t)streams[k], total_tiles(tiles), &e);
     if (st != CUKING_OK) return st;
   }
   return CUKING_OK;
@@ -1642,8 +1489,8 @@ cuking_status cuking_compute_counts(cuking_ctx *ctx, const cuking_submatrix *sm,
   if (ctx->kernel == CUKING_KERNEL_STREAM)
     return run_stream(ctx, *sm, words_per_sample, d_bit_sets, 0.f, 0, nullptr,
                       nullptr, nullptr, d_counts, (hipStream_t)stream);
-  return run_tiled(ctx, *sm, words_per_sample, d_bit_sets, 0, 0, true, 0.f, 0,
-                   nullptr, nullptr, nullptr, d_counts, (hipStream_t)stream);
+  return run_tiled(ctx, *sm, words_per_sample, d_bit_sets, 0, 0, true, 0.f,
+                   {0, nullptr, nullptr, nullptr, d_counts}, (hipStream_t)stream);
 }
 
 // ---- timing ---------------------------------------------------------------

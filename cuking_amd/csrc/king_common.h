@@ -238,11 +238,6 @@ struct TiledArgs {
   // (the tiles of a few rounds have not drifted apart yet).
   uint32_t rotate, rotate_min_steps;
   uint32_t rotate_min_tiles;  // (host side: launches of fewer tiles are not rotated)
-  // Persistent launch of the filter kernel (king_filter.hip king_filter_persistent_kernel):
-  // on entry (host side) 1 = allowed; in a launch != 0: the indices of the one-tile-per-
-  // workgroup grid that the resident workgroups take in turn before the dynamic tail.
-  uint32_t persist_wgs;
-  uint32_t persist_min_tiles;  // (host side: shorter launches go out one workgroup per tile)
   // one flag per tile of the launch chunk, directly behind the chunk's control words
   // (filter_ctrl + kCtrlChunkBytes: one memset clears both in front of a chunk)
   uint8_t *tile_done;
@@ -399,9 +394,7 @@ constexpr uint32_t kCtrlCand = 0, kCtrlDense = 1, kCtrlDyn = 2, kCtrlFinished = 
 // workgroup's turn on the XCD) mod kPosSlots at its segment ends, a new tile joins the most
 // advanced of them.
 constexpr uint32_t kCtrlStepTicks = 8, kCtrlPos = 16, kPosSlots = 16;
-// ... and behind the slots one ticket counter per XCD (persistent launch).
-constexpr uint32_t kCtrlTickets = kCtrlPos + 8 * kPosSlots * 2;
-constexpr size_t kCtrlChunkBytes = (kCtrlTickets + 16) * 4;
+constexpr size_t kCtrlChunkBytes = (kCtrlPos + 8 * kPosSlots * 2) * 4;
 constexpr uint32_t kTotalCand = 0, kTotalDense = 1, kTotalEarly = 2, kTotalRotated = 3;
 constexpr uint32_t kNumTotals = 4;
 __host__ __device__ inline const uint32_t *plane_check_steps(const uint4 *planes,
@@ -491,6 +484,7 @@ hipError_t launch_sample_stats(const uint64_t *d_bit_sets, uint32_t words_per_sa
                                uint32_t s_end, hipStream_t stream);
 // Test hook, process-wide: bitsets of fewer k-steps get no check points (default 64).
 void set_filter_check_min_steps(uint32_t steps);
+uint32_t filter_check_min_steps();
 // The sample order of plane samples [s_begin, s_end) of a kLayoutNibbleStats workspace
 // (king_sort.hip): statistics in stored order -> keys -> stable sort (or none) -> perm and
 // the statistics in plane order.  `sort_temp` / `sort_temp_bytes`: device scratch of at
@@ -514,11 +508,12 @@ hipError_t launch_mark_codes_ready(const uint32_t *gate, uint32_t *ready, hipStr
 size_t mfma_split_scratch_bytes(uint32_t wgs);
 size_t mfma_split_counter_bytes(uint32_t wgs);
 
+// Test hook: cap the workgroups per launch (0 = hardware limit only), and the cap set.
+void set_max_blocks_per_launch(uint64_t blocks);
+uint64_t max_blocks_override();
+
 // Converts plane-sample tiles [s_tile_begin, s_tile_end) (units of 64 plane
 // samples) of the block.
-// Test hook: cap the workgroups per launch (0 = hardware limit only).
-void set_max_blocks_per_launch(uint64_t blocks);
-
 hipError_t launch_prepare_planes(uint32_t layout, const uint64_t *d_bit_sets,
                                  uint32_t words_per_sample,
                                  const PlaneGeometry &geo, uint4 *d_planes,

@@ -43,8 +43,8 @@
 // (a tile starts its k loop where the tiles of its XCD are and wraps around, so
 // that they share their operands through the XCD's L2: "Rotated tiles"); tiles
 // that give up leave for a gated launch of the four-product kernel instead of
-// appending to a list; king_filter_persistent_kernel, the same launch from one
-// resident workgroup per CU (measured, off by default).
+// appending to a list.  (A persistent launch -- one resident workgroup per CU taking
+// tile after tile -- was measured 1.2 % slower and removed: r04_tile_gaps.txt.)
 //
 // Workgroup = 256 x 256 pairs, 4 wavefronts of 128 x 128 = 4 x 4 MFMA blocks (256
 // accumulator registers), k-step = 256 sites = 4 slices of 64, 5 LDS stages of
@@ -1066,43 +1066,6 @@ __global__ __launch_bounds__(256, 1) void king_filter_kernel(const TiledArgs a) 
   (void)filter_tile(a, blockIdx.x, lds);
 }
 
-// The same launch from ONE workgroup per CU that takes tile after tile (king_common.h
-// persist_wgs; option "filter_persistent", OFF by default).  A CU waits 32 us of a 430 us tile
-// for the dispatcher between two workgroups of the one-tile-per-workgroup grid
-// (profiles/r04_tile_gaps.txt: exit at the check point -> entry of the next workgroup on the same
-// CU; 160 KiB of LDS and 512 registers per workgroup) -- and yet this kernel, which does not
-// wait, runs configs[2] in 135.9-136.0 ms against 134.3-134.4 (same box, interleaved): the chip
-// is power-bound under the matrix pipes, and what an idle CU does not draw the others clock
-// on.  Kept as a measured alternative and for the tests.  The workgroups of XCD x (workgroups go to the XCDs round-robin by their index)
-// take the indices x, 8 + x, 16 + x, ... of the one-tile-per-workgroup grid through a ticket
-// counter of the XCD -- the same tiles in the same order as the dispatcher would hand them
-// out --, then the dynamic tail's tiles through its counter like everybody else.
-__global__ __launch_bounds__(256, 1) void king_filter_persistent_kernel(const TiledArgs a) {
-  extern __shared__ uint4 lds[];
-  const uint32_t x = blockIdx.x & 7;
-  bool tail = false;  // (uniform)
-  for (;;) {
-    uint32_t wg = a.launch_tiles + x;  // (an index of the dynamic tail)
-    if (!tail) {
-      uint32_t *slot = reinterpret_cast<uint32_t *>(lds);
-      if (threadIdx.x == 0)
-        *slot = __hip_atomic_fetch_add(a.filter_ctrl + kCtrlTickets + x, 1u, __ATOMIC_RELAXED,
-                                       __HIP_MEMORY_SCOPE_AGENT);
-      __syncthreads();
-      const uint32_t j = __builtin_amdgcn_readfirstlane(*slot);
-      __syncthreads();  // the word is stage memory from here on
-      if (j * 8 + x < a.persist_wgs) {
-        wg = j * 8 + x;
-      } else {
-        if (a.dyn_tiles == 0) break;
-        tail = true;
-      }
-    }
-    if (filter_tile(a, wg, lds) != 0) break;
-    __syncthreads();  // every wavefront is through with the tile's stage memory
-  }
-}
-
 // One wavefront per candidate pair: the reference's six sums (cuking.cu:219-239)
 // straight from the bitset, kinship, threshold, record (cuking.cu:284-313).
 __global__ __launch_bounds__(256) void king_refine_kernel(const TiledArgs a) {
@@ -1176,6 +1139,7 @@ __global__ __launch_bounds__(256) void king_refine_kernel(const TiledArgs a) {
 
 static std::atomic<uint32_t> g_check_min_steps{64};
 void set_filter_check_min_steps(uint32_t steps) { g_check_min_steps.store(steps); }
+uint32_t filter_check_min_steps() { return g_check_min_steps.load(); }
 
 hipError_t launch_sample_stats(const uint64_t *d_bit_sets, uint32_t words_per_sample,
                                const PlaneGeometry &geo, uint4 *d_planes, uint32_t s_begin,
@@ -1207,9 +1171,6 @@ hipError_t launch_filter(const TiledArgs &args, uint64_t num_tiles, hipStream_t 
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(king_filter_kernel),
                                        hipFuncAttributeMaxDynamicSharedMemorySize,
                                        (int)kFilterLdsBytes);
-    if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute(reinterpret_cast<const void *>(king_filter_persistent_kernel),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)kFilterLdsBytes);
     if (e != hipSuccess) return e;
     attr_set.mark();
   }
@@ -1289,15 +1250,7 @@ hipError_t launch_filter(const TiledArgs &args, uint64_t num_tiles, hipStream_t 
       e = hipMemsetAsync(args.tile_done + n_whole, 1, rest, stream);
       if (e != hipSuccess) return e;
     }
-    // On request ("filter_persistent"), launches of many rounds without remainder pieces:
-    // one resident workgroup per CU takes the grid's indices in turn.
-    a.persist_wgs = 0;
-    if (args.persist_wgs != 0 && rest == 0 && n >= args.persist_min_tiles) {
-      a.persist_wgs = (uint32_t)(a.dyn_tiles != 0 ? a.launch_tiles : grid);
-      king_filter_persistent_kernel<<<dim3(wgs), dim3(256), kFilterLdsBytes, stream>>>(a);
-    } else {
-      king_filter_kernel<<<dim3((uint32_t)grid), dim3(256), kFilterLdsBytes, stream>>>(a);
-    }
+    king_filter_kernel<<<dim3((uint32_t)grid), dim3(256), kFilterLdsBytes, stream>>>(a);
     e = hipGetLastError();
     if (e != hipSuccess) return e;
     king_refine_kernel<<<dim3(wgs * 4), dim3(256), 0, stream>>>(a);

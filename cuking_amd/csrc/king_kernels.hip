@@ -715,6 +715,7 @@ const TiledVariant kVariants[kNumTiledVariants] = {
 }  // namespace
 
 void set_max_blocks_per_launch(uint64_t blocks) { g_max_blocks_override = blocks; }
+uint64_t max_blocks_override() { return g_max_blocks_override; }
 
 uint64_t max_blocks_per_launch(uint32_t threads) {
   const uint64_t hw = 0xFFFFFFFFull / threads;

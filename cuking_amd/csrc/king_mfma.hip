@@ -33,8 +33,6 @@
 // measurements behind the choices; archive/profiles/r01_mfma_microbench.txt the
 // raw numbers.
 #include <hip/hip_runtime.h>
-#include <stdio.h>
-#include <stdlib.h>
 
 #include "king_common.h"
 #include "king_device.h"
@@ -1460,10 +1458,6 @@ hipError_t launch_mfma(bool full, bool nibble, const TiledArgs &args, uint64_t n
     if ((uint64_t)rest * tile_steps < 8ull * wgs) rest = 0;  // too little work to cut up
     whole = num_tiles - rest;
   }
-  if (getenv("CUKING_AMD_DEBUG"))
-    fprintf(stderr, "launch_mfma: tiles %llu whole %llu rest %u wgs %u scratch %p\n",
-            (unsigned long long)num_tiles, (unsigned long long)whole, rest, wgs,
-            (void *)args.split_scratch);
   TiledArgs a = args;
   a.split_tiles = 0;
   a.split_whole = 0;

@@ -179,49 +179,79 @@ typedef enum cuking_kernel {
   CUKING_KERNEL_STREAM = 1  /* one pair per wavefront, wave-level reductions */
 } cuking_kernel;
 cuking_status cuking_ctx_set_kernel(cuking_ctx *ctx, cuking_kernel kernel);
-/* Tuning knobs of the tiled kernel: "variant" (compiled kernel shape, 0 ..
- * cuking_num_variants()-1; also env CUKING_AMD_VARIANT; 0..4 are VALU
- * AND/popcount shapes, 5, 6 and 7 the matrix-core kernels: 5 = five plane
- * products on the reference's two bit planes, 6 = four plane products on one
- * fp4 code per site, 7 = the default: ONE plane product per pair as a rigorous
- * upper bound on kinship, and the reference's exact sums for the few pairs
- * that bound lets through (one wavefront per candidate pair; quadrants with
- * many candidates go to kernel 6) -- same records for any data, the bound only
- * decides who computes a pair exactly.  It applies to the lean form with
- * 0 < kin_threshold < 1/2; otherwise, and for the diagnostic counts, variant 7
- * runs kernel 6 on the quadrants of its tiles.  7 has 256-sample tiles, all
- * others 128 or 64 (cuking_tile_samples).  6 and 7 serve bitsets below 2^22
- * sites and hand wider ones to 5, which hands bitsets from 2^24 sites on to
- * VALU shape 2; the tile edge stays the context variant's), "split_wgs"
- * (matrix-core variant: short launches cut their remainder of tiles into this
- * many equal pieces, default one per CU, 0 = never), "band_rows"
- * (tile-rows per scheduling band, 1..64, 0 = chosen by block size, the default;
- * env CUKING_AMD_BAND_ROWS), "xcd_swizzle" (matrix-core variant: the
- * workgroups resident on one XCD hold consecutive tiles of the band order --
- * 2 = patches of 32 tiles dealt round-robin to the XCDs (default), 1 = one
- * contiguous chunk per XCD, 0 = off; env CUKING_AMD_XCD_SWIZZLE),
- * "dyn_tail_tiles" (matrix-core variant: launches of at least this many tiles
- * hand their last ~6 % out through a counter instead of by workgroup index, so
- * that the XCDs, which differ by 2-3 %, finish together; default 16384, 0 =
- * never; env CUKING_AMD_DYN_TAIL_TILES) and
- * "counts_mode" (0 = lean: four sums per pair in the main loop, the hom/hom
- * count behind IBS2 recounted only for emitted pairs; 1 = full: all five sums
- * for every pair; -1 = automatic: lean when kin_threshold > c / sqrt(sites), c = 2.05 (1.6 for the VALU variants),
- * i.e. when few pairs are expected to pass).  Test hooks of variant 7:
- * "filter_quadrant_cap" (candidates per 128 x 128 quadrant beyond which the
- * quadrant goes to kernel 6, default 384), "filter_cand_cap" (entries of the
- * candidate list per launch chunk, default 2^25) and "filter_split_min_steps" (k-steps
- * of 256 sites a piece of a short launch's remainder must have, default 8).
- * Results do not depend on any of them. */
+/* Options of a context, each an int64 (cuking_ctx_set_option refuses unknown keys and
+ * values out of range; cuking_ctx_get_option reads every key below).  Results do not
+ * depend on any of them.  Tuning knobs of the tiled kernel:
+ *   "variant"        compiled kernel shape, 0 .. cuking_num_variants()-1 (default also
+ *                    from env CUKING_AMD_VARIANT); 0..4 are VALU AND/popcount shapes, 5,
+ *                    6 and 7 the matrix-core kernels: 5 = five plane products on the
+ *                    reference's two bit planes, 6 = four plane products on one fp4 code
+ *                    per site, 7 = the default: ONE plane product per pair as a rigorous
+ *                    upper bound on kinship, and the reference's exact sums for the few
+ *                    pairs that bound lets through (one wavefront per candidate pair;
+ *                    quadrants with many candidates go to kernel 6) -- same records for
+ *                    any data, the bound only decides who computes a pair exactly.  It
+ *                    applies to the lean form with 0 < kin_threshold < 1/2; otherwise, and
+ *                    for the diagnostic counts, variant 7 runs kernel 6 on the quadrants
+ *                    of its tiles.  7 has 256-sample tiles, all others 128 or 64
+ *                    (cuking_tile_samples).  6 and 7 serve bitsets below 2^22 sites and
+ *                    hand wider ones to 5, which hands bitsets from 2^24 sites on to VALU
+ *                    shape 2; the tile edge stays the context variant's.
+ *   "band_rows"      tile-rows per scheduling band, 1..64, 0 = chosen by block size (default).
+ *   "counts_mode"    0 = lean: four sums per pair in the main loop, the hom/hom count behind
+ *                    IBS2 recounted only for emitted pairs; 1 = full: all five sums for
+ *                    every pair; -1 = automatic (default): lean when kin_threshold >
+ *                    c / sqrt(sites), c = 2.05 (1.6 for the VALU variants), i.e. when few
+ *                    pairs are expected to pass.
+ *   "split_wgs"      matrix-core variants: short launches cut their remainder of tiles into
+ *                    this many equal pieces, 0..4096, default one per CU, 0 = never.
+ *   "xcd_swizzle"    matrix-core variants: the workgroups resident on one XCD hold
+ *                    consecutive tiles of the band order -- 2 = patches of 32 tiles dealt
+ *                    round-robin to the XCDs (default), 1 = one contiguous chunk per XCD,
+ *                    0 = off.
+ *   "dyn_tail_tiles" matrix-core variants: launches of at least this many tiles hand their
+ *                    last ~6 % out through a counter instead of by workgroup index, so that
+ *                    the XCDs, which differ by 2-3 %, finish together; default 16384,
+ *                    0 = never.
+ *   "reuse_prepared" 0 (default) / 1: see cuking_invalidate below.
+ * Variant 7 (the filter):
+ *   "filter_sort"        0 / 1 (default) / 2: which conversions sort the samples by their
+ *                        share of missing calls (see cuking_tile_bounds below).
+ *   "filter_lazy_codes"  1 (default): kernel 6's codes are converted only when a launch hands
+ *                        it something; 0: with every conversion.
+ *   "filter_check0"      forecast check at an eighth of the sites: 0 off, 1 (default) for
+ *                        launches of fewer than 16 rounds, 2 always.
+ *   "filter_check1"      rigorous check inside the k loop: 0 off, 1 (default) the entry of
+ *                        the share menu picked from threshold and cohort, 2 + k (k = 1..7):
+ *                        entry k forced (2, entry 0, is the forecast's: refused).
+ *   "filter_check_emit"  live pairs per quadrant a tile may hand to the candidate list at
+ *                        the rigorous check and leave anyway, 0..255, default 64.
+ *   "filter_rotate"      rotated tiles: 0 off, 1 (default) a tile starts where the tiles of
+ *                        its XCD are; 2 (a phase per tile) and 3 + j (phase j, j < 128) are
+ *                        test hooks.
+ *   "filter_rotate_min_steps", "filter_rotate_min_tiles"
+ *                        bitsets of fewer k-steps of 256 sites (default 128) and launches of
+ *                        fewer tiles (default 2048) are not rotated.
+ * Test hooks that force paths ordinary cohorts do not take:
+ *   "filter_quadrant_cap"    candidates per 128 x 128 quadrant beyond which the quadrant
+ *                            goes to kernel 6, 0..16384, default 384.
+ *   "filter_cand_cap"        entries of the candidate list per launch chunk, default 2^25.
+ *   "filter_split_min_steps" k-steps of 256 sites a piece of a short launch's remainder
+ *                            must have, 1..4096, default 8.
+ *   "max_launch_blocks"      PROCESS-WIDE: workgroups per launch at most, 0 = the hardware's
+ *                            limit (default).
+ *   "filter_check_min_steps" PROCESS-WIDE: bitsets of fewer k-steps get no check points,
+ *                            4..2^20, default 64.
+ * Read-only (cuking_ctx_get_option): the counters "workspace_allocations", "host_syncs"
+ * and "conversions_skipped" (see cuking_ctx_reserve and cuking_invalidate below), and diagnostics of variant 7
+ * summed over the context's streams, which WAIT for the device: "filter_candidates"
+ * (pairs its bound has let through to the exact recount so far), "filter_dense_quadrants"
+ * (128 x 128 quadrants it has handed to kernel 6 so far), "filter_early_exits" (tiles that
+ * left at the rigorous check), "filter_rotated_tiles" (tiles that started at another phase
+ * than the first) and "filter_step_ticks16" (the 100 MHz counter's ticks per k-step x 16
+ * as the tiles of the last launch chunk measured them; 0 = none did). */
 cuking_status cuking_ctx_set_option(cuking_ctx *ctx, const char *key,
                                     int64_t value);
-/* Current value of "variant", "split_wgs", "band_rows", "xcd_swizzle",
- * "dyn_tail_tiles", "counts_mode", "reuse_prepared", "filter_quadrant_cap",
- * "filter_cand_cap" or "filter_split_min_steps"; diagnostics of variant 7 that WAIT for the device:
- * "filter_candidates" (pairs its bound has let through to the exact recount so
- * far) and "filter_dense_quadrants" (128 x 128 quadrants it has handed to kernel
- * 6 so far); read-only counters
- * "workspace_allocations", "host_syncs", "conversions_skipped". */
 cuking_status cuking_ctx_get_option(const cuking_ctx *ctx, const char *key,
                                     int64_t *value);
 int cuking_num_variants(void);

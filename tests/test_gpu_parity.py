@@ -436,8 +436,22 @@ def test_site_position_patterns(ctx, oracle, kernel, variant):
     select(ctx, "tiled", 0)
 
 
+# Every settable option (include/cuking_amd.h): a value it accepts and one it refuses.
+SETTABLE_OPTIONS = {
+    "variant": (2, 8), "band_rows": (9, 65), "counts_mode": (1, -2), "split_wgs": (0, 4097),
+    "xcd_swizzle": (0, 3), "dyn_tail_tiles": (5, 1 << 31), "reuse_prepared": (1, 2),
+    "filter_sort": (2, 3), "filter_lazy_codes": (0, -1), "filter_check0": (2, 3),
+    "filter_check1": (9, 2), "filter_check_emit": (255, 256), "filter_rotate": (130, 131),
+    "filter_rotate_min_steps": (4, 0), "filter_rotate_min_tiles": (1 << 30, (1 << 30) + 1),
+    "filter_quadrant_cap": (0, 16385), "filter_cand_cap": (7, (1 << 25) + 1),
+    "filter_split_min_steps": (4096, 0), "max_launch_blocks": (3, -1),
+    "filter_check_min_steps": (4, 3),
+}
+
+
 def test_options_round_trip(ctx):
-    """cuking_ctx_get_option reads back what set_option stored; the default
+    """cuking_ctx_get_option reads back what set_option stored, for every settable key;
+    each key refuses a value out of its range, and unknown keys are refused; the default
     kernel variant is the matrix-core one."""
     fresh = cuking_amd.KingContext(0)
     try:
@@ -449,9 +463,20 @@ def test_options_round_trip(ctx):
             fresh.set_option(key, value)
             assert fresh.get_option(key) == value
         assert fresh.tile_samples() == 128
+        for key, (good, bad) in SETTABLE_OPTIONS.items():
+            fresh.set_option(key, good)
+            assert fresh.get_option(key) == good, key
+            with pytest.raises(cuking_amd.CukingError):
+                fresh.set_option(key, bad)
+            assert fresh.get_option(key) == good, key
         with pytest.raises(cuking_amd.CukingError):
             fresh.get_option("no_such_option")
+        with pytest.raises(cuking_amd.CukingError):
+            fresh.set_option("no_such_option", 0)
     finally:
+        # (the last two are hooks of the whole process)
+        fresh.set_option("max_launch_blocks", 0)
+        fresh.set_option("filter_check_min_steps", 64)
         fresh.close()
 
 
@@ -1262,8 +1287,7 @@ def test_filter_check_points_inside_the_k_loop(ctx, oracle, missing):
     sub = np.ascontiguousarray(bits[idx])
     d_sub = ctx.upload_bitset(sub)
     defaults = {"filter_check0": 1, "filter_check1": 1, "filter_check_emit": 64,
-                "filter_rotate": 1, "filter_persistent": 0, "filter_persistent_min_tiles": 2048,
-                "filter_split_min_steps": 8,
+                "filter_rotate": 1, "filter_split_min_steps": 8,
                 "max_launch_blocks": 0, "filter_quadrant_cap": 384, "split_wgs": 256}
     ctx.set_option("filter_check_min_steps", 4)
     ctx.set_option("filter_rotate_min_steps", 4)
@@ -1290,12 +1314,8 @@ def test_filter_check_points_inside_the_k_loop(ctx, oracle, missing):
                       {"filter_rotate": 2, "filter_check0": 2, "split_wgs": 0},
                       {"filter_rotate": 2, "filter_check0": 2, "filter_check1": 0, "split_wgs": 0},
                       {"filter_rotate": 2, "filter_check0": 2, "filter_quadrant_cap": 0, "split_wgs": 0}]
-            # ... and the persistent launch (one resident workgroup per CU takes tile after
-            # tile): every second case above once more that way
-            cases += [{**c, "filter_persistent": 1, "filter_persistent_min_tiles": 0}
-                      for c in cases[3::2] if c.get("split_wgs") == 0]
             cases += [{"filter_rotate": 3 + ph, "filter_check0": c0, "filter_check1": 2 + k,
-                       "split_wgs": 0, "filter_persistent": ph & 1, "filter_persistent_min_tiles": 0}
+                       "split_wgs": 0}
                       for ph, c0, k in ((1, 0, 3), (9, 2, 1), (13, 0, 7), (31, 2, 4), (40, 0, 2),
                                         (57, 2, 5), (63, 0, 3), (63, 2, 7))]
             for opts in cases:
@@ -1363,10 +1383,8 @@ def test_filter_rotated_tiles_join_the_position_of_their_xcd(ctx, oracle):
     ctx.set_option("filter_rotate_min_tiles", 0)
     ctx.set_option("split_wgs", 0)             # whole tiles only (remainder pieces never rotate)
     try:
-        for rotate, persistent in ((1, 0), (0, 0), (1, 1), (0, 1), (1, 1)):
+        for rotate in (1, 0):
             ctx.set_option("filter_rotate", rotate)
-            ctx.set_option("filter_persistent", persistent)
-            ctx.set_option("filter_persistent_min_tiles", 0)
             r0 = ctx.get_option("filter_rotated_tiles")
             x0 = ctx.get_option("filter_early_exits")
             got = ctx.run(sm, bits.shape[1], d_bits, thr, max_results=1 << 20)
@@ -1384,7 +1402,6 @@ def test_filter_rotated_tiles_join_the_position_of_their_xcd(ctx, oracle):
     finally:
         for k, v in (("filter_check_min_steps", 64), ("filter_rotate_min_steps", 128),
                      ("filter_rotate_min_tiles", 2048), ("filter_rotate", 1), ("split_wgs", 256),
-                     ("filter_persistent", 0), ("filter_persistent_min_tiles", 2048),
                      ("counts_mode", -1)):
             ctx.set_option(k, v)
 
