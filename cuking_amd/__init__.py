@@ -8,6 +8,7 @@ from .api import (DEFAULT_KIN_THRESHOLD, DEFAULT_MAX_RESULTS,  # noqa: F401
                   KING_COUNTS_DTYPE, KING_RESULT_DTYPE, CukingError,
                   KingContext, ResourceExhaustedError, Submatrix,
                   bytes_per_pair, device_count, new_host_bitset, pack_host,
-                  padded_sites, sort_results, words_per_sample)
+                  padded_sites, sort_results, synth_model_number, synth_models,
+                  words_per_sample)
 
 __version__ = "0.1.0"

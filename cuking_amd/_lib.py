@@ -112,6 +112,10 @@ SIGNATURES = {
     "cuking_clock_probe": (_int, [_vp, _u64, _vp, _vp]),
     "cuking_synth_bitset": (_int, [_vp, _u64, _vp, _vp, _vp, _u32, _u32, _u32,
                                    _u32, _vp, _vp]),
+    "cuking_synth_num_models": (_int, []),
+    "cuking_synth_model_name": (C.c_char_p, [_int]),
+    "cuking_synth_bitset_model": (_int, [_vp, _int, _u64, _vp, _vp, _vp, _u32, _u32, _u32,
+                                         _u32, _vp, _vp]),
 }
 
 _lib = None

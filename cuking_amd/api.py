@@ -122,6 +122,24 @@ def device_count() -> int:
     return _lib.load().cuking_device_count()
 
 
+def synth_models() -> list:
+    """Names of the synthetic generator's cohort models, by number (the library's table)."""
+    lib = _lib.load()
+    return [lib.cuking_synth_model_name(k).decode() for k in range(lib.cuking_synth_num_models())]
+
+
+def synth_model_number(model) -> int:
+    """A cohort model given by number or by name -> its number; ValueError if unknown."""
+    names = synth_models()
+    if isinstance(model, str):
+        if model not in names:
+            raise ValueError(f"unknown synthetic cohort model '{model}' (known: {', '.join(names)})")
+        return names.index(model)
+    if isinstance(model, bool) or int(model) != model or not 0 <= int(model) < len(names):
+        raise ValueError(f"unknown synthetic cohort model {model!r} (0..{len(names) - 1})")
+    return int(model)
+
+
 @dataclass
 class KernelTiming:
     king_ms: float
@@ -312,16 +330,18 @@ class KingContext:
             _stream_handle(stream)))
 
     def synth_bitset(self, seed: int, kind, pa, pb, sample_begin: int,
-                     sample_end: int, num_sites: int, out=None, stream=None):
+                     sample_end: int, num_sites: int, out=None, stream=None, model=0):
         """Synthetic reference-layout bitset rows [sample_begin, sample_end)
-        (bit-identical to oracle/synth_oracle.c)."""
+        (bit-identical to oracle/synth_oracle.c).  ``model``: a cohort model of
+        the generator by number or name (``synth_models()``); 0 = "baseline"."""
         import torch
+        model = synth_model_number(model)
         wps = words_per_sample(num_sites)
         if out is None:
             out = self._tensor((sample_end - sample_begin, wps), torch.int64)
         assert out.numel() >= (sample_end - sample_begin) * wps
-        check(self.lib.cuking_synth_bitset(
-            self.handle, seed, kind.data_ptr(), pa.data_ptr(), pb.data_ptr(),
+        check(self.lib.cuking_synth_bitset_model(
+            self.handle, model, seed, kind.data_ptr(), pa.data_ptr(), pb.data_ptr(),
             sample_begin, sample_end, num_sites, wps, out.data_ptr(),
             _stream_handle(stream)))
         return out
@@ -372,6 +392,7 @@ __all__ = [
     "Submatrix", "KingContext", "KING_RESULT_DTYPE", "KING_COUNTS_DTYPE",
     "ResourceExhaustedError", "CukingError", "padded_sites",
     "words_per_sample", "bytes_per_pair", "new_host_bitset", "pack_host",
-    "sort_results", "device_count", "DEFAULT_KIN_THRESHOLD",
+    "sort_results", "device_count", "synth_models", "synth_model_number",
+    "DEFAULT_KIN_THRESHOLD",
     "DEFAULT_MAX_RESULTS",
 ]

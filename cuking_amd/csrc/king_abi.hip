@@ -144,6 +144,14 @@ struct cuking_ctx {
   void *sort_temp = nullptr;
   size_t sort_temp_bytes = 0;
 
+  // The synthetic generator's per-site and per-sample tables (synth.hip), and an event
+  // behind the last launch that reads them: a call on another stream waits for it before
+  // it rewrites them.
+  void *synth_tables = nullptr;
+  size_t synth_tables_bytes = 0;
+  hipStream_t synth_stream = nullptr;
+  hipEvent_t synth_done = nullptr;
+
   // What the plane workspace holds: the block it was converted for and which
   // 64-sample plane tiles of it have been converted (cuking_compute_king_rect
   // refuses to read anything else).
@@ -959,6 +967,8 @@ void cuking_ctx_destroy(cuking_ctx *ctx) {
   if (ctx->planes) (void)hipFree(ctx->planes);
   if (ctx->band_prefix) (void)hipFree(ctx->band_prefix);
   if (ctx->sort_temp) (void)hipFree(ctx->sort_temp);
+  if (ctx->synth_tables) (void)hipFree(ctx->synth_tables);
+  if (ctx->synth_done) (void)hipEventDestroy(ctx->synth_done);
   for (auto &e : ctx->scratch) {
     if (e.split) (void)hipFree(e.split);
     if (e.filter) (void)hipFree(e.filter);
@@ -1537,12 +1547,17 @@ cuking_status cuking_clock_probe(cuking_ctx *ctx, uint64_t microseconds,
 
 // ---- synthetic inputs -----------------------------------------------------
 
-cuking_status cuking_synth_bitset(cuking_ctx *ctx, uint64_t seed,
-                                  const uint32_t *d_kind, const uint32_t *d_pa,
-                                  const uint32_t *d_pb, uint32_t sample_begin,
-                                  uint32_t sample_end, uint32_t num_sites,
-                                  uint32_t words_per_sample,
-                                  uint64_t *d_bit_set, void *stream) {
+int cuking_synth_num_models(void) { return kNumSynthModels; }
+const char *cuking_synth_model_name(int model) { return synth_model_name(model); }
+
+cuking_status cuking_synth_bitset_model(cuking_ctx *ctx, int model, uint64_t seed,
+                                        const uint32_t *d_kind, const uint32_t *d_pa,
+                                        const uint32_t *d_pb, uint32_t sample_begin,
+                                        uint32_t sample_end, uint32_t num_sites,
+                                        uint32_t words_per_sample,
+                                        uint64_t *d_bit_set, void *stream) {
+  if (model < 0 || model >= kNumSynthModels)
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "unknown synthetic cohort model %d", model);
   cuking_status st = bind(ctx);
   if (st != CUKING_OK) return st;
   if (sample_end < sample_begin)
@@ -1553,10 +1568,30 @@ cuking_status cuking_synth_bitset(cuking_ctx *ctx, uint64_t seed,
                 num_sites);
   if (sample_end > sample_begin && (!d_kind || !d_pa || !d_pb || !d_bit_set))
     return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "null device pointer");
-  HIP_TRY(launch_synth(seed, d_kind, d_pa, d_pb, sample_begin, sample_end,
-                       num_sites, words_per_sample, d_bit_set,
-                       (hipStream_t)stream));
+  if (sample_end == sample_begin || words_per_sample == 0) return CUKING_OK;
+  st = grow(ctx, &ctx->synth_tables, &ctx->synth_tables_bytes,
+            synth_table_bytes(sample_end - sample_begin, words_per_sample));
+  if (st != CUKING_OK) return st;
+  const hipStream_t s = (hipStream_t)stream;
+  if (ctx->synth_done == nullptr)
+    HIP_TRY(hipEventCreateWithFlags(&ctx->synth_done, hipEventDisableTiming));
+  else if (ctx->synth_stream != s)
+    HIP_TRY(hipStreamWaitEvent(s, ctx->synth_done, 0));
+  HIP_TRY(launch_synth(model, seed, d_kind, d_pa, d_pb, sample_begin, sample_end,
+                       num_sites, words_per_sample, ctx->synth_tables, d_bit_set, s));
+  HIP_TRY(hipEventRecord(ctx->synth_done, s));
+  ctx->synth_stream = s;
   return CUKING_OK;
+}
+
+cuking_status cuking_synth_bitset(cuking_ctx *ctx, uint64_t seed,
+                                  const uint32_t *d_kind, const uint32_t *d_pa,
+                                  const uint32_t *d_pb, uint32_t sample_begin,
+                                  uint32_t sample_end, uint32_t num_sites,
+                                  uint32_t words_per_sample,
+                                  uint64_t *d_bit_set, void *stream) {
+  return cuking_synth_bitset_model(ctx, kSynthBaseline, seed, d_kind, d_pa, d_pb, sample_begin,
+                                   sample_end, num_sites, words_per_sample, d_bit_set, stream);
 }
 
 }  // extern "C"

@@ -537,11 +537,17 @@ hipError_t launch_pack_compact(uint32_t words_per_sample, uint32_t num_samples,
                                const uint32_t *d_sample_alt, size_t num_triples,
                                uint32_t *d_status, hipStream_t stream);
 
-hipError_t launch_synth(uint64_t seed, const uint32_t *d_kind,
+// Cohort models of the synthetic generator (synth.hip holds the specification).  d_tables:
+// synth_table_bytes() of scratch the launch fills and reads (per-site and per-sample
+// tables); it must stay untouched until the launch has run.
+enum { kSynthBaseline = 0, kSynthExome = 1, kSynthAdmixed = 2, kNumSynthModels = 3 };
+const char *synth_model_name(int model);
+size_t synth_table_bytes(uint32_t num_rows, uint32_t words_per_sample);
+hipError_t launch_synth(int model, uint64_t seed, const uint32_t *d_kind,
                         const uint32_t *d_pa, const uint32_t *d_pb,
                         uint32_t sample_begin, uint32_t sample_end,
                         uint32_t num_sites, uint32_t words_per_sample,
-                        uint64_t *d_bit_set, hipStream_t stream);
+                        void *d_tables, uint64_t *d_bit_set, hipStream_t stream);
 
 hipError_t launch_clock_probe(uint64_t microseconds, uint64_t *d_out,
                               hipStream_t stream);

@@ -528,12 +528,14 @@ Status SynthesiseCohort(Job *job) {
   if (st == CUKING_OK) st = cuking_copy_to_device(buf.ctx, d_pb, plan.pb.data(), plan_bytes, nullptr);
   uint64_t *d_bits = static_cast<uint64_t *>(buf.d_bits);
   if (st == CUKING_OK)
-    st = cuking_synth_bitset(buf.ctx, flags.synth_seed, d_kind, d_pa, d_pb, sm.i_begin, sm.i_end,
-                             job->metadata.num_sites, words_per_sample, d_bits, nullptr);
+    st = cuking_synth_bitset_model(buf.ctx, flags.synth_model, flags.synth_seed, d_kind, d_pa,
+                                   d_pb, sm.i_begin, sm.i_end, job->metadata.num_sites,
+                                   words_per_sample, d_bits, nullptr);
   if (st == CUKING_OK && sm.i_begin != sm.j_begin)
-    st = cuking_synth_bitset(buf.ctx, flags.synth_seed, d_kind, d_pa, d_pb, sm.j_begin, sm.j_end,
-                             job->metadata.num_sites, words_per_sample,
-                             d_bits + (size_t)(sm.i_end - sm.i_begin) * words_per_sample, nullptr);
+    st = cuking_synth_bitset_model(
+        buf.ctx, flags.synth_model, flags.synth_seed, d_kind, d_pa, d_pb, sm.j_begin, sm.j_end,
+        job->metadata.num_sites, words_per_sample,
+        d_bits + (size_t)(sm.i_end - sm.i_begin) * words_per_sample, nullptr);
   if (st == CUKING_OK) st = cuking_stream_synchronize(buf.ctx, nullptr);
   cuking_device_free(buf.ctx, d_plan);
   return FromAbi(st);
@@ -874,6 +876,9 @@ Status WriteOutput(Job *job) {
             << packer_stats.narrow_us.load() * 1e-6 << ", \"enqueue\": "
             << packer_stats.enqueue_us.load() * 1e-6 << "}"
             << ", \"pack\": \"" << (job->synthetic ? "synthetic" : job->pack_mode)
+            << (job->synthetic ? std::string("\", \"synthetic_model\": \"") +
+                                     cuking_synth_model_name(flags.synth_model)
+                               : std::string())
             << "\", \"decode\": \"" << (flags.decode != "table" ? "stream" : "table")
             << "\", \"decode_tasks\": " << job->tasks.size() << ", \"reader_threads\": "
             << flags.num_reader_threads << ", \"read_pack_seconds\": " << read_pack_seconds
@@ -935,6 +940,16 @@ int main(int argc, char **argv) {
   if (flags.help) {
     std::cout << cuking_host::Usage();
     return 0;
+  }
+  if (!flags.synthetic_model.empty()) {  // the names live in the library, for both hosts
+    flags.synth_model = -1;
+    for (int k = 0; k < cuking_synth_num_models(); ++k)
+      if (flags.synthetic_model == cuking_synth_model_name(k)) flags.synth_model = k;
+    if (flags.synth_model < 0) {
+      std::cerr << "ERROR: Illegal value '" << flags.synthetic_model
+                << "' specified for flag 'synthetic_model'" << std::endl;
+      return 1;
+    }
   }
   if (flags.variant >= 0) {
     // The library reads its default variant from the environment wherever it needs one --

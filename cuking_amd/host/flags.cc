@@ -80,6 +80,10 @@ std::string Usage() {
          "process with exit code 1, naming every rank's phase (default 1800; 0 = no limit)\n"
          "  --synthetic=N,M[,SEED] instead of --input_uri: synthetic cohort of N samples x M "
          "sites generated on the GPU (founders + planted relatives)\n"
+         "  --synthetic_model=NAME cohort model of --synthetic: baseline (default; allele "
+         "frequency uniform on [0.05, 0.5), 1 % missing), exome (log-uniform frequency from "
+         "2^-13, most sites rare) or admixed (the exome spectrum in two ancestries, call rate "
+         "per sample with a tail of poor samples)\n"
          "  --print_schedule       diagnostic: print the multi-GPU schedule (JSON) and "
          "exit before any GPU work\n"
          "  --dump_bitset=FILE     diagnostic: write the packed bitset (raw "
@@ -191,6 +195,9 @@ std::string ParseFlags(int argc, char **argv, Flags *flags) {
       flags->synth_samples = (uint32_t)parts[0];
       flags->synth_sites = (uint32_t)parts[1];
       flags->synth_seed = parts[2];
+    } else if (name == "synthetic_model") {
+      if (!need_value()) return "Missing value for --synthetic_model";
+      flags->synthetic_model = value;
     } else if (name == "print_schedule") {
       if (has_value && value != "true" && value != "1")
         return "Illegal value '" + value + "' specified for flag 'print_schedule'";
@@ -265,6 +272,8 @@ std::string ParseFlags(int argc, char **argv, Flags *flags) {
 }
 
 std::string ValidateFlags(const Flags &f) {
+  if (!f.synthetic_model.empty() && f.synthetic.empty())
+    return "--synthetic_model needs --synthetic";
   if (f.input_uri.empty() && f.synthetic.empty())
     return "No input URI specified";                                 // :438-440
   if (f.output_uri.empty()) return "No output URI specified";        // :444-446

@@ -64,6 +64,10 @@ struct Flags {
   std::string synthetic;
   uint32_t synth_samples = 0, synth_sites = 0;
   uint64_t synth_seed = 20240229;
+  // Cohort model of --synthetic, by name; cuking_main.cc resolves it through the library's
+  // table (cuking_synth_model_name) into synth_model.
+  std::string synthetic_model;
+  int synth_model = 0;
   bool print_schedule = false;          // diagnostic: print the multi-GPU
                                         // schedule as JSON and exit (no GPU used)
   bool help = false;

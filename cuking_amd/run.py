@@ -53,6 +53,9 @@ def parse_args(argv=None):
          help="N,M[,seed]: instead of reading --input-uri, generate the synthetic cohort of "
               "cuking_amd.synth on the GPU (BASELINE configs without their 10^9..10^11-row "
               "Parquet form)")
+    flag("synthetic-model", default="",
+         help="cohort model of --synthetic: baseline (default), exome or admixed "
+              "(csrc/synth.hip holds the specification)")
     return ap.parse_args(argv)
 
 
@@ -68,6 +71,8 @@ def resolve_uri(uri: str) -> Path:
 
 
 def validate(args):  # cuking.cu:437-462
+    if args.synthetic_model and not args.synthetic:
+        raise UsageError("--synthetic_model needs --synthetic")
     if not args.input_uri and not args.synthetic:
         raise UsageError("No input URI specified")
     if not args.output_uri:
@@ -159,6 +164,13 @@ def main(argv=None) -> int:
             if len(parts) not in (2, 3) or min(parts[:2]) <= 0:
                 raise UsageError("--synthetic expects N,M[,seed]")
             synthetic = (parts[0], parts[1], parts[2] if len(parts) == 3 else 20240229)
+        synth_model = 0
+        if args.synthetic_model:  # (host-only: the names live in the library)
+            names = cuking_amd.synth_models()
+            if args.synthetic_model not in names:
+                raise UsageError(f"Illegal value '{args.synthetic_model}' specified for flag "
+                                 "'synthetic_model'")
+            synth_model = names.index(args.synthetic_model)
     except ValueError:
         if rank == 0:
             print("\nError: INVALID_ARGUMENT: --synthetic expects N,M[,seed]", file=sys.stderr)
@@ -198,10 +210,11 @@ def main(argv=None) -> int:
                                                     local_rank)
                     # the block's samples, rows first then columns (cuking.cu:171-175)
                     ctx.synth_bitset(synthetic[2], kind, pa, pb, sm.i_begin, sm.i_end,
-                                     num_sites, out=bits[:sm.NumRows()])
+                                     num_sites, out=bits[:sm.NumRows()], model=synth_model)
                     if sm.i_begin != sm.j_begin:
                         ctx.synth_bitset(synthetic[2], kind, pa, pb, sm.j_begin, sm.j_end,
-                                         num_sites, out=bits[sm.NumRows():stored])
+                                         num_sites, out=bits[sm.NumRows():stored],
+                                         model=synth_model)
                     torch.cuda.synchronize()
                 else:
                     host = read_and_pack(in_dir, sm, num_sites, args.num_reader_threads)

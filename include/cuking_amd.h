@@ -440,13 +440,36 @@ cuking_status cuking_clock_probe(cuking_ctx *ctx, uint64_t microseconds,
  * Hardy-Weinberg genotypes (per-site AF ~ U(0.05,0.5), 1 % missing) and the
  * planted relatives described by kind/pa/pb (device arrays of num_samples
  * u32 each; 0 founder, 1 duplicate of pa, 2 child of pa x pb).  Row 0 of
- * d_bit_set is sample_begin.  Bit-identical to oracle/synth_oracle.c. */
+ * d_bit_set is sample_begin.  Bit-identical to oracle/synth_oracle.c.  The same
+ * as cuking_synth_bitset_model with model 0. */
 cuking_status cuking_synth_bitset(cuking_ctx *ctx, uint64_t seed,
                                   const uint32_t *d_kind, const uint32_t *d_pa,
                                   const uint32_t *d_pb, uint32_t sample_begin,
                                   uint32_t sample_end, uint32_t num_sites,
                                   uint32_t words_per_sample,
                                   uint64_t *d_bit_set, void *stream);
+
+/* Named cohort models of the generator, 0 .. cuking_synth_num_models()-1 (integer
+ * arithmetic only; csrc/synth.hip holds the specification, DESIGN.md 4.4 the reasons):
+ *   0 "baseline"  the cohort above
+ *   1 "exome"     a rare-variant spectrum: AF log-uniform on [2^-13, 1/2), 1 % missing
+ *   2 "admixed"   that spectrum in two ancestries whose frequencies differ at one site
+ *                 in four, and a call rate per sample: 0.5 % .. 3.5 % missing, one
+ *                 sample in a hundred 10 % .. 30 %
+ * cuking_synth_model_name gives "" outside the range. */
+int cuking_synth_num_models(void);
+const char *cuking_synth_model_name(int model);
+/* cuking_synth_bitset for cohort model `model`: same arguments, same checks, and
+ * CUKING_ERR_INVALID_ARGUMENT for a model outside the range.  The planted relatives
+ * apply to every model.  Small per-site and per-sample tables live in scratch of the
+ * context; calls on different streams are ordered by the library where one would
+ * rewrite them.  Asynchronous on `stream`. */
+cuking_status cuking_synth_bitset_model(cuking_ctx *ctx, int model, uint64_t seed,
+                                        const uint32_t *d_kind, const uint32_t *d_pa,
+                                        const uint32_t *d_pb, uint32_t sample_begin,
+                                        uint32_t sample_end, uint32_t num_sites,
+                                        uint32_t words_per_sample,
+                                        uint64_t *d_bit_set, void *stream);
 
 #ifdef __cplusplus
 }

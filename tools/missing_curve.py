@@ -7,6 +7,12 @@ every rate: kernel time per pass of both variants (HIP events around the whole c
 filter + refine + dense-quadrant kernels), candidates, dense quadrants -- and the records
 of the two variants compared byte for byte.
 
+COHORT_MODEL=exome|admixed|baseline replaces the base cohort by that model of the generator
+(csrc/synth.hip); the lines then also count the tiles that left at the check point, and the
+output goes to a file of the model's own, missing_curve_<model>_<samples>x<sites>.txt in the
+directory CURVE_OUT_DIR (default: the current directory), so that runs do not overwrite each
+other.
+
 usage: [MISSING_KS=0,3] [MISSING_HETERO=0.02,2] [MISSING_RELATED=0.25] python tools/missing_curve.py [samples] [sites] [threshold ...]
        -> gpurun_out/missing_curve.txt
 """
@@ -87,7 +93,7 @@ def run(ctx, variant, sm, wps, bits, thr, steps=5, warmup=1):
     return t.king_ms / max(t.king_launches, 1), recs, filt
 
 
-def main():
+def setup():
     n = int(sys.argv[1]) if len(sys.argv) > 1 else 10000
     m = int(sys.argv[2]) if len(sys.argv) > 2 else 100000
     thrs = [float(x) for x in sys.argv[3:]] or [0.0884, 0.0442]
@@ -98,17 +104,36 @@ def main():
     sm = cuking_amd.Submatrix(n)
     cohort = plan_cohort(n, SEED)
     kind, pa, pb = cohort_to_device(cohort, 0)
-    base = ctx.synth_bitset(SEED, kind, pa, pb, 0, n, m)
+    model = os.environ.get("COHORT_MODEL", "")
+    base = ctx.synth_bitset(SEED, kind, pa, pb, 0, n, m, model=model or 0)
     gen = torch.Generator(device="cuda:0")
     gen.manual_seed(7)
+    return ctx, sm, wps, n, m, thrs, base, gen, model
+
+
+def default_output():
     out = open("gpurun_out/missing_curve.txt", "w")
+    return out
+
+
+def model_output(model, n, m):
+    return open(os.path.join(os.environ.get("CURVE_OUT_DIR", "."),
+                             f"missing_curve_{model}_{n}x{m}.txt"), "w")
+
+
+def main():
+    ctx, sm, wps, n, m, thrs, base, gen, model = setup()
+    out = model_output(model, n, m) if model else default_output()
 
     def say(s):
         print(s, flush=True)
         out.write(s + "\n")
         out.flush()
 
-    say(f"# {n} samples x {m} sites, synthetic cohort (1 % missing) + extra missing calls of density 2^-k;")
+    if model:
+        say(f"# {n} samples x {m} sites, cohort model '{model}' + extra missing calls of density 2^-k;")
+    else:
+        say(f"# {n} samples x {m} sites, synthetic cohort (1 % missing) + extra missing calls of density 2^-k;")
     say("# lean form forced; kernel_ms = HIP events around the whole call; records of variants 7 and 6 compared")
     ks = [int(x) for x in os.environ.get("MISSING_KS", "0,6,5,4,3,2").split(",")]
     for k in ks:
@@ -119,11 +144,15 @@ def main():
         both = (het & hom).cpu().numpy().view(np.uint64)
         rate = float(np.unpackbits(both.view(np.uint8)).mean())
         for thr in thrs:
+            e0 = ctx.get_option("filter_early_exits")
             ms7, r7, filt = run(ctx, 7, sm, wps, bits, thr)
+            exits = (ctx.get_option("filter_early_exits") - e0) / 6   # 1 warm-up + 5 passes
+            left = f" tiles_left_at_the_check {exits:.0f} of {ctx.num_tiles(sm)}" if model else ""
             ms6, r6, _ = run(ctx, 6, sm, wps, bits, thr)
             same = r7.tobytes() == r6.tobytes()
             say(f"missing {rate:.4f} thr {thr} variant 7 kernel_ms {ms7:.3f} variant 6 kernel_ms {ms6:.3f} "
-                f"records {len(r7)} equal {same} candidates {filt[0]:.1f} dense_quadrants {filt[1]:.1f}")
+                f"records {len(r7)} equal {same} candidates {filt[0]:.1f} dense_quadrants {filt[1]:.1f}"
+                f"{left}")
             if not same:
                 raise SystemExit("variants disagree")
         del bits
