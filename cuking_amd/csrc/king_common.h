@@ -54,9 +54,13 @@ constexpr uint32_t kLayoutNibble = 2;
 // copy: the T2 layout -- T = hom-ref minus hom-alt alone, TWO bits per site (hom,
 // hom-alt), for every unit u of 64 sites and sample s one uint4, t2[u * s_stride
 // + s]: nibble t of dword d holds site 64 u + 8 d + t in bits 2-3 (code 0100 /
-// 1100 = +-2.0 after `& 0xCCCCCCCC`) and site 64 u + 32 + 8 d + t in bits 0-1 (the
-// same code after `<< 2`), half the bytes of the codes -- and one float2 per stored
-// sample: (homozygous - missing site count, het count).
+// 1100 = +-2.0 after `& 0xCCCCCCCC`) and site 64 u + 32 + 8 d + t in bits 0-1 as the
+// OFFSET 1 + T in plain binary (hom-alt 00, het / missing / padding 01, hom-ref 10:
+// the fp4 values 0 / 0.5 / 1.0 = (1 + T) / 2 after `& 0x33333333`, no shift; the
+// filter kernel takes the offset out again per sample, king_filter.hip "Offset
+// code"), half the bytes of the codes -- and one float2 per plane sample: (u~ =
+// homozygous - missing site count + 2 S + n_A, het count), S = the sum of T over the
+// sites in bits 0-1, n_A their number.
 constexpr uint32_t kLayoutNibbleStats = 3;
 
 struct PlaneGeometry {
@@ -308,7 +312,7 @@ __host__ __device__ inline size_t plane_bytes(const PlaneGeometry &g,
     return base + base / 4 + base / 2 + (size_t)g.s_stride * sizeof(float2) +
            (size_t)g.s_stride * kNumCum * sizeof(float) + 64 + 64 +
            // control block, perm, statistics before the sort, the sort's four arrays
-           64 + (size_t)g.s_stride * (4 + 8 + 4 * kNumCum + 16);
+           64 + (size_t)g.s_stride * (4 + 8 + 4 * (kNumCum + 1) + 16);
   return base;
 }
 // Where the T2 layout and the per-sample statistics of kLayoutNibbleStats start
@@ -354,6 +358,14 @@ constexpr int kMfmaN4Variant = 6;  // four plane products, nibble layout (king_m
 // of that is exact, i.e. below 2^22 sites (include/cuking_amd.h, numerics
 // contract); wider bitsets take the five-product variant.
 constexpr uint32_t kMfmaN4MaxSites = 1u << 22;
+// The filter kernel's sums (king_filter.hip "Offset code") in units of their steps: the
+// accumulators count quarters up to 2.5 per site, u~_i - 8 acc is an integer up to 3.5
+// per site, the value tested one up to 4 per site -- each an exact float up to 2^24.  The
+// per-sample u~ = u + 2 S + n_A over any set of sites is at most 2.5 per site, and so is every
+// partial of the range differences the kernel forms from the cumulative table (king_filter.hip
+// prefix_u_of: a wrapped range is (total - front) + wrapped end, never total + wrapped end,
+// which would reach 5 per site).
+static_assert(4ull * kMfmaN4MaxSites <= (1ull << 24), "filter kernel: exact float sums");
 constexpr int kMfmaN4Stages = 5;
 constexpr uint32_t kMfmaN4LdsBytes = kMfmaN4Stages * 2 * 2 * 4 * 128 * 16;  // 5 x 32 KiB
 static_assert(kMfmaN4LdsBytes <= 160 * 1024, "LDS of one CU");
@@ -403,8 +415,8 @@ __host__ __device__ inline const uint32_t *plane_check_steps(const uint4 *planes
 }
 // ... one control block (16 u32; word 0: codes_ready), then the sample order and what
 // building it needs, every array s_stride entries long: perm (u32), the statistics in
-// stored order before the sort (float2, then kNumCum floats), keys in / out and
-// values in / out of the sort (u32 each).
+// stored order before the sort (float2 (u, |H|), then kNumCum + 1 floats: u~ cumulative
+// and over all sites), keys in / out and values in / out of the sort (u32 each).
 __host__ __device__ inline uint32_t *plane_flags(const uint4 *planes, const PlaneGeometry &g) {
   return const_cast<uint32_t *>(plane_check_steps(planes, g)) + 16;
 }
@@ -419,7 +431,7 @@ __host__ __device__ inline float *plane_tmp_prefix(const uint4 *planes, const Pl
 }
 __host__ __device__ inline uint32_t *plane_sort_words(const uint4 *planes, const PlaneGeometry &g) {
   return reinterpret_cast<uint32_t *>(plane_tmp_prefix(planes, g) +
-                                      (size_t)g.s_stride * kNumCum);
+                                      (size_t)g.s_stride * (kNumCum + 1));
 }
 constexpr uint32_t kNoSample = 0xFFFFFFFFu;
 

@@ -22,9 +22,9 @@
 // the usual thresholds (>= 0.04) next to nothing but real records gets through.
 //
 // Pipeline per launch chunk (<= kFilterChunkTiles tiles of 256 x 256 pairs):
-//   1. king_filter_kernel: q for every pair on the matrix cores (T from the
-//      two-bit T2 layout, king_common.h: +-2.0 in fp4 after one v_and -- or a
-//      shift and a v_and -- per fragment dword; the accumulators carry 4 q), the
+//   1. king_filter_kernel: q for every pair on the matrix cores (from the
+//      two-bit T2 layout, king_common.h: one v_and per fragment dword for either
+//      site set; "Offset code" below says what the accumulators carry), the
 //      test above per pair; candidates are appended to a list, or, when a 128 x
 //      128 quadrant has more than quadrant_cap of them (or the list is full), the
 //      quadrant is put on the dense list.  Once most finished quadrants of a
@@ -37,6 +37,25 @@
 // Same records as every other variant, whatever the data: the bound only
 // decides WHO computes a pair exactly.
 //
+// Offset code.  A T2 nibble holds two sites.  Set B (bits 2-3) is T in the fp4
+// sign / magnitude code, +-2.0 after `& 0xCCCCCCCC`.  Set A (bits 0-1) is 1 + T in
+// plain binary, which `& 0x33333333` leaves as the fp4 values a' = (1 + T) / 2 = 0 /
+// 0.5 / 1.0 -- no shift.  A set-A product weighs 1/4, a set-B product 4; the set-B
+// MFMAs are the SCALED form of the same instruction with the exact E8M0 scale 2^-2 on
+// either operand (byte 0x7D), so that one accumulator holds
+//     acc = sum_B T_i T_j / 4 + sum_A a'_i a'_j = (q + n_A + S_i + S_j) / 4,
+// S = the sample's sum of T over the set-A sites of the range, n_A their number.  With
+// u~ = u + 2 S + n_A per sample (sample_stats_kernel) the value every test needs is
+//     u_i + u_j - 2 q = u~_i + u~_j - 8 acc,
+// evaluated as (u~_i - 8 acc) + u~_j: acc is a multiple of 1/4 of magnitude <= 2.5
+// sites / 4, u~_i - 8 acc = u_i - n_A - 2 S_j - 2 q an integer of magnitude <= 3.5
+// sites, the result one of <= 4 sites -- all exact floats up to 2^22 sites
+// (kMfmaN4MaxSites), so the value tested is the same float as u_i + u_j - 2 q computed
+// from q itself.  u~, S and n_A are sums over sites: prefixes, phase ranges, the wrap of
+// a rotated tile and the k-pieces of a split remainder work on differences and sums of
+// them like on u -- as long as every partial of such a difference is itself u~ over a
+// set of sites (<= 2.5 per site): prefix_u_of() subtracts before it adds the wrapped end.
+//
 // Round 4, all inside filter_tile() below: check points inside the k loop (a tile
 // none of whose pairs can still become a candidate leaves, and so does one that
 // holds a few, handing them to the candidate list: "Check points"); rotated tiles
@@ -48,8 +67,8 @@
 //
 // Workgroup = 256 x 256 pairs, 4 wavefronts of 128 x 128 = 4 x 4 MFMA blocks (256
 // accumulator registers), k-step = 256 sites = 4 slices of 64, 5 LDS stages of
-// 32 KiB by LDS-DMA.  Per k-step and wavefront: 64 MFMAs, 16 ds_read_b128, 192
-// VALU (128 v_and + 64 v_lshl), 8 requests of 1 KiB.  DESIGN.md 4.0 has the
+// 32 KiB by LDS-DMA.  Per k-step and wavefront: 64 MFMAs (32 of them scaled), 16
+// ds_read_b128, 128 VALU (v_and), 8 requests of 1 KiB.  DESIGN.md 4.0 has the
 // measurements; profiles/r03_ablation.txt, r03_filter_curve.txt, r04_l2_probe.txt and
 // r04_tile_gaps.txt the raw numbers.
 #include <hip/hip_runtime.h>
@@ -96,13 +115,19 @@ __device__ __forceinline__ uint32_t source_sample(const PlaneGeometry &geo, uint
   return c < geo.num_cols ? geo.num_rows + c : kNoPair;
 }
 
-// One wavefront per plane sample: (|Y| - |M|, |H|) as floats (exact below 2^24
-// sites).  Padding sites of the last word are missing (cuking.cu:513-523) and
-// count as such; padding samples get (0, 0).  Beside them the same |Y| - |M|
-// CUMULATIVE at every phase boundary of the k-steps (king_common.h phase_step:
-// cum[x - 1][sample] = over the first 256 phase_step(x) sites, x = 1 .. 127) -- what a
-// check point of a tile that started at any phase needs --, and the cohort's sums
-// (samples, missing calls, het calls) the kernel picks a check from.
+// One wavefront per plane sample: (u, |H|) = (|Y| - |M|, |H|) as floats (exact below
+// 2^24 sites) -- what the sample order is built from.  Padding sites of the last word
+// are missing (cuking.cu:513-523) and count as such; padding samples get (0, 0).
+// Beside them what the pair test reads ("Offset code" below):
+//     u~ = u + 2 S + n_A,   S = the sample's sum of T over the set-A sites (the high
+//     32 sites of every 64: the low fields of the T2 layout), n_A = their number
+//     (128 per k-step, padding sites included: T = 0 there),
+// over all sites (row kNumCum of `cum`) and CUMULATIVE at every phase boundary of the
+// k-steps (king_common.h phase_step: cum[x - 1][sample] = over the first 256
+// phase_step(x) sites, x = 1 .. 127) -- what a check point of a tile that started at any
+// phase needs; u, S and n_A are sums over sites, so differences of u~ serve every range
+// --, and the cohort's sums (samples, missing calls, het calls) the kernel picks a check
+// from.
 struct CheckWords {
   uint32_t w[kNumCheckShares];  // k-steps behind each share from the first site on (0: no checks)
 };
@@ -112,7 +137,7 @@ __global__ __launch_bounds__(256) void sample_stats_kernel(
     float2 *__restrict__ stats, float *__restrict__ cum, unsigned long long *__restrict__ sums,
     uint32_t *__restrict__ steps_out, CheckWords cw, uint32_t s_begin, uint32_t s_end) {
   __shared__ uint8_t phase_of[kStatsMaxSteps];  // the phase a k-step belongs to
-  __shared__ int32_t phase_sum[4][kNumPhases];  // per wavefront: |Y| - |M| per phase
+  __shared__ int32_t phase_sum[4][kNumPhases];  // per wavefront: |Y| - |M| + 2 S per phase
   const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   if (blockIdx.x == 0 && threadIdx.x < kNumCheckShares) steps_out[threadIdx.x] = cw.w[threadIdx.x];
   const uint32_t all_steps = geo.k_words / 8;  // k-steps of 256 sites
@@ -128,7 +153,7 @@ __global__ __launch_bounds__(256) void sample_stats_kernel(
   const uint32_t ps = s_begin + blockIdx.x * 4 + wave;
   if (ps >= s_end) return;  // whole wavefront
   const uint32_t src = source_sample(geo, ps);
-  int32_t yc = 0, mc = 0, hc = 0;
+  int32_t yc = 0, mc = 0, hc = 0, sa = 0;
   if (src != kNoPair) {
     const uint32_t n = words_per_sample / 2;
     const uint64_t *het = bits + (uint64_t)src * words_per_sample;
@@ -154,7 +179,11 @@ __global__ __launch_bounds__(256) void sample_stats_kernel(
         hc += __popcll(h[k] & ~v[k]);  // het
         // (a k-step is 4 words of 64 sites = 4 neighbouring lanes: their sum first, then ONE
         //  LDS add per k-step -- a dozen lanes share a phase)
-        int32_t d = y - m;
+        // T over the set-A sites of the word: hom-ref minus hom-alt
+        const uint64_t hom_a = in ? ~h[k] & 0xFFFFFFFF00000000ull : 0ull;
+        const int32_t t_a = __popcll(hom_a & ~v[k]) - __popcll(hom_a & v[k]);
+        sa += t_a;
+        int32_t d = y - m + 2 * t_a;
         d += __shfl_xor(d, 1);
         d += __shfl_xor(d, 2);
         if ((lane & 3) == 0 && in) atomicAdd(&phase_sum[wave][phase_of[w >> 2]], d);
@@ -165,6 +194,7 @@ __global__ __launch_bounds__(256) void sample_stats_kernel(
       yc += __shfl_xor(yc, off);
       mc += __shfl_xor(mc, off);
       hc += __shfl_xor(hc, off);
+      sa += __shfl_xor(sa, off);
     }
   }
   // (the wavefront's own LDS adds are done: same wavefront, in order) inclusive scan over
@@ -178,10 +208,15 @@ __global__ __launch_bounds__(256) void sample_stats_kernel(
     const int32_t up = __shfl_up(run, off);
     if ((int)lane >= off) run += up;
   }
-  cum[(size_t)(2 * lane) * geo.s_stride + ps] = (float)(run - p1);
-  if (2 * lane + 1 < kNumCum) cum[(size_t)(2 * lane + 1) * geo.s_stride + ps] = (float)run;
+  // (n_A in front of boundary x: 128 per k-step)
+  cum[(size_t)(2 * lane) * geo.s_stride + ps] =
+      (float)(run - p1 + (int32_t)(128u * phase_step(all_steps, 2 * lane + 1)));
+  if (2 * lane + 1 < kNumCum)
+    cum[(size_t)(2 * lane + 1) * geo.s_stride + ps] =
+        (float)(run + (int32_t)(128u * phase_step(all_steps, 2 * lane + 2)));
   if (lane == 0) {
     stats[ps] = make_float2((float)(yc - mc), (float)hc);
+    cum[(size_t)kNumCum * geo.s_stride + ps] = (float)(yc - mc + 2 * sa + (int32_t)(128u * all_steps));
     // (the cohort's sums feed a choice, not a result: a sample of the samples will do --
     //  three device-scope atomics on three addresses for EVERY sample cost 3 ms at 100k)
     if (src != kNoPair && ((blockIdx.x & 15) == 0 || gridDim.x < 64)) {
@@ -199,6 +234,11 @@ __device__ __forceinline__ v16f mma(const v8i a, const v8i b, const v16f c) {
   return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, b, c, 4 /* fp4 */, 4, 0, 0, 0, 0);
 }
 
+// The scaled form: both operands times the E8M0 scale in byte 0 of `scale` (a VGPR).
+__device__ __forceinline__ v16f mma_scaled(const v8i a, const v8i b, const v16f c, const int scale) {
+  return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, b, c, 4 /* fp4 */, 4, 0, scale, 0, scale);
+}
+
 __device__ __forceinline__ v8i tfrag(const uint4 w, uint32_t mask) {
   v8i r = {0, 0, 0, 0, 0, 0, 0, 0};
   r[0] = (int)(w.x & mask);
@@ -206,10 +246,6 @@ __device__ __forceinline__ v8i tfrag(const uint4 w, uint32_t mask) {
   r[2] = (int)(w.z & mask);
   r[3] = (int)(w.w & mask);
   return r;
-}
-
-__device__ __forceinline__ uint4 shl2(const uint4 w) {
-  return make_uint4(w.x << 2, w.y << 2, w.z << 2, w.w << 2);
 }
 
 // One LDS-DMA request: lane l's 16 bytes of SRC + OFF land at DST + OFF + 16 l
@@ -367,8 +403,14 @@ __device__ __forceinline__ int filter_tile(const TiledArgs &a, const uint32_t wg
   const uint4 *g_rows = a.t2 + (uint64_t)tr * kT;
   const uint4 *g_cols = a.t2 + a.geo.col_base + (uint64_t)tc * kT;
 
-  uint32_t mT;
+  // The masks of the two site sets of a T2 word and the scale of set B (king_common.h:
+  // +-2.0 x 2^-2 per operand, so that a set-B product weighs 1/4 like a set-A product),
+  // set once and pinned.
+  uint32_t mT, mA;
   asm volatile("s_mov_b32 %0, 0xcccccccc" : "=s"(mT));
+  asm volatile("s_mov_b32 %0, 0x33333333" : "=s"(mA));
+  int scaleB;
+  asm volatile("v_mov_b32 %0, 0x7d7d7d7d" : "=v"(scaleB));
 
   // LDS-DMA: wavefront (side, k-half) fetches that quarter of a stage: 2 units x
   // 4 runs of 64 samples, 1 KiB each.  Unit c of k-step s, k-half h is unit
@@ -437,7 +479,7 @@ __device__ __forceinline__ int filter_tile(const TiledArgs &a, const uint32_t wg
   uint4 RAW[8];            // the words of one unit: rows 0-3, columns 4-7
 #define F_READ(K, BUF, C)                                                      \
   RAW[K] = lds[(BUF) * kStageU4 + ((K) < 4 ? row_off : col_off) + (C) * kSliceU4 + ((K) & 3) * 32];
-// (plain ANDs and shifts: nothing but data orders them against the MFMAs, and
+// (plain ANDs: nothing but data orders them against the MFMAs, and
 // left alone the compiler builds every fragment right behind its LDS read, i.e.
 // waits for the read it has just issued.  The empty asm statements tie a build
 // to the place it is written in: not above the pin of its input, not below the
@@ -454,21 +496,24 @@ __device__ __forceinline__ int filter_tile(const TiledArgs &a, const uint32_t wg
     FB[NXT][(K) & 3] = tfrag(RAW[K], mT);                                      \
     F_PINF(FB[NXT][(K) & 3])                                                   \
   }
-// Set A of word K: bits 0-1 moved up to bits 2-3.
+// Set A of word K: bits 0-1 of every nibble as they are (1 + T: 0 / 0.5 / 1.0 in fp4).
 #define F_BUILD_A(NXT, K)                                                      \
   F_PIN4(RAW[K])                                                               \
   if ((K) < 4) {                                                               \
-    FA[NXT][(K) & 3] = tfrag(shl2(RAW[K]), mT);                                \
+    FA[NXT][(K) & 3] = tfrag(RAW[K], mA);                                      \
     F_PINF(FA[NXT][(K) & 3])                                                   \
   } else {                                                                     \
-    FB[NXT][(K) & 3] = tfrag(shl2(RAW[K]), mT);                                \
+    FB[NXT][(K) & 3] = tfrag(RAW[K], mA);                                      \
     F_PINF(FB[NXT][(K) & 3])                                                   \
   }
-#define F_MMA(CUR, BI, BJ) acc[BI][BJ] = mma(FA[CUR][BI], FB[CUR][BJ], acc[BI][BJ]);
+// (fragment set 0 holds set B: the scaled instruction; fragment set 1 holds set A)
+#define F_MMA(CUR, BI, BJ)                                                     \
+  acc[BI][BJ] = (CUR) == 0 ? mma_scaled(FA[CUR][BI], FB[CUR][BJ], acc[BI][BJ], scaleB) \
+                           : mma(FA[CUR][BI], FB[CUR][BJ], acc[BI][BJ]);
 #define F_BAR __builtin_amdgcn_sched_barrier(0);
   // Slice B of unit c (fragment set CUR): 16 MFMAs; in their gaps the set-A
-  // fragments of the same words (8 VALU per fragment: every second gap) and two
-  // requests.
+  // fragments of the same words (4 VALU per fragment, in every second gap: the
+  // gaps that take a request stay free) and two requests.
 #define F_SLICE_B(CUR, NXT, PA, DC, OFF0, OFF1)                                \
   {                                                                            \
     const char *src_ = (PA).src + (DC) * row_bytes;                            \
@@ -652,17 +697,19 @@ __device__ __forceinline__ int filter_tile(const TiledArgs &a, const uint32_t wg
   k0 = __builtin_amdgcn_readfirstlane(k0);
   wrap = __builtin_amdgcn_readfirstlane(wrap);
   start_abs = __builtin_amdgcn_readfirstlane(start_abs);
-  // u of plane sample idx over the `share` phases from this tile's first on (`total`: over
-  // all sites): cumulative counts in front of the inner boundaries, nothing in front of 0
+  // u~ of plane sample idx over the `share` phases from this tile's first on (`total`: over
+  // all sites): cumulative counts in front of the inner boundaries, nothing in front of 0.
+  // A range that goes around the end of the sites is (total - front of `phase`) + front of
+  // the wrapped end, in THAT order: every partial is then u~ over a contiguous range of
+  // sites or over two disjoint ones, at most 2.5 per site -- total + the wrapped end first
+  // would reach 5 per site, past 2^24 at 2^22 sites (king_common.h, kMfmaN4MaxSites).
   auto prefix_u_of = [&](uint32_t share, size_t idx, float total) {
-    const uint32_t hi = phase + share * kPhasesPerShare;
-    const uint32_t xb = hi > kNumPhases ? hi - kNumPhases : hi;  // (uniform)
-    float u = hi > kNumPhases ? total : 0.f;
-    if (xb == kNumPhases)
-      u += total;
-    else if (xb != 0)
-      u += a.prefix_u[(size_t)(xb - 1) * s_stride + idx];
+    const uint32_t hi = phase + share * kPhasesPerShare;  // (uniform; hi < 2 kNumPhases)
+    float u = hi >= kNumPhases ? total
+              : hi != 0        ? a.prefix_u[(size_t)(hi - 1) * s_stride + idx]
+                               : 0.f;
     if (phase != 0) u -= a.prefix_u[(size_t)(phase - 1) * s_stride + idx];
+    if (hi > kNumPhases) u += a.prefix_u[(size_t)(hi - kNumPhases - 1) * s_stride + idx];
     return u;
   };
   // The k-step this tile has reached, for the tiles of the XCD that start next (one lane of
@@ -756,7 +803,7 @@ __device__ __forceinline__ int filter_tile(const TiledArgs &a, const uint32_t wg
     // --- the check behind k-step seg_end of the tile
     const bool forecast = seg_end == chk0;  // uniform
     const float scale = forecast ? (float)kCheckShares64[0] * (1.f / 64.f) : 1.f;
-    float2 *const ck_rows = reinterpret_cast<float2 *>(lds);  // (u over the prefix, scaled bound)
+    float2 *const ck_rows = reinterpret_cast<float2 *>(lds);  // (u~ over the prefix, scaled bound)
     float2 *const ck_cols = ck_rows + kT;
     uint32_t *const ck_words = reinterpret_cast<uint32_t *>(ck_cols + kT);  // one per wavefront
     {
@@ -795,7 +842,7 @@ __device__ __forceinline__ int filter_tile(const TiledArgs &a, const uint32_t wg
           //  configs[2]; the test on the indices made the kernel a quarter longer)
 #pragma unroll
           for (int bj = 0; bj < 4; ++bj)
-            cnt += fmaf(-0.5f, acc[bi][bj][r], cr.x + cc[bj].x) < fminf(cr.y, cc[bj].y) ? 1u : 0u;
+            cnt += fmaf(-8.f, acc[bi][bj][r], cr.x) + cc[bj].x < fminf(cr.y, cc[bj].y) ? 1u : 0u;
         }
     }
 #pragma unroll
@@ -938,7 +985,7 @@ __device__ __forceinline__ int filter_tile(const TiledArgs &a, const uint32_t wg
 
   // --- epilogue: the bound, per pair.  C layout of the 32 x 32 MFMA: column =
   // lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5).
-  float2 *const st_rows = reinterpret_cast<float2 *>(lds);  // (u, t |H| + margin) per row
+  float2 *const st_rows = reinterpret_cast<float2 *>(lds);  // (u~, t |H| + margin) per row
   float2 *const st_cols = st_rows + kT;
   {
     const float t = 2.f - 4.f * a.kin_threshold;
@@ -977,7 +1024,7 @@ __device__ __forceinline__ int filter_tile(const TiledArgs &a, const uint32_t wg
 #pragma unroll
         for (int bj = 0; bj < 4; ++bj)
           best = fmaxf(best, fminf(sr.y, sc[bj].y) -
-                                 fmaf(-0.5f, acc[bi][bj][r], sr.x + sc[bj].x));
+                                 (fmaf(-8.f, acc[bi][bj][r], sr.x) + sc[bj].x));
       }
     if (__ballot(best > 0.f) == 0) {  // wave-uniform
       if (lane == 0)
@@ -1008,8 +1055,9 @@ __device__ __forceinline__ int filter_tile(const TiledArgs &a, const uint32_t wg
           // cuking.cu:199 plus the tile padding
           const bool valid = li < a.geo.num_rows && lj < a.geo.num_cols &&
                              a.i_begin + li < a.j_begin + lj;
-          // u_i + u_j - 2 q  <  t min(|H_i|, |H_j|) + margin   (acc = 4 q)
-          const float x_lb = fmaf(-0.5f, acc[bi][bj][r], sr.x + sc[bj].x);
+          // u_i + u_j - 2 q  <  t min(|H_i|, |H_j|) + margin   ("Offset code" above:
+          // u~_i - 8 acc first, below 2^24 in magnitude, then u~_j)
+          const float x_lb = fmaf(-8.f, acc[bi][bj][r], sr.x) + sc[bj].x;
           const bool cand = valid && x_lb < fminf(sr.y, sc[bj].y);
           const unsigned long long b = __ballot(cand);
           if (b != 0) {  // wave-uniform

@@ -262,8 +262,9 @@ __global__ __launch_bounds__(256) void prepare_nibbles_kernel(
   }  // CODES
   if constexpr (T2) {
     // One unit = one 64-bit word of the reference planes: its low 32 sites in
-    // bits 2-3 of the nibbles, its high 32 sites in bits 0-1; per site (hom-alt,
-    // hom) = the fp4 code's (sign, 2.0) bits.
+    // bits 2-3 of the nibbles, (hom-alt, hom) = the fp4 code's (sign, 2.0) bits; its
+    // high 32 sites in bits 0-1 as 1 + T in binary: (hom-ref, het or missing) = the
+    // fp4 code's (1.0, 0.5) bits, hom-alt 00.  Padding is missing: 01.
     uint4 *t2 = const_cast<uint4 *>(plane_t2(planes, geo));
 #pragma unroll
     for (int it = 0; it < kNibWords * kPrepSamples / 256; ++it) {
@@ -278,8 +279,8 @@ __global__ __launch_bounds__(256) void prepare_nibbles_kernel(
         const uint32_t h_lo = (uint32_t)(het >> (8 * d)), m_lo = (uint32_t)(hom >> (8 * d));
         const uint32_t h_hi = (uint32_t)(het >> (32 + 8 * d)), m_hi = (uint32_t)(hom >> (32 + 8 * d));
         const uint32_t y_lo = spread8(~h_lo), a_lo = spread8(m_lo & ~h_lo);
-        const uint32_t y_hi = spread8(~h_hi), a_hi = spread8(m_hi & ~h_hi);
-        out[d] = (a_lo << 3) | (y_lo << 2) | (a_hi << 1) | y_hi;
+        const uint32_t r_hi = spread8(~h_hi & ~m_hi), n_hi = spread8(h_hi);
+        out[d] = (a_lo << 3) | (y_lo << 2) | (r_hi << 1) | n_hi;
       }
       t2[(uint64_t)u * geo.s_stride + s0 + s] = make_uint4(out[0], out[1], out[2], out[3]);
     }

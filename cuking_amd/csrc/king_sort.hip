@@ -19,8 +19,9 @@
 //      the layout IS the stored order;
 //   3. a STABLE sort of (key, sample) pairs -- deterministic, and samples of equal share
 //      (an ordinary cohort: all of them) keep their stored order;
-//   4. perm and the statistics written in plane order; padding samples behind the real
-//      ones (kNoSample, zero statistics).
+//   4. perm and the statistics written in plane order -- (u~, |H|) and the cumulative u~,
+//      what the filter kernel's pair test reads --; padding samples behind the real ones
+//      (kNoSample; u~ = n_A, |H| = 0).
 #include <hip/hip_runtime.h>
 
 #include <hipcub/hipcub.hpp>
@@ -61,17 +62,22 @@ __global__ void apply_order_kernel(PlaneGeometry geo, uint32_t begin, uint32_t e
   const uint32_t p = begin + blockIdx.x * blockDim.x + threadIdx.x;
   if (p >= end) return;
   if (p - begin >= n) {
+    // (T = 0 at every site: u = S = 0, what is left of u~ is n_A, 128 per k-step --
+    //  king_filter.hip sample_stats_kernel)
+    const uint32_t all_steps = geo.k_words / 8;
     perm[p] = kNoSample;
-    stats[p] = make_float2(0.f, 0.f);
+    stats[p] = make_float2((float)(128u * all_steps), 0.f);
 #pragma unroll
-    for (uint32_t c = 0; c < kNumCum; ++c) prefix[(size_t)c * geo.s_stride + p] = 0.f;
+    for (uint32_t c = 0; c < kNumCum; ++c)
+      prefix[(size_t)c * geo.s_stride + p] = (float)(128u * phase_step(all_steps, c + 1));
     return;
   }
   const uint32_t src = order[p - begin];  // plane sample in stored order
   // the stored sample behind it: rows as they are, columns of an off-diagonal block behind
   // the rows (cuking.cu:171-175)
   perm[p] = (geo.diag || src < geo.rows_padded) ? src : geo.num_rows + (src - geo.col_base);
-  stats[p] = tmp_stats[src];
+  // (the pair test's u~ over all sites: the row behind the cumulative ones; |H|)
+  stats[p] = make_float2(tmp_prefix[(size_t)kNumCum * geo.s_stride + src], tmp_stats[src].y);
 #pragma unroll 7
   for (uint32_t c = 0; c < kNumCum; ++c)
     prefix[(size_t)c * geo.s_stride + p] = tmp_prefix[(size_t)c * geo.s_stride + src];
