@@ -63,6 +63,7 @@ def _newer(target: Path, deps) -> bool:
 def build_library(force: bool = False, save_temps: bool = False) -> Path:
     srcs = [CSRC / s for s in HIP_SOURCES + HOST_ABI_SOURCES]
     deps = srcs + [CSRC / "king_common.h", CSRC / "king_device.h", CSRC / "king_host.h",
+                   CSRC / "king_launch_plan.h",
                    CSRC / "king_submatrix.h", INCLUDE / "cuking_amd.h",
                    Path(__file__)]
     extra = os.environ.get("CUKING_EXTRA_HIPFLAGS", "").split()

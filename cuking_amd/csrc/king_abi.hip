@@ -399,9 +399,34 @@ cuking_status scratch_for(cuking_ctx *ctx, hipStream_t stream, uint64_t tiles,
   return CUKING_OK;
 }
 
-// The launch arguments of the pair kernels for the block `sm` of the prepared workspace
+// The filter's bound applies to a call (it only helps the lean form with a threshold inside
+// (0, 1/2)): the filter kernel runs (LaunchSwitches::filter_runs), and the four-product
+// kernel's codes may stay unconverted.
+bool filter_runs(const cuking_ctx *ctx, uint32_t words_per_sample, bool full, float kin_threshold) {
+  return effective_variant(ctx, words_per_sample) == kMfmaFilterVariant && !full &&
+         kin_threshold > 0.f && kin_threshold < 0.5f;
+}
+
+// The context's switches for a call that runs the `full` or the lean form: built once per
+// call, in front of the conversion (which asks whether the filter runs).
+LaunchSwitches launch_switches(const cuking_ctx *ctx, uint32_t words_per_sample, bool full,
+                               float kin_threshold) {
+  LaunchSwitches sw;
+  sw.xcd_swizzle = (uint32_t)ctx->xcd_swizzle;
+  sw.dyn_tail_tiles = ctx->dyn_tail_tiles;
+  sw.check0 = (uint32_t)ctx->filter_check0;
+  sw.check1 = (uint32_t)ctx->filter_check1;
+  sw.check_emit = (uint32_t)ctx->filter_check_emit;
+  sw.rotate = (uint32_t)ctx->filter_rotate;
+  sw.rotate_min_tiles = ctx->filter_rotate_min_tiles;
+  sw.split_min_steps = ctx->filter_split_min_steps;
+  sw.filter_runs = filter_runs(ctx, words_per_sample, full, kin_threshold);
+  return sw;
+}
+
+// The device arguments of the pair kernels for the block `sm` of the prepared workspace
 // (geometry `geo`, enumeration `tiles`; the stream's filter scratch sized for
-// `block_tiles`), with the context's switches.  Callers fill in the tile range.
+// `block_tiles`).  Callers fill in the tile range.
 struct Outputs {
   uint32_t max_results;
   cuking_result *results;
@@ -431,8 +456,6 @@ cuking_status launch_args(cuking_ctx *ctx, hipStream_t stream, const cuking_subm
   a.bits = d_bit_sets;
   a.words_per_sample = words_per_sample;
   a.split_wgs = ctx->split_wgs;
-  a.xcd_chunk = (uint32_t)ctx->xcd_swizzle;  // (switch: 1 chunks, 2 patches; the launch sets the value)
-  a.dyn_tiles = ctx->dyn_tail_tiles;         // (threshold; the launch sets the count)
   // the sample order of the workspace's layout, and the lazy-codes word
   if (plan_variant(ctx, words_per_sample).layout == kLayoutNibbleStats) {
     a.perm = plane_perm(ctx->planes, geo);
@@ -462,42 +485,24 @@ cuking_status launch_args(cuking_ctx *ctx, hipStream_t stream, const cuking_subm
   a.dense_list = reinterpret_cast<uint2 *>(base + l.dense);
   a.dense_cap = l.chunk_tiles * 4;
   // (remainder splitting follows the matrix-core kernels' switch: "split_wgs" 0 = never)
-  a.fsplit_first = ctx->filter_split_min_steps;  // (on entry: launch_filter)
   a.fsplit_slabs = ctx->split_wgs != 0 ? reinterpret_cast<float4 *>(base + l.slabs) : nullptr;
-  a.check0 = (uint32_t)ctx->filter_check0;  // (switches on entry: launch_filter)
-  a.check1 = (uint32_t)ctx->filter_check1 | ((uint32_t)ctx->filter_check_emit << 8) |
-             (ctx->filter_check0 != 0 ? 1u << 16 : 0u);
-  a.rotate = (uint32_t)ctx->filter_rotate;
   a.rotate_min_steps = ctx->filter_rotate_min_steps;
-  a.rotate_min_tiles = ctx->filter_rotate_min_tiles;
   a.check_steps = plane_check_steps(ctx->planes, geo);
   return CUKING_OK;
-}
-
-// The filter's bound applies to a call: the four-product kernel's codes may stay
-// unconverted.
-bool filter_runs(const cuking_ctx *ctx, uint32_t words_per_sample, bool full, float kin_threshold) {
-  return effective_variant(ctx, words_per_sample) == kMfmaFilterVariant && !full &&
-         kin_threshold > 0.f && kin_threshold < 0.5f;
 }
 
 // Enqueues `num_tiles` tiles of the planned geometry: as they are when the
 // kernel's tile edge is the geometry's, as four quadrants each otherwise.
 hipError_t launch_planned(const cuking_ctx *ctx, uint32_t words_per_sample, bool full,
-                          TiledArgs a, uint64_t num_tiles, hipStream_t stream) {
+                          TiledArgs a, const LaunchSwitches &sw, uint64_t num_tiles,
+                          hipStream_t stream) {
   const int kv = effective_variant(ctx, words_per_sample);
-  a.quad = 0;
-  a.tile_list = nullptr;
-  a.tile_list_count = nullptr;
-  a.tile_list_cap = 0;
   if (tiled_variant(kv).tile != tiled_variant(ctx->variant).tile) {
     // (only the filter variant's 256-sample geometry over a 128-tile kernel)
     if (tiled_variant(kv).tile * 2 != tiled_variant(ctx->variant).tile) return hipErrorInvalidValue;
-    a.quad = 1;
-    a.tile_begin *= 4;
-    num_tiles *= 4;
+    to_quadrants(&a, &num_tiles);
   }
-  return launch_tiled(kv, full, a, num_tiles, stream);
+  return launch_tiled(kv, full, a, sw, num_tiles, stream);
 }
 
 // A pair kernel that reads the workspace has been enqueued on `stream`.
@@ -748,8 +753,10 @@ cuking_status run_tiled(cuking_ctx *ctx, const cuking_submatrix &sm,
   PlaneGeometry geo;
   TileSpace tiles;
   const bool full = use_full_counts(ctx, kin_threshold, out.counts != nullptr, words_per_sample);
+  const LaunchSwitches sw = launch_switches(ctx, words_per_sample, full, kin_threshold);
+  // (where the filter runs the four-product kernel's codes may stay unconverted)
   cuking_status st = prepare(ctx, sm, words_per_sample, d_bit_sets, stream, &geo, &tiles,
-                             !filter_runs(ctx, words_per_sample, full, kin_threshold));
+                             !sw.filter_runs);
   if (st != CUKING_OK) return st;
   const uint64_t n_tiles = total_tiles(tiles);
   if (whole) {
@@ -771,7 +778,7 @@ cuking_status run_tiled(cuking_ctx *ctx, const cuking_submatrix &sm,
 
   EventPair *ev = nullptr;
   if (ctx->timing) HIP_TRY(ctx->king_timer.begin(stream, &ev));
-  HIP_TRY(launch_planned(ctx, words_per_sample, full, a, tile_end - tile_begin, stream));
+  HIP_TRY(launch_planned(ctx, words_per_sample, full, a, sw, tile_end - tile_begin, stream));
   note_reader(ctx, stream);
   mark_read(ctx, 0, 0xFFFFFFFFu);
   if (ev) HIP_TRY(hipEventRecord(ev->stop, stream));
@@ -1390,6 +1397,8 @@ cuking_status cuking_compute_king_rect(
                     sm->i_begin + c * v.tile);
   }
 
+  const bool full = use_full_counts(ctx, kin_threshold, false, words_per_sample);
+  LaunchSwitches sw = launch_switches(ctx, words_per_sample, full, kin_threshold);
   TiledArgs a;
   st = launch_args(ctx, (hipStream_t)stream, *sm, words_per_sample, d_bit_sets, geo, tiles,
                    total_tiles(make_tiles(geo, v, ctx->band_rows)), kin_threshold,
@@ -1400,10 +1409,8 @@ cuking_status cuking_compute_king_rect(
   a.rect_row0 = r0;
   a.rect_col0 = c0;
   a.rect_row_stride = stride;
-  a.xcd_chunk = ctx->xcd_swizzle == 2 ? 2u : 0u;  // (see above; patches keep the balance)
-  const bool full = use_full_counts(ctx, kin_threshold, false, words_per_sample);
-  if (v.layout == kLayoutNibbleStats && !ctx->prepared.codes &&
-      !filter_runs(ctx, words_per_sample, full, kin_threshold)) {
+  if (sw.xcd_swizzle != 2) sw.xcd_swizzle = 0;  // (see above; patches keep the balance)
+  if (v.layout == kLayoutNibbleStats && !ctx->prepared.codes && !sw.filter_runs) {
     // (a block converted without the four-product kernel's codes, and a call that runs
     //  that kernel directly)
     st = convert_codes_now(ctx, geo, words_per_sample, d_bit_sets, (hipStream_t)stream);
@@ -1412,7 +1419,7 @@ cuking_status cuking_compute_king_rect(
   }
   EventPair *ev = nullptr;
   if (ctx->timing) HIP_TRY(ctx->king_timer.begin((hipStream_t)stream, &ev));
-  HIP_TRY(launch_planned(ctx, words_per_sample, full, a, (uint64_t)n_rows * (c1 - c0),
+  HIP_TRY(launch_planned(ctx, words_per_sample, full, a, sw, (uint64_t)n_rows * (c1 - c0),
                          (hipStream_t)stream));
   note_reader(ctx, (hipStream_t)stream);
   {

@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "cuking_amd.h"
+#include "king_launch_plan.h"
 #include "king_submatrix.h"
 
 namespace cuking {
@@ -121,7 +122,9 @@ struct TileSpace {
   }
 };
 
-// Arguments of the tiled pair kernel.
+// Arguments of the tiled pair kernel: what the device reads, nothing else.  The context's
+// switches travel beside it (LaunchSwitches, king_launch_plan.h); the launchers turn them
+// into plans and fill the launch's fields here from those.
 struct TiledArgs {
   const uint4 *planes;
   PlaneGeometry geo;
@@ -162,8 +165,8 @@ struct TiledArgs {
   // xcd_chunk == 1: patches of 32 consecutive tiles, patch p on XCD p % 8
   // (workgroup b = XCD b % 8, j = b / 8 takes tile ((j / 32) * 8 + b % 8) * 32 +
   // j % 32); xcd_chunk > 1: one contiguous chunk of xcd_chunk tiles per XCD
-  // (workgroup b takes tile (b % 8) * xcd_chunk + b / 8).  On entry to a launch
-  // function the field is the context's switch (0 off, 1 chunks, 2 patches).
+  // (workgroup b takes tile (b % 8) * xcd_chunk + b / 8).  launch_tiles: the tiles
+  // mapped by workgroup index (read only with xcd_chunk or dyn_tiles set).
   uint32_t xcd_chunk, launch_tiles;
   // Dynamic tail (matrix-core kernel, whole-tile launches of many rounds): the
   // XCDs of an MI355X run this kernel at rates 2-3 % apart and a launch's
@@ -173,8 +176,6 @@ struct TiledArgs {
   // launch_tiles statically mapped ones each take the next tile from a counter
   // (in split_counters, zero between launches) or leave at once when none is
   // left -- an XCD that gets through its static share early takes more of them.
-  // On entry to a launch function dyn_tiles is the context's threshold: launches
-  // of at least that many tiles get a dynamic tail (0 = never).
   uint32_t dyn_tiles, dyn_wgs;
   // Quadrant mode (quad != 0): the tile space above is one of 256-sample tiles
   // (the filter variant's geometry) and the launch enumerates their four
@@ -228,20 +229,22 @@ struct TiledArgs {
   const uint32_t *check_steps;
   const float *prefix_u;
   const unsigned long long *cohort_sums;
-  // switches (check1, bits 0-7: 0 off, 1 automatic, 2 + k: entry k forced; bits 8-15: live
+  // check0: 0 no forecast, 1 this is a short launch, 2 forced; check1, bits 0-7: 0 off, 1
+  // automatic, 2 + k: entry k forced; bits 8-15: live
   // pairs per quadrant up to which a tile that fails the rigorous check hands them to the
   // candidate list and leaves anyway, kCheckEmitCap unless a test says otherwise; bit 16:
   // the tiles may give up at once where the cohort's sums say the bound lets every pair
-  // through -- the forecast's switch, whatever the launch's length)
+  // through -- the forecast's switch, whatever the launch's length.  Both are 0 in a launch
+  // without check points.
   uint32_t check0, check1;
   // Rotated tiles (king_filter.hip): 0 every tile starts at its first k-step; 1 a whole tile
   // with check points starts at the phase boundary the other tiles of its XCD are at
   // (filter_ctrl + kCtrlPos: one position word per XCD) and wraps around; 2 test hook: a
-  // phase drawn from the tile's index; 3 + j test hook: phase j.  rotate_min_steps: bitsets
-  // of fewer k-steps are not rotated; nor are launches of fewer than rotate_min_tiles tiles
-  // (the tiles of a few rounds have not drifted apart yet).
+  // phase drawn from the tile's index; 3 + j test hook: phase j -- 0 as well in a launch of
+  // too few tiles (king_launch_plan.h filter_plan).  rotate_min_steps: bitsets of fewer
+  // k-steps are not rotated.
   uint32_t rotate, rotate_min_steps;
-  uint32_t rotate_min_tiles;  // (host side: launches of fewer tiles are not rotated)
+  uint32_t rotate_min_tiles;  // (not read by the device, always 0; kept for the layout)
   // one flag per tile of the launch chunk, directly behind the chunk's control words
   // (filter_ctrl + kCtrlChunkBytes: one memset clears both in front of a chunk)
   uint8_t *tile_done;
@@ -476,20 +479,36 @@ const TiledVariant &tiled_variant(int v);
 // counts; chosen when nearly every pair is expected to pass the threshold);
 // otherwise the lean form: four sums in the main loop, IBS2 recounted for
 // emitted pairs only.  Same records either way.
-hipError_t launch_tiled(int variant, bool full, const TiledArgs &args,
+// `args`: the call's base arguments (no launch mode set: whole tiles in plain order);
+// every launcher fills the fields of its own modes from its plan.  The filter variant
+// runs its filter kernel iff sw.filter_runs (king_abi.hip filter_runs: the same answer
+// decides whether the four-product kernel's codes are converted up front).
+hipError_t launch_tiled(int variant, bool full, const TiledArgs &args, const LaunchSwitches &sw,
                         uint64_t num_tiles, hipStream_t stream);
 // The matrix-core kernel (king_mfma.hip); reached through launch_tiled.
-hipError_t launch_mfma(bool full, bool nibble, const TiledArgs &args, uint64_t num_tiles,
-                       uint32_t lds_bytes, hipStream_t stream);
-// The four-product kernel, lean form, over args.tile_list with `grid` workgroups.
-hipError_t launch_mfma_list(const TiledArgs &args, uint32_t grid, hipStream_t stream);
+hipError_t launch_mfma(bool full, bool nibble, const TiledArgs &args, const LaunchSwitches &sw,
+                       uint64_t num_tiles, uint32_t lds_bytes, hipStream_t stream);
+// The four-product kernel, lean form, over the first min(*count, cap) entries of the device
+// list `list` (TiledArgs::tile_list) with `grid` workgroups.
+hipError_t launch_mfma_list(const TiledArgs &args, const uint2 *list, const uint32_t *count,
+                            uint32_t cap, uint32_t grid, hipStream_t stream);
 // The four-product kernel, lean form, persistent mode (TiledArgs::gate): `grid`
-// workgroups walk num_units units from args.tile_begin on, if the gate is open.
-hipError_t launch_mfma_gated(const TiledArgs &args, uint64_t num_units, uint32_t grid,
+// workgroups walk num_units units from args.tile_begin on, if *gate != 0, skipping the
+// quadrants of tiles with skip_tiles[tile - skip_base] != 0.
+hipError_t launch_mfma_gated(const TiledArgs &args, uint64_t num_units, const uint32_t *gate,
+                             const uint8_t *skip_tiles, uint64_t skip_base, uint32_t grid,
                              hipStream_t stream);
 // The filter variant (king_filter.hip): num_tiles 256-sample tiles from
 // args.tile_begin; needs args.filter_ctrl etc. (king_abi.hip: filter scratch).
-hipError_t launch_filter(const TiledArgs &args, uint64_t num_tiles, hipStream_t stream);
+hipError_t launch_filter(const TiledArgs &args, const LaunchSwitches &sw, uint64_t num_tiles,
+                         hipStream_t stream);
+// Quadrant mode (TiledArgs::quad): the launch of *num_units 256-sample tiles from
+// a->tile_begin as their 128-sample quadrants.
+inline void to_quadrants(TiledArgs *a, uint64_t *num_units) {
+  a->quad = 1;
+  a->tile_begin *= 4;
+  *num_units *= 4;
+}
 // Statistics of plane samples [s_begin, s_end) of a kLayoutNibbleStats workspace.
 hipError_t launch_sample_stats(const uint64_t *d_bit_sets, uint32_t words_per_sample,
                                const PlaneGeometry &geo, uint4 *d_planes, uint32_t s_begin,

@@ -366,6 +366,18 @@ struct DeviceOnce {
     mask[d >> 6].fetch_or(1ull << (d & 63), std::memory_order_release);
   }
 };
+// Lets `Kernel` use `bytes` of dynamic LDS on the current device (one flag per kernel: every
+// launcher of the same kernel shares it).
+template <auto Kernel>
+hipError_t allow_dynamic_lds(uint32_t bytes) {
+  static DeviceOnce attr_set;
+  if (attr_set.done()) return hipSuccess;
+  const hipError_t e =
+      hipFuncSetAttribute(reinterpret_cast<const void *>(Kernel),
+                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+  if (e == hipSuccess) attr_set.mark();
+  return e;
+}
 
 // Workgroups per launch: one launch may not exceed 2^32 - 1 threads in x (HIP
 // truncates silently beyond that); tests can lower the cap.

@@ -1210,95 +1210,47 @@ hipError_t launch_sample_stats(const uint64_t *d_bit_sets, uint32_t words_per_sa
   return hipGetLastError();
 }
 
-hipError_t launch_filter(const TiledArgs &args, uint64_t num_tiles, hipStream_t stream) {
+hipError_t launch_filter(const TiledArgs &args, const LaunchSwitches &sw, uint64_t num_tiles,
+                         hipStream_t stream) {
   if ((uint64_t)args.geo.k_words * 32 > kMfmaN4MaxSites || args.filter_ctrl == nullptr ||
       args.cand_list == nullptr || args.dense_list == nullptr || args.sample_stats == nullptr)
     return hipErrorInvalidValue;
-  static DeviceOnce attr_set;  // per device, see king_device.h
-  if (!attr_set.done()) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(king_filter_kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)kFilterLdsBytes);
-    if (e != hipSuccess) return e;
-    attr_set.mark();
-  }
+  hipError_t e = allow_dynamic_lds<king_filter_kernel>(kFilterLdsBytes);
+  if (e != hipSuccess) return e;
   uint64_t cap = max_blocks_per_launch(256);
   if (cap > kFilterChunkTiles) cap = kFilterChunkTiles;
   // (a chunk's quadrants must fit the dense list)
   if (cap > args.dense_cap / 4) cap = args.dense_cap / 4;
   if (cap == 0) return hipErrorInvalidValue;
   const uint32_t wgs = args.split_wgs != 0 ? args.split_wgs : 256;  // one per CU
-  uint64_t done = 0;
-  while (done < num_tiles) {
-    const uint64_t n = num_tiles - done < cap ? num_tiles - done : cap;
+  const bool checks = args.tile_done != nullptr;
+  const bool can_split = args.fsplit_slabs != nullptr && args.fsplit_tickets != nullptr;
+  for (uint64_t done = 0; done < num_tiles;) {
+    const FilterPlan p = filter_plan(num_tiles - done, cap, wgs, args.geo.k_words / 8, checks,
+                                     can_split, kFilterSplitSlabs, sw);
     // (the chunk's control words and, directly behind them, its tile flags: one memset)
-    const bool checks = args.tile_done != nullptr;
-    hipError_t e = hipMemsetAsync(args.filter_ctrl, 0, kCtrlChunkBytes + (checks ? n : 0), stream);
+    e = hipMemsetAsync(args.filter_ctrl, 0, kCtrlChunkBytes + (checks ? p.n : 0), stream);
     if (e != hipSuccess) return e;
-    TiledArgs a = args;
-    a.tile_begin = args.tile_begin + done;
-    a.quad = 0;
-    a.tile_list = nullptr;
-    a.gate = nullptr;
-    a.skip_tiles = nullptr;
-    // check 0 (the forecast): for launches of fewer than 16 rounds, where the tiles that
-    // would have to give up make up most of the launch before anybody has finished
-    a.check0 = !checks ? 0u : args.check0 == 2 ? 2u : (args.check0 == 1 && n < 16ull * wgs) ? 1u : 0u;
-    a.check1 = checks ? args.check1 : 0u;
-    // (rotated tiles: for launches of many rounds -- the tiles of a few rounds have not
-    //  drifted apart yet, configs[1] has an L2 hit rate of 0.76 without)
-    a.rotate = checks && (n >= args.rotate_min_tiles || args.rotate >= 2) ? args.rotate : 0u;
-    // Short launches: the tiles beyond whole rounds of one per CU would leave most
-    // CUs idle for a whole tile time; each of them is cut into `parts` pieces of k
-    // instead (same launch, behind the whole tiles).
-    uint32_t rest = 0, parts = 0;
-    if (args.fsplit_slabs != nullptr && args.fsplit_tickets != nullptr && n < 16ull * wgs) {
-      rest = (uint32_t)(n % wgs);
-      if (rest != 0 && 2 * rest <= wgs && rest <= kFilterSplitSlabs / 2) {
-        parts = wgs / rest;
-        if (parts > 8) parts = 8;
-        if (parts * rest > kFilterSplitSlabs) parts = kFilterSplitSlabs / rest;
-        // (pieces of at least 8 k-steps -- on entry args.fsplit_first, a test hook --:
-        //  the pipeline's fill and the slab are per piece)
-        const uint32_t min_steps = args.fsplit_first != 0 ? args.fsplit_first : 8;
-        while (parts > 1 && args.geo.k_words / 8 / parts < min_steps) --parts;  // (k-steps of 256 sites)
-      }
-      if (parts < 2) rest = parts = 0;
-    }
-    const uint64_t n_whole = n - rest;  // tiles that go out whole
-    uint64_t grid = n_whole;
-    a.dyn_tiles = a.dyn_wgs = 0;
-    if (args.xcd_chunk == 2 && args.dyn_tiles != 0 && n_whole >= args.dyn_tiles / 4 &&
-        n_whole >= 288) {
-      // whole rounds of patches, then the last ~6 % through the counter with half
-      // as many workgroups again as tiles (launch_shape in king_mfma.hip; the
-      // threshold is the context's, in 128-sample tiles there)
-      const uint64_t fixed = (n_whole - n_whole / 16) / 256 * 256;
-      a.launch_tiles = (uint32_t)fixed;
-      a.xcd_chunk = 1;
-      a.dyn_tiles = (uint32_t)(n_whole - fixed);
-      a.dyn_wgs = a.dyn_tiles + a.dyn_tiles / 2;
-      grid = fixed + a.dyn_wgs;
-    } else if (args.xcd_chunk == 2 && n_whole >= 64) {  // patches of 32, dealt round-robin to the XCDs
-      a.launch_tiles = (uint32_t)n_whole;
-      a.xcd_chunk = 1;
-      grid = 8ull * 32 * ((((n_whole + 31) / 32) + 7) / 8);
-    } else {
-      a.xcd_chunk = 0;
-      a.launch_tiles = (uint32_t)n_whole;
-    }
-    // ... and behind them the pieces of the remainder
-    a.fsplit_parts = parts;
-    a.fsplit_tile0 = (uint32_t)n_whole;
-    a.fsplit_first = (uint32_t)grid;
-    grid += (uint64_t)rest * parts;
+    TiledArgs chunk = args;  // the chunk's tiles, no mode set: what the exact kernel starts from
+    chunk.tile_begin = args.tile_begin + done;
+    TiledArgs a = chunk;
+    a.check0 = p.check0;
+    a.check1 = p.check1;
+    a.rotate = p.rotate;
+    a.launch_tiles = p.whole.launch_tiles;
+    a.xcd_chunk = p.whole.xcd_chunk;
+    a.dyn_tiles = p.whole.dyn_tiles;
+    a.dyn_wgs = p.whole.dyn_wgs;
+    a.fsplit_parts = p.parts;
+    a.fsplit_tile0 = p.fsplit_tile0;
+    a.fsplit_first = p.fsplit_first;
     // (the tiles of the remainder pieces never leave early: done as far as the fallback
     //  launch is concerned)
-    if (checks && rest != 0) {
-      e = hipMemsetAsync(args.tile_done + n_whole, 1, rest, stream);
+    if (checks && p.rest != 0) {
+      e = hipMemsetAsync(args.tile_done + p.fsplit_tile0, 1, p.rest, stream);
       if (e != hipSuccess) return e;
     }
-    king_filter_kernel<<<dim3((uint32_t)grid), dim3(256), kFilterLdsBytes, stream>>>(a);
+    king_filter_kernel<<<dim3((uint32_t)p.grid), dim3(256), kFilterLdsBytes, stream>>>(a);
     e = hipGetLastError();
     if (e != hipSuccess) return e;
     king_refine_kernel<<<dim3(wgs * 4), dim3(256), 0, stream>>>(a);
@@ -1314,26 +1266,22 @@ hipError_t launch_filter(const TiledArgs &args, uint64_t num_tiles, hipStream_t 
       e = launch_mark_codes_ready(a.filter_ctrl, a.codes_ready, stream);
       if (e != hipSuccess) return e;
     }
-    TiledArgs d = a;
-    d.tile_list = a.dense_list;
-    d.tile_list_count = a.filter_ctrl + kCtrlDense;
-    d.tile_list_cap = a.dense_cap;
-    e = launch_mfma_list(d, wgs, stream);
+    // the quadrants that went dense
+    e = launch_mfma_list(chunk, args.dense_list, args.filter_ctrl + kCtrlDense, args.dense_cap,
+                         wgs, stream);
     if (e != hipSuccess) return e;
     if (checks) {
       // The fallback: every tile of the chunk that has not set its flag (it left at
       // check 0, or never started because most quadrants of the launch had gone dense),
       // in the four-product kernel's own order -- if there is any: the gate word.
-      TiledArgs f = a;
-      f.quad = 1;
-      f.tile_begin = a.tile_begin * 4;
-      f.gate = a.filter_ctrl + kCtrlGate;
-      f.skip_tiles = a.tile_done;
-      f.skip_base = a.tile_begin;
-      e = launch_mfma_gated(f, n * 4, wgs, stream);
+      TiledArgs f = chunk;
+      uint64_t units = p.n;
+      to_quadrants(&f, &units);
+      e = launch_mfma_gated(f, units, args.filter_ctrl + kCtrlGate, args.tile_done,
+                            chunk.tile_begin, wgs, stream);
       if (e != hipSuccess) return e;
     }
-    done += n;
+    done += p.n;
   }
   return hipSuccess;
 }

@@ -667,17 +667,11 @@ template <int TIT, int TJT, int RI, int RJ, int KC, int KU, int MINW, bool FULL,
           bool PHASED = false>
 hipError_t launch_variant(const TiledArgs &args, uint64_t num_tiles,
                           uint32_t lds_bytes, hipStream_t stream) {
-  auto kernel = king_tiled_kernel<TIT, TJT, RI, RJ, KC, KU, MINW, FULL, PHASED>;
+  constexpr auto kernel = king_tiled_kernel<TIT, TJT, RI, RJ, KC, KU, MINW, FULL, PHASED>;
   // The attribute belongs to the function object of ONE device: a host with
   // contexts on several GPUs has to set it on each of them.
-  static DeviceOnce attr_set;
-  if (!attr_set.done()) {
-    hipError_t e = hipFuncSetAttribute(
-        reinterpret_cast<const void *>(kernel),
-        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e != hipSuccess) return e;
-    attr_set.mark();
-  }
+  const hipError_t attr = allow_dynamic_lds<kernel>(lds_bytes);
+  if (attr != hipSuccess) return attr;
   // One launch may not exceed 2^32 - 1 threads in x (HIP truncates silently
   // beyond that), so long tile ranges go out as several launches.
   const uint64_t cap = max_blocks_per_launch(TIT * TJT);
@@ -725,7 +719,7 @@ uint64_t max_blocks_per_launch(uint32_t threads) {
 
 const TiledVariant &tiled_variant(int v) { return kVariants[v]; }
 
-hipError_t launch_tiled(int variant, bool full, const TiledArgs &args,
+hipError_t launch_tiled(int variant, bool full, const TiledArgs &args, const LaunchSwitches &sw,
                         uint64_t num_tiles, hipStream_t stream) {
   if (num_tiles == 0) return hipSuccess;
   const uint32_t lds = kVariants[variant].lds_bytes;
@@ -740,23 +734,15 @@ hipError_t launch_tiled(int variant, bool full, const TiledArgs &args,
     case 2: return CUKING_SHAPE(16, 32, 8, 4, 8, 2, 2);
     case 3: return CUKING_SHAPE(32, 32, 4, 4, 8, 2, 4);
     case 4: return CUKING_SHAPE(16, 16, 4, 4, 16, 2, 4);
-    case kMfmaVariant: return launch_mfma(full, false, args, num_tiles, lds, stream);
-    case kMfmaN4Variant: return launch_mfma(full, true, args, num_tiles, lds, stream);
+    case kMfmaVariant: return launch_mfma(full, false, args, sw, num_tiles, lds, stream);
+    case kMfmaN4Variant: return launch_mfma(full, true, args, sw, num_tiles, lds, stream);
     case kMfmaFilterVariant: {
-      // The bound only helps the lean form with a threshold inside (0, 1/2);
-      // otherwise the four-product kernel runs on the quadrants of the same
-      // 256-sample tiles.
-      const bool filter = !full && args.dense_counts == nullptr && args.quad == 0 &&
-                          args.kin_threshold > 0.f && args.kin_threshold < 0.5f &&
-                          args.filter_ctrl != nullptr;
-      if (filter) return launch_filter(args, num_tiles, stream);
+      // Where the bound does not help (LaunchSwitches::filter_runs) the four-product
+      // kernel runs on the quadrants of the same 256-sample tiles.
+      if (sw.filter_runs) return launch_filter(args, sw, num_tiles, stream);
       TiledArgs a = args;
-      if (a.quad == 0) {
-        a.quad = 1;
-        a.tile_begin = args.tile_begin * 4;
-        num_tiles *= 4;
-      }
-      return launch_mfma(full, true, a, num_tiles, kMfmaN4LdsBytes, stream);
+      to_quadrants(&a, &num_tiles);
+      return launch_mfma(full, true, a, sw, num_tiles, kMfmaN4LdsBytes, stream);
     }
     default: return hipErrorInvalidValue;
   }

@@ -1263,83 +1263,44 @@ __global__ __launch_bounds__(256, 1) void king_mfma_kernel(const TiledArgs a) {
   }  // pieces of this workgroup
 }
 
+// The launch's shape (king_launch_plan.h) in the device arguments.
+void set_shape(TiledArgs *a, const WholeShape &s) {
+  a->launch_tiles = s.launch_tiles;
+  a->xcd_chunk = s.xcd_chunk;
+  a->dyn_tiles = s.dyn_tiles;
+  a->dyn_wgs = s.dyn_wgs;
+}
+
+// Whole tiles [args.tile_begin, + num_blocks) in as many launches as the block limit asks
+// for, or (SPLIT) the one launch of args.split_whole whole tiles + args.split_wgs pieces.
 template <bool FULL, bool SPLIT, bool N4 = false>
-hipError_t launch_shape(const TiledArgs &args, uint64_t num_blocks,
+hipError_t launch_shape(const TiledArgs &args, const LaunchSwitches &sw, uint64_t num_blocks,
                         uint32_t lds_bytes, hipStream_t stream) {
-  auto kernel = king_mfma_kernel<FULL, SPLIT, N4>;
+  constexpr auto kernel = king_mfma_kernel<FULL, SPLIT, N4>;
   // (five products: the caller's figure is the 6-stage one of the variant table)
   if (N4) lds_bytes = kMfmaN4LdsBytes;
   else if (FULL) lds_bytes += kMfmaParkBytes;  // the parked fifth sum, behind the stages
   else lds_bytes = kStagesPaired * kStageU4 * sizeof(uint4);
-  static DeviceOnce attr_set;  // per device, see king_device.h
-  if (!attr_set.done()) {
-    hipError_t e = hipFuncSetAttribute(
-        reinterpret_cast<const void *>(kernel),
-        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e != hipSuccess) return e;
-    attr_set.mark();
-  }
-  if (SPLIT) {  // one launch: split_whole whole tiles + split_wgs pieces
-    TiledArgs a = args;
-    a.xcd_chunk = args.xcd_chunk == 2 && args.split_whole != 0 && args.split_whole % 256 == 0;
-    a.launch_tiles = args.split_whole;
-    // the pieces are taken from the counter as well (an XCD that finishes its
-    // whole tiles early takes more of them): half as many workgroups again
-    a.dyn_tiles = args.split_wgs;
-    a.dyn_wgs = args.split_wgs + args.split_wgs / 2;
-    num_blocks = (uint64_t)args.split_whole + a.dyn_wgs;
-    kernel<<<dim3((uint32_t)num_blocks), dim3(256), lds_bytes, stream>>>(a);
+  hipError_t e = allow_dynamic_lds<kernel>(lds_bytes);
+  if (e != hipSuccess) return e;
+  TiledArgs a = args;
+  if (SPLIT) {
+    const WholeShape s = split_shape(args.split_whole, args.split_wgs, sw.xcd_swizzle);
+    set_shape(&a, s);
+    kernel<<<dim3((uint32_t)s.grid), dim3(256), lds_bytes, stream>>>(a);
     return hipGetLastError();
   }
-  // (the XCD order pads a launch to a multiple of 8 workgroups)
-  uint64_t cap = max_blocks_per_launch(256);
-  const bool xcd_order = args.xcd_chunk != 0 && cap >= 64;
-  if (xcd_order) cap &= ~7ull;
-  // Dynamic tail: the last ~6 % of a launch's tiles (more than twice the 2-3 %
-  // by which the XCDs differ), behind a statically mapped part of whole
-  // patch rounds; half as many workgroups again as tiles, so that no XCD runs
-  // out of workgroups before the tiles run out.
-  const bool dyn_ok = args.dyn_tiles != 0 && args.xcd_chunk == 2 && xcd_order &&
-                      args.split_counters != nullptr;
-  const uint64_t dyn_min = args.dyn_tiles;
-  uint64_t done = 0;
-  while (done < num_blocks) {
-    uint64_t n = (num_blocks - done < cap) ? num_blocks - done : cap;
-    uint64_t dyn = 0, dyn_wgs = 0;
-    if (dyn_ok && n >= dyn_min && n >= 512) {
-      if (n + n / 8 > cap) n = cap - cap / 8;  // room for the tail's spare workgroups
-      const uint64_t fixed = (n - n / 16) / 256 * 256;
-      dyn = n - fixed;
-      dyn_wgs = dyn + dyn / 2;
-      if (fixed + dyn_wgs > cap) dyn = dyn_wgs = 0;  // (tiny block limits: test hook)
-    }
-    TiledArgs a = args;
+  // (the dynamic tail's counter sits in the split scratch)
+  const uint64_t dyn_min = args.split_counters != nullptr ? sw.dyn_tail_tiles : 0;
+  const uint64_t cap = max_blocks_per_launch(256);
+  for (uint64_t done = 0; done < num_blocks;) {
+    const WholeShape s = whole_shape(num_blocks - done, cap, sw.xcd_swizzle, dyn_min, kMfmaDynFloor);
     a.tile_begin = args.tile_begin + done;
-    a.dyn_tiles = (uint32_t)dyn;
-    a.dyn_wgs = (uint32_t)dyn_wgs;
-    uint64_t grid = n;
-    if (dyn != 0) {
-      a.launch_tiles = (uint32_t)(n - dyn);  // whole rounds of patches
-      a.xcd_chunk = 1;
-      grid = n - dyn + dyn_wgs;
-    } else if (xcd_order && n >= 64) {
-      a.launch_tiles = (uint32_t)n;
-      if (args.xcd_chunk == 2) {  // patches of 32
-        const uint64_t patches = (n + 31) / 32;
-        a.xcd_chunk = 1;
-        grid = 8ull * 32 * ((patches + 7) / 8);
-      } else {
-        a.xcd_chunk = (uint32_t)((n + 7) / 8);
-        if (a.xcd_chunk == 1) a.xcd_chunk = 2;  // (n >= 64: cannot happen; keeps 1 reserved)
-        grid = 8ull * a.xcd_chunk;
-      }
-    } else {
-      a.xcd_chunk = 0;
-    }
-    kernel<<<dim3((uint32_t)grid), dim3(256), lds_bytes, stream>>>(a);
-    hipError_t e = hipGetLastError();
+    set_shape(&a, s);
+    kernel<<<dim3((uint32_t)s.grid), dim3(256), lds_bytes, stream>>>(a);
+    e = hipGetLastError();
     if (e != hipSuccess) return e;
-    done += n;
+    done += s.tiles;
   }
   return hipSuccess;
 }
@@ -1355,138 +1316,79 @@ size_t mfma_split_counter_bytes(uint32_t wgs) { return split_counter_bytes(wgs);
 
 namespace {
 // launch_shape<FULL, SPLIT, N4> by run-time flags
-hipError_t launch_form(bool full, bool split, bool nibble, const TiledArgs &a, uint64_t blocks,
-                       uint32_t lds_bytes, hipStream_t stream) {
+hipError_t launch_form(bool full, bool split, bool nibble, const TiledArgs &a,
+                       const LaunchSwitches &sw, uint64_t blocks, uint32_t lds_bytes,
+                       hipStream_t stream) {
   if (nibble) {
     if (split)
-      return full ? launch_shape<true, true, true>(a, blocks, lds_bytes, stream)
-                  : launch_shape<false, true, true>(a, blocks, lds_bytes, stream);
-    return full ? launch_shape<true, false, true>(a, blocks, lds_bytes, stream)
-                : launch_shape<false, false, true>(a, blocks, lds_bytes, stream);
+      return full ? launch_shape<true, true, true>(a, sw, blocks, lds_bytes, stream)
+                  : launch_shape<false, true, true>(a, sw, blocks, lds_bytes, stream);
+    return full ? launch_shape<true, false, true>(a, sw, blocks, lds_bytes, stream)
+                : launch_shape<false, false, true>(a, sw, blocks, lds_bytes, stream);
   }
   if (split)
-    return full ? launch_shape<true, true>(a, blocks, lds_bytes, stream)
-                : launch_shape<false, true>(a, blocks, lds_bytes, stream);
-  return full ? launch_shape<true, false>(a, blocks, lds_bytes, stream)
-              : launch_shape<false, false>(a, blocks, lds_bytes, stream);
+    return full ? launch_shape<true, true>(a, sw, blocks, lds_bytes, stream)
+                : launch_shape<false, true>(a, sw, blocks, lds_bytes, stream);
+  return full ? launch_shape<true, false>(a, sw, blocks, lds_bytes, stream)
+              : launch_shape<false, false>(a, sw, blocks, lds_bytes, stream);
+}
+
+// ONE launch of the four-product kernel's lean form with `grid` workgroups that stride over
+// a list or a range, whatever the block limit (a test hook may set it below `grid`; a
+// second launch would walk the list again).
+hipError_t launch_strided(const TiledArgs &a, uint32_t grid, hipStream_t stream) {
+  if ((uint64_t)a.geo.k_words * 32 > kMfmaN4MaxSites) return hipErrorInvalidValue;
+  const uint64_t cap = max_blocks_per_launch(256);
+  if (grid > cap) grid = (uint32_t)cap;
+  if (grid == 0) return hipErrorInvalidValue;
+  constexpr auto kernel = king_mfma_kernel<false, false, true>;
+  const hipError_t e = allow_dynamic_lds<kernel>(kMfmaN4LdsBytes);
+  if (e != hipSuccess) return e;
+  kernel<<<dim3(grid), dim3(256), kMfmaN4LdsBytes, stream>>>(a);
+  return hipGetLastError();
 }
 }  // namespace
 
-hipError_t launch_mfma_list(const TiledArgs &args, uint32_t grid, hipStream_t stream) {
-  if ((uint64_t)args.geo.k_words * 32 > kMfmaN4MaxSites || args.tile_list == nullptr)
-    return hipErrorInvalidValue;
+hipError_t launch_mfma_list(const TiledArgs &args, const uint2 *list, const uint32_t *count,
+                            uint32_t cap, uint32_t grid, hipStream_t stream) {
+  if (list == nullptr) return hipErrorInvalidValue;
   TiledArgs a = args;
-  a.quad = 0;
-  a.tile_begin = 0;
+  a.tile_begin = 0;  // (the entries are tiles of the block, not of a range or a rectangle)
   a.rect_rows = 0;
-  a.split_tiles = a.split_whole = 0;
-  a.split_scratch = a.split_counters = nullptr;
-  a.xcd_chunk = 0;  // plain order, no dynamic tail
-  a.dyn_tiles = a.dyn_wgs = 0;
-  a.launch_tiles = 0;
-  // ONE launch whatever the block limit (a test hook may set it below `grid`): the
-  // workgroups stride over the list, a second launch would walk it again.
-  const uint64_t cap = max_blocks_per_launch(256);
-  if (grid > cap) grid = (uint32_t)cap;
-  if (grid == 0) return hipErrorInvalidValue;
-  auto kernel = king_mfma_kernel<false, false, true>;
-  static DeviceOnce attr_set;  // per device, see king_device.h
-  if (!attr_set.done()) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)kMfmaN4LdsBytes);
-    if (e != hipSuccess) return e;
-    attr_set.mark();
-  }
-  kernel<<<dim3(grid), dim3(256), kMfmaN4LdsBytes, stream>>>(a);
-  return hipGetLastError();
+  a.tile_list = list;
+  a.tile_list_count = count;
+  a.tile_list_cap = cap;
+  return launch_strided(a, grid, stream);
 }
 
-hipError_t launch_mfma_gated(const TiledArgs &args, uint64_t num_units, uint32_t grid,
+hipError_t launch_mfma_gated(const TiledArgs &args, uint64_t num_units, const uint32_t *gate,
+                             const uint8_t *skip_tiles, uint64_t skip_base, uint32_t grid,
                              hipStream_t stream) {
-  if ((uint64_t)args.geo.k_words * 32 > kMfmaN4MaxSites || args.gate == nullptr ||
-      args.tile_list != nullptr || num_units > 0xFFFFFFFFull)
-    return hipErrorInvalidValue;
+  if (gate == nullptr || num_units > 0xFFFFFFFFull) return hipErrorInvalidValue;
   TiledArgs a = args;
-  a.split_tiles = a.split_whole = 0;
-  a.split_scratch = a.split_counters = nullptr;
-  a.xcd_chunk = 0;
-  a.dyn_tiles = a.dyn_wgs = 0;
-  a.launch_tiles = 0;
+  a.gate = gate;
   a.gate_count = (uint32_t)num_units;
-  const uint64_t cap = max_blocks_per_launch(256);  // (ONE launch, see launch_mfma_list)
-  if (grid > cap) grid = (uint32_t)cap;
-  if (grid == 0) return hipErrorInvalidValue;
-  auto kernel = king_mfma_kernel<false, false, true>;
-  static DeviceOnce attr_set;  // per device, see king_device.h
-  if (!attr_set.done()) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)kMfmaN4LdsBytes);
-    if (e != hipSuccess) return e;
-    attr_set.mark();
-  }
-  kernel<<<dim3(grid), dim3(256), kMfmaN4LdsBytes, stream>>>(a);
-  return hipGetLastError();
+  a.skip_tiles = skip_tiles;
+  a.skip_base = skip_base;
+  return launch_strided(a, grid, stream);
 }
 
-hipError_t launch_mfma(bool full, bool nibble, const TiledArgs &args, uint64_t num_tiles,
-                       uint32_t lds_bytes, hipStream_t stream) {
+hipError_t launch_mfma(bool full, bool nibble, const TiledArgs &args, const LaunchSwitches &sw,
+                       uint64_t num_tiles, uint32_t lds_bytes, hipStream_t stream) {
   if ((uint64_t)args.geo.k_words * 32 > (nibble ? kMfmaN4MaxSites : kMfmaMaxSites))
     return hipErrorInvalidValue;
-  // Whole rounds of one tile per workgroup, then the remainder (the tiles that
-  // would leave most CUs idle for a whole tile time) cut into equal pieces of
-  // k-steps over all CUs, in the SAME launch: a CU that finishes its last
-  // whole tile goes straight on to a piece.  For launches of fewer than
-  // kSplitRounds tiles per CU: 36 tiles 0.57 -> 0.25 ms, 300 tiles
-  // 1.26 -> 0.91 ms, 820 tiles 2.40 -> 2.15 ms; configs[1] (3160 tiles = 12.3
-  // rounds, the dispatcher's back-filling does not hide the 13th: time follows
-  // ceil(rounds), archive/experiments/exp15.sh) 6.93 -> 6.75 ms and 7.12 -> 6.84 ms on two
-  // boxes.  A piece costs ~30 us per tile it touches (slab, ticket) and the
-  // pieces end as far apart as the whole tiles before them did (~0.3 ms after
-  // 12 rounds), which is what is left of the ideal 0.66 x 0.53 ms
-  // (archive/profiles/r02_tail.txt); beyond 64 rounds the gain is under 1 %.
-  constexpr uint64_t kSplitRounds = 64;
-  const uint32_t wgs = args.split_wgs;
-  const uint32_t tile_steps = args.geo.k_words / 8;
-  uint64_t whole = num_tiles;
-  uint32_t rest = 0;
-  if (wgs != 0 && args.split_scratch != nullptr && num_tiles < kSplitRounds * wgs) {
-    // under two tiles per CU everything goes out as pieces (300 tiles:
-    // 0.98 -> 0.91 ms); otherwise the remainder after whole rounds
-    rest = num_tiles < 2ull * wgs ? (uint32_t)num_tiles : (uint32_t)(num_tiles % wgs);
-    if ((uint64_t)rest * tile_steps < 8ull * wgs) rest = 0;  // too little work to cut up
-    whole = num_tiles - rest;
-  }
+  // Whole tiles first, then ONE launch of whole tiles and the remainder in pieces
+  // (king_launch_plan.h mfma_plan).  (Never split without scratch for the pieces.)
+  const MfmaPlan p = mfma_plan(num_tiles, args.split_scratch != nullptr ? args.split_wgs : 0,
+                               args.geo.k_words / 8, max_blocks_per_launch(256));
+  hipError_t e = launch_form(full, false, nibble, args, sw, p.first, lds_bytes, stream);
+  if (e != hipSuccess || p.split_tiles == 0) return e;
   TiledArgs a = args;
-  a.split_tiles = 0;
-  a.split_whole = 0;
-  if (rest == 0) return launch_form(full, false, nibble, a, whole, lds_bytes, stream);
-  // One launch: `head` whole-tile workgroups followed by the wgs pieces of the
-  // remainder, so that CUs finishing their last whole tile go straight on to
-  // pieces (a second launch would wait for the slowest whole tile first).
-  // Anything beyond one launch's block limit goes out whole before it.
-  const uint64_t cap = max_blocks_per_launch(256);
-  uint64_t head = whole;
-  if (cap <= wgs + wgs / 2) {
-    // (test hook: a block limit below the piece count) whole tiles on their
-    // own, in as many launches as it takes, then the pieces
-    if (head != 0) {
-      const hipError_t e = launch_form(full, false, nibble, a, head, lds_bytes, stream);
-      if (e != hipSuccess) return e;
-    }
-    a.tile_begin = args.tile_begin + head;
-    head = 0;
-  } else if (head + wgs + wgs / 2 > cap) {  // (the pieces' launch has wgs / 2 spare workgroups)
-    const uint64_t first = head + wgs + wgs / 2 - cap;
-    const hipError_t e = launch_form(full, false, nibble, a, first, lds_bytes, stream);
-    if (e != hipSuccess) return e;
-    a.tile_begin = args.tile_begin + first;
-    head -= first;
-  }
-  a.split_whole = (uint32_t)head;
-  a.split_tiles = rest;
-  return launch_form(full, true, nibble, a, head + wgs, lds_bytes, stream);
+  a.tile_begin = args.tile_begin + p.first;
+  a.split_whole = p.split_whole;
+  a.split_tiles = p.split_tiles;
+  return launch_form(full, true, nibble, a, sw, (uint64_t)p.split_whole + args.split_wgs, lds_bytes,
+                     stream);
 }
 
 }  // namespace cuking
