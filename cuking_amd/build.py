@@ -105,59 +105,25 @@ def build_library(force: bool = False, save_temps: bool = False) -> Path:
     return LIB_PATH
 
 
-def check_filter_loop(asm_path: Path, verbose: bool = False):
-    """The same check for king_filter_kernel (king_filter.hip): its k-loops hold LDS-DMA
-    requests and a hand-counted wait (22 in flight at a hand-over) and must hold no
-    scratch access and no other vmcnt wait."""
+def check_dma_loops(asm_path: Path, kernel: str, kernel_re: str, allowed_vmcnt, label_of,
+                    verbose: bool = False):
+    """The LDS-DMA requests of the matrix-core kernels are inline asm the compiler's
+    wait-count pass does not see, so ANY wait it inserts on the vector-memory counter
+    inside such a loop (for a spill reload or a load of its own still in flight at loop
+    entry) drains the whole prefetch pipeline every k-step -- 10 % of a launch the one
+    time it happened (round 2, full form).  Returns the offending loops of the kernels
+    `kernel` (symbols matching `kernel_re`, named by `label_of`): blocks with LDS-DMA and >= 16 MFMAs that hold a
+    scratch instruction or a vmcnt wait other than the hand-counted `allowed_vmcnt`.
+    `verbose` lists every such loop with what it holds."""
     import re
     text = Path(asm_path).read_text()
-    bodies = [m.group(1) for m in re.finditer(
-        r"\n_ZN6cuking12_GLOBAL__N_1\d+king_filter_kernelE\w+:(.*?)\.Lfunc_end", text, re.S)]
-    if not bodies:
-        return [f"no king_filter_kernel in {asm_path}"]
-    problems, seen = [], 0
-    for block in (b for body in bodies for b in re.split(r"\n(?=\.LBB\d+_\d+:)", body)):
-        lines = block.split("\n")
-        head = lines[0].split(":")[0]
-        end = next((i for i, l in enumerate(lines)
-                    if re.search(r"s_cbranch_\w+ " + re.escape(head) + r"\b", l)), None)
-        if end is None:
-            continue
-        loop = lines[:end + 1]
-        mfma = sum("v_mfma" in l for l in loop)
-        if mfma < 16 or not any("global_load_lds" in l for l in loop):
-            continue
-        seen += 1
-        scratch = [l.strip() for l in loop if "scratch_" in l]
-        waits = [l.strip() for l in loop if re.search(r"s_waitcnt.*vmcnt\(\d+\)", l)]
-        foreign = [w for w in waits if "vmcnt(22)" not in w]
-        if verbose:
-            print(f"king_filter_kernel: loop {head} ({mfma} MFMAs): scratch {len(scratch)}, "
-                  f"vmcnt waits {waits}")
-        if scratch or foreign:
-            problems.append(f"king_filter_kernel, loop {head}: scratch {scratch[:2]}, waits {foreign}")
-    if seen == 0:
-        problems.append("king_filter_kernel: no LDS-DMA loop found (listing format changed?)")
-    return problems
-
-
-def check_mfma_loops(asm_path: Path, verbose: bool = False):
-    """The LDS-DMA requests of king_mfma.hip are inline asm the compiler's wait-count
-    pass does not see, so ANY wait it inserts on the vector-memory counter inside
-    such a loop (for a spill reload or a load of its own still in flight at loop
-    entry) drains the whole prefetch pipeline every k-step -- 10 % of a launch the
-    one time it happened (round 2, full form).  Returns the offending loops: blocks
-    with LDS-DMA and >= 16 MFMAs that hold a scratch instruction or a vmcnt wait
-    other than the hand-counted ones."""
-    import re
-    text = Path(asm_path).read_text()
-    funcs = re.split(r"\n(?=_ZN6cuking12_GLOBAL__N_116king_mfma_kernel\w+:)", text)[1:]
+    funcs = re.split(r"\n(?=" + kernel_re + r"\w*:)", text)[1:]
     if not funcs:
-        return [f"no king_mfma_kernel in {asm_path}"]
+        return [f"no {kernel} in {asm_path}"]
+    counted = ("v_mfma", "global_load_lds", "ds_read", "v_and", "s_waitcnt", "s_barrier")
     problems = []
     for f in funcs:
-        m = re.match(r"_ZN6cuking12_GLOBAL__N_116king_mfma_kernelILb(\d)ELb(\d)ELb(\d)", f)
-        label = f"king_mfma_kernel<FULL={m.group(1)}, SPLIT={m.group(2)}, N4={m.group(3)}>"
+        label = label_of(f)
         body = f.split(".Lfunc_end")[0]
         seen = 0
         for block in re.split(r"\n(?=\.LBB\d+_\d+:)", body):
@@ -176,18 +142,38 @@ def check_mfma_loops(asm_path: Path, verbose: bool = False):
             seen += 1
             scratch = [l.strip() for l in loop if "scratch_" in l]
             waits = [l.strip() for l in loop if re.search(r"s_waitcnt.*vmcnt\(\d+\)", l)]
-            # (hand-counted: 16 = four stages in flight (full form); 24 = six (lean form,
-            #  paired hand-over); 20 = the four-product form's hand-over)
             foreign = [w for w in waits
-                       if not any(f"vmcnt({n})" in w for n in (16, 20, 24))]
+                       if not any(f"vmcnt({n})" in w for n in allowed_vmcnt)]
             if verbose:
-                print(f"{label}: loop {head} ({mfma} MFMAs): scratch {len(scratch)}, "
+                counts = ", ".join(f"{k} {sum(k in l for l in loop)}" for k in counted)
+                print(f"{label}: loop {head} ({counts}): scratch {len(scratch)}, "
                       f"vmcnt waits {waits}")
             if scratch or foreign:
                 problems.append(f"{label}, loop {head}: scratch {scratch[:2]}, waits {foreign}")
         if seen == 0:
             problems.append(f"{label}: no LDS-DMA loop found (listing format changed?)")
     return problems
+
+
+def check_filter_loop(asm_path: Path, verbose: bool = False):
+    """king_filter_kernel (king_filter.hip): its k-loops hold one hand-counted wait, 22
+    requests in flight at a hand-over."""
+    return check_dma_loops(asm_path, "king_filter_kernel",
+                           r"_ZN6cuking12_GLOBAL__N_1\d+king_filter_kernelE", (22,),
+                           lambda f: "king_filter_kernel", verbose)
+
+
+def check_mfma_loops(asm_path: Path, verbose: bool = False):
+    """king_mfma_kernel (king_mfma.hip), every form.  Hand-counted: 16 = four stages in
+    flight (full form); 24 = six (lean form, paired hand-over); 20 = the four-product
+    form's hand-over."""
+    import re
+
+    def label(f):
+        m = re.match(r"_ZN6cuking12_GLOBAL__N_116king_mfma_kernelILb(\d)ELb(\d)ELb(\d)", f)
+        return f"king_mfma_kernel<FULL={m.group(1)}, SPLIT={m.group(2)}, N4={m.group(3)}>"
+    return check_dma_loops(asm_path, "king_mfma_kernel",
+                           r"_ZN6cuking12_GLOBAL__N_116king_mfma_kernel", (16, 20, 24), label, verbose)
 
 
 def arrow_flags():

@@ -15,6 +15,22 @@ namespace cuking {
 typedef __attribute__((address_space(3))) void *lds_void_ptr;
 typedef const __attribute__((address_space(1))) void *global_void_ptr;
 
+// Control words, tickets and running totals that workgroups share: relaxed, device scope --
+// the value alone matters, nothing is ordered against it (where a payload goes with it, the
+// caller fences).
+template <typename T>
+__device__ __forceinline__ T relaxed_load(const T *p) {
+  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+template <typename T, typename V>
+__device__ __forceinline__ void relaxed_store(T *p, V v) {
+  __hip_atomic_store(p, (T)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+template <typename T, typename V>
+__device__ __forceinline__ T relaxed_add(T *p, V v) {  // returns the value before
+  return __hip_atomic_fetch_add(p, (T)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
 // cuking.cu:289-294: two float32 roundings (divide, add).  Numerator and
 // denominator are exact integers (< 2^24 for < 2^22 sites); the divide is the
 // IEEE-correct one (no fast-math, see build flags).  min == 0 gives -inf or

@@ -56,14 +56,14 @@
 // them like on u -- as long as every partial of such a difference is itself u~ over a
 // set of sites (<= 2.5 per site): prefix_u_of() subtracts before it adds the wrapped end.
 //
-// Round 4, all inside filter_tile() below: check points inside the k loop (a tile
-// none of whose pairs can still become a candidate leaves, and so does one that
-// holds a few, handing them to the candidate list: "Check points"); rotated tiles
-// (a tile starts its k loop where the tiles of its XCD are and wraps around, so
-// that they share their operands through the XCD's L2: "Rotated tiles"); tiles
-// that give up leave for a gated launch of the four-product kernel instead of
-// appending to a list.  (A persistent launch -- one resident workgroup per CU taking
-// tile after tile -- was measured 1.2 % slower and removed: r04_tile_gaps.txt.)
+// A workgroup's tile is filter_tile(): take_tile, launch_verdict (tiles that give up leave
+// for a gated launch of the four-product kernel), plan_checks ("Check points": a tile none
+// of whose pairs can still become a candidate leaves inside the k loop, and so does one that
+// holds a few, handing them over; "Rotated tiles": a tile starts where the tiles of its XCD
+// are and wraps around, so that they share their operands through the XCD's L2), the k loop
+// with check_sweep at its check points, leave_early, reduce_pieces, emit_candidates.  (A
+// persistent launch -- one resident workgroup per CU taking tile after tile -- was measured
+// 1.2 % slower and removed: r04_tile_gaps.txt.)
 //
 // Workgroup = 256 x 256 pairs, 4 wavefronts of 128 x 128 = 4 x 4 MFMA blocks (256
 // accumulator registers), k-step = 256 sites = 4 slices of 64, 5 LDS stages of
@@ -220,11 +220,9 @@ __global__ __launch_bounds__(256) void sample_stats_kernel(
     // (the cohort's sums feed a choice, not a result: a sample of the samples will do --
     //  three device-scope atomics on three addresses for EVERY sample cost 3 ms at 100k)
     if (src != kNoPair && ((blockIdx.x & 15) == 0 || gridDim.x < 64)) {
-      __hip_atomic_fetch_add(sums, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_fetch_add(sums + 1, (unsigned long long)mc, __ATOMIC_RELAXED,
-                             __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_fetch_add(sums + 2, (unsigned long long)hc, __ATOMIC_RELAXED,
-                             __HIP_MEMORY_SCOPE_AGENT);
+      relaxed_add(sums, 1ull);
+      relaxed_add(sums + 1, (unsigned long long)mc);
+      relaxed_add(sums + 2, (unsigned long long)hc);
     }
   }
 }
@@ -248,30 +246,59 @@ __device__ __forceinline__ v8i tfrag(const uint4 w, uint32_t mask) {
   return r;
 }
 
-// One LDS-DMA request: lane l's 16 bytes of SRC + OFF land at DST + OFF + 16 l
-// (the immediate offset moves source and destination alike).
-#define F_ISSUE(SRC, DST, OFF)                                                 \
-  asm volatile("s_mov_b32 m0, %0\n\t"                                          \
-               "s_nop 0\n\t"                                                   \
-               "global_load_lds_dwordx4 %1, %2 offset:" #OFF                   \
-               :                                                               \
-               : "s"(DST), "v"(lane16), "s"(SRC)                               \
-               : "memory", "m0")
+// ---- The phases of a tile, in the order filter_tile() (at the end) calls them: all inlined into
+// the one kernel; each sees of the others what its parameters and its result say.
+// The tile (or the piece of the k range of one) a workgroup has taken.  Wave-uniform.
+struct Tile {
+  bool split;            // a piece of one of the launch's last tiles (king_common.h, fsplit_*)
+  uint32_t bid;          // the tile's index within the launch
+  uint32_t tr, tc;       // its row and column in the tile space
+  uint32_t part, piece;  // split: the part of the k range, the piece's index within the launch
+};
 
-// One tile (or one piece of the k range of a tile) of the launch: what workgroup `wg` of a
-// grid of one workgroup per tile does.  Returns 1 when there was nothing left to take (the
-// dynamic tail is through: uniform, before anything else), 0 otherwise -- wavefronts return
-// from the epilogue one by one.  lds: [kStages][side][k-half][unit][256].
-__device__ __forceinline__ int filter_tile(const TiledArgs &a, const uint32_t wg, uint4 *const lds) {
+// Where a thread sits in the workgroup's 2 x 2 wavefronts and in the MFMA's operands.
+struct Lanes {
+  uint32_t lane, wave;
+  uint32_t wy, wx;  // the wavefront's quadrant
+  uint32_t g, lr;   // k-half of the MFMA operand, row / column inside a block
+};
+__device__ __forceinline__ Lanes lanes_of_thread() {
+  const uint32_t lane = threadIdx.x & 63;
+  const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  return Lanes{lane, wave, wave >> 1, wave & 1, lane >> 5, lane & 31};
+}
+
+// C layout of the 32 x 32 MFMA: register r of a lane holds column lane & 31 of this row
+// (g = lane >> 5).
+__device__ __forceinline__ uint32_t c_row(int r, uint32_t g) { return (r & 3) + 8 * (r >> 2) + 4 * g; }
+
+// The level of the bound for the cohort's unrelated pairs: its mean m (1 + m / (2 h (1 - m)))
+// at the cohort's missing rate m and het rate h (from its sums: samples, missing calls, het
+// calls) and its standard deviation 1 / sqrt(sites) (tools/bound_tiers.py,
+// profiles/r04_bound_tiers.txt).  False for a cohort without samples or het calls.
+__device__ __forceinline__ bool bound_level(const unsigned long long *cohort_sums, float sites,
+                                            float *mean, float *sigma) {
+  const float ns = (float)cohort_sums[0], nm = (float)cohort_sums[1], nh = (float)cohort_sums[2];
+  if (!(ns > 0.f && nh > 0.f)) return false;
+  const float m = nm / (ns * sites), h = nh / (ns * sites);
+  *mean = m * (1.f + m / (2.f * h * (1.f - m)));
+  *sigma = rsqrtf(sites);
+  return true;
+}
+
+// Which tile workgroup `wg` of a grid of one workgroup per tile takes.  False (uniform, before
+// anything else) when there is none: the dynamic tail is through, or the workgroup is padding.
+__device__ __forceinline__ bool take_tile(const TiledArgs &a, const uint32_t wg, uint4 *const lds,
+                                          Tile *t) {
   uint32_t bid = wg;
   // Remainder of a short launch (king_common.h, fsplit_*): piece `part` of the k
   // range of one of the launch's last tiles.
-  const bool split = a.fsplit_parts != 0 && wg >= a.fsplit_first;
-  uint32_t part = 0, piece = 0;
-  if (split) {
-    piece = wg - a.fsplit_first;
-    part = __builtin_amdgcn_readfirstlane(piece % a.fsplit_parts);
-    bid = a.fsplit_tile0 + piece / a.fsplit_parts;
+  t->split = a.fsplit_parts != 0 && wg >= a.fsplit_first;
+  t->part = t->piece = 0;
+  if (t->split) {
+    t->piece = wg - a.fsplit_first;
+    t->part = __builtin_amdgcn_readfirstlane(t->piece % a.fsplit_parts);
+    bid = a.fsplit_tile0 + t->piece / a.fsplit_parts;
   } else
   if (a.dyn_tiles != 0 && wg >= a.launch_tiles) {
     // dynamic tail (king_common.h): the next of the launch's last dyn_tiles tiles
@@ -279,348 +306,145 @@ __device__ __forceinline__ int filter_tile(const TiledArgs &a, const uint32_t wg
     // XCD that gets through its static share early takes more of these.  (The
     // counter is filter_ctrl[2], zeroed in front of every launch.)
     uint32_t *slot = reinterpret_cast<uint32_t *>(lds);
-    if (threadIdx.x == 0)
-      *slot = __hip_atomic_fetch_add(a.filter_ctrl + kCtrlDyn, 1u, __ATOMIC_RELAXED,
-                                     __HIP_MEMORY_SCOPE_AGENT);
+    if (threadIdx.x == 0) *slot = relaxed_add(a.filter_ctrl + kCtrlDyn, 1u);
     __syncthreads();
-    const uint32_t t = __builtin_amdgcn_readfirstlane(*slot);
+    const uint32_t next = __builtin_amdgcn_readfirstlane(*slot);
     __syncthreads();  // the word is stage memory from here on
-    if (t >= a.dyn_tiles) return 1;  // uniform: nothing left
-    bid = a.launch_tiles + t;
+    if (next >= a.dyn_tiles) return false;  // uniform: nothing left
+    bid = a.launch_tiles + next;
   } else if (a.xcd_chunk == 1) {
     // patches of 32 consecutive tiles dealt round-robin to the XCDs (king_common.h)
     const uint32_t x = bid & 7, j = bid >> 3;
     bid = (((j >> 5) * 8 + x) << 5) + (j & 31);
-    if (bid >= a.launch_tiles) return 0;  // padding (uniform)
+    if (bid >= a.launch_tiles) return false;  // padding (uniform)
   }
-  bid = __builtin_amdgcn_readfirstlane(bid);
+  t->bid = __builtin_amdgcn_readfirstlane(bid);
   uint32_t tr, tc;
-  if (!decode_tile_space(a, a.tile_begin + bid, &tr, &tc)) return 0;  // uniform
-  tr = __builtin_amdgcn_readfirstlane(tr);
-  tc = __builtin_amdgcn_readfirstlane(tc);
+  if (!decode_tile_space(a, a.tile_begin + t->bid, &tr, &tc)) return false;  // uniform
+  t->tr = __builtin_amdgcn_readfirstlane(tr);
+  t->tc = __builtin_amdgcn_readfirstlane(tc);
+  return true;
+}
 
-  const uint32_t lane = threadIdx.x & 63;
-  const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const uint32_t wy = wave >> 1, wx = wave & 1;  // the wavefront's quadrant
-  // When the bound does not thin this cohort out (a threshold inside the noise of
-  // unrelated pairs, heavy missingness) nearly every quadrant ends on the dense list
-  // anyway: once most of at least 512 finished quadrants of the launch have (or their
-  // tiles have left at check 0, below), every remaining tile leaves at once -- it
-  // touches nothing, and the fallback launch behind this one (the four-product kernel
-  // over the chunk in its own order, king_mfma.hip persistent mode) computes every tile
-  // that has not set its tile_done flag.  The worst case costs the exact kernel's time
-  // plus the first round of this one (short launches: plus an eighth of it, check 0).
-  uint32_t xcd_pos = 0;  // the k-step the tiles of this XCD are at (rotated tiles)
-  if (!split && a.tile_done != nullptr) {
-    // ONE decision per workgroup (the counters move while the wavefronts read them,
-    // and a wavefront that left alone would take its quarter of every stage's
-    // requests with it): thread 0 reads, the stage memory carries the verdict.
-    uint32_t *verdict = reinterpret_cast<uint32_t *>(lds);
-    if (threadIdx.x == 0) {
-      uint32_t leave = __hip_atomic_load(a.filter_ctrl + kCtrlAllLeave, __ATOMIC_RELAXED,
-                                         __HIP_MEMORY_SCOPE_AGENT);
-      // The cohort's own verdict first: where the bound's level for unrelated pairs (from the
-      // cohort's mean missing and het rates, as for the check points below) lies four
-      // standard deviations above the threshold, it lets every pair through, whatever the
-      // tile -- the first tiles need not find that out by computing their product.
-      if (leave == 0 && a.cohort_sums != nullptr && a.check_steps != nullptr) {
-        const float ns = (float)a.cohort_sums[0], nm = (float)a.cohort_sums[1],
-                    nh = (float)a.cohort_sums[2];
-        if (ns > 0.f && nh > 0.f) {
-          const float sites = 32.f * (float)a.geo.k_words;
-          const float m = nm / (ns * sites), h = nh / (ns * sites);
-          if (m * (1.f + m / (2.f * h * (1.f - m))) - 4.f * rsqrtf(sites) > a.kin_threshold &&
-              (a.check1 >> 16) != 0) {
-            leave = 1;
-            __hip_atomic_store(a.filter_ctrl + kCtrlAllLeave, 1u, __ATOMIC_RELAXED,
-                               __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(a.filter_ctrl + kCtrlGate, 1u, __ATOMIC_RELAXED,
-                               __HIP_MEMORY_SCOPE_AGENT);
-          }
-        }
-      }
-      if (leave == 0) {
-        const uint32_t dense_so_far =
-            __hip_atomic_load(a.filter_ctrl + kCtrlDense, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) +
-            __hip_atomic_load(a.filter_ctrl + kCtrlLeft, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const uint32_t finished = __hip_atomic_load(a.filter_ctrl + kCtrlFinished, __ATOMIC_RELAXED,
-                                                    __HIP_MEMORY_SCOPE_AGENT);
-        if (finished >= 512 && 2 * dense_so_far > finished) {
-          leave = 1;
-          __hip_atomic_store(a.filter_ctrl + kCtrlAllLeave, 1u, __ATOMIC_RELAXED,
-                             __HIP_MEMORY_SCOPE_AGENT);
-          __hip_atomic_store(a.filter_ctrl + kCtrlGate, 1u, __ATOMIC_RELAXED,
-                             __HIP_MEMORY_SCOPE_AGENT);
-        }
-      }
-      verdict[0] = leave;
+// The launch-wide verdict, for a whole tile of a launch with a fallback (a.tile_done): true
+// when the tile gives up.
+// When the bound does not thin this cohort out (a threshold inside the noise of
+// unrelated pairs, heavy missingness) nearly every quadrant ends on the dense list
+// anyway: once most of at least 512 finished quadrants of the launch have (or their
+// tiles have left at check 0, below), every remaining tile leaves at once -- it
+// touches nothing, and the fallback launch behind this one (the four-product kernel
+// over the chunk in its own order, king_mfma.hip persistent mode) computes every tile
+// that has not set its tile_done flag.  The worst case costs the exact kernel's time
+// plus the first round of this one (short launches: plus an eighth of it, check 0).
+// *xcd_pos: the k-step the tiles of this XCD are at (rotated tiles, plan_checks()).
+__device__ __forceinline__ bool launch_verdict(const TiledArgs &a, const uint32_t wg,
+                                               uint4 *const lds, uint32_t *xcd_pos) {
+  // ONE decision per workgroup (the counters move while the wavefronts read them,
+  // and a wavefront that left alone would take its quarter of every stage's
+  // requests with it): thread 0 reads, the stage memory carries the verdict.
+  uint32_t *verdict = reinterpret_cast<uint32_t *>(lds);
+  if (threadIdx.x == 0) {
+    uint32_t leave = relaxed_load(a.filter_ctrl + kCtrlAllLeave);
+    // (the first to find out says so: to the tiles behind it, and to the fallback launch)
+    auto all_leave = [&] {
+      leave = 1;
+      relaxed_store(a.filter_ctrl + kCtrlAllLeave, 1u);
+      relaxed_store(a.filter_ctrl + kCtrlGate, 1u);
+    };
+    // The cohort's own verdict first: where the bound's level for unrelated pairs (from the
+    // cohort's mean missing and het rates, as for the check points below) lies four
+    // standard deviations above the threshold, it lets every pair through, whatever the
+    // tile -- the first tiles need not find that out by computing their product.
+    float mean, sigma;
+    if (leave == 0 && a.cohort_sums != nullptr && a.check_steps != nullptr &&
+        bound_level(a.cohort_sums, 32.f * (float)a.geo.k_words, &mean, &sigma) &&
+        mean - 4.f * sigma > a.kin_threshold && (a.check1 >> 16) != 0)
+      all_leave();
+    if (leave == 0) {
+      const uint32_t dense_so_far =
+          relaxed_load(a.filter_ctrl + kCtrlDense) + relaxed_load(a.filter_ctrl + kCtrlLeft);
+      const uint32_t finished = relaxed_load(a.filter_ctrl + kCtrlFinished);
+      if (finished >= 512 && 2 * dense_so_far > finished) all_leave();
     }
-    // Rotated tiles (below): where the tiles of this XCD are -- workgroups go to the XCDs
-    // round-robin by their index.  Every slot says where one of them was and when; brought
-    // forward to now by the measured k-step time, the most advanced one counts.
-    if (a.rotate == 1 && threadIdx.x < kPosSlots) {
-      const uint32_t x = wg & 7;
-      const unsigned long long said = __hip_atomic_load(
-          reinterpret_cast<const unsigned long long *>(a.filter_ctrl + kCtrlPos) + x * kPosSlots +
-              threadIdx.x,
-          __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      const uint32_t ticks16 = __hip_atomic_load(a.filter_ctrl + kCtrlStepTicks + x,
-                                                 __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      uint32_t pos = (uint32_t)(said >> 32);
-      const uint32_t ago = (uint32_t)__builtin_amdgcn_s_memrealtime() - (uint32_t)said;
-      if (said != 0 && ticks16 != 0 && ago < 16384u)
-        pos += ago * 16u / ticks16;
-      verdict[1 + threadIdx.x] = pos;
-    }
-    __syncthreads();
-    const bool give_up = verdict[0] != 0;
-    if (a.rotate == 1) {
+    verdict[0] = leave;
+  }
+  // Rotated tiles (below): where the tiles of this XCD are -- workgroups go to the XCDs
+  // round-robin by their index.  Every slot says where one of them was and when; brought
+  // forward to now by the measured k-step time, the most advanced one counts.
+  if (a.rotate == 1 && threadIdx.x < kPosSlots) {
+    const uint32_t x = wg & 7;
+    const unsigned long long said = relaxed_load(
+        reinterpret_cast<const unsigned long long *>(a.filter_ctrl + kCtrlPos) + x * kPosSlots +
+        threadIdx.x);
+    const uint32_t ticks16 = relaxed_load(a.filter_ctrl + kCtrlStepTicks + x);
+    uint32_t pos = (uint32_t)(said >> 32);
+    const uint32_t ago = (uint32_t)__builtin_amdgcn_s_memrealtime() - (uint32_t)said;
+    if (said != 0 && ticks16 != 0 && ago < 16384u)
+      pos += ago * 16u / ticks16;
+    verdict[1 + threadIdx.x] = pos;
+  }
+  __syncthreads();
+  const bool give_up = verdict[0] != 0;
+  uint32_t pos = 0;
+  if (a.rotate == 1) {
 #pragma unroll
-      for (uint32_t k = 0; k < kPosSlots; ++k) xcd_pos = max(xcd_pos, verdict[1 + k]);
-    }
-    __syncthreads();  // the words are stage memory from here on
-    if (give_up) {  // uniform across the workgroup; tile_done stays 0
-      // (its quadrants count as handed over: "filter_dense_quadrants")
-      if (threadIdx.x == 0)
-        __hip_atomic_fetch_add(a.filter_totals + kTotalDense, 4ull, __ATOMIC_RELAXED,
-                               __HIP_MEMORY_SCOPE_AGENT);
-      return 0;
-    }
+    for (uint32_t k = 0; k < kPosSlots; ++k) pos = max(pos, verdict[1 + k]);
   }
-  xcd_pos = __builtin_amdgcn_readfirstlane(xcd_pos);
-  const uint32_t g = lane >> 5;                  // k-half of the MFMA operand
-  const uint32_t lr = lane & 31;                 // row / column inside a block
-  uint32_t lane16 = lane * 16;
-  const uint32_t s_stride = a.geo.s_stride;
-  // k-steps of 256 sites: all of them, or this piece's share
-  const uint32_t all_steps = a.geo.k_words / (4 * kUnits);
-  // (wave-uniform, but divisions run in vector registers: pinned to SGPRs for the
-  //  request addresses)
-  const uint32_t k_first = __builtin_amdgcn_readfirstlane(
-      split ? part * all_steps / a.fsplit_parts : 0u);
-  const uint32_t num_steps = __builtin_amdgcn_readfirstlane(
-      split ? (part + 1) * all_steps / a.fsplit_parts - k_first : all_steps);
-  const uint4 *g_rows = a.t2 + (uint64_t)tr * kT;
-  const uint4 *g_cols = a.t2 + a.geo.col_base + (uint64_t)tc * kT;
+  *xcd_pos = __builtin_amdgcn_readfirstlane(pos);
+  __syncthreads();  // the words are stage memory from here on
+  // uniform across the workgroup; tile_done stays 0
+  // (its quadrants count as handed over: "filter_dense_quadrants")
+  if (give_up && threadIdx.x == 0) relaxed_add(a.filter_totals + kTotalDense, 4ull);
+  return give_up;
+}
 
-  // The masks of the two site sets of a T2 word and the scale of set B (king_common.h:
-  // +-2.0 x 2^-2 per operand, so that a set-B product weighs 1/4 like a set-A product),
-  // set once and pinned.
-  uint32_t mT, mA;
-  asm volatile("s_mov_b32 %0, 0xcccccccc" : "=s"(mT));
-  asm volatile("s_mov_b32 %0, 0x33333333" : "=s"(mA));
-  int scaleB;
-  asm volatile("v_mov_b32 %0, 0x7d7d7d7d" : "=v"(scaleB));
-
-  // LDS-DMA: wavefront (side, k-half) fetches that quarter of a stage: 2 units x
-  // 4 runs of 64 samples, 1 KiB each.  Unit c of k-step s, k-half h is unit
-  // 4 s + 2 h + c of the T2 layout (the order of the sites inside k does not
-  // matter as long as rows and columns agree); every unit feeds TWO slices of 64
-  // sites per k-half: its bits 2-3 (set B) and its bits 0-1 (set A).
-  const uint32_t dma_side = wave >> 1, dma_h = wave & 1;
-  const uint32_t row_bytes = s_stride * 16;  // one unit of the layout
-  const char *const g_wave = reinterpret_cast<const char *>(
-      (dma_side ? g_cols : g_rows) + ((uint64_t)2 * kUnits * k_first + kUnits * dma_h) * s_stride);
-  const uint32_t l_wave = (uint32_t)(uintptr_t)(lds_void_ptr)(
-      lds + ((dma_side * 2 + dma_h) * kUnits) * kSliceU4);
-  struct Addr { const char *src; uint32_t dst; };  // of unit 0; unit 1: + row_bytes, + 4 KiB
-  const uint32_t kstep_bytes = 2 * kUnits * row_bytes;
-  // The pipeline runs over one SEGMENT of the piece's k-steps at a time (one segment,
-  // unless the tile has check points, below): `seg_src` is the wavefront's first request
-  // of the segment, `seg_steps` its k-steps.
-  const char *seg_src = g_wave;
-  uint32_t seg_steps = num_steps;
-  // (a rotated tile, below: k-step `seg_wrap` of the segment is the bitset's FIRST again --
-  //  all_steps k-steps back; 32-bit scalar selects and one signed product: a select between
-  //  two 64-bit addresses goes through vector registers, which the scalar pins cannot take)
-  uint32_t seg_wrap = 0xFFFFFFFFu;
-  auto addr_of = [&](uint32_t step, uint32_t buf) {
-    Addr pa;
-    if (step >= seg_steps) step = seg_steps - 1;  // clamped repeats (see king_mfma.hip)
-    const int32_t rel = (int32_t)step - (int32_t)(step >= seg_wrap ? all_steps : 0u);
-    pa.src = seg_src + (int64_t)rel * (int64_t)kstep_bytes;
-    pa.dst = l_wave + buf * (kStageU4 * 16);
-    asm volatile("" : "+s"(pa.src), "+s"(pa.dst));
-    return pa;
-  };
-  auto addr_next = [&](const Addr &cur, uint32_t step, uint32_t buf) {
-    Addr pa;
-    const int32_t adv = (int32_t)(step < seg_steps ? 1u : 0u) -
-                        (int32_t)(step == seg_wrap ? all_steps : 0u);
-    pa.src = cur.src + (int64_t)adv * (int64_t)kstep_bytes;
-    pa.dst = l_wave + buf * (kStageU4 * 16);
-    asm volatile("" : "+s"(pa.src), "+s"(pa.dst));
-    return pa;
-  };
-  // The four requests of unit c of the stage `pa` names.
-#define F_ISSUE4(PA, C)                                                        \
-  {                                                                            \
-    const char *src_ = (PA).src + (C) * row_bytes;                             \
-    const uint32_t dst_ = (PA).dst + (C) * (kSliceU4 * 16);                    \
-    F_ISSUE(src_, dst_, 0);                                                    \
-    F_ISSUE(src_, dst_, 1024);                                                 \
-    F_ISSUE(src_, dst_, 2048);                                                 \
-    F_ISSUE(src_, dst_, 3072);                                                 \
-  }
-
-  v16f acc[4][4];
-#pragma unroll
-  for (int bi = 0; bi < 4; ++bi)
-#pragma unroll
-    for (int bj = 0; bj < 4; ++bj)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[bi][bj][r] = 0.f;
-
-  // This lane's operand words inside a stage (uint4 units).
-  uint32_t row_off = ((0 * 2 + g) * kUnits) * kSliceU4 + wy * 128 + lr;
-  uint32_t col_off = ((1 * 2 + g) * kUnits) * kSliceU4 + wx * 128 + lr;
-  asm volatile("" : "+v"(row_off), "+v"(col_off), "+v"(lane16));
-  v8i FA[2][4], FB[2][4];  // T fragments [slice parity][block]
-  uint4 RAW[8];            // the words of one unit: rows 0-3, columns 4-7
-#define F_READ(K, BUF, C)                                                      \
-  RAW[K] = lds[(BUF) * kStageU4 + ((K) < 4 ? row_off : col_off) + (C) * kSliceU4 + ((K) & 3) * 32];
-// (plain ANDs: nothing but data orders them against the MFMAs, and
-// left alone the compiler builds every fragment right behind its LDS read, i.e.
-// waits for the read it has just issued.  The empty asm statements tie a build
-// to the place it is written in: not above the pin of its input, not below the
-// pin of its result -- as in king_mfma.hip.)
-#define F_PIN4(W) asm volatile("" : "+v"((W).x), "+v"((W).y), "+v"((W).z), "+v"((W).w));
-#define F_PINF(F) asm volatile("" : "+v"((F)[0]), "+v"((F)[1]), "+v"((F)[2]), "+v"((F)[3]));
-// Set B of word K: bits 2-3 of every nibble as they are.
-#define F_BUILD_B(NXT, K)                                                      \
-  F_PIN4(RAW[K])                                                               \
-  if ((K) < 4) {                                                               \
-    FA[NXT][(K) & 3] = tfrag(RAW[K], mT);                                      \
-    F_PINF(FA[NXT][(K) & 3])                                                   \
-  } else {                                                                     \
-    FB[NXT][(K) & 3] = tfrag(RAW[K], mT);                                      \
-    F_PINF(FB[NXT][(K) & 3])                                                   \
-  }
-// Set A of word K: bits 0-1 of every nibble as they are (1 + T: 0 / 0.5 / 1.0 in fp4).
-#define F_BUILD_A(NXT, K)                                                      \
-  F_PIN4(RAW[K])                                                               \
-  if ((K) < 4) {                                                               \
-    FA[NXT][(K) & 3] = tfrag(RAW[K], mA);                                      \
-    F_PINF(FA[NXT][(K) & 3])                                                   \
-  } else {                                                                     \
-    FB[NXT][(K) & 3] = tfrag(RAW[K], mA);                                      \
-    F_PINF(FB[NXT][(K) & 3])                                                   \
-  }
-// (fragment set 0 holds set B: the scaled instruction; fragment set 1 holds set A)
-#define F_MMA(CUR, BI, BJ)                                                     \
-  acc[BI][BJ] = (CUR) == 0 ? mma_scaled(FA[CUR][BI], FB[CUR][BJ], acc[BI][BJ], scaleB) \
-                           : mma(FA[CUR][BI], FB[CUR][BJ], acc[BI][BJ]);
-#define F_BAR __builtin_amdgcn_sched_barrier(0);
-  // Slice B of unit c (fragment set CUR): 16 MFMAs; in their gaps the set-A
-  // fragments of the same words (4 VALU per fragment, in every second gap: the
-  // gaps that take a request stay free) and two requests.
-#define F_SLICE_B(CUR, NXT, PA, DC, OFF0, OFF1)                                \
-  {                                                                            \
-    const char *src_ = (PA).src + (DC) * row_bytes;                            \
-    const uint32_t dst_ = (PA).dst + (DC) * (kSliceU4 * 16);                   \
-    F_ISSUE(src_, dst_, OFF0);                                                 \
-    F_MMA(CUR, 0, 0) F_BAR                                                     \
-    F_BUILD_A(NXT, 0) F_MMA(CUR, 0, 1) F_BAR                                   \
-    F_MMA(CUR, 0, 2) F_BAR                                                     \
-    F_BUILD_A(NXT, 1) F_MMA(CUR, 0, 3) F_BAR                                   \
-    F_MMA(CUR, 1, 0) F_BAR                                                     \
-    F_BUILD_A(NXT, 2) F_MMA(CUR, 1, 1) F_BAR                                   \
-    F_MMA(CUR, 1, 2) F_BAR                                                     \
-    F_BUILD_A(NXT, 3) F_MMA(CUR, 1, 3) F_BAR                                   \
-    F_ISSUE(src_, dst_, OFF1);                                                 \
-    F_MMA(CUR, 2, 0) F_BAR                                                     \
-    F_BUILD_A(NXT, 4) F_MMA(CUR, 2, 1) F_BAR                                   \
-    F_MMA(CUR, 2, 2) F_BAR                                                     \
-    F_BUILD_A(NXT, 5) F_MMA(CUR, 2, 3) F_BAR                                   \
-    F_MMA(CUR, 3, 0) F_BAR                                                     \
-    F_BUILD_A(NXT, 6) F_MMA(CUR, 3, 1) F_BAR                                   \
-    F_MMA(CUR, 3, 2) F_BAR                                                     \
-    F_BUILD_A(NXT, 7) F_MMA(CUR, 3, 3) F_BAR                                   \
-  }
-  // Slice A of a unit (fragment set CUR): 16 MFMAs; in the gaps of the first
-  // eight the LDS reads of the NEXT unit's words (RBUF, RC; behind the stage
-  // hand-over if SYNC: that read is the first of a new stage) and two requests,
-  // in the gaps of the last eight that unit's set-B fragments.
-#define F_SLICE_A(CUR, NXT, RBUF, RC, SYNC, PA, DC, OFF0, OFF1)                \
-  {                                                                            \
-    if (SYNC) {                                                                \
-      __builtin_amdgcn_s_waitcnt(vmcnt_imm(kSyncVm));                          \
-      __syncthreads();                                                         \
-    }                                                                          \
-    const char *src_ = (PA).src + (DC) * row_bytes;                            \
-    const uint32_t dst_ = (PA).dst + (DC) * (kSliceU4 * 16);                   \
-    F_READ(0, RBUF, RC) F_READ(1, RBUF, RC)                                    \
-    F_ISSUE(src_, dst_, OFF0);                                                 \
-    F_MMA(CUR, 0, 0) F_MMA(CUR, 0, 1) F_BAR                                    \
-    F_READ(2, RBUF, RC) F_READ(3, RBUF, RC)                                    \
-    F_MMA(CUR, 0, 2) F_MMA(CUR, 0, 3) F_BAR                                    \
-    F_READ(4, RBUF, RC) F_READ(5, RBUF, RC)                                    \
-    F_ISSUE(src_, dst_, OFF1);                                                 \
-    F_MMA(CUR, 1, 0) F_MMA(CUR, 1, 1) F_BAR                                    \
-    F_READ(6, RBUF, RC) F_READ(7, RBUF, RC)                                    \
-    F_MMA(CUR, 1, 2) F_MMA(CUR, 1, 3) F_BAR                                    \
-    F_BUILD_B(NXT, 0) F_MMA(CUR, 2, 0) F_BAR                                   \
-    F_BUILD_B(NXT, 1) F_MMA(CUR, 2, 1) F_BAR                                   \
-    F_BUILD_B(NXT, 2) F_MMA(CUR, 2, 2) F_BAR                                   \
-    F_BUILD_B(NXT, 3) F_MMA(CUR, 2, 3) F_BAR                                   \
-    F_BUILD_B(NXT, 4) F_MMA(CUR, 3, 0) F_BAR                                   \
-    F_BUILD_B(NXT, 5) F_MMA(CUR, 3, 1) F_BAR                                   \
-    F_BUILD_B(NXT, 6) F_MMA(CUR, 3, 2) F_BAR                                   \
-    F_BUILD_B(NXT, 7) F_MMA(CUR, 3, 3) F_BAR                                   \
-  }
-  // k-step s requests stage s + kStages - 1 into the buffer stage s - 1 left: every
-  // wavefront finished reading it before the hand-over of k-step s - 1.  The
-  // hand-over of k-step s (stage s + 1 must have landed) comes in its last slice:
-  // in flight then may be the stages after s + 1 and the requests of the newest one
-  // that the slices before the last have issued (kSyncVm: 2 x 8 + 6 = 22).
-#define F_KSTEP                                                                \
-  {                                                                            \
-    const uint32_t nbuf = buf == kStages - 1 ? 0 : buf + 1;                    \
-    F_SLICE_B(0, 1, pa, 0, 0, 1024)                                            \
-    F_SLICE_A(1, 0, buf, 1, false, pa, 0, 2048, 3072)                          \
-    F_SLICE_B(0, 1, pa, 1, 0, 1024)                                            \
-    F_SLICE_A(1, 0, nbuf, 0, true, pa, 1, 2048, 3072)                          \
-    pa = addr_next(pa, step + kStages, buf);                                   \
-    buf = nbuf;                                                                \
-    ++step;                                                                    \
-  }
-
-  // --- Check points (king_common.h).  X = sum over the sites of (g_i - g_j)^2 has only
-  // non-negative terms, so its sum over a PREFIX of the sites is a lower bound of X, and
-  // so is this kernel's bound of that prefix sum, u'_i + u'_j - 2 q' (u' over the prefix,
-  // sample_stats_kernel).  A pair can only pass the threshold when X < t min(|H_i|, |H_j|) +
-  // margin (|H| over ALL sites: the epilogue's own test): a tile none of whose 65,536 pairs
-  // satisfies u'_i + u'_j - 2 q' < that bound at the check point holds no record, whatever
-  // the remaining sites say -- it leaves.  For unrelated samples that happens from a share
-  // (1 - 2 thr) / (1 - 2 kappa) of the sites on, kappa = the level of the bound for unrelated
-  // pairs (their mean m (1 + m / (2 h (1 - m))) at missing rate m and het rate h, plus 4.6
-  // standard deviations 1 / sqrt(sites): tools/bound_tiers.py, profiles/r04_bound_tiers.txt):
-  // 0.88 of the sites at the default threshold and 1 % missing calls.  Every workgroup picks
-  // the same entry of the share menu from the cohort's sums.  (Check 0 is a FORECAST for
-  // short launches: the same test with the bound scaled to an eighth of the sites, counted
-  // per quadrant; a tile whose quadrants mostly look dense leaves for the exact kernel
-  // there instead of at its end.)  The pipeline is DRAINED at a check point -- the segment
-  // before it ends like a tile (every request landed, no fragment built ahead), the one
-  // behind it starts like a tile -- so that the check has the LDS for its per-sample
-  // values and the register file for its sweep, and the k loop's registers are not live
-  // across it: ~8 us per check of a 500 us tile.
-  //
-  // --- Rotated tiles.  The 32 tiles an XCD holds at a time are a patch of the tile space
-  // (8 rows x 4 columns: 12 strips of operands for 32 tiles), but they share those strips
-  // through the XCD's 4 MiB L2 only while they read the same k-steps at about the same
-  // time -- 21 k-steps of the patch fit.  Tiles that all start at k-step 0 do so in the
-  // first round of a launch and drift apart from there (L2 hit rate 0.36, 555 GB from the
-  // fabric per pass of configs[2]; one launch per round: 0.80 and 170 GB, and the chip
-  // holds 1.96-1.99 GHz instead of 1.86: tools/l2_probe.sh).  The order of the sites
-  // inside a sum does not matter, so a tile STARTS where the tiles of its XCD are: at the
-  // phase boundary (king_common.h phase_step: 128 phases) nearest to the k-step the most
-  // advanced of them has published, runs to the end of the sites, wraps around (a segment
-  // boundary like a check point's) and ends where it started.  A check point sits behind a
-  // share of the k-steps as before; the per-sample counts over "phases [p, p + e)" are
-  // differences of the cumulative counts sample_stats_kernel leaves.
+// --- Check points (king_common.h).  X = sum over the sites of (g_i - g_j)^2 has only
+// non-negative terms, so its sum over a PREFIX of the sites is a lower bound of X, and
+// so is this kernel's bound of that prefix sum, u'_i + u'_j - 2 q' (u' over the prefix,
+// sample_stats_kernel).  A pair can only pass the threshold when X < t min(|H_i|, |H_j|) +
+// margin (|H| over ALL sites: the epilogue's own test): a tile none of whose 65,536 pairs
+// satisfies u'_i + u'_j - 2 q' < that bound at the check point holds no record, whatever
+// the remaining sites say -- it leaves.  For unrelated samples that happens from a share
+// (1 - 2 thr) / (1 - 2 kappa) of the sites on, kappa = the level of the bound for unrelated
+// pairs (bound_level() above: its mean plus 4.6 standard deviations): 0.88 of the sites at
+// the default threshold and 1 % missing calls.  Every workgroup picks
+// the same entry of the share menu from the cohort's sums.  (Check 0 is a FORECAST for
+// short launches: the same test with the bound scaled to an eighth of the sites, counted
+// per quadrant; a tile whose quadrants mostly look dense leaves for the exact kernel
+// there instead of at its end.)  The pipeline is DRAINED at a check point -- the segment
+// before it ends like a tile (every request landed, no fragment built ahead), the one
+// behind it starts like a tile -- so that the check has the LDS for its per-sample
+// values and the register file for its sweep, and the k loop's registers are not live
+// across it: ~8 us per check of a 500 us tile.
+//
+// --- Rotated tiles.  The 32 tiles an XCD holds at a time are a patch of the tile space
+// (8 rows x 4 columns: 12 strips of operands for 32 tiles), but they share those strips
+// through the XCD's 4 MiB L2 only while they read the same k-steps at about the same
+// time -- 21 k-steps of the patch fit.  Tiles that all start at k-step 0 do so in the
+// first round of a launch and drift apart from there (L2 hit rate 0.36, 555 GB from the
+// fabric per pass of configs[2]; one launch per round: 0.80 and 170 GB, and the chip
+// holds 1.96-1.99 GHz instead of 1.86: tools/l2_probe.sh).  The order of the sites
+// inside a sum does not matter, so a tile STARTS where the tiles of its XCD are: at the
+// phase boundary (king_common.h phase_step: 128 phases) nearest to the k-step the most
+// advanced of them has published, runs to the end of the sites, wraps around (a segment
+// boundary like a check point's) and ends where it started.  A check point sits behind a
+// share of the k-steps as before; the per-sample counts over "phases [p, p + e)" are
+// differences of the cumulative counts sample_stats_kernel leaves.
+struct CheckPlan {
+  uint32_t chk0, chk1;  // k-steps of the tile in front of check 0 / check 1 (0: no such check)
+  uint32_t share1;      // the share of the sites in front of check 1, in 64ths
+  uint32_t phase;       // the phase boundary the tile starts at (0: not rotated)
+  uint32_t k0;          // ... as a k-step of the bitset
+  uint32_t wrap;        // k-steps of the tile in front of the end of the sites (0: none behind)
+  uint32_t start_abs;   // k0, counted on from the position the XCD's tiles have published
+};
+// `xcd_pos`: launch_verdict(); `all_steps`: the bitset's k-steps, `num_steps`: the tile's.
+__device__ __forceinline__ CheckPlan plan_checks(const TiledArgs &a, const Tile &t,
+                                                 const uint32_t xcd_pos, const uint32_t all_steps,
+                                                 const uint32_t num_steps) {
   uint32_t chk0 = 0, chk1 = 0, entry1 = 0, share1 = 0;
   uint32_t phase = 0, k0 = 0, wrap = 0, start_abs = 0;
-  if (!split && a.check_steps != nullptr && a.tile_done != nullptr) {
+  if (!t.split && a.check_steps != nullptr && a.tile_done != nullptr) {
     if (a.rotate != 0 && all_steps >= a.rotate_min_steps) {
       uint32_t base = 0;
       if (a.rotate == 1) {
@@ -632,7 +456,7 @@ __device__ __forceinline__ int filter_tile(const TiledArgs &a, const uint32_t wg
           base += all_steps;
         }
       } else if (a.rotate == 2) {
-        phase = (bid * 37u + 11u) & (kNumPhases - 1);  // (test hook)
+        phase = (t.bid * 37u + 11u) & (kNumPhases - 1);  // (test hook)
       } else {
         phase = (a.rotate - 3u) & (kNumPhases - 1);    // (test hook)
       }
@@ -642,16 +466,9 @@ __device__ __forceinline__ int filter_tile(const TiledArgs &a, const uint32_t wg
     }
     // kappa: the level of the bound for this cohort's unrelated pairs (from its mean missing
     // and het rates) plus 4.6 standard deviations and a little
-    float kappa = -1.f;
-    {
-      const float ns = (float)a.cohort_sums[0], nm = (float)a.cohort_sums[1],
-                  nh = (float)a.cohort_sums[2];
-      if (ns > 0.f && nh > 0.f) {
-        const float sites = 256.f * (float)all_steps;
-        const float m = nm / (ns * sites), h = nh / (ns * sites);
-        kappa = m * (1.f + m / (2.f * h * (1.f - m))) + 4.6f * rsqrtf(sites) + 0.003f;
-      }
-    }
+    float kappa = -1.f, mean, sigma;
+    if (bound_level(a.cohort_sums, 256.f * (float)all_steps, &mean, &sigma))
+      kappa = mean + 4.6f * sigma + 0.003f;
     // Check 0 (the forecast; a.check0: 1 = this is a short launch, 2 = forced): only for a
     // cohort whose unrelated pairs come anywhere near the threshold -- a drain and a sweep
     // per tile (1.5-3 % of configs[1]) that a clean cohort need not pay; a cohort that is
@@ -690,37 +507,447 @@ __device__ __forceinline__ int filter_tile(const TiledArgs &a, const uint32_t wg
     if (chk0 >= num_steps) chk0 = 0;
     if (chk1 >= num_steps || chk1 <= chk0) chk1 = 0;
   }
-  chk0 = __builtin_amdgcn_readfirstlane(chk0);
-  chk1 = __builtin_amdgcn_readfirstlane(chk1);
-  share1 = __builtin_amdgcn_readfirstlane(share1);
-  phase = __builtin_amdgcn_readfirstlane(phase);
-  k0 = __builtin_amdgcn_readfirstlane(k0);
-  wrap = __builtin_amdgcn_readfirstlane(wrap);
-  start_abs = __builtin_amdgcn_readfirstlane(start_abs);
-  // u~ of plane sample idx over the `share` phases from this tile's first on (`total`: over
-  // all sites): cumulative counts in front of the inner boundaries, nothing in front of 0.
-  // A range that goes around the end of the sites is (total - front of `phase`) + front of
-  // the wrapped end, in THAT order: every partial is then u~ over a contiguous range of
-  // sites or over two disjoint ones, at most 2.5 per site -- total + the wrapped end first
-  // would reach 5 per site, past 2^24 at 2^22 sites (king_common.h, kMfmaN4MaxSites).
-  auto prefix_u_of = [&](uint32_t share, size_t idx, float total) {
-    const uint32_t hi = phase + share * kPhasesPerShare;  // (uniform; hi < 2 kNumPhases)
-    float u = hi >= kNumPhases ? total
-              : hi != 0        ? a.prefix_u[(size_t)(hi - 1) * s_stride + idx]
-                               : 0.f;
-    if (phase != 0) u -= a.prefix_u[(size_t)(phase - 1) * s_stride + idx];
-    if (hi > kNumPhases) u += a.prefix_u[(size_t)(hi - kNumPhases - 1) * s_stride + idx];
-    return u;
-  };
-  // The k-step this tile has reached, for the tiles of the XCD that start next (one lane of
-  // one wavefront: the branch is scalar, the lane mask is set by hand -- a divergent branch
-  // here makes the compiler treat the segment loop as divergent)
-  unsigned long long *const pos_word =
-      reinterpret_cast<unsigned long long *>(a.filter_ctrl + kCtrlPos) +
-      (wg & 7) * kPosSlots + ((wg >> 3) & (kPosSlots - 1));
-  uint32_t *const ticks_word = a.filter_ctrl + kCtrlStepTicks + (wg & 7);
-  // (the first request of the tile goes out about now)
-  const uint32_t t_start = a.rotate == 1 ? (uint32_t)__builtin_amdgcn_s_memrealtime() : 0u;
+  auto sgpr = [](uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane(v); };
+  return CheckPlan{sgpr(chk0), sgpr(chk1), sgpr(share1), sgpr(phase), sgpr(k0), sgpr(wrap), sgpr(start_abs)};
+}
+
+// u~ of plane sample idx over the `share` phases from the tile's first on (`total`: over
+// all sites): cumulative counts in front of the inner boundaries, nothing in front of 0.
+// A range that goes around the end of the sites is (total - front of `phase`) + front of
+// the wrapped end, in THAT order: every partial is then u~ over a contiguous range of
+// sites or over two disjoint ones, at most 2.5 per site -- total + the wrapped end first
+// would reach 5 per site, past 2^24 at 2^22 sites (king_common.h, kMfmaN4MaxSites).
+__device__ __forceinline__ float prefix_u_of(const TiledArgs &a, const CheckPlan &p,
+                                             uint32_t share, size_t idx, float total) {
+  const uint32_t s_stride = a.geo.s_stride;
+  const uint32_t hi = p.phase + share * kPhasesPerShare;  // (uniform; hi < 2 kNumPhases)
+  float u = hi >= kNumPhases ? total
+            : hi != 0        ? a.prefix_u[(size_t)(hi - 1) * s_stride + idx]
+                             : 0.f;
+  if (p.phase != 0) u -= a.prefix_u[(size_t)(p.phase - 1) * s_stride + idx];
+  if (hi > kNumPhases) u += a.prefix_u[(size_t)(hi - kNumPhases - 1) * s_stride + idx];
+  return u;
+}
+
+// What a sweep over the tile's pairs reads per sample, staged in the (idle) stage memory by
+// the workgroup's 256 threads: (u~, scale (t |H| + margin)) of the tile's 256 row and 256
+// column samples, t = 2 - 4 thr; u~ over all sites, or (`prefix`, uniform) over the `share`
+// phases from the tile's first on.  Returns the rows' 256 values, the columns' are behind
+// them; barrier behind the stores.
+__device__ __forceinline__ const float2 *stage_bounds(const TiledArgs &a, const Tile &t,
+                                                      const CheckPlan &p, uint4 *const lds,
+                                                      const bool prefix, const uint32_t share,
+                                                      const float thr, const float scale) {
+  float2 *const rows = reinterpret_cast<float2 *>(lds), *const cols = rows + kT;
+  const float tt = 2.f - 4.f * thr;
+  const size_t ir = (size_t)t.tr * kT + threadIdx.x;
+  const size_t ic = (size_t)a.geo.col_base + (size_t)t.tc * kT + threadIdx.x;
+  float2 r = a.sample_stats[ir], c = a.sample_stats[ic];
+  if (prefix) {
+    r.x = prefix_u_of(a, p, share, ir, r.x);
+    c.x = prefix_u_of(a, p, share, ic, c.x);
+  }
+  r.y = scale * fmaf(tt, r.y, 8.f);
+  c.y = scale * fmaf(tt, c.y, 8.f);
+  rows[threadIdx.x] = r;
+  cols[threadIdx.x] = c;
+  __syncthreads();
+  return rows;
+}
+
+// How a tile came out of its k loop (uniform): it ran to its end, or it left at a check
+// point: at the forecast, or at the rigorous check -- with nothing alive, or with a few live
+// pairs that the epilogue (run on the prefix counts) hands to the candidate list.
+enum Leave : uint32_t { kStays = 0, kLeftForecast, kLeftEmpty, kLeftEmit };
+
+// The test at a check point (the pipeline is drained, the stage memory idle): the forecast
+// (check 0), or the rigorous check behind share1 of the tile's sites.
+__device__ __forceinline__ Leave check_sweep(const TiledArgs &a, const Tile &t, const CheckPlan &p,
+                                             const v16f (&acc)[4][4], uint4 *const lds,
+                                             const bool forecast, const uint32_t all_steps) {
+  const Lanes l = lanes_of_thread();
+  const float scale = forecast ? (float)kCheckShares64[0] * (1.f / 64.f) : 1.f;
+  const uint32_t share = forecast ? kCheckShares64[0] : p.share1;  // (uniform)
+  // (the forecast counts the pairs that WILL be candidates from an eighth of the sites:
+  //  the bound of an unrelated pair scatters sqrt(8) times as widely there as at the
+  //  end, 1 / sqrt(sites).  A quadrant goes dense from 2.3 % candidates on -- pairs two
+  //  standard deviations out --, so the prefix count matches the final one at that
+  //  point when the prefix is tested against a threshold 2 (sqrt(8) - 1) standard
+  //  deviations higher; tested against the threshold itself it called cohorts dense that
+  //  the list handles at a third of the cost: 7 % missing calls at the default threshold,
+  //  profiles/r04_missing_curve.txt)
+  const float thr_f = forecast ? a.kin_threshold + 3.66f * rsqrtf(256.f * (float)all_steps)
+                               : a.kin_threshold;
+  // (u~ over the prefix, scaled bound)
+  const float2 *const ck_rows = stage_bounds(a, t, p, lds, true, share, thr_f, scale);
+  const float2 *const ck_cols = ck_rows + kT;
+  uint32_t *const ck_words = reinterpret_cast<uint32_t *>(lds) + 4 * kT;  // behind them: one per wavefront
+  const uint32_t emit_cap = (a.check1 >> 8) & 0xFFu;  // (uniform; king_common.h check1)
+  uint32_t cnt = 0;  // pairs of this lane still under the bound
+  {
+    float2 cc[4];
+#pragma unroll
+    for (int bj = 0; bj < 4; ++bj) cc[bj] = ck_cols[l.wx * 128 + bj * 32 + l.lr];
+#pragma unroll
+    for (int bi = 0; bi < 4; ++bi)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const float2 cr = ck_rows[l.wy * 128 + bi * 32 + c_row(r, l.g)];
+        // (every element of the tile counts, the ones outside the block too: a tile on the
+        //  diagonal holds each sample against itself and stays -- 0.5 % of the tiles at
+        //  configs[2]; the test on the indices made the kernel a quarter longer)
+#pragma unroll
+        for (int bj = 0; bj < 4; ++bj)
+          cnt += fmaf(-8.f, acc[bi][bj][r], cr.x) + cc[bj].x < fminf(cr.y, cc[bj].y) ? 1u : 0u;
+      }
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off);
+  // (forecast: twice the cap -- the pairs of a quadrant share their samples, so the count
+  //  of a quadrant scatters more widely than independent pairs would; at 7 % missing calls
+  //  and the default threshold a sixth of the tiles left with the cap itself, for a launch
+  //  the candidate list handles in half the time)
+  // (rigorous check: the word carries the quadrant's live pairs, capped -- a tile with
+  //  only a FEW of them, the relatives it holds, hands exactly those to the candidate list
+  //  and leaves as well: a cohort with some relatedness in every tile keeps its early exits)
+  if (l.lane == 0)
+    ck_words[l.wave] = forecast ? (cnt > 2 * a.quadrant_cap ? 1u : 0u)
+                                : (cnt > emit_cap ? emit_cap + 1 : cnt);
+  __syncthreads();
+  uint32_t found = forecast ? ck_words[0] + ck_words[1] + ck_words[2] + ck_words[3]
+                            : max(max(ck_words[0], ck_words[1]), max(ck_words[2], ck_words[3]));
+  found = __builtin_amdgcn_readfirstlane(found);
+  __syncthreads();  // (the words are stage memory again from here on)
+  if (forecast) return found >= 3 ? kLeftForecast : kStays;
+  return found > emit_cap ? kStays : found != 0 ? kLeftEmit : kLeftEmpty;
+}
+
+// The book-keeping behind the k loop.  True when the tile left at a check point with
+// nothing to hand over: the workgroup is through.
+__device__ __forceinline__ bool leave_early(const TiledArgs &a, const Tile &t, const CheckPlan &p,
+                                            const Leave left) {
+  if (left == kLeftEmit && threadIdx.x == 0) relaxed_add(a.filter_totals + kTotalEarly, 1ull);
+  if (p.phase != 0 && threadIdx.x == 0) relaxed_add(a.filter_totals + kTotalRotated, 1ull);
+  if (left == kLeftForecast || left == kLeftEmpty) {
+    // Forecast: the tile leaves for the exact kernel -- its quadrants count as handed
+    // over, the fallback launch is needed.  Rigorous check: for good.
+    if (threadIdx.x == 0) {
+      relaxed_add(a.filter_ctrl + kCtrlFinished, 4u);
+      if (left == kLeftForecast) {
+        relaxed_add(a.filter_ctrl + kCtrlLeft, 4u);
+        relaxed_store(a.filter_ctrl + kCtrlGate, 1u);
+        relaxed_add(a.filter_totals + kTotalDense, 4ull);
+      } else {
+        a.tile_done[t.bid] = 1;
+        relaxed_add(a.filter_totals + kTotalEarly, 1ull);
+      }
+    }
+    return true;
+  }
+  // This tile runs to its end here: the fallback launch has nothing to do for it.
+  // (The tiles of remainder pieces are marked by the host.)
+  if (!t.split && a.tile_done != nullptr && threadIdx.x == 0) a.tile_done[t.bid] = 1;
+  return false;
+}
+
+// A piece of a split tile: park this piece (16-byte write-through stores, [4 registers]
+// [thread]), take a ticket of the tile; the last piece in adds the others to its own and
+// carries on (true) -- the others are through.
+__device__ __forceinline__ bool reduce_pieces(const TiledArgs &a, const Tile &t, v16f (&acc)[4][4],
+                                              uint4 *const lds) {
+  typedef uint32_t v4u __attribute__((ext_vector_type(4)));
+  constexpr uint32_t kSlabU4 = 64 * 256;  // float4 per slab
+  {
+    const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
+        a.fsplit_slabs + (size_t)t.piece * kSlabU4, 0, (int)(kSlabU4 * 16), 0x00020000);
+#pragma unroll
+    for (int bi = 0; bi < 4; ++bi)
+#pragma unroll
+      for (int bj = 0; bj < 4; ++bj)
+#pragma unroll
+        for (int r4 = 0; r4 < 4; ++r4) {
+          const v16f &c = acc[bi][bj];
+          const v4u v = {__float_as_uint(c[4 * r4]), __float_as_uint(c[4 * r4 + 1]),
+                         __float_as_uint(c[4 * r4 + 2]), __float_as_uint(c[4 * r4 + 3])};
+          __builtin_amdgcn_raw_buffer_store_b128(
+              v, rsrc, (int)((((bi * 4 + bj) * 4 + r4) * 256 + threadIdx.x) * 16), 0,
+              16 /* sc1 */);
+        }
+  }
+  // every wavefront's stores are done (and written through), then the ticket
+  // (cdna_hip_programming.md, Guideline 16: sc1 payload + counter)
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  uint32_t *flag = reinterpret_cast<uint32_t *>(lds);  // the stages are idle now
+  if (threadIdx.x == 0) {
+    uint32_t *counter = a.fsplit_tickets + t.piece / a.fsplit_parts;
+    const uint32_t ticket = relaxed_add(counter, 1u);
+    const bool last = ticket == a.fsplit_parts - 1;
+    if (last) {
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      *counter = 0;  // ready for the next launch
+    }
+    *flag = last ? 1u : 0u;
+  }
+  __syncthreads();
+  const bool last = *flag != 0;
+  __syncthreads();  // (the flag word becomes the epilogue's scratch)
+  if (!last) return false;
+  const uint32_t first_piece = t.piece - t.part;
+  for (uint32_t p = 0; p < a.fsplit_parts; ++p) {
+    if (p == t.part) continue;
+    const float4 *src = a.fsplit_slabs + (size_t)(first_piece + p) * kSlabU4 + threadIdx.x;
+#pragma unroll
+    for (int bi = 0; bi < 4; ++bi)
+#pragma unroll
+      for (int bj = 0; bj < 4; ++bj)
+#pragma unroll
+        for (int r4 = 0; r4 < 4; ++r4) {
+          const float4 v = src[((bi * 4 + bj) * 4 + r4) * 256];
+          acc[bi][bj][4 * r4] += v.x;
+          acc[bi][bj][4 * r4 + 1] += v.y;
+          acc[bi][bj][4 * r4 + 2] += v.z;
+          acc[bi][bj][4 * r4 + 3] += v.w;
+        }
+  }
+  return true;
+}
+
+// The epilogue: the bound, per pair; the candidates go to the list, or their quadrant to the
+// dense list.  `on_prefix`: the tile left at the rigorous check with a few live pairs: the
+// same test on the sums and the per-sample counts of the sites so far -- every record is
+// among the pairs it admits ("Check points" above).  Wavefronts return one by one.
+__device__ __forceinline__ void emit_candidates(const TiledArgs &a, const Tile &t,
+                                                const CheckPlan &p, const v16f (&acc)[4][4],
+                                                uint4 *const lds, const bool on_prefix) {
+  const Lanes l = lanes_of_thread();
+  // (u~, t |H| + margin) per row and per column
+  const float2 *const st_rows = stage_bounds(a, t, p, lds, on_prefix, p.share1, a.kin_threshold, 1.f);
+  const float2 *const st_cols = st_rows + kT;
+  float2 sc[4];
+#pragma unroll
+  for (int bj = 0; bj < 4; ++bj) sc[bj] = st_cols[l.wx * 128 + bj * 32 + l.lr];
+
+  // Nearly every wavefront has no candidate at all: a first sweep with the bare test
+  // (5 VALU per pair, the largest `bound - x_lb` of the lane: positive <=> the test
+  // below holds for some pair, the sign of a float difference is exact; pairs outside
+  // the block may raise a false alarm, which only costs the sweeps below), then out.
+  {
+    float best = -1.f;
+#pragma unroll
+    for (int bi = 0; bi < 4; ++bi)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const float2 sr = st_rows[l.wy * 128 + bi * 32 + c_row(r, l.g)];
+#pragma unroll
+        for (int bj = 0; bj < 4; ++bj)
+          best = fmaxf(best, fminf(sr.y, sc[bj].y) -
+                                 (fmaf(-8.f, acc[bi][bj][r], sr.x) + sc[bj].x));
+      }
+    if (l.lane == 0) relaxed_add(a.filter_ctrl + kCtrlFinished, 1u);
+    if (__ballot(best > 0.f) == 0) return;  // wave-uniform
+  }
+
+  uint32_t total = 0, base = 0, run = 0;  // wave-uniform
+#pragma nounroll
+  for (int pass = 0; pass < 2; ++pass) {  // 0: count the candidates, 1: append them
+    // (opaque per pass: otherwise the compiler computes the 256 pairs' indices and
+    //  validity once in front of the loop and parks them in scratch memory)
+    uint32_t tr_p = t.tr, tc_p = t.tc;
+    asm volatile("" : "+s"(tr_p), "+s"(tc_p));
+#pragma unroll
+    for (int bi = 0; bi < 4; ++bi) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const uint32_t row = l.wy * 128 + bi * 32 + c_row(r, l.g);
+        const float2 sr = st_rows[row];
+        const uint32_t li = tr_p * kT + row;
+#pragma unroll
+        for (int bj = 0; bj < 4; ++bj) {
+          const uint32_t lj = tc_p * kT + l.wx * 128 + bj * 32 + l.lr;
+          // cuking.cu:199 plus the tile padding
+          const bool valid = li < a.geo.num_rows && lj < a.geo.num_cols &&
+                             a.i_begin + li < a.j_begin + lj;
+          // u_i + u_j - 2 q  <  t min(|H_i|, |H_j|) + margin   ("Offset code" above:
+          // u~_i - 8 acc first, below 2^24 in magnitude, then u~_j)
+          const float x_lb = fmaf(-8.f, acc[bi][bj][r], sr.x) + sc[bj].x;
+          const bool cand = valid && x_lb < fminf(sr.y, sc[bj].y);
+          const unsigned long long b = __ballot(cand);
+          if (b != 0) {  // wave-uniform
+            if (pass == 0) {
+              total += (uint32_t)__popcll(b);
+            } else {
+              const uint32_t before = __builtin_amdgcn_mbcnt_hi(
+                  (uint32_t)(b >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b, 0u));
+              if (cand) a.cand_list[base + run + before] = make_uint2(li, lj);
+              run += (uint32_t)__popcll(b);
+            }
+          }
+        }
+      }
+    }
+    if (pass == 0) {
+      if (total == 0) break;  // wave-uniform: the usual case
+      bool dense = total > a.quadrant_cap;
+      if (!dense) {
+        uint32_t got = 0;
+        if (l.lane == 0) {
+          got = relaxed_add(a.filter_ctrl, total);
+          // (running total since the scratch was allocated: "filter_candidates")
+          relaxed_add(a.filter_totals + kTotalCand, total);
+        }
+        base = (uint32_t)__builtin_amdgcn_readfirstlane(got);
+        if (base >= a.cand_cap || total > a.cand_cap - base) {
+          // list full: the slots taken (if any) must not be read as pairs
+          for (uint32_t k = base + l.lane; k < a.cand_cap; k += 64)
+            a.cand_list[k] = make_uint2(kNoPair, kNoPair);
+          dense = true;
+        }
+      }
+      if (dense) {
+        if (l.lane == 0) {
+          const uint32_t slot = relaxed_add(a.filter_ctrl + kCtrlDense, 1u);
+          if (slot < a.dense_cap) a.dense_list[slot] = make_uint2(2 * t.tr + l.wy, 2 * t.tc + l.wx);
+          relaxed_add(a.filter_totals + kTotalDense, 1ull);
+        }
+        break;
+      }
+    }
+  }
+}
+
+// ---- The k loop's statements: macros over filter_tile()'s locals (acc, FA / FB / RAW, mT / mA /
+// scaleB, lane16 / row_off / col_off, row_bytes, and a segment's running pa, buf, step).
+// One LDS-DMA request: lane l's 16 bytes of SRC + OFF land at DST + OFF + 16 l
+// (the immediate offset moves source and destination alike).
+#define F_ISSUE(SRC, DST, OFF)                                                 \
+  asm volatile("s_mov_b32 m0, %0\n\t"                                          \
+               "s_nop 0\n\t"                                                   \
+               "global_load_lds_dwordx4 %1, %2 offset:" #OFF                   \
+               :                                                               \
+               : "s"(DST), "v"(lane16), "s"(SRC)                               \
+               : "memory", "m0")
+// The four requests of unit c of the stage `pa` names.
+#define F_ISSUE4(PA, C)                                                        \
+  {                                                                            \
+    const char *src_ = (PA).src + (C) * row_bytes;                             \
+    const uint32_t dst_ = (PA).dst + (C) * (kSliceU4 * 16);                    \
+    F_ISSUE(src_, dst_, 0);                                                    \
+    F_ISSUE(src_, dst_, 1024);                                                 \
+    F_ISSUE(src_, dst_, 2048);                                                 \
+    F_ISSUE(src_, dst_, 3072);                                                 \
+  }
+#define F_READ(K, BUF, C)                                                      \
+  RAW[K] = lds[(BUF) * kStageU4 + ((K) < 4 ? row_off : col_off) + (C) * kSliceU4 + ((K) & 3) * 32];
+// (plain ANDs: nothing but data orders them against the MFMAs, and
+// left alone the compiler builds every fragment right behind its LDS read, i.e.
+// waits for the read it has just issued.  The empty asm statements tie a build
+// to the place it is written in: not above the pin of its input, not below the
+// pin of its result -- as in king_mfma.hip.)
+#define F_PIN4(W) asm volatile("" : "+v"((W).x), "+v"((W).y), "+v"((W).z), "+v"((W).w));
+#define F_PINF(F) asm volatile("" : "+v"((F)[0]), "+v"((F)[1]), "+v"((F)[2]), "+v"((F)[3]));
+// Set B of word K: bits 2-3 of every nibble as they are.
+#define F_BUILD_B(NXT, K)                                                      \
+  F_PIN4(RAW[K])                                                               \
+  if ((K) < 4) {                                                               \
+    FA[NXT][(K) & 3] = tfrag(RAW[K], mT);                                      \
+    F_PINF(FA[NXT][(K) & 3])                                                   \
+  } else {                                                                     \
+    FB[NXT][(K) & 3] = tfrag(RAW[K], mT);                                      \
+    F_PINF(FB[NXT][(K) & 3])                                                   \
+  }
+// Set A of word K: bits 0-1 of every nibble as they are (1 + T: 0 / 0.5 / 1.0 in fp4).
+#define F_BUILD_A(NXT, K)                                                      \
+  F_PIN4(RAW[K])                                                               \
+  if ((K) < 4) {                                                               \
+    FA[NXT][(K) & 3] = tfrag(RAW[K], mA);                                      \
+    F_PINF(FA[NXT][(K) & 3])                                                   \
+  } else {                                                                     \
+    FB[NXT][(K) & 3] = tfrag(RAW[K], mA);                                      \
+    F_PINF(FB[NXT][(K) & 3])                                                   \
+  }
+// (fragment set 0 holds set B: the scaled instruction; fragment set 1 holds set A)
+#define F_MMA(CUR, BI, BJ)                                                     \
+  acc[BI][BJ] = (CUR) == 0 ? mma_scaled(FA[CUR][BI], FB[CUR][BJ], acc[BI][BJ], scaleB) \
+                           : mma(FA[CUR][BI], FB[CUR][BJ], acc[BI][BJ]);
+#define F_BAR __builtin_amdgcn_sched_barrier(0);
+// Slice B of unit c (fragment set CUR): 16 MFMAs; in their gaps the set-A
+// fragments of the same words (4 VALU per fragment, in every second gap: the
+// gaps that take a request stay free) and two requests.
+#define F_SLICE_B(CUR, NXT, PA, DC, OFF0, OFF1)                                \
+  {                                                                            \
+    const char *src_ = (PA).src + (DC) * row_bytes;                            \
+    const uint32_t dst_ = (PA).dst + (DC) * (kSliceU4 * 16);                   \
+    F_ISSUE(src_, dst_, OFF0);                                                 \
+    F_MMA(CUR, 0, 0) F_BAR                                                     \
+    F_BUILD_A(NXT, 0) F_MMA(CUR, 0, 1) F_BAR                                   \
+    F_MMA(CUR, 0, 2) F_BAR                                                     \
+    F_BUILD_A(NXT, 1) F_MMA(CUR, 0, 3) F_BAR                                   \
+    F_MMA(CUR, 1, 0) F_BAR                                                     \
+    F_BUILD_A(NXT, 2) F_MMA(CUR, 1, 1) F_BAR                                   \
+    F_MMA(CUR, 1, 2) F_BAR                                                     \
+    F_BUILD_A(NXT, 3) F_MMA(CUR, 1, 3) F_BAR                                   \
+    F_ISSUE(src_, dst_, OFF1);                                                 \
+    F_MMA(CUR, 2, 0) F_BAR                                                     \
+    F_BUILD_A(NXT, 4) F_MMA(CUR, 2, 1) F_BAR                                   \
+    F_MMA(CUR, 2, 2) F_BAR                                                     \
+    F_BUILD_A(NXT, 5) F_MMA(CUR, 2, 3) F_BAR                                   \
+    F_MMA(CUR, 3, 0) F_BAR                                                     \
+    F_BUILD_A(NXT, 6) F_MMA(CUR, 3, 1) F_BAR                                   \
+    F_MMA(CUR, 3, 2) F_BAR                                                     \
+    F_BUILD_A(NXT, 7) F_MMA(CUR, 3, 3) F_BAR                                   \
+  }
+// Slice A of a unit (fragment set CUR): 16 MFMAs; in the gaps of the first
+// eight the LDS reads of the NEXT unit's words (RBUF, RC; behind the stage
+// hand-over if SYNC: that read is the first of a new stage) and two requests,
+// in the gaps of the last eight that unit's set-B fragments.
+#define F_SLICE_A(CUR, NXT, RBUF, RC, SYNC, PA, DC, OFF0, OFF1)                \
+  {                                                                            \
+    if (SYNC) {                                                                \
+      __builtin_amdgcn_s_waitcnt(vmcnt_imm(kSyncVm));                          \
+      __syncthreads();                                                         \
+    }                                                                          \
+    const char *src_ = (PA).src + (DC) * row_bytes;                            \
+    const uint32_t dst_ = (PA).dst + (DC) * (kSliceU4 * 16);                   \
+    F_READ(0, RBUF, RC) F_READ(1, RBUF, RC)                                    \
+    F_ISSUE(src_, dst_, OFF0);                                                 \
+    F_MMA(CUR, 0, 0) F_MMA(CUR, 0, 1) F_BAR                                    \
+    F_READ(2, RBUF, RC) F_READ(3, RBUF, RC)                                    \
+    F_MMA(CUR, 0, 2) F_MMA(CUR, 0, 3) F_BAR                                    \
+    F_READ(4, RBUF, RC) F_READ(5, RBUF, RC)                                    \
+    F_ISSUE(src_, dst_, OFF1);                                                 \
+    F_MMA(CUR, 1, 0) F_MMA(CUR, 1, 1) F_BAR                                    \
+    F_READ(6, RBUF, RC) F_READ(7, RBUF, RC)                                    \
+    F_MMA(CUR, 1, 2) F_MMA(CUR, 1, 3) F_BAR                                    \
+    F_BUILD_B(NXT, 0) F_MMA(CUR, 2, 0) F_BAR                                   \
+    F_BUILD_B(NXT, 1) F_MMA(CUR, 2, 1) F_BAR                                   \
+    F_BUILD_B(NXT, 2) F_MMA(CUR, 2, 2) F_BAR                                   \
+    F_BUILD_B(NXT, 3) F_MMA(CUR, 2, 3) F_BAR                                   \
+    F_BUILD_B(NXT, 4) F_MMA(CUR, 3, 0) F_BAR                                   \
+    F_BUILD_B(NXT, 5) F_MMA(CUR, 3, 1) F_BAR                                   \
+    F_BUILD_B(NXT, 6) F_MMA(CUR, 3, 2) F_BAR                                   \
+    F_BUILD_B(NXT, 7) F_MMA(CUR, 3, 3) F_BAR                                   \
+  }
+// k-step s requests stage s + kStages - 1 into the buffer stage s - 1 left: every
+// wavefront finished reading it before the hand-over of k-step s - 1.  The
+// hand-over of k-step s (stage s + 1 must have landed) comes in its last slice:
+// in flight then may be the stages after s + 1 and the requests of the newest one
+// that the slices before the last have issued (kSyncVm: 2 x 8 + 6 = 22).
+#define F_KSTEP                                                                \
+  {                                                                            \
+    const uint32_t nbuf = buf == kStages - 1 ? 0 : buf + 1;                    \
+    F_SLICE_B(0, 1, pa, 0, 0, 1024)                                            \
+    F_SLICE_A(1, 0, buf, 1, false, pa, 0, 2048, 3072)                          \
+    F_SLICE_B(0, 1, pa, 1, 0, 1024)                                            \
+    F_SLICE_A(1, 0, nbuf, 0, true, pa, 1, 2048, 3072)                          \
+    pa = addr_next(pa, step + kStages, buf);                                   \
+    buf = nbuf;                                                                \
+    ++step;                                                                    \
+  }
+// The k-step this tile has reached, for the tiles of the XCD that start next (one lane of
+// one wavefront: the branch is scalar, the lane mask is set by hand -- a divergent branch
+// here makes the compiler treat the segment loop as divergent)
 #define F_PUBLISH(STEPS)                                                       \
   if (a.rotate == 1 && wave == 0) {                                            \
     const uint32_t now_ = (uint32_t)__builtin_amdgcn_s_memrealtime();          \
@@ -747,11 +974,102 @@ __device__ __forceinline__ int filter_tile(const TiledArgs &a, const uint32_t wg
                    : "memory");                                                \
   }
 
+// One tile (or one piece of the k range of a tile) of the launch: what workgroup `wg` of a
+// grid of one workgroup per tile does -- the phases above around the k loop.  Every return
+// but the epilogue's is uniform across the workgroup.  lds: [kStages][side][k-half][unit][256].
+__device__ __forceinline__ void filter_tile(const TiledArgs &a, const uint32_t wg, uint4 *const lds) {
+  Tile tile;
+  if (!take_tile(a, wg, lds, &tile)) return;
+  const Lanes ln = lanes_of_thread();
+  uint32_t xcd_pos = 0;
+  if (!tile.split && a.tile_done != nullptr && launch_verdict(a, wg, lds, &xcd_pos)) return;
+  // k-steps of 256 sites: all of them, or this piece's share
+  const uint32_t all_steps = a.geo.k_words / (4 * kUnits);
+  // (wave-uniform, but divisions run in vector registers: pinned to SGPRs for the
+  //  request addresses)
+  const uint32_t k_first = __builtin_amdgcn_readfirstlane(
+      tile.split ? tile.part * all_steps / a.fsplit_parts : 0u);
+  const uint32_t num_steps = __builtin_amdgcn_readfirstlane(
+      tile.split ? (tile.part + 1) * all_steps / a.fsplit_parts - k_first : all_steps);
+  const CheckPlan plan = plan_checks(a, tile, xcd_pos, all_steps, num_steps);
+
+  // --- the k loop: acc = (q + n_A + S_i + S_j) / 4 of the tile's pairs ("Offset code" above)
+  // (the names the F_* macros and the segment loop below use)
+  const uint32_t wave = ln.wave, chk0 = plan.chk0, chk1 = plan.chk1;
+  const uint32_t k0 = plan.k0, wrap = plan.wrap, start_abs = plan.start_abs;
+  uint32_t lane16 = ln.lane * 16;
+  const uint32_t s_stride = a.geo.s_stride;
+  const uint4 *g_rows = a.t2 + (uint64_t)tile.tr * kT;
+  const uint4 *g_cols = a.t2 + a.geo.col_base + (uint64_t)tile.tc * kT;
+
+  // The masks of the two site sets of a T2 word and the scale of set B (king_common.h:
+  // +-2.0 x 2^-2 per operand, so that a set-B product weighs 1/4 like a set-A product),
+  // set once and pinned.
+  uint32_t mT, mA;
+  asm volatile("s_mov_b32 %0, 0xcccccccc" : "=s"(mT));
+  asm volatile("s_mov_b32 %0, 0x33333333" : "=s"(mA));
+  int scaleB;
+  asm volatile("v_mov_b32 %0, 0x7d7d7d7d" : "=v"(scaleB));
+
+  // LDS-DMA: wavefront (side, k-half) fetches that quarter of a stage: 2 units x
+  // 4 runs of 64 samples, 1 KiB each.  Unit c of k-step s, k-half h is unit
+  // 4 s + 2 h + c of the T2 layout (the order of the sites inside k does not
+  // matter as long as rows and columns agree); every unit feeds TWO slices of 64
+  // sites per k-half: its bits 2-3 (set B) and its bits 0-1 (set A).
+  const uint32_t dma_side = wave >> 1, dma_h = wave & 1;
+  const uint32_t row_bytes = s_stride * 16;  // one unit of the layout
+  const char *const g_wave = reinterpret_cast<const char *>(
+      (dma_side ? g_cols : g_rows) + ((uint64_t)2 * kUnits * k_first + kUnits * dma_h) * s_stride);
+  const uint32_t l_wave = (uint32_t)(uintptr_t)(lds_void_ptr)(
+      lds + ((dma_side * 2 + dma_h) * kUnits) * kSliceU4);
+  struct Addr { const char *src; uint32_t dst; };  // of unit 0; unit 1: + row_bytes, + 4 KiB
+  const uint32_t kstep_bytes = 2 * kUnits * row_bytes;
+  // The pipeline runs over one SEGMENT of the piece's k-steps at a time (one segment,
+  // unless the tile has check points): `seg_src` is the wavefront's first request
+  // of the segment, `seg_steps` its k-steps.
+  const char *seg_src = g_wave;
+  uint32_t seg_steps = num_steps;
+  // (a rotated tile: k-step `seg_wrap` of the segment is the bitset's FIRST again --
+  //  all_steps k-steps back; 32-bit scalar selects and one signed product: a select between
+  //  two 64-bit addresses goes through vector registers, which the scalar pins cannot take)
+  uint32_t seg_wrap = 0xFFFFFFFFu;
+  auto addr_of = [&](uint32_t step, uint32_t buf) {
+    Addr pa;
+    if (step >= seg_steps) step = seg_steps - 1;  // clamped repeats (see king_mfma.hip)
+    const int32_t rel = (int32_t)step - (int32_t)(step >= seg_wrap ? all_steps : 0u);
+    pa.src = seg_src + (int64_t)rel * (int64_t)kstep_bytes;
+    pa.dst = l_wave + buf * (kStageU4 * 16);
+    asm volatile("" : "+s"(pa.src), "+s"(pa.dst));
+    return pa;
+  };
+  auto addr_next = [&](const Addr &cur, uint32_t step, uint32_t buf) {
+    Addr pa;
+    const int32_t adv = (int32_t)(step < seg_steps ? 1u : 0u) -
+                        (int32_t)(step == seg_wrap ? all_steps : 0u);
+    pa.src = cur.src + (int64_t)adv * (int64_t)kstep_bytes;
+    pa.dst = l_wave + buf * (kStageU4 * 16);
+    asm volatile("" : "+s"(pa.src), "+s"(pa.dst));
+    return pa;
+  };
+
+  v16f acc[4][4] = {};
+
+  // This lane's operand words inside a stage (uint4 units).
+  uint32_t row_off = ((0 * 2 + ln.g) * kUnits) * kSliceU4 + ln.wy * 128 + ln.lr;
+  uint32_t col_off = ((1 * 2 + ln.g) * kUnits) * kSliceU4 + ln.wx * 128 + ln.lr;
+  asm volatile("" : "+v"(row_off), "+v"(col_off), "+v"(lane16));
+  v8i FA[2][4], FB[2][4];  // T fragments [slice parity][block]
+  uint4 RAW[8];            // the words of one unit: rows 0-3, columns 4-7
+
+  unsigned long long *const pos_word =
+      reinterpret_cast<unsigned long long *>(a.filter_ctrl + kCtrlPos) +
+      (wg & 7) * kPosSlots + ((wg >> 3) & (kPosSlots - 1));
+  uint32_t *const ticks_word = a.filter_ctrl + kCtrlStepTicks + (wg & 7);
+  // (the first request of the tile goes out about now)
+  const uint32_t t_start = a.rotate == 1 ? (uint32_t)__builtin_amdgcn_s_memrealtime() : 0u;
+
   uint32_t seg_first = 0;  // k-steps of the piece behind us
-  // the tile left at a check point (uniform): at the forecast, or at the rigorous check --
-  // with nothing alive, or with a few live pairs that the epilogue below (run on the prefix
-  // counts) hands to the candidate list
-  bool left = false, left_forecast = false, left_emit = false;
+  Leave left = kStays;
 #pragma nounroll
   while (true) {
     uint32_t seg_end = num_steps;
@@ -801,78 +1119,18 @@ __device__ __forceinline__ int filter_tile(const TiledArgs &a, const uint32_t wg
     if (seg_end == num_steps) break;
 
     // --- the check behind k-step seg_end of the tile
-    const bool forecast = seg_end == chk0;  // uniform
-    const float scale = forecast ? (float)kCheckShares64[0] * (1.f / 64.f) : 1.f;
-    float2 *const ck_rows = reinterpret_cast<float2 *>(lds);  // (u~ over the prefix, scaled bound)
-    float2 *const ck_cols = ck_rows + kT;
-    uint32_t *const ck_words = reinterpret_cast<uint32_t *>(ck_cols + kT);  // one per wavefront
-    {
-      const uint32_t share = forecast ? kCheckShares64[0] : share1;  // (uniform)
-      // (the forecast counts the pairs that WILL be candidates from an eighth of the sites:
-      //  the bound of an unrelated pair scatters sqrt(8) times as widely there as at the
-      //  end, 1 / sqrt(sites).  A quadrant goes dense from 2.3 % candidates on -- pairs two
-      //  standard deviations out --, so the prefix count matches the final one at that
-      //  point when the prefix is tested against a threshold 2 (sqrt(8) - 1) standard
-      //  deviations higher; tested against the threshold itself it called cohorts dense that
-      //  the list handles at a third of the cost: 7 % missing calls at the default threshold,
-      //  profiles/r04_missing_curve.txt)
-      const float thr_f = forecast ? a.kin_threshold + 3.66f * rsqrtf(256.f * (float)all_steps)
-                                   : a.kin_threshold;
-      const float t = 2.f - 4.f * thr_f;
-      const size_t ir = (size_t)tr * kT + threadIdx.x;
-      const size_t ic = (size_t)a.geo.col_base + (size_t)tc * kT + threadIdx.x;
-      const float2 sr = a.sample_stats[ir], sc = a.sample_stats[ic];
-      ck_rows[threadIdx.x] = make_float2(prefix_u_of(share, ir, sr.x), scale * fmaf(t, sr.y, 8.f));
-      ck_cols[threadIdx.x] = make_float2(prefix_u_of(share, ic, sc.x), scale * fmaf(t, sc.y, 8.f));
-    }
-    __syncthreads();
-    const uint32_t emit_cap = (a.check1 >> 8) & 0xFFu;  // (uniform; king_common.h check1)
-    uint32_t cnt = 0;  // pairs of this lane still under the bound
-    {
-      float2 cc[4];
-#pragma unroll
-      for (int bj = 0; bj < 4; ++bj) cc[bj] = ck_cols[wx * 128 + bj * 32 + lr];
-#pragma unroll
-      for (int bi = 0; bi < 4; ++bi)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const float2 cr = ck_rows[wy * 128 + bi * 32 + (r & 3) + 8 * (r >> 2) + 4 * g];
-          // (every element of the tile counts, the ones outside the block too: a tile on the
-          //  diagonal holds each sample against itself and stays -- 0.5 % of the tiles at
-          //  configs[2]; the test on the indices made the kernel a quarter longer)
-#pragma unroll
-          for (int bj = 0; bj < 4; ++bj)
-            cnt += fmaf(-8.f, acc[bi][bj][r], cr.x) + cc[bj].x < fminf(cr.y, cc[bj].y) ? 1u : 0u;
-        }
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off);
-    // (forecast: twice the cap -- the pairs of a quadrant share their samples, so the count
-    //  of a quadrant scatters more widely than independent pairs would; at 7 % missing calls
-    //  and the default threshold a sixth of the tiles left with the cap itself, for a launch
-    //  the candidate list handles in half the time)
-    // (rigorous check: the word carries the quadrant's live pairs, capped -- a tile with
-    //  only a FEW of them, the relatives it holds, hands exactly those to the candidate list
-    //  and leaves as well: a cohort with some relatedness in every tile keeps its early exits)
-    if (lane == 0)
-      ck_words[wave] = forecast ? (cnt > 2 * a.quadrant_cap ? 1u : 0u)
-                                : (cnt > emit_cap ? emit_cap + 1 : cnt);
-    __syncthreads();
-    uint32_t found = forecast ? ck_words[0] + ck_words[1] + ck_words[2] + ck_words[3]
-                              : max(max(ck_words[0], ck_words[1]), max(ck_words[2], ck_words[3]));
-    found = __builtin_amdgcn_readfirstlane(found);
-    __syncthreads();  // (the words are stage memory again from here on)
-    if (forecast ? found >= 3 : found <= emit_cap) {
-      // The tile leaves (uniform; nothing is in flight; the book-keeping follows behind
-      // the loop: a divergent branch on the way out makes the compiler treat the whole
-      // loop as divergent, request addresses and all).
-      left = true;
-      left_forecast = forecast;
-      left_emit = !forecast && found != 0;
-      break;
-    }
+    left = check_sweep(a, tile, plan, acc, lds, seg_end == chk0, all_steps);
+    // The tile leaves (uniform; nothing is in flight; the book-keeping follows behind
+    // the loop: a divergent branch on the way out makes the compiler treat the whole
+    // loop as divergent, request addresses and all).
+    if (left != kStays) break;
     seg_first = seg_end;
   }
+
+  if (leave_early(a, tile, plan, left)) return;
+  if (tile.split && !reduce_pieces(a, tile, acc, lds)) return;
+  emit_candidates(a, tile, plan, acc, lds, left == kLeftEmit);
+}
 #undef F_KSTEP
 #undef F_SLICE_A
 #undef F_SLICE_B
@@ -884,234 +1142,12 @@ __device__ __forceinline__ int filter_tile(const TiledArgs &a, const uint32_t wg
 #undef F_PINF
 #undef F_READ
 #undef F_ISSUE4
+#undef F_ISSUE
 #undef F_PUBLISH
-  if (left && left_emit && threadIdx.x == 0)
-    __hip_atomic_fetch_add(a.filter_totals + kTotalEarly, 1ull, __ATOMIC_RELAXED,
-                           __HIP_MEMORY_SCOPE_AGENT);
-  if (phase != 0 && threadIdx.x == 0)
-    __hip_atomic_fetch_add(a.filter_totals + kTotalRotated, 1ull, __ATOMIC_RELAXED,
-                           __HIP_MEMORY_SCOPE_AGENT);
-  if (left && !left_emit) {
-    // Forecast: the tile leaves for the exact kernel -- its quadrants count as handed
-    // over, the fallback launch is needed.  Rigorous check: for good.
-    if (threadIdx.x == 0) {
-      __hip_atomic_fetch_add(a.filter_ctrl + kCtrlFinished, 4u, __ATOMIC_RELAXED,
-                             __HIP_MEMORY_SCOPE_AGENT);
-      if (left_forecast) {
-        __hip_atomic_fetch_add(a.filter_ctrl + kCtrlLeft, 4u, __ATOMIC_RELAXED,
-                               __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(a.filter_ctrl + kCtrlGate, 1u, __ATOMIC_RELAXED,
-                           __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_fetch_add(
-            a.filter_totals + kTotalDense, 4ull,
-            __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      } else {
-        a.tile_done[bid] = 1;
-        __hip_atomic_fetch_add(
-            a.filter_totals + kTotalEarly, 1ull,
-            __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-    }
-    return 0;
-  }
-
-  // This tile runs to its end here: the fallback launch has nothing to do for it.
-  // (The tiles of remainder pieces are marked by the host.)
-  if (!split && a.tile_done != nullptr && threadIdx.x == 0) a.tile_done[bid] = 1;
-
-  if (split) {
-    // Park this piece (16-byte write-through stores, [4 registers][thread]), take
-    // a ticket of the tile; the last piece in adds the others to its own.
-    typedef uint32_t v4u __attribute__((ext_vector_type(4)));
-    constexpr uint32_t kSlabU4 = 64 * 256;  // float4 per slab
-    {
-      const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
-          a.fsplit_slabs + (size_t)piece * kSlabU4, 0, (int)(kSlabU4 * 16), 0x00020000);
-#pragma unroll
-      for (int bi = 0; bi < 4; ++bi)
-#pragma unroll
-        for (int bj = 0; bj < 4; ++bj)
-#pragma unroll
-          for (int r4 = 0; r4 < 4; ++r4) {
-            v4u v;
-            v[0] = __float_as_uint(acc[bi][bj][4 * r4]);
-            v[1] = __float_as_uint(acc[bi][bj][4 * r4 + 1]);
-            v[2] = __float_as_uint(acc[bi][bj][4 * r4 + 2]);
-            v[3] = __float_as_uint(acc[bi][bj][4 * r4 + 3]);
-            __builtin_amdgcn_raw_buffer_store_b128(
-                v, rsrc, (int)((((bi * 4 + bj) * 4 + r4) * 256 + threadIdx.x) * 16), 0,
-                16 /* sc1 */);
-          }
-    }
-    // every wavefront's stores are done (and written through), then the ticket
-    // (cdna_hip_programming.md, Guideline 16: sc1 payload + counter)
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    uint32_t *flag = reinterpret_cast<uint32_t *>(lds);  // the stages are idle now
-    if (threadIdx.x == 0) {
-      uint32_t *counter = a.fsplit_tickets + piece / a.fsplit_parts;
-      const uint32_t ticket = __hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELAXED,
-                                                     __HIP_MEMORY_SCOPE_AGENT);
-      const bool last = ticket == a.fsplit_parts - 1;
-      if (last) {
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        *counter = 0;  // ready for the next launch
-      }
-      *flag = last ? 1u : 0u;
-    }
-    __syncthreads();
-    const bool last = *flag != 0;
-    __syncthreads();  // (the flag word becomes the epilogue's scratch)
-    if (!last) return 0;
-    const uint32_t first_piece = piece - part;
-    for (uint32_t p = 0; p < a.fsplit_parts; ++p) {
-      if (p == part) continue;
-      const float4 *src = a.fsplit_slabs + (size_t)(first_piece + p) * kSlabU4 + threadIdx.x;
-#pragma unroll
-      for (int bi = 0; bi < 4; ++bi)
-#pragma unroll
-        for (int bj = 0; bj < 4; ++bj)
-#pragma unroll
-          for (int r4 = 0; r4 < 4; ++r4) {
-            const float4 v = src[((bi * 4 + bj) * 4 + r4) * 256];
-            acc[bi][bj][4 * r4] += v.x;
-            acc[bi][bj][4 * r4 + 1] += v.y;
-            acc[bi][bj][4 * r4 + 2] += v.z;
-            acc[bi][bj][4 * r4 + 3] += v.w;
-          }
-    }
-  }
-
-  // --- epilogue: the bound, per pair.  C layout of the 32 x 32 MFMA: column =
-  // lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5).
-  float2 *const st_rows = reinterpret_cast<float2 *>(lds);  // (u~, t |H| + margin) per row
-  float2 *const st_cols = st_rows + kT;
-  {
-    const float t = 2.f - 4.f * a.kin_threshold;
-    const size_t ir = (size_t)tr * kT + threadIdx.x;
-    const size_t ic = (size_t)a.geo.col_base + (size_t)tc * kT + threadIdx.x;
-    float2 r = a.sample_stats[ir];
-    float2 c = a.sample_stats[ic];
-    if (left_emit) {
-      // (the tile left at the rigorous check with a few live pairs: the same test on the
-      //  sums and the per-sample counts of the sites so far -- every record is among the
-      //  pairs it admits, king_filter.hip "Check points")
-      r.x = prefix_u_of(share1, ir, r.x);
-      c.x = prefix_u_of(share1, ic, c.x);
-    }
-    r.y = fmaf(t, r.y, 8.f);
-    c.y = fmaf(t, c.y, 8.f);
-    st_rows[threadIdx.x] = r;
-    st_cols[threadIdx.x] = c;
-  }
-  __syncthreads();
-  float2 sc[4];
-#pragma unroll
-  for (int bj = 0; bj < 4; ++bj) sc[bj] = st_cols[wx * 128 + bj * 32 + lr];
-
-  // Nearly every wavefront has no candidate at all: a first sweep with the bare test
-  // (5 VALU per pair, the largest `bound - x_lb` of the lane: positive <=> the test
-  // below holds for some pair, the sign of a float difference is exact; pairs outside
-  // the block may raise a false alarm, which only costs the sweeps below), then out.
-  {
-    float best = -1.f;
-#pragma unroll
-    for (int bi = 0; bi < 4; ++bi)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const float2 sr = st_rows[wy * 128 + bi * 32 + (r & 3) + 8 * (r >> 2) + 4 * g];
-#pragma unroll
-        for (int bj = 0; bj < 4; ++bj)
-          best = fmaxf(best, fminf(sr.y, sc[bj].y) -
-                                 (fmaf(-8.f, acc[bi][bj][r], sr.x) + sc[bj].x));
-      }
-    if (__ballot(best > 0.f) == 0) {  // wave-uniform
-      if (lane == 0)
-        __hip_atomic_fetch_add(a.filter_ctrl + kCtrlFinished, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      return 0;
-    }
-  }
-  if (lane == 0)
-    __hip_atomic_fetch_add(a.filter_ctrl + kCtrlFinished, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-
-  uint32_t total = 0, base = 0, run = 0;  // wave-uniform
-#pragma nounroll
-  for (int pass = 0; pass < 2; ++pass) {  // 0: count the candidates, 1: append them
-    // (opaque per pass: otherwise the compiler computes the 256 pairs' indices and
-    //  validity once in front of the loop and parks them in scratch memory)
-    uint32_t tr_p = tr, tc_p = tc;
-    asm volatile("" : "+s"(tr_p), "+s"(tc_p));
-#pragma unroll
-    for (int bi = 0; bi < 4; ++bi) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const uint32_t row = wy * 128 + bi * 32 + (r & 3) + 8 * (r >> 2) + 4 * g;
-        const float2 sr = st_rows[row];
-        const uint32_t li = tr_p * kT + row;
-#pragma unroll
-        for (int bj = 0; bj < 4; ++bj) {
-          const uint32_t lj = tc_p * kT + wx * 128 + bj * 32 + lr;
-          // cuking.cu:199 plus the tile padding
-          const bool valid = li < a.geo.num_rows && lj < a.geo.num_cols &&
-                             a.i_begin + li < a.j_begin + lj;
-          // u_i + u_j - 2 q  <  t min(|H_i|, |H_j|) + margin   ("Offset code" above:
-          // u~_i - 8 acc first, below 2^24 in magnitude, then u~_j)
-          const float x_lb = fmaf(-8.f, acc[bi][bj][r], sr.x) + sc[bj].x;
-          const bool cand = valid && x_lb < fminf(sr.y, sc[bj].y);
-          const unsigned long long b = __ballot(cand);
-          if (b != 0) {  // wave-uniform
-            if (pass == 0) {
-              total += (uint32_t)__popcll(b);
-            } else {
-              const uint32_t before = __builtin_amdgcn_mbcnt_hi(
-                  (uint32_t)(b >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b, 0u));
-              if (cand) a.cand_list[base + run + before] = make_uint2(li, lj);
-              run += (uint32_t)__popcll(b);
-            }
-          }
-        }
-      }
-    }
-    if (pass == 0) {
-      if (total == 0) break;  // wave-uniform: the usual case
-      bool dense = total > a.quadrant_cap;
-      if (!dense) {
-        uint32_t got = 0;
-        if (lane == 0) {
-          got = __hip_atomic_fetch_add(a.filter_ctrl, total, __ATOMIC_RELAXED,
-                                       __HIP_MEMORY_SCOPE_AGENT);
-          // (running total since the scratch was allocated: "filter_candidates")
-          __hip_atomic_fetch_add(a.filter_totals + kTotalCand,
-                                 (unsigned long long)total, __ATOMIC_RELAXED,
-                                 __HIP_MEMORY_SCOPE_AGENT);
-        }
-        base = (uint32_t)__builtin_amdgcn_readfirstlane(got);
-        if (base >= a.cand_cap || total > a.cand_cap - base) {
-          // list full: the slots taken (if any) must not be read as pairs
-          for (uint32_t k = base + lane; k < a.cand_cap; k += 64)
-            a.cand_list[k] = make_uint2(kNoPair, kNoPair);
-          dense = true;
-        }
-      }
-      if (dense) {
-        if (lane == 0) {
-          const uint32_t slot = __hip_atomic_fetch_add(a.filter_ctrl + kCtrlDense, 1u, __ATOMIC_RELAXED,
-                                                       __HIP_MEMORY_SCOPE_AGENT);
-          if (slot < a.dense_cap) a.dense_list[slot] = make_uint2(2 * tr + wy, 2 * tc + wx);
-          __hip_atomic_fetch_add(a.filter_totals + kTotalDense, 1ull,
-                                 __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        break;
-      }
-    }
-  }
-  return 0;
-}
 
 __global__ __launch_bounds__(256, 1) void king_filter_kernel(const TiledArgs a) {
   extern __shared__ uint4 lds[];
-  (void)filter_tile(a, blockIdx.x, lds);
+  filter_tile(a, blockIdx.x, lds);
 }
 
 // One wavefront per candidate pair: the reference's six sums (cuking.cu:219-239)

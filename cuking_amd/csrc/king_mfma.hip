@@ -154,7 +154,7 @@ __device__ __attribute__((noinline)) void full_store_call(
 __device__ __attribute__((noinline)) uint32_t reserve_slots(uint32_t *result_index, uint32_t n) {
   uint32_t base = 0;
   if ((threadIdx.x & 63) == 0)
-    base = __hip_atomic_fetch_add(result_index, n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    base = relaxed_add(result_index, n);
   return (uint32_t)__builtin_amdgcn_readfirstlane(base);
 }
 
@@ -226,10 +226,9 @@ __global__ __launch_bounds__(256, 1) void king_mfma_kernel(const TiledArgs a) {
     uint32_t *slot = reinterpret_cast<uint32_t *>(lds);
     if (threadIdx.x == 0) {
       uint32_t *counter = a.split_counters + dyn_counter_index(a.split_wgs);
-      const uint32_t asked = __hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELAXED,
-                                                    __HIP_MEMORY_SCOPE_AGENT);
+      const uint32_t asked = relaxed_add(counter, 1u);
       if (asked == a.dyn_wgs - 1)
-        __hip_atomic_store(counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        relaxed_store(counter, 0u);
       *slot = asked;
     }
     __syncthreads();
@@ -1066,8 +1065,7 @@ __global__ __launch_bounds__(256, 1) void king_mfma_kernel(const TiledArgs a) {
       // One counter per workgroup (and pass): a workgroup owns the first unit
       // of at most one tile that continues into the next workgroup.
       uint32_t *counter = a.split_counters + w_first;
-      const uint32_t ticket = __hip_atomic_fetch_add(
-          counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      const uint32_t ticket = relaxed_add(counter, 1u);
       const bool last = ticket == w_last - w_first;
       if (last) {
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
