@@ -21,6 +21,9 @@ ERR_DEVICE = 5
 KERNEL_TILED = 0
 KERNEL_STREAM = 1
 
+KIN_UPPER = 0
+KIN_SYMMETRIC = 1
+
 
 class CukingError(RuntimeError):
     def __init__(self, status: int, message: str):
@@ -103,6 +106,9 @@ SIGNATURES = {
     "cuking_ctx_reserve": (_int, [_vp, _SM, _u32, C.POINTER(_vp), _sz]),
     "cuking_invalidate": (_int, [_vp]),
     "cuking_compute_counts": (_int, [_vp, _SM, _u32, _vp, _vp, _vp]),
+    "cuking_compute_kin_matrix": (_int, [_vp, _SM, _u32, _vp, _vp, _u64, _u32, _vp]),
+    "cuking_compute_kin_matrix_tiles": (_int, [_vp, _SM, _u32, _vp, _u64, _u64, _vp, _u64,
+                                               _u32, _vp]),
     "cuking_sort_results": (None, [_vp, _sz]),
     "cuking_timing_enable": (_int, [_vp, _int]),
     "cuking_timing_reset": (_int, [_vp]),

@@ -290,6 +290,52 @@ class KingContext:
         return out.cpu().numpy().view(np.uint32).reshape(r, c, 6).view(
             KING_COUNTS_DTYPE).reshape(r, c)
 
+    def kin_matrix(self, submatrix: Submatrix, words_per_sample: int, bit_sets,
+                   out=None, symmetric: bool = False, tile_range=None, stream=None):
+        """Dense kinship matrix (cuking_compute_kin_matrix): the float32 kinship of
+        every pair of the block as a [NumRows, NumCols] device tensor, pair (i, j)
+        at [i - i_begin, j - j_begin]; no threshold, no records.  Does not
+        synchronise.  A diagonal block gets its entries with i < j; with
+        ``symmetric`` also the mirrored ones and the diagonal (0.5, or NaN for a
+        sample without a het site).  ``out``: a float32 tensor of that shape on
+        this GPU to write into, possibly a view with a row pitch of its own
+        (``stride(1) == 1``); entries the call does not write keep what they hold.
+        Without it the result is allocated and untouched entries are NaN.
+        ``tile_range``: only the tiles [begin, end) of the block's enumeration
+        (``num_tiles``), as in ``compute_king``."""
+        import torch
+        self._check_bits(submatrix, words_per_sample, bit_sets)
+        r, c = submatrix.NumRows(), submatrix.NumCols()
+        if out is None:
+            out = torch.full((r, c), float("nan"), dtype=torch.float32,
+                             device=f"cuda:{self.device}")
+        else:
+            if not out.is_cuda or out.device.index != self.device:
+                raise ValueError("out must live on this context's GPU")
+            if out.dtype != torch.float32:
+                raise ValueError("out must be a float32 tensor")
+            if out.dim() != 2 or tuple(out.shape) != (r, c):
+                raise ValueError(f"out has shape {tuple(out.shape)}, the block needs ({r}, {c})")
+            if r > 1 and c > 0 and out.stride(0) < c or c > 1 and out.stride(1) != 1:
+                raise ValueError("out must have unit column stride and a row stride of at "
+                                 "least NumCols")
+        if symmetric and submatrix.i_begin != submatrix.j_begin:
+            raise ValueError("symmetric=True needs a diagonal block")
+        if symmetric and tile_range is not None:
+            raise ValueError("symmetric=True cannot be combined with a tile_range")
+        if r == 0 or c == 0:
+            return out
+        ld = out.stride(0) if r > 1 else max(out.stride(0), c)
+        flags = _lib.KIN_SYMMETRIC if symmetric else _lib.KIN_UPPER
+        args = (self.handle, C.byref(submatrix.c), words_per_sample, bit_sets.data_ptr())
+        tail = (out.data_ptr(), ld, flags, _stream_handle(stream))
+        if tile_range is None:
+            check(self.lib.cuking_compute_kin_matrix(*args, *tail))
+        else:
+            check(self.lib.cuking_compute_kin_matrix_tiles(
+                *args, tile_range[0], tile_range[1], *tail))
+        return out
+
     def run(self, submatrix: Submatrix, words_per_sample: int, bit_sets,
             kin_threshold: float = DEFAULT_KIN_THRESHOLD,
             max_results: int = DEFAULT_MAX_RESULTS, tile_range=None,
@@ -388,8 +434,14 @@ class KingContext:
                 f"{sm.NumSamples()} x {wps}")
 
 
+def kin_matrix(ctx: KingContext, submatrix: Submatrix, words_per_sample: int, bit_sets,
+               **kwargs):
+    """``ctx.kin_matrix(...)``: the dense float32 kinship matrix of a block."""
+    return ctx.kin_matrix(submatrix, words_per_sample, bit_sets, **kwargs)
+
+
 __all__ = [
-    "Submatrix", "KingContext", "KING_RESULT_DTYPE", "KING_COUNTS_DTYPE",
+    "Submatrix", "KingContext", "kin_matrix", "KING_RESULT_DTYPE", "KING_COUNTS_DTYPE",
     "ResourceExhaustedError", "CukingError", "padded_sites",
     "words_per_sample", "bytes_per_pair", "new_host_bitset", "pack_host",
     "sort_results", "device_count", "synth_models", "synth_model_number",

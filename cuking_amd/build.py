@@ -170,8 +170,9 @@ def check_mfma_loops(asm_path: Path, verbose: bool = False):
     import re
 
     def label(f):
-        m = re.match(r"_ZN6cuking12_GLOBAL__N_116king_mfma_kernelILb(\d)ELb(\d)ELb(\d)", f)
-        return f"king_mfma_kernel<FULL={m.group(1)}, SPLIT={m.group(2)}, N4={m.group(3)}>"
+        m = re.match(r"_ZN6cuking12_GLOBAL__N_116king_mfma_kernelILb(\d)ELb(\d)ELb(\d)ELb(\d)", f)
+        return (f"king_mfma_kernel<FULL={m.group(1)}, SPLIT={m.group(2)}, N4={m.group(3)}, "
+                f"KIN={m.group(4)}>")
     return check_dma_loops(asm_path, "king_mfma_kernel",
                            r"_ZN6cuking12_GLOBAL__N_116king_mfma_kernel", (16, 20, 24), label, verbose)
 

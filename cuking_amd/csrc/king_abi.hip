@@ -163,6 +163,9 @@ struct cuking_ctx {
     uint32_t tile = 0;  // tile edge of the geometry (the context variant's)
     const uint64_t *bits = nullptr;
     bool codes = true;  // every converted tile has its nibble codes (false: T2 only, lazy)
+    // converted for a dense kinship matrix: never sorted, whatever "filter_sort" says (a
+    // call of the other kind does not take the layout over: it converts again)
+    bool dense_order = false;
     // per 64 plane samples: 0 = not converted, 1 = converted (kernels that
     // read it, if any, all precede the tail of `ordered_on`), 2 = converted
     // and read by kernels enqueued since
@@ -432,6 +435,10 @@ struct Outputs {
   cuking_result *results;
   uint32_t *result_index, *result_overflow;
   cuking_counts *counts;
+  // dense kinship matrix (TiledArgs::dense_kin): every pair's float32 kinship, no records
+  float *kin;
+  uint64_t kin_ld;
+  uint32_t kin_flags;
 };
 cuking_status launch_args(cuking_ctx *ctx, hipStream_t stream, const cuking_submatrix &sm,
                           uint32_t words_per_sample, const uint64_t *d_bit_sets,
@@ -452,6 +459,9 @@ cuking_status launch_args(cuking_ctx *ctx, hipStream_t stream, const cuking_subm
   a.result_index = out.result_index;
   a.result_overflow = out.result_overflow;
   a.dense_counts = out.counts;
+  a.dense_kin = out.kin;
+  a.kin_ld = out.kin_ld;
+  a.kin_diag = (out.kin != nullptr && (out.kin_flags & CUKING_KIN_SYMMETRIC)) ? 1u : 0u;
   a.rect_row_stride = 1;
   a.bits = d_bit_sets;
   a.words_per_sample = words_per_sample;
@@ -644,8 +654,8 @@ cuking_status convert_codes_now(cuking_ctx *ctx, const PlaneGeometry &geo,
 cuking_status prepare(cuking_ctx *ctx, const cuking_submatrix &sm,
                       uint32_t words_per_sample, const uint64_t *d_bit_sets,
                       hipStream_t stream, PlaneGeometry *geo_out,
-                      TileSpace *tiles_out, bool need_codes, uint32_t s_tile_begin = 0,
-                      uint32_t s_tile_end = 0xFFFFFFFFu) {
+                      TileSpace *tiles_out, bool need_codes, bool dense_order,
+                      uint32_t s_tile_begin = 0, uint32_t s_tile_end = 0xFFFFFFFFu) {
   const int variant = effective_variant(ctx, words_per_sample);
   const TiledVariant v = plan_variant(ctx, words_per_sample);
   const PlaneGeometry geo = make_geometry(sm, words_per_sample, v);
@@ -662,7 +672,10 @@ cuking_status prepare(cuking_ctx *ctx, const cuking_submatrix &sm,
   const uint32_t t_end = s_tile_end < all_tiles ? s_tile_end : all_tiles;
   cuking_ctx::Prepared &pr = ctx->prepared;
   const bool new_prefix = !same_tile_space(ctx->prefix_for, tiles);
-  const bool same = same_block(pr, sm, words_per_sample, variant, v.tile, d_bit_sets);
+  // (a layout converted for a dense kinship matrix is unsorted: a call of the other kind
+  //  treats it as another block's, and the other way round)
+  const bool same = same_block(pr, sm, words_per_sample, variant, v.tile, d_bit_sets) &&
+                    pr.dense_order == dense_order;
   if (ctx->reuse_prepared && same && !new_prefix) {
     // The host has promised that the bitset behind this pointer is unchanged
     // since it was converted (cuking_invalidate otherwise): nothing to do when
@@ -692,6 +705,7 @@ cuking_status prepare(cuking_ctx *ctx, const cuking_submatrix &sm,
     pr.bits = d_bit_sets;
     pr.tiles.assign(all_tiles, 0);
     pr.codes = true;
+    pr.dense_order = dense_order;
   }
   for (uint32_t t = s_tile_begin; t < t_end; ++t)
     must_wait = must_wait || pr.tiles[t] == 2 || (pr.tiles[t] == 1 && other_stream);
@@ -724,7 +738,8 @@ cuking_status prepare(cuking_ctx *ctx, const cuking_submatrix &sm,
     HIP_TRY(hipMemsetAsync(plane_flags(ctx->planes, geo), 0, sizeof(uint32_t), stream));
     HIP_TRY(launch_sample_stats(d_bit_sets, words_per_sample, geo, ctx->planes, sb, se, stream));
     HIP_TRY(launch_sample_order(geo, words_per_sample, ctx->planes, sb, se,
-                                ctx->filter_sort == 2 || (ctx->filter_sort == 1 && whole),
+                                !dense_order &&
+                                    (ctx->filter_sort == 2 || (ctx->filter_sort == 1 && whole)),
                                 ctx->sort_temp, ctx->sort_temp_bytes, stream));
     HIP_TRY(launch_prepare_nibbles(codes, true, d_bit_sets, words_per_sample, geo, ctx->planes,
                                    plane_perm(ctx->planes, geo), s_tile_begin, t_end, nullptr,
@@ -752,11 +767,19 @@ cuking_status run_tiled(cuking_ctx *ctx, const cuking_submatrix &sm,
                         float kin_threshold, const Outputs &out, hipStream_t stream) {
   PlaneGeometry geo;
   TileSpace tiles;
-  const bool full = use_full_counts(ctx, kin_threshold, out.counts != nullptr, words_per_sample);
+  // A dense kinship matrix: the matrix-core kernels' lean form with an epilogue of its own
+  // (contexts of variant 6 and 7: the four-product kernel, the latter on the quadrants of
+  // its tiles; variant 5 and wide bitsets: the five-product kernel), on a layout that is
+  // never sorted; the VALU kernels store it from their full form.
+  const bool kin = out.kin != nullptr;
+  const int kv = effective_variant(ctx, words_per_sample);
+  const bool kin_mfma = kin && is_mfma_variant(kv);
+  const bool full = !kin_mfma && use_full_counts(ctx, kin_threshold, out.counts != nullptr || kin,
+                                               words_per_sample);
   const LaunchSwitches sw = launch_switches(ctx, words_per_sample, full, kin_threshold);
   // (where the filter runs the four-product kernel's codes may stay unconverted)
   cuking_status st = prepare(ctx, sm, words_per_sample, d_bit_sets, stream, &geo, &tiles,
-                             !sw.filter_runs);
+                             !sw.filter_runs, kin);
   if (st != CUKING_OK) return st;
   const uint64_t n_tiles = total_tiles(tiles);
   if (whole) {
@@ -778,9 +801,17 @@ cuking_status run_tiled(cuking_ctx *ctx, const cuking_submatrix &sm,
 
   EventPair *ev = nullptr;
   if (ctx->timing) HIP_TRY(ctx->king_timer.begin(stream, &ev));
-  HIP_TRY(launch_planned(ctx, words_per_sample, full, a, sw, tile_end - tile_begin, stream));
+  if (kin_mfma) {
+    uint64_t units = tile_end - tile_begin;
+    if (tiled_variant(ctx->variant).tile == kFilterTile) to_quadrants(&a, &units);
+    a.perm = nullptr;  // (the identity: prepare() above did not sort)
+    HIP_TRY(launch_mfma_kin(kv != kMfmaVariant, a, sw, units, stream));
+  } else {
+    HIP_TRY(launch_planned(ctx, words_per_sample, full, a, sw, tile_end - tile_begin, stream));
+  }
   note_reader(ctx, stream);
   mark_read(ctx, 0, 0xFFFFFFFFu);
+  if (a.kin_diag != 0) HIP_TRY(launch_kin_mirror(out.kin, out.kin_ld, geo.num_rows, stream));
   if (ev) HIP_TRY(hipEventRecord(ev->stop, stream));
   return CUKING_OK;
 }
@@ -790,12 +821,15 @@ cuking_status run_stream(cuking_ctx *ctx, const cuking_submatrix &sm,
                          float kin_threshold, uint32_t max_results,
                          cuking_result *d_results, uint32_t *d_result_index,
                          uint32_t *d_result_overflow, cuking_counts *d_counts,
-                         hipStream_t stream) {
+                         hipStream_t stream, float *d_kin = nullptr, uint64_t kin_ld = 0,
+                         uint32_t kin_flags = 0) {
   EventPair *ev = nullptr;
   if (ctx->timing) HIP_TRY(ctx->king_timer.begin(stream, &ev));
+  const uint32_t kin_diag = (d_kin != nullptr && (kin_flags & CUKING_KIN_SYMMETRIC)) ? 1u : 0u;
   HIP_TRY(launch_stream(sm, words_per_sample, d_bit_sets, kin_threshold,
                         max_results, d_results, d_result_index,
-                        d_result_overflow, d_counts, stream));
+                        d_result_overflow, d_counts, d_kin, kin_ld, kin_diag, stream));
+  if (kin_diag != 0) HIP_TRY(launch_kin_mirror(d_kin, kin_ld, sm_num_rows(sm), stream));
   if (ev) HIP_TRY(hipEventRecord(ev->stop, stream));
   return CUKING_OK;
 }
@@ -1329,7 +1363,7 @@ cuking_status cuking_prepare_samples(cuking_ctx *ctx, const cuking_submatrix *sm
   TileSpace tiles;
   // prepare() works in units of 64 plane samples.
   return prepare(ctx, *sm, words_per_sample, d_bit_sets, (hipStream_t)stream, &geo,
-                 &tiles, true, t0 * (tile / 64), t1 * (tile / 64));
+                 &tiles, true, false, t0 * (tile / 64), t1 * (tile / 64));
 }
 
 cuking_status cuking_compute_king_rect(
@@ -1508,6 +1542,70 @@ cuking_status cuking_compute_counts(cuking_ctx *ctx, const cuking_submatrix *sm,
                       nullptr, nullptr, d_counts, (hipStream_t)stream);
   return run_tiled(ctx, *sm, words_per_sample, d_bit_sets, 0, 0, true, 0.f,
                    {0, nullptr, nullptr, nullptr, d_counts}, (hipStream_t)stream);
+}
+
+// The checks the two dense-kinship entry points share, in front of anything that touches
+// a device.
+static cuking_status check_kin_args(const cuking_ctx *ctx, const cuking_submatrix *sm,
+                                    uint32_t words_per_sample, const uint64_t *d_bit_sets,
+                                    const float *d_kin, uint64_t ld, uint32_t flags,
+                                    bool tile_range) {
+  cuking_status st = check_compute_args(sm, words_per_sample, d_bit_sets);
+  if (st != CUKING_OK) return st;
+  if (flags != CUKING_KIN_UPPER && flags != CUKING_KIN_SYMMETRIC)
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "unknown kinship matrix flags 0x%x", flags);
+  if (ld < sm_num_cols(*sm))
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT,
+                       "kinship matrix: leading dimension %llu below the block's %u columns",
+                       (unsigned long long)ld, sm_num_cols(*sm));
+  if (flags == CUKING_KIN_SYMMETRIC && !sm_is_diag(*sm))
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT,
+                       "a symmetric kinship matrix needs a diagonal block (rows == columns)");
+  if (flags == CUKING_KIN_SYMMETRIC && tile_range)
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT,
+                       "a symmetric kinship matrix cannot be computed by tile ranges");
+  if (sm_num_rows(*sm) != 0 && sm_num_cols(*sm) != 0 && d_kin == nullptr)
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "null kinship matrix pointer");
+  if (ctx == nullptr) return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "null context");
+  return CUKING_OK;
+}
+
+cuking_status cuking_compute_kin_matrix(cuking_ctx *ctx, const cuking_submatrix *sm,
+                                        uint32_t words_per_sample, const uint64_t *d_bit_sets,
+                                        float *d_kin, uint64_t ld, uint32_t flags,
+                                        void *stream) {
+  cuking_status st =
+      check_kin_args(ctx, sm, words_per_sample, d_bit_sets, d_kin, ld, flags, false);
+  if (st != CUKING_OK) return st;
+  st = bind(ctx);
+  if (st != CUKING_OK) return st;
+  if (sm_num_rows(*sm) == 0 || sm_num_cols(*sm) == 0) return CUKING_OK;
+  if (ctx->kernel == CUKING_KERNEL_STREAM)
+    return run_stream(ctx, *sm, words_per_sample, d_bit_sets, 0.f, 0, nullptr, nullptr,
+                      nullptr, nullptr, (hipStream_t)stream, d_kin, ld, flags);
+  return run_tiled(ctx, *sm, words_per_sample, d_bit_sets, 0, 0, true, 0.f,
+                   {0, nullptr, nullptr, nullptr, nullptr, d_kin, ld, flags},
+                   (hipStream_t)stream);
+}
+
+cuking_status cuking_compute_kin_matrix_tiles(cuking_ctx *ctx, const cuking_submatrix *sm,
+                                              uint32_t words_per_sample,
+                                              const uint64_t *d_bit_sets, uint64_t tile_begin,
+                                              uint64_t tile_end, float *d_kin, uint64_t ld,
+                                              uint32_t flags, void *stream) {
+  cuking_status st =
+      check_kin_args(ctx, sm, words_per_sample, d_bit_sets, d_kin, ld, flags, true);
+  if (st != CUKING_OK) return st;
+  st = bind(ctx);
+  if (st != CUKING_OK) return st;
+  if (sm_num_rows(*sm) == 0 || sm_num_cols(*sm) == 0) {
+    if (tile_begin != 0 || tile_end != 0)
+      return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "empty block has no tiles");
+    return CUKING_OK;
+  }
+  return run_tiled(ctx, *sm, words_per_sample, d_bit_sets, tile_begin, tile_end, false, 0.f,
+                   {0, nullptr, nullptr, nullptr, nullptr, d_kin, ld, flags},
+                   (hipStream_t)stream);
 }
 
 // ---- timing ---------------------------------------------------------------

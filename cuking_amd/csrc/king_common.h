@@ -271,6 +271,18 @@ struct TiledArgs {
   // gated launch behind the filter kernel only if a quadrant went dense or a tile left
   // (codes_ready: device word, 1 once they are there for the prepared block).
   uint32_t *codes_ready;
+  // Dense kinship matrix (cuking_compute_kin_matrix; at the END of the struct: the kernels
+  // that do not read them keep their argument offsets): dense_kin non-null = no threshold,
+  // no records, the float32 kinship of pair (li, lj) goes to dense_kin[li * kin_ld + lj]
+  // (kin_ld in elements, 64-bit arithmetic).  kin_diag = 1 (a diagonal block, symmetric
+  // output): the pairs (i, i) are stored as well -- the upper triangle WITH the diagonal;
+  // the mirror kernel (launch_kin_mirror) fills the rest.  The matrix-core kernels have
+  // instantiations of their own for this (king_mfma.hip, KIN), which always run on an
+  // UNSORTED layout (perm is the identity and is not read); the VALU kernels store it from
+  // their full form (king_device.h dense_kin_pair).
+  float *dense_kin;
+  uint64_t kin_ld;
+  uint32_t kin_diag;
 };
 
 // Prefix statistics: the k-steps (of 256 sites) a check may sit behind, as shares of the
@@ -488,6 +500,16 @@ hipError_t launch_tiled(int variant, bool full, const TiledArgs &args, const Lau
 // The matrix-core kernel (king_mfma.hip); reached through launch_tiled.
 hipError_t launch_mfma(bool full, bool nibble, const TiledArgs &args, const LaunchSwitches &sw,
                        uint64_t num_tiles, uint32_t lds_bytes, hipStream_t stream);
+// The matrix-core kernels' dense-kinship form (TiledArgs::dense_kin; king_mfma.hip, KIN):
+// the lean k loop of the four-product (nibble) or the five-product kernel, and an epilogue
+// that stores the float32 kinship of every pair.  Same launch plan as launch_mfma
+// (chunking, XCD order, dynamic tail, remainder split).
+hipError_t launch_mfma_kin(bool nibble, const TiledArgs &args, const LaunchSwitches &sw,
+                           uint64_t num_tiles, hipStream_t stream);
+// Symmetric fill of an n x n kinship matrix whose upper triangle (and diagonal) is there:
+// kin[j * ld + i] = kin[i * ld + j] for i < j, tile-wise through LDS, reads and writes
+// coalesced.  Runs behind the pair kernel on the same stream.
+hipError_t launch_kin_mirror(float *d_kin, uint64_t ld, uint32_t n, hipStream_t stream);
 // The four-product kernel, lean form, over the first min(*count, cap) entries of the device
 // list `list` (TiledArgs::tile_list) with `grid` workgroups.
 hipError_t launch_mfma_list(const TiledArgs &args, const uint2 *list, const uint32_t *count,
@@ -555,7 +577,8 @@ hipError_t launch_stream(const cuking_submatrix &sm, uint32_t words_per_sample,
                          const uint64_t *d_bit_sets, float kin_threshold,
                          uint32_t max_results, cuking_result *d_results,
                          uint32_t *d_result_index, uint32_t *d_result_overflow,
-                         cuking_counts *d_dense_counts, hipStream_t stream);
+                         cuking_counts *d_dense_counts, float *d_dense_kin, uint64_t kin_ld,
+                         uint32_t kin_diag, hipStream_t stream);
 
 hipError_t launch_pack(const cuking_submatrix &sm, uint32_t words_per_sample,
                        uint64_t *d_bit_set, const int64_t *d_row_idx,

@@ -363,6 +363,17 @@ __device__ __forceinline__ void full_epilogue_pair(
   }
 }
 
+// Dense kinship matrix (TiledArgs::dense_kin), the VALU kernels' full form: the pair's
+// kinship, no threshold, stored at its place.  (These kernels read a layout in stored
+// order.)  With kin_diag the pairs (i, i) of a diagonal block, which `valid` leaves out,
+// are stored as well.
+__device__ __forceinline__ void dense_kin_pair(const TiledArgs &a, bool valid, uint32_t li,
+                                               uint32_t lj, uint32_t het_i, uint32_t het_j,
+                                               uint32_t both_het, uint32_t opp) {
+  if (!valid && !(a.kin_diag != 0 && li == lj && li < a.geo.num_rows)) return;
+  a.dense_kin[(uint64_t)li * a.kin_ld + lj] = king_kinship(het_i, het_j, both_het, opp);
+}
+
 // "Done once per device" flag for per-function attributes
 // (hipFuncSetAttribute applies to the current device's function object only).
 // Lock-free; a race merely sets the attribute twice.

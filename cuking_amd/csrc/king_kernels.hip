@@ -498,7 +498,9 @@ __global__ __launch_bounds__(TIT *TJT, MINW) void king_tiled_kernel(
       // cuking.cu:199 plus the tile padding
       const bool valid = li < a.geo.num_rows && lj < a.geo.num_cols &&
                          a.i_begin + li < a.j_begin + lj;
-      if (FULL)
+      if (FULL && a.dense_kin != nullptr)
+        dense_kin_pair(a, valid, li, lj, c_hi[x][y], c_hj[x][y], c_bh[x][y], c_opp[x][y]);
+      else if (FULL)
         full_epilogue_pair(a, valid, li, lj, c_hi[x][y], c_hj[x][y], c_bh[x][y],
                            c_opp[x][y], c_hh[x][y]);
       else
@@ -520,7 +522,8 @@ __global__ __launch_bounds__(256) void king_stream_kernel(
     const uint64_t *__restrict__ bits, const float kin_threshold,
     const uint32_t max_results, cuking_result *results, uint32_t *result_index,
     uint32_t *result_overflow, cuking_counts *dense_counts,
-    const uint64_t block_offset) {
+    const uint64_t block_offset, float *dense_kin, const uint64_t kin_ld,
+    const uint32_t kin_diag) {
   const uint32_t lane = threadIdx.x & 63;
   const uint32_t wave = threadIdx.x >> 6;
   const uint32_t num_cols = sm_num_cols(sm);
@@ -529,7 +532,8 @@ __global__ __launch_bounds__(256) void king_stream_kernel(
   const uint32_t li = (uint32_t)(b / col_groups);
   const uint32_t lj = (uint32_t)(b % col_groups) * 4 + wave;
   const uint32_t i = sm.i_begin + li, j = sm.j_begin + lj;
-  if (lj >= num_cols || i >= j) return;  // whole wavefront leaves together
+  // (kin_diag: a symmetric dense kinship matrix keeps the pairs (i, i))
+  if (lj >= num_cols || i >= j + kin_diag) return;  // whole wavefront leaves together
 
   const uint32_t n = words_per_sample / 2;
   const uint64_t *het_i_w =
@@ -575,6 +579,10 @@ __global__ __launch_bounds__(256) void king_stream_kernel(
     return;
   }
   const float kin = king_kinship(s_het_i, s_het_j, s_both, s_opp);
+  if (dense_kin != nullptr) {
+    dense_kin[(uint64_t)li * kin_ld + lj] = kin;
+    return;
+  }
   if (kin > kin_threshold) {
     const uint32_t ibs0 = s_opp, ibs2 = s_conc + s_both;
     emit_result(i, j, kin, ibs0, s_shared - ibs0 - ibs2, ibs2, max_results,
@@ -813,7 +821,8 @@ hipError_t launch_stream(const cuking_submatrix &sm, uint32_t words_per_sample,
                          const uint64_t *d_bit_sets, float kin_threshold,
                          uint32_t max_results, cuking_result *d_results,
                          uint32_t *d_result_index, uint32_t *d_result_overflow,
-                         cuking_counts *d_dense_counts, hipStream_t stream) {
+                         cuking_counts *d_dense_counts, float *d_dense_kin, uint64_t kin_ld,
+                         uint32_t kin_diag, hipStream_t stream) {
   const uint64_t rows = sm_num_rows(sm);
   const uint64_t col_groups = ((uint64_t)sm_num_cols(sm) + 3) / 4;
   const uint64_t blocks = rows * col_groups;
@@ -822,7 +831,7 @@ hipError_t launch_stream(const cuking_submatrix &sm, uint32_t words_per_sample,
     const uint64_t n = blocks - done < cap ? blocks - done : cap;
     king_stream_kernel<<<dim3((uint32_t)n), dim3(256), 0, stream>>>(
         sm, words_per_sample, d_bit_sets, kin_threshold, max_results, d_results,
-        d_result_index, d_result_overflow, d_dense_counts, done);
+        d_result_index, d_result_overflow, d_dense_counts, done, d_dense_kin, kin_ld, kin_diag);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
   }

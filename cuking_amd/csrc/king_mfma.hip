@@ -195,8 +195,16 @@ __device__ __forceinline__ uint32_t split_owner(uint64_t u, uint64_t units,
 // workgroup that delivers a tile's last part adds the others to its own and
 // runs the epilogue.
 // N4 = the four-product form on the nibble layout (below, "Four products").
-template <bool FULL, bool SPLIT, bool N4 = false>
+// KIN = the dense-kinship form of the lean kernels (TiledArgs::dense_kin): the same k loop,
+// and an epilogue that stores the float32 kinship of EVERY pair instead of appending
+// records -- instantiations of their own, so that the epilogues of the others carry neither
+// its branch nor its registers (a run-time branch in the shared full epilogue was enough
+// for the five-product full form to reload a spilled value inside its k loop).  The
+// four-product one is the hot path; the five-product one serves contexts of variant 5 and
+// bitsets from 2^22 sites on.
+template <bool FULL, bool SPLIT, bool N4 = false, bool KIN = false>
 __global__ __launch_bounds__(256, 1) void king_mfma_kernel(const TiledArgs a) {
+  static_assert(!KIN || !FULL, "the dense-kinship form is a lean one");
   // Five-product form: the lean form has 10 LDS stages and ONE stage barrier per
   // two k-steps (below); the full form parks its fifth sum in the LDS behind the
   // stages and keeps 6 stages with a barrier per k-step.  Four-product form:
@@ -1222,13 +1230,33 @@ __global__ __launch_bounds__(256, 1) void king_mfma_kernel(const TiledArgs a) {
         const uint32_t li =
             tr * kTile + wr + half_rows + bi * 32 + (r & 3) + 8 * (r >> 2) + 4 * g;
         // cuking.cu:199 plus the tile padding
+        // (dense kinship, symmetric output: the diagonal as well)
         const bool valid = li < a.geo.num_rows && lj < a.geo.num_cols &&
-                           a.i_begin + li < a.j_begin + lj;
+                           a.i_begin + li < a.j_begin + lj + (KIN ? a.kin_diag : 0u);
         if (FULL) {
           // diagnostic counts: cuking.cu:284-313 with all five sums at hand
           uint32_t het_i, het_j, both_het, opp, hom_hom;
           pair_sums(bi, bj, r, hh[r], &het_i, &het_j, &both_het, &opp, &hom_hom);
           full_epilogue_pair(a, valid, li, lj, het_i, het_j, both_het, opp, hom_hom);
+        } else if constexpr (KIN) {
+          // Dense kinship: the lean epilogue's expression for every pair (four products:
+          // lean_epilogue_pair_n4's, on the exact integers hi, hj, num = hi + hj - 2 dd +
+          // 2 q), with the IEEE divide -- and one store.
+          // Column = lane & 31: the 32 lanes of a half-wave write 128 contiguous bytes of
+          // matrix row li.  (An unsorted layout: plane index = stored sample.)
+          float kin;
+          if constexpr (N4) {
+            const uint32_t het_i = (uint32_t)(2.f * acc[bi][bj][0][r]);
+            const uint32_t het_j = (uint32_t)(2.f * acc[bi][bj][1][r]);
+            const int32_t num = (int32_t)(het_i + het_j) - 2 * (int32_t)acc[bi][bj][2][r] +
+                                2 * (int32_t)(0.25f * acc[bi][bj][3][r]);
+            kin = 0.5f + (float)num / (4.f * (float)(het_i < het_j ? het_i : het_j));
+          } else {
+            // (five products: the accumulators are the reference's own four sums)
+            kin = king_kinship((uint32_t)acc[bi][bj][2][r], (uint32_t)acc[bi][bj][3][r],
+                               (uint32_t)acc[bi][bj][1][r], (uint32_t)acc[bi][bj][0][r]);
+          }
+          if (valid) a.dense_kin[(uint64_t)li * a.kin_ld + lj] = kin;
         } else if constexpr (N4) {
           // Four products, lean: the decision needs hi, hj and the numerator
           // hi + hj - 2 dd + 2 q only; bh and opp of an emitted pair follow from
@@ -1271,10 +1299,10 @@ void set_shape(TiledArgs *a, const WholeShape &s) {
 
 // Whole tiles [args.tile_begin, + num_blocks) in as many launches as the block limit asks
 // for, or (SPLIT) the one launch of args.split_whole whole tiles + args.split_wgs pieces.
-template <bool FULL, bool SPLIT, bool N4 = false>
+template <bool FULL, bool SPLIT, bool N4 = false, bool KIN = false>
 hipError_t launch_shape(const TiledArgs &args, const LaunchSwitches &sw, uint64_t num_blocks,
                         uint32_t lds_bytes, hipStream_t stream) {
-  constexpr auto kernel = king_mfma_kernel<FULL, SPLIT, N4>;
+  constexpr auto kernel = king_mfma_kernel<FULL, SPLIT, N4, KIN>;
   // (five products: the caller's figure is the 6-stage one of the variant table)
   if (N4) lds_bytes = kMfmaN4LdsBytes;
   else if (FULL) lds_bytes += kMfmaParkBytes;  // the parked fifth sum, behind the stages
@@ -1313,10 +1341,19 @@ size_t mfma_split_scratch_bytes(uint32_t wgs) {
 size_t mfma_split_counter_bytes(uint32_t wgs) { return split_counter_bytes(wgs); }
 
 namespace {
-// launch_shape<FULL, SPLIT, N4> by run-time flags
-hipError_t launch_form(bool full, bool split, bool nibble, const TiledArgs &a,
+// launch_shape<FULL, SPLIT, N4, KIN> by run-time flags (kin: the dense-kinship form, which
+// is lean)
+hipError_t launch_form(bool full, bool split, bool nibble, bool kin, const TiledArgs &a,
                        const LaunchSwitches &sw, uint64_t blocks, uint32_t lds_bytes,
                        hipStream_t stream) {
+  if (kin) {
+    if (full) return hipErrorInvalidValue;
+    if (nibble)
+      return split ? launch_shape<false, true, true, true>(a, sw, blocks, lds_bytes, stream)
+                   : launch_shape<false, false, true, true>(a, sw, blocks, lds_bytes, stream);
+    return split ? launch_shape<false, true, false, true>(a, sw, blocks, lds_bytes, stream)
+                 : launch_shape<false, false, false, true>(a, sw, blocks, lds_bytes, stream);
+  }
   if (nibble) {
     if (split)
       return full ? launch_shape<true, true, true>(a, sw, blocks, lds_bytes, stream)
@@ -1371,22 +1408,72 @@ hipError_t launch_mfma_gated(const TiledArgs &args, uint64_t num_units, const ui
   return launch_strided(a, grid, stream);
 }
 
-hipError_t launch_mfma(bool full, bool nibble, const TiledArgs &args, const LaunchSwitches &sw,
-                       uint64_t num_tiles, uint32_t lds_bytes, hipStream_t stream) {
+namespace {
+hipError_t launch_planned_form(bool full, bool nibble, bool kin, const TiledArgs &args,
+                               const LaunchSwitches &sw, uint64_t num_tiles, uint32_t lds_bytes,
+                               hipStream_t stream) {
   if ((uint64_t)args.geo.k_words * 32 > (nibble ? kMfmaN4MaxSites : kMfmaMaxSites))
     return hipErrorInvalidValue;
   // Whole tiles first, then ONE launch of whole tiles and the remainder in pieces
   // (king_launch_plan.h mfma_plan).  (Never split without scratch for the pieces.)
   const MfmaPlan p = mfma_plan(num_tiles, args.split_scratch != nullptr ? args.split_wgs : 0,
                                args.geo.k_words / 8, max_blocks_per_launch(256));
-  hipError_t e = launch_form(full, false, nibble, args, sw, p.first, lds_bytes, stream);
+  hipError_t e = launch_form(full, false, nibble, kin, args, sw, p.first, lds_bytes, stream);
   if (e != hipSuccess || p.split_tiles == 0) return e;
   TiledArgs a = args;
   a.tile_begin = args.tile_begin + p.first;
   a.split_whole = p.split_whole;
   a.split_tiles = p.split_tiles;
-  return launch_form(full, true, nibble, a, sw, (uint64_t)p.split_whole + args.split_wgs, lds_bytes,
-                     stream);
+  return launch_form(full, true, nibble, kin, a, sw, (uint64_t)p.split_whole + args.split_wgs,
+                     lds_bytes, stream);
+}
+}  // namespace
+
+hipError_t launch_mfma(bool full, bool nibble, const TiledArgs &args, const LaunchSwitches &sw,
+                       uint64_t num_tiles, uint32_t lds_bytes, hipStream_t stream) {
+  return launch_planned_form(full, nibble, false, args, sw, num_tiles, lds_bytes, stream);
+}
+
+hipError_t launch_mfma_kin(bool nibble, const TiledArgs &args, const LaunchSwitches &sw,
+                           uint64_t num_tiles, hipStream_t stream) {
+  if (args.dense_kin == nullptr || args.perm != nullptr) return hipErrorInvalidValue;
+  if (num_tiles == 0) return hipSuccess;
+  // (the lean forms size their LDS themselves: launch_shape)
+  return launch_planned_form(false, nibble, true, args, sw, num_tiles, 0, stream);
+}
+
+// ---- symmetric fill of a dense kinship matrix --------------------------------------------
+namespace {
+constexpr uint32_t kMirrorTile = 32;
+// Workgroup (bx, by), by <= bx, reads the 32 x 32 tile at rows 32 by, columns 32 bx of the
+// upper triangle (rows of 128 contiguous bytes) into LDS and writes its transpose at rows
+// 32 bx, columns 32 by (again rows of 128 bytes), strictly below the diagonal only.
+__global__ __launch_bounds__(256) void kin_mirror_kernel(float *kin, const uint64_t ld,
+                                                         const uint32_t n) {
+  __shared__ float tile[kMirrorTile][kMirrorTile + 1];  // (+ 1: no bank conflicts on the columns)
+  const uint32_t bx = blockIdx.x, by = blockIdx.y;
+  if (by > bx) return;  // uniform
+  const uint32_t x = threadIdx.x & 31, y0 = threadIdx.x >> 5;
+#pragma unroll
+  for (uint32_t y = y0; y < kMirrorTile; y += 8) {
+    const uint32_t row = by * kMirrorTile + y, col = bx * kMirrorTile + x;
+    if (row < n && col < n) tile[y][x] = kin[(uint64_t)row * ld + col];
+  }
+  __syncthreads();
+#pragma unroll
+  for (uint32_t y = y0; y < kMirrorTile; y += 8) {
+    const uint32_t row = bx * kMirrorTile + y, col = by * kMirrorTile + x;
+    if (row < n && col < row) kin[(uint64_t)row * ld + col] = tile[x][y];
+  }
+}
+}  // namespace
+
+hipError_t launch_kin_mirror(float *d_kin, uint64_t ld, uint32_t n, hipStream_t stream) {
+  if (n < 2) return hipSuccess;
+  const uint32_t tiles = (n + kMirrorTile - 1) / kMirrorTile;
+  if (tiles > 65535) return hipErrorInvalidValue;  // (grid y; such a matrix is 16 TB)
+  kin_mirror_kernel<<<dim3(tiles, tiles), dim3(256), 0, stream>>>(d_kin, ld, n);
+  return hipGetLastError();
 }
 
 }  // namespace cuking

@@ -56,6 +56,11 @@ def parse_args(argv=None):
     flag("synthetic-model", default="",
          help="cohort model of --synthetic: baseline (default), exome or admixed "
               "(csrc/synth.hip holds the specification)")
+    flag("kin-matrix-uri", default="",
+         help="also write the block's dense kinship matrix -- the float32 kinship of EVERY "
+              "pair, no threshold -- to this .npy file ([NumRows, NumCols]; a diagonal block "
+              "symmetric with its diagonal).  One process only; the matrix must fit the GPU "
+              "beside the bitset (4 B x NumRows x NumCols: use --split-factor otherwise)")
     return ap.parse_args(argv)
 
 
@@ -83,6 +88,10 @@ def validate(args):  # cuking.cu:437-462
         raise UsageError("Invalid split factor")
     if not 0 <= args.shard_index < args.split_factor * (args.split_factor + 1) // 2:
         raise UsageError("Invalid shard index")
+    if args.kin_matrix_uri and int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise UsageError("--kin_matrix_uri needs one process (one GPU): a dense kinship matrix "
+                         "is not assembled from several GPUs; run the shards of a "
+                         "--split-factor one after the other instead")
 
 
 def read_and_pack(in_dir: Path, sm, num_sites: int, threads: int) -> np.ndarray:
@@ -144,6 +153,24 @@ def write_results(path: Path, recs: np.ndarray, sample_ids) -> None:
                    row_group_size=max(len(recs), 1))
 
 
+def write_kin_matrix(path: Path, ctx, sm, wps: int, bits, device: int) -> None:
+    """The block's dense kinship matrix as a float32 .npy (a diagonal block symmetric)."""
+    import torch
+    rows, cols = sm.NumRows(), sm.NumCols()
+    need = 4 * rows * cols
+    free, _ = torch.cuda.mem_get_info(device)
+    if need > free:
+        raise RuntimeError(
+            f"the kinship matrix of this block ({rows} x {cols} float32 = {need / 1e9:.1f} GB) "
+            f"does not fit the {free / 1e9:.1f} GB free on the GPU: split the cohort into "
+            "blocks with --split-factor (one matrix per shard)")
+    kin = ctx.kin_matrix(sm, wps, bits, symmetric=sm.i_begin == sm.j_begin)
+    torch.cuda.synchronize(device)
+    path.parent.mkdir(parents=True, exist_ok=True)
+    with open(path, "wb") as f:   # (np.save would append .npy to another suffix)
+        np.save(f, kin.cpu().numpy())
+
+
 def main(argv=None) -> int:
     args = parse_args(argv)
     import torch
@@ -158,6 +185,7 @@ def main(argv=None) -> int:
         validate(args)
         in_dir = resolve_uri(args.input_uri) if args.input_uri else None
         out_dir = resolve_uri(args.output_uri)
+        kin_path = resolve_uri(args.kin_matrix_uri) if args.kin_matrix_uri else None
         synthetic = None
         if args.synthetic:
             parts = [int(x) for x in args.synthetic.split(",")]
@@ -279,6 +307,8 @@ def main(argv=None) -> int:
             dt = time.perf_counter() - t1
             out = out_dir / f"part-{args.shard_index:05d}.snappy.parquet"
             write_results(out, recs, sample_ids)
+            if kin_path is not None:
+                write_kin_matrix(kin_path, ctx, sm, wps, bits, local_rank)
             pairs = sm.NumPairs()
             print(json.dumps({"pairs": pairs, "results": int(len(recs)), "gpus": world,
                               "compute_seconds": dt,

@@ -405,6 +405,48 @@ cuking_status cuking_compute_counts(cuking_ctx *ctx, const cuking_submatrix *sm,
                                     const uint64_t *d_bit_sets,
                                     cuking_counts *d_counts, void *stream);
 
+/* Dense kinship matrix: the float32 kinship of EVERY pair of the block, no threshold and
+ * no records (what hl.king returns, for PC-AiR style partitioning, for looking at the
+ * kinship distribution before choosing a threshold).  Pair (i, j) goes to
+ * d_kin[(i - i_begin) * ld + (j - j_begin)]; `ld` is the row pitch in ELEMENTS, at least
+ * NumCols (all index arithmetic is 64-bit).  The value is the numerics contract's kin above
+ * for the pair's exact integer sums -- bit for bit what a record of cuking_compute_king
+ * carries, including -inf and NaN when one of the samples has no het site.
+ *   CUKING_KIN_UPPER      an off-diagonal block: every entry is written.  A diagonal block:
+ *                         the entries with i < j; those with i >= j are left untouched
+ *                         (like cuking_compute_counts).
+ *   CUKING_KIN_SYMMETRIC  diagonal blocks only: [j][i] = [i][j] as well (a small kernel
+ *                         behind the pair kernel, on the same stream), and the diagonal
+ *                         holds what the expression gives for (i, i): 0.5 for a sample with
+ *                         a het site, NaN otherwise.
+ * INVALID_ARGUMENT for a null pointer, ld < NumCols, unknown flags, SYMMETRIC on an
+ * off-diagonal block or with a tile range; an empty block returns OK.  The matrix depends
+ * on no option and on neither cuking_kernel; entries land at the STORED samples' positions
+ * whatever "filter_sort" says (a dense call converts an unsorted layout; the next call of
+ * the other kind converts again).  The cost does not depend on the data: contexts of
+ * variant 6 and 7 run the four-product matrix-core kernel with an epilogue that stores the
+ * float (variant 7 on the quadrants of its tiles); the other variants, the stream kernel
+ * and bitsets from 2^22 sites on store it from their full forms.  Asynchronous on `stream`;
+ * workspace, stream ordering and "reuse_prepared" as for the other compute entry points.
+ * The tile form follows cuking_compute_king_tiles: a range writes exactly the entries of
+ * its tiles, disjoint ranges covering [0, num_tiles) equal the whole call.
+ * Out of scope: the C++ `cuking` binary, assembling one matrix from several GPUs,
+ * IBS0/1/2 matrices (the lean form does not hold the hom/hom count) and half-precision
+ * output.  The matrix is 4 B x NumRows x NumCols: 40 GB for a 100k-sample diagonal block;
+ * larger cohorts go block by block (cuking_submatrix_init with a split factor). */
+#define CUKING_KIN_UPPER     0u  /* entries with i >= j are left untouched */
+#define CUKING_KIN_SYMMETRIC 1u  /* diagonal block only: mirrored, diagonal filled */
+cuking_status cuking_compute_kin_matrix(cuking_ctx *ctx, const cuking_submatrix *sm,
+                                        uint32_t words_per_sample,
+                                        const uint64_t *d_bit_sets, float *d_kin,
+                                        uint64_t ld, uint32_t flags, void *stream);
+cuking_status cuking_compute_kin_matrix_tiles(cuking_ctx *ctx, const cuking_submatrix *sm,
+                                              uint32_t words_per_sample,
+                                              const uint64_t *d_bit_sets,
+                                              uint64_t tile_begin, uint64_t tile_end,
+                                              float *d_kin, uint64_t ld, uint32_t flags,
+                                              void *stream);
+
 /* cuking.cu:761-765 on host memory: sort by (sample_i, sample_j, kin). */
 void cuking_sort_results(cuking_result *results, size_t num_results);
 
