@@ -1,6 +1,6 @@
 // Device-side pieces shared by the pair kernels (king_kernels.hip,
-// king_mfma.hip): tile decoding, the kinship arithmetic, the record append and
-// the per-emitted-pair recount.
+// king_mfma.hip, king_filter.hip): tile decoding, the kinship arithmetic, the record
+// append, the per-emitted-pair recount, and the matrix-core kernels' lane geometry.
 #ifndef CUKING_AMD_KING_DEVICE_H_
 #define CUKING_AMD_KING_DEVICE_H_
 
@@ -29,6 +29,35 @@ __device__ __forceinline__ void relaxed_store(T *p, V v) {
 template <typename T, typename V>
 __device__ __forceinline__ T relaxed_add(T *p, V v) {  // returns the value before
   return __hip_atomic_fetch_add(p, (T)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// s_waitcnt vmcnt(N) immediate for N requests that may stay in flight.
+constexpr int vmcnt_imm(int n) { return 0x0F70 | (n & 15) | ((n >> 4) << 14); }
+
+// ---- The matrix-core kernels' workgroup (king_mfma.hip, king_filter.hip): 2 x 2 wavefronts,
+// 32 x 32 MFMA blocks.
+// Where a thread sits in the workgroup's 2 x 2 wavefronts and in the MFMA's operands.
+struct Lanes {
+  uint32_t lane, wave;
+  uint32_t wy, wx;  // the wavefront's quadrant
+  uint32_t g, lr;   // k-half of the MFMA operand, row / column inside a block
+};
+__device__ __forceinline__ Lanes lanes_of_thread() {
+  const uint32_t lane = threadIdx.x & 63;
+  const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  return Lanes{lane, wave, wave >> 1, wave & 1, lane >> 5, lane & 31};
+}
+
+// C layout of the 32 x 32 MFMA: register r of a lane holds column lane & 31 of this row
+// (g = lane >> 5).
+__device__ __forceinline__ uint32_t c_row(int r, uint32_t g) { return (r & 3) + 8 * (r >> 2) + 4 * g; }
+
+// Patch order of a launch's tiles (king_common.h, xcd_chunk == 1): workgroups are dealt
+// round-robin to the 8 XCDs, and XCD x takes the patches x, x + 8, ... of 32 consecutive
+// tiles -- the tile of workgroup `wg` (beyond the launch's tiles: padding).
+__device__ __forceinline__ uint32_t xcd_patch_tile(uint32_t wg) {
+  const uint32_t x = wg & 7, j = wg >> 3;
+  return (((j >> 5) * 8 + x) << 5) + (j & 31);
 }
 
 // cuking.cu:289-294: two float32 roundings (divide, add).  Numerator and

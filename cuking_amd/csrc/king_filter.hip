@@ -104,7 +104,6 @@ constexpr int kStageReqs = 4 * kUnits;                // requests per wavefront 
 constexpr int kSyncVm = (kStages - 3) * kStageReqs + (kStageReqs - 2);
 static_assert(kSyncVm < 64, "vmcnt is a 6-bit counter");
 static_assert(kStages * kStageU4 * 16 == (int)kFilterLdsBytes, "LDS size");
-constexpr int vmcnt_imm(int n) { return 0x0F70 | (n & 15) | ((n >> 4) << 14); }
 constexpr uint32_t kNoPair = 0xFFFFFFFFu;
 
 // Which stored sample of the reference bitset plane sample `ps` is (the same
@@ -256,22 +255,6 @@ struct Tile {
   uint32_t part, piece;  // split: the part of the k range, the piece's index within the launch
 };
 
-// Where a thread sits in the workgroup's 2 x 2 wavefronts and in the MFMA's operands.
-struct Lanes {
-  uint32_t lane, wave;
-  uint32_t wy, wx;  // the wavefront's quadrant
-  uint32_t g, lr;   // k-half of the MFMA operand, row / column inside a block
-};
-__device__ __forceinline__ Lanes lanes_of_thread() {
-  const uint32_t lane = threadIdx.x & 63;
-  const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  return Lanes{lane, wave, wave >> 1, wave & 1, lane >> 5, lane & 31};
-}
-
-// C layout of the 32 x 32 MFMA: register r of a lane holds column lane & 31 of this row
-// (g = lane >> 5).
-__device__ __forceinline__ uint32_t c_row(int r, uint32_t g) { return (r & 3) + 8 * (r >> 2) + 4 * g; }
-
 // The level of the bound for the cohort's unrelated pairs: its mean m (1 + m / (2 h (1 - m)))
 // at the cohort's missing rate m and het rate h (from its sums: samples, missing calls, het
 // calls) and its standard deviation 1 / sqrt(sites) (tools/bound_tiers.py,
@@ -314,8 +297,7 @@ __device__ __forceinline__ bool take_tile(const TiledArgs &a, const uint32_t wg,
     bid = a.launch_tiles + next;
   } else if (a.xcd_chunk == 1) {
     // patches of 32 consecutive tiles dealt round-robin to the XCDs (king_common.h)
-    const uint32_t x = bid & 7, j = bid >> 3;
-    bid = (((j >> 5) * 8 + x) << 5) + (j & 31);
+    bid = xcd_patch_tile(bid);
     if (bid >= a.launch_tiles) return false;  // padding (uniform)
   }
   t->bid = __builtin_amdgcn_readfirstlane(bid);

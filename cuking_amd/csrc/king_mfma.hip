@@ -32,6 +32,21 @@
 // k-step, kMfmaStages stages deep (king_common.h).  DESIGN.md 4.1 has the
 // measurements behind the choices; archive/profiles/r01_mfma_microbench.txt the
 // raw numbers.
+//
+// The kernel, king_mfma_kernel<FULL, SPLIT, N4, KIN>, is a short driver over phases, each
+// a function of its own that is inlined into it (DESIGN.md 4.1 has the table):
+//     take_work          which tile / piece / list entries the workgroup takes   (all)
+//     next_segment       the next run of k-steps inside one tile                 (all)
+//     hom_hom_pass       the fifth sum, from the het plane alone                 (FULL)
+//     five_product_loop  the k loop on the quad layout                           (!N4)
+//     four_product_loop  the k loop on the nibble layout                         (N4)
+//     reduce_parts       park and sum the parts of a cut-up tile                 (SPLIT)
+//     emit_full_records  two-sweep reservation and store         (FULL, no dense_counts)
+//     store_counts       the six counts of every pair            (FULL, dense_counts)
+//     store_kin          float32 kinship of every pair                           (KIN)
+//     lean_decide        threshold on the float sums, exact epilogue out of line (the rest)
+// A k loop's statements are macros over its function's locals, defined and undefined
+// inside that function.
 #include <hip/hip_runtime.h>
 
 #include "king_common.h"
@@ -58,8 +73,6 @@ constexpr int kPiecesPerWave = 4;            // 16 x 1 KiB per stage, 4 wavefron
 // 40k x 100k 95.2 -> 94.7 ms, configs[1] (bitset in the Infinity Cache) equal
 // (archive/experiments/exp25.sh).
 constexpr int kStagesPaired = 10;
-// s_waitcnt vmcnt(N) immediate for N requests that may stay in flight.
-constexpr int vmcnt_imm(int n) { return 0x0F70 | (n & 15) | ((n >> 4) << 14); }
 
 // v_bitop3_b32 truth tables over (het, hom_var, mask), index = 4 het + 2 hom + mask.
 constexpr int kA = 0x08;  // hom-alt:  ~het &  hom & mask
@@ -165,6 +178,41 @@ __device__ __attribute__((noinline)) uint32_t reserve_slots(uint32_t *result_ind
     if ((v) > 0) __builtin_amdgcn_sched_group_barrier(0x002, (v), 0);          \
   }
 
+// One LDS-DMA request: lane l's 16 bytes at SRC land at DST + 16 l (`lane16` of the
+// function around it).  OFFSET ("" or " offset:1024") is the instruction's immediate, which
+// moves source and destination alike.  Inline asm keeps it out of the compiler's wait-count
+// bookkeeping (king_kernels.hip).
+#define CUKING_LDS_DMA(DST, SRC, OFFSET)                                       \
+  asm volatile("s_mov_b32 m0, %0\n\t"                                          \
+               "s_nop 0\n\t"                                                   \
+               "global_load_lds_dwordx4 %1, %2" OFFSET                         \
+               :                                                               \
+               : "s"(DST), "v"(lane16), "s"(SRC)                               \
+               : "memory", "m0")
+
+// Registers 4 r4 .. 4 r4 + 3 of an accumulator block as one 16-byte value, and back.
+__device__ __forceinline__ float4 quarter(const v16f &v, int r4) {
+  return make_float4(v[4 * r4], v[4 * r4 + 1], v[4 * r4 + 2], v[4 * r4 + 3]);
+}
+__device__ __forceinline__ void add_quarter(v16f &v, int r4, const float4 x) {
+  v[4 * r4] += x.x;
+  v[4 * r4 + 1] += x.y;
+  v[4 * r4 + 2] += x.z;
+  v[4 * r4 + 3] += x.w;
+}
+__device__ __forceinline__ void unpack(const float4 x, float *f) {
+  f[0] = x.x;
+  f[1] = x.y;
+  f[2] = x.z;
+  f[3] = x.w;
+}
+// A lane's 16-byte slots, lane-linear: of a parked fifth sum [block pair][4 registers][lane],
+// and of a partial tile's slab [block pair][sum][4 registers][lane] (float4 units).
+constexpr int park_slot(int bi, int bj, int r4) { return ((bi * 2 + bj) * 4 + r4) * 64; }
+constexpr int slab_slot(int nsum, int bi, int bj, int q, int r4) {
+  return (((bi * 2 + bj) * nsum + q) * 4 + r4) * 64;
+}
+
 // Tickets: one per workgroup and pass (the full form makes two).
 __host__ __device__ inline size_t split_counter_bytes(uint32_t wgs) {
   return ((size_t)wgs * 2 * sizeof(uint32_t) + 255) / 256 * 256 + 256;
@@ -186,44 +234,74 @@ __device__ __forceinline__ uint32_t split_owner(uint64_t u, uint64_t units,
   return split_bound(w + 1, units, wgs) <= u ? w + 1 : w;
 }
 
-// SPLIT = false: workgroup = one tile, all k-steps.
-// SPLIT = true ("stream-k" remainder): the launch's tiles x k-steps are one
-// line of work units cut into equal pieces, one per workgroup, so a remainder
-// of tiles that would leave most CUs idle for a whole tile time still fills
-// the chip.  A piece covers the end of one tile and/or the start of the next;
-// each partial result (exact integers) is parked in a scratch slab, and the
-// workgroup that delivers a tile's last part adds the others to its own and
-// runs the epilogue.
-// N4 = the four-product form on the nibble layout (below, "Four products").
-// KIN = the dense-kinship form of the lean kernels (TiledArgs::dense_kin): the same k loop,
-// and an epilogue that stores the float32 kinship of EVERY pair instead of appending
-// records -- instantiations of their own, so that the epilogues of the others carry neither
-// its branch nor its registers (a run-time branch in the shared full epilogue was enough
-// for the five-product full form to reload a spilled value inside its k loop).  The
-// four-product one is the hot path; the five-product one serves contexts of variant 5 and
-// bitsets from 2^22 sites on.
-template <bool FULL, bool SPLIT, bool N4 = false, bool KIN = false>
-__global__ __launch_bounds__(256, 1) void king_mfma_kernel(const TiledArgs a) {
-  static_assert(!KIN || !FULL, "the dense-kinship form is a lean one");
-  // Five-product form: the lean form has 10 LDS stages and ONE stage barrier per
-  // two k-steps (below); the full form parks its fifth sum in the LDS behind the
-  // stages and keeps 6 stages with a barrier per k-step.  Four-product form:
-  // 5 stages of 32 KiB, every sum in registers.
-  constexpr bool PAIRED = !N4 && !FULL;
-  constexpr int NSTAGE = N4 ? kMfmaN4Stages : PAIRED ? kStagesPaired : kMfmaStages;
-  constexpr int NSUM = FULL ? 5 : 4; // sums per pair
-  // ... of which the main loop keeps NQ = 4 in its accumulators (five products:
-  // opp, bh, hi, hj; four products: hi / 2, hj / 2, dd, 4 q).  The full form's
-  // fifth sum, hom_hom, comes from a pass of its own in front of the main loop and
-  // waits for the epilogue PARKED in LDS (five products) or in 64 registers that
-  // the main loop does not touch (four products: `hh5`).
-  constexpr int NQ = 4;
-  constexpr bool PARKED = FULL && !N4;
-  constexpr bool HH5 = FULL && N4;
-  constexpr int BI = 2;              // 32-row blocks of the wavefront
-  extern __shared__ uint4 lds[];  // [NSTAGE][side][k-group][plane | slice][128]
+// ---- The forms.  Five-product form: the lean form has 10 LDS stages and ONE stage barrier
+// per two k-steps (five_product_loop()); the full form parks its fifth sum in the LDS behind
+// the stages and keeps 6 stages with a barrier per k-step.  Four-product form: 5 stages of
+// 32 KiB, every sum in registers.
+constexpr int stages_of(bool full, bool n4) {
+  return n4 ? kMfmaN4Stages : !full ? kStagesPaired : kMfmaStages;
+}
+constexpr int sums_of(bool full) { return full ? 5 : 4; }  // sums per pair
+// ... of which the main loop keeps kNQ = 4 in its accumulators (five products:
+// opp, bh, hi, hj; four products: hi / 2, hj / 2, dd, 4 q).  The full form's
+// fifth sum, hom_hom, comes from a pass of its own in front of the main loop and
+// waits for the epilogue PARKED in LDS (five products) or in 64 registers that
+// the main loop does not touch (four products: `hh5`).
+constexpr int kNQ = 4;
 
-  // Which tile (SPLIT: which piece) this workgroup takes.
+// ---- The phases of a workgroup, in the order king_mfma_kernel() (behind them) calls them:
+// all inlined into the one kernel; each sees of the others what its parameters and its
+// result say.
+// What a workgroup has taken.  Wave-uniform.
+struct Work {
+  uint32_t bid;                // the tile within the launch (list / gate mode: the entry)
+  uint32_t piece;              // SPLIT: the piece of the remainder
+  bool listed;                 // list / gate mode: entries bid, bid + grid, ... < list_count
+  uint32_t list_count;
+  uint64_t unit_lo, unit_hi;   // the work units still to do; unit = (tile, k-step)
+};
+// The next run of k-steps inside one tile.  Wave-uniform.
+struct Segment {
+  uint32_t tile;               // within the launch
+  uint32_t k_first, num_steps;
+  uint32_t tr, tc;             // its row and column in the tile space
+};
+// Nibble masks, pinned to SGPRs.
+struct NibbleMasks {
+  uint32_t m1, m2, m4;
+};
+__device__ __forceinline__ NibbleMasks nibble_masks() {
+  NibbleMasks m;
+  asm volatile("s_mov_b32 %0, 0x11111111" : "=s"(m.m1));
+  asm volatile("s_mov_b32 %0, 0x22222222" : "=s"(m.m2));
+  asm volatile("s_mov_b32 %0, 0x44444444" : "=s"(m.m4));
+  return m;
+}
+__device__ __forceinline__ uint32_t tile_steps_of(const TiledArgs &a) { return a.geo.k_words / 8; }
+
+// Five-product full form: this lane's slots (park_slot()) of the parked fifth sum, behind
+// the stages.
+__device__ __forceinline__ float4 *park_slots(uint4 *const lds, const Lanes &l) {
+  return reinterpret_cast<float4 *>(lds + stages_of(true, false) * kStageU4) +
+         (size_t)l.wave * (4 * 4 * 64) + l.lane;
+}
+
+__device__ __forceinline__ void zero_acc(v16f (&acc)[2][2][kNQ]) {
+#pragma unroll
+  for (int bi = 0; bi < 2; ++bi)
+#pragma unroll
+    for (int bj = 0; bj < 2; ++bj)
+#pragma unroll
+      for (int q = 0; q < kNQ; ++q)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[bi][bj][q][r] = 0.f;
+}
+
+// Which tile (SPLIT: which piece) this workgroup takes.  False (uniform, before any barrier
+// that others wait at) when there is none: the dynamic tail is through, the workgroup is
+// padding, or the list is shorter than the grid.
+template <bool SPLIT>
+__device__ __forceinline__ bool take_work(const TiledArgs &a, uint4 *const lds, Work *w) {
   uint32_t bid = blockIdx.x;
   uint32_t piece = 0;
   if (a.dyn_tiles != 0 && blockIdx.x >= a.launch_tiles) {
@@ -242,106 +320,244 @@ __global__ __launch_bounds__(256, 1) void king_mfma_kernel(const TiledArgs a) {
     __syncthreads();
     const uint32_t t = __builtin_amdgcn_readfirstlane(*slot);
     __syncthreads();  // the word is stage memory from here on
-    if (t >= a.dyn_tiles) return;  // uniform
+    if (t >= a.dyn_tiles) return false;  // uniform
     if (SPLIT) piece = t; else bid = a.launch_tiles + t;
   } else
   // (SPLIT launches: the whole-tile workgroups in front take the patch order
   // when their count is a multiple of 8 x 32; the pieces behind them do not)
   if (a.xcd_chunk != 0 && (!SPLIT || blockIdx.x < a.split_whole)) {
-    const uint32_t x = blockIdx.x & 7, j = blockIdx.x >> 3;
     // xcd_chunk == 1: patches of 32 consecutive tiles dealt round-robin to the
-    // XCDs (XCD x takes patches x, x + 8, ...); otherwise one contiguous chunk
-    // of xcd_chunk tiles per XCD.
-    bid = a.xcd_chunk == 1 ? (((j >> 5) * 8 + x) << 5) + (j & 31)
-                           : x * a.xcd_chunk + j;
-    if (bid >= a.launch_tiles) return;  // padding (uniform)
+    // XCDs (xcd_patch_tile()); otherwise one contiguous chunk of xcd_chunk tiles
+    // per XCD.
+    bid = a.xcd_chunk == 1 ? xcd_patch_tile(blockIdx.x)
+                           : (blockIdx.x & 7) * a.xcd_chunk + (blockIdx.x >> 3);
+    if (bid >= a.launch_tiles) return false;  // padding (uniform)
   }
   // Tile-list mode (king_common.h): entries bid, bid + grid, ... of the list.  The
   // persistent mode (gate != nullptr) walks the launch's own enumeration the same way:
   // units bid, bid + grid, ... of gate_count, or nothing at all when the gate is shut.
-  const bool listed = !SPLIT && (a.tile_list != nullptr || a.gate != nullptr);
-  uint32_t list_count = 0;
-  if (listed) {
+  w->listed = !SPLIT && (a.tile_list != nullptr || a.gate != nullptr);
+  w->list_count = 0;
+  if (w->listed) {
     if (a.gate != nullptr) {
-      list_count = *a.gate != 0 ? a.gate_count : 0u;  // (uniform: a scalar load)
+      w->list_count = *a.gate != 0 ? a.gate_count : 0u;  // (uniform: a scalar load)
     } else {
-      list_count = *a.tile_list_count;
-      if (list_count > a.tile_list_cap) list_count = a.tile_list_cap;
+      w->list_count = *a.tile_list_count;
+      if (w->list_count > a.tile_list_cap) w->list_count = a.tile_list_cap;
     }
     // Workgroups are dealt round-robin to the 8 XCDs: give the ones that share an
     // XCD (and its L2) CONSECUTIVE entries of every round -- the list is in tile
     // order more or less, neighbours share row / column strips.
     if ((gridDim.x & 7) == 0) bid = (bid & 7) * (gridDim.x >> 3) + (bid >> 3);
-    if (bid >= list_count) return;  // uniform
+    if (bid >= w->list_count) return false;  // uniform
   }
-  bid = __builtin_amdgcn_readfirstlane(bid);
-  piece = __builtin_amdgcn_readfirstlane(piece);
-
-  const uint32_t lane = threadIdx.x & 63;
-  const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const uint32_t wr = (wave >> 1) * 64;  // wavefront's rows inside the tile
-  const uint32_t wc = (wave & 1) * 64;   // ... and columns
-  const uint32_t g = lane >> 5;          // k-group of the MFMA operand
-  const uint32_t lr = lane & 31;         // row / column inside the block
-  uint32_t lane16 = lane * 16;           // byte offset of the lane in a DMA row
-  // This lane's operand rows inside a stage (uint4 units): rows / columns.
-  uint32_t row_off = (0 * 2 + g) * 2 * kTile + wr + lr;
-  uint32_t col_off = (1 * 2 + g) * 2 * kTile + wc + lr;
-  const uint32_t s_stride = a.geo.s_stride;
-  const uint32_t tile_steps = a.geo.k_words / 8;
-
-  uint32_t m1, m2, m4;  // nibble masks, pinned to SGPRs
-  asm volatile("s_mov_b32 %0, 0x11111111" : "=s"(m1));
-  asm volatile("s_mov_b32 %0, 0x22222222" : "=s"(m2));
-  asm volatile("s_mov_b32 %0, 0x44444444" : "=s"(m4));
+  w->bid = __builtin_amdgcn_readfirstlane(bid);
+  w->piece = __builtin_amdgcn_readfirstlane(piece);
 
   // Work units [unit_lo, unit_hi) of this workgroup; unit = (tile, k-step).
   // SPLIT launches: the first split_whole workgroups take one whole tile each,
   // the remaining split_wgs ones cut the units of the last split_tiles tiles
   // into equal pieces (piece index `piece`).
+  const uint32_t tile_steps = tile_steps_of(a);
   const uint64_t units = (uint64_t)a.split_tiles * tile_steps;      // of the cut-up tiles
   const uint64_t whole_units = SPLIT ? (uint64_t)a.split_whole * tile_steps : 0;
   const bool whole_wg = !SPLIT || blockIdx.x < a.split_whole;
+  w->unit_lo = whole_wg ? (uint64_t)w->bid * tile_steps
+                        : whole_units + split_bound(w->piece, units, a.split_wgs);
+  w->unit_hi = whole_wg ? w->unit_lo + tile_steps
+                        : whole_units + split_bound(w->piece + 1, units, a.split_wgs);
+  return true;
+}
 
-  uint64_t unit_lo = whole_wg ? (uint64_t)bid * tile_steps
-                              : whole_units + split_bound(piece, units, a.split_wgs);
-  uint64_t unit_hi = whole_wg ? unit_lo + tile_steps
-                              : whole_units + split_bound(piece + 1, units, a.split_wgs);
+// The walk over the workgroup's pieces: the next segment of its units, or false when it is
+// through.  (List / gate mode: the next entry, behind a barrier.)
+template <bool SPLIT>
+__device__ __forceinline__ bool next_segment(const TiledArgs &a, Work *w, Segment *s) {
+  const uint32_t tile_steps = tile_steps_of(a);
   while (true) {
-  if (listed && unit_lo >= unit_hi) {
-    bid += gridDim.x;
-    if (bid >= list_count) break;
-    __syncthreads();  // every wavefront is through with the stages of the last tile
-    unit_lo = (uint64_t)bid * tile_steps;
-    unit_hi = unit_lo + tile_steps;
+    if (w->listed && w->unit_lo >= w->unit_hi) {
+      w->bid += gridDim.x;
+      if (w->bid >= w->list_count) return false;
+      __syncthreads();  // every wavefront is through with the stages of the last tile
+      w->unit_lo = (uint64_t)w->bid * tile_steps;
+      w->unit_hi = w->unit_lo + tile_steps;
+    }
+    if (w->unit_lo >= w->unit_hi) return false;
+    // Everything about the piece is wave-uniform; the 64-bit divisions behind it
+    // are computed in vector registers, so pin the results to SGPRs (the SPLIT
+    // instantiation otherwise runs out of VGPRs in the main loop and spills).
+    const uint64_t unit_lo = w->unit_lo, unit_hi = w->unit_hi;
+    s->tile =
+        __builtin_amdgcn_readfirstlane((uint32_t)(unit_lo / tile_steps));  // within the launch
+    s->k_first = __builtin_amdgcn_readfirstlane(
+        (uint32_t)(unit_lo - (uint64_t)s->tile * tile_steps));
+    s->num_steps = __builtin_amdgcn_readfirstlane(
+        (unit_hi - unit_lo < (uint64_t)(tile_steps - s->k_first)) ? (uint32_t)(unit_hi - unit_lo)
+                                                                 : tile_steps - s->k_first);
+    w->unit_lo += s->num_steps;
+    if (SPLIT) {
+      // (the builtin returns int: the casts keep the low word from being sign-extended)
+      w->unit_lo =
+          ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(w->unit_lo >> 32)) << 32) |
+          (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)w->unit_lo);
+      w->unit_hi =
+          ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(w->unit_hi >> 32)) << 32) |
+          (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)w->unit_hi);
+    }
+    uint32_t tr, tc;
+    if (!decode_tile(a, a.tile_begin + s->tile, &tr, &tc)) continue;  // uniform
+    s->tr = __builtin_amdgcn_readfirstlane(tr);
+    s->tc = __builtin_amdgcn_readfirstlane(tc);
+    return true;
   }
-  if (unit_lo >= unit_hi) break;
-  // Everything about the piece is wave-uniform; the 64-bit divisions behind it
-  // are computed in vector registers, so pin the results to SGPRs (the SPLIT
-  // instantiation otherwise runs out of VGPRs in the main loop and spills).
-  const uint32_t seg_tile =
-      __builtin_amdgcn_readfirstlane((uint32_t)(unit_lo / tile_steps));  // within the launch
-  const uint32_t k_first = __builtin_amdgcn_readfirstlane(
-      (uint32_t)(unit_lo - (uint64_t)seg_tile * tile_steps));
-  const uint32_t num_steps = __builtin_amdgcn_readfirstlane(
-      (unit_hi - unit_lo < (uint64_t)(tile_steps - k_first)) ? (uint32_t)(unit_hi - unit_lo)
-                                                             : tile_steps - k_first);
-  unit_lo += num_steps;
-  if (SPLIT) {
-    // (the builtin returns int: the casts keep the low word from being sign-extended)
-    unit_lo = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(unit_lo >> 32)) << 32) |
-              (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)unit_lo);
-    unit_hi = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(unit_hi >> 32)) << 32) |
-              (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)unit_hi);
+}
+
+// Full form: the fifth sum, hom_hom = (A|R)_i . (A|R)_j, in a pass of its own
+// IN FRONT of the main loop.  Five sums for 2 x 2 blocks are 320 accumulator
+// registers, more than the main loop can hold beside its fragments; but
+// "homozygous and defined" is just ~het (missing and padding have the het bit
+// set, cuking.cu:688-697), so this pass reads ONE plane, builds one fragment
+// kind per side and issues 16 MFMAs per k-step against the main loop's 80.
+// With so few MFMAs per byte the LDS-DMA requests and stage barriers of the
+// main loop would dominate (measured: 1.9 ms of 8.8 at 10k x 100k), so every
+// lane fetches its own operand words straight from the plane layout into
+// registers, four k-steps ahead (512 B contiguous per half wavefront; each
+// word is read by two wavefronts, from L2): no LDS, no barrier, the
+// wavefronts drift freely.  The 64 result registers per lane are parked in
+// the 64 KiB of LDS behind the stages until the epilogue (the workgroup owns
+// the CU's whole 160 KiB anyway), so the main loop runs exactly as in the
+// lean form.  (Round 1's full form made two passes of six products over
+// 32-row blocks in the compiler's order: 10.3 ms at 10k x 100k against 7.0 ms
+// lean.)
+template <bool N4>
+__device__ __forceinline__ void hom_hom_pass(const TiledArgs &a, const Segment &s, const Lanes &l,
+                                             const NibbleMasks &m, uint4 *const lds,
+                                             v16f (&hh)[2][2]) {
+  const uint32_t g = l.g, lr = l.lr, wr = l.wy * 64, wc = l.wx * 64;
+  const uint32_t s_stride = a.geo.s_stride, k_first = s.k_first, num_steps = s.num_steps;
+  const uint32_t tr = s.tr, tc = s.tc;
+  const uint32_t m1 = m.m1, m2 = m.m2, m4 = m.m4;
+  constexpr int D = 4;  // k-steps in flight
+#pragma unroll
+  for (int bi = 0; bi < 2; ++bi)
+#pragma unroll
+    for (int bj = 0; bj < 2; ++bj)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) hh[bi][bj][r] = 0.f;
+  // The het plane, one uint4 per 128 sites and sample: plane 0 of the quad
+  // layout (planes interleaved: quad stride 2 rows), or the het-only copy the
+  // nibble layout carries behind its codes for this pass (quad stride 1).
+  constexpr uint32_t HS = N4 ? 1 : 2;
+  const uint4 *const h_base = N4 ? a.planes + (uint64_t)a.geo.k_words * s_stride : a.planes;
+  const uint4 *lane_rows = h_base + (uint64_t)tr * kTile + (uint64_t)g * HS * s_stride + wr + lr;
+  const uint4 *lane_cols = h_base + a.geo.col_base + (uint64_t)tc * kTile +
+                           (uint64_t)g * HS * s_stride + wc + lr;
+  uint4 Ha[D][2], Hb[D][2], Hs_a[2], Hs_b[2];
+  v8i Pa[2], Pb[2], Qa[2], Qb[2];
+  // het words of k-step min(step, last) (the repeats are masked out below)
+#define CUKING_HH_LOAD(U, STEP)                                                \
+  {                                                                            \
+    uint32_t s_ = (STEP);                                                      \
+    if (s_ >= num_steps) s_ = num_steps - 1;                                   \
+    const uint64_t off_ = (uint64_t)(s_ + k_first) * 2 * HS * s_stride;        \
+    _Pragma("unroll") for (int b = 0; b < 2; ++b) {                            \
+      Ha[U][b] = lane_rows[off_ + b * 32];                                     \
+      Hb[U][b] = lane_cols[off_ + b * 32];                                     \
+    }                                                                          \
   }
-  uint32_t tr, tc;
-  if (!decode_tile(a, a.tile_begin + seg_tile, &tr, &tc)) continue;  // uniform
-  tr = __builtin_amdgcn_readfirstlane(tr);
-  tc = __builtin_amdgcn_readfirstlane(tc);
+#define CUKING_HH_FRAGS(X, SA, SB, MASK)                                       \
+  _Pragma("unroll") for (int b = 0; b < 2; ++b) {                              \
+    X##a[b] = frag<kY>(SA[b], SA[b], MASK);                                    \
+    X##b[b] = frag<kY>(SB[b], SB[b], MASK);                                    \
+  }
+#define CUKING_HH_MMA(F, X)                                                    \
+  _Pragma("unroll") for (int bi = 0; bi < 2; ++bi)                             \
+  _Pragma("unroll") for (int bj = 0; bj < 2; ++bj)                             \
+    hh[bi][bj] = mma<F>(X##a[bi], X##b[bj], hh[bi][bj]);
+  // One k-step in four phases; while the four MFMAs of a phase issue, the
+  // VALU builds the next phase's fragments into the other register set (the
+  // last phase builds position 0 of the NEXT k-step, buffer UN).  A k-step
+  // beyond the end gets zero masks: its fragments are empty.
+#define CUKING_HH_KSTEP(U, UN)                                                 \
+  {                                                                            \
+    const bool live_ = step + (U) < num_steps;                                 \
+    const bool next_ = step + (U) + 1 < num_steps;                             \
+    const uint32_t k2_ = live_ ? m2 : 0u, k4_ = live_ ? m4 : 0u;               \
+    const uint32_t k1_ = live_ ? m1 : 0u, n1_ = next_ ? m1 : 0u;               \
+    CUKING_HH_FRAGS(Q, Ha[U], Hb[U], k2_)                                      \
+    CUKING_HH_MMA(0, P)                                                        \
+    CUKING_PACE(4, 4)                                                          \
+    __builtin_amdgcn_sched_barrier(0);                                         \
+    CUKING_HH_FRAGS(P, Ha[U], Hb[U], k4_)                                      \
+    _Pragma("unroll") for (int b = 0; b < 2; ++b) {                            \
+      Hs_a[b] = shr3(Ha[U][b]);                                                \
+      Hs_b[b] = shr3(Hb[U][b]);                                                \
+    }                                                                          \
+    CUKING_HH_MMA(1, Q)                                                        \
+    CUKING_PACE(4, 8)                                                          \
+    __builtin_amdgcn_sched_barrier(0);                                         \
+    CUKING_HH_FRAGS(Q, Hs_a, Hs_b, k1_)                                        \
+    CUKING_HH_MMA(2, P)                                                        \
+    CUKING_PACE(4, 4)                                                          \
+    __builtin_amdgcn_sched_barrier(0);                                         \
+    CUKING_HH_LOAD(U, step + D + (U))                                          \
+    CUKING_HH_FRAGS(P, Ha[UN], Hb[UN], n1_)                                    \
+    CUKING_HH_MMA(3, Q)                                                        \
+    CUKING_PACE(4, 4)                                                          \
+    __builtin_amdgcn_sched_barrier(0);                                         \
+  }
+  CUKING_HH_LOAD(0, 0)
+  CUKING_HH_LOAD(1, 1)
+  CUKING_HH_LOAD(2, 2)
+  CUKING_HH_LOAD(3, 3)
+  CUKING_HH_FRAGS(P, Ha[0], Hb[0], m1)
+  for (uint32_t step = 0; step < num_steps; step += D) {
+    CUKING_HH_KSTEP(0, 1)
+    CUKING_HH_KSTEP(1, 2)
+    CUKING_HH_KSTEP(2, 3)
+    CUKING_HH_KSTEP(3, 0)
+  }
+#undef CUKING_HH_LOAD
+#undef CUKING_HH_FRAGS
+#undef CUKING_HH_MMA
+#undef CUKING_HH_KSTEP
+  if constexpr (!N4) {
+    float4 *const park = park_slots(lds, l);
+#pragma unroll
+    for (int bi = 0; bi < 2; ++bi)
+#pragma unroll
+      for (int bj = 0; bj < 2; ++bj)
+#pragma unroll
+        for (int r4 = 0; r4 < 4; ++r4) park[park_slot(bi, bj, r4)] = quarter(hh[bi][bj], r4);
+  }
+  // (four-product form: the 64 registers stay where they are -- its main loop
+  //  needs 256 accumulators + ~100, they fit beside)
+  // (the prefetches beyond the end are in registers nobody reads; the
+  //  compiler's own wait counts cover them before the main loop's hand-counted
+  //  LDS-DMA starts: force that here)
+  __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
+}
 
-  const uint4 *g_rows = a.planes + (uint64_t)tr * kTile;
-  const uint4 *g_cols = a.planes + a.geo.col_base + (uint64_t)tc * kTile;
-
+// ---- Five products: the main loop over a segment's k-steps on the quad layout (file
+// header), from the first LDS-DMA request to the last k-step's MFMAs.  FULL: six stages,
+// hand-over every k-step; lean: ten, hand-over every two.  `lane16`, the lane's byte offset in
+// a DMA row, is the driver's and carried from segment to segment through the pin below (worked
+// out here per segment, the lean SPLIT form's k loop came out with three more LDS waits).
+template <bool FULL>
+__device__ __forceinline__ void five_product_loop(const TiledArgs &a, const Segment &s,
+                                                  const Lanes &l, const NibbleMasks &m,
+                                                  uint4 *const lds, uint32_t &lane16,
+                                                  v16f (&acc)[2][2][kNQ]) {
+  constexpr bool PAIRED = !FULL;
+  constexpr int NSTAGE = stages_of(FULL, false);
+  const uint32_t wave = l.wave, g = l.g, lr = l.lr, wr = l.wy * 64, wc = l.wx * 64;
+  const uint32_t s_stride = a.geo.s_stride, k_first = s.k_first, num_steps = s.num_steps;
+  const uint32_t m1 = m.m1, m2 = m.m2, m4 = m.m4;
+  // This lane's operand rows inside a stage (uint4 units): rows / columns.
+  uint32_t row_off = (0 * 2 + g) * 2 * kTile + wr + lr;
+  uint32_t col_off = (1 * 2 + g) * 2 * kTile + wc + lr;
+  const uint4 *g_rows = a.planes + (uint64_t)s.tr * kTile;
+  const uint4 *g_cols = a.planes + a.geo.col_base + (uint64_t)s.tc * kTile;
   // LDS-DMA addressing.  Row `row` = 4 wave + r (1 KiB) of a stage is
   // (side, k-group, plane p, half seg) = (row >> 3, row >> 2 & 1, row >> 1 & 1,
   // row & 1): a wavefront's four requests share side and k-group, and r = 2 p +
@@ -372,26 +588,10 @@ __global__ __launch_bounds__(256, 1) void king_mfma_kernel(const TiledArgs a) {
     asm volatile("" : "+s"(pa.src[0]), "+s"(pa.src[1]), "+s"(pa.dst[0]), "+s"(pa.dst[1]));
     return pa;
   };
-  // Request r of the four.  LDS-DMA, lane l's 16 bytes land at dst + 16 * l.
-  // Inline asm keeps it out of the compiler's wait-count bookkeeping
-  // (king_kernels.hip).
+  // Request r of the four.
   auto issue_piece = [&](const PieceAddr &pa, int r) {
-    if (r & 1)
-      asm volatile(
-          "s_mov_b32 m0, %0\n\t"
-          "s_nop 0\n\t"
-          "global_load_lds_dwordx4 %1, %2 offset:1024"
-          :
-          : "s"(pa.dst[r >> 1]), "v"(lane16), "s"(pa.src[r >> 1])
-          : "memory", "m0");
-    else
-      asm volatile(
-          "s_mov_b32 m0, %0\n\t"
-          "s_nop 0\n\t"
-          "global_load_lds_dwordx4 %1, %2"
-          :
-          : "s"(pa.dst[r >> 1]), "v"(lane16), "s"(pa.src[r >> 1])
-          : "memory", "m0");
+    if (r & 1) CUKING_LDS_DMA(pa.dst[r >> 1], pa.src[r >> 1], " offset:1024");
+    else CUKING_LDS_DMA(pa.dst[r >> 1], pa.src[r >> 1], "");
   };
   auto issue_stage = [&](uint32_t step, uint32_t buf) {
     const PieceAddr pa = piece_addr(step, buf);
@@ -410,161 +610,23 @@ __global__ __launch_bounds__(256, 1) void king_mfma_kernel(const TiledArgs a) {
     __syncthreads();
   };
 
-  // Full form: the fifth sum, hom_hom = (A|R)_i . (A|R)_j, in a pass of its own
-  // IN FRONT of the main loop.  Five sums for 2 x 2 blocks are 320 accumulator
-  // registers, more than the main loop can hold beside its fragments; but
-  // "homozygous and defined" is just ~het (missing and padding have the het bit
-  // set, cuking.cu:688-697), so this pass reads ONE plane, builds one fragment
-  // kind per side and issues 16 MFMAs per k-step against the main loop's 80.
-  // With so few MFMAs per byte the LDS-DMA requests and stage barriers of the
-  // main loop would dominate (measured: 1.9 ms of 8.8 at 10k x 100k), so every
-  // lane fetches its own operand words straight from the plane layout into
-  // registers, four k-steps ahead (512 B contiguous per half wavefront; each
-  // word is read by two wavefronts, from L2): no LDS, no barrier, the
-  // wavefronts drift freely.  The 64 result registers per lane are parked in
-  // the 64 KiB of LDS behind the stages until the epilogue (the workgroup owns
-  // the CU's whole 160 KiB anyway), so the main loop runs exactly as in the
-  // lean form.  (Round 1's full form made two passes of six products over
-  // 32-row blocks in the compiler's order: 10.3 ms at 10k x 100k against 7.0 ms
-  // lean.)
-  v16f hh5[BI][2];  // full form: hom_hom of the wavefront's pairs
-  if constexpr (FULL) {
-    constexpr int D = 4;  // k-steps in flight
-    v16f (&hh)[BI][2] = hh5;
-#pragma unroll
-    for (int bi = 0; bi < BI; ++bi)
-#pragma unroll
-      for (int bj = 0; bj < 2; ++bj)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) hh[bi][bj][r] = 0.f;
-    // The het plane, one uint4 per 128 sites and sample: plane 0 of the quad
-    // layout (planes interleaved: quad stride 2 rows), or the het-only copy the
-    // nibble layout carries behind its codes for this pass (quad stride 1).
-    constexpr uint32_t HS = N4 ? 1 : 2;
-    const uint4 *const h_base = N4 ? a.planes + (uint64_t)a.geo.k_words * s_stride : a.planes;
-    const uint4 *lane_rows = h_base + (uint64_t)tr * kTile + (uint64_t)g * HS * s_stride + wr + lr;
-    const uint4 *lane_cols = h_base + a.geo.col_base + (uint64_t)tc * kTile +
-                             (uint64_t)g * HS * s_stride + wc + lr;
-    uint4 Ha[D][BI], Hb[D][2], Hs_a[BI], Hs_b[2];
-    v8i Pa[BI], Pb[2], Qa[BI], Qb[2];
-    // het words of k-step min(step, last) (the repeats are masked out below)
-#define CUKING_HH_LOAD(U, STEP)                                                \
-    {                                                                          \
-      uint32_t s_ = (STEP);                                                    \
-      if (s_ >= num_steps) s_ = num_steps - 1;                                 \
-      const uint64_t off_ = (uint64_t)(s_ + k_first) * 2 * HS * s_stride;      \
-      _Pragma("unroll") for (int b = 0; b < 2; ++b) {                          \
-        Ha[U][b] = lane_rows[off_ + b * 32];                                   \
-        Hb[U][b] = lane_cols[off_ + b * 32];                                   \
-      }                                                                        \
-    }
-#define CUKING_HH_FRAGS(X, SA, SB, MASK)                                       \
-    _Pragma("unroll") for (int b = 0; b < 2; ++b) {                            \
-      X##a[b] = frag<kY>(SA[b], SA[b], MASK);                                  \
-      X##b[b] = frag<kY>(SB[b], SB[b], MASK);                                  \
-    }
-#define CUKING_HH_MMA(F, X)                                                    \
-    _Pragma("unroll") for (int bi = 0; bi < BI; ++bi)                          \
-    _Pragma("unroll") for (int bj = 0; bj < 2; ++bj)                           \
-      hh[bi][bj] = mma<F>(X##a[bi], X##b[bj], hh[bi][bj]);
-    // One k-step in four phases; while the four MFMAs of a phase issue, the
-    // VALU builds the next phase's fragments into the other register set (the
-    // last phase builds position 0 of the NEXT k-step, buffer UN).  A k-step
-    // beyond the end gets zero masks: its fragments are empty.
-#define CUKING_HH_KSTEP(U, UN)                                                 \
-    {                                                                          \
-      const bool live_ = step + (U) < num_steps;                               \
-      const bool next_ = step + (U) + 1 < num_steps;                           \
-      const uint32_t k2_ = live_ ? m2 : 0u, k4_ = live_ ? m4 : 0u;             \
-      const uint32_t k1_ = live_ ? m1 : 0u, n1_ = next_ ? m1 : 0u;             \
-      CUKING_HH_FRAGS(Q, Ha[U], Hb[U], k2_)                                    \
-      CUKING_HH_MMA(0, P)                                                      \
-      CUKING_PACE(4, 4)                                                        \
-      __builtin_amdgcn_sched_barrier(0);                                       \
-      CUKING_HH_FRAGS(P, Ha[U], Hb[U], k4_)                                    \
-      _Pragma("unroll") for (int b = 0; b < 2; ++b) {                          \
-        Hs_a[b] = shr3(Ha[U][b]);                                              \
-        Hs_b[b] = shr3(Hb[U][b]);                                              \
-      }                                                                        \
-      CUKING_HH_MMA(1, Q)                                                      \
-      CUKING_PACE(4, 8)                                                        \
-      __builtin_amdgcn_sched_barrier(0);                                       \
-      CUKING_HH_FRAGS(Q, Hs_a, Hs_b, k1_)                                      \
-      CUKING_HH_MMA(2, P)                                                      \
-      CUKING_PACE(4, 4)                                                        \
-      __builtin_amdgcn_sched_barrier(0);                                       \
-      CUKING_HH_LOAD(U, step + D + (U))                                        \
-      CUKING_HH_FRAGS(P, Ha[UN], Hb[UN], n1_)                                  \
-      CUKING_HH_MMA(3, Q)                                                      \
-      CUKING_PACE(4, 4)                                                        \
-      __builtin_amdgcn_sched_barrier(0);                                       \
-    }
-    CUKING_HH_LOAD(0, 0)
-    CUKING_HH_LOAD(1, 1)
-    CUKING_HH_LOAD(2, 2)
-    CUKING_HH_LOAD(3, 3)
-    CUKING_HH_FRAGS(P, Ha[0], Hb[0], m1)
-    for (uint32_t step = 0; step < num_steps; step += D) {
-      CUKING_HH_KSTEP(0, 1)
-      CUKING_HH_KSTEP(1, 2)
-      CUKING_HH_KSTEP(2, 3)
-      CUKING_HH_KSTEP(3, 0)
-    }
-#undef CUKING_HH_LOAD
-#undef CUKING_HH_FRAGS
-#undef CUKING_HH_MMA
-#undef CUKING_HH_KSTEP
-    if constexpr (PARKED) {
-      float4 *park = reinterpret_cast<float4 *>(lds + NSTAGE * kStageU4) +
-                     (size_t)wave * (4 * 4 * 64) + lane;
-#pragma unroll
-      for (int bi = 0; bi < BI; ++bi)
-#pragma unroll
-        for (int bj = 0; bj < 2; ++bj)
-#pragma unroll
-          for (int r4 = 0; r4 < 4; ++r4)
-            park[((bi * 2 + bj) * 4 + r4) * 64] =
-                make_float4(hh[bi][bj][4 * r4], hh[bi][bj][4 * r4 + 1], hh[bi][bj][4 * r4 + 2],
-                            hh[bi][bj][4 * r4 + 3]);
-    }
-    // (four-product form: the 64 registers stay where they are -- its main loop
-    //  needs 256 accumulators + ~100, they fit beside)
-    // (the prefetches beyond the end are in registers nobody reads; the
-    //  compiler's own wait counts cover them before the main loop's hand-counted
-    //  LDS-DMA starts: force that here)
-    __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
-  }
-
-  v16f acc[BI][2][NQ];
-  constexpr uint32_t half_rows = 0;
-  auto zero_acc = [&]() {
-#pragma unroll
-    for (int bi = 0; bi < BI; ++bi)
-#pragma unroll
-      for (int bj = 0; bj < 2; ++bj)
-#pragma unroll
-        for (int q = 0; q < NQ; ++q)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) acc[bi][bj][q][r] = 0.f;
-  };
-  if constexpr (!N4) zero_acc();  // (four products: behind the hom_hom pass)
-
+  zero_acc(acc);  // (four products: behind the hom_hom pass, in front of the pins on hh5)
   // Raw words of the k-step: [block][plane] for the row and the column side.
-  uint4 A[BI][2], B[2][2];
+  uint4 A[2][2], B[2][2];
 #define CUKING_LOAD_RAW(BUF)                                                   \
   {                                                                            \
     const uint4 *l_rows_ = lds + (BUF) * kStageU4 + row_off;                   \
     const uint4 *l_cols_ = lds + (BUF) * kStageU4 + col_off;                   \
     _Pragma("unroll") for (int p = 0; p < 2; ++p) {                            \
-      _Pragma("unroll") for (int b = 0; b < BI; ++b)                           \
-        A[b][p] = l_rows_[p * kTile + b * 32 + half_rows];                     \
+      _Pragma("unroll") for (int b = 0; b < 2; ++b)                            \
+        A[b][p] = l_rows_[p * kTile + b * 32];                                 \
       _Pragma("unroll") for (int b = 0; b < 2; ++b)                            \
         B[b][p] = l_cols_[p * kTile + b * 32];                                 \
     }                                                                          \
   }
 // Fragment set X = planes A, R, H, D of (SA, SB) at the nibble position MASK.
 #define CUKING_EXPAND(X, SA, SB, MASK)                                         \
-  _Pragma("unroll") for (int b = 0; b < BI; ++b) {                             \
+  _Pragma("unroll") for (int b = 0; b < 2; ++b) {                              \
     X##a[b][0] = frag<kA>(SA[b][0], SA[b][1], MASK);                           \
     X##a[b][1] = frag<kR>(SA[b][0], SA[b][1], MASK);                           \
     X##a[b][2] = frag<kH>(SA[b][0], SA[b][1], MASK);                           \
@@ -579,7 +641,7 @@ __global__ __launch_bounds__(256, 1) void king_mfma_kernel(const TiledArgs a) {
 // One plane product (fragment index PA of the rows x PB of the columns) for
 // the four block pairs.
 #define CUKING_MMA1(F, X, PA, PB, Q)                                           \
-  _Pragma("unroll") for (int bi = 0; bi < BI; ++bi)                            \
+  _Pragma("unroll") for (int bi = 0; bi < 2; ++bi)                             \
   _Pragma("unroll") for (int bj = 0; bj < 2; ++bj)                             \
     acc[bi][bj][Q] = mma<F>(X##a[bi][PA], X##b[bj][PB], acc[bi][bj][Q]);
 // opp (first half), bh, hi, hj: 16 MFMAs; then the second half of opp.
@@ -604,247 +666,250 @@ __global__ __launch_bounds__(256, 1) void king_mfma_kernel(const TiledArgs a) {
   // landed: the same vmcnt(16) as the unpaired form.  (In general, N stages:
   // even k-steps request stage i + N - 1, odd ones i + N - 3, and the wait
   // leaves the N - 4 youngest stages in flight.)
-  if constexpr (!N4) {
   constexpr int kPrologueStages = PAIRED ? NSTAGE - 2 : NSTAGE - 1;
 #pragma unroll
   for (int st = 0; st < kPrologueStages; ++st) issue_stage(st, st);
   stage_sync();
 
-  {
-    // Software pipeline: while the MFMAs of fragment f issue, the VALU builds
-    // fragment f + 1 into the other register set (an MFMA never reads a
-    // register written just before it); behind the MFMAs of f = 3 come the
-    // next k-step's stage hand-over, its LDS reads and its f = 0 fragment.
-    // Pacing (tools/micro/mfma_fill): a scaled fp4 MFMA holds the issue port
-    // 13 cycles (unscaled: 8) of its 32, a VALU instruction 4, so 4 (5) hide
-    // behind one MFMA.  The k-step's four LDS-DMA requests go one each into
-    // gaps without VALU work.
-    v8i Xa[2][4], Xb[2][4], Ya[2][4], Yb[2][4];
-    uint4 As[2][2], Bs[2][2];
-    CUKING_LOAD_RAW(0)
-    CUKING_EXPAND(X, A, B, m1)
-    uint32_t buf = 0;  // buffer of the k-step being multiplied
-    // The loop's per-lane invariants sit in registers from here on: a spill
-    // reload whose first use is inside the loop would put the compiler's
-    // s_waitcnt vmcnt(0) there, draining the DMA pipeline in every iteration.
-    asm volatile("" : "+v"(row_off), "+v"(col_off), "+v"(lane16));
-    // The raw words are dead after f = 1 (f = 2 and f = 3 read the shifted
-    // copies): hand-over and LDS reads of the next k-step in phase f = 2, one
-    // read behind each of its first eight MFMAs: configs[2] 594.5 ms; one per two
-    // MFMAs 600.1, all in front of the phase 608.8 (archive/profiles/r02_mfma_stamps.txt).
+  // Software pipeline: while the MFMAs of fragment f issue, the VALU builds
+  // fragment f + 1 into the other register set (an MFMA never reads a
+  // register written just before it); behind the MFMAs of f = 3 come the
+  // next k-step's stage hand-over, its LDS reads and its f = 0 fragment.
+  // Pacing (tools/micro/mfma_fill): a scaled fp4 MFMA holds the issue port
+  // 13 cycles (unscaled: 8) of its 32, a VALU instruction 4, so 4 (5) hide
+  // behind one MFMA.  The k-step's four LDS-DMA requests go one each into
+  // gaps without VALU work.
+  v8i Xa[2][4], Xb[2][4], Ya[2][4], Yb[2][4];
+  uint4 As[2][2], Bs[2][2];
+  CUKING_LOAD_RAW(0)
+  CUKING_EXPAND(X, A, B, m1)
+  uint32_t buf = 0;  // buffer of the k-step being multiplied
+  // The loop's per-lane invariants sit in registers from here on: a spill
+  // reload whose first use is inside the loop would put the compiler's
+  // s_waitcnt vmcnt(0) there, draining the DMA pipeline in every iteration.
+  asm volatile("" : "+v"(row_off), "+v"(col_off), "+v"(lane16));
+  // The raw words are dead after f = 1 (f = 2 and f = 3 read the shifted
+  // copies): hand-over and LDS reads of the next k-step in phase f = 2, one
+  // read behind each of its first eight MFMAs: configs[2] 594.5 ms; one per two
+  // MFMAs 600.1, all in front of the phase 608.8 (archive/profiles/r02_mfma_stamps.txt).
 #define CUKING_PHASE_F2(SYNC)                                                  \
-      if (SYNC) stage_sync();                                                  \
-      CUKING_LOAD_RAW(nbuf)                                                    \
-      CUKING_EXPAND(Y, As, Bs, m1)                                             \
-      CUKING_MMA16(2, X)                                                       \
-      CUKING_MMA4(2, X)                                                        \
-      _Pragma("unroll") for (int i_ = 0; i_ < 8; ++i_) {                       \
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                     \
-        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);                     \
-        __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);                     \
-      }                                                                        \
-      CUKING_PACE(8, 4) CUKING_PACE(4, 0)                                      \
-      __builtin_amdgcn_sched_barrier(0);
+    if (SYNC) stage_sync();                                                    \
+    CUKING_LOAD_RAW(nbuf)                                                      \
+    CUKING_EXPAND(Y, As, Bs, m1)                                               \
+    CUKING_MMA16(2, X)                                                         \
+    CUKING_MMA4(2, X)                                                          \
+    _Pragma("unroll") for (int i_ = 0; i_ < 8; ++i_) {                         \
+      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                       \
+      __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);                       \
+      __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);                       \
+    }                                                                          \
+    CUKING_PACE(8, 4) CUKING_PACE(4, 0)                                        \
+    __builtin_amdgcn_sched_barrier(0);
 #define CUKING_PHASE_F3(SYNC)                                                  \
-      CUKING_EXPAND(X, A, B, m1)                                               \
-      CUKING_MMA16(3, Y)                                                       \
-      CUKING_MMA4(3, Y)                                                        \
-      CUKING_PACE(4, 0) CUKING_PACE(16, 4)                                     \
-      __builtin_amdgcn_sched_barrier(0);
-    // One k-step.  Its four requests go to the addresses the k-step before it
-    // worked out (`pa`); in phase f = 3, where the MFMA gaps have room for scalar
-    // instructions, it works out those of the NEXT k-step, which requests stage
-    // STEP + 1 + NAHEAD into the buffer NBACK behind its own.  SYNC = hand stages
-    // over (wait + barrier) before the next k-step's LDS reads.
+    CUKING_EXPAND(X, A, B, m1)                                                 \
+    CUKING_MMA16(3, Y)                                                         \
+    CUKING_MMA4(3, Y)                                                          \
+    CUKING_PACE(4, 0) CUKING_PACE(16, 4)                                       \
+    __builtin_amdgcn_sched_barrier(0);
+  // One k-step.  Its four requests go to the addresses the k-step before it
+  // worked out (`pa`); in phase f = 3, where the MFMA gaps have room for scalar
+  // instructions, it works out those of the NEXT k-step, which requests stage
+  // STEP + 1 + NAHEAD into the buffer NBACK behind its own.  SYNC = hand stages
+  // over (wait + barrier) before the next k-step's LDS reads.
 #define CUKING_KSTEP(STEP, SYNC, NAHEAD, NBACK)                                \
-    {                                                                          \
-      const uint32_t nbuf = buf == NSTAGE - 1 ? 0 : buf + 1;                   \
-      const PieceAddr pa_ = pa;                                                \
-      /* f = 0 multiplies, f = 1 is built */                                   \
-      CUKING_EXPAND(Y, A, B, m2)                                               \
-      CUKING_MMA16(0, X)                                                       \
-      CUKING_PACE(16, 4)                                                       \
+  {                                                                            \
+    const uint32_t nbuf = buf == NSTAGE - 1 ? 0 : buf + 1;                     \
+    const PieceAddr pa_ = pa;                                                  \
+    /* f = 0 multiplies, f = 1 is built */                                     \
+    CUKING_EXPAND(Y, A, B, m2)                                                 \
+    CUKING_MMA16(0, X)                                                         \
+    CUKING_PACE(16, 4)                                                         \
+    __builtin_amdgcn_sched_barrier(0);                                         \
+    _Pragma("unroll") for (int r = 0; r < 4; ++r) {                            \
+      issue_piece(pa_, r);                                                     \
+      acc[r >> 1][r & 1][0] =                                                  \
+          mma<0>(Xa[r >> 1][1], Xb[r & 1][0], acc[r >> 1][r & 1][0]);          \
       __builtin_amdgcn_sched_barrier(0);                                       \
-      _Pragma("unroll") for (int r = 0; r < 4; ++r) {                          \
-        issue_piece(pa_, r);                                                   \
-        acc[r >> 1][r & 1][0] =                                                \
-            mma<0>(Xa[r >> 1][1], Xb[r & 1][0], acc[r >> 1][r & 1][0]);        \
-        __builtin_amdgcn_sched_barrier(0);                                     \
-      }                                                                        \
-      /* f = 1 multiplies (unscaled), f = 2 and the shifted words are built */ \
-      CUKING_EXPAND(X, A, B, m4)                                               \
-      _Pragma("unroll") for (int b = 0; b < 2; ++b)                            \
-      _Pragma("unroll") for (int p = 0; p < 2; ++p) {                          \
-        As[b][p] = shr3(A[b][p]);                                              \
-        Bs[b][p] = shr3(B[b][p]);                                              \
-      }                                                                        \
-      CUKING_MMA16(1, Y)                                                       \
-      CUKING_MMA4(1, Y)                                                        \
-      CUKING_PACE(20, 5)                                                       \
-      __builtin_amdgcn_sched_barrier(0);                                       \
-      CUKING_PHASE_F2(SYNC)                                                    \
-      pa = piece_addr((STEP) + 1 + (NAHEAD),                                   \
-                      nbuf >= (NBACK) ? nbuf - (NBACK) : nbuf + NSTAGE - (NBACK)); \
-      CUKING_PHASE_F3(SYNC)                                                    \
-      buf = nbuf;                                                              \
+    }                                                                          \
+    /* f = 1 multiplies (unscaled), f = 2 and the shifted words are built */   \
+    CUKING_EXPAND(X, A, B, m4)                                                 \
+    _Pragma("unroll") for (int b = 0; b < 2; ++b)                              \
+    _Pragma("unroll") for (int p = 0; p < 2; ++p) {                            \
+      As[b][p] = shr3(A[b][p]);                                                \
+      Bs[b][p] = shr3(B[b][p]);                                                \
+    }                                                                          \
+    CUKING_MMA16(1, Y)                                                         \
+    CUKING_MMA4(1, Y)                                                          \
+    CUKING_PACE(20, 5)                                                         \
+    __builtin_amdgcn_sched_barrier(0);                                         \
+    CUKING_PHASE_F2(SYNC)                                                      \
+    pa = piece_addr((STEP) + 1 + (NAHEAD),                                     \
+                    nbuf >= (NBACK) ? nbuf - (NBACK) : nbuf + NSTAGE - (NBACK)); \
+    CUKING_PHASE_F3(SYNC)                                                      \
+    buf = nbuf;                                                                \
+  }
+  // (the first k-step requests stage NSTAGE - 1 into the buffer behind its own)
+  PieceAddr pa = piece_addr(NSTAGE - 1, buf >= 1 ? buf - 1 : buf + NSTAGE - 1);
+  if constexpr (PAIRED) {
+    // even k-steps request stage + NSTAGE - 1 one buffer back, odd ones
+    // stage + NSTAGE - 3 three buffers back
+    uint32_t step = 0;
+    for (; step + 2 < num_steps; step += 2) {
+      CUKING_KSTEP(step, false, NSTAGE - 3, 3)
+      CUKING_KSTEP(step + 1, true, NSTAGE - 1, 1)
     }
-    // (the first k-step requests stage NSTAGE - 1 into the buffer behind its own)
-    PieceAddr pa = piece_addr(NSTAGE - 1, buf >= 1 ? buf - 1 : buf + NSTAGE - 1);
-    if constexpr (PAIRED) {
-      // even k-steps request stage + NSTAGE - 1 one buffer back, odd ones
-      // stage + NSTAGE - 3 three buffers back
-      uint32_t step = 0;
-      for (; step + 2 < num_steps; step += 2) {
-        CUKING_KSTEP(step, false, NSTAGE - 3, 3)
-        CUKING_KSTEP(step + 1, true, NSTAGE - 1, 1)
-      }
-      if (step + 1 < num_steps) CUKING_KSTEP(step, false, NSTAGE - 3, 3)
-    } else {
-      for (uint32_t step = 0; step + 1 < num_steps; ++step)
-        CUKING_KSTEP(step, true, NSTAGE - 1, 1)
-    }
+    if (step + 1 < num_steps) CUKING_KSTEP(step, false, NSTAGE - 3, 3)
+  } else {
+    for (uint32_t step = 0; step + 1 < num_steps; ++step)
+      CUKING_KSTEP(step, true, NSTAGE - 1, 1)
+  }
 #undef CUKING_KSTEP
 #undef CUKING_PHASE_F2
 #undef CUKING_PHASE_F3
-    // last k-step: nothing left to fetch
-    CUKING_EXPAND(Y, A, B, m2)
-    CUKING_MMA16(0, X)
-    CUKING_MMA4(0, X)
-    CUKING_EXPAND(X, A, B, m4)
+  // last k-step: nothing left to fetch
+  CUKING_EXPAND(Y, A, B, m2)
+  CUKING_MMA16(0, X)
+  CUKING_MMA4(0, X)
+  CUKING_EXPAND(X, A, B, m4)
 #pragma unroll
-    for (int b = 0; b < 2; ++b)
+  for (int b = 0; b < 2; ++b)
 #pragma unroll
-      for (int p = 0; p < 2; ++p) {
-        As[b][p] = shr3(A[b][p]);
-        Bs[b][p] = shr3(B[b][p]);
-      }
-    CUKING_MMA16(1, Y)
-    CUKING_MMA4(1, Y)
-    CUKING_EXPAND(Y, As, Bs, m1)
-    CUKING_MMA16(2, X)
-    CUKING_MMA4(2, X)
-    CUKING_MMA16(3, Y)
-    CUKING_MMA4(3, Y)
-  }
-  } else {
-    // ---- Four products ------------------------------------------------------
-    // With D = defined, H = het, Y = hom-ref or hom-alt, T = (hom-ref) - (hom-alt):
-    //     hi = H_i.D_j    hj = D_i.H_j    dd = D_i.D_j    q = T_i.T_j
-    // and  2 bh - 4 opp - hi - hj = hi + hj - 2 dd + 2 q   (kinship's numerator),
-    //      bh - hom_hom = hi + hj - dd,   hom_hom - 2 opp = q,
-    // so four MFMAs per block pair and 64 sites instead of five give the
-    // threshold decision (the minimum: {numerator, hi, hj} is not in the span of
-    // three rank-1 products), and one more sum -- hom_hom, recounted for the few
-    // emitted pairs (lean) or from the pass in front of this loop (full form: the
-    // same het-plane pass as the five-product kernel's, reading a het-only copy
-    // behind the codes; a fifth product Y_i.Y_j inside this loop would need 320
-    // accumulator registers, which the compiler then shuffles between the two
-    // halves of the register file around every MFMA, and a pass of its own over
-    // the staged codes moves all the bytes again for a quarter of the MFMAs:
-    // 3.2 ms of 8.8 at 10k x 100k) -- gives bh and opp.
-    // T needs a sign: the nibble layout (king_common.h) stores one fp4 code per
-    // site, H at bit 0 (0.5), D at bit 1 (1.0), Y at bit 2 (2.0), hom-alt in the
-    // SIGN bit, so that every fragment is ONE v_and_b32 of a stored dword with a
-    // constant (T: 0xC -> +-2.0) -- no bit-position passes, no shifted copies, no
-    // block scales: all MFMAs are the unscaled instruction, and each product
-    // carries a constant power of two (hi, hj: 1/2; q, hom_hom: 4) that the
-    // epilogue takes out exactly.  Per k-step (256 sites, 4 slices of 64) and
-    // wavefront: 64 MFMAs, 192 v_and (3.0 per MFMA; five products: 80 / 288),
-    // 16 ds_read_b128, 8 LDS-DMA requests of 1 KiB (twice the bytes).
-    //
-    // Pipeline (per slice c = 16 or 20 MFMAs): fragments are NOT double
-    // buffered; a fragment kind is rebuilt for slice c + 1 in the MFMA group
-    // behind its last use in slice c (group order hi, hj, dd, q[, hom_hom]), the
-    // raw words of slice c + 1 sit in the second raw buffer, and the LDS reads of
-    // slice c + 2 go into the buffer slice c has finished with.
-    constexpr int kSliceU4 = kTile;                  // one slice of one (side, k-group)
-    constexpr int kStageN4 = 2 * 2 * 4 * kSliceU4;   // uint4 per stage (32 KiB)
-    uint32_t mT;
-    asm volatile("s_mov_b32 %0, 0xcccccccc" : "=s"(mT));
-    const uint32_t mH = m1, mD = m2;
-    // DMA: wavefront (side, k-group) fetches that quarter of a stage: 4 slices x
-    // 2 halves of 64 samples, 1 KiB each.  Slice c of k-step s is group
-    // 8 s + 4 kg + c of the layout.
-    const uint4 *const g_wave4 = (dma_side ? g_cols : g_rows) +
-                                 (uint64_t)(8 * k_first + 4 * dma_kg) * s_stride;
-    const uint32_t l_wave4 = (uint32_t)(uintptr_t)(lds_void_ptr)(
-        lds + ((dma_side * 2 + dma_kg) * 4) * kSliceU4);
-    struct N4Addr { const uint4 *src; uint32_t dst; };
-    auto n4_addr = [&](uint32_t step, uint32_t buf) {
-      N4Addr pa;
-      if (step >= num_steps) step = num_steps - 1;  // (clamped repeats: see piece_addr)
-      pa.src = g_wave4 + (uint64_t)step * 8 * s_stride;
-      pa.dst = l_wave4 + buf * (kStageN4 * 16);
-      asm volatile("" : "+s"(pa.src), "+s"(pa.dst));
-      return pa;
-    };
-    // ... of the stage after the one `pa` names: one k-step further unless that was
-    // the last (then the same rows again: clamped repeats), into buffer `buf` --
-    // a compare, a select and two adds instead of n4_addr's 64-bit multiply chain
-    // (65 cycles of a k-step in the stamps, profiles/r03_stamps_n4.txt).
-    const uint32_t kstep_bytes = 8 * s_stride * 16;  // (< 2^32: 128 B x stored samples)
-    auto n4_next = [&](const N4Addr &cur, uint32_t step, uint32_t buf) {
-      N4Addr pa;
-      const uint32_t adv = step < num_steps ? kstep_bytes : 0u;
-      pa.src = reinterpret_cast<const uint4 *>(reinterpret_cast<const char *>(cur.src) + adv);
-      pa.dst = l_wave4 + buf * (kStageN4 * 16);
-      asm volatile("" : "+s"(pa.src), "+s"(pa.dst));
-      return pa;
-    };
-    auto n4_issue = [&](const N4Addr &pa, int c, int half) {
-      const uint4 *src = pa.src + (uint64_t)c * s_stride;
-      const uint32_t dst = pa.dst + c * (kSliceU4 * 16);
-      if (half)
-        asm volatile(
-            "s_mov_b32 m0, %0\n\t"
-            "s_nop 0\n\t"
-            "global_load_lds_dwordx4 %1, %2 offset:1024"
-            :
-            : "s"(dst), "v"(lane16), "s"(src)
-            : "memory", "m0");
-      else
-        asm volatile(
-            "s_mov_b32 m0, %0\n\t"
-            "s_nop 0\n\t"
-            "global_load_lds_dwordx4 %1, %2"
-            :
-            : "s"(dst), "v"(lane16), "s"(src)
-            : "memory", "m0");
-    };
-    // Stage hand-over, once per k-step (in its third slice, before the first LDS
-    // read of the next stage).  Requests of this wavefront still in flight then:
-    // stages s + 1 .. s + 3 and the 4 requests of stage s + 4 that slices 0 and 1
-    // have issued; stage s + 1 has landed when all but the 20 youngest have.
-    auto n4_sync = [&]() {
-      __builtin_amdgcn_s_waitcnt(vmcnt_imm(2 * 8 + 4));
-      __syncthreads();
-    };
-    // Stages 0 .. NSTAGE - 2 requested, stage 0 landed.
-    auto n4_prologue = [&]() {
-#pragma unroll
-      for (int st = 0; st < NSTAGE - 1; ++st) {
-        const N4Addr pa0 = n4_addr(st, st);
-#pragma unroll
-        for (int r = 0; r < 8; ++r) n4_issue(pa0, r >> 1, r & 1);
-      }
-      __builtin_amdgcn_s_waitcnt(vmcnt_imm(3 * 8));
-      __syncthreads();
-    };
-
-    // This lane's operand rows inside a stage (uint4 units): rows / columns.
-    uint32_t row_off4 = (0 * 2 + g) * 4 * kSliceU4 + wr + lr;
-    uint32_t col_off4 = (1 * 2 + g) * 4 * kSliceU4 + wc + lr;
-    asm volatile("" : "+v"(row_off4), "+v"(col_off4), "+v"(lane16));
-    uint4 RA[2][BI], RB[2][2];  // raw words [raw buffer][block]
-    // fragment kinds: 0 H, 1 D, 2 T, 3 Y
-    v8i Fa[4][BI], Fb[4][2];
-#define N4_READ(RB_, BUF, C)                                                   \
-    {                                                                          \
-      const uint4 *l_rows_ = lds + (BUF) * kStageN4 + row_off4 + (C) * kSliceU4; \
-      const uint4 *l_cols_ = lds + (BUF) * kStageN4 + col_off4 + (C) * kSliceU4; \
-      _Pragma("unroll") for (int b = 0; b < BI; ++b) RA[RB_][b] = l_rows_[b * 32]; \
-      _Pragma("unroll") for (int b = 0; b < 2; ++b) RB[RB_][b] = l_cols_[b * 32]; \
+    for (int p = 0; p < 2; ++p) {
+      As[b][p] = shr3(A[b][p]);
+      Bs[b][p] = shr3(B[b][p]);
     }
+  CUKING_MMA16(1, Y)
+  CUKING_MMA4(1, Y)
+  CUKING_EXPAND(Y, As, Bs, m1)
+  CUKING_MMA16(2, X)
+  CUKING_MMA4(2, X)
+  CUKING_MMA16(3, Y)
+  CUKING_MMA4(3, Y)
+#undef CUKING_LOAD_RAW
+#undef CUKING_EXPAND
+#undef CUKING_MMA1
+#undef CUKING_MMA16
+#undef CUKING_MMA4
+}
+
+// ---- Four products ------------------------------------------------------
+// With D = defined, H = het, Y = hom-ref or hom-alt, T = (hom-ref) - (hom-alt):
+//     hi = H_i.D_j    hj = D_i.H_j    dd = D_i.D_j    q = T_i.T_j
+// and  2 bh - 4 opp - hi - hj = hi + hj - 2 dd + 2 q   (kinship's numerator),
+//      bh - hom_hom = hi + hj - dd,   hom_hom - 2 opp = q,
+// so four MFMAs per block pair and 64 sites instead of five give the
+// threshold decision (the minimum: {numerator, hi, hj} is not in the span of
+// three rank-1 products), and one more sum -- hom_hom, recounted for the few
+// emitted pairs (lean) or from the pass in front of this loop (full form: the
+// same het-plane pass as the five-product kernel's, reading a het-only copy
+// behind the codes; a fifth product Y_i.Y_j inside this loop would need 320
+// accumulator registers, which the compiler then shuffles between the two
+// halves of the register file around every MFMA, and a pass of its own over
+// the staged codes moves all the bytes again for a quarter of the MFMAs:
+// 3.2 ms of 8.8 at 10k x 100k) -- gives bh and opp.
+// T needs a sign: the nibble layout (king_common.h) stores one fp4 code per
+// site, H at bit 0 (0.5), D at bit 1 (1.0), Y at bit 2 (2.0), hom-alt in the
+// SIGN bit, so that every fragment is ONE v_and_b32 of a stored dword with a
+// constant (T: 0xC -> +-2.0) -- no bit-position passes, no shifted copies, no
+// block scales: all MFMAs are the unscaled instruction, and each product
+// carries a constant power of two (hi, hj: 1/2; q, hom_hom: 4) that the
+// epilogue takes out exactly.  Per k-step (256 sites, 4 slices of 64) and
+// wavefront: 64 MFMAs, 192 v_and (3.0 per MFMA; five products: 80 / 288),
+// 16 ds_read_b128, 8 LDS-DMA requests of 1 KiB (twice the bytes).
+//
+// Pipeline (per slice c = 16 or 20 MFMAs): fragments are NOT double
+// buffered; a fragment kind is rebuilt for slice c + 1 in the MFMA group
+// behind its last use in slice c (group order hi, hj, dd, q[, hom_hom]), the
+// raw words of slice c + 1 sit in the second raw buffer, and the LDS reads of
+// slice c + 2 go into the buffer slice c has finished with.
+template <bool FULL>
+__device__ __forceinline__ void four_product_loop(const TiledArgs &a, const Segment &s,
+                                                  const Lanes &l, const NibbleMasks &m,
+                                                  uint4 *const lds, v16f (&acc)[2][2][kNQ],
+                                                  v16f (&hh5)[2][2]) {
+  constexpr bool HH5 = FULL;
+  constexpr int NSTAGE = stages_of(FULL, true);
+  const uint32_t wave = l.wave, g = l.g, lr = l.lr, wr = l.wy * 64, wc = l.wx * 64;
+  const uint32_t s_stride = a.geo.s_stride, k_first = s.k_first, num_steps = s.num_steps;
+  const uint32_t m1 = m.m1, m2 = m.m2;
+  uint32_t lane16 = l.lane * 16;           // byte offset of the lane in a DMA row
+  const uint32_t dma_side = wave >> 1, dma_kg = wave & 1;
+  const uint4 *g_rows = a.planes + (uint64_t)s.tr * kTile;
+  const uint4 *g_cols = a.planes + a.geo.col_base + (uint64_t)s.tc * kTile;
+  constexpr int kSliceU4 = kTile;                  // one slice of one (side, k-group)
+  constexpr int kStageN4 = 2 * 2 * 4 * kSliceU4;   // uint4 per stage (32 KiB)
+  uint32_t mT;
+  asm volatile("s_mov_b32 %0, 0xcccccccc" : "=s"(mT));
+  const uint32_t mH = m1, mD = m2;
+  // DMA: wavefront (side, k-group) fetches that quarter of a stage: 4 slices x
+  // 2 halves of 64 samples, 1 KiB each.  Slice c of k-step s is group
+  // 8 s + 4 kg + c of the layout.
+  const uint4 *const g_wave4 = (dma_side ? g_cols : g_rows) +
+                               (uint64_t)(8 * k_first + 4 * dma_kg) * s_stride;
+  const uint32_t l_wave4 = (uint32_t)(uintptr_t)(lds_void_ptr)(
+      lds + ((dma_side * 2 + dma_kg) * 4) * kSliceU4);
+  struct N4Addr { const uint4 *src; uint32_t dst; };
+  auto n4_addr = [&](uint32_t step, uint32_t buf) {
+    N4Addr pa;
+    if (step >= num_steps) step = num_steps - 1;  // (clamped repeats: see piece_addr)
+    pa.src = g_wave4 + (uint64_t)step * 8 * s_stride;
+    pa.dst = l_wave4 + buf * (kStageN4 * 16);
+    asm volatile("" : "+s"(pa.src), "+s"(pa.dst));
+    return pa;
+  };
+  // ... of the stage after the one `pa` names: one k-step further unless that was
+  // the last (then the same rows again: clamped repeats), into buffer `buf` --
+  // a compare, a select and two adds instead of n4_addr's 64-bit multiply chain
+  // (65 cycles of a k-step in the stamps, profiles/r03_stamps_n4.txt).
+  const uint32_t kstep_bytes = 8 * s_stride * 16;  // (< 2^32: 128 B x stored samples)
+  auto n4_next = [&](const N4Addr &cur, uint32_t step, uint32_t buf) {
+    N4Addr pa;
+    const uint32_t adv = step < num_steps ? kstep_bytes : 0u;
+    pa.src = reinterpret_cast<const uint4 *>(reinterpret_cast<const char *>(cur.src) + adv);
+    pa.dst = l_wave4 + buf * (kStageN4 * 16);
+    asm volatile("" : "+s"(pa.src), "+s"(pa.dst));
+    return pa;
+  };
+  auto n4_issue = [&](const N4Addr &pa, int c, int half) {
+    const uint4 *src = pa.src + (uint64_t)c * s_stride;
+    const uint32_t dst = pa.dst + c * (kSliceU4 * 16);
+    if (half) CUKING_LDS_DMA(dst, src, " offset:1024");
+    else CUKING_LDS_DMA(dst, src, "");
+  };
+  // Stage hand-over, once per k-step (in its third slice, before the first LDS
+  // read of the next stage).  Requests of this wavefront still in flight then:
+  // stages s + 1 .. s + 3 and the 4 requests of stage s + 4 that slices 0 and 1
+  // have issued; stage s + 1 has landed when all but the 20 youngest have.
+  auto n4_sync = [&]() {
+    __builtin_amdgcn_s_waitcnt(vmcnt_imm(2 * 8 + 4));
+    __syncthreads();
+  };
+  // Stages 0 .. NSTAGE - 2 requested, stage 0 landed.
+  auto n4_prologue = [&]() {
+#pragma unroll
+    for (int st = 0; st < NSTAGE - 1; ++st) {
+      const N4Addr pa0 = n4_addr(st, st);
+#pragma unroll
+      for (int r = 0; r < 8; ++r) n4_issue(pa0, r >> 1, r & 1);
+    }
+    __builtin_amdgcn_s_waitcnt(vmcnt_imm(3 * 8));
+    __syncthreads();
+  };
+
+  // This lane's operand rows inside a stage (uint4 units): rows / columns.
+  uint32_t row_off4 = (0 * 2 + g) * 4 * kSliceU4 + wr + lr;
+  uint32_t col_off4 = (1 * 2 + g) * 4 * kSliceU4 + wc + lr;
+  asm volatile("" : "+v"(row_off4), "+v"(col_off4), "+v"(lane16));
+  uint4 RA[2][2], RB[2][2];  // raw words [raw buffer][block]
+  // fragment kinds: 0 H, 1 D, 2 T, 3 Y
+  v8i Fa[4][2], Fb[4][2];
+#define N4_READ(RB_, BUF, C)                                                   \
+  {                                                                            \
+    const uint4 *l_rows_ = lds + (BUF) * kStageN4 + row_off4 + (C) * kSliceU4; \
+    const uint4 *l_cols_ = lds + (BUF) * kStageN4 + col_off4 + (C) * kSliceU4; \
+    _Pragma("unroll") for (int b = 0; b < 2; ++b) RA[RB_][b] = l_rows_[b * 32]; \
+    _Pragma("unroll") for (int b = 0; b < 2; ++b) RB[RB_][b] = l_cols_[b * 32]; \
+  }
 // Fragment builds are plain ANDs: nothing orders them against the MFMA groups
 // but data.  Left alone, the compiler gathers every build that reads a raw
 // buffer into the group that first touches it (60 ANDs behind 4 MFMAs, none
@@ -853,129 +918,129 @@ __global__ __launch_bounds__(256, 1) void king_mfma_kernel(const TiledArgs a) {
 // result, which ties it to the group it is written in.
 #define N4_PIN4(W) asm volatile("" : "+v"((W).x), "+v"((W).y), "+v"((W).z), "+v"((W).w));
 #define N4_PINF(F) asm volatile("" : "+v"((F)[0]), "+v"((F)[1]), "+v"((F)[2]), "+v"((F)[3]));
-#define N4_PIN_RAW_A(RB_) _Pragma("unroll") for (int b = 0; b < BI; ++b) N4_PIN4(RA[RB_][b])
+#define N4_PIN_RAW_A(RB_) _Pragma("unroll") for (int b = 0; b < 2; ++b) N4_PIN4(RA[RB_][b])
 #define N4_PIN_RAW_B(RB_) _Pragma("unroll") for (int b = 0; b < 2; ++b) N4_PIN4(RB[RB_][b])
-#define N4_PIN_A(K) _Pragma("unroll") for (int b = 0; b < BI; ++b) N4_PINF(Fa[K][b])
+#define N4_PIN_A(K) _Pragma("unroll") for (int b = 0; b < 2; ++b) N4_PINF(Fa[K][b])
 #define N4_PIN_B(K) _Pragma("unroll") for (int b = 0; b < 2; ++b) N4_PINF(Fb[K][b])
 #define N4_BUILD_A(K, RB_, MASK)                                               \
-    _Pragma("unroll") for (int b = 0; b < BI; ++b) Fa[K][b] = nfrag(RA[RB_][b], MASK);
+  _Pragma("unroll") for (int b = 0; b < 2; ++b) Fa[K][b] = nfrag(RA[RB_][b], MASK);
 #define N4_BUILD_B(K, RB_, MASK)                                               \
-    _Pragma("unroll") for (int b = 0; b < 2; ++b) Fb[K][b] = nfrag(RB[RB_][b], MASK);
+  _Pragma("unroll") for (int b = 0; b < 2; ++b) Fb[K][b] = nfrag(RB[RB_][b], MASK);
 // product Q = kind KA of the rows x kind KB of the columns, four block pairs
 #define N4_MMA(Q, KA, KB)                                                      \
-    _Pragma("unroll") for (int bi = 0; bi < BI; ++bi)                          \
-    _Pragma("unroll") for (int bj = 0; bj < 2; ++bj)                           \
-      acc[bi][bj][Q] = mma<1>(Fa[KA][bi], Fb[KB][bj], acc[bi][bj][Q]);
+  _Pragma("unroll") for (int bi = 0; bi < 2; ++bi)                             \
+  _Pragma("unroll") for (int bj = 0; bj < 2; ++bj)                             \
+    acc[bi][bj][Q] = mma<1>(Fa[KA][bi], Fb[KB][bj], acc[bi][bj][Q]);
 // A group of four MFMAs that also carries the slice's two DMA requests (in gaps
 // of their own) and the H columns of the next slice.
 #define N4_DMA_GROUP(Q, K, NXT, C)                                             \
-    _Pragma("unroll") for (int r = 0; r < 2; ++r) {                            \
-      n4_issue(pa, C, r);                                                      \
-      acc[0][r][Q] = mma<1>(Fa[K][0], Fb[K][r], acc[0][r][Q]);                 \
-      __builtin_amdgcn_sched_barrier(0);                                       \
-    }                                                                          \
-    N4_PIN_RAW_B(NXT)                                                          \
-    N4_BUILD_B(0, NXT, mH)                                                     \
-    _Pragma("unroll") for (int r = 0; r < 2; ++r)                              \
-      acc[1][r][Q] = mma<1>(Fa[K][1], Fb[K][r], acc[1][r][Q]);                 \
-    CUKING_PACE(2, 4)                                                          \
-    N4_PIN_B(0)                                                                \
-    __builtin_amdgcn_sched_barrier(0);
+  _Pragma("unroll") for (int r = 0; r < 2; ++r) {                              \
+    n4_issue(pa, C, r);                                                        \
+    acc[0][r][Q] = mma<1>(Fa[K][0], Fb[K][r], acc[0][r][Q]);                   \
+    __builtin_amdgcn_sched_barrier(0);                                         \
+  }                                                                            \
+  N4_PIN_RAW_B(NXT)                                                            \
+  N4_BUILD_B(0, NXT, mH)                                                       \
+  _Pragma("unroll") for (int r = 0; r < 2; ++r)                                \
+    acc[1][r][Q] = mma<1>(Fa[K][1], Fb[K][r], acc[1][r][Q]);                   \
+  CUKING_PACE(2, 4)                                                            \
+  N4_PIN_B(0)                                                                  \
+  __builtin_amdgcn_sched_barrier(0);
 // A group that issues the LDS reads of the slice after next (behind the stage
 // hand-over if SYNC) and builds the H rows of the next slice.
 #define N4_READ_GROUP(Q, KA, KB, CUR, NXT, RBUF, RSLICE, SYNC)                 \
-    if (SYNC) n4_sync();                                                       \
-    N4_READ(CUR, RBUF, RSLICE)                                                 \
-    N4_PIN_RAW_A(NXT)                                                          \
-    N4_BUILD_A(0, NXT, mH)                                                     \
-    N4_MMA(Q, KA, KB)                                                          \
-    _Pragma("unroll") for (int i_ = 0; i_ < 4; ++i_) {                         \
-      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                       \
-      __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);                       \
-      __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);                       \
-    }                                                                          \
-    N4_PIN_A(0)                                                                \
-    __builtin_amdgcn_sched_barrier(0);
+  if (SYNC) n4_sync();                                                         \
+  N4_READ(CUR, RBUF, RSLICE)                                                   \
+  N4_PIN_RAW_A(NXT)                                                            \
+  N4_BUILD_A(0, NXT, mH)                                                       \
+  N4_MMA(Q, KA, KB)                                                            \
+  _Pragma("unroll") for (int i_ = 0; i_ < 4; ++i_) {                           \
+    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                         \
+    __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);                         \
+    __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);                         \
+  }                                                                            \
+  N4_PIN_A(0)                                                                  \
+  __builtin_amdgcn_sched_barrier(0);
 // The last group of a slice: D of the next slice, columns first (the next
 // slice's first MFMAs read them).
 #define N4_LAST_GROUP(Q, KA, KB, NXT)                                          \
-    N4_PIN_RAW_A(NXT) N4_PIN_RAW_B(NXT)                                        \
-    N4_BUILD_B(1, NXT, mD) N4_BUILD_A(1, NXT, mD)                              \
-    N4_MMA(Q, KA, KB)                                                          \
-    CUKING_PACE(4, 4)                                                          \
-    N4_PIN_B(1) N4_PIN_A(1)                                                    \
-    __builtin_amdgcn_sched_barrier(0);
+  N4_PIN_RAW_A(NXT) N4_PIN_RAW_B(NXT)                                          \
+  N4_BUILD_B(1, NXT, mD) N4_BUILD_A(1, NXT, mD)                                \
+  N4_MMA(Q, KA, KB)                                                            \
+  CUKING_PACE(4, 4)                                                            \
+  N4_PIN_B(1) N4_PIN_A(1)                                                      \
+  __builtin_amdgcn_sched_barrier(0);
 // One slice.  CUR / NXT: raw buffers of this and the next slice; (RBUF, RSLICE):
 // stage buffer and slice whose raw words are read into CUR once this slice is
 // through with them (the slice after next); C: which slice's two DMA requests
 // go out; SYNC: stage hand-over in front of the reads.
 #define N4_SLICE(CUR, NXT, RBUF, RSLICE, SYNC, C)                              \
-    {                                                                          \
-      /* hi = H_i.D_j; T of this slice from its own raw words */               \
-      N4_PIN_RAW_A(CUR) N4_PIN_RAW_B(CUR)                                      \
-      N4_BUILD_A(2, CUR, mT) N4_BUILD_B(2, CUR, mT)                            \
-      N4_MMA(0, 0, 1)                                                          \
-      /* (last slice: the next k-step's request addresses -- a dependent chain  \
-         of ~10 scalar instructions -- among this group's MFMAs, not behind the \
-         k-step where nothing covers them) */                                  \
-      if ((C) == 3) pa_next = n4_next(pa, step + NSTAGE, buf);                 \
-      CUKING_PACE(4, 4)                                                        \
-      N4_PIN_A(2) N4_PIN_B(2)                                                  \
-      __builtin_amdgcn_sched_barrier(0);                                       \
-      /* hj = D_i.H_j */                                                       \
-      N4_READ_GROUP(1, 1, 0, CUR, NXT, RBUF, RSLICE, SYNC)                     \
-      /* dd = D_i.D_j */                                                       \
-      N4_DMA_GROUP(2, 1, NXT, C)                                               \
-      /* q = T_i.T_j */                                                        \
-      N4_LAST_GROUP(3, 2, 2, NXT)                                              \
-    }
-    zero_acc();
-    if constexpr (HH5) {
-      // 320 accumulator-like registers for a 256-entry accumulator file: say
-      // which 64 live in the other half (left to itself the compiler moves some
-      // of each through v_accvgpr copies around every MFMA of the split
-      // instantiation's main loop: 368 copies per k-step).
+  {                                                                            \
+    /* hi = H_i.D_j; T of this slice from its own raw words */                 \
+    N4_PIN_RAW_A(CUR) N4_PIN_RAW_B(CUR)                                        \
+    N4_BUILD_A(2, CUR, mT) N4_BUILD_B(2, CUR, mT)                              \
+    N4_MMA(0, 0, 1)                                                            \
+    /* (last slice: the next k-step's request addresses -- a dependent chain   \
+       of ~10 scalar instructions -- among this group's MFMAs, not behind the  \
+       k-step where nothing covers them) */                                    \
+    if ((C) == 3) pa_next = n4_next(pa, step + NSTAGE, buf);                   \
+    CUKING_PACE(4, 4)                                                          \
+    N4_PIN_A(2) N4_PIN_B(2)                                                    \
+    __builtin_amdgcn_sched_barrier(0);                                         \
+    /* hj = D_i.H_j */                                                         \
+    N4_READ_GROUP(1, 1, 0, CUR, NXT, RBUF, RSLICE, SYNC)                       \
+    /* dd = D_i.D_j */                                                         \
+    N4_DMA_GROUP(2, 1, NXT, C)                                                 \
+    /* q = T_i.T_j */                                                          \
+    N4_LAST_GROUP(3, 2, 2, NXT)                                                \
+  }
+  zero_acc(acc);
+  if constexpr (HH5) {
+    // 320 accumulator-like registers for a 256-entry accumulator file: say
+    // which 64 live in the other half (left to itself the compiler moves some
+    // of each through v_accvgpr copies around every MFMA of the split
+    // instantiation's main loop: 368 copies per k-step).
 #pragma unroll
-      for (int bi = 0; bi < BI; ++bi)
+    for (int bi = 0; bi < 2; ++bi)
 #pragma unroll
-        for (int bj = 0; bj < 2; ++bj) {
-          asm volatile("" : "+v"(hh5[bi][bj]));
+      for (int bj = 0; bj < 2; ++bj) {
+        asm volatile("" : "+v"(hh5[bi][bj]));
 #pragma unroll
-          for (int q = 0; q < NQ; ++q) asm volatile("" : "+a"(acc[bi][bj][q]));
-        }
-    }
-    n4_prologue();
-    N4_READ(0, 0, 0)
-    N4_READ(1, 0, 1)
-    N4_BUILD_A(0, 0, mH) N4_BUILD_B(0, 0, mH)
-    N4_BUILD_A(1, 0, mD) N4_BUILD_B(1, 0, mD)
-    uint32_t buf = 0;  // buffer of the k-step being multiplied
-    // k-step s requests stage s + NSTAGE - 1 into the buffer stage s - 1 left
-    // (all its reads were issued before the hand-over of k-step s - 1)
-    N4Addr pa = n4_addr(NSTAGE - 1, NSTAGE - 1);
-    // One k-step; four per loop trip (the trip's back edge and counter updates cost
-    // ~100 cycles with nothing to cover them: stamps, profiles/r03_stamps_n4.txt;
-    // 1, 2, 4 k-steps per trip: configs[2] 540 -> 529 -> 526 ms).
+        for (int q = 0; q < kNQ; ++q) asm volatile("" : "+a"(acc[bi][bj][q]));
+      }
+  }
+  n4_prologue();
+  N4_READ(0, 0, 0)
+  N4_READ(1, 0, 1)
+  N4_BUILD_A(0, 0, mH) N4_BUILD_B(0, 0, mH)
+  N4_BUILD_A(1, 0, mD) N4_BUILD_B(1, 0, mD)
+  uint32_t buf = 0;  // buffer of the k-step being multiplied
+  // k-step s requests stage s + NSTAGE - 1 into the buffer stage s - 1 left
+  // (all its reads were issued before the hand-over of k-step s - 1)
+  N4Addr pa = n4_addr(NSTAGE - 1, NSTAGE - 1);
+  // One k-step; four per loop trip (the trip's back edge and counter updates cost
+  // ~100 cycles with nothing to cover them: stamps, profiles/r03_stamps_n4.txt;
+  // 1, 2, 4 k-steps per trip: configs[2] 540 -> 529 -> 526 ms).
 #define N4_KSTEP                                                               \
-    {                                                                          \
-      const uint32_t nbuf = buf == NSTAGE - 1 ? 0 : buf + 1;                   \
-      N4Addr pa_next;                                                          \
-      N4_SLICE(0, 1, buf, 2, false, 0)                                         \
-      N4_SLICE(1, 0, buf, 3, false, 1)                                         \
-      N4_SLICE(0, 1, nbuf, 0, true, 2)                                         \
-      N4_SLICE(1, 0, nbuf, 1, false, 3)                                        \
-      pa = pa_next;                                                            \
-      buf = nbuf;                                                              \
-      ++step;                                                                  \
-    }
-    uint32_t step = 0;
-    while (step + 3 < num_steps) {
-      N4_KSTEP
-      N4_KSTEP
-      N4_KSTEP
-      N4_KSTEP
-    }
-    while (step < num_steps) N4_KSTEP
+  {                                                                            \
+    const uint32_t nbuf = buf == NSTAGE - 1 ? 0 : buf + 1;                     \
+    N4Addr pa_next;                                                            \
+    N4_SLICE(0, 1, buf, 2, false, 0)                                           \
+    N4_SLICE(1, 0, buf, 3, false, 1)                                           \
+    N4_SLICE(0, 1, nbuf, 0, true, 2)                                           \
+    N4_SLICE(1, 0, nbuf, 1, false, 3)                                          \
+    pa = pa_next;                                                              \
+    buf = nbuf;                                                                \
+    ++step;                                                                    \
+  }
+  uint32_t step = 0;
+  while (step + 3 < num_steps) {
+    N4_KSTEP
+    N4_KSTEP
+    N4_KSTEP
+    N4_KSTEP
+  }
+  while (step < num_steps) N4_KSTEP
 #undef N4_KSTEP
 #undef N4_READ
 #undef N4_PIN4
@@ -991,274 +1056,319 @@ __global__ __launch_bounds__(256, 1) void king_mfma_kernel(const TiledArgs a) {
 #undef N4_READ_GROUP
 #undef N4_LAST_GROUP
 #undef N4_SLICE
-  }
-  // The clamped repeats of the last stage must have landed before the
-  // workgroup's LDS goes away.
-  __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
-  if (SPLIT) __syncthreads();  // ... and nobody reads the stages any more
+}
 
-  // Full form: the fifth sum stays where the pass in front of the main loop
-  // parked it (this lane's 16-byte slots) and is read block by block.
-  float4 *const park = reinterpret_cast<float4 *>(lds + (PARKED ? NSTAGE * kStageU4 : 0)) +
-                       (size_t)wave * (4 * 4 * 64) + lane;
-#undef CUKING_LOAD_RAW
-#undef CUKING_EXPAND
-#undef CUKING_MMA1
-#undef CUKING_MMA16
-#undef CUKING_MMA4
-
-  if (SPLIT && num_steps != tile_steps) {
-    // Partial tile: park this part in its own slab (16-byte stores,
-    // lane-linear [wave][block pair][sum][4 registers][lane]), then take a
-    // ticket of the tile.  Slab of a part: 2 * workgroup + (0 for the piece in
-    // the workgroup's first tile, 1 for the piece in its second).
-    constexpr size_t kSlabU4 = 4 * 4 * 4 * 4 * 64;          // uint4 per slab (lean)
-    constexpr size_t kPassU4 = 4 * BI * 2 * NSUM * 4 * 64;  // ... of this form
-    static_assert(kPassU4 <= kSlabU4 * 5 / 4, "slab size");
-    // (positions inside the cut-up part of the launch: tile and units count
-    // from its first tile)
-    const uint32_t cut_tile = seg_tile - a.split_whole;
-    const uint64_t first_unit = (uint64_t)cut_tile * tile_steps;
-    const uint64_t my_first = split_bound(piece, units, a.split_wgs);
-    const uint32_t my_slab = 2 * piece + (my_first / tile_steps == cut_tile ? 0 : 1);
-    float4 *slabs = reinterpret_cast<float4 *>(a.split_scratch);
-    constexpr size_t kSlabStride = kSlabU4 * 5 / 4;  // sized for the full form
-    {
-      // Write-through (sc1) 16-byte stores: the data is in memory when the
-      // wait below returns, so no release fence (which would write back the
-      // whole L2: tens of microseconds with 256 KiB freshly dirtied).
-      typedef uint32_t v4u __attribute__((ext_vector_type(4)));
-      const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
-          slabs + my_slab * kSlabStride, 0, (int)(kPassU4 * 16), 0x00020000);
-      const int base = (int)((wave * (BI * 2 * NSUM * 4 * 64) + lane) * 16);
+// SPLIT, a partial tile: park this part in its own slab (16-byte stores,
+// lane-linear [wave][block pair][sum][4 registers][lane]), then take a
+// ticket of the tile.  Slab of a part: 2 * workgroup + (0 for the piece in
+// the workgroup's first tile, 1 for the piece in its second).  The workgroup that
+// delivers the tile's last part adds the others to its own and runs the epilogue (true);
+// the others are through with the tile.  `park`: the five-product full form's fifth sum.
+template <bool FULL, bool N4>
+__device__ __forceinline__ bool reduce_parts(const TiledArgs &a, const uint32_t piece,
+                                             const Segment &s, const Lanes &l, uint4 *const lds,
+                                             float4 *const park, v16f (&acc)[2][2][kNQ],
+                                             v16f (&hh5)[2][2]) {
+  constexpr int NSUM = sums_of(FULL);
+  constexpr bool HH5 = FULL && N4;
+  constexpr size_t kSlabU4 = 4 * 4 * 4 * 4 * 64;          // uint4 per slab (lean)
+  constexpr size_t kPassU4 = 4 * 2 * 2 * NSUM * 4 * 64;   // ... of this form
+  static_assert(kPassU4 <= kSlabU4 * 5 / 4, "slab size");
+  const uint32_t tile_steps = tile_steps_of(a);
+  const uint64_t units = (uint64_t)a.split_tiles * tile_steps;  // of the cut-up tiles
+  // (positions inside the cut-up part of the launch: tile and units count
+  // from its first tile)
+  const uint32_t cut_tile = s.tile - a.split_whole;
+  const uint64_t first_unit = (uint64_t)cut_tile * tile_steps;
+  const uint64_t my_first = split_bound(piece, units, a.split_wgs);
+  const uint32_t my_slab = 2 * piece + (my_first / tile_steps == cut_tile ? 0 : 1);
+  float4 *slabs = reinterpret_cast<float4 *>(a.split_scratch);
+  constexpr size_t kSlabStride = kSlabU4 * 5 / 4;  // sized for the full form
+  {
+    // Write-through (sc1) 16-byte stores: the data is in memory when the
+    // wait below returns, so no release fence (which would write back the
+    // whole L2: tens of microseconds with 256 KiB freshly dirtied).
+    typedef uint32_t v4u __attribute__((ext_vector_type(4)));
+    const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
+        slabs + my_slab * kSlabStride, 0, (int)(kPassU4 * 16), 0x00020000);
+    const int base = (int)((l.wave * (2 * 2 * NSUM * 4 * 64) + l.lane) * 16);
 #pragma unroll
-      for (int bi = 0; bi < BI; ++bi)
+    for (int bi = 0; bi < 2; ++bi)
 #pragma unroll
-        for (int bj = 0; bj < 2; ++bj)
+      for (int bj = 0; bj < 2; ++bj)
 #pragma unroll
-          for (int q = 0; q < NSUM; ++q)
-#pragma unroll
-            for (int r4 = 0; r4 < 4; ++r4) {
-              v4u v;
-              if (q < NQ) {
-                v[0] = __float_as_uint(acc[bi][bj][q][4 * r4]);
-                v[1] = __float_as_uint(acc[bi][bj][q][4 * r4 + 1]);
-                v[2] = __float_as_uint(acc[bi][bj][q][4 * r4 + 2]);
-                v[3] = __float_as_uint(acc[bi][bj][q][4 * r4 + 3]);
-              } else if constexpr (HH5) {
-                v[0] = __float_as_uint(hh5[bi][bj][4 * r4]);
-                v[1] = __float_as_uint(hh5[bi][bj][4 * r4 + 1]);
-                v[2] = __float_as_uint(hh5[bi][bj][4 * r4 + 2]);
-                v[3] = __float_as_uint(hh5[bi][bj][4 * r4 + 3]);
-              } else {
-                const float4 h = park[((bi * 2 + bj) * 4 + r4) * 64];
-                v[0] = __float_as_uint(h.x);
-                v[1] = __float_as_uint(h.y);
-                v[2] = __float_as_uint(h.z);
-                v[3] = __float_as_uint(h.w);
-              }
-              __builtin_amdgcn_raw_buffer_store_b128(
-                  v, rsrc, base + ((((bi * 2 + bj) * NSUM + q) * 4 + r4) * 64) * 16, 0,
-                  16 /* sc1 */);
-            }
-    }
-    // Every wavefront's stores are done (and written through), then the
-    // ticket (cdna_hip_programming.md, Guideline 16: sc1 payload + counter).
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    uint32_t *flag = reinterpret_cast<uint32_t *>(lds);  // stages are idle now
-    const uint32_t w_first = split_owner(first_unit, units, a.split_wgs);
-    const uint32_t w_last = split_owner(first_unit + tile_steps - 1, units, a.split_wgs);
-    if (threadIdx.x == 0) {
-      // One counter per workgroup (and pass): a workgroup owns the first unit
-      // of at most one tile that continues into the next workgroup.
-      uint32_t *counter = a.split_counters + w_first;
-      const uint32_t ticket = relaxed_add(counter, 1u);
-      const bool last = ticket == w_last - w_first;
-      if (last) {
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        *counter = 0;  // ready for the next launch
-      }
-      *flag = last ? 1u : 0u;
-    }
-    __syncthreads();
-    const bool last = *flag != 0;
-    __syncthreads();  // the flag word is stage memory again after this
-    if (!last) continue;
-    // Totals: this part is still in registers, the others come from their slabs.
-    for (uint32_t w = w_first; w <= w_last; ++w) {
-      if (w == piece) continue;
-      const uint32_t slab =
-          2 * w + (split_bound(w, units, a.split_wgs) / tile_steps == cut_tile ? 0 : 1);
-      const float4 *src =
-          slabs + slab * kSlabStride + (size_t)wave * (BI * 2 * NSUM * 4 * 64) + lane;
-#pragma unroll
-      for (int bi = 0; bi < BI; ++bi)
-#pragma unroll
-        for (int bj = 0; bj < 2; ++bj)
-#pragma unroll
-          for (int q = 0; q < NSUM; ++q)
-#pragma unroll
-            for (int r4 = 0; r4 < 4; ++r4) {
-              const float4 v = src[(((bi * 2 + bj) * NSUM + q) * 4 + r4) * 64];
-              if (q < NQ) {
-                acc[bi][bj][q][4 * r4] += v.x;
-                acc[bi][bj][q][4 * r4 + 1] += v.y;
-                acc[bi][bj][q][4 * r4 + 2] += v.z;
-                acc[bi][bj][q][4 * r4 + 3] += v.w;
-              } else if constexpr (HH5) {
-                hh5[bi][bj][4 * r4] += v.x;
-                hh5[bi][bj][4 * r4 + 1] += v.y;
-                hh5[bi][bj][4 * r4 + 2] += v.z;
-                hh5[bi][bj][4 * r4 + 3] += v.w;
-              } else {
-                float4 &h = park[((bi * 2 + bj) * 4 + r4) * 64];
-                h = make_float4(h.x + v.x, h.y + v.y, h.z + v.z, h.w + v.w);
-              }
-            }
-    }
-  }
-
-  // --- epilogue: kinship, threshold, append (cuking.cu:284-313).  C layout of
-  // the 32 x 32 MFMA: column = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5).
-  const auto emit_ctx = [&]() {
-    if constexpr (N4) return make_emit_ctx_p(a);
-    else return make_emit_ctx(a);
-  }();
-  // The five sums of pair (bi, bj, r) as integers.  Five products: they are the
-  // accumulators (hom_hom parked, `parked`).  Four products: hi / 2, hj / 2, dd,
-  // 4 q (and hom_hom in hh5) are, and bh = hi + hj - dd + hom_hom,
-  // opp = (hom_hom - q) / 2.
-  auto pair_sums = [&](int bi, int bj, int r, float parked, uint32_t *het_i, uint32_t *het_j,
-                       uint32_t *both_het, uint32_t *opp, uint32_t *hom_hom) {
-    if constexpr (N4) {
-      *het_i = (uint32_t)(2.f * acc[bi][bj][0][r]);
-      *het_j = (uint32_t)(2.f * acc[bi][bj][1][r]);
-      const uint32_t dd = (uint32_t)acc[bi][bj][2][r];
-      const int32_t q = (int32_t)(0.25f * acc[bi][bj][3][r]);
-      const uint32_t hh = HH5 ? (uint32_t)hh5[bi][bj][r] : 0u;  // (full form only)
-      *hom_hom = hh;
-      *both_het = *het_i + *het_j - dd + hh;
-      *opp = (uint32_t)((int32_t)hh - q) >> 1;
-    } else {
-      *het_i = (uint32_t)acc[bi][bj][2][r];
-      *het_j = (uint32_t)acc[bi][bj][3][r];
-      *both_het = (uint32_t)acc[bi][bj][1][r];
-      *opp = (uint32_t)acc[bi][bj][0][r];
-      *hom_hom = (uint32_t)parked;
-    }
-  };
-  if (FULL && a.dense_counts == nullptr) {
-    // Full form, records: sweep 0 decides every pair (cuking.cu:284-297) and
-    // counts, ONE reservation for the wavefront's records, sweep 1 stores them
-    // (cuking.cu:297-313; slot order inside the reservation: sweep order, then
-    // lane).  The decisions of sweep 0 are kept, one bit per pair.
-    uint32_t total = 0, base = 0, run = 0;  // wave-uniform
-    uint32_t decided[BI * 2] = {};          // bit r of word (bi, bj)
-#pragma nounroll
-    for (int pass = 0; pass < 2; ++pass) {  // (one body: the kernel has no registers for two)
-#pragma unroll
-      for (int bi = 0; bi < BI; ++bi) {
-#pragma unroll
-        for (int bj = 0; bj < 2; ++bj) {
-          const uint32_t lj = tc * kTile + wc + bj * 32 + lr;
+        for (int q = 0; q < NSUM; ++q)
 #pragma unroll
           for (int r4 = 0; r4 < 4; ++r4) {
-            const float4 h4 = PARKED ? park[((bi * 2 + bj) * 4 + r4) * 64]
-                                     : make_float4(0, 0, 0, 0);
-            const float hh[4] = {h4.x, h4.y, h4.z, h4.w};
+            float4 f;
+            if (q < kNQ) f = quarter(acc[bi][bj][q], r4);
+            else if constexpr (HH5) f = quarter(hh5[bi][bj], r4);
+            else f = park[park_slot(bi, bj, r4)];
+            const v4u v = {__float_as_uint(f.x), __float_as_uint(f.y), __float_as_uint(f.z),
+                           __float_as_uint(f.w)};
+            __builtin_amdgcn_raw_buffer_store_b128(
+                v, rsrc, base + slab_slot(NSUM, bi, bj, q, r4) * 16, 0, 16 /* sc1 */);
+          }
+  }
+  // Every wavefront's stores are done (and written through), then the
+  // ticket (cdna_hip_programming.md, Guideline 16: sc1 payload + counter).
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  uint32_t *flag = reinterpret_cast<uint32_t *>(lds);  // stages are idle now
+  const uint32_t w_first = split_owner(first_unit, units, a.split_wgs);
+  const uint32_t w_last = split_owner(first_unit + tile_steps - 1, units, a.split_wgs);
+  if (threadIdx.x == 0) {
+    // One counter per workgroup (and pass): a workgroup owns the first unit
+    // of at most one tile that continues into the next workgroup.
+    uint32_t *counter = a.split_counters + w_first;
+    const uint32_t ticket = relaxed_add(counter, 1u);
+    const bool last = ticket == w_last - w_first;
+    if (last) {
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      *counter = 0;  // ready for the next launch
+    }
+    *flag = last ? 1u : 0u;
+  }
+  __syncthreads();
+  const bool last = *flag != 0;
+  __syncthreads();  // the flag word is stage memory again after this
+  if (!last) return false;
+  // Totals: this part is still in registers, the others come from their slabs.
+  for (uint32_t w = w_first; w <= w_last; ++w) {
+    if (w == piece) continue;
+    const uint32_t slab =
+        2 * w + (split_bound(w, units, a.split_wgs) / tile_steps == cut_tile ? 0 : 1);
+    const float4 *src =
+        slabs + slab * kSlabStride + (size_t)l.wave * (2 * 2 * NSUM * 4 * 64) + l.lane;
 #pragma unroll
-            for (int r1 = 0; r1 < 4; ++r1) {
-              const int r = 4 * r4 + r1;
-              const uint32_t li =
-                  tr * kTile + wr + bi * 32 + (r & 3) + 8 * (r >> 2) + 4 * g;
-              uint32_t het_i, het_j, both_het, opp, hom_hom;
-              pair_sums(bi, bj, r, hh[r1], &het_i, &het_j, &both_het, &opp, &hom_hom);
-              if (pass == 0) {
-                // cuking.cu:199 plus the tile padding
-                const bool valid = li < a.geo.num_rows && lj < a.geo.num_cols &&
-                                   a.i_begin + li < a.j_begin + lj;
-                const bool emit =
-                    valid && king_kinship(het_i, het_j, both_het, opp) > a.kin_threshold;
-                decided[bi * 2 + bj] |= (emit ? 1u : 0u) << r;
-              } else {
-                const bool emit = (decided[bi * 2 + bj] >> r) & 1u;
-                const unsigned long long b = __ballot(emit);
-                if (b != 0) {  // wave-uniform
-                  const uint32_t before = __builtin_amdgcn_mbcnt_hi(
-                      (uint32_t)(b >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b, 0u));
-                  const uint32_t slot = base + run + before;
-                  run += (uint32_t)__popcll(b);
-                  if (emit)
-                    full_store_call(emit_ctx, slot, li, lj, het_i, het_j, both_het, opp,
-                                    hom_hom);
-                }
+    for (int bi = 0; bi < 2; ++bi)
+#pragma unroll
+      for (int bj = 0; bj < 2; ++bj)
+#pragma unroll
+        for (int q = 0; q < NSUM; ++q)
+#pragma unroll
+          for (int r4 = 0; r4 < 4; ++r4) {
+            const float4 v = src[slab_slot(NSUM, bi, bj, q, r4)];
+            if (q < kNQ) {
+              add_quarter(acc[bi][bj][q], r4, v);
+            } else if constexpr (HH5) {
+              add_quarter(hh5[bi][bj], r4, v);
+            } else {
+              float4 &h = park[park_slot(bi, bj, r4)];
+              h = make_float4(h.x + v.x, h.y + v.y, h.z + v.z, h.w + v.w);
+            }
+          }
+  }
+  return true;
+}
+
+// ---- Epilogues: kinship, threshold, append (cuking.cu:284-313).  C layout of the 32 x 32
+// MFMA: column = lane & 31, row = c_row(r, lane >> 5).
+// Row (column) within the block of register r of block row bi (of block column bj), from the
+// wavefront's first row (column) `row0` (`col0`).  The full form's epilogues work the origin out
+// per pair, the lean ones ONCE in front of their loops (pair_origin()); the other way round,
+// the k loops of the full four-product forms and of the unsplit dense-kinship forms each came
+// out of the compiler with one to four more LDS waits.
+struct PairOrigin {
+  uint32_t row0, col0;
+};
+__device__ __forceinline__ PairOrigin pair_origin(const Segment &s, const Lanes &l) {
+  return PairOrigin{s.tr * kTile + l.wy * 64, s.tc * kTile + l.wx * 64};
+}
+__device__ __forceinline__ uint32_t pair_row(const PairOrigin &o, const Lanes &l, int bi, int r) {
+  return o.row0 + bi * 32 + c_row(r, l.g);
+}
+__device__ __forceinline__ uint32_t pair_col(const PairOrigin &o, const Lanes &l, int bj) {
+  return o.col0 + bj * 32 + l.lr;
+}
+// cuking.cu:199 plus the tile padding (`diag` = 1: the pairs (i, i) as well)
+__device__ __forceinline__ bool pair_valid(const TiledArgs &a, uint32_t li, uint32_t lj,
+                                           uint32_t diag = 0) {
+  return li < a.geo.num_rows && lj < a.geo.num_cols && a.i_begin + li < a.j_begin + lj + diag;
+}
+template <bool N4>
+__device__ __forceinline__ auto emit_ctx_of(const TiledArgs &a) {
+  if constexpr (N4) return make_emit_ctx_p(a);
+  else return make_emit_ctx(a);
+}
+
+// The five sums of pair (bi, bj, r) as integers (full form).  Five products: they are the
+// accumulators (hom_hom parked, `parked`).  Four products: hi / 2, hj / 2, dd,
+// 4 q (and hom_hom in hh5) are, and bh = hi + hj - dd + hom_hom,
+// opp = (hom_hom - q) / 2.  (Full form only: the lean forms never run hom_hom_pass, their
+// `hh5` is a name for the k loop's and reduce_parts' signatures and holds nothing.)
+template <bool N4>
+__device__ __forceinline__ void pair_sums(const v16f (&acc)[2][2][kNQ], const v16f (&hh5)[2][2],
+                                          int bi, int bj, int r, float parked, uint32_t *het_i,
+                                          uint32_t *het_j, uint32_t *both_het, uint32_t *opp,
+                                          uint32_t *hom_hom) {
+  if constexpr (N4) {
+    *het_i = (uint32_t)(2.f * acc[bi][bj][0][r]);
+    *het_j = (uint32_t)(2.f * acc[bi][bj][1][r]);
+    const uint32_t dd = (uint32_t)acc[bi][bj][2][r];
+    const int32_t q = (int32_t)(0.25f * acc[bi][bj][3][r]);
+    const uint32_t hh = (uint32_t)hh5[bi][bj][r];  // (full form only)
+    *hom_hom = hh;
+    *both_het = *het_i + *het_j - dd + hh;
+    *opp = (uint32_t)((int32_t)hh - q) >> 1;
+  } else {
+    *het_i = (uint32_t)acc[bi][bj][2][r];
+    *het_j = (uint32_t)acc[bi][bj][3][r];
+    *both_het = (uint32_t)acc[bi][bj][1][r];
+    *opp = (uint32_t)acc[bi][bj][0][r];
+    *hom_hom = (uint32_t)parked;
+  }
+}
+
+// Full form, records: sweep 0 decides every pair (cuking.cu:284-297) and
+// counts, ONE reservation for the wavefront's records, sweep 1 stores them
+// (cuking.cu:297-313; slot order inside the reservation: sweep order, then
+// lane).  The decisions of sweep 0 are kept, one bit per pair.
+// The fifth sum stays where the pass in front of the main loop parked it (five products:
+// this lane's 16-byte slots `park`) and is read block by block.
+template <bool N4>
+__device__ __forceinline__ void emit_full_records(const TiledArgs &a, const Segment &s,
+                                                  const Lanes &l, const float4 *const park,
+                                                  const v16f (&acc)[2][2][kNQ],
+                                                  const v16f (&hh5)[2][2]) {
+  const auto emit_ctx = emit_ctx_of<N4>(a);
+  uint32_t total = 0, base = 0, run = 0;  // wave-uniform
+  uint32_t decided[2 * 2] = {};           // bit r of word (bi, bj)
+#pragma nounroll
+  for (int pass = 0; pass < 2; ++pass) {  // (one body: the kernel has no registers for two)
+#pragma unroll
+    for (int bi = 0; bi < 2; ++bi) {
+#pragma unroll
+      for (int bj = 0; bj < 2; ++bj) {
+        const uint32_t lj = pair_col(pair_origin(s, l), l, bj);
+#pragma unroll
+        for (int r4 = 0; r4 < 4; ++r4) {
+          float hh[4] = {};
+          if constexpr (!N4) unpack(park[park_slot(bi, bj, r4)], hh);
+#pragma unroll
+          for (int r1 = 0; r1 < 4; ++r1) {
+            const int r = 4 * r4 + r1;
+            const uint32_t li = pair_row(pair_origin(s, l), l, bi, r);
+            uint32_t het_i, het_j, both_het, opp, hom_hom;
+            pair_sums<N4>(acc, hh5, bi, bj, r, hh[r1], &het_i, &het_j, &both_het, &opp, &hom_hom);
+            if (pass == 0) {
+              const bool emit = pair_valid(a, li, lj) &&
+                                king_kinship(het_i, het_j, both_het, opp) > a.kin_threshold;
+              decided[bi * 2 + bj] |= (emit ? 1u : 0u) << r;
+            } else {
+              const bool emit = (decided[bi * 2 + bj] >> r) & 1u;
+              const unsigned long long b = __ballot(emit);
+              if (b != 0) {  // wave-uniform
+                const uint32_t before = __builtin_amdgcn_mbcnt_hi(
+                    (uint32_t)(b >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b, 0u));
+                const uint32_t slot = base + run + before;
+                run += (uint32_t)__popcll(b);
+                if (emit)
+                  full_store_call(emit_ctx, slot, li, lj, het_i, het_j, both_het, opp, hom_hom);
               }
             }
           }
         }
       }
-      if (pass == 0) {
-        total = 0;
-#pragma unroll
-        for (int k = 0; k < BI * 2; ++k) total += (uint32_t)__popc(decided[k]);
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) total += __shfl_xor(total, off);
-        total = (uint32_t)__builtin_amdgcn_readfirstlane(total);
-        if (total == 0) break;  // wave-uniform
-        base = reserve_slots(a.result_index, total);
-      }
     }
-  } else {
+    if (pass == 0) {
+      total = 0;
 #pragma unroll
-  for (int bi = 0; bi < BI; ++bi) {
+      for (int k = 0; k < 2 * 2; ++k) total += (uint32_t)__popc(decided[k]);
+#pragma unroll
+      for (int off = 32; off > 0; off >>= 1) total += __shfl_xor(total, off);
+      total = (uint32_t)__builtin_amdgcn_readfirstlane(total);
+      if (total == 0) break;  // wave-uniform
+      base = reserve_slots(a.result_index, total);
+    }
+  }
+}
+
+// Full form, diagnostic counts (TiledArgs::dense_counts): cuking.cu:284-313 with all five
+// sums at hand, for every pair.
+template <bool N4>
+__device__ __forceinline__ void store_counts(const TiledArgs &a, const Segment &s, const Lanes &l,
+                                             const float4 *const park,
+                                             const v16f (&acc)[2][2][kNQ],
+                                             const v16f (&hh5)[2][2]) {
+#pragma unroll
+  for (int bi = 0; bi < 2; ++bi) {
 #pragma unroll
     for (int bj = 0; bj < 2; ++bj) {
-      const uint32_t lj = tc * kTile + wc + bj * 32 + lr;
-      float hh[16];  // (full form) hom_hom of this block's 16 pairs
+      const uint32_t lj = pair_col(pair_origin(s, l), l, bj);
+      float hh[16] = {};  // (five products) hom_hom of this block's 16 pairs
+      if constexpr (!N4) {
 #pragma unroll
-      for (int r4 = 0; r4 < 4; ++r4) {
-        const float4 h = PARKED ? park[((bi * 2 + bj) * 4 + r4) * 64] : make_float4(0, 0, 0, 0);
-        hh[4 * r4] = h.x;
-        hh[4 * r4 + 1] = h.y;
-        hh[4 * r4 + 2] = h.z;
-        hh[4 * r4 + 3] = h.w;
+        for (int r4 = 0; r4 < 4; ++r4) unpack(park[park_slot(bi, bj, r4)], hh + 4 * r4);
       }
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const uint32_t li =
-            tr * kTile + wr + half_rows + bi * 32 + (r & 3) + 8 * (r >> 2) + 4 * g;
-        // cuking.cu:199 plus the tile padding
-        // (dense kinship, symmetric output: the diagonal as well)
-        const bool valid = li < a.geo.num_rows && lj < a.geo.num_cols &&
-                           a.i_begin + li < a.j_begin + lj + (KIN ? a.kin_diag : 0u);
-        if (FULL) {
-          // diagnostic counts: cuking.cu:284-313 with all five sums at hand
-          uint32_t het_i, het_j, both_het, opp, hom_hom;
-          pair_sums(bi, bj, r, hh[r], &het_i, &het_j, &both_het, &opp, &hom_hom);
-          full_epilogue_pair(a, valid, li, lj, het_i, het_j, both_het, opp, hom_hom);
-        } else if constexpr (KIN) {
-          // Dense kinship: the lean epilogue's expression for every pair (four products:
-          // lean_epilogue_pair_n4's, on the exact integers hi, hj, num = hi + hj - 2 dd +
-          // 2 q), with the IEEE divide -- and one store.
-          // Column = lane & 31: the 32 lanes of a half-wave write 128 contiguous bytes of
-          // matrix row li.  (An unsorted layout: plane index = stored sample.)
-          float kin;
-          if constexpr (N4) {
-            const uint32_t het_i = (uint32_t)(2.f * acc[bi][bj][0][r]);
-            const uint32_t het_j = (uint32_t)(2.f * acc[bi][bj][1][r]);
-            const int32_t num = (int32_t)(het_i + het_j) - 2 * (int32_t)acc[bi][bj][2][r] +
-                                2 * (int32_t)(0.25f * acc[bi][bj][3][r]);
-            kin = 0.5f + (float)num / (4.f * (float)(het_i < het_j ? het_i : het_j));
-          } else {
-            // (five products: the accumulators are the reference's own four sums)
-            kin = king_kinship((uint32_t)acc[bi][bj][2][r], (uint32_t)acc[bi][bj][3][r],
-                               (uint32_t)acc[bi][bj][1][r], (uint32_t)acc[bi][bj][0][r]);
-          }
-          if (valid) a.dense_kin[(uint64_t)li * a.kin_ld + lj] = kin;
-        } else if constexpr (N4) {
-          // Four products, lean: the decision needs hi, hj and the numerator
+        const uint32_t li = pair_row(pair_origin(s, l), l, bi, r);
+        uint32_t het_i, het_j, both_het, opp, hom_hom;
+        pair_sums<N4>(acc, hh5, bi, bj, r, hh[r], &het_i, &het_j, &both_het, &opp, &hom_hom);
+        full_epilogue_pair(a, pair_valid(a, li, lj), li, lj, het_i, het_j, both_het, opp, hom_hom);
+      }
+    }
+  }
+}
+
+// Dense kinship (KIN): the lean epilogue's expression for every pair (four products:
+// lean_epilogue_pair_n4's, on the exact integers hi, hj, num = hi + hj - 2 dd +
+// 2 q), with the IEEE divide -- and one store.
+// Column = lane & 31: the 32 lanes of a half-wave write 128 contiguous bytes of
+// matrix row li.  (An unsorted layout: plane index = stored sample.)
+template <bool N4>
+__device__ __forceinline__ void store_kin(const TiledArgs &a, const Segment &s, const Lanes &l,
+                                          const v16f (&acc)[2][2][kNQ]) {
+  const PairOrigin o = pair_origin(s, l);
+#pragma unroll
+  for (int bi = 0; bi < 2; ++bi) {
+#pragma unroll
+    for (int bj = 0; bj < 2; ++bj) {
+      const uint32_t lj = pair_col(o, l, bj);
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const uint32_t li = pair_row(o, l, bi, r);
+        // (symmetric output: the diagonal as well)
+        const bool valid = pair_valid(a, li, lj, a.kin_diag);
+        float kin;
+        if constexpr (N4) {
+          const uint32_t het_i = (uint32_t)(2.f * acc[bi][bj][0][r]);
+          const uint32_t het_j = (uint32_t)(2.f * acc[bi][bj][1][r]);
+          const int32_t num = (int32_t)(het_i + het_j) - 2 * (int32_t)acc[bi][bj][2][r] +
+                              2 * (int32_t)(0.25f * acc[bi][bj][3][r]);
+          kin = 0.5f + (float)num / (4.f * (float)(het_i < het_j ? het_i : het_j));
+        } else {
+          // (five products: the accumulators are the reference's own four sums)
+          kin = king_kinship((uint32_t)acc[bi][bj][2][r], (uint32_t)acc[bi][bj][3][r],
+                             (uint32_t)acc[bi][bj][1][r], (uint32_t)acc[bi][bj][0][r]);
+        }
+        if (valid) a.dense_kin[(uint64_t)li * a.kin_ld + lj] = kin;
+      }
+    }
+  }
+}
+
+// Lean form, records.  Nearly every pair fails the threshold: decide that on the float
+// sums without the IEEE divide, and only when some lane of the
+// wavefront may pass run the exact epilogue (wave-uniform branch, out of line).
+template <bool N4>
+__device__ __forceinline__ void lean_decide(const TiledArgs &a, const Segment &s, const Lanes &l,
+                                            const v16f (&acc)[2][2][kNQ]) {
+  const PairOrigin o = pair_origin(s, l);
+  const auto emit_ctx = emit_ctx_of<N4>(a);
+#pragma unroll
+  for (int bi = 0; bi < 2; ++bi) {
+#pragma unroll
+    for (int bj = 0; bj < 2; ++bj) {
+      const uint32_t lj = pair_col(o, l, bj);
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const uint32_t li = pair_row(o, l, bi, r);
+        const bool valid = pair_valid(a, li, lj);
+        if constexpr (N4) {
+          // Four products: the decision needs hi, hj and the numerator
           // hi + hj - 2 dd + 2 q only; bh and opp of an emitted pair follow from
           // the recount of hom_hom (king_device.h).
           const float f_hi = 2.f * acc[bi][bj][0][r], f_hj = 2.f * acc[bi][bj][1][r];
@@ -1268,25 +1378,75 @@ __global__ __launch_bounds__(256, 1) void king_mfma_kernel(const TiledArgs a) {
           if (__ballot(maybe) != 0)
             lean_epilogue_call_n4(emit_ctx, valid, li, lj, (uint32_t)f_hi, (uint32_t)f_hj,
                                   (uint32_t)acc[bi][bj][2][r],
-                                  (int32_t)(0.25f * acc[bi][bj][3][r]), lane);
+                                  (int32_t)(0.25f * acc[bi][bj][3][r]), l.lane);
         } else {
-          // Nearly every pair fails the threshold: decide that on the float
-          // sums without the IEEE divide, and only when some lane of the
-          // wavefront may pass run the exact epilogue (wave-uniform branch).
           const bool maybe =
               valid && kinship_may_pass(acc[bi][bj][2][r], acc[bi][bj][3][r],
                                         acc[bi][bj][1][r], acc[bi][bj][0][r], a.kin_threshold);
           if (__ballot(maybe) != 0)
             lean_epilogue_call(emit_ctx, valid, li, lj, (uint32_t)acc[bi][bj][2][r],
                                (uint32_t)acc[bi][bj][3][r], (uint32_t)acc[bi][bj][1][r],
-                               (uint32_t)acc[bi][bj][0][r], lane);
+                               (uint32_t)acc[bi][bj][0][r], l.lane);
         }
       }
     }
   }
+}
+
+// SPLIT = false: workgroup = one tile, all k-steps.
+// SPLIT = true ("stream-k" remainder): the launch's tiles x k-steps are one
+// line of work units cut into equal pieces, one per workgroup, so a remainder
+// of tiles that would leave most CUs idle for a whole tile time still fills
+// the chip.  A piece covers the end of one tile and/or the start of the next;
+// each partial result (exact integers) is parked in a scratch slab, and the
+// workgroup that delivers a tile's last part adds the others to its own and
+// runs the epilogue.
+// N4 = the four-product form on the nibble layout (four_product_loop()).
+// KIN = the dense-kinship form of the lean kernels (TiledArgs::dense_kin): the same k loop,
+// and an epilogue that stores the float32 kinship of EVERY pair instead of appending
+// records -- instantiations of their own, so that the epilogues of the others carry neither
+// its branch nor its registers (a run-time branch in the shared full epilogue was enough
+// for the five-product full form to reload a spilled value inside its k loop).  The
+// four-product one is the hot path; the five-product one serves contexts of variant 5 and
+// bitsets from 2^22 sites on.
+// The driver: take work -> per segment: hom_hom pass (FULL) -> k loop -> reduce parts
+// (SPLIT, a partial tile) -> epilogue.
+template <bool FULL, bool SPLIT, bool N4 = false, bool KIN = false>
+__global__ __launch_bounds__(256, 1) void king_mfma_kernel(const TiledArgs a) {
+  static_assert(!KIN || !FULL, "the dense-kinship form is a lean one");
+  extern __shared__ uint4 lds[];  // [NSTAGE][side][k-group][plane | slice][128]
+  Work work;
+  if (!take_work<SPLIT>(a, lds, &work)) return;  // uniform
+  const Lanes l = lanes_of_thread();
+  const NibbleMasks m = nibble_masks();
+  uint32_t lane16 = l.lane * 16;  // (five_product_loop())
+  Segment s;
+  while (next_segment<SPLIT>(a, &work, &s)) {
+    v16f hh5[2][2];  // full form: hom_hom of the wavefront's pairs (lean forms: never read)
+    v16f acc[2][2][kNQ];
+    if constexpr (FULL) hom_hom_pass<N4>(a, s, l, m, lds, hh5);
+    if constexpr (N4) four_product_loop<FULL>(a, s, l, m, lds, acc, hh5);
+    else five_product_loop<FULL>(a, s, l, m, lds, lane16, acc);
+    // The clamped repeats of the last stage must have landed before the
+    // workgroup's LDS goes away.
+    __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
+    if (SPLIT) __syncthreads();  // ... and nobody reads the stages any more
+
+    float4 *const park = FULL && !N4 ? park_slots(lds, l) : nullptr;
+    if (SPLIT && s.num_steps != tile_steps_of(a) &&
+        !reduce_parts<FULL, N4>(a, work.piece, s, l, lds, park, acc, hh5))
+      continue;
+
+    if constexpr (FULL) {
+      if (a.dense_counts == nullptr) emit_full_records<N4>(a, s, l, park, acc, hh5);
+      else store_counts<N4>(a, s, l, park, acc, hh5);
+    } else if constexpr (KIN) {
+      store_kin<N4>(a, s, l, acc);
+    } else {
+      lean_decide<N4>(a, s, l, acc);
+    }
+    if (SPLIT) __syncthreads();  // LDS is reused by the next piece
   }
-  if (SPLIT) __syncthreads();  // LDS is reused by the next piece
-  }  // pieces of this workgroup
 }
 
 // The launch's shape (king_launch_plan.h) in the device arguments.
@@ -1346,26 +1506,19 @@ namespace {
 hipError_t launch_form(bool full, bool split, bool nibble, bool kin, const TiledArgs &a,
                        const LaunchSwitches &sw, uint64_t blocks, uint32_t lds_bytes,
                        hipStream_t stream) {
-  if (kin) {
-    if (full) return hipErrorInvalidValue;
-    if (nibble)
-      return split ? launch_shape<false, true, true, true>(a, sw, blocks, lds_bytes, stream)
-                   : launch_shape<false, false, true, true>(a, sw, blocks, lds_bytes, stream);
-    return split ? launch_shape<false, true, false, true>(a, sw, blocks, lds_bytes, stream)
-                 : launch_shape<false, false, false, true>(a, sw, blocks, lds_bytes, stream);
-  }
-  if (nibble) {
-    if (split)
-      return full ? launch_shape<true, true, true>(a, sw, blocks, lds_bytes, stream)
-                  : launch_shape<false, true, true>(a, sw, blocks, lds_bytes, stream);
-    return full ? launch_shape<true, false, true>(a, sw, blocks, lds_bytes, stream)
-                : launch_shape<false, false, true>(a, sw, blocks, lds_bytes, stream);
-  }
-  if (split)
-    return full ? launch_shape<true, true>(a, sw, blocks, lds_bytes, stream)
-                : launch_shape<false, true>(a, sw, blocks, lds_bytes, stream);
-  return full ? launch_shape<true, false>(a, sw, blocks, lds_bytes, stream)
-              : launch_shape<false, false>(a, sw, blocks, lds_bytes, stream);
+  if (kin && full) return hipErrorInvalidValue;
+  using Launch = hipError_t (*)(const TiledArgs &, const LaunchSwitches &, uint64_t, uint32_t,
+                                hipStream_t);
+  static constexpr Launch kForms[2][2][2][2] = {  // [kin][nibble][split][full]
+      {{{launch_shape<false, false, false>, launch_shape<true, false, false>},
+        {launch_shape<false, true, false>, launch_shape<true, true, false>}},
+       {{launch_shape<false, false, true>, launch_shape<true, false, true>},
+        {launch_shape<false, true, true>, launch_shape<true, true, true>}}},
+      {{{launch_shape<false, false, false, true>, nullptr},
+        {launch_shape<false, true, false, true>, nullptr}},
+       {{launch_shape<false, false, true, true>, nullptr},
+        {launch_shape<false, true, true, true>, nullptr}}}};
+  return kForms[kin][nibble][split][full](a, sw, blocks, lds_bytes, stream);
 }
 
 // ONE launch of the four-product kernel's lean form with `grid` workgroups that stride over
