@@ -6,8 +6,9 @@ is loaded on first use and there is no CPU fallback.
 """
 from .api import (DEFAULT_KIN_THRESHOLD, DEFAULT_MAX_RESULTS,  # noqa: F401
                   KING_COUNTS_DTYPE, KING_RESULT_DTYPE, CukingError,
-                  KingContext, ResourceExhaustedError, Submatrix,
-                  bytes_per_pair, device_count, kin_matrix, new_host_bitset, pack_host,
+                  KingContext, KinSummary, ResourceExhaustedError, Submatrix,
+                  bytes_per_pair, device_count, kin_matrix, kin_summary, new_host_bitset,
+                  pack_host,
                   padded_sites, sort_results, synth_model_number, synth_models,
                   words_per_sample)
 

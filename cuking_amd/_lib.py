@@ -24,6 +24,13 @@ KERNEL_STREAM = 1
 KIN_UPPER = 0
 KIN_SYMMETRIC = 1
 
+KIN_BINS_MAX = 4096
+
+
+class CKinBins(C.Structure):
+    """cuking_kin_bins: the histogram of a kinship summary."""
+    _fields_ = [("lo", C.c_float), ("hi", C.c_float), ("num_bins", C.c_uint32)]
+
 
 class CukingError(RuntimeError):
     def __init__(self, status: int, message: str):
@@ -41,6 +48,7 @@ class CSubmatrix(C.Structure):
 _u32, _u64, _i64, _f32 = C.c_uint32, C.c_uint64, C.c_int64, C.c_float
 _vp, _sz, _int = C.c_void_p, C.c_size_t, C.c_int
 _SM = C.POINTER(CSubmatrix)
+_BINS = C.POINTER(CKinBins)
 
 # name -> (restype, argtypes); every symbol include/cuking_amd.h declares.
 SIGNATURES = {
@@ -109,6 +117,13 @@ SIGNATURES = {
     "cuking_compute_kin_matrix": (_int, [_vp, _SM, _u32, _vp, _vp, _u64, _u32, _vp]),
     "cuking_compute_kin_matrix_tiles": (_int, [_vp, _SM, _u32, _vp, _u64, _u64, _vp, _u64,
                                                _u32, _vp]),
+    "cuking_kin_hist_slots": (_u32, [_u32]),
+    "cuking_kin_bin_slot": (_u32, [_BINS, _f32]),
+    "cuking_kin_best_key": (_u64, [_f32, _u32]),
+    "cuking_kin_best_decode": (_u32, [_u64, C.POINTER(_f32), C.POINTER(_u32)]),
+    "cuking_compute_kin_summary": (_int, [_vp, _SM, _u32, _vp, _BINS, _vp, _vp, _vp]),
+    "cuking_compute_kin_summary_tiles": (_int, [_vp, _SM, _u32, _vp, _u64, _u64, _BINS, _vp,
+                                                _vp, _vp]),
     "cuking_sort_results": (None, [_vp, _sz]),
     "cuking_timing_enable": (_int, [_vp, _int]),
     "cuking_timing_reset": (_int, [_vp]),

@@ -336,6 +336,53 @@ class KingContext:
                 *args, tile_range[0], tile_range[1], *tail))
         return out
 
+    def kin_summary(self, submatrix: Submatrix, words_per_sample: int, bit_sets,
+                    lo: float = -1.0, hi: float = 0.5, bins: int = 1536, hist=None,
+                    best=None, tile_range=None, stream=None) -> "KinSummary":
+        """Kinship summary (cuking_compute_kin_summary): the histogram of the float32
+        kinship of every pair of the block and every sample's nearest relative,
+        without the matrix and without a threshold.  Does not synchronise; returns a
+        ``KinSummary`` holding the two device tensors.  ``hist`` (``bins + 3`` int64)
+        and ``best`` (``NumSamples()`` int64) are views of the library's uint64 data;
+        the call ACCUMULATES into them (counts add, keys take the maximum), so the
+        tensors of an earlier summary may be passed back in, e.g. for the tile
+        ranges of one block.  Without them zeroed ones are allocated.
+        ``tile_range``: only the tiles [begin, end) of the block's enumeration."""
+        import torch
+        self._check_bits(submatrix, words_per_sample, bit_sets)
+        if isinstance(bins, bool) or int(bins) != bins or not 1 <= bins <= _lib.KIN_BINS_MAX:
+            raise ValueError(f"bins must be an integer in [1, {_lib.KIN_BINS_MAX}]")
+        lo, hi = float(np.float32(lo)), float(np.float32(hi))
+        if not (np.isfinite(lo) and np.isfinite(hi) and lo < hi):
+            raise ValueError("the histogram needs finite bounds with lo < hi")
+        dev = f"cuda:{self.device}"
+
+        def output(t, name, length):
+            if t is None:
+                return torch.zeros(length, dtype=torch.int64, device=dev)
+            if not t.is_cuda or t.device.index != self.device:
+                raise ValueError(f"{name} must live on this context's GPU")
+            if t.dtype != torch.int64:
+                raise ValueError(f"{name} must be an int64 tensor (a view of the uint64 data)")
+            if t.dim() != 1 or t.numel() != length or not t.is_contiguous():
+                raise ValueError(f"{name} must be a contiguous vector of {length} entries, "
+                                 f"not {tuple(t.shape)}")
+            return t
+        hist = output(hist, "hist", int(bins) + 3)
+        best = output(best, "best", submatrix.NumSamples())
+        summary = KinSummary(hist, best, lo, hi, int(bins), submatrix, self.device)
+        if submatrix.NumRows() == 0 or submatrix.NumCols() == 0:
+            return summary
+        cbins = _lib.CKinBins(lo, hi, int(bins))
+        args = (self.handle, C.byref(submatrix.c), words_per_sample, bit_sets.data_ptr())
+        tail = (C.byref(cbins), hist.data_ptr(), best.data_ptr(), _stream_handle(stream))
+        if tile_range is None:
+            check(self.lib.cuking_compute_kin_summary(*args, *tail))
+        else:
+            check(self.lib.cuking_compute_kin_summary_tiles(
+                *args, tile_range[0], tile_range[1], *tail))
+        return summary
+
     def run(self, submatrix: Submatrix, words_per_sample: int, bit_sets,
             kin_threshold: float = DEFAULT_KIN_THRESHOLD,
             max_results: int = DEFAULT_MAX_RESULTS, tile_range=None,
@@ -434,14 +481,72 @@ class KingContext:
                 f"{sm.NumSamples()} x {wps}")
 
 
+class KinSummary:
+    """What ``KingContext.kin_summary`` returns: the device tensors ``hist`` (``bins + 3``
+    slots: UNDER, the bins, OVER, NAN) and ``best`` (one key per stored sample of the
+    block, rows first, then columns), int64 views of uint64 data, and ``(lo, hi, bins)``.
+    The accessors wait for the device."""
+
+    def __init__(self, hist, best, lo: float, hi: float, bins: int, submatrix: Submatrix,
+                 device: int):
+        self.hist, self.best = hist, best
+        self.lo, self.hi, self.bins = lo, hi, bins
+        self.submatrix, self.device = submatrix, device
+
+    def _host(self, t) -> np.ndarray:
+        import torch
+        torch.cuda.synchronize(self.device)
+        return t.cpu().numpy().view(np.uint64)
+
+    def counts(self) -> np.ndarray:
+        """The ``bins + 3`` slot counts as uint64."""
+        return self._host(self.hist)
+
+    def edges(self) -> np.ndarray:
+        """The ``bins + 1`` NOMINAL bin edges (float64); a kinship within a float32
+        rounding of one may be counted on either side (cuking_kin_bin_slot decides)."""
+        return self.lo + (self.hi - self.lo) * np.arange(self.bins + 1) / self.bins
+
+    def keys(self) -> np.ndarray:
+        """The nearest-relative keys as uint64 (0 = no partner with a defined kinship)."""
+        return self._host(self.best)
+
+    def nearest(self):
+        """``(kin float32, partner int64)`` per stored sample: the largest kinship the
+        sample has with any partner inside the block and that partner's GLOBAL index (the
+        lowest among equals); NaN and -1 where no pair of the sample has a defined kinship."""
+        keys = self.keys()
+        ordered = (keys >> np.uint64(32)).astype(np.uint32)
+        bits = np.where(ordered & np.uint32(0x80000000), ordered ^ np.uint32(0x80000000),
+                        ~ordered).astype(np.uint32)
+        kin = np.where(keys != 0, bits.view(np.float32), np.float32("nan")).astype(np.float32)
+        partner = np.where(keys != 0, (~keys & np.uint64(0xFFFFFFFF)).astype(np.int64),
+                           np.int64(-1))
+        return kin, partner
+
+    def count_at_least(self, b: int) -> int:
+        """Pairs in bin ``b`` (0-based) and above, OVER included, NAN not: the pairs whose
+        kinship is at least the nominal edge ``edges()[b]``."""
+        if not 0 <= b <= self.bins:
+            raise ValueError(f"bin {b} outside [0, {self.bins}]")
+        return int(self.counts()[1 + b:self.bins + 2].sum())
+
+
 def kin_matrix(ctx: KingContext, submatrix: Submatrix, words_per_sample: int, bit_sets,
                **kwargs):
     """``ctx.kin_matrix(...)``: the dense float32 kinship matrix of a block."""
     return ctx.kin_matrix(submatrix, words_per_sample, bit_sets, **kwargs)
 
 
+def kin_summary(ctx: KingContext, submatrix: Submatrix, words_per_sample: int, bit_sets,
+                **kwargs) -> KinSummary:
+    """``ctx.kin_summary(...)``: all-pairs kinship histogram and nearest relatives."""
+    return ctx.kin_summary(submatrix, words_per_sample, bit_sets, **kwargs)
+
+
 __all__ = [
-    "Submatrix", "KingContext", "kin_matrix", "KING_RESULT_DTYPE", "KING_COUNTS_DTYPE",
+    "Submatrix", "KingContext", "kin_matrix", "kin_summary", "KinSummary",
+    "KING_RESULT_DTYPE", "KING_COUNTS_DTYPE",
     "ResourceExhaustedError", "CukingError", "padded_sites",
     "words_per_sample", "bytes_per_pair", "new_host_bitset", "pack_host",
     "sort_results", "device_count", "synth_models", "synth_model_number",

@@ -63,7 +63,7 @@ def _newer(target: Path, deps) -> bool:
 def build_library(force: bool = False, save_temps: bool = False) -> Path:
     srcs = [CSRC / s for s in HIP_SOURCES + HOST_ABI_SOURCES]
     deps = srcs + [CSRC / "king_common.h", CSRC / "king_device.h", CSRC / "king_host.h",
-                   CSRC / "king_launch_plan.h",
+                   CSRC / "king_launch_plan.h", CSRC / "king_kin_summary.h",
                    CSRC / "king_submatrix.h", INCLUDE / "cuking_amd.h",
                    Path(__file__)]
     extra = os.environ.get("CUKING_EXTRA_HIPFLAGS", "").split()
@@ -170,7 +170,8 @@ def check_mfma_loops(asm_path: Path, verbose: bool = False):
     import re
 
     def label(f):
-        m = re.match(r"_ZN6cuking12_GLOBAL__N_116king_mfma_kernelILb(\d)ELb(\d)ELb(\d)ELb(\d)", f)
+        # (KIN is an int: 0 records, 1 dense matrix, 2 summary)
+        m = re.match(r"_ZN6cuking12_GLOBAL__N_116king_mfma_kernelILb(\d)ELb(\d)ELb(\d)ELi(\d)E", f)
         return (f"king_mfma_kernel<FULL={m.group(1)}, SPLIT={m.group(2)}, N4={m.group(3)}, "
                 f"KIN={m.group(4)}>")
     return check_dma_loops(asm_path, "king_mfma_kernel",

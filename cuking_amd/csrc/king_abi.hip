@@ -12,6 +12,7 @@
 
 #include "king_common.h"
 #include "king_host.h"
+#include "king_kin_summary.h"
 
 using namespace cuking;
 
@@ -439,6 +440,9 @@ struct Outputs {
   float *kin;
   uint64_t kin_ld;
   uint32_t kin_flags;
+  // kinship summary (TiledArgs::sum_hist / sum_best): every pair's kinship reduced, no records
+  uint64_t *sum_hist, *sum_best;
+  cuking_kin_bins sum_bins;
 };
 cuking_status launch_args(cuking_ctx *ctx, hipStream_t stream, const cuking_submatrix &sm,
                           uint32_t words_per_sample, const uint64_t *d_bit_sets,
@@ -462,6 +466,13 @@ cuking_status launch_args(cuking_ctx *ctx, hipStream_t stream, const cuking_subm
   a.dense_kin = out.kin;
   a.kin_ld = out.kin_ld;
   a.kin_diag = (out.kin != nullptr && (out.kin_flags & CUKING_KIN_SYMMETRIC)) ? 1u : 0u;
+  a.sum_hist = reinterpret_cast<unsigned long long *>(out.sum_hist);
+  a.sum_best = reinterpret_cast<unsigned long long *>(out.sum_best);
+  if (out.sum_hist != nullptr) {
+    a.sum_lo = out.sum_bins.lo;
+    a.sum_scale = kin_bin_scale(out.sum_bins);  // (once per call, on the host)
+    a.sum_bins = out.sum_bins.num_bins;
+  }
   a.rect_row_stride = 1;
   a.bits = d_bit_sets;
   a.words_per_sample = words_per_sample;
@@ -771,15 +782,20 @@ cuking_status run_tiled(cuking_ctx *ctx, const cuking_submatrix &sm,
   // (contexts of variant 6 and 7: the four-product kernel, the latter on the quadrants of
   // its tiles; variant 5 and wide bitsets: the five-product kernel), on a layout that is
   // never sorted; the VALU kernels store it from their full form.
+  // A kinship summary: the same, with an epilogue that reduces the float instead of storing
+  // it; matrix-core kernels only (the entry points have refused every other context).
+  const bool sum = out.sum_hist != nullptr || out.sum_best != nullptr;
   const bool kin = out.kin != nullptr;
   const int kv = effective_variant(ctx, words_per_sample);
-  const bool kin_mfma = kin && is_mfma_variant(kv);
+  if (sum && !is_mfma_variant(kv))
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "kinship summary: no matrix-core kernel");
+  const bool kin_mfma = (kin || sum) && is_mfma_variant(kv);
   const bool full = !kin_mfma && use_full_counts(ctx, kin_threshold, out.counts != nullptr || kin,
                                                words_per_sample);
   const LaunchSwitches sw = launch_switches(ctx, words_per_sample, full, kin_threshold);
   // (where the filter runs the four-product kernel's codes may stay unconverted)
   cuking_status st = prepare(ctx, sm, words_per_sample, d_bit_sets, stream, &geo, &tiles,
-                             !sw.filter_runs, kin);
+                             !sw.filter_runs, kin || sum);
   if (st != CUKING_OK) return st;
   const uint64_t n_tiles = total_tiles(tiles);
   if (whole) {
@@ -805,7 +821,8 @@ cuking_status run_tiled(cuking_ctx *ctx, const cuking_submatrix &sm,
     uint64_t units = tile_end - tile_begin;
     if (tiled_variant(ctx->variant).tile == kFilterTile) to_quadrants(&a, &units);
     a.perm = nullptr;  // (the identity: prepare() above did not sort)
-    HIP_TRY(launch_mfma_kin(kv != kMfmaVariant, a, sw, units, stream));
+    if (sum) HIP_TRY(launch_mfma_summary(kv != kMfmaVariant, a, sw, units, stream));
+    else HIP_TRY(launch_mfma_kin(kv != kMfmaVariant, a, sw, units, stream));
   } else {
     HIP_TRY(launch_planned(ctx, words_per_sample, full, a, sw, tile_end - tile_begin, stream));
   }
@@ -1606,6 +1623,95 @@ cuking_status cuking_compute_kin_matrix_tiles(cuking_ctx *ctx, const cuking_subm
   return run_tiled(ctx, *sm, words_per_sample, d_bit_sets, tile_begin, tile_end, false, 0.f,
                    {0, nullptr, nullptr, nullptr, nullptr, d_kin, ld, flags},
                    (hipStream_t)stream);
+}
+
+// The checks the two kinship-summary entry points share, in front of anything that touches
+// a device.
+static cuking_status check_summary_args(const cuking_ctx *ctx, const cuking_submatrix *sm,
+                                        uint32_t words_per_sample, const uint64_t *d_bit_sets,
+                                        const cuking_kin_bins *bins, const uint64_t *d_hist,
+                                        const uint64_t *d_best, bool tile_range,
+                                        uint64_t tile_begin, uint64_t tile_end) {
+  cuking_status st = check_compute_args(sm, words_per_sample, d_bit_sets);
+  if (st != CUKING_OK) return st;
+  if (d_hist == nullptr && d_best == nullptr)
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT,
+                       "kinship summary: both outputs (histogram and nearest relatives) are null");
+  if (d_hist != nullptr) {
+    if (bins == nullptr)
+      return cuking_fail(CUKING_ERR_INVALID_ARGUMENT,
+                         "kinship summary: a histogram needs bins (null bins pointer)");
+    if (bins->num_bins == 0 || bins->num_bins > CUKING_KIN_BINS_MAX)
+      return cuking_fail(CUKING_ERR_INVALID_ARGUMENT,
+                         "kinship summary: num_bins %u outside [1, %u]", bins->num_bins,
+                         CUKING_KIN_BINS_MAX);
+    if (!kin_bins_valid(*bins))
+      return cuking_fail(CUKING_ERR_INVALID_ARGUMENT,
+                         "kinship summary: histogram bounds must be finite with lo < hi "
+                         "(lo %g, hi %g)", (double)bins->lo, (double)bins->hi);
+  }
+  if (tile_range && tile_begin > tile_end)
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "tile range [%llu, %llu) is reversed",
+                       (unsigned long long)tile_begin, (unsigned long long)tile_end);
+  if (ctx == nullptr) return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "null context");
+  const bool empty = sm_num_rows(*sm) == 0 || sm_num_cols(*sm) == 0;
+  // (run_tiled checks the range as well, but only behind the conversion: this call refuses
+  //  a bad range before a device is touched)
+  if (tile_range) {
+    const uint64_t n_tiles = empty ? 0 : cuking_num_tiles(ctx, sm);
+    if (tile_end > n_tiles)
+      return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "tile range [%llu, %llu) outside [0, %llu)",
+                         (unsigned long long)tile_begin, (unsigned long long)tile_end,
+                         (unsigned long long)n_tiles);
+  }
+  if (ctx->kernel != CUKING_KERNEL_TILED || !is_mfma_variant(ctx->variant))
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT,
+                       "kinship summary: served by contexts of the tiled kernel with variant 5, "
+                       "6 or 7 (the matrix-core kernels) only; the VALU variants and the stream "
+                       "kernel have no summary form");
+  if (!is_mfma_variant(effective_variant(ctx, words_per_sample)))
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT,
+                       "kinship summary: bitsets from 2^24 sites on are not served (the "
+                       "matrix-core kernels count in float32)");
+  return CUKING_OK;
+}
+
+// What the two entry points share behind their checks: `whole` = every tile of the block.
+static cuking_status run_summary(cuking_ctx *ctx, const cuking_submatrix *sm,
+                                 uint32_t words_per_sample, const uint64_t *d_bit_sets,
+                                 bool whole, uint64_t tile_begin, uint64_t tile_end,
+                                 const cuking_kin_bins *bins, uint64_t *d_hist, uint64_t *d_best,
+                                 void *stream) {
+  cuking_status st = check_summary_args(ctx, sm, words_per_sample, d_bit_sets, bins, d_hist,
+                                        d_best, !whole, tile_begin, tile_end);
+  if (st != CUKING_OK) return st;
+  if (sm_num_rows(*sm) == 0 || sm_num_cols(*sm) == 0) return CUKING_OK;
+  st = bind(ctx);
+  if (st != CUKING_OK) return st;
+  Outputs out = {};
+  out.sum_hist = d_hist;
+  out.sum_best = d_best;
+  if (d_hist != nullptr) out.sum_bins = *bins;
+  return run_tiled(ctx, *sm, words_per_sample, d_bit_sets, tile_begin, tile_end, whole, 0.f, out,
+                   (hipStream_t)stream);
+}
+
+cuking_status cuking_compute_kin_summary(cuking_ctx *ctx, const cuking_submatrix *sm,
+                                         uint32_t words_per_sample, const uint64_t *d_bit_sets,
+                                         const cuking_kin_bins *bins, uint64_t *d_hist,
+                                         uint64_t *d_best, void *stream) {
+  return run_summary(ctx, sm, words_per_sample, d_bit_sets, true, 0, 0, bins, d_hist, d_best,
+                     stream);
+}
+
+cuking_status cuking_compute_kin_summary_tiles(cuking_ctx *ctx, const cuking_submatrix *sm,
+                                               uint32_t words_per_sample,
+                                               const uint64_t *d_bit_sets, uint64_t tile_begin,
+                                               uint64_t tile_end, const cuking_kin_bins *bins,
+                                               uint64_t *d_hist, uint64_t *d_best,
+                                               void *stream) {
+  return run_summary(ctx, sm, words_per_sample, d_bit_sets, false, tile_begin, tile_end, bins,
+                     d_hist, d_best, stream);
 }
 
 // ---- timing ---------------------------------------------------------------

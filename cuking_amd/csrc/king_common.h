@@ -283,6 +283,15 @@ struct TiledArgs {
   float *dense_kin;
   uint64_t kin_ld;
   uint32_t kin_diag;
+  // Kinship summary (cuking_compute_kin_summary; again at the END): the matrix-core kernels'
+  // summary form (king_mfma.hip summarise_kin, instantiations of their own, unsorted layout
+  // like dense_kin) adds every pair's kinship to the histogram sum_hist (sum_bins + 3 slots;
+  // slot rule king_kin_summary.h with sum_lo and sum_scale = the host's (float)bins /
+  // (hi - lo)) and raises the two samples' nearest-relative keys in sum_best (indexed by
+  // stored sample: rows, then an off-diagonal block's columns).  Either may be null.
+  unsigned long long *sum_hist, *sum_best;
+  float sum_lo, sum_scale;
+  uint32_t sum_bins;
 };
 
 // Prefix statistics: the k-steps (of 256 sites) a check may sit behind, as shares of the
@@ -506,6 +515,11 @@ hipError_t launch_mfma(bool full, bool nibble, const TiledArgs &args, const Laun
 // (chunking, XCD order, dynamic tail, remainder split).
 hipError_t launch_mfma_kin(bool nibble, const TiledArgs &args, const LaunchSwitches &sw,
                            uint64_t num_tiles, hipStream_t stream);
+// The matrix-core kernels' kinship-summary form (TiledArgs::sum_hist / sum_best; king_mfma.hip,
+// summarise_kin): the same lean k loops and launch plan, and an epilogue that reduces the
+// kinship of a tile's pairs in LDS instead of storing it.
+hipError_t launch_mfma_summary(bool nibble, const TiledArgs &args, const LaunchSwitches &sw,
+                               uint64_t num_tiles, hipStream_t stream);
 // Symmetric fill of an n x n kinship matrix whose upper triangle (and diagonal) is there:
 // kin[j * ld + i] = kin[i * ld + j] for i < j, tile-wise through LDS, reads and writes
 // coalesced.  Runs behind the pair kernel on the same stream.

@@ -16,6 +16,7 @@
 
 #include "../host/schedule.h"
 #include "king_submatrix.h"
+#include "king_kin_summary.h"
 
 using namespace cuking;
 
@@ -321,6 +322,25 @@ uint32_t cuking_schedule_staged_steps(uint32_t num_samples, uint32_t tile, uint3
     o[5] = steps[k].row_step;
   }
   return (uint32_t)steps.size();
+}
+
+// ---- kinship summary: the definitions of king_kin_summary.h, as the kernel uses them -----
+uint32_t cuking_kin_hist_slots(uint32_t num_bins) { return kin_hist_slots(num_bins); }
+
+uint32_t cuking_kin_bin_slot(const cuking_kin_bins *bins, float kin) {
+  if (bins == nullptr || !kin_bins_valid(*bins)) return 0xFFFFFFFFu;
+  return kin_bin_slot(bins->lo, kin_bin_scale(*bins), bins->num_bins, kin);
+}
+
+uint64_t cuking_kin_best_key(float kin, uint32_t partner) { return kin_best_key(kin, partner); }
+
+uint32_t cuking_kin_best_decode(uint64_t key, float *kin, uint32_t *partner) {
+  float k = 0.f;
+  uint32_t p = 0;
+  if (!kin_best_decode(key, &k, &p)) return 0;
+  if (kin != nullptr) *kin = k;
+  if (partner != nullptr) *partner = p;
+  return 1;
 }
 
 void cuking_sort_results(cuking_result *results, size_t num_results) {

@@ -43,7 +43,8 @@
 //     reduce_parts       park and sum the parts of a cut-up tile                 (SPLIT)
 //     emit_full_records  two-sweep reservation and store         (FULL, no dense_counts)
 //     store_counts       the six counts of every pair            (FULL, dense_counts)
-//     store_kin          float32 kinship of every pair                           (KIN)
+//     store_kin          float32 kinship of every pair                    (KIN = matrix)
+//     summarise_kin      histogram and nearest-relative keys of a tile    (KIN = summary)
 //     lean_decide        threshold on the float sums, exact epilogue out of line (the rest)
 // A k loop's statements are macros over its function's locals, defined and undefined
 // inside that function.
@@ -51,6 +52,7 @@
 
 #include "king_common.h"
 #include "king_device.h"
+#include "king_kin_summary.h"
 
 // The LDS-DMA statements below write M0 and say so in their clobber lists; the
 // compiler notes that it keeps no value of its own there (M0 is reserved).
@@ -73,6 +75,12 @@ constexpr int kPiecesPerWave = 4;            // 16 x 1 KiB per stage, 4 wavefron
 // 40k x 100k 95.2 -> 94.7 ms, configs[1] (bitset in the Infinity Cache) equal
 // (archive/experiments/exp25.sh).
 constexpr int kStagesPaired = 10;
+// The summary form's epilogue (summarise_kin()) reuses the stages: 256 keys of 8 bytes and the
+// largest histogram's counts.  Both lean forms have 160 KiB.
+constexpr uint32_t kMfmaSummaryLdsBytes = 2 * kTile * 8 + (CUKING_KIN_BINS_MAX + 3) * 4;
+static_assert(kMfmaSummaryLdsBytes <= kStagesPaired * kStageU4 * 16 &&
+                  kMfmaSummaryLdsBytes <= kMfmaN4LdsBytes,
+              "the summary's LDS fits the stages of either lean form");
 
 // v_bitop3_b32 truth tables over (het, hom_var, mask), index = 4 het + 2 hom + mask.
 constexpr int kA = 0x08;  // hom-alt:  ~het &  hom & mask
@@ -1315,9 +1323,23 @@ __device__ __forceinline__ void store_counts(const TiledArgs &a, const Segment &
 
 // Dense kinship (KIN): the lean epilogue's expression for every pair (four products:
 // lean_epilogue_pair_n4's, on the exact integers hi, hj, num = hi + hj - 2 dd +
-// 2 q), with the IEEE divide -- and one store.
+// 2 q), with the IEEE divide (pair_kin(), which the summary form shares) -- and one store.
 // Column = lane & 31: the 32 lanes of a half-wave write 128 contiguous bytes of
 // matrix row li.  (An unsorted layout: plane index = stored sample.)
+template <bool N4>
+__device__ __forceinline__ float pair_kin(const v16f (&acc)[2][2][kNQ], int bi, int bj, int r) {
+  if constexpr (N4) {
+    const uint32_t het_i = (uint32_t)(2.f * acc[bi][bj][0][r]);
+    const uint32_t het_j = (uint32_t)(2.f * acc[bi][bj][1][r]);
+    const int32_t num = (int32_t)(het_i + het_j) - 2 * (int32_t)acc[bi][bj][2][r] +
+                        2 * (int32_t)(0.25f * acc[bi][bj][3][r]);
+    return 0.5f + (float)num / (4.f * (float)(het_i < het_j ? het_i : het_j));
+  } else {
+    // (five products: the accumulators are the reference's own four sums)
+    return king_kinship((uint32_t)acc[bi][bj][2][r], (uint32_t)acc[bi][bj][3][r],
+                        (uint32_t)acc[bi][bj][1][r], (uint32_t)acc[bi][bj][0][r]);
+  }
+}
 template <bool N4>
 __device__ __forceinline__ void store_kin(const TiledArgs &a, const Segment &s, const Lanes &l,
                                           const v16f (&acc)[2][2][kNQ]) {
@@ -1332,22 +1354,75 @@ __device__ __forceinline__ void store_kin(const TiledArgs &a, const Segment &s, 
         const uint32_t li = pair_row(o, l, bi, r);
         // (symmetric output: the diagonal as well)
         const bool valid = pair_valid(a, li, lj, a.kin_diag);
-        float kin;
-        if constexpr (N4) {
-          const uint32_t het_i = (uint32_t)(2.f * acc[bi][bj][0][r]);
-          const uint32_t het_j = (uint32_t)(2.f * acc[bi][bj][1][r]);
-          const int32_t num = (int32_t)(het_i + het_j) - 2 * (int32_t)acc[bi][bj][2][r] +
-                              2 * (int32_t)(0.25f * acc[bi][bj][3][r]);
-          kin = 0.5f + (float)num / (4.f * (float)(het_i < het_j ? het_i : het_j));
-        } else {
-          // (five products: the accumulators are the reference's own four sums)
-          kin = king_kinship((uint32_t)acc[bi][bj][2][r], (uint32_t)acc[bi][bj][3][r],
-                             (uint32_t)acc[bi][bj][1][r], (uint32_t)acc[bi][bj][0][r]);
-        }
+        const float kin = pair_kin<N4>(acc, bi, bj, r);
         if (valid) a.dense_kin[(uint64_t)li * a.kin_ld + lj] = kin;
       }
     }
   }
+}
+
+// Kinship summary (KIN = summary): pair_kin() of every valid pair, REDUCED instead of stored.
+// The tile's histogram (uint32: a tile has 16,384 pairs) and its 128 row + 128 column
+// nearest-relative keys live in the LDS the stages no longer need: [row keys][column keys]
+// [sum_bins + 3 counts].  A lane first reduces in registers what it holds -- the maximum over
+// the two block columns of each of its 32 rows, the maximum over the 32 rows of each of its
+// two columns -- then LDS atomics, then the workgroup adds the non-zero counts and raises the
+// non-zero keys with one 64-bit global atomic each.  Slot and keys: king_kin_summary.h.
+// Barriers on BOTH sides, whatever the mode: the phase zeroes LDS other wavefronts may still
+// read operands from, and the next segment's LDS-DMA overwrites what it reads at its end.
+// (The caller's vmcnt(0) comes first: every wavefront's own requests have landed.)
+template <bool N4>
+__device__ __forceinline__ void summarise_kin(const TiledArgs &a, const Segment &s, const Lanes &l,
+                                              uint4 *const lds, const v16f (&acc)[2][2][kNQ]) {
+  unsigned long long *const keys = reinterpret_cast<unsigned long long *>(lds);
+  uint32_t *const hist = reinterpret_cast<uint32_t *>(keys + 2 * kTile);
+  const bool want_hist = a.sum_hist != nullptr, want_best = a.sum_best != nullptr;  // uniform
+  const uint32_t slots = want_hist ? kin_hist_slots(a.sum_bins) : 0u;
+  __syncthreads();  // nobody reads the stages any more
+  for (uint32_t k = threadIdx.x; k < 2 * kTile; k += 256) keys[k] = 0;
+  for (uint32_t k = threadIdx.x; k < slots; k += 256) hist[k] = 0;
+  __syncthreads();
+  const PairOrigin o = pair_origin(s, l);
+  unsigned long long col_key[2] = {0, 0};
+#pragma unroll
+  for (int bi = 0; bi < 2; ++bi) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const uint32_t li = pair_row(o, l, bi, r);
+      unsigned long long row_key = 0;
+#pragma unroll
+      for (int bj = 0; bj < 2; ++bj) {
+        const uint32_t lj = pair_col(o, l, bj);
+        if (pair_valid(a, li, lj)) {
+          const float kin = pair_kin<N4>(acc, bi, bj, r);
+          if (want_hist) atomicAdd(&hist[kin_bin_slot(a.sum_lo, a.sum_scale, a.sum_bins, kin)], 1u);
+          const unsigned long long kr = kin_best_key(kin, a.j_begin + lj);
+          const unsigned long long kc = kin_best_key(kin, a.i_begin + li);
+          row_key = kr > row_key ? kr : row_key;
+          col_key[bj] = kc > col_key[bj] ? kc : col_key[bj];
+        }
+      }
+      if (want_best && row_key != 0) atomicMax(&keys[l.wy * 64 + bi * 32 + c_row(r, l.g)], row_key);
+    }
+  }
+#pragma unroll
+  for (int bj = 0; bj < 2; ++bj)
+    if (want_best && col_key[bj] != 0)
+      atomicMax(&keys[kTile + l.wx * 64 + bj * 32 + l.lr], col_key[bj]);
+  __syncthreads();
+  for (uint32_t k = threadIdx.x; k < slots; k += 256) {
+    const uint32_t n = hist[k];
+    if (n != 0) atomicAdd(&a.sum_hist[k], (unsigned long long)n);
+  }
+  if (want_best) {
+    // thread t: row t of the tile, or column t - 128 (a non-zero key: a sample of the block)
+    const uint32_t t = threadIdx.x, x = t & (kTile - 1);
+    const unsigned long long key = keys[t];
+    const uint32_t sample = t < kTile ? s.tr * kTile + x
+                                      : (a.geo.diag ? 0u : a.geo.num_rows) + s.tc * kTile + x;
+    if (key != 0) atomicMax(&a.sum_best[sample], key);
+  }
+  __syncthreads();  // the next segment's requests overwrite this
 }
 
 // Lean form, records.  Nearly every pair fails the threshold: decide that on the float
@@ -1402,18 +1477,20 @@ __device__ __forceinline__ void lean_decide(const TiledArgs &a, const Segment &s
 // workgroup that delivers a tile's last part adds the others to its own and
 // runs the epilogue.
 // N4 = the four-product form on the nibble layout (four_product_loop()).
-// KIN = the dense-kinship form of the lean kernels (TiledArgs::dense_kin): the same k loop,
-// and an epilogue that stores the float32 kinship of EVERY pair instead of appending
-// records -- instantiations of their own, so that the epilogues of the others carry neither
+// KIN = kKinMatrix: the dense-kinship form of the lean kernels (TiledArgs::dense_kin): the same
+// k loop, and an epilogue that stores the float32 kinship of EVERY pair instead of appending
+// records; kKinSummary: the summary form (TiledArgs::sum_hist / sum_best), whose epilogue
+// reduces that kinship instead (summarise_kin()) -- instantiations of their own, so that the epilogues of the others carry neither
 // its branch nor its registers (a run-time branch in the shared full epilogue was enough
 // for the five-product full form to reload a spilled value inside its k loop).  The
 // four-product one is the hot path; the five-product one serves contexts of variant 5 and
 // bitsets from 2^22 sites on.
 // The driver: take work -> per segment: hom_hom pass (FULL) -> k loop -> reduce parts
 // (SPLIT, a partial tile) -> epilogue.
-template <bool FULL, bool SPLIT, bool N4 = false, bool KIN = false>
+constexpr int kRecords = 0, kKinMatrix = 1, kKinSummary = 2;  // KIN
+template <bool FULL, bool SPLIT, bool N4 = false, int KIN = kRecords>
 __global__ __launch_bounds__(256, 1) void king_mfma_kernel(const TiledArgs a) {
-  static_assert(!KIN || !FULL, "the dense-kinship form is a lean one");
+  static_assert(KIN == kRecords || !FULL, "the dense-kinship forms are lean ones");
   extern __shared__ uint4 lds[];  // [NSTAGE][side][k-group][plane | slice][128]
   Work work;
   if (!take_work<SPLIT>(a, lds, &work)) return;  // uniform
@@ -1440,8 +1517,10 @@ __global__ __launch_bounds__(256, 1) void king_mfma_kernel(const TiledArgs a) {
     if constexpr (FULL) {
       if (a.dense_counts == nullptr) emit_full_records<N4>(a, s, l, park, acc, hh5);
       else store_counts<N4>(a, s, l, park, acc, hh5);
-    } else if constexpr (KIN) {
+    } else if constexpr (KIN == kKinMatrix) {
       store_kin<N4>(a, s, l, acc);
+    } else if constexpr (KIN == kKinSummary) {
+      summarise_kin<N4>(a, s, l, lds, acc);
     } else {
       lean_decide<N4>(a, s, l, acc);
     }
@@ -1459,7 +1538,7 @@ void set_shape(TiledArgs *a, const WholeShape &s) {
 
 // Whole tiles [args.tile_begin, + num_blocks) in as many launches as the block limit asks
 // for, or (SPLIT) the one launch of args.split_whole whole tiles + args.split_wgs pieces.
-template <bool FULL, bool SPLIT, bool N4 = false, bool KIN = false>
+template <bool FULL, bool SPLIT, bool N4 = false, int KIN = kRecords>
 hipError_t launch_shape(const TiledArgs &args, const LaunchSwitches &sw, uint64_t num_blocks,
                         uint32_t lds_bytes, hipStream_t stream) {
   constexpr auto kernel = king_mfma_kernel<FULL, SPLIT, N4, KIN>;
@@ -1501,23 +1580,27 @@ size_t mfma_split_scratch_bytes(uint32_t wgs) {
 size_t mfma_split_counter_bytes(uint32_t wgs) { return split_counter_bytes(wgs); }
 
 namespace {
-// launch_shape<FULL, SPLIT, N4, KIN> by run-time flags (kin: the dense-kinship form, which
-// is lean)
-hipError_t launch_form(bool full, bool split, bool nibble, bool kin, const TiledArgs &a,
+// launch_shape<FULL, SPLIT, N4, KIN> by run-time flags (kin: kKinMatrix / kKinSummary, which
+// are lean)
+hipError_t launch_form(bool full, bool split, bool nibble, int kin, const TiledArgs &a,
                        const LaunchSwitches &sw, uint64_t blocks, uint32_t lds_bytes,
                        hipStream_t stream) {
-  if (kin && full) return hipErrorInvalidValue;
+  if (kin < kRecords || kin > kKinSummary || (kin != kRecords && full)) return hipErrorInvalidValue;
   using Launch = hipError_t (*)(const TiledArgs &, const LaunchSwitches &, uint64_t, uint32_t,
                                 hipStream_t);
-  static constexpr Launch kForms[2][2][2][2] = {  // [kin][nibble][split][full]
+  static constexpr Launch kForms[3][2][2][2] = {  // [kin][nibble][split][full]
       {{{launch_shape<false, false, false>, launch_shape<true, false, false>},
         {launch_shape<false, true, false>, launch_shape<true, true, false>}},
        {{launch_shape<false, false, true>, launch_shape<true, false, true>},
         {launch_shape<false, true, true>, launch_shape<true, true, true>}}},
-      {{{launch_shape<false, false, false, true>, nullptr},
-        {launch_shape<false, true, false, true>, nullptr}},
-       {{launch_shape<false, false, true, true>, nullptr},
-        {launch_shape<false, true, true, true>, nullptr}}}};
+      {{{launch_shape<false, false, false, kKinMatrix>, nullptr},
+        {launch_shape<false, true, false, kKinMatrix>, nullptr}},
+       {{launch_shape<false, false, true, kKinMatrix>, nullptr},
+        {launch_shape<false, true, true, kKinMatrix>, nullptr}}},
+      {{{launch_shape<false, false, false, kKinSummary>, nullptr},
+        {launch_shape<false, true, false, kKinSummary>, nullptr}},
+       {{launch_shape<false, false, true, kKinSummary>, nullptr},
+        {launch_shape<false, true, true, kKinSummary>, nullptr}}}};
   return kForms[kin][nibble][split][full](a, sw, blocks, lds_bytes, stream);
 }
 
@@ -1562,7 +1645,7 @@ hipError_t launch_mfma_gated(const TiledArgs &args, uint64_t num_units, const ui
 }
 
 namespace {
-hipError_t launch_planned_form(bool full, bool nibble, bool kin, const TiledArgs &args,
+hipError_t launch_planned_form(bool full, bool nibble, int kin, const TiledArgs &args,
                                const LaunchSwitches &sw, uint64_t num_tiles, uint32_t lds_bytes,
                                hipStream_t stream) {
   if ((uint64_t)args.geo.k_words * 32 > (nibble ? kMfmaN4MaxSites : kMfmaMaxSites))
@@ -1584,7 +1667,7 @@ hipError_t launch_planned_form(bool full, bool nibble, bool kin, const TiledArgs
 
 hipError_t launch_mfma(bool full, bool nibble, const TiledArgs &args, const LaunchSwitches &sw,
                        uint64_t num_tiles, uint32_t lds_bytes, hipStream_t stream) {
-  return launch_planned_form(full, nibble, false, args, sw, num_tiles, lds_bytes, stream);
+  return launch_planned_form(full, nibble, kRecords, args, sw, num_tiles, lds_bytes, stream);
 }
 
 hipError_t launch_mfma_kin(bool nibble, const TiledArgs &args, const LaunchSwitches &sw,
@@ -1592,7 +1675,18 @@ hipError_t launch_mfma_kin(bool nibble, const TiledArgs &args, const LaunchSwitc
   if (args.dense_kin == nullptr || args.perm != nullptr) return hipErrorInvalidValue;
   if (num_tiles == 0) return hipSuccess;
   // (the lean forms size their LDS themselves: launch_shape)
-  return launch_planned_form(false, nibble, true, args, sw, num_tiles, 0, stream);
+  return launch_planned_form(false, nibble, kKinMatrix, args, sw, num_tiles, 0, stream);
+}
+
+hipError_t launch_mfma_summary(bool nibble, const TiledArgs &args, const LaunchSwitches &sw,
+                               uint64_t num_tiles, hipStream_t stream) {
+  if ((args.sum_hist == nullptr && args.sum_best == nullptr) || args.perm != nullptr)
+    return hipErrorInvalidValue;
+  // (the tile's histogram sits in LDS: kMfmaSummaryLdsBytes)
+  if (args.sum_hist != nullptr && (args.sum_bins == 0 || args.sum_bins > CUKING_KIN_BINS_MAX))
+    return hipErrorInvalidValue;
+  if (num_tiles == 0) return hipSuccess;
+  return launch_planned_form(false, nibble, kKinSummary, args, sw, num_tiles, 0, stream);
 }
 
 // ---- symmetric fill of a dense kinship matrix --------------------------------------------

@@ -61,6 +61,15 @@ def parse_args(argv=None):
               "pair, no threshold -- to this .npy file ([NumRows, NumCols]; a diagonal block "
               "symmetric with its diagonal).  One process only; the matrix must fit the GPU "
               "beside the bitset (4 B x NumRows x NumCols: use --split-factor otherwise)")
+    flag("kin-summary-uri", default="",
+         help="also write the block's kinship summary -- the histogram of the float32 kinship "
+              "of EVERY pair and every sample's nearest relative, no matrix and no threshold "
+              "-- to this .npz file (hist, lo, hi, bins, best_kin, best_partner).  One process "
+              "only")
+    flag("kin-summary-bins", default="",
+         help="LO,HI,N: the histogram of --kin-summary-uri (default -1,0.5,1536; N + 3 slots: "
+              "below LO, the N bins, from HI on, NaN); write --kin-summary-bins=-0.25,0.25,64 "
+              "when LO is negative")
     return ap.parse_args(argv)
 
 
@@ -73,6 +82,23 @@ def resolve_uri(uri: str) -> Path:
         raise UsageError(f"Unsupported URI: {uri} (no GCS client in this build; "
                          "pass a local directory or file:// URI)")
     return Path(uri[7:] if uri.startswith("file://") else uri)
+
+
+def summary_bins(text: str):
+    """--kin-summary-bins LO,HI,N -> (lo, hi, n)."""
+    if not text:
+        return -1.0, 0.5, 1536
+    parts = text.split(",")
+    try:
+        # (as the library sees them: float32)
+        lo, hi, n = float(np.float32(parts[0])), float(np.float32(parts[1])), int(parts[2])
+        if len(parts) != 3 or not (np.isfinite(lo) and np.isfinite(hi) and lo < hi) or \
+                not 1 <= n <= 4096:
+            raise ValueError
+    except (ValueError, IndexError):
+        raise UsageError("--kin_summary_bins expects LO,HI,N with finite LO < HI and "
+                         "1 <= N <= 4096") from None
+    return lo, hi, n
 
 
 def validate(args):  # cuking.cu:437-462
@@ -92,6 +118,12 @@ def validate(args):  # cuking.cu:437-462
         raise UsageError("--kin_matrix_uri needs one process (one GPU): a dense kinship matrix "
                          "is not assembled from several GPUs; run the shards of a "
                          "--split-factor one after the other instead")
+    if args.kin_summary_bins and not args.kin_summary_uri:
+        raise UsageError("--kin_summary_bins needs --kin_summary_uri")
+    if args.kin_summary_uri and int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise UsageError("--kin_summary_uri needs one process (one GPU): summaries are not "
+                         "merged across ranks yet")
+    summary_bins(args.kin_summary_bins)
 
 
 def read_and_pack(in_dir: Path, sm, num_sites: int, threads: int) -> np.ndarray:
@@ -171,6 +203,17 @@ def write_kin_matrix(path: Path, ctx, sm, wps: int, bits, device: int) -> None:
         np.save(f, kin.cpu().numpy())
 
 
+def write_kin_summary(path: Path, ctx, sm, wps: int, bits, lo: float, hi: float, n: int) -> None:
+    """The block's kinship summary as an .npz: the histogram and, per stored sample of the
+    block (rows first, then columns), the nearest relative's kinship and global index."""
+    summary = ctx.kin_summary(sm, wps, bits, lo=lo, hi=hi, bins=n)
+    kin, partner = summary.nearest()
+    path.parent.mkdir(parents=True, exist_ok=True)
+    with open(path, "wb") as f:   # (np.savez would append .npz to another suffix)
+        np.savez(f, hist=summary.counts(), lo=np.float32(summary.lo), hi=np.float32(summary.hi),
+                 bins=np.int64(n), best_kin=kin, best_partner=partner)
+
+
 def main(argv=None) -> int:
     args = parse_args(argv)
     import torch
@@ -186,6 +229,7 @@ def main(argv=None) -> int:
         in_dir = resolve_uri(args.input_uri) if args.input_uri else None
         out_dir = resolve_uri(args.output_uri)
         kin_path = resolve_uri(args.kin_matrix_uri) if args.kin_matrix_uri else None
+        summary_path = resolve_uri(args.kin_summary_uri) if args.kin_summary_uri else None
         synthetic = None
         if args.synthetic:
             parts = [int(x) for x in args.synthetic.split(",")]
@@ -309,6 +353,9 @@ def main(argv=None) -> int:
             write_results(out, recs, sample_ids)
             if kin_path is not None:
                 write_kin_matrix(kin_path, ctx, sm, wps, bits, local_rank)
+            if summary_path is not None:
+                write_kin_summary(summary_path, ctx, sm, wps, bits,
+                                  *summary_bins(args.kin_summary_bins))
             pairs = sm.NumPairs()
             print(json.dumps({"pairs": pairs, "results": int(len(recs)), "gpus": world,
                               "compute_seconds": dt,

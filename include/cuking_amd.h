@@ -447,6 +447,80 @@ cuking_status cuking_compute_kin_matrix_tiles(cuking_ctx *ctx, const cuking_subm
                                               float *d_kin, uint64_t ld, uint32_t flags,
                                               void *stream);
 
+/* Kinship summary: the histogram of the float32 kinship of EVERY pair of the block and every
+ * sample's nearest relative, without the matrix and without a threshold -- what the look at
+ * the kinship distribution before choosing a threshold needs at sizes where the matrix (4 B x
+ * NumRows x NumCols) no longer fits, and where duplicate detection, "drop anyone related to
+ * anyone" and PC-AiR style partitioning start.  The output does not grow with the pair count.
+ *
+ * Histogram: cuking_kin_bins {lo, hi, num_bins}, lo < hi, both finite, 1 <= num_bins <=
+ * CUKING_KIN_BINS_MAX; d_hist holds num_bins + 3 (cuking_kin_hist_slots) uint64 slots.  The
+ * slot of a kinship `kin` is DEFINED by these float32 operations, one rounding each, nothing
+ * fused (cuking_kin_bin_slot evaluates exactly this on the host):
+ *     scale = (float)num_bins / (hi - lo)        once per call, on the host
+ *     kin is NaN                  -> slot num_bins + 2   NAN
+ *     kin < lo                    -> slot 0              UNDER (-inf as well)
+ *     t = (kin - lo) * scale
+ *     !(t < (float)num_bins)      -> slot num_bins + 1   OVER (+inf, kin >= hi)
+ *     otherwise                   -> slot 1 + (uint32_t)t
+ * The nominal edges lo + b (hi - lo) / num_bins are approximate: a kinship within a rounding
+ * of one may be counted on either side; the expression is the contract.  With hi = 0.5 exact
+ * duplicates (kin 0.5) land in OVER.
+ *
+ * Nearest relative: one uint64 key per sample, d_best[cuking_submatrix_sample_offset(s)]
+ * (cuking_submatrix_num_samples keys: rows first, then columns, a diagonal block's samples
+ * once).  High word: the order-preserving map of the kinship's bits (bits ^ 0x80000000 for a
+ * non-negative float, ~bits for a negative one); low word: ~partner, the partner's GLOBAL
+ * sample index -- under an unsigned maximum the larger kinship wins, among equal kinships the
+ * lower partner.  A NaN kinship never makes a key; key 0 = no partner with a defined kinship
+ * (no real key is 0: -inf maps to the high word 0x007FFFFF).  cuking_kin_best_key builds a
+ * key (0 for NaN), cuking_kin_best_decode takes one apart (returns 0 for key 0, else 1).
+ *
+ * cuking_compute_kin_summary counts every pair the block holds exactly once ((i < j) on a
+ * diagonal block, every (i, j) on an off-diagonal one: cuking_submatrix_num_pairs): pair
+ * (i, j) adds 1 to its slot of d_hist, raises d_best[offset(i)] to at least key(kin, j) and
+ * d_best[offset(j)] to at least key(kin, i).  Both outputs ACCUMULATE, like d_result_index:
+ * the call resets neither, the caller zeroes them; calls over disjoint tile ranges (the tiles
+ * form follows cuking_compute_king_tiles), on one GPU or several, add up to the whole call --
+ * histograms merge by sum, keys by maximum.  Either of d_hist / d_best may be NULL (bins may
+ * be NULL when d_hist is).  The kinship is the numerics contract's kin above for the pair's
+ * exact integer sums, bit for bit what a record or a matrix entry carries, -inf and NaN
+ * included; the result depends on no tuning option, and entries sit at the STORED samples'
+ * positions (the call converts the unsorted layout of the dense matrix; the next thresholded
+ * call converts again).  The cost does not depend on the data: the lean matrix-core k loop
+ * with an epilogue that reduces the kinship of a tile's pairs in LDS and merges with one
+ * 64-bit atomic per non-empty slot and key.
+ * INVALID_ARGUMENT, before any device is touched: a null context, submatrix or bitset; both
+ * outputs NULL; d_hist without bins; num_bins 0 or above CUKING_KIN_BINS_MAX; bounds that are
+ * not finite or not lo < hi; a bad tile range; a context that is not the tiled kernel with
+ * variant 5, 6 or 7, and bitsets from 2^24 sites on (the VALU and stream kernels have no
+ * summary form -- one atomic per pair would be a trap at the sizes this call is for).  An
+ * empty block returns OK.  Asynchronous on `stream`; workspace, stream ordering and
+ * "reuse_prepared" as for the other compute entry points.
+ * Out of scope: the C++ `cuking` binary, merging across ranks (the tiles form and the merge
+ * rules make it possible), IBS0/1/2 summaries, per-sample relative counts. */
+#define CUKING_KIN_BINS_MAX 4096u
+typedef struct cuking_kin_bins {
+  float lo, hi;
+  uint32_t num_bins;
+} cuking_kin_bins;
+/* Host-only (cuking_kin_bin_slot: 0xFFFFFFFF for bins the compute call would refuse). */
+uint32_t cuking_kin_hist_slots(uint32_t num_bins);
+uint32_t cuking_kin_bin_slot(const cuking_kin_bins *bins, float kin);
+uint64_t cuking_kin_best_key(float kin, uint32_t partner);
+uint32_t cuking_kin_best_decode(uint64_t key, float *kin, uint32_t *partner);
+cuking_status cuking_compute_kin_summary(cuking_ctx *ctx, const cuking_submatrix *sm,
+                                         uint32_t words_per_sample,
+                                         const uint64_t *d_bit_sets,
+                                         const cuking_kin_bins *bins, uint64_t *d_hist,
+                                         uint64_t *d_best, void *stream);
+cuking_status cuking_compute_kin_summary_tiles(cuking_ctx *ctx, const cuking_submatrix *sm,
+                                               uint32_t words_per_sample,
+                                               const uint64_t *d_bit_sets,
+                                               uint64_t tile_begin, uint64_t tile_end,
+                                               const cuking_kin_bins *bins, uint64_t *d_hist,
+                                               uint64_t *d_best, void *stream);
+
 /* cuking.cu:761-765 on host memory: sort by (sample_i, sample_j, kin). */
 void cuking_sort_results(cuking_result *results, size_t num_results);
 
