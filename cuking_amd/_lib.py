@@ -25,6 +25,8 @@ KIN_UPPER = 0
 KIN_SYMMETRIC = 1
 
 KIN_BINS_MAX = 4096
+REL_THRESHOLDS_MAX = 8
+REL_NO_BAND = 0xFFFFFFFF
 
 
 class CKinBins(C.Structure):
@@ -124,6 +126,11 @@ SIGNATURES = {
     "cuking_compute_kin_summary": (_int, [_vp, _SM, _u32, _vp, _BINS, _vp, _vp, _vp]),
     "cuking_compute_kin_summary_tiles": (_int, [_vp, _SM, _u32, _vp, _u64, _u64, _BINS, _vp,
                                                 _vp, _vp]),
+    "cuking_rel_band": (_u32, [C.POINTER(_f32), _u32, _f32]),
+    "cuking_compute_relative_counts": (_int, [_vp, _SM, _u32, _vp, C.POINTER(_f32), _u32, _vp,
+                                              _vp]),
+    "cuking_compute_relative_counts_tiles": (_int, [_vp, _SM, _u32, _vp, _u64, _u64,
+                                                    C.POINTER(_f32), _u32, _vp, _vp]),
     "cuking_sort_results": (None, [_vp, _sz]),
     "cuking_timing_enable": (_int, [_vp, _int]),
     "cuking_timing_reset": (_int, [_vp]),

@@ -27,6 +27,8 @@ KING_COUNTS_DTYPE = np.dtype(
 
 DEFAULT_KIN_THRESHOLD = 0.0884   # cuking.cu:43
 DEFAULT_MAX_RESULTS = 10 << 20   # cuking.cu:40
+# The KING cut-offs: 3rd / 2nd / 1st degree, duplicate (ascending, as the library wants them)
+KING_CUTOFFS = (0.0442, 0.0884, 0.177, 0.354)
 
 
 class ResourceExhaustedError(RuntimeError):
@@ -383,6 +385,58 @@ class KingContext:
                 *args, tile_range[0], tile_range[1], *tail))
         return summary
 
+    def relative_counts(self, submatrix: Submatrix, words_per_sample: int, bit_sets,
+                        thresholds=KING_CUTOFFS, out=None, tile_range=None,
+                        stream=None) -> "RelativeCounts":
+        """Relative counts (cuking_compute_relative_counts): per stored sample of the
+        block, the number of partners whose kinship falls in each band of ``thresholds``
+        (1 to 8 finite values, strictly ascending; band t: the largest t with
+        ``kin > thresholds[t]``, the comparison a record makes).  The thresholded call
+        at ``thresholds[0]`` without the records: nothing can overflow.  Does not
+        synchronise; returns a ``RelativeCounts`` holding the device tensor.  ``out``: a
+        contiguous int32 ``[NumSamples(), len(thresholds)]`` tensor (a view of the
+        library's uint32 data) the call ACCUMULATES into, e.g. for the tile ranges of
+        one block; without it a zeroed one is allocated.  ``tile_range``: only the tiles
+        [begin, end) of the block's enumeration."""
+        import torch
+        self._check_bits(submatrix, words_per_sample, bit_sets)
+        thr = np.asarray(thresholds, dtype=np.float32).reshape(-1)
+        if not 1 <= thr.size <= _lib.REL_THRESHOLDS_MAX:
+            raise ValueError(f"between 1 and {_lib.REL_THRESHOLDS_MAX} thresholds are needed")
+        if not np.isfinite(thr).all() or not (np.diff(thr) > 0).all():
+            raise ValueError("thresholds must be finite and strictly ascending (as float32)")
+        shape = (submatrix.NumSamples(), int(thr.size))
+        if out is None:
+            out = torch.zeros(shape, dtype=torch.int32, device=f"cuda:{self.device}")
+        else:
+            if not out.is_cuda or out.device.index != self.device:
+                raise ValueError("out must live on this context's GPU")
+            if out.dtype != torch.int32:
+                raise ValueError("out must be an int32 tensor (a view of the uint32 data)")
+            if tuple(out.shape) != shape or not out.is_contiguous():
+                raise ValueError(f"out must be a contiguous tensor of shape {shape}, "
+                                 f"not {tuple(out.shape)}")
+        counts = RelativeCounts(out, thr, submatrix, self.device)
+        if submatrix.NumRows() == 0 or submatrix.NumCols() == 0:
+            return counts
+        cthr = (C.c_float * thr.size)(*[float(t) for t in thr])
+        args = (self.handle, C.byref(submatrix.c), words_per_sample, bit_sets.data_ptr())
+        tail = (cthr, int(thr.size), out.data_ptr(), _stream_handle(stream))
+        if tile_range is None:
+            check(self.lib.cuking_compute_relative_counts(*args, *tail))
+        else:
+            check(self.lib.cuking_compute_relative_counts_tiles(
+                *args, tile_range[0], tile_range[1], *tail))
+        return counts
+
+    def count_records(self, submatrix: Submatrix, words_per_sample: int, bit_sets,
+                      kin_threshold: float) -> int:
+        """The exact number of records ``compute_king`` appends for this block at
+        ``kin_threshold`` -- its smallest sufficient ``max_results`` -- from one count
+        call with one threshold.  Waits for the device."""
+        return self.relative_counts(submatrix, words_per_sample, bit_sets,
+                                    thresholds=(kin_threshold,)).num_records(0)
+
     def run(self, submatrix: Submatrix, words_per_sample: int, bit_sets,
             kin_threshold: float = DEFAULT_KIN_THRESHOLD,
             max_results: int = DEFAULT_MAX_RESULTS, tile_range=None,
@@ -532,6 +586,43 @@ class KinSummary:
         return int(self.counts()[1 + b:self.bins + 2].sum())
 
 
+class RelativeCounts:
+    """What ``KingContext.relative_counts`` returns: the device tensor ``counts``
+    (``[NumSamples(), len(thresholds)]`` int32, a view of uint32 data; one row per stored
+    sample of the block, rows first, then columns) and the float32 ``thresholds``.  The
+    accessors wait for the device."""
+
+    def __init__(self, counts, thresholds, submatrix: Submatrix, device: int):
+        self.counts = counts
+        self.thresholds = np.asarray(thresholds, dtype=np.float32)
+        self.submatrix, self.device = submatrix, device
+
+    def bands(self) -> np.ndarray:
+        """Host ``[NumSamples, T]`` uint32: partners of each stored sample in band t
+        (``thresholds[t] < kin <= thresholds[t + 1]``; the last band is open above)."""
+        import torch
+        torch.cuda.synchronize(self.device)
+        return self.counts.cpu().numpy().view(np.uint32).reshape(self.counts.shape)
+
+    def at_least(self) -> np.ndarray:
+        """Host ``[NumSamples, T]`` uint64: partners of each stored sample with
+        ``kin > thresholds[t]`` -- the suffix sums of ``bands()``."""
+        b = self.bands().astype(np.uint64)
+        return np.cumsum(b[:, ::-1], axis=1, dtype=np.uint64)[:, ::-1]
+
+    def num_records(self, t: int) -> int:
+        """The exact number of records ``compute_king(kin_threshold=thresholds[t])`` appends
+        for this block: every such pair is counted at both its samples -- on a diagonal
+        block half the column sum, on an off-diagonal one the column sum over its rows."""
+        if not 0 <= t < self.thresholds.size:
+            raise ValueError(f"threshold {t} outside [0, {self.thresholds.size})")
+        column = self.at_least()[:, t]
+        sm = self.submatrix
+        if sm.i_begin == sm.j_begin:
+            return int(column.sum()) // 2
+        return int(column[:sm.NumRows()].sum())
+
+
 def kin_matrix(ctx: KingContext, submatrix: Submatrix, words_per_sample: int, bit_sets,
                **kwargs):
     """``ctx.kin_matrix(...)``: the dense float32 kinship matrix of a block."""
@@ -544,8 +635,15 @@ def kin_summary(ctx: KingContext, submatrix: Submatrix, words_per_sample: int, b
     return ctx.kin_summary(submatrix, words_per_sample, bit_sets, **kwargs)
 
 
+def relative_counts(ctx: KingContext, submatrix: Submatrix, words_per_sample: int, bit_sets,
+                    **kwargs) -> RelativeCounts:
+    """``ctx.relative_counts(...)``: per-sample partner counts at kinship thresholds."""
+    return ctx.relative_counts(submatrix, words_per_sample, bit_sets, **kwargs)
+
+
 __all__ = [
     "Submatrix", "KingContext", "kin_matrix", "kin_summary", "KinSummary",
+    "relative_counts", "RelativeCounts", "KING_CUTOFFS",
     "KING_RESULT_DTYPE", "KING_COUNTS_DTYPE",
     "ResourceExhaustedError", "CukingError", "padded_sites",
     "words_per_sample", "bytes_per_pair", "new_host_bitset", "pack_host",

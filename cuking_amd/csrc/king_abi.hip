@@ -443,6 +443,11 @@ struct Outputs {
   // kinship summary (TiledArgs::sum_hist / sum_best): every pair's kinship reduced, no records
   uint64_t *sum_hist, *sum_best;
   cuking_kin_bins sum_bins;
+  // relative counts (TiledArgs::rel_counts): the thresholded call without records; the
+  // call's kin_threshold is rel_thr[0]
+  uint32_t *rel_counts;
+  uint32_t rel_num;
+  float rel_thr[CUKING_REL_THRESHOLDS_MAX];
 };
 cuking_status launch_args(cuking_ctx *ctx, hipStream_t stream, const cuking_submatrix &sm,
                           uint32_t words_per_sample, const uint64_t *d_bit_sets,
@@ -472,6 +477,11 @@ cuking_status launch_args(cuking_ctx *ctx, hipStream_t stream, const cuking_subm
     a.sum_lo = out.sum_bins.lo;
     a.sum_scale = kin_bin_scale(out.sum_bins);  // (once per call, on the host)
     a.sum_bins = out.sum_bins.num_bins;
+  }
+  a.rel_counts = out.rel_counts;
+  if (out.rel_counts != nullptr) {
+    a.rel_num = out.rel_num;
+    for (uint32_t t = 0; t < out.rel_num; ++t) a.rel_thr[t] = out.rel_thr[t];
   }
   a.rect_row_stride = 1;
   a.bits = d_bit_sets;
@@ -789,9 +799,14 @@ cuking_status run_tiled(cuking_ctx *ctx, const cuking_submatrix &sm,
   const int kv = effective_variant(ctx, words_per_sample);
   if (sum && !is_mfma_variant(kv))
     return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "kinship summary: no matrix-core kernel");
+  // Relative counts: the thresholded call's lean form (sorted layout, the filter where its
+  // bound applies) whose kernels count instead of appending records; matrix-core kernels only.
+  const bool rel = out.rel_counts != nullptr;
+  if (rel && !is_mfma_variant(kv))
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "relative counts: no matrix-core kernel");
   const bool kin_mfma = (kin || sum) && is_mfma_variant(kv);
-  const bool full = !kin_mfma && use_full_counts(ctx, kin_threshold, out.counts != nullptr || kin,
-                                               words_per_sample);
+  const bool full = !kin_mfma && !rel &&
+                    use_full_counts(ctx, kin_threshold, out.counts != nullptr || kin, words_per_sample);
   const LaunchSwitches sw = launch_switches(ctx, words_per_sample, full, kin_threshold);
   // (where the filter runs the four-product kernel's codes may stay unconverted)
   cuking_status st = prepare(ctx, sm, words_per_sample, d_bit_sets, stream, &geo, &tiles,
@@ -1712,6 +1727,90 @@ cuking_status cuking_compute_kin_summary_tiles(cuking_ctx *ctx, const cuking_sub
                                                void *stream) {
   return run_summary(ctx, sm, words_per_sample, d_bit_sets, false, tile_begin, tile_end, bins,
                      d_hist, d_best, stream);
+}
+
+// The checks the two relative-counts entry points share, in front of anything that touches a
+// device.
+static cuking_status check_rel_args(const cuking_ctx *ctx, const cuking_submatrix *sm,
+                                    uint32_t words_per_sample, const uint64_t *d_bit_sets,
+                                    const float *thresholds, uint32_t num_thresholds,
+                                    const uint32_t *d_counts, bool tile_range,
+                                    uint64_t tile_begin, uint64_t tile_end) {
+  cuking_status st = check_compute_args(sm, words_per_sample, d_bit_sets);
+  if (st != CUKING_OK) return st;
+  if (thresholds == nullptr)
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "relative counts: null thresholds pointer");
+  if (num_thresholds == 0 || num_thresholds > CUKING_REL_THRESHOLDS_MAX)
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT,
+                       "relative counts: num_thresholds %u outside [1, %u]", num_thresholds,
+                       CUKING_REL_THRESHOLDS_MAX);
+  if (!rel_thresholds_valid(thresholds, num_thresholds))
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT,
+                       "relative counts: thresholds must be finite and strictly ascending");
+  if (sm_num_samples(*sm) != 0 && d_counts == nullptr)
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "relative counts: null counts pointer");
+  if (tile_range && tile_begin > tile_end)
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "tile range [%llu, %llu) is reversed",
+                       (unsigned long long)tile_begin, (unsigned long long)tile_end);
+  if (ctx == nullptr) return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "null context");
+  if (tile_range) {
+    const bool empty = sm_num_rows(*sm) == 0 || sm_num_cols(*sm) == 0;
+    const uint64_t n_tiles = empty ? 0 : cuking_num_tiles(ctx, sm);
+    if (tile_end > n_tiles)
+      return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "tile range [%llu, %llu) outside [0, %llu)",
+                         (unsigned long long)tile_begin, (unsigned long long)tile_end,
+                         (unsigned long long)n_tiles);
+  }
+  if (ctx->kernel != CUKING_KERNEL_TILED || !is_mfma_variant(ctx->variant))
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT,
+                       "relative counts: served by contexts of the tiled kernel with variant 5, "
+                       "6 or 7 (the matrix-core kernels) only; the VALU variants and the stream "
+                       "kernel have no counting form");
+  if (!is_mfma_variant(effective_variant(ctx, words_per_sample)))
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT,
+                       "relative counts: bitsets from 2^24 sites on are not served (the "
+                       "matrix-core kernels count in float32)");
+  return CUKING_OK;
+}
+
+// What the two entry points share behind their checks: `whole` = every tile of the block.
+static cuking_status run_rel(cuking_ctx *ctx, const cuking_submatrix *sm,
+                             uint32_t words_per_sample, const uint64_t *d_bit_sets, bool whole,
+                             uint64_t tile_begin, uint64_t tile_end, const float *thresholds,
+                             uint32_t num_thresholds, uint32_t *d_counts, void *stream) {
+  cuking_status st = check_rel_args(ctx, sm, words_per_sample, d_bit_sets, thresholds,
+                                    num_thresholds, d_counts, !whole, tile_begin, tile_end);
+  if (st != CUKING_OK) return st;
+  if (sm_num_rows(*sm) == 0 || sm_num_cols(*sm) == 0) return CUKING_OK;
+  st = bind(ctx);
+  if (st != CUKING_OK) return st;
+  Outputs out = {};
+  out.rel_counts = d_counts;
+  out.rel_num = num_thresholds;
+  for (uint32_t t = 0; t < num_thresholds; ++t) out.rel_thr[t] = thresholds[t];
+  // (the thresholded call at the lowest threshold: the filter's bound, the layout, the lean
+  //  form's cheap test all follow it)
+  return run_tiled(ctx, *sm, words_per_sample, d_bit_sets, tile_begin, tile_end, whole,
+                   thresholds[0], out, (hipStream_t)stream);
+}
+
+cuking_status cuking_compute_relative_counts(cuking_ctx *ctx, const cuking_submatrix *sm,
+                                             uint32_t words_per_sample,
+                                             const uint64_t *d_bit_sets, const float *thresholds,
+                                             uint32_t num_thresholds, uint32_t *d_counts,
+                                             void *stream) {
+  return run_rel(ctx, sm, words_per_sample, d_bit_sets, true, 0, 0, thresholds, num_thresholds,
+                 d_counts, stream);
+}
+
+cuking_status cuking_compute_relative_counts_tiles(cuking_ctx *ctx, const cuking_submatrix *sm,
+                                                   uint32_t words_per_sample,
+                                                   const uint64_t *d_bit_sets, uint64_t tile_begin,
+                                                   uint64_t tile_end, const float *thresholds,
+                                                   uint32_t num_thresholds, uint32_t *d_counts,
+                                                   void *stream) {
+  return run_rel(ctx, sm, words_per_sample, d_bit_sets, false, tile_begin, tile_end, thresholds,
+                 num_thresholds, d_counts, stream);
 }
 
 // ---- timing ---------------------------------------------------------------

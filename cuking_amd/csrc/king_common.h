@@ -292,6 +292,16 @@ struct TiledArgs {
   unsigned long long *sum_hist, *sum_best;
   float sum_lo, sum_scale;
   uint32_t sum_bins;
+  // Relative counts (cuking_compute_relative_counts; again at the END): rel_counts non-null =
+  // no records; a pair whose kinship falls in band t of the rel_num ascending thresholds
+  // rel_thr (band rule: king_kin_summary.h rel_band; kin_threshold = rel_thr[0]) adds 1 to
+  // rel_counts[s * rel_num + t] for both its STORED samples s (rows, then an off-diagonal
+  // block's columns; `perm` maps a sorted layout back).  The thresholded path with counting
+  // forms of its own: king_refine_count_kernel (king_filter.hip) and the matrix-core
+  // kernels' count_relatives epilogue (king_mfma.hip), chosen on the host.
+  uint32_t *rel_counts;
+  uint32_t rel_num;
+  float rel_thr[CUKING_REL_THRESHOLDS_MAX];
 };
 
 // Prefix statistics: the k-steps (of 256 sites) a check may sit behind, as shares of the
@@ -520,6 +530,9 @@ hipError_t launch_mfma_kin(bool nibble, const TiledArgs &args, const LaunchSwitc
 // kinship of a tile's pairs in LDS instead of storing it.
 hipError_t launch_mfma_summary(bool nibble, const TiledArgs &args, const LaunchSwitches &sw,
                                uint64_t num_tiles, hipStream_t stream);
+// (The relative-counts form, TiledArgs::rel_counts, has no launcher of its own: it IS the
+// thresholded call, so launch_mfma, launch_mfma_list, launch_mfma_gated and launch_filter pick
+// their counting kernels on the host when args.rel_counts is set; lean forms only.)
 // Symmetric fill of an n x n kinship matrix whose upper triangle (and diagonal) is there:
 // kin[j * ld + i] = kin[i * ld + j] for i < j, tile-wise through LDS, reads and writes
 // coalesced.  Runs behind the pair kernel on the same stream.

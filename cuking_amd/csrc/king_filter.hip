@@ -31,7 +31,9 @@
 //      launch have gone dense the remaining tiles hand theirs over unexamined.
 //   2. king_refine_kernel: one wavefront per candidate, the reference's own six
 //      sums straight from the bitset (king_kernels.hip stream kernel), exact
-//      kinship, record.
+//      kinship, record.  (A relative-counts call, TiledArgs::rel_counts, runs
+//      king_refine_count_kernel instead: the four sums kinship needs, its band, two
+//      atomics, no record -- and steps 3 and the fallback in their counting form.)
 //   3. the four-product kernel (king_mfma.hip, tile-list mode) over the dense
 //      quadrants -- nothing, on ordinary cohorts.
 // Same records as every other variant, whatever the data: the bound only
@@ -79,6 +81,7 @@
 
 #include "king_common.h"
 #include "king_device.h"
+#include "king_kin_summary.h"
 
 // The LDS-DMA statements below write M0 and say so in their clobber lists.
 #pragma clang diagnostic ignored "-Winline-asm"
@@ -1201,6 +1204,67 @@ __global__ __launch_bounds__(256) void king_refine_kernel(const TiledArgs a) {
   }
 }
 
+// The counting form of king_refine_kernel (TiledArgs::rel_counts, a kernel of its own so that
+// the record form stays as it is): one wavefront per candidate pair, only the four sums
+// kinship needs (cuking.cu:232-235), the same king_kinship() float a record carries, its band
+// among the call's thresholds (king_kin_summary.h rel_band) and one atomic per end of the
+// pair, at the STORED samples' rows of rel_counts.  No record, no IBS sums.
+__global__ __launch_bounds__(256) void king_refine_count_kernel(const TiledArgs a) {
+  const uint32_t lane = threadIdx.x & 63;
+  uint32_t count = *a.filter_ctrl;
+  if (count > a.cand_cap) count = a.cand_cap;
+  const uint32_t n = a.words_per_sample / 2;
+  const uint32_t stride = gridDim.x * 4;
+  for (uint32_t p = blockIdx.x * 4 + (threadIdx.x >> 6); p < count; p += stride) {
+    const uint2 e = a.cand_list[p];
+    if (e.x == kNoPair) continue;  // (uniform: a slot of a quadrant that went dense)
+    const uint32_t off_i = a.perm != nullptr ? a.perm[e.x] : e.x;
+    const uint32_t off_j = a.perm != nullptr ? a.perm[a.geo.col_base + e.y]
+                                             : (a.geo.diag ? e.y : a.geo.num_rows + e.y);
+    const uint64_t *het_i_w = a.bits + (uint64_t)off_i * a.words_per_sample;
+    const uint64_t *alt_i_w = het_i_w + n;
+    const uint64_t *het_j_w = a.bits + (uint64_t)off_j * a.words_per_sample;
+    const uint64_t *alt_j_w = het_j_w + n;
+    uint32_t s_het_i = 0, s_het_j = 0, s_both = 0, s_opp = 0;
+    constexpr uint32_t kAhead = 8;  // (as in king_refine_kernel)
+    for (uint32_t w0 = 0; w0 < n; w0 += 64 * kAhead) {
+      uint64_t hi[kAhead], ai[kAhead], hj[kAhead], aj[kAhead];
+#pragma unroll
+      for (uint32_t k = 0; k < kAhead; ++k) {
+        const uint32_t w = w0 + 64 * k + lane;
+        const bool in = w < n;  // beyond the plane: missing
+        hi[k] = in ? het_i_w[w] : ~0ull;
+        ai[k] = in ? alt_i_w[w] : ~0ull;
+        hj[k] = in ? het_j_w[w] : ~0ull;
+        aj[k] = in ? alt_j_w[w] : ~0ull;
+      }
+#pragma unroll
+      for (uint32_t k = 0; k < kAhead; ++k) {
+        const uint64_t ri = ~(hi[k] | ai[k]), rj = ~(hj[k] | aj[k]);
+        const uint64_t defined = ~((hi[k] & ai[k]) | (hj[k] & aj[k]));
+        s_het_i += __popcll(hi[k] & defined);
+        s_het_j += __popcll(hj[k] & defined);
+        s_both += __popcll(hi[k] & hj[k] & defined);
+        s_opp += __popcll(((ri & aj[k]) | (ai[k] & rj)) & defined);
+      }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+      s_het_i += __shfl_xor(s_het_i, off);
+      s_het_j += __shfl_xor(s_het_j, off);
+      s_both += __shfl_xor(s_both, off);
+      s_opp += __shfl_xor(s_opp, off);
+    }
+    if (lane == 0) {
+      const uint32_t band = rel_band(a.rel_thr, a.rel_num, king_kinship(s_het_i, s_het_j, s_both, s_opp));
+      if (band != kRelNoBand) {
+        atomicAdd(a.rel_counts + (size_t)off_i * a.rel_num + band, 1u);
+        atomicAdd(a.rel_counts + (size_t)off_j * a.rel_num + band, 1u);
+      }
+    }
+  }
+}
+
 }  // namespace
 
 static std::atomic<uint32_t> g_check_min_steps{64};
@@ -1232,6 +1296,8 @@ hipError_t launch_filter(const TiledArgs &args, const LaunchSwitches &sw, uint64
                          hipStream_t stream) {
   if ((uint64_t)args.geo.k_words * 32 > kMfmaN4MaxSites || args.filter_ctrl == nullptr ||
       args.cand_list == nullptr || args.dense_list == nullptr || args.sample_stats == nullptr)
+    return hipErrorInvalidValue;
+  if (args.rel_counts != nullptr && (args.rel_num == 0 || args.rel_num > CUKING_REL_THRESHOLDS_MAX))
     return hipErrorInvalidValue;
   hipError_t e = allow_dynamic_lds<king_filter_kernel>(kFilterLdsBytes);
   if (e != hipSuccess) return e;
@@ -1271,7 +1337,9 @@ hipError_t launch_filter(const TiledArgs &args, const LaunchSwitches &sw, uint64
     king_filter_kernel<<<dim3((uint32_t)p.grid), dim3(256), kFilterLdsBytes, stream>>>(a);
     e = hipGetLastError();
     if (e != hipSuccess) return e;
-    king_refine_kernel<<<dim3(wgs * 4), dim3(256), 0, stream>>>(a);
+    // (a relative-counts call: the counting form; so do the two launches below)
+    if (a.rel_counts != nullptr) king_refine_count_kernel<<<dim3(wgs * 4), dim3(256), 0, stream>>>(a);
+    else king_refine_kernel<<<dim3(wgs * 4), dim3(256), 0, stream>>>(a);
     e = hipGetLastError();
     if (e != hipSuccess) return e;
     if (a.codes_ready != nullptr) {

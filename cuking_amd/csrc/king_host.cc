@@ -343,6 +343,12 @@ uint32_t cuking_kin_best_decode(uint64_t key, float *kin, uint32_t *partner) {
   return 1;
 }
 
+// ---- relative counts: the band rule of king_kin_summary.h --------------------------------
+uint32_t cuking_rel_band(const float *thresholds, uint32_t num_thresholds, float kin) {
+  if (!rel_thresholds_valid(thresholds, num_thresholds)) return kRelNoBand;
+  return rel_band(thresholds, num_thresholds, kin);
+}
+
 void cuking_sort_results(cuking_result *results, size_t num_results) {
   std::sort(results, results + num_results,
             [](const cuking_result &a, const cuking_result &b) {

@@ -22,8 +22,15 @@
 //
 // Out of scope: the C++ `cuking` binary; merging across ranks (the tiles form and the merge
 // rules -- histograms by sum, keys by maximum -- make it possible later); the VALU and
-// stream kernels and bitsets from 2^24 sites on; IBS0/1/2 summaries; per-sample relative
-// counts.
+// stream kernels and bitsets from 2^24 sites on; IBS0/1/2 summaries.
+//
+// Relative counts (cuking_compute_relative_counts).  1 .. CUKING_REL_THRESHOLDS_MAX finite
+// float32 thresholds, strictly ascending.  The BAND of a kinship is the largest t with
+// kin > thresholds[t] -- the strict float32 comparison a record's `kin > kin_threshold`
+// makes --, kRelNoBand (0xFFFFFFFF) when there is none: NaN and -inf never get a band.
+// rel_band() below is THE definition: the refine kernel (king_filter.hip), the matrix-core
+// kernels' counting epilogue (king_mfma.hip count_relatives), cuking_rel_band and the tests
+// share it.
 #ifndef CUKING_AMD_KING_KIN_SUMMARY_H_
 #define CUKING_AMD_KING_KIN_SUMMARY_H_
 
@@ -85,6 +92,29 @@ CUKING_SUMMARY_HD inline bool kin_best_decode(uint64_t key, float *kin, uint32_t
   *kin = kin_bits_float((ordered & 0x80000000u) ? (ordered ^ 0x80000000u) : ~ordered);
   *partner = ~(uint32_t)key;
   return true;
+}
+
+// ---- relative counts: bands ------------------------------------------------------------
+constexpr uint32_t kRelNoBand = 0xFFFFFFFFu;
+CUKING_SUMMARY_HD inline bool rel_thresholds_valid(const float *thresholds, uint32_t n) {
+  if (thresholds == nullptr || n < 1 || n > CUKING_REL_THRESHOLDS_MAX) return false;
+  for (uint32_t t = 0; t < n; ++t) {
+    if (!kin_is_finite(thresholds[t])) return false;
+    if (t != 0 && !(thresholds[t - 1] < thresholds[t])) return false;
+  }
+  return true;
+}
+// The band of `kin` (file header): THE definition.  (Ascending thresholds: the last one
+// below kin is the largest.  A fixed trip count, unrolled on the device, so that thresholds
+// held in registers are never indexed by a variable; entries from n on are not read.)
+CUKING_SUMMARY_HD inline uint32_t rel_band(const float *thresholds, uint32_t n, float kin) {
+  uint32_t band = kRelNoBand;
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+  for (uint32_t t = 0; t < CUKING_REL_THRESHOLDS_MAX; ++t)
+    if (t < n && kin > thresholds[t]) band = t;
+  return band;
 }
 
 }  // namespace cuking

@@ -45,6 +45,7 @@
 //     store_counts       the six counts of every pair            (FULL, dense_counts)
 //     store_kin          float32 kinship of every pair                    (KIN = matrix)
 //     summarise_kin      histogram and nearest-relative keys of a tile    (KIN = summary)
+//     count_relatives    lean_decide's test, then band and two atomics (KIN = relative counts)
 //     lean_decide        threshold on the float sums, exact epilogue out of line (the rest)
 // A k loop's statements are macros over its function's locals, defined and undefined
 // inside that function.
@@ -141,6 +142,32 @@ __device__ __attribute__((noinline)) void lean_epilogue_call_n4(
     const EmitCtxP c, bool valid, uint32_t li, uint32_t lj, uint32_t het_i,
     uint32_t het_j, uint32_t dd, int32_t q, uint32_t lane) {
   lean_epilogue_pair_n4(c, valid, li, lj, het_i, het_j, dd, q, lane);
+}
+
+// The exact epilogue of the relative-counts form (count_relatives()), out of line for the same
+// reason: the pair's kinship from its four sums (kin_of_sums(), below), its band, and one
+// atomic per end of the pair at the STORED samples' rows.  Per lane: no recount, so nothing
+// needs the whole wavefront.
+struct RelCtx {
+  uint32_t *counts;
+  uint32_t num;
+  float thr[CUKING_REL_THRESHOLDS_MAX];
+  const uint32_t *perm;  // the layout's sample order, or nullptr (TiledArgs::perm)
+  uint32_t diag, num_rows, col_base;
+};
+template <bool N4>
+__device__ __forceinline__ float kin_of_sums(float s0, float s1, float s2, float s3);
+template <bool N4>
+__device__ __attribute__((noinline)) void rel_count_call(const RelCtx c, bool maybe, uint32_t li,
+                                                         uint32_t lj, float s0, float s1,
+                                                         float s2, float s3) {
+  if (!maybe) return;
+  const uint32_t band = rel_band(c.thr, c.num, kin_of_sums<N4>(s0, s1, s2, s3));
+  if (band == kRelNoBand) return;
+  const uint32_t si = c.perm != nullptr ? c.perm[li] : li;
+  const uint32_t sj = c.perm != nullptr ? c.perm[c.col_base + lj] : (c.diag ? lj : c.num_rows + lj);
+  atomicAdd(c.counts + (size_t)si * c.num + band, 1u);
+  atomicAdd(c.counts + (size_t)sj * c.num + band, 1u);
 }
 
 // Full form: a wavefront reserves the slots for ALL records of its 64 x 64 pairs
@@ -1326,19 +1353,23 @@ __device__ __forceinline__ void store_counts(const TiledArgs &a, const Segment &
 // 2 q), with the IEEE divide (pair_kin(), which the summary form shares) -- and one store.
 // Column = lane & 31: the 32 lanes of a half-wave write 128 contiguous bytes of
 // matrix row li.  (An unsorted layout: plane index = stored sample.)
+// (kin_of_sums: from a pair's four accumulators s0 .. s3 -- the relative-counts form passes
+//  them to its out-of-line epilogue)
 template <bool N4>
-__device__ __forceinline__ float pair_kin(const v16f (&acc)[2][2][kNQ], int bi, int bj, int r) {
+__device__ __forceinline__ float kin_of_sums(float s0, float s1, float s2, float s3) {
   if constexpr (N4) {
-    const uint32_t het_i = (uint32_t)(2.f * acc[bi][bj][0][r]);
-    const uint32_t het_j = (uint32_t)(2.f * acc[bi][bj][1][r]);
-    const int32_t num = (int32_t)(het_i + het_j) - 2 * (int32_t)acc[bi][bj][2][r] +
-                        2 * (int32_t)(0.25f * acc[bi][bj][3][r]);
+    const uint32_t het_i = (uint32_t)(2.f * s0);
+    const uint32_t het_j = (uint32_t)(2.f * s1);
+    const int32_t num = (int32_t)(het_i + het_j) - 2 * (int32_t)s2 + 2 * (int32_t)(0.25f * s3);
     return 0.5f + (float)num / (4.f * (float)(het_i < het_j ? het_i : het_j));
   } else {
     // (five products: the accumulators are the reference's own four sums)
-    return king_kinship((uint32_t)acc[bi][bj][2][r], (uint32_t)acc[bi][bj][3][r],
-                        (uint32_t)acc[bi][bj][1][r], (uint32_t)acc[bi][bj][0][r]);
+    return king_kinship((uint32_t)s2, (uint32_t)s3, (uint32_t)s1, (uint32_t)s0);
   }
+}
+template <bool N4>
+__device__ __forceinline__ float pair_kin(const v16f (&acc)[2][2][kNQ], int bi, int bj, int r) {
+  return kin_of_sums<N4>(acc[bi][bj][0][r], acc[bi][bj][1][r], acc[bi][bj][2][r], acc[bi][bj][3][r]);
 }
 template <bool N4>
 __device__ __forceinline__ void store_kin(const TiledArgs &a, const Segment &s, const Lanes &l,
@@ -1468,6 +1499,49 @@ __device__ __forceinline__ void lean_decide(const TiledArgs &a, const Segment &s
   }
 }
 
+// Relative counts (KIN = relative counts): lean_decide's cheap test against the lowest
+// threshold (a.kin_threshold = rel_thr[0]), and only where some lane of the wavefront may pass
+// the exact kinship, its band and the two atomics, out of line (rel_count_call()) -- no record
+// and no hom_hom recount.  Pairs in plane order, like the records: each once.
+template <bool N4>
+__device__ __forceinline__ void count_relatives(const TiledArgs &a, const Segment &s,
+                                                const Lanes &l, const v16f (&acc)[2][2][kNQ]) {
+  const PairOrigin o = pair_origin(s, l);
+  RelCtx c;
+  c.counts = a.rel_counts;
+  c.num = a.rel_num;
+#pragma unroll
+  for (uint32_t t = 0; t < CUKING_REL_THRESHOLDS_MAX; ++t) c.thr[t] = a.rel_thr[t];
+  c.perm = a.perm;
+  c.diag = a.geo.diag;
+  c.num_rows = a.geo.num_rows;
+  c.col_base = a.geo.col_base;
+#pragma unroll
+  for (int bi = 0; bi < 2; ++bi) {
+#pragma unroll
+    for (int bj = 0; bj < 2; ++bj) {
+      const uint32_t lj = pair_col(o, l, bj);
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const uint32_t li = pair_row(o, l, bi, r);
+        const bool valid = pair_valid(a, li, lj);
+        bool maybe;
+        if constexpr (N4) {
+          const float f_hi = 2.f * acc[bi][bj][0][r], f_hj = 2.f * acc[bi][bj][1][r];
+          const float f_num = f_hi + f_hj - 2.f * acc[bi][bj][2][r] + 0.5f * acc[bi][bj][3][r];
+          maybe = valid && kinship_may_pass_num(f_num, fminf(f_hi, f_hj), a.kin_threshold);
+        } else {
+          maybe = valid && kinship_may_pass(acc[bi][bj][2][r], acc[bi][bj][3][r],
+                                            acc[bi][bj][1][r], acc[bi][bj][0][r], a.kin_threshold);
+        }
+        if (__ballot(maybe) != 0)
+          rel_count_call<N4>(c, maybe, li, lj, acc[bi][bj][0][r], acc[bi][bj][1][r],
+                             acc[bi][bj][2][r], acc[bi][bj][3][r]);
+      }
+    }
+  }
+}
+
 // SPLIT = false: workgroup = one tile, all k-steps.
 // SPLIT = true ("stream-k" remainder): the launch's tiles x k-steps are one
 // line of work units cut into equal pieces, one per workgroup, so a remainder
@@ -1482,12 +1556,14 @@ __device__ __forceinline__ void lean_decide(const TiledArgs &a, const Segment &s
 // records; kKinSummary: the summary form (TiledArgs::sum_hist / sum_best), whose epilogue
 // reduces that kinship instead (summarise_kin()) -- instantiations of their own, so that the epilogues of the others carry neither
 // its branch nor its registers (a run-time branch in the shared full epilogue was enough
-// for the five-product full form to reload a spilled value inside its k loop).  The
+// for the five-product full form to reload a spilled value inside its k loop);
+// kRelCounts: the relative-counts form (TiledArgs::rel_counts, count_relatives()), the lean
+// record form without the records, which may run on a sorted layout like it.  The
 // four-product one is the hot path; the five-product one serves contexts of variant 5 and
 // bitsets from 2^22 sites on.
 // The driver: take work -> per segment: hom_hom pass (FULL) -> k loop -> reduce parts
 // (SPLIT, a partial tile) -> epilogue.
-constexpr int kRecords = 0, kKinMatrix = 1, kKinSummary = 2;  // KIN
+constexpr int kRecords = 0, kKinMatrix = 1, kKinSummary = 2, kRelCounts = 3;  // KIN
 template <bool FULL, bool SPLIT, bool N4 = false, int KIN = kRecords>
 __global__ __launch_bounds__(256, 1) void king_mfma_kernel(const TiledArgs a) {
   static_assert(KIN == kRecords || !FULL, "the dense-kinship forms are lean ones");
@@ -1521,6 +1597,8 @@ __global__ __launch_bounds__(256, 1) void king_mfma_kernel(const TiledArgs a) {
       store_kin<N4>(a, s, l, acc);
     } else if constexpr (KIN == kKinSummary) {
       summarise_kin<N4>(a, s, l, lds, acc);
+    } else if constexpr (KIN == kRelCounts) {
+      count_relatives<N4>(a, s, l, acc);
     } else {
       lean_decide<N4>(a, s, l, acc);
     }
@@ -1580,15 +1658,15 @@ size_t mfma_split_scratch_bytes(uint32_t wgs) {
 size_t mfma_split_counter_bytes(uint32_t wgs) { return split_counter_bytes(wgs); }
 
 namespace {
-// launch_shape<FULL, SPLIT, N4, KIN> by run-time flags (kin: kKinMatrix / kKinSummary, which
-// are lean)
+// launch_shape<FULL, SPLIT, N4, KIN> by run-time flags (kin: kKinMatrix / kKinSummary /
+// kRelCounts, which are lean)
 hipError_t launch_form(bool full, bool split, bool nibble, int kin, const TiledArgs &a,
                        const LaunchSwitches &sw, uint64_t blocks, uint32_t lds_bytes,
                        hipStream_t stream) {
-  if (kin < kRecords || kin > kKinSummary || (kin != kRecords && full)) return hipErrorInvalidValue;
+  if (kin < kRecords || kin > kRelCounts || (kin != kRecords && full)) return hipErrorInvalidValue;
   using Launch = hipError_t (*)(const TiledArgs &, const LaunchSwitches &, uint64_t, uint32_t,
                                 hipStream_t);
-  static constexpr Launch kForms[3][2][2][2] = {  // [kin][nibble][split][full]
+  static constexpr Launch kForms[4][2][2][2] = {  // [kin][nibble][split][full]
       {{{launch_shape<false, false, false>, launch_shape<true, false, false>},
         {launch_shape<false, true, false>, launch_shape<true, true, false>}},
        {{launch_shape<false, false, true>, launch_shape<true, false, true>},
@@ -1600,23 +1678,38 @@ hipError_t launch_form(bool full, bool split, bool nibble, int kin, const TiledA
       {{{launch_shape<false, false, false, kKinSummary>, nullptr},
         {launch_shape<false, true, false, kKinSummary>, nullptr}},
        {{launch_shape<false, false, true, kKinSummary>, nullptr},
-        {launch_shape<false, true, true, kKinSummary>, nullptr}}}};
+        {launch_shape<false, true, true, kKinSummary>, nullptr}}},
+      {{{launch_shape<false, false, false, kRelCounts>, nullptr},
+        {launch_shape<false, true, false, kRelCounts>, nullptr}},
+       {{launch_shape<false, false, true, kRelCounts>, nullptr},
+        {launch_shape<false, true, true, kRelCounts>, nullptr}}}};
   return kForms[kin][nibble][split][full](a, sw, blocks, lds_bytes, stream);
 }
 
 // ONE launch of the four-product kernel's lean form with `grid` workgroups that stride over
 // a list or a range, whatever the block limit (a test hook may set it below `grid`; a
 // second launch would walk the list again).
-hipError_t launch_strided(const TiledArgs &a, uint32_t grid, hipStream_t stream) {
-  if ((uint64_t)a.geo.k_words * 32 > kMfmaN4MaxSites) return hipErrorInvalidValue;
-  const uint64_t cap = max_blocks_per_launch(256);
-  if (grid > cap) grid = (uint32_t)cap;
-  if (grid == 0) return hipErrorInvalidValue;
-  constexpr auto kernel = king_mfma_kernel<false, false, true>;
+// The form a thresholded launch runs: records, or (TiledArgs::rel_counts) relative counts --
+// chosen here, on the host.
+int lean_form_of(const TiledArgs &a) { return a.rel_counts != nullptr ? kRelCounts : kRecords; }
+bool rel_args_ok(const TiledArgs &a) {
+  return a.rel_counts == nullptr || (a.rel_num >= 1 && a.rel_num <= CUKING_REL_THRESHOLDS_MAX);
+}
+template <int KIN>
+hipError_t launch_strided_form(const TiledArgs &a, uint32_t grid, hipStream_t stream) {
+  constexpr auto kernel = king_mfma_kernel<false, false, true, KIN>;
   const hipError_t e = allow_dynamic_lds<kernel>(kMfmaN4LdsBytes);
   if (e != hipSuccess) return e;
   kernel<<<dim3(grid), dim3(256), kMfmaN4LdsBytes, stream>>>(a);
   return hipGetLastError();
+}
+hipError_t launch_strided(const TiledArgs &a, uint32_t grid, hipStream_t stream) {
+  if ((uint64_t)a.geo.k_words * 32 > kMfmaN4MaxSites || !rel_args_ok(a)) return hipErrorInvalidValue;
+  const uint64_t cap = max_blocks_per_launch(256);
+  if (grid > cap) grid = (uint32_t)cap;
+  if (grid == 0) return hipErrorInvalidValue;
+  return lean_form_of(a) == kRelCounts ? launch_strided_form<kRelCounts>(a, grid, stream)
+                                       : launch_strided_form<kRecords>(a, grid, stream);
 }
 }  // namespace
 
@@ -1667,7 +1760,10 @@ hipError_t launch_planned_form(bool full, bool nibble, int kin, const TiledArgs 
 
 hipError_t launch_mfma(bool full, bool nibble, const TiledArgs &args, const LaunchSwitches &sw,
                        uint64_t num_tiles, uint32_t lds_bytes, hipStream_t stream) {
-  return launch_planned_form(full, nibble, kRecords, args, sw, num_tiles, lds_bytes, stream);
+  // (a relative-counts call, TiledArgs::rel_counts: the counting form, lean only)
+  if (!rel_args_ok(args)) return hipErrorInvalidValue;
+  return launch_planned_form(full, nibble, lean_form_of(args), args, sw, num_tiles, lds_bytes,
+                             stream);
 }
 
 hipError_t launch_mfma_kin(bool nibble, const TiledArgs &args, const LaunchSwitches &sw,

@@ -70,6 +70,15 @@ def parse_args(argv=None):
          help="LO,HI,N: the histogram of --kin-summary-uri (default -1,0.5,1536; N + 3 slots: "
               "below LO, the N bins, from HI on, NaN); write --kin-summary-bins=-0.25,0.25,64 "
               "when LO is negative")
+    flag("relative-counts-uri", default="",
+         help="also write the block's relative counts -- per sample, the number of partners "
+              "whose kinship falls in each band of a few thresholds, no records and nothing "
+              "that can overflow -- to this .npz file (bands, thresholds, samples).  One "
+              "process only")
+    flag("relative-thresholds", default="",
+         help="A,B,...: the 1 to 8 strictly ascending thresholds of --relative-counts-uri "
+              "(default: the KING cut-offs 0.0442,0.0884,0.177,0.354); write "
+              "--relative-thresholds=-0.1,0.1 when the first is negative")
     return ap.parse_args(argv)
 
 
@@ -101,6 +110,20 @@ def summary_bins(text: str):
     return lo, hi, n
 
 
+def relative_thresholds(text: str):
+    """--relative-thresholds A,B,... -> the thresholds as the library sees them (float32)."""
+    if not text:
+        return (0.0442, 0.0884, 0.177, 0.354)
+    try:
+        thr = np.array([float(x) for x in text.split(",")], dtype=np.float32)
+        if not 1 <= thr.size <= 8 or not np.isfinite(thr).all() or not (np.diff(thr) > 0).all():
+            raise ValueError
+    except ValueError:
+        raise UsageError("--relative_thresholds expects 1 to 8 finite, strictly ascending "
+                         "values A,B,...") from None
+    return tuple(float(t) for t in thr)
+
+
 def validate(args):  # cuking.cu:437-462
     if args.synthetic_model and not args.synthetic:
         raise UsageError("--synthetic_model needs --synthetic")
@@ -124,6 +147,12 @@ def validate(args):  # cuking.cu:437-462
         raise UsageError("--kin_summary_uri needs one process (one GPU): summaries are not "
                          "merged across ranks yet")
     summary_bins(args.kin_summary_bins)
+    if args.relative_thresholds and not args.relative_counts_uri:
+        raise UsageError("--relative_thresholds needs --relative_counts_uri")
+    if args.relative_counts_uri and int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise UsageError("--relative_counts_uri needs one process (one GPU): relative counts "
+                         "are not merged across ranks yet")
+    relative_thresholds(args.relative_thresholds)
 
 
 def read_and_pack(in_dir: Path, sm, num_sites: int, threads: int) -> np.ndarray:
@@ -214,6 +243,19 @@ def write_kin_summary(path: Path, ctx, sm, wps: int, bits, lo: float, hi: float,
                  bins=np.int64(n), best_kin=kin, best_partner=partner)
 
 
+def write_relative_counts(path: Path, ctx, sm, wps: int, bits, thresholds, sample_ids) -> None:
+    """The block's relative counts as an .npz: per stored sample of the block (rows first,
+    then columns; `samples` names them) the partners in each band of `thresholds`."""
+    counts = ctx.relative_counts(sm, wps, bits, thresholds=thresholds)
+    stored = list(range(sm.i_begin, sm.i_end))
+    if sm.i_begin != sm.j_begin:
+        stored += list(range(sm.j_begin, sm.j_end))
+    path.parent.mkdir(parents=True, exist_ok=True)
+    with open(path, "wb") as f:   # (np.savez would append .npz to another suffix)
+        np.savez(f, bands=counts.bands(), thresholds=counts.thresholds,
+                 samples=np.array([sample_ids[k] for k in stored], dtype=str))
+
+
 def main(argv=None) -> int:
     args = parse_args(argv)
     import torch
@@ -230,6 +272,7 @@ def main(argv=None) -> int:
         out_dir = resolve_uri(args.output_uri)
         kin_path = resolve_uri(args.kin_matrix_uri) if args.kin_matrix_uri else None
         summary_path = resolve_uri(args.kin_summary_uri) if args.kin_summary_uri else None
+        counts_path = resolve_uri(args.relative_counts_uri) if args.relative_counts_uri else None
         synthetic = None
         if args.synthetic:
             parts = [int(x) for x in args.synthetic.split(",")]
@@ -356,6 +399,9 @@ def main(argv=None) -> int:
             if summary_path is not None:
                 write_kin_summary(summary_path, ctx, sm, wps, bits,
                                   *summary_bins(args.kin_summary_bins))
+            if counts_path is not None:
+                write_relative_counts(counts_path, ctx, sm, wps, bits,
+                                      relative_thresholds(args.relative_thresholds), sample_ids)
             pairs = sm.NumPairs()
             print(json.dumps({"pairs": pairs, "results": int(len(recs)), "gpus": world,
                               "compute_seconds": dt,

@@ -498,7 +498,8 @@ cuking_status cuking_compute_kin_matrix_tiles(cuking_ctx *ctx, const cuking_subm
  * empty block returns OK.  Asynchronous on `stream`; workspace, stream ordering and
  * "reuse_prepared" as for the other compute entry points.
  * Out of scope: the C++ `cuking` binary, merging across ranks (the tiles form and the merge
- * rules make it possible), IBS0/1/2 summaries, per-sample relative counts. */
+ * rules make it possible), IBS0/1/2 summaries.  (Per-sample relative counts at thresholds:
+ * cuking_compute_relative_counts below.) */
 #define CUKING_KIN_BINS_MAX 4096u
 typedef struct cuking_kin_bins {
   float lo, hi;
@@ -520,6 +521,67 @@ cuking_status cuking_compute_kin_summary_tiles(cuking_ctx *ctx, const cuking_sub
                                                uint64_t tile_begin, uint64_t tile_end,
                                                const cuking_kin_bins *bins, uint64_t *d_hist,
                                                uint64_t *d_best, void *stream);
+
+/* Relative counts: for every sample of the block, how many partners it has in each band of a
+ * few kinship thresholds -- what "drop samples with too many relatives", ordering a maximal-
+ * independent-set pruning by degree and sorting a cohort into duplicate / 1st / 2nd / 3rd
+ * degree partners at the KING cut-offs (0.354, 0.177, 0.0884, 0.0442) need, and the exact
+ * max_results of a following cuking_compute_king.  No records, no buffer that can overflow.
+ *
+ * Thresholds: a HOST array of 1 .. CUKING_REL_THRESHOLDS_MAX finite float32 values, strictly
+ * ascending.  The BAND of a kinship is the largest t with kin > thresholds[t]: a strict
+ * float32 comparison, the one a record's `kin > kin_threshold` makes; 0xFFFFFFFF = none (NaN
+ * and -inf never get a band).  cuking_rel_band evaluates the rule on the host (0xFFFFFFFF
+ * also for thresholds the compute call would refuse).
+ *
+ * d_counts[cuking_submatrix_sample_offset(s) * num_thresholds + t] (uint32,
+ * cuking_submatrix_num_samples x num_thresholds entries: rows first, then columns, a diagonal
+ * block's samples once) = the number of partners of stored sample s whose kinship with it
+ * falls in band t.  Every pair the block holds is counted once (cuking_submatrix_num_pairs):
+ * a pair in band t adds 1 at both its samples.  "Partners with kin > thresholds[t]" are the
+ * suffix sums over t, taken on the host.  The output ACCUMULATES, like d_hist and
+ * d_result_index: the call does not reset it, the caller zeroes it; calls over disjoint tile
+ * ranges (the tiles form follows cuking_compute_king_tiles) add up to the whole call.  Entries
+ * sit at the STORED samples' positions whatever "filter_sort" says.
+ *
+ * The value counted is the numerics contract's kin above, bit for bit what a record carries:
+ * for every t, the suffix-summed count of a sample equals the number of records of
+ * cuking_compute_king(kin_threshold = thresholds[t]) that name it, and the column sum (halved
+ * on a diagonal block; over the rows of an off-diagonal one) is that call's record count.  The
+ * result depends on no tuning option.
+ *
+ * Cost: that of cuking_compute_king at thresholds[0], less the records -- the same layout
+ * (sorted, with the filter's statistics: with "reuse_prepared" a count call followed by a
+ * record call on the same bitset converts once), the same filter kernel and bound where 0 <
+ * thresholds[0] < 1/2 on a context of variant 7, and counting forms of the kernels behind it
+ * that skip the 24-byte record and the hom/hom recount: one atomic per end of a pair above
+ * thresholds[0], nothing for the others.
+ * INVALID_ARGUMENT, before any device is touched: a null context, submatrix, bitset,
+ * thresholds or d_counts; num_thresholds 0 or above CUKING_REL_THRESHOLDS_MAX; thresholds that
+ * are not finite or not strictly ascending; a bad tile range; a context that is not the tiled
+ * kernel with variant 5, 6 or 7, and bitsets from 2^24 sites on.  An empty block returns OK.
+ * Asynchronous on `stream` (the thresholds are read before the call returns); workspace,
+ * stream ordering, cuking_ctx_reserve and "reuse_prepared" as for the other compute entry
+ * points.
+ * Out of scope: the C++ `cuking` binary; merging across ranks (the tiles form and the merge
+ * rule -- counts add -- make it possible); splitting first degree into parent-child and
+ * siblings by IBS0 (the counting forms do not hold the hom/hom count); the VALU and stream
+ * kernels. */
+#define CUKING_REL_THRESHOLDS_MAX 8u
+/* Host-only. */
+uint32_t cuking_rel_band(const float *thresholds, uint32_t num_thresholds, float kin);
+cuking_status cuking_compute_relative_counts(cuking_ctx *ctx, const cuking_submatrix *sm,
+                                             uint32_t words_per_sample,
+                                             const uint64_t *d_bit_sets,
+                                             const float *thresholds, uint32_t num_thresholds,
+                                             uint32_t *d_counts, void *stream);
+cuking_status cuking_compute_relative_counts_tiles(cuking_ctx *ctx, const cuking_submatrix *sm,
+                                                   uint32_t words_per_sample,
+                                                   const uint64_t *d_bit_sets,
+                                                   uint64_t tile_begin, uint64_t tile_end,
+                                                   const float *thresholds,
+                                                   uint32_t num_thresholds, uint32_t *d_counts,
+                                                   void *stream);
 
 /* cuking.cu:761-765 on host memory: sort by (sample_i, sample_j, kin). */
 void cuking_sort_results(cuking_result *results, size_t num_results);
