@@ -7,6 +7,7 @@ is loaded on first use and there is no CPU fallback.
 from .api import (DEFAULT_KIN_THRESHOLD, DEFAULT_MAX_RESULTS,  # noqa: F401
                   KING_COUNTS_DTYPE, KING_CUTOFFS, KING_RESULT_DTYPE, CukingError,
                   RelativeCounts, relative_counts,
+                  UnrelatedSet, family_members, unrelated_key, unrelated_set, unrelated_set_host,
                   KingContext, KinSummary, ResourceExhaustedError, Submatrix,
                   bytes_per_pair, device_count, kin_matrix, kin_summary, new_host_bitset,
                   pack_host,

@@ -131,6 +131,10 @@ SIGNATURES = {
                                               _vp]),
     "cuking_compute_relative_counts_tiles": (_int, [_vp, _SM, _u32, _vp, _u64, _u64,
                                                     C.POINTER(_f32), _u32, _vp, _vp]),
+    "cuking_unrelated_key": (_u64, [_f32, _u32]),
+    "cuking_unrelated_set_host": (_int, [_vp, _u64, _u32, _f32, _vp, _vp, _vp]),
+    "cuking_unrelated_set": (_int, [_vp, _vp, _u64, _u32, _f32, _vp, _vp, _vp, C.POINTER(_u32),
+                                    _vp]),
     "cuking_sort_results": (None, [_vp, _sz]),
     "cuking_timing_enable": (_int, [_vp, _int]),
     "cuking_timing_reset": (_int, [_vp]),

@@ -437,6 +437,86 @@ class KingContext:
         return self.relative_counts(submatrix, words_per_sample, bit_sets,
                                     thresholds=(kin_threshold,)).num_records(0)
 
+    def unrelated_set(self, records, num_records: int, num_samples: int,
+                      prune_threshold: float = float("-inf"), priority=None,
+                      families: bool = True, stream=None) -> "UnrelatedSet":
+        """Unrelated set and families from the records (cuking_unrelated_set), on the
+        device.  ``records``: the device ``[*, 6]`` int32 tensor ``compute_king`` appended
+        to (several shards' buffers may be concatenated; repeats count once),
+        ``num_records`` its ``result_index``.  A record is an edge when ``kin >
+        prune_threshold`` (strict float32).  ``priority``: an optional float32 device
+        tensor of ``num_samples`` -- the higher priority is kept first, among equals the
+        lower index, NaN last; without it ``-degree`` (distinct partners).  Returns an
+        ``UnrelatedSet``: ``keep[s]`` = 1 iff no neighbour of s was kept before it in that
+        order, ``family[s]`` = the lowest index of s's connected component.  A record that
+        does not satisfy ``sample_i < sample_j < num_samples`` raises ``CukingError``
+        (invalid argument).  WAITS for the stream."""
+        import torch
+        num_records, num_samples = _count(num_records, "num_records"), _count(num_samples,
+                                                                               "num_samples")
+        thr = float(np.float32(prune_threshold))
+        if thr != thr:
+            raise ValueError("prune_threshold must not be NaN")
+        if not isinstance(records, torch.Tensor):
+            raise ValueError("records must be a device tensor (unrelated_set_host takes numpy)")
+        if not records.is_cuda or records.device.index != self.device:
+            raise ValueError("records must live on this context's GPU")
+        if records.dtype != torch.int32:
+            raise ValueError("records must be an int32 tensor (KingResult records)")
+        if records.dim() != 2 or records.shape[1] != 6 or not records.is_contiguous():
+            raise ValueError(f"records must be a contiguous [*, 6] tensor, not "
+                             f"{tuple(records.shape)}")
+        if records.shape[0] < num_records:
+            raise ValueError(f"records holds {records.shape[0]} records, num_records is "
+                             f"{num_records}")
+        if priority is not None:
+            if not isinstance(priority, torch.Tensor) or not priority.is_cuda or \
+                    priority.device.index != self.device:
+                raise ValueError("priority must live on this context's GPU")
+            if priority.dtype != torch.float32:
+                raise ValueError("priority must be a float32 tensor")
+            if tuple(priority.shape) != (num_samples,) or not priority.is_contiguous():
+                raise ValueError(f"priority must be a contiguous vector of {num_samples} "
+                                 f"entries, not {tuple(priority.shape)}")
+        dev = f"cuda:{self.device}"
+        keep = torch.empty(num_samples, dtype=torch.uint8, device=dev)
+        family = torch.empty(num_samples, dtype=torch.int32, device=dev) if families else None
+        rounds = C.c_uint32(0)
+        check(self.lib.cuking_unrelated_set(
+            self.handle, records.data_ptr() if num_records else None, num_records, num_samples,
+            thr, priority.data_ptr() if priority is not None else None,
+            keep.data_ptr() if num_samples else None,
+            family.data_ptr() if families and num_samples else None, C.byref(rounds),
+            _stream_handle(stream)))
+        return UnrelatedSet(keep, family, int(rounds.value), thr, self.device)
+
+    def prune(self, submatrix: Submatrix, words_per_sample: int, bit_sets,
+              kin_threshold: float, priority=None, families: bool = True) -> "UnrelatedSet":
+        """From bitsets to "these samples stay" for a whole-cohort diagonal block:
+        ``count_records`` for the exact buffer size, ``compute_king`` at ``kin_threshold``,
+        then ``unrelated_set`` on the records where they lie.  Waits for the device."""
+        import torch
+        if not (submatrix.i_begin == submatrix.j_begin == 0 and
+                submatrix.i_end == submatrix.j_end):
+            raise ValueError(
+                f"prune needs the whole-cohort diagonal block, not {submatrix!r}: for several "
+                "shards concatenate their record buffers and call unrelated_set(records, "
+                "num_records, num_samples)")
+        dev = f"cuda:{self.device}"
+        count = self.count_records(submatrix, words_per_sample, bit_sets, kin_threshold)
+        results = torch.zeros((max(count, 1), 6), dtype=torch.int32, device=dev)
+        index_and_flag = torch.zeros(2, dtype=torch.int32, device=dev)
+        if submatrix.NumSamples() > 1:
+            self.compute_king(submatrix, words_per_sample, bit_sets, kin_threshold, count,
+                              results, index_and_flag[0:1], index_and_flag[1:2])
+        torch.cuda.synchronize(self.device)
+        written, overflow = (int(x) & 0xFFFFFFFF for x in index_and_flag.tolist())
+        if overflow or written != count:
+            raise RuntimeError(f"the record call wrote {written} records (overflow {overflow}), "
+                               f"the count call announced {count}")
+        return self.unrelated_set(results, count, submatrix.i_end, kin_threshold,
+                                  priority=priority, families=families)
+
     def run(self, submatrix: Submatrix, words_per_sample: int, bit_sets,
             kin_threshold: float = DEFAULT_KIN_THRESHOLD,
             max_results: int = DEFAULT_MAX_RESULTS, tile_range=None,
@@ -623,6 +703,92 @@ class RelativeCounts:
         return int(column[:sm.NumRows()].sum())
 
 
+def _count(value, name: str) -> int:
+    if isinstance(value, bool) or int(value) != value or int(value) < 0:
+        raise ValueError(f"{name} must be a non-negative integer, not {value!r}")
+    return int(value)
+
+
+class UnrelatedSet:
+    """What ``KingContext.unrelated_set`` returns: the device tensors ``keep`` (uint8, 1 =
+    kept) and ``family`` (int32, a view of uint32 data: the lowest sample index of each
+    sample's connected component; None without ``families``), and ``rounds``, the number of
+    rounds of the parallel greedy that had a live edge (the call has waited: an int).  The
+    accessors copy to the host."""
+
+    def __init__(self, keep, family, rounds: int, prune_threshold: float, device: int):
+        self.keep, self.family, self.rounds = keep, family, rounds
+        self.prune_threshold, self.device = prune_threshold, device
+
+    def kept(self) -> np.ndarray:
+        """Indices of the kept samples, ascending."""
+        return np.flatnonzero(self.keep.cpu().numpy() == 1)
+
+    def dropped(self) -> np.ndarray:
+        """Indices of the dropped samples, ascending."""
+        return np.flatnonzero(self.keep.cpu().numpy() != 1)
+
+    def families(self) -> dict:
+        """root -> members (ascending) for every component of at least two samples."""
+        if self.family is None:
+            raise ValueError("this UnrelatedSet was computed with families=False")
+        return family_members(self.family.cpu().numpy().view(np.uint32))
+
+
+def family_members(family: np.ndarray) -> dict:
+    """root -> members (ascending index arrays) of the components of size >= 2 of a
+    ``family`` vector."""
+    family = np.asarray(family)
+    order = np.argsort(family, kind="stable")
+    roots, starts, sizes = np.unique(family[order], return_index=True, return_counts=True)
+    return {int(r): order[b:b + n] for r, b, n in zip(roots, starts, sizes) if n >= 2}
+
+
+def unrelated_set(ctx: KingContext, records, num_records: int, num_samples: int,
+                  **kwargs) -> UnrelatedSet:
+    """``ctx.unrelated_set(...)``: unrelated set and families from device records."""
+    return ctx.unrelated_set(records, num_records, num_samples, **kwargs)
+
+
+def unrelated_key(priority: float, sample: int) -> int:
+    """cuking_unrelated_key: the uint64 order key of a sample (host helper)."""
+    return int(_lib.load().cuking_unrelated_key(float(np.float32(priority)), int(sample)))
+
+
+def unrelated_set_host(records, num_samples: int, prune_threshold: float = float("-inf"),
+                       priority=None, families: bool = True):
+    """cuking_unrelated_set_host: the same contract on host memory, without a GPU.
+    ``records``: a numpy array of KING_RESULT_DTYPE records, or ``[*, 6]`` int32 / uint32
+    words.  Returns ``(keep uint8, family uint32 or None)``."""
+    num_samples = _count(num_samples, "num_samples")
+    recs = np.asarray(records)
+    if recs.dtype == KING_RESULT_DTYPE:
+        recs = recs.reshape(-1)
+    elif recs.dtype in (np.dtype(np.int32), np.dtype(np.uint32)) and \
+            (recs.ndim == 2 and recs.shape[1] == 6 or recs.size == 0):
+        recs = recs.reshape(-1, 6)
+    else:
+        raise ValueError("records must be KING_RESULT_DTYPE records or [*, 6] int32 / uint32 "
+                         f"words, not {recs.dtype} {recs.shape}")
+    recs = np.ascontiguousarray(recs)
+    thr = float(np.float32(prune_threshold))
+    if thr != thr:
+        raise ValueError("prune_threshold must not be NaN")
+    prio = None
+    if priority is not None:
+        prio = np.ascontiguousarray(priority, dtype=np.float32)
+        if prio.shape != (num_samples,):
+            raise ValueError(f"priority must be a vector of {num_samples} entries, not "
+                             f"{prio.shape}")
+    keep = np.zeros(num_samples, dtype=np.uint8)
+    family = np.zeros(num_samples, dtype=np.uint32) if families else None
+    check(_lib.load().cuking_unrelated_set_host(
+        recs.ctypes.data if recs.shape[0] else None, recs.shape[0], num_samples, thr,
+        prio.ctypes.data if prio is not None else None, keep.ctypes.data if num_samples else None,
+        family.ctypes.data if families and num_samples else None))
+    return keep, family
+
+
 def kin_matrix(ctx: KingContext, submatrix: Submatrix, words_per_sample: int, bit_sets,
                **kwargs):
     """``ctx.kin_matrix(...)``: the dense float32 kinship matrix of a block."""
@@ -644,6 +810,7 @@ def relative_counts(ctx: KingContext, submatrix: Submatrix, words_per_sample: in
 __all__ = [
     "Submatrix", "KingContext", "kin_matrix", "kin_summary", "KinSummary",
     "relative_counts", "RelativeCounts", "KING_CUTOFFS",
+    "unrelated_set", "unrelated_set_host", "unrelated_key", "UnrelatedSet", "family_members",
     "KING_RESULT_DTYPE", "KING_COUNTS_DTYPE",
     "ResourceExhaustedError", "CukingError", "padded_sites",
     "words_per_sample", "bytes_per_pair", "new_host_bitset", "pack_host",

@@ -27,7 +27,7 @@ CLI_PATH = PKG / "bin" / "cuking"
 LIB_FLAGS_PATH = PKG / "libcuking_amd.flags"
 
 HIP_SOURCES = ["king_abi.hip", "king_kernels.hip", "king_mfma.hip", "king_filter.hip",
-               "king_sort.hip", "synth.hip"]
+               "king_sort.hip", "king_prune.hip", "synth.hip"]
 # Host-only half of the ABI: plain C++, also compiled by the sanitizer tests.
 HOST_ABI_SOURCES = ["king_host.cc"]
 # IEEE-correct fp32 divide (kinship must match the reference bit for bit):
@@ -64,7 +64,7 @@ def build_library(force: bool = False, save_temps: bool = False) -> Path:
     srcs = [CSRC / s for s in HIP_SOURCES + HOST_ABI_SOURCES]
     deps = srcs + [CSRC / "king_common.h", CSRC / "king_device.h", CSRC / "king_host.h",
                    CSRC / "king_launch_plan.h", CSRC / "king_kin_summary.h",
-                   CSRC / "king_submatrix.h", INCLUDE / "cuking_amd.h",
+                   CSRC / "king_unrelated.h", CSRC / "king_submatrix.h", INCLUDE / "cuking_amd.h",
                    Path(__file__)]
     extra = os.environ.get("CUKING_EXTRA_HIPFLAGS", "").split()
     wanted = " ".join(extra)

@@ -13,6 +13,7 @@
 #include "king_common.h"
 #include "king_host.h"
 #include "king_kin_summary.h"
+#include "king_unrelated.h"
 
 using namespace cuking;
 
@@ -104,6 +105,7 @@ struct cuking_ctx {
   // Remainder splitting of the matrix-core kernel (king_mfma.hip): split_wgs
   // workgroups = one per CU.  0 = never split.
   uint32_t split_wgs = 0;
+  uint32_t num_cus = 0;  // what cuking_unrelated_set sizes its grids from
   // Scratch of one stream that launches pair kernels (launches on different streams may
   // overlap): the matrix-core kernel's zeroed remainder slab, and the filter variant's
   // control words, candidate list, dense-quadrant list and slabs (king_filter.hip), sized
@@ -114,6 +116,9 @@ struct cuking_ctx {
     uint32_t *split = nullptr;
     uint8_t *filter = nullptr;
     uint64_t filter_tiles = 0;
+    // cuking_unrelated_set's workspace (king_prune.hip), grown when a call needs more
+    void *prune = nullptr;
+    size_t prune_bytes = 0;
   };
   std::vector<StreamScratch> scratch;
   // The running totals of filter scratch that has been freed since (a larger block took
@@ -335,6 +340,7 @@ void evict_scratch(cuking_ctx *ctx, size_t k) {
   }
   free_filter_scratch(ctx, e);
   if (e.split != nullptr) (void)hipFree(e.split);
+  if (e.prune != nullptr) (void)hipFree(e.prune);
   ctx->scratch.erase(ctx->scratch.begin() + (ptrdiff_t)k);
 }
 
@@ -1030,6 +1036,7 @@ cuking_status cuking_ctx_create(int device, cuking_ctx **out) {
   ctx->device = device;
   ctx->variant = default_variant();
   ctx->split_wgs = (uint32_t)prop.multiProcessorCount;
+  ctx->num_cus = (uint32_t)prop.multiProcessorCount;
   *out = ctx;
   return CUKING_OK;
 }
@@ -1045,6 +1052,7 @@ void cuking_ctx_destroy(cuking_ctx *ctx) {
   for (auto &e : ctx->scratch) {
     if (e.split) (void)hipFree(e.split);
     if (e.filter) (void)hipFree(e.filter);
+    if (e.prune) (void)hipFree(e.prune);
   }
   for (auto &r : ctx->readers)
     if (r.second) (void)hipEventDestroy(r.second);
@@ -1811,6 +1819,79 @@ cuking_status cuking_compute_relative_counts_tiles(cuking_ctx *ctx, const cuking
                                                    void *stream) {
   return run_rel(ctx, sm, words_per_sample, d_bit_sets, false, tile_begin, tile_end, thresholds,
                  num_thresholds, d_counts, stream);
+}
+
+// ---- unrelated set and families from the records (king_unrelated.h, king_prune.hip) --------
+
+cuking_status cuking_unrelated_set(cuking_ctx *ctx, const cuking_result *d_records,
+                                   uint64_t num_records, uint32_t num_samples,
+                                   float prune_threshold, const float *d_priority,
+                                   uint8_t *d_keep, uint32_t *d_family, uint32_t *rounds,
+                                   void *stream) {
+  if (rounds != nullptr) *rounds = 0;
+  if (ctx == nullptr) return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "null context");
+  if (!unrel_threshold_valid(prune_threshold))
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "unrelated set: prune_threshold is NaN");
+  if (num_records != 0 && d_records == nullptr)
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "unrelated set: null records pointer");
+  if (num_samples != 0 && d_keep == nullptr)
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "unrelated set: null keep pointer");
+  if (num_samples > kUnrelMaxSamples || num_records > kUnrelMaxRecords)
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT,
+                       "unrelated set: at most 2^31 samples and 2^30 records are served");
+  if (num_samples == 0 && num_records != 0)
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT,
+                       "unrelated set: records name samples outside [0, num_samples)");
+  if (num_samples == 0) return CUKING_OK;
+  cuking_status st = bind(ctx);
+  if (st != CUKING_OK) return st;
+  // The stream's entry of the scratch cache; the workspace is sized once per call, in front
+  // of the round loop, and grown only when a call needs more.
+  hipStream_t s = (hipStream_t)stream;
+  cuking_ctx::StreamScratch *e = nullptr;
+  for (auto &x : ctx->scratch)
+    if (x.stream == s) e = &x;
+  if (e == nullptr) {
+    if (ctx->scratch.size() >= kMaxStreams) evict_scratch(ctx, 0);
+    ctx->scratch.push_back({s});
+    e = &ctx->scratch.back();
+  }
+  const size_t bytes = prune_workspace_bytes((uint32_t)num_records, num_samples,
+                                             d_priority == nullptr);
+  if (e->prune_bytes < bytes) {
+    if (e->prune != nullptr) {  // an earlier call on this stream may still run
+      ++ctx->host_syncs;
+      HIP_TRY(hipStreamSynchronize(s));
+      (void)hipFree(e->prune);
+      e->prune = nullptr;
+      e->prune_bytes = 0;
+    }
+    HIP_TRY(hipMalloc(&e->prune, bytes));
+    ++ctx->workspace_allocations;
+    e->prune_bytes = bytes;
+  }
+  uint32_t done = 0, syncs = 0;
+  int invalid = 0, exceeded = 0;
+  const int err = prune_run(e->prune, d_records, (uint32_t)num_records, num_samples,
+                            prune_threshold, d_priority, d_keep, d_family, ctx->num_cus, &done,
+                            &syncs, &invalid, &exceeded, stream);
+  ctx->host_syncs += syncs;
+  if (err != 0) {
+    (void)hipGetLastError();
+    return cuking_fail((hipError_t)err == hipErrorOutOfMemory ? CUKING_ERR_OUT_OF_MEMORY
+                                                              : CUKING_ERR_DEVICE,
+                       "unrelated set: %s", hipGetErrorString((hipError_t)err));
+  }
+  if (invalid)
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT,
+                       "unrelated set: a record does not satisfy sample_i < sample_j < "
+                       "num_samples (%u)", num_samples);
+  if (exceeded)
+    return cuking_fail(CUKING_ERR_DEVICE,
+                       "unrelated set: internal error, a loop ran past its bound of %u rounds",
+                       num_samples);
+  if (rounds != nullptr) *rounds = done;
+  return CUKING_OK;
 }
 
 // ---- timing ---------------------------------------------------------------

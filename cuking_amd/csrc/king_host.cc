@@ -10,6 +10,7 @@
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
+#include <numeric>
 #include <string>
 #include <tuple>
 #include <vector>
@@ -17,6 +18,7 @@
 #include "../host/schedule.h"
 #include "king_submatrix.h"
 #include "king_kin_summary.h"
+#include "king_unrelated.h"
 
 using namespace cuking;
 
@@ -347,6 +349,80 @@ uint32_t cuking_kin_best_decode(uint64_t key, float *kin, uint32_t *partner) {
 uint32_t cuking_rel_band(const float *thresholds, uint32_t num_thresholds, float kin) {
   if (!rel_thresholds_valid(thresholds, num_thresholds)) return kRelNoBand;
   return rel_band(thresholds, num_thresholds, kin);
+}
+
+// ---- unrelated set and families: the contract of king_unrelated.h with the plain algorithms --
+uint64_t cuking_unrelated_key(float priority, uint32_t sample) { return unrel_key(priority, sample); }
+
+cuking_status cuking_unrelated_set_host(const cuking_result *records, uint64_t num_records,
+                                        uint32_t num_samples, float prune_threshold,
+                                        const float *priority, uint8_t *keep, uint32_t *family) {
+  if (!unrel_threshold_valid(prune_threshold))
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "unrelated set: prune_threshold is NaN");
+  if (num_records != 0 && records == nullptr)
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "unrelated set: null records pointer");
+  if (num_samples != 0 && keep == nullptr)
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "unrelated set: null keep pointer");
+  // The edge set: valid records above the threshold, each pair once.
+  std::vector<uint64_t> edges;
+  for (uint64_t r = 0; r < num_records; ++r) {
+    const cuking_result &rec = records[r];
+    if (!unrel_record_valid(rec.sample_i, rec.sample_j, num_samples))
+      return cuking_fail(CUKING_ERR_INVALID_ARGUMENT,
+                         "unrelated set: a record does not satisfy sample_i < sample_j < "
+                         "num_samples (%u)", num_samples);
+    if (unrel_is_edge(rec.kin, prune_threshold))
+      edges.push_back(unrel_edge_word(rec.sample_i, rec.sample_j));
+  }
+  std::sort(edges.begin(), edges.end());
+  edges.erase(std::unique(edges.begin(), edges.end()), edges.end());
+  // Adjacency (CSR); a sample's row length is its number of distinct partners.
+  std::vector<uint64_t> row(num_samples + (size_t)1, 0);
+  for (const uint64_t e : edges) {
+    ++row[(uint32_t)(e >> 32) + (size_t)1];
+    ++row[(uint32_t)e + (size_t)1];
+  }
+  for (size_t s = 0; s < num_samples; ++s) row[s + 1] += row[s];
+  std::vector<uint32_t> adj(2 * edges.size());
+  {
+    std::vector<uint64_t> fill(row.begin(), row.end() - 1);
+    for (const uint64_t e : edges) {
+      const uint32_t i = (uint32_t)(e >> 32), j = (uint32_t)e;
+      adj[fill[i]++] = j;
+      adj[fill[j]++] = i;
+    }
+  }
+  std::vector<uint64_t> key(num_samples);
+  for (uint32_t s = 0; s < num_samples; ++s)
+    key[s] = unrel_key(priority != nullptr
+                           ? priority[s]
+                           : unrel_default_priority((uint32_t)(row[s + (size_t)1] - row[s])),
+                       s);
+  // The sequential greedy in descending key order.
+  std::vector<uint32_t> order(num_samples);
+  std::iota(order.begin(), order.end(), 0u);
+  std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return key[a] > key[b]; });
+  for (uint32_t s = 0; s < num_samples; ++s) keep[s] = kUnrelDropped;
+  for (const uint32_t s : order) {
+    bool related = false;
+    for (uint64_t k = row[s]; k < row[s + (size_t)1] && !related; ++k)
+      related = keep[adj[k]] == kUnrelKept;
+    if (!related) keep[s] = kUnrelKept;
+  }
+  if (family == nullptr) return CUKING_OK;
+  // Union-find, the lower root wins: a component's root is its lowest index.
+  std::vector<uint32_t> parent(num_samples);
+  std::iota(parent.begin(), parent.end(), 0u);
+  auto find = [&](uint32_t x) {
+    while (parent[x] != x) x = parent[x] = parent[parent[x]];
+    return x;
+  };
+  for (const uint64_t e : edges) {
+    const uint32_t a = find((uint32_t)(e >> 32)), b = find((uint32_t)e);
+    if (a != b) parent[std::max(a, b)] = std::min(a, b);
+  }
+  for (uint32_t s = 0; s < num_samples; ++s) family[s] = find(s);
+  return CUKING_OK;
 }
 
 void cuking_sort_results(cuking_result *results, size_t num_results) {

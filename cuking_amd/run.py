@@ -79,6 +79,18 @@ def parse_args(argv=None):
          help="A,B,...: the 1 to 8 strictly ascending thresholds of --relative-counts-uri "
               "(default: the KING cut-offs 0.0442,0.0884,0.177,0.354); write "
               "--relative-thresholds=-0.1,0.1 when the first is negative")
+    flag("unrelated-uri", default="",
+         help="also write the unrelated set and the families of the records' graph -- which "
+              "samples to keep so that no two kept samples are related, computed on the GPU "
+              "from the records -- to this .npz file (keep, family, samples, threshold).  One "
+              "process and --split-factor 1 only")
+    flag("unrelated-priority", default="",
+         help="a .npy file of one float32 priority per sample for --unrelated-uri: the higher "
+              "priority is kept first, among equals the earlier sample (default: fewer "
+              "relatives first)")
+    flag("unrelated-threshold", type=float, default=None,
+         help="records with kin above this are the edges of --unrelated-uri (default: "
+              "--kin-threshold; not below it)")
     return ap.parse_args(argv)
 
 
@@ -153,6 +165,29 @@ def validate(args):  # cuking.cu:437-462
         raise UsageError("--relative_counts_uri needs one process (one GPU): relative counts "
                          "are not merged across ranks yet")
     relative_thresholds(args.relative_thresholds)
+    if (args.unrelated_priority or args.unrelated_threshold is not None) and \
+            not args.unrelated_uri:
+        raise UsageError("--unrelated_priority and --unrelated_threshold need --unrelated_uri")
+    if args.unrelated_uri and int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise UsageError("--unrelated_uri needs one process (one GPU): unrelated sets are not "
+                         "merged across ranks yet")
+    if args.unrelated_uri and args.split_factor != 1:
+        raise UsageError("--unrelated_uri needs --split_factor 1: the unrelated set is a "
+                         "property of the whole cohort's records (concatenate the shards' "
+                         "record buffers and call unrelated_set instead)")
+    unrelated_threshold(args)
+
+
+def unrelated_threshold(args) -> float:
+    """--unrelated-threshold as the library sees it (float32); --kin-threshold without it."""
+    kin = float(np.float32(args.kin_threshold))
+    if args.unrelated_threshold is None:
+        return kin
+    t = float(np.float32(args.unrelated_threshold))
+    if t != t or t < kin:
+        raise UsageError("--unrelated_threshold must not be below --kin_threshold (the records "
+                         "hold no pair below it)")
+    return t
 
 
 def read_and_pack(in_dir: Path, sm, num_sites: int, threads: int) -> np.ndarray:
@@ -256,6 +291,30 @@ def write_relative_counts(path: Path, ctx, sm, wps: int, bits, thresholds, sampl
                  samples=np.array([sample_ids[k] for k in stored], dtype=str))
 
 
+def write_unrelated(path: Path, ctx, recs: np.ndarray, sample_ids, threshold: float,
+                    priority_path, device: int) -> None:
+    """The unrelated set and the families of the records' graph as an .npz: per sample of the
+    cohort (`samples` names them) `keep` (1 = stays) and `family` (the lowest index of its
+    connected component), and the `threshold` above which a record was an edge."""
+    import torch
+    n = len(sample_ids)
+    priority = None
+    if priority_path is not None:
+        host = np.load(priority_path)
+        if host.shape != (n,):
+            raise ValueError(f"--unrelated_priority holds {host.shape}, the cohort has {n} samples")
+        priority = torch.from_numpy(np.ascontiguousarray(host, dtype=np.float32)).to(
+            f"cuda:{device}")
+    words = np.ascontiguousarray(recs).view(np.int32).reshape(-1, 6)
+    records = torch.from_numpy(words).to(f"cuda:{device}")
+    got = ctx.unrelated_set(records, len(recs), n, threshold, priority=priority)
+    path.parent.mkdir(parents=True, exist_ok=True)
+    with open(path, "wb") as f:   # (np.savez would append .npz to another suffix)
+        np.savez(f, keep=got.keep.cpu().numpy(),
+                 family=got.family.cpu().numpy().view(np.uint32),
+                 samples=np.array(list(sample_ids), dtype=str), threshold=np.float32(threshold))
+
+
 def main(argv=None) -> int:
     args = parse_args(argv)
     import torch
@@ -273,6 +332,8 @@ def main(argv=None) -> int:
         kin_path = resolve_uri(args.kin_matrix_uri) if args.kin_matrix_uri else None
         summary_path = resolve_uri(args.kin_summary_uri) if args.kin_summary_uri else None
         counts_path = resolve_uri(args.relative_counts_uri) if args.relative_counts_uri else None
+        unrelated_path = resolve_uri(args.unrelated_uri) if args.unrelated_uri else None
+        priority_path = resolve_uri(args.unrelated_priority) if args.unrelated_priority else None
         synthetic = None
         if args.synthetic:
             parts = [int(x) for x in args.synthetic.split(",")]
@@ -402,6 +463,9 @@ def main(argv=None) -> int:
             if counts_path is not None:
                 write_relative_counts(counts_path, ctx, sm, wps, bits,
                                       relative_thresholds(args.relative_thresholds), sample_ids)
+            if unrelated_path is not None:
+                write_unrelated(unrelated_path, ctx, recs, sample_ids, unrelated_threshold(args),
+                                priority_path, local_rank)
             pairs = sm.NumPairs()
             print(json.dumps({"pairs": pairs, "results": int(len(recs)), "gpus": world,
                               "compute_seconds": dt,

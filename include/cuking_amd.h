@@ -583,6 +583,53 @@ cuking_status cuking_compute_relative_counts_tiles(cuking_ctx *ctx, const cuking
                                                    uint32_t num_thresholds, uint32_t *d_counts,
                                                    void *stream);
 
+/* Unrelated set and families from the records: which samples to keep so that no two kept
+ * samples are related, and which samples form one family -- the step behind the records, on the
+ * buffer cuking_compute_king wrote, without a trip to the host (24 B per record otherwise).
+ *
+ * Edge: a record with kin > prune_threshold (strict float32, the comparison a record itself
+ * makes; NaN is refused, -inf takes every record with a defined kinship above -inf).  Records
+ * may repeat (the concatenated buffers of several shards); repeats count once.  EVERY record
+ * must satisfy sample_i < sample_j < num_samples: one that does not makes the call fail with
+ * CUKING_ERR_INVALID_ARGUMENT, and nothing outside the per-sample arrays is read or written
+ * because of it (the outputs are then unspecified).
+ * Priority key: one uint64 per sample, cuking_unrelated_key(priority[s], s) =
+ * cuking_kin_best_key(priority[s], s) for a number -- the higher priority wins, among equals
+ * the LOWER sample index --; a NaN priority is lower than every number: high word 0, low word
+ * ~s.  Without priorities (NULL): -(float)degree[s], degree = the number of DISTINCT partners
+ * of s among the edges -- fewer relatives first.
+ * Unrelated set: the samples taken in descending key order; keep[s] = 1 if none of its
+ * neighbours was kept before it, else 0 -- the lexicographically first maximal independent set
+ * of that order; a sample without edges is kept.  A function of the edge SET and the keys
+ * alone: not of record order, repeats, launch shape or the timing of atomics.  This is
+ * deliberately NOT Hail's maximal_independent_set, which removes the currently highest-degree
+ * vertex and recomputes the degrees: that has no parallel form with a unique answer.
+ * Family: family[s] = the lowest sample index of the connected component of s in the edge
+ * graph (s itself without edges).  family may be NULL.
+ *
+ * cuking_unrelated_set_host: host memory, no GPU -- deduplicate, sort by key, the sequential
+ * greedy, union-find: the specification in executable form.
+ * cuking_unrelated_set: d_records exactly what cuking_compute_king appended, num_records from
+ * its *d_result_index (at most 2^30; num_samples at most 2^31); d_priority (num_samples
+ * floats) may be NULL; d_keep num_samples bytes, d_family num_samples words or NULL.  *rounds
+ * (HOST memory, may be NULL) receives the number of rounds of the parallel greedy that had a
+ * live edge (at most num_samples).  The call WAITS for `stream`: it reads a few control words
+ * back per batch of rounds.  Its workspace -- 16 B per record, 20 B per sample and, without
+ * priorities, 8 B x the power of two from 2 x num_records on for the duplicate removal --
+ * belongs to the context's per-stream cache and is sized once per call; nothing is allocated
+ * inside the round loop.  Results depend on no option.
+ * Out of scope: the C++ `cuking` binary, merging across ranks, Hail's dynamic-degree
+ * heuristic. */
+uint64_t cuking_unrelated_key(float priority, uint32_t sample);
+cuking_status cuking_unrelated_set_host(const cuking_result *records, uint64_t num_records,
+                                        uint32_t num_samples, float prune_threshold,
+                                        const float *priority, uint8_t *keep, uint32_t *family);
+cuking_status cuking_unrelated_set(cuking_ctx *ctx, const cuking_result *d_records,
+                                   uint64_t num_records, uint32_t num_samples,
+                                   float prune_threshold, const float *d_priority,
+                                   uint8_t *d_keep, uint32_t *d_family, uint32_t *rounds,
+                                   void *stream);
+
 /* cuking.cu:761-765 on host memory: sort by (sample_i, sample_j, kin). */
 void cuking_sort_results(cuking_result *results, size_t num_results);
 
