@@ -10,7 +10,7 @@ from .api import (DEFAULT_KIN_THRESHOLD, DEFAULT_MAX_RESULTS,  # noqa: F401
                   UnrelatedSet, family_members, unrelated_key, unrelated_set, unrelated_set_host,
                   KingContext, KinSummary, ResourceExhaustedError, Submatrix,
                   bytes_per_pair, device_count, kin_matrix, kin_summary, new_host_bitset,
-                  pack_host,
+                  pack_bed_host, pack_host,
                   padded_sites, sort_results, synth_model_number, synth_models,
                   words_per_sample)
 

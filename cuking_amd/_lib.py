@@ -67,6 +67,9 @@ SIGNATURES = {
     "cuking_pack_host": (_int, [_SM, _u32, _vp, _vp, _vp, _vp, _sz]),
     "cuking_narrow_triples": (_int, [_SM, _u32, _vp, _vp, _vp, _sz, _vp, _vp,
                                      C.POINTER(_sz)]),
+    "cuking_bed_row_bytes": (_u64, [_u32]),
+    "cuking_bed_check": (_int, [_vp, _u64, _u32, _u32]),
+    "cuking_pack_bed_host": (_int, [_SM, _u32, _vp, _vp, _u64, _u32, _u32, _u32]),
     "cuking_schedule_tile_partition": (None, [_u64, _u32, _vp]),
     "cuking_schedule_weighted_tile_partition": (_int, [_u64, _vp, _u32, _vp]),
     "cuking_schedule_calibration_tiles": (_u64, [_u64, _u32]),
@@ -95,6 +98,7 @@ SIGNATURES = {
                                   _vp, _vp]),
     "cuking_pack_device_compact": (_int, [_vp, _SM, _u32, _vp, _vp, _vp, _sz, _vp,
                                           _vp]),
+    "cuking_pack_bed_device": (_int, [_vp, _SM, _u32, _vp, _vp, _u64, _u32, _u32, _u32, _vp]),
     "cuking_ctx_set_kernel": (_int, [_vp, _int]),
     "cuking_ctx_set_option": (_int, [_vp, C.c_char_p, _i64]),
     "cuking_ctx_get_option": (_int, [_vp, C.c_char_p, C.POINTER(_i64)]),

@@ -113,6 +113,22 @@ def pack_host(sm: Submatrix, bit_set: np.ndarray, row_idx, col_idx,
         row_idx.size))
 
 
+def pack_bed_host(sm: Submatrix, bit_set: np.ndarray, bed_rows, row_bytes: int,
+                  site_begin: int, site_end: int, num_sites: int) -> None:
+    """cuking_pack_bed_host: rows [site_begin, site_end) of a variant-major PLINK .bed
+    (``bed_rows``: uint8, the row of ``site_begin`` first, ``row_bytes`` apart) into the
+    block's host bitset.  Plain stores: the words of the chunk are overwritten, whatever
+    ``bit_set`` held (include/cuking_amd.h has the mapping and the refused arguments)."""
+    rows = np.ascontiguousarray(bed_rows, dtype=np.uint8).reshape(-1)
+    assert bit_set.dtype == np.uint64 and bit_set.flags.c_contiguous
+    if rows.size < (site_end - site_begin) * row_bytes:
+        raise ValueError(f"bed_rows holds {rows.size} bytes, sites [{site_begin}, {site_end}) "
+                         f"need {(site_end - site_begin) * row_bytes}")
+    check(_lib.load().cuking_pack_bed_host(
+        C.byref(sm.c), bit_set.shape[1] if bit_set.ndim == 2 else words_per_sample(num_sites),
+        bit_set.ctypes.data, rows.ctypes.data, row_bytes, site_begin, site_end, num_sites))
+
+
 def sort_results(results: np.ndarray) -> np.ndarray:
     """cuking.cu:761-765 (in place)."""
     assert results.dtype == KING_RESULT_DTYPE and results.flags.c_contiguous
@@ -556,6 +572,79 @@ class KingContext:
             n_alt_alleles.data_ptr(), row_idx.numel(), status.data_ptr(),
             _stream_handle(stream)))
 
+    def pack_bed(self, submatrix: Submatrix, words_per_sample: int, bed_rows, row_bytes: int,
+                 site_begin: int, site_end: int, num_sites: int, out, stream=None) -> None:
+        """cuking_pack_bed_device: rows [site_begin, site_end) of a variant-major PLINK
+        .bed -- ``bed_rows``, a uint8 device tensor (any alignment: a view into a larger
+        buffer is fine), the row of ``site_begin`` first -- into the block's device bitset
+        ``out``.  A bit transpose with plain stores: the words of the chunk are overwritten
+        whatever ``out`` held, chunks covering [0, num_sites) write every word, no memset.
+        Asynchronous on the stream."""
+        import torch
+        self._check_bits(submatrix, words_per_sample, out)
+        if not bed_rows.is_cuda or bed_rows.device.index != self.device:
+            raise ValueError("bed_rows must live on this context's GPU")
+        if bed_rows.dtype != torch.uint8 or not bed_rows.is_contiguous():
+            raise ValueError("bed_rows must be a contiguous uint8 tensor")
+        if site_begin <= site_end and bed_rows.numel() < (site_end - site_begin) * row_bytes:
+            raise ValueError(f"bed_rows holds {bed_rows.numel()} bytes, sites [{site_begin}, "
+                             f"{site_end}) need {(site_end - site_begin) * row_bytes}")
+        if submatrix.NumSamples() == 0 or site_begin == site_end:
+            return
+        check(self.lib.cuking_pack_bed_device(
+            self.handle, C.byref(submatrix.c), words_per_sample, out.data_ptr(),
+            bed_rows.data_ptr(), row_bytes, site_begin, site_end, num_sites,
+            _stream_handle(stream)))
+
+    def load_bed(self, prefix, submatrix: Submatrix, chunk_bytes: int = 64 << 20, out=None):
+        """The block's device bitset from ``PREFIX.bed / .bim / .fam`` (cuking_amd.plink):
+        the file is read in chunks of a multiple of 64 sites (about ``chunk_bytes`` each)
+        into two pinned staging tensors, copied on a copy stream and transposed by
+        ``pack_bed`` on a pack stream, ordered by events -- the host only waits where a
+        staging tensor has to come free.  Nothing is sized by the whole file but the
+        result: ``[max(NumSamples, 1), words_per_sample]`` int64 (``out`` to write into).
+        Waits for the last chunk before it returns."""
+        import torch
+        from . import plink
+        dev = f"cuda:{self.device}"
+        with plink.open_bed(prefix) as bed:
+            if max(submatrix.i_end, submatrix.j_end) > bed.num_samples:
+                raise ValueError(f"{submatrix!r} reaches past the {bed.num_samples} samples of "
+                                 f"{bed.path}")
+            wps = words_per_sample(bed.num_sites)
+            stored = submatrix.NumSamples()
+            if out is None:
+                out = torch.empty((max(stored, 1), wps), dtype=torch.int64, device=dev)
+            self._check_bits(submatrix, wps, out)
+            if stored == 0 or bed.num_sites == 0:
+                return out
+            sites = max(64, int(chunk_bytes) // bed.row_bytes // 64 * 64)
+            sites = min(sites, (bed.num_sites + 63) // 64 * 64)
+            host = [torch.empty(sites * bed.row_bytes, dtype=torch.uint8).pin_memory()
+                    for _ in range(2)]
+            rows = [torch.empty(sites * bed.row_bytes, dtype=torch.uint8, device=dev)
+                    for _ in range(2)]
+            copy_stream, pack_stream = torch.cuda.Stream(dev), torch.cuda.Stream(dev)
+            copied = [torch.cuda.Event() for _ in range(2)]
+            packed = [torch.cuda.Event() for _ in range(2)]
+            pack_stream.wait_stream(torch.cuda.current_stream(self.device))
+            for k, begin in enumerate(range(0, bed.num_sites, sites)):
+                end, b = min(begin + sites, bed.num_sites), k & 1
+                nbytes = (end - begin) * bed.row_bytes
+                if k >= 2:
+                    copied[b].synchronize()         # the staging tensor is free again
+                    copy_stream.wait_event(packed[b])   # and so is its device copy
+                bed.read_rows(begin, end, host[b].numpy())
+                with torch.cuda.stream(copy_stream):
+                    rows[b][:nbytes].copy_(host[b][:nbytes], non_blocking=True)
+                copied[b].record(copy_stream)
+                pack_stream.wait_event(copied[b])
+                self.pack_bed(submatrix, wps, rows[b][:nbytes], bed.row_bytes, begin, end,
+                              bed.num_sites, out, stream=pack_stream)
+                packed[b].record(pack_stream)
+            pack_stream.synchronize()
+        return out
+
     def synth_bitset(self, seed: int, kind, pa, pb, sample_begin: int,
                      sample_end: int, num_sites: int, out=None, stream=None, model=0):
         """Synthetic reference-layout bitset rows [sample_begin, sample_end)
@@ -813,7 +902,7 @@ __all__ = [
     "unrelated_set", "unrelated_set_host", "unrelated_key", "UnrelatedSet", "family_members",
     "KING_RESULT_DTYPE", "KING_COUNTS_DTYPE",
     "ResourceExhaustedError", "CukingError", "padded_sites",
-    "words_per_sample", "bytes_per_pair", "new_host_bitset", "pack_host",
+    "words_per_sample", "bytes_per_pair", "new_host_bitset", "pack_host", "pack_bed_host",
     "sort_results", "device_count", "synth_models", "synth_model_number",
     "DEFAULT_KIN_THRESHOLD",
     "DEFAULT_MAX_RESULTS",

@@ -27,7 +27,7 @@ CLI_PATH = PKG / "bin" / "cuking"
 LIB_FLAGS_PATH = PKG / "libcuking_amd.flags"
 
 HIP_SOURCES = ["king_abi.hip", "king_kernels.hip", "king_mfma.hip", "king_filter.hip",
-               "king_sort.hip", "king_prune.hip", "synth.hip"]
+               "king_sort.hip", "king_prune.hip", "king_bed.hip", "synth.hip"]
 # Host-only half of the ABI: plain C++, also compiled by the sanitizer tests.
 HOST_ABI_SOURCES = ["king_host.cc"]
 # IEEE-correct fp32 divide (kinship must match the reference bit for bit):
@@ -95,10 +95,12 @@ def build_library(force: bool = False, save_temps: bool = False) -> Path:
             raise subprocess.CalledProcessError(r.returncode, cmd)
     problems = check_mfma_loops(cwd / "king_mfma-hip-amdgcn-amd-amdhsa-gfx950.s")
     problems += check_filter_loop(cwd / "king_filter-hip-amdgcn-amd-amdhsa-gfx950.s")
+    problems += check_no_scratch(cwd / "king_bed-hip-amdgcn-amd-amdhsa-gfx950.s", "pack_bed_kernel")
     if problems and not extra:
         LIB_PATH.unlink(missing_ok=True)
-        raise RuntimeError("matrix-core kernel: the compiler put vector-memory waits or scratch "
-                           "accesses inside an LDS-DMA loop:\n  " + "\n  ".join(problems))
+        raise RuntimeError("the compiler put vector-memory waits or scratch accesses inside an "
+                           "LDS-DMA loop of a matrix-core kernel, or gave a kernel that must not "
+                           "have one a scratch segment:\n  " + "\n  ".join(problems))
     for line in problems:
         print("warning (experiment build):", line, file=sys.stderr)
     LIB_FLAGS_PATH.write_text(wanted + "\n")
@@ -153,6 +155,18 @@ def check_dma_loops(asm_path: Path, kernel: str, kernel_re: str, allowed_vmcnt, 
         if seen == 0:
             problems.append(f"{label}: no LDS-DMA loop found (listing format changed?)")
     return problems
+
+
+def check_no_scratch(asm_path: Path, kernel: str):
+    """The kernels named `kernel` keep everything in registers: their descriptors in the
+    listing ask for a private segment of 0 bytes (a small array the compiler indexes at run
+    time would land there, at a multiple of the cost)."""
+    import re
+    found = re.findall(r"\.amdhsa_kernel (\S*" + re.escape(kernel) + r"\S*)\n(?:.*\n)*?"
+                       r"\s*\.amdhsa_private_segment_fixed_size (\d+)", Path(asm_path).read_text())
+    if not found:
+        return [f"no {kernel} in {asm_path}"]
+    return [f"{name}: {size} bytes of scratch per lane" for name, size in found if int(size)]
 
 
 def check_filter_loop(asm_path: Path, verbose: bool = False):

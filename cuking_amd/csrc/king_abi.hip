@@ -1225,6 +1225,24 @@ cuking_status cuking_pack_device_compact(cuking_ctx *ctx, const cuking_submatrix
   return CUKING_OK;
 }
 
+cuking_status cuking_pack_bed_device(cuking_ctx *ctx, const cuking_submatrix *sm,
+                                     uint32_t words_per_sample, uint64_t *d_bit_set,
+                                     const uint8_t *d_bed_rows, uint64_t row_bytes,
+                                     uint32_t site_begin, uint32_t site_end, uint32_t num_sites,
+                                     void *stream) {
+  // (the arguments first: a refused call touches no device)
+  if (ctx == nullptr) return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "null context");
+  cuking_status st = cuking_check_bed_args(sm, words_per_sample, d_bit_set, d_bed_rows, row_bytes,
+                                           site_begin, site_end, num_sites);
+  if (st != CUKING_OK) return st;
+  if (site_begin == site_end || sm_num_samples(*sm) == 0) return CUKING_OK;
+  st = bind(ctx);
+  if (st != CUKING_OK) return st;
+  HIP_TRY(launch_pack_bed(*sm, words_per_sample, d_bit_set, d_bed_rows, row_bytes, site_begin,
+                          site_end, (hipStream_t)stream));
+  return CUKING_OK;
+}
+
 cuking_status cuking_event_create(cuking_ctx *ctx, void **event) {
   cuking_status st = bind(ctx);
   if (st != CUKING_OK) return st;

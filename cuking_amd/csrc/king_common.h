@@ -618,6 +618,13 @@ hipError_t launch_pack_compact(uint32_t words_per_sample, uint32_t num_samples,
                                const uint32_t *d_sample_alt, size_t num_triples,
                                uint32_t *d_status, hipStream_t stream);
 
+// PLINK .bed rows -> bitset (king_bed.hip): sites [site_begin, site_end) of the block's stored
+// samples, d_bed_rows = the row of site_begin; arguments already checked (king_host.h
+// cuking_check_bed_args).  Plain stores, no status word: every code is legal.
+hipError_t launch_pack_bed(const cuking_submatrix &sm, uint32_t words_per_sample,
+                           uint64_t *d_bit_set, const uint8_t *d_bed_rows, uint64_t row_bytes,
+                           uint32_t site_begin, uint32_t site_end, hipStream_t stream);
+
 // Cohort models of the synthetic generator (synth.hip holds the specification).  d_tables:
 // synth_table_bytes() of scratch the launch fills and reads (per-site and per-sample
 // tables); it must stay untouched until the launch has run.

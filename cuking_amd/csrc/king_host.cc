@@ -1,9 +1,10 @@
 // Host-only half of the C ABI (include/cuking_amd.h): Submatrix arithmetic,
 // bitset sizing, the host pack with its relaxed atomics, the narrowing step of
-// the device pack, the record sort, the per-thread error message.  Plain C++
-// (no HIP): hipcc compiles it into libcuking_amd.so, and the sanitizer tests
-// compile the same file with g++ -fsanitize=thread / address so that the code
-// that runs on many reader threads is instrumented (tests/test_cli.py).
+// the device pack, the PLINK .bed pack and its checks, the record sort, the
+// per-thread error message.  Plain C++ (no HIP): hipcc compiles it into
+// libcuking_amd.so, and the sanitizer tests compile the same file with g++
+// -fsanitize=thread / address so that the code that runs on many reader threads
+// is instrumented (tests/test_cli.py, tests/test_bed_host.py).
 #include "king_host.h"
 
 #include <algorithm>
@@ -266,6 +267,106 @@ cuking_status cuking_narrow_triples(const cuking_submatrix *sm, uint32_t words_p
     ++w;
   }
   *num_out = w;
+  return CUKING_OK;
+}
+
+// ---- PLINK .bed input: the format's arithmetic, the checks and the host pack ----------------
+uint64_t cuking_bed_row_bytes(uint32_t num_samples_total) {
+  return ((uint64_t)num_samples_total + 3) / 4;
+}
+
+cuking_status cuking_bed_check(const uint8_t magic[3], uint64_t file_bytes,
+                               uint32_t num_samples_total, uint32_t num_sites) {
+  if (magic == nullptr) return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "null magic pointer");
+  if (magic[0] != 0x6c || magic[1] != 0x1b)
+    return cuking_fail(CUKING_ERR_FAILED_PRECONDITION,
+                       "not a PLINK .bed file: it starts with %02x %02x, not 6c 1b", magic[0],
+                       magic[1]);
+  if (magic[2] == 0x00)
+    return cuking_fail(CUKING_ERR_FAILED_PRECONDITION,
+                       "a sample-major .bed (third byte 00) is not supported: rewrite it "
+                       "variant-major (third byte 01)");
+  if (magic[2] != 0x01)
+    return cuking_fail(CUKING_ERR_FAILED_PRECONDITION,
+                       "not a PLINK .bed file: its third byte is %02x, not 01", magic[2]);
+  const uint64_t need = 3 + (uint64_t)num_sites * cuking_bed_row_bytes(num_samples_total);
+  if (file_bytes != need)
+    return cuking_fail(CUKING_ERR_FAILED_PRECONDITION,
+                       "the .bed file holds %llu bytes, but %u samples (.fam) x %u sites (.bim) "
+                       "need %llu: truncated, or not the .bed of these two files",
+                       (unsigned long long)file_bytes, num_samples_total, num_sites,
+                       (unsigned long long)need);
+  return CUKING_OK;
+}
+
+}  // extern "C"
+
+cuking_status cuking_check_bed_args(const cuking_submatrix *sm, uint32_t words_per_sample,
+                                    const void *bit_set, const void *bed_rows,
+                                    uint64_t row_bytes, uint32_t site_begin, uint32_t site_end,
+                                    uint32_t num_sites) {
+  if (sm == nullptr || bit_set == nullptr || bed_rows == nullptr)
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "pack bed: null pointer");
+  const cuking_status st = cuking_check_block(sm, words_per_sample);
+  if (st != CUKING_OK) return st;
+  if (site_begin % 64 != 0)
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT,
+                       "pack bed: site_begin (%u) must be a multiple of 64", site_begin);
+  if (site_begin > site_end || site_end > num_sites)
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT,
+                       "pack bed: sites [%u, %u) are not a range inside the %u sites", site_begin,
+                       site_end, num_sites);
+  if (site_end % 64 != 0 && site_end != num_sites)
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT,
+                       "pack bed: site_end (%u) must be a multiple of 64 or the number of sites "
+                       "(%u)", site_end, num_sites);
+  if (cuking_words_per_sample(num_sites) != words_per_sample)
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT,
+                       "pack bed: %u sites need %u words per sample, not %u", num_sites,
+                       cuking_words_per_sample(num_sites), words_per_sample);
+  if (row_bytes == 0 || row_bytes * 4 < std::max(sm->i_end, sm->j_end))
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT,
+                       "pack bed: rows of %llu bytes hold %llu samples, the block reaches "
+                       "sample %u", (unsigned long long)row_bytes,
+                       (unsigned long long)row_bytes * 4, std::max(sm->i_end, sm->j_end));
+  return CUKING_OK;
+}
+
+extern "C" {
+
+cuking_status cuking_pack_bed_host(const cuking_submatrix *sm, uint32_t words_per_sample,
+                                   uint64_t *bit_set, const uint8_t *bed_rows,
+                                   uint64_t row_bytes, uint32_t site_begin, uint32_t site_end,
+                                   uint32_t num_sites) {
+  const cuking_status st = cuking_check_bed_args(sm, words_per_sample, bit_set, bed_rows,
+                                                 row_bytes, site_begin, site_end, num_sites);
+  if (st != CUKING_OK) return st;
+  if (site_begin == site_end) return CUKING_OK;
+  const uint32_t plane_words = words_per_sample / 2;
+  const uint64_t word_begin = site_begin / 64, word_end = ((uint64_t)site_end + 63) / 64;
+  // The block's stored samples: rows, then the columns of an off-diagonal block.
+  const uint32_t begin[2] = {sm->i_begin, sm->j_begin}, end[2] = {sm->i_end, sm->j_end};
+  const uint32_t ranges = sm_is_diag(*sm) ? 1u : 2u;
+  for (uint64_t w = word_begin; w < word_end; ++w) {
+    for (uint32_t r = 0; r < ranges; ++r) {
+      for (uint32_t s = begin[r]; s < end[r]; ++s) {
+        uint64_t het = 0, hom = 0;
+        for (uint32_t bit = 0; bit < 64; ++bit) {
+          const uint64_t site = w * 64 + bit;
+          // code 1 = missing: what every site past the chunk's (= the file's) last one holds
+          uint32_t v = 1;
+          if (site < site_end)
+            v = (bed_rows[(site - site_begin) * row_bytes + (s >> 2)] >> (2 * (s & 3))) & 3u;
+          const uint64_t b0 = v & 1u, b1 = v >> 1;
+          het |= (b0 ^ b1) << bit;
+          hom |= (b1 ^ 1u) << bit;
+        }
+        uint64_t *row = bit_set + (uint64_t)sm_sample_offset(*sm, s) * words_per_sample;
+        row[w] = het;
+        row[w + plane_words] = hom;
+      }
+    }
+  }
   return CUKING_OK;
 }
 

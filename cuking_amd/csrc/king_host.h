@@ -11,5 +11,11 @@ cuking_status cuking_fail(cuking_status code, const char *fmt, ...)
     __attribute__((format(printf, 2, 3)));
 // Argument checks every entry point that takes a block makes.
 cuking_status cuking_check_block(const cuking_submatrix *sm, uint32_t words_per_sample);
+// Argument checks of cuking_pack_bed_host / cuking_pack_bed_device (include/cuking_amd.h lists
+// them); OK says nothing about there being work to do.
+cuking_status cuking_check_bed_args(const cuking_submatrix *sm, uint32_t words_per_sample,
+                                    const void *bit_set, const void *bed_rows,
+                                    uint64_t row_bytes, uint32_t site_begin, uint32_t site_end,
+                                    uint32_t num_sites);
 
 #endif  // CUKING_AMD_KING_HOST_H_

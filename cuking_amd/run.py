@@ -6,7 +6,8 @@
 
 One process per GPU.  Rank 0 reads `metadata.json` + `*.parquet`, packs the
 bitset through the C ABI (`cuking_pack_host`, reader threads like
-cuking.cu:550-553), the bitset goes to the other GPUs by the staged RCCL
+cuking.cu:550-553) -- or, with `--bed-uri PREFIX`, streams a PLINK `.bed` to its
+GPU and transposes it there (`KingContext.load_bed`) --, the bitset goes to the other GPUs by the staged RCCL
 broadcast of `cuking_amd.dist`, every rank evaluates its band of the pair
 space, rank 0 gathers, sorts and writes `part-<shard>.snappy.parquet` with the
 reference's schema (cuking.cu:767-870).  `--split-factor/--shard-index` select a
@@ -37,6 +38,10 @@ def parse_args(argv=None):
                         dest=name.replace("-", "_"), **kw)
 
     flag("input-uri", default="")
+    flag("bed-uri", default="",
+         help="PREFIX of a PLINK 1 binary genotype set (PREFIX.bed / .bim / .fam, variant-major) "
+              "to read instead of --input-uri: the dense 2-bit file goes to the GPU as it is and "
+              "is transposed into the bitset there; sample ids come from the .fam")
     flag("output-uri", default="")
     flag("requester-pays-project", default="")
     flag("num-reader-threads", type=int, default=36)
@@ -139,8 +144,12 @@ def relative_thresholds(text: str):
 def validate(args):  # cuking.cu:437-462
     if args.synthetic_model and not args.synthetic:
         raise UsageError("--synthetic_model needs --synthetic")
-    if not args.input_uri and not args.synthetic:
-        raise UsageError("No input URI specified")
+    if not args.input_uri and not args.bed_uri and not args.synthetic:
+        raise UsageError("No input URI specified: exactly one of --input_uri, --bed_uri and "
+                         "--synthetic is required")
+    if args.bed_uri and (args.input_uri or args.synthetic):
+        raise UsageError("exactly one of --input_uri, --bed_uri and --synthetic is required, "
+                         "--bed_uri came with another of them")
     if not args.output_uri:
         raise UsageError("No output URI specified")
     if args.num_reader_threads <= 0:
@@ -328,6 +337,7 @@ def main(argv=None) -> int:
     try:
         validate(args)
         in_dir = resolve_uri(args.input_uri) if args.input_uri else None
+        bed_prefix = resolve_uri(args.bed_uri) if args.bed_uri else None
         out_dir = resolve_uri(args.output_uri)
         kin_path = resolve_uri(args.kin_matrix_uri) if args.kin_matrix_uri else None
         summary_path = resolve_uri(args.kin_summary_uri) if args.kin_summary_uri else None
@@ -365,6 +375,9 @@ def main(argv=None) -> int:
         if synthetic:
             sample_ids = [f"S{k:07d}" for k in range(synthetic[0])]
             num_sites = synthetic[1]
+        elif bed_prefix is not None:
+            from cuking_amd import plink
+            sample_ids, num_sites = plink.read_fam(bed_prefix), plink.count_sites(bed_prefix)
         else:
             meta = json.loads((in_dir / "metadata.json").read_text())
             sample_ids, num_sites = list(meta["samples"]), int(meta["num_sites"])
@@ -392,6 +405,10 @@ def main(argv=None) -> int:
                                          num_sites, out=bits[sm.NumRows():stored],
                                          model=synth_model)
                     torch.cuda.synchronize()
+                elif bed_prefix is not None:
+                    # dense 2-bit rows -> bitset on the device (csrc/king_bed.hip); a bad or
+                    # truncated file raises here and is agreed on below like any read error
+                    ctx.load_bed(bed_prefix, sm, out=bits)
                 else:
                     host = read_and_pack(in_dir, sm, num_sites, args.num_reader_threads)
                     if stored:

@@ -106,6 +106,54 @@ cuking_status cuking_narrow_triples(const cuking_submatrix *sm,
                                     uint32_t *site, uint32_t *sample_alt,
                                     size_t *num_out);
 
+/* PLINK 1 binary genotypes (.bed/.bim/.fam), the dense 2-bit form every cohort already exists
+ * in and KING itself reads: the way into the bitset without one (row_idx, col_idx,
+ * n_alt_alleles) triple per genotype (20 B in Parquet columns, 8 B after
+ * cuking_narrow_triples, against 2 bits here).  The .bed is variant-major: 3 magic bytes
+ * 6c 1b 01, then for every variant (site) row_bytes = ceil(N / 4) bytes, N = the number of
+ * lines of the .fam.  Sample s of a site sits in byte s >> 2, bits 2 (s & 3) and 2 (s & 3) + 1;
+ * with v = (byte >> 2 (s & 3)) & 3:
+ *     v = 0  homozygous A1   n_alt 2 (A1 counted)   het 0, hom_var 1
+ *     v = 1  missing                                het 1, hom_var 1
+ *     v = 2  heterozygous    n_alt 1                het 1, hom_var 0
+ *     v = 3  homozygous A2   n_alt 0                het 0, hom_var 0
+ * i.e. het = b0 XOR b1, hom_var = NOT b1; unused high bits of a row's last byte are ignored,
+ * and all four codes are legal: the pack has no data-dependent failure.  Counting A1 rather
+ * than A2 is a convention only: all six sums of ComputeKingKernel (cuking.cu:216-240), and so
+ * the kinship and IBS0/1/2, are unchanged when the two alleles of a site are swapped
+ * (tests/test_bed_host.py proves it on the naive oracle).
+ *
+ * cuking_pack_bed_host / cuking_pack_bed_device write what cuking_pack_host produces from an
+ * all-ones bitset for the triples (site, sample, n_alt) of that table, byte for byte: sample s
+ * at bit_set + SampleOffset(s) * words_per_sample, [het | hom_var] planes, every site from
+ * num_sites to the end of the plane missing.  bed_rows points at the row of site `site_begin`
+ * -- a chunk of the file behind the magic, rows row_bytes apart, NO alignment (row_bytes is any
+ * positive value and the data starts at offset 3, so a row may begin at any byte); nothing
+ * outside [bed_rows, bed_rows + (site_end - site_begin) * row_bytes) is read.  A call
+ * OVERWRITES, for every stored sample of the block (rows, then columns; a diagonal block's
+ * samples once), the words [site_begin / 64, ceil(site_end / 64)) of both planes with plain
+ * stores, whatever was there; a call with site_end == num_sites thereby also writes every bit
+ * from num_sites to the end of the plane as missing.  Chunks that cover [0, num_sites) write
+ * every word of the block's rows: no memset is needed, unlike cuking_pack_device.  Rows of
+ * other samples and words outside the chunk's range are left alone.
+ * INVALID_ARGUMENT, before any device is touched: a null pointer; site_begin not a multiple of
+ * 64; site_end neither a multiple of 64 nor num_sites; site_begin > site_end or site_end >
+ * num_sites; cuking_words_per_sample(num_sites) != words_per_sample; 4 * row_bytes < j_end (or
+ * i_end).  site_begin == site_end returns OK without work, and so does an empty block.  All
+ * byte and word offsets are 64-bit (734k samples x 200k sites is a 36.7 GB file).
+ * cuking_bed_check (FAILED_PRECONDITION, one message each): bytes 0-1 are not 6c 1b -- not a
+ * PLINK .bed; a third byte of 00 -- sample-major, not supported; file_bytes != 3 + num_sites *
+ * row_bytes -- with both numbers in the message.
+ * Out of scope: the C++ `cuking` binary; .pgen, VCF and sample-major .bed; reading per rank
+ * instead of on rank 0; site or sample filtering while loading. */
+uint64_t cuking_bed_row_bytes(uint32_t num_samples_total); /* ceil(N / 4) */
+cuking_status cuking_bed_check(const uint8_t magic[3], uint64_t file_bytes,
+                               uint32_t num_samples_total, uint32_t num_sites);
+cuking_status cuking_pack_bed_host(const cuking_submatrix *sm, uint32_t words_per_sample,
+                                   uint64_t *bit_set, const uint8_t *bed_rows,
+                                   uint64_t row_bytes, uint32_t site_begin,
+                                   uint32_t site_end, uint32_t num_sites);
+
 /* Message of the calling thread's most recent failing call ("" if none). */
 const char *cuking_last_error(void);
 uint32_t cuking_abi_version(void);
@@ -132,8 +180,8 @@ cuking_status cuking_copy_to_host(cuking_ctx *ctx, void *dst, const void *d_src,
                                   size_t bytes, void *stream);
 cuking_status cuking_stream_synchronize(cuking_ctx *ctx, void *stream);
 /* Extra streams for hosts without their own (e.g. one per Parquet reader
- * thread).  The memory, copy, stream and cuking_pack_device entry points may
- * be called from several host threads at once, each on its own stream; the
+ * thread).  The memory, copy, stream, cuking_pack_device and cuking_pack_bed_device entry
+ * points may be called from several host threads at once, each on its own stream; the
  * compute / prepare / timing entry points need one caller at a time. */
 cuking_status cuking_stream_create(cuking_ctx *ctx, void **stream);
 cuking_status cuking_stream_destroy(cuking_ctx *ctx, void *stream);
@@ -172,6 +220,17 @@ cuking_status cuking_pack_device_compact(cuking_ctx *ctx, const cuking_submatrix
                                          const uint32_t *d_sample_alt,
                                          size_t num_triples, uint32_t *d_status,
                                          void *stream);
+
+/* cuking_pack_bed_host (above: format, mapping, semantics and refused arguments) as a kernel:
+ * a two-plane bit transpose through LDS, no atomics (csrc/king_bed.hip).  d_bed_rows is a
+ * chunk of the file's rows in DEVICE memory, at any alignment.  Asynchronous on `stream`; like
+ * cuking_pack_device it may be issued from several host threads, each on its own stream:
+ * chunks write disjoint words. */
+cuking_status cuking_pack_bed_device(cuking_ctx *ctx, const cuking_submatrix *sm,
+                                     uint32_t words_per_sample, uint64_t *d_bit_set,
+                                     const uint8_t *d_bed_rows, uint64_t row_bytes,
+                                     uint32_t site_begin, uint32_t site_end,
+                                     uint32_t num_sites, void *stream);
 
 /* Which device kernel evaluates the pairs. */
 typedef enum cuking_kernel {
