@@ -34,6 +34,11 @@ class CKinBins(C.Structure):
     _fields_ = [("lo", C.c_float), ("hi", C.c_float), ("num_bins", C.c_uint32)]
 
 
+class CSiteFilter(C.Structure):
+    """cuking_site_filter: the thresholds of the site rule."""
+    _fields_ = [("min_call_rate", C.c_float), ("min_maf", C.c_float), ("min_mac", C.c_uint32)]
+
+
 class CukingError(RuntimeError):
     def __init__(self, status: int, message: str):
         super().__init__(f"cuking_amd status {status}: {message}")
@@ -139,6 +144,12 @@ SIGNATURES = {
     "cuking_unrelated_set_host": (_int, [_vp, _u64, _u32, _f32, _vp, _vp, _vp]),
     "cuking_unrelated_set": (_int, [_vp, _vp, _u64, _u32, _f32, _vp, _vp, _vp, C.POINTER(_u32),
                                     _vp]),
+    "cuking_site_counts": (_int, [_vp, _vp, _u32, _u32, _vp, _vp]),
+    "cuking_sample_counts": (_int, [_vp, _vp, _u32, _u32, _u32, _vp, _vp]),
+    "cuking_site_mask_host": (_int, [_vp, _u32, _u32, C.POINTER(CSiteFilter), _vp, _vp,
+                                     C.POINTER(_u32)]),
+    "cuking_compact_sites_host": (_int, [_vp, _u32, _u32, _vp, _u32, _vp, _u32]),
+    "cuking_compact_sites": (_int, [_vp, _vp, _u32, _u32, _vp, _u32, _vp, _u32, _vp]),
     "cuking_sort_results": (None, [_vp, _sz]),
     "cuking_timing_enable": (_int, [_vp, _int]),
     "cuking_timing_reset": (_int, [_vp]),

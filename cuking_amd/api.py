@@ -129,6 +129,90 @@ def pack_bed_host(sm: Submatrix, bit_set: np.ndarray, bed_rows, row_bytes: int,
         bit_set.ctypes.data, rows.ctypes.data, row_bytes, site_begin, site_end, num_sites))
 
 
+def site_mask_words(keep) -> np.ndarray:
+    """A bool array of ``num_sites`` -> the mask words the library takes: uint64
+    ``[words_per_sample(num_sites) / 2]``, site s = bit ``s & 63`` of word ``s >> 6``."""
+    keep = np.asarray(keep).astype(bool).reshape(-1)
+    plane = words_per_sample(keep.size) // 2
+    padded = np.zeros(plane * 64, dtype=np.uint8)
+    padded[:keep.size] = keep
+    return np.packbits(padded, bitorder="little").view("<u8").astype(np.uint64)
+
+
+def site_mask_bool(keep_words, num_sites: int) -> np.ndarray:
+    """The mask words of ``num_sites`` sites -> a bool array of ``num_sites``."""
+    words = np.ascontiguousarray(keep_words, dtype=np.uint64).astype("<u8")
+    return np.unpackbits(words.view(np.uint8), bitorder="little")[:num_sites].astype(bool)
+
+
+def _host_counts(counts, plane: int) -> np.ndarray:
+    counts = np.asarray(counts)
+    if counts.dtype not in (np.dtype(np.uint32), np.dtype(np.int32)) or \
+            counts.shape != (plane * 64, 4):
+        raise ValueError(f"counts must be a uint32 (or int32) array of shape ({plane * 64}, 4), "
+                         f"not {counts.dtype} {counts.shape}")
+    return np.ascontiguousarray(counts).view(np.uint32)
+
+
+def site_mask_host(counts, num_sites: int, min_call_rate: float = 0.0, min_maf: float = 0.0,
+                   min_mac: int = 0, also=None):
+    """cuking_site_mask_host, the site rule: from the ``[64 P, 4]`` site counts (hom_ref,
+    het, hom_var, missing per plane site, as ``site_counts`` gives them) the mask of the sites
+    with a called genotype, ``called / n >= min_call_rate``, ``minor / (2 called) >= min_maf``
+    and ``minor >= min_mac`` (include/cuking_amd.h has the exact comparisons); ``also``: a
+    bool array of ``num_sites`` ANDed in (an LD-pruned list, a region).  Returns
+    ``(keep_words, num_kept)``: uint64 ``[P]`` as ``compact_sites`` takes them."""
+    num_sites = _count(num_sites, "num_sites")
+    plane = words_per_sample(num_sites) // 2
+    counts = _host_counts(counts, plane)
+    also_words = None
+    if also is not None:
+        also = np.asarray(also)
+        if also.shape != (num_sites,):
+            raise ValueError(f"also must hold {num_sites} entries, not {also.shape}")
+        also_words = site_mask_words(also)
+    rule = _lib.CSiteFilter(float(min_call_rate), float(min_maf), _count(min_mac, "min_mac"))
+    keep = np.zeros(plane, dtype=np.uint64)
+    kept = C.c_uint32(0)
+    check(_lib.load().cuking_site_mask_host(
+        counts.ctypes.data, num_sites, plane, C.byref(rule),
+        also_words.ctypes.data if also_words is not None else None, keep.ctypes.data,
+        C.byref(kept)))
+    return keep, int(kept.value)
+
+
+def _keep_words(keep_words, words_per_sample_in: int) -> np.ndarray:
+    keep = np.ascontiguousarray(keep_words, dtype=np.uint64).reshape(-1)
+    if keep.size != words_per_sample_in // 2:
+        raise ValueError(f"keep_words must hold {words_per_sample_in // 2} words (one per plane "
+                         f"word), not {keep.size}")
+    return keep
+
+
+def _popcount(words: np.ndarray) -> int:
+    return int(np.unpackbits(np.ascontiguousarray(words).view(np.uint8)).sum())
+
+
+def compact_sites_host(bit_sets: np.ndarray, words_per_sample_in: int, keep_words,
+                       num_sites: int, out=None):
+    """cuking_compact_sites_host: the host bitset ``[rows, words_per_sample_in]`` restricted
+    to the sites of ``keep_words`` -- the k-th kept site becomes site k, what follows the
+    last one is missing -- as ``(new_bits, new_words_per_sample, num_kept)``.  ``out``: a
+    uint64 ``[rows, words_per_sample(num_kept)]`` array to write into."""
+    assert bit_sets.dtype == np.uint64 and bit_sets.flags.c_contiguous
+    keep = _keep_words(keep_words, words_per_sample_in)
+    rows = bit_sets.size // words_per_sample_in
+    kept = _popcount(keep)
+    wps_out = words_per_sample(max(kept, 1))
+    if out is None:
+        out = np.empty((rows, wps_out), dtype=np.uint64)
+    assert out.dtype == np.uint64 and out.flags.c_contiguous and out.size >= rows * wps_out
+    check(_lib.load().cuking_compact_sites_host(
+        bit_sets.ctypes.data, rows, words_per_sample_in, keep.ctypes.data, num_sites,
+        out.ctypes.data, wps_out))
+    return out, wps_out, kept
+
+
 def sort_results(results: np.ndarray) -> np.ndarray:
     """cuking.cu:761-765 (in place)."""
     assert results.dtype == KING_RESULT_DTYPE and results.flags.c_contiguous
@@ -645,6 +729,106 @@ class KingContext:
             pack_stream.synchronize()
         return out
 
+    # -- site QC --------------------------------------------------------------
+    def _rows_of(self, bit_sets, words_per_sample: int) -> int:
+        import torch
+        if not isinstance(bit_sets, torch.Tensor) or not bit_sets.is_cuda or \
+                bit_sets.device.index != self.device:
+            raise ValueError("bit_sets must live on this context's GPU")
+        if bit_sets.dtype != torch.int64 or not bit_sets.is_contiguous():
+            raise ValueError("bit_sets must be a contiguous int64 tensor")
+        if words_per_sample <= 0 or words_per_sample % 2 or bit_sets.numel() % words_per_sample:
+            raise ValueError(f"bit_sets holds {bit_sets.numel()} words: not rows of "
+                             f"{words_per_sample} (a positive even number)")
+        return bit_sets.numel() // words_per_sample
+
+    def _counts_out(self, out, shape, zero: bool):
+        import torch
+        if out is None:
+            make = torch.zeros if zero else torch.empty
+            return make(shape, dtype=torch.int32, device=f"cuda:{self.device}")
+        if not out.is_cuda or out.device.index != self.device:
+            raise ValueError("out must live on this context's GPU")
+        if out.dtype != torch.int32:
+            raise ValueError("out must be an int32 tensor (a view of the uint32 data)")
+        if tuple(out.shape) != shape or not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous tensor of shape {shape}, "
+                             f"not {tuple(out.shape)}")
+        return out
+
+    def site_counts(self, bit_sets, words_per_sample: int, out=None, stream=None):
+        """Genotype counts per site (cuking_site_counts): for every plane site ``0 .. 64 P -
+        1`` the number of the rows of ``bit_sets`` (any row range of a bitset: ``[rows,
+        words_per_sample]``) that are hom-ref, het, hom-var and missing, as a device tensor
+        ``[64 P, 4]`` int32 (a view of uint32 data).  The call ACCUMULATES into ``out``, so
+        row ranges, blocks and GPUs merge by passing the tensor back in (or by sum); without
+        it a zeroed one is allocated.  Padding sites count as missing.  Does not
+        synchronise."""
+        rows = self._rows_of(bit_sets, words_per_sample)
+        out = self._counts_out(out, (words_per_sample // 2 * 64, 4), zero=True)
+        check(self.lib.cuking_site_counts(self.handle, bit_sets.data_ptr(), rows,
+                                          words_per_sample, out.data_ptr(),
+                                          _stream_handle(stream)))
+        return out
+
+    def sample_counts(self, bit_sets, words_per_sample: int, num_sites: int, out=None,
+                      stream=None):
+        """Genotype counts per sample (cuking_sample_counts): (hom_ref, het, hom_var,
+        missing) of every row of ``bit_sets`` over the sites ``[0, num_sites)`` -- padding is
+        not counted -- as a device tensor ``[rows, 4]`` int32, OVERWRITTEN.  Call rate and
+        heterozygosity follow: the usual ``priority`` of ``unrelated_set``.  Does not
+        synchronise."""
+        rows = self._rows_of(bit_sets, words_per_sample)
+        out = self._counts_out(out, (rows, 4), zero=False)
+        check(self.lib.cuking_sample_counts(self.handle, bit_sets.data_ptr(), rows,
+                                            words_per_sample, _count(num_sites, "num_sites"),
+                                            out.data_ptr(), _stream_handle(stream)))
+        return out
+
+    def compact_sites(self, bit_sets, words_per_sample: int, keep_words, num_sites: int,
+                      out=None, stream=None):
+        """The bitset restricted to the sites of a mask (cuking_compact_sites): the k-th
+        kept site of every row becomes site k of the result, what follows the last one is
+        missing -- byte for byte the bitset packed from the genotypes of the kept sites.
+        ``keep_words``: host uint64 ``[P]`` (``site_mask_host``, ``site_mask_words``); ANY
+        mask, not only the rule's.  Returns ``(new_bits, new_words_per_sample, num_kept)``;
+        ``out``: an int64 tensor of ``rows x words_per_sample(num_kept)`` words to write
+        into, not overlapping ``bit_sets``.  A mask that keeps no site raises ``CukingError``
+        ("no site passes").  Waits for the upload of the mask's table on ``stream``; the
+        kernel is asynchronous."""
+        import torch
+        rows = self._rows_of(bit_sets, words_per_sample)
+        keep = _keep_words(keep_words, words_per_sample)
+        kept = _popcount(keep)
+        wps_out = self.lib.cuking_words_per_sample(max(kept, 1))
+        if out is None:
+            out = torch.empty((max(rows, 1), wps_out), dtype=torch.int64,
+                              device=f"cuda:{self.device}")
+        elif self._rows_of(out, wps_out) < rows:
+            raise ValueError(f"out holds {out.numel()} words, {rows} rows of {wps_out} are "
+                             "needed")
+        check(self.lib.cuking_compact_sites(
+            self.handle, bit_sets.data_ptr(), rows, words_per_sample, keep.ctypes.data,
+            _count(num_sites, "num_sites"), out.data_ptr(), wps_out, _stream_handle(stream)))
+        return out, wps_out, kept
+
+    def filter_sites(self, bit_sets, words_per_sample: int, num_sites: int,
+                     min_call_rate: float = 0.0, min_maf: float = 0.0, min_mac: int = 0,
+                     also=None, stream=None) -> "SiteQC":
+        """Count, mask and compact in one call: ``site_counts`` of the rows of
+        ``bit_sets``, ``site_mask_host`` with the rule given, ``compact_sites`` with its
+        mask.  Returns a ``SiteQC`` whose ``bits`` / ``words_per_sample`` / ``num_sites``
+        everything behind (records, matrix, summary, relative counts) takes in place of the
+        unfiltered ones.  Waits for the counts."""
+        import torch
+        counts = self.site_counts(bit_sets, words_per_sample, stream=stream)
+        (stream if stream is not None else torch.cuda.current_stream(self.device)).synchronize()
+        host = counts.cpu().numpy().view(np.uint32)
+        keep, kept = site_mask_host(host, num_sites, min_call_rate, min_maf, min_mac, also)
+        bits, wps, _ = self.compact_sites(bit_sets, words_per_sample, keep, num_sites,
+                                          stream=stream)
+        return SiteQC(host, keep, num_sites, bits, wps, kept)
+
     def synth_bitset(self, seed: int, kind, pa, pb, sample_begin: int,
                      sample_end: int, num_sites: int, out=None, stream=None, model=0):
         """Synthetic reference-layout bitset rows [sample_begin, sample_end)
@@ -792,6 +976,47 @@ class RelativeCounts:
         return int(column[:sm.NumRows()].sum())
 
 
+class SiteQC:
+    """What ``KingContext.filter_sites`` returns.  The filtered cohort: ``bits`` (device
+    int64 ``[rows, words_per_sample]``), ``words_per_sample`` and ``num_sites`` (the number of
+    kept sites).  The input's sites: ``num_sites_in``, ``counts()``, ``keep()``,
+    ``kept_index()``, ``allele_freq()`` and ``call_rate()`` -- host arrays, one entry per
+    site of the INPUT."""
+
+    def __init__(self, site_counts: np.ndarray, keep_words: np.ndarray, num_sites_in: int,
+                 bits, words_per_sample: int, num_sites: int):
+        self.site_counts, self.keep_words, self.num_sites_in = site_counts, keep_words, num_sites_in
+        self.bits, self.words_per_sample, self.num_sites = bits, words_per_sample, num_sites
+
+    def counts(self) -> np.ndarray:
+        """uint32 ``[num_sites_in, 4]``: samples hom-ref, het, hom-var and missing."""
+        return self.site_counts[:self.num_sites_in]
+
+    def keep(self) -> np.ndarray:
+        """bool ``[num_sites_in]``: the sites that passed."""
+        return site_mask_bool(self.keep_words, self.num_sites_in)
+
+    def kept_index(self) -> np.ndarray:
+        """The input sites that passed, ascending: site k of ``bits`` is input site
+        ``kept_index()[k]``."""
+        return np.flatnonzero(self.keep())
+
+    def allele_freq(self) -> np.ndarray:
+        """float64 ``[num_sites_in]``: the frequency of the counted allele among the called
+        genotypes, ``(het + 2 hom_var) / (2 called)``; NaN where nothing was called."""
+        c = self.counts().astype(np.float64)
+        called = c[:, 0] + c[:, 1] + c[:, 2]
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return np.where(called > 0, (c[:, 1] + 2 * c[:, 2]) / (2 * called), np.nan)
+
+    def call_rate(self) -> np.ndarray:
+        """float64 ``[num_sites_in]``: ``called / (called + missing)``; NaN without samples."""
+        c = self.counts().astype(np.float64)
+        n = c.sum(axis=1)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return np.where(n > 0, (n - c[:, 3]) / n, np.nan)
+
+
 def _count(value, name: str) -> int:
     if isinstance(value, bool) or int(value) != value or int(value) < 0:
         raise ValueError(f"{name} must be a non-negative integer, not {value!r}")
@@ -903,6 +1128,7 @@ __all__ = [
     "KING_RESULT_DTYPE", "KING_COUNTS_DTYPE",
     "ResourceExhaustedError", "CukingError", "padded_sites",
     "words_per_sample", "bytes_per_pair", "new_host_bitset", "pack_host", "pack_bed_host",
+    "site_mask_host", "site_mask_words", "site_mask_bool", "compact_sites_host", "SiteQC",
     "sort_results", "device_count", "synth_models", "synth_model_number",
     "DEFAULT_KIN_THRESHOLD",
     "DEFAULT_MAX_RESULTS",

@@ -27,7 +27,8 @@ CLI_PATH = PKG / "bin" / "cuking"
 LIB_FLAGS_PATH = PKG / "libcuking_amd.flags"
 
 HIP_SOURCES = ["king_abi.hip", "king_kernels.hip", "king_mfma.hip", "king_filter.hip",
-               "king_sort.hip", "king_prune.hip", "king_bed.hip", "synth.hip"]
+               "king_sort.hip", "king_prune.hip", "king_bed.hip", "king_site_qc.hip",
+               "synth.hip"]
 # Host-only half of the ABI: plain C++, also compiled by the sanitizer tests.
 HOST_ABI_SOURCES = ["king_host.cc"]
 # IEEE-correct fp32 divide (kinship must match the reference bit for bit):
@@ -64,7 +65,8 @@ def build_library(force: bool = False, save_temps: bool = False) -> Path:
     srcs = [CSRC / s for s in HIP_SOURCES + HOST_ABI_SOURCES]
     deps = srcs + [CSRC / "king_common.h", CSRC / "king_device.h", CSRC / "king_host.h",
                    CSRC / "king_launch_plan.h", CSRC / "king_kin_summary.h",
-                   CSRC / "king_unrelated.h", CSRC / "king_submatrix.h", INCLUDE / "cuking_amd.h",
+                   CSRC / "king_unrelated.h", CSRC / "king_submatrix.h", CSRC / "king_site_qc.h",
+                   INCLUDE / "cuking_amd.h",
                    Path(__file__)]
     extra = os.environ.get("CUKING_EXTRA_HIPFLAGS", "").split()
     wanted = " ".join(extra)
@@ -96,6 +98,8 @@ def build_library(force: bool = False, save_temps: bool = False) -> Path:
     problems = check_mfma_loops(cwd / "king_mfma-hip-amdgcn-amd-amdhsa-gfx950.s")
     problems += check_filter_loop(cwd / "king_filter-hip-amdgcn-amd-amdhsa-gfx950.s")
     problems += check_no_scratch(cwd / "king_bed-hip-amdgcn-amd-amdhsa-gfx950.s", "pack_bed_kernel")
+    for kernel in ("site_counts_kernel", "sample_counts_kernel", "compact_sites_kernel"):
+        problems += check_no_scratch(cwd / "king_site_qc-hip-amdgcn-amd-amdhsa-gfx950.s", kernel)
     if problems and not extra:
         LIB_PATH.unlink(missing_ok=True)
         raise RuntimeError("the compiler put vector-memory waits or scratch accesses inside an "

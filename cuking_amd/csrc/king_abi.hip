@@ -13,6 +13,7 @@
 #include "king_common.h"
 #include "king_host.h"
 #include "king_kin_summary.h"
+#include "king_site_qc.h"
 #include "king_unrelated.h"
 
 using namespace cuking;
@@ -119,6 +120,9 @@ struct cuking_ctx {
     // cuking_unrelated_set's workspace (king_prune.hip), grown when a call needs more
     void *prune = nullptr;
     size_t prune_bytes = 0;
+    // cuking_compact_sites' table (king_site_qc.h), grown when a call needs more
+    void *sites = nullptr;
+    size_t sites_bytes = 0;
   };
   std::vector<StreamScratch> scratch;
   // The running totals of filter scratch that has been freed since (a larger block took
@@ -341,6 +345,7 @@ void evict_scratch(cuking_ctx *ctx, size_t k) {
   free_filter_scratch(ctx, e);
   if (e.split != nullptr) (void)hipFree(e.split);
   if (e.prune != nullptr) (void)hipFree(e.prune);
+  if (e.sites != nullptr) (void)hipFree(e.sites);
   ctx->scratch.erase(ctx->scratch.begin() + (ptrdiff_t)k);
 }
 
@@ -1053,6 +1058,7 @@ void cuking_ctx_destroy(cuking_ctx *ctx) {
     if (e.split) (void)hipFree(e.split);
     if (e.filter) (void)hipFree(e.filter);
     if (e.prune) (void)hipFree(e.prune);
+    if (e.sites) (void)hipFree(e.sites);
   }
   for (auto &r : ctx->readers)
     if (r.second) (void)hipEventDestroy(r.second);
@@ -1909,6 +1915,91 @@ cuking_status cuking_unrelated_set(cuking_ctx *ctx, const cuking_result *d_recor
                        "unrelated set: internal error, a loop ran past its bound of %u rounds",
                        num_samples);
   if (rounds != nullptr) *rounds = done;
+  return CUKING_OK;
+}
+
+// ---- site QC (king_site_qc.hip) -------------------------------------------
+
+cuking_status cuking_site_counts(cuking_ctx *ctx, const uint64_t *d_bit_set,
+                                 uint32_t num_stored, uint32_t words_per_sample,
+                                 uint32_t *d_counts, void *stream) {
+  // (the arguments first: a refused call touches no device)
+  if (ctx == nullptr) return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "null context");
+  cuking_status st = cuking_check_counts_args("site counts", d_bit_set, num_stored,
+                                              words_per_sample, d_counts);
+  if (st != CUKING_OK) return st;
+  if (num_stored == 0) return CUKING_OK;
+  st = bind(ctx);
+  if (st != CUKING_OK) return st;
+  HIP_TRY(launch_site_counts(d_bit_set, num_stored, words_per_sample, d_counts,
+                             (hipStream_t)stream));
+  return CUKING_OK;
+}
+
+cuking_status cuking_sample_counts(cuking_ctx *ctx, const uint64_t *d_bit_set,
+                                   uint32_t num_stored, uint32_t words_per_sample,
+                                   uint32_t num_sites, uint32_t *d_counts, void *stream) {
+  if (ctx == nullptr) return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "null context");
+  cuking_status st = cuking_check_counts_args("sample counts", d_bit_set, num_stored,
+                                              words_per_sample, d_counts);
+  if (st != CUKING_OK) return st;
+  if (cuking_words_per_sample(num_sites) != words_per_sample)
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT,
+                       "sample counts: %u sites need %u words per sample, not %u", num_sites,
+                       cuking_words_per_sample(num_sites), words_per_sample);
+  if (num_stored == 0) return CUKING_OK;
+  st = bind(ctx);
+  if (st != CUKING_OK) return st;
+  HIP_TRY(launch_sample_counts(d_bit_set, num_stored, words_per_sample, num_sites, d_counts,
+                               (hipStream_t)stream));
+  return CUKING_OK;
+}
+
+cuking_status cuking_compact_sites(cuking_ctx *ctx, const uint64_t *d_in, uint32_t num_stored,
+                                   uint32_t words_per_sample_in, const uint64_t *keep,
+                                   uint32_t num_sites_in, uint64_t *d_out,
+                                   uint32_t words_per_sample_out, void *stream) {
+  if (ctx == nullptr) return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "null context");
+  uint32_t kept = 0;
+  cuking_status st = cuking_check_compact_args(d_in, num_stored, words_per_sample_in, keep,
+                                               num_sites_in, d_out, words_per_sample_out, &kept);
+  if (st != CUKING_OK) return st;
+  if (num_stored == 0) return CUKING_OK;
+  st = bind(ctx);
+  if (st != CUKING_OK) return st;
+  hipStream_t s = (hipStream_t)stream;
+  cuking_ctx::StreamScratch *e = nullptr;
+  for (auto &x : ctx->scratch)
+    if (x.stream == s) e = &x;
+  if (e == nullptr) {
+    if (ctx->scratch.size() >= kMaxStreams) evict_scratch(ctx, 0);
+    ctx->scratch.push_back({s});
+    e = &ctx->scratch.back();
+  }
+  const uint32_t plane_in = words_per_sample_in / 2, plane_out = words_per_sample_out / 2;
+  const size_t bytes = compact_table_bytes(plane_in, plane_out);
+  if (e->sites_bytes < bytes) {
+    if (e->sites != nullptr) {  // an earlier call on this stream may still read it
+      ++ctx->host_syncs;
+      HIP_TRY(hipStreamSynchronize(s));
+      (void)hipFree(e->sites);
+      e->sites = nullptr;
+      e->sites_bytes = 0;
+    }
+    HIP_TRY(hipMalloc(&e->sites, bytes));
+    ++ctx->workspace_allocations;
+    e->sites_bytes = bytes;
+  }
+  // (8-byte units: the table starts with uint64 fields)
+  std::vector<uint64_t> table((bytes + 7) / 8);
+  build_compact_table(keep, plane_in, plane_out, table.data());
+  // Ordered on the stream behind whatever still reads the table of an earlier call.  Small and
+  // pageable: wait until the host buffer may go away.
+  HIP_TRY(hipMemcpyAsync(e->sites, table.data(), bytes, hipMemcpyHostToDevice, s));
+  ++ctx->host_syncs;
+  HIP_TRY(hipStreamSynchronize(s));
+  HIP_TRY(launch_compact_sites(d_in, num_stored, words_per_sample_in, e->sites, kept, d_out,
+                               words_per_sample_out, s));
   return CUKING_OK;
 }
 

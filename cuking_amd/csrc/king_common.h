@@ -625,6 +625,22 @@ hipError_t launch_pack_bed(const cuking_submatrix &sm, uint32_t words_per_sample
                            uint64_t *d_bit_set, const uint8_t *d_bed_rows, uint64_t row_bytes,
                            uint32_t site_begin, uint32_t site_end, hipStream_t stream);
 
+// Site QC (king_site_qc.hip; arguments already checked, king_host.h).  launch_site_counts ADDS
+// into d_counts [64 P][4], launch_sample_counts overwrites d_counts [num_stored][4];
+// launch_compact_sites reads d_table, the device copy of build_compact_table's output
+// (king_site_qc.h).  site_counts_block_samples: the most samples one workgroup of the count
+// kernel adds up between two flushes of its bit-sliced counters.
+hipError_t launch_site_counts(const uint64_t *d_bit_set, uint32_t num_stored,
+                              uint32_t words_per_sample, uint32_t *d_counts, hipStream_t stream);
+hipError_t launch_sample_counts(const uint64_t *d_bit_set, uint32_t num_stored,
+                                uint32_t words_per_sample, uint32_t num_sites,
+                                uint32_t *d_counts, hipStream_t stream);
+hipError_t launch_compact_sites(const uint64_t *d_in, uint32_t num_stored,
+                                uint32_t words_per_sample_in, const void *d_table,
+                                uint32_t num_kept, uint64_t *d_out,
+                                uint32_t words_per_sample_out, hipStream_t stream);
+uint32_t site_counts_block_samples();
+
 // Cohort models of the synthetic generator (synth.hip holds the specification).  d_tables:
 // synth_table_bytes() of scratch the launch fills and reads (per-site and per-sample
 // tables); it must stay untouched until the launch has run.

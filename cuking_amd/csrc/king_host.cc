@@ -370,6 +370,136 @@ cuking_status cuking_pack_bed_host(const cuking_submatrix *sm, uint32_t words_pe
   return CUKING_OK;
 }
 
+}  // extern "C"
+
+// ---- site QC: the argument checks, the site rule and the host compaction --------------------
+cuking_status cuking_check_counts_args(const char *what, const void *bit_set, uint32_t num_stored,
+                                       uint32_t words_per_sample, const void *counts) {
+  if (words_per_sample == 0 || (words_per_sample & 1))
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT,
+                       "%s: words_per_sample must be a positive even number", what);
+  if (num_stored != 0 && (bit_set == nullptr || counts == nullptr))
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "%s: null pointer", what);
+  return CUKING_OK;
+}
+
+cuking_status cuking_check_compact_args(const void *in, uint32_t num_stored,
+                                        uint32_t words_per_sample_in, const uint64_t *keep,
+                                        uint32_t num_sites_in, const void *out,
+                                        uint32_t words_per_sample_out, uint32_t *num_kept) {
+  if (in == nullptr || keep == nullptr || out == nullptr)
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "compact sites: null pointer");
+  if (words_per_sample_in == 0 || (words_per_sample_in & 1) || words_per_sample_out == 0 ||
+      (words_per_sample_out & 1))
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT,
+                       "compact sites: words_per_sample must be a positive even number");
+  if (cuking_words_per_sample(num_sites_in) != words_per_sample_in)
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT,
+                       "compact sites: %u sites need %u words per sample, not %u", num_sites_in,
+                       cuking_words_per_sample(num_sites_in), words_per_sample_in);
+  const uint32_t plane_in = words_per_sample_in / 2;
+  uint64_t kept = 0;
+  for (uint32_t w = 0; w < plane_in; ++w) {
+    const uint64_t first = (uint64_t)w * 64;  // bits of this word at or beyond num_sites_in
+    const uint64_t beyond = first >= num_sites_in        ? ~0ull
+                            : num_sites_in - first >= 64 ? 0ull
+                                                         : ~0ull << (num_sites_in - first);
+    if (keep[w] & beyond)
+      return cuking_fail(CUKING_ERR_INVALID_ARGUMENT,
+                         "compact sites: the mask keeps site %llu, the input has %u sites",
+                         (unsigned long long)(first + (uint64_t)__builtin_ctzll(keep[w] & beyond)),
+                         num_sites_in);
+    kept += (uint64_t)__builtin_popcountll(keep[w]);
+  }
+  if (kept == 0) return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "compact sites: no site passes");
+  if (cuking_words_per_sample((uint32_t)kept) != words_per_sample_out)
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT,
+                       "compact sites: the %llu kept sites need %u words per sample, not %u",
+                       (unsigned long long)kept, cuking_words_per_sample((uint32_t)kept),
+                       words_per_sample_out);
+  const uintptr_t a = reinterpret_cast<uintptr_t>(in), b = reinterpret_cast<uintptr_t>(out);
+  const uint64_t a_bytes = (uint64_t)num_stored * words_per_sample_in * 8;
+  const uint64_t b_bytes = (uint64_t)num_stored * words_per_sample_out * 8;
+  if (a < b + b_bytes && b < a + a_bytes)
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT,
+                       "compact sites: the output overlaps the input (the call works out of "
+                       "place)");
+  if (num_kept != nullptr) *num_kept = (uint32_t)kept;
+  return CUKING_OK;
+}
+
+extern "C" {
+
+cuking_status cuking_site_mask_host(const uint32_t *counts, uint32_t num_sites,
+                                    uint32_t plane_words, const cuking_site_filter *filter,
+                                    const uint64_t *also, uint64_t *keep, uint32_t *num_kept) {
+  if (counts == nullptr || filter == nullptr || keep == nullptr)
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "site mask: null pointer");
+  if (plane_words != cuking_words_per_sample(num_sites) / 2)
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT,
+                       "site mask: %u sites have %u plane words, not %u", num_sites,
+                       cuking_words_per_sample(num_sites) / 2, plane_words);
+  // (written so that NaN fails)
+  if (!(filter->min_call_rate >= 0.0f && filter->min_call_rate <= 1.0f))
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT,
+                       "site mask: min_call_rate (%g) must be in [0, 1]",
+                       (double)filter->min_call_rate);
+  if (!(filter->min_maf >= 0.0f && filter->min_maf <= 1.0f))
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "site mask: min_maf (%g) must be in [0, 1]",
+                       (double)filter->min_maf);
+  const double min_call_rate = (double)filter->min_call_rate, min_maf = (double)filter->min_maf;
+  uint32_t kept = 0;
+  for (uint32_t w = 0; w < plane_words; ++w) {
+    uint64_t word = 0;
+    for (uint32_t bit = 0; bit < 64; ++bit) {
+      const uint64_t s = (uint64_t)w * 64 + bit;
+      if (s >= num_sites) break;
+      const uint32_t *c = counts + s * 4;
+      const uint64_t called = (uint64_t)c[0] + c[1] + c[2], n = called + c[3];
+      const uint64_t alt = (uint64_t)c[1] + 2 * (uint64_t)c[2];
+      const uint64_t minor = std::min(alt, 2 * called - alt);
+      const double need_called = min_call_rate * (double)n;
+      const double need_minor = min_maf * (double)(2 * called);
+      const bool ok = called > 0 && (double)called >= need_called &&
+                      (double)minor >= need_minor && minor >= filter->min_mac;
+      if (ok) word |= 1ull << bit;
+    }
+    if (also != nullptr) word &= also[w];
+    keep[w] = word;
+    kept += (uint32_t)__builtin_popcountll(word);
+  }
+  if (num_kept != nullptr) *num_kept = kept;
+  return CUKING_OK;
+}
+
+cuking_status cuking_compact_sites_host(const uint64_t *bit_set_in, uint32_t num_stored,
+                                        uint32_t words_per_sample_in, const uint64_t *keep,
+                                        uint32_t num_sites_in, uint64_t *bit_set_out,
+                                        uint32_t words_per_sample_out) {
+  uint32_t kept = 0;
+  const cuking_status st =
+      cuking_check_compact_args(bit_set_in, num_stored, words_per_sample_in, keep, num_sites_in,
+                                bit_set_out, words_per_sample_out, &kept);
+  if (st != CUKING_OK) return st;
+  const uint32_t plane_in = words_per_sample_in / 2, plane_out = words_per_sample_out / 2;
+  for (uint32_t s = 0; s < num_stored; ++s) {
+    const uint64_t *in = bit_set_in + (uint64_t)s * words_per_sample_in;
+    uint64_t *out = bit_set_out + (uint64_t)s * words_per_sample_out;
+    // all missing, then one kept site after the other
+    for (uint32_t w = 0; w < words_per_sample_out; ++w) out[w] = ~0ull;
+    uint64_t k = 0;
+    for (uint64_t site = 0; site < num_sites_in; ++site) {
+      if (!((keep[site >> 6] >> (site & 63)) & 1)) continue;
+      const uint64_t het = (in[site >> 6] >> (site & 63)) & 1;
+      const uint64_t hom = (in[plane_in + (site >> 6)] >> (site & 63)) & 1;
+      if (!het) out[k >> 6] &= ~(1ull << (k & 63));
+      if (!hom) out[plane_out + (k >> 6)] &= ~(1ull << (k & 63));
+      ++k;
+    }
+  }
+  return CUKING_OK;
+}
+
 // ---- schedules of a block over the GPUs of a node (host/schedule.h) ----------
 void cuking_schedule_tile_partition(uint64_t num_tiles, uint32_t world, uint64_t *out) {
   if (world == 0 || out == nullptr) return;

@@ -17,5 +17,13 @@ cuking_status cuking_check_bed_args(const cuking_submatrix *sm, uint32_t words_p
                                     const void *bit_set, const void *bed_rows,
                                     uint64_t row_bytes, uint32_t site_begin, uint32_t site_end,
                                     uint32_t num_sites);
+// Argument checks of cuking_site_counts / cuking_sample_counts (`what` names the call) and of
+// cuking_compact_sites_host / cuking_compact_sites, which also gives the number of kept sites.
+cuking_status cuking_check_counts_args(const char *what, const void *bit_set, uint32_t num_stored,
+                                       uint32_t words_per_sample, const void *counts);
+cuking_status cuking_check_compact_args(const void *in, uint32_t num_stored,
+                                        uint32_t words_per_sample_in, const uint64_t *keep,
+                                        uint32_t num_sites_in, const void *out,
+                                        uint32_t words_per_sample_out, uint32_t *num_kept);
 
 #endif  // CUKING_AMD_KING_HOST_H_

@@ -7,7 +7,10 @@
 One process per GPU.  Rank 0 reads `metadata.json` + `*.parquet`, packs the
 bitset through the C ABI (`cuking_pack_host`, reader threads like
 cuking.cu:550-553) -- or, with `--bed-uri PREFIX`, streams a PLINK `.bed` to its
-GPU and transposes it there (`KingContext.load_bed`) --, the bitset goes to the other GPUs by the staged RCCL
+GPU and transposes it there (`KingContext.load_bed`) --, optionally drops sites
+by call rate, minor allele frequency / count or a list (`--site-min-call-rate`,
+`--site-min-maf`, `--site-min-mac`, `--site-keep-uri`: counts and compaction on the
+GPU, csrc/king_site_qc.hip), the bitset goes to the other GPUs by the staged RCCL
 broadcast of `cuking_amd.dist`, every rank evaluates its band of the pair
 space, rank 0 gathers, sorts and writes `part-<shard>.snappy.parquet` with the
 reference's schema (cuking.cu:767-870).  `--split-factor/--shard-index` select a
@@ -96,6 +99,27 @@ def parse_args(argv=None):
     flag("unrelated-threshold", type=float, default=None,
          help="records with kin above this are the edges of --unrelated-uri (default: "
               "--kin-threshold; not below it)")
+    flag("site-min-call-rate", type=float, default=None,
+         help="site QC before anything is computed: keep the sites whose share of called "
+              "genotypes is at least this (0..1).  Any of --site-min-call-rate, --site-min-maf, "
+              "--site-min-mac and --site-keep-uri makes the run count the genotypes per site on "
+              "the GPU, drop the sites that fail (and those without a called genotype) and "
+              "compact the bitset there; records and every side output then come from the kept "
+              "sites.  One process and --split-factor 1 only")
+    flag("site-min-maf", type=float, default=None,
+         help="site QC: keep the sites whose minor allele frequency among the called genotypes "
+              "is at least this (0..1; above 0.5 nothing passes)")
+    flag("site-min-mac", type=int, default=None,
+         help="site QC: keep the sites whose minor allele count is at least this (1 drops the "
+              "monomorphic sites)")
+    flag("site-keep-uri", default="",
+         help="site QC: a .npy file of one bool / uint8 per site, ANDed with the rule -- an "
+              "LD-pruned site list, a region")
+    flag("site-qc-uri", default="",
+         help="also write the site QC report of the INPUT cohort to this .npz file "
+              "(site_counts [sites, 4] = hom-ref, het, hom-var, missing; keep; sample_counts "
+              "[samples, 4]; samples; min_call_rate, min_maf, min_mac).  Alone it only reports: "
+              "nothing is filtered.  One process and --split-factor 1 only")
     return ap.parse_args(argv)
 
 
@@ -185,6 +209,36 @@ def validate(args):  # cuking.cu:437-462
                          "property of the whole cohort's records (concatenate the shards' "
                          "record buffers and call unrelated_set instead)")
     unrelated_threshold(args)
+    if site_filtering(args) or args.site_qc_uri:
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            raise UsageError("--site_min_call_rate, --site_min_maf, --site_min_mac, "
+                             "--site_keep_uri and --site_qc_uri need one process (one GPU): site "
+                             "counts are not merged across ranks yet")
+        if args.split_factor != 1:
+            raise UsageError("--site_min_call_rate, --site_min_maf, --site_min_mac, "
+                             "--site_keep_uri and --site_qc_uri need --split_factor 1: a site "
+                             "passes or fails on the whole cohort's counts")
+    site_rule(args)
+
+
+def site_filtering(args) -> bool:
+    """Does the run drop sites (any of the four flags that select them)?"""
+    return (args.site_min_call_rate is not None or args.site_min_maf is not None or
+            args.site_min_mac is not None or bool(args.site_keep_uri))
+
+
+def site_rule(args):
+    """--site-min-call-rate / --site-min-maf / --site-min-mac as the library sees them."""
+    rate = 0.0 if args.site_min_call_rate is None else float(np.float32(args.site_min_call_rate))
+    maf = 0.0 if args.site_min_maf is None else float(np.float32(args.site_min_maf))
+    mac = 0 if args.site_min_mac is None else args.site_min_mac
+    if not 0.0 <= rate <= 1.0:
+        raise UsageError("--site_min_call_rate must be in [0, 1]")
+    if not 0.0 <= maf <= 1.0:
+        raise UsageError("--site_min_maf must be in [0, 1]")
+    if not 0 <= mac <= 0xFFFFFFFF:
+        raise UsageError("--site_min_mac must be a count, 0 or more")
+    return rate, maf, mac
 
 
 def unrelated_threshold(args) -> float:
@@ -324,6 +378,36 @@ def write_unrelated(path: Path, ctx, recs: np.ndarray, sample_ids, threshold: fl
                  samples=np.array(list(sample_ids), dtype=str), threshold=np.float32(threshold))
 
 
+def site_qc(ctx, args, bits, wps: int, num_sites: int, sample_ids, keep_path, qc_path):
+    """Site QC of the whole cohort's bitset: counts on the GPU, the rule on the host, the
+    report if one is asked for, and -- with a flag that selects sites -- the compacted bitset.
+    Returns (bits, words_per_sample, num_sites) for everything behind."""
+    import cuking_amd
+    rate, maf, mac = site_rule(args)
+    also = None
+    if keep_path is not None:
+        also = np.load(keep_path)
+        if also.shape != (num_sites,):
+            raise ValueError(f"--site_keep_uri holds {also.shape}, the cohort has {num_sites} "
+                             "sites")
+    counts = ctx.site_counts(bits, wps).cpu().numpy().view(np.uint32)
+    keep, kept = cuking_amd.site_mask_host(counts, num_sites, rate, maf, mac, also=also)
+    if qc_path is not None:
+        per_sample = ctx.sample_counts(bits, wps, num_sites).cpu().numpy().view(np.uint32)
+        qc_path.parent.mkdir(parents=True, exist_ok=True)
+        with open(qc_path, "wb") as f:   # (np.savez would append .npz to another suffix)
+            np.savez(f, site_counts=counts[:num_sites],
+                     keep=cuking_amd.site_mask_bool(keep, num_sites), sample_counts=per_sample,
+                     samples=np.array(list(sample_ids), dtype=str),
+                     min_call_rate=np.float32(rate), min_maf=np.float32(maf),
+                     min_mac=np.uint32(mac))
+    if not site_filtering(args):
+        return bits, wps, num_sites
+    bits, wps, kept = ctx.compact_sites(bits, wps, keep, num_sites)
+    print(f"[cuking_amd.run] site QC keeps {kept} of {num_sites} sites", flush=True)
+    return bits, wps, kept
+
+
 def main(argv=None) -> int:
     args = parse_args(argv)
     import torch
@@ -344,6 +428,8 @@ def main(argv=None) -> int:
         counts_path = resolve_uri(args.relative_counts_uri) if args.relative_counts_uri else None
         unrelated_path = resolve_uri(args.unrelated_uri) if args.unrelated_uri else None
         priority_path = resolve_uri(args.unrelated_priority) if args.unrelated_priority else None
+        site_keep_path = resolve_uri(args.site_keep_uri) if args.site_keep_uri else None
+        site_qc_path = resolve_uri(args.site_qc_uri) if args.site_qc_uri else None
         synthetic = None
         if args.synthetic:
             parts = [int(x) for x in args.synthetic.split(",")]
@@ -424,6 +510,10 @@ def main(argv=None) -> int:
                 pack_error = RuntimeError("rank 0 failed to read the input")
         if pack_error is not None:
             raise RuntimeError(str(pack_error))
+        if site_filtering(args) or site_qc_path is not None:
+            # (one process, the whole cohort: validate) -- what follows sees the kept sites only
+            bits, wps, num_sites = site_qc(ctx, args, bits[:stored], wps, num_sites, sample_ids,
+                                           site_keep_path, site_qc_path)
         t1 = time.perf_counter()
         after_reserve = lambda: (0, 0)    # noqa: E731 - (allocations, host waits) since the reservation
         if sm.i_begin == sm.j_begin:

@@ -689,6 +689,88 @@ cuking_status cuking_unrelated_set(cuking_ctx *ctx, const cuking_result *d_recor
                                    uint8_t *d_keep, uint32_t *d_family, uint32_t *rounds,
                                    void *stream);
 
+/* Site QC: genotype counts per site and per sample, a site mask from the usual rule, and the
+ * bitset compacted to the kept sites -- the step between a loaded cohort (a .bed arrives
+ * unfiltered) and everything that reads a bitset, which then runs unchanged on a smaller
+ * words_per_sample.
+ *
+ * Layout (cuking.cu:507-523): uint64 bits[num_stored][words_per_sample], P = words_per_sample
+ * / 2 plane words, each sample [het words | hom_var words], site s = bit s & 63 of word s >> 6;
+ * (het, hom_var) = 00 hom-ref, 10 het, 01 hom-var, 11 missing; sites from num_sites to 64 P are
+ * padding and read as missing.  All calls take a plain range of num_stored rows, not a block:
+ * the caller of an off-diagonal block passes its rows and columns as it sees fit.
+ *
+ * cuking_site_counts: for every plane site 0 .. 64 P - 1, the number of the num_stored samples
+ * that are hom-ref, het, hom-var and missing is ADDED to d_counts[site][0 .. 3] (uint32
+ * [64 P][4], zeroed by the caller before the first call).  The four counts of a site sum to
+ * the number of samples counted; padding sites come out as missing += num_stored.  Because the
+ * call accumulates, row ranges, tile ranges and GPUs merge by sum; integer sums only, so the
+ * result does not depend on launch shape or timing.  One read of the bitset (king_site_qc.hip).
+ * cuking_sample_counts: OVERWRITES d_counts[sample][0 .. 3] (uint32 [num_stored][4]) with the
+ * (hom_ref, het, hom_var, missing) of each stored sample over the sites [0, num_sites) only:
+ * padding is not counted, the four sum to num_sites.  words_per_sample must be
+ * cuking_words_per_sample(num_sites).
+ * Both: INVALID_ARGUMENT for a null pointer (with num_stored != 0) and a words_per_sample that
+ * is zero or odd; num_stored == 0 returns OK without work.  Asynchronous on `stream`.
+ *
+ * cuking_site_mask_host, the site rule (host only: O(sites) work on 16 B per site).  With
+ * called = hom_ref + het + hom_var, n = called + missing, alt = het + 2 hom_var and minor =
+ * min(alt, 2 called - alt), site s is kept iff ALL of
+ *     s < num_sites
+ *     called > 0
+ *     (double)called >= (double)min_call_rate * (double)n
+ *     (double)minor  >= (double)min_maf * (double)(2 called)
+ *     minor >= min_mac
+ *     bit s of `also`, if `also` is not NULL ([P] words, site s = bit s & 63 of word s >> 6)
+ * each inequality one IEEE double product and one comparison, nothing fused.  {0, 0, 0} keeps
+ * every site with one called genotype; min_maf above 0.5 is legal and keeps nothing.  keep
+ * receives [plane_words] words in the same bit order, *num_kept (may be NULL) their popcount.
+ * INVALID_ARGUMENT: a null counts / filter / keep pointer; plane_words !=
+ * cuking_words_per_sample(num_sites) / 2; a rate or frequency outside [0, 1] or NaN.
+ * The compaction takes ANY mask: an LD-pruned site list, an HWE test or a region list is
+ * applied by passing its mask (or by passing it here as `also`).
+ *
+ * cuking_compact_sites_host / cuking_compact_sites: with K = popcount(keep), the k-th kept site
+ * (ascending) of every sample becomes site k of the output, in both planes; every bit from K to
+ * the end of the output plane is missing (1 in both planes).  The output is, byte for byte, the
+ * bitset cuking_pack_host builds from an all-ones one for the genotypes restricted to the kept
+ * sites.  keep: [words_per_sample_in / 2] words in HOST memory for both functions; it may be
+ * freed when the call returns.  Out of place: the output must not overlap the input.  Every
+ * output word is written once with a plain store, nothing else is written: no memset is needed.
+ * INVALID_ARGUMENT: K = 0 ("no site passes"); a null pointer; a words_per_sample that is zero
+ * or odd; words_per_sample_in != cuking_words_per_sample(num_sites_in); words_per_sample_out !=
+ * cuking_words_per_sample(K); a keep bit at or beyond num_sites_in; overlapping buffers.
+ * num_stored == 0 returns OK without work (after the checks).
+ * cuking_compact_sites derives a table of 64 B per input plane word and 4 B per output plane
+ * word from keep and uploads it into the context's per-stream cache, ordered on `stream`; it
+ * waits for that upload (and so for what `stream` held before), the kernel itself is
+ * asynchronous.  One caller per context at a time, like the compute entry points.
+ * Out of scope: the C++ `cuking` binary; several ranks; LD pruning and HWE themselves; sample
+ * filtering and reordering; in-place compaction; filtering inside the .bed loader before the
+ * transpose; rewriting a .bim. */
+typedef struct cuking_site_filter {
+  float min_call_rate; /* called / (called + missing), in [0, 1] */
+  float min_maf;       /* minor / (2 called), in [0, 1] */
+  uint32_t min_mac;    /* minor allele count */
+} cuking_site_filter;
+cuking_status cuking_site_counts(cuking_ctx *ctx, const uint64_t *d_bit_set,
+                                 uint32_t num_stored, uint32_t words_per_sample,
+                                 uint32_t *d_counts, void *stream);
+cuking_status cuking_sample_counts(cuking_ctx *ctx, const uint64_t *d_bit_set,
+                                   uint32_t num_stored, uint32_t words_per_sample,
+                                   uint32_t num_sites, uint32_t *d_counts, void *stream);
+cuking_status cuking_site_mask_host(const uint32_t *counts, uint32_t num_sites,
+                                    uint32_t plane_words, const cuking_site_filter *filter,
+                                    const uint64_t *also, uint64_t *keep, uint32_t *num_kept);
+cuking_status cuking_compact_sites_host(const uint64_t *bit_set_in, uint32_t num_stored,
+                                        uint32_t words_per_sample_in, const uint64_t *keep,
+                                        uint32_t num_sites_in, uint64_t *bit_set_out,
+                                        uint32_t words_per_sample_out);
+cuking_status cuking_compact_sites(cuking_ctx *ctx, const uint64_t *d_in, uint32_t num_stored,
+                                   uint32_t words_per_sample_in, const uint64_t *keep,
+                                   uint32_t num_sites_in, uint64_t *d_out,
+                                   uint32_t words_per_sample_out, void *stream);
+
 /* cuking.cu:761-765 on host memory: sort by (sample_i, sample_j, kin). */
 void cuking_sort_results(cuking_result *results, size_t num_results);
 
