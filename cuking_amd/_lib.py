@@ -150,6 +150,14 @@ SIGNATURES = {
                                      C.POINTER(_u32)]),
     "cuking_compact_sites_host": (_int, [_vp, _u32, _u32, _vp, _u32, _vp, _u32]),
     "cuking_compact_sites": (_int, [_vp, _vp, _u32, _u32, _vp, _u32, _vp, _u32, _vp]),
+    "cuking_ld_site_words": (_u32, [_u32]),
+    "cuking_ld_priority": (_f32, [_vp]),
+    "cuking_transpose_sites_host": (_int, [_vp, _u32, _u32, _u32, _vp, _u32]),
+    "cuking_transpose_sites": (_int, [_vp, _vp, _u32, _u32, _u32, _vp, _u32, _vp]),
+    "cuking_ld_edges_host": (_int, [_vp, _u32, _u32, _u32, _f32, _vp, _vp, _u64,
+                                    C.POINTER(_u64)]),
+    "cuking_ld_edges": (_int, [_vp, _vp, _u32, _u32, _u32, _f32, _vp, _vp, _u64,
+                               C.POINTER(_u64), _vp]),
     "cuking_sort_results": (None, [_vp, _sz]),
     "cuking_timing_enable": (_int, [_vp, _int]),
     "cuking_timing_reset": (_int, [_vp]),

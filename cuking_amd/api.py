@@ -213,6 +213,95 @@ def compact_sites_host(bit_sets: np.ndarray, words_per_sample_in: int, keep_word
     return out, wps_out, kept
 
 
+def ld_site_words(num_stored: int) -> int:
+    """Q: the uint64 words of one plane of one site in the site-major bitset."""
+    return int(_lib.load().cuking_ld_site_words(_count(num_stored, "num_stored")))
+
+
+def transpose_sites_host(bit_sets: np.ndarray, words_per_sample: int, num_sites: int, out=None):
+    """cuking_transpose_sites_host: the host bitset ``[rows, words_per_sample]`` as the
+    site-major bitset uint64 ``[num_sites, 2, Q]`` (plane 0 het, plane 1 hom_var, sample s =
+    bit ``s % 64`` of word ``s // 64``, the tail of the last word set: missing)."""
+    assert bit_sets.dtype == np.uint64 and bit_sets.flags.c_contiguous
+    num_sites = _count(num_sites, "num_sites")
+    rows = bit_sets.size // words_per_sample if words_per_sample else 0
+    q = ld_site_words(rows)
+    if out is None:
+        out = np.empty((num_sites, 2, q), dtype=np.uint64)
+    assert out.dtype == np.uint64 and out.flags.c_contiguous and out.size >= num_sites * 2 * q
+    # (an empty array has no address worth passing: the library refuses NULL, not "nothing")
+    pad = np.zeros(1, dtype=np.uint64)
+    check(_lib.load().cuking_transpose_sites_host(
+        (bit_sets if bit_sets.size else pad).ctypes.data, rows, words_per_sample, num_sites,
+        (out if out.size else pad).ctypes.data, q))
+    return out
+
+
+def _ld_arguments(window, r2):
+    window = _count(window, "window")
+    if window < 2:
+        raise ValueError(f"window must be at least 2 variants, not {window}")
+    r2 = float(np.float32(r2))
+    if not 0.0 <= r2 <= 1.0:
+        raise ValueError(f"r2 must be in [0, 1], not {r2}")
+    return min(window, 0xFFFFFFFF), r2
+
+
+def _ld_default_records(num_sites: int, window: int) -> int:
+    return max(1, min(num_sites * (window - 1), 4 * num_sites))
+
+
+def ld_edges_host(site_bits: np.ndarray, num_sites: int, num_stored: int, window: int = 50,
+                  r2: float = 0.2, group=None, max_records=None):
+    """cuking_ld_edges_host: the pairs of sites ``a < b``, ``b - a < window``, of one
+    ``group``, whose r^2 over the jointly called samples is above ``r2`` (include/cuking_amd.h
+    "LD pruning" has the exact rule), as ``(records, count)``: KING_RESULT_DTYPE records with
+    ``sample_i = a``, ``sample_j = b``, ``kin`` = r^2 and ``ibs0`` = the jointly called
+    samples, sorted by (a, b).  Without ``max_records`` the buffer is sized like the device
+    wrapper's and grown once to the exact count; with it, an overflow raises
+    ``ResourceExhaustedError`` whose ``num_records`` is the exact count."""
+    assert site_bits.dtype == np.uint64 and site_bits.flags.c_contiguous
+    num_sites, num_stored = _count(num_sites, "num_sites"), _count(num_stored, "num_stored")
+    window, r2 = _ld_arguments(window, r2)
+    if site_bits.size != num_sites * 2 * ld_site_words(num_stored):
+        raise ValueError(f"site_bits holds {site_bits.size} words, {num_sites} sites of "
+                         f"{num_stored} samples need {num_sites * 2 * ld_site_words(num_stored)}")
+    if group is not None:
+        group = np.ascontiguousarray(group, dtype=np.int32)
+        if group.shape != (num_sites,):
+            raise ValueError(f"group must hold {num_sites} entries, not {group.shape}")
+    pad = np.zeros(1, dtype=np.uint64)
+    count = C.c_uint64(0)
+
+    def call(capacity):
+        recs = np.zeros(max(capacity, 1), dtype=KING_RESULT_DTYPE)
+        status = _lib.load().cuking_ld_edges_host(
+            (site_bits if site_bits.size else pad).ctypes.data, num_sites, num_stored, window, r2,
+            group.ctypes.data if group is not None and num_sites else None, recs.ctypes.data,
+            capacity, C.byref(count))
+        return recs, status
+
+    recs, status = call(_ld_default_records(num_sites, window) if max_records is None
+                        else _count(max_records, "max_records"))
+    if status == _lib.ERR_RESOURCE_EXHAUSTED and max_records is None:
+        recs, status = call(int(count.value))
+    if status == _lib.ERR_RESOURCE_EXHAUSTED:
+        e = ResourceExhaustedError(_lib.load().cuking_last_error().decode())
+        e.num_records = int(count.value)
+        raise e
+    check(status)
+    return sort_results(recs[:count.value].copy()), int(count.value)
+
+
+def ld_priority_host(counts, num_sites: int) -> np.ndarray:
+    """cuking_ld_priority per site: float32 ``[num_sites]`` from the ``[64 P, 4]`` site counts
+    -- the minor allele frequency among the called genotypes, NaN without one (ranked last)."""
+    num_sites = _count(num_sites, "num_sites")
+    counts = _host_counts(counts, words_per_sample(num_sites) // 2)
+    fn = _lib.load().cuking_ld_priority
+    return np.array([fn(counts[s].ctypes.data) for s in range(num_sites)], dtype=np.float32)
+
+
 def sort_results(results: np.ndarray) -> np.ndarray:
     """cuking.cu:761-765 (in place)."""
     assert results.dtype == KING_RESULT_DTYPE and results.flags.c_contiguous
@@ -829,6 +918,126 @@ class KingContext:
                                           stream=stream)
         return SiteQC(host, keep, num_sites, bits, wps, kept)
 
+    # -- LD pruning -------------------------------------------------------------
+    def transpose_sites(self, bit_sets, words_per_sample: int, num_sites: int, out=None,
+                        stream=None):
+        """The site-major bitset (cuking_transpose_sites): the rows of ``bit_sets`` as an
+        int64 device tensor ``[num_sites, 2, Q]`` -- per site its het and its hom_var plane
+        over the samples, sample s = bit ``s % 64`` of word ``s // 64``, the tail of the last
+        word missing.  Plain stores into every word of ``out``; does not synchronise."""
+        import torch
+        rows = self._rows_of(bit_sets, words_per_sample)
+        num_sites = _count(num_sites, "num_sites")
+        q = self.lib.cuking_ld_site_words(rows)
+        if out is None:
+            out = torch.empty((num_sites, 2, q), dtype=torch.int64, device=f"cuda:{self.device}")
+        elif out.dtype != torch.int64 or not out.is_contiguous() or not out.is_cuda or \
+                out.device.index != self.device or out.numel() < num_sites * 2 * q:
+            raise ValueError(f"out must be a contiguous int64 tensor of {num_sites * 2 * q} words "
+                             "on this context's GPU")
+        check(self.lib.cuking_transpose_sites(
+            self.handle, bit_sets.data_ptr(), rows, words_per_sample, num_sites, out.data_ptr(),
+            q, _stream_handle(stream)))
+        return out
+
+    def ld_edges(self, site_bits, num_sites: int, num_stored: int, window: int = 50,
+                 r2: float = 0.2, group=None, max_records=None, out=None, stream=None):
+        """The LD edges of a site-major bitset (cuking_ld_edges): the pairs ``a < b`` with ``b
+        - a < window``, of one ``group`` (an int32 device tensor of ``num_sites``, e.g.
+        chromosomes; None = one group), whose r^2 is above ``r2``, as records ``sample_i = a,
+        sample_j = b, kin = r^2, ibs0 = jointly called samples`` in no particular order.
+        Returns ``(records, count)``: the ``[*, 6]`` int32 device tensor
+        ``unrelated_set`` takes and the number of edges.  Without ``max_records`` the buffer
+        holds ``min(num_sites x (window - 1), 4 x num_sites)`` records and the call is repeated
+        once with the exact count if that overflows; with it (or with ``out``, a tensor to
+        write into), an overflow raises ``ResourceExhaustedError`` whose ``num_records`` is
+        the exact count -- nothing is written past the buffer.  WAITS for the stream."""
+        import torch
+        num_sites, num_stored = _count(num_sites, "num_sites"), _count(num_stored, "num_stored")
+        window, r2 = _ld_arguments(window, r2)
+        dev = f"cuda:{self.device}"
+        need = num_sites * 2 * self.lib.cuking_ld_site_words(num_stored)
+        if not isinstance(site_bits, torch.Tensor) or not site_bits.is_cuda or \
+                site_bits.device.index != self.device or site_bits.dtype != torch.int64 or \
+                not site_bits.is_contiguous() or site_bits.numel() != need:
+            raise ValueError(f"site_bits must be a contiguous int64 tensor of {need} words on "
+                             "this context's GPU (transpose_sites)")
+        if group is not None:
+            if not isinstance(group, torch.Tensor):
+                group = torch.from_numpy(np.ascontiguousarray(group, dtype=np.int32)).to(dev)
+            if not group.is_cuda or group.device.index != self.device or \
+                    group.dtype != torch.int32 or tuple(group.shape) != (num_sites,) or \
+                    not group.is_contiguous():
+                raise ValueError(f"group must be a contiguous int32 vector of {num_sites} "
+                                 "entries on this context's GPU")
+        if out is not None:
+            if out.dtype != torch.int32 or out.dim() != 2 or out.shape[1] != 6 or \
+                    not out.is_contiguous() or not out.is_cuda or out.device.index != self.device:
+                raise ValueError("out must be a contiguous [*, 6] int32 tensor on this "
+                                 "context's GPU")
+            max_records = out.shape[0] if max_records is None else max_records
+            if _count(max_records, "max_records") > out.shape[0]:
+                raise ValueError(f"out holds {out.shape[0]} records, max_records is {max_records}")
+        count = C.c_uint64(0)
+
+        def call(records, capacity):
+            return self.lib.cuking_ld_edges(
+                self.handle, site_bits.data_ptr(), num_sites, num_stored, window, r2,
+                group.data_ptr() if group is not None and num_sites else None,
+                records.data_ptr(), capacity, C.byref(count), _stream_handle(stream))
+
+        grow = max_records is None
+        capacity = _ld_default_records(num_sites, window) if grow else _count(max_records,
+                                                                              "max_records")
+        records = out if out is not None else torch.empty((max(capacity, 1), 6),
+                                                          dtype=torch.int32, device=dev)
+        status = call(records, capacity)
+        if status == _lib.ERR_RESOURCE_EXHAUSTED and grow:
+            capacity = int(count.value)
+            records = torch.empty((capacity, 6), dtype=torch.int32, device=dev)
+            status = call(records, capacity)
+        if status == _lib.ERR_RESOURCE_EXHAUSTED:
+            e = ResourceExhaustedError(self.lib.cuking_last_error().decode())
+            e.num_records = int(count.value)
+            raise e
+        check(status)
+        return records, int(count.value)
+
+    def ld_prune(self, bit_sets, words_per_sample: int, num_sites: int, window: int = 50,
+                 r2: float = 0.2, group=None, priority=None, compact: bool = True) -> "LDPrune":
+        """LD pruning of a bitset where it lies: ``transpose_sites``; ``site_counts`` and from
+        them the default ``priority`` (minor allele frequency; or a float32 vector of
+        ``num_sites``, host or device: the higher is kept first, among equals the lower site);
+        ``ld_edges`` within ``window`` variants and ``group`` above ``r2``; ``unrelated_set``
+        on the edges -- the kept sites are the lexicographically first maximal independent
+        set in descending priority: no two kept sites of a group within the window have r^2
+        above ``r2``, every dropped site has a kept neighbour --; ``site_mask_words`` and,
+        with ``compact``, ``compact_sites``.  Returns an ``LDPrune`` whose ``bits`` /
+        ``words_per_sample`` / ``num_sites`` everything behind takes in place of the input's
+        (the input itself when every site is kept, or without ``compact``).  Waits for the
+        device."""
+        import torch
+        rows = self._rows_of(bit_sets, words_per_sample)
+        num_sites = _count(num_sites, "num_sites")
+        dev = f"cuda:{self.device}"
+        site_bits = self.transpose_sites(bit_sets, words_per_sample, num_sites)
+        if priority is None:
+            counts = self.site_counts(bit_sets, words_per_sample).cpu().numpy().view(np.uint32)
+            priority = ld_priority_host(counts, num_sites)
+        if not isinstance(priority, torch.Tensor):
+            priority = torch.from_numpy(np.ascontiguousarray(priority, dtype=np.float32)).to(dev)
+        records, count = self.ld_edges(site_bits, num_sites, rows, window, r2, group=group)
+        del site_bits
+        chosen = self.unrelated_set(records, count, num_sites, priority=priority, families=False)
+        keep = chosen.keep.cpu().numpy() == 1
+        keep_words = site_mask_words(keep)
+        kept = int(keep.sum())
+        bits, wps, sites = bit_sets, words_per_sample, num_sites
+        if compact and kept != num_sites:
+            bits, wps, sites = self.compact_sites(bit_sets, words_per_sample, keep_words, num_sites)
+            torch.cuda.synchronize(self.device)
+        return LDPrune(keep_words, num_sites, bits, wps, sites, records, count, chosen.rounds)
+
     def synth_bitset(self, seed: int, kind, pa, pb, sample_begin: int,
                      sample_end: int, num_sites: int, out=None, stream=None, model=0):
         """Synthetic reference-layout bitset rows [sample_begin, sample_end)
@@ -1017,6 +1226,35 @@ class SiteQC:
             return np.where(n > 0, (n - c[:, 3]) / n, np.nan)
 
 
+class LDPrune:
+    """What ``KingContext.ld_prune`` returns.  The pruned cohort: ``bits`` (device int64
+    ``[rows, words_per_sample]``), ``words_per_sample`` and ``num_sites`` -- like ``SiteQC``'s,
+    the input of everything behind.  About the input's sites: ``num_sites_in``, ``keep()``,
+    ``kept_index()``; about the graph: ``num_edges``, ``rounds`` (of the parallel greedy) and
+    ``edges()``."""
+
+    def __init__(self, keep_words: np.ndarray, num_sites_in: int, bits, words_per_sample: int,
+                 num_sites: int, records, num_edges: int, rounds: int):
+        self.keep_words, self.num_sites_in = keep_words, num_sites_in
+        self.bits, self.words_per_sample, self.num_sites = bits, words_per_sample, num_sites
+        self.records, self.num_edges, self.rounds = records, num_edges, rounds
+
+    def keep(self) -> np.ndarray:
+        """bool ``[num_sites_in]``: the sites that stay."""
+        return site_mask_bool(self.keep_words, self.num_sites_in)
+
+    def kept_index(self) -> np.ndarray:
+        """The input sites that stay, ascending: site k of a compacted ``bits`` is input
+        site ``kept_index()[k]``."""
+        return np.flatnonzero(self.keep())
+
+    def edges(self) -> np.ndarray:
+        """The edge records (``sample_i = a``, ``sample_j = b``, ``kin`` = r^2, ``ibs0`` = the
+        jointly called samples) on the host, sorted by (a, b)."""
+        host = self.records[:self.num_edges].cpu().numpy().view(np.uint32).reshape(-1)
+        return sort_results(host.view(KING_RESULT_DTYPE).copy())
+
+
 def _count(value, name: str) -> int:
     if isinstance(value, bool) or int(value) != value or int(value) < 0:
         raise ValueError(f"{name} must be a non-negative integer, not {value!r}")
@@ -1129,6 +1367,7 @@ __all__ = [
     "ResourceExhaustedError", "CukingError", "padded_sites",
     "words_per_sample", "bytes_per_pair", "new_host_bitset", "pack_host", "pack_bed_host",
     "site_mask_host", "site_mask_words", "site_mask_bool", "compact_sites_host", "SiteQC",
+    "ld_site_words", "transpose_sites_host", "ld_edges_host", "ld_priority_host", "LDPrune",
     "sort_results", "device_count", "synth_models", "synth_model_number",
     "DEFAULT_KIN_THRESHOLD",
     "DEFAULT_MAX_RESULTS",

@@ -28,7 +28,7 @@ LIB_FLAGS_PATH = PKG / "libcuking_amd.flags"
 
 HIP_SOURCES = ["king_abi.hip", "king_kernels.hip", "king_mfma.hip", "king_filter.hip",
                "king_sort.hip", "king_prune.hip", "king_bed.hip", "king_site_qc.hip",
-               "synth.hip"]
+               "king_ld.hip", "synth.hip"]
 # Host-only half of the ABI: plain C++, also compiled by the sanitizer tests.
 HOST_ABI_SOURCES = ["king_host.cc"]
 # IEEE-correct fp32 divide (kinship must match the reference bit for bit):
@@ -66,6 +66,7 @@ def build_library(force: bool = False, save_temps: bool = False) -> Path:
     deps = srcs + [CSRC / "king_common.h", CSRC / "king_device.h", CSRC / "king_host.h",
                    CSRC / "king_launch_plan.h", CSRC / "king_kin_summary.h",
                    CSRC / "king_unrelated.h", CSRC / "king_submatrix.h", CSRC / "king_site_qc.h",
+                   CSRC / "king_ld.h",
                    INCLUDE / "cuking_amd.h",
                    Path(__file__)]
     extra = os.environ.get("CUKING_EXTRA_HIPFLAGS", "").split()
@@ -100,6 +101,8 @@ def build_library(force: bool = False, save_temps: bool = False) -> Path:
     problems += check_no_scratch(cwd / "king_bed-hip-amdgcn-amd-amdhsa-gfx950.s", "pack_bed_kernel")
     for kernel in ("site_counts_kernel", "sample_counts_kernel", "compact_sites_kernel"):
         problems += check_no_scratch(cwd / "king_site_qc-hip-amdgcn-amd-amdhsa-gfx950.s", kernel)
+    for kernel in ("transpose_sites_kernel", "ld_edges_kernel"):
+        problems += check_no_scratch(cwd / "king_ld-hip-amdgcn-amd-amdhsa-gfx950.s", kernel)
     if problems and not extra:
         LIB_PATH.unlink(missing_ok=True)
         raise RuntimeError("the compiler put vector-memory waits or scratch accesses inside an "

@@ -13,6 +13,7 @@
 #include "king_common.h"
 #include "king_host.h"
 #include "king_kin_summary.h"
+#include "king_ld.h"
 #include "king_site_qc.h"
 #include "king_unrelated.h"
 
@@ -123,6 +124,8 @@ struct cuking_ctx {
     // cuking_compact_sites' table (king_site_qc.h), grown when a call needs more
     void *sites = nullptr;
     size_t sites_bytes = 0;
+    // cuking_ld_edges' edge counter (king_ld.hip): one word, allocated on first use
+    unsigned long long *ld_count = nullptr;
   };
   std::vector<StreamScratch> scratch;
   // The running totals of filter scratch that has been freed since (a larger block took
@@ -346,6 +349,7 @@ void evict_scratch(cuking_ctx *ctx, size_t k) {
   if (e.split != nullptr) (void)hipFree(e.split);
   if (e.prune != nullptr) (void)hipFree(e.prune);
   if (e.sites != nullptr) (void)hipFree(e.sites);
+  if (e.ld_count != nullptr) (void)hipFree(e.ld_count);
   ctx->scratch.erase(ctx->scratch.begin() + (ptrdiff_t)k);
 }
 
@@ -1059,6 +1063,7 @@ void cuking_ctx_destroy(cuking_ctx *ctx) {
     if (e.filter) (void)hipFree(e.filter);
     if (e.prune) (void)hipFree(e.prune);
     if (e.sites) (void)hipFree(e.sites);
+    if (e.ld_count) (void)hipFree(e.ld_count);
   }
   for (auto &r : ctx->readers)
     if (r.second) (void)hipEventDestroy(r.second);
@@ -2001,6 +2006,60 @@ cuking_status cuking_compact_sites(cuking_ctx *ctx, const uint64_t *d_in, uint32
   HIP_TRY(launch_compact_sites(d_in, num_stored, words_per_sample_in, e->sites, kept, d_out,
                                words_per_sample_out, s));
   return CUKING_OK;
+}
+
+// ---- LD pruning (king_ld.hip) ----------------------------------------------
+
+cuking_status cuking_transpose_sites(cuking_ctx *ctx, const uint64_t *d_bit_set,
+                                     uint32_t num_stored, uint32_t words_per_sample,
+                                     uint32_t num_sites, uint64_t *d_site_bits,
+                                     uint32_t words_per_site_plane, void *stream) {
+  if (ctx == nullptr) return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "null context");
+  cuking_status st = cuking_check_transpose_args(d_bit_set, num_stored, words_per_sample,
+                                                 num_sites, d_site_bits, words_per_site_plane);
+  if (st != CUKING_OK) return st;
+  if (num_stored == 0 || num_sites == 0) return CUKING_OK;
+  st = bind(ctx);
+  if (st != CUKING_OK) return st;
+  HIP_TRY(launch_transpose_sites(d_bit_set, num_stored, words_per_sample, num_sites, d_site_bits,
+                                 (hipStream_t)stream));
+  return CUKING_OK;
+}
+
+cuking_status cuking_ld_edges(cuking_ctx *ctx, const uint64_t *d_site_bits, uint32_t num_sites,
+                              uint32_t num_stored, uint32_t window, float r2_threshold,
+                              const int32_t *d_group, cuking_result *d_records,
+                              uint64_t max_records, uint64_t *num_records, void *stream) {
+  if (num_records != nullptr) *num_records = 0;
+  if (ctx == nullptr) return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "null context");
+  cuking_status st = cuking_check_ld_args(d_site_bits, num_stored, window, r2_threshold,
+                                          d_records, max_records, num_records);
+  if (st != CUKING_OK) return st;
+  if (num_sites < 2 || num_stored == 0) return CUKING_OK;
+  st = bind(ctx);
+  if (st != CUKING_OK) return st;
+  hipStream_t s = (hipStream_t)stream;
+  cuking_ctx::StreamScratch *e = nullptr;
+  for (auto &x : ctx->scratch)
+    if (x.stream == s) e = &x;
+  if (e == nullptr) {
+    if (ctx->scratch.size() >= kMaxStreams) evict_scratch(ctx, 0);
+    ctx->scratch.push_back({s});
+    e = &ctx->scratch.back();
+  }
+  if (e->ld_count == nullptr) {
+    HIP_TRY(hipMalloc(&e->ld_count, sizeof(unsigned long long)));
+    ++ctx->workspace_allocations;
+  }
+  HIP_TRY(hipMemsetAsync(e->ld_count, 0, sizeof(unsigned long long), s));
+  HIP_TRY(launch_ld_edges(d_site_bits, num_sites, num_stored, window, r2_threshold, d_group,
+                          d_records, max_records, e->ld_count, s));
+  unsigned long long count = 0;
+  HIP_TRY(hipMemcpyAsync(&count, e->ld_count, sizeof(count), hipMemcpyDeviceToHost, s));
+  ++ctx->host_syncs;
+  HIP_TRY(hipStreamSynchronize(s));
+  *num_records = count;
+  return cuking_ld_count_status(count, max_records);
 }
 
 // ---- timing ---------------------------------------------------------------

@@ -641,6 +641,18 @@ hipError_t launch_compact_sites(const uint64_t *d_in, uint32_t num_stored,
                                 uint32_t words_per_sample_out, hipStream_t stream);
 uint32_t site_counts_block_samples();
 
+// LD pruning (king_ld.hip; arguments already checked, king_host.h).  launch_transpose_sites
+// writes every word of d_site_bits [num_sites][2][Q] once; launch_ld_edges ADDS the number of
+// edges to *d_count (zeroed by the caller, on the stream) and stores the records whose slot is
+// below max_records.
+hipError_t launch_transpose_sites(const uint64_t *d_bit_set, uint32_t num_stored,
+                                  uint32_t words_per_sample, uint32_t num_sites,
+                                  uint64_t *d_site_bits, hipStream_t stream);
+hipError_t launch_ld_edges(const uint64_t *d_site_bits, uint32_t num_sites, uint32_t num_stored,
+                           uint32_t window, float r2_threshold, const int32_t *d_group,
+                           cuking_result *d_records, uint64_t max_records,
+                           unsigned long long *d_count, hipStream_t stream);
+
 // Cohort models of the synthetic generator (synth.hip holds the specification).  d_tables:
 // synth_table_bytes() of scratch the launch fills and reads (per-site and per-sample
 // tables); it must stay untouched until the launch has run.

@@ -19,6 +19,7 @@
 #include "../host/schedule.h"
 #include "king_submatrix.h"
 #include "king_kin_summary.h"
+#include "king_ld.h"
 #include "king_unrelated.h"
 
 using namespace cuking;
@@ -499,6 +500,124 @@ cuking_status cuking_compact_sites_host(const uint64_t *bit_set_in, uint32_t num
   }
   return CUKING_OK;
 }
+
+}  // extern "C"
+
+// ---- LD pruning: the argument checks, the host transpose and the host edge list -------------
+cuking_status cuking_check_transpose_args(const void *bit_set, uint32_t num_stored,
+                                          uint32_t words_per_sample, uint32_t num_sites,
+                                          const void *site_bits, uint32_t words_per_site_plane) {
+  if (bit_set == nullptr || site_bits == nullptr)
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "transpose sites: null pointer");
+  if (cuking_words_per_sample(num_sites) != words_per_sample)
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT,
+                       "transpose sites: %u sites need %u words per sample, not %u", num_sites,
+                       cuking_words_per_sample(num_sites), words_per_sample);
+  if (num_stored > kLdMaxStored)
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT,
+                       "transpose sites: at most 2^24 samples are served, not %u", num_stored);
+  if (ld_site_words(num_stored) != words_per_site_plane)
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT,
+                       "transpose sites: %u samples need %u words per site plane, not %u",
+                       num_stored, ld_site_words(num_stored), words_per_site_plane);
+  return CUKING_OK;
+}
+
+cuking_status cuking_check_ld_args(const void *site_bits, uint32_t num_stored, uint32_t window,
+                                   float r2_threshold, const void *records, uint64_t max_records,
+                                   const void *num_records) {
+  if (site_bits == nullptr || num_records == nullptr || (records == nullptr && max_records != 0))
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "ld edges: null pointer");
+  if (num_stored > kLdMaxStored)
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT,
+                       "ld edges: at most 2^24 samples are served, not %u (the sums must stay "
+                       "below 2^53)", num_stored);
+  if (!ld_window_valid(window))
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT,
+                       "ld edges: a window of %u variants holds no pair (at least 2)", window);
+  if (!ld_threshold_valid(r2_threshold))
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "ld edges: r2_threshold (%g) must be in [0, 1]",
+                       (double)r2_threshold);
+  return CUKING_OK;
+}
+
+cuking_status cuking_ld_count_status(uint64_t count, uint64_t max_records) {
+  if (count > kLdMaxEdges)
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT,
+                       "ld edges: %llu edges, more than the 2^30 the unrelated set accepts: a "
+                       "narrower window or a higher threshold", (unsigned long long)count);
+  if (count > max_records)
+    return cuking_fail(CUKING_ERR_RESOURCE_EXHAUSTED,
+                       "ld edges: %llu edges do not fit %llu records: retry with that many",
+                       (unsigned long long)count, (unsigned long long)max_records);
+  return CUKING_OK;
+}
+
+extern "C" {
+
+uint32_t cuking_ld_site_words(uint32_t num_stored) { return ld_site_words(num_stored); }
+
+float cuking_ld_priority(const uint32_t counts[4]) {
+  return counts != nullptr ? ld_priority(counts) : __builtin_nanf("");
+}
+
+cuking_status cuking_transpose_sites_host(const uint64_t *bit_set, uint32_t num_stored,
+                                          uint32_t words_per_sample, uint32_t num_sites,
+                                          uint64_t *site_bits, uint32_t words_per_site_plane) {
+  const cuking_status st = cuking_check_transpose_args(bit_set, num_stored, words_per_sample,
+                                                       num_sites, site_bits, words_per_site_plane);
+  if (st != CUKING_OK) return st;
+  const uint32_t plane_words = words_per_sample / 2, q_words = words_per_site_plane;
+  for (uint64_t site = 0; site < num_sites; ++site) {
+    for (uint32_t plane = 0; plane < 2; ++plane) {
+      uint64_t *row = site_bits + (site * 2 + plane) * q_words;
+      // all missing (the tail stays so), then one sample after the other
+      for (uint32_t q = 0; q < q_words; ++q) row[q] = ~0ull;
+      for (uint64_t s = 0; s < num_stored; ++s) {
+        const uint64_t word = bit_set[s * words_per_sample + plane * plane_words + (site >> 6)];
+        if (!((word >> (site & 63)) & 1)) row[s >> 6] &= ~(1ull << (s & 63));
+      }
+    }
+  }
+  return CUKING_OK;
+}
+
+cuking_status cuking_ld_edges_host(const uint64_t *site_bits, uint32_t num_sites,
+                                   uint32_t num_stored, uint32_t window, float r2_threshold,
+                                   const int32_t *group, cuking_result *records,
+                                   uint64_t max_records, uint64_t *num_records) {
+  if (num_records != nullptr) *num_records = 0;
+  const cuking_status st = cuking_check_ld_args(site_bits, num_stored, window, r2_threshold,
+                                                records, max_records, num_records);
+  if (st != CUKING_OK) return st;
+  const uint32_t q_words = ld_site_words(num_stored);
+  uint64_t count = 0;
+  for (uint64_t a = 0; a < num_sites; ++a) {
+    for (uint64_t b = a + 1; ld_pair_in_band(a, b, num_sites, window); ++b) {
+      if (group != nullptr && group[a] != group[b]) continue;
+      const uint64_t *ra = site_bits + a * 2 * q_words, *rb = site_bits + b * 2 * q_words;
+      LdCounts c;
+      c.clear();
+      for (uint32_t q = 0; q < q_words; ++q) {
+        uint64_t na, ha, va, nb, hb, vb;
+        ld_masks(ra[q], ra[q_words + q], na, ha, va);
+        ld_masks(rb[q], rb[q_words + q], nb, hb, vb);
+        c.add(na, ha, va, nb, hb, vb);
+      }
+      const LdMoments m = ld_moments(c);
+      if (!ld_is_edge(m, r2_threshold)) continue;
+      if (count < max_records)
+        records[count] = cuking_result{(uint32_t)a, (uint32_t)b, ld_r2(m), (uint32_t)m.n, 0, 0};
+      ++count;
+    }
+  }
+  *num_records = count;
+  return cuking_ld_count_status(count, max_records);
+}
+
+}  // extern "C"
+
+extern "C" {
 
 // ---- schedules of a block over the GPUs of a node (host/schedule.h) ----------
 void cuking_schedule_tile_partition(uint64_t num_tiles, uint32_t world, uint64_t *out) {

@@ -25,5 +25,16 @@ cuking_status cuking_check_compact_args(const void *in, uint32_t num_stored,
                                         uint32_t words_per_sample_in, const uint64_t *keep,
                                         uint32_t num_sites_in, const void *out,
                                         uint32_t words_per_sample_out, uint32_t *num_kept);
+// Argument checks of cuking_transpose_sites_host / cuking_transpose_sites and of
+// cuking_ld_edges_host / cuking_ld_edges (include/cuking_amd.h "LD pruning" lists them), and
+// the status of an edge count: INVALID_ARGUMENT above 2^30, RESOURCE_EXHAUSTED above
+// max_records.
+cuking_status cuking_check_transpose_args(const void *bit_set, uint32_t num_stored,
+                                          uint32_t words_per_sample, uint32_t num_sites,
+                                          const void *site_bits, uint32_t words_per_site_plane);
+cuking_status cuking_check_ld_args(const void *site_bits, uint32_t num_stored, uint32_t window,
+                                   float r2_threshold, const void *records, uint64_t max_records,
+                                   const void *num_records);
+cuking_status cuking_ld_count_status(uint64_t count, uint64_t max_records);
 
 #endif  // CUKING_AMD_KING_HOST_H_

@@ -59,6 +59,19 @@ def count_sites(prefix) -> int:
     return n
 
 
+def read_bim_chromosomes(prefix) -> np.ndarray:
+    """One int32 group id per variant of `PREFIX.bim`, in file order: the index of the first
+    appearance of its chromosome string (column 1) -- what `ld_edges` / `ld_prune` take as
+    `group`, so that no LD window reaches across a chromosome boundary."""
+    ids, out = {}, []
+    with open(_path(prefix, ".bim")) as f:
+        for line in f:
+            fields = line.split()
+            if fields:
+                out.append(ids.setdefault(fields[0], len(ids)))
+    return np.asarray(out, dtype=np.int32)
+
+
 class BedFile:
     """An open variant-major `.bed`: `num_samples`, `num_sites`, `row_bytes`, `sample_ids`
     and `read_rows`.  A context manager; `close()` releases the file."""
@@ -141,9 +154,11 @@ def encode_rows(geno: np.ndarray) -> np.ndarray:
             quads[:, :, 3] << 6).astype(np.uint8)
 
 
-def write_plink(prefix, geno: np.ndarray, sample_ids=None, chunk_sites: int = 4096) -> None:
+def write_plink(prefix, geno: np.ndarray, sample_ids=None, chunk_sites: int = 4096,
+                chromosomes=None) -> None:
     """Writes `PREFIX.bed / .bim / .fam` for int8 `[samples, sites]` genotypes (the value is
-    n_alt with A1 counted, negative = missing)."""
+    n_alt with A1 counted, negative = missing).  `chromosomes`: one name per site for the
+    `.bim` (default: all on "1")."""
     geno = np.asarray(geno)
     n, m = geno.shape
     if sample_ids is None:
@@ -155,8 +170,12 @@ def write_plink(prefix, geno: np.ndarray, sample_ids=None, chunk_sites: int = 40
     _path(prefix, ".bed").parent.mkdir(parents=True, exist_ok=True)
     with open(_path(prefix, ".fam"), "w") as f:
         f.writelines(f"{s} {s} 0 0 0 -9\n" for s in sample_ids)
+    if chromosomes is None:
+        chromosomes = ["1"] * m
+    if len(chromosomes) != m or any(len(str(c).split()) != 1 for c in chromosomes):
+        raise ValueError(f"chromosomes must be {m} names of one word each")
     with open(_path(prefix, ".bim"), "w") as f:
-        f.writelines(f"1\tv{k}\t0\t{k + 1}\tA\tC\n" for k in range(m))
+        f.writelines(f"{chromosomes[k]}\tv{k}\t0\t{k + 1}\tA\tC\n" for k in range(m))
     with open(_path(prefix, ".bed"), "wb") as f:
         f.write(MAGIC)
         for lo in range(0, m, chunk_sites):

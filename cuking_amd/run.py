@@ -10,7 +10,8 @@ cuking.cu:550-553) -- or, with `--bed-uri PREFIX`, streams a PLINK `.bed` to its
 GPU and transposes it there (`KingContext.load_bed`) --, optionally drops sites
 by call rate, minor allele frequency / count or a list (`--site-min-call-rate`,
 `--site-min-maf`, `--site-min-mac`, `--site-keep-uri`: counts and compaction on the
-GPU, csrc/king_site_qc.hip), the bitset goes to the other GPUs by the staged RCCL
+GPU, csrc/king_site_qc.hip) and thins the rest by LD (`--site-ld-window`, `--site-ld-r2`:
+csrc/king_ld.hip), the bitset goes to the other GPUs by the staged RCCL
 broadcast of `cuking_amd.dist`, every rank evaluates its band of the pair
 space, rank 0 gathers, sorts and writes `part-<shard>.snappy.parquet` with the
 reference's schema (cuking.cu:767-870).  `--split-factor/--shard-index` select a
@@ -120,6 +121,18 @@ def parse_args(argv=None):
               "(site_counts [sites, 4] = hom-ref, het, hom-var, missing; keep; sample_counts "
               "[samples, 4]; samples; min_call_rate, min_maf, min_mac).  Alone it only reports: "
               "nothing is filtered.  One process and --split-factor 1 only")
+    flag("site-ld-window", type=int, default=None,
+         help="LD pruning after the site QC rule, on the GPU: among the sites within a window "
+              "of this many variants (default 50; pairs up to W - 1 apart, never across the "
+              "chromosomes of a --bed-uri's .bim) no two kept sites have an r^2 above "
+              "--site-ld-r2; of a correlated pair the site with the higher minor allele "
+              "frequency stays.  Any of --site-ld-window, --site-ld-r2 and --site-ld-uri turns "
+              "it on.  One process and --split-factor 1 only")
+    flag("site-ld-r2", type=float, default=None,
+         help="LD pruning: the r^2 threshold (0..1, default 0.2)")
+    flag("site-ld-uri", default="",
+         help="LD pruning: also write its report to this .npz file (keep over the sites that "
+              "entered the pruning, kept_index in input-site numbering, num_edges, window, r2)")
     return ap.parse_args(argv)
 
 
@@ -219,6 +232,31 @@ def validate(args):  # cuking.cu:437-462
                              "--site_keep_uri and --site_qc_uri need --split_factor 1: a site "
                              "passes or fails on the whole cohort's counts")
     site_rule(args)
+    if ld_pruning(args):
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            raise UsageError("--site_ld_window, --site_ld_r2 and --site_ld_uri need one process "
+                             "(one GPU): LD edges are not merged across ranks yet")
+        if args.split_factor != 1:
+            raise UsageError("--site_ld_window, --site_ld_r2 and --site_ld_uri need "
+                             "--split_factor 1: r^2 is taken over the whole cohort's samples")
+    ld_rule(args)
+
+
+def ld_pruning(args) -> bool:
+    """Does the run prune by LD (any of its three flags)?"""
+    return (args.site_ld_window is not None or args.site_ld_r2 is not None or
+            bool(args.site_ld_uri))
+
+
+def ld_rule(args):
+    """--site-ld-window / --site-ld-r2 as the library sees them."""
+    window = 50 if args.site_ld_window is None else args.site_ld_window
+    r2 = 0.2 if args.site_ld_r2 is None else float(np.float32(args.site_ld_r2))
+    if not 2 <= window <= 0xFFFFFFFF:
+        raise UsageError("--site_ld_window must be at least 2 variants")
+    if not 0.0 <= r2 <= 1.0:
+        raise UsageError("--site_ld_r2 must be in [0, 1]")
+    return window, r2
 
 
 def site_filtering(args) -> bool:
@@ -381,7 +419,8 @@ def write_unrelated(path: Path, ctx, recs: np.ndarray, sample_ids, threshold: fl
 def site_qc(ctx, args, bits, wps: int, num_sites: int, sample_ids, keep_path, qc_path):
     """Site QC of the whole cohort's bitset: counts on the GPU, the rule on the host, the
     report if one is asked for, and -- with a flag that selects sites -- the compacted bitset.
-    Returns (bits, words_per_sample, num_sites) for everything behind."""
+    Returns (bits, words_per_sample, num_sites, kept_index) for everything behind: the kept
+    sites' numbers among the input's."""
     import cuking_amd
     rate, maf, mac = site_rule(args)
     also = None
@@ -402,10 +441,29 @@ def site_qc(ctx, args, bits, wps: int, num_sites: int, sample_ids, keep_path, qc
                      min_call_rate=np.float32(rate), min_maf=np.float32(maf),
                      min_mac=np.uint32(mac))
     if not site_filtering(args):
-        return bits, wps, num_sites
+        return bits, wps, num_sites, np.arange(num_sites)
+    index = np.flatnonzero(cuking_amd.site_mask_bool(keep, num_sites))
     bits, wps, kept = ctx.compact_sites(bits, wps, keep, num_sites)
     print(f"[cuking_amd.run] site QC keeps {kept} of {num_sites} sites", flush=True)
-    return bits, wps, kept
+    return bits, wps, kept, index
+
+
+def ld_prune(ctx, args, bits, wps: int, num_sites: int, group, input_index, ld_path):
+    """LD pruning of the bitset site QC left: edges and the kept set on the GPU, the report if
+    one is asked for, the compacted bitset.  `group`: chromosome ids of the sites that enter,
+    or None; `input_index`: their numbers among the input's sites.  Returns (bits,
+    words_per_sample, num_sites) for everything behind."""
+    window, r2 = ld_rule(args)
+    got = ctx.ld_prune(bits, wps, num_sites, window=window, r2=r2, group=group)
+    if ld_path is not None:
+        ld_path.parent.mkdir(parents=True, exist_ok=True)
+        with open(ld_path, "wb") as f:   # (np.savez would append .npz to another suffix)
+            np.savez(f, keep=got.keep(), kept_index=input_index[got.kept_index()],
+                     num_edges=np.int64(got.num_edges), window=np.int64(window),
+                     r2=np.float32(r2))
+    print(f"[cuking_amd.run] LD pruning keeps {got.num_sites} of {num_sites} sites "
+          f"({got.num_edges} edges)", flush=True)
+    return got.bits, got.words_per_sample, got.num_sites
 
 
 def main(argv=None) -> int:
@@ -430,6 +488,7 @@ def main(argv=None) -> int:
         priority_path = resolve_uri(args.unrelated_priority) if args.unrelated_priority else None
         site_keep_path = resolve_uri(args.site_keep_uri) if args.site_keep_uri else None
         site_qc_path = resolve_uri(args.site_qc_uri) if args.site_qc_uri else None
+        site_ld_path = resolve_uri(args.site_ld_uri) if args.site_ld_uri else None
         synthetic = None
         if args.synthetic:
             parts = [int(x) for x in args.synthetic.split(",")]
@@ -512,8 +571,18 @@ def main(argv=None) -> int:
             raise RuntimeError(str(pack_error))
         if site_filtering(args) or site_qc_path is not None:
             # (one process, the whole cohort: validate) -- what follows sees the kept sites only
-            bits, wps, num_sites = site_qc(ctx, args, bits[:stored], wps, num_sites, sample_ids,
-                                           site_keep_path, site_qc_path)
+            bits, wps, num_sites, site_index = site_qc(ctx, args, bits[:stored], wps, num_sites,
+                                                       sample_ids, site_keep_path, site_qc_path)
+        else:
+            site_index = np.arange(num_sites)
+        if ld_pruning(args):
+            # after the rule, on the bitset it left; chromosomes only a .bim names
+            group = None
+            if bed_prefix is not None:
+                from cuking_amd import plink
+                group = plink.read_bim_chromosomes(bed_prefix)[site_index]
+            bits, wps, num_sites = ld_prune(ctx, args, bits[:stored], wps, num_sites, group,
+                                            site_index, site_ld_path)
         t1 = time.perf_counter()
         after_reserve = lambda: (0, 0)    # noqa: E731 - (allocations, host waits) since the reservation
         if sm.i_begin == sm.j_begin:

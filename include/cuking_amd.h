@@ -745,7 +745,7 @@ cuking_status cuking_unrelated_set(cuking_ctx *ctx, const cuking_result *d_recor
  * word from keep and uploads it into the context's per-stream cache, ordered on `stream`; it
  * waits for that upload (and so for what `stream` held before), the kernel itself is
  * asynchronous.  One caller per context at a time, like the compute entry points.
- * Out of scope: the C++ `cuking` binary; several ranks; LD pruning and HWE themselves; sample
+ * Out of scope: the C++ `cuking` binary; several ranks; HWE itself (LD pruning: below); sample
  * filtering and reordering; in-place compaction; filtering inside the .bed loader before the
  * transpose; rewriting a .bim. */
 typedef struct cuking_site_filter {
@@ -770,6 +770,80 @@ cuking_status cuking_compact_sites(cuking_ctx *ctx, const uint64_t *d_in, uint32
                                    uint32_t words_per_sample_in, const uint64_t *keep,
                                    uint32_t num_sites_in, uint64_t *d_out,
                                    uint32_t words_per_sample_out, void *stream);
+
+/* LD pruning: which sites to keep so that no two kept sites within a window of variants are
+ * correlated above a threshold -- the thinning every protocol runs between site QC and KING, on
+ * the bitset where it lies.  Two calls produce the EDGES (pairs of sites with r^2 above the
+ * threshold); cuking_unrelated_set, with sites as its "samples" and the minor allele frequency
+ * as the priority, picks the kept set; cuking_compact_sites applies it.  csrc/king_ld.h holds
+ * every definition below as code shared by host, device and tests.
+ *
+ * Site-major bitset: Q = ceil(num_stored / 64); uint64 site_bits[num_sites][2][Q], plane 0 =
+ * het, plane 1 = hom_var, sample s = bit s % 64 of word s / 64, missing = both bits, bits of
+ * samples >= num_stored in the last word SET in both planes (the tail reads as missing).  Only
+ * the num_sites real sites have rows; the padding sites of the input are not transposed.
+ * cuking_transpose_sites_host / cuking_transpose_sites: the bit transpose of the sample-major
+ * bitset [num_stored][words_per_sample] into that form.  Every output word is written once with
+ * a plain store: no memset is needed.  INVALID_ARGUMENT: a null pointer; words_per_sample !=
+ * cuking_words_per_sample(num_sites); words_per_site_plane != Q; num_stored > 2^24.  num_sites
+ * == 0 or num_stored == 0 returns OK without work (after the checks).  Asynchronous on `stream`.
+ *
+ * Per-pair sums, for sites a < b, with N = ~(het & hom) (called), H = het & ~hom, V = hom &
+ * ~het per site, the dosage g = H + 2 V and pc the popcount over all Q words:
+ *     n = pc(Na & Nb)
+ *     Sx = pc(Ha & Nb) + 2 pc(Va & Nb),  Sxx = pc(Ha & Nb) + 4 pc(Va & Nb); Sy, Syy likewise
+ *     Sxy = pc(Ha & Hb) + 2 pc(Ha & Vb) + 2 pc(Va & Hb) + 4 pc(Va & Vb)
+ *     cov = n Sxy - Sx Sy,  vx = n Sxx - Sx^2,  vy = n Syy - Sy^2     (int64)
+ * num_stored <= 2^24 makes each an integer below 2^53: it converts to double exactly.
+ * Edge rule: (a, b) is an edge iff ALL of
+ *     a < b < num_sites
+ *     b - a < window                       (a window of W variants: pairs up to W - 1 apart)
+ *     group[a] == group[b]                 (when group is not NULL: chromosomes)
+ *     vx > 0 and vy > 0
+ *     (double)cov * (double)cov > ((double)r2_threshold * (double)vx) * (double)vy
+ * -- three IEEE double products, each rounded once, no addition, nothing fused: host and device
+ * agree bit for bit.  A monomorphic or all-missing site has no edges; r2_threshold = 1 yields no
+ * edge at all (for perfectly correlated sites both sides round the same integer).
+ * Edge record: cuking_result {sample_i = a, sample_j = b, kin = (float)((double)cov *
+ * (double)cov / ((double)vx * (double)vy)), ibs0 = n, ibs1 = ibs2 = 0}.  Record order is
+ * unspecified; the set is the contract.
+ *
+ * cuking_ld_edges_host / cuking_ld_edges: EVERY edge is counted, those whose slot is below
+ * max_records are stored; *num_records (HOST memory) receives the exact count.  A count above
+ * 2^30 (what cuking_unrelated_set accepts) returns INVALID_ARGUMENT; otherwise a count above
+ * max_records returns CUKING_ERR_RESOURCE_EXHAUSTED -- nothing is written past the buffer, the
+ * caller retries once with exactly *num_records.  cuking_ld_edges WAITS for `stream` (it reads
+ * the count back).  INVALID_ARGUMENT before any work: a null site_bits / num_records pointer, a
+ * null records pointer with max_records != 0; num_stored > 2^24; window < 2; r2_threshold NaN
+ * or outside [0, 1].  num_sites < 2 or num_stored == 0 gives 0 edges.
+ *
+ * Default priority of a site from its cuking_site_counts row, with called, alt and minor as in
+ * cuking_site_mask_host: cuking_ld_priority = (float)((double)minor / (double)(2 called)), NaN
+ * when called == 0 (ranked last by cuking_unrelated_key); among equals the lower site wins.
+ * Kept set: cuking_unrelated_set(edges, prune_threshold = -inf, priority).  No two kept sites
+ * of one group within the window have r^2 above the threshold, and every dropped site has a
+ * kept neighbour.  It keeps the higher-MAF site of a correlated pair, as PLINK does, but it is
+ * deliberately NOT PLINK's sliding, order-dependent removal: it has one well-defined answer.
+ * Out of scope: the C++ `cuking` binary and several ranks; windows in base pairs; PLINK's
+ * step-wise removal order; reading the site-major form straight from a .bed; a VIF-based
+ * --indep; phased or haplotype r^2; HWE; rewriting a .bim. */
+uint32_t cuking_ld_site_words(uint32_t num_stored); /* Q */
+float cuking_ld_priority(const uint32_t counts[4]);
+cuking_status cuking_transpose_sites_host(const uint64_t *bit_set, uint32_t num_stored,
+                                          uint32_t words_per_sample, uint32_t num_sites,
+                                          uint64_t *site_bits, uint32_t words_per_site_plane);
+cuking_status cuking_transpose_sites(cuking_ctx *ctx, const uint64_t *d_bit_set,
+                                     uint32_t num_stored, uint32_t words_per_sample,
+                                     uint32_t num_sites, uint64_t *d_site_bits,
+                                     uint32_t words_per_site_plane, void *stream);
+cuking_status cuking_ld_edges_host(const uint64_t *site_bits, uint32_t num_sites,
+                                   uint32_t num_stored, uint32_t window, float r2_threshold,
+                                   const int32_t *group, cuking_result *records,
+                                   uint64_t max_records, uint64_t *num_records);
+cuking_status cuking_ld_edges(cuking_ctx *ctx, const uint64_t *d_site_bits, uint32_t num_sites,
+                              uint32_t num_stored, uint32_t window, float r2_threshold,
+                              const int32_t *d_group, cuking_result *d_records,
+                              uint64_t max_records, uint64_t *num_records, void *stream);
 
 /* cuking.cu:761-765 on host memory: sort by (sample_i, sample_j, kin). */
 void cuking_sort_results(cuking_result *results, size_t num_results);
