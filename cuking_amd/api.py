@@ -345,6 +345,37 @@ def _stream_handle(stream=None) -> int:
     return int(s.cuda_stream)
 
 
+def _device_tensor(device: int, t, name: str, dtype, shape=None, min_numel=None, cols=None,
+                   contiguous: bool = True):
+    """``t`` if it is a torch tensor of ``dtype`` on GPU ``device``, contiguous (unless told
+    otherwise), of ``shape`` / at least ``min_numel`` elements / ``[*, cols]`` where given;
+    ValueError otherwise."""
+    import torch
+    if not isinstance(t, torch.Tensor):
+        raise ValueError(f"{name} must be a device tensor, not {type(t).__name__}")
+    if not t.is_cuda or t.device.index != device:
+        raise ValueError(f"{name} must live on this context's GPU")
+    if t.dtype != dtype or contiguous and not t.is_contiguous():
+        raise ValueError(f"{name} must be a {'contiguous ' if contiguous else ''}"
+                         f"{str(dtype).replace('torch.', '')} tensor")
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{name} must have shape {tuple(shape)}, not {tuple(t.shape)}")
+    if cols is not None and (t.dim() != 2 or t.shape[1] != cols):
+        raise ValueError(f"{name} must be a [*, {cols}] tensor, not {tuple(t.shape)}")
+    if min_numel is not None and t.numel() < min_numel:
+        raise ValueError(f"{name} holds {t.numel()} elements, {min_numel} are needed")
+    return t
+
+
+def _whole_or_tiles(fn, fn_tiles, head, tile_range, tail) -> None:
+    """The entry point of the whole block, or its ``_tiles`` twin with the tile range between
+    the arguments the two share."""
+    if tile_range is None:
+        check(fn(*head, *tail))
+    else:
+        check(fn_tiles(*head, tile_range[0], tile_range[1], *tail))
+
+
 class KingContext:
     """One per GPU (cuking_ctx).  Device buffers are torch tensors on that GPU;
     bitsets are int64 tensors holding the reference's uint64 words."""
@@ -411,16 +442,10 @@ class KingContext:
         not reset here).  Asynchronous on the stream."""
         self._check_bits(submatrix, words_per_sample, bit_sets)
         assert results.numel() * results.element_size() >= max_results * 24
-        args = (self.handle, C.byref(submatrix.c), words_per_sample,
-                bit_sets.data_ptr())
-        tail = (kin_threshold, max_results, results.data_ptr(),
-                result_index.data_ptr(), result_overflow.data_ptr(),
-                _stream_handle(stream))
-        if tile_range is None:
-            check(self.lib.cuking_compute_king(*args, *tail))
-        else:
-            check(self.lib.cuking_compute_king_tiles(
-                *args, tile_range[0], tile_range[1], *tail))
+        _whole_or_tiles(self.lib.cuking_compute_king, self.lib.cuking_compute_king_tiles,
+                        self._block(submatrix, words_per_sample, bit_sets), tile_range,
+                        (kin_threshold, max_results, results.data_ptr(), result_index.data_ptr(),
+                         result_overflow.data_ptr(), _stream_handle(stream)))
 
     def prepare_samples(self, submatrix: Submatrix, words_per_sample: int,
                         bit_sets, sample_begin: int, sample_end: int,
@@ -429,8 +454,7 @@ class KingContext:
         [sample_begin, sample_end) into the kernel layout."""
         self._check_bits(submatrix, words_per_sample, bit_sets)
         check(self.lib.cuking_prepare_samples(
-            self.handle, C.byref(submatrix.c), words_per_sample,
-            bit_sets.data_ptr(), sample_begin, sample_end,
+            *self._block(submatrix, words_per_sample, bit_sets), sample_begin, sample_end,
             _stream_handle(stream)))
 
     def compute_king_rect(self, submatrix: Submatrix, words_per_sample: int,
@@ -445,11 +469,9 @@ class KingContext:
         assert results.numel() * results.element_size() >= max_results * 24
         step = rows[2] if len(rows) > 2 else 0
         check(self.lib.cuking_compute_king_rect(
-            self.handle, C.byref(submatrix.c), words_per_sample,
-            bit_sets.data_ptr(), rows[0], rows[1], step, cols[0], cols[1],
-            kin_threshold, max_results, results.data_ptr(),
-            result_index.data_ptr(), result_overflow.data_ptr(),
-            _stream_handle(stream)))
+            *self._block(submatrix, words_per_sample, bit_sets), rows[0], rows[1], step, cols[0],
+            cols[1], kin_threshold, max_results, results.data_ptr(), result_index.data_ptr(),
+            result_overflow.data_ptr(), _stream_handle(stream)))
 
     def reserve(self, submatrix: Submatrix, words_per_sample: int, streams=()) -> None:
         """Sizes the workspace for the block (and the split slabs of the
@@ -475,8 +497,8 @@ class KingContext:
         out = torch.zeros((r, c, 6), dtype=torch.int32,
                           device=f"cuda:{self.device}")
         check(self.lib.cuking_compute_counts(
-            self.handle, C.byref(submatrix.c), words_per_sample,
-            bit_sets.data_ptr(), out.data_ptr(), _stream_handle(stream)))
+            *self._block(submatrix, words_per_sample, bit_sets), out.data_ptr(),
+            _stream_handle(stream)))
         torch.cuda.synchronize(self.device)
         return out.cpu().numpy().view(np.uint32).reshape(r, c, 6).view(
             KING_COUNTS_DTYPE).reshape(r, c)
@@ -501,12 +523,7 @@ class KingContext:
             out = torch.full((r, c), float("nan"), dtype=torch.float32,
                              device=f"cuda:{self.device}")
         else:
-            if not out.is_cuda or out.device.index != self.device:
-                raise ValueError("out must live on this context's GPU")
-            if out.dtype != torch.float32:
-                raise ValueError("out must be a float32 tensor")
-            if out.dim() != 2 or tuple(out.shape) != (r, c):
-                raise ValueError(f"out has shape {tuple(out.shape)}, the block needs ({r}, {c})")
+            _device_tensor(self.device, out, "out", torch.float32, shape=(r, c), contiguous=False)
             if r > 1 and c > 0 and out.stride(0) < c or c > 1 and out.stride(1) != 1:
                 raise ValueError("out must have unit column stride and a row stride of at "
                                  "least NumCols")
@@ -518,13 +535,10 @@ class KingContext:
             return out
         ld = out.stride(0) if r > 1 else max(out.stride(0), c)
         flags = _lib.KIN_SYMMETRIC if symmetric else _lib.KIN_UPPER
-        args = (self.handle, C.byref(submatrix.c), words_per_sample, bit_sets.data_ptr())
-        tail = (out.data_ptr(), ld, flags, _stream_handle(stream))
-        if tile_range is None:
-            check(self.lib.cuking_compute_kin_matrix(*args, *tail))
-        else:
-            check(self.lib.cuking_compute_kin_matrix_tiles(
-                *args, tile_range[0], tile_range[1], *tail))
+        _whole_or_tiles(self.lib.cuking_compute_kin_matrix,
+                        self.lib.cuking_compute_kin_matrix_tiles,
+                        self._block(submatrix, words_per_sample, bit_sets), tile_range,
+                        (out.data_ptr(), ld, flags, _stream_handle(stream)))
         return out
 
     def kin_summary(self, submatrix: Submatrix, words_per_sample: int, bit_sets,
@@ -546,32 +560,21 @@ class KingContext:
         lo, hi = float(np.float32(lo)), float(np.float32(hi))
         if not (np.isfinite(lo) and np.isfinite(hi) and lo < hi):
             raise ValueError("the histogram needs finite bounds with lo < hi")
-        dev = f"cuda:{self.device}"
 
         def output(t, name, length):
             if t is None:
-                return torch.zeros(length, dtype=torch.int64, device=dev)
-            if not t.is_cuda or t.device.index != self.device:
-                raise ValueError(f"{name} must live on this context's GPU")
-            if t.dtype != torch.int64:
-                raise ValueError(f"{name} must be an int64 tensor (a view of the uint64 data)")
-            if t.dim() != 1 or t.numel() != length or not t.is_contiguous():
-                raise ValueError(f"{name} must be a contiguous vector of {length} entries, "
-                                 f"not {tuple(t.shape)}")
-            return t
+                return torch.zeros(length, dtype=torch.int64, device=f"cuda:{self.device}")
+            return _device_tensor(self.device, t, name, torch.int64, shape=(length,))
         hist = output(hist, "hist", int(bins) + 3)
         best = output(best, "best", submatrix.NumSamples())
         summary = KinSummary(hist, best, lo, hi, int(bins), submatrix, self.device)
         if submatrix.NumRows() == 0 or submatrix.NumCols() == 0:
             return summary
         cbins = _lib.CKinBins(lo, hi, int(bins))
-        args = (self.handle, C.byref(submatrix.c), words_per_sample, bit_sets.data_ptr())
-        tail = (C.byref(cbins), hist.data_ptr(), best.data_ptr(), _stream_handle(stream))
-        if tile_range is None:
-            check(self.lib.cuking_compute_kin_summary(*args, *tail))
-        else:
-            check(self.lib.cuking_compute_kin_summary_tiles(
-                *args, tile_range[0], tile_range[1], *tail))
+        _whole_or_tiles(self.lib.cuking_compute_kin_summary,
+                        self.lib.cuking_compute_kin_summary_tiles,
+                        self._block(submatrix, words_per_sample, bit_sets), tile_range,
+                        (C.byref(cbins), hist.data_ptr(), best.data_ptr(), _stream_handle(stream)))
         return summary
 
     def relative_counts(self, submatrix: Submatrix, words_per_sample: int, bit_sets,
@@ -587,35 +590,21 @@ class KingContext:
         library's uint32 data) the call ACCUMULATES into, e.g. for the tile ranges of
         one block; without it a zeroed one is allocated.  ``tile_range``: only the tiles
         [begin, end) of the block's enumeration."""
-        import torch
         self._check_bits(submatrix, words_per_sample, bit_sets)
         thr = np.asarray(thresholds, dtype=np.float32).reshape(-1)
         if not 1 <= thr.size <= _lib.REL_THRESHOLDS_MAX:
             raise ValueError(f"between 1 and {_lib.REL_THRESHOLDS_MAX} thresholds are needed")
         if not np.isfinite(thr).all() or not (np.diff(thr) > 0).all():
             raise ValueError("thresholds must be finite and strictly ascending (as float32)")
-        shape = (submatrix.NumSamples(), int(thr.size))
-        if out is None:
-            out = torch.zeros(shape, dtype=torch.int32, device=f"cuda:{self.device}")
-        else:
-            if not out.is_cuda or out.device.index != self.device:
-                raise ValueError("out must live on this context's GPU")
-            if out.dtype != torch.int32:
-                raise ValueError("out must be an int32 tensor (a view of the uint32 data)")
-            if tuple(out.shape) != shape or not out.is_contiguous():
-                raise ValueError(f"out must be a contiguous tensor of shape {shape}, "
-                                 f"not {tuple(out.shape)}")
+        out = self._counts_out(out, (submatrix.NumSamples(), int(thr.size)), zero=True)
         counts = RelativeCounts(out, thr, submatrix, self.device)
         if submatrix.NumRows() == 0 or submatrix.NumCols() == 0:
             return counts
         cthr = (C.c_float * thr.size)(*[float(t) for t in thr])
-        args = (self.handle, C.byref(submatrix.c), words_per_sample, bit_sets.data_ptr())
-        tail = (cthr, int(thr.size), out.data_ptr(), _stream_handle(stream))
-        if tile_range is None:
-            check(self.lib.cuking_compute_relative_counts(*args, *tail))
-        else:
-            check(self.lib.cuking_compute_relative_counts_tiles(
-                *args, tile_range[0], tile_range[1], *tail))
+        _whole_or_tiles(self.lib.cuking_compute_relative_counts,
+                        self.lib.cuking_compute_relative_counts_tiles,
+                        self._block(submatrix, words_per_sample, bit_sets), tile_range,
+                        (cthr, int(thr.size), out.data_ptr(), _stream_handle(stream)))
         return counts
 
     def count_records(self, submatrix: Submatrix, words_per_sample: int, bit_sets,
@@ -646,27 +635,13 @@ class KingContext:
         thr = float(np.float32(prune_threshold))
         if thr != thr:
             raise ValueError("prune_threshold must not be NaN")
-        if not isinstance(records, torch.Tensor):
-            raise ValueError("records must be a device tensor (unrelated_set_host takes numpy)")
-        if not records.is_cuda or records.device.index != self.device:
-            raise ValueError("records must live on this context's GPU")
-        if records.dtype != torch.int32:
-            raise ValueError("records must be an int32 tensor (KingResult records)")
-        if records.dim() != 2 or records.shape[1] != 6 or not records.is_contiguous():
-            raise ValueError(f"records must be a contiguous [*, 6] tensor, not "
-                             f"{tuple(records.shape)}")
+        # (KingResult records; unrelated_set_host takes numpy)
+        _device_tensor(self.device, records, "records", torch.int32, cols=6)
         if records.shape[0] < num_records:
             raise ValueError(f"records holds {records.shape[0]} records, num_records is "
                              f"{num_records}")
         if priority is not None:
-            if not isinstance(priority, torch.Tensor) or not priority.is_cuda or \
-                    priority.device.index != self.device:
-                raise ValueError("priority must live on this context's GPU")
-            if priority.dtype != torch.float32:
-                raise ValueError("priority must be a float32 tensor")
-            if tuple(priority.shape) != (num_samples,) or not priority.is_contiguous():
-                raise ValueError(f"priority must be a contiguous vector of {num_samples} "
-                                 f"entries, not {tuple(priority.shape)}")
+            _device_tensor(self.device, priority, "priority", torch.float32, shape=(num_samples,))
         dev = f"cuda:{self.device}"
         keep = torch.empty(num_samples, dtype=torch.uint8, device=dev)
         family = torch.empty(num_samples, dtype=torch.int32, device=dev) if families else None
@@ -684,27 +659,38 @@ class KingContext:
         """From bitsets to "these samples stay" for a whole-cohort diagonal block:
         ``count_records`` for the exact buffer size, ``compute_king`` at ``kin_threshold``,
         then ``unrelated_set`` on the records where they lie.  Waits for the device."""
-        import torch
         if not (submatrix.i_begin == submatrix.j_begin == 0 and
                 submatrix.i_end == submatrix.j_end):
             raise ValueError(
                 f"prune needs the whole-cohort diagonal block, not {submatrix!r}: for several "
                 "shards concatenate their record buffers and call unrelated_set(records, "
                 "num_records, num_samples)")
-        dev = f"cuda:{self.device}"
         count = self.count_records(submatrix, words_per_sample, bit_sets, kin_threshold)
-        results = torch.zeros((max(count, 1), 6), dtype=torch.int32, device=dev)
-        index_and_flag = torch.zeros(2, dtype=torch.int32, device=dev)
-        if submatrix.NumSamples() > 1:
-            self.compute_king(submatrix, words_per_sample, bit_sets, kin_threshold, count,
-                              results, index_and_flag[0:1], index_and_flag[1:2])
-        torch.cuda.synchronize(self.device)
-        written, overflow = (int(x) & 0xFFFFFFFF for x in index_and_flag.tolist())
+        results, written, overflow = self._collect_records(
+            submatrix, words_per_sample, bit_sets, kin_threshold, count,
+            launch=submatrix.NumSamples() > 1)
         if overflow or written != count:
             raise RuntimeError(f"the record call wrote {written} records (overflow {overflow}), "
                                f"the count call announced {count}")
         return self.unrelated_set(results, count, submatrix.i_end, kin_threshold,
                                   priority=priority, families=families)
+
+    def _collect_records(self, submatrix: Submatrix, words_per_sample: int, bit_sets,
+                         kin_threshold: float, max_results: int, tile_range=None,
+                         launch: bool = True):
+        """Zeroed record buffer and index / overflow words, ``compute_king`` into them (unless
+        ``launch`` is off), the wait for the device: ``(results, written, overflow)``."""
+        import torch
+        dev = f"cuda:{self.device}"
+        results = torch.zeros((max(max_results, 1), 6), dtype=torch.int32, device=dev)
+        index_and_flag = torch.zeros(2, dtype=torch.int32, device=dev)
+        if launch:
+            self.compute_king(submatrix, words_per_sample, bit_sets, kin_threshold, max_results,
+                              results, index_and_flag[0:1], index_and_flag[1:2],
+                              tile_range=tile_range)
+        torch.cuda.synchronize(self.device)
+        written, overflow = (int(x) & 0xFFFFFFFF for x in index_and_flag.tolist())
+        return results, written, overflow
 
     def run(self, submatrix: Submatrix, words_per_sample: int, bit_sets,
             kin_threshold: float = DEFAULT_KIN_THRESHOLD,
@@ -712,16 +698,8 @@ class KingContext:
             sort: bool = True) -> np.ndarray:
         """cuking.cu:713-765: allocate + zero the result buffer, launch, wait,
         raise on overflow, return the (sorted) host records."""
-        import torch
-        dev = f"cuda:{self.device}"
-        results = torch.zeros((max(max_results, 1), 6), dtype=torch.int32,
-                              device=dev)
-        index_and_flag = torch.zeros(2, dtype=torch.int32, device=dev)
-        self.compute_king(submatrix, words_per_sample, bit_sets, kin_threshold,
-                          max_results, results, index_and_flag[0:1],
-                          index_and_flag[1:2], tile_range=tile_range)
-        torch.cuda.synchronize(self.device)
-        count, overflow = (int(x) & 0xFFFFFFFF for x in index_and_flag.tolist())
+        results, count, overflow = self._collect_records(
+            submatrix, words_per_sample, bit_sets, kin_threshold, max_results, tile_range)
         if overflow:
             raise ResourceExhaustedError(
                 "Could not store all results: try increasing the "
@@ -755,10 +733,7 @@ class KingContext:
         Asynchronous on the stream."""
         import torch
         self._check_bits(submatrix, words_per_sample, out)
-        if not bed_rows.is_cuda or bed_rows.device.index != self.device:
-            raise ValueError("bed_rows must live on this context's GPU")
-        if bed_rows.dtype != torch.uint8 or not bed_rows.is_contiguous():
-            raise ValueError("bed_rows must be a contiguous uint8 tensor")
+        _device_tensor(self.device, bed_rows, "bed_rows", torch.uint8)
         if site_begin <= site_end and bed_rows.numel() < (site_end - site_begin) * row_bytes:
             raise ValueError(f"bed_rows holds {bed_rows.numel()} bytes, sites [{site_begin}, "
                              f"{site_end}) need {(site_end - site_begin) * row_bytes}")
@@ -821,11 +796,7 @@ class KingContext:
     # -- site QC --------------------------------------------------------------
     def _rows_of(self, bit_sets, words_per_sample: int) -> int:
         import torch
-        if not isinstance(bit_sets, torch.Tensor) or not bit_sets.is_cuda or \
-                bit_sets.device.index != self.device:
-            raise ValueError("bit_sets must live on this context's GPU")
-        if bit_sets.dtype != torch.int64 or not bit_sets.is_contiguous():
-            raise ValueError("bit_sets must be a contiguous int64 tensor")
+        _device_tensor(self.device, bit_sets, "bit_sets", torch.int64)
         if words_per_sample <= 0 or words_per_sample % 2 or bit_sets.numel() % words_per_sample:
             raise ValueError(f"bit_sets holds {bit_sets.numel()} words: not rows of "
                              f"{words_per_sample} (a positive even number)")
@@ -836,14 +807,7 @@ class KingContext:
         if out is None:
             make = torch.zeros if zero else torch.empty
             return make(shape, dtype=torch.int32, device=f"cuda:{self.device}")
-        if not out.is_cuda or out.device.index != self.device:
-            raise ValueError("out must live on this context's GPU")
-        if out.dtype != torch.int32:
-            raise ValueError("out must be an int32 tensor (a view of the uint32 data)")
-        if tuple(out.shape) != shape or not out.is_contiguous():
-            raise ValueError(f"out must be a contiguous tensor of shape {shape}, "
-                             f"not {tuple(out.shape)}")
-        return out
+        return _device_tensor(self.device, out, "out", torch.int32, shape=shape)
 
     def site_counts(self, bit_sets, words_per_sample: int, out=None, stream=None):
         """Genotype counts per site (cuking_site_counts): for every plane site ``0 .. 64 P -
@@ -931,10 +895,8 @@ class KingContext:
         q = self.lib.cuking_ld_site_words(rows)
         if out is None:
             out = torch.empty((num_sites, 2, q), dtype=torch.int64, device=f"cuda:{self.device}")
-        elif out.dtype != torch.int64 or not out.is_contiguous() or not out.is_cuda or \
-                out.device.index != self.device or out.numel() < num_sites * 2 * q:
-            raise ValueError(f"out must be a contiguous int64 tensor of {num_sites * 2 * q} words "
-                             "on this context's GPU")
+        else:
+            _device_tensor(self.device, out, "out", torch.int64, min_numel=num_sites * 2 * q)
         check(self.lib.cuking_transpose_sites(
             self.handle, bit_sets.data_ptr(), rows, words_per_sample, num_sites, out.data_ptr(),
             q, _stream_handle(stream)))
@@ -957,24 +919,16 @@ class KingContext:
         window, r2 = _ld_arguments(window, r2)
         dev = f"cuda:{self.device}"
         need = num_sites * 2 * self.lib.cuking_ld_site_words(num_stored)
-        if not isinstance(site_bits, torch.Tensor) or not site_bits.is_cuda or \
-                site_bits.device.index != self.device or site_bits.dtype != torch.int64 or \
-                not site_bits.is_contiguous() or site_bits.numel() != need:
-            raise ValueError(f"site_bits must be a contiguous int64 tensor of {need} words on "
-                             "this context's GPU (transpose_sites)")
+        _device_tensor(self.device, site_bits, "site_bits", torch.int64, min_numel=need)
+        if site_bits.numel() != need:
+            raise ValueError(f"site_bits holds {site_bits.numel()} words, {num_sites} sites of "
+                             f"{num_stored} samples take {need} (transpose_sites)")
         if group is not None:
             if not isinstance(group, torch.Tensor):
                 group = torch.from_numpy(np.ascontiguousarray(group, dtype=np.int32)).to(dev)
-            if not group.is_cuda or group.device.index != self.device or \
-                    group.dtype != torch.int32 or tuple(group.shape) != (num_sites,) or \
-                    not group.is_contiguous():
-                raise ValueError(f"group must be a contiguous int32 vector of {num_sites} "
-                                 "entries on this context's GPU")
+            _device_tensor(self.device, group, "group", torch.int32, shape=(num_sites,))
         if out is not None:
-            if out.dtype != torch.int32 or out.dim() != 2 or out.shape[1] != 6 or \
-                    not out.is_contiguous() or not out.is_cuda or out.device.index != self.device:
-                raise ValueError("out must be a contiguous [*, 6] int32 tensor on this "
-                                 "context's GPU")
+            _device_tensor(self.device, out, "out", torch.int32, cols=6)
             max_records = out.shape[0] if max_records is None else max_records
             if _count(max_records, "max_records") > out.shape[0]:
                 raise ValueError(f"out holds {out.shape[0]} records, max_records is {max_records}")
@@ -1087,14 +1041,12 @@ class KingContext:
     # -- helpers --------------------------------------------------------------
     def _check_bits(self, sm: Submatrix, wps: int, bit_sets) -> None:
         import torch
-        if not bit_sets.is_cuda or bit_sets.device.index != self.device:
-            raise ValueError("bit_sets must live on this context's GPU")
-        if bit_sets.dtype != torch.int64 or not bit_sets.is_contiguous():
-            raise ValueError("bit_sets must be a contiguous int64 tensor")
-        if bit_sets.numel() < sm.NumSamples() * wps:
-            raise ValueError(
-                f"bit_sets holds {bit_sets.numel()} words, the block needs "
-                f"{sm.NumSamples()} x {wps}")
+        _device_tensor(self.device, bit_sets, "bit_sets", torch.int64,
+                       min_numel=sm.NumSamples() * wps)
+
+    def _block(self, sm: Submatrix, wps: int, bit_sets) -> tuple:
+        """The arguments every call on a block starts with."""
+        return (self.handle, C.byref(sm.c), wps, bit_sets.data_ptr())
 
 
 class KinSummary:

@@ -63,12 +63,7 @@ def _newer(target: Path, deps) -> bool:
 
 def build_library(force: bool = False, save_temps: bool = False) -> Path:
     srcs = [CSRC / s for s in HIP_SOURCES + HOST_ABI_SOURCES]
-    deps = srcs + [CSRC / "king_common.h", CSRC / "king_device.h", CSRC / "king_host.h",
-                   CSRC / "king_launch_plan.h", CSRC / "king_kin_summary.h",
-                   CSRC / "king_unrelated.h", CSRC / "king_submatrix.h", CSRC / "king_site_qc.h",
-                   CSRC / "king_ld.h",
-                   INCLUDE / "cuking_amd.h",
-                   Path(__file__)]
+    deps = srcs + sorted(CSRC.glob("*.h")) + [INCLUDE / "cuking_amd.h", Path(__file__)]
     extra = os.environ.get("CUKING_EXTRA_HIPFLAGS", "").split()
     wanted = " ".join(extra)
     # (no stamp = a library from before stamps existed, or a box the stamp did not

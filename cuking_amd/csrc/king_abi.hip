@@ -32,6 +32,13 @@ namespace {
     }                                                                      \
   } while (0)
 
+// Makes the context's device current, or returns bind()'s refusal.
+#define BIND_OR_RETURN(ctx)                    \
+  do {                                         \
+    const cuking_status _st = bind(ctx);       \
+    if (_st != CUKING_OK) return _st;          \
+  } while (0)
+
 uint32_t ceil_div(uint32_t a, uint32_t b) {
   return (uint32_t)(((uint64_t)a + b - 1) / b);
 }
@@ -112,20 +119,20 @@ struct cuking_ctx {
   // overlap): the matrix-core kernel's zeroed remainder slab, and the filter variant's
   // control words, candidate list, dense-quadrant list and slabs (king_filter.hip), sized
   // for a block of `filter_tiles` tiles (of its enumeration).  Each is allocated on first
-  // use; at most kMaxStreams streams, the oldest makes room.
+  // use; at most kMaxStreams streams, the oldest makes room (stream_entry below).
+  struct DeviceBuf {
+    void *p = nullptr;
+    size_t bytes = 0;
+  };
   struct StreamScratch {
     hipStream_t stream;
     uint32_t *split = nullptr;
     uint8_t *filter = nullptr;
     uint64_t filter_tiles = 0;
-    // cuking_unrelated_set's workspace (king_prune.hip), grown when a call needs more
-    void *prune = nullptr;
-    size_t prune_bytes = 0;
-    // cuking_compact_sites' table (king_site_qc.h), grown when a call needs more
-    void *sites = nullptr;
-    size_t sites_bytes = 0;
-    // cuking_ld_edges' edge counter (king_ld.hip): one word, allocated on first use
-    unsigned long long *ld_count = nullptr;
+    // Grown when a call needs more (grow_on_stream below): cuking_unrelated_set's workspace
+    // (king_prune.hip), cuking_compact_sites' table (king_site_qc.h) and cuking_ld_edges'
+    // edge counter (king_ld.hip: one word).
+    DeviceBuf prune, sites, ld_count;
   };
   std::vector<StreamScratch> scratch;
   // The running totals of filter scratch that has been freed since (a larger block took
@@ -320,18 +327,35 @@ uint64_t total_tiles(const TileSpace &t) {
 // stays small).
 constexpr size_t kMaxStreams = 8;
 
-// Frees the filter scratch of a stream on which nothing runs any more; its running totals
-// join the context's.
-void free_filter_scratch(cuking_ctx *ctx, cuking_ctx::StreamScratch &e) {
+// Frees the filter scratch of a stream on which nothing runs any more; with `retire` its
+// running totals join the context's.
+void free_filter_scratch(cuking_ctx *ctx, cuking_ctx::StreamScratch &e, bool retire = true) {
   if (e.filter == nullptr) return;
   unsigned long long v[kNumTotals] = {};
-  if (hipMemcpy(v, e.filter + filter_scratch_layout(e.filter_tiles).totals, sizeof v,
-                hipMemcpyDeviceToHost) == hipSuccess) {
-    for (uint32_t k = 0; k < kNumTotals; ++k) ctx->filter_totals_retired[k] += v[k];
+  if (retire) {
+    if (hipMemcpy(v, e.filter + filter_scratch_layout(e.filter_tiles).totals, sizeof v,
+                  hipMemcpyDeviceToHost) == hipSuccess)
+      for (uint32_t k = 0; k < kNumTotals; ++k) ctx->filter_totals_retired[k] += v[k];
+    (void)hipGetLastError();
   }
-  (void)hipGetLastError();
   (void)hipFree(e.filter);
   e.filter = nullptr;
+}
+
+void free_split_slab(cuking_ctx::StreamScratch &e) {
+  if (e.split != nullptr) (void)hipFree(e.split);
+  e.split = nullptr;
+}
+
+// Frees everything an entry of the stream cache owns, once nothing runs on its stream any
+// more: THE list of its buffers (a new one is added to StreamScratch and here).
+void free_stream_scratch(cuking_ctx *ctx, cuking_ctx::StreamScratch &e, bool retire_totals) {
+  free_filter_scratch(ctx, e, retire_totals);
+  free_split_slab(e);
+  for (cuking_ctx::DeviceBuf *b : {&e.prune, &e.sites, &e.ld_count}) {
+    if (b->p != nullptr) (void)hipFree(b->p);
+    *b = {};
+  }
 }
 
 // Waits for the stream of ctx->scratch[k] and drops its entry.  A stream its owner has
@@ -345,12 +369,37 @@ void evict_scratch(cuking_ctx *ctx, size_t k) {
     (void)hipDeviceSynchronize();
     (void)hipGetLastError();
   }
-  free_filter_scratch(ctx, e);
-  if (e.split != nullptr) (void)hipFree(e.split);
-  if (e.prune != nullptr) (void)hipFree(e.prune);
-  if (e.sites != nullptr) (void)hipFree(e.sites);
-  if (e.ld_count != nullptr) (void)hipFree(e.ld_count);
+  free_stream_scratch(ctx, e, true);
   ctx->scratch.erase(ctx->scratch.begin() + (ptrdiff_t)k);
+}
+
+// The entry of `stream` in the context's cache, created (empty: no allocation) when the
+// stream has none, after the oldest entry has made room when the cache is full.  The pointer
+// is valid until the next call that may add or drop an entry: stream_entry and evict_scratch.
+cuking_ctx::StreamScratch *stream_entry(cuking_ctx *ctx, hipStream_t stream) {
+  for (auto &x : ctx->scratch)
+    if (x.stream == stream) return &x;
+  if (ctx->scratch.size() >= kMaxStreams) evict_scratch(ctx, 0);
+  ctx->scratch.push_back({stream});
+  return &ctx->scratch.back();
+}
+
+// Makes the stream-owned buffer *buf at least `need` bytes.  Replacing one waits for its
+// stream first (an earlier call on it may still use the old one) and leaves the entry clean
+// should the allocation fail.
+cuking_status grow_on_stream(cuking_ctx *ctx, hipStream_t stream, cuking_ctx::DeviceBuf *buf,
+                             size_t need) {
+  if (need <= buf->bytes) return CUKING_OK;
+  if (buf->p != nullptr) {
+    ++ctx->host_syncs;
+    HIP_TRY(hipStreamSynchronize(stream));
+    (void)hipFree(buf->p);
+    *buf = {};
+  }
+  HIP_TRY(hipMalloc(&buf->p, need));
+  ++ctx->workspace_allocations;
+  buf->bytes = need;
+  return CUKING_OK;
 }
 
 // What a launch of the context's variant needs per stream.
@@ -383,14 +432,7 @@ cuking_status scratch_for(cuking_ctx *ctx, hipStream_t stream, uint64_t tiles,
   *out = nullptr;
   const bool split = uses_split_slab(ctx), filter = uses_filter_scratch(ctx);
   if (!split && !filter) return CUKING_OK;
-  cuking_ctx::StreamScratch *e = nullptr;
-  for (auto &x : ctx->scratch)
-    if (x.stream == stream) e = &x;
-  if (e == nullptr) {
-    if (ctx->scratch.size() >= kMaxStreams) evict_scratch(ctx, 0);
-    ctx->scratch.push_back({stream});
-    e = &ctx->scratch.back();
-  }
+  cuking_ctx::StreamScratch *e = stream_entry(ctx, stream);
   cuking_status st;
   if (split && e->split == nullptr) {
     // (the tickets in front of the slab)
@@ -1058,13 +1100,8 @@ void cuking_ctx_destroy(cuking_ctx *ctx) {
   if (ctx->sort_temp) (void)hipFree(ctx->sort_temp);
   if (ctx->synth_tables) (void)hipFree(ctx->synth_tables);
   if (ctx->synth_done) (void)hipEventDestroy(ctx->synth_done);
-  for (auto &e : ctx->scratch) {
-    if (e.split) (void)hipFree(e.split);
-    if (e.filter) (void)hipFree(e.filter);
-    if (e.prune) (void)hipFree(e.prune);
-    if (e.sites) (void)hipFree(e.sites);
-    if (e.ld_count) (void)hipFree(e.ld_count);
-  }
+  // (nobody reads the filter's totals any more: they are not copied back)
+  for (auto &e : ctx->scratch) free_stream_scratch(ctx, e, false);
   for (auto &r : ctx->readers)
     if (r.second) (void)hipEventDestroy(r.second);
   ctx->king_timer.destroy();
@@ -1090,10 +1127,7 @@ cuking_status cuking_ctx_set_option(cuking_ctx *ctx, const char *key,
     return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, o->error, o->error_arg);
   if ((o->effects & kResizesSlabs) && value != o->get(ctx)) {
     HIP_TRY(hipDeviceSynchronize());
-    for (auto &e : ctx->scratch) {
-      if (e.split) (void)hipFree(e.split);
-      e.split = nullptr;
-    }
+    for (auto &e : ctx->scratch) free_split_slab(e);
   }
   o->set(ctx, value);
   if (o->effects & kInvalidatesLayout) ctx->prepared.valid = false;
@@ -1101,8 +1135,7 @@ cuking_status cuking_ctx_set_option(cuking_ctx *ctx, const char *key,
 }
 
 cuking_status cuking_device_alloc(cuking_ctx *ctx, size_t bytes, void **d_ptr) {
-  cuking_status st = bind(ctx);
-  if (st != CUKING_OK) return st;
+  BIND_OR_RETURN(ctx);
   if (d_ptr == nullptr) return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "null out pointer");
   *d_ptr = nullptr;
   if (bytes == 0) return CUKING_OK;
@@ -1111,16 +1144,14 @@ cuking_status cuking_device_alloc(cuking_ctx *ctx, size_t bytes, void **d_ptr) {
 }
 
 cuking_status cuking_device_free(cuking_ctx *ctx, void *d_ptr) {
-  cuking_status st = bind(ctx);
-  if (st != CUKING_OK) return st;
+  BIND_OR_RETURN(ctx);
   if (d_ptr) HIP_TRY(hipFree(d_ptr));
   return CUKING_OK;
 }
 
 cuking_status cuking_memset_async(cuking_ctx *ctx, void *d_ptr, int byte_value,
                                   size_t bytes, void *stream) {
-  cuking_status st = bind(ctx);
-  if (st != CUKING_OK) return st;
+  BIND_OR_RETURN(ctx);
   if (bytes) HIP_TRY(hipMemsetAsync(d_ptr, byte_value, bytes, (hipStream_t)stream));
   return CUKING_OK;
 }
@@ -1128,8 +1159,7 @@ cuking_status cuking_memset_async(cuking_ctx *ctx, void *d_ptr, int byte_value,
 cuking_status cuking_copy_to_device(cuking_ctx *ctx, void *d_dst,
                                     const void *src, size_t bytes,
                                     void *stream) {
-  cuking_status st = bind(ctx);
-  if (st != CUKING_OK) return st;
+  BIND_OR_RETURN(ctx);
   if (bytes)
     HIP_TRY(hipMemcpyAsync(d_dst, src, bytes, hipMemcpyHostToDevice,
                            (hipStream_t)stream));
@@ -1138,8 +1168,7 @@ cuking_status cuking_copy_to_device(cuking_ctx *ctx, void *d_dst,
 
 cuking_status cuking_copy_to_host(cuking_ctx *ctx, void *dst, const void *d_src,
                                   size_t bytes, void *stream) {
-  cuking_status st = bind(ctx);
-  if (st != CUKING_OK) return st;
+  BIND_OR_RETURN(ctx);
   if (bytes)
     HIP_TRY(hipMemcpyAsync(dst, d_src, bytes, hipMemcpyDeviceToHost,
                            (hipStream_t)stream));
@@ -1147,15 +1176,13 @@ cuking_status cuking_copy_to_host(cuking_ctx *ctx, void *dst, const void *d_src,
 }
 
 cuking_status cuking_stream_synchronize(cuking_ctx *ctx, void *stream) {
-  cuking_status st = bind(ctx);
-  if (st != CUKING_OK) return st;
+  BIND_OR_RETURN(ctx);
   HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
   return CUKING_OK;
 }
 
 cuking_status cuking_stream_create(cuking_ctx *ctx, void **stream) {
-  cuking_status st = bind(ctx);
-  if (st != CUKING_OK) return st;
+  BIND_OR_RETURN(ctx);
   if (stream == nullptr) return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "null out pointer");
   hipStream_t s = nullptr;
   HIP_TRY(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
@@ -1164,8 +1191,7 @@ cuking_status cuking_stream_create(cuking_ctx *ctx, void **stream) {
 }
 
 cuking_status cuking_stream_destroy(cuking_ctx *ctx, void *stream) {
-  cuking_status st = bind(ctx);
-  if (st != CUKING_OK) return st;
+  BIND_OR_RETURN(ctx);
   if (stream) {
     // hipStreamDestroy lets the stream's work finish; nothing may name it later.
     auto &rs = ctx->readers;
@@ -1182,8 +1208,7 @@ cuking_status cuking_stream_destroy(cuking_ctx *ctx, void *stream) {
 }
 
 cuking_status cuking_host_alloc(cuking_ctx *ctx, size_t bytes, void **ptr) {
-  cuking_status st = bind(ctx);
-  if (st != CUKING_OK) return st;
+  BIND_OR_RETURN(ctx);
   if (ptr == nullptr) return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "null out pointer");
   *ptr = nullptr;
   if (bytes == 0) return CUKING_OK;
@@ -1192,8 +1217,7 @@ cuking_status cuking_host_alloc(cuking_ctx *ctx, size_t bytes, void **ptr) {
 }
 
 cuking_status cuking_host_free(cuking_ctx *ctx, void *ptr) {
-  cuking_status st = bind(ctx);
-  if (st != CUKING_OK) return st;
+  BIND_OR_RETURN(ctx);
   if (ptr) HIP_TRY(hipHostFree(ptr));
   return CUKING_OK;
 }
@@ -1207,9 +1231,8 @@ cuking_status cuking_pack_device(cuking_ctx *ctx, const cuking_submatrix *sm,
                                  const int32_t *d_n_alt_alleles,
                                  size_t num_triples, uint32_t *d_status,
                                  void *stream) {
-  cuking_status st = bind(ctx);
-  if (st != CUKING_OK) return st;
-  st = cuking_check_block(sm, words_per_sample);
+  BIND_OR_RETURN(ctx);
+  cuking_status st = cuking_check_block(sm, words_per_sample);
   if (st != CUKING_OK) return st;
   if (num_triples &&
       (!d_bit_set || !d_row_idx || !d_col_idx || !d_n_alt_alleles || !d_status))
@@ -1225,9 +1248,8 @@ cuking_status cuking_pack_device_compact(cuking_ctx *ctx, const cuking_submatrix
                                          const uint32_t *d_site,
                                          const uint32_t *d_sample_alt, size_t num_triples,
                                          uint32_t *d_status, void *stream) {
-  cuking_status st = bind(ctx);
-  if (st != CUKING_OK) return st;
-  st = cuking_check_block(sm, words_per_sample);
+  BIND_OR_RETURN(ctx);
+  cuking_status st = cuking_check_block(sm, words_per_sample);
   if (st != CUKING_OK) return st;
   if (num_triples && (!d_bit_set || !d_site || !d_sample_alt || !d_status))
     return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "null device pointer");
@@ -1247,16 +1269,14 @@ cuking_status cuking_pack_bed_device(cuking_ctx *ctx, const cuking_submatrix *sm
                                            site_begin, site_end, num_sites);
   if (st != CUKING_OK) return st;
   if (site_begin == site_end || sm_num_samples(*sm) == 0) return CUKING_OK;
-  st = bind(ctx);
-  if (st != CUKING_OK) return st;
+  BIND_OR_RETURN(ctx);
   HIP_TRY(launch_pack_bed(*sm, words_per_sample, d_bit_set, d_bed_rows, row_bytes, site_begin,
                           site_end, (hipStream_t)stream));
   return CUKING_OK;
 }
 
 cuking_status cuking_event_create(cuking_ctx *ctx, void **event) {
-  cuking_status st = bind(ctx);
-  if (st != CUKING_OK) return st;
+  BIND_OR_RETURN(ctx);
   if (event == nullptr) return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "null out pointer");
   hipEvent_t e = nullptr;
   HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
@@ -1265,22 +1285,19 @@ cuking_status cuking_event_create(cuking_ctx *ctx, void **event) {
 }
 
 cuking_status cuking_event_record(cuking_ctx *ctx, void *event, void *stream) {
-  cuking_status st = bind(ctx);
-  if (st != CUKING_OK) return st;
+  BIND_OR_RETURN(ctx);
   HIP_TRY(hipEventRecord((hipEvent_t)event, (hipStream_t)stream));
   return CUKING_OK;
 }
 
 cuking_status cuking_event_synchronize(cuking_ctx *ctx, void *event) {
-  cuking_status st = bind(ctx);
-  if (st != CUKING_OK) return st;
+  BIND_OR_RETURN(ctx);
   HIP_TRY(hipEventSynchronize((hipEvent_t)event));
   return CUKING_OK;
 }
 
 cuking_status cuking_event_destroy(cuking_ctx *ctx, void *event) {
-  cuking_status st = bind(ctx);
-  if (st != CUKING_OK) return st;
+  BIND_OR_RETURN(ctx);
   if (event) HIP_TRY(hipEventDestroy((hipEvent_t)event));
   return CUKING_OK;
 }
@@ -1349,6 +1366,34 @@ static cuking_status check_compute_args(const cuking_submatrix *sm,
   return CUKING_OK;
 }
 
+// What cuking_compute_king and cuking_compute_king_tiles share: `whole` = every tile of the
+// block (the only form the stream kernel serves).
+static cuking_status run_king(cuking_ctx *ctx, const cuking_submatrix *sm,
+                              uint32_t words_per_sample, const uint64_t *d_bit_sets, bool whole,
+                              uint64_t tile_begin, uint64_t tile_end, float kin_threshold,
+                              uint32_t max_results, cuking_result *d_results,
+                              uint32_t *d_result_index, uint32_t *d_result_overflow,
+                              void *stream) {
+  BIND_OR_RETURN(ctx);
+  const cuking_status st = check_compute_args(sm, words_per_sample, d_bit_sets);
+  if (st != CUKING_OK) return st;
+  if (!d_result_index || !d_result_overflow || (max_results && !d_results))
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "null result pointer");
+  if (sm_num_rows(*sm) == 0 || sm_num_cols(*sm) == 0) {
+    if (!whole && (tile_begin != 0 || tile_end != 0))
+      return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "empty block has no tiles");
+    return CUKING_OK;
+  }
+  if (whole && ctx->kernel == CUKING_KERNEL_STREAM)
+    return run_stream(ctx, *sm, words_per_sample, d_bit_sets, kin_threshold,
+                      max_results, d_results, d_result_index, d_result_overflow,
+                      nullptr, (hipStream_t)stream);
+  return run_tiled(ctx, *sm, words_per_sample, d_bit_sets, tile_begin, tile_end, whole,
+                   kin_threshold,
+                   {max_results, d_results, d_result_index, d_result_overflow, nullptr},
+                   (hipStream_t)stream);
+}
+
 cuking_status cuking_compute_king(cuking_ctx *ctx, const cuking_submatrix *sm,
                                   uint32_t words_per_sample,
                                   const uint64_t *d_bit_sets,
@@ -1356,20 +1401,8 @@ cuking_status cuking_compute_king(cuking_ctx *ctx, const cuking_submatrix *sm,
                                   cuking_result *d_results,
                                   uint32_t *d_result_index,
                                   uint32_t *d_result_overflow, void *stream) {
-  cuking_status st = bind(ctx);
-  if (st != CUKING_OK) return st;
-  st = check_compute_args(sm, words_per_sample, d_bit_sets);
-  if (st != CUKING_OK) return st;
-  if (!d_result_index || !d_result_overflow || (max_results && !d_results))
-    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "null result pointer");
-  if (sm_num_rows(*sm) == 0 || sm_num_cols(*sm) == 0) return CUKING_OK;
-  if (ctx->kernel == CUKING_KERNEL_STREAM)
-    return run_stream(ctx, *sm, words_per_sample, d_bit_sets, kin_threshold,
-                      max_results, d_results, d_result_index, d_result_overflow,
-                      nullptr, (hipStream_t)stream);
-  return run_tiled(ctx, *sm, words_per_sample, d_bit_sets, 0, 0, true, kin_threshold,
-                   {max_results, d_results, d_result_index, d_result_overflow, nullptr},
-                   (hipStream_t)stream);
+  return run_king(ctx, sm, words_per_sample, d_bit_sets, true, 0, 0, kin_threshold, max_results,
+                  d_results, d_result_index, d_result_overflow, stream);
 }
 
 cuking_status cuking_compute_king_tiles(
@@ -1377,21 +1410,9 @@ cuking_status cuking_compute_king_tiles(
     const uint64_t *d_bit_sets, uint64_t tile_begin, uint64_t tile_end,
     float kin_threshold, uint32_t max_results, cuking_result *d_results,
     uint32_t *d_result_index, uint32_t *d_result_overflow, void *stream) {
-  cuking_status st = bind(ctx);
-  if (st != CUKING_OK) return st;
-  st = check_compute_args(sm, words_per_sample, d_bit_sets);
-  if (st != CUKING_OK) return st;
-  if (!d_result_index || !d_result_overflow || (max_results && !d_results))
-    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "null result pointer");
-  if (sm_num_rows(*sm) == 0 || sm_num_cols(*sm) == 0) {
-    if (tile_begin != 0 || tile_end != 0)
-      return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "empty block has no tiles");
-    return CUKING_OK;
-  }
-  return run_tiled(ctx, *sm, words_per_sample, d_bit_sets, tile_begin, tile_end, false,
-                   kin_threshold,
-                   {max_results, d_results, d_result_index, d_result_overflow, nullptr},
-                   (hipStream_t)stream);
+  return run_king(ctx, sm, words_per_sample, d_bit_sets, false, tile_begin, tile_end,
+                  kin_threshold, max_results, d_results, d_result_index, d_result_overflow,
+                  stream);
 }
 
 // Offsets of a sample range inside a diagonal block, in tiles.
@@ -1416,9 +1437,8 @@ cuking_status cuking_prepare_samples(cuking_ctx *ctx, const cuking_submatrix *sm
                                      const uint64_t *d_bit_sets,
                                      uint32_t sample_begin, uint32_t sample_end,
                                      void *stream) {
-  cuking_status st = bind(ctx);
-  if (st != CUKING_OK) return st;
-  st = check_compute_args(sm, words_per_sample, d_bit_sets);
+  BIND_OR_RETURN(ctx);
+  cuking_status st = check_compute_args(sm, words_per_sample, d_bit_sets);
   if (st != CUKING_OK) return st;
   if (!sm_is_diag(*sm))
     return cuking_fail(CUKING_ERR_INVALID_ARGUMENT,
@@ -1441,9 +1461,8 @@ cuking_status cuking_compute_king_rect(
     uint32_t row_step, uint32_t col_begin, uint32_t col_end, float kin_threshold,
     uint32_t max_results, cuking_result *d_results, uint32_t *d_result_index,
     uint32_t *d_result_overflow, void *stream) {
-  cuking_status st = bind(ctx);
-  if (st != CUKING_OK) return st;
-  st = check_compute_args(sm, words_per_sample, d_bit_sets);
+  BIND_OR_RETURN(ctx);
+  cuking_status st = check_compute_args(sm, words_per_sample, d_bit_sets);
   if (st != CUKING_OK) return st;
   if (!sm_is_diag(*sm))
     return cuking_fail(CUKING_ERR_INVALID_ARGUMENT,
@@ -1537,9 +1556,8 @@ cuking_status cuking_compute_king_rect(
 cuking_status cuking_ctx_reserve(cuking_ctx *ctx, const cuking_submatrix *sm,
                                  uint32_t words_per_sample, void *const *streams,
                                  size_t num_streams) {
-  cuking_status st = bind(ctx);
-  if (st != CUKING_OK) return st;
-  st = cuking_check_block(sm, words_per_sample);
+  BIND_OR_RETURN(ctx);
+  cuking_status st = cuking_check_block(sm, words_per_sample);
   if (st != CUKING_OK) return st;
   if (num_streams != 0 && streams == nullptr)
     return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "null stream list");
@@ -1599,9 +1617,8 @@ cuking_status cuking_compute_counts(cuking_ctx *ctx, const cuking_submatrix *sm,
                                     uint32_t words_per_sample,
                                     const uint64_t *d_bit_sets,
                                     cuking_counts *d_counts, void *stream) {
-  cuking_status st = bind(ctx);
-  if (st != CUKING_OK) return st;
-  st = check_compute_args(sm, words_per_sample, d_bit_sets);
+  BIND_OR_RETURN(ctx);
+  cuking_status st = check_compute_args(sm, words_per_sample, d_bit_sets);
   if (st != CUKING_OK) return st;
   if (sm_num_rows(*sm) == 0 || sm_num_cols(*sm) == 0) return CUKING_OK;
   if (d_counts == nullptr)
@@ -1639,22 +1656,35 @@ static cuking_status check_kin_args(const cuking_ctx *ctx, const cuking_submatri
   return CUKING_OK;
 }
 
+// What the two entry points share behind their checks: `whole` = every tile of the block
+// (the only form the stream kernel serves).
+static cuking_status run_kin_matrix(cuking_ctx *ctx, const cuking_submatrix *sm,
+                                    uint32_t words_per_sample, const uint64_t *d_bit_sets,
+                                    bool whole, uint64_t tile_begin, uint64_t tile_end,
+                                    float *d_kin, uint64_t ld, uint32_t flags, void *stream) {
+  const cuking_status st =
+      check_kin_args(ctx, sm, words_per_sample, d_bit_sets, d_kin, ld, flags, !whole);
+  if (st != CUKING_OK) return st;
+  BIND_OR_RETURN(ctx);
+  if (sm_num_rows(*sm) == 0 || sm_num_cols(*sm) == 0) {
+    if (!whole && (tile_begin != 0 || tile_end != 0))
+      return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "empty block has no tiles");
+    return CUKING_OK;
+  }
+  if (whole && ctx->kernel == CUKING_KERNEL_STREAM)
+    return run_stream(ctx, *sm, words_per_sample, d_bit_sets, 0.f, 0, nullptr, nullptr,
+                      nullptr, nullptr, (hipStream_t)stream, d_kin, ld, flags);
+  return run_tiled(ctx, *sm, words_per_sample, d_bit_sets, tile_begin, tile_end, whole, 0.f,
+                   {0, nullptr, nullptr, nullptr, nullptr, d_kin, ld, flags},
+                   (hipStream_t)stream);
+}
+
 cuking_status cuking_compute_kin_matrix(cuking_ctx *ctx, const cuking_submatrix *sm,
                                         uint32_t words_per_sample, const uint64_t *d_bit_sets,
                                         float *d_kin, uint64_t ld, uint32_t flags,
                                         void *stream) {
-  cuking_status st =
-      check_kin_args(ctx, sm, words_per_sample, d_bit_sets, d_kin, ld, flags, false);
-  if (st != CUKING_OK) return st;
-  st = bind(ctx);
-  if (st != CUKING_OK) return st;
-  if (sm_num_rows(*sm) == 0 || sm_num_cols(*sm) == 0) return CUKING_OK;
-  if (ctx->kernel == CUKING_KERNEL_STREAM)
-    return run_stream(ctx, *sm, words_per_sample, d_bit_sets, 0.f, 0, nullptr, nullptr,
-                      nullptr, nullptr, (hipStream_t)stream, d_kin, ld, flags);
-  return run_tiled(ctx, *sm, words_per_sample, d_bit_sets, 0, 0, true, 0.f,
-                   {0, nullptr, nullptr, nullptr, nullptr, d_kin, ld, flags},
-                   (hipStream_t)stream);
+  return run_kin_matrix(ctx, sm, words_per_sample, d_bit_sets, true, 0, 0, d_kin, ld, flags,
+                        stream);
 }
 
 cuking_status cuking_compute_kin_matrix_tiles(cuking_ctx *ctx, const cuking_submatrix *sm,
@@ -1662,19 +1692,41 @@ cuking_status cuking_compute_kin_matrix_tiles(cuking_ctx *ctx, const cuking_subm
                                               const uint64_t *d_bit_sets, uint64_t tile_begin,
                                               uint64_t tile_end, float *d_kin, uint64_t ld,
                                               uint32_t flags, void *stream) {
-  cuking_status st =
-      check_kin_args(ctx, sm, words_per_sample, d_bit_sets, d_kin, ld, flags, true);
-  if (st != CUKING_OK) return st;
-  st = bind(ctx);
-  if (st != CUKING_OK) return st;
-  if (sm_num_rows(*sm) == 0 || sm_num_cols(*sm) == 0) {
-    if (tile_begin != 0 || tile_end != 0)
-      return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "empty block has no tiles");
-    return CUKING_OK;
+  return run_kin_matrix(ctx, sm, words_per_sample, d_bit_sets, false, tile_begin, tile_end,
+                        d_kin, ld, flags, stream);
+}
+
+// What the checks of the reducing calls (kinship summary, relative counts) end with, in front
+// of anything that touches a device: the tile range, the context and what it can serve.
+// `what` names the call, `form` the kernel form a context may lack.
+static cuking_status check_reducing_args(const cuking_ctx *ctx, const cuking_submatrix *sm,
+                                         uint32_t words_per_sample, bool tile_range,
+                                         uint64_t tile_begin, uint64_t tile_end,
+                                         const char *what, const char *form) {
+  if (tile_range && tile_begin > tile_end)
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "tile range [%llu, %llu) is reversed",
+                       (unsigned long long)tile_begin, (unsigned long long)tile_end);
+  if (ctx == nullptr) return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "null context");
+  // (run_tiled checks the range as well, but only behind the conversion: this call refuses
+  //  a bad range before a device is touched)
+  if (tile_range) {
+    const bool empty = sm_num_rows(*sm) == 0 || sm_num_cols(*sm) == 0;
+    const uint64_t n_tiles = empty ? 0 : cuking_num_tiles(ctx, sm);
+    if (tile_end > n_tiles)
+      return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "tile range [%llu, %llu) outside [0, %llu)",
+                         (unsigned long long)tile_begin, (unsigned long long)tile_end,
+                         (unsigned long long)n_tiles);
   }
-  return run_tiled(ctx, *sm, words_per_sample, d_bit_sets, tile_begin, tile_end, false, 0.f,
-                   {0, nullptr, nullptr, nullptr, nullptr, d_kin, ld, flags},
-                   (hipStream_t)stream);
+  if (ctx->kernel != CUKING_KERNEL_TILED || !is_mfma_variant(ctx->variant))
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT,
+                       "%s: served by contexts of the tiled kernel with variant 5, 6 or 7 (the "
+                       "matrix-core kernels) only; the VALU variants and the stream kernel have "
+                       "no %s", what, form);
+  if (!is_mfma_variant(effective_variant(ctx, words_per_sample)))
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT,
+                       "%s: bitsets from 2^24 sites on are not served (the matrix-core kernels "
+                       "count in float32)", what);
+  return CUKING_OK;
 }
 
 // The checks the two kinship-summary entry points share, in front of anything that touches
@@ -1702,30 +1754,8 @@ static cuking_status check_summary_args(const cuking_ctx *ctx, const cuking_subm
                          "kinship summary: histogram bounds must be finite with lo < hi "
                          "(lo %g, hi %g)", (double)bins->lo, (double)bins->hi);
   }
-  if (tile_range && tile_begin > tile_end)
-    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "tile range [%llu, %llu) is reversed",
-                       (unsigned long long)tile_begin, (unsigned long long)tile_end);
-  if (ctx == nullptr) return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "null context");
-  const bool empty = sm_num_rows(*sm) == 0 || sm_num_cols(*sm) == 0;
-  // (run_tiled checks the range as well, but only behind the conversion: this call refuses
-  //  a bad range before a device is touched)
-  if (tile_range) {
-    const uint64_t n_tiles = empty ? 0 : cuking_num_tiles(ctx, sm);
-    if (tile_end > n_tiles)
-      return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "tile range [%llu, %llu) outside [0, %llu)",
-                         (unsigned long long)tile_begin, (unsigned long long)tile_end,
-                         (unsigned long long)n_tiles);
-  }
-  if (ctx->kernel != CUKING_KERNEL_TILED || !is_mfma_variant(ctx->variant))
-    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT,
-                       "kinship summary: served by contexts of the tiled kernel with variant 5, "
-                       "6 or 7 (the matrix-core kernels) only; the VALU variants and the stream "
-                       "kernel have no summary form");
-  if (!is_mfma_variant(effective_variant(ctx, words_per_sample)))
-    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT,
-                       "kinship summary: bitsets from 2^24 sites on are not served (the "
-                       "matrix-core kernels count in float32)");
-  return CUKING_OK;
+  return check_reducing_args(ctx, sm, words_per_sample, tile_range, tile_begin, tile_end,
+                             "kinship summary", "summary form");
 }
 
 // What the two entry points share behind their checks: `whole` = every tile of the block.
@@ -1738,8 +1768,7 @@ static cuking_status run_summary(cuking_ctx *ctx, const cuking_submatrix *sm,
                                         d_best, !whole, tile_begin, tile_end);
   if (st != CUKING_OK) return st;
   if (sm_num_rows(*sm) == 0 || sm_num_cols(*sm) == 0) return CUKING_OK;
-  st = bind(ctx);
-  if (st != CUKING_OK) return st;
+  BIND_OR_RETURN(ctx);
   Outputs out = {};
   out.sum_hist = d_hist;
   out.sum_best = d_best;
@@ -1786,28 +1815,8 @@ static cuking_status check_rel_args(const cuking_ctx *ctx, const cuking_submatri
                        "relative counts: thresholds must be finite and strictly ascending");
   if (sm_num_samples(*sm) != 0 && d_counts == nullptr)
     return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "relative counts: null counts pointer");
-  if (tile_range && tile_begin > tile_end)
-    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "tile range [%llu, %llu) is reversed",
-                       (unsigned long long)tile_begin, (unsigned long long)tile_end);
-  if (ctx == nullptr) return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "null context");
-  if (tile_range) {
-    const bool empty = sm_num_rows(*sm) == 0 || sm_num_cols(*sm) == 0;
-    const uint64_t n_tiles = empty ? 0 : cuking_num_tiles(ctx, sm);
-    if (tile_end > n_tiles)
-      return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "tile range [%llu, %llu) outside [0, %llu)",
-                         (unsigned long long)tile_begin, (unsigned long long)tile_end,
-                         (unsigned long long)n_tiles);
-  }
-  if (ctx->kernel != CUKING_KERNEL_TILED || !is_mfma_variant(ctx->variant))
-    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT,
-                       "relative counts: served by contexts of the tiled kernel with variant 5, "
-                       "6 or 7 (the matrix-core kernels) only; the VALU variants and the stream "
-                       "kernel have no counting form");
-  if (!is_mfma_variant(effective_variant(ctx, words_per_sample)))
-    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT,
-                       "relative counts: bitsets from 2^24 sites on are not served (the "
-                       "matrix-core kernels count in float32)");
-  return CUKING_OK;
+  return check_reducing_args(ctx, sm, words_per_sample, tile_range, tile_begin, tile_end,
+                             "relative counts", "counting form");
 }
 
 // What the two entry points share behind their checks: `whole` = every tile of the block.
@@ -1819,8 +1828,7 @@ static cuking_status run_rel(cuking_ctx *ctx, const cuking_submatrix *sm,
                                     num_thresholds, d_counts, !whole, tile_begin, tile_end);
   if (st != CUKING_OK) return st;
   if (sm_num_rows(*sm) == 0 || sm_num_cols(*sm) == 0) return CUKING_OK;
-  st = bind(ctx);
-  if (st != CUKING_OK) return st;
+  BIND_OR_RETURN(ctx);
   Outputs out = {};
   out.rel_counts = d_counts;
   out.rel_num = num_thresholds;
@@ -1872,36 +1880,18 @@ cuking_status cuking_unrelated_set(cuking_ctx *ctx, const cuking_result *d_recor
     return cuking_fail(CUKING_ERR_INVALID_ARGUMENT,
                        "unrelated set: records name samples outside [0, num_samples)");
   if (num_samples == 0) return CUKING_OK;
-  cuking_status st = bind(ctx);
-  if (st != CUKING_OK) return st;
+  BIND_OR_RETURN(ctx);
   // The stream's entry of the scratch cache; the workspace is sized once per call, in front
   // of the round loop, and grown only when a call needs more.
   hipStream_t s = (hipStream_t)stream;
-  cuking_ctx::StreamScratch *e = nullptr;
-  for (auto &x : ctx->scratch)
-    if (x.stream == s) e = &x;
-  if (e == nullptr) {
-    if (ctx->scratch.size() >= kMaxStreams) evict_scratch(ctx, 0);
-    ctx->scratch.push_back({s});
-    e = &ctx->scratch.back();
-  }
+  cuking_ctx::StreamScratch *e = stream_entry(ctx, s);
   const size_t bytes = prune_workspace_bytes((uint32_t)num_records, num_samples,
                                              d_priority == nullptr);
-  if (e->prune_bytes < bytes) {
-    if (e->prune != nullptr) {  // an earlier call on this stream may still run
-      ++ctx->host_syncs;
-      HIP_TRY(hipStreamSynchronize(s));
-      (void)hipFree(e->prune);
-      e->prune = nullptr;
-      e->prune_bytes = 0;
-    }
-    HIP_TRY(hipMalloc(&e->prune, bytes));
-    ++ctx->workspace_allocations;
-    e->prune_bytes = bytes;
-  }
+  const cuking_status st = grow_on_stream(ctx, s, &e->prune, bytes);
+  if (st != CUKING_OK) return st;
   uint32_t done = 0, syncs = 0;
   int invalid = 0, exceeded = 0;
-  const int err = prune_run(e->prune, d_records, (uint32_t)num_records, num_samples,
+  const int err = prune_run(e->prune.p, d_records, (uint32_t)num_records, num_samples,
                             prune_threshold, d_priority, d_keep, d_family, ctx->num_cus, &done,
                             &syncs, &invalid, &exceeded, stream);
   ctx->host_syncs += syncs;
@@ -1934,8 +1924,7 @@ cuking_status cuking_site_counts(cuking_ctx *ctx, const uint64_t *d_bit_set,
                                               words_per_sample, d_counts);
   if (st != CUKING_OK) return st;
   if (num_stored == 0) return CUKING_OK;
-  st = bind(ctx);
-  if (st != CUKING_OK) return st;
+  BIND_OR_RETURN(ctx);
   HIP_TRY(launch_site_counts(d_bit_set, num_stored, words_per_sample, d_counts,
                              (hipStream_t)stream));
   return CUKING_OK;
@@ -1953,8 +1942,7 @@ cuking_status cuking_sample_counts(cuking_ctx *ctx, const uint64_t *d_bit_set,
                        "sample counts: %u sites need %u words per sample, not %u", num_sites,
                        cuking_words_per_sample(num_sites), words_per_sample);
   if (num_stored == 0) return CUKING_OK;
-  st = bind(ctx);
-  if (st != CUKING_OK) return st;
+  BIND_OR_RETURN(ctx);
   HIP_TRY(launch_sample_counts(d_bit_set, num_stored, words_per_sample, num_sites, d_counts,
                                (hipStream_t)stream));
   return CUKING_OK;
@@ -1970,40 +1958,22 @@ cuking_status cuking_compact_sites(cuking_ctx *ctx, const uint64_t *d_in, uint32
                                                num_sites_in, d_out, words_per_sample_out, &kept);
   if (st != CUKING_OK) return st;
   if (num_stored == 0) return CUKING_OK;
-  st = bind(ctx);
-  if (st != CUKING_OK) return st;
+  BIND_OR_RETURN(ctx);
   hipStream_t s = (hipStream_t)stream;
-  cuking_ctx::StreamScratch *e = nullptr;
-  for (auto &x : ctx->scratch)
-    if (x.stream == s) e = &x;
-  if (e == nullptr) {
-    if (ctx->scratch.size() >= kMaxStreams) evict_scratch(ctx, 0);
-    ctx->scratch.push_back({s});
-    e = &ctx->scratch.back();
-  }
+  cuking_ctx::StreamScratch *e = stream_entry(ctx, s);
   const uint32_t plane_in = words_per_sample_in / 2, plane_out = words_per_sample_out / 2;
   const size_t bytes = compact_table_bytes(plane_in, plane_out);
-  if (e->sites_bytes < bytes) {
-    if (e->sites != nullptr) {  // an earlier call on this stream may still read it
-      ++ctx->host_syncs;
-      HIP_TRY(hipStreamSynchronize(s));
-      (void)hipFree(e->sites);
-      e->sites = nullptr;
-      e->sites_bytes = 0;
-    }
-    HIP_TRY(hipMalloc(&e->sites, bytes));
-    ++ctx->workspace_allocations;
-    e->sites_bytes = bytes;
-  }
+  st = grow_on_stream(ctx, s, &e->sites, bytes);
+  if (st != CUKING_OK) return st;
   // (8-byte units: the table starts with uint64 fields)
   std::vector<uint64_t> table((bytes + 7) / 8);
   build_compact_table(keep, plane_in, plane_out, table.data());
   // Ordered on the stream behind whatever still reads the table of an earlier call.  Small and
   // pageable: wait until the host buffer may go away.
-  HIP_TRY(hipMemcpyAsync(e->sites, table.data(), bytes, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(e->sites.p, table.data(), bytes, hipMemcpyHostToDevice, s));
   ++ctx->host_syncs;
   HIP_TRY(hipStreamSynchronize(s));
-  HIP_TRY(launch_compact_sites(d_in, num_stored, words_per_sample_in, e->sites, kept, d_out,
+  HIP_TRY(launch_compact_sites(d_in, num_stored, words_per_sample_in, e->sites.p, kept, d_out,
                                words_per_sample_out, s));
   return CUKING_OK;
 }
@@ -2019,8 +1989,7 @@ cuking_status cuking_transpose_sites(cuking_ctx *ctx, const uint64_t *d_bit_set,
                                                  num_sites, d_site_bits, words_per_site_plane);
   if (st != CUKING_OK) return st;
   if (num_stored == 0 || num_sites == 0) return CUKING_OK;
-  st = bind(ctx);
-  if (st != CUKING_OK) return st;
+  BIND_OR_RETURN(ctx);
   HIP_TRY(launch_transpose_sites(d_bit_set, num_stored, words_per_sample, num_sites, d_site_bits,
                                  (hipStream_t)stream));
   return CUKING_OK;
@@ -2036,26 +2005,17 @@ cuking_status cuking_ld_edges(cuking_ctx *ctx, const uint64_t *d_site_bits, uint
                                           d_records, max_records, num_records);
   if (st != CUKING_OK) return st;
   if (num_sites < 2 || num_stored == 0) return CUKING_OK;
-  st = bind(ctx);
-  if (st != CUKING_OK) return st;
+  BIND_OR_RETURN(ctx);
   hipStream_t s = (hipStream_t)stream;
-  cuking_ctx::StreamScratch *e = nullptr;
-  for (auto &x : ctx->scratch)
-    if (x.stream == s) e = &x;
-  if (e == nullptr) {
-    if (ctx->scratch.size() >= kMaxStreams) evict_scratch(ctx, 0);
-    ctx->scratch.push_back({s});
-    e = &ctx->scratch.back();
-  }
-  if (e->ld_count == nullptr) {
-    HIP_TRY(hipMalloc(&e->ld_count, sizeof(unsigned long long)));
-    ++ctx->workspace_allocations;
-  }
-  HIP_TRY(hipMemsetAsync(e->ld_count, 0, sizeof(unsigned long long), s));
+  cuking_ctx::StreamScratch *e = stream_entry(ctx, s);
+  st = grow_on_stream(ctx, s, &e->ld_count, sizeof(unsigned long long));
+  if (st != CUKING_OK) return st;
+  unsigned long long *d_count = static_cast<unsigned long long *>(e->ld_count.p);
+  HIP_TRY(hipMemsetAsync(d_count, 0, sizeof(unsigned long long), s));
   HIP_TRY(launch_ld_edges(d_site_bits, num_sites, num_stored, window, r2_threshold, d_group,
-                          d_records, max_records, e->ld_count, s));
+                          d_records, max_records, d_count, s));
   unsigned long long count = 0;
-  HIP_TRY(hipMemcpyAsync(&count, e->ld_count, sizeof(count), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(&count, d_count, sizeof(count), hipMemcpyDeviceToHost, s));
   ++ctx->host_syncs;
   HIP_TRY(hipStreamSynchronize(s));
   *num_records = count;
@@ -2080,8 +2040,7 @@ cuking_status cuking_timing_reset(cuking_ctx *ctx) {
 cuking_status cuking_timing_collect(cuking_ctx *ctx, double *king_ms,
                                     uint64_t *king_launches, double *prepare_ms,
                                     uint64_t *prepare_launches) {
-  cuking_status st = bind(ctx);
-  if (st != CUKING_OK) return st;
+  BIND_OR_RETURN(ctx);
   double a = 0, b = 0;
   uint64_t na = 0, nb = 0;
   HIP_TRY(ctx->king_timer.collect(&a, &na));
@@ -2095,8 +2054,7 @@ cuking_status cuking_timing_collect(cuking_ctx *ctx, double *king_ms,
 
 cuking_status cuking_clock_probe(cuking_ctx *ctx, uint64_t microseconds,
                                  uint64_t *d_ticks, void *stream) {
-  cuking_status st = bind(ctx);
-  if (st != CUKING_OK) return st;
+  BIND_OR_RETURN(ctx);
   if (d_ticks == nullptr) return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "null out pointer");
   if (microseconds == 0 || microseconds > 60ull * 1000 * 1000)
     return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "probe time outside (0, 60 s]");
@@ -2117,8 +2075,7 @@ cuking_status cuking_synth_bitset_model(cuking_ctx *ctx, int model, uint64_t see
                                         uint64_t *d_bit_set, void *stream) {
   if (model < 0 || model >= kNumSynthModels)
     return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "unknown synthetic cohort model %d", model);
-  cuking_status st = bind(ctx);
-  if (st != CUKING_OK) return st;
+  BIND_OR_RETURN(ctx);
   if (sample_end < sample_begin)
     return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "sample range reversed");
   if (words_per_sample != cuking_words_per_sample(num_sites))
@@ -2128,8 +2085,8 @@ cuking_status cuking_synth_bitset_model(cuking_ctx *ctx, int model, uint64_t see
   if (sample_end > sample_begin && (!d_kind || !d_pa || !d_pb || !d_bit_set))
     return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "null device pointer");
   if (sample_end == sample_begin || words_per_sample == 0) return CUKING_OK;
-  st = grow(ctx, &ctx->synth_tables, &ctx->synth_tables_bytes,
-            synth_table_bytes(sample_end - sample_begin, words_per_sample));
+  const cuking_status st = grow(ctx, &ctx->synth_tables, &ctx->synth_tables_bytes,
+                                synth_table_bytes(sample_end - sample_begin, words_per_sample));
   if (st != CUKING_OK) return st;
   const hipStream_t s = (hipStream_t)stream;
   if (ctx->synth_done == nullptr)
