@@ -1,11 +1,14 @@
 """Seeded random GPU-vs-oracle sweeps, shared by `pytest -m gpu`
 (tests/test_gpu_fuzz.py) and the command-line fuzzers (tools/fuzz_gpu.py,
-tools/fuzz_split.py, tools/stress_split.py) that run the same cases in bulk.
+tools/fuzz_reducing.py, tools/fuzz_split.py, tools/stress_split.py) that run the
+same cases in bulk.
 
 Every failure is reported as a reproducer: the generator function, its seed and
 the index of the case, plus the case's parameters -- `python tools/fuzz_gpu.py
-SEED CASES FIRST_CASE` replays it.  The checker is the CPU oracle
-(oracle/pyoracle.py); everything checked goes through the C ABI."""
+SEED CASES FIRST_CASE` replays it (run_reducing: `python tools/fuzz_reducing.py
+SEED CASES FIRST_CASE [SIZE_CLASS]`, the size class being the tag's `sweep`).
+The checker is the CPU oracle (oracle/pyoracle.py); everything checked goes
+through the C ABI."""
 from __future__ import annotations
 
 import itertools
@@ -189,6 +192,352 @@ def run_general(ctx, seed: int, cases: int, first_case: int = 0, log=None) -> in
     ctx.set_option("filter_check_min_steps", 64)
     ctx.set_option("filter_sort", 1)
     ctx.set_option("filter_lazy_codes", 1)
+    return ran
+
+
+# ---- the reducing calls: kin_matrix, kin_summary, relative_counts ---------------------------
+NUM_TILED_VARIANTS = 8            # (tests/test_gpu_kin_matrix.py test_variant_count pins it)
+STREAM_KERNEL = NUM_TILED_VARIANTS            # the matrix "variant" that stands for the stream kernel
+REDUCING_VARIANTS = (5, 6, 7)     # the only contexts kin_summary and relative_counts are served by
+SIZE_CLASSES = ("small", "tiles", "giveup")
+# (lo, hi, bins): the shipped default, a coarse one whose ends cut into the data, one bin,
+# hi above 0.5 (duplicates inside the bins), a power of two
+BIN_MENU = [(-1.0, 0.5, 1536), (-0.25, 0.25, 7), (-0.125, 0.375, 1), (0.0, 0.5001, 4096),
+            (-0.5, 0.5, 64)]
+# ascending; 0.5 is the kinship of the planted duplicate, 0.0 one that random pairs hit: the
+# strict `>` decides.  0.001 (class "small" only) sits inside the noise of unrelated pairs:
+# the filter variant gives up at once and the gated fallback computes the block
+THRESHOLD_MENU = [-0.5, 0.0, 0.0442, 0.0884, 0.177, 0.354, 0.45, 0.5]
+CALLS = ("run", "kin_matrix", "kin_summary", "relative_counts")
+# the shipped values of everything a case sets
+SHIPPED = dict(variant=7, counts_mode=-1, xcd_swizzle=2, band_rows=0, split_wgs=256,
+               dyn_tail_tiles=16384, max_launch_blocks=0, reuse_prepared=0,
+               filter_quadrant_cap=384, filter_cand_cap=1 << 25, filter_split_min_steps=8,
+               filter_check0=1, filter_check1=1, filter_check_emit=64, filter_rotate=1,
+               filter_rotate_min_steps=128, filter_rotate_min_tiles=2048,
+               filter_check_min_steps=64, filter_sort=1, filter_lazy_codes=1)
+
+
+def reducing_cases(seed: int, cases: int, first_case: int = 0, size_class=None):
+    """The cases of run_reducing, without a context: yields (tag, geno) -- the reproducer (every
+    parameter of the case) and the cohort's int8 [n, m] genotypes.  Every random number of a
+    case is drawn before the `first_case` skip: a seed names the same cases whatever is
+    skipped."""
+    from conftest import random_genotypes
+    if size_class is not None and size_class not in SIZE_CLASSES:
+        raise ValueError(f"size_class {size_class!r}: one of {SIZE_CLASSES} or None")
+    rng = np.random.default_rng(seed)
+    for case in range(cases):
+        n = int(rng.integers(2, 700))
+        m = int(rng.integers(1, 2500))
+        cls = "small"
+        if rng.random() < 0.15:   # enough tiles for the XCD-aware order (launches of >= 64 tiles)
+            cls = "tiles"
+        if rng.random() < 0.01 and cls == "small":
+            cls = "giveup"
+        cls = size_class or cls
+        n_tiles = int(rng.integers(1400, 2300))
+        # the filter variant's give-up decision: more tiles than CUs (> 23 x 23 tiles of 256
+        # samples) and a lowest threshold inside the noise of so few sites (run_general)
+        n_big, m_big = int(rng.integers(5900, 6600)), int(rng.integers(100, 200))
+        # enough k-steps for remainder pieces of the matrix-core kernels' k loop
+        pieces = rng.random() < 0.25
+        m_long = int(rng.integers(8000, 30000))
+        wgs = int(rng.choice([0, 256, 256]))
+        wgs_long = int(rng.choice([3, 6, 16]))
+        k = int(rng.integers(1, 4))
+        shard = int(rng.integers(0, k * (k + 1) // 2))
+        matrix_variant = int(rng.integers(0, NUM_TILED_VARIANTS + 1))
+        variant = int(rng.choice(REDUCING_VARIANTS))
+        filter_mostly = rng.random() < 0.75
+        mode = int(rng.integers(-1, 2))
+        if cls == "tiles":
+            n = n_tiles
+        elif cls == "giveup":
+            n, m, k, shard = n_big, m_big, 1, 0
+            if filter_mostly:
+                variant = 7
+        elif pieces:
+            m, wgs = m_long, wgs_long
+        missing = float(rng.choice([0.0, 0.02, 0.3]))
+        geno = random_genotypes(rng, n, m, missing=missing)
+        low_call = rng.random() < 0.3
+        who = rng.choice(n, size=max(1, n // 16), replace=False)
+        thin = rng.random((len(who), m)) < 0.4
+        if low_call:                 # a few low-call-rate samples (the sorted layout's case)
+            geno[who] = np.where(thin, -1, geno[who])
+        if n >= 5:
+            geno[1] = -1             # nothing defined: NaN with everybody
+            geno[2] = 0              # no het site: -inf
+        if n > 3:
+            geno[n - 1] = geno[0]    # a duplicate pair: 0.5
+        swizzle = int(rng.integers(0, 3))
+        band = int(rng.choice([0, 0, 1, 3, 5, 17]))
+        reuse = int(rng.integers(0, 2))
+        w = int(rng.integers(2, 6))
+        qcap = int(rng.choice([384, 384, 0, 2]))
+        ccap = int(rng.choice([1 << 20, 1 << 20, 0, 5]))
+        smin = int(rng.choice([8, 1, 1]))
+        chk0 = int(rng.choice([1, 0, 2, 2]))
+        chk1 = int(rng.choice([1, 0, 3, 5, 7, 9]))
+        srt, lazy = int(rng.integers(0, 3)), int(rng.integers(0, 2))
+        emit = int(rng.choice([64, 64, 0, 1, 255]))
+        rot = int(rng.choice([1, 0, 2, 2, 3 + int(rng.integers(0, 64))]))
+        dyn = int(rng.integers(0, 2))
+        blocks = int(rng.choice([0, 0, 3, 17]))
+        bins = BIN_MENU[int(rng.integers(0, len(BIN_MENU)))]
+        menu = list(THRESHOLD_MENU)
+        if cls == "small":
+            menu = sorted(menu + [0.001])
+        if cls == "giveup":          # (about one sigma out; every pair of 6,000 samples would
+            menu = [t for t in menu if t > 0.0884]    # not fit the record call's --max_results)
+        count = int(rng.integers(1, 9))
+        picked = rng.permutation(len(menu))[:min(count, len(menu))]
+        thresholds = sorted(menu[int(p)] for p in picked)
+        if cls == "giveup":
+            thresholds = [0.0884] + thresholds[:7]
+        symmetric = bool(rng.integers(0, 2))
+        pad = int(rng.choice([0, 1, 37]))
+        side_stream = bool(rng.random() < 0.3)
+        order = [CALLS[int(c)] for c in rng.permutation(len(CALLS))]
+        if case < first_case:
+            continue
+        tag = dict(fuzzer="run_reducing", seed=seed, case=case, sweep=size_class or "mixed",
+                   size_class=cls, n=n, m=m,
+                   split_factor=k, shard=shard, missing=missing, low_call=bool(low_call),
+                   matrix_variant="stream" if matrix_variant == STREAM_KERNEL else matrix_variant,
+                   variant=variant, counts_mode=mode, bins=bins, thresholds=thresholds,
+                   tile_ranges=w, symmetric=symmetric, out_pad=pad, side_stream=side_stream,
+                   order=order, xcd_swizzle=swizzle, band_rows=band, split_wgs=wgs,
+                   dyn_tail_tiles=dyn, max_launch_blocks=blocks, reuse_prepared=reuse,
+                   filter_quadrant_cap=qcap, filter_cand_cap=ccap, filter_split_min_steps=smin,
+                   filter_check0=chk0, filter_check1=chk1, filter_check_min_steps=4,
+                   filter_sort=srt, filter_lazy_codes=lazy, filter_check_emit=emit,
+                   filter_rotate=rot, filter_rotate_min_steps=4, filter_rotate_min_tiles=0)
+        yield tag, geno
+
+
+def reducing_tags(seed: int, cases: int, first_case: int = 0, size_class=None) -> list:
+    return [tag for tag, _ in reducing_cases(seed, cases, first_case, size_class)]
+
+
+def reducing_oracle(tag, geno):
+    """(oracle block, its bitset, ONE all_pairs call) of a case."""
+    from oracle import pyoracle
+    osm = pyoracle.submatrix(tag["n"], tag["split_factor"], tag["shard"])
+    bits = pyoracle.bitset_from_genotypes(geno, osm)
+    return osm, bits, pyoracle.all_pairs(osm, bits)
+
+
+def reducing_compared_share(seed: int, cases: int, size_class=None):
+    """(pairs of the sweep, those among them whose kinship is not NaN) from the generator and
+    the oracle alone: the share assert_same compares bit for bit."""
+    pairs = compared = 0
+    for tag, geno in reducing_cases(seed, cases, 0, size_class):
+        kin = reducing_oracle(tag, geno)[2][3]
+        pairs += kin.size
+        compared += int((~np.isnan(kin)).sum())
+    return pairs, compared
+
+
+def run_reducing(ctx, seed: int, cases: int, first_case: int = 0, log=None, size_class=None,
+                 stats=None) -> int:
+    """The three reducing calls and the record call, interleaved in a random order over one
+    bitset (and with reuse_prepared one prepared layout): shapes up to launches of >= 64 tiles
+    and more tiles than CUs, every block of a split, every option run_general draws plus the
+    launch shapes, bins, thresholds, tile ranges, a strided output, a side stream
+    (tools/fuzz_reducing.py).  Everything is compared exactly with what ONE oracle.all_pairs
+    call gives (tests/reducing_cases.py).  Returns the number of cases run; `stats`, a dict,
+    gains the sweep's `pairs`, `compared` (those whose kinship is not NaN: compared bit for
+    bit) and `giveup_dense_quadrants` (the filter_dense_quadrants counter's rise over the
+    relative_counts calls of the class "giveup")."""
+    import torch
+    import cuking_amd
+    import reducing_cases as rc
+    from cuking_amd.dist import tile_partition
+    from oracle import pyoracle
+    from test_gpu_kin_matrix import symmetric_expectation
+
+    stats = stats if stats is not None else {}
+    for key in ("pairs", "compared", "giveup_dense_quadrants"):
+        stats.setdefault(key, 0)
+    dev = f"cuda:{ctx.device}"
+    sentinel = float(rc.SENTINEL)
+    t0, ran = time.time(), 0
+    try:
+        for tag, geno in reducing_cases(seed, cases, first_case, size_class):
+            n, m, k, shard = tag["n"], tag["m"], tag["split_factor"], tag["shard"]
+            thresholds, bins, w = tag["thresholds"], tag["bins"], tag["tile_ranges"]
+            osm, bits, all_pairs = reducing_oracle(tag, geno)
+            block = osm.as_tuple()
+            exp = rc.expect_all(block, all_pairs, bins, thresholds)
+            oi, oj, kin = exp.pairs
+            stats["pairs"] += kin.size
+            stats["compared"] += int((~np.isnan(kin)).sum())
+            records, _, _ = pyoracle.compute(osm, bits, thresholds[0], threads=8)
+            above = int((kin > np.float32(thresholds[0])).sum())
+            if above != len(records):
+                raise FuzzMismatch(f"the oracle disagrees with itself: {above} pairs above "
+                                   f"{thresholds[0]}, {len(records)} records; {tag}")
+            suffix = exp.bands[:, ::-1].astype(np.uint64).cumsum(axis=1)[:, ::-1]
+            sm = cuking_amd.Submatrix(n, k, shard)
+            assert sm.as_tuple() == block
+            rows, cols, stored = sm.NumRows(), sm.NumCols(), sm.NumSamples()
+            diag = block[0] == block[2]
+            symmetric = tag["symmetric"] and diag
+
+            for key in SHIPPED:
+                if key != "variant":
+                    ctx.set_option(key, tag[key])
+            # (a new bitset may land on a recycled pointer: tell the library)
+            ctx.invalidate()
+            d_bits = (ctx.upload_bitset(bits) if bits.shape[0] else
+                      torch.zeros(2, dtype=torch.int64, device=dev))
+            wps = cuking_amd.words_per_sample(m)
+            stream = torch.cuda.Stream(dev) if tag["side_stream"] else torch.cuda.current_stream()
+            stream.wait_stream(torch.cuda.current_stream())
+
+            def fail(what, detail=""):
+                raise FuzzMismatch(f"{what}: {detail}; reproduce with {tag} (tools/fuzz_reducing.py "
+                                   f"{seed} {tag['case'] + 1} {tag['case']} {tag['sweep']})")
+
+            def host(t):
+                """After ONE wait for the case's stream, nothing else."""
+                stream.synchronize()
+                return t.cpu().numpy()
+
+            def select(variant):
+                if variant == "stream":
+                    ctx.set_kernel("stream")
+                else:
+                    ctx.set_kernel("tiled")
+                    ctx.set_option("variant", variant)
+
+            def ranges():
+                tiles = ctx.num_tiles(sm) if rows and cols else 0
+                return tile_partition(tiles, w) if tiles >= 2 else []
+
+            def matrix_into():
+                """(the prefilled buffer, its [rows, cols] view with a row pitch of its own)"""
+                buf = torch.full((rows, cols + tag["out_pad"]), sentinel, dtype=torch.float32,
+                                 device=dev)
+                return buf, buf[:, :cols]
+
+            def check_matrix(buf, want, what):
+                got = host(buf)
+                try:
+                    rc.assert_same(np.ascontiguousarray(got[:, :cols]), want, what)
+                except AssertionError as e:
+                    fail(what, str(e))
+                if not (got[:, cols:] == rc.SENTINEL).all():
+                    fail(what, "the padding columns of the strided output were written")
+
+            def call_run():
+                select(tag["variant"])
+                for rep in range(2 if tag["reuse_prepared"] else 1):   # the second call reuses the layout
+                    got = ctx.run(sm, wps, d_bits, thresholds[0])
+                    if got.tobytes() != records.tobytes():
+                        fail(f"run (rep {rep})", _diff(got, records))
+
+            def call_kin_matrix():
+                select(tag["matrix_variant"])
+                buf, out = matrix_into()
+                ctx.kin_matrix(sm, wps, d_bits, out=out, symmetric=symmetric, stream=stream)
+                want = exp.matrix
+                if symmetric:
+                    want = symmetric_expectation(exp.matrix, geno[block[0]:block[1]])
+                check_matrix(buf, want, f"kin_matrix (symmetric {symmetric})")
+                if tag["matrix_variant"] != "stream" and ranges():
+                    buf, out = matrix_into()
+                    for r in ranges():
+                        ctx.kin_matrix(sm, wps, d_bits, out=out, tile_range=r, stream=stream)
+                    check_matrix(buf, exp.matrix, f"kin_matrix, {w} tile ranges")
+
+            def check_summary(summary, pattern, times, what):
+                hist = host(summary.hist).view(np.uint64)
+                keys = host(summary.best).view(np.uint64)
+                added = hist - pattern
+                if not np.array_equal(added, times * exp.hist):
+                    fail(what, f"histogram differs at slots "
+                               f"{np.flatnonzero(added != times * exp.hist)[:8]}")
+                if int(added.sum()) != times * kin.size:
+                    fail(what, f"{int(added.sum())} pairs counted, the block has {kin.size}")
+                if not np.array_equal(keys, exp.keys):
+                    fail(what, f"keys differ at samples {np.flatnonzero(keys != exp.keys)[:8]}")
+                best_kin, partner = rc.decode_keys(keys)
+                nan = np.isnan(exp.best_kin)
+                if not (np.array_equal(partner, exp.best_partner) and np.isnan(best_kin[nan]).all()
+                        and np.array_equal(best_kin.view(np.uint32)[~nan],
+                                           exp.best_kin.view(np.uint32)[~nan])):
+                    fail(what, "nearest relatives differ")
+                api_kin, api_partner = summary.nearest()
+                if not (np.array_equal(api_partner, partner) and
+                        np.array_equal(api_kin.view(np.uint32), best_kin.view(np.uint32))):
+                    fail(what, "KinSummary.nearest() decodes the keys differently")
+
+            def call_kin_summary():
+                select(tag["variant"])
+                pattern = (np.arange(bins[2] + 3, dtype=np.uint64) * np.uint64(7) + np.uint64(3))
+                kw = dict(lo=bins[0], hi=bins[1], bins=bins[2], stream=stream)
+
+                def outputs():
+                    return (torch.from_numpy(pattern.view(np.int64).copy()).to(dev),
+                            torch.zeros(stored, dtype=torch.int64, device=dev))
+                hist, best = outputs()
+                summary = ctx.kin_summary(sm, wps, d_bits, hist=hist, best=best, **kw)
+                check_summary(summary, pattern, 1, "kin_summary")
+                if ranges():
+                    hist, best = outputs()
+                    for r in ranges():
+                        summary = ctx.kin_summary(sm, wps, d_bits, hist=hist, best=best,
+                                                  tile_range=r, **kw)
+                    check_summary(summary, pattern, 1, f"kin_summary, {w} tile ranges")
+
+            def check_counts(counts, times, what):
+                got = host(counts.counts).view(np.uint32).reshape(stored, len(thresholds))
+                if not np.array_equal(got, np.uint32(times) * exp.bands):
+                    fail(what, f"counts differ at (sample, band) "
+                               f"{np.argwhere(got != np.uint32(times) * exp.bands)[:8].tolist()}")
+                if not np.array_equal(counts.at_least(), np.uint64(times) * suffix):
+                    fail(what, "suffix sums differ")
+                if counts.num_records(0) != times * above:
+                    fail(what, f"num_records(0) {counts.num_records(0)}, the oracle has "
+                               f"{above} pairs above {thresholds[0]}")
+
+            def call_relative_counts():
+                select(tag["variant"])
+                giveup = tag["size_class"] == "giveup"
+                before = ctx.get_option("filter_dense_quadrants") if giveup else 0
+                out = torch.zeros((stored, len(thresholds)), dtype=torch.int32, device=dev)
+                counts = ctx.relative_counts(sm, wps, d_bits, thresholds=thresholds, out=out,
+                                             stream=stream)
+                check_counts(counts, 1, "relative_counts")
+                if giveup:
+                    stats["giveup_dense_quadrants"] += \
+                        ctx.get_option("filter_dense_quadrants") - before
+                ctx.relative_counts(sm, wps, d_bits, thresholds=thresholds, out=out, stream=stream)
+                check_counts(counts, 2, "relative_counts, a second call into the same tensor")
+                if ranges():
+                    out = torch.zeros((stored, len(thresholds)), dtype=torch.int32, device=dev)
+                    for r in ranges():
+                        counts = ctx.relative_counts(sm, wps, d_bits, thresholds=thresholds,
+                                                     out=out, tile_range=r, stream=stream)
+                    check_counts(counts, 1, f"relative_counts, {w} tile ranges")
+
+            calls = dict(run=call_run, kin_matrix=call_kin_matrix, kin_summary=call_kin_summary,
+                         relative_counts=call_relative_counts)
+            with torch.cuda.stream(stream):
+                for name in tag["order"]:
+                    calls[name]()
+            stream.synchronize()
+            ran += 1
+            if log and tag["case"] % 10 == 0:
+                log(f"run_reducing seed {seed} case {tag['case']} ok ({time.time() - t0:.0f}s)")
+    finally:
+        ctx.set_kernel("tiled")
+        for key, value in SHIPPED.items():
+            ctx.set_option(key, value)
+        ctx.invalidate()
     return ran
 
 

@@ -17,6 +17,17 @@ pytestmark = pytest.mark.gpu
 # box with 16 host threads (the CPU oracle is most of it)
 GENERAL = [(101, 500), (102, 500), (103, 500)]
 SPLIT = [(201, 100), (202, 100), (203, 100)]
+# run_reducing (kin_matrix, kin_summary, relative_counts and the record call interleaved), in
+# one session on one MI355X box in which the three general sweeps took 22, 30 and 23 s: the
+# mixed sweeps 20 s (seed 301: one case of the class "giveup" among them), 13 s and 10 s, the
+# sweep of launches of >= 64 tiles 13 s, the three cases with more tiles than CUs 10 s (the
+# oracle and the numpy expectations are most of it: 21 million pairs per case of that class)
+REDUCING = [(301, 120), (302, 120), (303, 120)]
+REDUCING_TILES = [(311, 30)]
+REDUCING_GIVEUP = [(321, 3)]
+# (what tests/test_reducing_cases.py checks on the CPU: the share of pairs compared bit for bit)
+REDUCING_SWEEPS = [(s, c, None) for s, c in REDUCING] + \
+    [(s, c, "tiles") for s, c in REDUCING_TILES] + [(s, c, "giveup") for s, c in REDUCING_GIVEUP]
 SCALE = float(os.environ.get("CUKING_FUZZ_SCALE", "1"))
 
 
@@ -38,6 +49,37 @@ def test_random_remainder_splits_ranges_and_staged_streams(ctx, seed, cases):
     ran = fuzz_cases.run_split(ctx, seed, max(1, int(cases * SCALE)), log=_log)
     print(f"run_split seed {seed}: {ran} cases OK in {time.time() - t0:.0f}s")
     assert ran == max(1, int(cases * SCALE))
+
+
+def _reducing_sweep(ctx, seed, cases, size_class):
+    """One run_reducing sweep: every case drawn was run, and at least 95 % of its pairs had a
+    kinship that is not NaN (the only entries assert_same does not compare bit for bit)."""
+    t0 = time.time()
+    cases, stats = max(1, int(cases * SCALE)), {}
+    ran = fuzz_cases.run_reducing(ctx, seed, cases, log=_log, size_class=size_class, stats=stats)
+    print(f"run_reducing seed {seed} ({size_class}): {ran} cases OK in {time.time() - t0:.0f}s, "
+          f"{stats['compared']} of {stats['pairs']} pairs compared bit for bit")
+    assert ran == cases
+    assert stats["pairs"] > 0 and stats["compared"] >= 0.95 * stats["pairs"], stats
+    return stats
+
+
+@pytest.mark.parametrize("seed,cases", REDUCING)
+def test_random_reducing_calls_interleaved(ctx, seed, cases):
+    _reducing_sweep(ctx, seed, cases, None)
+
+
+@pytest.mark.parametrize("seed,cases", REDUCING_TILES)
+def test_random_reducing_calls_launches_of_64_tiles(ctx, seed, cases):
+    _reducing_sweep(ctx, seed, cases, "tiles")
+
+
+@pytest.mark.parametrize("seed,cases", REDUCING_GIVEUP)
+def test_random_reducing_calls_more_tiles_than_cus(ctx, seed, cases):
+    """... and the filter variant's give-up path was really taken by a relative_counts call:
+    later tiles handed their quadrants to the four-product kernel's counting form."""
+    stats = _reducing_sweep(ctx, seed, cases, "giveup")
+    assert stats["giveup_dense_quadrants"] > 0, stats
 
 
 def test_one_staged_configuration_repeated(ctx):

@@ -19,6 +19,7 @@ import pytest
 import cuking_amd
 from cuking_amd import _lib
 from conftest import random_genotypes
+from reducing_cases import assert_same
 
 pytestmark = pytest.mark.gpu
 
@@ -76,19 +77,6 @@ def cohort(n, m, split_factor=1, shard_index=0, low_call=()):
     exp.setflags(write=False)
     bits.setflags(write=False)
     return bits, sm, exp
-
-
-def assert_same(got, exp, what=""):
-    """Bit-equal on the uint32 view; NaN where the expectation is NaN."""
-    assert got.shape == exp.shape and got.dtype == np.float32, what
-    nan = np.isnan(exp)
-    assert np.isnan(got[nan]).all(), f"{what}: a NaN entry of the oracle is not NaN"
-    bad = got.view(np.uint32)[~nan] != exp.view(np.uint32)[~nan]
-    if bad.any():
-        where = np.argwhere(~nan)[bad][0]
-        raise AssertionError(f"{what}: {int(bad.sum())} entries differ, first at "
-                             f"{tuple(where)}: got {got[tuple(where)]!r}, "
-                             f"expected {exp[tuple(where)]!r}")
 
 
 def prefilled(shape):

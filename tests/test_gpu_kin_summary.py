@@ -17,6 +17,7 @@ import pytest
 import cuking_amd
 from cuking_amd import _lib
 from conftest import random_genotypes
+from reducing_cases import histogram_of, nearest_of, slots_of
 
 pytestmark = pytest.mark.gpu
 
@@ -49,55 +50,6 @@ def make_genotypes(n, m, seed, low_call=()):
 
 
 # ---- the expectation, from the kinship of every pair ---------------------------------------
-def slots_of(kin, lo, hi, num_bins):
-    """The slot rule, vectorised: float32 operations, one rounding each."""
-    lo, hi, nb = f32(lo), f32(hi), f32(num_bins)
-    scale = f32(nb / f32(hi - lo))
-    with np.errstate(invalid="ignore", over="ignore"):
-        t = ((kin - lo).astype(f32) * scale).astype(f32)
-        inside = ~np.isnan(kin) & ~(kin < lo) & (t < nb)
-    slot = np.where(inside, 1 + np.where(inside, t, 0).astype(np.int64), num_bins + 1)
-    slot = np.where(kin < lo, 0, slot)
-    return np.where(np.isnan(kin), num_bins + 2, slot)
-
-
-def histogram_of(kin, lo, hi, num_bins):
-    return np.bincount(slots_of(kin, lo, hi, num_bins), minlength=num_bins + 3).astype(u64)
-
-
-def key_of(kin, partner):
-    bits = np.asarray(kin, dtype=f32).view(u32)
-    ordered = np.where(bits & u32(0x80000000), ~bits, bits ^ u32(0x80000000)).astype(u32)
-    key = (ordered.astype(u64) << u64(32)) | (~np.asarray(partner).astype(u32)).astype(u64)
-    return np.where(np.isnan(kin), u64(0), key)
-
-
-def nearest_of(sm, oi, oj, kin):
-    """Arg-max per stored sample of the block (rows first, then columns): the largest
-    kinship that is not NaN, the lowest partner among equals.  -> (kin, partner, keys)."""
-    i_begin, i_end, j_begin, j_end = sm
-    diag = i_begin == j_begin
-    rows = i_end - i_begin
-    count = rows if diag else rows + (j_end - j_begin)
-    off_i = oi - i_begin
-    off_j = oj - j_begin + (0 if diag else rows)
-    sample = np.concatenate([off_i, off_j]).astype(np.int64)
-    partner = np.concatenate([oj, oi]).astype(np.int64)
-    k = np.concatenate([kin, kin])
-    keep = ~np.isnan(k)
-    sample, partner, k = sample[keep], partner[keep], k[keep]
-    order = np.lexsort((partner, -k.astype(np.float64), sample))
-    sample, partner, k = sample[order], partner[order], k[order]
-    first = np.ones(sample.size, dtype=bool)
-    first[1:] = sample[1:] != sample[:-1]
-    best_kin = np.full(count, f32("nan"), dtype=f32)
-    best_partner = np.full(count, -1, dtype=np.int64)
-    best_kin[sample[first]] = k[first]
-    best_partner[sample[first]] = partner[first]
-    keys = np.where(best_partner >= 0, key_of(best_kin, np.maximum(best_partner, 0)), u64(0))
-    return best_kin, best_partner, keys
-
-
 @functools.lru_cache(maxsize=None)
 def cohort(n, m, split_factor=1, shard_index=0, low_call=()):
     """(bits of the block's samples, its ranges, (oi, oj, kin) of every pair).  Once per shape."""

@@ -16,6 +16,7 @@ import pytest
 
 import cuking_amd
 from cuking_amd import _lib
+from reducing_cases import bands_of, counts_of
 
 pytestmark = pytest.mark.gpu
 
@@ -66,28 +67,6 @@ def make_genotypes(n, m, seed, low_call=()):
 
 
 # ---- the expectation, from the kinship of every pair ---------------------------------------
-def bands_of(kin, thresholds):
-    """The band rule, vectorised: the largest t with kin > thresholds[t] (strict, float32;
-    ascending thresholds: the number of thresholds below kin, less one), -1 = none."""
-    thr = np.asarray(thresholds, dtype=f32)
-    with np.errstate(invalid="ignore"):
-        return (np.asarray(kin, dtype=f32)[:, None] > thr[None, :]).sum(axis=1) - 1
-
-
-def counts_of(sm, oi, oj, kin, thresholds):
-    """[stored samples of the block (rows first, then columns), T] uint32."""
-    i_begin, i_end, j_begin, j_end = sm
-    diag = i_begin == j_begin
-    rows = i_end - i_begin
-    count = rows if diag else rows + (j_end - j_begin)
-    band = bands_of(kin, thresholds)
-    keep = band >= 0
-    out = np.zeros((count, len(thresholds)), dtype=u32)
-    np.add.at(out, ((oi - i_begin)[keep], band[keep]), 1)
-    np.add.at(out, ((oj - j_begin + (0 if diag else rows))[keep], band[keep]), 1)
-    return out
-
-
 @functools.lru_cache(maxsize=None)
 def cohort(n, m, split_factor=1, shard_index=0, low_call=()):
     """(bits of the block's samples, its ranges, (oi, oj, kin) of every pair).  Once per shape."""
