@@ -6,7 +6,8 @@ same cases in bulk.
 Every failure is reported as a reproducer: the generator function, its seed and
 the index of the case, plus the case's parameters -- `python tools/fuzz_gpu.py
 SEED CASES FIRST_CASE` replays it (run_reducing: `python tools/fuzz_reducing.py
-SEED CASES FIRST_CASE [SIZE_CLASS]`, the size class being the tag's `sweep`).
+SEED CASES FIRST_CASE [SIZE_CLASS]`, the size class being the tag's `sweep`; run_pipeline:
+`python tools/fuzz_pipeline.py SEED CASES --first-case K --size-class CLASS`).
 The checker is the CPU oracle (oracle/pyoracle.py); everything checked goes
 through the C ABI."""
 from __future__ import annotations
@@ -537,6 +538,302 @@ def run_reducing(ctx, seed: int, cases: int, first_case: int = 0, log=None, size
         ctx.set_kernel("tiled")
         for key, value in SHIPPED.items():
             ctx.set_option(key, value)
+        ctx.invalidate()
+    return ran
+
+
+# ---- the input pipeline: bed, site QC, LD, unrelated set -------------------------------------
+GUARD64 = -0x5A5A5A5A5A5A5A5B          # 0xA5A5A5A5A5A5A5A5 as int64
+GUARD32 = -0x5A5A5A5B                  # 0xA5A5A5A5 as int32
+
+
+def run_pipeline(ctx, seed: int, cases: int, first_case: int = 0, log=None, size_class=None,
+                 stats=None) -> int:
+    """The calls in front of the pair kernels -- pack_bed, site_counts, sample_counts,
+    compact_sites, filter_sites, transpose_sites, ld_edges, ld_prune, unrelated_set, prune and a
+    pair-kernel call on the filtered bits -- 4 to 10 of them in a random order over one cohort,
+    each on a stream of a pool of 10 (the context keeps scratch for 8: entries are evicted) and
+    with a launch cap of its own (tools/fuzz_pipeline.py).  Every output is compared exactly,
+    guard words included, with the numpy expectation of tests/pipeline_cases.py and with the
+    library's host function.  The checks of the asynchronous calls wait until the case's last
+    call has been issued.  Returns the number of cases run; `stats`, a dict, gains the calls
+    per kind and `evictions`: a stream that returns after eight others were used since."""
+    import torch
+    import cuking_amd
+    import pipeline_cases as pc
+    from cuking_amd import api
+
+    stats = stats if stats is not None else {}
+    for key in pc.KINDS + ("evictions",):
+        stats.setdefault(key, 0)
+    dev = f"cuda:{ctx.device}"
+    pool = [torch.cuda.Stream(dev) for _ in range(pc.NUM_STREAMS)]
+    recent = []                        # streams by last use, the latest last
+    t0, ran = time.time(), 0
+
+    def touch(index):
+        if index in recent:
+            stats["evictions"] += len(recent) - 1 - recent.index(index) >= pc.MAX_STREAMS
+            recent.remove(index)
+        recent.append(index)
+
+    def host_records(t, count):
+        return cuking_amd.sort_results(_records(t, count))
+
+    def device_records(recs, rng):
+        words = np.ascontiguousarray(recs[rng.permutation(len(recs))]).view(np.int32)
+        return torch.from_numpy(words.reshape(-1, 6).copy()).to(dev)
+
+    try:
+        for tag, geno in pc.pipeline_cases(seed, cases, first_case, size_class):
+            n, m = geno.shape
+            wps = cuking_amd.words_per_sample(m)
+            q = cuking_amd.ld_site_words(n)
+            bits = pc.pack(geno)
+            host_site_bits = None
+            ctx.invalidate()
+            d_bits = ctx.upload_bitset(bits)
+            torch.cuda.synchronize()
+            pending = []
+            result = dict(bits=d_bits, wps=wps, stream=None)    # of filter_sites / ld_prune
+            edges = None               # the current LD edges on the device: (tensor, count)
+
+            for number, (call, e) in enumerate(zip(tag["calls"], pc.expect_calls(tag, geno))):
+                kind, stream = call["kind"], pool[call["stream"]]
+
+                def fail(what, call=call, number=number):
+                    raise FuzzMismatch(
+                        f"{call['kind']} (call {number}): {what}; {call}; reproduce with "
+                        f"n={n} m={m} cohort={tag['cohort']} (tools/fuzz_pipeline.py {seed} "
+                        f"{tag['case'] + 1} --first-case {tag['case']} --size-class "
+                        f"{tag['sweep']})")
+
+                def same(got, want, what, fail=fail):
+                    if got.shape != want.shape or got.tobytes() != want.tobytes():
+                        where = (np.argwhere(got != want)[:4].tolist()
+                                 if got.shape == want.shape else [got.shape, want.shape])
+                        fail(f"{what} differs at {where}")
+
+                def later(stream, whole, lo, hi, want, what, guard, same=same, fail=fail):
+                    """Once the case's calls are issued: rows [lo, hi) of `whole` equal `want`,
+                    the rows around them still hold the guard."""
+                    def check():
+                        stream.synchronize()
+                        host = whole.cpu().numpy()
+                        if not ((host[:lo] == guard).all() and (host[hi:] == guard).all()):
+                            fail(f"{what}: guard words were written")
+                        same(host[lo:hi].view(want.dtype).reshape(want.shape), want, what)
+                    pending.append(check)
+
+                def transposed():
+                    nonlocal host_site_bits
+                    if host_site_bits is None:
+                        host_site_bits = pc.site_bits_numpy(geno)
+                    return host_site_bits
+
+                touch(call["stream"])
+                stats[kind] += 1
+                ctx.set_option("max_launch_blocks", call["max_launch_blocks"])
+                with torch.cuda.stream(stream):
+                    if kind == "pack_bed":
+                        sm = cuking_amd.Submatrix(n, call["split"], call["shard"])
+                        stored, rows = sm.NumSamples(), e["rows"]
+                        rb = rows.shape[1]
+                        want = np.full((stored, wps), np.uint64(0xA5A5A5A5A5A5A5A5), np.uint64)
+                        for begin, end in e["chunks"]:
+                            cuking_amd.pack_bed_host(sm, want, rows[begin:end], rb, begin, end, m)
+                        same(want, e["bits"], "pack_bed_host against the numpy decode")
+                        whole = torch.full((stored + 2, wps), GUARD64, dtype=torch.int64,
+                                           device=dev)
+                        buf = torch.zeros(call["offset"] + rows.size, dtype=torch.uint8, device=dev)
+                        d_rows = buf[call["offset"]:]
+                        d_rows.copy_(torch.from_numpy(rows.reshape(-1)))
+                        stream.synchronize()
+                        for (begin, end), s in zip(e["chunks"], call["chunk_streams"]):
+                            touch(s)
+                            ctx.pack_bed(sm, wps, d_rows[begin * rb:end * rb], rb, begin, end, m,
+                                         whole[1:stored + 1], stream=pool[s])
+                        for s in call["chunk_streams"]:
+                            stream.wait_stream(pool[s])
+                        later(stream, whole, 1, stored + 1, e["bits"], "the bitset", GUARD64)
+                    elif kind == "site_counts":
+                        slots = wps // 2 * 64
+                        whole = torch.full((slots + 16, 4), GUARD32, dtype=torch.int32, device=dev)
+                        whole[:slots] = 0
+                        stream.synchronize()
+                        last = stream
+                        for (begin, end), s in zip(call["ranges"], call["range_streams"]):
+                            last.synchronize()     # one `out`, two streams: in turn
+                            last = pool[s] if s >= 0 else stream
+                            if s >= 0:
+                                touch(s)
+                            ctx.site_counts(d_bits[begin:end], wps, out=whole[:slots], stream=last)
+                        later(last, whole, 0, slots, e["counts"], "site counts", GUARD32)
+                    elif kind == "sample_counts":
+                        whole = torch.full((n + 2, 4), GUARD32, dtype=torch.int32, device=dev)
+                        ctx.sample_counts(d_bits, wps, m, out=whole[1:n + 1], stream=stream)
+                        later(stream, whole, 1, n + 1, e["counts"], "sample counts", GUARD32)
+                    elif kind == "compact_sites":
+                        words = cuking_amd.site_mask_words(e["keep"])
+                        want, want_wps, want_kept = cuking_amd.compact_sites_host(bits, wps, words, m)
+                        same(want, e["bits"], "compact_sites_host against pack(geno[:, keep])")
+                        if call["guarded"]:
+                            whole = torch.full((n + 2, want_wps), GUARD64, dtype=torch.int64,
+                                               device=dev)
+                            _, got_wps, kept = ctx.compact_sites(d_bits, wps, words, m,
+                                                                 out=whole[1:n + 1], stream=stream)
+                            later(stream, whole, 1, n + 1, e["bits"], "compacted bits", GUARD64)
+                        else:
+                            out, got_wps, kept = ctx.compact_sites(d_bits, wps, words, m,
+                                                                   stream=stream)
+                            later(stream, out, 0, n, e["bits"], "compacted bits", GUARD64)
+                        if (got_wps, kept) != (want_wps, want_kept):
+                            fail(f"words_per_sample, kept {(got_wps, kept)}")
+                    elif kind == "filter_sites":
+                        args = (call["min_call_rate"], call["min_maf"], call["min_mac"], e["also"])
+                        words, _ = cuking_amd.site_mask_host(pc.site_counts_numpy(geno, wps // 2),
+                                                             m, *args)
+                        same(cuking_amd.site_mask_bool(words, m), e["keep"],
+                             "site_mask_host against rule_numpy")
+                        try:
+                            qc = ctx.filter_sites(d_bits, wps, m, *args, stream=stream)
+                        except cuking_amd.CukingError as err:
+                            if not (e["fails"] and "no site passes" in str(err)):
+                                fail(f"raised {err}")
+                        else:
+                            if e["fails"]:
+                                fail("no site passes, but no error")
+                            same(qc.keep(), e["keep"], "kept sites")
+                            same(qc.counts(), e["counts"], "site counts")
+                            if (qc.num_sites, qc.words_per_sample) != \
+                                    (int(e["keep"].sum()), e["bits"].shape[1]):
+                                fail(f"num_sites, words_per_sample "
+                                     f"{(qc.num_sites, qc.words_per_sample)}")
+                            later(stream, qc.bits, 0, n, e["bits"], "filtered bits", GUARD64)
+                            result = dict(bits=qc.bits, wps=qc.words_per_sample, stream=stream)
+                    elif kind == "transpose_sites":
+                        same(cuking_amd.transpose_sites_host(bits, wps, m), e["site_bits"],
+                             "transpose_sites_host against site_bits_numpy")
+                        whole = torch.full((m + 2, 2, q), GUARD64, dtype=torch.int64, device=dev)
+                        ctx.transpose_sites(d_bits, wps, m, out=whole[1:m + 1], stream=stream)
+                        later(stream, whole, 1, m + 1, e["site_bits"], "site-major bits", GUARD64)
+                    elif kind == "ld_edges":
+                        want, count = cuking_amd.ld_edges_host(transposed(), m, n, call["window"],
+                                                               call["r2"], group=e["group"])
+                        same(want, e["edges"], "ld_edges_host against ld_edges_fast")
+                        site_bits = ctx.transpose_sites(d_bits, wps, m, stream=stream)
+                        group = None if e["group"] is None else \
+                            torch.from_numpy(e["group"]).to(dev)
+                        kw = dict(window=call["window"], r2=call["r2"], group=group, stream=stream)
+                        if e["room"] is None:
+                            records, got = ctx.ld_edges(site_bits, m, n, **kw)
+                            if got != count:
+                                fail(f"{got} edges, not {count}")
+                            same(host_records(records, got), e["edges"], "edges")
+                            edges = (records, got)
+                        else:
+                            room = e["room"]
+                            whole = torch.full((room + 8, 6), GUARD32, dtype=torch.int32,
+                                               device=dev)
+                            try:
+                                _, got = ctx.ld_edges(site_bits, m, n, out=whole[:room], **kw)
+                            except cuking_amd.ResourceExhaustedError as err:
+                                if not e["exhausted"] or err.num_records != count:
+                                    fail(f"ResourceExhaustedError, num_records {err.num_records}, "
+                                         f"{count} edges, room {room}")
+                                got = room
+                            else:
+                                if e["exhausted"] or got != count:
+                                    fail(f"{got} edges in a buffer of {room}, not {count}")
+                            host = whole.cpu().numpy()
+                            if not (host[room:] == GUARD32).all():
+                                fail("guard records were written")
+                            stored = host_records(whole, got)
+                            if e["exhausted"]:
+                                have = {r.tobytes() for r in stored}
+                                if len(have) != room or not have <= {r.tobytes() for r in e["edges"]}:
+                                    fail("the stored records are no subset of the edges")
+                                edges = None
+                            else:
+                                same(stored, e["edges"], "edges")
+                                edges = (whole[:room], got)
+                    elif kind == "ld_prune":
+                        keep, _ = api.unrelated_set_host(e["edges"], m, priority=e["used"],
+                                                         families=False)
+                        same(keep == 1, e["keep"], "unrelated_set_host against greedy_numpy")
+                        priority = e["priority"]
+                        if priority is not None and call["place"] == "device":
+                            priority = torch.from_numpy(priority).to(dev)
+                        got = ctx.ld_prune(d_bits, wps, m, window=call["window"], r2=call["r2"],
+                                           group=e["group"], priority=priority,
+                                           compact=call["compact"])
+                        if got.num_edges != len(e["edges"]):
+                            fail(f"{got.num_edges} edges, not {len(e['edges'])}")
+                        same(got.edges(), e["edges"], "edges")
+                        same(got.keep(), e["keep"], "kept sites")
+                        if e["bits"] is None:
+                            if got.bits is not d_bits or (got.words_per_sample, got.num_sites) != \
+                                    (wps, m):
+                                fail("the input bits were to come back")
+                        else:
+                            if (got.num_sites, got.words_per_sample) != \
+                                    (int(e["keep"].sum()), e["bits"].shape[1]):
+                                fail(f"num_sites, words_per_sample "
+                                     f"{(got.num_sites, got.words_per_sample)}")
+                            later(stream, got.bits, 0, n, e["bits"], "pruned bits", GUARD64)
+                        result = dict(bits=got.bits, wps=got.words_per_sample, stream=stream)
+                    elif kind in ("unrelated_set", "prune"):
+                        keep, family = api.unrelated_set_host(e["records"], e["count"], e["thr"],
+                                                              priority=e["priority"])
+                        same(keep, e["keep"], "unrelated_set_host's keep against the yardstick")
+                        same(family, e["family"], "unrelated_set_host's family")
+                        priority = None if e["priority"] is None else \
+                            torch.from_numpy(e["priority"]).to(dev)
+                        if kind == "prune":
+                            got = ctx.prune(cuking_amd.Submatrix(n), wps, d_bits, e["thr"],
+                                            priority=priority, families=call["families"])
+                        else:
+                            if e["source"] == "edges" and edges is not None and \
+                                    edges[1] == len(e["records"]):
+                                records = edges[0]      # where ld_edges left them
+                            else:
+                                records = device_records(e["records"],
+                                                         np.random.default_rng(call["seed"]))
+                            got = ctx.unrelated_set(records, len(e["records"]), e["count"], e["thr"],
+                                                    priority=priority, families=call["families"],
+                                                    stream=stream)
+                        same(got.keep.cpu().numpy(), e["keep"], "keep")
+                        if call["families"]:
+                            same(got.family.cpu().numpy().view(np.uint32), e["family"], "family")
+                        elif got.family is not None:
+                            fail("families=False returned a family vector")
+                    elif kind == "pair":
+                        if result["stream"] is not None:
+                            stream.wait_stream(result["stream"])
+                        sm = cuking_amd.Submatrix(n)
+                        ctx.invalidate()
+                        if call["call"] == "run":
+                            got = ctx.run(sm, result["wps"], result["bits"], call["thr"])
+                            if got.tobytes() != e["records"].tobytes():
+                                fail(_diff(got, e["records"]))
+                        else:
+                            out = ctx.kin_matrix(sm, result["wps"], result["bits"], symmetric=True,
+                                                 stream=stream)
+                            stream.synchronize()
+                            try:
+                                import reducing_cases
+                                reducing_cases.assert_same(out.cpu().numpy(), e["matrix"],
+                                                           "kin_matrix")
+                            except AssertionError as err:
+                                fail(str(err))
+            for check in pending:
+                check()
+            torch.cuda.synchronize()
+            ran += 1
+            if log and tag["case"] % 10 == 0:
+                log(f"run_pipeline seed {seed} case {tag['case']} ok ({time.time() - t0:.0f}s)")
+    finally:
+        ctx.set_option("max_launch_blocks", 0)
         ctx.invalidate()
     return ran
 

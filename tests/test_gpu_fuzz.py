@@ -28,6 +28,16 @@ REDUCING_GIVEUP = [(321, 3)]
 # (what tests/test_reducing_cases.py checks on the CPU: the share of pairs compared bit for bit)
 REDUCING_SWEEPS = [(s, c, None) for s, c in REDUCING] + \
     [(s, c, "tiles") for s, c in REDUCING_TILES] + [(s, c, "giveup") for s, c in REDUCING_GIVEUP]
+# run_pipeline (bed, site QC, LD and unrelated-set calls interleaved on a pool of 10 streams), in
+# one session on one MI355X box in which the three mixed run_reducing sweeps took 20, 12 and
+# 10 s: the three sweeps of the class "small" 2 s each, the one around the sample boundaries
+# 1 s, the one around the site boundaries 3 s (numpy and the oracle are most of it)
+PIPELINE = [(401, 200), (402, 200), (403, 200)]
+PIPELINE_SAMPLES = [(411, 40)]
+PIPELINE_SITES = [(421, 40)]
+# (what tests/test_pipeline_cases.py holds to its conditions on the CPU)
+PIPELINE_SWEEPS = [(s, c, "small") for s, c in PIPELINE] + \
+    [(s, c, "samples") for s, c in PIPELINE_SAMPLES] + [(s, c, "sites") for s, c in PIPELINE_SITES]
 SCALE = float(os.environ.get("CUKING_FUZZ_SCALE", "1"))
 
 
@@ -80,6 +90,35 @@ def test_random_reducing_calls_more_tiles_than_cus(ctx, seed, cases):
     later tiles handed their quadrants to the four-product kernel's counting form."""
     stats = _reducing_sweep(ctx, seed, cases, "giveup")
     assert stats["giveup_dense_quadrants"] > 0, stats
+
+
+def _pipeline_sweep(ctx, seed, cases, size_class):
+    """One run_pipeline sweep: every case drawn was run, every kind of call at least once, and
+    a stream came back after the context had given its scratch entry to another."""
+    import pipeline_cases
+    t0 = time.time()
+    cases, stats = max(1, int(cases * SCALE)), {}
+    ran = fuzz_cases.run_pipeline(ctx, seed, cases, log=_log, size_class=size_class, stats=stats)
+    print(f"run_pipeline seed {seed} ({size_class}): {ran} cases OK in {time.time() - t0:.0f}s, "
+          f"{stats}")
+    assert ran == cases
+    assert all(stats[kind] > 0 for kind in pipeline_cases.KINDS), stats
+    assert stats["evictions"] > 0, stats
+
+
+@pytest.mark.parametrize("seed,cases", PIPELINE)
+def test_random_pipeline_calls_interleaved(ctx, seed, cases):
+    _pipeline_sweep(ctx, seed, cases, "small")
+
+
+@pytest.mark.parametrize("seed,cases", PIPELINE_SAMPLES)
+def test_random_pipeline_calls_sample_boundaries(ctx, seed, cases):
+    _pipeline_sweep(ctx, seed, cases, "samples")
+
+
+@pytest.mark.parametrize("seed,cases", PIPELINE_SITES)
+def test_random_pipeline_calls_site_boundaries(ctx, seed, cases):
+    _pipeline_sweep(ctx, seed, cases, "sites")
 
 
 def test_one_staged_configuration_repeated(ctx):
