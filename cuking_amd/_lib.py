@@ -28,6 +28,10 @@ KIN_BINS_MAX = 4096
 REL_THRESHOLDS_MAX = 8
 REL_NO_BAND = 0xFFFFFFFF
 
+GENO_RHS_MAX = 64
+GENO_TABLE_PER_COLUMN = 0
+GENO_TABLE_PER_ROW = 1
+
 
 class CKinBins(C.Structure):
     """cuking_kin_bins: the histogram of a kinship summary."""
@@ -158,6 +162,10 @@ SIGNATURES = {
                                     C.POINTER(_u64)]),
     "cuking_ld_edges": (_int, [_vp, _vp, _u32, _u32, _u32, _f32, _vp, _vp, _u64,
                                C.POINTER(_u64), _vp]),
+    "cuking_geno_matmul_host": (_int, [_vp, _u32, _u32, _u32, _vp, _int, _vp, _u32, _u32, _vp,
+                                       _u32]),
+    "cuking_geno_matmul": (_int, [_vp, _vp, _u32, _u32, _u32, _vp, _int, _vp, _u32, _u32, _vp,
+                                  _u32, _vp]),
     "cuking_sort_results": (None, [_vp, _sz]),
     "cuking_timing_enable": (_int, [_vp, _int]),
     "cuking_timing_reset": (_int, [_vp]),

@@ -293,6 +293,48 @@ def ld_edges_host(site_bits: np.ndarray, num_sites: int, num_stored: int, window
     return sort_results(recs[:count.value].copy()), int(count.value)
 
 
+def _geno_host_matrix(a, name: str, min_rows: int, cols=None) -> np.ndarray:
+    """A float32 host matrix whose rows are contiguous (a pitch between rows is fine)."""
+    if not isinstance(a, np.ndarray) or a.dtype != np.float32 or a.ndim != 2 or \
+            (a.shape[1] > 1 and a.strides[1] != 4) or a.strides[0] % 4 or \
+            (a.shape[0] > 1 and a.strides[0] < 4 * a.shape[1]):
+        raise ValueError(f"{name} must be a float32 [rows, cols] array with contiguous rows")
+    if a.shape[0] < min_rows or cols is not None and a.shape[1] != cols:
+        raise ValueError(f"{name} must have at least {min_rows} rows"
+                         f"{'' if cols is None else f' of {cols} columns'}, not {a.shape}")
+    return a
+
+
+def geno_matmul_host(bits: np.ndarray, words_per_row: int, num_cols: int, table, rhs,
+                     per_row: bool = False, out=None) -> np.ndarray:
+    """cuking_geno_matmul_host: ``out[r, c] = sum_k table[r or k, code(r, k)] * rhs[k, c]`` over
+    the columns ``k < num_cols`` of the host bitset ``[rows, words_per_row]`` (a row is its het
+    words, then its hom_var words; code 0 hom-ref, 1 het, 2 hom-var, 3 missing), accumulated in
+    double and rounded once: the specification of ``KingContext.geno_matmul`` in executable
+    form.  ``table``: float32 ``[num_cols, 4]``, or ``[rows, 4]`` with ``per_row``; ``rhs``:
+    float32 ``[num_cols, num_rhs]``; ``out``: float32 ``[rows, num_rhs]`` to write into (both
+    may be column slices of wider arrays: their row pitch is passed on)."""
+    assert bits.dtype == np.uint64 and bits.flags.c_contiguous
+    words_per_row, num_cols = _count(words_per_row, "words_per_row"), _count(num_cols, "num_cols")
+    rows = bits.size // words_per_row if words_per_row else 0
+    table = _geno_host_matrix(table, "table", rows if per_row else num_cols, 4)
+    if not table.flags.c_contiguous:
+        raise ValueError("table must be contiguous")
+    rhs = _geno_host_matrix(rhs, "rhs", num_cols)
+    num_rhs = rhs.shape[1]
+    if out is None:
+        out = np.empty((rows, num_rhs), dtype=np.float32)
+    _geno_host_matrix(out, "out", rows, num_rhs)
+    pad = np.zeros(4, dtype=np.float32)
+    check(_lib.load().cuking_geno_matmul_host(
+        (bits if bits.size else pad).ctypes.data, rows, words_per_row, num_cols,
+        (table if table.size else pad).ctypes.data,
+        _lib.GENO_TABLE_PER_ROW if per_row else _lib.GENO_TABLE_PER_COLUMN,
+        (rhs if rhs.size else pad).ctypes.data, max(rhs.strides[0] // 4, num_rhs), num_rhs,
+        (out if out.size else pad).ctypes.data, max(out.strides[0] // 4, num_rhs)))
+    return out
+
+
 def ld_priority_host(counts, num_sites: int) -> np.ndarray:
     """cuking_ld_priority per site: float32 ``[num_sites]`` from the ``[64 P, 4]`` site counts
     -- the minor allele frequency among the called genotypes, NaN without one (ranked last)."""
@@ -992,6 +1034,62 @@ class KingContext:
             torch.cuda.synchronize(self.device)
         return LDPrune(keep_words, num_sites, bits, wps, sites, records, count, chosen.rounds)
 
+    # -- genotype matrix products, PCA ------------------------------------------
+    def _geno_matrix(self, t, name: str, min_rows: int, cols=None):
+        import torch
+        _device_tensor(self.device, t, name, torch.float32, contiguous=False)
+        # (the strides of an empty tensor say nothing)
+        if t.dim() != 2 or t.numel() and ((t.shape[1] > 1 and t.stride(1) != 1) or
+                                          (t.shape[0] > 1 and t.stride(0) < t.shape[1])):
+            raise ValueError(f"{name} must be a [rows, cols] tensor with contiguous rows")
+        if t.shape[0] < min_rows or cols is not None and t.shape[1] != cols:
+            raise ValueError(f"{name} must have at least {min_rows} rows"
+                             f"{'' if cols is None else f' of {cols} columns'}, "
+                             f"not {tuple(t.shape)}")
+        return t
+
+    def geno_matmul(self, bits, words_per_row: int, num_cols: int, table, rhs,
+                    per_row: bool = False, out=None, stream=None):
+        """The 2-bit genotype matrix times a dense float32 matrix (cuking_geno_matmul), the
+        genotypes never expanded: ``out[r, c] = sum_k table[r or k, code(r, k)] * rhs[k, c]``
+        over the columns ``k < num_cols`` of ``bits`` (``[rows, words_per_row]``: a row is its
+        het words, then its hom_var words; code 0 hom-ref, 1 het, 2 hom-var, 3 missing).  The
+        sample-major bitset with a per-column ``table`` (float32 ``[num_cols, 4]``) gives ``Z
+        B``; ``transpose_sites`` of it, as ``[num_sites, 2 Q]`` with ``num_cols`` = the samples
+        and ``per_row`` (``table`` ``[rows, 4]``), gives ``Z^T A``.  ``rhs``: float32
+        ``[num_cols, num_rhs <= 64]``; ``out``: float32 ``[rows, num_rhs]``, overwritten (both
+        may be column slices of wider tensors).  Exact for integer tables and ``rhs`` while the
+        sums stay below 2^24; the same bits on every call.  Does not synchronise."""
+        import torch
+        rows = self._rows_of(bits, words_per_row)
+        num_cols = _count(num_cols, "num_cols")
+        table = self._geno_matrix(table, "table", rows if per_row else num_cols, 4)
+        if not table.is_contiguous():
+            raise ValueError("table must be contiguous")
+        rhs = self._geno_matrix(rhs, "rhs", num_cols)
+        num_rhs = rhs.shape[1]
+        if out is None:
+            out = torch.empty((rows, num_rhs), dtype=torch.float32, device=f"cuda:{self.device}")
+        self._geno_matrix(out, "out", rows, num_rhs)
+        check(self.lib.cuking_geno_matmul(
+            self.handle, bits.data_ptr(), rows, words_per_row, num_cols, table.data_ptr(),
+            _lib.GENO_TABLE_PER_ROW if per_row else _lib.GENO_TABLE_PER_COLUMN,
+            rhs.data_ptr(), max(rhs.stride(0), num_rhs), num_rhs, out.data_ptr(),
+            max(out.stride(0), num_rhs), _stream_handle(stream)))
+        return out
+
+    def pca(self, bits, words_per_sample: int, num_sites: int, k: int = 10, fit=None,
+            oversample: int = 10, iterations: int = 10, seed: int = 0):
+        """Principal components of the standardized genotype matrix (cuking_amd/pca.py has the
+        definition): fitted on the rows of ``bits`` that the boolean mask ``fit`` (host or
+        device, one entry per row, e.g. ``UnrelatedSet.keep``; None = all) selects, every row
+        projected.  ``site_counts`` of the fit rows, ``hwe_table``, ``transpose_sites``, then
+        randomized subspace iteration whose only contact with the genotypes is
+        ``geno_matmul``.  Returns a ``PCAResult`` of host arrays.  Waits for the device."""
+        from . import pca as _pca
+        return _pca.pca_device(self, bits, words_per_sample, num_sites, k=k, fit=fit,
+                               oversample=oversample, iterations=iterations, seed=seed)
+
     def synth_bitset(self, seed: int, kind, pa, pb, sample_begin: int,
                      sample_end: int, num_sites: int, out=None, stream=None, model=0):
         """Synthetic reference-layout bitset rows [sample_begin, sample_end)
@@ -1320,6 +1418,7 @@ __all__ = [
     "words_per_sample", "bytes_per_pair", "new_host_bitset", "pack_host", "pack_bed_host",
     "site_mask_host", "site_mask_words", "site_mask_bool", "compact_sites_host", "SiteQC",
     "ld_site_words", "transpose_sites_host", "ld_edges_host", "ld_priority_host", "LDPrune",
+    "geno_matmul_host",
     "sort_results", "device_count", "synth_models", "synth_model_number",
     "DEFAULT_KIN_THRESHOLD",
     "DEFAULT_MAX_RESULTS",

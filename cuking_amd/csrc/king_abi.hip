@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "king_common.h"
+#include "king_geno.h"
 #include "king_host.h"
 #include "king_kin_summary.h"
 #include "king_ld.h"
@@ -2020,6 +2021,26 @@ cuking_status cuking_ld_edges(cuking_ctx *ctx, const uint64_t *d_site_bits, uint
   HIP_TRY(hipStreamSynchronize(s));
   *num_records = count;
   return cuking_ld_count_status(count, max_records);
+}
+
+// ---- genotype matrix products (king_geno.hip) -------------------------------
+
+cuking_status cuking_geno_matmul(cuking_ctx *ctx, const uint64_t *d_bits, uint32_t num_rows,
+                                 uint32_t words_per_row, uint32_t num_cols, const float *d_table,
+                                 int table_axis, const float *d_b, uint32_t ldb, uint32_t num_rhs,
+                                 float *d_out, uint32_t ldo, void *stream) {
+  // (the arguments first: a refused call touches no device)
+  if (ctx == nullptr) return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "null context");
+  const cuking_status st = cuking_check_geno_args(d_bits, num_rows, words_per_row, num_cols,
+                                                  d_table, table_axis, d_b, ldb, num_rhs, d_out,
+                                                  ldo);
+  if (st != CUKING_OK) return st;
+  if (num_rows == 0) return CUKING_OK;
+  BIND_OR_RETURN(ctx);
+  HIP_TRY(launch_geno_matmul(d_bits, num_rows, words_per_row, num_cols, d_table,
+                             table_axis == kGenoTablePerRow, d_b, ldb, num_rhs, d_out, ldo,
+                             (hipStream_t)stream));
+  return CUKING_OK;
 }
 
 // ---- timing ---------------------------------------------------------------

@@ -653,6 +653,13 @@ hipError_t launch_ld_edges(const uint64_t *d_site_bits, uint32_t num_sites, uint
                            cuking_result *d_records, uint64_t max_records,
                            unsigned long long *d_count, hipStream_t stream);
 
+// Genotype matrix products (king_geno.hip; arguments already checked, king_host.h).  Plain
+// stores into d_out[r][0 .. num_rhs) of every row; num_cols == 0 stores zeros.
+hipError_t launch_geno_matmul(const uint64_t *d_bits, uint32_t num_rows, uint32_t words_per_row,
+                              uint32_t num_cols, const float *d_table, bool per_row,
+                              const float *d_b, uint32_t ldb, uint32_t num_rhs, float *d_out,
+                              uint32_t ldo, hipStream_t stream);
+
 // Cohort models of the synthetic generator (synth.hip holds the specification).  d_tables:
 // synth_table_bytes() of scratch the launch fills and reads (per-site and per-sample
 // tables); it must stay untouched until the launch has run.

@@ -18,6 +18,7 @@
 
 #include "../host/schedule.h"
 #include "king_submatrix.h"
+#include "king_geno.h"
 #include "king_kin_summary.h"
 #include "king_ld.h"
 #include "king_unrelated.h"
@@ -613,6 +614,65 @@ cuking_status cuking_ld_edges_host(const uint64_t *site_bits, uint32_t num_sites
   }
   *num_records = count;
   return cuking_ld_count_status(count, max_records);
+}
+
+}  // extern "C"
+
+// ---- genotype matrix products: the argument checks and the host twin ------------------------
+cuking_status cuking_check_geno_args(const void *bits, uint32_t num_rows, uint32_t words_per_row,
+                                     uint32_t num_cols, const void *table, int table_axis,
+                                     const void *b, uint32_t ldb, uint32_t num_rhs,
+                                     const void *out, uint32_t ldo) {
+  if (words_per_row == 0 || words_per_row % 2 != 0)
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT,
+                       "geno matmul: words_per_row (%u) must be positive and even", words_per_row);
+  if (num_cols > 64ull * (words_per_row / 2))
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT,
+                       "geno matmul: %u columns do not fit %u plane words (%llu bits)", num_cols,
+                       words_per_row / 2, 64ull * (words_per_row / 2));
+  if (num_rhs == 0 || num_rhs > kGenoRhsMax)
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT,
+                       "geno matmul: num_rhs (%u) must be in [1, %u]", num_rhs, kGenoRhsMax);
+  if (ldb < num_rhs || ldo < num_rhs)
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT,
+                       "geno matmul: pitches ldb (%u) and ldo (%u) must be at least num_rhs (%u)",
+                       ldb, ldo, num_rhs);
+  if (!geno_axis_valid(table_axis))
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT,
+                       "geno matmul: unknown table axis %d (per column %d, per row %d)",
+                       table_axis, kGenoTablePerColumn, kGenoTablePerRow);
+  if (num_rows == 0) return CUKING_OK;
+  if (out == nullptr)
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "geno matmul: null out pointer");
+  if (num_cols != 0 && (bits == nullptr || table == nullptr || b == nullptr))
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "geno matmul: null pointer");
+  return CUKING_OK;
+}
+
+extern "C" {
+
+cuking_status cuking_geno_matmul_host(const uint64_t *bits, uint32_t num_rows,
+                                      uint32_t words_per_row, uint32_t num_cols,
+                                      const float *table, int table_axis, const float *b,
+                                      uint32_t ldb, uint32_t num_rhs, float *out, uint32_t ldo) {
+  const cuking_status st = cuking_check_geno_args(bits, num_rows, words_per_row, num_cols, table,
+                                                  table_axis, b, ldb, num_rhs, out, ldo);
+  if (st != CUKING_OK) return st;
+  const uint32_t plane_words = words_per_row / 2;
+  const bool per_row = table_axis == kGenoTablePerRow;
+  std::vector<double> acc(num_rhs);
+  for (uint64_t r = 0; r < num_rows; ++r) {
+    std::fill(acc.begin(), acc.end(), 0.0);
+    const uint64_t *row = num_cols != 0 ? bits + r * words_per_row : nullptr;
+    for (uint64_t k = 0; k < num_cols; ++k) {
+      const uint32_t code = geno_code(row[k >> 6], row[plane_words + (k >> 6)], (uint32_t)(k & 63));
+      const double t = (double)table[(per_row ? r : k) * 4 + code];
+      const float *bk = b + k * ldb;
+      for (uint32_t c = 0; c < num_rhs; ++c) acc[c] += t * (double)bk[c];
+    }
+    for (uint32_t c = 0; c < num_rhs; ++c) out[r * ldo + c] = (float)acc[c];
+  }
+  return CUKING_OK;
 }
 
 }  // extern "C"

@@ -36,5 +36,11 @@ cuking_status cuking_check_ld_args(const void *site_bits, uint32_t num_stored, u
                                    float r2_threshold, const void *records, uint64_t max_records,
                                    const void *num_records);
 cuking_status cuking_ld_count_status(uint64_t count, uint64_t max_records);
+// Argument checks of cuking_geno_matmul_host / cuking_geno_matmul (include/cuking_amd.h
+// "Genotype matrix products" lists them); OK says nothing about there being work to do.
+cuking_status cuking_check_geno_args(const void *bits, uint32_t num_rows, uint32_t words_per_row,
+                                     uint32_t num_cols, const void *table, int table_axis,
+                                     const void *b, uint32_t ldb, uint32_t num_rhs,
+                                     const void *out, uint32_t ldo);
 
 #endif  // CUKING_AMD_KING_HOST_H_

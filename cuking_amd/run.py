@@ -133,6 +133,17 @@ def parse_args(argv=None):
     flag("site-ld-uri", default="",
          help="LD pruning: also write its report to this .npz file (keep over the sites that "
               "entered the pruning, kept_index in input-site numbering, num_edges, window, r2)")
+    flag("pca-uri", default="",
+         help="also write the principal components of the standardized genotypes -- fitted on "
+              "the samples --pca-fit selects, EVERY sample projected, on the bitset site QC and "
+              "LD pruning left (cuking_amd/pca.py) -- to this .npz file (eigenvalues, scores, "
+              "loadings, allele_freq, sites_used, fit, samples).  One process and "
+              "--split-factor 1 only")
+    flag("pca-components", type=int, default=None,
+         help="the number of components of --pca-uri (default 10)")
+    flag("pca-fit", default="",
+         help="the samples the components of --pca-uri are fitted on: all (default) or "
+              "unrelated, the kept samples of this run's --unrelated-uri")
     return ap.parse_args(argv)
 
 
@@ -240,6 +251,22 @@ def validate(args):  # cuking.cu:437-462
             raise UsageError("--site_ld_window, --site_ld_r2 and --site_ld_uri need "
                              "--split_factor 1: r^2 is taken over the whole cohort's samples")
     ld_rule(args)
+    if (args.pca_components is not None or args.pca_fit) and not args.pca_uri:
+        raise UsageError("--pca_components and --pca_fit need --pca_uri")
+    if args.pca_uri:
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            raise UsageError("--pca_uri needs one process (one GPU): the products are not "
+                             "merged across ranks yet")
+        if args.split_factor != 1:
+            raise UsageError("--pca_uri needs --split_factor 1: the components are fitted on the "
+                             "whole cohort's bitset")
+        if args.pca_fit not in ("", "all", "unrelated"):
+            raise UsageError("--pca_fit expects all or unrelated")
+        if args.pca_fit == "unrelated" and not args.unrelated_uri:
+            raise UsageError("--pca_fit unrelated needs the unrelated set of the same run: pass "
+                             "--unrelated_uri as well")
+        if args.pca_components is not None and args.pca_components < 1:
+            raise UsageError("--pca_components must be at least 1")
 
 
 def ld_pruning(args) -> bool:
@@ -393,10 +420,11 @@ def write_relative_counts(path: Path, ctx, sm, wps: int, bits, thresholds, sampl
 
 
 def write_unrelated(path: Path, ctx, recs: np.ndarray, sample_ids, threshold: float,
-                    priority_path, device: int) -> None:
+                    priority_path, device: int) -> np.ndarray:
     """The unrelated set and the families of the records' graph as an .npz: per sample of the
     cohort (`samples` names them) `keep` (1 = stays) and `family` (the lowest index of its
-    connected component), and the `threshold` above which a record was an edge."""
+    connected component), and the `threshold` above which a record was an edge.  Returns
+    `keep`."""
     import torch
     n = len(sample_ids)
     priority = None
@@ -410,10 +438,24 @@ def write_unrelated(path: Path, ctx, recs: np.ndarray, sample_ids, threshold: fl
     records = torch.from_numpy(words).to(f"cuda:{device}")
     got = ctx.unrelated_set(records, len(recs), n, threshold, priority=priority)
     path.parent.mkdir(parents=True, exist_ok=True)
+    keep = got.keep.cpu().numpy()
     with open(path, "wb") as f:   # (np.savez would append .npz to another suffix)
-        np.savez(f, keep=got.keep.cpu().numpy(),
-                 family=got.family.cpu().numpy().view(np.uint32),
+        np.savez(f, keep=keep, family=got.family.cpu().numpy().view(np.uint32),
                  samples=np.array(list(sample_ids), dtype=str), threshold=np.float32(threshold))
+    return keep
+
+
+def write_pca(path: Path, ctx, bits, wps: int, num_sites: int, components: int, fit,
+              sample_ids) -> None:
+    """The principal components as an .npz: `eigenvalues` [k], `scores` [samples, k],
+    `loadings` [sites, k], `allele_freq` and `sites_used` [sites] (of the sites QC and pruning
+    left), `fit` [samples] (the samples the components were fitted on) and `samples`."""
+    got = ctx.pca(bits, wps, num_sites, k=components, fit=fit)
+    path.parent.mkdir(parents=True, exist_ok=True)
+    with open(path, "wb") as f:   # (np.savez would append .npz to another suffix)
+        np.savez(f, eigenvalues=got.eigenvalues, scores=got.scores, loadings=got.loadings,
+                 allele_freq=got.allele_freq, sites_used=got.sites_used, fit=got.fit,
+                 samples=np.array(list(sample_ids), dtype=str))
 
 
 def site_qc(ctx, args, bits, wps: int, num_sites: int, sample_ids, keep_path, qc_path):
@@ -489,6 +531,7 @@ def main(argv=None) -> int:
         site_keep_path = resolve_uri(args.site_keep_uri) if args.site_keep_uri else None
         site_qc_path = resolve_uri(args.site_qc_uri) if args.site_qc_uri else None
         site_ld_path = resolve_uri(args.site_ld_uri) if args.site_ld_uri else None
+        pca_path = resolve_uri(args.pca_uri) if args.pca_uri else None
         synthetic = None
         if args.synthetic:
             parts = [int(x) for x in args.synthetic.split(",")]
@@ -639,9 +682,16 @@ def main(argv=None) -> int:
             if counts_path is not None:
                 write_relative_counts(counts_path, ctx, sm, wps, bits,
                                       relative_thresholds(args.relative_thresholds), sample_ids)
+            unrelated_keep = None
             if unrelated_path is not None:
-                write_unrelated(unrelated_path, ctx, recs, sample_ids, unrelated_threshold(args),
-                                priority_path, local_rank)
+                unrelated_keep = write_unrelated(unrelated_path, ctx, recs, sample_ids,
+                                                 unrelated_threshold(args), priority_path,
+                                                 local_rank)
+            if pca_path is not None:
+                fit = unrelated_keep == 1 if args.pca_fit == "unrelated" else None
+                write_pca(pca_path, ctx, bits[:stored], wps, num_sites,
+                          10 if args.pca_components is None else args.pca_components, fit,
+                          sample_ids)
             pairs = sm.NumPairs()
             print(json.dumps({"pairs": pairs, "results": int(len(recs)), "gpus": world,
                               "compute_seconds": dt,

@@ -845,6 +845,56 @@ cuking_status cuking_ld_edges(cuking_ctx *ctx, const uint64_t *d_site_bits, uint
                               const int32_t *d_group, cuking_result *d_records,
                               uint64_t max_records, uint64_t *num_records, void *stream);
 
+/* Genotype matrix products: the 2-bit genotype matrix times a dense float32 matrix, without
+ * ever expanding the genotypes -- what randomized PCA (cuking_amd/pca.py), projection and
+ * association scans need from the big data.  csrc/king_geno.h holds the decode as code shared
+ * by host, device and tests.
+ *
+ *     bits   uint64 [num_rows][words_per_row]; words_per_row even, W = words_per_row / 2; a row
+ *            is [W het words | W hom_var words]; column k = bit k & 63 of word k >> 6;
+ *            num_cols <= 64 W
+ *     code(r,k)  0 hom-ref (00), 1 het (het bit only), 2 hom-var (hom_var bit only), 3 missing
+ *            (both bits) -- the order of cuking_site_counts
+ *     table  float32 [num_cols][4] with CUKING_GENO_TABLE_PER_COLUMN,
+ *            float32 [num_rows][4] with CUKING_GENO_TABLE_PER_ROW
+ *     B      float32 [num_cols][ldb]
+ *     out    float32 [num_rows][ldo]; 1 <= num_rhs <= CUKING_GENO_RHS_MAX; ldb, ldo >= num_rhs
+ *     out[r][c] = sum over k < num_cols of table(r or k)[code(r,k)] * B[k][c],  c < num_rhs
+ *
+ * Both bitsets fit with no conversion: the sample-major one with num_cols = num_sites and a
+ * per-column table (Z B), and the site-major planes of cuking_transpose_sites with
+ * words_per_row = 2 Q, num_cols = num_stored and a per-row table (Z^T A; the tail bits there
+ * read as missing).  Columns at or beyond num_cols contribute nothing, whatever their bits
+ * hold.  out[r][0 .. num_rhs) is OVERWRITTEN with plain stores; the elements between num_rhs
+ * and ldo are left alone.  cuking_geno_matmul is asynchronous on `stream`.
+ *
+ * Numerics (inputs finite): the result differs from the real-number sum by at most
+ * (num_cols + 2) 2^-24 sum_k |table B| -- the bound of a float32 accumulation of num_cols terms
+ * in any order with one rounding per product and per addition.  The device adds in ascending k
+ * with one fused multiply-add per term (the f32-input MFMA of gfx950); the host twin accumulates
+ * in double and rounds once.  So when every table entry and every B entry is an integer and
+ * sum_k |table B| < 2^24, the result is EXACT, on both.  The same inputs give the same bits on
+ * every call, stream and launch: one workgroup owns an output row over the whole k range, there
+ * are no atomics, no partial sums and no split of k.
+ *
+ * INVALID_ARGUMENT before any device is touched: words_per_row zero or odd; num_cols > 64 W;
+ * num_rhs 0 or above CUKING_GENO_RHS_MAX; ldb or ldo below num_rhs; an unknown table axis; and,
+ * with work to do, a null pointer (out when num_rows != 0; bits, table, B when num_cols != 0 as
+ * well).  num_rows == 0 returns OK without work; num_cols == 0 writes zeros.
+ * Out of scope: the C++ `cuking` binary; several ranks; the N x N relationship matrix;
+ * half-precision operands; a row gather as part of the call. */
+#define CUKING_GENO_RHS_MAX 64
+#define CUKING_GENO_TABLE_PER_COLUMN 0
+#define CUKING_GENO_TABLE_PER_ROW 1
+cuking_status cuking_geno_matmul_host(const uint64_t *bits, uint32_t num_rows,
+                                      uint32_t words_per_row, uint32_t num_cols,
+                                      const float *table, int table_axis, const float *b,
+                                      uint32_t ldb, uint32_t num_rhs, float *out, uint32_t ldo);
+cuking_status cuking_geno_matmul(cuking_ctx *ctx, const uint64_t *d_bits, uint32_t num_rows,
+                                 uint32_t words_per_row, uint32_t num_cols, const float *d_table,
+                                 int table_axis, const float *d_b, uint32_t ldb, uint32_t num_rhs,
+                                 float *d_out, uint32_t ldo, void *stream);
+
 /* cuking.cu:761-765 on host memory: sort by (sample_i, sample_j, kin). */
 void cuking_sort_results(cuking_result *results, size_t num_results);
 
