@@ -17,5 +17,7 @@ from .api import (DEFAULT_KIN_THRESHOLD, DEFAULT_MAX_RESULTS,  # noqa: F401
                   padded_sites, sort_results, synth_model_number, synth_models,
                   words_per_sample)
 from .pca import PCAResult, hwe_table, pca_host  # noqa: F401
+from .pcrelate import (PCRelateResult, isaf_fit, pcrelate_host,  # noqa: F401
+                       pcrelate_matrix_host)
 
 __version__ = "0.1.0"

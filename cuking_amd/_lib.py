@@ -32,6 +32,8 @@ GENO_RHS_MAX = 64
 GENO_TABLE_PER_COLUMN = 0
 GENO_TABLE_PER_ROW = 1
 
+PCRELATE_COLUMNS_MAX = 32
+
 
 class CKinBins(C.Structure):
     """cuking_kin_bins: the histogram of a kinship summary."""
@@ -166,6 +168,10 @@ SIGNATURES = {
                                        _u32]),
     "cuking_geno_matmul": (_int, [_vp, _vp, _u32, _u32, _u32, _vp, _int, _vp, _u32, _u32, _vp,
                                   _u32, _vp]),
+    "cuking_pcrelate_matrix_host": (_int, [_vp, _u32, _u32, _u32, _vp, _u32, _vp, _u32, _u32,
+                                           _f32, _f32, _SM, _vp, _u64]),
+    "cuking_pcrelate_matrix": (_int, [_vp, _vp, _u32, _u32, _u32, _vp, _u32, _vp, _u32, _u32,
+                                      _f32, _f32, _SM, _vp, _u64, _vp]),
     "cuking_sort_results": (None, [_vp, _sz]),
     "cuking_timing_enable": (_int, [_vp, _int]),
     "cuking_timing_reset": (_int, [_vp]),

@@ -1090,6 +1090,35 @@ class KingContext:
         return _pca.pca_device(self, bits, words_per_sample, num_sites, k=k, fit=fit,
                                oversample=oversample, iterations=iterations, seed=seed)
 
+    def pcrelate_matrix(self, bits, words_per_sample: int, num_sites: int, x, beta, lo: float,
+                        hi: float, block=None, out=None, stream=None):
+        """The bare PC-Relate kernel call (cuking_pcrelate_matrix; include/cuking_amd.h
+        "PC-Relate" has the definition): the float32 kinship ``num / (4 den)`` of every pair of
+        ``block`` (a ``Submatrix`` or ``(i_begin, i_end, j_begin, j_end)`` over the rows of
+        ``bits``; None = all) as a ``[rows, cols]`` device tensor, from ``x`` float32
+        ``[num_stored, d <= 32]`` (column 0 the intercept), ``beta`` float32 ``[>= num_sites,
+        d]`` and the bounds ``lo < mu < hi``.  ``out``: a float32 tensor of that shape to write
+        into, possibly a view with a row pitch of its own.  The same bytes on every call and
+        stream; ``[i, j]`` and ``[j, i]`` are the same bytes.  Does not synchronise."""
+        from . import pcrelate as _pcr
+        return _pcr.pcrelate_matrix_device(self, bits, words_per_sample, num_sites, x, beta,
+                                           float(lo), float(hi), block, out, stream)
+
+    def pcrelate(self, bits, words_per_sample: int, num_sites: int, scores, fit=None,
+                 min_maf: float = 0.01, block=None, out=None, stream=None):
+        """PC-Relate (cuking_amd/pcrelate.py has the definition): the ancestry-adjusted kinship
+        of every pair of ``block`` (None = the whole cohort).  ``scores``: float32
+        ``[num_stored, k]`` on host or device, e.g. ``PCAResult.scores[:, :k]``; ``fit``: the
+        boolean mask of the rows the allele-frequency model is fitted on (None = all), e.g.
+        ``PCAResult.fit``.  ``site_counts`` and ``transpose_sites`` of the fit rows, one
+        ``geno_matmul`` for the per-site regression on ``[1, scores]``, a ``d x d`` solve in
+        float64, then ``pcrelate_matrix`` with the bounds ``min_maf < mu < 1 - min_maf``.
+        Returns a ``PCRelateResult`` whose ``kin`` is a device tensor; the fit waits for the
+        device, the matrix call does not."""
+        from . import pcrelate as _pcr
+        return _pcr.pcrelate_device(self, bits, words_per_sample, num_sites, scores, fit=fit,
+                                    min_maf=min_maf, block=block, out=out, stream=stream)
+
     def synth_bitset(self, seed: int, kind, pa, pb, sample_begin: int,
                      sample_end: int, num_sites: int, out=None, stream=None, model=0):
         """Synthetic reference-layout bitset rows [sample_begin, sample_end)

@@ -2043,6 +2043,27 @@ cuking_status cuking_geno_matmul(cuking_ctx *ctx, const uint64_t *d_bits, uint32
   return CUKING_OK;
 }
 
+// ---- PC-Relate (king_pcrelate.hip) -------------------------------------------
+
+cuking_status cuking_pcrelate_matrix(cuking_ctx *ctx, const uint64_t *d_bits, uint32_t num_stored,
+                                     uint32_t words_per_sample, uint32_t num_sites,
+                                     const float *d_x, uint32_t ldx, const float *d_beta,
+                                     uint32_t ldbeta, uint32_t d, float lo, float hi,
+                                     const cuking_submatrix *block, float *d_out, uint64_t ldo,
+                                     void *stream) {
+  // (the arguments first: a refused call touches no device)
+  if (ctx == nullptr) return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "null context");
+  const cuking_status st = cuking_check_pcrelate_args(d_bits, num_stored, words_per_sample,
+                                                      num_sites, d_x, ldx, d_beta, ldbeta, d, lo,
+                                                      hi, block, d_out, ldo);
+  if (st != CUKING_OK) return st;
+  if (sm_num_rows(*block) == 0 || sm_num_cols(*block) == 0) return CUKING_OK;
+  BIND_OR_RETURN(ctx);
+  HIP_TRY(launch_pcrelate_matrix(d_bits, words_per_sample, num_sites, d_x, ldx, d_beta, ldbeta, d,
+                                 lo, hi, *block, d_out, ldo, (hipStream_t)stream));
+  return CUKING_OK;
+}
+
 // ---- timing ---------------------------------------------------------------
 
 cuking_status cuking_timing_enable(cuking_ctx *ctx, int enabled) {

@@ -660,6 +660,14 @@ hipError_t launch_geno_matmul(const uint64_t *d_bits, uint32_t num_rows, uint32_
                               const float *d_b, uint32_t ldb, uint32_t num_rhs, float *d_out,
                               uint32_t ldo, hipStream_t stream);
 
+// PC-Relate (king_pcrelate.hip; arguments already checked, king_host.h).  Plain stores into
+// d_out[i - i_begin][j - j_begin] of every pair of `block`; num_sites == 0 stores NaN.
+hipError_t launch_pcrelate_matrix(const uint64_t *d_bits, uint32_t words_per_sample,
+                                  uint32_t num_sites, const float *d_x, uint32_t ldx,
+                                  const float *d_beta, uint32_t ldbeta, uint32_t d, float lo,
+                                  float hi, const cuking_submatrix &block, float *d_out,
+                                  uint64_t ldo, hipStream_t stream);
+
 // Cohort models of the synthetic generator (synth.hip holds the specification).  d_tables:
 // synth_table_bytes() of scratch the launch fills and reads (per-site and per-sample
 // tables); it must stay untouched until the launch has run.

@@ -21,6 +21,7 @@
 #include "king_geno.h"
 #include "king_kin_summary.h"
 #include "king_ld.h"
+#include "king_pcrelate.h"
 #include "king_unrelated.h"
 
 using namespace cuking;
@@ -50,7 +51,9 @@ cuking_status cuking_check_block(const cuking_submatrix *sm,
                           uint32_t words_per_sample) {
   if (sm == nullptr) return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "null submatrix");
   if (sm->i_end < sm->i_begin || sm->j_end < sm->j_begin)
-    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "submatrix ranges are reversed");
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT,
+                       "submatrix ranges are reversed: rows [%u, %u) x columns [%u, %u)",
+                       sm->i_begin, sm->i_end, sm->j_begin, sm->j_end);
   if (!sm_is_diag(*sm) && sm->j_begin < sm->i_end && sm_num_rows(*sm) != 0 &&
       sm_num_cols(*sm) != 0)
     return cuking_fail(CUKING_ERR_INVALID_ARGUMENT,
@@ -61,7 +64,7 @@ cuking_status cuking_check_block(const cuking_submatrix *sm,
                 "a diagonal block needs identical row and column ranges");
   if (words_per_sample == 0 || (words_per_sample & 1))
     return cuking_fail(CUKING_ERR_INVALID_ARGUMENT,
-                "words_per_sample must be a positive even number");
+                "words_per_sample (%u) must be a positive even number", words_per_sample);
   return CUKING_OK;
 }
 
@@ -672,6 +675,99 @@ cuking_status cuking_geno_matmul_host(const uint64_t *bits, uint32_t num_rows,
     }
     for (uint32_t c = 0; c < num_rhs; ++c) out[r * ldo + c] = (float)acc[c];
   }
+  return CUKING_OK;
+}
+
+}  // extern "C"
+
+// ---- PC-Relate: the argument checks and the host twin ---------------------------------------
+cuking_status cuking_check_pcrelate_args(const void *bits, uint32_t num_stored,
+                                         uint32_t words_per_sample, uint32_t num_sites,
+                                         const void *x, uint32_t ldx, const void *beta,
+                                         uint32_t ldbeta, uint32_t d, float lo, float hi,
+                                         const cuking_submatrix *block, const void *out,
+                                         uint64_t ldo) {
+  const cuking_status st = cuking_check_block(block, words_per_sample);
+  if (st != CUKING_OK) return st;
+  if (d == 0 || d > kPcrelateColumnsMax)
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "pcrelate: d (%u) must be in [1, %u]", d,
+                       kPcrelateColumnsMax);
+  if (ldx < d || ldbeta < d)
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT,
+                       "pcrelate: pitches ldx (%u) and ldbeta (%u) must be at least d (%u)", ldx,
+                       ldbeta, d);
+  if (num_sites > 64ull * (words_per_sample / 2))
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT,
+                       "pcrelate: %u sites do not fit %u plane words (%llu bits)", num_sites,
+                       words_per_sample / 2, 64ull * (words_per_sample / 2));
+  if (!pcrelate_bounds_valid(lo, hi))
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT,
+                       "pcrelate: bounds lo = %g, hi = %g are not 0 <= lo < hi <= 1", (double)lo,
+                       (double)hi);
+  if (block->i_end > num_stored || block->j_end > num_stored)
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT,
+                       "pcrelate: block rows [%u, %u) x columns [%u, %u) outside the %u stored "
+                       "samples", block->i_begin, block->i_end, block->j_begin, block->j_end,
+                       num_stored);
+  if (ldo < sm_num_cols(*block))
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT,
+                       "pcrelate: output pitch %llu below the block's %u columns",
+                       (unsigned long long)ldo, sm_num_cols(*block));
+  if (sm_num_rows(*block) == 0 || sm_num_cols(*block) == 0) return CUKING_OK;
+  if (out == nullptr)
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "pcrelate: null out pointer");
+  if (num_sites != 0 && (bits == nullptr || x == nullptr || beta == nullptr))
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "pcrelate: null pointer");
+  return CUKING_OK;
+}
+
+extern "C" {
+
+cuking_status cuking_pcrelate_matrix_host(const uint64_t *bits, uint32_t num_stored,
+                                          uint32_t words_per_sample, uint32_t num_sites,
+                                          const float *x, uint32_t ldx, const float *beta,
+                                          uint32_t ldbeta, uint32_t d, float lo, float hi,
+                                          const cuking_submatrix *block, float *out,
+                                          uint64_t ldo) {
+  const cuking_status st = cuking_check_pcrelate_args(bits, num_stored, words_per_sample,
+                                                      num_sites, x, ldx, beta, ldbeta, d, lo, hi,
+                                                      block, out, ldo);
+  if (st != CUKING_OK) return st;
+  const uint32_t rows = sm_num_rows(*block), cols = sm_num_cols(*block);
+  if (rows == 0 || cols == 0) return CUKING_OK;
+  const uint32_t plane_words = words_per_sample / 2;
+  // r and v of the block's samples, [sample][site]: rows first, then columns
+  const auto expand = [&](uint32_t begin, uint32_t count, std::vector<float> *r,
+                          std::vector<float> *v) {
+    r->assign((size_t)count * num_sites, 0.0f);
+    v->assign((size_t)count * num_sites, 0.0f);
+    for (uint32_t k = 0; k < count; ++k) {
+      const uint64_t sample = (uint64_t)begin + k;
+      const uint64_t *row = bits + sample * words_per_sample;
+      for (uint64_t s = 0; s < num_sites; ++s) {
+        const uint32_t code = geno_code(row[s >> 6], row[plane_words + (s >> 6)], (uint32_t)(s & 63));
+        const float mu = pcrelate_mu(x + sample * ldx, beta + s * ldbeta, d);
+        pcrelate_element(code, mu, lo, hi, &(*r)[(size_t)k * num_sites + s],
+                         &(*v)[(size_t)k * num_sites + s]);
+      }
+    }
+  };
+  std::vector<float> ri, vi, rj, vj;
+  expand(block->i_begin, rows, &ri, &vi);
+  const bool diag = sm_is_diag(*block);
+  if (!diag) expand(block->j_begin, cols, &rj, &vj);
+  const std::vector<float> &rc = diag ? ri : rj, &vc = diag ? vi : vj;
+  for (uint32_t i = 0; i < rows; ++i)
+    for (uint32_t j = 0; j < cols; ++j) {
+      double num = 0.0, den = 0.0;
+      const float *a = ri.data() + (size_t)i * num_sites, *b = rc.data() + (size_t)j * num_sites;
+      const float *p = vi.data() + (size_t)i * num_sites, *q = vc.data() + (size_t)j * num_sites;
+      for (uint32_t s = 0; s < num_sites; ++s) {
+        num += (double)a[s] * (double)b[s];
+        den += (double)p[s] * (double)q[s];
+      }
+      out[(uint64_t)i * ldo + j] = pcrelate_kin((float)num, (float)den);
+    }
   return CUKING_OK;
 }
 

@@ -42,5 +42,13 @@ cuking_status cuking_check_geno_args(const void *bits, uint32_t num_rows, uint32
                                      uint32_t num_cols, const void *table, int table_axis,
                                      const void *b, uint32_t ldb, uint32_t num_rhs,
                                      const void *out, uint32_t ldo);
+// Argument checks of cuking_pcrelate_matrix_host / cuking_pcrelate_matrix (include/cuking_amd.h
+// "PC-Relate" lists them); OK says nothing about there being work to do.
+cuking_status cuking_check_pcrelate_args(const void *bits, uint32_t num_stored,
+                                         uint32_t words_per_sample, uint32_t num_sites,
+                                         const void *x, uint32_t ldx, const void *beta,
+                                         uint32_t ldbeta, uint32_t d, float lo, float hi,
+                                         const cuking_submatrix *block, const void *out,
+                                         uint64_t ldo);
 
 #endif  // CUKING_AMD_KING_HOST_H_

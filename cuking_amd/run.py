@@ -144,6 +144,17 @@ def parse_args(argv=None):
     flag("pca-fit", default="",
          help="the samples the components of --pca-uri are fitted on: all (default) or "
               "unrelated, the kept samples of this run's --unrelated-uri")
+    flag("pcrelate-uri", default="",
+         help="also write the PC-Relate kinship matrix of the whole cohort -- ancestry-adjusted "
+              "with the scores and the fit of this run's --pca-uri (cuking_amd/pcrelate.py) -- to "
+              "this float32 .npy file [samples, samples].  Needs --pca-uri; one process and "
+              "--split-factor 1 only")
+    flag("pcrelate-components", type=int, default=None,
+         help="the number of leading components --pcrelate-uri adjusts for (default: all of "
+              "--pca-components; at most 31)")
+    flag("pcrelate-min-maf", type=float, default=None,
+         help="--pcrelate-uri uses the elements whose individual-specific allele frequency "
+              "lies strictly between this and 1 minus this (default 0.01)")
     return ap.parse_args(argv)
 
 
@@ -267,6 +278,42 @@ def validate(args):  # cuking.cu:437-462
                              "--unrelated_uri as well")
         if args.pca_components is not None and args.pca_components < 1:
             raise UsageError("--pca_components must be at least 1")
+    if (args.pcrelate_components is not None or args.pcrelate_min_maf is not None) and \
+            not args.pcrelate_uri:
+        raise UsageError("--pcrelate_components and --pcrelate_min_maf need --pcrelate_uri")
+    if args.pcrelate_uri:
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            raise UsageError("--pcrelate_uri needs one process (one GPU): the matrix is not "
+                             "assembled across ranks yet")
+        if args.split_factor != 1:
+            raise UsageError("--pcrelate_uri needs --split_factor 1: it writes the whole "
+                             "cohort's matrix")
+        if not args.pca_uri:
+            raise UsageError("--pcrelate_uri needs the principal components of the same run: "
+                             "pass --pca_uri as well")
+        pca_k = 10 if args.pca_components is None else args.pca_components
+        k = pcrelate_components(args)
+        if k < 1 or k > pca_k:
+            raise UsageError(f"--pcrelate_components must be between 1 and --pca_components "
+                             f"({pca_k})")
+        if k + 1 > PCRELATE_COLUMNS_MAX:
+            raise UsageError(f"--pcrelate_components must be at most {PCRELATE_COLUMNS_MAX - 1} "
+                             "(the intercept takes one of the kernel's "
+                             f"{PCRELATE_COLUMNS_MAX} columns)")
+        maf = args.pcrelate_min_maf
+        if maf is not None and not 0.0 <= maf < 0.5:   # (false for a NaN)
+            raise UsageError("--pcrelate_min_maf must be in [0, 0.5)")
+
+
+PCRELATE_COLUMNS_MAX = 32   # (CUKING_PCRELATE_COLUMNS_MAX; host-only here: no library load)
+
+
+def pcrelate_components(args) -> int:
+    """The number of components --pcrelate-uri adjusts for: its own flag, else all of the
+    PCA's."""
+    if args.pcrelate_components is not None:
+        return args.pcrelate_components
+    return 10 if args.pca_components is None else args.pca_components
 
 
 def ld_pruning(args) -> bool:
@@ -446,7 +493,7 @@ def write_unrelated(path: Path, ctx, recs: np.ndarray, sample_ids, threshold: fl
 
 
 def write_pca(path: Path, ctx, bits, wps: int, num_sites: int, components: int, fit,
-              sample_ids) -> None:
+              sample_ids):
     """The principal components as an .npz: `eigenvalues` [k], `scores` [samples, k],
     `loadings` [sites, k], `allele_freq` and `sites_used` [sites] (of the sites QC and pruning
     left), `fit` [samples] (the samples the components were fitted on) and `samples`."""
@@ -456,6 +503,28 @@ def write_pca(path: Path, ctx, bits, wps: int, num_sites: int, components: int, 
         np.savez(f, eigenvalues=got.eigenvalues, scores=got.scores, loadings=got.loadings,
                  allele_freq=got.allele_freq, sites_used=got.sites_used, fit=got.fit,
                  samples=np.array(list(sample_ids), dtype=str))
+    return got
+
+
+def write_pcrelate(path: Path, ctx, bits, wps: int, num_sites: int, pca, components: int,
+                   min_maf: float, device: int) -> None:
+    """The whole cohort's PC-Relate kinship matrix as a float32 .npy [samples, samples], from
+    the leading `components` scores and the fit of this run's PCA."""
+    import torch
+    n = bits.shape[0]
+    need = 4 * n * n
+    free, _ = torch.cuda.mem_get_info(device)
+    if need > free:
+        raise RuntimeError(
+            f"the PC-Relate matrix of this cohort ({n} x {n} float32 = {need / 1e9:.1f} GB) "
+            f"does not fit the {free / 1e9:.1f} GB free on the GPU: call "
+            "KingContext.pcrelate block by block instead (block=...)")
+    scores = np.ascontiguousarray(pca.scores[:, :components])
+    got = ctx.pcrelate(bits, wps, num_sites, scores, fit=pca.fit, min_maf=min_maf)
+    torch.cuda.synchronize(device)
+    path.parent.mkdir(parents=True, exist_ok=True)
+    with open(path, "wb") as f:   # (np.save would append .npy to another suffix)
+        np.save(f, got.kin.cpu().numpy())
 
 
 def site_qc(ctx, args, bits, wps: int, num_sites: int, sample_ids, keep_path, qc_path):
@@ -532,6 +601,7 @@ def main(argv=None) -> int:
         site_qc_path = resolve_uri(args.site_qc_uri) if args.site_qc_uri else None
         site_ld_path = resolve_uri(args.site_ld_uri) if args.site_ld_uri else None
         pca_path = resolve_uri(args.pca_uri) if args.pca_uri else None
+        pcrelate_path = resolve_uri(args.pcrelate_uri) if args.pcrelate_uri else None
         synthetic = None
         if args.synthetic:
             parts = [int(x) for x in args.synthetic.split(",")]
@@ -689,9 +759,14 @@ def main(argv=None) -> int:
                                                  local_rank)
             if pca_path is not None:
                 fit = unrelated_keep == 1 if args.pca_fit == "unrelated" else None
-                write_pca(pca_path, ctx, bits[:stored], wps, num_sites,
-                          10 if args.pca_components is None else args.pca_components, fit,
-                          sample_ids)
+                pca = write_pca(pca_path, ctx, bits[:stored], wps, num_sites,
+                                10 if args.pca_components is None else args.pca_components, fit,
+                                sample_ids)
+                if pcrelate_path is not None:
+                    write_pcrelate(pcrelate_path, ctx, bits[:stored], wps, num_sites, pca,
+                                   pcrelate_components(args),
+                                   0.01 if args.pcrelate_min_maf is None
+                                   else args.pcrelate_min_maf, local_rank)
             pairs = sm.NumPairs()
             print(json.dumps({"pairs": pairs, "results": int(len(recs)), "gpus": world,
                               "compute_seconds": dt,

@@ -895,6 +895,71 @@ cuking_status cuking_geno_matmul(cuking_ctx *ctx, const uint64_t *d_bits, uint32
                                  int table_axis, const float *d_b, uint32_t ldb, uint32_t num_rhs,
                                  float *d_out, uint32_t ldo, void *stream);
 
+/* PC-Relate: the ancestry-adjusted kinship of every pair of a block, from the 2-bit genotypes
+ * and a low-rank model of each sample's allele frequencies (Conomos et al. 2016; GENESIS
+ * pcrelate, hl.pc_relate) -- what follows principal components fitted on the unrelated set
+ * (cuking_amd/pca.py) in PC-AiR / PC-Relate.  KING-robust reads ancestry distance as negative
+ * kinship; this estimator does not.  csrc/king_pcrelate.h holds the element functions as code
+ * shared by host, device and tests; cuking_amd/pcrelate.py fits beta with the genotype matrix
+ * product above.
+ *
+ *     bits   uint64 [num_stored][words_per_sample], the sample-major bitset, codes as above
+ *     X      float32 [num_stored][ldx], d columns used, 1 <= d <= CUKING_PCRELATE_COLUMNS_MAX;
+ *            column 0 is the intercept, the others principal-component scores
+ *     beta   float32 [num_sites][ldbeta], d columns used
+ *     lo, hi float32, 0 <= lo < hi <= 1 (the wrapper passes min_maf and 1 - min_maf)
+ *     block  rows [i_begin, i_end) x columns [j_begin, j_end) of the STORED samples (indices
+ *            into bits and X), identical ranges or disjoint with rows first
+ *     out    float32, out[(i - i_begin) * ldo + (j - j_begin)], ldo in ELEMENTS >= columns
+ *
+ *     mu(i,s)    = 0.5f * (fmaf chain in ascending c, from 0.0f, of X[i][c] * beta[s][c]): the
+ *                  individual-specific allele frequency (zero terms may pad the chain)
+ *     valid(i,s) = code(i,s) != 3 and lo < mu < hi (strict float32 comparisons)
+ *     r(i,s)     = (float)g - 2.0f * mu when valid, else 0.0f       (g = the code, 0 1 2)
+ *     v(i,s)     = sqrtf(mu * (1.0f - mu)) when valid, else 0.0f    (correctly rounded)
+ *     num(i,j)   = sum over s < num_sites of r(i,s) r(j,s)
+ *     den(i,j)   = sum over s < num_sites of v(i,s) v(j,s)
+ *     kin(i,j)   = num / (4.0f * den)                               (IEEE float32 division)
+ *
+ * No multiply and add of r or v is contracted, so host and device hold the same r and v bit
+ * for bit.  The zeros of the invalid elements are what restricts both sums to the jointly valid
+ * sites -- there is no pair-wise mask --, and a pair without one gets NaN.  The diagonal is an
+ * entry like any other: 2 kin(i,i) - 1 is the inbreeding estimate.  Sites at or beyond
+ * num_sites contribute nothing, whatever their bits hold.
+ *
+ * Numerics.  The device accumulates each sum in float32 in ascending s with one fused
+ * multiply-add per term (the f32-input MFMA of gfx950); there is no split of the site range, no
+ * atomics and no partial-sum scratch.  The same inputs give the same bytes on every call and
+ * stream, kin(i,j) and kin(j,i) are the same bytes, and an entry does not depend on the block
+ * it was computed in.  The host twin accumulates both sums in double, rounds each once and
+ * divides in float32.  Both stay within (num_sites + 2) 2^-24 sum |r r| and sum |v v| of the
+ * sums of their r and v.
+ *
+ * Every entry of the block is OVERWRITTEN with plain stores (a diagonal block computes both
+ * triangles); nothing between the block's columns and ldo is written.  cuking_pcrelate_matrix
+ * is asynchronous on `stream`.  INVALID_ARGUMENT before any device is touched: d 0 or above
+ * the maximum; ldx or ldbeta below d; num_sites > 64 (words_per_sample / 2); words_per_sample
+ * zero or odd; bounds not 0 <= lo < hi <= 1; a null, reversed or overlapping block or one
+ * outside num_stored; ldo below the block's columns; and, with work to do, a null pointer (out;
+ * bits, X, beta when num_sites != 0 as well).  An empty block returns OK without work;
+ * num_sites == 0 writes NaN.
+ * Out of scope: the C++ `cuking` binary; several ranks; the IBD-sharing k0 / k2; re-scoring
+ * only the KING records, without a matrix; half-precision operands; a triangular launch for
+ * diagonal blocks; GENESIS's "truncate" bound and its kinship rescaling. */
+#define CUKING_PCRELATE_COLUMNS_MAX 32
+cuking_status cuking_pcrelate_matrix_host(const uint64_t *bits, uint32_t num_stored,
+                                          uint32_t words_per_sample, uint32_t num_sites,
+                                          const float *x, uint32_t ldx, const float *beta,
+                                          uint32_t ldbeta, uint32_t d, float lo, float hi,
+                                          const cuking_submatrix *block, float *out,
+                                          uint64_t ldo);
+cuking_status cuking_pcrelate_matrix(cuking_ctx *ctx, const uint64_t *d_bits, uint32_t num_stored,
+                                     uint32_t words_per_sample, uint32_t num_sites,
+                                     const float *d_x, uint32_t ldx, const float *d_beta,
+                                     uint32_t ldbeta, uint32_t d, float lo, float hi,
+                                     const cuking_submatrix *block, float *d_out, uint64_t ldo,
+                                     void *stream);
+
 /* cuking.cu:761-765 on host memory: sort by (sample_i, sample_j, kin). */
 void cuking_sort_results(cuking_result *results, size_t num_results);
 
