@@ -33,6 +33,7 @@ GENO_TABLE_PER_COLUMN = 0
 GENO_TABLE_PER_ROW = 1
 
 PCRELATE_COLUMNS_MAX = 32
+PCRELATE_K0_SWITCH = 0.17677669529663689   # (rounded to float32 where it is compared)
 
 
 class CKinBins(C.Structure):
@@ -172,6 +173,10 @@ SIGNATURES = {
                                            _f32, _f32, _SM, _vp, _u64]),
     "cuking_pcrelate_matrix": (_int, [_vp, _vp, _u32, _u32, _u32, _vp, _u32, _vp, _u32, _u32,
                                       _f32, _f32, _SM, _vp, _u64, _vp]),
+    "cuking_pcrelate_pairs_host": (_int, [_vp, _u32, _u32, _u32, _vp, _u32, _vp, _u32, _u32,
+                                          _f32, _f32, _vp, _vp, _u64, _u32, _vp]),
+    "cuking_pcrelate_pairs": (_int, [_vp, _vp, _u32, _u32, _u32, _vp, _u32, _vp, _u32, _u32,
+                                     _f32, _f32, _vp, _vp, _u64, _u32, _vp, _vp]),
     "cuking_sort_results": (None, [_vp, _sz]),
     "cuking_timing_enable": (_int, [_vp, _int]),
     "cuking_timing_reset": (_int, [_vp]),

@@ -1119,6 +1119,42 @@ class KingContext:
         return _pcr.pcrelate_device(self, bits, words_per_sample, num_sites, scores, fit=fit,
                                     min_maf=min_maf, block=block, out=out, stream=stream)
 
+    def pcrelate_pairs_raw(self, bits, words_per_sample: int, num_sites: int, x, beta, lo: float,
+                           hi: float, pairs, f=None, num_records=None, out=None, stream=None):
+        """The bare kernel call for listed pairs (cuking_pcrelate_pairs; include/cuking_amd.h
+        "PC-Relate for listed pairs" has the definition): ``kin``, ``k0``, ``k1``, ``k2``,
+        ``ibs0`` and ``sites`` of every pair of ``pairs`` -- the int32 ``[*, 6]`` record tensor
+        of ``compute_king`` with ``num_records``, an int32 / int64 ``[P, 2]`` tensor, or a host
+        array of either form -- from ``x``, ``beta`` and the bounds as ``pcrelate_matrix``
+        takes them and ``f``, a float32 device tensor of the stored samples' inbreeding
+        coefficients (None = all zero).  Returns an int32 ``[P, 8]`` device tensor, one
+        cuking_pcrelate_pair per row in input order (``pcrelate.pairs_to_host`` gives it
+        names); ``out``: such a tensor to write into.  A row depends on its own pair only; an
+        index outside the stored samples gives a NaN row.  One thread runs all sites of a
+        pair: a short list is bound by that latency.  Does not synchronise."""
+        from . import pcrelate as _pcr
+        return _pcr.pcrelate_pairs_raw_device(self, bits, words_per_sample, num_sites, x, beta,
+                                              float(lo), float(hi), pairs, f, num_records, out,
+                                              stream)
+
+    def pcrelate_pairs(self, bits, words_per_sample: int, num_sites: int, pairs, scores=None,
+                       model=None, fit=None, min_maf: float = 0.01, inbreeding=None,
+                       num_records=None, stream=None):
+        """PC-Relate on a list of pairs, without a matrix: ancestry-adjusted kinship and the
+        IBD-sharing coefficients k0, k1, k2 of ``pairs`` (as ``pcrelate_pairs_raw`` takes them;
+        ``num_records`` with a record buffer).  ``model``: an earlier ``PCRelateResult`` or
+        ``PCRelatePairs`` whose ``x`` and ``beta`` are reused; otherwise the model is fitted on
+        ``scores`` and ``fit`` as ``pcrelate`` does.  ``inbreeding``: float32 ``[num_stored]``
+        on the host, or None: then the self pairs ``(s, s)`` of all stored samples run first
+        and ``f = 2 kin(s, s) - 1`` (a NaN stays NaN and makes that sample's ``k2`` NaN).  A
+        pair outside the stored samples raises ValueError.  Returns a ``PCRelatePairs`` of host
+        arrays; waits for the device."""
+        from . import pcrelate as _pcr
+        return _pcr.pcrelate_pairs_device(self, bits, words_per_sample, num_sites, pairs,
+                                          scores=scores, model=model, fit=fit, min_maf=min_maf,
+                                          inbreeding=inbreeding, num_records=num_records,
+                                          stream=stream)
+
     def synth_bitset(self, seed: int, kind, pa, pb, sample_begin: int,
                      sample_end: int, num_sites: int, out=None, stream=None, model=0):
         """Synthetic reference-layout bitset rows [sample_begin, sample_end)

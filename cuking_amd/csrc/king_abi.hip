@@ -2064,6 +2064,27 @@ cuking_status cuking_pcrelate_matrix(cuking_ctx *ctx, const uint64_t *d_bits, ui
   return CUKING_OK;
 }
 
+cuking_status cuking_pcrelate_pairs(cuking_ctx *ctx, const uint64_t *d_bits, uint32_t num_stored,
+                                    uint32_t words_per_sample, uint32_t num_sites,
+                                    const float *d_x, uint32_t ldx, const float *d_beta,
+                                    uint32_t ldbeta, uint32_t d, float lo, float hi,
+                                    const float *d_f, const void *d_pairs, uint64_t num_pairs,
+                                    uint32_t pair_stride, cuking_pcrelate_pair *d_out,
+                                    void *stream) {
+  // (the arguments first: a refused call touches no device)
+  if (ctx == nullptr) return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "null context");
+  const cuking_status st = cuking_check_pcrelate_pairs_args(d_bits, words_per_sample, num_sites,
+                                                            d_x, ldx, d_beta, ldbeta, d, lo, hi,
+                                                            d_pairs, num_pairs, pair_stride, d_out);
+  if (st != CUKING_OK) return st;
+  if (num_pairs == 0) return CUKING_OK;
+  BIND_OR_RETURN(ctx);
+  HIP_TRY(launch_pcrelate_pairs(d_bits, num_stored, words_per_sample, num_sites, d_x, ldx, d_beta,
+                                ldbeta, d, lo, hi, d_f, d_pairs, num_pairs, pair_stride, d_out,
+                                (hipStream_t)stream));
+  return CUKING_OK;
+}
+
 // ---- timing ---------------------------------------------------------------
 
 cuking_status cuking_timing_enable(cuking_ctx *ctx, int enabled) {

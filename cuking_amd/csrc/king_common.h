@@ -668,6 +668,15 @@ hipError_t launch_pcrelate_matrix(const uint64_t *d_bits, uint32_t words_per_sam
                                   float hi, const cuking_submatrix &block, float *d_out,
                                   uint64_t ldo, hipStream_t stream);
 
+// PC-Relate for listed pairs (king_pcrelate_pairs.hip; arguments already checked, king_host.h).
+// Plain stores into d_out[0 .. num_pairs); num_sites == 0 stores the NaN rows.
+hipError_t launch_pcrelate_pairs(const uint64_t *d_bits, uint32_t num_stored,
+                                 uint32_t words_per_sample, uint32_t num_sites, const float *d_x,
+                                 uint32_t ldx, const float *d_beta, uint32_t ldbeta, uint32_t d,
+                                 float lo, float hi, const float *d_f, const void *d_pairs,
+                                 uint64_t num_pairs, uint32_t pair_stride,
+                                 cuking_pcrelate_pair *d_out, hipStream_t stream);
+
 // Cohort models of the synthetic generator (synth.hip holds the specification).  d_tables:
 // synth_table_bytes() of scratch the launch fills and reads (per-site and per-sample
 // tables); it must stay untouched until the launch has run.

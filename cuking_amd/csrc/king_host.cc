@@ -11,6 +11,7 @@
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
+#include <cstring>
 #include <numeric>
 #include <string>
 #include <tuple>
@@ -681,14 +682,11 @@ cuking_status cuking_geno_matmul_host(const uint64_t *bits, uint32_t num_rows,
 }  // extern "C"
 
 // ---- PC-Relate: the argument checks and the host twin ---------------------------------------
-cuking_status cuking_check_pcrelate_args(const void *bits, uint32_t num_stored,
-                                         uint32_t words_per_sample, uint32_t num_sites,
-                                         const void *x, uint32_t ldx, const void *beta,
-                                         uint32_t ldbeta, uint32_t d, float lo, float hi,
-                                         const cuking_submatrix *block, const void *out,
-                                         uint64_t ldo) {
-  const cuking_status st = cuking_check_block(block, words_per_sample);
-  if (st != CUKING_OK) return st;
+namespace {
+
+// What the matrix and the listed pairs share: the model's shape and the bounds.
+cuking_status check_pcrelate_model(uint32_t words_per_sample, uint32_t num_sites, uint32_t ldx,
+                                   uint32_t ldbeta, uint32_t d, float lo, float hi) {
   if (d == 0 || d > kPcrelateColumnsMax)
     return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "pcrelate: d (%u) must be in [1, %u]", d,
                        kPcrelateColumnsMax);
@@ -704,6 +702,21 @@ cuking_status cuking_check_pcrelate_args(const void *bits, uint32_t num_stored,
     return cuking_fail(CUKING_ERR_INVALID_ARGUMENT,
                        "pcrelate: bounds lo = %g, hi = %g are not 0 <= lo < hi <= 1", (double)lo,
                        (double)hi);
+  return CUKING_OK;
+}
+
+}  // namespace
+
+cuking_status cuking_check_pcrelate_args(const void *bits, uint32_t num_stored,
+                                         uint32_t words_per_sample, uint32_t num_sites,
+                                         const void *x, uint32_t ldx, const void *beta,
+                                         uint32_t ldbeta, uint32_t d, float lo, float hi,
+                                         const cuking_submatrix *block, const void *out,
+                                         uint64_t ldo) {
+  cuking_status st = cuking_check_block(block, words_per_sample);
+  if (st != CUKING_OK) return st;
+  st = check_pcrelate_model(words_per_sample, num_sites, ldx, ldbeta, d, lo, hi);
+  if (st != CUKING_OK) return st;
   if (block->i_end > num_stored || block->j_end > num_stored)
     return cuking_fail(CUKING_ERR_INVALID_ARGUMENT,
                        "pcrelate: block rows [%u, %u) x columns [%u, %u) outside the %u stored "
@@ -768,6 +781,77 @@ cuking_status cuking_pcrelate_matrix_host(const uint64_t *bits, uint32_t num_sto
       }
       out[(uint64_t)i * ldo + j] = pcrelate_kin((float)num, (float)den);
     }
+  return CUKING_OK;
+}
+
+}  // extern "C"
+
+// ---- PC-Relate for listed pairs --------------------------------------------------------------
+cuking_status cuking_check_pcrelate_pairs_args(const void *bits, uint32_t words_per_sample,
+                                               uint32_t num_sites, const void *x, uint32_t ldx,
+                                               const void *beta, uint32_t ldbeta, uint32_t d,
+                                               float lo, float hi, const void *pairs,
+                                               uint64_t num_pairs, uint32_t pair_stride,
+                                               const void *out) {
+  if (words_per_sample == 0 || (words_per_sample & 1))
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT,
+                       "words_per_sample (%u) must be a positive even number", words_per_sample);
+  const cuking_status st = check_pcrelate_model(words_per_sample, num_sites, ldx, ldbeta, d, lo, hi);
+  if (st != CUKING_OK) return st;
+  if (!pcrelate_pair_stride_valid(pair_stride))
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT,
+                       "pcrelate pairs: pair_stride (%u bytes) must be at least 8 and a multiple "
+                       "of 4", pair_stride);
+  if (num_pairs == 0) return CUKING_OK;
+  if (out == nullptr)
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "pcrelate pairs: null out pointer");
+  if (pairs == nullptr)
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "pcrelate pairs: null pairs pointer");
+  if (num_sites != 0 && (bits == nullptr || x == nullptr || beta == nullptr))
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "pcrelate pairs: null pointer");
+  return CUKING_OK;
+}
+
+extern "C" {
+
+cuking_status cuking_pcrelate_pairs_host(const uint64_t *bits, uint32_t num_stored,
+                                         uint32_t words_per_sample, uint32_t num_sites,
+                                         const float *x, uint32_t ldx, const float *beta,
+                                         uint32_t ldbeta, uint32_t d, float lo, float hi,
+                                         const float *f, const void *pairs, uint64_t num_pairs,
+                                         uint32_t pair_stride, cuking_pcrelate_pair *out) {
+  const cuking_status st = cuking_check_pcrelate_pairs_args(bits, words_per_sample, num_sites, x,
+                                                            ldx, beta, ldbeta, d, lo, hi, pairs,
+                                                            num_pairs, pair_stride, out);
+  if (st != CUKING_OK) return st;
+  const uint32_t plane_words = words_per_sample / 2;
+  for (uint64_t p = 0; p < num_pairs; ++p) {
+    uint32_t in[2];
+    memcpy(in, static_cast<const unsigned char *>(pairs) + p * pair_stride, sizeof(in));
+    PcrelatePairSums sum;
+    if (in[0] < num_stored && in[1] < num_stored && num_sites != 0) {
+      // (the smaller index leads the chains, as on the device)
+      const uint64_t si = in[0] < in[1] ? in[0] : in[1], sj = in[0] < in[1] ? in[1] : in[0];
+      const uint64_t *row_i = bits + si * words_per_sample, *row_j = bits + sj * words_per_sample;
+      const float one_plus_f_i = f != nullptr ? 1.0f + f[si] : 1.0f;
+      const float one_plus_f_j = f != nullptr ? 1.0f + f[sj] : 1.0f;
+      for (uint64_t s = 0; s < num_sites; ++s) {
+        const uint32_t bit = (uint32_t)(s & 63);
+        const float *b = beta + s * ldbeta;
+        pcrelate_pair_site(&sum, geno_code(row_i[s >> 6], row_i[plane_words + (s >> 6)], bit),
+                           pcrelate_mu(x + si * ldx, b, d), one_plus_f_i,
+                           geno_code(row_j[s >> 6], row_j[plane_words + (s >> 6)], bit),
+                           pcrelate_mu(x + sj * ldx, b, d), one_plus_f_j, lo, hi);
+      }
+    }
+    cuking_pcrelate_pair row;
+    row.sample_i = in[0];
+    row.sample_j = in[1];
+    pcrelate_pair_result(sum, &row.kin, &row.k0, &row.k1, &row.k2);
+    row.ibs0 = sum.ibs0;
+    row.sites = sum.sites;
+    out[p] = row;
+  }
   return CUKING_OK;
 }
 

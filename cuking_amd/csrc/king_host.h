@@ -50,5 +50,13 @@ cuking_status cuking_check_pcrelate_args(const void *bits, uint32_t num_stored,
                                          uint32_t ldbeta, uint32_t d, float lo, float hi,
                                          const cuking_submatrix *block, const void *out,
                                          uint64_t ldo);
+// Argument checks of cuking_pcrelate_pairs_host / cuking_pcrelate_pairs (include/cuking_amd.h
+// "PC-Relate for listed pairs" lists them); OK says nothing about there being work to do.
+cuking_status cuking_check_pcrelate_pairs_args(const void *bits, uint32_t words_per_sample,
+                                               uint32_t num_sites, const void *x, uint32_t ldx,
+                                               const void *beta, uint32_t ldbeta, uint32_t d,
+                                               float lo, float hi, const void *pairs,
+                                               uint64_t num_pairs, uint32_t pair_stride,
+                                               const void *out);
 
 #endif  // CUKING_AMD_KING_HOST_H_

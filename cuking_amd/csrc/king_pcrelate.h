@@ -14,6 +14,15 @@
 // Sums.  num(i, j) = sum_s r(i, s) r(j, s), den(i, j) = sum_s v(i, s) v(j, s), kin = num /
 // (4.0f * den) in IEEE float32 (NaN without a jointly valid site).  The zeros of the invalid
 // elements are what restricts both sums to the jointly valid sites.
+//
+// Listed pairs (include/cuking_amd.h, "PC-Relate for listed pairs"; king_pcrelate_pairs.hip and
+// cuking_pcrelate_pairs_host).  On top of the element above, with f the sample's inbreeding
+// coefficient: var = mu * (1.0f - mu), s2 = (1.0f + f) * var, dom = mu, 0.0f or 1.0f - mu for
+// the codes 0, 1, 2, e = dom - s2; an invalid element has s2 = e = 0.0f.  A pair holds seven
+// sums over its jointly valid sites (PcrelatePairSums); each float sum is ONE float32 chain from
+// +0.0f in ascending s with one fmaf per term, which pcrelate_pair_site writes out and host and
+// device both run, so the two agree bit for bit.  pcrelate_pair_result turns the sums into kin,
+// k0, k1, k2.
 #ifndef CUKING_AMD_KING_PCRELATE_H_
 #define CUKING_AMD_KING_PCRELATE_H_
 
@@ -53,6 +62,81 @@ CUKING_HD inline float pcrelate_kin(float num, float den) { return num / (4.0f *
 
 CUKING_HD inline bool pcrelate_bounds_valid(float lo, float hi) {
   return 0.0f <= lo && lo < hi && hi <= 1.0f;  // (false for a NaN)
+}
+
+// ---- listed pairs ----------------------------------------------------------------------------
+
+// (CUKING_PCRELATE_K0_SWITCH: 2^(-5/2) rounded to float32, 0x3E3504F3)
+constexpr float kPcrelateK0Switch = 0.17677669529663689f;
+
+// s2 and e of one element; `one_plus_f` = 1.0f + f of its sample.
+CUKING_HD inline void pcrelate_dominance(uint32_t code, float mu, bool valid, float one_plus_f,
+                                         float *s2, float *e) {
+  const float var = mu * (1.0f - mu);
+  const float scaled = one_plus_f * var;
+  const float dom = code == 0u ? mu : code == 1u ? 0.0f : 1.0f - mu;
+  const float diff = dom - scaled;
+  *s2 = valid ? scaled : 0.0f;
+  *e = valid ? diff : 0.0f;
+}
+
+struct PcrelatePairSums {
+  float num = 0.0f, den = 0.0f, dnum = 0.0f, dden = 0.0f, hden = 0.0f;
+  uint32_t ibs0 = 0, sites = 0;
+};
+
+// One site of one pair: i is the first sample of the chains, j the second (the callers put the
+// smaller index first, which is what makes (i, j) and (j, i) the same bytes although the two
+// terms of hden are taken in a fixed order).  A site that is not jointly valid adds nothing.
+CUKING_HD inline void pcrelate_pair_site(PcrelatePairSums *sum, uint32_t code_i, float mu_i,
+                                         float one_plus_f_i, uint32_t code_j, float mu_j,
+                                         float one_plus_f_j, float lo, float hi) {
+  float r_i, v_i, s2_i, e_i, r_j, v_j, s2_j, e_j;
+  const bool valid_i = pcrelate_valid(code_i, mu_i, lo, hi);
+  const bool valid_j = pcrelate_valid(code_j, mu_j, lo, hi);
+  pcrelate_element(code_i, mu_i, lo, hi, &r_i, &v_i);
+  pcrelate_element(code_j, mu_j, lo, hi, &r_j, &v_j);
+  pcrelate_dominance(code_i, mu_i, valid_i, one_plus_f_i, &s2_i, &e_i);
+  pcrelate_dominance(code_j, mu_j, valid_j, one_plus_f_j, &s2_j, &e_j);
+  const float a = mu_i * (1.0f - mu_j);
+  const float b = (1.0f - mu_i) * mu_j;
+  const float num = fmaf(r_i, r_j, sum->num);
+  const float den = fmaf(v_i, v_j, sum->den);
+  const float dnum = fmaf(e_i, e_j, sum->dnum);
+  const float dden = fmaf(s2_i, s2_j, sum->dden);
+  const float hden = fmaf(b, b, fmaf(a, a, sum->hden));
+  const bool joint = valid_i && valid_j;
+  sum->num = joint ? num : sum->num;
+  sum->den = joint ? den : sum->den;
+  sum->dnum = joint ? dnum : sum->dnum;
+  sum->dden = joint ? dden : sum->dden;
+  sum->hden = joint ? hden : sum->hden;
+  // (jointly valid codes are 0, 1, 2: only (0, 2) and (2, 0) differ in exactly the hom bit)
+  sum->ibs0 += (joint && (code_i ^ code_j) == 2u) ? 1u : 0u;
+  sum->sites += joint ? 1u : 0u;
+}
+
+// Every NaN is stored as the one quiet NaN 0x7FC00000, whatever the division made of it.
+CUKING_HD inline float pcrelate_canonical(float value) {
+  return value != value ? __builtin_nanf("") : value;
+}
+
+CUKING_HD inline void pcrelate_pair_result(const PcrelatePairSums &sum, float *kin, float *k0,
+                                           float *k1, float *k2) {
+  const float kin_v = pcrelate_kin(sum.num, sum.den);
+  const float k2_v = sum.dnum / sum.dden;
+  const float high = (1.0f - 4.0f * kin_v) + k2_v;
+  const float low = (float)sum.ibs0 / sum.hden;
+  const float k0_v = kin_v > kPcrelateK0Switch ? high : low;   // (false for a NaN)
+  const float k1_v = (1.0f - k2_v) - k0_v;
+  *kin = pcrelate_canonical(kin_v);
+  *k0 = pcrelate_canonical(k0_v);
+  *k1 = pcrelate_canonical(k1_v);
+  *k2 = pcrelate_canonical(k2_v);
+}
+
+CUKING_HD inline bool pcrelate_pair_stride_valid(uint32_t pair_stride) {
+  return pair_stride >= 8u && pair_stride % 4u == 0u;
 }
 
 }  // namespace cuking

@@ -149,12 +149,19 @@ def parse_args(argv=None):
               "with the scores and the fit of this run's --pca-uri (cuking_amd/pcrelate.py) -- to "
               "this float32 .npy file [samples, samples].  Needs --pca-uri; one process and "
               "--split-factor 1 only")
+    flag("pcrelate-pairs-uri", default="",
+         help="also re-score this run's records with PC-Relate -- no matrix: kin, k0, k1, k2, "
+              "ibs0, sites and the relationship code of every record's pair, ancestry-adjusted "
+              "with the scores and the fit of this run's --pca-uri -- and write them to this .npz "
+              "(with sample_i, sample_j, inbreeding, samples).  Needs --pca-uri; one process and "
+              "--split-factor 1 only")
     flag("pcrelate-components", type=int, default=None,
-         help="the number of leading components --pcrelate-uri adjusts for (default: all of "
-              "--pca-components; at most 31)")
+         help="the number of leading components --pcrelate-uri and --pcrelate-pairs-uri adjust "
+              "for (default: all of --pca-components; at most 31)")
     flag("pcrelate-min-maf", type=float, default=None,
-         help="--pcrelate-uri uses the elements whose individual-specific allele frequency "
-              "lies strictly between this and 1 minus this (default 0.01)")
+         help="--pcrelate-uri and --pcrelate-pairs-uri use the elements whose "
+              "individual-specific allele frequency lies strictly between this and 1 minus this "
+              "(default 0.01)")
     return ap.parse_args(argv)
 
 
@@ -279,8 +286,19 @@ def validate(args):  # cuking.cu:437-462
         if args.pca_components is not None and args.pca_components < 1:
             raise UsageError("--pca_components must be at least 1")
     if (args.pcrelate_components is not None or args.pcrelate_min_maf is not None) and \
-            not args.pcrelate_uri:
-        raise UsageError("--pcrelate_components and --pcrelate_min_maf need --pcrelate_uri")
+            not (args.pcrelate_uri or args.pcrelate_pairs_uri):
+        raise UsageError("--pcrelate_components and --pcrelate_min_maf need --pcrelate_uri or "
+                         "--pcrelate_pairs_uri")
+    if args.pcrelate_pairs_uri:
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            raise UsageError("--pcrelate_pairs_uri needs one process (one GPU): the records are "
+                             "not re-scored across ranks yet")
+        if args.split_factor != 1:
+            raise UsageError("--pcrelate_pairs_uri needs --split_factor 1: the model is fitted "
+                             "on the whole cohort's bitset")
+        if not args.pca_uri:
+            raise UsageError("--pcrelate_pairs_uri needs the principal components of the same "
+                             "run: pass --pca_uri as well")
     if args.pcrelate_uri:
         if int(os.environ.get("WORLD_SIZE", "1")) > 1:
             raise UsageError("--pcrelate_uri needs one process (one GPU): the matrix is not "
@@ -291,6 +309,7 @@ def validate(args):  # cuking.cu:437-462
         if not args.pca_uri:
             raise UsageError("--pcrelate_uri needs the principal components of the same run: "
                              "pass --pca_uri as well")
+    if args.pcrelate_uri or args.pcrelate_pairs_uri:
         pca_k = 10 if args.pca_components is None else args.pca_components
         k = pcrelate_components(args)
         if k < 1 or k > pca_k:
@@ -527,6 +546,22 @@ def write_pcrelate(path: Path, ctx, bits, wps: int, num_sites: int, pca, compone
         np.save(f, got.kin.cpu().numpy())
 
 
+def write_pcrelate_pairs(path: Path, ctx, bits, wps: int, num_sites: int, pca, components: int,
+                         min_maf: float, recs, sample_ids) -> None:
+    """This run's records re-scored by PC-Relate as an .npz: `sample_i`, `sample_j`, `kin`,
+    `k0`, `k1`, `k2`, `ibs0`, `sites`, `relationship` (one entry per record, in the records'
+    order; the codes of PCRelatePairs.relationship), `inbreeding` [samples] and `samples`."""
+    scores = np.ascontiguousarray(pca.scores[:, :components])
+    got = ctx.pcrelate_pairs(bits, wps, num_sites, recs, scores=scores, fit=pca.fit,
+                             min_maf=min_maf)
+    path.parent.mkdir(parents=True, exist_ok=True)
+    with open(path, "wb") as f:   # (np.savez would append .npz to another suffix)
+        np.savez(f, sample_i=got.sample_i, sample_j=got.sample_j, kin=got.kin, k0=got.k0,
+                 k1=got.k1, k2=got.k2, ibs0=got.ibs0, sites=got.sites,
+                 relationship=got.relationship(), inbreeding=got.inbreeding,
+                 samples=np.array(list(sample_ids), dtype=str))
+
+
 def site_qc(ctx, args, bits, wps: int, num_sites: int, sample_ids, keep_path, qc_path):
     """Site QC of the whole cohort's bitset: counts on the GPU, the rule on the host, the
     report if one is asked for, and -- with a flag that selects sites -- the compacted bitset.
@@ -602,6 +637,7 @@ def main(argv=None) -> int:
         site_ld_path = resolve_uri(args.site_ld_uri) if args.site_ld_uri else None
         pca_path = resolve_uri(args.pca_uri) if args.pca_uri else None
         pcrelate_path = resolve_uri(args.pcrelate_uri) if args.pcrelate_uri else None
+        pairs_path = resolve_uri(args.pcrelate_pairs_uri) if args.pcrelate_pairs_uri else None
         synthetic = None
         if args.synthetic:
             parts = [int(x) for x in args.synthetic.split(",")]
@@ -767,6 +803,11 @@ def main(argv=None) -> int:
                                    pcrelate_components(args),
                                    0.01 if args.pcrelate_min_maf is None
                                    else args.pcrelate_min_maf, local_rank)
+                if pairs_path is not None:
+                    write_pcrelate_pairs(pairs_path, ctx, bits[:stored], wps, num_sites, pca,
+                                         pcrelate_components(args),
+                                         0.01 if args.pcrelate_min_maf is None
+                                         else args.pcrelate_min_maf, recs, sample_ids)
             pairs = sm.NumPairs()
             print(json.dumps({"pairs": pairs, "results": int(len(recs)), "gpus": world,
                               "compute_seconds": dt,

@@ -943,9 +943,9 @@ cuking_status cuking_geno_matmul(cuking_ctx *ctx, const uint64_t *d_bits, uint32
  * outside num_stored; ldo below the block's columns; and, with work to do, a null pointer (out;
  * bits, X, beta when num_sites != 0 as well).  An empty block returns OK without work;
  * num_sites == 0 writes NaN.
- * Out of scope: the C++ `cuking` binary; several ranks; the IBD-sharing k0 / k2; re-scoring
- * only the KING records, without a matrix; half-precision operands; a triangular launch for
- * diagonal blocks; GENESIS's "truncate" bound and its kinship rescaling. */
+ * Out of scope: the C++ `cuking` binary; several ranks; half-precision operands; a triangular
+ * launch for diagonal blocks; GENESIS's "truncate" bound and its kinship rescaling.  (The
+ * IBD-sharing k0 / k2 and re-scoring only listed pairs: the section below.) */
 #define CUKING_PCRELATE_COLUMNS_MAX 32
 cuking_status cuking_pcrelate_matrix_host(const uint64_t *bits, uint32_t num_stored,
                                           uint32_t words_per_sample, uint32_t num_sites,
@@ -959,6 +959,73 @@ cuking_status cuking_pcrelate_matrix(cuking_ctx *ctx, const uint64_t *d_bits, ui
                                      uint32_t ldbeta, uint32_t d, float lo, float hi,
                                      const cuking_submatrix *block, float *d_out, uint64_t ldo,
                                      void *stream);
+
+/* PC-Relate for listed pairs: kinship and the IBD-sharing coefficients k0, k1, k2 of a LIST of
+ * pairs -- typically the records of cuking_compute_king -- without a matrix (the estimators of
+ * Conomos et al. 2016 as hl.pc_relate states them).  csrc/king_pcrelate.h holds the element
+ * functions and the per-site update as code shared by host, device and tests.
+ *
+ *     bits, X, beta, d, lo, hi   exactly as cuking_pcrelate_matrix takes them
+ *     f       float32 [num_stored], the samples' inbreeding coefficients, or null (all 0.0f)
+ *     pairs   num_pairs entries, entry p read as two uint32 (i, j) at pairs + p * pair_stride
+ *             BYTES; pair_stride >= 8 and a multiple of 4, pairs 4-byte aligned: a cuking_result
+ *             buffer (stride 24) or a plain [P][2] array (stride 8).  i and j index the stored
+ *             samples in any order; i == j (the self pair) and repeats are allowed
+ *     out     one cuking_pcrelate_pair per entry, in input order, written with plain stores
+ *
+ * Per element, on top of mu, valid, r and v above (no multiply and add contracted):
+ *     var = mu * (1.0f - mu)              (the product v takes the root of)
+ *     s2  = (1.0f + f_i) * var            when valid, else 0.0f
+ *     dom = mu, 0.0f, 1.0f - mu           for the codes 0, 1, 2
+ *     e   = dom - s2                      when valid, else 0.0f
+ * Per pair, over the JOINTLY valid sites s < num_sites (both elements valid; any other site
+ * adds nothing), each float sum ONE float32 chain from +0.0f in ascending s, one fmaf per term:
+ *     num   fmaf(r_i, r_j, .)      den   fmaf(v_i, v_j, .)
+ *     dnum  fmaf(e_i, e_j, .)      dden  fmaf(s2_i, s2_j, .)
+ *     hden  fmaf(a, a, .) then fmaf(b, b, .), a = mu_i * (1.0f - mu_j), b = (1.0f - mu_i) * mu_j
+ *     ibs0  uint32: the sites with codes (0, 2) or (2, 0);  sites  uint32: all of them
+ * In these chains i is the SMALLER index of the entry and j the larger (the order matters to
+ * hden's rounding only), which is what makes (i, j) and (j, i) the same bytes; sample_i and
+ * sample_j of the output row are copied from the input as they stand.  Then, in IEEE float32:
+ *     kin = num / (4.0f * den)            k2 = dnum / dden
+ *     k0  = kin > CUKING_PCRELATE_K0_SWITCH ? (1.0f - 4.0f * kin) + k2 : (float)ibs0 / hden
+ *           (the comparison is false for a NaN)
+ *     k1  = (1.0f - k2) - k0
+ * A NaN is stored as the quiet NaN 0x7FC00000.  A pair without a jointly valid site gets four
+ * NaNs and two zeros; so does a pair with an index >= num_stored, for which no memory outside
+ * the arrays is read.  num_sites == 0 writes such rows for every pair.
+ *
+ * The host twin evaluates the very same chains: host and device agree BIT FOR BIT in every
+ * field.  A row depends on its own pair only -- not on its position in the list, the length of
+ * the list, the stride, the stream or the call.  One thread runs all sites of a pair, so a
+ * short list is bound by that thread's latency, not by throughput.
+ *
+ * cuking_pcrelate_pairs is asynchronous on `stream`.  INVALID_ARGUMENT before any device is
+ * touched: d 0 or above the maximum; ldx or ldbeta below d; num_sites > 64 (words_per_sample /
+ * 2); words_per_sample zero or odd; bounds not 0 <= lo < hi <= 1; pair_stride below 8 or not a
+ * multiple of 4; and, with work to do, a null pointer (pairs, out; bits, X, beta when
+ * num_sites != 0 as well).  num_pairs == 0 returns OK without work.
+ * Out of scope: the C++ `cuking` binary; several ranks; GENESIS's rescaling of the
+ * coefficients; a k0 / k2 matrix. */
+#define CUKING_PCRELATE_K0_SWITCH 0.17677669529663689f /* 2^(-5/2) in float32 */
+typedef struct cuking_pcrelate_pair {
+  uint32_t sample_i, sample_j; /* copied from the input */
+  float kin, k0, k1, k2;
+  uint32_t ibs0, sites; /* counts over the jointly valid sites */
+} cuking_pcrelate_pair;
+cuking_status cuking_pcrelate_pairs_host(const uint64_t *bits, uint32_t num_stored,
+                                         uint32_t words_per_sample, uint32_t num_sites,
+                                         const float *x, uint32_t ldx, const float *beta,
+                                         uint32_t ldbeta, uint32_t d, float lo, float hi,
+                                         const float *f, const void *pairs, uint64_t num_pairs,
+                                         uint32_t pair_stride, cuking_pcrelate_pair *out);
+cuking_status cuking_pcrelate_pairs(cuking_ctx *ctx, const uint64_t *d_bits, uint32_t num_stored,
+                                    uint32_t words_per_sample, uint32_t num_sites,
+                                    const float *d_x, uint32_t ldx, const float *d_beta,
+                                    uint32_t ldbeta, uint32_t d, float lo, float hi,
+                                    const float *d_f, const void *d_pairs, uint64_t num_pairs,
+                                    uint32_t pair_stride, cuking_pcrelate_pair *d_out,
+                                    void *stream);
 
 /* cuking.cu:761-765 on host memory: sort by (sample_i, sample_j, kin). */
 void cuking_sort_results(cuking_result *results, size_t num_results);
