@@ -17,8 +17,9 @@ from .api import (DEFAULT_KIN_THRESHOLD, DEFAULT_MAX_RESULTS,  # noqa: F401
                   padded_sites, sort_results, synth_model_number, synth_models,
                   words_per_sample)
 from .pca import PCAResult, hwe_table, pca_host  # noqa: F401
-from .pcrelate import (PCRELATE_PAIR_DTYPE, PCRelatePairs, PCRelateResult,  # noqa: F401
-                       isaf_fit, pcrelate_host, pcrelate_matrix_host, pcrelate_pairs_host,
-                       pcrelate_pairs_raw_host)
+from .pcrelate import (PCRELATE_PAIR_DTYPE, PCRelatePairs, PCRelateRecords,  # noqa: F401
+                       PCRelateResult, isaf_fit, pcrelate_host, pcrelate_matrix_host,
+                       pcrelate_pairs_host, pcrelate_pairs_raw_host, pcrelate_records_host,
+                       pcrelate_records_raw_host)
 
 __version__ = "0.1.0"

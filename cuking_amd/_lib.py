@@ -33,7 +33,8 @@ GENO_TABLE_PER_COLUMN = 0
 GENO_TABLE_PER_ROW = 1
 
 PCRELATE_COLUMNS_MAX = 32
-PCRELATE_K0_SWITCH = 0.17677669529663689   # (rounded to float32 where it is compared)
+PCRELATE_TRIANGLE_SIDE_MAX = 1 << 25
+PCRELATE_K0_SWITCH =0.17677669529663689   # (rounded to float32 where it is compared)
 
 
 class CKinBins(C.Structure):
@@ -173,6 +174,13 @@ SIGNATURES = {
                                            _f32, _f32, _SM, _vp, _u64]),
     "cuking_pcrelate_matrix": (_int, [_vp, _vp, _u32, _u32, _u32, _vp, _u32, _vp, _u32, _u32,
                                       _f32, _f32, _SM, _vp, _u64, _vp]),
+    "cuking_pcrelate_records_host": (_int, [_vp, _u32, _u32, _u32, _vp, _u32, _vp, _u32, _u32,
+                                            _f32, _f32, _SM, _f32, _vp, _u64, C.POINTER(_u64)]),
+    "cuking_pcrelate_records": (_int, [_vp, _vp, _u32, _u32, _u32, _vp, _u32, _vp, _u32, _u32,
+                                       _f32, _f32, _SM, _f32, _vp, _u64, C.POINTER(_u64), _vp]),
+    "cuking_pcrelate_triangle_tiles": (_u64, [_u64]),
+    "cuking_pcrelate_triangle_index": (_u64, [_u64, _u32, _u32]),
+    "cuking_pcrelate_triangle_tile": (_u32, [_u64, _u64, C.POINTER(_u32), C.POINTER(_u32)]),
     "cuking_pcrelate_pairs_host": (_int, [_vp, _u32, _u32, _u32, _vp, _u32, _vp, _u32, _u32,
                                           _f32, _f32, _vp, _vp, _u64, _u32, _vp]),
     "cuking_pcrelate_pairs": (_int, [_vp, _vp, _u32, _u32, _u32, _vp, _u32, _vp, _u32, _u32,

@@ -1119,6 +1119,44 @@ class KingContext:
         return _pcr.pcrelate_device(self, bits, words_per_sample, num_sites, scores, fit=fit,
                                     min_maf=min_maf, block=block, out=out, stream=stream)
 
+    def pcrelate_records_raw(self, bits, words_per_sample: int, num_sites: int, x, beta,
+                             lo: float, hi: float, min_kin: float, block=None, max_records=None,
+                             out=None, stream=None):
+        """The bare kernel call for the pairs above a threshold (cuking_pcrelate_records;
+        include/cuking_amd.h "PC-Relate records" has the definition): the pairs of ``block``
+        (as ``pcrelate_matrix`` takes it; of a diagonal block those with ``i < j``) whose
+        kinship is above ``min_kin`` in the strict float32 comparison, as records ``sample_i <
+        sample_j, kin, ibs0 = ibs1 = ibs2 = 0`` in no particular order, ``kin`` the bytes
+        ``pcrelate_matrix`` writes for the pair.  Returns ``(records, count)``: the ``[*, 6]``
+        int32 device tensor ``unrelated_set`` and ``pcrelate_pairs`` take and the number of
+        records.  Only the upper triangle of a diagonal block's tiles is launched; no matrix
+        exists.  Without ``max_records`` the buffer holds 16 records per sample of the block
+        and the call is repeated once with the exact count if that overflows; with it (or with
+        ``out``, a tensor to write into), an overflow raises ``ResourceExhaustedError`` whose
+        ``num_records`` is the exact count -- nothing is written past the buffer;
+        ``max_records=0`` only counts.  WAITS for the stream."""
+        from . import pcrelate as _pcr
+        return _pcr.pcrelate_records_raw_device(self, bits, words_per_sample, num_sites, x, beta,
+                                                float(lo), float(hi), min_kin, block,
+                                                max_records, out, stream)
+
+    def pcrelate_records(self, bits, words_per_sample: int, num_sites: int, scores=None,
+                         model=None, fit=None, min_maf: float = 0.01,
+                         min_kinship: float = KING_CUTOFFS[0], block=None, max_records=None):
+        """PC-Relate for all pairs above a kinship threshold, without a matrix: the
+        counterpart of ``compute_king`` whose list holds the cross-ancestry relatives a KING
+        threshold misses.  ``model``: an earlier ``PCRelateResult``, ``PCRelateRecords`` or
+        ``PCRelatePairs`` whose ``x`` and ``beta`` are reused; otherwise the model is fitted on
+        ``scores`` and ``fit`` as ``pcrelate`` does.  ``min_kinship`` defaults to the third-degree
+        cut-off ``KING_CUTOFFS[0]``, a convention.  Returns a ``PCRelateRecords`` whose
+        ``records`` / ``num_records`` go to ``pcrelate_pairs`` (with ``model=`` the result) and
+        ``unrelated_set`` as they stand.  Waits for the device."""
+        from . import pcrelate as _pcr
+        return _pcr.pcrelate_records_device(self, bits, words_per_sample, num_sites,
+                                            scores=scores, model=model, fit=fit, min_maf=min_maf,
+                                            min_kinship=min_kinship, block=block,
+                                            max_records=max_records)
+
     def pcrelate_pairs_raw(self, bits, words_per_sample: int, num_sites: int, x, beta, lo: float,
                            hi: float, pairs, f=None, num_records=None, out=None, stream=None):
         """The bare kernel call for listed pairs (cuking_pcrelate_pairs; include/cuking_amd.h

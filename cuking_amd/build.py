@@ -29,7 +29,7 @@ LIB_FLAGS_PATH = PKG / "libcuking_amd.flags"
 HIP_SOURCES = ["king_abi.hip", "king_kernels.hip", "king_mfma.hip", "king_filter.hip",
                "king_sort.hip", "king_prune.hip", "king_bed.hip", "king_site_qc.hip",
                "king_ld.hip", "king_geno.hip", "king_pcrelate.hip",
-               "king_pcrelate_pairs.hip", "synth.hip"]
+               "king_pcrelate_records.hip", "king_pcrelate_pairs.hip", "synth.hip"]
 # Host-only half of the ABI: plain C++, also compiled by the sanitizer tests.
 HOST_ABI_SOURCES = ["king_host.cc"]
 # IEEE-correct fp32 divide (kinship must match the reference bit for bit):
@@ -103,6 +103,8 @@ def build_library(force: bool = False, save_temps: bool = False) -> Path:
                                  "geno_matmul_kernel")
     problems += check_no_scratch(cwd / "king_pcrelate-hip-amdgcn-amd-amdhsa-gfx950.s",
                                  "pcrelate_matrix_kernel")
+    problems += check_no_scratch(cwd / "king_pcrelate_records-hip-amdgcn-amd-amdhsa-gfx950.s",
+                                 "pcrelate_records_kernel")
     problems += check_no_scratch(cwd / "king_pcrelate_pairs-hip-amdgcn-amd-amdhsa-gfx950.s",
                                  "pcrelate_pairs_kernel")
     if problems and not extra:

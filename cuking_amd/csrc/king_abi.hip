@@ -131,9 +131,10 @@ struct cuking_ctx {
     uint8_t *filter = nullptr;
     uint64_t filter_tiles = 0;
     // Grown when a call needs more (grow_on_stream below): cuking_unrelated_set's workspace
-    // (king_prune.hip), cuking_compact_sites' table (king_site_qc.h) and cuking_ld_edges'
-    // edge counter (king_ld.hip: one word).
-    DeviceBuf prune, sites, ld_count;
+    // (king_prune.hip), cuking_compact_sites' table (king_site_qc.h) and the record counter of
+    // cuking_ld_edges and cuking_pcrelate_records (one word; each call zeroes it on the stream
+    // and has read it back when it returns).
+    DeviceBuf prune, sites, record_count;
   };
   std::vector<StreamScratch> scratch;
   // The running totals of filter scratch that has been freed since (a larger block took
@@ -353,7 +354,7 @@ void free_split_slab(cuking_ctx::StreamScratch &e) {
 void free_stream_scratch(cuking_ctx *ctx, cuking_ctx::StreamScratch &e, bool retire_totals) {
   free_filter_scratch(ctx, e, retire_totals);
   free_split_slab(e);
-  for (cuking_ctx::DeviceBuf *b : {&e.prune, &e.sites, &e.ld_count}) {
+  for (cuking_ctx::DeviceBuf *b : {&e.prune, &e.sites, &e.record_count}) {
     if (b->p != nullptr) (void)hipFree(b->p);
     *b = {};
   }
@@ -2009,9 +2010,9 @@ cuking_status cuking_ld_edges(cuking_ctx *ctx, const uint64_t *d_site_bits, uint
   BIND_OR_RETURN(ctx);
   hipStream_t s = (hipStream_t)stream;
   cuking_ctx::StreamScratch *e = stream_entry(ctx, s);
-  st = grow_on_stream(ctx, s, &e->ld_count, sizeof(unsigned long long));
+  st = grow_on_stream(ctx, s, &e->record_count, sizeof(unsigned long long));
   if (st != CUKING_OK) return st;
-  unsigned long long *d_count = static_cast<unsigned long long *>(e->ld_count.p);
+  unsigned long long *d_count = static_cast<unsigned long long *>(e->record_count.p);
   HIP_TRY(hipMemsetAsync(d_count, 0, sizeof(unsigned long long), s));
   HIP_TRY(launch_ld_edges(d_site_bits, num_sites, num_stored, window, r2_threshold, d_group,
                           d_records, max_records, d_count, s));
@@ -2062,6 +2063,39 @@ cuking_status cuking_pcrelate_matrix(cuking_ctx *ctx, const uint64_t *d_bits, ui
   HIP_TRY(launch_pcrelate_matrix(d_bits, words_per_sample, num_sites, d_x, ldx, d_beta, ldbeta, d,
                                  lo, hi, *block, d_out, ldo, (hipStream_t)stream));
   return CUKING_OK;
+}
+
+cuking_status cuking_pcrelate_records(cuking_ctx *ctx, const uint64_t *d_bits,
+                                      uint32_t num_stored, uint32_t words_per_sample,
+                                      uint32_t num_sites, const float *d_x, uint32_t ldx,
+                                      const float *d_beta, uint32_t ldbeta, uint32_t d, float lo,
+                                      float hi, const cuking_submatrix *block, float min_kin,
+                                      cuking_result *d_records, uint64_t max_records,
+                                      uint64_t *num_records, void *stream) {
+  if (num_records != nullptr) *num_records = 0;
+  // (the arguments first: a refused call touches no device)
+  if (ctx == nullptr) return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "null context");
+  cuking_status st = cuking_check_pcrelate_records_args(
+      d_bits, num_stored, words_per_sample, num_sites, d_x, ldx, d_beta, ldbeta, d, lo, hi, block,
+      min_kin, d_records, max_records, num_records);
+  if (st != CUKING_OK) return st;
+  // (without a site every kin is NaN: no record)
+  if (sm_num_rows(*block) == 0 || sm_num_cols(*block) == 0 || num_sites == 0) return CUKING_OK;
+  BIND_OR_RETURN(ctx);
+  hipStream_t s = (hipStream_t)stream;
+  cuking_ctx::StreamScratch *e = stream_entry(ctx, s);
+  st = grow_on_stream(ctx, s, &e->record_count, sizeof(unsigned long long));
+  if (st != CUKING_OK) return st;
+  unsigned long long *d_count = static_cast<unsigned long long *>(e->record_count.p);
+  HIP_TRY(hipMemsetAsync(d_count, 0, sizeof(unsigned long long), s));
+  HIP_TRY(launch_pcrelate_records(d_bits, words_per_sample, num_sites, d_x, ldx, d_beta, ldbeta, d,
+                                  lo, hi, *block, min_kin, d_records, max_records, d_count, s));
+  unsigned long long count = 0;
+  HIP_TRY(hipMemcpyAsync(&count, d_count, sizeof(count), hipMemcpyDeviceToHost, s));
+  ++ctx->host_syncs;
+  HIP_TRY(hipStreamSynchronize(s));
+  *num_records = count;
+  return cuking_pcrelate_count_status(count, max_records);
 }
 
 cuking_status cuking_pcrelate_pairs(cuking_ctx *ctx, const uint64_t *d_bits, uint32_t num_stored,

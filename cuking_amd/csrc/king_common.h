@@ -668,6 +668,16 @@ hipError_t launch_pcrelate_matrix(const uint64_t *d_bits, uint32_t words_per_sam
                                   float hi, const cuking_submatrix &block, float *d_out,
                                   uint64_t ldo, hipStream_t stream);
 
+// PC-Relate records (king_pcrelate_records.hip; arguments already checked, king_host.h).  ADDS
+// the number of pairs of `block` with kin > min_kin to *d_count (zeroed by the caller, on the
+// stream) and stores the records whose slot is below max_records; num_sites == 0 adds nothing.
+hipError_t launch_pcrelate_records(const uint64_t *d_bits, uint32_t words_per_sample,
+                                   uint32_t num_sites, const float *d_x, uint32_t ldx,
+                                   const float *d_beta, uint32_t ldbeta, uint32_t d, float lo,
+                                   float hi, const cuking_submatrix &block, float min_kin,
+                                   cuking_result *d_records, uint64_t max_records,
+                                   unsigned long long *d_count, hipStream_t stream);
+
 // PC-Relate for listed pairs (king_pcrelate_pairs.hip; arguments already checked, king_host.h).
 // Plain stores into d_out[0 .. num_pairs); num_sites == 0 stores the NaN rows.
 hipError_t launch_pcrelate_pairs(const uint64_t *d_bits, uint32_t num_stored,

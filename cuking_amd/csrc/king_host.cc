@@ -707,12 +707,13 @@ cuking_status check_pcrelate_model(uint32_t words_per_sample, uint32_t num_sites
 
 }  // namespace
 
-cuking_status cuking_check_pcrelate_args(const void *bits, uint32_t num_stored,
-                                         uint32_t words_per_sample, uint32_t num_sites,
-                                         const void *x, uint32_t ldx, const void *beta,
-                                         uint32_t ldbeta, uint32_t d, float lo, float hi,
-                                         const cuking_submatrix *block, const void *out,
-                                         uint64_t ldo) {
+namespace {
+
+// What the matrix and the records share: the block, the model and the block inside the stored
+// samples.
+cuking_status check_pcrelate_block(uint32_t num_stored, uint32_t words_per_sample,
+                                   uint32_t num_sites, uint32_t ldx, uint32_t ldbeta, uint32_t d,
+                                   float lo, float hi, const cuking_submatrix *block) {
   cuking_status st = cuking_check_block(block, words_per_sample);
   if (st != CUKING_OK) return st;
   st = check_pcrelate_model(words_per_sample, num_sites, ldx, ldbeta, d, lo, hi);
@@ -722,6 +723,20 @@ cuking_status cuking_check_pcrelate_args(const void *bits, uint32_t num_stored,
                        "pcrelate: block rows [%u, %u) x columns [%u, %u) outside the %u stored "
                        "samples", block->i_begin, block->i_end, block->j_begin, block->j_end,
                        num_stored);
+  return CUKING_OK;
+}
+
+}  // namespace
+
+cuking_status cuking_check_pcrelate_args(const void *bits, uint32_t num_stored,
+                                         uint32_t words_per_sample, uint32_t num_sites,
+                                         const void *x, uint32_t ldx, const void *beta,
+                                         uint32_t ldbeta, uint32_t d, float lo, float hi,
+                                         const cuking_submatrix *block, const void *out,
+                                         uint64_t ldo) {
+  const cuking_status st = check_pcrelate_block(num_stored, words_per_sample, num_sites, ldx,
+                                                ldbeta, d, lo, hi, block);
+  if (st != CUKING_OK) return st;
   if (ldo < sm_num_cols(*block))
     return cuking_fail(CUKING_ERR_INVALID_ARGUMENT,
                        "pcrelate: output pitch %llu below the block's %u columns",
@@ -734,20 +749,49 @@ cuking_status cuking_check_pcrelate_args(const void *bits, uint32_t num_stored,
   return CUKING_OK;
 }
 
-extern "C" {
-
-cuking_status cuking_pcrelate_matrix_host(const uint64_t *bits, uint32_t num_stored,
-                                          uint32_t words_per_sample, uint32_t num_sites,
-                                          const float *x, uint32_t ldx, const float *beta,
-                                          uint32_t ldbeta, uint32_t d, float lo, float hi,
-                                          const cuking_submatrix *block, float *out,
-                                          uint64_t ldo) {
-  const cuking_status st = cuking_check_pcrelate_args(bits, num_stored, words_per_sample,
-                                                      num_sites, x, ldx, beta, ldbeta, d, lo, hi,
-                                                      block, out, ldo);
+cuking_status cuking_check_pcrelate_records_args(const void *bits, uint32_t num_stored,
+                                                 uint32_t words_per_sample, uint32_t num_sites,
+                                                 const void *x, uint32_t ldx, const void *beta,
+                                                 uint32_t ldbeta, uint32_t d, float lo, float hi,
+                                                 const cuking_submatrix *block, float min_kin,
+                                                 const void *records, uint64_t max_records,
+                                                 const void *num_records) {
+  const cuking_status st = check_pcrelate_block(num_stored, words_per_sample, num_sites, ldx,
+                                                ldbeta, d, lo, hi, block);
   if (st != CUKING_OK) return st;
-  const uint32_t rows = sm_num_rows(*block), cols = sm_num_cols(*block);
-  if (rows == 0 || cols == 0) return CUKING_OK;
+  if (min_kin != min_kin)
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "pcrelate records: min_kin is NaN");
+  if (num_records == nullptr)
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "pcrelate records: null num_records pointer");
+  if (records == nullptr && max_records != 0)
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT,
+                       "pcrelate records: null records pointer with max_records = %llu",
+                       (unsigned long long)max_records);
+  if (sm_num_rows(*block) == 0 || sm_num_cols(*block) == 0 || num_sites == 0) return CUKING_OK;
+  if (bits == nullptr || x == nullptr || beta == nullptr)
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "pcrelate records: null pointer");
+  return CUKING_OK;
+}
+
+cuking_status cuking_pcrelate_count_status(uint64_t count, uint64_t max_records) {
+  if (count > max_records)
+    return cuking_fail(CUKING_ERR_RESOURCE_EXHAUSTED,
+                       "pcrelate records: %llu records do not fit %llu: retry with that many",
+                       (unsigned long long)count, (unsigned long long)max_records);
+  return CUKING_OK;
+}
+
+namespace {
+
+// The host twin of both calls: visit(i, j, kin) for the pairs of `block` in ascending (i, j),
+// i and j counted from the block's first row and column; with `upper_only` the pairs i < j of
+// a diagonal block.  Sums in double, rounded once, divided in float32.
+template <class Visit>
+void pcrelate_host_scan(const uint64_t *bits, uint32_t words_per_sample, uint32_t num_sites,
+                        const float *x, uint32_t ldx, const float *beta, uint32_t ldbeta,
+                        uint32_t d, float lo, float hi, const cuking_submatrix &block,
+                        bool upper_only, Visit visit) {
+  const uint32_t rows = sm_num_rows(block), cols = sm_num_cols(block);
   const uint32_t plane_words = words_per_sample / 2;
   // r and v of the block's samples, [sample][site]: rows first, then columns
   const auto expand = [&](uint32_t begin, uint32_t count, std::vector<float> *r,
@@ -766,12 +810,12 @@ cuking_status cuking_pcrelate_matrix_host(const uint64_t *bits, uint32_t num_sto
     }
   };
   std::vector<float> ri, vi, rj, vj;
-  expand(block->i_begin, rows, &ri, &vi);
-  const bool diag = sm_is_diag(*block);
-  if (!diag) expand(block->j_begin, cols, &rj, &vj);
+  expand(block.i_begin, rows, &ri, &vi);
+  const bool diag = sm_is_diag(block);
+  if (!diag) expand(block.j_begin, cols, &rj, &vj);
   const std::vector<float> &rc = diag ? ri : rj, &vc = diag ? vi : vj;
   for (uint32_t i = 0; i < rows; ++i)
-    for (uint32_t j = 0; j < cols; ++j) {
+    for (uint32_t j = (diag && upper_only) ? i + 1 : 0; j < cols; ++j) {
       double num = 0.0, den = 0.0;
       const float *a = ri.data() + (size_t)i * num_sites, *b = rc.data() + (size_t)j * num_sites;
       const float *p = vi.data() + (size_t)i * num_sites, *q = vc.data() + (size_t)j * num_sites;
@@ -779,9 +823,75 @@ cuking_status cuking_pcrelate_matrix_host(const uint64_t *bits, uint32_t num_sto
         num += (double)a[s] * (double)b[s];
         den += (double)p[s] * (double)q[s];
       }
-      out[(uint64_t)i * ldo + j] = pcrelate_kin((float)num, (float)den);
+      visit(i, j, pcrelate_kin((float)num, (float)den));
     }
+}
+
+}  // namespace
+
+extern "C" {
+
+cuking_status cuking_pcrelate_matrix_host(const uint64_t *bits, uint32_t num_stored,
+                                          uint32_t words_per_sample, uint32_t num_sites,
+                                          const float *x, uint32_t ldx, const float *beta,
+                                          uint32_t ldbeta, uint32_t d, float lo, float hi,
+                                          const cuking_submatrix *block, float *out,
+                                          uint64_t ldo) {
+  const cuking_status st = cuking_check_pcrelate_args(bits, num_stored, words_per_sample,
+                                                      num_sites, x, ldx, beta, ldbeta, d, lo, hi,
+                                                      block, out, ldo);
+  if (st != CUKING_OK) return st;
+  if (sm_num_rows(*block) == 0 || sm_num_cols(*block) == 0) return CUKING_OK;
+  pcrelate_host_scan(bits, words_per_sample, num_sites, x, ldx, beta, ldbeta, d, lo, hi, *block,
+                     false, [&](uint32_t i, uint32_t j, float kin) {
+                       out[(uint64_t)i * ldo + j] = kin;
+                     });
   return CUKING_OK;
+}
+
+cuking_status cuking_pcrelate_records_host(const uint64_t *bits, uint32_t num_stored,
+                                           uint32_t words_per_sample, uint32_t num_sites,
+                                           const float *x, uint32_t ldx, const float *beta,
+                                           uint32_t ldbeta, uint32_t d, float lo, float hi,
+                                           const cuking_submatrix *block, float min_kin,
+                                           cuking_result *records, uint64_t max_records,
+                                           uint64_t *num_records) {
+  if (num_records != nullptr) *num_records = 0;
+  const cuking_status st = cuking_check_pcrelate_records_args(
+      bits, num_stored, words_per_sample, num_sites, x, ldx, beta, ldbeta, d, lo, hi, block,
+      min_kin, records, max_records, num_records);
+  if (st != CUKING_OK) return st;
+  // (without a site every kin is NaN: no record)
+  if (sm_num_rows(*block) == 0 || sm_num_cols(*block) == 0 || num_sites == 0) return CUKING_OK;
+  uint64_t count = 0;
+  pcrelate_host_scan(bits, words_per_sample, num_sites, x, ldx, beta, ldbeta, d, lo, hi, *block,
+                     true, [&](uint32_t i, uint32_t j, float kin) {
+                       if (!pcrelate_is_record(kin, min_kin)) return;
+                       if (count < max_records)
+                         records[count] = cuking_result{block->i_begin + i, block->j_begin + j,
+                                                        kin, 0, 0, 0};
+                       ++count;
+                     });
+  *num_records = count;
+  return cuking_pcrelate_count_status(count, max_records);
+}
+
+uint64_t cuking_pcrelate_triangle_tiles(uint64_t side) {
+  return side <= kPcrelateTriangleSideMax ? pcrelate_triangle_tiles(side) : 0;
+}
+
+uint64_t cuking_pcrelate_triangle_index(uint64_t side, uint32_t tile_i, uint32_t tile_j) {
+  if (side > kPcrelateTriangleSideMax || tile_j >= side || tile_i > tile_j) return UINT64_MAX;
+  return pcrelate_triangle_index(side, tile_i, tile_j);
+}
+
+uint32_t cuking_pcrelate_triangle_tile(uint64_t side, uint64_t index, uint32_t *tile_i,
+                                       uint32_t *tile_j) {
+  if (tile_i == nullptr || tile_j == nullptr || side > kPcrelateTriangleSideMax ||
+      index >= pcrelate_triangle_tiles(side))
+    return 0;
+  pcrelate_triangle_tile(side, index, tile_i, tile_j);
+  return 1;
 }
 
 }  // extern "C"

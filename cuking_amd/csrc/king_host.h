@@ -50,6 +50,17 @@ cuking_status cuking_check_pcrelate_args(const void *bits, uint32_t num_stored,
                                          uint32_t ldbeta, uint32_t d, float lo, float hi,
                                          const cuking_submatrix *block, const void *out,
                                          uint64_t ldo);
+// Argument checks of cuking_pcrelate_records_host / cuking_pcrelate_records (include/cuking_amd.h
+// "PC-Relate records" lists them: those of the matrix call through one shared check, then its
+// own), and the status of a record count: RESOURCE_EXHAUSTED above max_records.
+cuking_status cuking_check_pcrelate_records_args(const void *bits, uint32_t num_stored,
+                                                 uint32_t words_per_sample, uint32_t num_sites,
+                                                 const void *x, uint32_t ldx, const void *beta,
+                                                 uint32_t ldbeta, uint32_t d, float lo, float hi,
+                                                 const cuking_submatrix *block, float min_kin,
+                                                 const void *records, uint64_t max_records,
+                                                 const void *num_records);
+cuking_status cuking_pcrelate_count_status(uint64_t count, uint64_t max_records);
 // Argument checks of cuking_pcrelate_pairs_host / cuking_pcrelate_pairs (include/cuking_amd.h
 // "PC-Relate for listed pairs" lists them); OK says nothing about there being work to do.
 cuking_status cuking_check_pcrelate_pairs_args(const void *bits, uint32_t words_per_sample,

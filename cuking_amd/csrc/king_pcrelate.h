@@ -15,6 +15,11 @@
 // (4.0f * den) in IEEE float32 (NaN without a jointly valid site).  The zeros of the invalid
 // elements are what restricts both sums to the jointly valid sites.
 //
+// Records (include/cuking_amd.h, "PC-Relate records"; king_pcrelate_records.hip and
+// cuking_pcrelate_records_host).  The same sums and kin; pcrelate_is_record is the rule that
+// makes a pair a record, pcrelate_triangle_tile the map from a workgroup's number to its tile
+// when only the upper triangle of a diagonal block is launched.
+//
 // Listed pairs (include/cuking_amd.h, "PC-Relate for listed pairs"; king_pcrelate_pairs.hip and
 // cuking_pcrelate_pairs_host).  On top of the element above, with f the sample's inbreeding
 // coefficient: var = mu * (1.0f - mu), s2 = (1.0f + f) * var, dom = mu, 0.0f or 1.0f - mu for
@@ -62,6 +67,39 @@ CUKING_HD inline float pcrelate_kin(float num, float den) { return num / (4.0f *
 
 CUKING_HD inline bool pcrelate_bounds_valid(float lo, float hi) {
   return 0.0f <= lo && lo < hi && hi <= 1.0f;  // (false for a NaN)
+}
+
+// ---- records (include/cuking_amd.h, "PC-Relate records") -------------------------------------
+
+// A pair is a record iff its kinship is above the threshold: the strict float32 comparison of
+// a KING record, false for a NaN on either side.
+CUKING_HD inline bool pcrelate_is_record(float kin, float min_kin) { return kin > min_kin; }
+
+// Tiles of a diagonal block of `side` x `side` tiles: the upper triangle with its diagonal,
+// tile_j >= tile_i, numbered row by row -- row i holds side - i tiles and starts at
+// i side - i (i - 1) / 2.  side <= 2^25 (2^32 - 1 samples in tiles of 128), so every count is
+// below 2^50.
+constexpr uint64_t kPcrelateTriangleSideMax = 1ull << 25;  // (CUKING_PCRELATE_TRIANGLE_SIDE_MAX)
+
+CUKING_HD inline uint64_t pcrelate_triangle_tiles(uint64_t side) { return side * (side + 1) / 2; }
+
+CUKING_HD inline uint64_t pcrelate_triangle_index(uint64_t side, uint32_t tile_i, uint32_t tile_j) {
+  const uint64_t i = tile_i;
+  return i * (2 * side - i + 1) / 2 + (tile_j - i);  // (one of the two factors is even)
+}
+
+// The inverse.  Counted from the END, the triangle is rows of 1, 2, 3, ... tiles: `back` tiles
+// behind `index` put it into row m from the end, m the largest with m (m + 1) / 2 <= back.  The
+// square root (8 back + 1 < 2^53 is exact in a double) only proposes m; the two loops make it
+// exact whatever the rounding of sqrt.
+CUKING_HD inline void pcrelate_triangle_tile(uint64_t side, uint64_t index, uint32_t *tile_i,
+                                             uint32_t *tile_j) {
+  const uint64_t back = pcrelate_triangle_tiles(side) - 1 - index;
+  uint64_t m = (uint64_t)((sqrt((double)(8 * back + 1)) - 1.0) * 0.5);
+  while (m * (m + 1) / 2 > back) --m;
+  while ((m + 1) * (m + 2) / 2 <= back) ++m;
+  *tile_i = (uint32_t)(side - 1 - m);
+  *tile_j = (uint32_t)(side - 1 - (back - m * (m + 1) / 2));
 }
 
 // ---- listed pairs ----------------------------------------------------------------------------

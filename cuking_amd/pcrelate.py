@@ -16,6 +16,11 @@ definition).  The same model evaluated on a list of pairs -- the records of ``co
 an int ``[P, 2]`` array -- gives ``kin``, ``k0``, ``k1``, ``k2``, ``ibs0`` and ``sites`` per
 pair without a matrix; the inbreeding coefficients its ``k2`` needs come from the self pairs
 ``(s, s)``: ``f = 2 kin(s, s) - 1``.
+
+Records (``pcrelate_records``; include/cuking_amd.h "PC-Relate records" holds the definition).
+The pairs of a block with ``kin > min_kinship`` as the records ``compute_king`` writes, without
+a matrix: the list ``pcrelate_pairs`` and ``unrelated_set`` take, drawn from the ancestry-adjusted
+kinship itself.
 """
 from __future__ import annotations
 
@@ -369,7 +374,7 @@ def _inbreeding_of(self_rows: np.ndarray) -> np.ndarray:
 def _model_of(model):
     for name in ("x", "beta", "sites_used", "fit"):
         if not hasattr(model, name):
-            raise ValueError("model must be a PCRelateResult or a PCRelatePairs, not "
+            raise ValueError("model must be a PCRelateResult, PCRelateRecords or PCRelatePairs, not "
                              f"{type(model).__name__}")
     return model.x, model.beta, model.sites_used, model.fit
 
@@ -506,3 +511,191 @@ def pcrelate_pairs_device(ctx, bits, words_per_sample: int, num_sites: int, pair
     if stream is not None:
         stream.synchronize()
     return PCRelatePairs(pairs_to_host(rows), f, beta, used, fit_mask, x)
+
+
+# ---- records: the pairs above a kinship threshold ----------------------------------------------
+
+@dataclass
+class PCRelateRecords:
+    """What ``KingContext.pcrelate_records`` / ``pcrelate_records_host`` return: ``records``
+    (the first ``num_records`` rows are the pairs with ``kin > min_kinship``, ``sample_i <
+    sample_j``, in no particular order: the int32 ``[*, 6]`` device tensor ``unrelated_set`` and
+    ``pcrelate_pairs`` take, or ``KING_RESULT_DTYPE`` rows from the host twin), ``num_records``,
+    ``min_kinship``, ``block`` and the model: ``beta``, ``sites_used``, ``fit``, ``x`` as in
+    ``PCRelateResult`` -- which makes the object the ``model`` argument of ``pcrelate_pairs``."""
+    records: object
+    num_records: int
+    min_kinship: float
+    block: Submatrix
+    beta: np.ndarray
+    sites_used: np.ndarray
+    fit: np.ndarray
+    x: np.ndarray
+
+    def sorted(self) -> np.ndarray:
+        """The records as ``KING_RESULT_DTYPE`` rows on the host, by ``(sample_i, sample_j)``
+        (a copy; waits for it)."""
+        return records_to_host(self.records, self.num_records)
+
+
+def records_to_host(records, num_records: int) -> np.ndarray:
+    """The first ``num_records`` rows of a record buffer (the ``[*, 6]`` int32 device tensor or
+    host ``KING_RESULT_DTYPE`` rows) as sorted ``KING_RESULT_DTYPE`` rows on the host."""
+    from .api import sort_results
+    if isinstance(records, np.ndarray):
+        rows = records[:num_records].copy()
+    else:
+        rows = np.ascontiguousarray(records[:num_records].cpu().numpy()) \
+            .view(KING_RESULT_DTYPE).reshape(-1).copy()
+    return sort_results(rows)
+
+
+def _min_kin(min_kin) -> float:
+    min_kin = float(np.float32(min_kin))
+    if min_kin != min_kin:
+        raise ValueError("pcrelate records: min_kin must not be NaN")
+    return min_kin
+
+
+def _default_records(block: Submatrix) -> int:
+    """The buffer of a call without ``max_records``: 16 records per sample of the block, at
+    most its pairs (the call is repeated once with the exact count if that overflows)."""
+    rows, cols = max(block.i_end - block.i_begin, 0), max(block.j_end - block.j_begin, 0)
+    pairs = rows * (rows - 1) // 2 if block.i_begin == block.j_begin else rows * cols
+    return max(1, min(pairs, 16 * (rows + cols)))
+
+
+def _exhausted(count: int):
+    from .api import ResourceExhaustedError
+    e = ResourceExhaustedError(_lib.load().cuking_last_error().decode())
+    e.num_records = count
+    return e
+
+
+def pcrelate_records_raw_host(bits: np.ndarray, words_per_sample: int, num_sites: int, x, beta,
+                              lo: float, hi: float, min_kin: float, block=None,
+                              max_records=None):
+    """cuking_pcrelate_records_host, the bare call: the pairs of ``block`` (as
+    ``pcrelate_matrix_host`` takes it) with ``kin > min_kin`` as ``(records, count)``,
+    ``KING_RESULT_DTYPE`` rows in ascending ``(sample_i, sample_j)`` with the kinship bytes of
+    ``pcrelate_matrix_host``.  The buffer rule is ``ld_edges_host``'s: without ``max_records`` a
+    default buffer, grown once to the exact count; with it, an overflow raises
+    ``ResourceExhaustedError`` whose ``num_records`` is the exact count."""
+    assert bits.dtype == np.uint64 and bits.flags.c_contiguous
+    words_per_sample = _count(words_per_sample, "words_per_sample")
+    num_sites = _count(num_sites, "num_sites")
+    num_stored = bits.size // words_per_sample if words_per_sample else 0
+    x = _geno_host_matrix(x, "x", num_stored)
+    beta = _geno_host_matrix(beta, "beta", num_sites, x.shape[1])
+    block = _block(block, num_stored)
+    min_kin = _min_kin(min_kin)
+    d = x.shape[1]
+    pad = np.zeros(4, dtype=np.float32)
+    count = C.c_uint64(0)
+
+    def call(capacity):
+        recs = np.zeros(max(capacity, 1), dtype=KING_RESULT_DTYPE)
+        status = _lib.load().cuking_pcrelate_records_host(
+            (bits if bits.size else pad).ctypes.data, num_stored, words_per_sample, num_sites,
+            (x if x.size else pad).ctypes.data, max(x.strides[0] // 4, d),
+            (beta if beta.size else pad).ctypes.data, max(beta.strides[0] // 4, d), d, lo, hi,
+            C.byref(block.c), min_kin, recs.ctypes.data, capacity, C.byref(count))
+        return recs, status
+
+    recs, status = call(_default_records(block) if max_records is None
+                        else _count(max_records, "max_records"))
+    if status == _lib.ERR_RESOURCE_EXHAUSTED and max_records is None:
+        recs, status = call(int(count.value))
+    if status == _lib.ERR_RESOURCE_EXHAUSTED:
+        raise _exhausted(int(count.value))
+    check(status)
+    return recs[:count.value].copy(), int(count.value)
+
+
+def pcrelate_records_host(bits: np.ndarray, words_per_sample: int, num_sites: int, scores=None,
+                          model=None, fit=None, min_maf: float = 0.01,
+                          min_kinship: float = KING_CUTOFFS[0], block=None,
+                          max_records=None) -> PCRelateRecords:
+    """``KingContext.pcrelate_records`` on host memory and the host twins: no GPU."""
+    lo, hi = _bounds(min_maf)
+    words_per_sample = _count(words_per_sample, "words_per_sample")
+    num_sites = _count(num_sites, "num_sites")
+    if (scores is None) == (model is None):
+        raise ValueError("pcrelate records: give either scores or model")
+    if model is not None:
+        x, beta, used, fit_mask = _model_of(model)
+    else:
+        op = HostIsafOperator(bits, words_per_sample, num_sites, fit)
+        x, beta, used = isaf_fit(op, scores)
+        fit_mask = op.fit
+    block = _block(block, bits.size // words_per_sample if words_per_sample else 0)
+    recs, count = pcrelate_records_raw_host(bits, words_per_sample, num_sites, x, beta, lo, hi,
+                                            min_kinship, block, max_records)
+    return PCRelateRecords(recs, count, _min_kin(min_kinship), block, beta, used, fit_mask, x)
+
+
+def pcrelate_records_raw_device(ctx, bits, words_per_sample: int, num_sites: int, x, beta,
+                                lo: float, hi: float, min_kin: float, block=None,
+                                max_records=None, out=None, stream=None):
+    import torch
+    from .api import _device_tensor, _stream_handle
+    num_stored = ctx._rows_of(bits, words_per_sample)
+    num_sites = _count(num_sites, "num_sites")
+    x = ctx._geno_matrix(x, "x", num_stored)
+    d = x.shape[1]
+    beta = ctx._geno_matrix(beta, "beta", num_sites, d)
+    block = _block(block, num_stored)
+    min_kin = _min_kin(min_kin)
+    dev = f"cuda:{ctx.device}"
+    if out is not None:
+        _device_tensor(ctx.device, out, "out", torch.int32, cols=6)
+        max_records = out.shape[0] if max_records is None else max_records
+        if _count(max_records, "max_records") > out.shape[0]:
+            raise ValueError(f"out holds {out.shape[0]} records, max_records is {max_records}")
+    count = C.c_uint64(0)
+
+    def call(records, capacity):
+        return ctx.lib.cuking_pcrelate_records(
+            ctx.handle, bits.data_ptr(), num_stored, words_per_sample, num_sites, x.data_ptr(),
+            max(x.stride(0), d), beta.data_ptr(), max(beta.stride(0), d), d, lo, hi,
+            C.byref(block.c), min_kin, records.data_ptr() if capacity else None, capacity,
+            C.byref(count), _stream_handle(stream))
+
+    grow = max_records is None
+    capacity = _default_records(block) if grow else _count(max_records, "max_records")
+    records = out if out is not None else torch.empty((max(capacity, 1), 6), dtype=torch.int32,
+                                                      device=dev)
+    status = call(records, capacity)
+    if status == _lib.ERR_RESOURCE_EXHAUSTED and grow:
+        capacity = int(count.value)
+        records = torch.empty((capacity, 6), dtype=torch.int32, device=dev)
+        status = call(records, capacity)
+    if status == _lib.ERR_RESOURCE_EXHAUSTED:
+        raise _exhausted(int(count.value))
+    check(status)
+    return records, int(count.value)
+
+
+def pcrelate_records_device(ctx, bits, words_per_sample: int, num_sites: int, scores=None,
+                            model=None, fit=None, min_maf: float = 0.01,
+                            min_kinship: float = KING_CUTOFFS[0], block=None,
+                            max_records=None) -> PCRelateRecords:
+    import torch
+    lo, hi = _bounds(min_maf)
+    words_per_sample = _count(words_per_sample, "words_per_sample")
+    num_sites = _count(num_sites, "num_sites")
+    if (scores is None) == (model is None):
+        raise ValueError("pcrelate records: give either scores or model")
+    dev = f"cuda:{ctx.device}"
+    if model is not None:
+        x, beta, used, fit_mask = _model_of(model)
+    else:
+        op = DeviceIsafOperator(ctx, bits, words_per_sample, num_sites, fit)
+        x, beta, used = isaf_fit(op, scores)
+        fit_mask = op.fit
+    block = _block(block, ctx._rows_of(bits, words_per_sample))
+    d_x = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).to(dev)
+    d_beta = torch.from_numpy(np.ascontiguousarray(beta, dtype=np.float32)).to(dev)
+    records, count = pcrelate_records_raw_device(ctx, bits, words_per_sample, num_sites, d_x,
+                                                 d_beta, lo, hi, min_kinship, block, max_records)
+    return PCRelateRecords(records, count, _min_kin(min_kinship), block, beta, used, fit_mask, x)

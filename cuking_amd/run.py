@@ -155,11 +155,23 @@ def parse_args(argv=None):
               "with the scores and the fit of this run's --pca-uri -- and write them to this .npz "
               "(with sample_i, sample_j, inbreeding, samples).  Needs --pca-uri; one process and "
               "--split-factor 1 only")
+    flag("pcrelate-records-uri", default="",
+         help="also scan ALL pairs of the cohort with PC-Relate -- no matrix, ancestry-adjusted "
+              "with the scores and the fit of this run's --pca-uri -- and write the pairs whose "
+              "kinship is above --pcrelate-min-kinship to this .npz: sample_i, sample_j, kin, "
+              "then k0, k1, k2, ibs0, sites, kin_pairs and the relationship code of those pairs "
+              "(with samples, min_kinship, num_records).  Needs --pca-uri; one process and "
+              "--split-factor 1 only")
+    flag("pcrelate-min-kinship", type=float, default=None,
+         help="the threshold of --pcrelate-records-uri: pairs with a kinship strictly above it "
+              "(default 0.0442, the third-degree cut-off)")
     flag("pcrelate-components", type=int, default=None,
-         help="the number of leading components --pcrelate-uri and --pcrelate-pairs-uri adjust "
+         help="the number of leading components --pcrelate-uri, --pcrelate-pairs-uri and "
+              "--pcrelate-records-uri adjust "
               "for (default: all of --pca-components; at most 31)")
     flag("pcrelate-min-maf", type=float, default=None,
-         help="--pcrelate-uri and --pcrelate-pairs-uri use the elements whose "
+         help="--pcrelate-uri, --pcrelate-pairs-uri and --pcrelate-records-uri use the elements "
+              "whose "
               "individual-specific allele frequency lies strictly between this and 1 minus this "
               "(default 0.01)")
     return ap.parse_args(argv)
@@ -286,7 +298,7 @@ def validate(args):  # cuking.cu:437-462
         if args.pca_components is not None and args.pca_components < 1:
             raise UsageError("--pca_components must be at least 1")
     if (args.pcrelate_components is not None or args.pcrelate_min_maf is not None) and \
-            not (args.pcrelate_uri or args.pcrelate_pairs_uri):
+            not (args.pcrelate_uri or args.pcrelate_pairs_uri or args.pcrelate_records_uri):
         raise UsageError("--pcrelate_components and --pcrelate_min_maf need --pcrelate_uri or "
                          "--pcrelate_pairs_uri")
     if args.pcrelate_pairs_uri:
@@ -299,6 +311,21 @@ def validate(args):  # cuking.cu:437-462
         if not args.pca_uri:
             raise UsageError("--pcrelate_pairs_uri needs the principal components of the same "
                              "run: pass --pca_uri as well")
+    if args.pcrelate_min_kinship is not None and not args.pcrelate_records_uri:
+        raise UsageError("--pcrelate_min_kinship needs --pcrelate_records_uri")
+    if args.pcrelate_records_uri:
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            raise UsageError("--pcrelate_records_uri needs one process (one GPU): the scan is "
+                             "not split across ranks yet")
+        if args.split_factor != 1:
+            raise UsageError("--pcrelate_records_uri needs --split_factor 1: it scans the whole "
+                             "cohort's pairs")
+        if not args.pca_uri:
+            raise UsageError("--pcrelate_records_uri needs the principal components of the same "
+                             "run: pass --pca_uri as well")
+        t = args.pcrelate_min_kinship
+        if t is not None and t != t:
+            raise UsageError("--pcrelate_min_kinship must not be NaN")
     if args.pcrelate_uri:
         if int(os.environ.get("WORLD_SIZE", "1")) > 1:
             raise UsageError("--pcrelate_uri needs one process (one GPU): the matrix is not "
@@ -309,7 +336,7 @@ def validate(args):  # cuking.cu:437-462
         if not args.pca_uri:
             raise UsageError("--pcrelate_uri needs the principal components of the same run: "
                              "pass --pca_uri as well")
-    if args.pcrelate_uri or args.pcrelate_pairs_uri:
+    if args.pcrelate_uri or args.pcrelate_pairs_uri or args.pcrelate_records_uri:
         pca_k = 10 if args.pca_components is None else args.pca_components
         k = pcrelate_components(args)
         if k < 1 or k > pca_k:
@@ -562,6 +589,31 @@ def write_pcrelate_pairs(path: Path, ctx, bits, wps: int, num_sites: int, pca, c
                  samples=np.array(list(sample_ids), dtype=str))
 
 
+def write_pcrelate_records(path: Path, ctx, bits, wps: int, num_sites: int, pca, components: int,
+                           min_maf: float, min_kinship: float, sample_ids) -> None:
+    """The pairs of the whole cohort whose PC-Relate kinship is above `min_kinship` as an .npz:
+    `sample_i`, `sample_j`, `kin` of the records sorted by (sample_i, sample_j); `k0`, `k1`,
+    `k2`, `ibs0`, `sites`, `kin_pairs` (the pairs' own kinship) and `relationship` of
+    pcrelate_pairs on them, in the same order; `samples`, `min_kinship`, `num_records`."""
+    import torch
+    scores = np.ascontiguousarray(pca.scores[:, :components])
+    found = ctx.pcrelate_records(bits, wps, num_sites, scores=scores, fit=pca.fit,
+                                 min_maf=min_maf, min_kinship=min_kinship)
+    rows = found.sorted()
+    dev = f"cuda:{ctx.device}"
+    flat = torch.from_numpy(rows.view(np.int32).reshape(-1, 6).copy()).to(dev)
+    got = ctx.pcrelate_pairs(bits, wps, num_sites, flat, model=found, min_maf=min_maf,
+                             num_records=found.num_records)
+    path.parent.mkdir(parents=True, exist_ok=True)
+    with open(path, "wb") as f:   # (np.savez would append .npz to another suffix)
+        np.savez(f, sample_i=rows["sample_i"], sample_j=rows["sample_j"], kin=rows["kin"],
+                 k0=got.k0, k1=got.k1, k2=got.k2, ibs0=got.ibs0, sites=got.sites,
+                 kin_pairs=got.kin, relationship=got.relationship(),
+                 samples=np.array(list(sample_ids), dtype=str),
+                 min_kinship=np.float32(found.min_kinship),
+                 num_records=np.int64(found.num_records))
+
+
 def site_qc(ctx, args, bits, wps: int, num_sites: int, sample_ids, keep_path, qc_path):
     """Site QC of the whole cohort's bitset: counts on the GPU, the rule on the host, the
     report if one is asked for, and -- with a flag that selects sites -- the compacted bitset.
@@ -638,6 +690,8 @@ def main(argv=None) -> int:
         pca_path = resolve_uri(args.pca_uri) if args.pca_uri else None
         pcrelate_path = resolve_uri(args.pcrelate_uri) if args.pcrelate_uri else None
         pairs_path = resolve_uri(args.pcrelate_pairs_uri) if args.pcrelate_pairs_uri else None
+        records_path = resolve_uri(args.pcrelate_records_uri) if args.pcrelate_records_uri \
+            else None
         synthetic = None
         if args.synthetic:
             parts = [int(x) for x in args.synthetic.split(",")]
@@ -808,6 +862,13 @@ def main(argv=None) -> int:
                                          pcrelate_components(args),
                                          0.01 if args.pcrelate_min_maf is None
                                          else args.pcrelate_min_maf, recs, sample_ids)
+                if records_path is not None:
+                    write_pcrelate_records(records_path, ctx, bits[:stored], wps, num_sites, pca,
+                                           pcrelate_components(args),
+                                           0.01 if args.pcrelate_min_maf is None
+                                           else args.pcrelate_min_maf,
+                                           0.0442 if args.pcrelate_min_kinship is None
+                                           else args.pcrelate_min_kinship, sample_ids)
             pairs = sm.NumPairs()
             print(json.dumps({"pairs": pairs, "results": int(len(recs)), "gpus": world,
                               "compute_seconds": dt,

@@ -945,7 +945,8 @@ cuking_status cuking_geno_matmul(cuking_ctx *ctx, const uint64_t *d_bits, uint32
  * num_sites == 0 writes NaN.
  * Out of scope: the C++ `cuking` binary; several ranks; half-precision operands; a triangular
  * launch for diagonal blocks; GENESIS's "truncate" bound and its kinship rescaling.  (The
- * IBD-sharing k0 / k2 and re-scoring only listed pairs: the section below.) */
+ * pairs above a threshold without a matrix, the IBD-sharing k0 / k2 and re-scoring only listed
+ * pairs: the sections below.) */
 #define CUKING_PCRELATE_COLUMNS_MAX 32
 cuking_status cuking_pcrelate_matrix_host(const uint64_t *bits, uint32_t num_stored,
                                           uint32_t words_per_sample, uint32_t num_sites,
@@ -959,6 +960,72 @@ cuking_status cuking_pcrelate_matrix(cuking_ctx *ctx, const uint64_t *d_bits, ui
                                      uint32_t ldbeta, uint32_t d, float lo, float hi,
                                      const cuking_submatrix *block, float *d_out, uint64_t ldo,
                                      void *stream);
+
+/* PC-Relate records: the pairs of a block whose ancestry-adjusted kinship is above a threshold,
+ * as cuking_result records and without a matrix -- the PC-Relate counterpart of
+ * cuking_compute_king (hl.pc_relate(min_kinship=...), GENESIS pcrelate followed by a filter).
+ * Memory is proportional to the number of relatives, and a list drawn here holds the
+ * cross-ancestry relatives a KING threshold misses.  The records are what cuking_unrelated_set
+ * and cuking_pcrelate_pairs (stride 24) take.
+ *
+ *     bits, num_stored, words_per_sample, num_sites, X, ldx, beta, ldbeta, d, lo, hi, block
+ *                 exactly as cuking_pcrelate_matrix takes them
+ *     min_kin     float32 threshold, not NaN (-inf and +inf are allowed)
+ *     records     room for max_records cuking_result; may be null when max_records == 0
+ *     num_records HOST memory: receives the number of qualifying pairs
+ *
+ * Pairs of a block: a diagonal block (identical ranges) has the entries with i < j, an
+ * off-diagonal block (disjoint ranges, rows first) every entry; the diagonal is never a record.
+ * A pair is a record iff kin(i, j) > min_kin, the strict float32 comparison a KING record
+ * makes, kin being pcrelate_kin(num, den) of the section above from the same r, v and chains.
+ * The comparison is false for a NaN: a pair without a jointly valid site is never a record, not
+ * even at min_kin = -inf.  A record is {sample_i = i, sample_j = j, kin, ibs0 = ibs1 = ibs2 = 0}
+ * with sample_i < sample_j, i and j indices of the stored samples.
+ *
+ * Device: kin is the same bytes as the entry cuking_pcrelate_matrix writes for that pair, in
+ * any block that holds it; only the upper triangle of a diagonal block's tiles is launched
+ * (csrc/king_pcrelate.h: pcrelate_triangle_tile).  The ORDER of the records is unspecified and
+ * may differ between calls: the set is the contract (sort with cuking_sort_results).  Host
+ * twin: kin is the same bytes as cuking_pcrelate_matrix_host, records in ascending (i, j).
+ *
+ * EVERY qualifying pair is counted, those whose slot is below max_records are stored, and
+ * *num_records receives the exact count (it starts at zero on every call).  A count above
+ * max_records returns RESOURCE_EXHAUSTED with nothing written past the buffer -- which of the
+ * records were stored is then unspecified on the device, the first max_records on the host --
+ * and the caller retries with exactly *num_records; max_records == 0 with null records is the
+ * counting call.  There is no 2^30 limit here; cuking_unrelated_set has its own.
+ * cuking_pcrelate_records WAITS for `stream` (it reads the count back).
+ *
+ * INVALID_ARGUMENT before any device is touched: everything cuking_pcrelate_matrix refuses
+ * about the model and the block, through the same check; a NaN min_kin; a null num_records; a
+ * null records with max_records != 0; and, with work to do, a null bits, X or beta.  An empty
+ * block, a 1 x 1 diagonal block and num_sites == 0 give 0 records and OK.
+ *
+ * cuking_pcrelate_triangle_tiles / _index / _tile expose the tile map of a diagonal block for
+ * tests: side x side tiles, the tiles tile_j >= tile_i numbered row by row; side at most
+ * CUKING_PCRELATE_TRIANGLE_SIDE_MAX.  _tiles returns 0, _index UINT64_MAX and _tile 0 for
+ * arguments outside the map.
+ * Out of scope: the C++ `cuking` binary; several ranks; a triangular MATRIX call; IBS counts in
+ * the record; k0 / k2 inside the scan (cuking_pcrelate_pairs on the records gives them). */
+#define CUKING_PCRELATE_TRIANGLE_SIDE_MAX (1ull << 25)
+cuking_status cuking_pcrelate_records_host(const uint64_t *bits, uint32_t num_stored,
+                                           uint32_t words_per_sample, uint32_t num_sites,
+                                           const float *x, uint32_t ldx, const float *beta,
+                                           uint32_t ldbeta, uint32_t d, float lo, float hi,
+                                           const cuking_submatrix *block, float min_kin,
+                                           cuking_result *records, uint64_t max_records,
+                                           uint64_t *num_records);
+cuking_status cuking_pcrelate_records(cuking_ctx *ctx, const uint64_t *d_bits,
+                                      uint32_t num_stored, uint32_t words_per_sample,
+                                      uint32_t num_sites, const float *d_x, uint32_t ldx,
+                                      const float *d_beta, uint32_t ldbeta, uint32_t d, float lo,
+                                      float hi, const cuking_submatrix *block, float min_kin,
+                                      cuking_result *d_records, uint64_t max_records,
+                                      uint64_t *num_records, void *stream);
+uint64_t cuking_pcrelate_triangle_tiles(uint64_t side);
+uint64_t cuking_pcrelate_triangle_index(uint64_t side, uint32_t tile_i, uint32_t tile_j);
+uint32_t cuking_pcrelate_triangle_tile(uint64_t side, uint64_t index, uint32_t *tile_i,
+                                       uint32_t *tile_j);
 
 /* PC-Relate for listed pairs: kinship and the IBD-sharing coefficients k0, k1, k2 of a LIST of
  * pairs -- typically the records of cuking_compute_king -- without a matrix (the estimators of
