@@ -21,5 +21,7 @@ from .pcrelate import (PCRELATE_PAIR_DTYPE, PCRelatePairs, PCRelateRecords,  # n
                        PCRelateResult, isaf_fit, pcrelate_host, pcrelate_matrix_host,
                        pcrelate_pairs_host, pcrelate_pairs_raw_host, pcrelate_records_host,
                        pcrelate_records_raw_host)
+from .ibd import (IBD_PAIR_DTYPE, IBD_SEGMENT_DTYPE, IBDPairs, genome_length,  # noqa: F401
+                  ibd_segments_host, ibd_segments_raw_host)
 
 __version__ = "0.1.0"

@@ -36,6 +36,8 @@ PCRELATE_COLUMNS_MAX = 32
 PCRELATE_TRIANGLE_SIDE_MAX = 1 << 25
 PCRELATE_K0_SWITCH =0.17677669529663689   # (rounded to float32 where it is compared)
 
+IBD_MIN_SITES = 64
+
 
 class CKinBins(C.Structure):
     """cuking_kin_bins: the histogram of a kinship summary."""
@@ -185,6 +187,10 @@ SIGNATURES = {
                                           _f32, _f32, _vp, _vp, _u64, _u32, _vp]),
     "cuking_pcrelate_pairs": (_int, [_vp, _vp, _u32, _u32, _u32, _vp, _u32, _vp, _u32, _u32,
                                      _f32, _f32, _vp, _vp, _u64, _u32, _vp, _vp]),
+    "cuking_ibd_pairs_host": (_int, [_vp, _u32, _u32, _u32, _vp, _vp, _u32, _u32, _vp, _u64,
+                                     _u32, _vp, _vp, _u64, C.POINTER(_u64)]),
+    "cuking_ibd_pairs": (_int, [_vp, _vp, _u32, _u32, _u32, _vp, _vp, _u32, _u32, _vp, _u64,
+                                _u32, _vp, _vp, _u64, C.POINTER(_u64), _vp]),
     "cuking_sort_results": (None, [_vp, _sz]),
     "cuking_timing_enable": (_int, [_vp, _int]),
     "cuking_timing_reset": (_int, [_vp]),

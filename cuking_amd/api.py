@@ -1193,6 +1193,45 @@ class KingContext:
                                           inbreeding=inbreeding, num_records=num_records,
                                           stream=stream)
 
+    def ibd_segments_raw(self, bits, words_per_sample: int, num_sites: int, pairs, group=None,
+                         pos=None, min_sites: int = 512, min_length: int = 0,
+                         segments: bool = False, max_segments=None, num_records=None, out=None,
+                         stream=None):
+        """The bare kernel call for IBD segments (cuking_ibd_pairs; include/cuking_amd.h "IBD
+        segments for listed pairs" has the definition): for every pair of ``pairs`` (as
+        ``pcrelate_pairs_raw`` takes them) the number, summed length and longest of the runs of
+        at least ``min_sites`` sites and ``min_length`` positions without an opposite
+        homozygote (kind 1) and without a difference (kind 2).  ``group``: int32
+        ``[num_sites]`` (chromosomes, as ``ld_prune`` takes them) and ``pos``: uint32
+        ``[num_sites]`` (non-decreasing inside a group), host arrays or int32 device tensors;
+        None = one group, the site index.  Returns ``(rows, segments, num_segments)``: an int32
+        ``[P, 10]`` device tensor, one cuking_ibd_pair per row in input order
+        (``ibd.rows_to_host`` gives it names; ``out``: such a tensor to write into), and with
+        ``segments`` (or a ``max_segments``) an int32 ``[*, 4]`` device tensor whose first
+        ``num_segments`` rows are cuking_ibd_segment in no particular order, else None and 0.
+        Without ``max_segments`` the buffer is grown once to the exact count; with it an
+        overflow raises ``ResourceExhaustedError`` whose ``num_segments`` is the exact count.
+        Waits for the stream when ``pos`` is given or segments are counted."""
+        from . import ibd as _ibd
+        return _ibd.ibd_segments_raw_device(self, bits, words_per_sample, num_sites, pairs, group,
+                                            pos, min_sites, min_length, segments, max_segments,
+                                            num_records, out, stream)
+
+    def ibd_segments(self, bits, words_per_sample: int, num_sites: int, pairs, group=None,
+                     pos=None, min_sites: int = 512, min_length: int = 0, segments: bool = False,
+                     max_segments=None, num_records=None, stream=None):
+        """IBD segments of a list of pairs -- typically the records of ``compute_king`` with
+        ``num_records`` -- as an ``IBDPairs`` of host arrays (arguments as ``ibd_segments_raw``
+        takes them): its ``proportions()`` are the IBD1 / IBD2 shares of ``genome_length`` and
+        a kinship, its ``relationship()`` the degree with the parent-child / full-sibling
+        split, with no allele frequency and no principal component involved.  One wrong
+        homozygote splits a segment: there is no tolerance for genotyping errors.  Waits for
+        the device."""
+        from . import ibd as _ibd
+        return _ibd.ibd_segments_device(self, bits, words_per_sample, num_sites, pairs, group,
+                                        pos, min_sites, min_length, segments, max_segments,
+                                        num_records, stream)
+
     def synth_bitset(self, seed: int, kind, pa, pb, sample_begin: int,
                      sample_end: int, num_sites: int, out=None, stream=None, model=0):
         """Synthetic reference-layout bitset rows [sample_begin, sample_end)

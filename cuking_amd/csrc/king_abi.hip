@@ -13,6 +13,7 @@
 #include "king_common.h"
 #include "king_geno.h"
 #include "king_host.h"
+#include "king_ibd.h"
 #include "king_kin_summary.h"
 #include "king_ld.h"
 #include "king_site_qc.h"
@@ -133,8 +134,10 @@ struct cuking_ctx {
     // Grown when a call needs more (grow_on_stream below): cuking_unrelated_set's workspace
     // (king_prune.hip), cuking_compact_sites' table (king_site_qc.h) and the record counter of
     // cuking_ld_edges and cuking_pcrelate_records (one word; each call zeroes it on the stream
-    // and has read it back when it returns).
-    DeviceBuf prune, sites, record_count;
+    // and has read it back when it returns; cuking_ibd_pairs counts its segments there too),
+    // and the group-start bitmask of cuking_ibd_pairs (king_ibd.h; each call rebuilds it on
+    // the stream).
+    DeviceBuf prune, sites, record_count, ibd_groups;
   };
   std::vector<StreamScratch> scratch;
   // The running totals of filter scratch that has been freed since (a larger block took
@@ -354,7 +357,7 @@ void free_split_slab(cuking_ctx::StreamScratch &e) {
 void free_stream_scratch(cuking_ctx *ctx, cuking_ctx::StreamScratch &e, bool retire_totals) {
   free_filter_scratch(ctx, e, retire_totals);
   free_split_slab(e);
-  for (cuking_ctx::DeviceBuf *b : {&e.prune, &e.sites, &e.record_count}) {
+  for (cuking_ctx::DeviceBuf *b : {&e.prune, &e.sites, &e.record_count, &e.ibd_groups}) {
     if (b->p != nullptr) (void)hipFree(b->p);
     *b = {};
   }
@@ -2117,6 +2120,64 @@ cuking_status cuking_pcrelate_pairs(cuking_ctx *ctx, const uint64_t *d_bits, uin
                                 ldbeta, d, lo, hi, d_f, d_pairs, num_pairs, pair_stride, d_out,
                                 (hipStream_t)stream));
   return CUKING_OK;
+}
+
+// ---- IBD segments for listed pairs (king_ibd.hip) ------------------------------
+
+cuking_status cuking_ibd_pairs(cuking_ctx *ctx, const uint64_t *d_bits, uint32_t num_stored,
+                               uint32_t words_per_sample, uint32_t num_sites,
+                               const int32_t *d_group, const uint32_t *d_pos, uint32_t min_sites,
+                               uint32_t min_length, const void *d_pairs, uint64_t num_pairs,
+                               uint32_t pair_stride, cuking_ibd_pair *d_out,
+                               cuking_ibd_segment *d_segments, uint64_t max_segments,
+                               uint64_t *num_segments, void *stream) {
+  if (num_segments != nullptr) *num_segments = 0;
+  // (the arguments first: a refused call touches no device)
+  if (ctx == nullptr) return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "null context");
+  cuking_status st = cuking_check_ibd_args(d_bits, words_per_sample, num_sites, min_sites,
+                                           d_pairs, num_pairs, pair_stride, d_out, d_segments,
+                                           max_segments, num_segments);
+  if (st != CUKING_OK) return st;
+  if (num_pairs == 0) return CUKING_OK;
+  BIND_OR_RETURN(ctx);
+  hipStream_t s = (hipStream_t)stream;
+  if (d_pos != nullptr && num_sites > 1) {
+    // The host check of the positions, on copies: ordered on the stream behind whatever
+    // writes the arrays.
+    std::vector<uint32_t> pos(num_sites);
+    std::vector<int32_t> group(d_group != nullptr ? num_sites : 0);
+    HIP_TRY(hipMemcpyAsync(pos.data(), d_pos, (size_t)num_sites * 4, hipMemcpyDeviceToHost, s));
+    if (d_group != nullptr)
+      HIP_TRY(hipMemcpyAsync(group.data(), d_group, (size_t)num_sites * 4,
+                             hipMemcpyDeviceToHost, s));
+    ++ctx->host_syncs;
+    HIP_TRY(hipStreamSynchronize(s));
+    st = cuking_check_ibd_positions(d_group != nullptr ? group.data() : nullptr, pos.data(),
+                                    num_sites);
+    if (st != CUKING_OK) return st;
+  }
+  cuking_ctx::StreamScratch *e = stream_entry(ctx, s);
+  st = grow_on_stream(ctx, s, &e->ibd_groups, ibd_scan_words(num_sites) * sizeof(uint64_t));
+  if (st != CUKING_OK) return st;
+  uint64_t *d_group_bits = static_cast<uint64_t *>(e->ibd_groups.p);
+  HIP_TRY(launch_ibd_group_bits(d_group, num_sites, d_group_bits, s));
+  unsigned long long *d_count = nullptr;
+  if (num_segments != nullptr) {
+    st = grow_on_stream(ctx, s, &e->record_count, sizeof(unsigned long long));
+    if (st != CUKING_OK) return st;
+    d_count = static_cast<unsigned long long *>(e->record_count.p);
+    HIP_TRY(hipMemsetAsync(d_count, 0, sizeof(unsigned long long), s));
+  }
+  HIP_TRY(launch_ibd_pairs(d_bits, num_stored, words_per_sample, num_sites, d_group_bits, d_pos,
+                           min_sites, min_length, d_pairs, num_pairs, pair_stride, d_out,
+                           d_segments, max_segments, d_count, s));
+  if (num_segments == nullptr) return CUKING_OK;
+  unsigned long long count = 0;
+  HIP_TRY(hipMemcpyAsync(&count, d_count, sizeof(count), hipMemcpyDeviceToHost, s));
+  ++ctx->host_syncs;
+  HIP_TRY(hipStreamSynchronize(s));
+  *num_segments = count;
+  return cuking_ibd_count_status(count, max_segments);
 }
 
 // ---- timing ---------------------------------------------------------------

@@ -687,6 +687,22 @@ hipError_t launch_pcrelate_pairs(const uint64_t *d_bits, uint32_t num_stored,
                                  uint64_t num_pairs, uint32_t pair_stride,
                                  cuking_pcrelate_pair *d_out, hipStream_t stream);
 
+// IBD segments for listed pairs (king_ibd.hip; arguments already checked, king_host.h).
+// launch_ibd_group_bits fills d_group_bits[0 .. ibd_scan_words(num_sites)) (king_ibd.h: bit s set
+// iff site s starts a group; d_group may be null).  launch_ibd_pairs stores d_out[0 ..
+// num_pairs) with plain stores and, when d_count is not null, ADDS the number of segments to
+// *d_count (zeroed by the caller, on the stream) and stores those whose slot is below
+// max_segments; num_sites == 0 stores zero rows.
+hipError_t launch_ibd_group_bits(const int32_t *d_group, uint32_t num_sites,
+                                 uint64_t *d_group_bits, hipStream_t stream);
+hipError_t launch_ibd_pairs(const uint64_t *d_bits, uint32_t num_stored,
+                            uint32_t words_per_sample, uint32_t num_sites,
+                            const uint64_t *d_group_bits, const uint32_t *d_pos,
+                            uint32_t min_sites, uint32_t min_length, const void *d_pairs,
+                            uint64_t num_pairs, uint32_t pair_stride, cuking_ibd_pair *d_out,
+                            cuking_ibd_segment *d_segments, uint64_t max_segments,
+                            unsigned long long *d_count, hipStream_t stream);
+
 // Cohort models of the synthetic generator (synth.hip holds the specification).  d_tables:
 // synth_table_bytes() of scratch the launch fills and reads (per-site and per-sample
 // tables); it must stay untouched until the launch has run.

@@ -20,6 +20,7 @@
 #include "../host/schedule.h"
 #include "king_submatrix.h"
 #include "king_geno.h"
+#include "king_ibd.h"
 #include "king_kin_summary.h"
 #include "king_ld.h"
 #include "king_pcrelate.h"
@@ -963,6 +964,150 @@ cuking_status cuking_pcrelate_pairs_host(const uint64_t *bits, uint32_t num_stor
     out[p] = row;
   }
   return CUKING_OK;
+}
+
+}  // extern "C"
+
+// ---- IBD segments for listed pairs -------------------------------------------------------------
+cuking_status cuking_check_ibd_args(const void *bits, uint32_t words_per_sample,
+                                    uint32_t num_sites, uint32_t min_sites, const void *pairs,
+                                    uint64_t num_pairs, uint32_t pair_stride, const void *out,
+                                    const void *segments, uint64_t max_segments,
+                                    const void *num_segments) {
+  if (words_per_sample == 0 || (words_per_sample & 1))
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT,
+                       "words_per_sample (%u) must be a positive even number", words_per_sample);
+  if (num_sites > 64ull * (words_per_sample / 2))
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT,
+                       "ibd pairs: %u sites do not fit %u plane words (%llu bits)", num_sites,
+                       words_per_sample / 2, 64ull * (words_per_sample / 2));
+  if (min_sites < kIbdMinSites)
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT,
+                       "ibd pairs: min_sites (%u) must be at least %u: a run of %u or more sites "
+                       "always closes in a later 64-site word than it starts in, so the scan "
+                       "never enumerates the runs inside one word", min_sites, kIbdMinSites,
+                       kIbdMinSites);
+  if (!pcrelate_pair_stride_valid(pair_stride))
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT,
+                       "ibd pairs: pair_stride (%u bytes) must be at least 8 and a multiple of 4",
+                       pair_stride);
+  if (num_segments == nullptr && (segments != nullptr || max_segments != 0))
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT,
+                       "ibd pairs: a segment buffer needs a num_segments pointer");
+  if (num_segments != nullptr && num_pairs > (1ull << 32))
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT,
+                       "ibd pairs: a segment list names its pair in 32 bits, %llu pairs are too "
+                       "many", (unsigned long long)num_pairs);
+  if (num_pairs == 0) return CUKING_OK;
+  if (out == nullptr)
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "ibd pairs: null out pointer");
+  if (pairs == nullptr)
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "ibd pairs: null pairs pointer");
+  if (max_segments != 0 && segments == nullptr)
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "ibd pairs: null segments pointer");
+  if (num_sites != 0 && bits == nullptr)
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "ibd pairs: null bits pointer");
+  return CUKING_OK;
+}
+
+cuking_status cuking_check_ibd_positions(const int32_t *group, const uint32_t *pos,
+                                         uint32_t num_sites) {
+  if (pos == nullptr) return CUKING_OK;
+  for (uint64_t s = 1; s < num_sites; ++s)
+    if (!ibd_group_start(group, num_sites, s) && pos[s] < pos[s - 1])
+      return cuking_fail(CUKING_ERR_FAILED_PRECONDITION,
+                         "ibd pairs: pos must not decrease inside a group, but pos[%llu] = %u "
+                         "follows pos[%llu] = %u", (unsigned long long)s, pos[s],
+                         (unsigned long long)(s - 1), pos[s - 1]);
+  return CUKING_OK;
+}
+
+cuking_status cuking_ibd_count_status(uint64_t count, uint64_t max_segments) {
+  if (count > max_segments)
+    return cuking_fail(CUKING_ERR_RESOURCE_EXHAUSTED,
+                       "ibd pairs: %llu segments do not fit %llu: retry with that many",
+                       (unsigned long long)count, (unsigned long long)max_segments);
+  return CUKING_OK;
+}
+
+extern "C" {
+
+cuking_status cuking_ibd_pairs_host(const uint64_t *bits, uint32_t num_stored,
+                                    uint32_t words_per_sample, uint32_t num_sites,
+                                    const int32_t *group, const uint32_t *pos,
+                                    uint32_t min_sites, uint32_t min_length, const void *pairs,
+                                    uint64_t num_pairs, uint32_t pair_stride,
+                                    cuking_ibd_pair *out, cuking_ibd_segment *segments,
+                                    uint64_t max_segments, uint64_t *num_segments) {
+  if (num_segments != nullptr) *num_segments = 0;
+  cuking_status st = cuking_check_ibd_args(bits, words_per_sample, num_sites, min_sites, pairs,
+                                           num_pairs, pair_stride, out, segments, max_segments,
+                                           num_segments);
+  if (st != CUKING_OK) return st;
+  if (num_pairs == 0) return CUKING_OK;
+  st = cuking_check_ibd_positions(group, pos, num_sites);
+  if (st != CUKING_OK) return st;
+  const uint32_t plane_words = words_per_sample / 2;
+  const uint64_t words = ibd_scan_words(num_sites);
+  // the group-start bitmask of the call, as the device builds it
+  std::vector<uint64_t> group_bits(words, 0);
+  for (uint64_t s = 0; s <= num_sites; ++s)
+    if (ibd_group_start(group, num_sites, s)) group_bits[s >> 6] |= 1ull << (s & 63);
+  uint64_t count = 0;
+  for (uint64_t p = 0; p < num_pairs; ++p) {
+    uint32_t in[2];
+    memcpy(in, static_cast<const unsigned char *>(pairs) + p * pair_stride, sizeof(in));
+    IbdKindSums sums[2];
+    if (in[0] < num_stored && in[1] < num_stored) {
+      const uint64_t *row_i = bits + (uint64_t)in[0] * words_per_sample;
+      const uint64_t *row_j = bits + (uint64_t)in[1] * words_per_sample;
+      uint32_t open[2] = {kIbdInherit, kIbdInherit}, edge[2] = {0, 0};
+      for (uint64_t w = 0; w < words; ++w) {
+        const uint64_t valid = ibd_valid_mask(num_sites, w);
+        uint64_t het_i = 0, hom_i = 0, het_j = 0, hom_j = 0;
+        if (valid != 0) {  // (then w < plane_words)
+          het_i = row_i[w];
+          hom_i = row_i[plane_words + w];
+          het_j = row_j[w];
+          hom_j = row_j[plane_words + w];
+        }
+        const uint64_t in_run[2] = {valid & ~ibd_opp(het_i, hom_i, het_j, hom_j),
+                                    valid & ~ibd_diff(het_i, hom_i, het_j, hom_j)};
+        for (uint32_t k = 0; k < 2; ++k) {
+          const uint64_t starts = ibd_starts(in_run[k], edge[k], group_bits[w]);
+          const uint64_t closes = ibd_closes(in_run[k], edge[k], group_bits[w]);
+          if (edge[k] != 0 && closes != 0) {
+            const uint32_t a = open[k], b = ibd_close_last(closes, w);
+            const uint32_t pos_a = pos != nullptr ? pos[a] : a, pos_b = pos != nullptr ? pos[b] : b;
+            if (ibd_is_segment(a, b, pos_a, pos_b, min_sites, min_length)) {
+              sums[k].add(pos_b - pos_a);
+              if (num_segments != nullptr) {
+                if (count < max_segments)
+                  segments[count] = cuking_ibd_segment{(uint32_t)p, k + 1, a, b};
+                ++count;
+              }
+            }
+          }
+          const uint32_t start = ibd_open_start(starts, w);
+          if (start != kIbdInherit) open[k] = start;
+          edge[k] = (uint32_t)(in_run[k] >> 63);
+        }
+      }
+    }
+    cuking_ibd_pair row;
+    row.sample_i = in[0];
+    row.sample_j = in[1];
+    row.segments1 = sums[0].segments;
+    row.segments2 = sums[1].segments;
+    row.length1 = sums[0].length;
+    row.length2 = sums[1].length;
+    row.longest1 = sums[0].longest;
+    row.longest2 = sums[1].longest;
+    out[p] = row;
+  }
+  if (num_segments == nullptr) return CUKING_OK;
+  *num_segments = count;
+  return cuking_ibd_count_status(count, max_segments);
 }
 
 }  // extern "C"

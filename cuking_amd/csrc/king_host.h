@@ -69,5 +69,18 @@ cuking_status cuking_check_pcrelate_pairs_args(const void *bits, uint32_t words_
                                                float lo, float hi, const void *pairs,
                                                uint64_t num_pairs, uint32_t pair_stride,
                                                const void *out);
+// Argument checks of cuking_ibd_pairs_host / cuking_ibd_pairs (include/cuking_amd.h "IBD segments
+// for listed pairs" lists them; OK says nothing about there being work to do), the check of
+// positions on HOST copies of group and pos (FAILED_PRECONDITION names the first site whose
+// position decreases inside a group), and the status of a segment count: RESOURCE_EXHAUSTED
+// above max_segments.
+cuking_status cuking_check_ibd_args(const void *bits, uint32_t words_per_sample,
+                                    uint32_t num_sites, uint32_t min_sites, const void *pairs,
+                                    uint64_t num_pairs, uint32_t pair_stride, const void *out,
+                                    const void *segments, uint64_t max_segments,
+                                    const void *num_segments);
+cuking_status cuking_check_ibd_positions(const int32_t *group, const uint32_t *pos,
+                                         uint32_t num_sites);
+cuking_status cuking_ibd_count_status(uint64_t count, uint64_t max_segments);
 
 #endif  // CUKING_AMD_KING_HOST_H_

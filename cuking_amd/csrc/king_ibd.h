@@ -1,0 +1,125 @@
+// IBD segments for listed pairs (include/cuking_amd.h, "IBD segments for listed pairs"): the
+// definitions the kernels of king_ibd.hip, the host twin of king_host.cc and the tests share, so
+// that they cannot drift apart.  Plain C++: hipcc compiles the functions for the device, the
+// sanitizer build of the tests (tests/ibd_host_driver.cc) for the host.  Integers only.
+//
+// Words.  Word w of a plane holds the sites 64 w .. 64 w + 63, site s at bit s & 63.  A scan
+// looks at ibd_scan_words(num_sites) = num_sites / 64 + 1 words: the last one holds bit
+// num_sites, where the last run closes; it lies beyond the plane when num_sites is a multiple
+// of 64, and a word at or beyond the plane is never loaded (its `in` mask is zero anyway).
+//
+// Per word and kind, with `brk` the break mask (ibd_opp for kind 1, ibd_diff for kind 2):
+//     in     = ibd_valid_mask(num_sites, w) & ~brk     the sites that are inside some run
+//     group  bit s set iff site s is the first of its group; bit 0 of word 0 and the bit at
+//            num_sites are set, the bits beyond it clear (ibd_group_word)
+//     before = in << 1 | prev, prev = bit 63 of the word before's `in` (0 for word 0)
+//     starts = in & (~before | group)       bit a: a run starts at site a
+//     closes = before & (~in | group)       bit t: the run that holds site t - 1 ends there
+// A group boundary inside a run gives a close and a start at the same bit, the close first.
+// Along the sites starts and closes alternate, so inside a word:
+//   - the run that is open at the word's entry (prev == 1) closes at the word's first close
+//     bit, if it has one: b = 64 w + ctz(closes) - 1;
+//   - the run that is open at the word's end started at the word's last start bit, if it has
+//     one -- otherwise it is the run that was open at the entry ("inherit").
+// A run that starts AND closes inside one word has at most 63 sites (bits 0 .. 62, closed at
+// bit 63), and a run of 64 or more sites always closes in a later word than it starts in: with
+// min_sites >= kIbdMinSites = 64 only the first rule can yield a segment, at most one per word
+// and kind, and nobody enumerates bits.
+#ifndef CUKING_AMD_KING_IBD_H_
+#define CUKING_AMD_KING_IBD_H_
+
+#include <cstddef>
+#include <cstdint>
+
+#ifndef CUKING_HD
+#ifdef __HIPCC__
+#define CUKING_HD __host__ __device__
+#else
+#define CUKING_HD
+#endif
+#endif
+
+namespace cuking {
+
+constexpr uint32_t kIbdMinSites = 64;
+// "no start in this word": the open run is the one that was open before
+constexpr uint32_t kIbdInherit = 0xFFFFFFFFu;
+
+CUKING_HD inline uint64_t ibd_scan_words(uint32_t num_sites) {
+  return (uint64_t)num_sites / 64 + 1;
+}
+
+// The sites of word w below num_sites.
+CUKING_HD inline uint64_t ibd_valid_mask(uint32_t num_sites, uint64_t w) {
+  const uint64_t first = w * 64;
+  if (first >= num_sites) return 0;
+  const uint64_t left = num_sites - first;
+  return left >= 64 ? ~0ull : (1ull << left) - 1;
+}
+
+// Codes (0, 2) or (2, 0): one sample hom-ref, the other hom-var.
+CUKING_HD inline uint64_t ibd_opp(uint64_t het_i, uint64_t hom_i, uint64_t het_j,
+                                  uint64_t hom_j) {
+  const uint64_t ref_i = ~(het_i | hom_i), var_i = hom_i & ~het_i;
+  const uint64_t ref_j = ~(het_j | hom_j), var_j = hom_j & ~het_j;
+  return (ref_i & var_j) | (var_i & ref_j);
+}
+
+// A site that either sample misses (both bits).
+CUKING_HD inline uint64_t ibd_missing(uint64_t het_i, uint64_t hom_i, uint64_t het_j,
+                                      uint64_t hom_j) {
+  return (het_i & hom_i) | (het_j & hom_j);
+}
+
+// Both called and the codes differ.
+CUKING_HD inline uint64_t ibd_diff(uint64_t het_i, uint64_t hom_i, uint64_t het_j,
+                                   uint64_t hom_j) {
+  return ((het_i ^ het_j) | (hom_i ^ hom_j)) & ~ibd_missing(het_i, hom_i, het_j, hom_j);
+}
+
+CUKING_HD inline uint64_t ibd_starts(uint64_t in, uint64_t prev, uint64_t group) {
+  return in & (~(in << 1 | prev) | group);
+}
+CUKING_HD inline uint64_t ibd_closes(uint64_t in, uint64_t prev, uint64_t group) {
+  return (in << 1 | prev) & (~in | group);
+}
+
+// The first site of the run that is open at the end of a word with these starts, or
+// kIbdInherit.  (A start is a site below num_sites <= 2^32 - 1: never the sentinel.)
+CUKING_HD inline uint32_t ibd_open_start(uint64_t starts, uint64_t w) {
+  return starts != 0 ? (uint32_t)(w * 64 + 63 - (uint32_t)__builtin_clzll(starts)) : kIbdInherit;
+}
+// The last site of the run that closes at the first close bit of the word (closes != 0, and
+// not bit 0 of word 0: prev is 0 there).
+CUKING_HD inline uint32_t ibd_close_last(uint64_t closes, uint64_t w) {
+  return (uint32_t)(w * 64 + (uint32_t)__builtin_ctzll(closes) - 1);
+}
+
+// Whether site s is the first of its group (s <= num_sites; group may be null: one group).
+CUKING_HD inline bool ibd_group_start(const int32_t *group, uint32_t num_sites, uint64_t s) {
+  if (s == 0 || s == num_sites) return true;
+  return s < num_sites && group != nullptr && group[s] != group[s - 1];
+}
+
+// THE segment test of a run [a, b] with pos_a = pos[a], pos_b = pos[b] (pos[s] = s without
+// positions; pos_b >= pos_a inside a group).  The length of the segment is pos_b - pos_a.
+CUKING_HD inline bool ibd_is_segment(uint32_t a, uint32_t b, uint32_t pos_a, uint32_t pos_b,
+                                     uint32_t min_sites, uint32_t min_length) {
+  return b - a + 1 >= min_sites && pos_b - pos_a >= min_length;
+}
+
+// What a pair accumulates per kind; the sums and maxima are integers, so the order in which
+// the segments arrive does not matter.
+struct IbdKindSums {
+  uint32_t segments = 0, longest = 0;
+  uint64_t length = 0;
+  CUKING_HD void add(uint32_t len) {
+    ++segments;
+    length += len;
+    longest = len > longest ? len : longest;
+  }
+};
+
+}  // namespace cuking
+
+#endif  // CUKING_AMD_KING_IBD_H_

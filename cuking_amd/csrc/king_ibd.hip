@@ -1,0 +1,233 @@
+// IBD segments for listed pairs on the device (include/cuking_amd.h "IBD segments for listed
+// pairs" holds the contract, king_ibd.h the word masks and the segment test as code,
+// king_host.cc the host twin that walks the same words one by one; DESIGN.md 4.3h the reasons
+// for the shape): ibd_group_bits_kernel and ibd_pairs_kernel.
+//
+// One WAVEFRONT owns one pair.  Per step of kIbdStepWords = 64 words (4096 sites) lane l loads
+// word 64 step + l of the four planes of the pair (coalesced: 512 bytes per plane and step) and
+// of the per-call group-start bitmask; a word without a site below num_sites is not loaded.
+// Then, for each kind (king_ibd.h has the masks):
+//   edge     bit 63 of the left neighbour's `in` mask, one cross-lane move; lane 0 takes the
+//            value carried from the step before
+//   scan     every lane offers the last start bit of its word, or "inherit"; an inclusive
+//            wavefront scan with the operator "right operand unless it says inherit" (six
+//            cross-lane moves), shifted by one lane and seeded with the carried value, tells
+//            each lane the first site of the run that is open at its word's entry
+//   close    a lane whose word is entered inside a run and has a close bit owns that run: it
+//            reads pos[a] and pos[b], makes THE segment test and adds to its own integer
+//            counters; with a segment list it takes a slot with one atomic add
+//   carry    lane 63's scan value and edge bit go to the next step
+// At the end six integer wave reductions (sums and maxima: the order does not matter) feed one
+// 40-byte row per pair.  No floating point, no LDS, no scratch.  A pair with an index >=
+// num_stored loads nothing and stores zeros.
+#include <hip/hip_runtime.h>
+
+#include "king_common.h"
+#include "king_device.h"
+#include "king_ibd.h"
+
+namespace cuking {
+
+namespace {
+
+constexpr uint32_t kIbdWaves = 4;       // pairs of a workgroup: one per wavefront
+constexpr uint32_t kIbdThreads = 64 * kIbdWaves;
+constexpr uint32_t kIbdStepWords = 64;  // words per step: one per lane
+static_assert(sizeof(cuking_ibd_pair) == 40, "ten dwords per output row");
+static_assert(sizeof(cuking_ibd_segment) == 16, "four dwords per segment");
+
+// One thread per bit of the mask, one wavefront per word: the ballot IS the word.
+__global__ __launch_bounds__(kIbdThreads) void ibd_group_bits_kernel(
+    const int32_t *__restrict__ group, uint32_t num_sites, uint64_t *__restrict__ group_bits) {
+  const uint64_t s = (uint64_t)blockIdx.x * kIbdThreads + threadIdx.x;
+  const uint64_t word = __ballot(s <= num_sites && ibd_group_start(group, num_sites, s));
+  // (whole wavefronts: s / 64 is the same for all 64 lanes)
+  if ((threadIdx.x & 63) == 0 && s / 64 < ibd_scan_words(num_sites)) group_bits[s / 64] = word;
+}
+
+struct IbdArgs {
+  const uint64_t *bits;
+  const uint64_t *group_bits;
+  const uint32_t *pos;  // or nullptr: pos[s] = s
+  const unsigned char *pairs;
+  cuking_ibd_pair *out;
+  cuking_ibd_segment *segments;
+  unsigned long long *count;  // or nullptr: segments are not enumerated
+  uint64_t max_segments;
+  uint64_t num_pairs;
+  uint64_t pair_base;  // first pair of this launch
+  uint32_t pair_stride;
+  uint32_t num_stored, words_per_sample, num_sites, min_sites, min_length;
+};
+
+// What a wavefront carries from step to step for one kind (the same in every lane), and the
+// lane's own sums.
+struct IbdKind {
+  uint32_t open = kIbdInherit;  // first site of the run open at the end of the step before
+  uint32_t edge = 0;            // bit 63 of the last `in` word of the step before
+  IbdKindSums sums;
+};
+
+// Inclusive scan over the lanes with "right operand unless it says inherit".
+__device__ __forceinline__ uint32_t ibd_wave_scan(uint32_t v, uint32_t lane) {
+#pragma unroll
+  for (uint32_t off = 1; off < 64; off <<= 1) {
+    const uint32_t left = __shfl_up(v, off);
+    if (lane >= off && v == kIbdInherit) v = left;
+  }
+  return v;
+}
+
+// One step of one kind: `in` and `group` are the lane's word w.
+__device__ __forceinline__ void ibd_kind_step(const IbdArgs &a, uint32_t kind, uint64_t p,
+                                              uint64_t w, uint32_t lane, uint64_t in,
+                                              uint64_t group, IbdKind &k) {
+  const uint32_t last = (uint32_t)(in >> 63);
+  uint32_t prev = __shfl_up(last, 1);
+  if (lane == 0) prev = k.edge;
+  const uint64_t starts = ibd_starts(in, prev, group), closes = ibd_closes(in, prev, group);
+  const uint32_t scan = ibd_wave_scan(ibd_open_start(starts, w), lane);
+  uint32_t open = __shfl_up(scan, 1);
+  if (lane == 0 || open == kIbdInherit) open = k.open;
+  // (prev != 0: site 64 w - 1 is inside a run, so a start precedes this word and `open` is
+  //  a site; the run's last site is below num_sites)
+  if (prev != 0 && closes != 0) {
+    const uint32_t first = open, end = ibd_close_last(closes, w);
+    const uint32_t pos_a = a.pos != nullptr ? a.pos[first] : first;
+    const uint32_t pos_b = a.pos != nullptr ? a.pos[end] : end;
+    if (ibd_is_segment(first, end, pos_a, pos_b, a.min_sites, a.min_length)) {
+      k.sums.add(pos_b - pos_a);
+      if (a.count != nullptr) {
+        const unsigned long long slot = atomicAdd(a.count, 1ull);
+        if (slot < a.max_segments) {
+          cuking_ibd_segment seg;
+          seg.pair = (uint32_t)p;
+          seg.kind = kind;
+          seg.first_site = first;
+          seg.last_site = end;
+          a.segments[slot] = seg;
+        }
+      }
+    }
+  }
+  const uint32_t tail = __shfl(scan, 63);
+  if (tail != kIbdInherit) k.open = tail;
+  k.edge = __shfl(last, 63);
+}
+
+__device__ __forceinline__ uint32_t ibd_wave_sum(uint32_t v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+  return v;
+}
+__device__ __forceinline__ uint32_t ibd_wave_max(uint32_t v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const uint32_t other = __shfl_xor(v, off);
+    v = other > v ? other : v;
+  }
+  return v;
+}
+__device__ __forceinline__ uint64_t ibd_wave_sum64(uint64_t v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const uint32_t lo = __shfl_xor((uint32_t)v, off), hi = __shfl_xor((uint32_t)(v >> 32), off);
+    v += (uint64_t)hi << 32 | lo;
+  }
+  return v;
+}
+
+__global__ __launch_bounds__(kIbdThreads) void ibd_pairs_kernel(const IbdArgs a) {
+  const uint32_t lane = threadIdx.x & 63;
+  const uint64_t p = a.pair_base + (uint64_t)blockIdx.x * kIbdWaves + threadIdx.x / 64;
+  if (p >= a.num_pairs) return;  // (the whole wavefront: there is no barrier below)
+
+  const uint32_t *entry = reinterpret_cast<const uint32_t *>(a.pairs + p * a.pair_stride);
+  const uint32_t in_i = entry[0], in_j = entry[1];
+  const bool active = in_i < a.num_stored && in_j < a.num_stored;
+  const uint32_t plane_words = a.words_per_sample / 2;
+  const uint64_t *bits_i = a.bits + (uint64_t)(active ? in_i : 0) * a.words_per_sample;
+  const uint64_t *bits_j = a.bits + (uint64_t)(active ? in_j : 0) * a.words_per_sample;
+
+  IbdKind kind1, kind2;
+  const uint64_t words = ibd_scan_words(a.num_sites);
+  if (active) {
+    for (uint64_t w0 = 0; w0 < words; w0 += kIbdStepWords) {
+      const uint64_t w = w0 + lane;
+      const uint64_t valid = ibd_valid_mask(a.num_sites, w);
+      // (valid != 0 implies w < plane_words: num_sites <= 64 plane_words; the last step may be
+      //  partial and the word of bit num_sites may lie beyond the plane: neither is loaded)
+      uint64_t het_i = 0, hom_i = 0, het_j = 0, hom_j = 0;
+      if (valid != 0) {
+        het_i = bits_i[w];
+        hom_i = bits_i[plane_words + w];
+        het_j = bits_j[w];
+        hom_j = bits_j[plane_words + w];
+      }
+      const uint64_t group = w < words ? a.group_bits[w] : 0;
+      ibd_kind_step(a, 1, p, w, lane, valid & ~ibd_opp(het_i, hom_i, het_j, hom_j), group, kind1);
+      ibd_kind_step(a, 2, p, w, lane, valid & ~ibd_diff(het_i, hom_i, het_j, hom_j), group, kind2);
+    }
+  }
+
+  cuking_ibd_pair row;
+  row.sample_i = in_i;
+  row.sample_j = in_j;
+  row.segments1 = ibd_wave_sum(kind1.sums.segments);
+  row.segments2 = ibd_wave_sum(kind2.sums.segments);
+  row.length1 = ibd_wave_sum64(kind1.sums.length);
+  row.length2 = ibd_wave_sum64(kind2.sums.length);
+  row.longest1 = ibd_wave_max(kind1.sums.longest);
+  row.longest2 = ibd_wave_max(kind2.sums.longest);
+  if (lane == 0) a.out[p] = row;
+}
+
+}  // namespace
+
+hipError_t launch_ibd_group_bits(const int32_t *d_group, uint32_t num_sites,
+                                 uint64_t *d_group_bits, hipStream_t stream) {
+  // (at most 2^26 + 1 words: 2^24 + 1 workgroups, below every launch limit)
+  const uint64_t blocks = (ibd_scan_words(num_sites) + kIbdWaves - 1) / kIbdWaves;
+  ibd_group_bits_kernel<<<dim3((uint32_t)blocks), dim3(kIbdThreads), 0, stream>>>(
+      d_group, num_sites, d_group_bits);
+  return hipGetLastError();
+}
+
+hipError_t launch_ibd_pairs(const uint64_t *d_bits, uint32_t num_stored,
+                            uint32_t words_per_sample, uint32_t num_sites,
+                            const uint64_t *d_group_bits, const uint32_t *d_pos,
+                            uint32_t min_sites, uint32_t min_length, const void *d_pairs,
+                            uint64_t num_pairs, uint32_t pair_stride, cuking_ibd_pair *d_out,
+                            cuking_ibd_segment *d_segments, uint64_t max_segments,
+                            unsigned long long *d_count, hipStream_t stream) {
+  if (num_pairs == 0) return hipSuccess;
+  IbdArgs a;
+  a.bits = d_bits;
+  a.group_bits = d_group_bits;
+  a.pos = d_pos;
+  a.pairs = static_cast<const unsigned char *>(d_pairs);
+  a.out = d_out;
+  a.segments = d_segments;
+  a.count = d_count;
+  a.max_segments = max_segments;
+  a.num_pairs = num_pairs;
+  a.pair_base = 0;
+  a.pair_stride = pair_stride;
+  a.num_stored = num_stored;
+  a.words_per_sample = words_per_sample;
+  a.num_sites = num_sites;
+  a.min_sites = min_sites;
+  a.min_length = min_length;
+  const uint64_t blocks = (num_pairs + kIbdWaves - 1) / kIbdWaves;
+  const uint64_t cap = max_blocks_per_launch(kIbdThreads);
+  for (uint64_t done = 0; done < blocks; done += cap) {
+    const uint64_t n = blocks - done < cap ? blocks - done : cap;
+    a.pair_base = done * kIbdWaves;
+    ibd_pairs_kernel<<<dim3((uint32_t)n), dim3(kIbdThreads), 0, stream>>>(a);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+
+}  // namespace cuking

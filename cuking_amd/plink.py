@@ -72,6 +72,27 @@ def read_bim_chromosomes(prefix) -> np.ndarray:
     return np.asarray(out, dtype=np.int32)
 
 
+def read_bim_positions(prefix) -> np.ndarray:
+    """The base-pair coordinate (column 4) of every variant of `PREFIX.bim`, in file order, as
+    uint32 -- what `ibd_segments` takes as `pos`; ValueError names a line without one or with
+    one outside [0, 2^32)."""
+    out = []
+    with open(_path(prefix, ".bim")) as f:
+        for number, line in enumerate(f, 1):
+            fields = line.split()
+            if not fields:
+                continue
+            try:
+                value = int(fields[3])
+                if not 0 <= value <= 0xFFFFFFFF:
+                    raise ValueError
+            except (IndexError, ValueError):
+                raise ValueError(f"{_path(prefix, '.bim')}:{number}: expected a base-pair "
+                                 "coordinate in [0, 2^32) in column 4") from None
+            out.append(value)
+    return np.asarray(out, dtype=np.uint32)
+
+
 class BedFile:
     """An open variant-major `.bed`: `num_samples`, `num_sites`, `row_bytes`, `sample_ids`
     and `read_rows`.  A context manager; `close()` releases the file."""
@@ -155,10 +176,11 @@ def encode_rows(geno: np.ndarray) -> np.ndarray:
 
 
 def write_plink(prefix, geno: np.ndarray, sample_ids=None, chunk_sites: int = 4096,
-                chromosomes=None) -> None:
+                chromosomes=None, positions=None) -> None:
     """Writes `PREFIX.bed / .bim / .fam` for int8 `[samples, sites]` genotypes (the value is
     n_alt with A1 counted, negative = missing).  `chromosomes`: one name per site for the
-    `.bim` (default: all on "1")."""
+    `.bim` (default: all on "1"); `positions`: one base-pair coordinate per site (default:
+    the site's number from 1)."""
     geno = np.asarray(geno)
     n, m = geno.shape
     if sample_ids is None:
@@ -174,8 +196,12 @@ def write_plink(prefix, geno: np.ndarray, sample_ids=None, chunk_sites: int = 40
         chromosomes = ["1"] * m
     if len(chromosomes) != m or any(len(str(c).split()) != 1 for c in chromosomes):
         raise ValueError(f"chromosomes must be {m} names of one word each")
+    if positions is None:
+        positions = range(1, m + 1)
+    if len(positions) != m or any(not 0 <= int(p) <= 0xFFFFFFFF for p in positions):
+        raise ValueError(f"positions must be {m} coordinates in [0, 2^32)")
     with open(_path(prefix, ".bim"), "w") as f:
-        f.writelines(f"{chromosomes[k]}\tv{k}\t0\t{k + 1}\tA\tC\n" for k in range(m))
+        f.writelines(f"{chromosomes[k]}\tv{k}\t0\t{int(positions[k])}\tA\tC\n" for k in range(m))
     with open(_path(prefix, ".bed"), "wb") as f:
         f.write(MAGIC)
         for lo in range(0, m, chunk_sites):

@@ -162,6 +162,28 @@ def parse_args(argv=None):
               "then k0, k1, k2, ibs0, sites, kin_pairs and the relationship code of those pairs "
               "(with samples, min_kinship, num_records).  Needs --pca-uri; one process and "
               "--split-factor 1 only")
+    flag("ibd-segments-uri", default="",
+         help="also scan this run's records for IBD segments -- the runs of at least "
+              "--ibd-min-sites sites without an opposite homozygote (IBD1) and without a "
+              "difference (IBD2), no allele frequencies and no principal components involved "
+              "(cuking_amd/ibd.py) -- and write them to this .npz: sample_i, sample_j, segments1, "
+              "segments2, length1, length2, longest1, longest2, total_length, pi1, pi2, kin_ibd "
+              "and the relationship code of every record's pair (with samples, min_sites, "
+              "min_length).  The scan runs on the bitset the records were computed on, after "
+              "site QC and LD pruning: LD pruning thins the markers a segment is counted in, so "
+              "choose --ibd-min-sites for the markers that are left.  With --bed-uri the "
+              "chromosomes and base-pair positions of the .bim bound and measure the segments; "
+              "otherwise there is one group and the position is the site index.  One process "
+              "and --split-factor 1 only")
+    flag("ibd-min-sites", type=int, default=None,
+         help="the fewest sites of a segment of --ibd-segments-uri (default 512; at least 64)")
+    flag("ibd-min-length", type=int, default=None,
+         help="the least length of a segment of --ibd-segments-uri, in the .bim's positions "
+              "(default 0)")
+    flag("ibd-segment-list", action="store_true",
+         help="--ibd-segments-uri also writes the segments themselves: segment_pair (the "
+              "record's number), segment_kind, segment_first_site, segment_last_site (site "
+              "numbers among the input's sites), sorted")
     flag("pcrelate-min-kinship", type=float, default=None,
          help="the threshold of --pcrelate-records-uri: pairs with a kinship strictly above it "
               "(default 0.0442, the third-degree cut-off)")
@@ -311,6 +333,22 @@ def validate(args):  # cuking.cu:437-462
         if not args.pca_uri:
             raise UsageError("--pcrelate_pairs_uri needs the principal components of the same "
                              "run: pass --pca_uri as well")
+    if (args.ibd_min_sites is not None or args.ibd_min_length is not None or
+            args.ibd_segment_list) and not args.ibd_segments_uri:
+        raise UsageError("--ibd_min_sites, --ibd_min_length and --ibd_segment_list need "
+                         "--ibd_segments_uri")
+    if args.ibd_segments_uri:
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            raise UsageError("--ibd_segments_uri needs one process (one GPU): the records are "
+                             "not scanned across ranks yet")
+        if args.split_factor != 1:
+            raise UsageError("--ibd_segments_uri needs --split_factor 1: it scans the records of "
+                             "the whole cohort's bitset")
+        if args.ibd_min_sites is not None and args.ibd_min_sites < IBD_MIN_SITES:
+            raise UsageError(f"--ibd_min_sites must be at least {IBD_MIN_SITES}: shorter runs "
+                             "lie inside one 64-site word, which the scan does not enumerate")
+        if args.ibd_min_length is not None and not 0 <= args.ibd_min_length < 1 << 32:
+            raise UsageError("--ibd_min_length must be in [0, 2^32)")
     if args.pcrelate_min_kinship is not None and not args.pcrelate_records_uri:
         raise UsageError("--pcrelate_min_kinship needs --pcrelate_records_uri")
     if args.pcrelate_records_uri:
@@ -352,6 +390,7 @@ def validate(args):  # cuking.cu:437-462
 
 
 PCRELATE_COLUMNS_MAX = 32   # (CUKING_PCRELATE_COLUMNS_MAX; host-only here: no library load)
+IBD_MIN_SITES = 64          # (CUKING_IBD_MIN_SITES)
 
 
 def pcrelate_components(args) -> int:
@@ -614,6 +653,34 @@ def write_pcrelate_records(path: Path, ctx, bits, wps: int, num_sites: int, pca,
                  num_records=np.int64(found.num_records))
 
 
+def write_ibd_segments(path: Path, ctx, bits, wps: int, num_sites: int, recs, group, pos,
+                       site_index, min_sites: int, min_length: int, with_list: bool,
+                       sample_ids) -> None:
+    """This run's records scanned for IBD segments as an .npz: `sample_i`, `sample_j`,
+    `segments1`, `segments2`, `length1`, `length2`, `longest1`, `longest2`, `pi1`, `pi2`,
+    `kin_ibd`, `relationship` (one entry per record, in the records' order; the codes of
+    IBDPairs.relationship), `total_length`, `samples`, `min_sites`, `min_length`; with
+    `with_list` the sorted segments as `segment_pair`, `segment_kind`, `segment_first_site`,
+    `segment_last_site` (through `site_index`: numbers among the input's sites)."""
+    got = ctx.ibd_segments(bits, wps, num_sites, recs, group=group, pos=pos,
+                           min_sites=min_sites, min_length=min_length, segments=with_list)
+    pi1, pi2, kin = got.proportions()
+    extra = {}
+    if with_list:
+        segs = got.sorted()
+        extra = dict(segment_pair=segs["pair"], segment_kind=segs["kind"],
+                     segment_first_site=site_index[segs["first_site"]],
+                     segment_last_site=site_index[segs["last_site"]])
+    path.parent.mkdir(parents=True, exist_ok=True)
+    with open(path, "wb") as f:   # (np.savez would append .npz to another suffix)
+        np.savez(f, sample_i=got.sample_i, sample_j=got.sample_j, segments1=got.segments1,
+                 segments2=got.segments2, length1=got.length1, length2=got.length2,
+                 longest1=got.longest1, longest2=got.longest2, pi1=pi1, pi2=pi2, kin_ibd=kin,
+                 relationship=got.relationship(), total_length=np.int64(got.total_length),
+                 samples=np.array(list(sample_ids), dtype=str), min_sites=np.int64(min_sites),
+                 min_length=np.int64(min_length), **extra)
+
+
 def site_qc(ctx, args, bits, wps: int, num_sites: int, sample_ids, keep_path, qc_path):
     """Site QC of the whole cohort's bitset: counts on the GPU, the rule on the host, the
     report if one is asked for, and -- with a flag that selects sites -- the compacted bitset.
@@ -650,18 +717,20 @@ def ld_prune(ctx, args, bits, wps: int, num_sites: int, group, input_index, ld_p
     """LD pruning of the bitset site QC left: edges and the kept set on the GPU, the report if
     one is asked for, the compacted bitset.  `group`: chromosome ids of the sites that enter,
     or None; `input_index`: their numbers among the input's sites.  Returns (bits,
-    words_per_sample, num_sites) for everything behind."""
+    words_per_sample, num_sites, kept_index) for everything behind: the kept sites' numbers
+    among the input's sites."""
     window, r2 = ld_rule(args)
     got = ctx.ld_prune(bits, wps, num_sites, window=window, r2=r2, group=group)
+    kept_index = input_index[got.kept_index()]
     if ld_path is not None:
         ld_path.parent.mkdir(parents=True, exist_ok=True)
         with open(ld_path, "wb") as f:   # (np.savez would append .npz to another suffix)
-            np.savez(f, keep=got.keep(), kept_index=input_index[got.kept_index()],
+            np.savez(f, keep=got.keep(), kept_index=kept_index,
                      num_edges=np.int64(got.num_edges), window=np.int64(window),
                      r2=np.float32(r2))
     print(f"[cuking_amd.run] LD pruning keeps {got.num_sites} of {num_sites} sites "
           f"({got.num_edges} edges)", flush=True)
-    return got.bits, got.words_per_sample, got.num_sites
+    return got.bits, got.words_per_sample, got.num_sites, kept_index
 
 
 def main(argv=None) -> int:
@@ -692,6 +761,7 @@ def main(argv=None) -> int:
         pairs_path = resolve_uri(args.pcrelate_pairs_uri) if args.pcrelate_pairs_uri else None
         records_path = resolve_uri(args.pcrelate_records_uri) if args.pcrelate_records_uri \
             else None
+        ibd_path = resolve_uri(args.ibd_segments_uri) if args.ibd_segments_uri else None
         synthetic = None
         if args.synthetic:
             parts = [int(x) for x in args.synthetic.split(",")]
@@ -784,8 +854,8 @@ def main(argv=None) -> int:
             if bed_prefix is not None:
                 from cuking_amd import plink
                 group = plink.read_bim_chromosomes(bed_prefix)[site_index]
-            bits, wps, num_sites = ld_prune(ctx, args, bits[:stored], wps, num_sites, group,
-                                            site_index, site_ld_path)
+            bits, wps, num_sites, site_index = ld_prune(ctx, args, bits[:stored], wps, num_sites,
+                                                        group, site_index, site_ld_path)
         t1 = time.perf_counter()
         after_reserve = lambda: (0, 0)    # noqa: E731 - (allocations, host waits) since the reservation
         if sm.i_begin == sm.j_begin:
@@ -869,6 +939,17 @@ def main(argv=None) -> int:
                                            else args.pcrelate_min_maf,
                                            0.0442 if args.pcrelate_min_kinship is None
                                            else args.pcrelate_min_kinship, sample_ids)
+            if ibd_path is not None:
+                ibd_group = ibd_pos = None
+                if bed_prefix is not None:
+                    from cuking_amd import plink
+                    ibd_group = plink.read_bim_chromosomes(bed_prefix)[site_index]
+                    ibd_pos = plink.read_bim_positions(bed_prefix)[site_index]
+                write_ibd_segments(ibd_path, ctx, bits[:stored], wps, num_sites, recs, ibd_group,
+                                   ibd_pos, site_index,
+                                   512 if args.ibd_min_sites is None else args.ibd_min_sites,
+                                   0 if args.ibd_min_length is None else args.ibd_min_length,
+                                   args.ibd_segment_list, sample_ids)
             pairs = sm.NumPairs()
             print(json.dumps({"pairs": pairs, "results": int(len(recs)), "gpus": world,
                               "compute_seconds": dt,

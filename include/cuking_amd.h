@@ -1094,6 +1094,95 @@ cuking_status cuking_pcrelate_pairs(cuking_ctx *ctx, const uint64_t *d_bits, uin
                                     uint32_t pair_stride, cuking_pcrelate_pair *d_out,
                                     void *stream);
 
+/* IBD segments for listed pairs: the long stretches of the genome in which two samples never
+ * carry opposite homozygotes (IBD1) or never differ (IBD2), for a LIST of pairs -- typically the
+ * records of cuking_compute_king (KING --ibdseg, IBIS and TRUFFLE do this on unphased data).
+ * From their lengths follow the shared proportions, a kinship and the parent-child / full-sibling
+ * split with no allele frequency, no principal component and no min_maf.  Everything is decided
+ * on integers: host, device and a restatement in numpy agree bit for bit.  csrc/king_ibd.h holds
+ * the word masks and the segment test as code shared by host, device and tests.
+ *
+ *     bits    uint64 [num_stored][words_per_sample], the sample-major bitset; codes as in
+ *             cuking_site_counts: 0 hom-ref, 1 het, 2 hom-var, 3 missing
+ *     group   int32 [num_sites] or null (one group); sites s - 1 and s are in one group iff the
+ *             values are equal (chromosomes, as cuking_ld_edges takes them)
+ *     pos     uint32 [num_sites] or null (pos[s] = s); non-decreasing inside a group: base
+ *             pairs, or centimorgans as integer micro-Morgans
+ *     pairs, num_pairs, pair_stride   exactly as cuking_pcrelate_pairs reads them
+ *     out     one cuking_ibd_pair per entry, in input order, written with plain stores
+ *
+ * For a pair (i, j) and a site s < num_sites:
+ *     opp(s)   the codes are (0, 2) or (2, 0)
+ *     diff(s)  both are called and the codes differ (opp is a subset of diff)
+ * A site that either sample misses is neither.  Bits from num_sites to the end of the plane are
+ * never looked at, whatever they hold.
+ *     run of kind 1   a maximal interval [a, b] of sites of one group without an opp site
+ *     run of kind 2   a maximal interval [a, b] of sites of one group without a diff site
+ *     segment         a run with b - a + 1 >= min_sites and pos[b] - pos[a] >= min_length; its
+ *                     length is pos[b] - pos[a]
+ * A break site belongs to no run; a group boundary ends a run without removing a site; missing
+ * sites neither break nor end a run.  Every kind-2 segment lies inside a kind-1 segment, so
+ * length2 <= length1.
+ *
+ * min_sites >= CUKING_IBD_MIN_SITES = 64 is part of the contract: a run of 64 or more sites
+ * always closes in a later 64-site word than it starts in, so the runs of up to 63 sites that
+ * open and close inside one word can never qualify and the kernel never enumerates bits.  The
+ * defaults of the wrappers, min_sites = 512 and min_length = 0, are conventions.
+ *
+ * (i, j) and (j, i) give the same counts and lengths; sample_i and sample_j are copied from the
+ * input as they stand.  The self pair is legal: it has no break, so every group that satisfies
+ * the minimum is one segment of both kinds.  A pair with an index >= num_stored gets zeros, and
+ * no memory outside the arrays is read for it.  A row depends on its own pair only -- not on its
+ * position in the list, the length of the list, the stride, the stream or the call.
+ *
+ * Segment list (optional).  num_segments null: segments are not enumerated, segments must be
+ * null and max_segments 0, and cuking_ibd_pairs is asynchronous on `stream`.  num_segments not
+ * null (HOST memory): EVERY segment of every pair is counted, those whose slot is below
+ * max_segments are stored as cuking_ibd_segment {pair = the index into the list, kind, first_site
+ * = a, last_site = b}, and *num_segments receives the exact count (it starts at zero on every
+ * call).  The order is unspecified on the device (the set is the contract) and by (pair, word of
+ * the last site's successor, kind) on the host.  A count above max_segments returns
+ * RESOURCE_EXHAUSTED with nothing written past the buffer and every row of `out` written; the
+ * caller retries with exactly *num_segments; max_segments == 0 with null segments is the
+ * counting call.  cuking_ibd_pairs then WAITS for `stream` (it reads the count back); it also
+ * waits when pos is given, for the check below.
+ *
+ * INVALID_ARGUMENT before any device is touched: words_per_sample zero or odd; num_sites > 64
+ * (words_per_sample / 2); min_sites < 64; pair_stride below 8 or not a multiple of 4; a segment
+ * buffer or a max_segments without num_segments; a segment list for more than 2^32 pairs; and,
+ * with work to do, a null pointer (pairs, out; segments when max_segments != 0; bits when
+ * num_sites != 0 as well).  FAILED_PRECONDITION before the launch, naming the first offending
+ * site: pos[s] < pos[s - 1] inside a group (the device call copies group and pos to the host for
+ * this check).  num_pairs == 0 returns OK without work (after the checks of the arguments);
+ * num_sites == 0 writes zero rows.
+ * Out of scope: the C++ `cuking` binary; several ranks; tolerance for genotyping errors inside a
+ * run (one wrong homozygote splits a segment); trimming segment ends; an all-pairs scan; phased
+ * IBD; recombination maps beyond an integer pos. */
+#define CUKING_IBD_MIN_SITES 64
+typedef struct cuking_ibd_pair {
+  uint32_t sample_i, sample_j;   /* copied from the input */
+  uint32_t segments1, segments2; /* number of segments of kind 1 / 2 */
+  uint64_t length1, length2;     /* sum of their lengths */
+  uint32_t longest1, longest2;   /* largest single length, 0 without a segment */
+} cuking_ibd_pair;               /* 40 bytes */
+typedef struct cuking_ibd_segment {
+  uint32_t pair, kind, first_site, last_site;
+} cuking_ibd_segment; /* 16 bytes */
+cuking_status cuking_ibd_pairs_host(const uint64_t *bits, uint32_t num_stored,
+                                    uint32_t words_per_sample, uint32_t num_sites,
+                                    const int32_t *group, const uint32_t *pos,
+                                    uint32_t min_sites, uint32_t min_length, const void *pairs,
+                                    uint64_t num_pairs, uint32_t pair_stride,
+                                    cuking_ibd_pair *out, cuking_ibd_segment *segments,
+                                    uint64_t max_segments, uint64_t *num_segments);
+cuking_status cuking_ibd_pairs(cuking_ctx *ctx, const uint64_t *d_bits, uint32_t num_stored,
+                               uint32_t words_per_sample, uint32_t num_sites,
+                               const int32_t *d_group, const uint32_t *d_pos, uint32_t min_sites,
+                               uint32_t min_length, const void *d_pairs, uint64_t num_pairs,
+                               uint32_t pair_stride, cuking_ibd_pair *d_out,
+                               cuking_ibd_segment *d_segments, uint64_t max_segments,
+                               uint64_t *num_segments, void *stream);
+
 /* cuking.cu:761-765 on host memory: sort by (sample_i, sample_j, kin). */
 void cuking_sort_results(cuking_result *results, size_t num_results);
 
