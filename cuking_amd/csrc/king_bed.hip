@@ -198,16 +198,10 @@ hipError_t launch_pack_bed(const cuking_submatrix &sm, uint32_t words_per_sample
   a.sample_tiles = a.tiles0 + (two ? tiles_of(sm.j_begin, sm.j_end) : 0u);
   const uint64_t site_tiles = ((uint64_t)(site_end - site_begin) + kBedTileSites - 1) / kBedTileSites;
   const uint64_t tiles = site_tiles * a.sample_tiles;
-  // One launch may not exceed 2^32 - 1 threads in x (launch_variant, king_kernels.hip).
-  const uint64_t cap = max_blocks_per_launch(kBedThreads);
-  for (uint64_t done = 0; done < tiles; done += cap) {
-    const uint64_t n = tiles - done < cap ? tiles - done : cap;
+  return launch_in_chunks(tiles, kBedThreads, [&](uint64_t done, uint32_t n) {
     a.tile_base = done;
-    pack_bed_kernel<<<dim3((uint32_t)n), dim3(kBedThreads), 0, stream>>>(a);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
+    pack_bed_kernel<<<dim3(n), dim3(kBedThreads), 0, stream>>>(a);
+  });
 }
 
 }  // namespace cuking

@@ -439,6 +439,21 @@ hipError_t allow_dynamic_lds(uint32_t bytes) {
 // truncates silently beyond that); tests can lower the cap.
 uint64_t max_blocks_per_launch(uint32_t threads);
 
+// `blocks` workgroups of `threads` threads as launches of at most that many:
+// `launch(done, n)` launches the n workgroups from number `done` on, which it hands to the
+// kernel as their base.  Returns the first error.
+template <typename Launch>
+hipError_t launch_in_chunks(uint64_t blocks, uint32_t threads, Launch &&launch) {
+  const uint64_t cap = max_blocks_per_launch(threads);
+  for (uint64_t done = 0; done < blocks; done += cap) {
+    const uint64_t n = blocks - done < cap ? blocks - done : cap;
+    launch(done, (uint32_t)n);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+
 }  // namespace cuking
 
 #endif  // CUKING_AMD_KING_DEVICE_H_

@@ -140,15 +140,10 @@ __global__ __launch_bounds__(kGenoThreads) void geno_matmul_kernel(const GenoArg
 template <bool PER_ROW, bool TWO>
 hipError_t launch_geno(GenoArgs a, hipStream_t stream) {
   const uint64_t blocks = ((uint64_t)a.num_rows + kGenoRows - 1) / kGenoRows;
-  const uint64_t cap = max_blocks_per_launch(kGenoThreads);
-  for (uint64_t done = 0; done < blocks; done += cap) {
-    const uint64_t n = blocks - done < cap ? blocks - done : cap;
+  return launch_in_chunks(blocks, kGenoThreads, [&](uint64_t done, uint32_t n) {
     a.block_base = done;
-    geno_matmul_kernel<PER_ROW, TWO><<<dim3((uint32_t)n), dim3(kGenoThreads), 0, stream>>>(a);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
+    geno_matmul_kernel<PER_ROW, TWO><<<dim3(n), dim3(kGenoThreads), 0, stream>>>(a);
+  });
 }
 
 }  // namespace

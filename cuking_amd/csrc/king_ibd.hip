@@ -219,15 +219,10 @@ hipError_t launch_ibd_pairs(const uint64_t *d_bits, uint32_t num_stored,
   a.min_sites = min_sites;
   a.min_length = min_length;
   const uint64_t blocks = (num_pairs + kIbdWaves - 1) / kIbdWaves;
-  const uint64_t cap = max_blocks_per_launch(kIbdThreads);
-  for (uint64_t done = 0; done < blocks; done += cap) {
-    const uint64_t n = blocks - done < cap ? blocks - done : cap;
+  return launch_in_chunks(blocks, kIbdThreads, [&](uint64_t done, uint32_t n) {
     a.pair_base = done * kIbdWaves;
-    ibd_pairs_kernel<<<dim3((uint32_t)n), dim3(kIbdThreads), 0, stream>>>(a);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
+    ibd_pairs_kernel<<<dim3(n), dim3(kIbdThreads), 0, stream>>>(a);
+  });
 }
 
 }  // namespace cuking

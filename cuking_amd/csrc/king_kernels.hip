@@ -826,16 +826,11 @@ hipError_t launch_stream(const cuking_submatrix &sm, uint32_t words_per_sample,
   const uint64_t rows = sm_num_rows(sm);
   const uint64_t col_groups = ((uint64_t)sm_num_cols(sm) + 3) / 4;
   const uint64_t blocks = rows * col_groups;
-  const uint64_t cap = max_blocks_per_launch(256);
-  for (uint64_t done = 0; done < blocks; done += cap) {
-    const uint64_t n = blocks - done < cap ? blocks - done : cap;
-    king_stream_kernel<<<dim3((uint32_t)n), dim3(256), 0, stream>>>(
+  return launch_in_chunks(blocks, 256, [&](uint64_t done, uint32_t n) {
+    king_stream_kernel<<<dim3(n), dim3(256), 0, stream>>>(
         sm, words_per_sample, d_bit_sets, kin_threshold, max_results, d_results,
         d_result_index, d_result_overflow, d_dense_counts, done, d_dense_kin, kin_ld, kin_diag);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
+  });
 }
 
 hipError_t launch_pack(const cuking_submatrix &sm, uint32_t words_per_sample,

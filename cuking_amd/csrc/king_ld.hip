@@ -290,15 +290,10 @@ hipError_t launch_transpose_sites(const uint64_t *d_bit_set, uint32_t num_stored
   const uint64_t real_words = ((uint64_t)num_sites + 63) / 64;
   a.word_tiles = (uint32_t)((real_words + kTrWords - 1) / kTrWords);
   const uint64_t blocks = (uint64_t)a.word_tiles * ((a.q_words + kTrGroups - 1) / kTrGroups);
-  const uint64_t cap = max_blocks_per_launch(kTrThreads);
-  for (uint64_t done = 0; done < blocks; done += cap) {
-    const uint64_t n = blocks - done < cap ? blocks - done : cap;
+  return launch_in_chunks(blocks, kTrThreads, [&](uint64_t done, uint32_t n) {
     a.block_base = done;
-    transpose_sites_kernel<<<dim3((uint32_t)n), dim3(kTrThreads), 0, stream>>>(a);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
+    transpose_sites_kernel<<<dim3(n), dim3(kTrThreads), 0, stream>>>(a);
+  });
 }
 
 hipError_t launch_ld_edges(const uint64_t *d_site_bits, uint32_t num_sites, uint32_t num_stored,
@@ -322,15 +317,10 @@ hipError_t launch_ld_edges(const uint64_t *d_site_bits, uint32_t num_sites, uint
   if (col_tiles > row_tiles) col_tiles = row_tiles;
   a.col_tiles = (uint32_t)col_tiles;
   const uint64_t blocks = row_tiles * col_tiles;
-  const uint64_t cap = max_blocks_per_launch(kLdThreads);
-  for (uint64_t done = 0; done < blocks; done += cap) {
-    const uint64_t n = blocks - done < cap ? blocks - done : cap;
+  return launch_in_chunks(blocks, kLdThreads, [&](uint64_t done, uint32_t n) {
     a.block_base = done;
-    ld_edges_kernel<<<dim3((uint32_t)n), dim3(kLdThreads), 0, stream>>>(a);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
+    ld_edges_kernel<<<dim3(n), dim3(kLdThreads), 0, stream>>>(a);
+  });
 }
 
 }  // namespace cuking

@@ -16,7 +16,8 @@
 // elements are what restricts both sums to the jointly valid sites.
 //
 // Records (include/cuking_amd.h, "PC-Relate records"; king_pcrelate_records.hip and
-// cuking_pcrelate_records_host).  The same sums and kin; pcrelate_is_record is the rule that
+// cuking_pcrelate_records_host).  The same sums and kin -- on the device the matrix and the
+// record kernel call one tile body, king_pcrelate_tile.h --; pcrelate_is_record is the rule that
 // makes a pair a record, pcrelate_triangle_tile the map from a workgroup's number to its tile
 // when only the upper triangle of a diagonal block is launched.
 //
@@ -33,6 +34,7 @@
 
 #include <cmath>
 #include <cstdint>
+#include <type_traits>
 
 #include "king_geno.h"
 
@@ -68,6 +70,18 @@ CUKING_HD inline float pcrelate_kin(float num, float den) { return num / (4.0f *
 CUKING_HD inline bool pcrelate_bounds_valid(float lo, float hi) {
   return 0.0f <= lo && lo < hi && hi <= 1.0f;  // (false for a NaN)
 }
+
+#ifdef __HIPCC__
+// The kernels hold an X row in D registers, D = d rounded up to 4 / 8 / 16 / 32, a template
+// parameter: `launch(std::integral_constant<uint32_t, D>)` launches the kernel for that D.
+template <typename Launch>
+hipError_t pcrelate_dispatch_columns(uint32_t d, Launch &&launch) {
+  if (d <= 4) return launch(std::integral_constant<uint32_t, 4>{});
+  if (d <= 8) return launch(std::integral_constant<uint32_t, 8>{});
+  if (d <= 16) return launch(std::integral_constant<uint32_t, 16>{});
+  return launch(std::integral_constant<uint32_t, kPcrelateColumnsMax>{});
+}
+#endif
 
 // ---- records (include/cuking_amd.h, "PC-Relate records") -------------------------------------
 

@@ -150,20 +150,6 @@ __global__ __launch_bounds__(kPairThreads) void pcrelate_pairs_kernel(const PcrP
   }
 }
 
-template <uint32_t D>
-hipError_t launch_pairs(PcrPairArgs a, hipStream_t stream) {
-  const uint64_t blocks = (a.num_pairs + kPairThreads - 1) / kPairThreads;
-  const uint64_t cap = max_blocks_per_launch(kPairThreads);
-  for (uint64_t done = 0; done < blocks; done += cap) {
-    const uint64_t n = blocks - done < cap ? blocks - done : cap;
-    a.pair_base = done * kPairThreads;
-    pcrelate_pairs_kernel<D><<<dim3((uint32_t)n), dim3(kPairThreads), 0, stream>>>(a);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
-}
-
 }  // namespace
 
 hipError_t launch_pcrelate_pairs(const uint64_t *d_bits, uint32_t num_stored,
@@ -191,10 +177,14 @@ hipError_t launch_pcrelate_pairs(const uint64_t *d_bits, uint32_t num_stored,
   a.d = d;
   a.lo = lo;
   a.hi = hi;
-  if (d <= 4) return launch_pairs<4>(a, stream);
-  if (d <= 8) return launch_pairs<8>(a, stream);
-  if (d <= 16) return launch_pairs<16>(a, stream);
-  return launch_pairs<32>(a, stream);
+  const uint64_t blocks = (num_pairs + kPairThreads - 1) / kPairThreads;
+  return pcrelate_dispatch_columns(d, [&](auto columns) {
+    return launch_in_chunks(blocks, kPairThreads, [&](uint64_t done, uint32_t n) {
+      a.pair_base = done * kPairThreads;
+      pcrelate_pairs_kernel<decltype(columns)::value>
+          <<<dim3(n), dim3(kPairThreads), 0, stream>>>(a);
+    });
+  });
 }
 
 }  // namespace cuking

@@ -230,30 +230,20 @@ hipError_t launch_site_counts(const uint64_t *d_bit_set, uint32_t num_stored,
   a.wave_samples = (uint32_t)wave;
   a.sample_chunks = (uint32_t)(((uint64_t)num_stored + wave * 4 - 1) / (wave * 4));
   const uint64_t blocks = tiles * a.sample_chunks;
-  const uint64_t cap = max_blocks_per_launch(kSiteThreads);
-  for (uint64_t done = 0; done < blocks; done += cap) {
-    const uint64_t n = blocks - done < cap ? blocks - done : cap;
+  return launch_in_chunks(blocks, kSiteThreads, [&](uint64_t done, uint32_t n) {
     a.block_base = done;
-    site_counts_kernel<<<dim3((uint32_t)n), dim3(kSiteThreads), 0, stream>>>(a);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
+    site_counts_kernel<<<dim3(n), dim3(kSiteThreads), 0, stream>>>(a);
+  });
 }
 
 hipError_t launch_sample_counts(const uint64_t *d_bit_set, uint32_t num_stored,
                                 uint32_t words_per_sample, uint32_t num_sites,
                                 uint32_t *d_counts, hipStream_t stream) {
   const uint64_t blocks = ((uint64_t)num_stored + kSampleThreads / 64 - 1) / (kSampleThreads / 64);
-  const uint64_t cap = max_blocks_per_launch(kSampleThreads);
-  for (uint64_t done = 0; done < blocks; done += cap) {
-    const uint64_t n = blocks - done < cap ? blocks - done : cap;
-    sample_counts_kernel<<<dim3((uint32_t)n), dim3(kSampleThreads), 0, stream>>>(
+  return launch_in_chunks(blocks, kSampleThreads, [&](uint64_t done, uint32_t n) {
+    sample_counts_kernel<<<dim3(n), dim3(kSampleThreads), 0, stream>>>(
         d_bit_set, num_stored, words_per_sample, num_sites, d_counts, done);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
+  });
 }
 
 hipError_t launch_compact_sites(const uint64_t *d_in, uint32_t num_stored,
@@ -272,15 +262,10 @@ hipError_t launch_compact_sites(const uint64_t *d_in, uint32_t num_stored,
   a.kept = num_kept;
   a.items = (((uint64_t)num_stored + kCompactRows - 1) / kCompactRows) * (words_per_sample_out / 2);
   const uint64_t blocks = (a.items + kCompactThreads - 1) / kCompactThreads;
-  const uint64_t cap = max_blocks_per_launch(kCompactThreads);
-  for (uint64_t done = 0; done < blocks; done += cap) {
-    const uint64_t n = blocks - done < cap ? blocks - done : cap;
+  return launch_in_chunks(blocks, kCompactThreads, [&](uint64_t done, uint32_t n) {
     a.block_base = done;
-    compact_sites_kernel<<<dim3((uint32_t)n), dim3(kCompactThreads), 0, stream>>>(a);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
+    compact_sites_kernel<<<dim3(n), dim3(kCompactThreads), 0, stream>>>(a);
+  });
 }
 
 }  // namespace cuking

@@ -70,6 +70,28 @@ def test_same_bytes_on_two_streams_and_no_columns(ctx, run_device):
     assert tuple(out.shape) == (0, case.rhs + case.ldb_pad)
 
 
+def test_launches_are_split(ctx, run_device):
+    """A cap of one workgroup per launch sends the 257 rows (128 to a workgroup) out in three
+    launches, two of them with block_base != 0: the bytes of the one launch, in both layouts
+    and with one and two column blocks of B."""
+    rng = np.random.default_rng(78)
+    for case in (Case(257, 700, 33, False, 2, 3), Case(257, 65, 31, True, 0, 1)):
+        codes = codes_of(rng, case.rows, case.cols)
+        bits, words = bits_of(codes, case.per_row)
+        table = real_table(rng, case.rows if case.per_row else case.cols)
+        b = rng.standard_normal((case.cols, case.rhs + case.ldb_pad)).astype(np.float32)
+        blank = np.full((case.rows, case.rhs + case.ldo_pad), np.nan, dtype=np.float32)
+        args = (bits, words, case.cols, table, case.per_row, b, case.rhs, blank)
+        whole = run_device(*args)
+        ctx.set_option("max_launch_blocks", 1)
+        try:
+            split = run_device(*args)
+        finally:
+            ctx.set_option("max_launch_blocks", 0)
+        assert np.isfinite(whole[:, :case.rhs]).all()
+        assert np.array_equal(split.view(np.uint8), whole.view(np.uint8))
+
+
 def test_refused_arguments_on_a_live_context(ctx):
     """Every refusal of the contract through cuking_geno_matmul with a context: INVALID_ARGUMENT
     and a message, the output of the refused calls untouched."""

@@ -80,6 +80,23 @@ def test_a_second_stream_and_a_second_call_give_the_same_bytes(ctx):
     assert ibd.rows_to_host(rows).tobytes() == first_rows[order].tobytes()
 
 
+def test_launches_are_split(ctx):
+    """A cap of one workgroup per launch sends the 15 pairs (four to a workgroup) out in four
+    launches, three of them with a pair base above 0: the bytes of the one launch."""
+    case = next(c for c in ic.CASES if c.name.startswith("every word a group"))
+    assert len(ic.inputs(case).index) > 2 * 4
+    want_rows, want_segments = run_device(ctx, case)
+    ctx.set_option("max_launch_blocks", 1)
+    try:
+        rows, segments = run_device(ctx, case)
+    finally:
+        ctx.set_option("max_launch_blocks", 0)
+    assert np.array_equal(rows.view(np.uint8), want_rows.view(np.uint8))
+    assert np.array_equal(ibd.sort_segments(segments).view(np.uint8),
+                          ibd.sort_segments(want_segments).view(np.uint8))
+    assert len(want_segments) > 0
+
+
 def test_zero_sites_and_an_empty_list(ctx):
     import torch
     inp = ic.inputs(ic.REFUSAL_CASE)

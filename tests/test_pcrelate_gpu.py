@@ -108,6 +108,24 @@ def test_block_equals_the_whole_call_and_streams_agree(ctx):
     assert outs[0].cpu().numpy().tobytes() == outs[1].cpu().numpy().tobytes() == want.tobytes()
 
 
+def test_launches_are_split(ctx):
+    """A cap of two workgroups per launch sends the 3 x 3 tiles of 257 samples out in five
+    launches, four of them with block_base != 0: the bytes of the one launch."""
+    import torch
+    case = next(c for c in pc.CASES if c.name == "257x700 d3")
+    inp = pc.inputs(case)
+    bits, x, beta = _upload(ctx, inp)
+    whole = device_backend(case)
+    ctx.set_option("max_launch_blocks", 2)
+    try:
+        split = ctx.pcrelate_matrix(bits, inp.wps, case.sites, x, beta, inp.lo, inp.hi,
+                                    block=case.block)
+        torch.cuda.synchronize()
+    finally:
+        ctx.set_option("max_launch_blocks", 0)
+    assert np.array_equal(split.cpu().numpy().view(np.uint8), whole.view(np.uint8))
+
+
 def test_zero_sites_write_nan_and_an_empty_block_is_ok(ctx):
     import torch
     inp = pc.inputs(pc.CASES[4])

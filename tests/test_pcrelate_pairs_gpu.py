@@ -121,6 +121,29 @@ def test_the_same_pair_gives_the_same_bytes(ctx):
     assert got is out and pcr.pairs_to_host(out).tobytes() == whole.tobytes()
 
 
+def test_launches_are_split(ctx):
+    """A cap of one workgroup per launch sends a list of 1300 pairs (512 to a workgroup) out in
+    three launches, two of them with a pair base above 0: the bytes of the one launch."""
+    import torch
+    case = next(c for c in pp.CASES if c.name == "P513 S129 d11")
+    inp = pp.inputs(case)
+    bits, x, beta, f = _upload(ctx, inp)
+    index = np.ascontiguousarray(np.concatenate([inp.index, inp.index[::-1], inp.index])[:1300])
+
+    def run():
+        rows = ctx.pcrelate_pairs_raw(bits, inp.wps, case.sites, x, beta, inp.lo, inp.hi, index, f)
+        torch.cuda.synchronize()
+        return pcr.pairs_to_host(rows)
+    whole = run()
+    ctx.set_option("max_launch_blocks", 1)
+    try:
+        split = run()
+    finally:
+        ctx.set_option("max_launch_blocks", 0)
+    assert whole[:513].tobytes() == device_backend(case).tobytes()
+    assert np.array_equal(split.view(np.uint8), whole.view(np.uint8))
+
+
 def test_out_of_range_rows_no_site_rows_and_zero_sites(ctx):
     import torch
     case = next(c for c in pp.CASES if c.name == "exact P513 S65 stride 24")

@@ -134,6 +134,27 @@ def test_calls_streams_and_sub_blocks_give_the_same_set():
     rc.same_records(cuking_amd.sort_results(np.concatenate(parts)), everything)
 
 
+def test_launches_are_split(ctx):
+    """A cap of two workgroups per launch sends the six tiles of the 257-sample triangle out in
+    three launches, the last with block_base = 4; the off-diagonal block has 2 x 1 tiles, which
+    a cap of one splits as well.  At a gap threshold and at -inf: the sorted records and the
+    count of the one launch."""
+    case = next(c for c in rc.CASES if c.name == "257x700 d3")
+    calls = [(t, block) for t in (rc.gap_thresholds(case)[1].threshold, -rc.INF)
+             for block in (None, (0, 130, 130, 257))]
+    whole = [device_records(case, t, block=block) for t, block in calls]
+    assert whole[0][1] > 64 and whole[3][1] > 64
+    for cap in (2, 1):
+        ctx.set_option("max_launch_blocks", cap)
+        try:
+            split = [device_records(case, t, block=block) for t, block in calls]
+        finally:
+            ctx.set_option("max_launch_blocks", 0)
+        for (got, count), (want, want_count) in zip(split, whole):
+            assert count == want_count == want.shape[0]
+            assert np.array_equal(got.view(np.uint8), want.view(np.uint8))
+
+
 def test_overflow_counts_exactly_and_writes_nothing_behind_the_buffer(ctx):
     import torch
     case = next(c for c in rc.CASES if c.name == "257x700 d3")
