@@ -1196,7 +1196,7 @@ class KingContext:
     def ibd_segments_raw(self, bits, words_per_sample: int, num_sites: int, pairs, group=None,
                          pos=None, min_sites: int = 512, min_length: int = 0,
                          segments: bool = False, max_segments=None, num_records=None, out=None,
-                         stream=None):
+                         stream=None, bridge_sites: int = 0):
         """The bare kernel call for IBD segments (cuking_ibd_pairs; include/cuking_amd.h "IBD
         segments for listed pairs" has the definition): for every pair of ``pairs`` (as
         ``pcrelate_pairs_raw`` takes them) the number, summed length and longest of the runs of
@@ -1211,26 +1211,32 @@ class KingContext:
         ``num_segments`` rows are cuking_ibd_segment in no particular order, else None and 0.
         Without ``max_segments`` the buffer is grown once to the exact count; with it an
         overflow raises ``ResourceExhaustedError`` whose ``num_segments`` is the exact count.
-        Waits for the stream when ``pos`` is given or segments are counted."""
+        Waits for the stream when ``pos`` is given or segments are counted.
+        ``bridge_sites`` (0, or at least 64) links two runs of at least that many sites across
+        one break site of a group (cuking_ibd_pairs_bridged, "IBD segments with bridged
+        breaks"); the call then returns a fourth value, ``bridged``: an int32 ``[P, 2]`` device
+        tensor (``ibd.bridged_to_host``) with the bridged breaks inside the counted segments of
+        kind 1 and of kind 2.  0 is the strict call and the strict kernel."""
         from . import ibd as _ibd
         return _ibd.ibd_segments_raw_device(self, bits, words_per_sample, num_sites, pairs, group,
                                             pos, min_sites, min_length, segments, max_segments,
-                                            num_records, out, stream)
+                                            num_records, out, stream, bridge_sites)
 
     def ibd_segments(self, bits, words_per_sample: int, num_sites: int, pairs, group=None,
                      pos=None, min_sites: int = 512, min_length: int = 0, segments: bool = False,
-                     max_segments=None, num_records=None, stream=None):
+                     max_segments=None, num_records=None, stream=None, bridge_sites: int = 0):
         """IBD segments of a list of pairs -- typically the records of ``compute_king`` with
         ``num_records`` -- as an ``IBDPairs`` of host arrays (arguments as ``ibd_segments_raw``
         takes them): its ``proportions()`` are the IBD1 / IBD2 shares of ``genome_length`` and
         a kinship, its ``relationship()`` the degree with the parent-child / full-sibling
-        split, with no allele frequency and no principal component involved.  One wrong
-        homozygote splits a segment: there is no tolerance for genotyping errors.  Waits for
-        the device."""
+        split, with no allele frequency and no principal component involved.  With
+        ``bridge_sites = 0`` one wrong homozygote splits a segment; ``bridge_sites`` of 64 or
+        more forgives an isolated one between two runs of at least that many sites, and
+        ``IBDPairs.bridged`` counts the forgiven.  Waits for the device."""
         from . import ibd as _ibd
         return _ibd.ibd_segments_device(self, bits, words_per_sample, num_sites, pairs, group,
                                         pos, min_sites, min_length, segments, max_segments,
-                                        num_records, stream)
+                                        num_records, stream, bridge_sites)
 
     def synth_bitset(self, seed: int, kind, pa, pb, sample_begin: int,
                      sample_end: int, num_sites: int, out=None, stream=None, model=0):

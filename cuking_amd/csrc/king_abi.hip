@@ -2124,19 +2124,25 @@ cuking_status cuking_pcrelate_pairs(cuking_ctx *ctx, const uint64_t *d_bits, uin
 
 // ---- IBD segments for listed pairs (king_ibd.hip) ------------------------------
 
-cuking_status cuking_ibd_pairs(cuking_ctx *ctx, const uint64_t *d_bits, uint32_t num_stored,
-                               uint32_t words_per_sample, uint32_t num_sites,
-                               const int32_t *d_group, const uint32_t *d_pos, uint32_t min_sites,
-                               uint32_t min_length, const void *d_pairs, uint64_t num_pairs,
-                               uint32_t pair_stride, cuking_ibd_pair *d_out,
-                               cuking_ibd_segment *d_segments, uint64_t max_segments,
-                               uint64_t *num_segments, void *stream) {
+// Both entry points: bridge_sites == 0 is the strict call.
+static cuking_status ibd_pairs_device(cuking_ctx *ctx, const uint64_t *d_bits,
+                                      uint32_t num_stored, uint32_t words_per_sample,
+                                      uint32_t num_sites, const int32_t *d_group,
+                                      const uint32_t *d_pos, uint32_t min_sites,
+                                      uint32_t min_length, uint32_t bridge_sites,
+                                      const void *d_pairs, uint64_t num_pairs,
+                                      uint32_t pair_stride, cuking_ibd_pair *d_out,
+                                      uint32_t *d_bridged, cuking_ibd_segment *d_segments,
+                                      uint64_t max_segments, uint64_t *num_segments,
+                                      void *stream) {
   if (num_segments != nullptr) *num_segments = 0;
   // (the arguments first: a refused call touches no device)
   if (ctx == nullptr) return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "null context");
   cuking_status st = cuking_check_ibd_args(d_bits, words_per_sample, num_sites, min_sites,
                                            d_pairs, num_pairs, pair_stride, d_out, d_segments,
                                            max_segments, num_segments);
+  if (st != CUKING_OK) return st;
+  st = cuking_check_ibd_bridge(bridge_sites);
   if (st != CUKING_OK) return st;
   if (num_pairs == 0) return CUKING_OK;
   BIND_OR_RETURN(ctx);
@@ -2169,8 +2175,8 @@ cuking_status cuking_ibd_pairs(cuking_ctx *ctx, const uint64_t *d_bits, uint32_t
     HIP_TRY(hipMemsetAsync(d_count, 0, sizeof(unsigned long long), s));
   }
   HIP_TRY(launch_ibd_pairs(d_bits, num_stored, words_per_sample, num_sites, d_group_bits, d_pos,
-                           min_sites, min_length, d_pairs, num_pairs, pair_stride, d_out,
-                           d_segments, max_segments, d_count, s));
+                           min_sites, min_length, bridge_sites, d_pairs, num_pairs, pair_stride,
+                           d_out, d_bridged, d_segments, max_segments, d_count, s));
   if (num_segments == nullptr) return CUKING_OK;
   unsigned long long count = 0;
   HIP_TRY(hipMemcpyAsync(&count, d_count, sizeof(count), hipMemcpyDeviceToHost, s));
@@ -2178,6 +2184,33 @@ cuking_status cuking_ibd_pairs(cuking_ctx *ctx, const uint64_t *d_bits, uint32_t
   HIP_TRY(hipStreamSynchronize(s));
   *num_segments = count;
   return cuking_ibd_count_status(count, max_segments);
+}
+
+cuking_status cuking_ibd_pairs(cuking_ctx *ctx, const uint64_t *d_bits, uint32_t num_stored,
+                               uint32_t words_per_sample, uint32_t num_sites,
+                               const int32_t *d_group, const uint32_t *d_pos, uint32_t min_sites,
+                               uint32_t min_length, const void *d_pairs, uint64_t num_pairs,
+                               uint32_t pair_stride, cuking_ibd_pair *d_out,
+                               cuking_ibd_segment *d_segments, uint64_t max_segments,
+                               uint64_t *num_segments, void *stream) {
+  return ibd_pairs_device(ctx, d_bits, num_stored, words_per_sample, num_sites, d_group, d_pos,
+                          min_sites, min_length, 0, d_pairs, num_pairs, pair_stride, d_out,
+                          nullptr, d_segments, max_segments, num_segments, stream);
+}
+
+cuking_status cuking_ibd_pairs_bridged(cuking_ctx *ctx, const uint64_t *d_bits,
+                                       uint32_t num_stored, uint32_t words_per_sample,
+                                       uint32_t num_sites, const int32_t *d_group,
+                                       const uint32_t *d_pos, uint32_t min_sites,
+                                       uint32_t min_length, uint32_t bridge_sites,
+                                       const void *d_pairs, uint64_t num_pairs,
+                                       uint32_t pair_stride, cuking_ibd_pair *d_out,
+                                       uint32_t *d_bridged, cuking_ibd_segment *d_segments,
+                                       uint64_t max_segments, uint64_t *num_segments,
+                                       void *stream) {
+  return ibd_pairs_device(ctx, d_bits, num_stored, words_per_sample, num_sites, d_group, d_pos,
+                          min_sites, min_length, bridge_sites, d_pairs, num_pairs, pair_stride,
+                          d_out, d_bridged, d_segments, max_segments, num_segments, stream);
 }
 
 // ---- timing ---------------------------------------------------------------

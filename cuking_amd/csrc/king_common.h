@@ -692,14 +692,16 @@ hipError_t launch_pcrelate_pairs(const uint64_t *d_bits, uint32_t num_stored,
 // iff site s starts a group; d_group may be null).  launch_ibd_pairs stores d_out[0 ..
 // num_pairs) with plain stores and, when d_count is not null, ADDS the number of segments to
 // *d_count (zeroed by the caller, on the stream) and stores those whose slot is below
-// max_segments; num_sites == 0 stores zero rows.
+// max_segments; num_sites == 0 stores zero rows.  bridge_sites == 0 launches the strict kernel,
+// anything else the bridging instantiation; d_bridged ([num_pairs][2]) may be null.
 hipError_t launch_ibd_group_bits(const int32_t *d_group, uint32_t num_sites,
                                  uint64_t *d_group_bits, hipStream_t stream);
 hipError_t launch_ibd_pairs(const uint64_t *d_bits, uint32_t num_stored,
                             uint32_t words_per_sample, uint32_t num_sites,
                             const uint64_t *d_group_bits, const uint32_t *d_pos,
-                            uint32_t min_sites, uint32_t min_length, const void *d_pairs,
-                            uint64_t num_pairs, uint32_t pair_stride, cuking_ibd_pair *d_out,
+                            uint32_t min_sites, uint32_t min_length, uint32_t bridge_sites,
+                            const void *d_pairs, uint64_t num_pairs, uint32_t pair_stride,
+                            cuking_ibd_pair *d_out, uint32_t *d_bridged,
                             cuking_ibd_segment *d_segments, uint64_t max_segments,
                             unsigned long long *d_count, hipStream_t stream);
 

@@ -1030,69 +1030,112 @@ cuking_status cuking_ibd_count_status(uint64_t count, uint64_t max_segments) {
   return CUKING_OK;
 }
 
-extern "C" {
+cuking_status cuking_check_ibd_bridge(uint32_t bridge_sites) {
+  if (bridge_sites != 0 && bridge_sites < kIbdMinSites)
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT,
+                       "ibd pairs: bridge_sites (%u) must be 0 or at least %u: a run of %u or more "
+                       "sites always closes in a later 64-site word than it starts in, so a "
+                       "bridged break is the only break of its word", bridge_sites, kIbdMinSites,
+                       kIbdMinSites);
+  return CUKING_OK;
+}
 
-cuking_status cuking_ibd_pairs_host(const uint64_t *bits, uint32_t num_stored,
-                                    uint32_t words_per_sample, uint32_t num_sites,
-                                    const int32_t *group, const uint32_t *pos,
-                                    uint32_t min_sites, uint32_t min_length, const void *pairs,
-                                    uint64_t num_pairs, uint32_t pair_stride,
-                                    cuking_ibd_pair *out, cuking_ibd_segment *segments,
-                                    uint64_t max_segments, uint64_t *num_segments) {
+namespace {
+
+// The group-start bitmask of a call, as the device builds it.
+std::vector<uint64_t> ibd_group_bits(const int32_t *group, uint32_t num_sites) {
+  std::vector<uint64_t> group_bits(ibd_scan_words(num_sites), 0);
+  for (uint64_t s = 0; s <= num_sites; ++s)
+    if (ibd_group_start(group, num_sites, s)) group_bits[s >> 6] |= 1ull << (s & 63);
+  return group_bits;
+}
+
+// The words of one pair, one at a time: on_run(k, a, b) for every run [a, b] of kind k + 1 that
+// crosses a word edge, by (word of b + 1, kind).
+template <class OnRun>
+void ibd_walk_runs(const uint64_t *row_i, const uint64_t *row_j, uint32_t plane_words,
+                   uint32_t num_sites, const std::vector<uint64_t> &group_bits, OnRun on_run) {
+  uint32_t open[2] = {kIbdInherit, kIbdInherit}, edge[2] = {0, 0};
+  for (uint64_t w = 0; w < group_bits.size(); ++w) {
+    const uint64_t valid = ibd_valid_mask(num_sites, w);
+    uint64_t het_i = 0, hom_i = 0, het_j = 0, hom_j = 0;
+    if (valid != 0) {  // (then w < plane_words)
+      het_i = row_i[w];
+      hom_i = row_i[plane_words + w];
+      het_j = row_j[w];
+      hom_j = row_j[plane_words + w];
+    }
+    const uint64_t in_run[2] = {valid & ~ibd_opp(het_i, hom_i, het_j, hom_j),
+                                valid & ~ibd_diff(het_i, hom_i, het_j, hom_j)};
+    for (uint32_t k = 0; k < 2; ++k) {
+      const uint64_t starts = ibd_starts(in_run[k], edge[k], group_bits[w]);
+      const uint64_t closes = ibd_closes(in_run[k], edge[k], group_bits[w]);
+      if (edge[k] != 0 && closes != 0) on_run(k, open[k], ibd_close_last(closes, w));
+      const uint32_t start = ibd_open_start(starts, w);
+      if (start != kIbdInherit) open[k] = start;
+      edge[k] = (uint32_t)(in_run[k] >> 63);
+    }
+  }
+}
+
+// Rows, bridged counts and the segment list of both host calls.  bridge_sites == 0 links
+// nothing and tests every run where it closes; otherwise a chain is tested when the next run is
+// not linked to it, the last one after the walk.
+cuking_status ibd_pairs_host(const uint64_t *bits, uint32_t num_stored, uint32_t words_per_sample,
+                             uint32_t num_sites, const int32_t *group, const uint32_t *pos,
+                             uint32_t min_sites, uint32_t min_length, uint32_t bridge_sites,
+                             const void *pairs, uint64_t num_pairs, uint32_t pair_stride,
+                             cuking_ibd_pair *out, uint32_t *bridged,
+                             cuking_ibd_segment *segments, uint64_t max_segments,
+                             uint64_t *num_segments) {
   if (num_segments != nullptr) *num_segments = 0;
   cuking_status st = cuking_check_ibd_args(bits, words_per_sample, num_sites, min_sites, pairs,
                                            num_pairs, pair_stride, out, segments, max_segments,
                                            num_segments);
   if (st != CUKING_OK) return st;
+  st = cuking_check_ibd_bridge(bridge_sites);
+  if (st != CUKING_OK) return st;
   if (num_pairs == 0) return CUKING_OK;
   st = cuking_check_ibd_positions(group, pos, num_sites);
   if (st != CUKING_OK) return st;
-  const uint32_t plane_words = words_per_sample / 2;
-  const uint64_t words = ibd_scan_words(num_sites);
-  // the group-start bitmask of the call, as the device builds it
-  std::vector<uint64_t> group_bits(words, 0);
-  for (uint64_t s = 0; s <= num_sites; ++s)
-    if (ibd_group_start(group, num_sites, s)) group_bits[s >> 6] |= 1ull << (s & 63);
+  const std::vector<uint64_t> group_bits = ibd_group_bits(group, num_sites);
   uint64_t count = 0;
   for (uint64_t p = 0; p < num_pairs; ++p) {
     uint32_t in[2];
     memcpy(in, static_cast<const unsigned char *>(pairs) + p * pair_stride, sizeof(in));
     IbdKindSums sums[2];
     if (in[0] < num_stored && in[1] < num_stored) {
-      const uint64_t *row_i = bits + (uint64_t)in[0] * words_per_sample;
-      const uint64_t *row_j = bits + (uint64_t)in[1] * words_per_sample;
-      uint32_t open[2] = {kIbdInherit, kIbdInherit}, edge[2] = {0, 0};
-      for (uint64_t w = 0; w < words; ++w) {
-        const uint64_t valid = ibd_valid_mask(num_sites, w);
-        uint64_t het_i = 0, hom_i = 0, het_j = 0, hom_j = 0;
-        if (valid != 0) {  // (then w < plane_words)
-          het_i = row_i[w];
-          hom_i = row_i[plane_words + w];
-          het_j = row_j[w];
-          hom_j = row_j[plane_words + w];
+      // THE segment test of a chain [a, b] with `links` bridged breaks
+      auto test = [&](uint32_t k, uint32_t a, uint32_t b, uint32_t links) {
+        const uint32_t pos_a = pos != nullptr ? pos[a] : a, pos_b = pos != nullptr ? pos[b] : b;
+        if (!ibd_is_segment(a, b, pos_a, pos_b, min_sites, min_length)) return;
+        sums[k].add(pos_b - pos_a);
+        sums[k].bridged += links;
+        if (num_segments != nullptr) {
+          if (count < max_segments) segments[count] = cuking_ibd_segment{(uint32_t)p, k + 1, a, b};
+          ++count;
         }
-        const uint64_t in_run[2] = {valid & ~ibd_opp(het_i, hom_i, het_j, hom_j),
-                                    valid & ~ibd_diff(het_i, hom_i, het_j, hom_j)};
-        for (uint32_t k = 0; k < 2; ++k) {
-          const uint64_t starts = ibd_starts(in_run[k], edge[k], group_bits[w]);
-          const uint64_t closes = ibd_closes(in_run[k], edge[k], group_bits[w]);
-          if (edge[k] != 0 && closes != 0) {
-            const uint32_t a = open[k], b = ibd_close_last(closes, w);
-            const uint32_t pos_a = pos != nullptr ? pos[a] : a, pos_b = pos != nullptr ? pos[b] : b;
-            if (ibd_is_segment(a, b, pos_a, pos_b, min_sites, min_length)) {
-              sums[k].add(pos_b - pos_a);
-              if (num_segments != nullptr) {
-                if (count < max_segments)
-                  segments[count] = cuking_ibd_segment{(uint32_t)p, k + 1, a, b};
-                ++count;
-              }
-            }
-          }
-          const uint32_t start = ibd_open_start(starts, w);
-          if (start != kIbdInherit) open[k] = start;
-          edge[k] = (uint32_t)(in_run[k] >> 63);
-        }
-      }
+      };
+      IbdChain chain[2];
+      ibd_walk_runs(bits + (uint64_t)in[0] * words_per_sample,
+                    bits + (uint64_t)in[1] * words_per_sample, words_per_sample / 2, num_sites,
+                    group_bits, [&](uint32_t k, uint32_t a, uint32_t b) {
+                      if (bridge_sites == 0) return test(k, a, b, 0);
+                      IbdChain &c = chain[k];
+                      if (c.have && ibd_linked(c.last_first, c.last_end, a, b, bridge_sites,
+                                               group_bits.data())) {
+                        ++c.links;
+                      } else {
+                        if (c.have) test(k, c.first, c.last_end, c.links);
+                        c.have = 1;
+                        c.first = a;
+                        c.links = 0;
+                      }
+                      c.last_first = a;
+                      c.last_end = b;
+                    });
+      for (uint32_t k = 0; k < 2; ++k)
+        if (chain[k].have) test(k, chain[k].first, chain[k].last_end, chain[k].links);
     }
     cuking_ibd_pair row;
     row.sample_i = in[0];
@@ -1104,10 +1147,44 @@ cuking_status cuking_ibd_pairs_host(const uint64_t *bits, uint32_t num_stored,
     row.longest1 = sums[0].longest;
     row.longest2 = sums[1].longest;
     out[p] = row;
+    if (bridged != nullptr) {
+      bridged[2 * p] = sums[0].bridged;
+      bridged[2 * p + 1] = sums[1].bridged;
+    }
   }
   if (num_segments == nullptr) return CUKING_OK;
   *num_segments = count;
   return cuking_ibd_count_status(count, max_segments);
+}
+
+}  // namespace
+
+extern "C" {
+
+cuking_status cuking_ibd_pairs_host(const uint64_t *bits, uint32_t num_stored,
+                                    uint32_t words_per_sample, uint32_t num_sites,
+                                    const int32_t *group, const uint32_t *pos,
+                                    uint32_t min_sites, uint32_t min_length, const void *pairs,
+                                    uint64_t num_pairs, uint32_t pair_stride,
+                                    cuking_ibd_pair *out, cuking_ibd_segment *segments,
+                                    uint64_t max_segments, uint64_t *num_segments) {
+  return ibd_pairs_host(bits, num_stored, words_per_sample, num_sites, group, pos, min_sites,
+                        min_length, 0, pairs, num_pairs, pair_stride, out, nullptr, segments,
+                        max_segments, num_segments);
+}
+
+cuking_status cuking_ibd_pairs_bridged_host(const uint64_t *bits, uint32_t num_stored,
+                                            uint32_t words_per_sample, uint32_t num_sites,
+                                            const int32_t *group, const uint32_t *pos,
+                                            uint32_t min_sites, uint32_t min_length,
+                                            uint32_t bridge_sites, const void *pairs,
+                                            uint64_t num_pairs, uint32_t pair_stride,
+                                            cuking_ibd_pair *out, uint32_t *bridged,
+                                            cuking_ibd_segment *segments, uint64_t max_segments,
+                                            uint64_t *num_segments) {
+  return ibd_pairs_host(bits, num_stored, words_per_sample, num_sites, group, pos, min_sites,
+                        min_length, bridge_sites, pairs, num_pairs, pair_stride, out, bridged,
+                        segments, max_segments, num_segments);
 }
 
 }  // extern "C"

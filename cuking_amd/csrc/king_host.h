@@ -82,5 +82,7 @@ cuking_status cuking_check_ibd_args(const void *bits, uint32_t words_per_sample,
 cuking_status cuking_check_ibd_positions(const int32_t *group, const uint32_t *pos,
                                          uint32_t num_sites);
 cuking_status cuking_ibd_count_status(uint64_t count, uint64_t max_segments);
+// The one refusal the bridged calls add: 0 < bridge_sites < 64.
+cuking_status cuking_check_ibd_bridge(uint32_t bridge_sites);
 
 #endif  // CUKING_AMD_KING_HOST_H_

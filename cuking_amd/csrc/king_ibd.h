@@ -25,6 +25,15 @@
 // bit 63), and a run of 64 or more sites always closes in a later word than it starts in: with
 // min_sites >= kIbdMinSites = 64 only the first rule can yield a segment, at most one per word
 // and kind, and nobody enumerates bits.
+//
+// Bridged breaks ("IBD segments with bridged breaks" in the header).  With bridge_sites != 0 two
+// consecutive runs on either side of ONE break site are linked when both have at least
+// bridge_sites >= kIbdMinSites sites and no group starts at the break or behind it (ibd_linked),
+// and a segment is a maximal chain of linked runs.  Both runs of a link cross a word edge, so
+// they are among the runs the first rule yields, in site order; a run that opens and closes
+// inside one word lies between its neighbours and keeps them more than one site apart.  IbdChain
+// is the chain whose last run is the last one seen: the host twin carries it from word to word,
+// a wavefront from step to step.
 #ifndef CUKING_AMD_KING_IBD_H_
 #define CUKING_AMD_KING_IBD_H_
 
@@ -108,11 +117,31 @@ CUKING_HD inline bool ibd_is_segment(uint32_t a, uint32_t b, uint32_t pos_a, uin
   return b - a + 1 >= min_sites && pos_b - pos_a >= min_length;
 }
 
+// Whether the run [a2, b2] is linked to the run [a, b] in front of it.  a2 == b + 2 leaves exactly
+// site b + 1 between them, which belongs to no run and lies below num_sites: a break.  group_bits
+// is the group-start mask of the call (only read when everything else holds; a2 < num_sites keeps
+// both bits inside its ibd_scan_words words).
+CUKING_HD inline bool ibd_linked(uint32_t a, uint32_t b, uint32_t a2, uint32_t b2,
+                                 uint32_t bridge_sites, const uint64_t *group_bits) {
+  if (bridge_sites == 0 || (uint64_t)b + 2 != a2) return false;
+  if (b - a + 1 < bridge_sites || b2 - a2 + 1 < bridge_sites) return false;
+  const uint64_t brk = (uint64_t)b + 1;
+  return ((group_bits[brk >> 6] >> (brk & 63)) & 1) == 0 &&
+         ((group_bits[a2 >> 6] >> (a2 & 63)) & 1) == 0;
+}
+
+// The chain that ends with the last run seen so far: sites first .. last_end, its last run
+// last_first .. last_end, `links` bridged breaks inside.
+struct IbdChain {
+  uint32_t have = 0, first = 0, last_first = 0, last_end = 0, links = 0;
+};
+
 // What a pair accumulates per kind; the sums and maxima are integers, so the order in which
 // the segments arrive does not matter.
 struct IbdKindSums {
   uint32_t segments = 0, longest = 0;
   uint64_t length = 0;
+  uint32_t bridged = 0;  // links inside the counted segments
   CUKING_HD void add(uint32_t len) {
     ++segments;
     length += len;

@@ -20,7 +20,23 @@
 // At the end six integer wave reductions (sums and maxima: the order does not matter) feed one
 // 40-byte row per pair.  No floating point, no LDS, no scratch.  A pair with an index >=
 // num_stored loads nothing and stores zeros.
+//
+// Bridged breaks (bridge_sites != 0) are a second instantiation of the same kernel, so that
+// bridge_sites == 0 launches the code above as it stands.  There the lanes that would make the
+// segment test hold a closed run each, in site order along the lanes, and
+//   link     a ballot names the lanes with a run; each finds the lane of the run in front of it
+//            in the mask, fetches that run with two cross-lane reads -- the first run of a step
+//            takes the chain carried from the steps before -- and decides ibd_linked
+//   chain    a second ballot names the linked runs; a chain starts at the nearest run at or
+//            below the lane that is not linked, its first site is one more cross-lane read, its
+//            links a population count of the mask
+//   test     a run that is NOT linked ends the chain in front of it: that lane fetches the
+//            chain's first site and links, makes THE segment test and takes the list slot
+//   carry    the chain of the last run of the step goes to the next step; the word of bit
+//            num_sites closes every run, so one test after the loop ends the scan
 #include <hip/hip_runtime.h>
+
+#include <type_traits>
 
 #include "king_common.h"
 #include "king_device.h"
@@ -59,6 +75,13 @@ struct IbdArgs {
   uint32_t pair_stride;
   uint32_t num_stored, words_per_sample, num_sites, min_sites, min_length;
 };
+// ... and what the bridging instantiation reads on top
+struct IbdBridgeArgs : IbdArgs {
+  uint32_t *bridged;  // [num_pairs][2] or nullptr
+  uint32_t bridge_sites;
+};
+template <bool kBridge>
+using IbdArgsOf = typename std::conditional<kBridge, IbdBridgeArgs, IbdArgs>::type;
 
 // What a wavefront carries from step to step for one kind (the same in every lane), and the
 // lane's own sums.
@@ -66,6 +89,7 @@ struct IbdKind {
   uint32_t open = kIbdInherit;  // first site of the run open at the end of the step before
   uint32_t edge = 0;            // bit 63 of the last `in` word of the step before
   IbdKindSums sums;
+  IbdChain chain;               // bridging only: the chain of the last run so far
 };
 
 // Inclusive scan over the lanes with "right operand unless it says inherit".
@@ -78,9 +102,86 @@ __device__ __forceinline__ uint32_t ibd_wave_scan(uint32_t v, uint32_t lane) {
   return v;
 }
 
+// THE segment test of a run or chain [first, end] with `links` bridged breaks, by one lane.
+__device__ __forceinline__ void ibd_test(const IbdArgs &a, uint32_t kind, uint64_t p,
+                                         uint32_t first, uint32_t end, uint32_t links,
+                                         IbdKindSums &sums) {
+  const uint32_t pos_a = a.pos != nullptr ? a.pos[first] : first;
+  const uint32_t pos_b = a.pos != nullptr ? a.pos[end] : end;
+  if (ibd_is_segment(first, end, pos_a, pos_b, a.min_sites, a.min_length)) {
+    sums.add(pos_b - pos_a);
+    sums.bridged += links;
+    if (a.count != nullptr) {
+      const unsigned long long slot = atomicAdd(a.count, 1ull);
+      if (slot < a.max_segments) {
+        cuking_ibd_segment seg;
+        seg.pair = (uint32_t)p;
+        seg.kind = kind;
+        seg.first_site = first;
+        seg.last_site = end;
+        a.segments[slot] = seg;
+      }
+    }
+  }
+}
+
+// The highest lane of a non-empty mask.
+__device__ __forceinline__ uint32_t ibd_top_lane(uint64_t mask) {
+  return 63 - (uint32_t)__builtin_clzll(mask);
+}
+
+// The runs that close in this step, linked into chains (all 64 lanes call this together).
+// `event`: the lane holds the closed run [first, end]; the lanes hold them in site order.
+__device__ __forceinline__ void ibd_chain_step(const IbdBridgeArgs &a, uint32_t kind, uint64_t p,
+                                               uint32_t lane, bool event, uint32_t first,
+                                               uint32_t end, IbdKind &k) {
+  const uint64_t events = __ballot(event);
+  if (events == 0) return;  // (the whole wavefront)
+  const IbdChain carried = k.chain;
+  const uint64_t below = (1ull << lane) - 1, upto = below | 1ull << lane;
+  // link: the run in front of mine is the one of lane q, or the last of the carried chain
+  const uint64_t before = events & below;
+  const bool inside = before != 0;
+  const uint32_t q = inside ? ibd_top_lane(before) : 0;
+  uint32_t q_first = __shfl(first, q), q_end = __shfl(end, q);
+  if (!inside) {
+    q_first = carried.last_first;
+    q_end = carried.last_end;
+  }
+  const bool follows = inside || carried.have != 0;
+  const bool linked = event && follows &&
+                      ibd_linked(q_first, q_end, first, end, a.bridge_sites, a.group_bits);
+  // chain: from the nearest run at or below me that is not linked, or the carried chain
+  const uint64_t heads = events & ~__ballot(linked);
+  const uint64_t mine = heads & upto;
+  const uint32_t h = mine != 0 ? ibd_top_lane(mine) : 0;
+  uint32_t chain_first = __shfl(first, h);
+  // (the events in (h, lane] are all linked; 2 << 63 is 0: nothing above lane 63)
+  uint32_t chain_links = (uint32_t)__builtin_popcountll(events & upto & ~((2ull << h) - 1));
+  if (mine == 0) {
+    chain_first = carried.first;
+    chain_links = carried.links + (uint32_t)__builtin_popcountll(events & upto);
+  }
+  // test: a run that is not linked ends the chain in front of it
+  uint32_t done_first = __shfl(chain_first, q), done_links = __shfl(chain_links, q);
+  if (!inside) {
+    done_first = carried.first;
+    done_links = carried.links;
+  }
+  if (event && !linked && follows) ibd_test(a, kind, p, done_first, q_end, done_links, k.sums);
+  // carry: the chain of the step's last run
+  const uint32_t z = ibd_top_lane(events);
+  k.chain.have = 1;
+  k.chain.first = __shfl(chain_first, z);
+  k.chain.links = __shfl(chain_links, z);
+  k.chain.last_first = __shfl(first, z);
+  k.chain.last_end = __shfl(end, z);
+}
+
 // One step of one kind: `in` and `group` are the lane's word w.
-__device__ __forceinline__ void ibd_kind_step(const IbdArgs &a, uint32_t kind, uint64_t p,
-                                              uint64_t w, uint32_t lane, uint64_t in,
+template <bool kBridge>
+__device__ __forceinline__ void ibd_kind_step(const IbdArgsOf<kBridge> &a, uint32_t kind,
+                                              uint64_t p, uint64_t w, uint32_t lane, uint64_t in,
                                               uint64_t group, IbdKind &k) {
   const uint32_t last = (uint32_t)(in >> 63);
   uint32_t prev = __shfl_up(last, 1);
@@ -91,24 +192,11 @@ __device__ __forceinline__ void ibd_kind_step(const IbdArgs &a, uint32_t kind, u
   if (lane == 0 || open == kIbdInherit) open = k.open;
   // (prev != 0: site 64 w - 1 is inside a run, so a start precedes this word and `open` is
   //  a site; the run's last site is below num_sites)
-  if (prev != 0 && closes != 0) {
-    const uint32_t first = open, end = ibd_close_last(closes, w);
-    const uint32_t pos_a = a.pos != nullptr ? a.pos[first] : first;
-    const uint32_t pos_b = a.pos != nullptr ? a.pos[end] : end;
-    if (ibd_is_segment(first, end, pos_a, pos_b, a.min_sites, a.min_length)) {
-      k.sums.add(pos_b - pos_a);
-      if (a.count != nullptr) {
-        const unsigned long long slot = atomicAdd(a.count, 1ull);
-        if (slot < a.max_segments) {
-          cuking_ibd_segment seg;
-          seg.pair = (uint32_t)p;
-          seg.kind = kind;
-          seg.first_site = first;
-          seg.last_site = end;
-          a.segments[slot] = seg;
-        }
-      }
-    }
+  const bool event = prev != 0 && closes != 0;
+  if constexpr (kBridge) {
+    ibd_chain_step(a, kind, p, lane, event, open, event ? ibd_close_last(closes, w) : 0, k);
+  } else {
+    if (event) ibd_test(a, kind, p, open, ibd_close_last(closes, w), 0, k.sums);
   }
   const uint32_t tail = __shfl(scan, 63);
   if (tail != kIbdInherit) k.open = tail;
@@ -137,7 +225,8 @@ __device__ __forceinline__ uint64_t ibd_wave_sum64(uint64_t v) {
   return v;
 }
 
-__global__ __launch_bounds__(kIbdThreads) void ibd_pairs_kernel(const IbdArgs a) {
+template <bool kBridge>
+__global__ __launch_bounds__(kIbdThreads) void ibd_pairs_kernel(const IbdArgsOf<kBridge> a) {
   const uint32_t lane = threadIdx.x & 63;
   const uint64_t p = a.pair_base + (uint64_t)blockIdx.x * kIbdWaves + threadIdx.x / 64;
   if (p >= a.num_pairs) return;  // (the whole wavefront: there is no barrier below)
@@ -165,8 +254,17 @@ __global__ __launch_bounds__(kIbdThreads) void ibd_pairs_kernel(const IbdArgs a)
         hom_j = bits_j[plane_words + w];
       }
       const uint64_t group = w < words ? a.group_bits[w] : 0;
-      ibd_kind_step(a, 1, p, w, lane, valid & ~ibd_opp(het_i, hom_i, het_j, hom_j), group, kind1);
-      ibd_kind_step(a, 2, p, w, lane, valid & ~ibd_diff(het_i, hom_i, het_j, hom_j), group, kind2);
+      ibd_kind_step<kBridge>(a, 1, p, w, lane, valid & ~ibd_opp(het_i, hom_i, het_j, hom_j),
+                             group, kind1);
+      ibd_kind_step<kBridge>(a, 2, p, w, lane, valid & ~ibd_diff(het_i, hom_i, het_j, hom_j),
+                             group, kind2);
+    }
+    if constexpr (kBridge) {
+      // (every run is closed by now: the chains that are left are whole)
+      if (lane == 0 && kind1.chain.have)
+        ibd_test(a, 1, p, kind1.chain.first, kind1.chain.last_end, kind1.chain.links, kind1.sums);
+      if (lane == 0 && kind2.chain.have)
+        ibd_test(a, 2, p, kind2.chain.first, kind2.chain.last_end, kind2.chain.links, kind2.sums);
     }
   }
 
@@ -180,6 +278,14 @@ __global__ __launch_bounds__(kIbdThreads) void ibd_pairs_kernel(const IbdArgs a)
   row.longest1 = ibd_wave_max(kind1.sums.longest);
   row.longest2 = ibd_wave_max(kind2.sums.longest);
   if (lane == 0) a.out[p] = row;
+  if constexpr (kBridge) {
+    const uint32_t bridged1 = ibd_wave_sum(kind1.sums.bridged);
+    const uint32_t bridged2 = ibd_wave_sum(kind2.sums.bridged);
+    if (lane == 0 && a.bridged != nullptr) {
+      a.bridged[2 * p] = bridged1;
+      a.bridged[2 * p + 1] = bridged2;
+    }
+  }
 }
 
 }  // namespace
@@ -196,12 +302,13 @@ hipError_t launch_ibd_group_bits(const int32_t *d_group, uint32_t num_sites,
 hipError_t launch_ibd_pairs(const uint64_t *d_bits, uint32_t num_stored,
                             uint32_t words_per_sample, uint32_t num_sites,
                             const uint64_t *d_group_bits, const uint32_t *d_pos,
-                            uint32_t min_sites, uint32_t min_length, const void *d_pairs,
-                            uint64_t num_pairs, uint32_t pair_stride, cuking_ibd_pair *d_out,
+                            uint32_t min_sites, uint32_t min_length, uint32_t bridge_sites,
+                            const void *d_pairs, uint64_t num_pairs, uint32_t pair_stride,
+                            cuking_ibd_pair *d_out, uint32_t *d_bridged,
                             cuking_ibd_segment *d_segments, uint64_t max_segments,
                             unsigned long long *d_count, hipStream_t stream) {
   if (num_pairs == 0) return hipSuccess;
-  IbdArgs a;
+  IbdBridgeArgs a;
   a.bits = d_bits;
   a.group_bits = d_group_bits;
   a.pos = d_pos;
@@ -218,10 +325,23 @@ hipError_t launch_ibd_pairs(const uint64_t *d_bits, uint32_t num_stored,
   a.num_sites = num_sites;
   a.min_sites = min_sites;
   a.min_length = min_length;
+  a.bridged = d_bridged;
+  a.bridge_sites = bridge_sites;
   const uint64_t blocks = (num_pairs + kIbdWaves - 1) / kIbdWaves;
+  if (bridge_sites == 0) {
+    // nothing is linked: the strict kernel, and no pair has a bridged break
+    if (d_bridged != nullptr) {
+      const hipError_t err = hipMemsetAsync(d_bridged, 0, num_pairs * 2 * sizeof(uint32_t), stream);
+      if (err != hipSuccess) return err;
+    }
+    return launch_in_chunks(blocks, kIbdThreads, [&](uint64_t done, uint32_t n) {
+      a.pair_base = done * kIbdWaves;
+      ibd_pairs_kernel<false><<<dim3(n), dim3(kIbdThreads), 0, stream>>>(a);
+    });
+  }
   return launch_in_chunks(blocks, kIbdThreads, [&](uint64_t done, uint32_t n) {
     a.pair_base = done * kIbdWaves;
-    ibd_pairs_kernel<<<dim3(n), dim3(kIbdThreads), 0, stream>>>(a);
+    ibd_pairs_kernel<true><<<dim3(n), dim3(kIbdThreads), 0, stream>>>(a);
   });
 }
 

@@ -4,6 +4,10 @@ TRUFFLE on unphased data.  include/cuking_amd.h "IBD segments for listed pairs" 
 definition, csrc/king_ibd.h the word masks; this module wraps the call and derives the shared
 proportions, a kinship and the relationship from the lengths.  No allele frequency, no principal
 component and no ``min_maf`` enters, so the answer does not depend on a model of ancestry.
+
+``bridge_sites`` (0, or at least 64) forgives isolated genotyping errors: two runs of at least
+that many sites on either side of one break site of a group are linked, and a segment is a
+chain of linked runs (the header's "IBD segments with bridged breaks").  0 is the strict call.
 """
 from __future__ import annotations
 
@@ -41,12 +45,16 @@ class IBDPairs:
     number of segments of kind 1 / 2), ``length1``, ``length2`` (uint64: the sum of their
     lengths), ``longest1``, ``longest2`` (uint32); ``total_length`` (``genome_length`` of the
     call); ``segments`` (``IBD_SEGMENT_DTYPE`` rows in no particular order, or None when they
-    were not asked for); ``min_sites`` and ``min_length`` of the call."""
+    were not asked for); ``min_sites``, ``min_length`` and ``bridge_sites`` of the call;
+    ``bridged`` (uint32 ``[P, 2]`` when ``bridge_sites`` is not 0, else None): the bridged breaks
+    inside the counted segments of kind 1 and of kind 2 -- the errors that were forgiven."""
     rows: np.ndarray
     total_length: int
     segments: object
     min_sites: int
     min_length: int
+    bridge_sites: int = 0
+    bridged: object = None
 
     sample_i = property(lambda self: self.rows["sample_i"])
     sample_j = property(lambda self: self.rows["sample_j"])
@@ -131,6 +139,10 @@ def _thresholds(min_sites, min_length):
     return _count(min_sites, "min_sites"), _count(min_length, "min_length")
 
 
+def _bridge(bridge_sites) -> int:
+    return _count(bridge_sites, "bridge_sites")
+
+
 def _default_segments(count: int) -> int:
     """The buffer of a call without ``max_segments``: four segments per pair (the call is
     repeated once with the exact count if that overflows)."""
@@ -146,35 +158,44 @@ def _exhausted(count: int):
 
 def ibd_segments_raw_host(bits: np.ndarray, words_per_sample: int, num_sites: int, pairs,
                           group=None, pos=None, min_sites: int = 512, min_length: int = 0,
-                          segments: bool = False, max_segments=None, num_records=None):
+                          segments: bool = False, max_segments=None, num_records=None,
+                          bridge_sites: int = 0):
     """cuking_ibd_pairs_host, the bare call: ``(rows, segments)`` -- one ``IBD_PAIR_DTYPE`` row
     per pair of ``pairs`` (records with ``num_records``, or an integer ``[P, 2]`` array) and,
     with ``segments`` (or a ``max_segments``), the ``IBD_SEGMENT_DTYPE`` rows, else None.  Bit
     for bit what ``KingContext.ibd_segments_raw`` gives.  The buffer rule is ``ld_edges_host``'s:
     without ``max_segments`` a default buffer, grown once to the exact count; with it, an
-    overflow raises ``ResourceExhaustedError`` whose ``num_segments`` is the exact count."""
+    overflow raises ``ResourceExhaustedError`` whose ``num_segments`` is the exact count.
+    With ``bridge_sites`` not 0 it is cuking_ibd_pairs_bridged_host and returns ``(rows,
+    segments, bridged)``, ``bridged`` uint32 ``[P, 2]``."""
     assert bits.dtype == np.uint64 and bits.flags.c_contiguous
     words_per_sample = _count(words_per_sample, "words_per_sample")
     num_sites = _count(num_sites, "num_sites")
     min_sites, min_length = _thresholds(min_sites, min_length)
+    bridge_sites = _bridge(bridge_sites)
     num_stored = bits.size // words_per_sample if words_per_sample else 0
     group = _site_array(group, "group", num_sites, np.int32)
     pos = _site_array(pos, "pos", num_sites, np.uint32)
     owner, ptr, count, stride = _host_pairs(pairs, num_records)   # (owner keeps ptr alive)
     out = np.zeros(count, dtype=IBD_PAIR_DTYPE)
+    bridged = np.zeros((count, 2), dtype=np.uint32)
     pad = np.zeros(4, dtype=np.uint64)
     found = C.c_uint64(0)
     want = segments or max_segments is not None
 
     def call(capacity):
         segs = np.zeros(max(capacity, 1), dtype=IBD_SEGMENT_DTYPE)
-        status = _lib.load().cuking_ibd_pairs_host(
-            (bits if bits.size else pad).ctypes.data, num_stored, words_per_sample, num_sites,
-            None if group is None or not group.size else group.ctypes.data,
-            None if pos is None or not pos.size else pos.ctypes.data, min_sites, min_length,
-            ptr if count else None, count, stride, out.ctypes.data if count else None,
-            segs.ctypes.data if want and capacity else None, capacity if want else 0,
-            C.byref(found) if want else None)
+        head = ((bits if bits.size else pad).ctypes.data, num_stored, words_per_sample, num_sites,
+                None if group is None or not group.size else group.ctypes.data,
+                None if pos is None or not pos.size else pos.ctypes.data, min_sites, min_length)
+        pair = (ptr if count else None, count, stride, out.ctypes.data if count else None)
+        tail = (segs.ctypes.data if want and capacity else None, capacity if want else 0,
+                C.byref(found) if want else None)
+        if bridge_sites == 0:
+            status = _lib.load().cuking_ibd_pairs_host(*head, *pair, *tail)
+        else:
+            status = _lib.load().cuking_ibd_pairs_bridged_host(
+                *head, bridge_sites, *pair, bridged.ctypes.data if count else None, *tail)
         return segs, status
 
     segs, status = call(0 if not want else _default_segments(count) if max_segments is None
@@ -184,18 +205,20 @@ def ibd_segments_raw_host(bits: np.ndarray, words_per_sample: int, num_sites: in
     if status == _lib.ERR_RESOURCE_EXHAUSTED:
         raise _exhausted(int(found.value))
     check(status)
-    return out, segs[:found.value].copy() if want else None
+    segs = segs[:found.value].copy() if want else None
+    return (out, segs) if bridge_sites == 0 else (out, segs, bridged)
 
 
 def ibd_segments_host(bits: np.ndarray, words_per_sample: int, num_sites: int, pairs,
                       group=None, pos=None, min_sites: int = 512, min_length: int = 0,
-                      segments: bool = False, max_segments=None, num_records=None) -> IBDPairs:
+                      segments: bool = False, max_segments=None, num_records=None,
+                      bridge_sites: int = 0) -> IBDPairs:
     """``KingContext.ibd_segments`` on host memory and the host twin: no GPU."""
-    rows, segs = ibd_segments_raw_host(bits, words_per_sample, num_sites, pairs, group, pos,
-                                       min_sites, min_length, segments, max_segments,
-                                       num_records)
+    rows, segs, *bridged = ibd_segments_raw_host(bits, words_per_sample, num_sites, pairs, group,
+                                                 pos, min_sites, min_length, segments,
+                                                 max_segments, num_records, bridge_sites)
     return IBDPairs(rows, genome_length(group, pos, num_sites), segs, int(min_sites),
-                    int(min_length))
+                    int(min_length), int(bridge_sites), *bridged)
 
 
 def rows_to_host(rows) -> np.ndarray:
@@ -209,6 +232,12 @@ def segments_to_host(segments, num_segments: int) -> np.ndarray:
     ``ibd_segments_raw`` as ``IBD_SEGMENT_DTYPE`` rows on the host (waits for the copy)."""
     return np.ascontiguousarray(segments[:num_segments].cpu().numpy()) \
         .view(IBD_SEGMENT_DTYPE).reshape(-1)
+
+
+def bridged_to_host(bridged) -> np.ndarray:
+    """The ``[P, 2]`` int32 device tensor of ``ibd_segments_raw`` as uint32 on the host (waits for
+    the copy)."""
+    return np.ascontiguousarray(bridged.cpu().numpy()).view(np.uint32)
 
 
 def _device_sites(ctx, values, name: str, num_sites: int, dtype):
@@ -227,12 +256,13 @@ def _device_sites(ctx, values, name: str, num_sites: int, dtype):
 def ibd_segments_raw_device(ctx, bits, words_per_sample: int, num_sites: int, pairs, group=None,
                             pos=None, min_sites: int = 512, min_length: int = 0,
                             segments: bool = False, max_segments=None, num_records=None,
-                            out=None, stream=None):
+                            out=None, stream=None, bridge_sites: int = 0):
     import torch
     from .api import _device_tensor, _stream_handle
     words_per_sample = _count(words_per_sample, "words_per_sample")
     num_sites = _count(num_sites, "num_sites")
     min_sites, min_length = _thresholds(min_sites, min_length)
+    bridge_sites = _bridge(bridge_sites)
     num_stored = ctx._rows_of(bits, words_per_sample)
     dev = f"cuda:{ctx.device}"
     d_group = _device_sites(ctx, group, "group", num_sites, np.int32)
@@ -242,6 +272,9 @@ def ibd_segments_raw_device(ctx, bits, words_per_sample: int, num_sites: int, pa
         out = torch.empty((count, 10), dtype=torch.int32, device=dev)
     else:
         _device_tensor(ctx.device, out, "out", torch.int32, shape=(count, 10))
+    bridged = None
+    if bridge_sites != 0:   # (uint32 travels as its int32 bit pattern)
+        bridged = torch.empty((count, 2), dtype=torch.int32, device=dev)
     want = segments or max_segments is not None
     found = C.c_uint64(0)
     # (uploads ran on the current stream: `stream` waits for them)
@@ -249,13 +282,18 @@ def ibd_segments_raw_device(ctx, bits, words_per_sample: int, num_sites: int, pa
         stream.wait_stream(torch.cuda.current_stream())
 
     def call(segs, capacity):
-        return ctx.lib.cuking_ibd_pairs(
-            ctx.handle, bits.data_ptr(), num_stored, words_per_sample, num_sites,
-            None if d_group is None or not num_sites else d_group.data_ptr(),
-            None if d_pos is None or not num_sites else d_pos.data_ptr(), min_sites, min_length,
-            owner.data_ptr() if count else None, count, stride,
-            out.data_ptr() if count else None, segs.data_ptr() if want and capacity else None,
-            capacity if want else 0, C.byref(found) if want else None, _stream_handle(stream))
+        head = (ctx.handle, bits.data_ptr(), num_stored, words_per_sample, num_sites,
+                None if d_group is None or not num_sites else d_group.data_ptr(),
+                None if d_pos is None or not num_sites else d_pos.data_ptr(), min_sites,
+                min_length)
+        pair = (owner.data_ptr() if count else None, count, stride,
+                out.data_ptr() if count else None)
+        tail = (segs.data_ptr() if want and capacity else None, capacity if want else 0,
+                C.byref(found) if want else None, _stream_handle(stream))
+        if bridge_sites == 0:
+            return ctx.lib.cuking_ibd_pairs(*head, *pair, *tail)
+        return ctx.lib.cuking_ibd_pairs_bridged(*head, bridge_sites, *pair,
+                                                bridged.data_ptr() if count else None, *tail)
 
     grow = max_segments is None
     capacity = 0 if not want else _default_segments(count) if grow \
@@ -273,22 +311,23 @@ def ibd_segments_raw_device(ctx, bits, words_per_sample: int, num_sites: int, pa
         for t in (owner, d_group, d_pos, segs):
             if t is not None:
                 t.record_stream(stream)
-    return out, (segs if want else None), int(found.value)
+    got = (out, (segs if want else None), int(found.value))
+    return got if bridge_sites == 0 else got + (bridged,)
 
 
 def ibd_segments_device(ctx, bits, words_per_sample: int, num_sites: int, pairs, group=None,
                         pos=None, min_sites: int = 512, min_length: int = 0,
                         segments: bool = False, max_segments=None, num_records=None,
-                        stream=None) -> IBDPairs:
+                        stream=None, bridge_sites: int = 0) -> IBDPairs:
     import torch
     host_group = group.cpu().numpy() if isinstance(group, torch.Tensor) else group
     host_pos = pos.cpu().numpy().view(np.uint32) if isinstance(pos, torch.Tensor) else pos
     total = genome_length(host_group, host_pos, num_sites)
-    rows, segs, found = ibd_segments_raw_device(ctx, bits, words_per_sample, num_sites, pairs,
-                                                group, pos, min_sites, min_length, segments,
-                                                max_segments, num_records, stream=stream)
+    rows, segs, found, *bridged = ibd_segments_raw_device(
+        ctx, bits, words_per_sample, num_sites, pairs, group, pos, min_sites, min_length, segments,
+        max_segments, num_records, stream=stream, bridge_sites=bridge_sites)
     if stream is not None:
         stream.synchronize()
     return IBDPairs(rows_to_host(rows), total,
                     None if segs is None else segments_to_host(segs, found), int(min_sites),
-                    int(min_length))
+                    int(min_length), int(bridge_sites), *map(bridged_to_host, bridged))

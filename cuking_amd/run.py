@@ -180,6 +180,12 @@ def parse_args(argv=None):
     flag("ibd-min-length", type=int, default=None,
          help="the least length of a segment of --ibd-segments-uri, in the .bim's positions "
               "(default 0)")
+    flag("ibd-bridge-sites", type=int, default=None,
+         help="--ibd-segments-uri forgives isolated genotyping errors: two runs of at least this "
+              "many sites on either side of one break site of a chromosome count as one "
+              "segment (0, or at least 64; default: no bridging).  Adds bridge_sites, bridged1 "
+              "and bridged2 (the bridged breaks inside each record's counted segments) to the "
+              "file")
     flag("ibd-segment-list", action="store_true",
          help="--ibd-segments-uri also writes the segments themselves: segment_pair (the "
               "record's number), segment_kind, segment_first_site, segment_last_site (site "
@@ -337,6 +343,13 @@ def validate(args):  # cuking.cu:437-462
             args.ibd_segment_list) and not args.ibd_segments_uri:
         raise UsageError("--ibd_min_sites, --ibd_min_length and --ibd_segment_list need "
                          "--ibd_segments_uri")
+    if args.ibd_bridge_sites is not None:
+        if not args.ibd_segments_uri:
+            raise UsageError("--ibd_bridge_sites needs --ibd_segments_uri")
+        if args.ibd_bridge_sites != 0 and not IBD_MIN_SITES <= args.ibd_bridge_sites < 1 << 32:
+            raise UsageError(f"--ibd_bridge_sites must be 0 or at least {IBD_MIN_SITES} (and "
+                             "below 2^32): shorter runs lie inside one 64-site word, which the "
+                             "scan does not enumerate")
     if args.ibd_segments_uri:
         if int(os.environ.get("WORLD_SIZE", "1")) > 1:
             raise UsageError("--ibd_segments_uri needs one process (one GPU): the records are "
@@ -655,20 +668,28 @@ def write_pcrelate_records(path: Path, ctx, bits, wps: int, num_sites: int, pca,
 
 def write_ibd_segments(path: Path, ctx, bits, wps: int, num_sites: int, recs, group, pos,
                        site_index, min_sites: int, min_length: int, with_list: bool,
-                       sample_ids) -> None:
+                       sample_ids, bridge_sites=None) -> None:
     """This run's records scanned for IBD segments as an .npz: `sample_i`, `sample_j`,
     `segments1`, `segments2`, `length1`, `length2`, `longest1`, `longest2`, `pi1`, `pi2`,
     `kin_ibd`, `relationship` (one entry per record, in the records' order; the codes of
     IBDPairs.relationship), `total_length`, `samples`, `min_sites`, `min_length`; with
     `with_list` the sorted segments as `segment_pair`, `segment_kind`, `segment_first_site`,
-    `segment_last_site` (through `site_index`: numbers among the input's sites)."""
+    `segment_last_site` (through `site_index`: numbers among the input's sites); with a
+    `bridge_sites` (0 included) also `bridge_sites`, `bridged1` and `bridged2`."""
     got = ctx.ibd_segments(bits, wps, num_sites, recs, group=group, pos=pos,
-                           min_sites=min_sites, min_length=min_length, segments=with_list)
+                           min_sites=min_sites, min_length=min_length, segments=with_list,
+                           bridge_sites=bridge_sites or 0)
     pi1, pi2, kin = got.proportions()
     extra = {}
+    if bridge_sites is not None:
+        bridged = got.bridged if got.bridged is not None else \
+            np.zeros((len(got.rows), 2), dtype=np.uint32)   # (0: nothing is bridged)
+        extra = dict(bridge_sites=np.int64(bridge_sites),
+                     bridged1=np.ascontiguousarray(bridged[:, 0]),
+                     bridged2=np.ascontiguousarray(bridged[:, 1]))
     if with_list:
         segs = got.sorted()
-        extra = dict(segment_pair=segs["pair"], segment_kind=segs["kind"],
+        extra.update(segment_pair=segs["pair"], segment_kind=segs["kind"],
                      segment_first_site=site_index[segs["first_site"]],
                      segment_last_site=site_index[segs["last_site"]])
     path.parent.mkdir(parents=True, exist_ok=True)
@@ -949,7 +970,7 @@ def main(argv=None) -> int:
                                    ibd_pos, site_index,
                                    512 if args.ibd_min_sites is None else args.ibd_min_sites,
                                    0 if args.ibd_min_length is None else args.ibd_min_length,
-                                   args.ibd_segment_list, sample_ids)
+                                   args.ibd_segment_list, sample_ids, args.ibd_bridge_sites)
             pairs = sm.NumPairs()
             print(json.dumps({"pairs": pairs, "results": int(len(recs)), "gpus": world,
                               "compute_seconds": dt,

@@ -1155,9 +1155,9 @@ cuking_status cuking_pcrelate_pairs(cuking_ctx *ctx, const uint64_t *d_bits, uin
  * site: pos[s] < pos[s - 1] inside a group (the device call copies group and pos to the host for
  * this check).  num_pairs == 0 returns OK without work (after the checks of the arguments);
  * num_sites == 0 writes zero rows.
- * Out of scope: the C++ `cuking` binary; several ranks; tolerance for genotyping errors inside a
- * run (one wrong homozygote splits a segment); trimming segment ends; an all-pairs scan; phased
- * IBD; recombination maps beyond an integer pos. */
+ * One wrong homozygote splits a run; cuking_ibd_pairs_bridged below forgives isolated ones.
+ * Out of scope: the C++ `cuking` binary; several ranks; an all-pairs scan; phased IBD;
+ * recombination maps beyond an integer pos. */
 #define CUKING_IBD_MIN_SITES 64
 typedef struct cuking_ibd_pair {
   uint32_t sample_i, sample_j;   /* copied from the input */
@@ -1182,6 +1182,69 @@ cuking_status cuking_ibd_pairs(cuking_ctx *ctx, const uint64_t *d_bits, uint32_t
                                uint32_t pair_stride, cuking_ibd_pair *d_out,
                                cuking_ibd_segment *d_segments, uint64_t max_segments,
                                uint64_t *num_segments, void *stream);
+
+/* IBD segments with bridged breaks: the call above, tolerant of sparse genotyping errors.  On
+ * real calls with 0.1 - 1 % discordance a single wrong homozygote cuts a true IBD stretch into
+ * pieces that fall below min_sites; KING --ibdseg, IBIS and TRUFFLE all forgive such errors.
+ * Everything of "IBD segments for listed pairs" stays -- codes, opp, diff, groups, pos, runs,
+ * missing sites, the segment test -- and one argument is added: bridge_sites, either 0 or >=
+ * CUKING_IBD_MIN_SITES.  Still decided on integers and a function of the pair's genotypes only.
+ *
+ * For one pair and one kind, the runs in site order:
+ *     linked    two consecutive runs [a, b] and [a', b'] are linked iff
+ *                 a' == b + 2 (exactly one site lies between them: a break of this kind),
+ *                 sites b, b + 1, b + 2 lie in one group (no group starts at b + 1 or b + 2),
+ *                 b - a + 1 >= bridge_sites and b' - a' + 1 >= bridge_sites (missing sites
+ *                 count as sites, as they do for min_sites)
+ *     chain     a maximal sequence of runs joined by links; its interval [A, B] goes from the
+ *               first site of its first run to the last site of its last run and includes the
+ *               bridged break sites
+ *     segment   a chain with B - A + 1 >= min_sites and pos[B] - pos[A] >= min_length; its
+ *               length is pos[B] - pos[A]
+ * Consequences:
+ *   - bridge_sites = 0 links nothing: the call above, byte for byte;
+ *   - a link depends on the two runs and the site between them only, so the chains are unique;
+ *   - a segment has at most one break per bridge_sites + 1 sites;
+ *   - two adjacent break sites are never bridged, nor is a break that is the first or the last
+ *     site of a group, nor a break at site 0 or at num_sites - 1;
+ *   - a run inside a chain may be shorter than min_sites: 100 + 1 + 100 sites pass min_sites =
+ *     150 at bridge_sites = 64;
+ *   - kind 2 bridges diff sites, kind 1 opp sites, independently.  A bridged diff site that is
+ *     also opp is bridged in kind 1 too (the kind-1 runs around it contain the kind-2 runs), so
+ *     every kind-2 chain lies inside a kind-1 chain and length2 <= length1 still holds;
+ *   - bridge_sites >= 64 plays the part of min_sites >= 64: both runs of a link close in a later
+ *     word than they start in, a bridged break is the only break of its 64-site word, and nobody
+ *     enumerates bits.
+ *
+ * out and segments keep their rows; first_site and last_site are the chain's A and B.
+ *     bridged   uint32 [num_pairs][2] or null: the links inside the COUNTED segments of kind 1
+ *               and of kind 2 -- the number of forgiven errors, what a user looks at to judge
+ *               bridge_sites.  Plain stores; zero for a pair with an index >= num_stored.
+ * Every refusal of the call above applies, and 0 < bridge_sites < 64 is INVALID_ARGUMENT.  The
+ * segment-list buffer rule, the waits, (i, j) == (j, i) and "a row depends on its own pair only"
+ * are unchanged.  The order of the segment list is unspecified on the host and on the device:
+ * the set is the contract.  (At bridge_sites = 0 the device runs the kernel of the call above.)
+ * Out of scope: gaps of more than one site; per-segment error counts in the list; trimming of
+ * segment ends; a model of the error rate. */
+cuking_status cuking_ibd_pairs_bridged_host(const uint64_t *bits, uint32_t num_stored,
+                                            uint32_t words_per_sample, uint32_t num_sites,
+                                            const int32_t *group, const uint32_t *pos,
+                                            uint32_t min_sites, uint32_t min_length,
+                                            uint32_t bridge_sites, const void *pairs,
+                                            uint64_t num_pairs, uint32_t pair_stride,
+                                            cuking_ibd_pair *out, uint32_t *bridged,
+                                            cuking_ibd_segment *segments, uint64_t max_segments,
+                                            uint64_t *num_segments);
+cuking_status cuking_ibd_pairs_bridged(cuking_ctx *ctx, const uint64_t *d_bits,
+                                       uint32_t num_stored, uint32_t words_per_sample,
+                                       uint32_t num_sites, const int32_t *d_group,
+                                       const uint32_t *d_pos, uint32_t min_sites,
+                                       uint32_t min_length, uint32_t bridge_sites,
+                                       const void *d_pairs, uint64_t num_pairs,
+                                       uint32_t pair_stride, cuking_ibd_pair *d_out,
+                                       uint32_t *d_bridged, cuking_ibd_segment *d_segments,
+                                       uint64_t max_segments, uint64_t *num_segments,
+                                       void *stream);
 
 /* cuking.cu:761-765 on host memory: sort by (sample_i, sample_j, kin). */
 void cuking_sort_results(cuking_result *results, size_t num_results);

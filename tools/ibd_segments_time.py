@@ -10,8 +10,15 @@ Random pairs of unrelated samples have next to no segment: the list costs its co
 wait, not its stores.  The registers and occupancy of the kernel come from the build (`python -m
 cuking_amd.build --lib --force --save-temps`), not from this tool.
 
-usage: python tools/ibd_segments_time.py [OUT]   (OUT is overwritten; default: nothing is written)
+With `--bridge-sites N` the yardsticks are `bits.clone()` and the strict scan of the same process
+(PC-Relate is left out): after each strict measurement the same list goes through
+`ibd_segments_raw(..., bridge_sites=N)`, the bridging instantiation of the kernel, without and
+with the segment list, and the record carries `vs_strict`, its median over the strict one's.
+
+usage: python tools/ibd_segments_time.py [--bridge-sites N] [OUT]
+       (OUT is overwritten; default: nothing is written)
 """
+import argparse
 import json
 import os
 import sys
@@ -24,7 +31,11 @@ import torch
 import cuking_amd
 from cuking_amd.synth import cohort_to_device, plan_cohort
 
-out = open(sys.argv[1] if len(sys.argv) > 1 else os.devnull, "w")
+parser = argparse.ArgumentParser()
+parser.add_argument("out", nargs="?", default=os.devnull)
+parser.add_argument("--bridge-sites", type=int, default=0)
+args = parser.parse_args()
+out = open(args.out, "w")
 
 
 def say(record):
@@ -71,20 +82,31 @@ bytes_per_pair = 4 * ((m + 63) // 64) * 8
 for p in (10_000, 100_000, 1_000_000):
     d_pairs = torch.from_numpy(rng.integers(0, n, size=(p, 2)).astype(np.int32)).to("cuda:0")
     warm = 2 if p < 1_000_000 else 1
-    rows = torch.empty((p, 8), dtype=torch.int32, device="cuda:0")
-    med, low = timed(lambda: ctx.pcrelate_pairs_raw(bits, wps, m, d_x, d_beta, 0.01, 0.99,
-                                                    d_pairs, d_f, out=rows), warm=warm)
-    say(dict(op="pcrelate_pairs", pairs=p, d=d, median_ms=med, min_ms=low,
-             ns_per_pair=med * 1e6 / p))
+    if not args.bridge_sites:
+        rows = torch.empty((p, 8), dtype=torch.int32, device="cuda:0")
+        med, low = timed(lambda: ctx.pcrelate_pairs_raw(bits, wps, m, d_x, d_beta, 0.01, 0.99,
+                                                        d_pairs, d_f, out=rows), warm=warm)
+        say(dict(op="pcrelate_pairs", pairs=p, d=d, median_ms=med, min_ms=low,
+                 ns_per_pair=med * 1e6 / p))
     rows = torch.empty((p, 10), dtype=torch.int32, device="cuda:0")
     for with_list in (False, True):
-        found = []
+        strict_ms = None
+        for bridge in (0, args.bridge_sites) if args.bridge_sites else (0,):
+            found = []
 
-        def scan():
-            found.append(ctx.ibd_segments_raw(bits, wps, m, d_pairs, segments=with_list,
-                                              out=rows)[2])
-        med, low = timed(scan, warm=warm)
-        say(dict(op="ibd_segments", pairs=p, segment_list=with_list, min_sites=512,
-                 segments_found=found[-1], median_ms=med, min_ms=low, ns_per_pair=med * 1e6 / p,
-                 bytes_per_pair=bytes_per_pair, gb_per_s=bytes_per_pair * p / med / 1e6))
+            def scan():
+                found.append(ctx.ibd_segments_raw(bits, wps, m, d_pairs, segments=with_list,
+                                                  out=rows, bridge_sites=bridge)[2])
+            med, low = timed(scan, warm=warm)
+            record = dict(op="ibd_segments", pairs=p, segment_list=with_list, min_sites=512,
+                          segments_found=found[-1], median_ms=med, min_ms=low,
+                          ns_per_pair=med * 1e6 / p, bytes_per_pair=bytes_per_pair,
+                          gb_per_s=bytes_per_pair * p / med / 1e6)
+            if args.bridge_sites:
+                record["bridge_sites"] = bridge
+            if bridge:
+                record["vs_strict"] = med / strict_ms
+            else:
+                strict_ms = med
+            say(record)
 out.close()
