@@ -1238,6 +1238,44 @@ class KingContext:
                                         pos, min_sites, min_length, segments, max_segments,
                                         num_records, stream, bridge_sites)
 
+    def roh_segments_raw(self, bits, words_per_sample: int, num_sites: int, samples=None,
+                         group=None, pos=None, min_sites: int = 512, min_length: int = 0,
+                         bridge_sites: int = 0, segments: bool = False, max_segments=None,
+                         out=None, stream=None):
+        """The bare kernel call for runs of homozygosity (cuking_roh_samples;
+        include/cuking_amd.h "Runs of homozygosity" has the definition): for every sample of
+        ``samples`` (an integer ``[S]`` host array or int32 device tensor, repeats and any order
+        allowed; None: every row of ``bits``) the number, summed length and longest of the runs
+        of at least ``min_sites`` sites and ``min_length`` positions without a heterozygous
+        call.  ``group``, ``pos``, ``bridge_sites`` (which here forgives one isolated het),
+        ``segments``, ``max_segments`` and the waits are those of ``ibd_segments_raw``.  Returns
+        ``(rows, segments, num_segments)``: an int32 ``[S, 6]`` device tensor, one
+        cuking_roh_sample per row in list order (``roh.rows_to_host`` gives it names; ``out``:
+        such a tensor to write into), and with ``segments`` an int32 ``[*, 4]`` device tensor
+        whose first ``num_segments`` rows are cuking_ibd_segment (``pair`` = the row index,
+        ``kind`` 0) in no particular order, else None and 0.  The buffer defaults to four
+        segments per sample and is grown once to the exact count."""
+        from . import roh as _roh
+        return _roh.roh_segments_raw_device(self, bits, words_per_sample, num_sites, samples,
+                                            group, pos, min_sites, min_length, bridge_sites,
+                                            segments, max_segments, out, stream)
+
+    def roh_segments(self, bits, words_per_sample: int, num_sites: int, samples=None,
+                     group=None, pos=None, min_sites: int = 512, min_length: int = 0,
+                     bridge_sites: int = 0, segments: bool = False, max_segments=None,
+                     stream=None):
+        """Runs of homozygosity of the listed samples as a ``ROHSamples`` of host arrays
+        (arguments as ``roh_segments_raw`` takes them): its ``froh()`` is the share of
+        ``genome_length`` inside the runs -- the inbreeding estimate with no allele frequency
+        and no principal component involved --, its ``segment_list`` says where they lie.
+        ``bridge_sites`` of 64 or more forgives an isolated het between two runs of at least
+        that many sites, and ``ROHSamples.bridged`` counts the forgiven.  Waits for the
+        device."""
+        from . import roh as _roh
+        return _roh.roh_segments_device(self, bits, words_per_sample, num_sites, samples, group,
+                                        pos, min_sites, min_length, bridge_sites, segments,
+                                        max_segments, stream)
+
     def synth_bitset(self, seed: int, kind, pa, pb, sample_begin: int,
                      sample_end: int, num_sites: int, out=None, stream=None, model=0):
         """Synthetic reference-layout bitset rows [sample_begin, sample_end)

@@ -108,8 +108,8 @@ def build_library(force: bool = False, save_temps: bool = False) -> Path:
                                  "pcrelate_records_kernel")
     problems += check_no_scratch(cwd / "king_pcrelate_pairs-hip-amdgcn-amd-amdhsa-gfx950.s",
                                  "pcrelate_pairs_kernel")
-    problems += check_no_scratch(cwd / "king_ibd-hip-amdgcn-amd-amdhsa-gfx950.s",
-                                 "ibd_pairs_kernel")
+    for kernel in ("ibd_pairs_kernel", "roh_samples_kernel"):
+        problems += check_no_scratch(cwd / "king_ibd-hip-amdgcn-amd-amdhsa-gfx950.s", kernel)
     if problems and not extra:
         LIB_PATH.unlink(missing_ok=True)
         raise RuntimeError("the compiler put vector-memory waits or scratch accesses inside an "

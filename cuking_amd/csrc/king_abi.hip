@@ -2124,29 +2124,17 @@ cuking_status cuking_pcrelate_pairs(cuking_ctx *ctx, const uint64_t *d_bits, uin
 
 // ---- IBD segments for listed pairs (king_ibd.hip) ------------------------------
 
-// Both entry points: bridge_sites == 0 is the strict call.
-static cuking_status ibd_pairs_device(cuking_ctx *ctx, const uint64_t *d_bits,
-                                      uint32_t num_stored, uint32_t words_per_sample,
-                                      uint32_t num_sites, const int32_t *d_group,
-                                      const uint32_t *d_pos, uint32_t min_sites,
-                                      uint32_t min_length, uint32_t bridge_sites,
-                                      const void *d_pairs, uint64_t num_pairs,
-                                      uint32_t pair_stride, cuking_ibd_pair *d_out,
-                                      uint32_t *d_bridged, cuking_ibd_segment *d_segments,
-                                      uint64_t max_segments, uint64_t *num_segments,
-                                      void *stream) {
-  if (num_segments != nullptr) *num_segments = 0;
-  // (the arguments first: a refused call touches no device)
-  if (ctx == nullptr) return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "null context");
-  cuking_status st = cuking_check_ibd_args(d_bits, words_per_sample, num_sites, min_sites,
-                                           d_pairs, num_pairs, pair_stride, d_out, d_segments,
-                                           max_segments, num_segments);
-  if (st != CUKING_OK) return st;
-  st = cuking_check_ibd_bridge(bridge_sites);
-  if (st != CUKING_OK) return st;
-  if (num_pairs == 0) return CUKING_OK;
+// What the pair calls and the scan of single samples share once their arguments are checked and
+// there is work to do: the host check of the positions, the group bits and the count word of the
+// stream's scratch, `launch(d_group_bits, d_count, stream)`, and the count read back.
+extern "C++" {
+template <class Launch>
+static cuking_status ibd_scan_device(cuking_ctx *ctx, uint32_t num_sites, const int32_t *d_group,
+                                     const uint32_t *d_pos, uint64_t max_segments,
+                                     uint64_t *num_segments, void *stream, Launch &&launch) {
   BIND_OR_RETURN(ctx);
   hipStream_t s = (hipStream_t)stream;
+  cuking_status st;
   if (d_pos != nullptr && num_sites > 1) {
     // The host check of the positions, on copies: ordered on the stream behind whatever
     // writes the arrays.
@@ -2174,9 +2162,7 @@ static cuking_status ibd_pairs_device(cuking_ctx *ctx, const uint64_t *d_bits,
     d_count = static_cast<unsigned long long *>(e->record_count.p);
     HIP_TRY(hipMemsetAsync(d_count, 0, sizeof(unsigned long long), s));
   }
-  HIP_TRY(launch_ibd_pairs(d_bits, num_stored, words_per_sample, num_sites, d_group_bits, d_pos,
-                           min_sites, min_length, bridge_sites, d_pairs, num_pairs, pair_stride,
-                           d_out, d_bridged, d_segments, max_segments, d_count, s));
+  HIP_TRY(launch(d_group_bits, d_count, s));
   if (num_segments == nullptr) return CUKING_OK;
   unsigned long long count = 0;
   HIP_TRY(hipMemcpyAsync(&count, d_count, sizeof(count), hipMemcpyDeviceToHost, s));
@@ -2184,6 +2170,63 @@ static cuking_status ibd_pairs_device(cuking_ctx *ctx, const uint64_t *d_bits,
   HIP_TRY(hipStreamSynchronize(s));
   *num_segments = count;
   return cuking_ibd_count_status(count, max_segments);
+}
+}  // extern "C++"
+
+// Both entry points: bridge_sites == 0 is the strict call.
+static cuking_status ibd_pairs_device(cuking_ctx *ctx, const uint64_t *d_bits,
+                                      uint32_t num_stored, uint32_t words_per_sample,
+                                      uint32_t num_sites, const int32_t *d_group,
+                                      const uint32_t *d_pos, uint32_t min_sites,
+                                      uint32_t min_length, uint32_t bridge_sites,
+                                      const void *d_pairs, uint64_t num_pairs,
+                                      uint32_t pair_stride, cuking_ibd_pair *d_out,
+                                      uint32_t *d_bridged, cuking_ibd_segment *d_segments,
+                                      uint64_t max_segments, uint64_t *num_segments,
+                                      void *stream) {
+  if (num_segments != nullptr) *num_segments = 0;
+  // (the arguments first: a refused call touches no device)
+  if (ctx == nullptr) return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "null context");
+  cuking_status st = cuking_check_ibd_args(d_bits, words_per_sample, num_sites, min_sites,
+                                           d_pairs, num_pairs, pair_stride, d_out, d_segments,
+                                           max_segments, num_segments);
+  if (st != CUKING_OK) return st;
+  st = cuking_check_ibd_bridge(bridge_sites);
+  if (st != CUKING_OK) return st;
+  if (num_pairs == 0) return CUKING_OK;
+  return ibd_scan_device(
+      ctx, num_sites, d_group, d_pos, max_segments, num_segments, stream,
+      [&](const uint64_t *d_group_bits, unsigned long long *d_count, hipStream_t s) {
+        return launch_ibd_pairs(d_bits, num_stored, words_per_sample, num_sites, d_group_bits,
+                                d_pos, min_sites, min_length, bridge_sites, d_pairs, num_pairs,
+                                pair_stride, d_out, d_bridged, d_segments, max_segments, d_count,
+                                s);
+      });
+}
+
+// ---- runs of homozygosity (king_ibd.hip) ----------------------------------------
+cuking_status cuking_roh_samples(cuking_ctx *ctx, const uint64_t *d_bits, uint32_t num_stored,
+                                 uint32_t words_per_sample, uint32_t num_sites,
+                                 const int32_t *d_group, const uint32_t *d_pos,
+                                 uint32_t min_sites, uint32_t min_length, uint32_t bridge_sites,
+                                 const uint32_t *d_samples, uint64_t num_samples,
+                                 cuking_roh_sample *d_out, cuking_ibd_segment *d_segments,
+                                 uint64_t max_segments, uint64_t *num_segments, void *stream) {
+  if (num_segments != nullptr) *num_segments = 0;
+  // (the arguments first: a refused call touches no device)
+  if (ctx == nullptr) return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "null context");
+  const cuking_status st = cuking_check_roh_args(d_bits, words_per_sample, num_sites, min_sites,
+                                                 bridge_sites, num_samples, d_out, d_segments,
+                                                 max_segments, num_segments);
+  if (st != CUKING_OK) return st;
+  if (num_samples == 0) return CUKING_OK;
+  return ibd_scan_device(
+      ctx, num_sites, d_group, d_pos, max_segments, num_segments, stream,
+      [&](const uint64_t *d_group_bits, unsigned long long *d_count, hipStream_t s) {
+        return launch_roh_samples(d_bits, num_stored, words_per_sample, num_sites, d_group_bits,
+                                  d_pos, min_sites, min_length, bridge_sites, d_samples,
+                                  num_samples, d_out, d_segments, max_segments, d_count, s);
+      });
 }
 
 cuking_status cuking_ibd_pairs(cuking_ctx *ctx, const uint64_t *d_bits, uint32_t num_stored,

@@ -704,6 +704,16 @@ hipError_t launch_ibd_pairs(const uint64_t *d_bits, uint32_t num_stored,
                             cuking_ibd_pair *d_out, uint32_t *d_bridged,
                             cuking_ibd_segment *d_segments, uint64_t max_segments,
                             unsigned long long *d_count, hipStream_t stream);
+// Runs of homozygosity (king_ibd.hip; arguments already checked): one row per entry of d_samples
+// (null: samples 0 .. num_samples - 1), the group bits, the count and the segment list as above.
+hipError_t launch_roh_samples(const uint64_t *d_bits, uint32_t num_stored,
+                              uint32_t words_per_sample, uint32_t num_sites,
+                              const uint64_t *d_group_bits, const uint32_t *d_pos,
+                              uint32_t min_sites, uint32_t min_length, uint32_t bridge_sites,
+                              const uint32_t *d_samples, uint64_t num_samples,
+                              cuking_roh_sample *d_out, cuking_ibd_segment *d_segments,
+                              uint64_t max_segments, unsigned long long *d_count,
+                              hipStream_t stream);
 
 // Cohort models of the synthetic generator (synth.hip holds the specification).  d_tables:
 // synth_table_bytes() of scratch the launch fills and reads (per-site and per-sample

@@ -1159,6 +1159,107 @@ cuking_status ibd_pairs_host(const uint64_t *bits, uint32_t num_stored, uint32_t
 
 }  // namespace
 
+// ---- runs of homozygosity ----------------------------------------------------------------------
+cuking_status cuking_check_roh_args(const void *bits, uint32_t words_per_sample,
+                                    uint32_t num_sites, uint32_t min_sites, uint32_t bridge_sites,
+                                    uint64_t num_samples, const void *out, const void *segments,
+                                    uint64_t max_segments, const void *num_segments) {
+  // The checks of the pair calls, in their order and with their messages.  The list of samples
+  // may be null and has no stride: `out` stands in for it (a null `out` is refused first).
+  const cuking_status st =
+      cuking_check_ibd_args(bits, words_per_sample, num_sites, min_sites, out, num_samples,
+                            2 * sizeof(uint32_t), out, segments, max_segments, num_segments);
+  return st != CUKING_OK ? st : cuking_check_ibd_bridge(bridge_sites);
+}
+
+extern "C" {
+
+// The words of one sample, one at a time, with the functions of king_ibd.h: what
+// ibd_pairs_host does for a pair, with roh_break as the break mask and one kind.
+cuking_status cuking_roh_samples_host(const uint64_t *bits, uint32_t num_stored,
+                                      uint32_t words_per_sample, uint32_t num_sites,
+                                      const int32_t *group, const uint32_t *pos,
+                                      uint32_t min_sites, uint32_t min_length,
+                                      uint32_t bridge_sites, const uint32_t *samples,
+                                      uint64_t num_samples, cuking_roh_sample *out,
+                                      cuking_ibd_segment *segments, uint64_t max_segments,
+                                      uint64_t *num_segments) {
+  if (num_segments != nullptr) *num_segments = 0;
+  cuking_status st = cuking_check_roh_args(bits, words_per_sample, num_sites, min_sites,
+                                           bridge_sites, num_samples, out, segments,
+                                           max_segments, num_segments);
+  if (st != CUKING_OK) return st;
+  if (num_samples == 0) return CUKING_OK;
+  st = cuking_check_ibd_positions(group, pos, num_sites);
+  if (st != CUKING_OK) return st;
+  const std::vector<uint64_t> group_bits = ibd_group_bits(group, num_sites);
+  const uint32_t plane_words = words_per_sample / 2;
+  uint64_t count = 0;
+  for (uint64_t r = 0; r < num_samples; ++r) {
+    const uint64_t sample = samples != nullptr ? samples[r] : r;
+    IbdKindSums sums;
+    if (sample < num_stored) {
+      // THE segment test of a chain [a, b] with `links` bridged breaks
+      auto test = [&](uint32_t a, uint32_t b, uint32_t links) {
+        const uint32_t pos_a = pos != nullptr ? pos[a] : a, pos_b = pos != nullptr ? pos[b] : b;
+        if (!ibd_is_segment(a, b, pos_a, pos_b, min_sites, min_length)) return;
+        sums.add(pos_b - pos_a);
+        sums.bridged += links;
+        if (num_segments != nullptr) {
+          if (count < max_segments)
+            segments[count] = cuking_ibd_segment{(uint32_t)r, CUKING_ROH_KIND, a, b};
+          ++count;
+        }
+      };
+      const uint64_t *row = bits + sample * words_per_sample;
+      IbdChain c;
+      uint32_t open = kIbdInherit, edge = 0;
+      for (uint64_t w = 0; w < group_bits.size(); ++w) {
+        const uint64_t valid = ibd_valid_mask(num_sites, w);
+        // (valid != 0 implies w < plane_words)
+        const uint64_t brk = valid != 0 ? roh_break(row[w], row[plane_words + w]) : 0;
+        const uint64_t in = valid & ~brk;
+        const uint64_t starts = ibd_starts(in, edge, group_bits[w]);
+        const uint64_t closes = ibd_closes(in, edge, group_bits[w]);
+        if (edge != 0 && closes != 0) {
+          const uint32_t a = open, b = ibd_close_last(closes, w);
+          if (bridge_sites == 0) {
+            test(a, b, 0);
+          } else {
+            if (c.have && ibd_linked(c.last_first, c.last_end, a, b, bridge_sites,
+                                     group_bits.data())) {
+              ++c.links;
+            } else {
+              if (c.have) test(c.first, c.last_end, c.links);
+              c.have = 1;
+              c.first = a;
+              c.links = 0;
+            }
+            c.last_first = a;
+            c.last_end = b;
+          }
+        }
+        const uint32_t start = ibd_open_start(starts, w);
+        if (start != kIbdInherit) open = start;
+        edge = (uint32_t)(in >> 63);
+      }
+      if (c.have) test(c.first, c.last_end, c.links);
+    }
+    cuking_roh_sample row_out;
+    row_out.length = sums.length;
+    row_out.sample = (uint32_t)sample;
+    row_out.segments = sums.segments;
+    row_out.longest = sums.longest;
+    row_out.bridged = sums.bridged;
+    out[r] = row_out;
+  }
+  if (num_segments == nullptr) return CUKING_OK;
+  *num_segments = count;
+  return cuking_ibd_count_status(count, max_segments);
+}
+
+}  // extern "C"
+
 extern "C" {
 
 cuking_status cuking_ibd_pairs_host(const uint64_t *bits, uint32_t num_stored,

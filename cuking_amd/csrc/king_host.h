@@ -84,5 +84,11 @@ cuking_status cuking_check_ibd_positions(const int32_t *group, const uint32_t *p
 cuking_status cuking_ibd_count_status(uint64_t count, uint64_t max_segments);
 // The one refusal the bridged calls add: 0 < bridge_sites < 64.
 cuking_status cuking_check_ibd_bridge(uint32_t bridge_sites);
+// Argument checks of cuking_roh_samples_host / cuking_roh_samples: the two above, for a list of
+// samples that may be null and has no stride.
+cuking_status cuking_check_roh_args(const void *bits, uint32_t words_per_sample,
+                                    uint32_t num_sites, uint32_t min_sites, uint32_t bridge_sites,
+                                    uint64_t num_samples, const void *out, const void *segments,
+                                    uint64_t max_segments, const void *num_segments);
 
 #endif  // CUKING_AMD_KING_HOST_H_

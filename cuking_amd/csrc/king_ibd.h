@@ -8,7 +8,8 @@
 // num_sites, where the last run closes; it lies beyond the plane when num_sites is a multiple
 // of 64, and a word at or beyond the plane is never loaded (its `in` mask is zero anyway).
 //
-// Per word and kind, with `brk` the break mask (ibd_opp for kind 1, ibd_diff for kind 2):
+// Per word and kind, with `brk` the break mask (ibd_opp for kind 1, ibd_diff for kind 2, and
+// roh_break for the runs of homozygosity of one sample, which are scanned the same way):
 //     in     = ibd_valid_mask(num_sites, w) & ~brk     the sites that are inside some run
 //     group  bit s set iff site s is the first of its group; bit 0 of word 0 and the bit at
 //            num_sites are set, the bits beyond it clear (ibd_group_word)
@@ -85,6 +86,10 @@ CUKING_HD inline uint64_t ibd_diff(uint64_t het_i, uint64_t hom_i, uint64_t het_
                                    uint64_t hom_j) {
   return ((het_i ^ het_j) | (hom_i ^ hom_j)) & ~ibd_missing(het_i, hom_i, het_j, hom_j);
 }
+
+// Runs of homozygosity (the header's "Runs of homozygosity"): the break mask of ONE sample, a
+// heterozygous call (code 1).  Missing (both bits) is no break.
+CUKING_HD inline uint64_t roh_break(uint64_t het, uint64_t hom) { return het & ~hom; }
 
 CUKING_HD inline uint64_t ibd_starts(uint64_t in, uint64_t prev, uint64_t group) {
   return in & (~(in << 1 | prev) | group);

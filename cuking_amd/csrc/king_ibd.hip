@@ -1,7 +1,8 @@
 // IBD segments for listed pairs on the device (include/cuking_amd.h "IBD segments for listed
 // pairs" holds the contract, king_ibd.h the word masks and the segment test as code,
 // king_host.cc the host twin that walks the same words one by one; DESIGN.md 4.3h the reasons
-// for the shape): ibd_group_bits_kernel and ibd_pairs_kernel.
+// for the shape): ibd_group_bits_kernel and ibd_pairs_kernel; and, at the end, the same scan of
+// one sample against itself, roh_samples_kernel ("Runs of homozygosity").
 //
 // One WAVEFRONT owns one pair.  Per step of kIbdStepWords = 64 words (4096 sites) lane l loads
 // word 64 step + l of the four planes of the pair (coalesced: 512 bytes per plane and step) and
@@ -288,6 +289,62 @@ __global__ __launch_bounds__(kIbdThreads) void ibd_pairs_kernel(const IbdArgsOf<
   }
 }
 
+// ---- runs of homozygosity (the header's "Runs of homozygosity") ----------------------------------
+// The scan above of a sample with itself: ONE kind, whose break mask is roh_break of the sample's
+// two planes, and one wavefront per listed sample.  The arguments are those of the pair kernel
+// with `pairs` the list of samples (uint32 each, or nullptr: row r is sample r), num_pairs its
+// length and `out` / `bridged` unused: the 24-byte row carries the bridged count itself.
+static_assert(sizeof(cuking_roh_sample) == 24, "six dwords per output row");
+template <bool kBridge>
+struct RohArgs : IbdArgsOf<kBridge> {
+  cuking_roh_sample *rows;
+};
+
+template <bool kBridge>
+__global__ __launch_bounds__(kIbdThreads) void roh_samples_kernel(const RohArgs<kBridge> a) {
+  const uint32_t lane = threadIdx.x & 63;
+  const uint64_t r = a.pair_base + (uint64_t)blockIdx.x * kIbdWaves + threadIdx.x / 64;
+  if (r >= a.num_pairs) return;  // (the whole wavefront: there is no barrier below)
+
+  const uint64_t sample =
+      a.pairs != nullptr ? reinterpret_cast<const uint32_t *>(a.pairs)[r] : r;
+  const bool active = sample < a.num_stored;
+  const uint32_t plane_words = a.words_per_sample / 2;
+  const uint64_t *bits = a.bits + (active ? sample : 0) * a.words_per_sample;
+
+  IbdKind k;
+  const uint64_t words = ibd_scan_words(a.num_sites);
+  if (active) {
+    for (uint64_t w0 = 0; w0 < words; w0 += kIbdStepWords) {
+      const uint64_t w = w0 + lane;
+      const uint64_t valid = ibd_valid_mask(a.num_sites, w);
+      // (valid != 0 implies w < plane_words, as in ibd_pairs_kernel)
+      uint64_t het = 0, hom = 0;
+      if (valid != 0) {
+        het = bits[w];
+        hom = bits[plane_words + w];
+      }
+      const uint64_t group = w < words ? a.group_bits[w] : 0;
+      ibd_kind_step<kBridge>(a, CUKING_ROH_KIND, r, w, lane, valid & ~roh_break(het, hom), group,
+                             k);
+    }
+    if constexpr (kBridge) {
+      // (every run is closed by now: the chain that is left is whole)
+      if (lane == 0 && k.chain.have)
+        ibd_test(a, CUKING_ROH_KIND, r, k.chain.first, k.chain.last_end, k.chain.links, k.sums);
+    }
+  }
+
+  cuking_roh_sample row;
+  row.length = ibd_wave_sum64(k.sums.length);
+  row.sample = (uint32_t)sample;
+  row.segments = ibd_wave_sum(k.sums.segments);
+  row.longest = ibd_wave_max(k.sums.longest);
+  row.bridged = 0;
+  if constexpr (kBridge) row.bridged = ibd_wave_sum(k.sums.bridged);
+  if (lane == 0) a.rows[r] = row;
+}
+
 }  // namespace
 
 hipError_t launch_ibd_group_bits(const int32_t *d_group, uint32_t num_sites,
@@ -343,6 +400,55 @@ hipError_t launch_ibd_pairs(const uint64_t *d_bits, uint32_t num_stored,
     a.pair_base = done * kIbdWaves;
     ibd_pairs_kernel<true><<<dim3(n), dim3(kIbdThreads), 0, stream>>>(a);
   });
+}
+
+namespace {
+
+template <bool kBridge>
+hipError_t launch_roh(const IbdBridgeArgs &from, cuking_roh_sample *d_out, hipStream_t stream) {
+  RohArgs<kBridge> a;
+  static_cast<IbdArgsOf<kBridge> &>(a) = from;  // (the strict form drops the bridge fields)
+  a.rows = d_out;
+  const uint64_t blocks = (a.num_pairs + kIbdWaves - 1) / kIbdWaves;
+  return launch_in_chunks(blocks, kIbdThreads, [&](uint64_t done, uint32_t n) {
+    a.pair_base = done * kIbdWaves;
+    roh_samples_kernel<kBridge><<<dim3(n), dim3(kIbdThreads), 0, stream>>>(a);
+  });
+}
+
+}  // namespace
+
+hipError_t launch_roh_samples(const uint64_t *d_bits, uint32_t num_stored,
+                              uint32_t words_per_sample, uint32_t num_sites,
+                              const uint64_t *d_group_bits, const uint32_t *d_pos,
+                              uint32_t min_sites, uint32_t min_length, uint32_t bridge_sites,
+                              const uint32_t *d_samples, uint64_t num_samples,
+                              cuking_roh_sample *d_out, cuking_ibd_segment *d_segments,
+                              uint64_t max_segments, unsigned long long *d_count,
+                              hipStream_t stream) {
+  if (num_samples == 0) return hipSuccess;
+  IbdBridgeArgs a;
+  a.bits = d_bits;
+  a.group_bits = d_group_bits;
+  a.pos = d_pos;
+  a.pairs = reinterpret_cast<const unsigned char *>(d_samples);
+  a.out = nullptr;
+  a.segments = d_segments;
+  a.count = d_count;
+  a.max_segments = max_segments;
+  a.num_pairs = num_samples;
+  a.pair_base = 0;
+  a.pair_stride = sizeof(uint32_t);
+  a.num_stored = num_stored;
+  a.words_per_sample = words_per_sample;
+  a.num_sites = num_sites;
+  a.min_sites = min_sites;
+  a.min_length = min_length;
+  a.bridged = nullptr;
+  a.bridge_sites = bridge_sites;
+  // (bridge_sites == 0 links nothing: the strict instantiation)
+  return bridge_sites == 0 ? launch_roh<false>(a, d_out, stream)
+                           : launch_roh<true>(a, d_out, stream);
 }
 
 }  // namespace cuking

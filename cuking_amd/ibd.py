@@ -156,6 +156,24 @@ def _exhausted(count: int):
     return e
 
 
+def _segment_buffer(call, count: int, want: bool, max_segments, found):
+    """The buffer rule of a segment list, shared by every call that has one: ``call(capacity)``
+    makes a buffer of ``capacity`` segments, calls the library and returns ``(buffer, status)``;
+    ``found`` is the ``c_uint64`` the library counts into.  Without ``max_segments`` the buffer
+    is ``_default_segments(count)`` and the call is repeated once with the exact count; with it
+    an overflow raises ``ResourceExhaustedError`` whose ``num_segments`` is the exact count.
+    Returns the buffer of the call that succeeded."""
+    grow = max_segments is None
+    segs, status = call(0 if not want else _default_segments(count) if grow
+                        else _count(max_segments, "max_segments"))
+    if status == _lib.ERR_RESOURCE_EXHAUSTED and grow:
+        segs, status = call(int(found.value))
+    if status == _lib.ERR_RESOURCE_EXHAUSTED:
+        raise _exhausted(int(found.value))
+    check(status)
+    return segs
+
+
 def ibd_segments_raw_host(bits: np.ndarray, words_per_sample: int, num_sites: int, pairs,
                           group=None, pos=None, min_sites: int = 512, min_length: int = 0,
                           segments: bool = False, max_segments=None, num_records=None,
@@ -198,13 +216,7 @@ def ibd_segments_raw_host(bits: np.ndarray, words_per_sample: int, num_sites: in
                 *head, bridge_sites, *pair, bridged.ctypes.data if count else None, *tail)
         return segs, status
 
-    segs, status = call(0 if not want else _default_segments(count) if max_segments is None
-                        else _count(max_segments, "max_segments"))
-    if status == _lib.ERR_RESOURCE_EXHAUSTED and max_segments is None:
-        segs, status = call(int(found.value))
-    if status == _lib.ERR_RESOURCE_EXHAUSTED:
-        raise _exhausted(int(found.value))
-    check(status)
+    segs = _segment_buffer(call, count, want, max_segments, found)
     segs = segs[:found.value].copy() if want else None
     return (out, segs) if bridge_sites == 0 else (out, segs, bridged)
 
@@ -281,7 +293,8 @@ def ibd_segments_raw_device(ctx, bits, words_per_sample: int, num_sites: int, pa
     if stream is not None:
         stream.wait_stream(torch.cuda.current_stream())
 
-    def call(segs, capacity):
+    def call(capacity):
+        segs = torch.empty((max(capacity, 1), 4), dtype=torch.int32, device=dev)
         head = (ctx.handle, bits.data_ptr(), num_stored, words_per_sample, num_sites,
                 None if d_group is None or not num_sites else d_group.data_ptr(),
                 None if d_pos is None or not num_sites else d_pos.data_ptr(), min_sites,
@@ -291,22 +304,11 @@ def ibd_segments_raw_device(ctx, bits, words_per_sample: int, num_sites: int, pa
         tail = (segs.data_ptr() if want and capacity else None, capacity if want else 0,
                 C.byref(found) if want else None, _stream_handle(stream))
         if bridge_sites == 0:
-            return ctx.lib.cuking_ibd_pairs(*head, *pair, *tail)
-        return ctx.lib.cuking_ibd_pairs_bridged(*head, bridge_sites, *pair,
-                                                bridged.data_ptr() if count else None, *tail)
+            return segs, ctx.lib.cuking_ibd_pairs(*head, *pair, *tail)
+        return segs, ctx.lib.cuking_ibd_pairs_bridged(
+            *head, bridge_sites, *pair, bridged.data_ptr() if count else None, *tail)
 
-    grow = max_segments is None
-    capacity = 0 if not want else _default_segments(count) if grow \
-        else _count(max_segments, "max_segments")
-    segs = torch.empty((max(capacity, 1), 4), dtype=torch.int32, device=dev)
-    status = call(segs, capacity)
-    if status == _lib.ERR_RESOURCE_EXHAUSTED and grow:
-        capacity = int(found.value)
-        segs = torch.empty((capacity, 4), dtype=torch.int32, device=dev)
-        status = call(segs, capacity)
-    if status == _lib.ERR_RESOURCE_EXHAUSTED:
-        raise _exhausted(int(found.value))
-    check(status)
+    segs = _segment_buffer(call, count, want, max_segments, found)
     if stream is not None:  # (converted copies are freed on return)
         for t in (owner, d_group, d_pos, segs):
             if t is not None:

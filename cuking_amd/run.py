@@ -190,6 +190,27 @@ def parse_args(argv=None):
          help="--ibd-segments-uri also writes the segments themselves: segment_pair (the "
               "record's number), segment_kind, segment_first_site, segment_last_site (site "
               "numbers among the input's sites), sorted")
+    flag("roh-uri", default="",
+         help="also scan every sample of this run for runs of homozygosity -- the runs of at "
+              "least --roh-min-sites sites without a heterozygous call, no allele frequencies "
+              "and no principal components involved (cuking_amd/roh.py) -- and write them to "
+              "this .npz: sample, segments, length, longest, bridged, froh (length over "
+              "total_length: the inbreeding estimate F_ROH), total_length (with samples, "
+              "min_sites, min_length, bridge_sites).  The scan runs on the bitset the records "
+              "were computed on, after site QC and LD pruning, and takes chromosomes and "
+              "base-pair positions from the .bim under --bed-uri exactly as "
+              "--ibd-segments-uri does.  One process and --split-factor 1 only")
+    flag("roh-min-sites", type=int, default=None,
+         help="the fewest sites of a run of --roh-uri (default 512; at least 64)")
+    flag("roh-min-length", type=int, default=None,
+         help="the least length of a run of --roh-uri, in the .bim's positions (default 0)")
+    flag("roh-bridge-sites", type=int, default=None,
+         help="--roh-uri forgives isolated heterozygous calls (genotyping errors): two runs of "
+              "at least this many sites on either side of one het of a chromosome count as one "
+              "run (0, or at least 64; default 0: no bridging)")
+    flag("roh-segment-list", action="store_true",
+         help="--roh-uri also writes the runs themselves: seg_sample, seg_first_site, "
+              "seg_last_site (site numbers among the input's sites), sorted")
     flag("pcrelate-min-kinship", type=float, default=None,
          help="the threshold of --pcrelate-records-uri: pairs with a kinship strictly above it "
               "(default 0.0442, the third-degree cut-off)")
@@ -362,6 +383,28 @@ def validate(args):  # cuking.cu:437-462
                              "lie inside one 64-site word, which the scan does not enumerate")
         if args.ibd_min_length is not None and not 0 <= args.ibd_min_length < 1 << 32:
             raise UsageError("--ibd_min_length must be in [0, 2^32)")
+    if (args.roh_min_sites is not None or args.roh_min_length is not None or
+            args.roh_bridge_sites is not None or args.roh_segment_list) and not args.roh_uri:
+        raise UsageError("--roh_min_sites, --roh_min_length, --roh_bridge_sites and "
+                         "--roh_segment_list need --roh_uri")
+    if args.roh_uri:
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            raise UsageError("--roh_uri needs one process (one GPU): the samples are not "
+                             "scanned across ranks yet")
+        if args.split_factor != 1:
+            raise UsageError("--roh_uri needs --split_factor 1: it scans the samples of the "
+                             "whole cohort's bitset")
+        if args.roh_min_sites is not None and not IBD_MIN_SITES <= args.roh_min_sites < 1 << 32:
+            raise UsageError(f"--roh_min_sites must be at least {IBD_MIN_SITES} (and below "
+                             "2^32): shorter runs lie inside one 64-site word, which the scan "
+                             "does not enumerate")
+        if args.roh_min_length is not None and not 0 <= args.roh_min_length < 1 << 32:
+            raise UsageError("--roh_min_length must be in [0, 2^32)")
+        b = args.roh_bridge_sites
+        if b is not None and b != 0 and not IBD_MIN_SITES <= b < 1 << 32:
+            raise UsageError(f"--roh_bridge_sites must be 0 or at least {IBD_MIN_SITES} (and "
+                             "below 2^32): shorter runs lie inside one 64-site word, which the "
+                             "scan does not enumerate")
     if args.pcrelate_min_kinship is not None and not args.pcrelate_records_uri:
         raise UsageError("--pcrelate_min_kinship needs --pcrelate_records_uri")
     if args.pcrelate_records_uri:
@@ -702,6 +745,30 @@ def write_ibd_segments(path: Path, ctx, bits, wps: int, num_sites: int, recs, gr
                  min_length=np.int64(min_length), **extra)
 
 
+def write_roh(path: Path, ctx, bits, wps: int, num_sites: int, group, pos, site_index,
+              min_sites: int, min_length: int, bridge_sites: int, with_list: bool,
+              sample_ids) -> None:
+    """Every sample of this run scanned for runs of homozygosity as an .npz: `sample`,
+    `segments`, `length`, `longest`, `bridged`, `froh` (one entry per sample, in the cohort's
+    order), `total_length`, `samples`, `min_sites`, `min_length`, `bridge_sites`; with
+    `with_list` the sorted runs as `seg_sample`, `seg_first_site`, `seg_last_site` (through
+    `site_index`: numbers among the input's sites)."""
+    got = ctx.roh_segments(bits, wps, num_sites, group=group, pos=pos, min_sites=min_sites,
+                           min_length=min_length, bridge_sites=bridge_sites, segments=with_list)
+    extra = {}
+    if with_list:
+        segs = got.sorted()
+        extra = dict(seg_sample=segs["pair"], seg_first_site=site_index[segs["first_site"]],
+                     seg_last_site=site_index[segs["last_site"]])
+    path.parent.mkdir(parents=True, exist_ok=True)
+    with open(path, "wb") as f:   # (np.savez would append .npz to another suffix)
+        np.savez(f, sample=got.sample, segments=got.segments, length=got.length,
+                 longest=got.longest, bridged=got.bridged, froh=got.froh(),
+                 total_length=np.int64(got.total_length),
+                 samples=np.array(list(sample_ids), dtype=str), min_sites=np.int64(min_sites),
+                 min_length=np.int64(min_length), bridge_sites=np.int64(bridge_sites), **extra)
+
+
 def site_qc(ctx, args, bits, wps: int, num_sites: int, sample_ids, keep_path, qc_path):
     """Site QC of the whole cohort's bitset: counts on the GPU, the rule on the host, the
     report if one is asked for, and -- with a flag that selects sites -- the compacted bitset.
@@ -783,6 +850,7 @@ def main(argv=None) -> int:
         records_path = resolve_uri(args.pcrelate_records_uri) if args.pcrelate_records_uri \
             else None
         ibd_path = resolve_uri(args.ibd_segments_uri) if args.ibd_segments_uri else None
+        roh_path = resolve_uri(args.roh_uri) if args.roh_uri else None
         synthetic = None
         if args.synthetic:
             parts = [int(x) for x in args.synthetic.split(",")]
@@ -960,12 +1028,17 @@ def main(argv=None) -> int:
                                            else args.pcrelate_min_maf,
                                            0.0442 if args.pcrelate_min_kinship is None
                                            else args.pcrelate_min_kinship, sample_ids)
+            ibd_group = ibd_pos = None
+            if (ibd_path is not None or roh_path is not None) and bed_prefix is not None:
+                from cuking_amd import plink
+                ibd_group = plink.read_bim_chromosomes(bed_prefix)[site_index]
+                ibd_pos = plink.read_bim_positions(bed_prefix)[site_index]
+            if roh_path is not None:
+                write_roh(roh_path, ctx, bits[:stored], wps, num_sites, ibd_group, ibd_pos,
+                          site_index, 512 if args.roh_min_sites is None else args.roh_min_sites,
+                          0 if args.roh_min_length is None else args.roh_min_length,
+                          args.roh_bridge_sites or 0, args.roh_segment_list, sample_ids)
             if ibd_path is not None:
-                ibd_group = ibd_pos = None
-                if bed_prefix is not None:
-                    from cuking_amd import plink
-                    ibd_group = plink.read_bim_chromosomes(bed_prefix)[site_index]
-                    ibd_pos = plink.read_bim_positions(bed_prefix)[site_index]
                 write_ibd_segments(ibd_path, ctx, bits[:stored], wps, num_sites, recs, ibd_group,
                                    ibd_pos, site_index,
                                    512 if args.ibd_min_sites is None else args.ibd_min_sites,

@@ -1246,6 +1246,65 @@ cuking_status cuking_ibd_pairs_bridged(cuking_ctx *ctx, const uint64_t *d_bits,
                                        uint64_t max_segments, uint64_t *num_segments,
                                        void *stream);
 
+/* Runs of homozygosity: the long stretches of the genome in which ONE sample carries no
+ * heterozygous call -- the IBD of a sample's own two haplotypes (king --roh, plink --homozyg,
+ * bcftools roh).  Their summed length over the genome's length is F_ROH, the inbreeding estimate
+ * that needs no allele frequency and no principal component; a whole-chromosome run flags
+ * uniparental disomy or a large deletion.  It is "IBD segments for listed pairs" with another
+ * break mask and one kind, decided on the same integers by the same code (csrc/king_ibd.h).
+ *
+ * The codes are those of the bitset:
+ *     het bit 0, hom bit 0   hom-ref
+ *     het bit 1, hom bit 0   het
+ *     het bit 0, hom bit 1   hom-var
+ *     het bit 1, hom bit 1   missing
+ *     break   for one sample and word, brk = het & ~hom (roh_break): a heterozygous call
+ *     in      ibd_valid_mask(num_sites, w) & ~brk, the sites inside some run.  A missing
+ *             genotype neither breaks nor ends a run; bits at or beyond num_sites never matter
+ *             (all-ones padding gives the same bytes)
+ * Everything else is "IBD segments" with this `in`: runs per group (ibd_starts / ibd_closes with
+ * the group-start mask), THE segment test ibd_is_segment(a, b, pos[a], pos[b], min_sites,
+ * min_length) with the length pos[b] - pos[a], and with bridge_sites != 0 the links of "IBD
+ * segments with bridged breaks" (ibd_linked) and maximal chains: one isolated het between two
+ * runs of at least bridge_sites sites of one group is forgiven (plink --homozyg-window-het 1).
+ * min_sites >= CUKING_IBD_MIN_SITES; bridge_sites is 0 or >= 64; group or pos may be null; pos
+ * must not decrease inside a group.  The refusals and their messages are those of
+ * cuking_ibd_pairs_bridged (a null list of samples is legal, and there is no stride).
+ *
+ *     samples   uint32 [num_samples] or null: the samples 0 .. num_samples - 1.  Repeats and any
+ *               order are allowed
+ *     out       one cuking_roh_sample of 24 bytes per listed sample, in list order, plain stores.
+ *               `bridged` counts the bridged het sites inside the counted segments and is 0 at
+ *               bridge_sites == 0.  A listed index >= num_stored loads nothing and gets zeros
+ *               with `sample` echoed.  A row depends on its own sample only
+ * Segment list (optional): cuking_ibd_segment rows with pair = the row index, kind =
+ * CUKING_ROH_KIND and first_site / last_site the chain's ends, in no specified order.  The buffer,
+ * the count, RESOURCE_EXHAUSTED and the waits are exactly those of cuking_ibd_pairs; without a
+ * list (num_segments null) and without pos the call is asynchronous on its stream.
+ * Out of scope: a maximum gap between neighbouring sites (pass chromosome arms as `group`);
+ * PLINK's sliding-window and density rules; more than one het per bridge; allele-frequency or
+ * LOD-weighted runs; several ranks. */
+#define CUKING_ROH_KIND 0
+typedef struct cuking_roh_sample {
+  uint64_t length;                              /* sum of the segments' lengths */
+  uint32_t sample, segments, longest, bridged;  /* the listed index; count; largest length */
+} cuking_roh_sample;                            /* 24 bytes */
+cuking_status cuking_roh_samples_host(const uint64_t *bits, uint32_t num_stored,
+                                      uint32_t words_per_sample, uint32_t num_sites,
+                                      const int32_t *group, const uint32_t *pos,
+                                      uint32_t min_sites, uint32_t min_length,
+                                      uint32_t bridge_sites, const uint32_t *samples,
+                                      uint64_t num_samples, cuking_roh_sample *out,
+                                      cuking_ibd_segment *segments, uint64_t max_segments,
+                                      uint64_t *num_segments);
+cuking_status cuking_roh_samples(cuking_ctx *ctx, const uint64_t *d_bits, uint32_t num_stored,
+                                 uint32_t words_per_sample, uint32_t num_sites,
+                                 const int32_t *d_group, const uint32_t *d_pos,
+                                 uint32_t min_sites, uint32_t min_length, uint32_t bridge_sites,
+                                 const uint32_t *d_samples, uint64_t num_samples,
+                                 cuking_roh_sample *d_out, cuking_ibd_segment *d_segments,
+                                 uint64_t max_segments, uint64_t *num_segments, void *stream);
+
 /* cuking.cu:761-765 on host memory: sort by (sample_i, sample_j, kin). */
 void cuking_sort_results(cuking_result *results, size_t num_results);
 
