@@ -137,7 +137,9 @@ struct cuking_ctx {
     // and has read it back when it returns; cuking_ibd_pairs counts its segments there too),
     // and the group-start bitmask of cuking_ibd_pairs (king_ibd.h; each call rebuilds it on
     // the stream).
-    DeviceBuf prune, sites, record_count, ibd_groups;
+    // ... and the site order's scratch (king_sort.hip: counts, the sort, the permuted bitset;
+    // each conversion with the order on rebuilds it on the stream).
+    DeviceBuf prune, sites, record_count, ibd_groups, site_order;
   };
   std::vector<StreamScratch> scratch;
   // The running totals of filter scratch that has been freed since (a larger block took
@@ -166,6 +168,20 @@ struct cuking_ctx {
   // behind a sub-rectangle are not the ones its bounds name).
   int filter_sort = 1;
   bool filter_lazy_codes = true;
+  // The kernel layout's SITES in the order of the X they contribute to unrelated pairs
+  // (king_sort.hip "Site order"): -1 (default) for whole-block conversions of calls the filter
+  // runs for, on blocks of at least kSiteOrderMinTiles tiles with check points, whose curve
+  // forecasts a check at least kSiteOrderMinGain 64ths earlier than stored order's at the
+  // call's threshold (prepare() reads the curve back: one host wait per such conversion); 0
+  // never; 1 for every such conversion whatever the block's size and the forecast.  Bitsets
+  // too wide for the gather (site_order_scratch) keep stored order; so do the ranges of a
+  // staged pass.
+  int filter_site_order = -1;
+  uint32_t filter_site_order_min_tiles = (uint32_t)kSiteOrderMinTiles;  // (test hook)
+  // What the last conversion that built a curve read from it (read-only keys
+  // "site_order_share", "site_order_stored_share", "site_order_sigma_e6", "site_order_on").
+  SiteOrderForecast order_forecast = {0, 0, false};
+  float order_sigma = 0.f;
   void *sort_temp = nullptr;
   size_t sort_temp_bytes = 0;
 
@@ -191,6 +207,16 @@ struct cuking_ctx {
     // converted for a dense kinship matrix: never sorted, whatever "filter_sort" says (a
     // call of the other kind does not take the layout over: it converts again)
     bool dense_order = false;
+    // the T2 layout and the per-sample counts hold the sites in the site order, and the
+    // workspace its curve (TiledArgs::site_curve); order_wanted: the conversion was one the
+    // option let build a curve (site_order: ... and the curve said yes, or the option was 1)
+    bool site_order = false, order_wanted = false;
+    // the threshold of the call the order was decided for, and -- after an automatic "no" --
+    // the conversions of this block at that threshold that still trust it without building
+    // the curve again (kSiteOrderNoTrust: the bitset behind the pointer may have changed, but
+    // a stale "no" only costs what stored order costs)
+    float order_thr = 0.f;
+    uint32_t order_no_left = 0;
     // per 64 plane samples: 0 = not converted, 1 = converted (kernels that
     // read it, if any, all precede the tail of `ordered_on`), 2 = converted
     // and read by kernels enqueued since
@@ -357,7 +383,8 @@ void free_split_slab(cuking_ctx::StreamScratch &e) {
 void free_stream_scratch(cuking_ctx *ctx, cuking_ctx::StreamScratch &e, bool retire_totals) {
   free_filter_scratch(ctx, e, retire_totals);
   free_split_slab(e);
-  for (cuking_ctx::DeviceBuf *b : {&e.prune, &e.sites, &e.record_count, &e.ibd_groups}) {
+  for (cuking_ctx::DeviceBuf *b :
+       {&e.prune, &e.sites, &e.record_count, &e.ibd_groups, &e.site_order}) {
     if (b->p != nullptr) (void)hipFree(b->p);
     *b = {};
   }
@@ -581,6 +608,8 @@ cuking_status launch_args(cuking_ctx *ctx, hipStream_t stream, const cuking_subm
   a.fsplit_slabs = ctx->split_wgs != 0 ? reinterpret_cast<float4 *>(base + l.slabs) : nullptr;
   a.rotate_min_steps = ctx->filter_rotate_min_steps;
   a.check_steps = plane_check_steps(ctx->planes, geo);
+  if (ctx->prepared.site_order) a.site_curve = plane_site_curve(ctx->planes, geo);
+  a.site_rotate = ctx->filter_site_order == 2;
   return CUKING_OK;
 }
 
@@ -738,7 +767,8 @@ cuking_status prepare(cuking_ctx *ctx, const cuking_submatrix &sm,
                       uint32_t words_per_sample, const uint64_t *d_bit_sets,
                       hipStream_t stream, PlaneGeometry *geo_out,
                       TileSpace *tiles_out, bool need_codes, bool dense_order,
-                      uint32_t s_tile_begin = 0, uint32_t s_tile_end = 0xFFFFFFFFu) {
+                      uint32_t s_tile_begin = 0, uint32_t s_tile_end = 0xFFFFFFFFu,
+                      bool filter_call = false, float kin_threshold = 0.f) {
   const int variant = effective_variant(ctx, words_per_sample);
   const TiledVariant v = plan_variant(ctx, words_per_sample);
   const PlaneGeometry geo = make_geometry(sm, words_per_sample, v);
@@ -757,8 +787,30 @@ cuking_status prepare(cuking_ctx *ctx, const cuking_submatrix &sm,
   const bool new_prefix = !same_tile_space(ctx->prefix_for, tiles);
   // (a layout converted for a dense kinship matrix is unsorted: a call of the other kind
   //  treats it as another block's, and the other way round)
+  // Site order ("filter_site_order"): whole-block conversions for a call the filter runs for
+  // (`filter_call`).  Automatic: blocks of at least kSiteOrderMinTiles tiles whose bitset is
+  // long enough for check points get their curve built (`order_wanted`); whether the layout
+  // then takes the order is decided from the curve, below.
+  const uint32_t num_stored = geo.diag ? geo.num_rows : geo.num_rows + geo.num_cols;
+  SiteOrderScratch order_layout = {};
+  bool order_wanted = false;
+  if (filter_call && !dense_order && v.layout == kLayoutNibbleStats && ctx->filter_site_order != 0 &&
+      s_tile_begin == 0 && t_end == all_tiles) {
+    order_layout = site_order_scratch(num_stored, words_per_sample);
+    order_wanted = order_layout.bytes != 0 &&
+                 (ctx->filter_site_order >= 1 ||
+                  (total_tiles(tiles) >= ctx->filter_site_order_min_tiles &&
+                   geo.k_words / 8 >= filter_check_min_steps()));
+  }
+  // (... and a layout converted under another answer to that is another block's as well.  A
+  //  layout that is reused keeps the decision of the call that converted it, whatever
+  //  threshold this one has: its share comes from the curve and this call's threshold.)
   const bool same = same_block(pr, sm, words_per_sample, variant, v.tile, d_bit_sets) &&
-                    pr.dense_order == dense_order;
+                    pr.dense_order == dense_order && pr.order_wanted == order_wanted &&
+                    // (the share of an ordered layout comes from its curve at the call's
+                    //  threshold and may be "no check at all" at another one, where stored
+                    //  order would have had one: such a call decides and converts afresh)
+                    !(pr.site_order && pr.order_thr != kin_threshold);
   if (ctx->reuse_prepared && same && !new_prefix) {
     // The host has promised that the bitset behind this pointer is unchanged
     // since it was converted (cuking_invalidate otherwise): nothing to do when
@@ -789,6 +841,9 @@ cuking_status prepare(cuking_ctx *ctx, const cuking_submatrix &sm,
     pr.tiles.assign(all_tiles, 0);
     pr.codes = true;
     pr.dense_order = dense_order;
+    pr.order_wanted = order_wanted;
+    pr.site_order = false;
+    pr.order_no_left = 0;
   }
   for (uint32_t t = s_tile_begin; t < t_end; ++t)
     must_wait = must_wait || pr.tiles[t] == 2 || (pr.tiles[t] == 1 && other_stream);
@@ -819,14 +874,63 @@ cuking_status prepare(cuking_ctx *ctx, const cuking_submatrix &sm,
     // (whatever is converted now, the codes of the block as a whole are not "there" unless
     //  this conversion or convert_codes_now() below says so)
     HIP_TRY(hipMemsetAsync(plane_flags(ctx->planes, geo), 0, sizeof(uint32_t), stream));
-    HIP_TRY(launch_sample_stats(d_bit_sets, words_per_sample, geo, ctx->planes, sb, se, stream));
+    // Site order: counts, weights, sort, and the bitset with every sample's sites in that
+    // order in this stream's scratch -- what the statistics and T2 are built from, so that
+    // both see the SAME order (one extra write and read of the bitset, against a gather in
+    // each of the two kernels).  The codes stay in stored order, like everything that recounts.
+    // The scratch (a second copy of the bitset among it) is allocated here, on first use and
+    // again for a larger block -- cuking_ctx_reserve does not know it --, and the host waits
+    // for the curve before it decides: the order takes the layout when the option says 1, or
+    // when the curve forecasts the check at least kSiteOrderMinGain 64ths earlier than stored
+    // order has it and the launch-wide verdict does not send every tile away first.  A "no"
+    // has cost the counts, the sort and the wait, not the gather, and keeps rotated tiles.
+    const uint64_t *layout_bits = d_bit_sets;
+    bool site_order = false;
+    // (an automatic "no" is remembered for the block: conversion inside every pass of a
+    //  cohort the order cannot help must not pay the counts, the sort and the wait each time)
+    const bool trust_no = ctx->filter_site_order == -1 && pr.order_no_left != 0 &&
+                          pr.order_thr == kin_threshold;
+    if (trust_no) --pr.order_no_left;
+    if (order_wanted && !trust_no) {
+      cuking_ctx::StreamScratch *e = stream_entry(ctx, stream);
+      st = grow_on_stream(ctx, stream, &e->site_order, order_layout.bytes);
+      if (st != CUKING_OK) return st;
+      SiteCurve *d_curve = plane_site_curve(ctx->planes, geo);
+      HIP_TRY(launch_site_order(d_bit_sets, num_stored, words_per_sample, geo, e->site_order.p,
+                                order_layout, d_curve, stream));
+      SiteCurve curve;
+      HIP_TRY(hipMemcpyAsync(&curve, d_curve, sizeof curve, hipMemcpyDeviceToHost, stream));
+      ++ctx->host_syncs;
+      HIP_TRY(hipStreamSynchronize(stream));
+      const SiteOrderForecast f = site_order_forecast(curve, num_stored, geo.k_words, kin_threshold);
+      ctx->order_forecast = f;
+      ctx->order_sigma = curve.sigma;
+      site_order = ctx->filter_site_order >= 1 ||
+                   (!f.verdict_first && f.order64 != 0 &&
+                    (f.stored64 == 0 || f.order64 + kSiteOrderMinGain <= f.stored64));
+      pr.order_thr = kin_threshold;
+      pr.order_no_left = site_order ? 0u : kSiteOrderNoTrust;
+    }
+    pr.site_order = site_order;
+    if (site_order) {
+      cuking_ctx::StreamScratch *e = stream_entry(ctx, stream);
+      HIP_TRY(launch_site_permute(d_bit_sets, num_stored, words_per_sample, e->site_order.p,
+                                  order_layout, stream));
+      layout_bits = reinterpret_cast<const uint64_t *>(static_cast<const uint8_t *>(e->site_order.p) +
+                                                       order_layout.permuted);
+    }
+    HIP_TRY(launch_sample_stats(layout_bits, words_per_sample, geo, ctx->planes, sb, se, stream));
     HIP_TRY(launch_sample_order(geo, words_per_sample, ctx->planes, sb, se,
                                 !dense_order &&
                                     (ctx->filter_sort == 2 || (ctx->filter_sort == 1 && whole)),
                                 ctx->sort_temp, ctx->sort_temp_bytes, stream));
-    HIP_TRY(launch_prepare_nibbles(codes, true, d_bit_sets, words_per_sample, geo, ctx->planes,
-                                   plane_perm(ctx->planes, geo), s_tile_begin, t_end, nullptr,
-                                   nullptr, stream));
+    HIP_TRY(launch_prepare_nibbles(codes && !site_order, true, layout_bits, words_per_sample, geo,
+                                   ctx->planes, plane_perm(ctx->planes, geo), s_tile_begin, t_end,
+                                   nullptr, nullptr, stream));
+    if (codes && site_order)
+      HIP_TRY(launch_prepare_nibbles(true, false, d_bit_sets, words_per_sample, geo, ctx->planes,
+                                     plane_perm(ctx->planes, geo), s_tile_begin, t_end, nullptr,
+                                     nullptr, stream));
     if (!codes) {
       pr.codes = false;
     } else if (!pr.codes) {
@@ -872,7 +976,8 @@ cuking_status run_tiled(cuking_ctx *ctx, const cuking_submatrix &sm,
   const LaunchSwitches sw = launch_switches(ctx, words_per_sample, full, kin_threshold);
   // (where the filter runs the four-product kernel's codes may stay unconverted)
   cuking_status st = prepare(ctx, sm, words_per_sample, d_bit_sets, stream, &geo, &tiles,
-                             !sw.filter_runs, kin || sum);
+                             !sw.filter_runs, kin || sum, 0, 0xFFFFFFFFu, sw.filter_runs,
+                             kin_threshold);
   if (st != CUKING_OK) return st;
   const uint64_t n_tiles = total_tiles(tiles);
   if (whole) {
@@ -968,6 +1073,10 @@ const Option kOptions[] = {
      CTX_FIELD(filter_sort)},
     {"filter_lazy_codes", 0, 1, "filter_lazy_codes outside [0, 1]", 0, kInvalidatesLayout,
      CTX_FIELD(filter_lazy_codes)},
+    {"filter_site_order", -1, 2, "filter_site_order outside [-1, 2]", 0, kInvalidatesLayout,
+     CTX_FIELD(filter_site_order)},
+    {"filter_site_order_min_tiles", 0, 1 << 30, "filter_site_order_min_tiles outside [0, 2^30]",
+     0, kInvalidatesLayout, CTX_FIELD(filter_site_order_min_tiles)},
     {"filter_check0", 0, 2, "filter_check0 outside [0, 2]", 0, 0, CTX_FIELD(filter_check0)},
     {"filter_check1", 0, 1 + kNumCheckShares, "filter_check1 outside {0, 1, 3 .. %u}",
      1 + kNumCheckShares, 0, CTX_FIELD(filter_check1), /*hole=*/2},
@@ -1008,7 +1117,14 @@ cuking_status read_diagnostic(const cuking_ctx *ctx, const char *key, int64_t *v
   const std::pair<const char *, uint64_t> counters[] = {
       {"workspace_allocations", ctx->workspace_allocations},
       {"host_syncs", ctx->host_syncs},
-      {"conversions_skipped", ctx->conversions_skipped}};
+      {"conversions_skipped", ctx->conversions_skipped},
+      // (site order: what the last conversion that built a curve read from it -- the share
+      //  of an unrotated tile's check in 64ths by the curve and by stored order's rule, 0 =
+      //  none; the counts' sigma in millionths; whether the prepared layout took the order)
+      {"site_order_share", ctx->order_forecast.order64},
+      {"site_order_stored_share", ctx->order_forecast.stored64},
+      {"site_order_sigma_e6", (uint64_t)llroundf(ctx->order_sigma * 1e6f)},
+      {"site_order_on", ctx->prepared.valid && ctx->prepared.site_order ? 1u : 0u}};
   for (const auto &c : counters)
     if (strcmp(c.first, key) == 0) {
       *value = (int64_t)c.second;

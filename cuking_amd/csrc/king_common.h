@@ -302,6 +302,14 @@ struct TiledArgs {
   uint32_t *rel_counts;
   uint32_t rel_num;
   float rel_thr[CUKING_REL_THRESHOLDS_MAX];
+  // Site order (king_sort.hip "Site order"; again at the END): non-null = the T2 layout and
+  // the per-sample counts hold the sites sorted by the X they contribute to an unrelated
+  // pair, and this is the cohort's measured curve (SiteCurve) the filter kernel takes the
+  // share in front of its rigorous check from.  nullptr: stored order, the linear rule.
+  const struct SiteCurve *site_curve;
+  // ("filter_site_order" 2, a measurement switch: the tiles of such a layout ARE rotated, each
+  //  takes the share of the range it covers from the curve -- king_filter.hip plan_checks)
+  uint32_t site_rotate;
 };
 
 // Prefix statistics: the k-steps (of 256 sites) a check may sit behind, as shares of the
@@ -322,6 +330,54 @@ constexpr uint32_t kPhasesPerShare = kNumPhases / 64;
 constexpr uint32_t kNumCum = kNumPhases - 1;  // inner boundaries (0 is zero, the last the total)
 __host__ __device__ inline uint32_t phase_step(uint32_t all_steps, uint32_t x) {
   return (uint32_t)((uint64_t)all_steps * x / kNumPhases);
+}
+// Site order (king_sort.hip): the cohort's curve of X over the layout's site order, left by
+// the conversion beside the cohort's sums.  cum[x] = the sum over the sites in front of phase
+// boundary x + 1 (cum[kNumPhases - 1]: over all sites) of the site's weight, the sum of
+// (g - g')^2 over the unordered pairs of samples both defined there,
+//     w = ref het + het alt + 4 ref alt        (exact integers from the site's counts);
+// a random pair's expected X over a range of sites is that range's weight / pairs of samples.
+// sigma: the standard deviation of the bound's kinship for such a pair from the SAME counts,
+// sqrt(sum over the sites of Var (g - g')^2) / (4 mean |H|) -- on a flat spectrum near the
+// 1 / sqrt(sites) of bound_level() (king_filter.hip), on an exome-like one several times that.
+// het_calls, missing_calls: the cohort's totals from the same counts (what bound_level() takes
+// its mean from, there from a sample of the samples).
+// Automatic ("filter_site_order" -1): blocks of at least this many 256-sample tiles -- the
+// gather grows with the samples, what it saves with their square; measured at 100k sites and a
+// gain of 8/64 (profiles/r18_site_order.txt F): the order still loses 0.1 of 28.7 ms at 16,290
+// tiles and wins 8.4 of 131 at 76,636, the floor sits between -- AND a curve that forecasts a check at least
+// kSiteOrderMinGain 64ths earlier than stored order's (site_order_forecast()); a block that
+// fails the second test has paid the counts, the sort and one host wait, and keeps stored
+// order and its rotated tiles.
+constexpr uint64_t kSiteOrderMinTiles = 24576;
+constexpr uint32_t kSiteOrderMinGain = 2;
+constexpr uint32_t kSiteOrderNoTrust = 15;  // conversions of a block that trust its last "no"
+struct SiteCurve {
+  unsigned long long cum[kNumPhases];
+  unsigned long long het_calls, missing_calls;
+  float sigma;
+  uint32_t pad[11];
+};
+static_assert(sizeof(SiteCurve) % 64 == 0, "whole 64-byte lines");
+// The share of the k-steps (in 64ths) a tile that starts at phase boundary `phase` needs in
+// front of its rigorous check when the sites are in the curve's order: candidate `share64`
+// will do when the weight of the phases [phase, phase + share64 kPhasesPerShare) (around the
+// end) is at least `need` of all weight -- need = (1 - 2 thr) / (1 - 2 kappa), the share of
+// X an unrelated pair must have shown (king_filter.hip "Check points"; in stored order X is
+// taken to grow linearly and need IS the share).
+// site_curve_mass: that weight as a share of all weight (0 for a cohort without any).
+__host__ __device__ inline float site_curve_mass(const unsigned long long *cum, uint32_t phase,
+                                                 uint32_t share64) {
+  const uint32_t hi = phase + share64 * kPhasesPerShare;  // (< 2 kNumPhases)
+  auto front = [&](uint32_t x) { return x == 0 ? 0ull : cum[x - 1]; };
+  const unsigned long long all = cum[kNumPhases - 1];
+  const unsigned long long got = hi <= kNumPhases ? front(hi) - front(phase)
+                                                  : (all - front(phase)) + front(hi - kNumPhases);
+  return all != 0 ? (float)got / (float)all : 0.f;
+}
+__host__ __device__ inline bool site_curve_covers(const unsigned long long *cum, uint32_t phase,
+                                                  uint32_t share64, float need) {
+  return site_curve_mass(cum, phase, share64) >= need;
 }
 // k-steps (of 256 sites) behind share k for a bitset of `all_steps` k-steps, counted from
 // the bitset's first site; 0 when the bitset is too short for a check to pay.
@@ -346,7 +402,9 @@ __host__ __device__ inline size_t plane_bytes(const PlaneGeometry &g,
     return base + base / 4 + base / 2 + (size_t)g.s_stride * sizeof(float2) +
            (size_t)g.s_stride * kNumCum * sizeof(float) + 64 + 64 +
            // control block, perm, statistics before the sort, the sort's four arrays
-           64 + (size_t)g.s_stride * (4 + 8 + 4 * (kNumCum + 1) + 16);
+           64 + (size_t)g.s_stride * (4 + 8 + 4 * (kNumCum + 1) + 16) +
+           // the site order's curve, behind everything else
+           sizeof(SiteCurve);
   return base;
 }
 // Where the T2 layout and the per-sample statistics of kLayoutNibbleStats start
@@ -467,6 +525,10 @@ __host__ __device__ inline uint32_t *plane_sort_words(const uint4 *planes, const
   return reinterpret_cast<uint32_t *>(plane_tmp_prefix(planes, g) +
                                       (size_t)g.s_stride * (kNumCum + 1));
 }
+// ... and behind the sort's arrays the site order's curve.
+__host__ __device__ inline SiteCurve *plane_site_curve(const uint4 *planes, const PlaneGeometry &g) {
+  return reinterpret_cast<SiteCurve *>(plane_sort_words(planes, g) + 4 * (size_t)g.s_stride);
+}
 constexpr uint32_t kNoSample = 0xFFFFFFFFu;
 
 // Scratch of one stream: the chunk's control words and one flag per tile of a launch chunk
@@ -573,6 +635,36 @@ size_t sort_temp_bytes_for(uint32_t n);
 hipError_t launch_sample_order(const PlaneGeometry &geo, uint32_t words_per_sample,
                                uint4 *d_planes, uint32_t s_begin, uint32_t s_end, bool sort,
                                void *sort_temp, size_t sort_temp_bytes, hipStream_t stream);
+// Site order (king_sort.hip): the scratch a conversion with the order on needs for a block of
+// `num_stored` stored samples (0: the order cannot be built for this width -- a sample's two
+// planes must fit the gather's LDS), and the conversion's first steps: site counts, weights,
+// stable sort, the bitset with every sample's sites in that order at the scratch's
+// `permuted` (same shape as d_bit_sets: what sample_stats_kernel and the T2 conversion then
+// read instead), and the curve at `curve`.
+// launch_site_order: counts, weights, sort and curve; launch_site_permute: the gather -- two
+// calls, so that the host may read the curve in between and keep stored order after all.
+struct SiteOrderScratch {
+  size_t counts, keys, vals, sort_temp, sort_temp_bytes, permuted, bytes;
+};
+SiteOrderScratch site_order_scratch(uint32_t num_stored, uint32_t words_per_sample);
+hipError_t launch_site_order(const uint64_t *d_bit_sets, uint32_t num_stored,
+                             uint32_t words_per_sample, const PlaneGeometry &geo, void *d_scratch,
+                             const SiteOrderScratch &layout, SiteCurve *d_curve,
+                             hipStream_t stream);
+hipError_t launch_site_permute(const uint64_t *d_bit_sets, uint32_t num_stored,
+                               uint32_t words_per_sample, void *d_scratch,
+                               const SiteOrderScratch &layout, hipStream_t stream);
+// What a curve forecasts for the rigorous check of an unrotated tile at threshold `thr`, in
+// 64ths of the k-steps (0: no check up to 62/64): `stored64` by the linear rule of stored
+// order, `order64` from the curve -- the arithmetic of the filter kernel (king_filter.hip
+// plan_checks, launch_verdict), with the cohort's rates from all samples instead of a sample
+// of them.  `verdict_first`: the launch-wide verdict lets every tile leave before it starts.
+struct SiteOrderForecast {
+  uint32_t stored64, order64;
+  bool verdict_first;
+};
+SiteOrderForecast site_order_forecast(const SiteCurve &curve, uint32_t num_stored,
+                                      uint32_t k_words, float thr);
 // Codes (+ het-only copy) and / or T2 of plane tiles [s_tile_begin, s_tile_end) of a
 // nibble workspace; `gate` != nullptr: only if a quadrant went dense or a tile left
 // (filter control words) and the codes are not there yet (*ready == 0).

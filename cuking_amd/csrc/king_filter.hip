@@ -67,6 +67,14 @@
 // persistent launch -- one resident workgroup per CU taking tile after tile -- was measured
 // 1.2 % slower and removed: r04_tile_gaps.txt.)
 //
+// Site order (king_sort.hip, TiledArgs::site_curve): the conversion may hand this kernel the
+// sites sorted by what they add to X of unrelated pairs.  Nothing in the k loop, the epilogue
+// or the refine kernel knows: the sums are over all sites either way.  Only the SHARE in front
+// of the rigorous check changes -- taken from the cohort's measured curve (launch_verdict,
+// plan_checks) instead of the linear rule -- and such a layout's tiles are not rotated
+// (launch_filter; rotated tiles on such a layout were measured slower than stored order).
+// configs[2]: 125.2 -> 118.1 ms per step, profiles/r18_site_order.txt.
+//
 // Workgroup = 256 x 256 pairs, 4 wavefronts of 128 x 128 = 4 x 4 MFMA blocks (256
 // accumulator registers), k-step = 256 sites = 4 slices of 64, 5 LDS stages of
 // 32 KiB by LDS-DMA.  Per k-step and wavefront: 64 MFMAs (32 of them scaled), 16
@@ -322,8 +330,17 @@ __device__ __forceinline__ bool take_tile(const TiledArgs &a, const uint32_t wg,
 // that has not set its tile_done flag.  The worst case costs the exact kernel's time
 // plus the first round of this one (short launches: plus an eighth of it, check 0).
 // *xcd_pos: the k-step the tiles of this XCD are at (rotated tiles, plan_checks()).
+// *order_share: site order only (TiledArgs::site_curve) -- the share in front of the
+// rigorous check, in 64ths, for a tile that starts at phase boundary `start_phase`
+// (hook_phase(); 0 = the curve allows none up to 62/64).
+// hook_phase: the phase a test hook makes tile t start at (TiledArgs::rotate 2 / 3 + j), else 0.
+__device__ __forceinline__ uint32_t hook_phase(const TiledArgs &a, const Tile &t) {
+  if (a.rotate < 2 || a.geo.k_words / 8 < a.rotate_min_steps) return 0;
+  return (a.rotate == 2 ? t.bid * 37u + 11u : a.rotate - 3u) & (kNumPhases - 1);
+}
 __device__ __forceinline__ bool launch_verdict(const TiledArgs &a, const uint32_t wg,
-                                               uint4 *const lds, uint32_t *xcd_pos) {
+                                               uint4 *const lds, uint32_t *xcd_pos,
+                                               const uint32_t start_phase, uint32_t *order_share) {
   // ONE decision per workgroup (the counters move while the wavefronts read them,
   // and a wavefront that left alone would take its quarter of every stage's
   // requests with it): thread 0 reads, the stage memory carries the verdict.
@@ -368,7 +385,31 @@ __device__ __forceinline__ bool launch_verdict(const TiledArgs &a, const uint32_
       pos += ago * 16u / ticks16;
     verdict[1 + threadIdx.x] = pos;
   }
+  // Site order: X does not grow linearly in the site index, the conversion has left the
+  // curve (king_common.h SiteCurve).  The share becomes the first 64th (32 .. 62) behind
+  // which the tile has seen `need` of an unrelated pair's X: need = (1 - 2 thr) / (1 - 2
+  // kappa) as in stored order ("Check points" below), kappa with the standard deviation the
+  // site counts give.  One wavefront tries every share at once, one word carries the
+  // answer to the workgroup (ONE decision per workgroup, as above).  It need not be thread
+  // 0's wavefront: unlike the counters above, the curve and the cohort's sums are written by
+  // the conversion in front of the launch and do not change while it runs, so every reader
+  // sees one snapshot; the stage memory still carries the one answer.
+  if (a.site_curve != nullptr && (threadIdx.x >> 6) == 1) {
+    const uint32_t s = threadIdx.x & 63;
+    float mean, sigma;
+    bool ok = false;
+    if (a.cohort_sums != nullptr &&
+        bound_level(a.cohort_sums, 32.f * (float)a.geo.k_words, &mean, &sigma)) {
+      const float kappa = mean + 4.6f * a.site_curve->sigma + 0.003f;
+      const float need = (1.f - 2.f * a.kin_threshold) / (1.f - 2.f * kappa);
+      ok = kappa < 0.5f && s >= 32 && s <= 62 &&
+           site_curve_covers(a.site_curve->cum, start_phase, s, need);
+    }
+    const unsigned long long fits = __ballot(ok);
+    if (s == 0) verdict[1 + kPosSlots] = fits != 0 ? (uint32_t)__ffsll(fits) - 1u : 0u;
+  }
   __syncthreads();
+  *order_share = a.site_curve != nullptr ? __builtin_amdgcn_readfirstlane(verdict[1 + kPosSlots]) : 0u;
   const bool give_up = verdict[0] != 0;
   uint32_t pos = 0;
   if (a.rotate == 1) {
@@ -423,9 +464,17 @@ struct CheckPlan {
   uint32_t wrap;        // k-steps of the tile in front of the end of the sites (0: none behind)
   uint32_t start_abs;   // k0, counted on from the position the XCD's tiles have published
 };
-// `xcd_pos`: launch_verdict(); `all_steps`: the bitset's k-steps, `num_steps`: the tile's.
+// `xcd_pos`, `order_share`: launch_verdict(); `all_steps`: the bitset's k-steps, `num_steps`:
+// the tile's.
+// --- Site order (TiledArgs::site_curve; king_sort.hip).  The prefix bound does not care WHICH
+// sites the prefix holds, so the conversion may put the sites that contribute most to X of
+// unrelated pairs in front; the share then comes from the cohort's measured curve
+// (launch_verdict) instead of the linear rule.  A tile that started at another phase would
+// begin with the light sites: launch_filter turns the rotation off for such a layout (its
+// test hooks stay, their share is taken over the range the tile covers).
 __device__ __forceinline__ CheckPlan plan_checks(const TiledArgs &a, const Tile &t,
-                                                 const uint32_t xcd_pos, const uint32_t all_steps,
+                                                 const uint32_t xcd_pos, const uint32_t order_share,
+                                                 const uint32_t all_steps,
                                                  const uint32_t num_steps) {
   uint32_t chk0 = 0, chk1 = 0, entry1 = 0, share1 = 0;
   uint32_t phase = 0, k0 = 0, wrap = 0, start_abs = 0;
@@ -449,6 +498,28 @@ __device__ __forceinline__ CheckPlan plan_checks(const TiledArgs &a, const Tile 
       start_abs = base + k0;
       wrap = k0 != 0 ? all_steps - k0 : 0u;
     }
+    // Site order with rotated tiles (TiledArgs::site_rotate): the phase is only known here,
+    // so the share of the range [phase, phase + share) around the end is looked up now --
+    // the weight of a range grows with its length: bisection over 32 .. 62, wave-uniform,
+    // from words the launch does not change.
+    uint32_t curve_share = order_share;
+    if (a.site_curve != nullptr && a.rotate == 1 && phase != 0) {
+      curve_share = 0;
+      float m0, s0;
+      if (a.cohort_sums != nullptr && bound_level(a.cohort_sums, 256.f * (float)all_steps, &m0, &s0)) {
+        const float kap = m0 + 4.6f * a.site_curve->sigma + 0.003f;
+        const float need = (1.f - 2.f * a.kin_threshold) / (1.f - 2.f * kap);
+        if (kap < 0.5f && site_curve_covers(a.site_curve->cum, phase, 62, need)) {
+          uint32_t lo = 32, hi = 62;
+          while (lo < hi) {
+            const uint32_t mid = (lo + hi) / 2;
+            if (site_curve_covers(a.site_curve->cum, phase, mid, need)) hi = mid;
+            else lo = mid + 1;
+          }
+          curve_share = lo;
+        }
+      }
+    }
     // kappa: the level of the bound for this cohort's unrelated pairs (from its mean missing
     // and het rates) plus 4.6 standard deviations and a little
     float kappa = -1.f, mean, sigma;
@@ -471,6 +542,12 @@ __device__ __forceinline__ CheckPlan plan_checks(const TiledArgs &a, const Tile 
     const uint32_t sw1 = a.check1 & 0xFFu;
     if (sw1 >= 2) {
       entry1 = sw1 - 2;
+    } else if (sw1 == 1 && a.site_curve != nullptr) {
+      // (site order: the share the curve gives for this tile's range)
+      if (curve_share != 0) {
+        share1 = curve_share;
+        entry1 = 1;
+      }
     } else if (sw1 == 1 && kappa >= 0.f) {
       // The share behind which no unrelated pair of this cohort is still under the bound, in
       // 64ths, rounded up -- any of them: the counts are there at every phase boundary.  (A
@@ -551,7 +628,11 @@ __device__ __forceinline__ Leave check_sweep(const TiledArgs &a, const Tile &t, 
                                              const v16f (&acc)[4][4], uint4 *const lds,
                                              const bool forecast, const uint32_t all_steps) {
   const Lanes l = lanes_of_thread();
-  const float scale = forecast ? (float)kCheckShares64[0] * (1.f / 64.f) : 1.f;
+  // (site order: the forecast's prefix holds that share of an unrelated pair's X, not an eighth)
+  const float scale = !forecast ? 1.f
+                      : a.site_curve != nullptr
+                          ? site_curve_mass(a.site_curve->cum, p.phase, kCheckShares64[0])
+                          : (float)kCheckShares64[0] * (1.f / 64.f);
   const uint32_t share = forecast ? kCheckShares64[0] : p.share1;  // (uniform)
   // (the forecast counts the pairs that WILL be candidates from an eighth of the sites:
   //  the bound of an unrelated pair scatters sqrt(8) times as widely there as at the
@@ -966,8 +1047,10 @@ __device__ __forceinline__ void filter_tile(const TiledArgs &a, const uint32_t w
   Tile tile;
   if (!take_tile(a, wg, lds, &tile)) return;
   const Lanes ln = lanes_of_thread();
-  uint32_t xcd_pos = 0;
-  if (!tile.split && a.tile_done != nullptr && launch_verdict(a, wg, lds, &xcd_pos)) return;
+  uint32_t xcd_pos = 0, order_share = 0;
+  if (!tile.split && a.tile_done != nullptr &&
+      launch_verdict(a, wg, lds, &xcd_pos, hook_phase(a, tile), &order_share))
+    return;
   // k-steps of 256 sites: all of them, or this piece's share
   const uint32_t all_steps = a.geo.k_words / (4 * kUnits);
   // (wave-uniform, but divisions run in vector registers: pinned to SGPRs for the
@@ -976,7 +1059,7 @@ __device__ __forceinline__ void filter_tile(const TiledArgs &a, const uint32_t w
       tile.split ? tile.part * all_steps / a.fsplit_parts : 0u);
   const uint32_t num_steps = __builtin_amdgcn_readfirstlane(
       tile.split ? (tile.part + 1) * all_steps / a.fsplit_parts - k_first : all_steps);
-  const CheckPlan plan = plan_checks(a, tile, xcd_pos, all_steps, num_steps);
+  const CheckPlan plan = plan_checks(a, tile, xcd_pos, order_share, all_steps, num_steps);
 
   // --- the k loop: acc = (q + n_A + S_i + S_j) / 4 of the tile's pairs ("Offset code" above)
   // (the names the F_* macros and the segment loop below use)
@@ -1292,7 +1375,7 @@ hipError_t launch_sample_stats(const uint64_t *d_bit_sets, uint32_t words_per_sa
   return hipGetLastError();
 }
 
-hipError_t launch_filter(const TiledArgs &args, const LaunchSwitches &sw, uint64_t num_tiles,
+hipError_t launch_filter(const TiledArgs &args, const LaunchSwitches &switches, uint64_t num_tiles,
                          hipStream_t stream) {
   if ((uint64_t)args.geo.k_words * 32 > kMfmaN4MaxSites || args.filter_ctrl == nullptr ||
       args.cand_list == nullptr || args.dense_list == nullptr || args.sample_stats == nullptr)
@@ -1308,6 +1391,13 @@ hipError_t launch_filter(const TiledArgs &args, const LaunchSwitches &sw, uint64
   if (cap == 0) return hipErrorInvalidValue;
   const uint32_t wgs = args.split_wgs != 0 ? args.split_wgs : 256;  // one per CU
   const bool checks = args.tile_done != nullptr;
+  // Site order: no rotated tiles.  A tile that joins the others at phase p would need the
+  // weight of [p, p + e) around the end: from the middle of a descending order that is MORE
+  // k-steps than stored order takes (0.90 of them on the flat spectrum, against 0.875), so
+  // the launch pays the L2 cost of tiles that all start at the first site instead
+  // (profiles/r04_l2_probe.txt: hit rate 0.41 against 0.75, about 3.5 % of the clock).
+  LaunchSwitches sw = switches;
+  if (args.site_curve != nullptr && sw.rotate == 1 && args.site_rotate == 0) sw.rotate = 0;
   const bool can_split = args.fsplit_slabs != nullptr && args.fsplit_tickets != nullptr;
   for (uint64_t done = 0; done < num_tiles;) {
     const FilterPlan p = filter_plan(num_tiles - done, cap, wgs, args.geo.k_words / 8, checks,

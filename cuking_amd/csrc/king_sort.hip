@@ -151,4 +151,277 @@ hipError_t launch_sample_order(const PlaneGeometry &geo, uint32_t words_per_samp
   return hipSuccess;
 }
 
+// ---- Site order.  X = sum over the sites of (g_i - g_j)^2 has only non-negative terms and
+// KING's sums do not care in which order the sites are visited, as long as every sample uses
+// the same one.  The filter kernel's rigorous check (king_filter.hip "Check points") lets a
+// tile leave once X over the sites SO FAR has passed the level no record stays under; with
+// the sites that contribute most to X of unrelated pairs in front, that happens earlier.
+// Steps of a whole-block conversion with the order on:
+//   1. site counts (king_site_qc.hip: hom-ref, het, hom-alt, missing per site, one pass);
+//   2. weight per site, w = ref het + het alt + 4 ref alt: the sum of (g - g')^2 over the
+//      pairs of samples, an exact integer;
+//   3. a STABLE descending sort of (weight, site): deterministic for one bitset, ties --
+//      monomorphic sites, and the padding of the last word behind them -- keep stored order;
+//   4. the bitset once more with every sample's sites in that order (permute_sites_kernel),
+//      in stream scratch: sample_stats_kernel and the T2 conversion read it instead of the
+//      caller's and stay as they are.  Everything that recounts exactly (king_refine_kernel,
+//      the four-product kernel's codes) keeps reading the caller's bitset;
+//   5. the curve: the weight in front of every phase boundary, and sigma (SiteCurve).
+namespace {
+
+constexpr uint32_t kOrderLdsBytes = 64 * 1024;  // what a kernel may ask for without more ado
+
+__global__ void site_keys_kernel(const uint32_t *__restrict__ counts, uint32_t sites,
+                                 unsigned long long *__restrict__ keys,
+                                 uint32_t *__restrict__ vals) {
+  const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
+  if (s >= sites) return;
+  const uint4 c = reinterpret_cast<const uint4 *>(counts)[s];  // ref, het, alt, missing
+  const unsigned long long r = c.x, h = c.y, a = c.z;
+  keys[s] = r * h + h * a + 4ull * r * a;
+  vals[s] = s;
+}
+
+// One workgroup per phase: the weight of its sites (in the new order), their share of the
+// variance and of the het rate, and their het and missing calls (phase_v: four per phase);
+// site_curve_scan_kernel adds the phases up.
+__global__ __launch_bounds__(256) void site_curve_kernel(
+    const uint32_t *__restrict__ counts, const uint32_t *__restrict__ order, uint32_t sites,
+    uint32_t all_steps, unsigned long long *__restrict__ phase_w, double *__restrict__ phase_v) {
+  __shared__ unsigned long long w_part[4];
+  __shared__ double v_part[4], h_part[4], hc_part[4], mc_part[4];
+  const uint32_t x = blockIdx.x;
+  const uint32_t begin = 256u * phase_step(all_steps, x), end = 256u * phase_step(all_steps, x + 1);
+  unsigned long long w = 0;
+  double var = 0., het = 0., hc = 0., mc = 0.;  // (calls: integers below 2^53)
+  for (uint32_t d = begin + threadIdx.x; d < end && d < sites; d += 256) {
+    const uint4 c = reinterpret_cast<const uint4 *>(counts)[order[d]];
+    const double r = c.x, h = c.y, a = c.z, n = r + h + a + (double)c.w;
+    const double pairs = 0.5 * n * (n - 1.);
+    hc += h;
+    mc += (double)c.w;
+    if (pairs < 1.) continue;
+    w += (unsigned long long)c.x * c.y + (unsigned long long)c.y * c.z +
+         4ull * (unsigned long long)c.x * c.z;
+    // (g - g')^2 of a random pair: 1 with p1, 4 with p4
+    const double p1 = (r * h + h * a) / pairs, p4 = r * a / pairs, mean = p1 + 4. * p4;
+    var += p1 + 16. * p4 - mean * mean;
+    het += h / n;
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    w += __shfl_xor(w, off);
+    var += __shfl_xor(var, off);
+    het += __shfl_xor(het, off);
+    hc += __shfl_xor(hc, off);
+    mc += __shfl_xor(mc, off);
+  }
+  if ((threadIdx.x & 63) == 0) {
+    w_part[threadIdx.x >> 6] = w;
+    v_part[threadIdx.x >> 6] = var;
+    h_part[threadIdx.x >> 6] = het;
+    hc_part[threadIdx.x >> 6] = hc;
+    mc_part[threadIdx.x >> 6] = mc;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    phase_w[x] = w_part[0] + w_part[1] + w_part[2] + w_part[3];
+    phase_v[4 * x] = v_part[0] + v_part[1] + v_part[2] + v_part[3];
+    phase_v[4 * x + 1] = h_part[0] + h_part[1] + h_part[2] + h_part[3];
+    phase_v[4 * x + 2] = hc_part[0] + hc_part[1] + hc_part[2] + hc_part[3];
+    phase_v[4 * x + 3] = mc_part[0] + mc_part[1] + mc_part[2] + mc_part[3];
+  }
+}
+
+// (128 phases: one thread adds them up)
+__global__ __launch_bounds__(64) void site_curve_scan_kernel(
+    const unsigned long long *__restrict__ phase_w, const double *__restrict__ phase_v,
+    SiteCurve *__restrict__ curve) {
+  if (threadIdx.x != 0) return;
+  unsigned long long run = 0;
+  double var = 0., het = 0., hc = 0., mc = 0.;
+  for (uint32_t x = 0; x < kNumPhases; ++x) {
+    run += phase_w[x];
+    curve->cum[x] = run;
+    var += phase_v[4 * x];
+    het += phase_v[4 * x + 1];
+    hc += phase_v[4 * x + 2];
+    mc += phase_v[4 * x + 3];
+  }
+  curve->het_calls = (unsigned long long)hc;
+  curve->missing_calls = (unsigned long long)mc;
+  curve->sigma = het > 0. ? (float)(sqrt(var) / (4. * het)) : 1.f;
+}
+
+// The gather.  A workgroup stages the two planes of G samples in LDS, interleaved per 32
+// sites ({het, hom-alt} halves: one 8-byte read serves both planes), then every wavefront
+// assembles runs of 64 output words: lane l looks up the source of destination site
+// 64 W + l (`order`, the same for every sample: read once per G samples), fetches its two
+// bits, and two ballots ARE output word W of the two planes; lane j keeps word j of the
+// run, so that the run goes out as one 512-byte store per plane and sample.
+template <int G>
+__global__ __launch_bounds__(256) void permute_sites_kernel(
+    const uint64_t *__restrict__ bits, uint64_t *__restrict__ out,
+    const uint32_t *__restrict__ order, uint32_t num_stored, uint32_t words_per_sample) {
+  extern __shared__ uint4 row[];  // [G][plane word]: {het lo, hom lo, het hi, hom hi}
+  const uint32_t P = words_per_sample / 2;
+  const uint32_t s0 = blockIdx.x * G;
+  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int g = 0; g < G; ++g) {
+    const uint32_t s = s0 + g < num_stored ? s0 + g : num_stored - 1;  // (repeats: not stored)
+    const uint64_t *het = bits + (uint64_t)s * words_per_sample, *hom = het + P;
+    for (uint32_t w = threadIdx.x; w < P; w += 256) {
+      const uint64_t h = het[w], m = hom[w];
+      row[g * P + w] = make_uint4((uint32_t)h, (uint32_t)m, (uint32_t)(h >> 32), (uint32_t)(m >> 32));
+    }
+  }
+  __syncthreads();
+  const uint2 *half = reinterpret_cast<const uint2 *>(row);  // [G][2 P]: 32 sites of both planes
+  for (uint32_t w0 = 64 * wave; w0 < P; w0 += 256) {
+    uint64_t oh[G], om[G];
+#pragma unroll
+    for (int g = 0; g < G; ++g) oh[g] = om[g] = 0;
+    // (eight words at a time: their eight reads of `order` go out before the first is used)
+    for (uint32_t j0 = 0; j0 < 64 && w0 + j0 < P; j0 += 8) {
+      uint32_t src[8];
+#pragma unroll
+      for (uint32_t k = 0; k < 8; ++k) {
+        const uint32_t W = w0 + j0 + k < P ? w0 + j0 + k : P - 1;  // (behind the plane: a repeat, not stored)
+        src[k] = order[64 * W + lane];                             // < 64 P
+      }
+#pragma unroll
+      for (uint32_t k = 0; k < 8; ++k) {
+        const uint32_t at = src[k] >> 5, bit = 1u << (src[k] & 31);
+        const bool mine = lane == j0 + k;
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+          const uint2 x = half[g * 2 * P + at];
+          const uint64_t bh = __ballot((x.x & bit) != 0), bm = __ballot((x.y & bit) != 0);
+          if (mine) {
+            oh[g] = bh;
+            om[g] = bm;
+          }
+        }
+      }
+    }
+    if (w0 + lane < P) {
+#pragma unroll
+      for (int g = 0; g < G; ++g) {
+        if (s0 + g >= num_stored) continue;
+        uint64_t *dst = out + (uint64_t)(s0 + g) * words_per_sample + w0 + lane;
+        dst[0] = oh[g];
+        dst[P] = om[g];
+      }
+    }
+  }
+  // (words_per_sample odd: the word behind the two planes is never read by the conversion)
+}
+
+size_t up256(size_t x) { return (x + 255) / 256 * 256; }
+
+// bits of a weight for `n` samples: 6 n^2 / 2 at most
+int weight_bits(uint32_t n) {
+  int b = 1;
+  while (b < 32 && (1ull << b) <= n) ++b;
+  return 2 * b + 2 < 64 ? 2 * b + 2 : 64;
+}
+
+}  // namespace
+
+SiteOrderScratch site_order_scratch(uint32_t num_stored, uint32_t words_per_sample) {
+  SiteOrderScratch l = {};
+  const uint32_t P = words_per_sample / 2;
+  if (num_stored < 2 || P == 0 || (size_t)P * 16 > kOrderLdsBytes) return l;
+  const size_t sites = (size_t)P * 64;
+  size_t temp = 0;
+  unsigned long long *nil_k = nullptr;
+  uint32_t *nil_v = nullptr;
+  if (hipcub::DeviceRadixSort::SortPairsDescending(nullptr, temp, nil_k, nil_k, nil_v, nil_v,
+                                                   (int)sites, 0, 64) != hipSuccess)
+    return l;
+  l.counts = 0;                                      // u32 [sites][4]
+  l.keys = l.counts + up256(sites * 16);             // u64 in, out; then the phases' sums
+  l.vals = l.keys + up256(sites * 16) + up256(kNumPhases * 40);  // u32 in, out
+  l.sort_temp = l.vals + up256(sites * 8);
+  l.sort_temp_bytes = up256(temp);
+  l.permuted = l.sort_temp + l.sort_temp_bytes;
+  l.bytes = l.permuted + up256((size_t)num_stored * words_per_sample * 8);
+  return l;
+}
+
+hipError_t launch_site_order(const uint64_t *d_bit_sets, uint32_t num_stored,
+                             uint32_t words_per_sample, const PlaneGeometry &geo, void *d_scratch,
+                             const SiteOrderScratch &l, SiteCurve *d_curve, hipStream_t stream) {
+  if (l.bytes == 0 || d_scratch == nullptr) return hipErrorInvalidValue;
+  const uint32_t P = words_per_sample / 2, sites = P * 64;
+  uint8_t *base = static_cast<uint8_t *>(d_scratch);
+  uint32_t *counts = reinterpret_cast<uint32_t *>(base + l.counts);
+  unsigned long long *keys_in = reinterpret_cast<unsigned long long *>(base + l.keys);
+  unsigned long long *keys_out = keys_in + sites;
+  unsigned long long *phase_w =
+      reinterpret_cast<unsigned long long *>(base + l.keys + up256((size_t)sites * 16));
+  double *phase_v = reinterpret_cast<double *>(phase_w + kNumPhases);
+  uint32_t *vals_in = reinterpret_cast<uint32_t *>(base + l.vals), *vals_out = vals_in + sites;
+  hipError_t e = hipMemsetAsync(counts, 0, (size_t)sites * 16, stream);
+  if (e != hipSuccess) return e;
+  e = launch_site_counts(d_bit_sets, num_stored, words_per_sample, counts, stream);
+  if (e != hipSuccess) return e;
+  site_keys_kernel<<<dim3((sites + 255) / 256), dim3(256), 0, stream>>>(counts, sites, keys_in,
+                                                                       vals_in);
+  e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  size_t temp = l.sort_temp_bytes;
+  e = hipcub::DeviceRadixSort::SortPairsDescending(base + l.sort_temp, temp, keys_in, keys_out,
+                                                   vals_in, vals_out, (int)sites, 0,
+                                                   weight_bits(num_stored), stream);
+  if (e != hipSuccess) return e;
+  site_curve_kernel<<<dim3(kNumPhases), dim3(256), 0, stream>>>(counts, vals_out, sites,
+                                                                geo.k_words / 8, phase_w, phase_v);
+  e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  site_curve_scan_kernel<<<dim3(1), dim3(64), 0, stream>>>(phase_w, phase_v, d_curve);
+  return hipGetLastError();
+}
+
+hipError_t launch_site_permute(const uint64_t *d_bit_sets, uint32_t num_stored,
+                               uint32_t words_per_sample, void *d_scratch,
+                               const SiteOrderScratch &l, hipStream_t stream) {
+  if (l.bytes == 0 || d_scratch == nullptr) return hipErrorInvalidValue;
+  const uint32_t P = words_per_sample / 2, sites = P * 64;
+  uint8_t *base = static_cast<uint8_t *>(d_scratch);
+  const uint32_t *vals_out = reinterpret_cast<const uint32_t *>(base + l.vals) + sites;
+  uint64_t *permuted = reinterpret_cast<uint64_t *>(base + l.permuted);
+  const uint32_t groups2 = (num_stored + 1) / 2;
+  if ((size_t)P * 32 <= kOrderLdsBytes)
+    permute_sites_kernel<2><<<dim3(groups2), dim3(256), P * 32, stream>>>(
+        d_bit_sets, permuted, vals_out, num_stored, words_per_sample);
+  else
+    permute_sites_kernel<1><<<dim3(num_stored), dim3(256), P * 16, stream>>>(
+        d_bit_sets, permuted, vals_out, num_stored, words_per_sample);
+  return hipGetLastError();
+}
+
+SiteOrderForecast site_order_forecast(const SiteCurve &c, uint32_t num_stored, uint32_t k_words,
+                                      float thr) {
+  SiteOrderForecast f = {0, 0, false};
+  const float sites = 32.f * (float)k_words, ns = (float)num_stored;
+  if (!(ns > 0.f && c.het_calls != 0)) return f;
+  // (bound_level() of king_filter.hip)
+  const float m = (float)c.missing_calls / (ns * sites), h = (float)c.het_calls / (ns * sites);
+  const float mean = m * (1.f + m / (2.f * h * (1.f - m))), sigma = 1.f / sqrtf(sites);
+  f.verdict_first = mean - 4.f * sigma > thr;
+  const float k_lin = mean + 4.6f * sigma + 0.003f, k_ord = mean + 4.6f * c.sigma + 0.003f;
+  if (k_lin < 0.5f) {
+    const float f64 = 64.f * (1.f - 2.f * thr) / (1.f - 2.f * k_lin);
+    if (f64 <= 62.f) f.stored64 = f64 > 32.f ? (uint32_t)ceilf(f64) : 32u;
+  }
+  if (k_ord < 0.5f) {
+    const float need = (1.f - 2.f * thr) / (1.f - 2.f * k_ord);
+    for (uint32_t s = 32; s <= 62 && f.order64 == 0; ++s)
+      if (site_curve_covers(c.cum, 0, s, need)) f.order64 = s;
+  }
+  return f;
+}
+
 }  // namespace cuking

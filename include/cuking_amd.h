@@ -278,6 +278,30 @@ cuking_status cuking_ctx_set_kernel(cuking_ctx *ctx, cuking_kernel kernel);
  *                        share of missing calls (see cuking_tile_bounds below).
  *   "filter_lazy_codes"  1 (default): kernel 6's codes are converted only when a launch hands
  *                        it something; 0: with every conversion.
+ *   "filter_site_order"  the layout's SITES sorted by what they add to X of unrelated pairs, so
+ *                        that tiles leave at an earlier check (the share comes from the
+ *                        cohort's measured curve): -1 (default) whole-block conversions of
+ *                        blocks of at least 24576 tiles with
+ *                        check points, and of those only where the curve forecasts the check
+ *                        at least 2/64 of the k-steps earlier than stored order has it at
+ *                        the converting call's threshold (a "no" is trusted for the next 15
+ *                        conversions of the same block at that threshold; a call at another
+ *                        threshold decides and converts again); 0 never; 1 every whole-block
+ *                        conversion; 2 is 1 with the tiles still rotated, each taking the
+ *                        share of the range it covers (a measurement switch: measured slower
+ *                        than stored order).  Bitsets beyond 262,144 sites and the ranges of
+ *                        cuking_prepare_samples keep stored order.  Tiles of such a layout
+ *                        are not rotated.  Cost: a conversion that builds the curve waits
+ *                        for the stream once to read it (counted in "host_syncs"), and a
+ *                        layout that takes the order keeps a second copy of the bitset in
+ *                        the stream's scratch for the life of the context (2.5 GB at 100k x
+ *                        100k), allocated by that conversion: cuking_ctx_reserve does not
+ *                        cover it, so the first such call may allocate and wait.
+ *                        Read-only: "site_order_on" (the prepared layout took the order),
+ *                        "site_order_share" / "site_order_stored_share" (the share in front
+ *                        of an unrotated tile's check, in 64ths, by the curve and by stored
+ *                        order's rule as the last such conversion forecast them; 0 = none),
+ *                        "site_order_sigma_e6".
  *   "filter_check0"      forecast check at an eighth of the sites: 0 off, 1 (default) for
  *                        launches of fewer than 16 rounds, 2 always.
  *   "filter_check1"      rigorous check inside the k loop: 0 off, 1 (default) the entry of
@@ -292,6 +316,8 @@ cuking_status cuking_ctx_set_kernel(cuking_ctx *ctx, cuking_kernel kernel);
  *                        bitsets of fewer k-steps of 256 sites (default 128) and launches of
  *                        fewer tiles (default 2048) are not rotated.
  * Test hooks that force paths ordinary cohorts do not take:
+ *   "filter_site_order_min_tiles"  the tile count from which "filter_site_order" -1 builds a
+ *                            curve, default 24576.
  *   "filter_quadrant_cap"    candidates per 128 x 128 quadrant beyond which the quadrant
  *                            goes to kernel 6, 0..16384, default 384.
  *   "filter_cand_cap"        entries of the candidate list per launch chunk, default 2^25.
