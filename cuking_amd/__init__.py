@@ -22,7 +22,7 @@ from .pcrelate import (PCRELATE_PAIR_DTYPE, PCRelatePairs, PCRelateRecords,  # n
                        pcrelate_pairs_host, pcrelate_pairs_raw_host, pcrelate_records_host,
                        pcrelate_records_raw_host)
 from .ibd import (IBD_PAIR_DTYPE, IBD_SEGMENT_DTYPE, IBDPairs, genome_length,  # noqa: F401
-                  ibd_segments_host, ibd_segments_raw_host)
+                  ibd_scan_host, ibd_scan_raw_host, ibd_segments_host, ibd_segments_raw_host)
 from .roh import (ROH_SAMPLE_DTYPE, ROHSamples, roh_segments_host,  # noqa: F401
                   roh_segments_raw_host)
 

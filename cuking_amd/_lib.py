@@ -197,6 +197,10 @@ SIGNATURES = {
     "cuking_ibd_pairs_bridged": (_int, [_vp, _vp, _u32, _u32, _u32, _vp, _vp, _u32, _u32, _u32,
                                         _vp, _u64, _u32, _vp, _vp, _vp, _u64, C.POINTER(_u64),
                                         _vp]),
+    "cuking_ibd_scan_host": (_int, [_vp, _u32, _u32, _u32, _vp, _vp, _u32, _u32, _SM, _u64, _vp,
+                                    _u64, C.POINTER(_u64)]),
+    "cuking_ibd_scan": (_int, [_vp, _vp, _u32, _u32, _u32, _vp, _vp, _u32, _u32, _SM, _u64, _vp,
+                               _u64, C.POINTER(_u64), _vp]),
     "cuking_roh_samples_host": (_int, [_vp, _u32, _u32, _u32, _vp, _vp, _u32, _u32, _u32, _vp,
                                        _u64, _vp, _vp, _u64, C.POINTER(_u64)]),
     "cuking_roh_samples": (_int, [_vp, _vp, _u32, _u32, _u32, _vp, _vp, _u32, _u32, _u32, _vp,

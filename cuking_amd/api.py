@@ -1238,6 +1238,39 @@ class KingContext:
                                         pos, min_sites, min_length, segments, max_segments,
                                         num_records, stream, bridge_sites)
 
+    def ibd_scan_raw(self, bits, words_per_sample: int, num_sites: int, group=None, pos=None,
+                     min_sites: int = 512, min_length: int = 0, min_total: int = 0, block=None,
+                     max_records=None, out=None, stream=None):
+        """The bare kernel call for the IBD scan of a block (cuking_ibd_scan; include/cuking_amd.h
+        "IBD scan of a block" has the definition): every pair of ``block`` (as
+        ``pcrelate_records_raw`` takes it; None = all stored samples) is scanned as
+        ``ibd_segments_raw`` scans a listed pair, strictly, and the pairs with a kind-1 segment
+        and ``length1 >= min_total`` become records.  Returns ``(records, num_records)``: an
+        int32 ``[*, 10]`` device tensor whose first ``num_records`` rows are cuking_ibd_pair
+        with ``sample_i < sample_j``, in no particular order (``ibd.records_to_host`` sorts and
+        names them; ``out``: such a tensor to write into).  Without ``max_records`` the buffer
+        is 16 records per sample of the block, grown once to the exact count; with it an
+        overflow raises ``ResourceExhaustedError`` whose ``num_records`` is the exact count,
+        and ``max_records=0`` counts.  Waits for the stream once, to read the count, and once
+        more when ``pos`` is given."""
+        from . import ibd as _ibd
+        return _ibd.ibd_scan_raw_device(self, bits, words_per_sample, num_sites, group, pos,
+                                        min_sites, min_length, min_total, block, max_records,
+                                        out, stream)
+
+    def ibd_scan(self, bits, words_per_sample: int, num_sites: int, group=None, pos=None,
+                 min_sites: int = 512, min_length: int = 0, min_total: int = 0, block=None,
+                 max_records=None, stream=None):
+        """The pairs of a block that share an IBD1 segment, found without a list, as an
+        ``IBDPairs`` of host arrays by ``(sample_i, sample_j)`` (arguments as ``ibd_scan_raw``
+        takes them): ``proportions()`` and ``relationship()`` work as for ``ibd_segments``, and
+        ``pairs()`` is the list to hand to ``ibd_segments`` -- with ``bridge_sites = B``, a
+        scan at ``min_sites = B`` misses no pair the bridged call would report -- or to
+        ``pcrelate_pairs``.  Waits for the device."""
+        from . import ibd as _ibd
+        return _ibd.ibd_scan_device(self, bits, words_per_sample, num_sites, group, pos,
+                                    min_sites, min_length, min_total, block, max_records, stream)
+
     def roh_segments_raw(self, bits, words_per_sample: int, num_sites: int, samples=None,
                          group=None, pos=None, min_sites: int = 512, min_length: int = 0,
                          bridge_sites: int = 0, segments: bool = False, max_segments=None,

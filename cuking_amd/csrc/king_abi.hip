@@ -2242,12 +2242,15 @@ cuking_status cuking_pcrelate_pairs(cuking_ctx *ctx, const uint64_t *d_bits, uin
 
 // What the pair calls and the scan of single samples share once their arguments are checked and
 // there is work to do: the host check of the positions, the group bits and the count word of the
-// stream's scratch, `launch(d_group_bits, d_count, stream)`, and the count read back.
+// stream's scratch, `launch(d_group_bits, d_count, stream)`, and the count read back and judged
+// by `count_status` (segments for the listed calls, records for the scan of a block).
 extern "C++" {
 template <class Launch>
 static cuking_status ibd_scan_device(cuking_ctx *ctx, uint32_t num_sites, const int32_t *d_group,
                                      const uint32_t *d_pos, uint64_t max_segments,
-                                     uint64_t *num_segments, void *stream, Launch &&launch) {
+                                     uint64_t *num_segments, void *stream, Launch &&launch,
+                                     cuking_status (*count_status)(uint64_t, uint64_t) =
+                                         cuking_ibd_count_status) {
   BIND_OR_RETURN(ctx);
   hipStream_t s = (hipStream_t)stream;
   cuking_status st;
@@ -2285,7 +2288,7 @@ static cuking_status ibd_scan_device(cuking_ctx *ctx, uint32_t num_sites, const 
   ++ctx->host_syncs;
   HIP_TRY(hipStreamSynchronize(s));
   *num_segments = count;
-  return cuking_ibd_count_status(count, max_segments);
+  return count_status(count, max_segments);
 }
 }  // extern "C++"
 
@@ -2370,6 +2373,32 @@ cuking_status cuking_ibd_pairs_bridged(cuking_ctx *ctx, const uint64_t *d_bits,
   return ibd_pairs_device(ctx, d_bits, num_stored, words_per_sample, num_sites, d_group, d_pos,
                           min_sites, min_length, bridge_sites, d_pairs, num_pairs, pair_stride,
                           d_out, d_bridged, d_segments, max_segments, num_segments, stream);
+}
+
+// ---- IBD scan of a block (king_ibd_scan.hip) -----------------------------------
+cuking_status cuking_ibd_scan(cuking_ctx *ctx, const uint64_t *d_bits, uint32_t num_stored,
+                              uint32_t words_per_sample, uint32_t num_sites,
+                              const int32_t *d_group, const uint32_t *d_pos, uint32_t min_sites,
+                              uint32_t min_length, const cuking_submatrix *block,
+                              uint64_t min_total, cuking_ibd_pair *d_records,
+                              uint64_t max_records, uint64_t *num_records, void *stream) {
+  if (num_records != nullptr) *num_records = 0;
+  // (the arguments first: a refused call touches no device)
+  if (ctx == nullptr) return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "null context");
+  const cuking_status st = cuking_check_ibd_scan_args(d_bits, num_stored, words_per_sample,
+                                                      num_sites, min_sites, block, d_records,
+                                                      max_records, num_records);
+  if (st != CUKING_OK) return st;
+  // (without a site no run exists: no record)
+  if (sm_num_rows(*block) == 0 || sm_num_cols(*block) == 0 || num_sites == 0) return CUKING_OK;
+  return ibd_scan_device(
+      ctx, num_sites, d_group, d_pos, max_records, num_records, stream,
+      [&](const uint64_t *d_group_bits, unsigned long long *d_count, hipStream_t s) {
+        return launch_ibd_scan(d_bits, words_per_sample, num_sites, d_group_bits, d_pos,
+                               min_sites, min_length, *block, min_total, d_records, max_records,
+                               d_count, s);
+      },
+      cuking_ibd_scan_count_status);
 }
 
 // ---- timing ---------------------------------------------------------------

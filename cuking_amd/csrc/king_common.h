@@ -796,6 +796,16 @@ hipError_t launch_ibd_pairs(const uint64_t *d_bits, uint32_t num_stored,
                             cuking_ibd_pair *d_out, uint32_t *d_bridged,
                             cuking_ibd_segment *d_segments, uint64_t max_segments,
                             unsigned long long *d_count, hipStream_t stream);
+// IBD scan of a block (king_ibd_scan.hip; arguments already checked, king_host.h): ADDS the
+// number of pairs of `block` with a kind-1 segment and length1 >= min_total to *d_count (zeroed
+// by the caller, on the stream) and stores the records whose slot is below max_records;
+// d_group_bits as above; num_sites == 0 adds nothing.
+hipError_t launch_ibd_scan(const uint64_t *d_bits, uint32_t words_per_sample, uint32_t num_sites,
+                           const uint64_t *d_group_bits, const uint32_t *d_pos,
+                           uint32_t min_sites, uint32_t min_length,
+                           const cuking_submatrix &block, uint64_t min_total,
+                           cuking_ibd_pair *d_records, uint64_t max_records,
+                           unsigned long long *d_count, hipStream_t stream);
 // Runs of homozygosity (king_ibd.hip; arguments already checked): one row per entry of d_samples
 // (null: samples 0 .. num_samples - 1), the group bits, the count and the segment list as above.
 hipError_t launch_roh_samples(const uint64_t *d_bits, uint32_t num_stored,

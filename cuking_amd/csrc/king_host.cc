@@ -1078,9 +1078,45 @@ void ibd_walk_runs(const uint64_t *row_i, const uint64_t *row_j, uint32_t plane_
   }
 }
 
-// Rows, bridged counts and the segment list of both host calls.  bridge_sites == 0 links
-// nothing and tests every run where it closes; otherwise a chain is tested when the next run is
-// not linked to it, the last one after the walk.
+// Both kinds of ONE pair (i, j), the per-pair walk every host twin shares: the sums of its
+// segments, and on_segment(k, a, b, links) for each segment [a, b] of kind k + 1.
+// bridge_sites == 0 links nothing and tests every run where it closes; otherwise a chain is
+// tested when the next run is not linked to it, the last one after the walk.
+template <class OnSegment>
+void ibd_pair_sums(const uint64_t *bits, uint32_t words_per_sample, uint32_t num_sites,
+                   const std::vector<uint64_t> &group_bits, const uint32_t *pos,
+                   uint32_t min_sites, uint32_t min_length, uint32_t bridge_sites, uint64_t i,
+                   uint64_t j, IbdKindSums sums[2], OnSegment on_segment) {
+  // THE segment test of a chain [a, b] with `links` bridged breaks
+  auto test = [&](uint32_t k, uint32_t a, uint32_t b, uint32_t links) {
+    const uint32_t pos_a = pos != nullptr ? pos[a] : a, pos_b = pos != nullptr ? pos[b] : b;
+    if (!ibd_is_segment(a, b, pos_a, pos_b, min_sites, min_length)) return;
+    sums[k].add(pos_b - pos_a);
+    sums[k].bridged += links;
+    on_segment(k, a, b, links);
+  };
+  IbdChain chain[2];
+  ibd_walk_runs(bits + i * words_per_sample, bits + j * words_per_sample, words_per_sample / 2,
+                num_sites, group_bits, [&](uint32_t k, uint32_t a, uint32_t b) {
+                  if (bridge_sites == 0) return test(k, a, b, 0);
+                  IbdChain &c = chain[k];
+                  if (c.have && ibd_linked(c.last_first, c.last_end, a, b, bridge_sites,
+                                           group_bits.data())) {
+                    ++c.links;
+                  } else {
+                    if (c.have) test(k, c.first, c.last_end, c.links);
+                    c.have = 1;
+                    c.first = a;
+                    c.links = 0;
+                  }
+                  c.last_first = a;
+                  c.last_end = b;
+                });
+  for (uint32_t k = 0; k < 2; ++k)
+    if (chain[k].have) test(k, chain[k].first, chain[k].last_end, chain[k].links);
+}
+
+// Rows, bridged counts and the segment list of both host calls.
 cuking_status ibd_pairs_host(const uint64_t *bits, uint32_t num_stored, uint32_t words_per_sample,
                              uint32_t num_sites, const int32_t *group, const uint32_t *pos,
                              uint32_t min_sites, uint32_t min_length, uint32_t bridge_sites,
@@ -1104,39 +1140,15 @@ cuking_status ibd_pairs_host(const uint64_t *bits, uint32_t num_stored, uint32_t
     uint32_t in[2];
     memcpy(in, static_cast<const unsigned char *>(pairs) + p * pair_stride, sizeof(in));
     IbdKindSums sums[2];
-    if (in[0] < num_stored && in[1] < num_stored) {
-      // THE segment test of a chain [a, b] with `links` bridged breaks
-      auto test = [&](uint32_t k, uint32_t a, uint32_t b, uint32_t links) {
-        const uint32_t pos_a = pos != nullptr ? pos[a] : a, pos_b = pos != nullptr ? pos[b] : b;
-        if (!ibd_is_segment(a, b, pos_a, pos_b, min_sites, min_length)) return;
-        sums[k].add(pos_b - pos_a);
-        sums[k].bridged += links;
-        if (num_segments != nullptr) {
-          if (count < max_segments) segments[count] = cuking_ibd_segment{(uint32_t)p, k + 1, a, b};
-          ++count;
-        }
-      };
-      IbdChain chain[2];
-      ibd_walk_runs(bits + (uint64_t)in[0] * words_per_sample,
-                    bits + (uint64_t)in[1] * words_per_sample, words_per_sample / 2, num_sites,
-                    group_bits, [&](uint32_t k, uint32_t a, uint32_t b) {
-                      if (bridge_sites == 0) return test(k, a, b, 0);
-                      IbdChain &c = chain[k];
-                      if (c.have && ibd_linked(c.last_first, c.last_end, a, b, bridge_sites,
-                                               group_bits.data())) {
-                        ++c.links;
-                      } else {
-                        if (c.have) test(k, c.first, c.last_end, c.links);
-                        c.have = 1;
-                        c.first = a;
-                        c.links = 0;
-                      }
-                      c.last_first = a;
-                      c.last_end = b;
+    if (in[0] < num_stored && in[1] < num_stored)
+      ibd_pair_sums(bits, words_per_sample, num_sites, group_bits, pos, min_sites, min_length,
+                    bridge_sites, in[0], in[1], sums,
+                    [&](uint32_t k, uint32_t a, uint32_t b, uint32_t) {
+                      if (num_segments == nullptr) return;
+                      if (count < max_segments)
+                        segments[count] = cuking_ibd_segment{(uint32_t)p, k + 1, a, b};
+                      ++count;
                     });
-      for (uint32_t k = 0; k < 2; ++k)
-        if (chain[k].have) test(k, chain[k].first, chain[k].last_end, chain[k].links);
-    }
     cuking_ibd_pair row;
     row.sample_i = in[0];
     row.sample_j = in[1];
@@ -1256,6 +1268,82 @@ cuking_status cuking_roh_samples_host(const uint64_t *bits, uint32_t num_stored,
   if (num_segments == nullptr) return CUKING_OK;
   *num_segments = count;
   return cuking_ibd_count_status(count, max_segments);
+}
+
+}  // extern "C"
+
+// ---- IBD scan of a block -----------------------------------------------------------------------
+cuking_status cuking_check_ibd_scan_args(const void *bits, uint32_t num_stored,
+                                         uint32_t words_per_sample, uint32_t num_sites,
+                                         uint32_t min_sites, const cuking_submatrix *block,
+                                         const void *records, uint64_t max_records,
+                                         const void *num_records) {
+  cuking_status st = cuking_check_block(block, words_per_sample);
+  if (st != CUKING_OK) return st;
+  // (words_per_sample, num_sites and min_sites: the checks of the listed call, with no list)
+  st = cuking_check_ibd_args(bits, words_per_sample, num_sites, min_sites, nullptr, 0,
+                             2 * sizeof(uint32_t), nullptr, nullptr, 0, nullptr);
+  if (st != CUKING_OK) return st;
+  if (block->i_end > num_stored || block->j_end > num_stored)
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT,
+                       "ibd scan: block rows [%u, %u) x columns [%u, %u) outside the %u stored "
+                       "samples", block->i_begin, block->i_end, block->j_begin, block->j_end,
+                       num_stored);
+  if (num_records == nullptr)
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "ibd scan: null num_records pointer");
+  if (records == nullptr && max_records != 0)
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT,
+                       "ibd scan: null records pointer with max_records = %llu",
+                       (unsigned long long)max_records);
+  if (sm_num_rows(*block) == 0 || sm_num_cols(*block) == 0 || num_sites == 0) return CUKING_OK;
+  if (bits == nullptr)
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "ibd scan: null bits pointer");
+  return CUKING_OK;
+}
+
+cuking_status cuking_ibd_scan_count_status(uint64_t count, uint64_t max_records) {
+  if (count > max_records)
+    return cuking_fail(CUKING_ERR_RESOURCE_EXHAUSTED,
+                       "ibd scan: %llu records do not fit %llu: retry with that many",
+                       (unsigned long long)count, (unsigned long long)max_records);
+  return CUKING_OK;
+}
+
+extern "C" {
+
+// The pairs of the block in ascending (i, j), each through the walk of the listed call's twin.
+cuking_status cuking_ibd_scan_host(const uint64_t *bits, uint32_t num_stored,
+                                   uint32_t words_per_sample, uint32_t num_sites,
+                                   const int32_t *group, const uint32_t *pos, uint32_t min_sites,
+                                   uint32_t min_length, const cuking_submatrix *block,
+                                   uint64_t min_total, cuking_ibd_pair *records,
+                                   uint64_t max_records, uint64_t *num_records) {
+  if (num_records != nullptr) *num_records = 0;
+  cuking_status st = cuking_check_ibd_scan_args(bits, num_stored, words_per_sample, num_sites,
+                                                min_sites, block, records, max_records,
+                                                num_records);
+  if (st != CUKING_OK) return st;
+  // (without a site no run exists: no record)
+  if (sm_num_rows(*block) == 0 || sm_num_cols(*block) == 0 || num_sites == 0) return CUKING_OK;
+  st = cuking_check_ibd_positions(group, pos, num_sites);
+  if (st != CUKING_OK) return st;
+  const std::vector<uint64_t> group_bits = ibd_group_bits(group, num_sites);
+  const bool diag = sm_is_diag(*block);
+  uint64_t count = 0;
+  for (uint64_t i = block->i_begin; i < block->i_end; ++i)
+    for (uint64_t j = diag ? i + 1 : block->j_begin; j < block->j_end; ++j) {
+      IbdKindSums sums[2];
+      ibd_pair_sums(bits, words_per_sample, num_sites, group_bits, pos, min_sites, min_length, 0,
+                    i, j, sums, [](uint32_t, uint32_t, uint32_t, uint32_t) {});
+      if (sums[0].segments < 1 || sums[0].length < min_total) continue;
+      if (count < max_records)
+        records[count] = cuking_ibd_pair{(uint32_t)i,     (uint32_t)j,    sums[0].segments,
+                                         sums[1].segments, sums[0].length, sums[1].length,
+                                         sums[0].longest,  sums[1].longest};
+      ++count;
+    }
+  *num_records = count;
+  return cuking_ibd_scan_count_status(count, max_records);
 }
 
 }  // extern "C"

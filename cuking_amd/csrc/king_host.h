@@ -90,5 +90,16 @@ cuking_status cuking_check_roh_args(const void *bits, uint32_t words_per_sample,
                                     uint32_t num_sites, uint32_t min_sites, uint32_t bridge_sites,
                                     uint64_t num_samples, const void *out, const void *segments,
                                     uint64_t max_segments, const void *num_segments);
+// Argument checks of cuking_ibd_scan_host / cuking_ibd_scan (include/cuking_amd.h "IBD scan of a
+// block" lists them: the block through the check of the PC-Relate records, words_per_sample,
+// num_sites and min_sites through cuking_check_ibd_args, then its own; OK says nothing about
+// there being work to do), and the status of a record count: RESOURCE_EXHAUSTED above
+// max_records.
+cuking_status cuking_check_ibd_scan_args(const void *bits, uint32_t num_stored,
+                                         uint32_t words_per_sample, uint32_t num_sites,
+                                         uint32_t min_sites, const cuking_submatrix *block,
+                                         const void *records, uint64_t max_records,
+                                         const void *num_records);
+cuking_status cuking_ibd_scan_count_status(uint64_t count, uint64_t max_records);
 
 #endif  // CUKING_AMD_KING_HOST_H_

@@ -1,6 +1,6 @@
 // IBD segments for listed pairs (include/cuking_amd.h, "IBD segments for listed pairs"): the
-// definitions the kernels of king_ibd.hip, the host twin of king_host.cc and the tests share, so
-// that they cannot drift apart.  Plain C++: hipcc compiles the functions for the device, the
+// definitions the kernels of king_ibd.hip, the scan of a block of king_ibd_scan.hip ("IBD scan of
+// a block"), the host twins of king_host.cc and the tests share, so that they cannot drift apart.  Plain C++: hipcc compiles the functions for the device, the
 // sanitizer build of the tests (tests/ibd_host_driver.cc) for the host.  Integers only.
 //
 // Words.  Word w of a plane holds the sites 64 w .. 64 w + 63, site s at bit s & 63.  A scan
@@ -120,6 +120,11 @@ CUKING_HD inline bool ibd_group_start(const int32_t *group, uint32_t num_sites, 
 CUKING_HD inline bool ibd_is_segment(uint32_t a, uint32_t b, uint32_t pos_a, uint32_t pos_b,
                                      uint32_t min_sites, uint32_t min_length) {
   return b - a + 1 >= min_sites && pos_b - pos_a >= min_length;
+}
+// Its first half alone, for a caller that wants to know whether pos[a] and pos[b] are worth
+// reading: false means ibd_is_segment is false whatever the positions.
+CUKING_HD inline bool ibd_enough_sites(uint32_t a, uint32_t b, uint32_t min_sites) {
+  return b - a + 1 >= min_sites;
 }
 
 // Whether the run [a2, b2] is linked to the run [a, b] in front of it.  a2 == b + 2 leaves exactly

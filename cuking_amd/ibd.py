@@ -8,6 +8,9 @@ component and no ``min_maf`` enters, so the answer does not depend on a model of
 ``bridge_sites`` (0, or at least 64) forgives isolated genotyping errors: two runs of at least
 that many sites on either side of one break site of a group are linked, and a segment is a
 chain of linked runs (the header's "IBD segments with bridged breaks").  0 is the strict call.
+
+``ibd_scan`` needs no list: it scans every pair of a block and keeps the pairs with a kind-1
+segment (the header's "IBD scan of a block"), as ``pcrelate_records`` does for PC-Relate.
 """
 from __future__ import annotations
 
@@ -20,7 +23,7 @@ from . import _lib
 from ._lib import check
 from .api import KING_CUTOFFS, _count
 from .pcrelate import (DUPLICATE, FULL_SIBLING, PARENT_CHILD, SECOND_DEGREE, THIRD_DEGREE,
-                       UNRELATED, _device_pairs, _host_pairs)
+                       UNRELATED, _block, _default_records, _device_pairs, _host_pairs)
 
 MIN_SITES = _lib.IBD_MIN_SITES
 # cuking_ibd_pair, cuking_ibd_segment
@@ -47,7 +50,10 @@ class IBDPairs:
     call); ``segments`` (``IBD_SEGMENT_DTYPE`` rows in no particular order, or None when they
     were not asked for); ``min_sites``, ``min_length`` and ``bridge_sites`` of the call;
     ``bridged`` (uint32 ``[P, 2]`` when ``bridge_sites`` is not 0, else None): the bridged breaks
-    inside the counted segments of kind 1 and of kind 2 -- the errors that were forgiven."""
+    inside the counted segments of kind 1 and of kind 2 -- the errors that were forgiven.
+    From ``KingContext.ibd_scan`` / ``ibd_scan_host`` the rows are the records of the scan by
+    ``(sample_i, sample_j)``, ``min_total`` its threshold (else None) and ``block`` its block;
+    ``num_records`` is the number of rows either way."""
     rows: np.ndarray
     total_length: int
     segments: object
@@ -55,6 +61,10 @@ class IBDPairs:
     min_length: int
     bridge_sites: int = 0
     bridged: object = None
+    min_total: object = None
+    block: object = None
+
+    num_records = property(lambda self: int(self.rows.shape[0]))
 
     sample_i = property(lambda self: self.rows["sample_i"])
     sample_j = property(lambda self: self.rows["sample_j"])
@@ -64,6 +74,11 @@ class IBDPairs:
     length2 = property(lambda self: self.rows["length2"])
     longest1 = property(lambda self: self.rows["longest1"])
     longest2 = property(lambda self: self.rows["longest2"])
+
+    def pairs(self) -> np.ndarray:
+        """``(sample_i, sample_j)`` of the rows as the uint32 ``[P, 2]`` array ``ibd_segments``
+        and ``pcrelate_pairs`` take as their list."""
+        return np.stack([self.sample_i, self.sample_j], axis=1).astype(np.uint32)
 
     def sorted(self) -> np.ndarray:
         """The segments by ``(pair, kind, first_site)`` (a copy); ValueError without a list."""
@@ -333,3 +348,149 @@ def ibd_segments_device(ctx, bits, words_per_sample: int, num_sites: int, pairs,
     return IBDPairs(rows_to_host(rows), total,
                     None if segs is None else segments_to_host(segs, found), int(min_sites),
                     int(min_length), int(bridge_sites), *map(bridged_to_host, bridged))
+
+
+# ---- the scan of a block: every pair, no list --------------------------------------------------
+
+def sort_records(rows: np.ndarray) -> np.ndarray:
+    """``IBD_PAIR_DTYPE`` rows by ``(sample_i, sample_j)`` (a copy)."""
+    return np.sort(rows, order=["sample_i", "sample_j"])
+
+
+def _min_total(min_total) -> int:
+    min_total = int(min_total)
+    if not 0 <= min_total < 1 << 64:
+        raise ValueError(f"min_total must be in [0, 2^64), not {min_total}")
+    return min_total
+
+
+def _records_exhausted(count: int):
+    from .api import ResourceExhaustedError
+    e = ResourceExhaustedError(_lib.load().cuking_last_error().decode())
+    e.num_records = count
+    return e
+
+
+def _record_buffer(call, block, max_records, found):
+    """The buffer rule of ``pcrelate_records``: ``call(capacity)`` makes a buffer of ``capacity``
+    records, calls the library and returns ``(buffer, status)``; ``found`` is the ``c_uint64``
+    the library counts into.  Without ``max_records`` the buffer is that call's default (16
+    records per sample of the block) and the call is repeated once with the exact count; with
+    it an overflow raises ``ResourceExhaustedError`` whose ``num_records`` is the exact count."""
+    grow = max_records is None
+    recs, status = call(_default_records(block) if grow else _count(max_records, "max_records"))
+    if status == _lib.ERR_RESOURCE_EXHAUSTED and grow:
+        recs, status = call(int(found.value))
+    if status == _lib.ERR_RESOURCE_EXHAUSTED:
+        raise _records_exhausted(int(found.value))
+    check(status)
+    return recs
+
+
+def ibd_scan_raw_host(bits: np.ndarray, words_per_sample: int, num_sites: int, group=None,
+                      pos=None, min_sites: int = 512, min_length: int = 0, min_total: int = 0,
+                      block=None, max_records=None):
+    """cuking_ibd_scan_host, the bare call: ``(records, count)`` -- the pairs of ``block`` (a
+    ``Submatrix`` or ``(i_begin, i_end, j_begin, j_end)`` over the stored samples; None = all)
+    with a kind-1 segment and ``length1 >= min_total`` as ``IBD_PAIR_DTYPE`` rows in ascending
+    ``(sample_i, sample_j)``, each the bytes ``ibd_segments_raw_host`` gives for that pair.  The
+    buffer rule is ``pcrelate_records_raw_host``'s."""
+    assert bits.dtype == np.uint64 and bits.flags.c_contiguous
+    words_per_sample = _count(words_per_sample, "words_per_sample")
+    num_sites = _count(num_sites, "num_sites")
+    min_sites, min_length = _thresholds(min_sites, min_length)
+    min_total = _min_total(min_total)
+    num_stored = bits.size // words_per_sample if words_per_sample else 0
+    group = _site_array(group, "group", num_sites, np.int32)
+    pos = _site_array(pos, "pos", num_sites, np.uint32)
+    block = _block(block, num_stored)
+    pad = np.zeros(4, dtype=np.uint64)
+    found = C.c_uint64(0)
+
+    def call(capacity):
+        recs = np.zeros(max(capacity, 1), dtype=IBD_PAIR_DTYPE)
+        status = _lib.load().cuking_ibd_scan_host(
+            (bits if bits.size else pad).ctypes.data, num_stored, words_per_sample, num_sites,
+            None if group is None or not group.size else group.ctypes.data,
+            None if pos is None or not pos.size else pos.ctypes.data, min_sites, min_length,
+            C.byref(block.c), min_total, recs.ctypes.data if capacity else None, capacity,
+            C.byref(found))
+        return recs, status
+
+    recs = _record_buffer(call, block, max_records, found)
+    return recs[:found.value].copy(), int(found.value)
+
+
+def ibd_scan_host(bits: np.ndarray, words_per_sample: int, num_sites: int, group=None, pos=None,
+                  min_sites: int = 512, min_length: int = 0, min_total: int = 0, block=None,
+                  max_records=None) -> IBDPairs:
+    """``KingContext.ibd_scan`` on host memory and the host twin: no GPU."""
+    recs, _ = ibd_scan_raw_host(bits, words_per_sample, num_sites, group, pos, min_sites,
+                                min_length, min_total, block, max_records)
+    num_stored = bits.size // words_per_sample if words_per_sample else 0
+    return IBDPairs(recs, genome_length(group, pos, num_sites), None, int(min_sites),
+                    int(min_length), min_total=int(min_total), block=_block(block, num_stored))
+
+
+def records_to_host(records, num_records: int) -> np.ndarray:
+    """The first ``num_records`` rows of the ``[*, 10]`` int32 device tensor of ``ibd_scan_raw``
+    as ``IBD_PAIR_DTYPE`` rows on the host by ``(sample_i, sample_j)`` (waits for the copy)."""
+    return sort_records(rows_to_host(records[:num_records]))
+
+
+def ibd_scan_raw_device(ctx, bits, words_per_sample: int, num_sites: int, group=None, pos=None,
+                        min_sites: int = 512, min_length: int = 0, min_total: int = 0,
+                        block=None, max_records=None, out=None, stream=None):
+    import torch
+    from .api import _device_tensor, _stream_handle
+    words_per_sample = _count(words_per_sample, "words_per_sample")
+    num_sites = _count(num_sites, "num_sites")
+    min_sites, min_length = _thresholds(min_sites, min_length)
+    min_total = _min_total(min_total)
+    num_stored = ctx._rows_of(bits, words_per_sample)
+    dev = f"cuda:{ctx.device}"
+    d_group = _device_sites(ctx, group, "group", num_sites, np.int32)
+    d_pos = _device_sites(ctx, pos, "pos", num_sites, np.uint32)
+    block = _block(block, num_stored)
+    if out is not None:
+        _device_tensor(ctx.device, out, "out", torch.int32, cols=10)
+        max_records = out.shape[0] if max_records is None else max_records
+        if _count(max_records, "max_records") > out.shape[0]:
+            raise ValueError(f"out holds {out.shape[0]} records, max_records is {max_records}")
+    found = C.c_uint64(0)
+    # (uploads ran on the current stream: `stream` waits for them)
+    if stream is not None:
+        stream.wait_stream(torch.cuda.current_stream())
+
+    def call(capacity):
+        recs = out if out is not None else \
+            torch.empty((max(capacity, 1), 10), dtype=torch.int32, device=dev)
+        status = ctx.lib.cuking_ibd_scan(
+            ctx.handle, bits.data_ptr(), num_stored, words_per_sample, num_sites,
+            None if d_group is None or not num_sites else d_group.data_ptr(),
+            None if d_pos is None or not num_sites else d_pos.data_ptr(), min_sites, min_length,
+            C.byref(block.c), min_total, recs.data_ptr() if capacity else None, capacity,
+            C.byref(found), _stream_handle(stream))
+        return recs, status
+
+    recs = _record_buffer(call, block, max_records, found)
+    if stream is not None:  # (converted copies are freed on return)
+        for t in (d_group, d_pos, recs):
+            if t is not None:
+                t.record_stream(stream)
+    return recs, int(found.value)
+
+
+def ibd_scan_device(ctx, bits, words_per_sample: int, num_sites: int, group=None, pos=None,
+                    min_sites: int = 512, min_length: int = 0, min_total: int = 0, block=None,
+                    max_records=None, stream=None) -> IBDPairs:
+    import torch
+    host_group = group.cpu().numpy() if isinstance(group, torch.Tensor) else group
+    host_pos = pos.cpu().numpy().view(np.uint32) if isinstance(pos, torch.Tensor) else pos
+    total = genome_length(host_group, host_pos, num_sites)
+    recs, count = ibd_scan_raw_device(ctx, bits, words_per_sample, num_sites, group, pos,
+                                      min_sites, min_length, min_total, block, max_records,
+                                      stream=stream)
+    return IBDPairs(records_to_host(recs, count), total, None, int(min_sites), int(min_length),
+                    min_total=int(min_total),
+                    block=_block(block, ctx._rows_of(bits, words_per_sample)))

@@ -190,6 +190,26 @@ def parse_args(argv=None):
          help="--ibd-segments-uri also writes the segments themselves: segment_pair (the "
               "record's number), segment_kind, segment_first_site, segment_last_site (site "
               "numbers among the input's sites), sorted")
+    flag("ibd-scan-uri", default="",
+         help="also scan EVERY pair of the cohort for IBD segments, without a list: the pairs "
+              "with a run of at least --ibd-scan-min-sites sites without an opposite homozygote "
+              "(IBD1) whose summed length reaches --ibd-scan-min-total (cuking_amd/ibd.py, "
+              "ibd_scan) -- relatives whose kinship lies below this run's threshold included -- "
+              "written to this .npz: sample_i, sample_j, segments1, segments2, length1, length2, "
+              "longest1, longest2, total_length, pi1, pi2, kin_ibd and relationship, one entry "
+              "per pair found, by (sample_i, sample_j) (with samples, min_sites, min_length, "
+              "min_total).  The scan runs on the bitset the records were computed on, after "
+              "site QC and LD pruning, and takes chromosomes and base-pair positions from the "
+              ".bim under --bed-uri exactly as --ibd-segments-uri does.  One process and "
+              "--split-factor 1 only")
+    flag("ibd-scan-min-sites", type=int, default=None,
+         help="the fewest sites of a segment of --ibd-scan-uri (default 512; at least 64)")
+    flag("ibd-scan-min-length", type=int, default=None,
+         help="the least length of a segment of --ibd-scan-uri, in the .bim's positions "
+              "(default 0)")
+    flag("ibd-scan-min-total", type=int, default=None,
+         help="the least summed length of a pair's IBD1 segments for --ibd-scan-uri to keep the "
+              "pair (default 0: every pair with a segment)")
     flag("roh-uri", default="",
          help="also scan every sample of this run for runs of homozygosity -- the runs of at "
               "least --roh-min-sites sites without a heterozygous call, no allele frequencies "
@@ -383,6 +403,26 @@ def validate(args):  # cuking.cu:437-462
                              "lie inside one 64-site word, which the scan does not enumerate")
         if args.ibd_min_length is not None and not 0 <= args.ibd_min_length < 1 << 32:
             raise UsageError("--ibd_min_length must be in [0, 2^32)")
+    if (args.ibd_scan_min_sites is not None or args.ibd_scan_min_length is not None or
+            args.ibd_scan_min_total is not None) and not args.ibd_scan_uri:
+        raise UsageError("--ibd_scan_min_sites, --ibd_scan_min_length and --ibd_scan_min_total "
+                         "need --ibd_scan_uri")
+    if args.ibd_scan_uri:
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            raise UsageError("--ibd_scan_uri needs one process (one GPU): the pairs are not "
+                             "scanned across ranks yet")
+        if args.split_factor != 1:
+            raise UsageError("--ibd_scan_uri needs --split_factor 1: it scans every pair of the "
+                             "whole cohort's bitset")
+        if args.ibd_scan_min_sites is not None and \
+                not IBD_MIN_SITES <= args.ibd_scan_min_sites < 1 << 32:
+            raise UsageError(f"--ibd_scan_min_sites must be at least {IBD_MIN_SITES} (and below "
+                             "2^32): shorter runs lie inside one 64-site word, which the scan "
+                             "does not enumerate")
+        if args.ibd_scan_min_length is not None and not 0 <= args.ibd_scan_min_length < 1 << 32:
+            raise UsageError("--ibd_scan_min_length must be in [0, 2^32)")
+        if args.ibd_scan_min_total is not None and not 0 <= args.ibd_scan_min_total < 1 << 64:
+            raise UsageError("--ibd_scan_min_total must be in [0, 2^64)")
     if (args.roh_min_sites is not None or args.roh_min_length is not None or
             args.roh_bridge_sites is not None or args.roh_segment_list) and not args.roh_uri:
         raise UsageError("--roh_min_sites, --roh_min_length, --roh_bridge_sites and "
@@ -745,6 +785,26 @@ def write_ibd_segments(path: Path, ctx, bits, wps: int, num_sites: int, recs, gr
                  min_length=np.int64(min_length), **extra)
 
 
+def write_ibd_scan(path: Path, ctx, bits, wps: int, num_sites: int, group, pos, min_sites: int,
+                   min_length: int, min_total: int, sample_ids) -> None:
+    """Every pair of this run scanned for IBD segments as an .npz: `sample_i`, `sample_j`,
+    `segments1`, `segments2`, `length1`, `length2`, `longest1`, `longest2`, `pi1`, `pi2`,
+    `kin_ibd`, `relationship` (one entry per pair with an IBD1 segment and `length1 >=
+    min_total`, by (sample_i, sample_j); the codes of IBDPairs.relationship), `total_length`,
+    `samples`, `min_sites`, `min_length`, `min_total`."""
+    got = ctx.ibd_scan(bits, wps, num_sites, group=group, pos=pos, min_sites=min_sites,
+                       min_length=min_length, min_total=min_total)
+    pi1, pi2, kin = got.proportions()
+    path.parent.mkdir(parents=True, exist_ok=True)
+    with open(path, "wb") as f:   # (np.savez would append .npz to another suffix)
+        np.savez(f, sample_i=got.sample_i, sample_j=got.sample_j, segments1=got.segments1,
+                 segments2=got.segments2, length1=got.length1, length2=got.length2,
+                 longest1=got.longest1, longest2=got.longest2, pi1=pi1, pi2=pi2, kin_ibd=kin,
+                 relationship=got.relationship(), total_length=np.int64(got.total_length),
+                 samples=np.array(list(sample_ids), dtype=str), min_sites=np.int64(min_sites),
+                 min_length=np.int64(min_length), min_total=np.uint64(min_total))
+
+
 def write_roh(path: Path, ctx, bits, wps: int, num_sites: int, group, pos, site_index,
               min_sites: int, min_length: int, bridge_sites: int, with_list: bool,
               sample_ids) -> None:
@@ -851,6 +911,7 @@ def main(argv=None) -> int:
             else None
         ibd_path = resolve_uri(args.ibd_segments_uri) if args.ibd_segments_uri else None
         roh_path = resolve_uri(args.roh_uri) if args.roh_uri else None
+        scan_path = resolve_uri(args.ibd_scan_uri) if args.ibd_scan_uri else None
         synthetic = None
         if args.synthetic:
             parts = [int(x) for x in args.synthetic.split(",")]
@@ -1029,7 +1090,8 @@ def main(argv=None) -> int:
                                            0.0442 if args.pcrelate_min_kinship is None
                                            else args.pcrelate_min_kinship, sample_ids)
             ibd_group = ibd_pos = None
-            if (ibd_path is not None or roh_path is not None) and bed_prefix is not None:
+            if (ibd_path is not None or roh_path is not None or scan_path is not None) and \
+                    bed_prefix is not None:
                 from cuking_amd import plink
                 ibd_group = plink.read_bim_chromosomes(bed_prefix)[site_index]
                 ibd_pos = plink.read_bim_positions(bed_prefix)[site_index]
@@ -1044,6 +1106,13 @@ def main(argv=None) -> int:
                                    512 if args.ibd_min_sites is None else args.ibd_min_sites,
                                    0 if args.ibd_min_length is None else args.ibd_min_length,
                                    args.ibd_segment_list, sample_ids, args.ibd_bridge_sites)
+            if scan_path is not None:
+                write_ibd_scan(scan_path, ctx, bits[:stored], wps, num_sites, ibd_group, ibd_pos,
+                               512 if args.ibd_scan_min_sites is None
+                               else args.ibd_scan_min_sites,
+                               0 if args.ibd_scan_min_length is None
+                               else args.ibd_scan_min_length,
+                               args.ibd_scan_min_total or 0, sample_ids)
             pairs = sm.NumPairs()
             print(json.dumps({"pairs": pairs, "results": int(len(recs)), "gpus": world,
                               "compute_seconds": dt,

@@ -1182,8 +1182,9 @@ cuking_status cuking_pcrelate_pairs(cuking_ctx *ctx, const uint64_t *d_bits, uin
  * this check).  num_pairs == 0 returns OK without work (after the checks of the arguments);
  * num_sites == 0 writes zero rows.
  * One wrong homozygote splits a run; cuking_ibd_pairs_bridged below forgives isolated ones.
- * Out of scope: the C++ `cuking` binary; several ranks; an all-pairs scan; phased IBD;
- * recombination maps beyond an integer pos. */
+ * All pairs of a block, without a list: cuking_ibd_scan ("IBD scan of a block" below).
+ * Out of scope: the C++ `cuking` binary; several ranks; phased IBD; recombination maps beyond an
+ * integer pos. */
 #define CUKING_IBD_MIN_SITES 64
 typedef struct cuking_ibd_pair {
   uint32_t sample_i, sample_j;   /* copied from the input */
@@ -1208,6 +1209,73 @@ cuking_status cuking_ibd_pairs(cuking_ctx *ctx, const uint64_t *d_bits, uint32_t
                                uint32_t pair_stride, cuking_ibd_pair *d_out,
                                cuking_ibd_segment *d_segments, uint64_t max_segments,
                                uint64_t *num_segments, void *stream);
+
+/* IBD scan of a block: the pairs of a block that share a kind-1 segment, found without a list.
+ * The list of "IBD segments for listed pairs" usually is the record buffer of cuking_compute_king
+ * or cuking_pcrelate_records, cut at a threshold on the very average the segments improve on: a
+ * fourth-degree pair with two long shared stretches and a KING kinship of 0.02 never reaches it.
+ * This call looks at every pair, as KING --ibdseg and IBIS do, and keeps the pairs that have
+ * something: it is to cuking_ibd_pairs what cuking_pcrelate_records is to the PC-Relate matrix.
+ *
+ *     bits, num_stored, words_per_sample, num_sites, group, pos, min_sites, min_length
+ *                 exactly as cuking_ibd_pairs takes them; runs, segments and lengths are those
+ *                 of that section and are strict (no bridging); min_sites >= CUKING_IBD_MIN_SITES
+ *     block       exactly as cuking_pcrelate_records takes it: rows x columns of STORED samples
+ *     min_total   uint64 threshold on length1; 0 keeps every pair with a segment
+ *     records     room for max_records cuking_ibd_pair; may be null when max_records == 0
+ *     num_records HOST memory: receives the number of qualifying pairs
+ *
+ * Pairs of a block: a diagonal block (identical ranges) has the pairs i < j, an off-diagonal
+ * block (disjoint ranges, rows first) every pair; the self pair is never a record.
+ * Pair (i, j) is a record iff segments1 >= 1 && length1 >= min_total, length1 being the uint64
+ * sum of the lengths of its kind-1 segments.  The record is the cuking_ibd_pair with sample_i = i
+ * < sample_j = j and, from segments1 on, the same bytes cuking_ibd_pairs[_host] writes for that
+ * pair.  The scan decides nothing of its own: it uses the masks, ibd_starts / ibd_closes /
+ * ibd_open_start / ibd_close_last and ibd_is_segment of csrc/king_ibd.h.  A record does not
+ * depend on the block that holds the pair, on the launch shape, on the stream or on the call.
+ *
+ * EVERY qualifying pair is counted, those whose slot is below max_records are stored, and
+ * *num_records receives the exact count (it starts at zero on every call).  A count above
+ * max_records returns RESOURCE_EXHAUSTED with nothing written past the buffer -- which of the
+ * records were stored is then unspecified on the device, the first max_records on the host --
+ * and the caller retries with exactly *num_records; max_records == 0 with null records is the
+ * counting call.  The ORDER of the records is unspecified on the device and may differ between
+ * calls: the set is the contract.  Host twin: ascending (i, j).  cuking_ibd_scan WAITS for
+ * `stream` once, to read the count back; like cuking_ibd_pairs it waits once more, before the
+ * launch, when pos is given (the check below).
+ *
+ * INVALID_ARGUMENT before any device is touched: a null, reversed or overlapping block, through
+ * the check of cuking_pcrelate_records; everything cuking_ibd_pairs refuses about
+ * words_per_sample, num_sites and min_sites, through its check; a block outside the stored
+ * samples; a null num_records; a null records with max_records != 0; and, with work to do, a
+ * null bits.  FAILED_PRECONDITION for a pos that decreases inside a group, through the check of
+ * cuking_ibd_pairs.  An empty block, a 1 x 1 diagonal block and num_sites == 0 give 0 records
+ * and OK.
+ *
+ * A screen for the bridged call.  Every run of a chain that cuking_ibd_pairs_bridged links has at
+ * least bridge_sites sites, and an unlinked segment has at least min_sites >= bridge_sites sites.
+ * So for B >= 64 a scan at min_sites = B, min_length = 0, min_total = 0 records EVERY pair for
+ * which the bridged call reports a kind-1 segment, for any bridge_sites = B, any min_sites >= B
+ * and any min_length: scan loosely, then give the records' pairs to the bridged call.
+ *
+ * Device: one workgroup per 32 x 32 tile of pairs, the samples' words staged through LDS once per
+ * tile, only the tiles tile_j >= tile_i of a diagonal block (csrc/king_ibd_scan.hip).  Memory is
+ * the record buffer, one counter and the group mask: nothing proportional to the pairs.
+ * Out of scope: bridging inside the scan; a segment list from the scan (cuking_ibd_pairs with a
+ * segment list on the records gives it); the C++ `cuking` binary; several ranks; a threshold on
+ * kind 2. */
+cuking_status cuking_ibd_scan_host(const uint64_t *bits, uint32_t num_stored,
+                                   uint32_t words_per_sample, uint32_t num_sites,
+                                   const int32_t *group, const uint32_t *pos, uint32_t min_sites,
+                                   uint32_t min_length, const cuking_submatrix *block,
+                                   uint64_t min_total, cuking_ibd_pair *records,
+                                   uint64_t max_records, uint64_t *num_records);
+cuking_status cuking_ibd_scan(cuking_ctx *ctx, const uint64_t *d_bits, uint32_t num_stored,
+                              uint32_t words_per_sample, uint32_t num_sites,
+                              const int32_t *d_group, const uint32_t *d_pos, uint32_t min_sites,
+                              uint32_t min_length, const cuking_submatrix *block,
+                              uint64_t min_total, cuking_ibd_pair *d_records,
+                              uint64_t max_records, uint64_t *num_records, void *stream);
 
 /* IBD segments with bridged breaks: the call above, tolerant of sparse genotyping errors.  On
  * real calls with 0.1 - 1 % discordance a single wrong homozygote cuts a true IBD stretch into
