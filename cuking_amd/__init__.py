@@ -25,5 +25,7 @@ from .ibd import (IBD_PAIR_DTYPE, IBD_SEGMENT_DTYPE, IBDPairs, genome_length,  #
                   ibd_scan_host, ibd_scan_raw_host, ibd_segments_host, ibd_segments_raw_host)
 from .roh import (ROH_SAMPLE_DTYPE, ROHSamples, roh_segments_host,  # noqa: F401
                   roh_segments_raw_host)
+from .mendel import (MENDEL_TRIO_DTYPE, NO_PARENT, MendelErrors, candidate_trios,  # noqa: F401
+                     mendel_errors_host, mendel_errors_raw_host, trios_from_parents)
 
 __version__ = "0.1.0"

@@ -1309,6 +1309,34 @@ class KingContext:
                                         pos, min_sites, min_length, bridge_sites, segments,
                                         max_segments, stream)
 
+    def mendel_errors_raw(self, bits, words_per_sample: int, num_sites: int, trios,
+                          error_bits=None, out=None, stream=None):
+        """The bare kernel call for Mendelian errors (cuking_mendel_trios; include/cuking_amd.h
+        "Mendelian errors" has the definition and the table of the eight codes): for every
+        ``(child, father, mother)`` of ``trios`` (an integer ``[T, 3]`` host array or int32
+        device tensor; ``mendel.NO_PARENT`` for an absent parent; repeats, any order and shared
+        parents allowed) the sites with each error code and the called sites.  Returns ``(rows,
+        error_bits)``: an int32 ``[T, 12]`` device tensor, one cuking_mendel_trio per row in
+        list order (``mendel.rows_to_host`` gives it names; ``out``: such a tensor to write
+        into), and -- with ``error_bits`` True or an int64 ``[T, words_per_sample / 2]`` device
+        tensor -- the error mask of every trio, which ``mendel.site_counts_device`` sums per
+        site; else None.  Does not synchronise."""
+        from . import mendel as _mendel
+        return _mendel.mendel_errors_raw_device(self, bits, words_per_sample, num_sites, trios,
+                                                error_bits, out, stream)
+
+    def mendel_errors(self, bits, words_per_sample: int, num_sites: int, trios,
+                      site_counts: bool = False, stream=None, _chunk_trios=None):
+        """Mendelian errors of the listed trios and duos as a ``MendelErrors`` of host arrays
+        (arguments as ``mendel_errors_raw`` takes them): ``errors`` ``[T, 8]`` by PLINK's and
+        Hail's codes, ``called``, ``total()``, ``rate()`` and ``per_sample()``; with
+        ``site_counts`` also ``site_errors``, the number of listed trios with an error at each
+        site.  The error mask behind the site counts goes through one buffer of at most 64 MB
+        in chunks of trios, which does not change the result.  Waits for the device."""
+        from . import mendel as _mendel
+        return _mendel.mendel_errors_device(self, bits, words_per_sample, num_sites, trios,
+                                            site_counts, stream, _chunk_trios)
+
     def synth_bitset(self, seed: int, kind, pa, pb, sample_begin: int,
                      sample_end: int, num_sites: int, out=None, stream=None, model=0):
         """Synthetic reference-layout bitset rows [sample_begin, sample_end)

@@ -2348,6 +2348,38 @@ cuking_status cuking_roh_samples(cuking_ctx *ctx, const uint64_t *d_bits, uint32
       });
 }
 
+// ---- Mendelian errors (king_mendel.hip) -----------------------------------------
+cuking_status cuking_mendel_trios(cuking_ctx *ctx, const uint64_t *d_bits, uint32_t num_stored,
+                                  uint32_t words_per_sample, uint32_t num_sites,
+                                  const uint32_t *d_trios, uint64_t num_trios,
+                                  cuking_mendel_trio *d_out, uint64_t *d_error_bits,
+                                  void *stream) {
+  // (the arguments first: a refused call touches no device)
+  if (ctx == nullptr) return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "null context");
+  const cuking_status st =
+      cuking_check_mendel_args(d_bits, words_per_sample, num_sites, d_trios, num_trios, d_out);
+  if (st != CUKING_OK) return st;
+  if (num_trios == 0) return CUKING_OK;
+  BIND_OR_RETURN(ctx);
+  HIP_TRY(launch_mendel_trios(d_bits, num_stored, words_per_sample, num_sites, d_trios, num_trios,
+                              d_out, d_error_bits, (hipStream_t)stream));
+  return CUKING_OK;
+}
+
+cuking_status cuking_mendel_site_counts(cuking_ctx *ctx, const uint64_t *d_error_bits,
+                                        uint64_t num_trios, uint32_t plane_words,
+                                        uint32_t *d_counts, void *stream) {
+  if (ctx == nullptr) return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "null context");
+  const cuking_status st =
+      cuking_check_mendel_site_args(d_error_bits, num_trios, plane_words, d_counts);
+  if (st != CUKING_OK) return st;
+  if (num_trios == 0) return CUKING_OK;
+  BIND_OR_RETURN(ctx);
+  HIP_TRY(launch_mendel_site_counts(d_error_bits, num_trios, plane_words, d_counts,
+                                    (hipStream_t)stream));
+  return CUKING_OK;
+}
+
 cuking_status cuking_ibd_pairs(cuking_ctx *ctx, const uint64_t *d_bits, uint32_t num_stored,
                                uint32_t words_per_sample, uint32_t num_sites,
                                const int32_t *d_group, const uint32_t *d_pos, uint32_t min_sites,

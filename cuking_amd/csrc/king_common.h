@@ -816,6 +816,17 @@ hipError_t launch_roh_samples(const uint64_t *d_bits, uint32_t num_stored,
                               cuking_roh_sample *d_out, cuking_ibd_segment *d_segments,
                               uint64_t max_segments, unsigned long long *d_count,
                               hipStream_t stream);
+// Mendelian errors (king_mendel.hip; arguments already checked): one 48-byte row per listed trio
+// and, with d_error_bits, the error mask [num_trios][words_per_sample / 2]; and the column sums of
+// such a mask, ADDED to d_counts [64 plane_words].
+hipError_t launch_mendel_trios(const uint64_t *d_bits, uint32_t num_stored,
+                               uint32_t words_per_sample, uint32_t num_sites,
+                               const uint32_t *d_trios, uint64_t num_trios,
+                               cuking_mendel_trio *d_out, uint64_t *d_error_bits,
+                               hipStream_t stream);
+hipError_t launch_mendel_site_counts(const uint64_t *d_error_bits, uint64_t num_trios,
+                                     uint32_t plane_words, uint32_t *d_counts,
+                                     hipStream_t stream);
 
 // Cohort models of the synthetic generator (synth.hip holds the specification).  d_tables:
 // synth_table_bytes() of scratch the launch fills and reads (per-site and per-sample

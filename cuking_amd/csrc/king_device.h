@@ -31,6 +31,30 @@ __device__ __forceinline__ T relaxed_add(T *p, V v) {  // returns the value befo
   return __hip_atomic_fetch_add(p, (T)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// Integer reductions over the 64 lanes of a wavefront, every lane gets the result (the IBD, ROH
+// and Mendel kernels: king_ibd.hip, king_mendel.hip).  Integers: the order does not matter.
+__device__ __forceinline__ uint32_t ibd_wave_sum(uint32_t v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+  return v;
+}
+__device__ __forceinline__ uint32_t ibd_wave_max(uint32_t v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const uint32_t other = __shfl_xor(v, off);
+    v = other > v ? other : v;
+  }
+  return v;
+}
+__device__ __forceinline__ uint64_t ibd_wave_sum64(uint64_t v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const uint32_t lo = __shfl_xor((uint32_t)v, off), hi = __shfl_xor((uint32_t)(v >> 32), off);
+    v += (uint64_t)hi << 32 | lo;
+  }
+  return v;
+}
+
 // s_waitcnt vmcnt(N) immediate for N requests that may stay in flight.
 constexpr int vmcnt_imm(int n) { return 0x0F70 | (n & 15) | ((n >> 4) << 14); }
 

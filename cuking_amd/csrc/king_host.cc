@@ -23,6 +23,7 @@
 #include "king_ibd.h"
 #include "king_kin_summary.h"
 #include "king_ld.h"
+#include "king_mendel.h"
 #include "king_pcrelate.h"
 #include "king_unrelated.h"
 
@@ -1344,6 +1345,95 @@ cuking_status cuking_ibd_scan_host(const uint64_t *bits, uint32_t num_stored,
     }
   *num_records = count;
   return cuking_ibd_scan_count_status(count, max_records);
+}
+
+}  // extern "C"
+
+// ---- Mendelian errors --------------------------------------------------------------------------
+cuking_status cuking_check_mendel_args(const void *bits, uint32_t words_per_sample,
+                                       uint32_t num_sites, const void *trios, uint64_t num_trios,
+                                       const void *out) {
+  if (words_per_sample == 0 || (words_per_sample & 1))
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT,
+                       "words_per_sample (%u) must be a positive even number", words_per_sample);
+  if (num_sites > 64ull * (words_per_sample / 2))
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT,
+                       "mendel trios: %u sites do not fit %u plane words (%llu bits)", num_sites,
+                       words_per_sample / 2, 64ull * (words_per_sample / 2));
+  if (num_trios == 0) return CUKING_OK;
+  if (out == nullptr)
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "mendel trios: null out pointer");
+  if (trios == nullptr)
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "mendel trios: null trios pointer");
+  if (num_sites != 0 && bits == nullptr)
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "mendel trios: null bits pointer");
+  return CUKING_OK;
+}
+
+cuking_status cuking_check_mendel_site_args(const void *error_bits, uint64_t num_trios,
+                                            uint32_t plane_words, const void *counts) {
+  if (plane_words == 0)
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT,
+                       "mendel site counts: the mask must have at least one word per trio");
+  if (num_trios >= (1ull << 32))
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT,
+                       "mendel site counts: a count has 32 bits, %llu trios are too many for one "
+                       "call", (unsigned long long)num_trios);
+  if (num_trios != 0 && (error_bits == nullptr || counts == nullptr))
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "mendel site counts: null pointer");
+  return CUKING_OK;
+}
+
+extern "C" {
+
+// The words of a trio, one at a time, with the functions of king_mendel.h.
+cuking_status cuking_mendel_trios_host(const uint64_t *bits, uint32_t num_stored,
+                                       uint32_t words_per_sample, uint32_t num_sites,
+                                       const uint32_t *trios, uint64_t num_trios,
+                                       cuking_mendel_trio *out, uint64_t *error_bits) {
+  const cuking_status st =
+      cuking_check_mendel_args(bits, words_per_sample, num_sites, trios, num_trios, out);
+  if (st != CUKING_OK) return st;
+  const uint32_t plane_words = words_per_sample / 2;
+  for (uint64_t t = 0; t < num_trios; ++t) {
+    const uint32_t who[3] = {trios[3 * t], trios[3 * t + 1], trios[3 * t + 2]};
+    cuking_mendel_trio row = {};
+    row.child = who[0];
+    row.father = who[1];
+    row.mother = who[2];
+    for (uint32_t w = 0; w < plane_words; ++w) {
+      const uint64_t valid = ibd_valid_mask(num_sites, w);
+      MendelWord x[3];  // child, father, mother; an absent sample stays missing everywhere
+      for (int k = 0; k < 3; ++k)
+        if (valid != 0 && who[0] < num_stored && who[k] < num_stored) {
+          const uint64_t *r = bits + (uint64_t)who[k] * words_per_sample;
+          x[k] = mendel_word(r[w], r[plane_words + w], valid);
+        }
+      uint64_t code[kMendelCodes], any = 0;
+      mendel_code_masks(x[1], x[2], x[0], code);
+      for (uint32_t k = 0; k < kMendelCodes; ++k) {
+        row.errors[k] += (uint32_t)__builtin_popcountll(code[k]);
+        any |= code[k];
+      }
+      row.called += (uint32_t)__builtin_popcountll(
+          mendel_called(x[1], who[1] != kMendelNoParent, x[2], who[2] != kMendelNoParent, x[0]));
+      if (error_bits != nullptr) error_bits[t * plane_words + w] = any;
+    }
+    out[t] = row;
+  }
+  return CUKING_OK;
+}
+
+cuking_status cuking_mendel_site_counts_host(const uint64_t *error_bits, uint64_t num_trios,
+                                             uint32_t plane_words, uint32_t *counts) {
+  const cuking_status st =
+      cuking_check_mendel_site_args(error_bits, num_trios, plane_words, counts);
+  if (st != CUKING_OK) return st;
+  for (uint64_t t = 0; t < num_trios; ++t)
+    for (uint32_t w = 0; w < plane_words; ++w)
+      for (uint64_t x = error_bits[t * plane_words + w]; x != 0; x &= x - 1)
+        ++counts[(uint64_t)w * 64 + (uint32_t)__builtin_ctzll(x)];
+  return CUKING_OK;
 }
 
 }  // extern "C"

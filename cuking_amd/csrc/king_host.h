@@ -101,5 +101,13 @@ cuking_status cuking_check_ibd_scan_args(const void *bits, uint32_t num_stored,
                                          const void *records, uint64_t max_records,
                                          const void *num_records);
 cuking_status cuking_ibd_scan_count_status(uint64_t count, uint64_t max_records);
+// Argument checks of cuking_mendel_trios_host / cuking_mendel_trios and of
+// cuking_mendel_site_counts_host / cuking_mendel_site_counts (include/cuking_amd.h "Mendelian
+// errors" lists them); OK says nothing about there being work to do.
+cuking_status cuking_check_mendel_args(const void *bits, uint32_t words_per_sample,
+                                       uint32_t num_sites, const void *trios, uint64_t num_trios,
+                                       const void *out);
+cuking_status cuking_check_mendel_site_args(const void *error_bits, uint64_t num_trios,
+                                            uint32_t plane_words, const void *counts);
 
 #endif  // CUKING_AMD_KING_HOST_H_

@@ -204,27 +204,8 @@ __device__ __forceinline__ void ibd_kind_step(const IbdArgsOf<kBridge> &a, uint3
   k.edge = __shfl(last, 63);
 }
 
-__device__ __forceinline__ uint32_t ibd_wave_sum(uint32_t v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  return v;
-}
-__device__ __forceinline__ uint32_t ibd_wave_max(uint32_t v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const uint32_t other = __shfl_xor(v, off);
-    v = other > v ? other : v;
-  }
-  return v;
-}
-__device__ __forceinline__ uint64_t ibd_wave_sum64(uint64_t v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const uint32_t lo = __shfl_xor((uint32_t)v, off), hi = __shfl_xor((uint32_t)(v >> 32), off);
-    v += (uint64_t)hi << 32 | lo;
-  }
-  return v;
-}
+// (ibd_wave_sum, ibd_wave_max and ibd_wave_sum64 live in king_device.h: king_mendel.hip uses them
+//  too)
 
 template <bool kBridge>
 __global__ __launch_bounds__(kIbdThreads) void ibd_pairs_kernel(const IbdArgsOf<kBridge> a) {

@@ -50,6 +50,36 @@ def read_fam(prefix) -> list:
     return ids
 
 
+def read_fam_parents(prefix) -> np.ndarray:
+    """The parents `PREFIX.fam` declares, as `int64 [n, 2]`: the row index (file order, the order
+    of `read_fam`) of each sample's father and mother, -1 for "0" and for an id that is not in
+    the file.  Ids are matched by IID when the IIDs are all distinct, else within the sample's
+    FID -- the rule by which `read_fam` makes ids distinct (and its ValueError if they are not).
+    `mendel.trios_from_parents` turns the result into a list of trios."""
+    rows = []
+    with open(_path(prefix, ".fam")) as f:
+        for number, line in enumerate(f, 1):
+            fields = line.split()
+            if not fields:
+                continue
+            if len(fields) < 4:
+                raise ValueError(f"{_path(prefix, '.fam')}:{number}: expected FID, IID, father "
+                                 "and mother")
+            rows.append(fields[:4])
+    by_iid = len({r[1] for r in rows}) == len(rows)
+    key = (lambda fid, iid: iid) if by_iid else (lambda fid, iid: (fid, iid))
+    index = {key(r[0], r[1]): k for k, r in enumerate(rows)}
+    if len(index) != len(rows):
+        raise ValueError(f"{_path(prefix, '.fam')}: sample ids are not distinct, neither as IID "
+                         "nor as FID_IID")
+    parents = np.full((len(rows), 2), -1, dtype=np.int64)
+    for k, (fid, _, father, mother) in enumerate(rows):
+        for column, who in enumerate((father, mother)):
+            if who != "0":
+                parents[k, column] = index.get(key(fid, who), -1)
+    return parents
+
+
 def count_sites(prefix) -> int:
     """The number of lines (variants) of `PREFIX.bim`."""
     n = 0

@@ -231,6 +231,23 @@ def parse_args(argv=None):
     flag("roh-segment-list", action="store_true",
          help="--roh-uri also writes the runs themselves: seg_sample, seg_first_site, "
               "seg_last_site (site numbers among the input's sites), sorted")
+    flag("mendel-uri", default="",
+         help="also count the Mendelian errors of trios and duos -- the sites at which a child's "
+              "genotype cannot come from its parents', by the eight autosomal codes of plink "
+              "--mendel and hl.mendel_errors (cuking_amd/mendel.py) -- and write them to this "
+              ".npz: child, father, mother (sample numbers, -1 for an absent parent), called, "
+              "errors [T, 8], rate (errors over called), per_sample (the errors that implicate "
+              "each sample, PLINK's .imendel rule) and samples.  The trios are those the .fam "
+              "under --bed-uri declares, or --mendel-trios.  The count runs on the bitset the "
+              "records were computed on, after site QC and LD pruning.  One process and "
+              "--split-factor 1 only")
+    flag("mendel-trios", default="",
+         help="the trios of --mendel-uri: a .npy with an integer [T, 3] array of (child, father, "
+              "mother) sample numbers, -1 for an absent parent (required unless --bed-uri names a "
+              ".fam that declares parents)")
+    flag("mendel-site-counts", action="store_true",
+         help="--mendel-uri also writes site_errors, the number of listed trios with an error "
+              "at each site, and site_index, the sites' numbers among the input's sites")
     flag("pcrelate-min-kinship", type=float, default=None,
          help="the threshold of --pcrelate-records-uri: pairs with a kinship strictly above it "
               "(default 0.0442, the third-degree cut-off)")
@@ -445,6 +462,18 @@ def validate(args):  # cuking.cu:437-462
             raise UsageError(f"--roh_bridge_sites must be 0 or at least {IBD_MIN_SITES} (and "
                              "below 2^32): shorter runs lie inside one 64-site word, which the "
                              "scan does not enumerate")
+    if (args.mendel_trios or args.mendel_site_counts) and not args.mendel_uri:
+        raise UsageError("--mendel_trios and --mendel_site_counts need --mendel_uri")
+    if args.mendel_uri:
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            raise UsageError("--mendel_uri needs one process (one GPU): the trios are not "
+                             "counted across ranks yet")
+        if args.split_factor != 1:
+            raise UsageError("--mendel_uri needs --split_factor 1: it reads the samples of the "
+                             "whole cohort's bitset")
+        if not args.mendel_trios and not args.bed_uri:
+            raise UsageError("--mendel_uri needs --mendel_trios: only the .fam under --bed_uri "
+                             "declares parents")
     if args.pcrelate_min_kinship is not None and not args.pcrelate_records_uri:
         raise UsageError("--pcrelate_min_kinship needs --pcrelate_records_uri")
     if args.pcrelate_records_uri:
@@ -829,6 +858,59 @@ def write_roh(path: Path, ctx, bits, wps: int, num_sites: int, group, pos, site_
                  min_length=np.int64(min_length), bridge_sites=np.int64(bridge_sites), **extra)
 
 
+def load_mendel_trios(trios_path, bed_prefix, num_samples):
+    """The trios of --mendel-uri as uint32 [T, 3] with NO_PARENT for an absent parent: the .npy of
+    --mendel-trios, else what the .fam declares.  Host only; UsageError for what the user got
+    wrong.  `num_samples`: the cohort's size where it is known by now, else None."""
+    from cuking_amd import mendel, plink
+    if trios_path is None:
+        try:
+            trios = mendel.trios_from_parents(plink.read_fam_parents(bed_prefix))
+        except (OSError, ValueError) as e:
+            raise UsageError(f"--mendel_uri: {e}") from e
+        if len(trios) == 0:
+            raise UsageError(f"--mendel_uri: {bed_prefix}.fam declares no parent that is in the "
+                             "file: pass the trios with --mendel_trios")
+        return trios
+    try:
+        listed = np.load(trios_path, allow_pickle=False)
+    except (OSError, ValueError) as e:
+        raise UsageError(f"--mendel_trios: cannot read {trios_path}: {e}") from e
+    if listed.ndim != 2 or listed.shape[1] != 3 or listed.dtype.kind not in "iu":
+        raise UsageError(f"--mendel_trios must hold an integer [T, 3] array, not {listed.dtype} "
+                         f"{listed.shape}")
+    listed = listed.astype(np.int64)
+    limit = mendel.NO_PARENT if num_samples is None else num_samples
+    if listed.size and (int(listed.min()) < -1 or int(listed.max()) >= limit or
+                        int(listed[:, 0].min(initial=0)) < 0):
+        raise UsageError("--mendel_trios must hold sample numbers below the cohort's size"
+                         f"{'' if num_samples is None else f' ({num_samples})'}, -1 for an "
+                         "absent parent only")
+    return np.where(listed < 0, mendel.NO_PARENT, listed).astype(np.uint32)
+
+
+def write_mendel(path: Path, ctx, bits, wps: int, num_sites: int, trios, with_sites: bool,
+                 site_index, sample_ids) -> None:
+    """The Mendelian errors of the listed trios as an .npz: `child`, `father`, `mother` (int64,
+    -1 for an absent parent), `called`, `errors` [T, 8], `rate`, `per_sample` (one entry per
+    sample of the cohort), `samples`; with `with_sites` also `site_errors` (one entry per site of
+    the bitset) and `site_index` (those sites' numbers among the input's sites)."""
+    from cuking_amd import mendel
+    got = ctx.mendel_errors(bits, wps, num_sites, trios, site_counts=with_sites)
+    extra = {}
+    if with_sites:
+        extra = dict(site_errors=got.site_errors, site_index=np.asarray(site_index))
+
+    def number(who):
+        return np.where(who == mendel.NO_PARENT, -1, who.astype(np.int64))
+    path.parent.mkdir(parents=True, exist_ok=True)
+    with open(path, "wb") as f:   # (np.savez would append .npz to another suffix)
+        np.savez(f, child=number(got.child), father=number(got.father),
+                 mother=number(got.mother), called=got.called, errors=got.errors,
+                 rate=got.rate(), per_sample=got.per_sample(len(sample_ids)),
+                 samples=np.array(list(sample_ids), dtype=str), **extra)
+
+
 def site_qc(ctx, args, bits, wps: int, num_sites: int, sample_ids, keep_path, qc_path):
     """Site QC of the whole cohort's bitset: counts on the GPU, the rule on the host, the
     report if one is asked for, and -- with a flag that selects sites -- the compacted bitset.
@@ -925,6 +1007,18 @@ def main(argv=None) -> int:
                 raise UsageError(f"Illegal value '{args.synthetic_model}' specified for flag "
                                  "'synthetic_model'")
             synth_model = names.index(args.synthetic_model)
+        mendel_path = resolve_uri(args.mendel_uri) if args.mendel_uri else None
+        mendel_trios = None
+        if mendel_path is not None:   # (host only: a bad list is a usage error, before any GPU)
+            known = synthetic[0] if synthetic else None
+            if known is None and bed_prefix is not None:
+                from cuking_amd import plink
+                try:
+                    known = len(plink.read_fam(bed_prefix))
+                except (OSError, ValueError) as e:
+                    raise UsageError(f"--mendel_uri: {e}") from e
+            mendel_trios = load_mendel_trios(
+                resolve_uri(args.mendel_trios) if args.mendel_trios else None, bed_prefix, known)
     except ValueError:
         if rank == 0:
             print("\nError: INVALID_ARGUMENT: --synthetic expects N,M[,seed]", file=sys.stderr)
@@ -1100,6 +1194,9 @@ def main(argv=None) -> int:
                           site_index, 512 if args.roh_min_sites is None else args.roh_min_sites,
                           0 if args.roh_min_length is None else args.roh_min_length,
                           args.roh_bridge_sites or 0, args.roh_segment_list, sample_ids)
+            if mendel_path is not None:
+                write_mendel(mendel_path, ctx, bits[:stored], wps, num_sites, mendel_trios,
+                             args.mendel_site_counts, site_index, sample_ids)
             if ibd_path is not None:
                 write_ibd_segments(ibd_path, ctx, bits[:stored], wps, num_sites, recs, ibd_group,
                                    ibd_pos, site_index,

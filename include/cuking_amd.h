@@ -1399,6 +1399,79 @@ cuking_status cuking_roh_samples(cuking_ctx *ctx, const uint64_t *d_bits, uint32
                                  cuking_roh_sample *d_out, cuking_ibd_segment *d_segments,
                                  uint64_t max_segments, uint64_t *num_segments, void *stream);
 
+/* Mendelian errors: the sites at which a child's genotype cannot come from its parents'
+ * (plink --mendel, hl.mendel_errors, the trio check of KING --build and of gnomAD's sample QC),
+ * counted per trio or duo and per site on the bitset where it lies.  The counts confirm or reject
+ * a declared or inferred trio, point at the sample that is wrong, and name the sites that are.
+ * Integers only: host twin and kernel agree byte for byte (csrc/king_mendel.h is the definition as
+ * code, mendel_code_masks, used by both and by the tests).
+ *
+ * Per sample and word, with valid = ibd_valid_mask(num_sites, w) (the codes of the bitset as under
+ * "Runs of homozygosity"):
+ *     R = ~het & ~hom & valid   hom-ref
+ *     H =  het & ~hom & valid   het
+ *     V =  hom & ~het & valid   hom-var
+ *     C = R | H | V             called
+ * A parent that is absent reads as missing everywhere (R = H = V = 0): its index is
+ * CUKING_MENDEL_NO_PARENT, or a listed index >= num_stored, which loads nothing.  The error codes
+ * carry the numbers of PLINK and Hail, autosomal only (f father, m mother, c child):
+ *     code   father   mother   child
+ *       1      R        R        H
+ *       2      V        V        H
+ *       3      V      not V      R
+ *       4    not V      V        R
+ *       5      V        V        R
+ *       6      R      not R      V
+ *       7    not R      R        V
+ *       8      R        R        V
+ * "not V" and "not R" include missing and absent, so a duo with a father can only show codes 3 and
+ * 6 and a duo with a mother only 4 and 7.  The eight masks are pairwise disjoint; their OR is the
+ * error mask of the trio and word.  Bits at or beyond num_sites never matter (all-ones and
+ * all-zero padding give the same bytes).
+ *
+ * cuking_mendel_trios:
+ *     trios       uint32 [num_trios][3]: child, father, mother.  Repeats, any order, shared parents,
+ *                 a child that is its own parent are all legal
+ *     out         one cuking_mendel_trio of 48 bytes per listed trio, in list order, plain stores:
+ *                 the three indices echoed, errors[k] = the number of sites with code k + 1, and
+ *                 called = the number of sites where the child and every parent whose index is not
+ *                 CUKING_MENDEL_NO_PARENT are called (a listed parent >= num_stored: 0).  A child
+ *                 >= num_stored gives zeros.  A row depends on its own three indices only
+ *     error_bits  null, or uint64 [num_trios][W], W = words_per_sample / 2: the error mask of
+ *                 every trio and word (zero at and beyond num_sites), plain stores
+ * Refused with INVALID_ARGUMENT: a null context (device form), words_per_sample zero or odd,
+ * num_sites > 64 W, and with num_trios != 0 a null trios, out or (num_sites != 0) bits pointer.
+ * num_trios == 0 is no work.  No atomics: the result cannot depend on timing or launch shape.  The
+ * device call is asynchronous on its stream, with or without error_bits.
+ *
+ * cuking_mendel_site_counts ADDS, for every plane site 0 .. 64 W - 1, the number of the num_trios
+ * rows of error_bits (uint64 [num_trios][W]) whose bit is set to counts (uint32 [64 W]): like
+ * cuking_site_counts it accumulates, so chunks of trios merge by sum.  Refused: a null context, W
+ * == 0, num_trios >= 2^32 (a count has 32 bits), and with num_trios != 0 a null pointer.
+ * Asynchronous on its stream.
+ * Out of scope: X, Y and haploid codes 9-12; setting erroneous genotypes to missing; sex; more
+ * than one generation; per-error rows; several ranks. */
+#define CUKING_MENDEL_NO_PARENT 0xFFFFFFFFu
+typedef struct cuking_mendel_trio {
+  uint32_t child, father, mother; /* as listed */
+  uint32_t called;                /* sites where everyone who is not NO_PARENT is called */
+  uint32_t errors[8];             /* errors[k]: sites with code k + 1 */
+} cuking_mendel_trio;             /* 48 bytes */
+cuking_status cuking_mendel_trios_host(const uint64_t *bits, uint32_t num_stored,
+                                       uint32_t words_per_sample, uint32_t num_sites,
+                                       const uint32_t *trios, uint64_t num_trios,
+                                       cuking_mendel_trio *out, uint64_t *error_bits);
+cuking_status cuking_mendel_trios(cuking_ctx *ctx, const uint64_t *d_bits, uint32_t num_stored,
+                                  uint32_t words_per_sample, uint32_t num_sites,
+                                  const uint32_t *d_trios, uint64_t num_trios,
+                                  cuking_mendel_trio *d_out, uint64_t *d_error_bits,
+                                  void *stream);
+cuking_status cuking_mendel_site_counts_host(const uint64_t *error_bits, uint64_t num_trios,
+                                             uint32_t plane_words, uint32_t *counts);
+cuking_status cuking_mendel_site_counts(cuking_ctx *ctx, const uint64_t *d_error_bits,
+                                        uint64_t num_trios, uint32_t plane_words,
+                                        uint32_t *d_counts, void *stream);
+
 /* cuking.cu:761-765 on host memory: sort by (sample_i, sample_j, kin). */
 void cuking_sort_results(cuking_result *results, size_t num_results);
 
