@@ -609,7 +609,7 @@ cuking_status launch_args(cuking_ctx *ctx, hipStream_t stream, const cuking_subm
   a.rotate_min_steps = ctx->filter_rotate_min_steps;
   a.check_steps = plane_check_steps(ctx->planes, geo);
   if (ctx->prepared.site_order) a.site_curve = plane_site_curve(ctx->planes, geo);
-  a.site_rotate = ctx->filter_site_order == 2;
+  a.site_lap = ctx->filter_site_order == 2 || (ctx->filter_site_order == -1 && kSiteOrderAutoLap);
   return CUKING_OK;
 }
 

@@ -307,9 +307,11 @@ struct TiledArgs {
   // pair, and this is the cohort's measured curve (SiteCurve) the filter kernel takes the
   // share in front of its rigorous check from.  nullptr: stored order, the linear rule.
   const struct SiteCurve *site_curve;
-  // ("filter_site_order" 2, a measurement switch: the tiles of such a layout ARE rotated, each
-  //  takes the share of the range it covers from the curve -- king_filter.hip plan_checks)
-  uint32_t site_rotate;
+  // (1: a launch of such a layout that "filter_rotate" 1 would rotate keeps that switch, its
+  //  tiles rotate inside the head of the order -- king_filter.hip plan_checks, "head lap";
+  //  0: launch_filter turns that rotation off.  "filter_site_order" 2, and -1 by
+  //  kSiteOrderAutoLap below)
+  uint32_t site_lap;
 };
 
 // Prefix statistics: the k-steps (of 256 sites) a check may sit behind, as shares of the
@@ -352,6 +354,9 @@ __host__ __device__ inline uint32_t phase_step(uint32_t all_steps, uint32_t x) {
 constexpr uint64_t kSiteOrderMinTiles = 24576;
 constexpr uint32_t kSiteOrderMinGain = 2;
 constexpr uint32_t kSiteOrderNoTrust = 15;  // conversions of a block that trust its last "no"
+// Automatic mode takes the head lap (king_filter.hip plan_checks) wherever it takes the order
+// and the launch would rotate a stored-order layout: profiles/r20_head_lap.txt.
+constexpr bool kSiteOrderAutoLap = true;
 struct SiteCurve {
   unsigned long long cum[kNumPhases];
   unsigned long long het_calls, missing_calls;

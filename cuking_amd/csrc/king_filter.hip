@@ -71,9 +71,12 @@
 // sites sorted by what they add to X of unrelated pairs.  Nothing in the k loop, the epilogue
 // or the refine kernel knows: the sums are over all sites either way.  Only the SHARE in front
 // of the rigorous check changes -- taken from the cohort's measured curve (launch_verdict,
-// plan_checks) instead of the linear rule -- and such a layout's tiles are not rotated
-// (launch_filter; rotated tiles on such a layout were measured slower than stored order).
-// configs[2]: 125.2 -> 118.1 ms per step, profiles/r18_site_order.txt.
+// plan_checks) instead of the linear rule -- and where a tile of such a layout rotates: not
+// around the end of the sites (that starts a tile on the light sites: measured slower than
+// stored order) but inside the head of the order, the sites in front of the check (plan_checks,
+// "head lap"; launch_filter says which launches take it).
+// configs[2]: 125.2 -> 118.1 ms per step, profiles/r18_site_order.txt; the head lap:
+// profiles/r20_head_lap.txt.
 //
 // Workgroup = 256 x 256 pairs, 4 wavefronts of 128 x 128 = 4 x 4 MFMA blocks (256
 // accumulator registers), k-step = 256 sites = 4 slices of 64, 5 LDS stages of
@@ -330,17 +333,12 @@ __device__ __forceinline__ bool take_tile(const TiledArgs &a, const uint32_t wg,
 // that has not set its tile_done flag.  The worst case costs the exact kernel's time
 // plus the first round of this one (short launches: plus an eighth of it, check 0).
 // *xcd_pos: the k-step the tiles of this XCD are at (rotated tiles, plan_checks()).
-// *order_share: site order only (TiledArgs::site_curve) -- the share in front of the
-// rigorous check, in 64ths, for a tile that starts at phase boundary `start_phase`
-// (hook_phase(); 0 = the curve allows none up to 62/64).
-// hook_phase: the phase a test hook makes tile t start at (TiledArgs::rotate 2 / 3 + j), else 0.
-__device__ __forceinline__ uint32_t hook_phase(const TiledArgs &a, const Tile &t) {
-  if (a.rotate < 2 || a.geo.k_words / 8 < a.rotate_min_steps) return 0;
-  return (a.rotate == 2 ? t.bid * 37u + 11u : a.rotate - 3u) & (kNumPhases - 1);
-}
+// *order_share: site order only (TiledArgs::site_curve) -- the share of the sites from the
+// first on that stands in front of the rigorous check, in 64ths: the HEAD of the order
+// (0 = the curve allows none up to 62/64).  The same for every tile of the launch.
 __device__ __forceinline__ bool launch_verdict(const TiledArgs &a, const uint32_t wg,
                                                uint4 *const lds, uint32_t *xcd_pos,
-                                               const uint32_t start_phase, uint32_t *order_share) {
+                                               uint32_t *order_share) {
   // ONE decision per workgroup (the counters move while the wavefronts read them,
   // and a wavefront that left alone would take its quarter of every stage's
   // requests with it): thread 0 reads, the stage memory carries the verdict.
@@ -403,7 +401,7 @@ __device__ __forceinline__ bool launch_verdict(const TiledArgs &a, const uint32_
       const float kappa = mean + 4.6f * a.site_curve->sigma + 0.003f;
       const float need = (1.f - 2.f * a.kin_threshold) / (1.f - 2.f * kappa);
       ok = kappa < 0.5f && s >= 32 && s <= 62 &&
-           site_curve_covers(a.site_curve->cum, start_phase, s, need);
+           site_curve_covers(a.site_curve->cum, 0, s, need);
     }
     const unsigned long long fits = __ballot(ok);
     if (s == 0) verdict[1 + kPosSlots] = fits != 0 ? (uint32_t)__ffsll(fits) - 1u : 0u;
@@ -461,65 +459,34 @@ struct CheckPlan {
   uint32_t share1;      // the share of the sites in front of check 1, in 64ths
   uint32_t phase;       // the phase boundary the tile starts at (0: not rotated)
   uint32_t k0;          // ... as a k-step of the bitset
-  uint32_t wrap;        // k-steps of the tile in front of the end of the sites (0: none behind)
+  uint32_t wrap;        // k-steps of the tile in front of the end of its ring (0: none behind)
+  uint32_t ring;        // the k-steps the tile goes around: all of them, or the head's (lap)
+  uint32_t count_phase; // the phase boundary the counts at a check start at: `phase`, lap: 0
   uint32_t start_abs;   // k0, counted on from the position the XCD's tiles have published
 };
 // `xcd_pos`, `order_share`: launch_verdict(); `all_steps`: the bitset's k-steps, `num_steps`:
 // the tile's.
 // --- Site order (TiledArgs::site_curve; king_sort.hip).  The prefix bound does not care WHICH
 // sites the prefix holds, so the conversion may put the sites that contribute most to X of
-// unrelated pairs in front; the share then comes from the cohort's measured curve
-// (launch_verdict) instead of the linear rule.  A tile that started at another phase would
-// begin with the light sites: launch_filter turns the rotation off for such a layout (its
-// test hooks stay, their share is taken over the range the tile covers).
+// unrelated pairs in front; the share H (64ths) then comes from the cohort's measured curve
+// (launch_verdict) instead of the linear rule.  A tile that wrapped around the END of the
+// sites would begin with the light ones, so a tile of such a layout rotates inside the HEAD
+// of the order instead -- the head lap: it starts at a phase p in [0, 2 H), runs to the end
+// of the head (k-step kH), wraps to the first site and runs up to p.  There it has summed
+// exactly the head's sites, in another order: the rigorous check is the unrotated tile's,
+// on the same counts (those in front of boundary 2 H, nothing subtracted), and only a tile
+// that stays goes on into the tail [kH, all_steps).  The ring the XCD's tiles share is the
+// head's kH k-steps: positions are published and joined modulo kH, and a tile in its tail
+// says nothing.  Without a lap (no share, a forced menu entry, a forecast check in this
+// launch, a head shorter than rotate_min_steps) such a tile is not rotated.
 __device__ __forceinline__ CheckPlan plan_checks(const TiledArgs &a, const Tile &t,
                                                  const uint32_t xcd_pos, const uint32_t order_share,
                                                  const uint32_t all_steps,
                                                  const uint32_t num_steps) {
   uint32_t chk0 = 0, chk1 = 0, entry1 = 0, share1 = 0;
-  uint32_t phase = 0, k0 = 0, wrap = 0, start_abs = 0;
+  uint32_t phase = 0, k0 = 0, wrap = 0, start_abs = 0, ring = all_steps;
+  bool lap = false;
   if (!t.split && a.check_steps != nullptr && a.tile_done != nullptr) {
-    if (a.rotate != 0 && all_steps >= a.rotate_min_steps) {
-      uint32_t base = 0;
-      if (a.rotate == 1) {
-        const uint32_t r = xcd_pos % all_steps;
-        base = xcd_pos - r;
-        phase = (r * kNumPhases + all_steps / 2) / all_steps;
-        if (phase >= kNumPhases) {
-          phase = 0;
-          base += all_steps;
-        }
-      } else if (a.rotate == 2) {
-        phase = (t.bid * 37u + 11u) & (kNumPhases - 1);  // (test hook)
-      } else {
-        phase = (a.rotate - 3u) & (kNumPhases - 1);    // (test hook)
-      }
-      k0 = phase_step(all_steps, phase);
-      start_abs = base + k0;
-      wrap = k0 != 0 ? all_steps - k0 : 0u;
-    }
-    // Site order with rotated tiles (TiledArgs::site_rotate): the phase is only known here,
-    // so the share of the range [phase, phase + share) around the end is looked up now --
-    // the weight of a range grows with its length: bisection over 32 .. 62, wave-uniform,
-    // from words the launch does not change.
-    uint32_t curve_share = order_share;
-    if (a.site_curve != nullptr && a.rotate == 1 && phase != 0) {
-      curve_share = 0;
-      float m0, s0;
-      if (a.cohort_sums != nullptr && bound_level(a.cohort_sums, 256.f * (float)all_steps, &m0, &s0)) {
-        const float kap = m0 + 4.6f * a.site_curve->sigma + 0.003f;
-        const float need = (1.f - 2.f * a.kin_threshold) / (1.f - 2.f * kap);
-        if (kap < 0.5f && site_curve_covers(a.site_curve->cum, phase, 62, need)) {
-          uint32_t lo = 32, hi = 62;
-          while (lo < hi) {
-            const uint32_t mid = (lo + hi) / 2;
-            if (site_curve_covers(a.site_curve->cum, phase, mid, need)) hi = mid;
-            else lo = mid + 1;
-          }
-          curve_share = lo;
-        }
-      }
-    }
     // kappa: the level of the bound for this cohort's unrelated pairs (from its mean missing
     // and het rates) plus 4.6 standard deviations and a little
     float kappa = -1.f, mean, sigma;
@@ -529,23 +496,53 @@ __device__ __forceinline__ CheckPlan plan_checks(const TiledArgs &a, const Tile 
     // cohort whose unrelated pairs come anywhere near the threshold -- a drain and a sweep
     // per tile (1.5-3 % of configs[1]) that a clean cohort need not pay; a cohort that is
     // clean on average but holds a few bad samples then carries its dense tiles to their
-    // end before the quadrant lists take them over.
-    // k-steps from phase boundary `phase` on that cover `share` phases (around the end)
+    // end before the quadrant lists take them over.  (The same for every tile of a launch.)
+    const bool take0 = (a.check0 == 2 || (a.check0 == 1 && kappa > 0.7f * a.kin_threshold)) &&
+                       a.check_steps[0] != 0;
+    const uint32_t sw1 = a.check1 & 0xFFu;
+    // the ring: every k-step (stored order), or the head's (site order, the head lap)
+    const uint32_t head = order_share * kPhasesPerShare;  // phases
+    const uint32_t k_head = phase_step(all_steps, head);
+    lap = a.site_curve != nullptr && a.rotate != 0 && order_share != 0 && sw1 == 1 && !take0 &&
+          a.check_steps[1] != 0 && k_head >= a.rotate_min_steps && k_head < num_steps;
+    if (lap) ring = k_head;
+    const uint32_t ring_phases = lap ? head : kNumPhases;
+    if (a.rotate != 0 && (lap || (a.site_curve == nullptr && all_steps >= a.rotate_min_steps))) {
+      uint32_t base = 0;
+      if (a.rotate == 1) {
+        const uint32_t r = xcd_pos % ring;
+        base = xcd_pos - r;
+        phase = (r * kNumPhases + all_steps / 2) / all_steps;  // (the boundary nearest to r)
+      } else if (a.rotate == 2) {
+        phase = ((t.bid * 37u + 11u) & (kNumPhases - 1)) % ring_phases;  // (test hook)
+      } else {
+        phase = ((a.rotate - 3u) & (kNumPhases - 1)) % ring_phases;    // (test hook)
+      }
+      k0 = phase_step(all_steps, phase);
+      // (the ring's end is its beginning, one turn on -- also where a short bitset puts a
+      //  boundary inside the ring on the ring's last k-step)
+      if (phase >= ring_phases || k0 >= ring) {
+        phase = 0;
+        k0 = 0;
+        base += ring;
+      }
+      start_abs = base + k0;
+      wrap = k0 != 0 ? ring - k0 : 0u;
+    }
+    // k-steps from phase boundary `phase` on that cover `share` phases (around the end;
+    // stored order, or an unrotated tile: a lap's one check sits behind the ring)
     auto steps_of = [&](uint32_t share) {
       const uint32_t hi = phase + share * kPhasesPerShare;
       return hi <= kNumPhases ? phase_step(all_steps, hi) - k0
                               : (all_steps - k0) + phase_step(all_steps, hi - kNumPhases);
     };
-    if ((a.check0 == 2 || (a.check0 == 1 && kappa > 0.7f * a.kin_threshold)) &&
-        a.check_steps[0] != 0)
-      chk0 = steps_of(kCheckShares64[0]);
-    const uint32_t sw1 = a.check1 & 0xFFu;
+    if (take0) chk0 = steps_of(kCheckShares64[0]);
     if (sw1 >= 2) {
       entry1 = sw1 - 2;
     } else if (sw1 == 1 && a.site_curve != nullptr) {
-      // (site order: the share the curve gives for this tile's range)
-      if (curve_share != 0) {
-        share1 = curve_share;
+      // (site order: the share the curve gives, the head)
+      if (order_share != 0) {
+        share1 = order_share;
         entry1 = 1;
       }
     } else if (sw1 == 1 && kappa >= 0.f) {
@@ -565,12 +562,14 @@ __device__ __forceinline__ CheckPlan plan_checks(const TiledArgs &a, const Tile 
 #pragma unroll
     for (uint32_t k = 1; k < kNumCheckShares; ++k)
       if (sw1 >= 2 && k == entry1) share1 = kCheckShares64[k];
-    if (share1 != 0 && a.check_steps[entry1] != 0) chk1 = steps_of(share1);
+    // (a lap: behind one turn of the ring, wherever the tile started)
+    if (share1 != 0 && a.check_steps[entry1] != 0) chk1 = lap ? ring : steps_of(share1);
     if (chk0 >= num_steps) chk0 = 0;
     if (chk1 >= num_steps || chk1 <= chk0) chk1 = 0;
   }
   auto sgpr = [](uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane(v); };
-  return CheckPlan{sgpr(chk0), sgpr(chk1), sgpr(share1), sgpr(phase), sgpr(k0), sgpr(wrap), sgpr(start_abs)};
+  return CheckPlan{sgpr(chk0), sgpr(chk1), sgpr(share1), sgpr(phase), sgpr(k0),
+                   sgpr(wrap), sgpr(ring), sgpr(lap ? 0u : phase), sgpr(start_abs)};
 }
 
 // u~ of plane sample idx over the `share` phases from the tile's first on (`total`: over
@@ -579,14 +578,16 @@ __device__ __forceinline__ CheckPlan plan_checks(const TiledArgs &a, const Tile 
 // the wrapped end, in THAT order: every partial is then u~ over a contiguous range of
 // sites or over two disjoint ones, at most 2.5 per site -- total + the wrapped end first
 // would reach 5 per site, past 2^24 at 2^22 sites (king_common.h, kMfmaN4MaxSites).
+// (A head lap has covered the head from the first site on, whatever its phase: count_phase 0.)
 __device__ __forceinline__ float prefix_u_of(const TiledArgs &a, const CheckPlan &p,
                                              uint32_t share, size_t idx, float total) {
   const uint32_t s_stride = a.geo.s_stride;
-  const uint32_t hi = p.phase + share * kPhasesPerShare;  // (uniform; hi < 2 kNumPhases)
+  const uint32_t from = p.count_phase;
+  const uint32_t hi = from + share * kPhasesPerShare;  // (uniform; hi < 2 kNumPhases)
   float u = hi >= kNumPhases ? total
             : hi != 0        ? a.prefix_u[(size_t)(hi - 1) * s_stride + idx]
                              : 0.f;
-  if (p.phase != 0) u -= a.prefix_u[(size_t)(p.phase - 1) * s_stride + idx];
+  if (from != 0) u -= a.prefix_u[(size_t)(from - 1) * s_stride + idx];
   if (hi > kNumPhases) u += a.prefix_u[(size_t)(hi - kNumPhases - 1) * s_stride + idx];
   return u;
 }
@@ -631,7 +632,7 @@ __device__ __forceinline__ Leave check_sweep(const TiledArgs &a, const Tile &t, 
   // (site order: the forecast's prefix holds that share of an unrelated pair's X, not an eighth)
   const float scale = !forecast ? 1.f
                       : a.site_curve != nullptr
-                          ? site_curve_mass(a.site_curve->cum, p.phase, kCheckShares64[0])
+                          ? site_curve_mass(a.site_curve->cum, p.count_phase, kCheckShares64[0])
                           : (float)kCheckShares64[0] * (1.f / 64.f);
   const uint32_t share = forecast ? kCheckShares64[0] : p.share1;  // (uniform)
   // (the forecast counts the pairs that WILL be candidates from an eighth of the sites:
@@ -1011,16 +1012,19 @@ __device__ __forceinline__ void emit_candidates(const TiledArgs &a, const Tile &
     buf = nbuf;                                                                \
     ++step;                                                                    \
   }
-// The k-step this tile has reached, for the tiles of the XCD that start next (one lane of
+// The k-step this tile has reached, for the tiles of the XCD that start next -- counted
+// around the tile's ring (a head lap: around the head; behind its one turn, in the tail, a
+// tile says nothing: it would pull newcomers out of the head) (one lane of
 // one wavefront: the branch is scalar, the lane mask is set by hand -- a divergent branch
 // here makes the compiler treat the segment loop as divergent)
 #define F_PUBLISH(STEPS)                                                       \
-  if (a.rotate == 1 && wave == 0) {                                            \
+  if (a.rotate == 1 && wave == 0 && (STEPS) <= ring) {                         \
     const uint32_t now_ = (uint32_t)__builtin_amdgcn_s_memrealtime();          \
     const unsigned long long val_ =                                            \
         ((unsigned long long)(start_abs + (STEPS)) << 32) | now_;              \
-    /* ticks per k-step x 16, once the tile has made enough of them to tell */ \
-    const uint32_t t16_ = (STEPS) >= 32 ? (now_ - t_start) * 16u / (STEPS) : 0u; \
+    /* ticks per k-step x 16, once the tile has made enough of them to tell   \
+       (16: the head of the shortest bitset whose tiles lap says so too) */    \
+    const uint32_t t16_ = (STEPS) >= 16 ? (now_ - t_start) * 16u / (STEPS) : 0u; \
     const uint32_t zero_ = 0;                                                  \
     unsigned long long save_;                                                  \
     asm volatile("s_mov_b64 %0, exec\n\t"                                      \
@@ -1049,7 +1053,7 @@ __device__ __forceinline__ void filter_tile(const TiledArgs &a, const uint32_t w
   const Lanes ln = lanes_of_thread();
   uint32_t xcd_pos = 0, order_share = 0;
   if (!tile.split && a.tile_done != nullptr &&
-      launch_verdict(a, wg, lds, &xcd_pos, hook_phase(a, tile), &order_share))
+      launch_verdict(a, wg, lds, &xcd_pos, &order_share))
     return;
   // k-steps of 256 sites: all of them, or this piece's share
   const uint32_t all_steps = a.geo.k_words / (4 * kUnits);
@@ -1064,7 +1068,7 @@ __device__ __forceinline__ void filter_tile(const TiledArgs &a, const uint32_t w
   // --- the k loop: acc = (q + n_A + S_i + S_j) / 4 of the tile's pairs ("Offset code" above)
   // (the names the F_* macros and the segment loop below use)
   const uint32_t wave = ln.wave, chk0 = plan.chk0, chk1 = plan.chk1;
-  const uint32_t k0 = plan.k0, wrap = plan.wrap, start_abs = plan.start_abs;
+  const uint32_t k0 = plan.k0, wrap = plan.wrap, ring = plan.ring, start_abs = plan.start_abs;
   uint32_t lane16 = ln.lane * 16;
   const uint32_t s_stride = a.geo.s_stride;
   const uint4 *g_rows = a.t2 + (uint64_t)tile.tr * kT;
@@ -1098,13 +1102,13 @@ __device__ __forceinline__ void filter_tile(const TiledArgs &a, const uint32_t w
   const char *seg_src = g_wave;
   uint32_t seg_steps = num_steps;
   // (a rotated tile: k-step `seg_wrap` of the segment is the bitset's FIRST again --
-  //  all_steps k-steps back; 32-bit scalar selects and one signed product: a select between
+  //  `ring` k-steps back; 32-bit scalar selects and one signed product: a select between
   //  two 64-bit addresses goes through vector registers, which the scalar pins cannot take)
   uint32_t seg_wrap = 0xFFFFFFFFu;
   auto addr_of = [&](uint32_t step, uint32_t buf) {
     Addr pa;
     if (step >= seg_steps) step = seg_steps - 1;  // clamped repeats (see king_mfma.hip)
-    const int32_t rel = (int32_t)step - (int32_t)(step >= seg_wrap ? all_steps : 0u);
+    const int32_t rel = (int32_t)step - (int32_t)(step >= seg_wrap ? ring : 0u);
     pa.src = seg_src + (int64_t)rel * (int64_t)kstep_bytes;
     pa.dst = l_wave + buf * (kStageU4 * 16);
     asm volatile("" : "+s"(pa.src), "+s"(pa.dst));
@@ -1113,7 +1117,7 @@ __device__ __forceinline__ void filter_tile(const TiledArgs &a, const uint32_t w
   auto addr_next = [&](const Addr &cur, uint32_t step, uint32_t buf) {
     Addr pa;
     const int32_t adv = (int32_t)(step < seg_steps ? 1u : 0u) -
-                        (int32_t)(step == seg_wrap ? all_steps : 0u);
+                        (int32_t)(step == seg_wrap ? ring : 0u);
     pa.src = cur.src + (int64_t)adv * (int64_t)kstep_bytes;
     pa.dst = l_wave + buf * (kStageU4 * 16);
     asm volatile("" : "+s"(pa.src), "+s"(pa.dst));
@@ -1145,9 +1149,12 @@ __device__ __forceinline__ void filter_tile(const TiledArgs &a, const uint32_t w
     if (chk0 > seg_first) seg_end = chk0;
     seg_end = __builtin_amdgcn_readfirstlane(seg_end);
     seg_steps = seg_end - seg_first;
-    // (the segment's first k-step of the bitset: behind the end of the sites it counts from
-    //  0 again; a segment that holds the end goes around it without a pause)
-    const uint32_t seg_k = seg_first >= wrap && wrap != 0 ? seg_first - wrap : k0 + seg_first;
+    // (the segment's first k-step of the bitset: behind the end of the ring it counts from
+    //  0 again; a segment that holds the end goes around it without a pause; behind one turn
+    //  of a head lap's ring, in the tail, the tile's k-steps are the bitset's)
+    const uint32_t seg_k = seg_first >= ring                ? seg_first
+                           : seg_first >= wrap && wrap != 0 ? seg_first - wrap
+                                                            : k0 + seg_first;
     seg_src = g_wave + (uint64_t)seg_k * kstep_bytes;
     seg_wrap = __builtin_amdgcn_readfirstlane(
         wrap > seg_first && wrap < seg_end ? wrap - seg_first : 0xFFFFFFFFu);
@@ -1391,13 +1398,16 @@ hipError_t launch_filter(const TiledArgs &args, const LaunchSwitches &switches, 
   if (cap == 0) return hipErrorInvalidValue;
   const uint32_t wgs = args.split_wgs != 0 ? args.split_wgs : 256;  // one per CU
   const bool checks = args.tile_done != nullptr;
-  // Site order: no rotated tiles.  A tile that joins the others at phase p would need the
-  // weight of [p, p + e) around the end: from the middle of a descending order that is MORE
-  // k-steps than stored order takes (0.90 of them on the flat spectrum, against 0.875), so
-  // the launch pays the L2 cost of tiles that all start at the first site instead
-  // (profiles/r04_l2_probe.txt: hit rate 0.41 against 0.75, about 3.5 % of the clock).
+  // Site order: a tile never wraps around the end of the sites (from the middle of a
+  // descending order the weight of [p, p + e) takes MORE k-steps than stored order: 0.90 of
+  // them on the flat spectrum, against 0.875).  Where the caller allows it (site_lap:
+  // "filter_site_order" 2, and -1 as king_common.h kSiteOrderAutoLap says) a launch that would
+  // rotate a stored-order layout rotates its tiles inside the head of the order instead
+  // (plan_checks, "head lap"); otherwise the rotation is off and the launch pays the L2 cost
+  // of tiles that all start at the first site (profiles/r04_l2_probe.txt: hit rate 0.41
+  // against 0.75, about 3.5 % of the clock).  The test hooks always take the lap.
   LaunchSwitches sw = switches;
-  if (args.site_curve != nullptr && sw.rotate == 1 && args.site_rotate == 0) sw.rotate = 0;
+  if (args.site_curve != nullptr && sw.rotate == 1 && args.site_lap == 0) sw.rotate = 0;
   const bool can_split = args.fsplit_slabs != nullptr && args.fsplit_tickets != nullptr;
   for (uint64_t done = 0; done < num_tiles;) {
     const FilterPlan p = filter_plan(num_tiles - done, cap, wgs, args.geo.k_words / 8, checks,

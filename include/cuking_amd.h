@@ -287,11 +287,18 @@ cuking_status cuking_ctx_set_kernel(cuking_ctx *ctx, cuking_kernel kernel);
  *                        the converting call's threshold (a "no" is trusted for the next 15
  *                        conversions of the same block at that threshold; a call at another
  *                        threshold decides and converts again); 0 never; 1 every whole-block
- *                        conversion; 2 is 1 with the tiles still rotated, each taking the
- *                        share of the range it covers (a measurement switch: measured slower
- *                        than stored order).  Bitsets beyond 262,144 sites and the ranges of
- *                        cuking_prepare_samples keep stored order.  Tiles of such a layout
- *                        are not rotated.  Cost: a conversion that builds the curve waits
+ *                        conversion, its tiles not rotated; 2 is 1 with the head lap: where
+ *                        "filter_rotate" would rotate a stored-order layout, a tile starts
+ *                        where the tiles of its XCD are INSIDE the head of the order (the
+ *                        sites in front of its check), wraps at the head's end and is checked
+ *                        after one lap -- the same check on the same counts as 1, so the same
+ *                        tiles leave and the same records come out.  -1 takes the lap
+ *                        wherever it takes the order.  A launch with a forecast check, a
+ *                        forced "filter_check1" entry, no share from the curve or a head
+ *                        shorter than "filter_rotate_min_steps" takes no lap: its tiles are
+ *                        not rotated.  Bitsets beyond 262,144 sites and the ranges of
+ *                        cuking_prepare_samples keep stored order.
+ *                        Cost: a conversion that builds the curve waits
  *                        for the stream once to read it (counted in "host_syncs"), and a
  *                        layout that takes the order keeps a second copy of the bitset in
  *                        the stream's scratch for the life of the context (2.5 GB at 100k x
