@@ -251,6 +251,37 @@ def _ld_default_records(num_sites: int, window: int) -> int:
     return max(1, min(num_sites * (window - 1), 4 * num_sites))
 
 
+def _counted_buffer(call, default: int, max_items, name: str, found, attr: str):
+    """THE buffer rule of every call with a counted output (LD edges, PC-Relate and IBD scan
+    records, IBD and ROH segments): ``call(capacity)`` makes a buffer of ``capacity`` items (or
+    takes the caller's ``out``), calls the library and returns ``(buffer, status)``; ``found``
+    is the ``c_uint64`` the library counts into.  Without ``max_items`` (the user's ``name``
+    argument) the buffer holds ``default`` items and the call is repeated once with the exact
+    count if that overflows; with it an overflow raises ``ResourceExhaustedError`` whose
+    ``attr`` (``num_records`` / ``num_segments``) is the exact count.  A list that is not
+    wanted is ``default`` 0 with no counter given to the library: it cannot overflow.
+    Returns the buffer of the call that succeeded."""
+    grow = max_items is None
+    buffer, status = call(default if grow else _count(max_items, name))
+    if status == _lib.ERR_RESOURCE_EXHAUSTED and grow:
+        buffer, status = call(int(found.value))
+    if status == _lib.ERR_RESOURCE_EXHAUSTED:
+        e = ResourceExhaustedError(_lib.load().cuking_last_error().decode())
+        setattr(e, attr, int(found.value))
+        raise e
+    check(status)
+    return buffer
+
+
+def _out_capacity(out, max_records):
+    """``max_records`` of a call that writes into the caller's ``out``: its rows by default, and
+    never more than them."""
+    max_records = out.shape[0] if max_records is None else max_records
+    if _count(max_records, "max_records") > out.shape[0]:
+        raise ValueError(f"out holds {out.shape[0]} records, max_records is {max_records}")
+    return max_records
+
+
 def ld_edges_host(site_bits: np.ndarray, num_sites: int, num_stored: int, window: int = 50,
                   r2: float = 0.2, group=None, max_records=None):
     """cuking_ld_edges_host: the pairs of sites ``a < b``, ``b - a < window``, of one
@@ -281,15 +312,8 @@ def ld_edges_host(site_bits: np.ndarray, num_sites: int, num_stored: int, window
             capacity, C.byref(count))
         return recs, status
 
-    recs, status = call(_ld_default_records(num_sites, window) if max_records is None
-                        else _count(max_records, "max_records"))
-    if status == _lib.ERR_RESOURCE_EXHAUSTED and max_records is None:
-        recs, status = call(int(count.value))
-    if status == _lib.ERR_RESOURCE_EXHAUSTED:
-        e = ResourceExhaustedError(_lib.load().cuking_last_error().decode())
-        e.num_records = int(count.value)
-        raise e
-    check(status)
+    recs = _counted_buffer(call, _ld_default_records(num_sites, window), max_records,
+                           "max_records", count, "num_records")
     return sort_results(recs[:count.value].copy()), int(count.value)
 
 
@@ -971,32 +995,19 @@ class KingContext:
             _device_tensor(self.device, group, "group", torch.int32, shape=(num_sites,))
         if out is not None:
             _device_tensor(self.device, out, "out", torch.int32, cols=6)
-            max_records = out.shape[0] if max_records is None else max_records
-            if _count(max_records, "max_records") > out.shape[0]:
-                raise ValueError(f"out holds {out.shape[0]} records, max_records is {max_records}")
+            max_records = _out_capacity(out, max_records)
         count = C.c_uint64(0)
 
-        def call(records, capacity):
-            return self.lib.cuking_ld_edges(
+        def call(capacity):
+            records = out if out is not None else torch.empty((max(capacity, 1), 6),
+                                                              dtype=torch.int32, device=dev)
+            return records, self.lib.cuking_ld_edges(
                 self.handle, site_bits.data_ptr(), num_sites, num_stored, window, r2,
                 group.data_ptr() if group is not None and num_sites else None,
                 records.data_ptr(), capacity, C.byref(count), _stream_handle(stream))
 
-        grow = max_records is None
-        capacity = _ld_default_records(num_sites, window) if grow else _count(max_records,
-                                                                              "max_records")
-        records = out if out is not None else torch.empty((max(capacity, 1), 6),
-                                                          dtype=torch.int32, device=dev)
-        status = call(records, capacity)
-        if status == _lib.ERR_RESOURCE_EXHAUSTED and grow:
-            capacity = int(count.value)
-            records = torch.empty((capacity, 6), dtype=torch.int32, device=dev)
-            status = call(records, capacity)
-        if status == _lib.ERR_RESOURCE_EXHAUSTED:
-            e = ResourceExhaustedError(self.lib.cuking_last_error().decode())
-            e.num_records = int(count.value)
-            raise e
-        check(status)
+        records = _counted_buffer(call, _ld_default_records(num_sites, window), max_records,
+                                  "max_records", count, "num_records")
         return records, int(count.value)
 
     def ld_prune(self, bit_sets, words_per_sample: int, num_sites: int, window: int = 50,

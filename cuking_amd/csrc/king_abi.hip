@@ -434,6 +434,27 @@ cuking_status grow_on_stream(cuking_ctx *ctx, hipStream_t stream, cuking_ctx::De
   return CUKING_OK;
 }
 
+// THE counted output: `launch(d_count, stream)` writes up to `max` items and counts all of them
+// into the zeroed count word of the stream's scratch; the count is read back (one host sync)
+// into *num and judged by `count_status(count, max)`: RESOURCE_EXHAUSTED with the exact count
+// when they do not fit.
+template <class Launch>
+cuking_status counted_output(cuking_ctx *ctx, hipStream_t s, uint64_t max, uint64_t *num,
+                             cuking_status (*count_status)(uint64_t, uint64_t), Launch &&launch) {
+  cuking_ctx::StreamScratch *e = stream_entry(ctx, s);
+  const cuking_status st = grow_on_stream(ctx, s, &e->record_count, sizeof(unsigned long long));
+  if (st != CUKING_OK) return st;
+  unsigned long long *d_count = static_cast<unsigned long long *>(e->record_count.p);
+  HIP_TRY(hipMemsetAsync(d_count, 0, sizeof(unsigned long long), s));
+  HIP_TRY(launch(d_count, s));
+  unsigned long long count = 0;
+  HIP_TRY(hipMemcpyAsync(&count, d_count, sizeof(count), hipMemcpyDeviceToHost, s));
+  ++ctx->host_syncs;
+  HIP_TRY(hipStreamSynchronize(s));
+  *num = count;
+  return count_status(count, max);
+}
+
 // What a launch of the context's variant needs per stream.
 bool uses_split_slab(const cuking_ctx *ctx) {
   return ctx->split_wgs != 0 && is_mfma_variant(ctx->variant);
@@ -2127,20 +2148,12 @@ cuking_status cuking_ld_edges(cuking_ctx *ctx, const uint64_t *d_site_bits, uint
   if (st != CUKING_OK) return st;
   if (num_sites < 2 || num_stored == 0) return CUKING_OK;
   BIND_OR_RETURN(ctx);
-  hipStream_t s = (hipStream_t)stream;
-  cuking_ctx::StreamScratch *e = stream_entry(ctx, s);
-  st = grow_on_stream(ctx, s, &e->record_count, sizeof(unsigned long long));
-  if (st != CUKING_OK) return st;
-  unsigned long long *d_count = static_cast<unsigned long long *>(e->record_count.p);
-  HIP_TRY(hipMemsetAsync(d_count, 0, sizeof(unsigned long long), s));
-  HIP_TRY(launch_ld_edges(d_site_bits, num_sites, num_stored, window, r2_threshold, d_group,
-                          d_records, max_records, d_count, s));
-  unsigned long long count = 0;
-  HIP_TRY(hipMemcpyAsync(&count, d_count, sizeof(count), hipMemcpyDeviceToHost, s));
-  ++ctx->host_syncs;
-  HIP_TRY(hipStreamSynchronize(s));
-  *num_records = count;
-  return cuking_ld_count_status(count, max_records);
+  return counted_output(ctx, (hipStream_t)stream, max_records, num_records, cuking_ld_count_status,
+                        [&](unsigned long long *d_count, hipStream_t s) {
+                          return launch_ld_edges(d_site_bits, num_sites, num_stored, window,
+                                                 r2_threshold, d_group, d_records, max_records,
+                                                 d_count, s);
+                        });
 }
 
 // ---- genotype matrix products (king_geno.hip) -------------------------------
@@ -2201,20 +2214,13 @@ cuking_status cuking_pcrelate_records(cuking_ctx *ctx, const uint64_t *d_bits,
   // (without a site every kin is NaN: no record)
   if (sm_num_rows(*block) == 0 || sm_num_cols(*block) == 0 || num_sites == 0) return CUKING_OK;
   BIND_OR_RETURN(ctx);
-  hipStream_t s = (hipStream_t)stream;
-  cuking_ctx::StreamScratch *e = stream_entry(ctx, s);
-  st = grow_on_stream(ctx, s, &e->record_count, sizeof(unsigned long long));
-  if (st != CUKING_OK) return st;
-  unsigned long long *d_count = static_cast<unsigned long long *>(e->record_count.p);
-  HIP_TRY(hipMemsetAsync(d_count, 0, sizeof(unsigned long long), s));
-  HIP_TRY(launch_pcrelate_records(d_bits, words_per_sample, num_sites, d_x, ldx, d_beta, ldbeta, d,
-                                  lo, hi, *block, min_kin, d_records, max_records, d_count, s));
-  unsigned long long count = 0;
-  HIP_TRY(hipMemcpyAsync(&count, d_count, sizeof(count), hipMemcpyDeviceToHost, s));
-  ++ctx->host_syncs;
-  HIP_TRY(hipStreamSynchronize(s));
-  *num_records = count;
-  return cuking_pcrelate_count_status(count, max_records);
+  return counted_output(
+      ctx, (hipStream_t)stream, max_records, num_records, cuking_pcrelate_count_status,
+      [&](unsigned long long *d_count, hipStream_t s) {
+        return launch_pcrelate_records(d_bits, words_per_sample, num_sites, d_x, ldx, d_beta,
+                                       ldbeta, d, lo, hi, *block, min_kin, d_records, max_records,
+                                       d_count, s);
+      });
 }
 
 cuking_status cuking_pcrelate_pairs(cuking_ctx *ctx, const uint64_t *d_bits, uint32_t num_stored,
@@ -2241,9 +2247,9 @@ cuking_status cuking_pcrelate_pairs(cuking_ctx *ctx, const uint64_t *d_bits, uin
 // ---- IBD segments for listed pairs (king_ibd.hip) ------------------------------
 
 // What the pair calls and the scan of single samples share once their arguments are checked and
-// there is work to do: the host check of the positions, the group bits and the count word of the
-// stream's scratch, `launch(d_group_bits, d_count, stream)`, and the count read back and judged
-// by `count_status` (segments for the listed calls, records for the scan of a block).
+// there is work to do: the host check of the positions, the group bits of the stream's scratch
+// and `launch(d_group_bits, d_count, stream)` -- as a counted output judged by `count_status`
+// (segments for the listed calls, records for the scan of a block) when a count is wanted.
 extern "C++" {
 template <class Launch>
 static cuking_status ibd_scan_device(cuking_ctx *ctx, uint32_t num_sites, const int32_t *d_group,
@@ -2274,21 +2280,14 @@ static cuking_status ibd_scan_device(cuking_ctx *ctx, uint32_t num_sites, const 
   if (st != CUKING_OK) return st;
   uint64_t *d_group_bits = static_cast<uint64_t *>(e->ibd_groups.p);
   HIP_TRY(launch_ibd_group_bits(d_group, num_sites, d_group_bits, s));
-  unsigned long long *d_count = nullptr;
-  if (num_segments != nullptr) {
-    st = grow_on_stream(ctx, s, &e->record_count, sizeof(unsigned long long));
-    if (st != CUKING_OK) return st;
-    d_count = static_cast<unsigned long long *>(e->record_count.p);
-    HIP_TRY(hipMemsetAsync(d_count, 0, sizeof(unsigned long long), s));
+  if (num_segments == nullptr) {  // no count wanted: nothing to wait for
+    HIP_TRY(launch(d_group_bits, nullptr, s));
+    return CUKING_OK;
   }
-  HIP_TRY(launch(d_group_bits, d_count, s));
-  if (num_segments == nullptr) return CUKING_OK;
-  unsigned long long count = 0;
-  HIP_TRY(hipMemcpyAsync(&count, d_count, sizeof(count), hipMemcpyDeviceToHost, s));
-  ++ctx->host_syncs;
-  HIP_TRY(hipStreamSynchronize(s));
-  *num_segments = count;
-  return count_status(count, max_segments);
+  return counted_output(ctx, s, max_segments, num_segments, count_status,
+                        [&](unsigned long long *d_count, hipStream_t on) {
+                          return launch(d_group_bits, d_count, on);
+                        });
 }
 }  // extern "C++"
 

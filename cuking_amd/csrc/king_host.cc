@@ -1051,43 +1051,17 @@ std::vector<uint64_t> ibd_group_bits(const int32_t *group, uint32_t num_sites) {
   return group_bits;
 }
 
-// The words of one pair, one at a time: on_run(k, a, b) for every run [a, b] of kind k + 1 that
-// crosses a word edge, by (word of b + 1, kind).
-template <class OnRun>
-void ibd_walk_runs(const uint64_t *row_i, const uint64_t *row_j, uint32_t plane_words,
-                   uint32_t num_sites, const std::vector<uint64_t> &group_bits, OnRun on_run) {
-  uint32_t open[2] = {kIbdInherit, kIbdInherit}, edge[2] = {0, 0};
-  for (uint64_t w = 0; w < group_bits.size(); ++w) {
-    const uint64_t valid = ibd_valid_mask(num_sites, w);
-    uint64_t het_i = 0, hom_i = 0, het_j = 0, hom_j = 0;
-    if (valid != 0) {  // (then w < plane_words)
-      het_i = row_i[w];
-      hom_i = row_i[plane_words + w];
-      het_j = row_j[w];
-      hom_j = row_j[plane_words + w];
-    }
-    const uint64_t in_run[2] = {valid & ~ibd_opp(het_i, hom_i, het_j, hom_j),
-                                valid & ~ibd_diff(het_i, hom_i, het_j, hom_j)};
-    for (uint32_t k = 0; k < 2; ++k) {
-      const uint64_t starts = ibd_starts(in_run[k], edge[k], group_bits[w]);
-      const uint64_t closes = ibd_closes(in_run[k], edge[k], group_bits[w]);
-      if (edge[k] != 0 && closes != 0) on_run(k, open[k], ibd_close_last(closes, w));
-      const uint32_t start = ibd_open_start(starts, w);
-      if (start != kIbdInherit) open[k] = start;
-      edge[k] = (uint32_t)(in_run[k] >> 63);
-    }
-  }
-}
-
-// Both kinds of ONE pair (i, j), the per-pair walk every host twin shares: the sums of its
-// segments, and on_segment(k, a, b, links) for each segment [a, b] of kind k + 1.
-// bridge_sites == 0 links nothing and tests every run where it closes; otherwise a chain is
-// tested when the next run is not linked to it, the last one after the walk.
-template <class OnSegment>
-void ibd_pair_sums(const uint64_t *bits, uint32_t words_per_sample, uint32_t num_sites,
-                   const std::vector<uint64_t> &group_bits, const uint32_t *pos,
-                   uint32_t min_sites, uint32_t min_length, uint32_t bridge_sites, uint64_t i,
-                   uint64_t j, IbdKindSums sums[2], OnSegment on_segment) {
+// The words of ONE subject (a pair: two kinds; a sample against itself: one), one at a time, the
+// walk every host twin shares.  in_run(w, valid, in) gives the kKinds `in` masks of word w, valid
+// & ~break (valid != 0 implies w < plane_words: only then may it load).  The runs that cross a
+// word edge arrive by (word of b + 1, kind) and go through the kind's chain: bridge_sites == 0
+// links nothing and tests every run where it closes; otherwise a chain is tested when the next
+// run is not linked to it, the last one after the walk.  sums[k] takes the segments of kind
+// k + 1, and on_segment(k, a, b, links) is called for each.
+template <uint32_t kKinds, class InRun, class OnSegment>
+void ibd_walk_sums(uint32_t num_sites, const std::vector<uint64_t> &group_bits,
+                   const uint32_t *pos, uint32_t min_sites, uint32_t min_length,
+                   uint32_t bridge_sites, IbdKindSums *sums, InRun in_run, OnSegment on_segment) {
   // THE segment test of a chain [a, b] with `links` bridged breaks
   auto test = [&](uint32_t k, uint32_t a, uint32_t b, uint32_t links) {
     const uint32_t pos_a = pos != nullptr ? pos[a] : a, pos_b = pos != nullptr ? pos[b] : b;
@@ -1096,25 +1070,43 @@ void ibd_pair_sums(const uint64_t *bits, uint32_t words_per_sample, uint32_t num
     sums[k].bridged += links;
     on_segment(k, a, b, links);
   };
-  IbdChain chain[2];
-  ibd_walk_runs(bits + i * words_per_sample, bits + j * words_per_sample, words_per_sample / 2,
-                num_sites, group_bits, [&](uint32_t k, uint32_t a, uint32_t b) {
-                  if (bridge_sites == 0) return test(k, a, b, 0);
-                  IbdChain &c = chain[k];
-                  if (c.have && ibd_linked(c.last_first, c.last_end, a, b, bridge_sites,
-                                           group_bits.data())) {
-                    ++c.links;
-                  } else {
-                    if (c.have) test(k, c.first, c.last_end, c.links);
-                    c.have = 1;
-                    c.first = a;
-                    c.links = 0;
-                  }
-                  c.last_first = a;
-                  c.last_end = b;
-                });
-  for (uint32_t k = 0; k < 2; ++k)
-    if (chain[k].have) test(k, chain[k].first, chain[k].last_end, chain[k].links);
+  IbdWalk walk[kKinds];
+  IbdChain chain[kKinds];
+  uint32_t a, b, first, end, links;
+  for (uint64_t w = 0; w < group_bits.size(); ++w) {
+    uint64_t in[kKinds];
+    in_run(w, ibd_valid_mask(num_sites, w), in);
+    for (uint32_t k = 0; k < kKinds; ++k)
+      if (walk[k].step(in[k], group_bits[w], w, &a, &b) &&
+          chain[k].step(a, b, bridge_sites, group_bits.data(), &first, &end, &links))
+        test(k, first, end, links);
+  }
+  for (uint32_t k = 0; k < kKinds; ++k)
+    if (chain[k].flush(&first, &end, &links)) test(k, first, end, links);
+}
+
+// Both kinds of ONE pair (i, j): the break masks are ibd_opp and ibd_diff of its four planes.
+template <class OnSegment>
+void ibd_pair_sums(const uint64_t *bits, uint32_t words_per_sample, uint32_t num_sites,
+                   const std::vector<uint64_t> &group_bits, const uint32_t *pos,
+                   uint32_t min_sites, uint32_t min_length, uint32_t bridge_sites, uint64_t i,
+                   uint64_t j, IbdKindSums sums[2], OnSegment on_segment) {
+  const uint64_t *row_i = bits + i * words_per_sample, *row_j = bits + j * words_per_sample;
+  const uint32_t plane_words = words_per_sample / 2;
+  ibd_walk_sums<2>(
+      num_sites, group_bits, pos, min_sites, min_length, bridge_sites, sums,
+      [&](uint64_t w, uint64_t valid, uint64_t in[2]) {
+        uint64_t het_i = 0, hom_i = 0, het_j = 0, hom_j = 0;
+        if (valid != 0) {
+          het_i = row_i[w];
+          hom_i = row_i[plane_words + w];
+          het_j = row_j[w];
+          hom_j = row_j[plane_words + w];
+        }
+        in[0] = valid & ~ibd_opp(het_i, hom_i, het_j, hom_j);
+        in[1] = valid & ~ibd_diff(het_i, hom_i, het_j, hom_j);
+      },
+      on_segment);
 }
 
 // Rows, bridged counts and the segment list of both host calls.
@@ -1187,8 +1179,8 @@ cuking_status cuking_check_roh_args(const void *bits, uint32_t words_per_sample,
 
 extern "C" {
 
-// The words of one sample, one at a time, with the functions of king_ibd.h: what
-// ibd_pairs_host does for a pair, with roh_break as the break mask and one kind.
+// The walk of the pair calls for one sample against itself: one kind, whose break mask is
+// roh_break of the sample's two planes.
 cuking_status cuking_roh_samples_host(const uint64_t *bits, uint32_t num_stored,
                                       uint32_t words_per_sample, uint32_t num_sites,
                                       const int32_t *group, const uint32_t *pos,
@@ -1212,51 +1204,18 @@ cuking_status cuking_roh_samples_host(const uint64_t *bits, uint32_t num_stored,
     const uint64_t sample = samples != nullptr ? samples[r] : r;
     IbdKindSums sums;
     if (sample < num_stored) {
-      // THE segment test of a chain [a, b] with `links` bridged breaks
-      auto test = [&](uint32_t a, uint32_t b, uint32_t links) {
-        const uint32_t pos_a = pos != nullptr ? pos[a] : a, pos_b = pos != nullptr ? pos[b] : b;
-        if (!ibd_is_segment(a, b, pos_a, pos_b, min_sites, min_length)) return;
-        sums.add(pos_b - pos_a);
-        sums.bridged += links;
-        if (num_segments != nullptr) {
-          if (count < max_segments)
-            segments[count] = cuking_ibd_segment{(uint32_t)r, CUKING_ROH_KIND, a, b};
-          ++count;
-        }
-      };
       const uint64_t *row = bits + sample * words_per_sample;
-      IbdChain c;
-      uint32_t open = kIbdInherit, edge = 0;
-      for (uint64_t w = 0; w < group_bits.size(); ++w) {
-        const uint64_t valid = ibd_valid_mask(num_sites, w);
-        // (valid != 0 implies w < plane_words)
-        const uint64_t brk = valid != 0 ? roh_break(row[w], row[plane_words + w]) : 0;
-        const uint64_t in = valid & ~brk;
-        const uint64_t starts = ibd_starts(in, edge, group_bits[w]);
-        const uint64_t closes = ibd_closes(in, edge, group_bits[w]);
-        if (edge != 0 && closes != 0) {
-          const uint32_t a = open, b = ibd_close_last(closes, w);
-          if (bridge_sites == 0) {
-            test(a, b, 0);
-          } else {
-            if (c.have && ibd_linked(c.last_first, c.last_end, a, b, bridge_sites,
-                                     group_bits.data())) {
-              ++c.links;
-            } else {
-              if (c.have) test(c.first, c.last_end, c.links);
-              c.have = 1;
-              c.first = a;
-              c.links = 0;
-            }
-            c.last_first = a;
-            c.last_end = b;
-          }
-        }
-        const uint32_t start = ibd_open_start(starts, w);
-        if (start != kIbdInherit) open = start;
-        edge = (uint32_t)(in >> 63);
-      }
-      if (c.have) test(c.first, c.last_end, c.links);
+      ibd_walk_sums<1>(
+          num_sites, group_bits, pos, min_sites, min_length, bridge_sites, &sums,
+          [&](uint64_t w, uint64_t valid, uint64_t in[1]) {
+            in[0] = valid != 0 ? valid & ~roh_break(row[w], row[plane_words + w]) : 0;
+          },
+          [&](uint32_t, uint32_t a, uint32_t b, uint32_t) {
+            if (num_segments == nullptr) return;
+            if (count < max_segments)
+              segments[count] = cuking_ibd_segment{(uint32_t)r, CUKING_ROH_KIND, a, b};
+            ++count;
+          });
     }
     cuking_roh_sample row_out;
     row_out.length = sums.length;

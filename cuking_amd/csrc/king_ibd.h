@@ -1,6 +1,8 @@
 // IBD segments for listed pairs (include/cuking_amd.h, "IBD segments for listed pairs"): the
 // definitions the kernels of king_ibd.hip, the scan of a block of king_ibd_scan.hip ("IBD scan of
-// a block"), the host twins of king_host.cc and the tests share, so that they cannot drift apart.  Plain C++: hipcc compiles the functions for the device, the
+// a block"), the host twins of king_host.cc and the tests share, so that they cannot drift apart:
+// the word masks, the walk over the words of one kind (IbdWalk), the chain of bridged runs
+// (IbdChain) and the segment test.  Plain C++: hipcc compiles the functions for the device, the
 // sanitizer build of the tests (tests/ibd_host_driver.cc) for the host.  Integers only.
 //
 // Words.  Word w of a plane holds the sites 64 w .. 64 w + 63, site s at bit s & 63.  A scan
@@ -25,7 +27,9 @@
 // A run that starts AND closes inside one word has at most 63 sites (bits 0 .. 62, closed at
 // bit 63), and a run of 64 or more sites always closes in a later word than it starts in: with
 // min_sites >= kIbdMinSites = 64 only the first rule can yield a segment, at most one per word
-// and kind, and nobody enumerates bits.
+// and kind, and nobody enumerates bits.  IbdWalk::step is these two rules for whoever takes the
+// words one by one (the host twins; ibd_scan_word of king_ibd_scan.hip still restates them, see
+// DESIGN.md 4.3j); a wavefront takes 64 words at once (ibd_kind_step of king_ibd.hip).
 //
 // Bridged breaks ("IBD segments with bridged breaks" in the header).  With bridge_sites != 0 two
 // consecutive runs on either side of ONE break site are linked when both have at least
@@ -33,8 +37,8 @@
 // and a segment is a maximal chain of linked runs.  Both runs of a link cross a word edge, so
 // they are among the runs the first rule yields, in site order; a run that opens and closes
 // inside one word lies between its neighbours and keeps them more than one site apart.  IbdChain
-// is the chain whose last run is the last one seen: the host twin carries it from word to word,
-// a wavefront from step to step.
+// is the chain whose last run is the last one seen: the host twin carries it from word to word
+// (IbdChain::step, IbdChain::flush), a wavefront from step to step.
 #ifndef CUKING_AMD_KING_IBD_H_
 #define CUKING_AMD_KING_IBD_H_
 
@@ -144,6 +148,60 @@ CUKING_HD inline bool ibd_linked(uint32_t a, uint32_t b, uint32_t a2, uint32_t b
 // last_first .. last_end, `links` bridged breaks inside.
 struct IbdChain {
   uint32_t have = 0, first = 0, last_first = 0, last_end = 0, links = 0;
+
+  // The next closed run [a, b], in site order.  True: the chain [*first_out, *end_out] with
+  // *links_out bridged breaks is finished and wants THE segment test.  bridge_sites == 0 links
+  // nothing: every run is reported where it closes and nothing is kept for flush().
+  CUKING_HD bool step(uint32_t a, uint32_t b, uint32_t bridge_sites, const uint64_t *group_bits,
+                      uint32_t *first_out, uint32_t *end_out, uint32_t *links_out) {
+    if (bridge_sites == 0) {
+      *first_out = a;
+      *end_out = b;
+      *links_out = 0;
+      return true;
+    }
+    bool done = false;
+    if (have && ibd_linked(last_first, last_end, a, b, bridge_sites, group_bits)) {
+      ++links;
+    } else {
+      done = flush(first_out, end_out, links_out);
+      have = 1;
+      first = a;
+      links = 0;
+    }
+    last_first = a;
+    last_end = b;
+    return done;
+  }
+  // After the walk every run is closed: the chain that is left, if any, is whole.
+  CUKING_HD bool flush(uint32_t *first_out, uint32_t *end_out, uint32_t *links_out) const {
+    if (!have) return false;
+    *first_out = first;
+    *end_out = last_end;
+    *links_out = links;
+    return true;
+  }
+};
+
+// The walk over the words of one kind, one word at a time in ascending w.
+struct IbdWalk {
+  uint32_t prev = 0;            // bit 63 of the word before's `in`
+  uint32_t open = kIbdInherit;  // first site of the run that is open at the end of that word
+
+  // Word w with its `in` and group masks.  True: the run [*a, *b] that was open at the word's
+  // entry closes in it.
+  CUKING_HD bool step(uint64_t in, uint64_t group, uint64_t w, uint32_t *a, uint32_t *b) {
+    const uint64_t starts = ibd_starts(in, prev, group), closes = ibd_closes(in, prev, group);
+    const bool closed = prev != 0 && closes != 0;
+    if (closed) {
+      *a = open;
+      *b = ibd_close_last(closes, w);
+    }
+    const uint32_t start = ibd_open_start(starts, w);
+    if (start != kIbdInherit) open = start;
+    prev = (uint32_t)(in >> 63);
+    return closed;
+  }
 };
 
 // What a pair accumulates per kind; the sums and maxima are integers, so the order in which

@@ -326,6 +326,48 @@ __global__ __launch_bounds__(kIbdThreads) void roh_samples_kernel(const RohArgs<
   if (lane == 0) a.rows[r] = row;
 }
 
+// What both launches below fill alike; `out` and `bridged` are the pair call's own.
+IbdBridgeArgs ibd_common_args(const uint64_t *d_bits, uint32_t num_stored,
+                              uint32_t words_per_sample, uint32_t num_sites,
+                              const uint64_t *d_group_bits, const uint32_t *d_pos,
+                              uint32_t min_sites, uint32_t min_length, uint32_t bridge_sites,
+                              const void *d_list, uint64_t num_entries, uint32_t stride,
+                              cuking_ibd_segment *d_segments, uint64_t max_segments,
+                              unsigned long long *d_count) {
+  IbdBridgeArgs a;
+  a.bits = d_bits;
+  a.group_bits = d_group_bits;
+  a.pos = d_pos;
+  a.pairs = static_cast<const unsigned char *>(d_list);
+  a.out = nullptr;
+  a.segments = d_segments;
+  a.count = d_count;
+  a.max_segments = max_segments;
+  a.num_pairs = num_entries;
+  a.pair_base = 0;
+  a.pair_stride = stride;
+  a.num_stored = num_stored;
+  a.words_per_sample = words_per_sample;
+  a.num_sites = num_sites;
+  a.min_sites = min_sites;
+  a.min_length = min_length;
+  a.bridged = nullptr;
+  a.bridge_sites = bridge_sites;
+  return a;
+}
+
+// One wavefront per entry of the list, in launches of at most the grid limit.  `a` is a copy of
+// the kernel's own argument type (not deduced: the strict kernels take the slice they read).
+template <class Args>
+hipError_t ibd_launch_waves(void (*kernel)(Args), typename std::common_type<Args>::type a,
+                            hipStream_t stream) {
+  const uint64_t blocks = (a.num_pairs + kIbdWaves - 1) / kIbdWaves;
+  return launch_in_chunks(blocks, kIbdThreads, [&](uint64_t done, uint32_t n) {
+    a.pair_base = done * kIbdWaves;
+    kernel<<<dim3(n), dim3(kIbdThreads), 0, stream>>>(a);
+  });
+}
+
 }  // namespace
 
 hipError_t launch_ibd_group_bits(const int32_t *d_group, uint32_t num_sites,
@@ -346,41 +388,21 @@ hipError_t launch_ibd_pairs(const uint64_t *d_bits, uint32_t num_stored,
                             cuking_ibd_segment *d_segments, uint64_t max_segments,
                             unsigned long long *d_count, hipStream_t stream) {
   if (num_pairs == 0) return hipSuccess;
-  IbdBridgeArgs a;
-  a.bits = d_bits;
-  a.group_bits = d_group_bits;
-  a.pos = d_pos;
-  a.pairs = static_cast<const unsigned char *>(d_pairs);
+  IbdBridgeArgs a = ibd_common_args(d_bits, num_stored, words_per_sample, num_sites, d_group_bits,
+                                    d_pos, min_sites, min_length, bridge_sites, d_pairs,
+                                    num_pairs, pair_stride, d_segments, max_segments, d_count);
   a.out = d_out;
-  a.segments = d_segments;
-  a.count = d_count;
-  a.max_segments = max_segments;
-  a.num_pairs = num_pairs;
-  a.pair_base = 0;
-  a.pair_stride = pair_stride;
-  a.num_stored = num_stored;
-  a.words_per_sample = words_per_sample;
-  a.num_sites = num_sites;
-  a.min_sites = min_sites;
-  a.min_length = min_length;
   a.bridged = d_bridged;
-  a.bridge_sites = bridge_sites;
-  const uint64_t blocks = (num_pairs + kIbdWaves - 1) / kIbdWaves;
   if (bridge_sites == 0) {
-    // nothing is linked: the strict kernel, and no pair has a bridged break
+    // nothing is linked: the strict kernel (it drops the bridge fields), and no pair has a
+    // bridged break
     if (d_bridged != nullptr) {
       const hipError_t err = hipMemsetAsync(d_bridged, 0, num_pairs * 2 * sizeof(uint32_t), stream);
       if (err != hipSuccess) return err;
     }
-    return launch_in_chunks(blocks, kIbdThreads, [&](uint64_t done, uint32_t n) {
-      a.pair_base = done * kIbdWaves;
-      ibd_pairs_kernel<false><<<dim3(n), dim3(kIbdThreads), 0, stream>>>(a);
-    });
+    return ibd_launch_waves(ibd_pairs_kernel<false>, a, stream);
   }
-  return launch_in_chunks(blocks, kIbdThreads, [&](uint64_t done, uint32_t n) {
-    a.pair_base = done * kIbdWaves;
-    ibd_pairs_kernel<true><<<dim3(n), dim3(kIbdThreads), 0, stream>>>(a);
-  });
+  return ibd_launch_waves(ibd_pairs_kernel<true>, a, stream);
 }
 
 namespace {
@@ -390,11 +412,7 @@ hipError_t launch_roh(const IbdBridgeArgs &from, cuking_roh_sample *d_out, hipSt
   RohArgs<kBridge> a;
   static_cast<IbdArgsOf<kBridge> &>(a) = from;  // (the strict form drops the bridge fields)
   a.rows = d_out;
-  const uint64_t blocks = (a.num_pairs + kIbdWaves - 1) / kIbdWaves;
-  return launch_in_chunks(blocks, kIbdThreads, [&](uint64_t done, uint32_t n) {
-    a.pair_base = done * kIbdWaves;
-    roh_samples_kernel<kBridge><<<dim3(n), dim3(kIbdThreads), 0, stream>>>(a);
-  });
+  return ibd_launch_waves(roh_samples_kernel<kBridge>, a, stream);
 }
 
 }  // namespace
@@ -408,25 +426,9 @@ hipError_t launch_roh_samples(const uint64_t *d_bits, uint32_t num_stored,
                               uint64_t max_segments, unsigned long long *d_count,
                               hipStream_t stream) {
   if (num_samples == 0) return hipSuccess;
-  IbdBridgeArgs a;
-  a.bits = d_bits;
-  a.group_bits = d_group_bits;
-  a.pos = d_pos;
-  a.pairs = reinterpret_cast<const unsigned char *>(d_samples);
-  a.out = nullptr;
-  a.segments = d_segments;
-  a.count = d_count;
-  a.max_segments = max_segments;
-  a.num_pairs = num_samples;
-  a.pair_base = 0;
-  a.pair_stride = sizeof(uint32_t);
-  a.num_stored = num_stored;
-  a.words_per_sample = words_per_sample;
-  a.num_sites = num_sites;
-  a.min_sites = min_sites;
-  a.min_length = min_length;
-  a.bridged = nullptr;
-  a.bridge_sites = bridge_sites;
+  const IbdBridgeArgs a = ibd_common_args(
+      d_bits, num_stored, words_per_sample, num_sites, d_group_bits, d_pos, min_sites, min_length,
+      bridge_sites, d_samples, num_samples, sizeof(uint32_t), d_segments, max_segments, d_count);
   // (bridge_sites == 0 links nothing: the strict instantiation)
   return bridge_sites == 0 ? launch_roh<false>(a, d_out, stream)
                            : launch_roh<true>(a, d_out, stream);

@@ -21,7 +21,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import check
-from .api import KING_CUTOFFS, _count
+from .api import KING_CUTOFFS, _count, _counted_buffer, _out_capacity
 from .pcrelate import (DUPLICATE, FULL_SIBLING, PARENT_CHILD, SECOND_DEGREE, THIRD_DEGREE,
                        UNRELATED, _block, _default_records, _device_pairs, _host_pairs)
 
@@ -164,29 +164,12 @@ def _default_segments(count: int) -> int:
     return max(1, 4 * count)
 
 
-def _exhausted(count: int):
-    from .api import ResourceExhaustedError
-    e = ResourceExhaustedError(_lib.load().cuking_last_error().decode())
-    e.num_segments = count
-    return e
-
-
 def _segment_buffer(call, count: int, want: bool, max_segments, found):
-    """The buffer rule of a segment list, shared by every call that has one: ``call(capacity)``
-    makes a buffer of ``capacity`` segments, calls the library and returns ``(buffer, status)``;
-    ``found`` is the ``c_uint64`` the library counts into.  Without ``max_segments`` the buffer
-    is ``_default_segments(count)`` and the call is repeated once with the exact count; with it
-    an overflow raises ``ResourceExhaustedError`` whose ``num_segments`` is the exact count.
-    Returns the buffer of the call that succeeded."""
-    grow = max_segments is None
-    segs, status = call(0 if not want else _default_segments(count) if grow
-                        else _count(max_segments, "max_segments"))
-    if status == _lib.ERR_RESOURCE_EXHAUSTED and grow:
-        segs, status = call(int(found.value))
-    if status == _lib.ERR_RESOURCE_EXHAUSTED:
-        raise _exhausted(int(found.value))
-    check(status)
-    return segs
+    """The buffer rule (``_counted_buffer``) of a segment list, for every call that has one:
+    ``_default_segments(count)`` by default, and a list that is not wanted (then
+    ``max_segments`` is None) has capacity 0 and is not counted."""
+    return _counted_buffer(call, _default_segments(count) if want else 0, max_segments,
+                           "max_segments", found, "num_segments")
 
 
 def ibd_segments_raw_host(bits: np.ndarray, words_per_sample: int, num_sites: int, pairs,
@@ -364,27 +347,11 @@ def _min_total(min_total) -> int:
     return min_total
 
 
-def _records_exhausted(count: int):
-    from .api import ResourceExhaustedError
-    e = ResourceExhaustedError(_lib.load().cuking_last_error().decode())
-    e.num_records = count
-    return e
-
-
 def _record_buffer(call, block, max_records, found):
-    """The buffer rule of ``pcrelate_records``: ``call(capacity)`` makes a buffer of ``capacity``
-    records, calls the library and returns ``(buffer, status)``; ``found`` is the ``c_uint64``
-    the library counts into.  Without ``max_records`` the buffer is that call's default (16
-    records per sample of the block) and the call is repeated once with the exact count; with
-    it an overflow raises ``ResourceExhaustedError`` whose ``num_records`` is the exact count."""
-    grow = max_records is None
-    recs, status = call(_default_records(block) if grow else _count(max_records, "max_records"))
-    if status == _lib.ERR_RESOURCE_EXHAUSTED and grow:
-        recs, status = call(int(found.value))
-    if status == _lib.ERR_RESOURCE_EXHAUSTED:
-        raise _records_exhausted(int(found.value))
-    check(status)
-    return recs
+    """The buffer rule (``_counted_buffer``) of the scan's records, with the default of
+    ``pcrelate_records``: 16 records per sample of the block."""
+    return _counted_buffer(call, _default_records(block), max_records, "max_records", found,
+                           "num_records")
 
 
 def ibd_scan_raw_host(bits: np.ndarray, words_per_sample: int, num_sites: int, group=None,
@@ -454,9 +421,7 @@ def ibd_scan_raw_device(ctx, bits, words_per_sample: int, num_sites: int, group=
     block = _block(block, num_stored)
     if out is not None:
         _device_tensor(ctx.device, out, "out", torch.int32, cols=10)
-        max_records = out.shape[0] if max_records is None else max_records
-        if _count(max_records, "max_records") > out.shape[0]:
-            raise ValueError(f"out holds {out.shape[0]} records, max_records is {max_records}")
+        max_records = _out_capacity(out, max_records)
     found = C.c_uint64(0)
     # (uploads ran on the current stream: `stream` waits for them)
     if stream is not None:

@@ -31,8 +31,8 @@ import numpy as np
 
 from . import _lib
 from ._lib import check
-from .api import (KING_CUTOFFS, KING_RESULT_DTYPE, Submatrix, _count, _geno_host_matrix,
-                  geno_matmul_host)
+from .api import (KING_CUTOFFS, KING_RESULT_DTYPE, Submatrix, _count, _counted_buffer,
+                  _geno_host_matrix, _out_capacity, geno_matmul_host)
 from .pca import DeviceOperator, HostOperator
 
 COLUMNS_MAX = _lib.PCRELATE_COLUMNS_MAX
@@ -565,13 +565,6 @@ def _default_records(block: Submatrix) -> int:
     return max(1, min(pairs, 16 * (rows + cols)))
 
 
-def _exhausted(count: int):
-    from .api import ResourceExhaustedError
-    e = ResourceExhaustedError(_lib.load().cuking_last_error().decode())
-    e.num_records = count
-    return e
-
-
 def pcrelate_records_raw_host(bits: np.ndarray, words_per_sample: int, num_sites: int, x, beta,
                               lo: float, hi: float, min_kin: float, block=None,
                               max_records=None):
@@ -602,13 +595,8 @@ def pcrelate_records_raw_host(bits: np.ndarray, words_per_sample: int, num_sites
             C.byref(block.c), min_kin, recs.ctypes.data, capacity, C.byref(count))
         return recs, status
 
-    recs, status = call(_default_records(block) if max_records is None
-                        else _count(max_records, "max_records"))
-    if status == _lib.ERR_RESOURCE_EXHAUSTED and max_records is None:
-        recs, status = call(int(count.value))
-    if status == _lib.ERR_RESOURCE_EXHAUSTED:
-        raise _exhausted(int(count.value))
-    check(status)
+    recs = _counted_buffer(call, _default_records(block), max_records, "max_records", count,
+                           "num_records")
     return recs[:count.value].copy(), int(count.value)
 
 
@@ -649,30 +637,20 @@ def pcrelate_records_raw_device(ctx, bits, words_per_sample: int, num_sites: int
     dev = f"cuda:{ctx.device}"
     if out is not None:
         _device_tensor(ctx.device, out, "out", torch.int32, cols=6)
-        max_records = out.shape[0] if max_records is None else max_records
-        if _count(max_records, "max_records") > out.shape[0]:
-            raise ValueError(f"out holds {out.shape[0]} records, max_records is {max_records}")
+        max_records = _out_capacity(out, max_records)
     count = C.c_uint64(0)
 
-    def call(records, capacity):
-        return ctx.lib.cuking_pcrelate_records(
+    def call(capacity):
+        records = out if out is not None else torch.empty((max(capacity, 1), 6),
+                                                          dtype=torch.int32, device=dev)
+        return records, ctx.lib.cuking_pcrelate_records(
             ctx.handle, bits.data_ptr(), num_stored, words_per_sample, num_sites, x.data_ptr(),
             max(x.stride(0), d), beta.data_ptr(), max(beta.stride(0), d), d, lo, hi,
             C.byref(block.c), min_kin, records.data_ptr() if capacity else None, capacity,
             C.byref(count), _stream_handle(stream))
 
-    grow = max_records is None
-    capacity = _default_records(block) if grow else _count(max_records, "max_records")
-    records = out if out is not None else torch.empty((max(capacity, 1), 6), dtype=torch.int32,
-                                                      device=dev)
-    status = call(records, capacity)
-    if status == _lib.ERR_RESOURCE_EXHAUSTED and grow:
-        capacity = int(count.value)
-        records = torch.empty((capacity, 6), dtype=torch.int32, device=dev)
-        status = call(records, capacity)
-    if status == _lib.ERR_RESOURCE_EXHAUSTED:
-        raise _exhausted(int(count.value))
-    check(status)
+    records = _counted_buffer(call, _default_records(block), max_records, "max_records", count,
+                              "num_records")
     return records, int(count.value)
 
 

@@ -19,39 +19,14 @@
 #include <vector>
 
 #include "cuking_amd.h"
+#include "ibd_driver_common.h"
 
 namespace {
-
-uint64_t g_state = 0x9E3779B97F4A7C15ull;
-uint64_t next_random() {
-  g_state = g_state * 6364136223846793005ull + 1442695040888963407ull;
-  uint64_t x = g_state;
-  x ^= x >> 33;
-  x *= 0xFF51AFD7ED558CCDull;
-  x ^= x >> 33;
-  return x;
-}
-
-int g_failures = 0;
-void fail(const char *what, uint32_t sites, uint64_t extra) {
-  fprintf(stderr, "%s: %u sites (%llu)\n", what, sites, (unsigned long long)extra);
-  ++g_failures;
-}
 
 typedef std::tuple<uint32_t, uint32_t, uint32_t, uint32_t> Seg;
 struct Run {
   uint32_t a, b;
 };
-
-uint32_t code_of(const uint64_t *row, uint32_t plane, uint32_t s) {
-  return (uint32_t)((row[s >> 6] >> (s & 63)) & 1) |
-         (uint32_t)((row[plane + (s >> 6)] >> (s & 63)) & 1) << 1;
-}
-void set_code(uint64_t *row, uint32_t plane, uint32_t s, uint32_t code) {
-  const uint64_t bit = 1ull << (s & 63);
-  row[s >> 6] = (row[s >> 6] & ~bit) | ((code & 1) ? bit : 0);
-  row[plane + (s >> 6)] = (row[plane + (s >> 6)] & ~bit) | ((code & 2) ? bit : 0);
-}
 
 void run_shape(uint32_t sites, bool groups, bool positions, uint32_t stride, uint32_t min_sites,
                uint32_t bridge_sites) {
@@ -184,14 +159,6 @@ void run_shape(uint32_t sites, bool groups, bool positions, uint32_t stride, uin
           return fail("the strict call", sites, found);
       }
     }
-  }
-}
-
-void expect(const char *what, cuking_status got, cuking_status want) {
-  if (got != want) {
-    fprintf(stderr, "%s: status %d, expected %d (%s)\n", what, (int)got, (int)want,
-            cuking_last_error());
-    ++g_failures;
   }
 }
 

@@ -1,0 +1,45 @@
+// What the stand-alone drivers of the IBD and ROH host twins share (ibd_host_driver.cc,
+// ibd_bridge_host_driver.cc, ibd_scan_host_driver.cc, roh_host_driver.cc): the random numbers,
+// the failure count and its two reporters, and the genotype code of a site of a bitset row.
+#ifndef CUKING_AMD_TESTS_IBD_DRIVER_COMMON_H_
+#define CUKING_AMD_TESTS_IBD_DRIVER_COMMON_H_
+
+#include <cstdint>
+#include <cstdio>
+
+#include "cuking_amd.h"
+
+inline uint64_t g_state = 0x9E3779B97F4A7C15ull;
+inline uint64_t next_random() {
+  g_state = g_state * 6364136223846793005ull + 1442695040888963407ull;
+  uint64_t x = g_state;
+  x ^= x >> 33;
+  x *= 0xFF51AFD7ED558CCDull;
+  x ^= x >> 33;
+  return x;
+}
+
+inline int g_failures = 0;
+inline void fail(const char *what, uint32_t sites, uint64_t extra) {
+  fprintf(stderr, "%s: %u sites (%llu)\n", what, sites, (unsigned long long)extra);
+  ++g_failures;
+}
+inline void expect(const char *what, cuking_status got, cuking_status want) {
+  if (got != want) {
+    fprintf(stderr, "%s: status %d, expected %d (%s)\n", what, (int)got, (int)want,
+            cuking_last_error());
+    ++g_failures;
+  }
+}
+
+inline uint32_t code_of(const uint64_t *row, uint32_t plane, uint32_t s) {
+  return (uint32_t)((row[s >> 6] >> (s & 63)) & 1) |
+         (uint32_t)((row[plane + (s >> 6)] >> (s & 63)) & 1) << 1;
+}
+inline void set_code(uint64_t *row, uint32_t plane, uint32_t s, uint32_t code) {
+  const uint64_t bit = 1ull << (s & 63);
+  row[s >> 6] = (row[s >> 6] & ~bit) | ((code & 1) ? bit : 0);
+  row[plane + (s >> 6)] = (row[plane + (s >> 6)] & ~bit) | ((code & 2) ? bit : 0);
+}
+
+#endif  // CUKING_AMD_TESTS_IBD_DRIVER_COMMON_H_

@@ -15,24 +15,9 @@
 #include <vector>
 
 #include "cuking_amd.h"
+#include "ibd_driver_common.h"
 
 namespace {
-
-uint64_t g_state = 0x9E3779B97F4A7C15ull;
-uint64_t next_random() {
-  g_state = g_state * 6364136223846793005ull + 1442695040888963407ull;
-  uint64_t x = g_state;
-  x ^= x >> 33;
-  x *= 0xFF51AFD7ED558CCDull;
-  x ^= x >> 33;
-  return x;
-}
-
-int g_failures = 0;
-void fail(const char *what, uint32_t sites, uint64_t extra) {
-  fprintf(stderr, "%s: %u sites (%llu)\n", what, sites, (unsigned long long)extra);
-  ++g_failures;
-}
 
 void run_shape(uint32_t n, uint32_t sites, bool groups, bool positions, uint32_t min_sites,
                const cuking_submatrix &block, uint64_t min_total) {
@@ -95,14 +80,6 @@ void run_shape(uint32_t n, uint32_t sites, bool groups, bool positions, uint32_t
     if (found != total) return fail("count", sites, found);
     if (room && memcmp(out.get(), want.data(), room * sizeof(cuking_ibd_pair)) != 0)
       return fail("records", sites, mode);
-  }
-}
-
-void expect(const char *what, cuking_status got, cuking_status want) {
-  if (got != want) {
-    fprintf(stderr, "%s: status %d, expected %d (%s)\n", what, (int)got, (int)want,
-            cuking_last_error());
-    ++g_failures;
   }
 }
 

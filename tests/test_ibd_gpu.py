@@ -80,6 +80,20 @@ def test_a_second_stream_and_a_second_call_give_the_same_bytes(ctx):
     assert ibd.rows_to_host(rows).tobytes() == first_rows[order].tobytes()
 
 
+def test_the_waits_of_one_call(ctx):
+    """One raw call waits once, for its count, and without a list not at all (no positions: no
+    check of them to wait for)."""
+    case = next(c for c in ic.CASES if c.name.startswith("two steps"))
+    inp = ic.inputs(case)
+    bits = _device_bits(inp)
+    for kw, want in ((dict(max_segments=1 << 16), 1), (dict(), 0)):
+        before = ctx.get_option("host_syncs")
+        _, segments, found = ctx.ibd_segments_raw(bits, inp.wps, case.sites, inp.index,
+                                                  min_sites=case.min_sites, **kw)
+        assert ctx.get_option("host_syncs") - before == want
+        assert (segments is not None) == bool(want) and (want or found == 0)
+
+
 def test_launches_are_split(ctx):
     """A cap of one workgroup per launch sends the 15 pairs (four to a workgroup) out in four
     launches, three of them with a pair base above 0: the bytes of the one launch."""

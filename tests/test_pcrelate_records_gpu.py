@@ -164,6 +164,11 @@ def test_overflow_counts_exactly_and_writes_nothing_behind_the_buffer(ctx):
     full, total = device_records(case, t)
     assert total > 64
     true_set = {(int(r["sample_i"]), int(r["sample_j"])): r["kin"].tobytes() for r in full}
+    before = ctx.get_option("host_syncs")
+    _, count = ctx.pcrelate_records_raw(bits, inp.wps, case.sites, x, beta, inp.lo, inp.hi, t,
+                                        block=case.block, max_records=total)
+    assert count == total
+    assert ctx.get_option("host_syncs") - before == 1   # (the count, and nothing else)
     for room in (total - 1, total // 2, 0):
         buf = torch.full((room + 3, 6), -1414812757, dtype=torch.int32,
                          device=f"cuda:{ctx.device}")      # (0xABABABAB)
