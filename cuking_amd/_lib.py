@@ -155,6 +155,8 @@ SIGNATURES = {
     "cuking_unrelated_set": (_int, [_vp, _vp, _u64, _u32, _f32, _vp, _vp, _vp, C.POINTER(_u32),
                                     _vp]),
     "cuking_site_counts": (_int, [_vp, _vp, _u32, _u32, _vp, _vp]),
+    "cuking_test_site_gather": (_int, [_vp, _vp, _u32, _u32, _vp, _int, _vp, _int, _vp, _u64,
+                                       _vp, _vp]),
     "cuking_sample_counts": (_int, [_vp, _vp, _u32, _u32, _u32, _vp, _vp]),
     "cuking_site_mask_host": (_int, [_vp, _u32, _u32, C.POINTER(CSiteFilter), _vp, _vp,
                                      C.POINTER(_u32)]),

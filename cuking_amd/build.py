@@ -96,6 +96,8 @@ def build_library(force: bool = False, save_temps: bool = False) -> Path:
     problems = check_mfma_loops(cwd / "king_mfma-hip-amdgcn-amd-amdhsa-gfx950.s")
     problems += check_filter_loop(cwd / "king_filter-hip-amdgcn-amd-amdhsa-gfx950.s")
     problems += check_no_scratch(cwd / "king_bed-hip-amdgcn-amd-amdhsa-gfx950.s", "pack_bed_kernel")
+    problems += check_no_scratch(cwd / "king_sort-hip-amdgcn-amd-amdhsa-gfx950.s",
+                                 "gather_sites_kernel")
     for kernel in ("site_counts_kernel", "sample_counts_kernel", "compact_sites_kernel"):
         problems += check_no_scratch(cwd / "king_site_qc-hip-amdgcn-amd-amdhsa-gfx950.s", kernel)
     for kernel in ("transpose_sites_kernel", "ld_edges_kernel"):

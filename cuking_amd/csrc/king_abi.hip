@@ -178,6 +178,10 @@ struct cuking_ctx {
   // staged pass.
   int filter_site_order = -1;
   uint32_t filter_site_order_min_tiles = (uint32_t)kSiteOrderMinTiles;  // (test hook)
+  // The kernel that writes the ordered copy (site_gather_pick): -1 (default) 4 samples per
+  // LDS field where the sites fit, else 2, else the ballot kernel; 0 the ballot kernel; 4 / 2
+  // forced (4 is refused by the conversion where it does not fit).  Same bytes either way.
+  int filter_site_gather = -1;
   // What the last conversion that built a curve read from it (read-only keys
   // "site_order_share", "site_order_stored_share", "site_order_sigma_e6", "site_order_on").
   SiteOrderForecast order_forecast = {0, 0, false};
@@ -823,6 +827,11 @@ cuking_status prepare(cuking_ctx *ctx, const cuking_submatrix &sm,
                   (total_tiles(tiles) >= ctx->filter_site_order_min_tiles &&
                    geo.k_words / 8 >= filter_check_min_steps()));
   }
+  const int site_gather = site_gather_pick(ctx->filter_site_gather, words_per_sample);
+  if (order_wanted && site_gather < 0)
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT,
+                       "filter_site_gather %d: %u words per sample do not fit the gather's LDS",
+                       ctx->filter_site_gather, words_per_sample);
   // (... and a layout converted under another answer to that is another block's as well.  A
   //  layout that is reused keeps the decision of the call that converted it, whatever
   //  threshold this one has: its share comes from the curve and this call's threshold.)
@@ -933,14 +942,21 @@ cuking_status prepare(cuking_ctx *ctx, const cuking_submatrix &sm,
       pr.order_no_left = site_order ? 0u : kSiteOrderNoTrust;
     }
     pr.site_order = site_order;
+    // The byte-wide gather of a diagonal block (plane sample = stored sample) counts the
+    // statistics on the words it assembles: the separate kernel keeps the padding samples
+    // behind the stored ones, which read nothing.
+    const bool fused_stats = site_order && site_gather > 0 && geo.diag != 0;
     if (site_order) {
       cuking_ctx::StreamScratch *e = stream_entry(ctx, stream);
+      const SiteGatherStats fused = {stats_arrays(geo, ctx->planes), geo, se};
       HIP_TRY(launch_site_permute(d_bit_sets, num_stored, words_per_sample, e->site_order.p,
-                                  order_layout, stream));
+                                  order_layout, site_gather, fused_stats ? &fused : nullptr,
+                                  stream));
       layout_bits = reinterpret_cast<const uint64_t *>(static_cast<const uint8_t *>(e->site_order.p) +
                                                        order_layout.permuted);
     }
-    HIP_TRY(launch_sample_stats(layout_bits, words_per_sample, geo, ctx->planes, sb, se, stream));
+    HIP_TRY(launch_sample_stats(layout_bits, words_per_sample, geo, ctx->planes,
+                                fused_stats ? num_stored : sb, se, stream));
     HIP_TRY(launch_sample_order(geo, words_per_sample, ctx->planes, sb, se,
                                 !dense_order &&
                                     (ctx->filter_sort == 2 || (ctx->filter_sort == 1 && whole)),
@@ -1071,6 +1087,7 @@ struct Option {
   int64_t (*get)(const cuking_ctx *);
   void (*set)(cuking_ctx *, int64_t);
   int64_t hole = INT64_MIN;  // a value inside the bounds that is refused as well
+  bool (*valid)(int64_t) = nullptr;  // what else a value inside the bounds must satisfy
 };
 
 // Reads and stores a field of the context.
@@ -1098,6 +1115,9 @@ const Option kOptions[] = {
      CTX_FIELD(filter_site_order)},
     {"filter_site_order_min_tiles", 0, 1 << 30, "filter_site_order_min_tiles outside [0, 2^30]",
      0, kInvalidatesLayout, CTX_FIELD(filter_site_order_min_tiles)},
+    {"filter_site_gather", -1, 4, "filter_site_gather outside {-1, 0, 2, 4}", 0,
+     kInvalidatesLayout, CTX_FIELD(filter_site_gather), /*hole=*/INT64_MIN,
+     [](int64_t v) { return v == -1 || (v & 1) == 0; }},
     {"filter_check0", 0, 2, "filter_check0 outside [0, 2]", 0, 0, CTX_FIELD(filter_check0)},
     {"filter_check1", 0, 1 + kNumCheckShares, "filter_check1 outside {0, 1, 3 .. %u}",
      1 + kNumCheckShares, 0, CTX_FIELD(filter_check1), /*hole=*/2},
@@ -1265,7 +1285,7 @@ cuking_status cuking_ctx_set_option(cuking_ctx *ctx, const char *key,
     return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "null argument");
   const Option *o = find_option(key);
   if (o == nullptr) return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "unknown option %s", key);
-  if (value < o->lo || value > o->hi || value == o->hole)
+  if (value < o->lo || value > o->hi || value == o->hole || (o->valid && !o->valid(value)))
     return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, o->error, o->error_arg);
   if ((o->effects & kResizesSlabs) && value != o->get(ctx)) {
     HIP_TRY(hipDeviceSynchronize());
@@ -2069,6 +2089,65 @@ cuking_status cuking_site_counts(cuking_ctx *ctx, const uint64_t *d_bit_set,
   BIND_OR_RETURN(ctx);
   HIP_TRY(launch_site_counts(d_bit_set, num_stored, words_per_sample, d_counts,
                              (hipStream_t)stream));
+  return CUKING_OK;
+}
+
+cuking_status cuking_test_site_gather(cuking_ctx *ctx, const uint64_t *d_bit_set,
+                                      uint32_t num_stored, uint32_t words_per_sample,
+                                      const uint32_t *d_order, int gather, uint64_t *d_permuted,
+                                      int stats, void *d_stats, uint64_t stats_bytes,
+                                      uint64_t *layout, void *stream) {
+  if (ctx == nullptr) return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "null context");
+  if (d_bit_set == nullptr || d_order == nullptr || d_permuted == nullptr)
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "site gather: null pointer");
+  if (num_stored == 0 || words_per_sample < 2)
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "site gather: no samples or no plane words");
+  if ((gather != 0 && gather != 2 && gather != 4) ||
+      site_gather_pick(gather, words_per_sample) != gather)
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT,
+                       "site gather: form %d does not serve %u words per sample", gather,
+                       words_per_sample);
+  if (stats < 0 || stats > 2 || (stats == 1 && gather == 0))
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT,
+                       "site gather: statistics %d with form %d (0 none, 1 inside the byte-wide "
+                       "gather, 2 the separate kernel)", stats, gather);
+  // The statistics of a whole diagonal block of num_stored samples in the filter variant's
+  // geometry: stats, cum, the sums and the check steps one behind the other.
+  cuking_submatrix sm;
+  cuking_status status = cuking_submatrix_init(&sm, num_stored, 1, 0);
+  if (status != CUKING_OK) return status;
+  const PlaneGeometry geo = make_geometry(sm, words_per_sample, tiled_variant(7));
+  const uint64_t off_cum = (uint64_t)geo.s_stride * sizeof(float2);
+  const uint64_t off_sums = off_cum + (uint64_t)geo.s_stride * (kNumCum + 1) * sizeof(float);
+  const uint64_t off_steps = off_sums + 64, bytes = off_steps + 64;
+  if (layout != nullptr) {
+    layout[0] = geo.s_stride;
+    layout[1] = off_cum;
+    layout[2] = off_sums;
+    layout[3] = off_steps;
+    layout[4] = bytes;
+  }
+  if (stats != 0 && (d_stats == nullptr || stats_bytes < bytes))
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT,
+                       "site gather: the statistics need %llu bytes", (unsigned long long)bytes);
+  BIND_OR_RETURN(ctx);
+  uint8_t *base = static_cast<uint8_t *>(d_stats);
+  SiteGatherStats fused = {};
+  if (stats != 0) {
+    fused.to = {reinterpret_cast<float2 *>(base), reinterpret_cast<float *>(base + off_cum),
+                reinterpret_cast<unsigned long long *>(base + off_sums),
+                reinterpret_cast<uint32_t *>(base + off_steps)};
+    fused.geo = geo;
+    fused.s_end = geo.s_stride;
+    HIP_TRY(hipMemsetAsync(base + off_sums, 0, 64, (hipStream_t)stream));
+  }
+  HIP_TRY(launch_site_gather(d_bit_set, num_stored, words_per_sample, d_order, d_permuted, gather,
+                             stats == 1 ? &fused : nullptr, (hipStream_t)stream));
+  // (the padding samples behind the stored ones, or with 2 every plane sample, as prepare())
+  if (stats != 0)
+    HIP_TRY(launch_sample_stats_to(d_permuted, words_per_sample, geo, fused.to,
+                                   stats == 1 ? num_stored : 0, geo.s_stride,
+                                   (hipStream_t)stream));
   return CUKING_OK;
 }
 

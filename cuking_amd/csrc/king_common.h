@@ -629,6 +629,23 @@ inline void to_quadrants(TiledArgs *a, uint64_t *num_units) {
 hipError_t launch_sample_stats(const uint64_t *d_bit_sets, uint32_t words_per_sample,
                                const PlaneGeometry &geo, uint4 *d_planes, uint32_t s_begin,
                                uint32_t s_end, hipStream_t stream);
+// Where the statistics go: (|Y| - |M|, |H|) per plane sample, the kNumCum + 1 rows of the
+// cumulative u~ (s_stride apart), the cohort's three sums and the check steps -- of a
+// workspace (stats_arrays) or a caller's (tests).
+struct SampleStatsArrays {
+  float2 *stats;
+  float *cum;
+  unsigned long long *sums;
+  uint32_t *steps;
+};
+inline SampleStatsArrays stats_arrays(const PlaneGeometry &geo, uint4 *d_planes) {
+  return {plane_tmp_stats(d_planes, geo), plane_tmp_prefix(d_planes, geo),
+          const_cast<unsigned long long *>(plane_cohort_sums(d_planes, geo)),
+          const_cast<uint32_t *>(plane_check_steps(d_planes, geo))};
+}
+hipError_t launch_sample_stats_to(const uint64_t *d_bit_sets, uint32_t words_per_sample,
+                                  const PlaneGeometry &geo, const SampleStatsArrays &to,
+                                  uint32_t s_begin, uint32_t s_end, hipStream_t stream);
 // Test hook, process-wide: bitsets of fewer k-steps get no check points (default 64).
 void set_filter_check_min_steps(uint32_t steps);
 uint32_t filter_check_min_steps();
@@ -656,9 +673,31 @@ hipError_t launch_site_order(const uint64_t *d_bit_sets, uint32_t num_stored,
                              uint32_t words_per_sample, const PlaneGeometry &geo, void *d_scratch,
                              const SiteOrderScratch &layout, SiteCurve *d_curve,
                              hipStream_t stream);
+// `gather`: what site_gather_pick() made of "filter_site_gather" for this width -- 4 or 2
+// samples per LDS field (gather_sites_kernel, king_site_gather.h), 0 the ballot kernel
+// (permute_sites_kernel); -1 from site_gather_pick: the option forces a form that does not
+// fit.  The kernels write the same bytes.
+// `fused` (gather 4 or 2 only, a whole diagonal block: plane sample = stored sample): the
+// gather also leaves what sample_stats_kernel would leave for plane samples [0, num_stored)
+// of a conversion of plane samples [0, s_end) -- the same bytes, the cohort's sums from the
+// same samples --, counted on the output words while a wavefront holds them; the padding
+// samples behind them stay with launch_sample_stats.
+int site_gather_pick(int option, uint32_t words_per_sample);
+struct SiteGatherStats {
+  SampleStatsArrays to;
+  PlaneGeometry geo;
+  uint32_t s_end;
+};
 hipError_t launch_site_permute(const uint64_t *d_bit_sets, uint32_t num_stored,
                                uint32_t words_per_sample, void *d_scratch,
-                               const SiteOrderScratch &layout, hipStream_t stream);
+                               const SiteOrderScratch &layout, int gather,
+                               const SiteGatherStats *fused, hipStream_t stream);
+// The gather alone: d_permuted[sample][plane][d] = d_bit_sets[sample][plane][d_order[d]] for
+// the 64 * (words_per_sample / 2) sites of a plane (d_order: a permutation of them).
+hipError_t launch_site_gather(const uint64_t *d_bit_sets, uint32_t num_stored,
+                              uint32_t words_per_sample, const uint32_t *d_order,
+                              uint64_t *d_permuted, int gather, const SiteGatherStats *fused,
+                              hipStream_t stream);
 // What a curve forecasts for the rigorous check of an unrotated tile at threshold `thr`, in
 // 64ths of the k-steps (0: no check up to 62/64): `stored64` by the linear rule of stored
 // order, `order64` from the curve -- the arithmetic of the filter kernel (king_filter.hip

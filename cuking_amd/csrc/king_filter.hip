@@ -1364,14 +1364,21 @@ uint32_t filter_check_min_steps() { return g_check_min_steps.load(); }
 hipError_t launch_sample_stats(const uint64_t *d_bit_sets, uint32_t words_per_sample,
                                const PlaneGeometry &geo, uint4 *d_planes, uint32_t s_begin,
                                uint32_t s_end, hipStream_t stream) {
-  if (s_end > geo.s_stride) s_end = geo.s_stride;
-  if (s_begin >= s_end) return hipSuccess;
   // (in stored order, into the arrays the sample order is built from: king_sort.hip puts
   //  them into plane order)
-  float2 *stats = plane_tmp_stats(d_planes, geo);
-  float *prefix = plane_tmp_prefix(d_planes, geo);
-  unsigned long long *sums = const_cast<unsigned long long *>(plane_cohort_sums(d_planes, geo));
-  uint32_t *steps = const_cast<uint32_t *>(plane_check_steps(d_planes, geo));
+  return launch_sample_stats_to(d_bit_sets, words_per_sample, geo, stats_arrays(geo, d_planes),
+                                s_begin, s_end, stream);
+}
+
+hipError_t launch_sample_stats_to(const uint64_t *d_bit_sets, uint32_t words_per_sample,
+                                  const PlaneGeometry &geo, const SampleStatsArrays &to,
+                                  uint32_t s_begin, uint32_t s_end, hipStream_t stream) {
+  if (s_end > geo.s_stride) s_end = geo.s_stride;
+  if (s_begin >= s_end) return hipSuccess;
+  float2 *stats = to.stats;
+  float *prefix = to.cum;
+  unsigned long long *sums = to.sums;
+  uint32_t *steps = to.steps;
   CheckWords cw;
   const uint32_t all_steps = geo.k_words / 8;  // k-steps of 256 sites
   if (all_steps > kStatsMaxSteps) return hipErrorInvalidValue;

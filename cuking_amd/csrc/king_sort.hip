@@ -27,6 +27,8 @@
 #include <hipcub/hipcub.hpp>
 
 #include "king_common.h"
+#include "king_device.h"
+#include "king_site_gather.h"
 
 namespace cuking {
 
@@ -162,8 +164,10 @@ hipError_t launch_sample_order(const PlaneGeometry &geo, uint32_t words_per_samp
 //      pairs of samples, an exact integer;
 //   3. a STABLE descending sort of (weight, site): deterministic for one bitset, ties --
 //      monomorphic sites, and the padding of the last word behind them -- keep stored order;
-//   4. the bitset once more with every sample's sites in that order (permute_sites_kernel),
-//      in stream scratch: sample_stats_kernel and the T2 conversion read it instead of the
+//   4. the bitset once more with every sample's sites in that order (gather_sites_kernel,
+//      which counts the statistics of a diagonal block's samples on the way;
+//      permute_sites_kernel where "filter_site_gather" says 0), in stream scratch:
+//      sample_stats_kernel and the T2 conversion read it instead of the
 //      caller's and stay as they are.  Everything that recounts exactly (king_refine_kernel,
 //      the four-product kernel's codes) keeps reading the caller's bitset;
 //   5. the curve: the weight in front of every phase boundary, and sigma (SiteCurve).
@@ -318,6 +322,250 @@ __global__ __launch_bounds__(256) void permute_sites_kernel(
   // (words_per_sample odd: the word behind the two planes is never read by the conversion)
 }
 
+// The byte-wide gather (king_site_gather.h has its arithmetic).  A workgroup stages G samples
+// in LDS interleaved per site -- a thread takes source word w of all 2 G rows and turns its
+// eight 8 x 8 bit matrices (field x site) around: 64 sites' fields, one 64- or 32-byte
+// store --, then every wavefront assembles kGatherBatch destination words at a time:
+//   1. lane l reads the field of order[64 W + l] for each word W of the batch (one byte read
+//      serves all G samples and both planes) and puts it at [W][l] of the wavefront's tile;
+//   2. lane l takes eight neighbouring sites of one word (one 8-byte read), turns the 8 x 8
+//      matrix (site x field) around and has byte l & 7 of that word for every field, which
+//      goes to [field][word][byte] of the tile (in place: everything is read before anything
+//      is written, and the LDS serves a wavefront's requests in order);
+//   3. the tile IS the 2 G x kGatherBatch output words: a lane stores G / 2 of them, 16 lanes
+//      one 128-byte run of a (sample, plane) row.
+// No workgroup barrier behind the staging: a tile belongs to one wavefront.
+constexpr uint32_t kGatherLdsMax = 160 * 1024;  // a CU's LDS: one workgroup per CU
+
+__device__ __forceinline__ void wave_lds_order() {
+  // (lanes of one wavefront hand data to each other through LDS: the compiler keeps the
+  //  accesses in program order, the hardware serves them in that order)
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+}
+
+// STATS: the statistics of sample_stats_kernel (king_filter.hip) for the G samples as well,
+// where plane sample = stored sample.  After step 2 the tile holds both planes of 16 words
+// of every sample: lane l counts word l & 15 of sample l >> 4 with that kernel's
+// expressions -- the totals in registers over the batches, the per-phase sums by integer
+// adds in LDS (any order: the same integers) --, and behind the last batch wavefront g does
+// sample g's scan and writes with that kernel's float conversions.  The cohort's sums take
+// the samples that kernel's grid of `stats_grid` workgroups of four would have added.
+struct GatherStatsArgs {
+  float2 *stats;
+  float *cum;
+  unsigned long long *sums;
+  uint32_t *steps_out;
+  uint32_t s_stride, all_steps, stats_grid;
+  uint32_t steps[kNumCheckShares];
+};
+// LDS behind the tiles: kNumPhases sums and four totals (|Y|, |M|, |H|, S) per sample.
+constexpr uint32_t kGatherStatsBytes = 4 * (kNumPhases + 4) * 4;
+
+template <int G, bool STATS>
+__global__ __launch_bounds__(1024) void gather_sites_kernel(
+    const uint64_t *__restrict__ bits, uint64_t *__restrict__ out,
+    const uint32_t *__restrict__ order, uint32_t num_stored, uint32_t words_per_sample,
+    GatherStatsArgs st) {
+  extern __shared__ uint4 gather_lds[];  // the sites' fields, then a tile per wavefront
+  static_assert(G == 2 || G == 4, "a nibble or a byte per site");
+  static_assert(kGatherBatch % 8 == 0 && (2 * G * kGatherBatch) % 64 == 0, "whole rounds");
+  static_assert(kGatherBatch == 16, "the statistics: 16 lanes per sample");
+  const uint32_t P = words_per_sample / 2;
+  const uint32_t s0 = blockIdx.x * G;
+  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6, waves = blockDim.x >> 6;
+  uint8_t *site = reinterpret_cast<uint8_t *>(gather_lds);
+  uint8_t *tile = site + ((gather_site_bytes(G, P) + 15u) & ~15u) + wave * kGatherTileBytes;
+  // [G][kNumPhases] per-phase sums, then [G][4] totals
+  int32_t *phase_sum = reinterpret_cast<int32_t *>(site + ((gather_site_bytes(G, P) + 15u) & ~15u) +
+                                                   waves * kGatherTileBytes);
+  int32_t *totals = phase_sum + G * kNumPhases;
+  if (STATS) {
+    for (uint32_t i = threadIdx.x; i < G * (kNumPhases + 4); i += blockDim.x) phase_sum[i] = 0;
+    if (blockIdx.x == 0) {
+#pragma unroll
+      for (uint32_t k = 0; k < kNumCheckShares; ++k)
+        if (threadIdx.x == k) st.steps_out[k] = st.steps[k];
+    }
+  }
+  int32_t yc = 0, mc = 0, hc = 0, sa = 0;  // of word lane & 15 of sample lane >> 4, over the batches
+
+  const uint64_t *het[G];
+#pragma unroll
+  for (int g = 0; g < G; ++g) {
+    const uint32_t s = s0 + g < num_stored ? s0 + g : num_stored - 1;  // (repeats: not stored)
+    het[g] = bits + (uint64_t)s * words_per_sample;
+  }
+  for (uint32_t w = threadIdx.x; w < P; w += blockDim.x) {
+    uint64_t f[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+      f[gather_field_bit(g, 0)] = het[g][w];
+      f[gather_field_bit(g, 1)] = het[g][P + w];
+    }
+    if (G == 4) {
+      uint4 *dst = reinterpret_cast<uint4 *>(site + 64 * w);
+#pragma unroll
+      for (uint32_t b = 0; b < 8; b += 2) {
+        const uint64_t lo = gather_interleave8(f, b), hi = gather_interleave8(f, b + 1);
+        dst[b / 2] = make_uint4((uint32_t)lo, (uint32_t)(lo >> 32), (uint32_t)hi, (uint32_t)(hi >> 32));
+      }
+    } else {
+      uint4 *dst = reinterpret_cast<uint4 *>(site + 32 * w);
+#pragma unroll
+      for (uint32_t b = 0; b < 8; b += 4)
+        dst[b / 4] = make_uint4(gather_pack_nibbles(gather_interleave8(f, b)),
+                                gather_pack_nibbles(gather_interleave8(f, b + 1)),
+                                gather_pack_nibbles(gather_interleave8(f, b + 2)),
+                                gather_pack_nibbles(gather_interleave8(f, b + 3)));
+    }
+  }
+  __syncthreads();
+
+  constexpr uint32_t kRounds = kGatherBatch / 8;          // 8 words of 8 bytes: 64 lanes
+  constexpr uint32_t kOutRounds = 2 * G * kGatherBatch / 64;
+  uint64_t *tile64 = reinterpret_cast<uint64_t *>(tile);
+  const uint32_t last_site = 64 * P - 1;
+  for (uint32_t w0 = kGatherBatch * wave; w0 < P; w0 += kGatherBatch * waves) {
+    uint32_t src[kGatherBatch];
+#pragma unroll
+    for (uint32_t k = 0; k < kGatherBatch; ++k) {
+      const uint32_t W = w0 + k < P ? w0 + k : P - 1;  // (behind the plane: a repeat, not stored)
+      const uint32_t at = order[64 * W + lane];
+      src[k] = at < last_site ? at : last_site;        // (a permutation: never taken)
+    }
+    uint32_t field[kGatherBatch];
+#pragma unroll
+    for (uint32_t k = 0; k < kGatherBatch; ++k) field[k] = site[gather_byte_index(G, src[k])];
+#pragma unroll
+    for (uint32_t k = 0; k < kGatherBatch; ++k)
+      tile[64 * k + lane] = (uint8_t)gather_field_of(G, src[k], field[k]);
+    wave_lds_order();
+    uint64_t x[kRounds];
+#pragma unroll
+    for (uint32_t r = 0; r < kRounds; ++r) x[r] = tile64[64 * r + lane];
+    wave_lds_order();
+#pragma unroll
+    for (uint32_t r = 0; r < kRounds; ++r) {
+      const uint64_t y = gather_assemble8(x[r]);
+      const uint32_t k = 8 * r + (lane >> 3), b = lane & 7;
+#pragma unroll
+      for (uint32_t f = 0; f < 2 * G; ++f) tile[gather_out_byte(f, k, b)] = (uint8_t)(y >> (8 * f));
+    }
+    wave_lds_order();
+#pragma unroll
+    for (uint32_t r = 0; r < kOutRounds; ++r) {
+      const uint32_t i = 64 * r + lane, f = gather_out_field(i), k = gather_out_word(i);
+      const uint64_t word = tile64[i];
+      const uint32_t s = s0 + f / 2;
+      if (w0 + k < P && s < num_stored)
+        out[(uint64_t)s * words_per_sample + (f & 1) * P + w0 + k] = word;
+    }
+    if (STATS) {
+      // (sample_stats_kernel's expressions, word for word)
+      const uint32_t g = (lane >> 4) & (G - 1), w = w0 + (lane & 15);
+      const bool in = (lane >> 4) < G && w < P;  // (beyond the plane: contributes nothing)
+      const uint64_t h = in ? tile64[gather_field_bit(g, 0) * kGatherBatch + (lane & 15)] : 0ull;
+      const uint64_t v = in ? tile64[gather_field_bit(g, 1) * kGatherBatch + (lane & 15)] : 0ull;
+      const int32_t y = in ? __popcll(~h) : 0;
+      const int32_t m = __popcll(h & v);
+      yc += y;
+      mc += m;
+      hc += __popcll(h & ~v);
+      const uint64_t hom_a = in ? ~h & 0xFFFFFFFF00000000ull : 0ull;
+      const int32_t t_a = __popcll(hom_a & ~v) - __popcll(hom_a & v);
+      sa += t_a;
+      // (a k-step is 4 words: 4 neighbouring lanes, the batch starts at a multiple of 16)
+      int32_t d = y - m + 2 * t_a;
+      d += __shfl_xor(d, 1);
+      d += __shfl_xor(d, 2);
+      if ((lane & 3) == 0 && in) {
+        const uint32_t x = (kNumPhases * ((w >> 2) + 1) - 1) / st.all_steps;
+        atomicAdd(&phase_sum[g * kNumPhases + (x < kNumPhases ? x : kNumPhases - 1)], d);
+      }
+    }
+    wave_lds_order();
+  }
+  // (words_per_sample odd: the word behind the two planes is never read by the conversion)
+  if (!STATS) return;
+#pragma unroll
+  for (int off = 8; off > 0; off >>= 1) {
+    yc += __shfl_xor(yc, off);
+    mc += __shfl_xor(mc, off);
+    hc += __shfl_xor(hc, off);
+    sa += __shfl_xor(sa, off);
+  }
+  if ((lane & 15) == 0 && (lane >> 4) < G) {
+    int32_t *t = totals + 4 * (lane >> 4);
+    atomicAdd(t, yc);
+    atomicAdd(t + 1, mc);
+    atomicAdd(t + 2, hc);
+    atomicAdd(t + 3, sa);
+  }
+  __syncthreads();
+  const uint32_t ps = s0 + wave;
+  if (wave >= G || ps >= num_stored) return;  // whole wavefront
+  yc = totals[4 * wave];
+  mc = totals[4 * wave + 1];
+  hc = totals[4 * wave + 2];
+  sa = totals[4 * wave + 3];
+  // inclusive scan over the phases -- lane l holds phases 2 l and 2 l + 1 --: the count in
+  // front of boundary x + 1 is the scan's value at phase x
+  static_assert(kNumPhases == 128, "two phases per lane");
+  const int32_t p0 = phase_sum[wave * kNumPhases + 2 * lane];
+  const int32_t p1 = phase_sum[wave * kNumPhases + 2 * lane + 1];
+  int32_t run = p0 + p1;
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    const int32_t up = __shfl_up(run, off);
+    if ((int)lane >= off) run += up;
+  }
+  // (n_A in front of boundary x: 128 per k-step)
+  st.cum[(size_t)(2 * lane) * st.s_stride + ps] =
+      (float)(run - p1 + (int32_t)(128u * phase_step(st.all_steps, 2 * lane + 1)));
+  if (2 * lane + 1 < kNumCum)
+    st.cum[(size_t)(2 * lane + 1) * st.s_stride + ps] =
+        (float)(run + (int32_t)(128u * phase_step(st.all_steps, 2 * lane + 2)));
+  if (lane == 0) {
+    st.stats[ps] = make_float2((float)(yc - mc), (float)hc);
+    st.cum[(size_t)kNumCum * st.s_stride + ps] =
+        (float)(yc - mc + 2 * sa + (int32_t)(128u * st.all_steps));
+    // (the samples sample_stats_kernel's workgroup ps / 4 of stats_grid would have added)
+    if (((ps >> 2) & 15) == 0 || st.stats_grid < 64) {
+      relaxed_add(st.sums, 1ull);
+      relaxed_add(st.sums + 1, (unsigned long long)mc);
+      relaxed_add(st.sums + 2, (unsigned long long)hc);
+    }
+  }
+}
+
+// Threads of a gather_sites_kernel<G> workgroup for `P` words per plane: as many wavefronts
+// as leave room for their tiles (and the statistics' sums, whether they are taken or not: one
+// rule per width) behind the staged sites; 0: the sites do not fit.
+uint32_t gather_lds_bytes(int group, uint32_t P, uint32_t threads) {
+  return ((gather_site_bytes((uint32_t)group, P) + 15u) & ~15u) + (threads / 64) * kGatherTileBytes +
+         kGatherStatsBytes;
+}
+uint32_t gather_threads(int group, uint32_t P) {
+  for (uint32_t threads = 1024; threads >= 512; threads /= 2)
+    if (gather_lds_bytes(group, P, threads) <= kGatherLdsMax) return threads;
+  return 0;
+}
+
+template <int G, bool STATS>
+hipError_t launch_gather_form(const uint64_t *d_bit_sets, uint32_t num_stored,
+                              uint32_t words_per_sample, const uint32_t *d_order,
+                              uint64_t *d_permuted, const GatherStatsArgs &st, hipStream_t stream) {
+  const uint32_t P = words_per_sample / 2, threads = gather_threads(G, P);
+  if (threads == 0) return hipErrorInvalidValue;
+  const hipError_t e = allow_dynamic_lds<gather_sites_kernel<G, STATS>>(kGatherLdsMax);
+  if (e != hipSuccess) return e;
+  gather_sites_kernel<G, STATS><<<dim3((num_stored + G - 1) / G), dim3(threads),
+                                  gather_lds_bytes(G, P, threads), stream>>>(
+      d_bit_sets, d_permuted, d_order, num_stored, words_per_sample, st);
+  return hipGetLastError();
+}
+
 size_t up256(size_t x) { return (x + 255) / 256 * 256; }
 
 // bits of a weight for `n` samples: 6 n^2 / 2 at most
@@ -384,22 +632,71 @@ hipError_t launch_site_order(const uint64_t *d_bit_sets, uint32_t num_stored,
   return hipGetLastError();
 }
 
-hipError_t launch_site_permute(const uint64_t *d_bit_sets, uint32_t num_stored,
-                               uint32_t words_per_sample, void *d_scratch,
-                               const SiteOrderScratch &l, hipStream_t stream) {
-  if (l.bytes == 0 || d_scratch == nullptr) return hipErrorInvalidValue;
-  const uint32_t P = words_per_sample / 2, sites = P * 64;
-  uint8_t *base = static_cast<uint8_t *>(d_scratch);
-  const uint32_t *vals_out = reinterpret_cast<const uint32_t *>(base + l.vals) + sites;
-  uint64_t *permuted = reinterpret_cast<uint64_t *>(base + l.permuted);
+int site_gather_pick(int option, uint32_t words_per_sample) {
+  const uint32_t P = words_per_sample / 2;
+  if (P == 0 || (size_t)P * 16 > kOrderLdsBytes) return option <= 0 ? 0 : -1;
+  if (option == 0) return 0;
+  if ((option == -1 || option == 4) && gather_threads(4, P) != 0) return 4;
+  if ((option == -1 || option == 2) && gather_threads(2, P) != 0) return 2;
+  return option == -1 ? 0 : -1;
+}
+
+hipError_t launch_site_gather(const uint64_t *d_bit_sets, uint32_t num_stored,
+                              uint32_t words_per_sample, const uint32_t *d_order,
+                              uint64_t *d_permuted, int gather, const SiteGatherStats *fused,
+                              hipStream_t stream) {
+  const uint32_t P = words_per_sample / 2;
+  if (num_stored == 0 || P == 0 || (size_t)P * 16 > kOrderLdsBytes) return hipErrorInvalidValue;
+  if (gather == 4 || gather == 2) {
+    GatherStatsArgs st = {};
+    if (fused != nullptr) {
+      const PlaneGeometry &geo = fused->geo;
+      // (plane sample = stored sample, and every one of them inside the conversion's range)
+      const uint32_t s_end = fused->s_end < geo.s_stride ? fused->s_end : geo.s_stride;
+      if (!geo.diag || geo.num_rows != num_stored || s_end < num_stored || geo.k_words < 8)
+        return hipErrorInvalidValue;
+      st.stats = fused->to.stats;
+      st.cum = fused->to.cum;
+      st.sums = fused->to.sums;
+      st.steps_out = fused->to.steps;
+      st.s_stride = geo.s_stride;
+      st.all_steps = geo.k_words / 8;
+      st.stats_grid = (s_end + 3) / 4;  // (launch_sample_stats over plane samples [0, s_end))
+      for (uint32_t k = 0; k < kNumCheckShares; ++k)
+        st.steps[k] = check_step_of(st.all_steps, k, filter_check_min_steps());
+    }
+    if (gather == 4)
+      return fused ? launch_gather_form<4, true>(d_bit_sets, num_stored, words_per_sample, d_order,
+                                                 d_permuted, st, stream)
+                   : launch_gather_form<4, false>(d_bit_sets, num_stored, words_per_sample,
+                                                  d_order, d_permuted, st, stream);
+    return fused ? launch_gather_form<2, true>(d_bit_sets, num_stored, words_per_sample, d_order,
+                                               d_permuted, st, stream)
+                 : launch_gather_form<2, false>(d_bit_sets, num_stored, words_per_sample, d_order,
+                                                d_permuted, st, stream);
+  }
+  if (gather != 0 || fused != nullptr) return hipErrorInvalidValue;
   const uint32_t groups2 = (num_stored + 1) / 2;
   if ((size_t)P * 32 <= kOrderLdsBytes)
     permute_sites_kernel<2><<<dim3(groups2), dim3(256), P * 32, stream>>>(
-        d_bit_sets, permuted, vals_out, num_stored, words_per_sample);
+        d_bit_sets, d_permuted, d_order, num_stored, words_per_sample);
   else
     permute_sites_kernel<1><<<dim3(num_stored), dim3(256), P * 16, stream>>>(
-        d_bit_sets, permuted, vals_out, num_stored, words_per_sample);
+        d_bit_sets, d_permuted, d_order, num_stored, words_per_sample);
   return hipGetLastError();
+}
+
+hipError_t launch_site_permute(const uint64_t *d_bit_sets, uint32_t num_stored,
+                               uint32_t words_per_sample, void *d_scratch,
+                               const SiteOrderScratch &l, int gather,
+                               const SiteGatherStats *fused, hipStream_t stream) {
+  if (l.bytes == 0 || d_scratch == nullptr) return hipErrorInvalidValue;
+  const uint32_t sites = (words_per_sample / 2) * 64;
+  uint8_t *base = static_cast<uint8_t *>(d_scratch);
+  const uint32_t *vals_out = reinterpret_cast<const uint32_t *>(base + l.vals) + sites;
+  uint64_t *permuted = reinterpret_cast<uint64_t *>(base + l.permuted);
+  return launch_site_gather(d_bit_sets, num_stored, words_per_sample, vals_out, permuted, gather,
+                            fused, stream);
 }
 
 SiteOrderForecast site_order_forecast(const SiteCurve &c, uint32_t num_stored, uint32_t k_words,

@@ -309,6 +309,14 @@ cuking_status cuking_ctx_set_kernel(cuking_ctx *ctx, cuking_kernel kernel);
  *                        of an unrotated tile's check, in 64ths, by the curve and by stored
  *                        order's rule as the last such conversion forecast them; 0 = none),
  *                        "site_order_sigma_e6".
+ *   "filter_site_gather" the kernel that writes that second copy: -1 (default) a workgroup
+ *                        stages 4 samples in LDS, a byte per site, where the sites fit beside
+ *                        the wavefronts' tiles (up to 153,472 sites), else 2 samples, a
+ *                        nibble per site (every width the order serves), and assembles the
+ *                        output words by bit-matrix transposes; 0 the earlier kernel, one
+ *                        ballot per output word and plane; 4 / 2 force a form (4: the
+ *                        conversion is refused where it does not fit).  The same bytes
+ *                        either way.
  *   "filter_check0"      forecast check at an eighth of the sites: 0 off, 1 (default) for
  *                        launches of fewer than 16 rounds, 2 always.
  *   "filter_check1"      rigorous check inside the k loop: 0 off, 1 (default) the entry of
@@ -1481,6 +1489,32 @@ cuking_status cuking_mendel_site_counts(cuking_ctx *ctx, const uint64_t *d_error
 
 /* cuking.cu:761-765 on host memory: sort by (sample_i, sample_j, kin). */
 void cuking_sort_results(cuking_result *results, size_t num_results);
+
+/* ------------------------------------------------------------------------ */
+/* Test entry points: single steps of a conversion on the caller's buffers.   */
+/* ------------------------------------------------------------------------ */
+
+/* The gather of the site order ("filter_site_order") alone: for every sample s <
+ * num_stored and both planes of 64 * (words_per_sample / 2) sites,
+ *   d_permuted[s][plane] bit d = d_bit_set[s][plane] bit d_order[d],
+ * rows words_per_sample words apart as in d_bit_set; the word behind the two planes of an
+ * odd words_per_sample is not written.  d_order: a permutation of the plane's sites (the
+ * padding sites of the last word among them), device memory.  gather: 0, 2 or 4 as
+ * "filter_site_gather" (-1 is not taken here); CUKING_ERR_INVALID_ARGUMENT where that form
+ * does not serve the width.  Every form writes the same bytes.
+ * stats: 0 none; otherwise the sample statistics of a conversion of a whole diagonal block
+ * of num_stored samples from that copy, into d_stats (device, stats_bytes long) -- (|Y| - |M|,
+ * |H|) per plane sample, the 128 rows of the cumulative counts, the cohort's three sums and
+ * the check steps, one behind the other -- 1: counted inside the byte-wide gather (gather 2 or
+ * 4; what a conversion does), 2: by the separate kernel behind the gather.  The same bytes
+ * either way.  layout (host, 5 words, may be null): the padded sample count, the byte offsets
+ * of the rows, the sums and the steps, and the bytes needed; it is filled before stats_bytes
+ * is checked.  Asynchronous on `stream`. */
+cuking_status cuking_test_site_gather(cuking_ctx *ctx, const uint64_t *d_bit_set,
+                                      uint32_t num_stored, uint32_t words_per_sample,
+                                      const uint32_t *d_order, int gather, uint64_t *d_permuted,
+                                      int stats, void *d_stats, uint64_t stats_bytes,
+                                      uint64_t *layout, void *stream);
 
 /* ------------------------------------------------------------------------ */
 /* Measurement hooks (replace the StopWatch prints, cuking.cu:325-337).      */
