@@ -14,6 +14,7 @@ from .api import (DEFAULT_KIN_THRESHOLD, DEFAULT_MAX_RESULTS,  # noqa: F401
                   LDPrune, ld_edges_host, ld_priority_host, ld_site_words, transpose_sites_host,
                   geno_matmul_host,
                   SiteQC, compact_sites_host, site_mask_bool, site_mask_host, site_mask_words,
+                  HWE_MIDP, hwe_site_mask, hwe_sites_host,
                   padded_sites, sort_results, synth_model_number, synth_models,
                   words_per_sample)
 from .pca import PCAResult, hwe_table, pca_host  # noqa: F401

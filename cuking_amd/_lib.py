@@ -211,6 +211,8 @@ SIGNATURES = {
     "cuking_mendel_trios": (_int, [_vp, _vp, _u32, _u32, _u32, _vp, _u64, _vp, _vp, _vp]),
     "cuking_mendel_site_counts_host": (_int, [_vp, _u64, _u32, _vp]),
     "cuking_mendel_site_counts": (_int, [_vp, _vp, _u64, _u32, _vp, _vp]),
+    "cuking_hwe_sites_host": (_int, [_vp, _u32, _u32, _vp]),
+    "cuking_hwe_sites": (_int, [_vp, _vp, _u32, _u32, _vp, _vp]),
     "cuking_sort_results": (None, [_vp, _sz]),
     "cuking_timing_enable": (_int, [_vp, _int]),
     "cuking_timing_reset": (_int, [_vp]),

@@ -181,6 +181,51 @@ def site_mask_host(counts, num_sites: int, min_call_rate: float = 0.0, min_maf: 
     return keep, int(kept.value)
 
 
+HWE_MIDP = 1  # CUKING_HWE_MIDP
+
+
+def hwe_sites_host(counts, num_sites: int, midp: bool = False) -> np.ndarray:
+    """cuking_hwe_sites_host, the Hardy-Weinberg exact test per site: from the ``[*, 4]`` site
+    counts (hom_ref, het, hom_var, missing per site, as ``site_counts`` gives them; missing is
+    ignored) the p-value of each of the first ``num_sites`` rows as float64 ``[num_sites]``.
+    ``midp``: the mid-p form (half the observed table's probability leaves the tail).  1.0 where
+    nothing was called, NaN above 2^24 people (include/cuking_amd.h has the walk, operation by
+    operation: the device call returns the same bytes)."""
+    num_sites = _count(num_sites, "num_sites")
+    counts = np.asarray(counts)
+    if counts.dtype not in (np.dtype(np.uint32), np.dtype(np.int32)) or counts.ndim != 2 or \
+            counts.shape[1] != 4 or counts.shape[0] < num_sites:
+        raise ValueError(f"counts must be a uint32 (or int32) array of at least {num_sites} rows "
+                         f"of 4, not {counts.dtype} {counts.shape}")
+    counts = np.ascontiguousarray(counts).view(np.uint32)
+    p = np.empty(num_sites, dtype=np.float64)
+    check(_lib.load().cuking_hwe_sites_host(counts.ctypes.data, num_sites,
+                                            HWE_MIDP if midp else 0, p.ctypes.data))
+    return p
+
+
+def _min_hwe_p(min_hwe_p) -> float:
+    value = float(min_hwe_p)
+    if not 0.0 <= value <= 1.0:  # (NaN fails)
+        raise ValueError(f"min_hwe_p ({min_hwe_p}) must be in [0, 1]")
+    return value
+
+
+def hwe_site_mask(p, min_hwe_p: float, also=None) -> np.ndarray:
+    """The Hardy-Weinberg rule of ``filter_sites`` on host arrays: site s passes iff ``p[s] >=
+    min_hwe_p`` as doubles -- false for NaN -- and ``also[s]``, where ``also`` (a bool array of
+    the same length) is given.  Returns the bool array that goes on as ``also``."""
+    p = np.asarray(p, dtype=np.float64).reshape(-1)
+    with np.errstate(invalid="ignore"):
+        keep = p >= _min_hwe_p(min_hwe_p)
+    if also is not None:
+        also = np.asarray(also)
+        if also.shape != p.shape:
+            raise ValueError(f"also must hold {p.size} entries, not {also.shape}")
+        keep &= also.astype(bool)
+    return keep
+
+
 def _keep_words(keep_words, words_per_sample_in: int) -> np.ndarray:
     keep = np.ascontiguousarray(keep_words, dtype=np.uint64).reshape(-1)
     if keep.size != words_per_sample_in // 2:
@@ -931,22 +976,63 @@ class KingContext:
             _count(num_sites, "num_sites"), out.data_ptr(), wps_out, _stream_handle(stream)))
         return out, wps_out, kept
 
+    def hwe_sites(self, counts, num_sites: int, midp: bool = False, out=None, stream=None):
+        """The Hardy-Weinberg exact test per site (cuking_hwe_sites): from the device counts
+        tensor of ``site_counts`` (int32 ``[*, 4]``, at least ``num_sites`` rows; missing is
+        ignored) the p-values of the first ``num_sites`` sites as a float64 device tensor
+        ``[num_sites]``, OVERWRITTEN -- byte for byte what ``hwe_sites_host`` returns.  ``midp``:
+        the mid-p form.  ``out``: a float64 ``[num_sites]`` tensor to write into.  Does not
+        synchronise."""
+        import torch
+        num_sites = _count(num_sites, "num_sites")
+        _device_tensor(self.device, counts, "counts", torch.int32, cols=4,
+                       min_numel=4 * num_sites)
+        if out is None:
+            out = torch.empty((num_sites,), dtype=torch.float64, device=f"cuda:{self.device}")
+        else:
+            _device_tensor(self.device, out, "out", torch.float64, shape=(num_sites,))
+        check(self.lib.cuking_hwe_sites(self.handle, counts.data_ptr(), num_sites,
+                                        HWE_MIDP if midp else 0, out.data_ptr(),
+                                        _stream_handle(stream)))
+        return out
+
     def filter_sites(self, bit_sets, words_per_sample: int, num_sites: int,
                      min_call_rate: float = 0.0, min_maf: float = 0.0, min_mac: int = 0,
-                     also=None, stream=None) -> "SiteQC":
+                     also=None, stream=None, min_hwe_p: float = 0.0, hwe_midp: bool = False,
+                     hwe_counts=None) -> "SiteQC":
         """Count, mask and compact in one call: ``site_counts`` of the rows of
         ``bit_sets``, ``site_mask_host`` with the rule given, ``compact_sites`` with its
         mask.  Returns a ``SiteQC`` whose ``bits`` / ``words_per_sample`` / ``num_sites``
         everything behind (records, matrix, summary, relative counts) takes in place of the
-        unfiltered ones.  Waits for the counts."""
+        unfiltered ones.  Waits for the counts.
+
+        ``min_hwe_p`` > 0 adds the Hardy-Weinberg rule: ``hwe_sites`` (``hwe_midp``: its mid-p
+        form) runs on the call's own counts -- or on ``hwe_counts``, a ``[64 P, 4]`` counts
+        tensor of the rows the test should see, e.g. ``site_counts(bits[unrelated])`` for
+        PLINK's "founders only" -- and a site is additionally kept iff ``p >= min_hwe_p``
+        (false for NaN), ANDed into ``also``; ``SiteQC.hwe_p()`` has the p-values."""
         import torch
+        min_hwe_p = _min_hwe_p(min_hwe_p)
+        if hwe_counts is not None and not min_hwe_p > 0.0:
+            raise ValueError("hwe_counts is read by the Hardy-Weinberg rule only: min_hwe_p must "
+                             "be above 0")
+        if hwe_counts is not None:
+            _device_tensor(self.device, hwe_counts, "hwe_counts", torch.int32,
+                           shape=(max(words_per_sample, 0) // 2 * 64, 4))
         counts = self.site_counts(bit_sets, words_per_sample, stream=stream)
+        hwe_p = None
+        if min_hwe_p > 0.0:
+            hwe_p = self.hwe_sites(counts if hwe_counts is None else hwe_counts,
+                                   _count(num_sites, "num_sites"), hwe_midp, stream=stream)
         (stream if stream is not None else torch.cuda.current_stream(self.device)).synchronize()
         host = counts.cpu().numpy().view(np.uint32)
+        if hwe_p is not None:
+            hwe_p = hwe_p.cpu().numpy()
+            also = hwe_site_mask(hwe_p, min_hwe_p, also)
         keep, kept = site_mask_host(host, num_sites, min_call_rate, min_maf, min_mac, also)
         bits, wps, _ = self.compact_sites(bit_sets, words_per_sample, keep, num_sites,
                                           stream=stream)
-        return SiteQC(host, keep, num_sites, bits, wps, kept)
+        return SiteQC(host, keep, num_sites, bits, wps, kept, hwe_p)
 
     # -- LD pruning -------------------------------------------------------------
     def transpose_sites(self, bit_sets, words_per_sample: int, num_sites: int, out=None,
@@ -1497,13 +1583,19 @@ class SiteQC:
     """What ``KingContext.filter_sites`` returns.  The filtered cohort: ``bits`` (device
     int64 ``[rows, words_per_sample]``), ``words_per_sample`` and ``num_sites`` (the number of
     kept sites).  The input's sites: ``num_sites_in``, ``counts()``, ``keep()``,
-    ``kept_index()``, ``allele_freq()`` and ``call_rate()`` -- host arrays, one entry per
-    site of the INPUT."""
+    ``kept_index()``, ``allele_freq()``, ``call_rate()`` and ``hwe_p()`` -- host arrays, one
+    entry per site of the INPUT."""
 
     def __init__(self, site_counts: np.ndarray, keep_words: np.ndarray, num_sites_in: int,
-                 bits, words_per_sample: int, num_sites: int):
+                 bits, words_per_sample: int, num_sites: int, hwe_p=None):
         self.site_counts, self.keep_words, self.num_sites_in = site_counts, keep_words, num_sites_in
         self.bits, self.words_per_sample, self.num_sites = bits, words_per_sample, num_sites
+        self._hwe_p = hwe_p
+
+    def hwe_p(self):
+        """float64 ``[num_sites_in]``: the Hardy-Weinberg exact p-value of every input site, or
+        ``None`` when the rule was not asked for (``min_hwe_p`` = 0)."""
+        return self._hwe_p
 
     def counts(self) -> np.ndarray:
         """uint32 ``[num_sites_in, 4]``: samples hom-ref, het, hom-var and missing."""

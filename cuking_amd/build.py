@@ -30,7 +30,7 @@ HIP_SOURCES = ["king_abi.hip", "king_kernels.hip", "king_mfma.hip", "king_filter
                "king_sort.hip", "king_prune.hip", "king_bed.hip", "king_site_qc.hip",
                "king_ld.hip", "king_geno.hip", "king_pcrelate.hip",
                "king_pcrelate_records.hip", "king_pcrelate_pairs.hip", "king_ibd.hip",
-               "king_ibd_scan.hip", "king_mendel.hip", "synth.hip"]
+               "king_ibd_scan.hip", "king_mendel.hip", "king_hwe.hip", "synth.hip"]
 # Host-only half of the ABI: plain C++, also compiled by the sanitizer tests.
 HOST_ABI_SOURCES = ["king_host.cc"]
 # IEEE-correct fp32 divide (kinship must match the reference bit for bit):
@@ -116,6 +116,8 @@ def build_library(force: bool = False, save_temps: bool = False) -> Path:
                                  "ibd_scan_kernel")
     for kernel in ("mendel_trios_kernel", "mendel_site_counts_kernel"):
         problems += check_no_scratch(cwd / "king_mendel-hip-amdgcn-amd-amdhsa-gfx950.s", kernel)
+    problems += check_no_scratch(cwd / "king_hwe-hip-amdgcn-amd-amdhsa-gfx950.s",
+                                 "hwe_sites_kernel")
     if problems and not extra:
         LIB_PATH.unlink(missing_ok=True)
         raise RuntimeError("the compiler put vector-memory waits or scratch accesses inside an "

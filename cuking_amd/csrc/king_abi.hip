@@ -2458,6 +2458,24 @@ cuking_status cuking_mendel_site_counts(cuking_ctx *ctx, const uint64_t *d_error
   return CUKING_OK;
 }
 
+// ---- Hardy-Weinberg test (king_hwe.hip) -------------------------------------------
+cuking_status cuking_hwe_sites(cuking_ctx *ctx, const uint32_t *d_counts, uint32_t num_sites,
+                               uint32_t flags, double *d_p, void *stream) {
+  // (the arguments first: a refused call touches no device)
+  if (ctx == nullptr) return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "null context");
+  const cuking_status st = cuking_check_hwe_args(d_counts, num_sites, flags, d_p);
+  if (st != CUKING_OK) return st;
+  if (num_sites == 0) return CUKING_OK;
+  // (the kernel loads a row as one 16-byte word; cuking_site_counts' array is aligned like that)
+  if (reinterpret_cast<uintptr_t>(d_counts) % 16 != 0 || reinterpret_cast<uintptr_t>(d_p) % 8 != 0)
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT,
+                       "hwe sites: d_counts must be 16-byte and d_p 8-byte aligned");
+  BIND_OR_RETURN(ctx);
+  HIP_TRY(launch_hwe_sites(d_counts, num_sites, (flags & CUKING_HWE_MIDP) != 0, d_p,
+                           (hipStream_t)stream));
+  return CUKING_OK;
+}
+
 cuking_status cuking_ibd_pairs(cuking_ctx *ctx, const uint64_t *d_bits, uint32_t num_stored,
                                uint32_t words_per_sample, uint32_t num_sites,
                                const int32_t *d_group, const uint32_t *d_pos, uint32_t min_sites,

@@ -872,6 +872,11 @@ hipError_t launch_mendel_site_counts(const uint64_t *d_error_bits, uint64_t num_
                                      uint32_t plane_words, uint32_t *d_counts,
                                      hipStream_t stream);
 
+// Hardy-Weinberg exact test (king_hwe.hip; arguments already checked, king_host.h): plain stores
+// into d_p[0 .. num_sites) from rows [0, num_sites) of a site_counts array (16-byte aligned).
+hipError_t launch_hwe_sites(const uint32_t *d_counts, uint32_t num_sites, bool midp, double *d_p,
+                            hipStream_t stream);
+
 // Cohort models of the synthetic generator (synth.hip holds the specification).  d_tables:
 // synth_table_bytes() of scratch the launch fills and reads (per-site and per-sample
 // tables); it must stay untouched until the launch has run.

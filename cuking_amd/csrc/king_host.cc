@@ -20,6 +20,7 @@
 #include "../host/schedule.h"
 #include "king_submatrix.h"
 #include "king_geno.h"
+#include "king_hwe.h"
 #include "king_ibd.h"
 #include "king_kin_summary.h"
 #include "king_ld.h"
@@ -1392,6 +1393,32 @@ cuking_status cuking_mendel_site_counts_host(const uint64_t *error_bits, uint64_
     for (uint32_t w = 0; w < plane_words; ++w)
       for (uint64_t x = error_bits[t * plane_words + w]; x != 0; x &= x - 1)
         ++counts[(uint64_t)w * 64 + (uint32_t)__builtin_ctzll(x)];
+  return CUKING_OK;
+}
+
+}  // extern "C"
+
+// ---- Hardy-Weinberg test -------------------------------------------------------------------------
+cuking_status cuking_check_hwe_args(const void *counts, uint32_t num_sites, uint32_t flags,
+                                    const void *p) {
+  if (flags & ~CUKING_HWE_MIDP)
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "hwe sites: unknown flags 0x%x", flags);
+  if (num_sites != 0 && (counts == nullptr || p == nullptr))
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "hwe sites: null pointer");
+  return CUKING_OK;
+}
+
+extern "C" {
+
+// The sites one at a time, with the function of king_hwe.h.
+cuking_status cuking_hwe_sites_host(const uint32_t *counts, uint32_t num_sites, uint32_t flags,
+                                    double *p) {
+  const cuking_status st = cuking_check_hwe_args(counts, num_sites, flags, p);
+  if (st != CUKING_OK) return st;
+  for (uint32_t s = 0; s < num_sites; ++s) {
+    const uint32_t *c = counts + (uint64_t)s * 4;
+    p[s] = hwe_exact_p(c[0], c[1], c[2], (flags & CUKING_HWE_MIDP) != 0);
+  }
   return CUKING_OK;
 }
 

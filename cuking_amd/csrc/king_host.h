@@ -109,5 +109,9 @@ cuking_status cuking_check_mendel_args(const void *bits, uint32_t words_per_samp
                                        const void *out);
 cuking_status cuking_check_mendel_site_args(const void *error_bits, uint64_t num_trios,
                                             uint32_t plane_words, const void *counts);
+// Argument checks of cuking_hwe_sites_host / cuking_hwe_sites (include/cuking_amd.h
+// "Hardy-Weinberg test" lists them); OK says nothing about there being work to do.
+cuking_status cuking_check_hwe_args(const void *counts, uint32_t num_sites, uint32_t flags,
+                                    const void *p);
 
 #endif  // CUKING_AMD_KING_HOST_H_

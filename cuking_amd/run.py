@@ -8,9 +8,9 @@ One process per GPU.  Rank 0 reads `metadata.json` + `*.parquet`, packs the
 bitset through the C ABI (`cuking_pack_host`, reader threads like
 cuking.cu:550-553) -- or, with `--bed-uri PREFIX`, streams a PLINK `.bed` to its
 GPU and transposes it there (`KingContext.load_bed`) --, optionally drops sites
-by call rate, minor allele frequency / count or a list (`--site-min-call-rate`,
-`--site-min-maf`, `--site-min-mac`, `--site-keep-uri`: counts and compaction on the
-GPU, csrc/king_site_qc.hip) and thins the rest by LD (`--site-ld-window`, `--site-ld-r2`:
+by call rate, minor allele frequency / count, the Hardy-Weinberg exact test or a list
+(`--site-min-call-rate`, `--site-min-maf`, `--site-min-mac`, `--site-hwe-p`, `--site-keep-uri`:
+counts, test and compaction on the GPU, csrc/king_site_qc.hip and csrc/king_hwe.hip) and thins the rest by LD (`--site-ld-window`, `--site-ld-r2`:
 csrc/king_ld.hip), the bitset goes to the other GPUs by the staged RCCL
 broadcast of `cuking_amd.dist`, every rank evaluates its band of the pair
 space, rank 0 gathers, sorts and writes `part-<shard>.snappy.parquet` with the
@@ -103,7 +103,7 @@ def parse_args(argv=None):
     flag("site-min-call-rate", type=float, default=None,
          help="site QC before anything is computed: keep the sites whose share of called "
               "genotypes is at least this (0..1).  Any of --site-min-call-rate, --site-min-maf, "
-              "--site-min-mac and --site-keep-uri makes the run count the genotypes per site on "
+              "--site-min-mac, --site-hwe-p and --site-keep-uri makes the run count the genotypes per site on "
               "the GPU, drop the sites that fail (and those without a called genotype) and "
               "compact the bitset there; records and every side output then come from the kept "
               "sites.  One process and --split-factor 1 only")
@@ -113,13 +113,22 @@ def parse_args(argv=None):
     flag("site-min-mac", type=int, default=None,
          help="site QC: keep the sites whose minor allele count is at least this (1 drops the "
               "monomorphic sites)")
+    flag("site-hwe-p", type=float, default=None,
+         help="site QC: keep the sites whose Hardy-Weinberg exact test p-value (Wigginton et "
+              "al. 2005, computed on the GPU from the cohort's genotype counts: plink --hwe) is "
+              "at least this (0..1, e.g. 1e-6); applied with the rule, before LD pruning")
+    ap.add_argument("--site-hwe-midp", "--site_hwe_midp", dest="site_hwe_midp",
+                    action="store_true",
+                    help="site QC: --site-hwe-p uses the mid-p form of the test (half the "
+                         "observed table's probability leaves the tail); needs --site-hwe-p")
     flag("site-keep-uri", default="",
          help="site QC: a .npy file of one bool / uint8 per site, ANDed with the rule -- an "
               "LD-pruned site list, a region")
     flag("site-qc-uri", default="",
          help="also write the site QC report of the INPUT cohort to this .npz file "
               "(site_counts [sites, 4] = hom-ref, het, hom-var, missing; keep; sample_counts "
-              "[samples, 4]; samples; min_call_rate, min_maf, min_mac).  Alone it only reports: "
+              "[samples, 4]; samples; min_call_rate, min_maf, min_mac; with --site-hwe-p also "
+              "hwe_p, min_hwe_p and hwe_midp).  Alone it only reports: "
               "nothing is filtered.  One process and --split-factor 1 only")
     flag("site-ld-window", type=int, default=None,
          help="LD pruning after the site QC rule, on the GPU: among the sites within a window "
@@ -351,14 +360,15 @@ def validate(args):  # cuking.cu:437-462
     unrelated_threshold(args)
     if site_filtering(args) or args.site_qc_uri:
         if int(os.environ.get("WORLD_SIZE", "1")) > 1:
-            raise UsageError("--site_min_call_rate, --site_min_maf, --site_min_mac, "
+            raise UsageError("--site_min_call_rate, --site_min_maf, --site_min_mac, --site_hwe_p, "
                              "--site_keep_uri and --site_qc_uri need one process (one GPU): site "
                              "counts are not merged across ranks yet")
         if args.split_factor != 1:
-            raise UsageError("--site_min_call_rate, --site_min_maf, --site_min_mac, "
+            raise UsageError("--site_min_call_rate, --site_min_maf, --site_min_mac, --site_hwe_p, "
                              "--site_keep_uri and --site_qc_uri need --split_factor 1: a site "
                              "passes or fails on the whole cohort's counts")
     site_rule(args)
+    hwe_rule(args)
     if ld_pruning(args):
         if int(os.environ.get("WORLD_SIZE", "1")) > 1:
             raise UsageError("--site_ld_window, --site_ld_r2 and --site_ld_uri need one process "
@@ -544,9 +554,21 @@ def ld_rule(args):
 
 
 def site_filtering(args) -> bool:
-    """Does the run drop sites (any of the four flags that select them)?"""
+    """Does the run drop sites (any of the five flags that select them)?"""
     return (args.site_min_call_rate is not None or args.site_min_maf is not None or
-            args.site_min_mac is not None or bool(args.site_keep_uri))
+            args.site_min_mac is not None or args.site_hwe_p is not None or
+            bool(args.site_keep_uri))
+
+
+def hwe_rule(args):
+    """--site-hwe-p / --site-hwe-midp as the library sees them: (threshold or None, midp)."""
+    if args.site_hwe_p is None:
+        if args.site_hwe_midp:
+            raise UsageError("--site_hwe_midp needs --site_hwe_p")
+        return None, False
+    if not 0.0 <= args.site_hwe_p <= 1.0:   # (NaN fails)
+        raise UsageError("--site_hwe_p must be in [0, 1]")
+    return float(args.site_hwe_p), bool(args.site_hwe_midp)
 
 
 def site_rule(args):
@@ -924,7 +946,15 @@ def site_qc(ctx, args, bits, wps: int, num_sites: int, sample_ids, keep_path, qc
         if also.shape != (num_sites,):
             raise ValueError(f"--site_keep_uri holds {also.shape}, the cohort has {num_sites} "
                              "sites")
-    counts = ctx.site_counts(bits, wps).cpu().numpy().view(np.uint32)
+    min_hwe_p, hwe_midp = hwe_rule(args)
+    d_counts = ctx.site_counts(bits, wps)
+    extra = {}
+    if min_hwe_p is not None:
+        # the exact test on the device, from the counts where they lie; the rule on the host
+        hwe_p = ctx.hwe_sites(d_counts, num_sites, midp=hwe_midp).cpu().numpy()
+        also = cuking_amd.hwe_site_mask(hwe_p, min_hwe_p, also)
+        extra = dict(hwe_p=hwe_p, min_hwe_p=np.float64(min_hwe_p), hwe_midp=np.bool_(hwe_midp))
+    counts = d_counts.cpu().numpy().view(np.uint32)
     keep, kept = cuking_amd.site_mask_host(counts, num_sites, rate, maf, mac, also=also)
     if qc_path is not None:
         per_sample = ctx.sample_counts(bits, wps, num_sites).cpu().numpy().view(np.uint32)
@@ -934,7 +964,7 @@ def site_qc(ctx, args, bits, wps: int, num_sites: int, sample_ids, keep_path, qc
                      keep=cuking_amd.site_mask_bool(keep, num_sites), sample_counts=per_sample,
                      samples=np.array(list(sample_ids), dtype=str),
                      min_call_rate=np.float32(rate), min_maf=np.float32(maf),
-                     min_mac=np.uint32(mac))
+                     min_mac=np.uint32(mac), **extra)
     if not site_filtering(args):
         return bits, wps, num_sites, np.arange(num_sites)
     index = np.flatnonzero(cuking_amd.site_mask_bool(keep, num_sites))

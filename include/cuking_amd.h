@@ -786,9 +786,9 @@ cuking_status cuking_unrelated_set(cuking_ctx *ctx, const cuking_result *d_recor
  * word from keep and uploads it into the context's per-stream cache, ordered on `stream`; it
  * waits for that upload (and so for what `stream` held before), the kernel itself is
  * asynchronous.  One caller per context at a time, like the compute entry points.
- * Out of scope: the C++ `cuking` binary; several ranks; HWE itself (LD pruning: below); sample
- * filtering and reordering; in-place compaction; filtering inside the .bed loader before the
- * transpose; rewriting a .bim. */
+ * Out of scope: the C++ `cuking` binary; several ranks (LD pruning and the Hardy-Weinberg test:
+ * below); sample filtering and reordering; in-place compaction; filtering inside the .bed loader
+ * before the transpose; rewriting a .bim. */
 typedef struct cuking_site_filter {
   float min_call_rate; /* called / (called + missing), in [0, 1] */
   float min_maf;       /* minor / (2 called), in [0, 1] */
@@ -867,7 +867,7 @@ cuking_status cuking_compact_sites(cuking_ctx *ctx, const uint64_t *d_in, uint32
  * deliberately NOT PLINK's sliding, order-dependent removal: it has one well-defined answer.
  * Out of scope: the C++ `cuking` binary and several ranks; windows in base pairs; PLINK's
  * step-wise removal order; reading the site-major form straight from a .bed; a VIF-based
- * --indep; phased or haplotype r^2; HWE; rewriting a .bim. */
+ * --indep; phased or haplotype r^2; rewriting a .bim. */
 uint32_t cuking_ld_site_words(uint32_t num_stored); /* Q */
 float cuking_ld_priority(const uint32_t counts[4]);
 cuking_status cuking_transpose_sites_host(const uint64_t *bit_set, uint32_t num_stored,
@@ -1486,6 +1486,52 @@ cuking_status cuking_mendel_site_counts_host(const uint64_t *error_bits, uint64_
 cuking_status cuking_mendel_site_counts(cuking_ctx *ctx, const uint64_t *d_error_bits,
                                         uint64_t num_trios, uint32_t plane_words,
                                         uint32_t *d_counts, void *stream);
+
+/* Hardy-Weinberg test: the exact test of Wigginton, Cutler and Abecasis (2005) per site from its
+ * genotype counts (plink --hwe, hl.hardy_weinberg_test) -- the site-QC rule that needs more than a
+ * comparison, computed where the counts lie.  csrc/king_hwe.h holds the definition below as code
+ * (hwe_exact_p), shared by kernel, host twin and tests; only *, /, +, - and comparisons on IEEE
+ * doubles in ONE order, so host, device and a restatement in any language with doubles agree bit
+ * for bit.
+ *
+ * p(hom_ref, het, hom_var, midp), with n = hom_ref + het + hom_var:
+ *     n == 0 gives 1.0; n > 2^24 (the library's sample limit) gives NaN.
+ *     r0 = min(hom_ref, hom_var), c0 = max(hom_ref, hom_var); total = 1.0, tail = 1.0: the
+ *     observed table is term 1.0 and counts as "no more likely than itself".
+ *     Up (more hets): t = 1, x = het, hr = r0, hc = c0, all doubles.  While hr > 0:
+ *         t = (t * (4.0 * hr * hc)) / ((x + 2.0) * (x + 1.0));  x += 2; hr -= 1; hc -= 1;
+ *         if t == 0.0 the direction ends (every later term is 0);
+ *         if !(t < inf) the result is 0.0 (another table is more than 10^308 times as likely);
+ *         otherwise total += t, and tail += t if t <= 1 + 2^-27.
+ *     Down (fewer hets): again from t = 1, x = het, hr = r0, hc = c0.  While x >= 2:
+ *         t = (t * (x * (x - 1.0))) / (4.0 * (hr + 1.0) * (hc + 1.0));  x -= 2; hr += 1; hc += 1;
+ *         followed by the same three steps.
+ *     if midp: tail -= 0.5 (half the observed table's probability, Graffelman and Moreno 2013).
+ *     p = tail / total.
+ * Both integer products stay below 2^50 and are exact; up is summed before down; subnormal terms
+ * are kept (nothing is flushed to zero).  The tie constant 1 + 2^-27 is derived: a table exactly as
+ * likely as the observed one is reached after at most 2^24 steps of two roundings each, so its
+ * computed term is within 2 * 2^24 * 2^-53 = 2^-28 of 1 -- every exact tie is counted.
+ *
+ * cuking_hwe_sites / cuking_hwe_sites_host:
+ *     counts   uint32 [.][4], the array of cuking_site_counts: hom_ref, het, hom_var, missing
+ *              (ignored); rows [0, num_sites) are read.  Device form: 16-byte aligned
+ *     p        double [num_sites], overwritten with plain stores
+ *     flags    CUKING_HWE_MIDP or 0
+ * Refused with INVALID_ARGUMENT: a null context (device form), any other flag bit, with num_sites
+ * != 0 a null pointer, and a misaligned device pointer.  num_sites == 0 is no work.  The device
+ * call (king_hwe.hip: one thread per site, one chain per owner) is asynchronous on `stream`; no
+ * atomics, no scratch buffer, nothing data-dependent that can fail.  A site is kept by the usual
+ * rule iff p >= threshold, which is false for NaN; the mask goes to cuking_site_mask_host as `also`.
+ * Out of scope: a lane-parallel split of one site's walk (it would change the rounding order);
+ * log-space or lgamma forms; the chi-square test; X-chromosome and haploid HWE; ancestry-adjusted
+ * HWE; choosing founder or control rows (the caller counts the rows it wants); excess versus
+ * deficit; the C++ `cuking` binary; several ranks. */
+#define CUKING_HWE_MIDP 1u
+cuking_status cuking_hwe_sites_host(const uint32_t *counts, uint32_t num_sites, uint32_t flags,
+                                    double *p);
+cuking_status cuking_hwe_sites(cuking_ctx *ctx, const uint32_t *d_counts, uint32_t num_sites,
+                               uint32_t flags, double *d_p, void *stream);
 
 /* cuking.cu:761-765 on host memory: sort by (sample_i, sample_j, kin). */
 void cuking_sort_results(cuking_result *results, size_t num_results);
