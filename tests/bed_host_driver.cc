@@ -1,5 +1,5 @@
 // Stand-alone driver of cuking_pack_bed_host for the sanitizer build of
-// tests/test_bed_host.py (g++ -fsanitize=address,undefined, csrc/king_host.cc compiled in):
+// tests/test_bed_host.py (built and run by tests/host_driver.py, csrc/king_host.cc linked in):
 // 37 samples x 129 sites, every shard of a split factor of 3, one-shot and in chunks, every
 // buffer an exact-size heap allocation so that a byte read or written past an end is caught.
 // The result is compared with cuking_pack_host of the same genotypes as triples.
@@ -10,16 +10,16 @@
 #include <vector>
 
 #include "cuking_amd.h"
+#include "host_driver_common.h"
 
 int main() {
   const uint32_t N = 37, M = 129;
   const uint64_t row_bytes = cuking_bed_row_bytes(N);
   const uint32_t wps = cuking_words_per_sample(M);
   std::unique_ptr<uint8_t[]> rows(new uint8_t[M * row_bytes]);
-  uint64_t state = 0x9E3779B97F4A7C15ull;
   for (uint64_t k = 0; k < M * row_bytes; ++k) {
-    state = state * 6364136223846793005ull + 1442695040888963407ull;
-    rows[k] = (uint8_t)(state >> 56);
+    next_random();
+    rows[k] = (uint8_t)(g_state >> 56);  // (the top byte of the generator's state)
   }
   // the same genotypes as triples (code 1 = missing = no triple)
   std::vector<int64_t> row_idx, col_idx;
@@ -33,7 +33,6 @@ int main() {
       col_idx.push_back(s);
       n_alt.push_back(alt);
     }
-  int failures = 0;
   for (uint32_t shard = 0; shard < 6; ++shard) {
     cuking_submatrix sm;
     if (cuking_submatrix_init(&sm, N, 3, shard) != CUKING_OK) return 2;
@@ -61,14 +60,14 @@ int main() {
       }
       if (st != CUKING_OK) {
         fprintf(stderr, "shard %u: %s\n", shard, cuking_last_error());
-        ++failures;
+        ++g_failures;
       } else if (memcmp(want.get(), got.get(), words * 8) != 0) {
         fprintf(stderr, "shard %u (%s): differs from cuking_pack_host\n", shard,
                 chunked ? "chunks" : "one call");
-        ++failures;
+        ++g_failures;
       }
     }
   }
-  printf("bed_host_driver: %d failures\n", failures);
-  return failures ? 1 : 0;
+  printf("bed_host_driver: %d failures\n", g_failures);
+  return g_failures != 0;
 }

@@ -1,6 +1,6 @@
 // Stand-alone driver of the host side of the genotype matrix product for the sanitizer build
-// of tests/test_geno_matmul_host.py (g++ -fsanitize=address,undefined, csrc/king_host.cc
-// compiled in).  Every buffer is an exact-size heap allocation, so a byte read or written past
+// of tests/test_geno_matmul_host.py (built and run by tests/host_driver.py, csrc/king_host.cc
+// linked in).  Every buffer is an exact-size heap allocation, so a byte read or written past
 // an end is caught.
 //   1. cuking_geno_matmul_host against the sum over plain code arrays, both table axes, integer
 //      operands (exact), pitches equal to and above num_rhs, pad elements untouched, garbage
@@ -13,25 +13,12 @@
 #include <vector>
 
 #include "cuking_amd.h"
+#include "host_driver_common.h"
 #include "king_geno.h"
 
 namespace {
 
-uint64_t g_state = 0x9E3779B97F4A7C15ull;
-uint64_t next_random() {
-  g_state = g_state * 6364136223846793005ull + 1442695040888963407ull;
-  uint64_t x = g_state;
-  x ^= x >> 33;
-  x *= 0xFF51AFD7ED558CCDull;
-  x ^= x >> 33;
-  return x;
-}
-
-int g_failures = 0;
-void fail(const char *what, uint32_t rows, uint32_t cols, uint32_t rhs) {
-  fprintf(stderr, "%s: %u rows x %u columns x %u right-hand sides\n", what, rows, cols, rhs);
-  ++g_failures;
-}
+// (fail: what, rows, columns, right-hand sides)
 
 void run_shape(uint32_t rows, uint32_t cols, uint32_t rhs, int axis, uint32_t ldb, uint32_t ldo) {
   const uint32_t plane = (cols + 63) / 64 + (cols % 3 == 0 ? 1 : 0);  // (room beyond num_cols too)

@@ -1,8 +1,9 @@
-// What the stand-alone drivers of the IBD and ROH host twins share (ibd_host_driver.cc,
-// ibd_bridge_host_driver.cc, ibd_scan_host_driver.cc, roh_host_driver.cc): the random numbers,
-// the failure count and its two reporters, and the genotype code of a site of a bitset row.
-#ifndef CUKING_AMD_TESTS_IBD_DRIVER_COMMON_H_
-#define CUKING_AMD_TESTS_IBD_DRIVER_COMMON_H_
+// What the stand-alone sanitizer drivers (tests/*_host_driver.cc, built and run by
+// tests/host_driver.py) share: the random numbers, the failure count and its two reporters, a bit
+// of a word array and the genotype code of a site of a bitset row.  Every driver ends with the
+// count print and `return g_failures != 0`.
+#ifndef CUKING_AMD_TESTS_HOST_DRIVER_COMMON_H_
+#define CUKING_AMD_TESTS_HOST_DRIVER_COMMON_H_
 
 #include <cstdint>
 #include <cstdio>
@@ -20,8 +21,10 @@ inline uint64_t next_random() {
 }
 
 inline int g_failures = 0;
-inline void fail(const char *what, uint32_t sites, uint64_t extra) {
-  fprintf(stderr, "%s: %u sites (%llu)\n", what, sites, (unsigned long long)extra);
+// (a label and up to three numbers that place the failure: a shape, an index, a mode)
+inline void fail(const char *what, uint64_t a = 0, uint64_t b = 0, uint64_t c = 0) {
+  fprintf(stderr, "%s: %llu, %llu, %llu\n", what, (unsigned long long)a, (unsigned long long)b,
+          (unsigned long long)c);
   ++g_failures;
 }
 inline void expect(const char *what, cuking_status got, cuking_status want) {
@@ -32,6 +35,9 @@ inline void expect(const char *what, cuking_status got, cuking_status want) {
   }
 }
 
+inline bool bit_of(const uint64_t *words, uint64_t k) { return (words[k >> 6] >> (k & 63)) & 1; }
+
+// 0 hom-ref, 1 het, 2 hom-var, 3 missing
 inline uint32_t code_of(const uint64_t *row, uint32_t plane, uint32_t s) {
   return (uint32_t)((row[s >> 6] >> (s & 63)) & 1) |
          (uint32_t)((row[plane + (s >> 6)] >> (s & 63)) & 1) << 1;
@@ -42,4 +48,4 @@ inline void set_code(uint64_t *row, uint32_t plane, uint32_t s, uint32_t code) {
   row[plane + (s >> 6)] = (row[plane + (s >> 6)] & ~bit) | ((code & 2) ? bit : 0);
 }
 
-#endif  // CUKING_AMD_TESTS_IBD_DRIVER_COMMON_H_
+#endif  // CUKING_AMD_TESTS_HOST_DRIVER_COMMON_H_

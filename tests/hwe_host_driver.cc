@@ -1,5 +1,6 @@
 // Stand-alone driver of the Hardy-Weinberg host twin for the sanitizer build of
-// tests/test_hwe_host.py: a program of its own, nothing is loaded into Python.
+// tests/test_hwe_host.py (built and run by tests/host_driver.py, csrc/king_host.cc linked in): a
+// program of its own, nothing is loaded into Python.
 //
 // Reads count rows "hom_ref het hom_var" from standard input, one per line, and for every row
 // prints the bits of four doubles in hex: hwe_exact_p (csrc/king_hwe.h) without and with mid-p,
@@ -14,13 +15,13 @@
 #include <vector>
 
 #include "cuking_amd.h"
+#include "host_driver_common.h"
 #include "king_hwe.h"
 
-static int failures = 0;
 #define EXPECT(cond)                                                   \
   do {                                                                 \
     if (!(cond)) {                                                     \
-      ++failures;                                                      \
+      ++g_failures;                                                    \
       std::printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond);    \
     }                                                                  \
   } while (0)
@@ -81,6 +82,6 @@ int main() {
   delete[] counts;
   delete[] p;
   delete[] p_mid;
-  std::printf("%d failures\n", failures);
-  return failures == 0 ? 0 : 1;
+  std::printf("%d failures\n", g_failures);
+  return g_failures != 0;
 }

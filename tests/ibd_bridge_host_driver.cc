@@ -1,6 +1,6 @@
 // Stand-alone driver of the host side of the IBD segments with bridged breaks for the sanitizer
-// build of tests/test_ibd_bridge_host.py (g++ -fsanitize=address,undefined, csrc/king_host.cc
-// compiled in).  Every buffer is an exact-size heap allocation, so a byte read or written past an
+// build of tests/test_ibd_bridge_host.py (built and run by tests/host_driver.py, csrc/king_host.cc
+// linked in).  Every buffer is an exact-size heap allocation, so a byte read or written past an
 // end is caught -- the group-start mask read for a link and the planes of exactly
 // ceil(num_sites / 64) words above all.
 //   1. cuking_ibd_pairs_bridged_host against a walk over the sites one by one that links its
@@ -19,7 +19,7 @@
 #include <vector>
 
 #include "cuking_amd.h"
-#include "ibd_driver_common.h"
+#include "host_driver_common.h"
 
 namespace {
 

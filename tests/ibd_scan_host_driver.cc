@@ -1,5 +1,5 @@
 // Stand-alone driver of the host side of the IBD scan of a block for the sanitizer build of
-// tests/test_ibd_scan_host.py (g++ -fsanitize=address,undefined, csrc/king_host.cc compiled in).
+// tests/test_ibd_scan_host.py (built and run by tests/host_driver.py, csrc/king_host.cc linked in).
 // Every buffer is an exact-size heap allocation, so a byte read or written past an end is caught
 // -- the planes of exactly num_sites / 64 words above all: with num_sites a multiple of 64 the
 // word of bit num_sites lies beyond them.
@@ -15,7 +15,7 @@
 #include <vector>
 
 #include "cuking_amd.h"
-#include "ibd_driver_common.h"
+#include "host_driver_common.h"
 
 namespace {
 

@@ -1,5 +1,5 @@
 // Stand-alone driver of the host side of LD pruning for the sanitizer build of
-// tests/test_ld_host.py (g++ -fsanitize=address,undefined, csrc/king_host.cc compiled in).
+// tests/test_ld_host.py (built and run by tests/host_driver.py, csrc/king_host.cc linked in).
 // Every buffer is an exact-size heap allocation, so a byte read or written past an end is caught.
 //   1. cuking_transpose_sites_host against a bit-by-bit restatement, over the odd shapes;
 //   2. cuking_ld_edges_host against the sums taken from plain genotype arrays and the
@@ -13,25 +13,12 @@
 #include <vector>
 
 #include "cuking_amd.h"
+#include "host_driver_common.h"
 #include "king_ld.h"
 
 namespace {
 
-uint64_t g_state = 0x9E3779B97F4A7C15ull;
-uint64_t next_random() {
-  g_state = g_state * 6364136223846793005ull + 1442695040888963407ull;
-  uint64_t x = g_state;
-  x ^= x >> 33;
-  x *= 0xFF51AFD7ED558CCDull;
-  x ^= x >> 33;
-  return x;
-}
-
-int g_failures = 0;
-void fail(const char *what, uint32_t n, uint32_t m, uint32_t window) {
-  fprintf(stderr, "%s: %u samples x %u sites, window %u\n", what, n, m, window);
-  ++g_failures;
-}
+// (fail: what, samples, sites, window)
 
 // genotypes [n][m]: 0, 1, 2 or -1 (missing); a site copies its left neighbour now and then
 std::vector<int8_t> random_genotypes(uint32_t n, uint32_t m) {

@@ -1,5 +1,5 @@
 // Stand-alone driver of the host side of the Mendelian errors for the sanitizer build of
-// tests/test_mendel_host.py (g++ -fsanitize=address,undefined, csrc/king_host.cc compiled in).
+// tests/test_mendel_host.py (built and run by tests/host_driver.py, csrc/king_host.cc linked in).
 // Every buffer is an exact-size heap allocation, so a byte read or written past an end is caught
 // -- the planes of exactly ceil(num_sites / 64) words, the list of trios, the rows, the mask and
 // the counts above all.
@@ -16,31 +16,12 @@
 #include <vector>
 
 #include "cuking_amd.h"
+#include "host_driver_common.h"
 #include "king_mendel.h"
 
 namespace {
 
-uint64_t g_state = 0x9E3779B97F4A7C15ull;
-uint64_t next_random() {
-  g_state = g_state * 6364136223846793005ull + 1442695040888963407ull;
-  uint64_t x = g_state;
-  x ^= x >> 33;
-  x *= 0xFF51AFD7ED558CCDull;
-  x ^= x >> 33;
-  return x;
-}
-
-int g_failures = 0;
-void fail(const char *what, uint32_t sites, uint64_t extra) {
-  fprintf(stderr, "%s: %u sites (%llu)\n", what, sites, (unsigned long long)extra);
-  ++g_failures;
-}
-
-// 0 hom-ref, 1 het, 2 hom-var, 3 missing
-uint32_t code_of(const uint64_t *row, uint32_t plane, uint32_t s) {
-  return (uint32_t)((row[s >> 6] >> (s & 63)) & 1) |
-         (uint32_t)((row[plane + (s >> 6)] >> (s & 63)) & 1) << 1;
-}
+// (fail: what, sites, one more number)
 
 // The table of the header, written out: the error code of one site, 0 for none.
 uint32_t classify(uint32_t f, uint32_t m, uint32_t c) {
@@ -132,10 +113,6 @@ void run_shape(uint32_t sites, uint32_t n, bool with_mask) {
         break;
       }
   }
-}
-
-void expect(const char *what, cuking_status got, cuking_status want) {
-  if (got != want) fail(what, 0, (uint64_t)got);
 }
 
 void check_refusals() {

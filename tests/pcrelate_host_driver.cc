@@ -1,5 +1,5 @@
 // Stand-alone driver of the host side of PC-Relate for the sanitizer build of
-// tests/test_pcrelate_host.py (g++ -fsanitize=address,undefined, csrc/king_host.cc compiled in).
+// tests/test_pcrelate_host.py (built and run by tests/host_driver.py, csrc/king_host.cc linked in).
 // Every buffer is an exact-size heap allocation, so a byte read or written past an end is
 // caught.
 //   1. cuking_pcrelate_matrix_host in the exact setting (d = 1, X = 1, beta in {0, 1, 2}: num an
@@ -14,25 +14,12 @@
 #include <vector>
 
 #include "cuking_amd.h"
+#include "host_driver_common.h"
 #include "king_pcrelate.h"
 
 namespace {
 
-uint64_t g_state = 0x9E3779B97F4A7C15ull;
-uint64_t next_random() {
-  g_state = g_state * 6364136223846793005ull + 1442695040888963407ull;
-  uint64_t x = g_state;
-  x ^= x >> 33;
-  x *= 0xFF51AFD7ED558CCDull;
-  x ^= x >> 33;
-  return x;
-}
-
-int g_failures = 0;
-void fail(const char *what, uint32_t n, uint32_t sites, uint32_t extra) {
-  fprintf(stderr, "%s: %u samples x %u sites (%u)\n", what, n, sites, extra);
-  ++g_failures;
-}
+// (fail: what, samples, sites, one more number)
 
 void run_shape(uint32_t n, uint32_t sites, cuking_submatrix block, uint32_t pad) {
   const uint32_t plane = (sites + 63) / 64 + (sites % 3 == 0 ? 1 : 0);  // (room beyond num_sites)

@@ -1,6 +1,6 @@
 // Stand-alone driver of the host side of PC-Relate for listed pairs for the sanitizer build of
-// tests/test_pcrelate_pairs_host.py (g++ -fsanitize=address,undefined, csrc/king_host.cc
-// compiled in).  Every buffer is an exact-size heap allocation, so a byte read or written past
+// tests/test_pcrelate_pairs_host.py (built and run by tests/host_driver.py, csrc/king_host.cc
+// linked in).  Every buffer is an exact-size heap allocation, so a byte read or written past
 // an end is caught.
 //   1. cuking_pcrelate_pairs_host in the exact setting (d = 1, X = 1, beta in {0, 1, 2}, f null:
 //      every sum a dyadic number) against the integer formula on plain code arrays, strides 8 and
@@ -15,25 +15,12 @@
 #include <vector>
 
 #include "cuking_amd.h"
+#include "host_driver_common.h"
 #include "king_pcrelate.h"
 
 namespace {
 
-uint64_t g_state = 0x9E3779B97F4A7C15ull;
-uint64_t next_random() {
-  g_state = g_state * 6364136223846793005ull + 1442695040888963407ull;
-  uint64_t x = g_state;
-  x ^= x >> 33;
-  x *= 0xFF51AFD7ED558CCDull;
-  x ^= x >> 33;
-  return x;
-}
-
-int g_failures = 0;
-void fail(const char *what, uint32_t n, uint32_t sites, uint32_t extra) {
-  fprintf(stderr, "%s: %u samples x %u sites (%u)\n", what, n, sites, extra);
-  ++g_failures;
-}
+// (fail: what, samples, sites, one more number)
 
 bool same_float(float a, float b) { return (std::isnan(a) && std::isnan(b)) || a == b; }
 

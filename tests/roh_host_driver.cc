@@ -1,8 +1,8 @@
 // Stand-alone driver of the host side of the runs of homozygosity for the sanitizer build of
-// tests/test_roh_host.py (g++ -fsanitize=address,undefined, csrc/king_host.cc compiled in).  Every
-// buffer is an exact-size heap allocation, so a byte read or written past an end is caught -- the
-// planes of exactly ceil(num_sites / 64) words, the group-start mask read for a link and the list
-// of samples above all.
+// tests/test_roh_host.py (built and run by tests/host_driver.py, csrc/king_host.cc linked in).
+// Every buffer is an exact-size heap allocation, so a byte read or written past an end is caught
+// -- the planes of exactly ceil(num_sites / 64) words, the group-start mask read for a link and
+// the list of samples above all.
 //   1. cuking_roh_samples_host against a walk over the sites one by one that links its runs
 //      afterwards: sample 0 is homozygous but for single hets at the word and step edges, next to
 //      each other, next to a group boundary, at site 0 and at the last site, and close to the end
@@ -19,7 +19,7 @@
 #include <vector>
 
 #include "cuking_amd.h"
-#include "ibd_driver_common.h"
+#include "host_driver_common.h"
 
 namespace {
 

@@ -1,5 +1,6 @@
 // Stand-alone driver of the byte-wide site gather's arithmetic (csrc/king_site_gather.h) for the
-// sanitizer build of tests/test_site_gather_host.py (g++ -fsanitize=address,undefined).
+// sanitizer build of tests/test_site_gather_host.py (built and run by tests/host_driver.py, with
+// nothing of the library linked in: of host_driver_common.h it uses what calls none of it).
 // gather_sites_kernel (csrc/king_sort.hip) replayed on the host, lane by lane, with the header's
 // helpers -- interleave, nibble pack, field lookup, 8 x 8 transposes, byte routing --, for G = 2
 // and G = 4, against a plain bit loop.  The staged sites and the wavefront's tile are exact-size
@@ -12,23 +13,12 @@
 #include <numeric>
 #include <vector>
 
+#include "host_driver_common.h"
 #include "king_site_gather.h"
 
 namespace {
 
 using namespace cuking;
-
-uint64_t g_state = 0x9E3779B97F4A7C15ull;
-uint64_t next_random() {
-  g_state = g_state * 6364136223846793005ull + 1442695040888963407ull;
-  uint64_t x = g_state;
-  x ^= x >> 33;
-  x *= 0xFF51AFD7ED558CCDull;
-  x ^= x >> 33;
-  return x;
-}
-
-int g_failures = 0;
 
 constexpr uint64_t kUnwritten = 0xA5A5A5A5A5A5A5A5ull;
 
@@ -155,5 +145,5 @@ int main() {
       }
     }
   printf("%d cases, %d failures\n", cases, g_failures);
-  return g_failures == 0 ? 0 : 1;
+  return g_failures != 0;
 }

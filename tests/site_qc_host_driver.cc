@@ -1,5 +1,5 @@
 // Stand-alone driver of the host side of site QC for the sanitizer build of
-// tests/test_site_qc_host.py (g++ -fsanitize=address,undefined, csrc/king_host.cc compiled in).
+// tests/test_site_qc_host.py (built and run by tests/host_driver.py, csrc/king_host.cc linked in).
 // Every buffer is an exact-size heap allocation, so a byte read or written past an end is caught.
 //   1. cuking_compact_sites_host against a bit-by-bit restatement, over several shapes and masks;
 //   2. the compaction kernel's own arithmetic (csrc/king_site_qc.h: the table built from the
@@ -15,27 +15,12 @@
 #include <vector>
 
 #include "cuking_amd.h"
+#include "host_driver_common.h"
 #include "king_site_qc.h"
 
 namespace {
 
-uint64_t g_state = 0x9E3779B97F4A7C15ull;
-uint64_t next_random() {
-  g_state = g_state * 6364136223846793005ull + 1442695040888963407ull;
-  uint64_t x = g_state;
-  x ^= x >> 33;
-  x *= 0xFF51AFD7ED558CCDull;
-  x ^= x >> 33;
-  return x;
-}
-
-int g_failures = 0;
-void fail(const char *what, uint32_t n, uint32_t m, int mask) {
-  fprintf(stderr, "%s: %u samples x %u sites, mask %d\n", what, n, m, mask);
-  ++g_failures;
-}
-
-bool bit_of(const uint64_t *words, uint64_t k) { return (words[k >> 6] >> (k & 63)) & 1; }
+// (fail: what, samples, sites, the kind of mask)
 
 // a bitset as the pack leaves it: random codes, padding missing
 std::unique_ptr<uint64_t[]> random_bitset(uint32_t n, uint32_t m, uint32_t wps) {
@@ -190,12 +175,12 @@ int main() {
     if (cuking_compact_sites_host(bits.get(), 2, wps, keep.get(), m, out.get(), 2) !=
             CUKING_ERR_INVALID_ARGUMENT ||
         strstr(cuking_last_error(), "no site passes") == nullptr)
-      fail("an empty mask is not refused", 2, m, -1);
+      fail("an empty mask is not refused", 2, m);
     keep[2] = 2;  // site 129
     if (cuking_compact_sites_host(bits.get(), 2, wps, keep.get(), m, out.get(), 2) !=
         CUKING_ERR_INVALID_ARGUMENT)
-      fail("a keep bit beyond num_sites is not refused", 2, m, -1);
+      fail("a keep bit beyond num_sites is not refused", 2, m);
   }
   printf("site_qc_host_driver: %d failures\n", g_failures);
-  return g_failures ? 1 : 0;
+  return g_failures != 0;
 }

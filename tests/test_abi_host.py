@@ -12,6 +12,7 @@ import pytest
 import cuking_amd
 from cuking_amd import _lib
 from conftest import ROOT, random_genotypes
+from host_driver import compile_c99
 
 
 def has_gpu():
@@ -37,16 +38,9 @@ def test_library_exports_every_declared_symbol():
 
 def test_header_is_plain_c(tmp_path):
     """The boundary must be consumable from C (no C++ / torch types)."""
-    import subprocess
-    src = tmp_path / "t.c"
-    src.write_text('#include "cuking_amd.h"\n'
-                   "int main(void) { cuking_result r; cuking_submatrix s;"
-                   " (void)r; (void)s; return sizeof(cuking_result) == 24 ? 0 : 1; }\n")
-    exe = tmp_path / "t"
-    subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-pedantic",
-                    f"-I{ROOT / 'include'}", str(src), "-o", str(exe)],
-                   check=True)
-    assert subprocess.run([str(exe)]).returncode == 0
+    compile_c99(tmp_path, '#include "cuking_amd.h"\n'
+                "int main(void) { cuking_result r; cuking_submatrix s;"
+                " (void)r; (void)s; return sizeof(cuking_result) == 24 ? 0 : 1; }\n", run=True)
 
 
 @pytest.mark.parametrize("n", [1, 2, 5, 10, 37, 100, 734000])

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 from conftest import random_genotypes
+from host_driver import compile_c99, run_sanitized_driver
 
 import cuking_amd
 from cuking_amd import _lib, plink
@@ -253,8 +254,7 @@ def test_driver_usage_errors_need_no_gpu(tmp_path, capsys):
 
 
 def test_header_is_still_plain_c(tmp_path):
-    src = tmp_path / "tu.c"
-    src.write_text("""
+    compile_c99(tmp_path, """
 #include "cuking_amd.h"
 typedef char abi_is_2[CUKING_ABI_VERSION == 2 ? 1 : -1];
 int use(const cuking_submatrix *sm, uint64_t *bits, const uint8_t *rows) {
@@ -267,8 +267,6 @@ int use(const cuking_submatrix *sm, uint64_t *bits, const uint8_t *rows) {
   return (int)cuking_pack_bed_host(sm, 2, bits, rows, cuking_bed_row_bytes(5), 0, 2, 2);
 }
 """)
-    subprocess.run(["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", f"-I{ROOT / 'include'}",
-                    "-c", str(src), "-o", str(tmp_path / "tu.o")], check=True)
     assert _lib.load().cuking_abi_version() == 2
 
 
@@ -276,11 +274,4 @@ def test_host_pack_under_asan_ubsan(tmp_path):
     """csrc/king_host.cc and a stand-alone driver (tests/bed_host_driver.cc: exact-size heap
     buffers, 37 x 129, shard by shard, one call and chunks) built with AddressSanitizer +
     UBSan.  A program of its own on the CPU: nothing is loaded into Python."""
-    from cuking_amd import build as b
-    exe = tmp_path / "bed_host_asan"
-    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined",
-                    "-fno-sanitize-recover=undefined", f"-I{b.INCLUDE}", f"-I{b.CSRC}",
-                    str(ROOT / "tests" / "bed_host_driver.cc"),
-                    *[str(b.CSRC / f) for f in b.HOST_ABI_SOURCES], "-o", str(exe)], check=True)
-    p = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300)
-    assert p.returncode == 0 and "0 failures" in p.stdout, p.stdout + p.stderr
+    run_sanitized_driver(tmp_path, "bed_host_driver")

@@ -3,13 +3,13 @@ against the dense float64 reference over the shared case list -- exact for integ
 within the accumulation bound for real ones --, its output rules, the refusals of both entry
 points, the header, and the host code under AddressSanitizer + UBSan.  No GPU."""
 import ctypes as C
-import subprocess
 from pathlib import Path
 
 import numpy as np
 import pytest
 
 from geno_cases import CASES, check_both_layouts, check_bound, check_exact, refusals
+from host_driver import compile_c99, run_sanitized_driver
 
 import cuking_amd
 from cuking_amd import _lib
@@ -112,8 +112,7 @@ def test_shared_constants():
 
 
 def test_header_is_still_plain_c(tmp_path):
-    src = tmp_path / "tu.c"
-    src.write_text("""
+    compile_c99(tmp_path, """
 #include "cuking_amd.h"
 int use(const uint64_t *bits, const float *table, const float *b, float *out) {
   cuking_status (*device)(cuking_ctx *, const uint64_t *, uint32_t, uint32_t, uint32_t,
@@ -124,8 +123,6 @@ int use(const uint64_t *bits, const float *table, const float *b, float *out) {
                                       out, CUKING_GENO_RHS_MAX);
 }
 """)
-    subprocess.run(["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", f"-I{ROOT / 'include'}",
-                    "-c", str(src), "-o", str(tmp_path / "tu.o")], check=True)
 
 
 def test_host_side_under_asan_ubsan(tmp_path):
@@ -133,11 +130,4 @@ def test_host_side_under_asan_ubsan(tmp_path):
     heap buffers, the host product against the definition on plain code arrays, the refusals)
     built with AddressSanitizer + UBSan.  A program of its own on the CPU: nothing is loaded
     into Python."""
-    from cuking_amd import build as b
-    exe = tmp_path / "geno_host_asan"
-    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined",
-                    "-fno-sanitize-recover=undefined", f"-I{b.INCLUDE}", f"-I{b.CSRC}",
-                    str(ROOT / "tests" / "geno_matmul_host_driver.cc"),
-                    *[str(b.CSRC / f) for f in b.HOST_ABI_SOURCES], "-o", str(exe)], check=True)
-    p = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300)
-    assert p.returncode == 0 and "0 failures" in p.stdout, p.stdout + p.stderr
+    run_sanitized_driver(tmp_path, "geno_matmul_host_driver")

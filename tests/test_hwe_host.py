@@ -4,7 +4,6 @@ tie constant's margin, the paper's known answers, what the case lists cover, the
 of filter_sites, the refusals, the ABI symbols and the stand-alone sanitizer driver."""
 import ctypes as C
 import math
-import subprocess
 from fractions import Fraction
 from pathlib import Path
 
@@ -16,6 +15,7 @@ from cuking_amd import _lib
 from cuking_amd._lib import CukingError, check
 
 import hwe_cases as hc
+from host_driver import run_sanitized_driver
 
 ROOT = Path(__file__).resolve().parent.parent
 
@@ -179,16 +179,9 @@ def test_host_side_under_asan_ubsan(tmp_path):
     """csrc/king_host.cc and a stand-alone driver (tests/hwe_host_driver.cc) built with
     AddressSanitizer + UBSan, contraction off.  A program of its own on the CPU: nothing is loaded
     into Python.  It recomputes the fixed edge rows and the paper's; the test compares the bits."""
-    from cuking_amd import build as b
-    exe = tmp_path / "hwe_host_asan"
-    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-ffp-contract=off",
-                    "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                    f"-I{b.INCLUDE}", f"-I{b.CSRC}", str(ROOT / "tests" / "hwe_host_driver.cc"),
-                    *[str(b.CSRC / f) for f in b.HOST_ABI_SOURCES], "-o", str(exe)], check=True)
     rows = [r for r, _ in hc.EDGE_ROWS] + [r for r, _ in hc.WIGGINTON]
-    text = "".join(f"{a} {b_} {c}\n" for a, b_, c in rows)
-    done = subprocess.run([str(exe)], input=text, capture_output=True, text=True, timeout=300)
-    assert done.returncode == 0 and "0 failures" in done.stdout, done.stdout + done.stderr
+    text = "".join(f"{a} {b} {c}\n" for a, b, c in rows)
+    done = run_sanitized_driver(tmp_path, "hwe_host_driver", stdin=text)
     lines = [l for l in done.stdout.splitlines() if l.startswith("row ")]
     assert len(lines) == len(rows)
     for row, line in zip(rows, lines):

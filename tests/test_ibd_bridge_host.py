@@ -3,22 +3,19 @@ ibd_bridge_cases.py (rows, bridged counts and sorted segments, bytewise), bridge
 the strict call, the refusals, the stand-alone sanitizer driver, and the end-to-end check on the
 synthetic cohort with genotyping errors."""
 import ctypes as C
-import subprocess
 from functools import lru_cache
-from pathlib import Path
 
 import numpy as np
 import pytest
 
 import ibd_bridge_cases as bc
 import ibd_cases as ic
+from host_driver import run_sanitized_driver
 from test_ibd_host import E2E, e2e_cohort
 
 import cuking_amd
 from cuking_amd import _lib, ibd
 from cuking_amd import pcrelate as pcr
-
-ROOT = Path(__file__).resolve().parent.parent
 
 
 @pytest.mark.parametrize("case", bc.CASES, ids=lambda c: c.name)
@@ -181,15 +178,7 @@ def test_a_row_depends_on_its_own_pair_only():
 def test_host_side_under_asan_ubsan(tmp_path):
     """csrc/king_host.cc and a stand-alone driver (tests/ibd_bridge_host_driver.cc) built with
     AddressSanitizer + UBSan.  A program of its own on the CPU: nothing is loaded into Python."""
-    from cuking_amd import build as b
-    exe = tmp_path / "ibd_bridge_host_asan"
-    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-ffp-contract=off",
-                    "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                    f"-I{b.INCLUDE}", f"-I{b.CSRC}",
-                    str(ROOT / "tests" / "ibd_bridge_host_driver.cc"),
-                    *[str(b.CSRC / f) for f in b.HOST_ABI_SOURCES], "-o", str(exe)], check=True)
-    p = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300)
-    assert p.returncode == 0 and "0 failures" in p.stdout, p.stdout + p.stderr
+    run_sanitized_driver(tmp_path, "ibd_bridge_host_driver")
 
 
 # ---- the end-to-end check on the synthetic cohort with genotyping errors ------------------------

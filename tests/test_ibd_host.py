@@ -3,7 +3,6 @@ ibd_cases.py (rows and sorted segments, bytewise), the row rules, every refusal 
 the overflow rule, genome_length / proportions() / relationship() on hand-made values, the .bim
 positions, the stand-alone sanitizer driver, and the end-to-end check on the synthetic cohort."""
 import ctypes as C
-import subprocess
 from functools import lru_cache
 from pathlib import Path
 
@@ -11,6 +10,7 @@ import numpy as np
 import pytest
 
 import ibd_cases as ic
+from host_driver import run_sanitized_driver
 
 import cuking_amd
 from cuking_amd import _lib, ibd, plink
@@ -251,14 +251,7 @@ def test_bim_positions_round_trip(tmp_path):
 def test_host_side_under_asan_ubsan(tmp_path):
     """csrc/king_host.cc and a stand-alone driver (tests/ibd_host_driver.cc) built with
     AddressSanitizer + UBSan.  A program of its own on the CPU: nothing is loaded into Python."""
-    from cuking_amd import build as b
-    exe = tmp_path / "ibd_host_asan"
-    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-ffp-contract=off",
-                    "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                    f"-I{b.INCLUDE}", f"-I{b.CSRC}", str(ROOT / "tests" / "ibd_host_driver.cc"),
-                    *[str(b.CSRC / f) for f in b.HOST_ABI_SOURCES], "-o", str(exe)], check=True)
-    p = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300)
-    assert p.returncode == 0 and "0 failures" in p.stdout, p.stdout + p.stderr
+    run_sanitized_driver(tmp_path, "ibd_host_driver")
 
 
 def test_the_test_encoder_is_the_library_layout():

@@ -3,22 +3,19 @@ explicit list of all pairs and against the per-site numpy walk of ibd_cases.py, 
 70-sample cohort, min_total, the buffer rule, the refusals, the superset guarantee for the bridged
 call, the stand-alone sanitizer driver and the end-to-end check on the synthetic cohort."""
 import ctypes as C
-import subprocess
-from pathlib import Path
 
 import numpy as np
 import pytest
 
 import ibd_cases as ic
 import ibd_scan_cases as sc
+from host_driver import run_sanitized_driver
 from test_ibd_bridge_host import e2e_codes
 from test_ibd_host import E2E, e2e_cohort
 
 import cuking_amd
 from cuking_amd import _lib, ibd
 from cuking_amd import pcrelate as pcr
-
-ROOT = Path(__file__).resolve().parent.parent
 
 
 def check_case(case):
@@ -213,15 +210,7 @@ def test_the_scan_is_a_superset_of_the_bridged_call(oracle, bridge):
 def test_host_side_under_asan_ubsan(tmp_path):
     """csrc/king_host.cc and a stand-alone driver (tests/ibd_scan_host_driver.cc) built with
     AddressSanitizer + UBSan.  A program of its own on the CPU: nothing is loaded into Python."""
-    from cuking_amd import build as b
-    exe = tmp_path / "ibd_scan_host_asan"
-    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-ffp-contract=off",
-                    "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                    f"-I{b.INCLUDE}", f"-I{b.CSRC}",
-                    str(ROOT / "tests" / "ibd_scan_host_driver.cc"),
-                    *[str(b.CSRC / f) for f in b.HOST_ABI_SOURCES], "-o", str(exe)], check=True)
-    p = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300)
-    assert p.returncode == 0 and "0 failures" in p.stdout, p.stdout + p.stderr
+    run_sanitized_driver(tmp_path, "ibd_scan_host_driver")
 
 
 def test_end_to_end_on_the_host(oracle):

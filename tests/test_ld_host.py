@@ -3,12 +3,11 @@ executable form) against a known answer written out by hand and against the nump
 bit for bit; the kept set against the sequential greedy; the refusals; the driver's usage
 errors.  No GPU."""
 import ctypes as C
-import subprocess
-from pathlib import Path
 
 import numpy as np
 import pytest
 
+from host_driver import compile_c99, run_sanitized_driver
 from ld_cases import (GUARD, check_guarantees, greedy_numpy, ld_cohort, ld_edges_numpy,
                       priority_numpy, same_records, site_bits_numpy,
                       test_the_restatement_is_the_squared_correlation)  # noqa: F401 (collected)
@@ -16,8 +15,6 @@ from site_qc_cases import pack, site_counts_numpy
 
 import cuking_amd
 from cuking_amd import _lib
-
-ROOT = Path(__file__).resolve().parent.parent
 
 
 def host_edges(geno, window, r2, group=None):
@@ -248,8 +245,7 @@ def test_driver_usage_errors_need_no_gpu(tmp_path, capsys, monkeypatch):
 
 
 def test_header_is_still_plain_c(tmp_path):
-    src = tmp_path / "tu.c"
-    src.write_text("""
+    compile_c99(tmp_path, """
 #include "cuking_amd.h"
 typedef char abi_is_2[CUKING_ABI_VERSION == 2 ? 1 : -1];
 int use(const uint64_t *bits, uint64_t *site_bits, const int32_t *group, cuking_result *records) {
@@ -267,8 +263,6 @@ int use(const uint64_t *bits, uint64_t *site_bits, const int32_t *group, cuking_
   return (int)cuking_ld_edges_host(site_bits, 100, 70, 50, 0.2f, group, records, 16, &count);
 }
 """)
-    subprocess.run(["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", f"-I{ROOT / 'include'}",
-                    "-c", str(src), "-o", str(tmp_path / "tu.o")], check=True)
     assert _lib.load().cuking_abi_version() == 2
 
 
@@ -277,11 +271,4 @@ def test_host_side_under_asan_ubsan(tmp_path):
     buffers; the host transpose and edge list against the definition on plain genotype arrays,
     the helpers of csrc/king_ld.h) built with AddressSanitizer + UBSan.  A program of its own
     on the CPU: nothing is loaded into Python."""
-    from cuking_amd import build as b
-    exe = tmp_path / "ld_host_asan"
-    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined",
-                    "-fno-sanitize-recover=undefined", f"-I{b.INCLUDE}", f"-I{b.CSRC}",
-                    str(ROOT / "tests" / "ld_host_driver.cc"),
-                    *[str(b.CSRC / f) for f in b.HOST_ABI_SOURCES], "-o", str(exe)], check=True)
-    p = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300)
-    assert p.returncode == 0 and "0 failures" in p.stdout, p.stdout + p.stderr
+    run_sanitized_driver(tmp_path, "ld_host_driver")

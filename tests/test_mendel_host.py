@@ -4,19 +4,17 @@ covers, the chunked wrapper, per_sample, candidate_trios on a hand-built pedigre
 read_fam_parents on written .fam files, the refusals with their messages and the stand-alone
 sanitizer driver."""
 import ctypes as C
-import subprocess
 from pathlib import Path
 
 import numpy as np
 import pytest
 
 import mendel_cases as mc
+from host_driver import run_sanitized_driver
 
 import cuking_amd
 from cuking_amd import _lib, mendel, pcrelate, plink
 from cuking_amd.mendel import NO_PARENT
-
-ROOT = Path(__file__).resolve().parent.parent
 
 
 @pytest.mark.parametrize("case", mc.CASES, ids=lambda c: c.name)
@@ -339,11 +337,4 @@ def test_the_wrappers_refuse_too():
 def test_host_side_under_asan_ubsan(tmp_path):
     """csrc/king_host.cc and a stand-alone driver (tests/mendel_host_driver.cc) built with
     AddressSanitizer + UBSan.  A program of its own on the CPU: nothing is loaded into Python."""
-    from cuking_amd import build as b
-    exe = tmp_path / "mendel_host_asan"
-    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-ffp-contract=off",
-                    "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                    f"-I{b.INCLUDE}", f"-I{b.CSRC}", str(ROOT / "tests" / "mendel_host_driver.cc"),
-                    *[str(b.CSRC / f) for f in b.HOST_ABI_SOURCES], "-o", str(exe)], check=True)
-    p = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300)
-    assert p.returncode == 0 and "0 failures" in p.stdout, p.stdout + p.stderr
+    run_sanitized_driver(tmp_path, "mendel_host_driver")

@@ -2,7 +2,6 @@
 float64 reference of pcrelate_pairs_cases.py, the teeth of the tolerances, the refusals through
 the raw ABI, the wrapper's errors, relationship() on hand-made values, the stand-alone sanitizer
 driver, and the end-to-end fixture through pca_host -> pcrelate_pairs_host."""
-import subprocess
 from functools import lru_cache
 from pathlib import Path
 
@@ -11,6 +10,7 @@ import pytest
 
 import pcrelate_cases as pc
 import pcrelate_pairs_cases as pp
+from host_driver import run_sanitized_driver
 
 import cuking_amd
 from cuking_amd import _lib
@@ -200,15 +200,7 @@ def test_host_side_under_asan_ubsan(tmp_path):
     """csrc/king_host.cc and a stand-alone driver (tests/pcrelate_pairs_host_driver.cc) built
     with AddressSanitizer + UBSan and without contraction.  A program of its own on the CPU:
     nothing is loaded into Python."""
-    from cuking_amd import build as b
-    exe = tmp_path / "pcrelate_pairs_host_asan"
-    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-ffp-contract=off",
-                    "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                    f"-I{b.INCLUDE}", f"-I{b.CSRC}",
-                    str(ROOT / "tests" / "pcrelate_pairs_host_driver.cc"),
-                    *[str(b.CSRC / f) for f in b.HOST_ABI_SOURCES], "-o", str(exe)], check=True)
-    p = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300)
-    assert p.returncode == 0 and "0 failures" in p.stdout, p.stdout + p.stderr
+    run_sanitized_driver(tmp_path, "pcrelate_pairs_host_driver")
 
 
 # ---- the end-to-end fixture -------------------------------------------------------------------

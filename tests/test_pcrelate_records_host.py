@@ -4,7 +4,6 @@ against the float64 reference at the gap thresholds of pcrelate_records_cases.py
 stand-alone sanitizer driver, and the end-to-end fixture through pca_host ->
 pcrelate_records_host."""
 import ctypes as C
-import subprocess
 from functools import lru_cache
 from pathlib import Path
 
@@ -13,6 +12,7 @@ import pytest
 
 import pcrelate_cases as pc
 import pcrelate_records_cases as rc
+from host_driver import run_sanitized_driver
 
 import cuking_amd
 from cuking_amd import KING_RESULT_DTYPE, _lib
@@ -215,15 +215,7 @@ def test_host_side_under_asan_ubsan(tmp_path):
     """csrc/king_host.cc and a stand-alone driver (tests/pcrelate_records_host_driver.cc) built
     with AddressSanitizer + UBSan and without contraction.  A program of its own on the CPU:
     nothing is loaded into Python."""
-    from cuking_amd import build as b
-    exe = tmp_path / "pcrelate_records_host_asan"
-    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-ffp-contract=off",
-                    "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                    f"-I{b.INCLUDE}", f"-I{b.CSRC}",
-                    str(ROOT / "tests" / "pcrelate_records_host_driver.cc"),
-                    *[str(b.CSRC / f) for f in b.HOST_ABI_SOURCES], "-o", str(exe)], check=True)
-    p = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300)
-    assert p.returncode == 0 and "0 failures" in p.stdout, p.stdout + p.stderr
+    run_sanitized_driver(tmp_path, "pcrelate_records_host_driver")
 
 
 def test_end_to_end_on_the_host():

@@ -3,18 +3,15 @@ and sorted segments, bytewise), the independent cross-check through the IBD code
 with their messages, the overflow rule, froh(), the stand-alone sanitizer driver and the
 end-to-end cohort with genotyping errors."""
 import ctypes as C
-import subprocess
-from pathlib import Path
 
 import numpy as np
 import pytest
 
 import roh_cases as rc
+from host_driver import run_sanitized_driver
 
 import cuking_amd
 from cuking_amd import _lib, ibd, roh
-
-ROOT = Path(__file__).resolve().parent.parent
 
 
 def bridges_of(case):
@@ -262,14 +259,7 @@ def test_froh_on_hand_made_values():
 def test_host_side_under_asan_ubsan(tmp_path):
     """csrc/king_host.cc and a stand-alone driver (tests/roh_host_driver.cc) built with
     AddressSanitizer + UBSan.  A program of its own on the CPU: nothing is loaded into Python."""
-    from cuking_amd import build as b
-    exe = tmp_path / "roh_host_asan"
-    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-ffp-contract=off",
-                    "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                    f"-I{b.INCLUDE}", f"-I{b.CSRC}", str(ROOT / "tests" / "roh_host_driver.cc"),
-                    *[str(b.CSRC / f) for f in b.HOST_ABI_SOURCES], "-o", str(exe)], check=True)
-    p = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300)
-    assert p.returncode == 0 and "0 failures" in p.stdout, p.stdout + p.stderr
+    run_sanitized_driver(tmp_path, "roh_host_driver")
 
 
 # ---- end to end ----------------------------------------------------------------------------------

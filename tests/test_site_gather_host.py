@@ -2,25 +2,17 @@
 per-site interleave, the nibble pack, the 8 x 8 bit transposes and the byte routing) replayed
 lane by lane by a stand-alone program against a plain bit loop, under AddressSanitizer + UBSan;
 the option's accepted values; the test entry point's refusals."""
-import subprocess
-from pathlib import Path
+from host_driver import run_sanitized_driver
 
 from cuking_amd import _lib
-
-ROOT = Path(__file__).resolve().parent.parent
 
 
 def test_gather_arithmetic_under_asan_ubsan(tmp_path):
     """tests/site_gather_host_driver.cc: G = 2 and 4 over 1, 2, 3, 5, 9 samples, planes of 1, 3,
     7, 65 and 320 words and an odd words_per_sample, four orders each.  A program of its own on
     the CPU: nothing is loaded into Python."""
-    from cuking_amd import build as b
-    exe = tmp_path / "site_gather_host_asan"
-    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined",
-                    "-fno-sanitize-recover=undefined", f"-I{b.INCLUDE}", f"-I{b.CSRC}",
-                    str(ROOT / "tests" / "site_gather_host_driver.cc"), "-o", str(exe)], check=True)
-    p = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300)
-    assert p.returncode == 0 and "240 cases, 0 failures" in p.stdout, p.stdout + p.stderr
+    run_sanitized_driver(tmp_path, "site_gather_host_driver", link_host=False,
+                         expect="240 cases, 0 failures")
 
 
 def test_the_entry_point_checks_its_arguments_before_it_touches_a_device():

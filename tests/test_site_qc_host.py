@@ -2,19 +2,16 @@
 form) against the definition written out by hand, against numpy restatements and against
 cuking_pack_host of the kept genotypes; the refusals; the driver's usage errors.  No GPU."""
 import ctypes as C
-import subprocess
-from pathlib import Path
 
 import numpy as np
 import pytest
 
 from conftest import random_genotypes
+from host_driver import compile_c99, run_sanitized_driver
 from site_qc_cases import GUARD, SAMPLES, SITES, masks, pack, rule_numpy, site_counts_numpy
 
 import cuking_amd
 from cuking_amd import _lib
-
-ROOT = Path(__file__).resolve().parent.parent
 
 
 def test_known_answer_from_the_definition():
@@ -204,8 +201,7 @@ def test_driver_usage_errors_need_no_gpu(tmp_path, capsys, monkeypatch):
 
 
 def test_header_is_still_plain_c(tmp_path):
-    src = tmp_path / "tu.c"
-    src.write_text("""
+    compile_c99(tmp_path, """
 #include "cuking_amd.h"
 typedef char abi_is_2[CUKING_ABI_VERSION == 2 ? 1 : -1];
 int use(const uint32_t *counts, const uint64_t *in, uint64_t *keep, uint64_t *out) {
@@ -224,8 +220,6 @@ int use(const uint32_t *counts, const uint64_t *in, uint64_t *keep, uint64_t *ou
                                         cuking_words_per_sample(kept));
 }
 """)
-    subprocess.run(["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", f"-I{ROOT / 'include'}",
-                    "-c", str(src), "-o", str(tmp_path / "tu.o")], check=True)
     assert _lib.load().cuking_abi_version() == 2
 
 
@@ -235,11 +229,4 @@ def test_host_side_under_asan_ubsan(tmp_path):
     the count kernel's bit-sliced counters from csrc/king_site_qc.h run on the host, the site
     rule) built with AddressSanitizer + UBSan.  A program of its own on the CPU: nothing is
     loaded into Python."""
-    from cuking_amd import build as b
-    exe = tmp_path / "site_qc_host_asan"
-    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined",
-                    "-fno-sanitize-recover=undefined", f"-I{b.INCLUDE}", f"-I{b.CSRC}",
-                    str(ROOT / "tests" / "site_qc_host_driver.cc"),
-                    *[str(b.CSRC / f) for f in b.HOST_ABI_SOURCES], "-o", str(exe)], check=True)
-    p = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300)
-    assert p.returncode == 0 and "0 failures" in p.stdout, p.stdout + p.stderr
+    run_sanitized_driver(tmp_path, "site_qc_host_driver")
