@@ -327,6 +327,33 @@ def _out_capacity(out, max_records):
     return max_records
 
 
+def _ld_edges(place, site_bits, num_sites, num_stored, window, r2, group, max_records,
+              out=None):
+    num_sites, num_stored = _count(num_sites, "num_sites"), _count(num_stored, "num_stored")
+    window, r2 = _ld_arguments(window, r2)
+    have, need = place.words(site_bits, "site_bits"), num_sites * 2 * ld_site_words(num_stored)
+    if have != need:
+        raise ValueError(f"site_bits holds {have} words, {num_sites} sites of {num_stored} "
+                         f"samples take {need} (transpose_sites)")
+    group = place.sites(group, "group", num_sites, np.int32)
+    if out is not None:
+        place.out(out, "out", KING_RESULT_DTYPE)
+        max_records = _out_capacity(out, max_records)
+    count = C.c_uint64(0)
+    place.uploads_done()
+
+    def call(capacity):
+        recs = out if out is not None else place.alloc(max(capacity, 1), KING_RESULT_DTYPE)
+        return recs, place.fn("ld_edges")(
+            place.ptr(site_bits, pad=True), num_sites, num_stored, window, r2, place.ptr(group),
+            place.ptr(recs, pad=True), capacity, C.byref(count))
+
+    recs = _counted_buffer(call, _ld_default_records(num_sites, window), max_records,
+                           "max_records", count, "num_records")
+    place.keep()
+    return place.trim(recs, count.value), int(count.value)
+
+
 def ld_edges_host(site_bits: np.ndarray, num_sites: int, num_stored: int, window: int = 50,
                   r2: float = 0.2, group=None, max_records=None):
     """cuking_ld_edges_host: the pairs of sites ``a < b``, ``b - a < window``, of one
@@ -336,42 +363,27 @@ def ld_edges_host(site_bits: np.ndarray, num_sites: int, num_stored: int, window
     samples, sorted by (a, b).  Without ``max_records`` the buffer is sized like the device
     wrapper's and grown once to the exact count; with it, an overflow raises
     ``ResourceExhaustedError`` whose ``num_records`` is the exact count."""
-    assert site_bits.dtype == np.uint64 and site_bits.flags.c_contiguous
-    num_sites, num_stored = _count(num_sites, "num_sites"), _count(num_stored, "num_stored")
-    window, r2 = _ld_arguments(window, r2)
-    if site_bits.size != num_sites * 2 * ld_site_words(num_stored):
-        raise ValueError(f"site_bits holds {site_bits.size} words, {num_sites} sites of "
-                         f"{num_stored} samples need {num_sites * 2 * ld_site_words(num_stored)}")
-    if group is not None:
-        group = np.ascontiguousarray(group, dtype=np.int32)
-        if group.shape != (num_sites,):
-            raise ValueError(f"group must hold {num_sites} entries, not {group.shape}")
-    pad = np.zeros(1, dtype=np.uint64)
-    count = C.c_uint64(0)
-
-    def call(capacity):
-        recs = np.zeros(max(capacity, 1), dtype=KING_RESULT_DTYPE)
-        status = _lib.load().cuking_ld_edges_host(
-            (site_bits if site_bits.size else pad).ctypes.data, num_sites, num_stored, window, r2,
-            group.ctypes.data if group is not None and num_sites else None, recs.ctypes.data,
-            capacity, C.byref(count))
-        return recs, status
-
-    recs = _counted_buffer(call, _ld_default_records(num_sites, window), max_records,
-                           "max_records", count, "num_records")
-    return sort_results(recs[:count.value].copy()), int(count.value)
+    from ._place import HOST
+    recs, count = _ld_edges(HOST, site_bits, num_sites, num_stored, window, r2, group, max_records)
+    return sort_results(recs), count
 
 
-def _geno_host_matrix(a, name: str, min_rows: int, cols=None) -> np.ndarray:
-    """A float32 host matrix whose rows are contiguous (a pitch between rows is fine)."""
-    if not isinstance(a, np.ndarray) or a.dtype != np.float32 or a.ndim != 2 or \
-            (a.shape[1] > 1 and a.strides[1] != 4) or a.strides[0] % 4 or \
-            (a.shape[0] > 1 and a.strides[0] < 4 * a.shape[1]):
-        raise ValueError(f"{name} must be a float32 [rows, cols] array with contiguous rows")
-    if a.shape[0] < min_rows or cols is not None and a.shape[1] != cols:
-        raise ValueError(f"{name} must have at least {min_rows} rows"
-                         f"{'' if cols is None else f' of {cols} columns'}, not {a.shape}")
-    return a
+def _geno_matmul(place, bits, words_per_row, num_cols, table, rhs, per_row, out):
+    words_per_row, num_cols = _count(words_per_row, "words_per_row"), _count(num_cols, "num_cols")
+    rows = place.bits(bits, words_per_row)
+    table, ldt = place.matrix(table, "table", rows if per_row else num_cols, 4)
+    if table.shape[0] > 1 and ldt != 4:
+        raise ValueError("table must be contiguous")
+    rhs, ldr = place.matrix(rhs, "rhs", num_cols)
+    num_rhs = rhs.shape[1]
+    if out is None:
+        out = place.alloc((rows, num_rhs), np.float32)
+    out, ldo = place.matrix(out, "out", rows, num_rhs)
+    check(place.fn("geno_matmul")(
+        place.ptr(bits, pad=True), rows, words_per_row, num_cols, place.ptr(table, pad=True),
+        _lib.GENO_TABLE_PER_ROW if per_row else _lib.GENO_TABLE_PER_COLUMN,
+        place.ptr(rhs, pad=True), ldr, num_rhs, place.ptr(out, pad=True), ldo))
+    return out
 
 
 def geno_matmul_host(bits: np.ndarray, words_per_row: int, num_cols: int, table, rhs,
@@ -383,25 +395,8 @@ def geno_matmul_host(bits: np.ndarray, words_per_row: int, num_cols: int, table,
     form.  ``table``: float32 ``[num_cols, 4]``, or ``[rows, 4]`` with ``per_row``; ``rhs``:
     float32 ``[num_cols, num_rhs]``; ``out``: float32 ``[rows, num_rhs]`` to write into (both
     may be column slices of wider arrays: their row pitch is passed on)."""
-    assert bits.dtype == np.uint64 and bits.flags.c_contiguous
-    words_per_row, num_cols = _count(words_per_row, "words_per_row"), _count(num_cols, "num_cols")
-    rows = bits.size // words_per_row if words_per_row else 0
-    table = _geno_host_matrix(table, "table", rows if per_row else num_cols, 4)
-    if not table.flags.c_contiguous:
-        raise ValueError("table must be contiguous")
-    rhs = _geno_host_matrix(rhs, "rhs", num_cols)
-    num_rhs = rhs.shape[1]
-    if out is None:
-        out = np.empty((rows, num_rhs), dtype=np.float32)
-    _geno_host_matrix(out, "out", rows, num_rhs)
-    pad = np.zeros(4, dtype=np.float32)
-    check(_lib.load().cuking_geno_matmul_host(
-        (bits if bits.size else pad).ctypes.data, rows, words_per_row, num_cols,
-        (table if table.size else pad).ctypes.data,
-        _lib.GENO_TABLE_PER_ROW if per_row else _lib.GENO_TABLE_PER_COLUMN,
-        (rhs if rhs.size else pad).ctypes.data, max(rhs.strides[0] // 4, num_rhs), num_rhs,
-        (out if out.size else pad).ctypes.data, max(out.strides[0] // 4, num_rhs)))
-    return out
+    from ._place import HOST
+    return _geno_matmul(HOST, bits, words_per_row, num_cols, table, rhs, per_row, out)
 
 
 def ld_priority_host(counts, num_sites: int) -> np.ndarray:
@@ -1066,35 +1061,9 @@ class KingContext:
         once with the exact count if that overflows; with it (or with ``out``, a tensor to
         write into), an overflow raises ``ResourceExhaustedError`` whose ``num_records`` is
         the exact count -- nothing is written past the buffer.  WAITS for the stream."""
-        import torch
-        num_sites, num_stored = _count(num_sites, "num_sites"), _count(num_stored, "num_stored")
-        window, r2 = _ld_arguments(window, r2)
-        dev = f"cuda:{self.device}"
-        need = num_sites * 2 * self.lib.cuking_ld_site_words(num_stored)
-        _device_tensor(self.device, site_bits, "site_bits", torch.int64, min_numel=need)
-        if site_bits.numel() != need:
-            raise ValueError(f"site_bits holds {site_bits.numel()} words, {num_sites} sites of "
-                             f"{num_stored} samples take {need} (transpose_sites)")
-        if group is not None:
-            if not isinstance(group, torch.Tensor):
-                group = torch.from_numpy(np.ascontiguousarray(group, dtype=np.int32)).to(dev)
-            _device_tensor(self.device, group, "group", torch.int32, shape=(num_sites,))
-        if out is not None:
-            _device_tensor(self.device, out, "out", torch.int32, cols=6)
-            max_records = _out_capacity(out, max_records)
-        count = C.c_uint64(0)
-
-        def call(capacity):
-            records = out if out is not None else torch.empty((max(capacity, 1), 6),
-                                                              dtype=torch.int32, device=dev)
-            return records, self.lib.cuking_ld_edges(
-                self.handle, site_bits.data_ptr(), num_sites, num_stored, window, r2,
-                group.data_ptr() if group is not None and num_sites else None,
-                records.data_ptr(), capacity, C.byref(count), _stream_handle(stream))
-
-        records = _counted_buffer(call, _ld_default_records(num_sites, window), max_records,
-                                  "max_records", count, "num_records")
-        return records, int(count.value)
+        from ._place import DevicePlace
+        return _ld_edges(DevicePlace(self, stream), site_bits, num_sites, num_stored, window, r2,
+                         group, max_records, out)
 
     def ld_prune(self, bit_sets, words_per_sample: int, num_sites: int, window: int = 50,
                  r2: float = 0.2, group=None, priority=None, compact: bool = True) -> "LDPrune":
@@ -1132,19 +1101,6 @@ class KingContext:
         return LDPrune(keep_words, num_sites, bits, wps, sites, records, count, chosen.rounds)
 
     # -- genotype matrix products, PCA ------------------------------------------
-    def _geno_matrix(self, t, name: str, min_rows: int, cols=None):
-        import torch
-        _device_tensor(self.device, t, name, torch.float32, contiguous=False)
-        # (the strides of an empty tensor say nothing)
-        if t.dim() != 2 or t.numel() and ((t.shape[1] > 1 and t.stride(1) != 1) or
-                                          (t.shape[0] > 1 and t.stride(0) < t.shape[1])):
-            raise ValueError(f"{name} must be a [rows, cols] tensor with contiguous rows")
-        if t.shape[0] < min_rows or cols is not None and t.shape[1] != cols:
-            raise ValueError(f"{name} must have at least {min_rows} rows"
-                             f"{'' if cols is None else f' of {cols} columns'}, "
-                             f"not {tuple(t.shape)}")
-        return t
-
     def geno_matmul(self, bits, words_per_row: int, num_cols: int, table, rhs,
                     per_row: bool = False, out=None, stream=None):
         """The 2-bit genotype matrix times a dense float32 matrix (cuking_geno_matmul), the
@@ -1157,23 +1113,9 @@ class KingContext:
         ``[num_cols, num_rhs <= 64]``; ``out``: float32 ``[rows, num_rhs]``, overwritten (both
         may be column slices of wider tensors).  Exact for integer tables and ``rhs`` while the
         sums stay below 2^24; the same bits on every call.  Does not synchronise."""
-        import torch
-        rows = self._rows_of(bits, words_per_row)
-        num_cols = _count(num_cols, "num_cols")
-        table = self._geno_matrix(table, "table", rows if per_row else num_cols, 4)
-        if not table.is_contiguous():
-            raise ValueError("table must be contiguous")
-        rhs = self._geno_matrix(rhs, "rhs", num_cols)
-        num_rhs = rhs.shape[1]
-        if out is None:
-            out = torch.empty((rows, num_rhs), dtype=torch.float32, device=f"cuda:{self.device}")
-        self._geno_matrix(out, "out", rows, num_rhs)
-        check(self.lib.cuking_geno_matmul(
-            self.handle, bits.data_ptr(), rows, words_per_row, num_cols, table.data_ptr(),
-            _lib.GENO_TABLE_PER_ROW if per_row else _lib.GENO_TABLE_PER_COLUMN,
-            rhs.data_ptr(), max(rhs.stride(0), num_rhs), num_rhs, out.data_ptr(),
-            max(out.stride(0), num_rhs), _stream_handle(stream)))
-        return out
+        from ._place import DevicePlace
+        return _geno_matmul(DevicePlace(self, stream), bits, words_per_row, num_cols, table, rhs,
+                            per_row, out)
 
     def pca(self, bits, words_per_sample: int, num_sites: int, k: int = 10, fit=None,
             oversample: int = 10, iterations: int = 10, seed: int = 0):

@@ -20,10 +20,10 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib
-from ._lib import check
+from ._place import HOST, DevicePlace, site_array, tensor_to_host
 from .api import KING_CUTOFFS, _count, _counted_buffer, _out_capacity
 from .pcrelate import (DUPLICATE, FULL_SIBLING, PARENT_CHILD, SECOND_DEGREE, THIRD_DEGREE,
-                       UNRELATED, _block, _default_records, _device_pairs, _host_pairs)
+                       UNRELATED, _block, _default_records)
 
 MIN_SITES = _lib.IBD_MIN_SITES
 # cuking_ibd_pair, cuking_ibd_segment
@@ -117,20 +117,6 @@ class IBDPairs:
         return code
 
 
-def _site_array(values, name: str, num_sites: int, dtype):
-    """None, or ``values`` as a contiguous ``dtype`` ``[num_sites]`` host array."""
-    if values is None:
-        return None
-    values = np.asarray(values)
-    if values.ndim != 1 or values.shape[0] != num_sites or values.dtype.kind not in "iu":
-        raise ValueError(f"{name} must be an integer [{num_sites}] array, not {values.dtype} "
-                         f"{values.shape}")
-    info = np.iinfo(dtype)
-    if values.size and (int(values.min()) < info.min or int(values.max()) > info.max):
-        raise ValueError(f"{name} must fit {np.dtype(dtype).name}")
-    return np.ascontiguousarray(values, dtype=dtype)
-
-
 def genome_length(group, pos, num_sites: int) -> int:
     """The length a pair that shares everything would have: the sum over the groups of
     ``pos[last] - pos[first]`` (``pos`` None: the site index; ``group`` None: one group), on
@@ -138,9 +124,9 @@ def genome_length(group, pos, num_sites: int) -> int:
     num_sites = _count(num_sites, "num_sites")
     if num_sites == 0:
         return 0
-    group = _site_array(group, "group", num_sites, np.int32)
+    group = site_array(group, "group", num_sites, np.int32)
     pos = np.arange(num_sites, dtype=np.int64) if pos is None else \
-        _site_array(pos, "pos", num_sites, np.uint32).astype(np.int64)
+        site_array(pos, "pos", num_sites, np.uint32).astype(np.int64)
     first = np.ones(num_sites, dtype=bool)
     if group is not None:
         first[1:] = group[1:] != group[:-1]
@@ -150,12 +136,22 @@ def genome_length(group, pos, num_sites: int) -> int:
     return int(pos[last].sum() - pos[first].sum())
 
 
-def _thresholds(min_sites, min_length):
-    return _count(min_sites, "min_sites"), _count(min_length, "min_length")
+def _place_genome_length(place, group, pos, num_sites: int) -> int:
+    return genome_length(place.host_sites(group, np.int32), place.host_sites(pos, np.uint32),
+                         num_sites)
 
 
-def _bridge(bridge_sites) -> int:
-    return _count(bridge_sites, "bridge_sites")
+def _scan_head(place, bits, words_per_sample, num_sites, group, pos, min_sites, min_length):
+    """What the argument list of every run walk (IBD pairs, IBD scan, ROH) begins with, as
+    ``(head, num_stored, owners)``; ``owners`` keeps the site arrays behind ``head`` alive."""
+    words_per_sample = _count(words_per_sample, "words_per_sample")
+    num_sites = _count(num_sites, "num_sites")
+    min_sites, min_length = _count(min_sites, "min_sites"), _count(min_length, "min_length")
+    num_stored = place.bits(bits, words_per_sample)
+    group = place.sites(group, "group", num_sites, np.int32)
+    pos = place.sites(pos, "pos", num_sites, np.uint32)
+    return (place.ptr(bits, pad=True), num_stored, words_per_sample, num_sites, place.ptr(group),
+            place.ptr(pos), min_sites, min_length), num_stored, (group, pos)
 
 
 def _default_segments(count: int) -> int:
@@ -164,12 +160,60 @@ def _default_segments(count: int) -> int:
     return max(1, 4 * count)
 
 
-def _segment_buffer(call, count: int, want: bool, max_segments, found):
-    """The buffer rule (``_counted_buffer``) of a segment list, for every call that has one:
-    ``_default_segments(count)`` by default, and a list that is not wanted (then
-    ``max_segments`` is None) has capacity 0 and is not counted."""
-    return _counted_buffer(call, _default_segments(count) if want else 0, max_segments,
+def _segment_list(place, call, count: int, want: bool, max_segments):
+    """The segment list of a call that has one, as ``(segments or None, num_segments)``:
+    ``call(pointer, capacity, counter)`` is the library call with the list's three arguments.
+    The buffer rule is ``_counted_buffer``'s with ``_default_segments(count)`` by default; a
+    list that is not wanted (then ``max_segments`` is None) has no buffer, capacity 0 and no
+    counter."""
+    found = C.c_uint64(0)
+
+    def sized(capacity):
+        segs = place.alloc(max(capacity, 1), IBD_SEGMENT_DTYPE)
+        return segs, call(place.ptr(segs) if want and capacity else None,
+                          capacity if want else 0, C.byref(found) if want else None)
+
+    segs = _counted_buffer(sized, _default_segments(count) if want else 0, max_segments,
                            "max_segments", found, "num_segments")
+    place.keep(segs)
+    return (place.trim(segs, found.value) if want else None), int(found.value)
+
+
+def _ibd_segments_raw(place, bits, words_per_sample, num_sites, pairs, group, pos, min_sites,
+                      min_length, segments, max_segments, num_records, bridge_sites, out=None):
+    head, _, owners = _scan_head(place, bits, words_per_sample, num_sites, group, pos, min_sites,
+                                 min_length)
+    bridge_sites = _count(bridge_sites, "bridge_sites")
+    owner, count, stride = place.pairs(pairs, num_records)
+    out = place.alloc(count, IBD_PAIR_DTYPE) if out is None else \
+        place.out(out, "out", IBD_PAIR_DTYPE, count)
+    pair = (place.ptr(owner) if count else None, count, stride, place.ptr(out))
+    # (uint32 travels as its int32 bit pattern)
+    bridged = place.alloc((count, 2), np.uint32) if bridge_sites else None
+    place.uploads_done()
+
+    def call(*tail):
+        if bridge_sites == 0:
+            return place.fn("ibd_pairs")(*head, *pair, *tail)
+        return place.fn("ibd_pairs_bridged")(*head, bridge_sites, *pair, place.ptr(bridged),
+                                             *tail)
+
+    got = (out, *_segment_list(place, call, count, segments or max_segments is not None,
+                               max_segments))
+    return got if bridge_sites == 0 else got + (bridged,)
+
+
+def _ibd_segments(place, bits, words_per_sample, num_sites, pairs, group, pos, min_sites,
+                  min_length, segments, max_segments, num_records, bridge_sites) -> IBDPairs:
+    total = _place_genome_length(place, group, pos, num_sites)
+    rows, segs, found, *bridged = _ibd_segments_raw(
+        place, bits, words_per_sample, num_sites, pairs, group, pos, min_sites, min_length,
+        segments, max_segments, num_records, bridge_sites)
+    place.finish()
+    return IBDPairs(place.to_host(rows, IBD_PAIR_DTYPE), total,
+                    None if segs is None else place.to_host(segs, IBD_SEGMENT_DTYPE, found),
+                    int(min_sites), int(min_length), int(bridge_sites),
+                    *(place.to_host(b, np.uint32) for b in bridged))
 
 
 def ibd_segments_raw_host(bits: np.ndarray, words_per_sample: int, num_sites: int, pairs,
@@ -184,39 +228,10 @@ def ibd_segments_raw_host(bits: np.ndarray, words_per_sample: int, num_sites: in
     overflow raises ``ResourceExhaustedError`` whose ``num_segments`` is the exact count.
     With ``bridge_sites`` not 0 it is cuking_ibd_pairs_bridged_host and returns ``(rows,
     segments, bridged)``, ``bridged`` uint32 ``[P, 2]``."""
-    assert bits.dtype == np.uint64 and bits.flags.c_contiguous
-    words_per_sample = _count(words_per_sample, "words_per_sample")
-    num_sites = _count(num_sites, "num_sites")
-    min_sites, min_length = _thresholds(min_sites, min_length)
-    bridge_sites = _bridge(bridge_sites)
-    num_stored = bits.size // words_per_sample if words_per_sample else 0
-    group = _site_array(group, "group", num_sites, np.int32)
-    pos = _site_array(pos, "pos", num_sites, np.uint32)
-    owner, ptr, count, stride = _host_pairs(pairs, num_records)   # (owner keeps ptr alive)
-    out = np.zeros(count, dtype=IBD_PAIR_DTYPE)
-    bridged = np.zeros((count, 2), dtype=np.uint32)
-    pad = np.zeros(4, dtype=np.uint64)
-    found = C.c_uint64(0)
-    want = segments or max_segments is not None
-
-    def call(capacity):
-        segs = np.zeros(max(capacity, 1), dtype=IBD_SEGMENT_DTYPE)
-        head = ((bits if bits.size else pad).ctypes.data, num_stored, words_per_sample, num_sites,
-                None if group is None or not group.size else group.ctypes.data,
-                None if pos is None or not pos.size else pos.ctypes.data, min_sites, min_length)
-        pair = (ptr if count else None, count, stride, out.ctypes.data if count else None)
-        tail = (segs.ctypes.data if want and capacity else None, capacity if want else 0,
-                C.byref(found) if want else None)
-        if bridge_sites == 0:
-            status = _lib.load().cuking_ibd_pairs_host(*head, *pair, *tail)
-        else:
-            status = _lib.load().cuking_ibd_pairs_bridged_host(
-                *head, bridge_sites, *pair, bridged.ctypes.data if count else None, *tail)
-        return segs, status
-
-    segs = _segment_buffer(call, count, want, max_segments, found)
-    segs = segs[:found.value].copy() if want else None
-    return (out, segs) if bridge_sites == 0 else (out, segs, bridged)
+    rows, segs, _, *bridged = _ibd_segments_raw(
+        HOST, bits, words_per_sample, num_sites, pairs, group, pos, min_sites, min_length,
+        segments, max_segments, num_records, bridge_sites)
+    return (rows, segs, *bridged)
 
 
 def ibd_segments_host(bits: np.ndarray, words_per_sample: int, num_sites: int, pairs,
@@ -224,113 +239,44 @@ def ibd_segments_host(bits: np.ndarray, words_per_sample: int, num_sites: int, p
                       segments: bool = False, max_segments=None, num_records=None,
                       bridge_sites: int = 0) -> IBDPairs:
     """``KingContext.ibd_segments`` on host memory and the host twin: no GPU."""
-    rows, segs, *bridged = ibd_segments_raw_host(bits, words_per_sample, num_sites, pairs, group,
-                                                 pos, min_sites, min_length, segments,
-                                                 max_segments, num_records, bridge_sites)
-    return IBDPairs(rows, genome_length(group, pos, num_sites), segs, int(min_sites),
-                    int(min_length), int(bridge_sites), *bridged)
+    return _ibd_segments(HOST, bits, words_per_sample, num_sites, pairs, group, pos, min_sites,
+                         min_length, segments, max_segments, num_records, bridge_sites)
 
 
 def rows_to_host(rows) -> np.ndarray:
     """The ``[P, 10]`` int32 device tensor of ``ibd_segments_raw`` as ``IBD_PAIR_DTYPE`` rows on
     the host (waits for the copy)."""
-    return np.ascontiguousarray(rows.cpu().numpy()).view(IBD_PAIR_DTYPE).reshape(-1)
+    return tensor_to_host(rows, IBD_PAIR_DTYPE)
 
 
 def segments_to_host(segments, num_segments: int) -> np.ndarray:
     """The first ``num_segments`` rows of the ``[*, 4]`` int32 device tensor of
     ``ibd_segments_raw`` as ``IBD_SEGMENT_DTYPE`` rows on the host (waits for the copy)."""
-    return np.ascontiguousarray(segments[:num_segments].cpu().numpy()) \
-        .view(IBD_SEGMENT_DTYPE).reshape(-1)
+    return tensor_to_host(segments[:num_segments], IBD_SEGMENT_DTYPE)
 
 
 def bridged_to_host(bridged) -> np.ndarray:
     """The ``[P, 2]`` int32 device tensor of ``ibd_segments_raw`` as uint32 on the host (waits for
     the copy)."""
-    return np.ascontiguousarray(bridged.cpu().numpy()).view(np.uint32)
-
-
-def _device_sites(ctx, values, name: str, num_sites: int, dtype):
-    """None, or ``values`` (a host array, or an int32 device tensor of ``num_sites``) on the
-    device; uint32 travels as its int32 bit pattern."""
-    import torch
-    from .api import _device_tensor
-    if values is None:
-        return None
-    if isinstance(values, torch.Tensor):
-        return _device_tensor(ctx.device, values, name, torch.int32, shape=(num_sites,))
-    host = _site_array(values, name, num_sites, dtype)
-    return torch.from_numpy(host.view(np.int32)).to(f"cuda:{ctx.device}")
+    return tensor_to_host(bridged, np.uint32)
 
 
 def ibd_segments_raw_device(ctx, bits, words_per_sample: int, num_sites: int, pairs, group=None,
                             pos=None, min_sites: int = 512, min_length: int = 0,
                             segments: bool = False, max_segments=None, num_records=None,
                             out=None, stream=None, bridge_sites: int = 0):
-    import torch
-    from .api import _device_tensor, _stream_handle
-    words_per_sample = _count(words_per_sample, "words_per_sample")
-    num_sites = _count(num_sites, "num_sites")
-    min_sites, min_length = _thresholds(min_sites, min_length)
-    bridge_sites = _bridge(bridge_sites)
-    num_stored = ctx._rows_of(bits, words_per_sample)
-    dev = f"cuda:{ctx.device}"
-    d_group = _device_sites(ctx, group, "group", num_sites, np.int32)
-    d_pos = _device_sites(ctx, pos, "pos", num_sites, np.uint32)
-    owner, count, stride = _device_pairs(ctx, pairs, num_records)
-    if out is None:
-        out = torch.empty((count, 10), dtype=torch.int32, device=dev)
-    else:
-        _device_tensor(ctx.device, out, "out", torch.int32, shape=(count, 10))
-    bridged = None
-    if bridge_sites != 0:   # (uint32 travels as its int32 bit pattern)
-        bridged = torch.empty((count, 2), dtype=torch.int32, device=dev)
-    want = segments or max_segments is not None
-    found = C.c_uint64(0)
-    # (uploads ran on the current stream: `stream` waits for them)
-    if stream is not None:
-        stream.wait_stream(torch.cuda.current_stream())
-
-    def call(capacity):
-        segs = torch.empty((max(capacity, 1), 4), dtype=torch.int32, device=dev)
-        head = (ctx.handle, bits.data_ptr(), num_stored, words_per_sample, num_sites,
-                None if d_group is None or not num_sites else d_group.data_ptr(),
-                None if d_pos is None or not num_sites else d_pos.data_ptr(), min_sites,
-                min_length)
-        pair = (owner.data_ptr() if count else None, count, stride,
-                out.data_ptr() if count else None)
-        tail = (segs.data_ptr() if want and capacity else None, capacity if want else 0,
-                C.byref(found) if want else None, _stream_handle(stream))
-        if bridge_sites == 0:
-            return segs, ctx.lib.cuking_ibd_pairs(*head, *pair, *tail)
-        return segs, ctx.lib.cuking_ibd_pairs_bridged(
-            *head, bridge_sites, *pair, bridged.data_ptr() if count else None, *tail)
-
-    segs = _segment_buffer(call, count, want, max_segments, found)
-    if stream is not None:  # (converted copies are freed on return)
-        for t in (owner, d_group, d_pos, segs):
-            if t is not None:
-                t.record_stream(stream)
-    got = (out, (segs if want else None), int(found.value))
-    return got if bridge_sites == 0 else got + (bridged,)
+    return _ibd_segments_raw(DevicePlace(ctx, stream), bits, words_per_sample, num_sites, pairs,
+                             group, pos, min_sites, min_length, segments, max_segments,
+                             num_records, bridge_sites, out)
 
 
 def ibd_segments_device(ctx, bits, words_per_sample: int, num_sites: int, pairs, group=None,
                         pos=None, min_sites: int = 512, min_length: int = 0,
                         segments: bool = False, max_segments=None, num_records=None,
                         stream=None, bridge_sites: int = 0) -> IBDPairs:
-    import torch
-    host_group = group.cpu().numpy() if isinstance(group, torch.Tensor) else group
-    host_pos = pos.cpu().numpy().view(np.uint32) if isinstance(pos, torch.Tensor) else pos
-    total = genome_length(host_group, host_pos, num_sites)
-    rows, segs, found, *bridged = ibd_segments_raw_device(
-        ctx, bits, words_per_sample, num_sites, pairs, group, pos, min_sites, min_length, segments,
-        max_segments, num_records, stream=stream, bridge_sites=bridge_sites)
-    if stream is not None:
-        stream.synchronize()
-    return IBDPairs(rows_to_host(rows), total,
-                    None if segs is None else segments_to_host(segs, found), int(min_sites),
-                    int(min_length), int(bridge_sites), *map(bridged_to_host, bridged))
+    return _ibd_segments(DevicePlace(ctx, stream), bits, words_per_sample, num_sites, pairs,
+                         group, pos, min_sites, min_length, segments, max_segments, num_records,
+                         bridge_sites)
 
 
 # ---- the scan of a block: every pair, no list --------------------------------------------------
@@ -340,18 +286,40 @@ def sort_records(rows: np.ndarray) -> np.ndarray:
     return np.sort(rows, order=["sample_i", "sample_j"])
 
 
-def _min_total(min_total) -> int:
+def _ibd_scan_raw(place, bits, words_per_sample, num_sites, group, pos, min_sites, min_length,
+                  min_total, block, max_records, out=None):
+    head, num_stored, owners = _scan_head(place, bits, words_per_sample, num_sites, group, pos,
+                                          min_sites, min_length)
     min_total = int(min_total)
     if not 0 <= min_total < 1 << 64:
         raise ValueError(f"min_total must be in [0, 2^64), not {min_total}")
-    return min_total
+    block = _block(block, num_stored)
+    if out is not None:
+        place.out(out, "out", IBD_PAIR_DTYPE)
+        max_records = _out_capacity(out, max_records)
+    found = C.c_uint64(0)
+    place.uploads_done()
 
+    def call(capacity):
+        recs = out if out is not None else place.alloc(max(capacity, 1), IBD_PAIR_DTYPE)
+        return recs, place.fn("ibd_scan")(*head, C.byref(block.c), min_total,
+                                          place.ptr(recs) if capacity else None, capacity,
+                                          C.byref(found))
 
-def _record_buffer(call, block, max_records, found):
-    """The buffer rule (``_counted_buffer``) of the scan's records, with the default of
-    ``pcrelate_records``: 16 records per sample of the block."""
-    return _counted_buffer(call, _default_records(block), max_records, "max_records", found,
+    # (the buffer rule and the default of ``pcrelate_records``: 16 records per sample of the block)
+    recs = _counted_buffer(call, _default_records(block), max_records, "max_records", found,
                            "num_records")
+    place.keep(recs)
+    return place.trim(recs, found.value), int(found.value), block
+
+
+def _ibd_scan(place, bits, words_per_sample, num_sites, group, pos, min_sites, min_length,
+              min_total, block, max_records) -> IBDPairs:
+    total = _place_genome_length(place, group, pos, num_sites)
+    recs, count, block = _ibd_scan_raw(place, bits, words_per_sample, num_sites, group, pos,
+                                       min_sites, min_length, min_total, block, max_records)
+    return IBDPairs(sort_records(place.to_host(recs, IBD_PAIR_DTYPE, count)), total, None,
+                    int(min_sites), int(min_length), min_total=int(min_total), block=block)
 
 
 def ibd_scan_raw_host(bits: np.ndarray, words_per_sample: int, num_sites: int, group=None,
@@ -362,41 +330,16 @@ def ibd_scan_raw_host(bits: np.ndarray, words_per_sample: int, num_sites: int, g
     with a kind-1 segment and ``length1 >= min_total`` as ``IBD_PAIR_DTYPE`` rows in ascending
     ``(sample_i, sample_j)``, each the bytes ``ibd_segments_raw_host`` gives for that pair.  The
     buffer rule is ``pcrelate_records_raw_host``'s."""
-    assert bits.dtype == np.uint64 and bits.flags.c_contiguous
-    words_per_sample = _count(words_per_sample, "words_per_sample")
-    num_sites = _count(num_sites, "num_sites")
-    min_sites, min_length = _thresholds(min_sites, min_length)
-    min_total = _min_total(min_total)
-    num_stored = bits.size // words_per_sample if words_per_sample else 0
-    group = _site_array(group, "group", num_sites, np.int32)
-    pos = _site_array(pos, "pos", num_sites, np.uint32)
-    block = _block(block, num_stored)
-    pad = np.zeros(4, dtype=np.uint64)
-    found = C.c_uint64(0)
-
-    def call(capacity):
-        recs = np.zeros(max(capacity, 1), dtype=IBD_PAIR_DTYPE)
-        status = _lib.load().cuking_ibd_scan_host(
-            (bits if bits.size else pad).ctypes.data, num_stored, words_per_sample, num_sites,
-            None if group is None or not group.size else group.ctypes.data,
-            None if pos is None or not pos.size else pos.ctypes.data, min_sites, min_length,
-            C.byref(block.c), min_total, recs.ctypes.data if capacity else None, capacity,
-            C.byref(found))
-        return recs, status
-
-    recs = _record_buffer(call, block, max_records, found)
-    return recs[:found.value].copy(), int(found.value)
+    return _ibd_scan_raw(HOST, bits, words_per_sample, num_sites, group, pos, min_sites,
+                         min_length, min_total, block, max_records)[:2]
 
 
 def ibd_scan_host(bits: np.ndarray, words_per_sample: int, num_sites: int, group=None, pos=None,
                   min_sites: int = 512, min_length: int = 0, min_total: int = 0, block=None,
                   max_records=None) -> IBDPairs:
     """``KingContext.ibd_scan`` on host memory and the host twin: no GPU."""
-    recs, _ = ibd_scan_raw_host(bits, words_per_sample, num_sites, group, pos, min_sites,
-                                min_length, min_total, block, max_records)
-    num_stored = bits.size // words_per_sample if words_per_sample else 0
-    return IBDPairs(recs, genome_length(group, pos, num_sites), None, int(min_sites),
-                    int(min_length), min_total=int(min_total), block=_block(block, num_stored))
+    return _ibd_scan(HOST, bits, words_per_sample, num_sites, group, pos, min_sites, min_length,
+                     min_total, block, max_records)
 
 
 def records_to_host(records, num_records: int) -> np.ndarray:
@@ -408,54 +351,12 @@ def records_to_host(records, num_records: int) -> np.ndarray:
 def ibd_scan_raw_device(ctx, bits, words_per_sample: int, num_sites: int, group=None, pos=None,
                         min_sites: int = 512, min_length: int = 0, min_total: int = 0,
                         block=None, max_records=None, out=None, stream=None):
-    import torch
-    from .api import _device_tensor, _stream_handle
-    words_per_sample = _count(words_per_sample, "words_per_sample")
-    num_sites = _count(num_sites, "num_sites")
-    min_sites, min_length = _thresholds(min_sites, min_length)
-    min_total = _min_total(min_total)
-    num_stored = ctx._rows_of(bits, words_per_sample)
-    dev = f"cuda:{ctx.device}"
-    d_group = _device_sites(ctx, group, "group", num_sites, np.int32)
-    d_pos = _device_sites(ctx, pos, "pos", num_sites, np.uint32)
-    block = _block(block, num_stored)
-    if out is not None:
-        _device_tensor(ctx.device, out, "out", torch.int32, cols=10)
-        max_records = _out_capacity(out, max_records)
-    found = C.c_uint64(0)
-    # (uploads ran on the current stream: `stream` waits for them)
-    if stream is not None:
-        stream.wait_stream(torch.cuda.current_stream())
-
-    def call(capacity):
-        recs = out if out is not None else \
-            torch.empty((max(capacity, 1), 10), dtype=torch.int32, device=dev)
-        status = ctx.lib.cuking_ibd_scan(
-            ctx.handle, bits.data_ptr(), num_stored, words_per_sample, num_sites,
-            None if d_group is None or not num_sites else d_group.data_ptr(),
-            None if d_pos is None or not num_sites else d_pos.data_ptr(), min_sites, min_length,
-            C.byref(block.c), min_total, recs.data_ptr() if capacity else None, capacity,
-            C.byref(found), _stream_handle(stream))
-        return recs, status
-
-    recs = _record_buffer(call, block, max_records, found)
-    if stream is not None:  # (converted copies are freed on return)
-        for t in (d_group, d_pos, recs):
-            if t is not None:
-                t.record_stream(stream)
-    return recs, int(found.value)
+    return _ibd_scan_raw(DevicePlace(ctx, stream), bits, words_per_sample, num_sites, group, pos,
+                         min_sites, min_length, min_total, block, max_records, out)[:2]
 
 
 def ibd_scan_device(ctx, bits, words_per_sample: int, num_sites: int, group=None, pos=None,
                     min_sites: int = 512, min_length: int = 0, min_total: int = 0, block=None,
                     max_records=None, stream=None) -> IBDPairs:
-    import torch
-    host_group = group.cpu().numpy() if isinstance(group, torch.Tensor) else group
-    host_pos = pos.cpu().numpy().view(np.uint32) if isinstance(pos, torch.Tensor) else pos
-    total = genome_length(host_group, host_pos, num_sites)
-    recs, count = ibd_scan_raw_device(ctx, bits, words_per_sample, num_sites, group, pos,
-                                      min_sites, min_length, min_total, block, max_records,
-                                      stream=stream)
-    return IBDPairs(records_to_host(recs, count), total, None, int(min_sites), int(min_length),
-                    min_total=int(min_total),
-                    block=_block(block, ctx._rows_of(bits, words_per_sample)))
+    return _ibd_scan(DevicePlace(ctx, stream), bits, words_per_sample, num_sites, group, pos,
+                     min_sites, min_length, min_total, block, max_records)

@@ -14,8 +14,8 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from . import _lib
 from ._lib import check
+from ._place import HOST, DevicePlace, tensor_to_host
 from .api import _count
 from .pcrelate import PARENT_CHILD
 
@@ -163,162 +163,113 @@ def candidate_trios(pairs, relationship, related=None) -> np.ndarray:
     return np.array(found, dtype=np.uint32).reshape(-1, 3)
 
 
-# ---- the host twin --------------------------------------------------------------------------------
+# ---- the calls, over a place (the host twin and the device) ---------------------------------------
+def _mendel_errors_raw(place, bits, words_per_sample, num_sites, trios, error_bits, out=None):
+    words_per_sample = _count(words_per_sample, "words_per_sample")
+    num_sites = _count(num_sites, "num_sites")
+    num_stored = place.bits(bits, words_per_sample)
+    listed = place.index_list(trios, "trios", 3, _trio_list)
+    count = listed.shape[0]
+    out = place.alloc(count, MENDEL_TRIO_DTYPE) if out is None else \
+        place.out(out, "out", MENDEL_TRIO_DTYPE, count)
+    if error_bits is True:
+        error_bits = place.alloc((count, words_per_sample // 2), np.uint64)
+    elif error_bits is not None and error_bits is not False:
+        place.out(error_bits, "error_bits", np.uint64, (count, words_per_sample // 2))
+    else:
+        error_bits = None
+    place.uploads_done()
+    check(place.fn("mendel_trios")(place.ptr(bits, pad=True), num_stored, words_per_sample,
+                                   num_sites, place.ptr(listed), count, place.ptr(out),
+                                   place.ptr(error_bits)))
+    place.keep()
+    return out, error_bits
+
+
+def _site_counts(place, error_bits, counts):
+    place.words(error_bits, "error_bits")
+    if error_bits.ndim != 2:
+        raise ValueError(f"error_bits must be [T, W], not {tuple(error_bits.shape)}")
+    num_trios, plane = error_bits.shape
+    fresh = None
+    if counts is None:
+        counts = fresh = place.zeros(64 * plane, np.uint32)   # (zeroed on the current stream)
+    else:
+        place.out(counts, "counts", np.uint32, 64 * plane)
+    place.uploads_done()
+    check(place.fn("mendel_site_counts")(place.ptr(error_bits), num_trios if plane else 0,
+                                         max(plane, 1), place.ptr(counts)))
+    place.keep(fresh)
+    return counts
+
+
+def _mendel_errors(place, bits, words_per_sample, num_sites, trios, site_counts, chunk):
+    listed = place.index_list(_trio_list(place.host_sites(trios, np.uint32)), "trios", 3,
+                              _trio_list)
+    count = listed.shape[0]
+    rows = place.alloc(count, MENDEL_TRIO_DTYPE)
+    counts = None
+    if not site_counts:
+        _mendel_errors_raw(place, bits, words_per_sample, num_sites, listed, None, rows)
+    else:
+        plane = _count(words_per_sample, "words_per_sample") // 2
+        step = min(_chunk_rows(plane, chunk), max(count, 1))
+        # ONE mask buffer for every chunk: the calls of a stream run in order
+        mask = place.alloc((step, plane), np.uint64)
+        counts = place.zeros(64 * plane, np.uint32)
+        for lo in range(0, count, step):
+            n = min(step, count - lo)
+            _mendel_errors_raw(place, bits, words_per_sample, num_sites, listed[lo:lo + n],
+                               mask[:n], rows[lo:lo + n])
+            _site_counts(place, mask[:n], counts)
+        place.keep(mask, counts)
+    place.keep(rows)
+    place.finish()
+    host_rows = place.to_host(rows, MENDEL_TRIO_DTYPE)
+    if counts is None:
+        return MendelErrors(host_rows)
+    return MendelErrors(host_rows, place.to_host(counts, np.uint32)[:num_sites].copy())
+
+
 def mendel_errors_raw_host(bits: np.ndarray, words_per_sample: int, num_sites: int, trios,
                            error_bits: bool = False):
     """cuking_mendel_trios_host, the bare call: ``(rows, error_bits)`` -- one
     ``MENDEL_TRIO_DTYPE`` row per entry of ``trios`` (an integer ``[T, 3]`` array) and, with
     ``error_bits``, the uint64 ``[T, words_per_sample / 2]`` error mask, else None.  Bit for bit
     what ``KingContext.mendel_errors_raw`` gives."""
-    assert bits.dtype == np.uint64 and bits.flags.c_contiguous
-    words_per_sample = _count(words_per_sample, "words_per_sample")
-    num_sites = _count(num_sites, "num_sites")
-    num_stored = bits.size // words_per_sample if words_per_sample else 0
-    listed = _trio_list(trios)
-    count = len(listed)
-    out = np.zeros(count, dtype=MENDEL_TRIO_DTYPE)
-    mask = np.zeros((count, words_per_sample // 2), dtype=np.uint64) if error_bits else None
-    pad = np.zeros(4, dtype=np.uint64)
-    check(_lib.load().cuking_mendel_trios_host(
-        (bits if bits.size else pad).ctypes.data, num_stored, words_per_sample, num_sites,
-        listed.ctypes.data if count else None, count, out.ctypes.data if count else None,
-        mask.ctypes.data if error_bits and mask.size else None))
-    return out, mask
+    return _mendel_errors_raw(HOST, bits, words_per_sample, num_sites, trios, bool(error_bits))
 
 
 def site_counts_host(error_bits: np.ndarray, counts=None) -> np.ndarray:
     """cuking_mendel_site_counts_host: ADDS the column sums of the uint64 ``[T, W]`` mask to
     ``counts`` (uint32 ``[64 W]``; default: zeros) and returns it."""
-    assert error_bits.dtype == np.uint64 and error_bits.ndim == 2 and \
-        error_bits.flags.c_contiguous
-    num_trios, plane = error_bits.shape
-    if counts is None:
-        counts = np.zeros(64 * plane, dtype=np.uint32)
-    assert counts.dtype == np.uint32 and counts.shape == (64 * plane,) and \
-        counts.flags.c_contiguous
-    check(_lib.load().cuking_mendel_site_counts_host(
-        error_bits.ctypes.data if error_bits.size else None, num_trios if plane else 0,
-        max(plane, 1), counts.ctypes.data if counts.size else None))
-    return counts
+    return _site_counts(HOST, error_bits, counts)
 
 
 def mendel_errors_host(bits: np.ndarray, words_per_sample: int, num_sites: int, trios,
                        site_counts: bool = False, _chunk_trios=None) -> MendelErrors:
     """``KingContext.mendel_errors`` on host memory and the host twin: no GPU."""
-    listed = _trio_list(trios)
-    if not site_counts:
-        return MendelErrors(mendel_errors_raw_host(bits, words_per_sample, num_sites, listed)[0])
-    plane = _count(words_per_sample, "words_per_sample") // 2
-    step = _chunk_rows(plane, _chunk_trios)
-    rows = np.zeros(len(listed), dtype=MENDEL_TRIO_DTYPE)
-    counts = np.zeros(64 * plane, dtype=np.uint32)
-    for lo in range(0, len(listed), step):
-        rows[lo:lo + step], mask = mendel_errors_raw_host(bits, words_per_sample, num_sites,
-                                                          listed[lo:lo + step], error_bits=True)
-        site_counts_host(mask, counts)
-    return MendelErrors(rows, counts[:num_sites].copy())
+    return _mendel_errors(HOST, bits, words_per_sample, num_sites, trios, site_counts,
+                          _chunk_trios)
 
 
-# ---- the device -----------------------------------------------------------------------------------
 def rows_to_host(rows) -> np.ndarray:
     """The ``[T, 12]`` int32 device tensor of ``mendel_errors_raw`` as ``MENDEL_TRIO_DTYPE`` rows
     on the host (waits for the copy)."""
-    return np.ascontiguousarray(rows.cpu().numpy()).view(MENDEL_TRIO_DTYPE).reshape(-1)
+    return tensor_to_host(rows, MENDEL_TRIO_DTYPE)
 
 
 def mendel_errors_raw_device(ctx, bits, words_per_sample: int, num_sites: int, trios,
                              error_bits=None, out=None, stream=None):
-    import torch
-    from .api import _device_tensor, _stream_handle
-    words_per_sample = _count(words_per_sample, "words_per_sample")
-    num_sites = _count(num_sites, "num_sites")
-    num_stored = ctx._rows_of(bits, words_per_sample)
-    dev = f"cuda:{ctx.device}"
-    uploaded = None
-    if isinstance(trios, torch.Tensor):   # (uint32 travels as its int32 bit pattern)
-        d_trios = _device_tensor(ctx.device, trios, "trios", torch.int32, cols=3)
-    else:
-        uploaded = d_trios = torch.from_numpy(_trio_list(trios).view(np.int32)).to(dev)
-    count = d_trios.shape[0]
-    if out is None:
-        out = torch.empty((count, 12), dtype=torch.int32, device=dev)
-    else:
-        _device_tensor(ctx.device, out, "out", torch.int32, shape=(count, 12))
-    if error_bits is True:
-        error_bits = torch.empty((count, words_per_sample // 2), dtype=torch.int64, device=dev)
-    elif error_bits is not None and error_bits is not False:
-        _device_tensor(ctx.device, error_bits, "error_bits", torch.int64,
-                       shape=(count, words_per_sample // 2))
-    else:
-        error_bits = None
-    # (the upload ran on the current stream: `stream` waits for it)
-    if stream is not None:
-        stream.wait_stream(torch.cuda.current_stream())
-    check(ctx.lib.cuking_mendel_trios(
-        ctx.handle, bits.data_ptr(), num_stored, words_per_sample, num_sites,
-        d_trios.data_ptr() if count else None, count, out.data_ptr() if count else None,
-        error_bits.data_ptr() if error_bits is not None and error_bits.numel() else None,
-        _stream_handle(stream)))
-    if stream is not None and uploaded is not None:   # (the converted copy is freed on return)
-        uploaded.record_stream(stream)
-    return out, error_bits
+    return _mendel_errors_raw(DevicePlace(ctx, stream), bits, words_per_sample, num_sites, trios,
+                              error_bits, out)
 
 
 def site_counts_device(ctx, error_bits, counts=None, stream=None):
-    import torch
-    from .api import _device_tensor, _stream_handle
-    _device_tensor(ctx.device, error_bits, "error_bits", torch.int64)
-    if error_bits.dim() != 2 or error_bits.shape[1] == 0:
-        raise ValueError(f"error_bits must be a [T, W] tensor with W > 0, not "
-                         f"{tuple(error_bits.shape)}")
-    num_trios, plane = error_bits.shape
-    if counts is None:
-        counts = torch.zeros(64 * plane, dtype=torch.int32, device=f"cuda:{ctx.device}")
-        if stream is not None:   # (zeroed on the current stream)
-            stream.wait_stream(torch.cuda.current_stream())
-            counts.record_stream(stream)
-    else:
-        _device_tensor(ctx.device, counts, "counts", torch.int32, shape=(64 * plane,))
-    check(ctx.lib.cuking_mendel_site_counts(
-        ctx.handle, error_bits.data_ptr() if num_trios else None, num_trios, plane,
-        counts.data_ptr(), _stream_handle(stream)))
-    return counts
+    return _site_counts(DevicePlace(ctx, stream), error_bits, counts)
 
 
 def mendel_errors_device(ctx, bits, words_per_sample: int, num_sites: int, trios,
                          site_counts: bool = False, stream=None, _chunk_trios=None):
-    import torch
-    listed = _trio_list(trios.cpu().numpy().view(np.uint32)
-                        if isinstance(trios, torch.Tensor) else trios)
-    count = len(listed)
-    dev = f"cuda:{ctx.device}"
-    d_trios = torch.from_numpy(listed.view(np.int32)).to(dev)
-    rows = torch.empty((count, 12), dtype=torch.int32, device=dev)
-    counts = None
-    if not site_counts:
-        mendel_errors_raw_device(ctx, bits, words_per_sample, num_sites, d_trios, out=rows,
-                                 stream=stream)
-    else:
-        plane = _count(words_per_sample, "words_per_sample") // 2
-        step = min(_chunk_rows(plane, _chunk_trios), max(count, 1))
-        # ONE mask buffer for every chunk: the calls of a stream run in order
-        mask = torch.empty((step, plane), dtype=torch.int64, device=dev)
-        counts = torch.zeros(64 * plane, dtype=torch.int32, device=dev)
-        if stream is not None:
-            stream.wait_stream(torch.cuda.current_stream())
-        for lo in range(0, count, step):
-            n = min(step, count - lo)
-            mendel_errors_raw_device(ctx, bits, words_per_sample, num_sites, d_trios[lo:lo + n],
-                                     error_bits=mask[:n], out=rows[lo:lo + n], stream=stream)
-            site_counts_device(ctx, mask[:n], counts, stream)
-        if stream is not None:
-            mask.record_stream(stream)
-            counts.record_stream(stream)
-    if stream is not None:
-        d_trios.record_stream(stream)
-        rows.record_stream(stream)
-        stream.synchronize()
-    host_rows = rows_to_host(rows)
-    if counts is None:
-        return MendelErrors(host_rows)
-    return MendelErrors(host_rows, counts.cpu().numpy().view(np.uint32)[:num_sites].copy())
+    return _mendel_errors(DevicePlace(ctx, stream), bits, words_per_sample, num_sites, trios,
+                          site_counts, _chunk_trios)

@@ -31,8 +31,9 @@ import numpy as np
 
 from . import _lib
 from ._lib import check
+from ._place import HOST, DevicePlace, tensor_to_host
 from .api import (KING_CUTOFFS, KING_RESULT_DTYPE, Submatrix, _count, _counted_buffer,
-                  _geno_host_matrix, _out_capacity, geno_matmul_host)
+                  _out_capacity, geno_matmul_host)
 from .pca import DeviceOperator, HostOperator
 
 COLUMNS_MAX = _lib.PCRELATE_COLUMNS_MAX
@@ -147,6 +148,57 @@ def _block(block, num_stored: int) -> Submatrix:
     return block
 
 
+def _model_head(place, bits, words_per_sample, num_sites, x, beta):
+    """What the argument list of every PC-Relate call begins with, up to ``d``, as ``(head,
+    num_stored)``: the bitset, ``x`` float32 ``[num_stored, d]`` and ``beta`` float32 ``[>=
+    num_sites, d]`` with their leading dimensions."""
+    words_per_sample = _count(words_per_sample, "words_per_sample")
+    num_sites = _count(num_sites, "num_sites")
+    num_stored = place.bits(bits, words_per_sample)
+    x, ldx = place.matrix(x, "x", num_stored)
+    d = x.shape[1]
+    beta, ldb = place.matrix(beta, "beta", num_sites, d)
+    return (place.ptr(bits, pad=True), num_stored, words_per_sample, num_sites,
+            place.ptr(x, pad=True), ldx, place.ptr(beta, pad=True), ldb, d), num_stored
+
+
+def _fit_model(place, bits, words_per_sample, num_sites, scores, model, fit, what: str):
+    """``(x, beta, used, fit)`` of ``model``, or fitted on ``scores`` and ``fit``."""
+    if (scores is None) == (model is None):
+        raise ValueError(f"pcrelate {what}: give either scores or model")
+    if model is not None:
+        return _model_of(model)
+    op = place.isaf_operator(bits, words_per_sample, num_sites, fit)
+    return (*isaf_fit(op, scores), op.fit)
+
+
+def _pcrelate_matrix(place, bits, words_per_sample, num_sites, x, beta, lo, hi, block, out):
+    head, num_stored = _model_head(place, bits, words_per_sample, num_sites, x, beta)
+    block = _block(block, num_stored)
+    rows, cols = block.i_end - block.i_begin, block.j_end - block.j_begin
+    if out is None:
+        out = place.alloc((max(rows, 0), max(cols, 0)), np.float32)
+    out, ldo = place.matrix(out, "out", rows, cols)
+    check(place.fn("pcrelate_matrix")(*head, lo, hi, C.byref(block.c), place.ptr(out, pad=True),
+                                      ldo))
+    return out
+
+
+def _pcrelate(place, bits, words_per_sample, num_sites, scores, fit, min_maf, block, out):
+    lo, hi = _bounds(min_maf)
+    op = place.isaf_operator(bits, _count(words_per_sample, "words_per_sample"),
+                             _count(num_sites, "num_sites"), fit)
+    x, beta, used = isaf_fit(op, scores)
+    block = _block(block, op.bits.shape[0])
+    # (the fit ran on the current stream: `stream` waits for it and for the two copies, which
+    # are freed when this returns)
+    there = place.from_host(x), place.from_host(beta)
+    place.uploads_done()
+    kin = _pcrelate_matrix(place, bits, words_per_sample, num_sites, *there, lo, hi, block, out)
+    place.keep()
+    return PCRelateResult(kin, beta, used, op.fit, x, block)
+
+
 def pcrelate_matrix_host(bits: np.ndarray, words_per_sample: int, num_sites: int, x, beta,
                          lo: float, hi: float, block=None, out=None) -> np.ndarray:
     """cuking_pcrelate_matrix_host: the kinship of every pair of ``block`` (a ``Submatrix`` or
@@ -155,87 +207,25 @@ def pcrelate_matrix_host(bits: np.ndarray, words_per_sample: int, num_sites: int
     double, rounded once, divided in float32: the specification of
     ``KingContext.pcrelate_matrix`` in executable form.  ``out``: float32 ``[rows, cols]`` to
     write into (may be a column slice of a wider array)."""
-    assert bits.dtype == np.uint64 and bits.flags.c_contiguous
-    words_per_sample = _count(words_per_sample, "words_per_sample")
-    num_sites = _count(num_sites, "num_sites")
-    num_stored = bits.size // words_per_sample if words_per_sample else 0
-    x = _geno_host_matrix(x, "x", num_stored)
-    beta = _geno_host_matrix(beta, "beta", num_sites, x.shape[1])
-    block = _block(block, num_stored)
-    rows, cols = block.i_end - block.i_begin, block.j_end - block.j_begin
-    if out is None:
-        out = np.empty((max(rows, 0), max(cols, 0)), dtype=np.float32)
-    else:
-        _geno_host_matrix(out, "out", rows, cols)
-    d = x.shape[1]
-    pad = np.zeros(4, dtype=np.float32)
-    check(_lib.load().cuking_pcrelate_matrix_host(
-        (bits if bits.size else pad).ctypes.data, num_stored, words_per_sample, num_sites,
-        (x if x.size else pad).ctypes.data, max(x.strides[0] // 4, d),
-        (beta if beta.size else pad).ctypes.data, max(beta.strides[0] // 4, d), d, lo, hi,
-        C.byref(block.c), (out if out.size else pad).ctypes.data,
-        max(out.strides[0] // 4, cols)))
-    return out
+    return _pcrelate_matrix(HOST, bits, words_per_sample, num_sites, x, beta, lo, hi, block, out)
 
 
 def pcrelate_host(bits: np.ndarray, words_per_sample: int, num_sites: int, scores, fit=None,
                   min_maf: float = 0.01, block=None, out=None) -> PCRelateResult:
     """``KingContext.pcrelate`` on host memory and the host twins: no GPU."""
-    lo, hi = _bounds(min_maf)
-    op = HostIsafOperator(bits, _count(words_per_sample, "words_per_sample"),
-                          _count(num_sites, "num_sites"), fit)
-    x, beta, used = isaf_fit(op, scores)
-    block = _block(block, op.bits.shape[0])
-    kin = pcrelate_matrix_host(bits, words_per_sample, num_sites, x, beta, lo, hi, block, out)
-    return PCRelateResult(kin, beta, used, op.fit, x, block)
+    return _pcrelate(HOST, bits, words_per_sample, num_sites, scores, fit, min_maf, block, out)
 
 
 def pcrelate_matrix_device(ctx, bits, words_per_sample: int, num_sites: int, x, beta, lo: float,
                            hi: float, block=None, out=None, stream=None):
-    import torch
-    from .api import _device_tensor, _stream_handle
-    num_stored = ctx._rows_of(bits, words_per_sample)
-    num_sites = _count(num_sites, "num_sites")
-    x = ctx._geno_matrix(x, "x", num_stored)
-    d = x.shape[1]
-    beta = ctx._geno_matrix(beta, "beta", num_sites, d)
-    block = _block(block, num_stored)
-    rows, cols = block.i_end - block.i_begin, block.j_end - block.j_begin
-    if out is None:
-        out = torch.empty((max(rows, 0), max(cols, 0)), dtype=torch.float32,
-                          device=f"cuda:{ctx.device}")
-    else:
-        _device_tensor(ctx.device, out, "out", torch.float32, shape=(rows, cols),
-                       contiguous=False)
-        if rows > 1 and cols > 0 and out.stride(0) < cols or cols > 1 and out.stride(1) != 1:
-            raise ValueError("out must have unit column stride and a row stride of at least "
-                             "the block's columns")
-    ldo = out.stride(0) if rows > 1 else max(out.stride(0), cols)
-    check(ctx.lib.cuking_pcrelate_matrix(
-        ctx.handle, bits.data_ptr(), num_stored, words_per_sample, num_sites, x.data_ptr(),
-        max(x.stride(0), d), beta.data_ptr(), max(beta.stride(0), d), d, lo, hi,
-        C.byref(block.c), out.data_ptr(), ldo, _stream_handle(stream)))
-    return out
+    return _pcrelate_matrix(DevicePlace(ctx, stream), bits, words_per_sample, num_sites, x, beta,
+                            lo, hi, block, out)
 
 
 def pcrelate_device(ctx, bits, words_per_sample: int, num_sites: int, scores, fit=None,
                     min_maf: float = 0.01, block=None, out=None, stream=None) -> PCRelateResult:
-    import torch
-    lo, hi = _bounds(min_maf)
-    op = DeviceIsafOperator(ctx, bits, _count(words_per_sample, "words_per_sample"),
-                            _count(num_sites, "num_sites"), fit)
-    x, beta, used = isaf_fit(op, scores)
-    block = _block(block, op.bits.shape[0])
-    # (the fit ran on the current stream: `stream` waits for it and for the two copies)
-    d_x, d_beta = op.from_host(x), op.from_host(beta)
-    if stream is not None:
-        stream.wait_stream(torch.cuda.current_stream())
-    kin = pcrelate_matrix_device(ctx, bits, words_per_sample, num_sites, d_x, d_beta, lo, hi,
-                                 block, out, stream)
-    if stream is not None:  # (d_x and d_beta are freed when this returns)
-        d_x.record_stream(stream)
-        d_beta.record_stream(stream)
-    return PCRelateResult(kin, beta, used, op.fit, x, block)
+    return _pcrelate(DevicePlace(ctx, stream), bits, words_per_sample, num_sites, scores, fit,
+                     min_maf, block, out)
 
 
 # ---- listed pairs ------------------------------------------------------------------------------
@@ -285,38 +275,6 @@ class PCRelatePairs:
         return code
 
 
-def _host_pairs(pairs, num_records=None):
-    """(array that owns the memory, pointer, count, stride in bytes) of a host pair list:
-    ``KING_RESULT_DTYPE`` records or ``[*, 6]`` int32 / uint32 (the first ``num_records``;
-    stride 24), or an integer ``[P, 2]`` array (stride 8)."""
-    pairs = np.asarray(pairs)
-    if pairs.dtype == KING_RESULT_DTYPE and pairs.ndim == 1 or \
-            pairs.ndim == 2 and pairs.shape[1] == 6 and pairs.dtype in (np.int32, np.uint32):
-        recs = np.ascontiguousarray(pairs)
-        count = recs.shape[0] if num_records is None else _count(num_records, "num_records")
-        if count > recs.shape[0]:
-            raise ValueError(f"pairs holds {recs.shape[0]} records, num_records is {count}")
-        return recs, recs.ctypes.data, count, 24
-    if num_records is not None:
-        raise ValueError("num_records goes with a record buffer, not with a [P, 2] array")
-    if pairs.ndim != 2 or pairs.shape[1] != 2 or pairs.dtype.kind not in "iu":
-        raise ValueError("pairs must be KING_RESULT_DTYPE records, [*, 6] int32 / uint32 records "
-                         f"or an integer [P, 2] array, not {pairs.dtype} {pairs.shape}")
-    if pairs.size and (int(pairs.min()) < 0 or int(pairs.max()) > 0xFFFFFFFF):
-        raise ValueError("pairs must hold sample indices in [0, 2^32)")
-    flat = np.ascontiguousarray(pairs, dtype=np.uint32)
-    return flat, flat.ctypes.data, flat.shape[0], 8
-
-
-def _pair_indices(owner, count: int, stride: int) -> np.ndarray:
-    """uint32 ``[count, 2]`` of what ``_host_pairs`` returned."""
-    if stride == 8:
-        return owner[:count]
-    if owner.dtype == KING_RESULT_DTYPE:
-        return np.stack([owner["sample_i"][:count], owner["sample_j"][:count]], axis=1)
-    return owner[:count, :2].view(np.uint32) if owner.dtype == np.int32 else owner[:count, :2]
-
-
 def _check_pair_range(indices, num_stored: int):
     if indices.size and int(indices.max()) >= num_stored:
         bad = int(np.argmax((indices >= num_stored).any(axis=1)))
@@ -324,13 +282,20 @@ def _check_pair_range(indices, num_stored: int):
                          f"{int(indices[bad, 1])}) is outside the {num_stored} stored samples")
 
 
-def _host_inbreeding(f, num_stored: int):
-    if f is None:
-        return None
-    f = np.ascontiguousarray(f)
-    if f.dtype != np.float32 or f.shape != (num_stored,):
-        raise ValueError(f"inbreeding must be float32 [{num_stored}], not {f.dtype} {f.shape}")
-    return f
+def _pcrelate_pairs_raw(place, bits, words_per_sample, num_sites, x, beta, lo, hi, pairs, f,
+                        num_records, out=None):
+    head, num_stored = _model_head(place, bits, words_per_sample, num_sites, x, beta)
+    if f is not None:
+        f = place.vector(f, "inbreeding", np.float32, num_stored)
+    owner, count, stride = place.pairs(pairs, num_records)
+    out = place.alloc(count, PCRELATE_PAIR_DTYPE) if out is None else \
+        place.out(out, "out", PCRELATE_PAIR_DTYPE, count)
+    place.uploads_done()
+    check(place.fn("pcrelate_pairs")(*head, lo, hi, place.ptr(f, pad=True),
+                                     place.ptr(owner) if count else None, count, stride,
+                                     place.ptr(out)))
+    place.keep()
+    return out
 
 
 def pcrelate_pairs_raw_host(bits: np.ndarray, words_per_sample: int, num_sites: int, x, beta,
@@ -341,24 +306,8 @@ def pcrelate_pairs_raw_host(bits: np.ndarray, words_per_sample: int, num_sites: 
     float32 ``[num_stored]`` (None = all zero).  The same float32 chains as the kernel: bit for
     bit what ``KingContext.pcrelate_pairs_raw`` gives.  An index outside the stored samples is
     not an error here: its row holds NaN."""
-    assert bits.dtype == np.uint64 and bits.flags.c_contiguous
-    words_per_sample = _count(words_per_sample, "words_per_sample")
-    num_sites = _count(num_sites, "num_sites")
-    num_stored = bits.size // words_per_sample if words_per_sample else 0
-    x = _geno_host_matrix(x, "x", num_stored)
-    beta = _geno_host_matrix(beta, "beta", num_sites, x.shape[1])
-    f = _host_inbreeding(f, num_stored)
-    owner, ptr, count, stride = _host_pairs(pairs, num_records)
-    out = np.empty(count, dtype=PCRELATE_PAIR_DTYPE)
-    d = x.shape[1]
-    pad = np.zeros(4, dtype=np.float32)
-    check(_lib.load().cuking_pcrelate_pairs_host(
-        (bits if bits.size else pad).ctypes.data, num_stored, words_per_sample, num_sites,
-        (x if x.size else pad).ctypes.data, max(x.strides[0] // 4, d),
-        (beta if beta.size else pad).ctypes.data, max(beta.strides[0] // 4, d), d, lo, hi,
-        None if f is None else (f if f.size else pad).ctypes.data, ptr if count else None, count,
-        stride, out.ctypes.data if count else None))
-    return out
+    return _pcrelate_pairs_raw(HOST, bits, words_per_sample, num_sites, x, beta, lo, hi, pairs, f,
+                               num_records)
 
 
 def _self_pairs(num_stored: int) -> np.ndarray:
@@ -379,138 +328,55 @@ def _model_of(model):
     return model.x, model.beta, model.sites_used, model.fit
 
 
+def _pcrelate_pairs(place, bits, words_per_sample, num_sites, pairs, scores, model, fit, min_maf,
+                    inbreeding, num_records) -> PCRelatePairs:
+    lo, hi = _bounds(min_maf)
+    words_per_sample = _count(words_per_sample, "words_per_sample")
+    num_sites = _count(num_sites, "num_sites")
+    x, beta, used, fit_mask = _fit_model(place, bits, words_per_sample, num_sites, scores, model,
+                                         fit, "pairs")
+    num_stored = place.bits(bits, words_per_sample)
+    owner, count, stride = place.pairs(pairs, num_records)
+    _check_pair_range(place.pair_indices(owner, count, stride, num_stored), num_stored)
+    args = (place, bits, words_per_sample, num_sites, place.from_host(x), place.from_host(beta),
+            lo, hi)
+    if inbreeding is None:
+        selfs = _pcrelate_pairs_raw(*args, _self_pairs(num_stored), None, None)
+        place.finish()
+        f = _inbreeding_of(place.to_host(selfs, PCRELATE_PAIR_DTYPE))
+    else:
+        f = HOST.vector(inbreeding, "inbreeding", np.float32, num_stored)
+    rows = _pcrelate_pairs_raw(*args, owner, place.from_host(f), count if stride == 24 else None)
+    place.finish()
+    return PCRelatePairs(place.to_host(rows, PCRELATE_PAIR_DTYPE), f, beta, used, fit_mask, x)
+
+
 def pcrelate_pairs_host(bits: np.ndarray, words_per_sample: int, num_sites: int, pairs,
                         scores=None, model=None, fit=None, min_maf: float = 0.01,
                         inbreeding=None, num_records=None) -> PCRelatePairs:
     """``KingContext.pcrelate_pairs`` on host memory and the host twins: no GPU."""
-    lo, hi = _bounds(min_maf)
-    words_per_sample = _count(words_per_sample, "words_per_sample")
-    num_sites = _count(num_sites, "num_sites")
-    if (scores is None) == (model is None):
-        raise ValueError("pcrelate pairs: give either scores or model")
-    if model is not None:
-        x, beta, used, fit_mask = _model_of(model)
-    else:
-        op = HostIsafOperator(bits, words_per_sample, num_sites, fit)
-        x, beta, used = isaf_fit(op, scores)
-        fit_mask = op.fit
-    num_stored = bits.size // words_per_sample if words_per_sample else 0
-    owner, _, count, stride = _host_pairs(pairs, num_records)
-    _check_pair_range(_pair_indices(owner, count, stride), num_stored)
-    if inbreeding is None:
-        f = _inbreeding_of(pcrelate_pairs_raw_host(bits, words_per_sample, num_sites, x, beta,
-                                                   lo, hi, _self_pairs(num_stored)))
-    else:
-        f = _host_inbreeding(inbreeding, num_stored)
-    rows = pcrelate_pairs_raw_host(bits, words_per_sample, num_sites, x, beta, lo, hi, owner, f,
-                                   count if stride == 24 else None)
-    return PCRelatePairs(rows, f, beta, used, fit_mask, x)
+    return _pcrelate_pairs(HOST, bits, words_per_sample, num_sites, pairs, scores, model, fit,
+                           min_maf, inbreeding, num_records)
 
 
 def pairs_to_host(rows) -> np.ndarray:
     """The ``[P, 8]`` int32 device tensor of ``pcrelate_pairs_raw`` as ``PCRELATE_PAIR_DTYPE``
     rows on the host (waits for the copy)."""
-    return np.ascontiguousarray(rows.cpu().numpy()).view(PCRELATE_PAIR_DTYPE).reshape(-1)
-
-
-def _device_pairs(ctx, pairs, num_records=None):
-    """(tensor that owns the memory, count, stride in bytes) of a pair list on the device: an
-    int32 ``[*, 6]`` record tensor (the first ``num_records``), an int32 / int64 ``[P, 2]``
-    tensor, or one of the host forms of ``_host_pairs``, uploaded."""
-    import torch
-    dev = f"cuda:{ctx.device}"
-    if not isinstance(pairs, torch.Tensor):
-        owner, _, count, stride = _host_pairs(pairs, num_records)
-        flat = np.ascontiguousarray(owner).view(np.int32).reshape(owner.shape[0], stride // 4)
-        return torch.from_numpy(flat).to(dev), count, stride
-    if not pairs.is_cuda or pairs.device.index != ctx.device:
-        raise ValueError("pairs must live on this context's GPU")
-    if pairs.dim() == 2 and pairs.shape[1] == 6 and pairs.dtype == torch.int32:
-        count = pairs.shape[0] if num_records is None else _count(num_records, "num_records")
-        if count > pairs.shape[0]:
-            raise ValueError(f"pairs holds {pairs.shape[0]} records, num_records is {count}")
-        return pairs.contiguous(), count, 24
-    if num_records is not None:
-        raise ValueError("num_records goes with a record buffer, not with a [P, 2] tensor")
-    if pairs.dim() != 2 or pairs.shape[1] != 2 or pairs.dtype not in (torch.int32, torch.int64):
-        raise ValueError("pairs must be an int32 [*, 6] record tensor or an int32 / int64 "
-                         f"[P, 2] tensor, not {pairs.dtype} {tuple(pairs.shape)}")
-    if pairs.dtype == torch.int64:
-        if pairs.numel() and (int(pairs.min()) < 0 or int(pairs.max()) > 0xFFFFFFFF):
-            raise ValueError("pairs must hold sample indices in [0, 2^32)")
-        pairs = pairs.to(torch.int32)   # (wraps: the low 32 bits are the uint32)
-    return pairs.contiguous(), pairs.shape[0], 8
+    return tensor_to_host(rows, PCRELATE_PAIR_DTYPE)
 
 
 def pcrelate_pairs_raw_device(ctx, bits, words_per_sample: int, num_sites: int, x, beta,
                               lo: float, hi: float, pairs, f=None, num_records=None, out=None,
                               stream=None):
-    import torch
-    from .api import _device_tensor, _stream_handle
-    num_stored = ctx._rows_of(bits, words_per_sample)
-    num_sites = _count(num_sites, "num_sites")
-    x = ctx._geno_matrix(x, "x", num_stored)
-    d = x.shape[1]
-    beta = ctx._geno_matrix(beta, "beta", num_sites, d)
-    if f is not None:
-        _device_tensor(ctx.device, f, "f", torch.float32, shape=(num_stored,))
-    owner, count, stride = _device_pairs(ctx, pairs, num_records)
-    if out is None:
-        out = torch.empty((count, 8), dtype=torch.int32, device=f"cuda:{ctx.device}")
-    else:
-        _device_tensor(ctx.device, out, "out", torch.int32, shape=(count, 8))
-    check(ctx.lib.cuking_pcrelate_pairs(
-        ctx.handle, bits.data_ptr(), num_stored, words_per_sample, num_sites, x.data_ptr(),
-        max(x.stride(0), d), beta.data_ptr(), max(beta.stride(0), d), d, lo, hi,
-        None if f is None else f.data_ptr(), owner.data_ptr() if count else None, count, stride,
-        out.data_ptr() if count else None, _stream_handle(stream)))
-    if stream is not None and owner is not pairs:  # (a converted copy is freed on return)
-        owner.record_stream(stream)
-    return out
+    return _pcrelate_pairs_raw(DevicePlace(ctx, stream), bits, words_per_sample, num_sites, x,
+                               beta, lo, hi, pairs, f, num_records, out)
 
 
 def pcrelate_pairs_device(ctx, bits, words_per_sample: int, num_sites: int, pairs, scores=None,
                           model=None, fit=None, min_maf: float = 0.01, inbreeding=None,
                           num_records=None, stream=None) -> PCRelatePairs:
-    import torch
-    lo, hi = _bounds(min_maf)
-    words_per_sample = _count(words_per_sample, "words_per_sample")
-    num_sites = _count(num_sites, "num_sites")
-    if (scores is None) == (model is None):
-        raise ValueError("pcrelate pairs: give either scores or model")
-    num_stored = ctx._rows_of(bits, words_per_sample)
-    dev = f"cuda:{ctx.device}"
-    if model is not None:
-        x, beta, used, fit_mask = _model_of(model)
-    else:
-        op = DeviceIsafOperator(ctx, bits, words_per_sample, num_sites, fit)
-        x, beta, used = isaf_fit(op, scores)
-        fit_mask = op.fit
-    owner, count, stride = _device_pairs(ctx, pairs, num_records)
-    index = owner[:count, :2]
-    if count and bool(((index < 0) | (index >= num_stored)).any()):   # (int32: < 0 is >= 2^31)
-        _check_pair_range(index.cpu().numpy().view(np.uint32), num_stored)
-    d_x = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).to(dev)
-    d_beta = torch.from_numpy(np.ascontiguousarray(beta, dtype=np.float32)).to(dev)
-    # (the fit and the copies ran on the current stream: `stream` waits for them)
-    if stream is not None:
-        stream.wait_stream(torch.cuda.current_stream())
-    args = (ctx, bits, words_per_sample, num_sites, d_x, d_beta, lo, hi)
-    if inbreeding is None:
-        selfs = pcrelate_pairs_raw_device(*args, _self_pairs(num_stored), stream=stream)
-        if stream is not None:
-            stream.synchronize()
-        f = _inbreeding_of(pairs_to_host(selfs))
-    else:
-        f = _host_inbreeding(inbreeding, num_stored)
-    d_f = torch.from_numpy(f).to(dev)
-    if stream is not None:
-        stream.wait_stream(torch.cuda.current_stream())
-    rows = pcrelate_pairs_raw_device(*args, owner, d_f, count if stride == 24 else None,
-                                     stream=stream)
-    if stream is not None:
-        stream.synchronize()
-    return PCRelatePairs(pairs_to_host(rows), f, beta, used, fit_mask, x)
+    return _pcrelate_pairs(DevicePlace(ctx, stream), bits, words_per_sample, num_sites, pairs,
+                           scores, model, fit, min_maf, inbreeding, num_records)
 
 
 # ---- records: the pairs above a kinship threshold ----------------------------------------------
@@ -545,8 +411,7 @@ def records_to_host(records, num_records: int) -> np.ndarray:
     if isinstance(records, np.ndarray):
         rows = records[:num_records].copy()
     else:
-        rows = np.ascontiguousarray(records[:num_records].cpu().numpy()) \
-            .view(KING_RESULT_DTYPE).reshape(-1).copy()
+        rows = tensor_to_host(records[:num_records], KING_RESULT_DTYPE).copy()
     return sort_results(rows)
 
 
@@ -565,6 +430,41 @@ def _default_records(block: Submatrix) -> int:
     return max(1, min(pairs, 16 * (rows + cols)))
 
 
+def _pcrelate_records_raw(place, bits, words_per_sample, num_sites, x, beta, lo, hi, min_kin,
+                          block, max_records, out=None):
+    head, num_stored = _model_head(place, bits, words_per_sample, num_sites, x, beta)
+    block = _block(block, num_stored)
+    min_kin = _min_kin(min_kin)
+    if out is not None:
+        place.out(out, "out", KING_RESULT_DTYPE)
+        max_records = _out_capacity(out, max_records)
+    count = C.c_uint64(0)
+
+    def call(capacity):
+        recs = out if out is not None else place.alloc(max(capacity, 1), KING_RESULT_DTYPE)
+        return recs, place.fn("pcrelate_records")(*head, lo, hi, C.byref(block.c), min_kin,
+                                                  place.ptr(recs) if capacity else None,
+                                                  capacity, C.byref(count))
+
+    recs = _counted_buffer(call, _default_records(block), max_records, "max_records", count,
+                           "num_records")
+    return place.trim(recs, count.value), int(count.value)
+
+
+def _pcrelate_records(place, bits, words_per_sample, num_sites, scores, model, fit, min_maf,
+                      min_kinship, block, max_records) -> PCRelateRecords:
+    lo, hi = _bounds(min_maf)
+    words_per_sample = _count(words_per_sample, "words_per_sample")
+    num_sites = _count(num_sites, "num_sites")
+    x, beta, used, fit_mask = _fit_model(place, bits, words_per_sample, num_sites, scores, model,
+                                         fit, "records")
+    block = _block(block, place.bits(bits, words_per_sample))
+    recs, count = _pcrelate_records_raw(place, bits, words_per_sample, num_sites,
+                                        place.from_host(x), place.from_host(beta), lo, hi,
+                                        min_kinship, block, max_records)
+    return PCRelateRecords(recs, count, _min_kin(min_kinship), block, beta, used, fit_mask, x)
+
+
 def pcrelate_records_raw_host(bits: np.ndarray, words_per_sample: int, num_sites: int, x, beta,
                               lo: float, hi: float, min_kin: float, block=None,
                               max_records=None):
@@ -574,30 +474,8 @@ def pcrelate_records_raw_host(bits: np.ndarray, words_per_sample: int, num_sites
     ``pcrelate_matrix_host``.  The buffer rule is ``ld_edges_host``'s: without ``max_records`` a
     default buffer, grown once to the exact count; with it, an overflow raises
     ``ResourceExhaustedError`` whose ``num_records`` is the exact count."""
-    assert bits.dtype == np.uint64 and bits.flags.c_contiguous
-    words_per_sample = _count(words_per_sample, "words_per_sample")
-    num_sites = _count(num_sites, "num_sites")
-    num_stored = bits.size // words_per_sample if words_per_sample else 0
-    x = _geno_host_matrix(x, "x", num_stored)
-    beta = _geno_host_matrix(beta, "beta", num_sites, x.shape[1])
-    block = _block(block, num_stored)
-    min_kin = _min_kin(min_kin)
-    d = x.shape[1]
-    pad = np.zeros(4, dtype=np.float32)
-    count = C.c_uint64(0)
-
-    def call(capacity):
-        recs = np.zeros(max(capacity, 1), dtype=KING_RESULT_DTYPE)
-        status = _lib.load().cuking_pcrelate_records_host(
-            (bits if bits.size else pad).ctypes.data, num_stored, words_per_sample, num_sites,
-            (x if x.size else pad).ctypes.data, max(x.strides[0] // 4, d),
-            (beta if beta.size else pad).ctypes.data, max(beta.strides[0] // 4, d), d, lo, hi,
-            C.byref(block.c), min_kin, recs.ctypes.data, capacity, C.byref(count))
-        return recs, status
-
-    recs = _counted_buffer(call, _default_records(block), max_records, "max_records", count,
-                           "num_records")
-    return recs[:count.value].copy(), int(count.value)
+    return _pcrelate_records_raw(HOST, bits, words_per_sample, num_sites, x, beta, lo, hi, min_kin,
+                                 block, max_records)
 
 
 def pcrelate_records_host(bits: np.ndarray, words_per_sample: int, num_sites: int, scores=None,
@@ -605,75 +483,20 @@ def pcrelate_records_host(bits: np.ndarray, words_per_sample: int, num_sites: in
                           min_kinship: float = KING_CUTOFFS[0], block=None,
                           max_records=None) -> PCRelateRecords:
     """``KingContext.pcrelate_records`` on host memory and the host twins: no GPU."""
-    lo, hi = _bounds(min_maf)
-    words_per_sample = _count(words_per_sample, "words_per_sample")
-    num_sites = _count(num_sites, "num_sites")
-    if (scores is None) == (model is None):
-        raise ValueError("pcrelate records: give either scores or model")
-    if model is not None:
-        x, beta, used, fit_mask = _model_of(model)
-    else:
-        op = HostIsafOperator(bits, words_per_sample, num_sites, fit)
-        x, beta, used = isaf_fit(op, scores)
-        fit_mask = op.fit
-    block = _block(block, bits.size // words_per_sample if words_per_sample else 0)
-    recs, count = pcrelate_records_raw_host(bits, words_per_sample, num_sites, x, beta, lo, hi,
-                                            min_kinship, block, max_records)
-    return PCRelateRecords(recs, count, _min_kin(min_kinship), block, beta, used, fit_mask, x)
+    return _pcrelate_records(HOST, bits, words_per_sample, num_sites, scores, model, fit, min_maf,
+                             min_kinship, block, max_records)
 
 
 def pcrelate_records_raw_device(ctx, bits, words_per_sample: int, num_sites: int, x, beta,
                                 lo: float, hi: float, min_kin: float, block=None,
                                 max_records=None, out=None, stream=None):
-    import torch
-    from .api import _device_tensor, _stream_handle
-    num_stored = ctx._rows_of(bits, words_per_sample)
-    num_sites = _count(num_sites, "num_sites")
-    x = ctx._geno_matrix(x, "x", num_stored)
-    d = x.shape[1]
-    beta = ctx._geno_matrix(beta, "beta", num_sites, d)
-    block = _block(block, num_stored)
-    min_kin = _min_kin(min_kin)
-    dev = f"cuda:{ctx.device}"
-    if out is not None:
-        _device_tensor(ctx.device, out, "out", torch.int32, cols=6)
-        max_records = _out_capacity(out, max_records)
-    count = C.c_uint64(0)
-
-    def call(capacity):
-        records = out if out is not None else torch.empty((max(capacity, 1), 6),
-                                                          dtype=torch.int32, device=dev)
-        return records, ctx.lib.cuking_pcrelate_records(
-            ctx.handle, bits.data_ptr(), num_stored, words_per_sample, num_sites, x.data_ptr(),
-            max(x.stride(0), d), beta.data_ptr(), max(beta.stride(0), d), d, lo, hi,
-            C.byref(block.c), min_kin, records.data_ptr() if capacity else None, capacity,
-            C.byref(count), _stream_handle(stream))
-
-    records = _counted_buffer(call, _default_records(block), max_records, "max_records", count,
-                              "num_records")
-    return records, int(count.value)
+    return _pcrelate_records_raw(DevicePlace(ctx, stream), bits, words_per_sample, num_sites, x,
+                                 beta, lo, hi, min_kin, block, max_records, out)
 
 
 def pcrelate_records_device(ctx, bits, words_per_sample: int, num_sites: int, scores=None,
                             model=None, fit=None, min_maf: float = 0.01,
                             min_kinship: float = KING_CUTOFFS[0], block=None,
                             max_records=None) -> PCRelateRecords:
-    import torch
-    lo, hi = _bounds(min_maf)
-    words_per_sample = _count(words_per_sample, "words_per_sample")
-    num_sites = _count(num_sites, "num_sites")
-    if (scores is None) == (model is None):
-        raise ValueError("pcrelate records: give either scores or model")
-    dev = f"cuda:{ctx.device}"
-    if model is not None:
-        x, beta, used, fit_mask = _model_of(model)
-    else:
-        op = DeviceIsafOperator(ctx, bits, words_per_sample, num_sites, fit)
-        x, beta, used = isaf_fit(op, scores)
-        fit_mask = op.fit
-    block = _block(block, ctx._rows_of(bits, words_per_sample))
-    d_x = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).to(dev)
-    d_beta = torch.from_numpy(np.ascontiguousarray(beta, dtype=np.float32)).to(dev)
-    records, count = pcrelate_records_raw_device(ctx, bits, words_per_sample, num_sites, d_x,
-                                                 d_beta, lo, hi, min_kinship, block, max_records)
-    return PCRelateRecords(records, count, _min_kin(min_kinship), block, beta, used, fit_mask, x)
+    return _pcrelate_records(DevicePlace(ctx), bits, words_per_sample, num_sites, scores, model,
+                             fit, min_maf, min_kinship, block, max_records)
