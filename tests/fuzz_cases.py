@@ -7,7 +7,8 @@ Every failure is reported as a reproducer: the generator function, its seed and
 the index of the case, plus the case's parameters -- `python tools/fuzz_gpu.py
 SEED CASES FIRST_CASE` replays it (run_reducing: `python tools/fuzz_reducing.py
 SEED CASES FIRST_CASE [SIZE_CLASS]`, the size class being the tag's `sweep`; run_pipeline:
-`python tools/fuzz_pipeline.py SEED CASES --first-case K --size-class CLASS`).
+`python tools/fuzz_pipeline.py SEED CASES --first-case K --size-class CLASS`; run_site_order:
+`python tools/fuzz_site_order.py SEED CASES FIRST_CASE`).
 The checker is the CPU oracle (oracle/pyoracle.py); everything checked goes
 through the C ABI."""
 from __future__ import annotations
@@ -537,6 +538,151 @@ def run_reducing(ctx, seed: int, cases: int, first_case: int = 0, log=None, size
     finally:
         ctx.set_kernel("tiled")
         for key, value in SHIPPED.items():
+            ctx.set_option(key, value)
+        ctx.invalidate()
+    return ran
+
+
+# ---- the filter path with the site order on --------------------------------------------------
+def run_site_order(ctx, seed: int, cases: int, first_case: int = 0, log=None, stats=None) -> int:
+    """The filter variant with "filter_site_order" 1 / 2 / -1 (tests/site_order_cases.py): every
+    block of a split, lengths from one site to 94 k-steps, thresholds the filter runs for and
+    does not, lean and full forms, every gather form, everything run_general draws for the
+    filter, and three to six of -- the record call, the record call at a second threshold, tile
+    ranges, relative_counts, kin_matrix, a staged pass -- in a random order over one bitset, on
+    a side stream in some cases (tools/fuzz_site_order.py).  Everything is compared exactly
+    with what ONE oracle.all_pairs call gives.  Behind every whole-block call for which
+    prepare() makes it plain (site_order_cases.expected_flag) "site_order_on" must be what
+    the rule says: a silent fall-back to stored order is a mismatch.  Returns the number of
+    cases run; `stats`, a dict, gains the calls per kind, `expected_ordered` and `ordered`
+    (whole-block calls the rule expects an ordered layout behind, and those of them that left
+    one), `automatic_ordered` (calls under a rule the sweep only records that left one),
+    `early_exits` (the rise of filter_early_exits) and `gathers` (the values of
+    "filter_site_gather" a call ordered a layout under)."""
+    import torch
+    import cuking_amd
+    import reducing_cases as rc
+    import site_order_cases as so
+    from cuking_amd.dist import tile_partition
+
+    stats = stats if stats is not None else {}
+    for key in so.KINDS + ("expected_ordered", "ordered", "automatic_ordered", "early_exits"):
+        stats.setdefault(key, 0)
+    stats.setdefault("gathers", [])
+    shipped = dict(SHIPPED, **so.SHIPPED)
+    dev = f"cuda:{ctx.device}"
+    t0, ran = time.time(), 0
+    exits0 = ctx.get_option("filter_early_exits")
+    try:
+        for tag, geno in so.site_order_cases(seed, cases, first_case):
+            n, m, k, shard = tag["n"], tag["m"], tag["split_factor"], tag["shard"]
+            thresholds, w = tag["thresholds"], tag["tile_ranges"]
+            osm, bits, all_pairs = so.site_order_oracle(tag, geno)
+            block = osm.as_tuple()
+            exp = rc.expect_all(block, all_pairs, BIN_MENU[0], thresholds)
+            records = {t: so.records_of(all_pairs, t) for t in (tag["thr"], tag["thr2"])}
+            sm = cuking_amd.Submatrix(n, k, shard)
+            assert sm.as_tuple() == block and bits.shape[0] == sm.NumSamples() >= 2
+            rows, cols, stored = sm.NumRows(), sm.NumCols(), sm.NumSamples()
+
+            ctx.set_kernel("tiled")
+            for key in shipped:
+                if key in tag:
+                    ctx.set_option(key, tag[key])
+            ctx.set_option("variant", 7)
+            # (a new bitset may land on a recycled pointer: tell the library)
+            ctx.invalidate()
+            d_bits = ctx.upload_bitset(bits)
+            wps = cuking_amd.words_per_sample(m)
+            stream = torch.cuda.Stream(dev) if tag["side_stream"] else torch.cuda.current_stream()
+            stream.wait_stream(torch.cuda.current_stream())
+
+            def fail(what, detail=""):
+                raise FuzzMismatch(f"{what}: {detail}; reproduce with {tag} "
+                                   f"(tools/fuzz_site_order.py {seed} {tag['case'] + 1} "
+                                   f"{tag['case']})")
+
+            def flag(kind):
+                """"site_order_on" behind a whole-block call, against the rule."""
+                got = ctx.get_option("site_order_on")
+                want = so.expected_flag(tag, kind, so.call_threshold(tag, kind))
+                if want is None:
+                    stats["automatic_ordered"] += got
+                else:
+                    stats["expected_ordered"] += want
+                    stats["ordered"] += got
+                    if got != want:
+                        fail(kind, f"site_order_on {got}, the rule says {want}")
+                if got and tag["filter_site_gather"] not in stats["gathers"]:
+                    stats["gathers"] = sorted(stats["gathers"] + [tag["filter_site_gather"]])
+
+            def call_run(kind="run"):
+                thr = so.call_threshold(tag, kind)
+                for rep in range(2 if tag["reuse_prepared"] else 1):   # the second call reuses the layout
+                    got = ctx.run(sm, wps, d_bits, thr)
+                    if got.tobytes() != records[thr].tobytes():
+                        fail(f"{kind} at {thr} (rep {rep})", _diff(got, records[thr]))
+                    flag(kind)
+
+            def call_tile_ranges():
+                tiles = ctx.num_tiles(sm)
+                parts = [ctx.run(sm, wps, d_bits, tag["thr"], tile_range=r)
+                         for r in tile_partition(tiles, w)]
+                merged = cuking_amd.sort_results(np.ascontiguousarray(np.concatenate(parts)))
+                if merged.tobytes() != records[tag["thr"]].tobytes():
+                    fail(f"{w} tile ranges", _diff(merged, records[tag["thr"]]))
+
+            def call_relative_counts():
+                out = torch.zeros((stored, len(thresholds)), dtype=torch.int32, device=dev)
+                for times in (1, 2):                 # the call accumulates
+                    counts = ctx.relative_counts(sm, wps, d_bits, thresholds=thresholds, out=out,
+                                                 stream=stream)
+                    stream.synchronize()
+                    got = counts.bands()
+                    if not np.array_equal(got, np.uint32(times) * exp.bands):
+                        fail(f"relative_counts (call {times})", f"counts differ at (sample, band) "
+                             f"{np.argwhere(got != np.uint32(times) * exp.bands)[:8].tolist()}")
+                    if counts.num_records(0) != times * len(records[tag["thr"]]):
+                        fail("relative_counts", f"num_records(0) {counts.num_records(0)}, the "
+                             f"oracle has {len(records[tag['thr']])} records")
+                    flag("relative_counts")
+
+            def call_kin_matrix():
+                out = torch.full((rows, cols), float(rc.SENTINEL), dtype=torch.float32, device=dev)
+                ctx.kin_matrix(sm, wps, d_bits, out=out, stream=stream)
+                stream.synchronize()
+                try:
+                    rc.assert_same(out.cpu().numpy(), exp.matrix, "kin_matrix")
+                except AssertionError as e:
+                    fail("kin_matrix", str(e))
+                if ctx.get_option("site_order_on"):
+                    fail("kin_matrix", "the dense layout claims the site order")
+
+            def call_staged():
+                want = records[tag["thr"]]
+                merged = _staged(ctx, sm, wps, d_bits, tag["thr"], max(len(want), 1) + 8, n,
+                                 tag["world"], tag["chunks"], tag["streams"])
+                if merged.tobytes() != want.tobytes():
+                    fail(f"staged (world {tag['world']}, chunks {tag['chunks']}, streams "
+                         f"{tag['streams']})", _diff(merged, want))
+                if ctx.get_option("site_order_on"):
+                    fail("staged", "a staged pass claims the site order")
+
+            calls = dict(run=call_run, run2=lambda: call_run("run2"),
+                         tile_ranges=call_tile_ranges, relative_counts=call_relative_counts,
+                         kin_matrix=call_kin_matrix, staged=call_staged)
+            with torch.cuda.stream(stream):
+                for kind in tag["calls"]:
+                    calls[kind]()
+                    stats[kind] += 1
+            stream.synchronize()
+            ran += 1
+            if log and tag["case"] % 10 == 0:
+                log(f"run_site_order seed {seed} case {tag['case']} ok ({time.time() - t0:.0f}s)")
+    finally:
+        stats["early_exits"] += ctx.get_option("filter_early_exits") - exits0
+        ctx.set_kernel("tiled")
+        for key, value in shipped.items():
             ctx.set_option(key, value)
         ctx.invalidate()
     return ran

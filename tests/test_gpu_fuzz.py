@@ -38,6 +38,12 @@ PIPELINE_SITES = [(421, 40)]
 # (what tests/test_pipeline_cases.py holds to its conditions on the CPU)
 PIPELINE_SWEEPS = [(s, c, "small") for s, c in PIPELINE] + \
     [(s, c, "samples") for s, c in PIPELINE_SAMPLES] + [(s, c, "sites") for s, c in PIPELINE_SITES]
+# run_site_order (the filter path with "filter_site_order" on: record calls at two thresholds,
+# tile ranges, relative_counts, kin_matrix and a staged pass interleaved), in
+# one session on one MI355X box with 16 host threads: 7, 7 and 6 s (the oracle's all_pairs call
+# and the numpy expectations are most of it), against the 22 to 30 s of a general sweep
+SITE_ORDER = [(501, 100), (502, 100), (503, 100)]
+# (what tests/test_site_order_cases.py holds to its conditions on the CPU)
 SCALE = float(os.environ.get("CUKING_FUZZ_SCALE", "1"))
 
 
@@ -119,6 +125,23 @@ def test_random_pipeline_calls_sample_boundaries(ctx, seed, cases):
 @pytest.mark.parametrize("seed,cases", PIPELINE_SITES)
 def test_random_pipeline_calls_site_boundaries(ctx, seed, cases):
     _pipeline_sweep(ctx, seed, cases, "sites")
+
+
+@pytest.mark.parametrize("seed,cases", SITE_ORDER)
+def test_random_site_order_calls_interleaved(ctx, seed, cases):
+    """One run_site_order sweep: every case drawn was run; every whole-block call the rule of
+    prepare() expects an ordered layout behind left one (a mismatch raises at once: the sums
+    say that there were such calls); tiles left at a check; every gather form ordered a
+    layout."""
+    import site_order_cases
+    t0 = time.time()
+    cases, stats = max(1, int(cases * SCALE)), {}
+    ran = fuzz_cases.run_site_order(ctx, seed, cases, log=_log, stats=stats)
+    print(f"run_site_order seed {seed}: {ran} cases OK in {time.time() - t0:.0f}s, {stats}")
+    assert ran == cases
+    assert stats["ordered"] == stats["expected_ordered"] > 0, stats
+    assert stats["early_exits"] > 0, stats
+    assert stats["gathers"] == sorted(site_order_cases.GATHERS), stats
 
 
 def test_one_staged_configuration_repeated(ctx):
