@@ -8,7 +8,9 @@ the index of the case, plus the case's parameters -- `python tools/fuzz_gpu.py
 SEED CASES FIRST_CASE` replays it (run_reducing: `python tools/fuzz_reducing.py
 SEED CASES FIRST_CASE [SIZE_CLASS]`, the size class being the tag's `sweep`; run_pipeline:
 `python tools/fuzz_pipeline.py SEED CASES --first-case K --size-class CLASS`; run_site_order:
-`python tools/fuzz_site_order.py SEED CASES FIRST_CASE`).
+`python tools/fuzz_site_order.py SEED CASES FIRST_CASE`; run_pcrelate, whose checkers are the
+float64 references of tests/pcrelate_cases.py and tests/pcrelate_pairs_cases.py and the host
+twins: `python tools/fuzz_pcrelate.py SEED CASES FIRST_CASE SIZE_CLASS`).
 The checker is the CPU oracle (oracle/pyoracle.py); everything checked goes
 through the C ABI."""
 from __future__ import annotations
@@ -684,6 +686,248 @@ def run_site_order(ctx, seed: int, cases: int, first_case: int = 0, log=None, st
         ctx.set_kernel("tiled")
         for key, value in shipped.items():
             ctx.set_option(key, value)
+        ctx.invalidate()
+    return ran
+
+
+# ---- PC-Relate: matrix, records and listed pairs over one bitset and one model -----------------
+PCR_GUARD = 0x7FC00123                 # a NaN of its own: a kernel's NaN in a guard shows
+
+
+def run_pcrelate(ctx, seed: int, cases: int, first_case: int = 0, log=None, size_class=None,
+                 stats=None, twin_every: int = 1) -> int:
+    """The three PC-Relate calls (tests/pcrelate_fuzz_cases.py has the cases and the size
+    classes "small", "tiles" and "exact"): per case, on the case's stream and under its launch
+    cap, the matrix of the block, the matrix of a sub-block, the records and the listed pairs in
+    the drawn order, checked after one wait at the end -- against the float64 references of
+    pcrelate_cases.py and pcrelate_pairs_cases.py within their tolerances, against each other
+    on bytes (the sub-block and the records against the matrix, a reordered part of the list
+    against the list) and against the host twins (on every `twin_every`-th case; on bytes in the
+    class "exact").  The record call returns its count, so it waits by itself; and its two
+    thresholds that pairs sit ON -- the median and the 95th-percentile value of the device
+    matrix -- need the matrix on the host: those two calls follow the wait.  Returns the number
+    of cases run; `stats`, a dict, gains the calls per kind, `d_seen` (per kernel the sorted D
+    buckets launched), `split_launches` (calls under a launch cap that really split them),
+    `entries` and `compared` (matrix entries, and those of them that are not NaN and so were
+    held to a tolerance or to bytes)."""
+    import torch
+    import cuking_amd
+    import pcrelate_cases as pc
+    import pcrelate_fuzz_cases as pf
+    import pcrelate_pairs_cases as pp
+    import pcrelate_records_cases as rc
+    from cuking_amd import pcrelate as pcr
+
+    stats = stats if stats is not None else {}
+    for key in ("matrix", "matrix_sub", "records", "pairs", "split_launches", "entries",
+                "compared", "twins"):
+        stats.setdefault(key, 0)
+    stats.setdefault("d_seen", {kind: [] for kind in pf.KINDS})
+    dev = f"cuda:{ctx.device}"
+    t0, ran = time.time(), 0
+    try:
+        for tag, inp in pf.pcrelate_sweep_cases(seed, cases, first_case, size_class):
+            exact = tag["size_class"] == "exact"
+            sites, block, sub = tag["sites"], inp.block, inp.sub_block
+            rows, cols = block[1] - block[0], block[3] - block[2]
+            splits = pf.split_launches(tag)
+
+            def fail(what, detail=""):
+                raise FuzzMismatch(f"{what}: {detail}; reproduce with {tag} "
+                                   f"(tools/fuzz_pcrelate.py {seed} {tag['case'] + 1} "
+                                   f"{tag['case']} {tag['size_class']})")
+
+            def held(what, check, *args, **kw):
+                try:
+                    return check(*args, **kw)
+                except AssertionError as e:
+                    fail(what, str(e)[:400])
+
+            def padded(a):   # the host's pitch, NaN between the columns and the pitch
+                wide = np.full((a.shape[0], a.strides[0] // 4), np.float32(np.nan), np.float32)
+                wide[:, :a.shape[1]] = a
+                return torch.from_numpy(wide).to(dev)[:, :a.shape[1]]
+
+            def guarded(shape):
+                return torch.full(shape, PCR_GUARD, dtype=torch.int32, device=dev)
+
+            # (a new bitset may land on a recycled pointer: tell the library)
+            ctx.invalidate()
+            bits = ctx.upload_bitset(inp.bits.copy())
+            x, beta = padded(inp.x), padded(inp.beta)
+            f = None if inp.f is None else torch.from_numpy(inp.f).to(dev)
+            words = np.ascontiguousarray(inp.pairs).view(np.int32).reshape(-1, tag["stride"] // 4)
+            d_list = torch.from_numpy(words.copy()).to(dev)
+            d_part = torch.from_numpy(words[inp.part].copy()).to(dev)
+            head = (bits, inp.wps, sites, x, beta, inp.lo, inp.hi)
+            wide = guarded((rows + 2, cols + tag["pads"][2]))
+            sub_rows, sub_cols = sub[1] - sub[0], sub[3] - sub[2]
+            sub_wide = guarded((sub_rows + 2, sub_cols + tag["pads"][2]))
+            room = max(rc.num_pairs(block), 1)
+            rec_buf = guarded((room + 3, 6))
+            got = {}
+            stream = torch.cuda.Stream(dev) if tag["side_stream"] else torch.cuda.current_stream()
+            stream.wait_stream(torch.cuda.current_stream())
+
+            def records_at(min_kin, **kw):
+                recs, count = ctx.pcrelate_records_raw(*head, min_kin, block=block, stream=stream,
+                                                       **kw)
+                return pcr.records_to_host(recs, count), count
+
+            def call_matrix():
+                ctx.pcrelate_matrix(*head, block=block, stream=stream,
+                                    out=wide.view(torch.float32)[1:rows + 1, :cols])
+
+            def call_matrix_sub():
+                ctx.pcrelate_matrix(*head, block=sub, stream=stream,
+                                    out=sub_wide.view(torch.float32)[1:sub_rows + 1, :sub_cols])
+
+            def call_records():
+                got["records"] = records_at(-np.inf, max_records=room, out=rec_buf)
+                got["none"] = records_at(np.inf)
+                total = got["records"][1]
+                if tag["short_buffer"] and total > 0:
+                    short = guarded((total + 2, 6))
+                    try:
+                        records_at(-np.inf, max_records=total - 1, out=short)
+                        fail("records", f"a buffer of {total - 1} records took {total}")
+                    except cuking_amd.ResourceExhaustedError as e:
+                        if e.num_records != total:
+                            fail("records", f"a short buffer counted {e.num_records}, not {total}")
+                    got["short"] = short
+
+            def call_pairs():
+                got["pairs"] = ctx.pcrelate_pairs_raw(*head, d_list, f, stream=stream)
+                got["part"] = ctx.pcrelate_pairs_raw(*head, d_part, f, stream=stream)
+
+            calls = dict(matrix=call_matrix, matrix_sub=call_matrix_sub, records=call_records,
+                         pairs=call_pairs)
+            ctx.set_option("max_launch_blocks", tag["max_launch_blocks"])
+            with torch.cuda.stream(stream):
+                for kind in tag["calls"]:
+                    calls[kind]()
+                    stats[kind] += 1
+                    stats["split_launches"] += bool(splits[kind])
+                    seen = stats["d_seen"][kind.split("_")[0]]
+                    if pf.bucket(tag["d"]) not in seen:
+                        seen.append(pf.bucket(tag["d"]))
+                        seen.sort()
+            stream.synchronize()                 # THE wait
+
+            # ---- the matrix
+            host = wide.cpu().numpy()
+            kin = np.ascontiguousarray(host[1:rows + 1, :cols]).view(np.float32)
+            touched = host.copy()
+            touched[1:rows + 1, :cols] = PCR_GUARD
+            if (touched != PCR_GUARD).any():
+                fail("matrix", f"guard rows or pitch written at {np.argwhere(touched != PCR_GUARD)[:5].tolist()}")
+            stats["entries"] += kin.size
+            stats["compared"] += int((~np.isnan(kin)).sum())
+            if exact:
+                want = pc.exact_expected_of(inp.code, inp.beta, block)
+                if kin.tobytes() != want.tobytes():
+                    fail("matrix", "differs from the integer formula at "
+                         f"{np.argwhere(kin.view(np.uint32) != want.view(np.uint32))[:5].tolist()}")
+            else:
+                held("matrix against the float64 reference", pc.check_reference_of, inp.ref, kin,
+                     "matrix", quiet=True)
+            if rc.is_diagonal(block) and not np.array_equal(kin.view(np.uint32),
+                                                            kin.view(np.uint32).T):
+                fail("matrix", "a diagonal block is not bytewise symmetric")
+            sub_host = sub_wide.cpu().numpy()
+            sub_kin = sub_host[1:sub_rows + 1, :sub_cols].copy()
+            sub_host[1:sub_rows + 1, :sub_cols] = PCR_GUARD
+            if (sub_host != PCR_GUARD).any():
+                fail("matrix_sub", "guard rows or pitch written")
+            same = kin.view(np.int32)[sub[0] - block[0]:sub[1] - block[0],
+                                      sub[2] - block[2]:sub[3] - block[2]]
+            if not np.array_equal(sub_kin, same):
+                fail("matrix_sub", f"block {sub} differs from the same entries of {block} at "
+                     f"{np.argwhere(sub_kin != same)[:5].tolist()}")
+
+            # ---- the records: the matrix thresholded, on bytes
+            def records_hold(recs, count, min_kin, what):
+                want = rc.threshold_matrix(kin, block, min_kin)
+                if count != recs.shape[0] or count != want.shape[0]:
+                    fail(what, f"count {count}, {recs.shape[0]} records, the matrix gives "
+                         f"{want.shape[0]}")
+                held(what, rc.check_records, recs, block)
+                held(what, rc.same_records, recs, want)
+
+            everything, total = got["records"]
+            records_hold(everything, total, -np.inf, "records at -inf")
+            records_hold(*got["none"], np.inf, "records at +inf")
+            if not exact:
+                held("records at -inf against the float64 reference", rc.check_records_reference,
+                     inp.ref, block, everything, "records", quiet=True)
+            if (rec_buf[total:].cpu().numpy() != PCR_GUARD).any():
+                fail("records", "written behind the count")
+            if "short" in got:
+                short = got["short"].cpu().numpy()
+                if (short[total - 1:] != PCR_GUARD).any():
+                    fail("records", "a short buffer was written behind max_records")
+                stored = np.ascontiguousarray(short[:total - 1]).view(
+                    cuking_amd.KING_RESULT_DTYPE).reshape(-1)
+                held("records in a short buffer", rc.check_records, stored, block)
+            values = np.sort(kin[rc.pair_mask(block) & ~np.isnan(kin)])
+            on_value = [float(values[int(q * values.size)]) for q in (0.5, 0.95)] \
+                if values.size else []
+            with torch.cuda.stream(stream):
+                for t in on_value:               # (a pair sits on t: the strict > decides)
+                    records_hold(*records_at(t), t, f"records at the value {t!r}")
+                    stats["records"] += 1
+
+            # ---- the listed pairs
+            rows_got = pcr.pairs_to_host(got["pairs"])
+            held("pairs", pp.check_rows_of, inp.index, rows_got)
+            if exact:
+                want = pp.exact_expected_of(inp)
+                if rows_got.tobytes() != want.tobytes():
+                    fail("pairs", "differ from the integer formula")
+            else:
+                held("pairs against the float64 reference", pp.check_reference_of, inp.pair_ref,
+                     inp.index, rows_got, "pairs", quiet=True)
+                # the kin of a listed pair of the block against the matrix entry
+                i, j = inp.index[:, 0].astype(np.int64), inp.index[:, 1].astype(np.int64)
+                ok = (i >= block[0]) & (i < block[1]) & (j >= block[2]) & (j < block[3])
+                entry = kin[i[ok] - block[0], j[ok] - block[2]]
+                mine = rows_got["kin"][ok]
+                if not np.array_equal(np.isnan(entry), np.isnan(mine)):
+                    fail("pairs", "NaN where the matrix has none, or the reverse")
+                fin = ~np.isnan(entry)
+                tol = inp.ref.twin_tolerance()[i[ok] - block[0], j[ok] - block[2]]
+                if (np.abs(mine.astype(np.float64) - entry)[fin] > tol[fin]).any():
+                    fail("pairs", "kin further than the twin tolerance from the matrix entry")
+            part_got = pcr.pairs_to_host(got["part"])
+            if part_got.tobytes() != rows_got[inp.part].tobytes():
+                fail("pairs", "a reordered part of the list gives other row bytes")
+
+            # ---- the host twins
+            if tag["case"] % twin_every == 0:
+                stats["twins"] += 1
+                model = (inp.bits, inp.wps, sites, inp.x, inp.beta, inp.lo, inp.hi)
+                twin = pcr.pcrelate_matrix_host(*model, block=block)
+                if exact:
+                    if twin.tobytes() != kin.tobytes():
+                        fail("matrix", "differs from the host twin's bytes")
+                else:
+                    held("matrix against the host twin", pc.check_twin_of, inp.ref, kin, twin,
+                         "matrix", quiet=True)
+                for t, (recs, _) in ((-np.inf, got["records"]), (np.inf, got["none"])):
+                    twin_recs, _ = pcr.pcrelate_records_raw_host(*model, t, block=block)
+                    if rc.pair_set(twin_recs) != rc.pair_set(recs):
+                        fail(f"records at {t}", "another pair set than the host twin's")
+                    if exact:
+                        held(f"records at {t} against the host twin", rc.same_records, recs,
+                             twin_recs)
+                twin_rows = pcr.pcrelate_pairs_raw_host(*model, inp.pairs, inp.f)
+                if twin_rows.tobytes() != rows_got.tobytes():
+                    fail("pairs", "differ from the host twin's bytes")
+            ran += 1
+            if log and tag["case"] % 10 == 0:
+                log(f"run_pcrelate seed {seed} case {tag['case']} ok ({time.time() - t0:.0f}s)")
+    finally:
+        ctx.set_option("max_launch_blocks", 0)
         ctx.invalidate()
     return ran
 

@@ -37,6 +37,11 @@ class Case:
     lo: float = 0.01
     edge_every: int = 7   # one site in this many has mu around lo, another one around hi
     immune: tuple = ()    # the DEFECTS that cannot show on this case, by its construction
+    extra_word: object = None   # a garbage plane word beyond the sites (None: where sites % 3 == 0)
+    pads: object = None   # (x, beta, out) pitch pads of their own (None: `pad` for all three)
+
+    def pad_of(self, which: int) -> int:
+        return self.pad if self.pads is None else self.pads[which]
 
 
 def _whole(n):
@@ -62,6 +67,30 @@ CASES = (
 )
 REAL_CASES = tuple(c for c in CASES if not c.exact)
 EXACT_CASES = tuple(c for c in CASES if c.exact)
+
+# ---- the d ladder: every d from 1 to 32 -- every bucket of pcrelate_dispatch_columns (4, 8, 16,
+# 32) at its width, below it and at the first d of the next -- at the smallest shape that still
+# has a partial tile (130 = 128 + 2), a partial site step (97 = 3 x 32 + 1) and a partial beta
+# staging pass; the whole block and an off-diagonal one that starts and ends off a tile edge.
+# One site in 7 + d has mu around lo and as many around hi: e(i, s) grows with d + 2 (the reason
+# is in the module docstring).  LADDER_SEEDS[d] is the smallest seed at which
+# Reference.margin_violations() is 0, found on the CPU: seed 1 at every d (about 0.02 elements
+# within e of a bound are expected per rung); check_reference asserts it on every rung, on the
+# CPU in test_pcrelate_host.py.
+LADDER_N, LADDER_SITES = 130, 97
+LADDER_BLOCKS = (_whole(LADDER_N), (5, 70, 97, 130))
+LADDER_SEEDS = {d: 1 for d in range(1, 33)}
+
+
+def ladder_case(d: int, block=LADDER_BLOCKS[0], seed=None, n=LADDER_N, sites=LADDER_SITES) -> Case:
+    """The rung of the ladder at `d` (or the same construction at another shape or seed)."""
+    seed = LADDER_SEEDS[d] if seed is None else seed
+    kind = "" if block == _whole(n) else " block"
+    return Case(f"ladder {n}x{sites} d{d}{kind}", n, sites, d, tuple(block), seed=seed,
+                pad=d % 3, edge_every=7 + d)
+
+
+LADDER = tuple(ladder_case(d, block) for d in range(1, 33) for block in LADDER_BLOCKS)
 
 
 def pack_codes(code, rng, extra_words=0):
@@ -109,8 +138,9 @@ def inputs(case: Case) -> Inputs:
         beta = rng.integers(0, 3, size=(sites, 1)).astype(np.float32)
         # the planted pair without a jointly valid site: sample 0 is called at the even
         # sites only, sample 1 at the odd ones
-        code[0, 1::2] = 3
-        code[1, 0::2] = 3
+        if n > 1:
+            code[0, 1::2] = 3
+            code[1, 0::2] = 3
     else:
         # mu = p_s + a sample-specific shift: most sites inside the bounds for everybody, one
         # in edge_every with mu around or below lo (invalid for many), as many near 1
@@ -128,10 +158,12 @@ def inputs(case: Case) -> Inputs:
         x, beta = x.astype(np.float32), beta.astype(np.float32)
     if n > 2:
         code[2] = 3                          # an all-missing sample
-    bits = pack_codes(code, rng, extra_words=1 if sites % 3 == 0 else 0)
+    extra = sites % 3 == 0 if case.extra_word is None else case.extra_word
+    bits = pack_codes(code, rng, extra_words=1 if extra else 0)
     for a in (code, bits):
         a.setflags(write=False)
-    return Inputs(case, code, bits, _padded(x, case.pad), _padded(beta, case.pad), lo, hi)
+    return Inputs(case, code, bits, _padded(x, case.pad_of(0)), _padded(beta, case.pad_of(1)), lo,
+                  hi)
 
 
 DEFECTS = ("missing as hom-ref", "factor 4 dropped", "last step skipped", "planes swapped",
@@ -178,6 +210,7 @@ class Reference:
         self.d_num = np.abs(ri) @ eps_r[j0:j1].T + eps_r[i0:i1] @ np.abs(rj).T
         self.d_den = vi @ eps_v[j0:j1].T + eps_v[i0:i1] @ vj.T
         self.sites = sites
+        self._bounds = (lo, hi)
 
     def _tolerance(self, d_num, d_den):
         acc = (self.sites + 2) * EPS
@@ -208,24 +241,27 @@ class Reference:
 @lru_cache(maxsize=None)
 def reference(case: Case, defect=None) -> Reference:
     inp = inputs(case)
-    ref = Reference(inp.code, inp.x, inp.beta, inp.lo, inp.hi, case.block, defect)
-    ref._bounds = (inp.lo, inp.hi)
-    return ref
+    return Reference(inp.code, inp.x, inp.beta, inp.lo, inp.hi, case.block, defect)
 
 
-def exact_expected(case: Case) -> np.ndarray:
-    """The integer formula of the exact cases, float32 [rows, cols]: where beta is 1, mu is 0.5,
-    r = g - 1 and v = 0.5; elsewhere the site is invalid.  num is an integer, 4 den the count of
-    the jointly called valid sites, both below 2^24, so kin = fl(num / count), NaN for 0 / 0."""
-    inp = inputs(case)
-    site_ok = inp.beta[:, 0] == 1.0
-    called = ((inp.code != 3) & site_ok).astype(np.int64)
-    g = (inp.code.astype(np.int64) - 1) * called
-    i0, i1, j0, j1 = case.block
+def exact_expected_of(code, beta, block) -> np.ndarray:
+    """The integer formula of the exact construction, float32 [rows, cols]: where beta is 1, mu
+    is 0.5, r = g - 1 and v = 0.5; elsewhere the site is invalid.  num is an integer, 4 den the
+    count of the jointly called valid sites, both below 2^24, so kin = fl(num / count), NaN for
+    0 / 0."""
+    site_ok = beta[:code.shape[1], 0] == 1.0
+    called = ((code != 3) & site_ok).astype(np.int64)
+    g = (code.astype(np.int64) - 1) * called
+    i0, i1, j0, j1 = block
     num, count = g[i0:i1] @ g[j0:j1].T, called[i0:i1] @ called[j0:j1].T
     assert np.abs(num).max() < 2 ** 24 and count.max() < 2 ** 24
     with np.errstate(invalid="ignore"):
         return num.astype(np.float32) / count.astype(np.float32)
+
+
+def exact_expected(case: Case) -> np.ndarray:
+    inp = inputs(case)
+    return exact_expected_of(inp.code, inp.beta, case.block)
 
 
 def check_exact(case: Case, backend):
@@ -241,34 +277,49 @@ def check_exact(case: Case, backend):
 def check_reference(case: Case, backend, label=""):
     """A float32 backend against the float64 reference: identical NaN positions, every other
     entry within the reference's tolerance.  Returns the largest error / tolerance."""
-    ref = reference(case)
-    assert ref.margin_violations() == 0, f"{case.name}: choose another seed"
-    got, tol = backend(case), ref.tolerance()
+    return check_reference_of(reference(case), backend(case), case.name, label)
+
+
+def check_reference_of(ref: Reference, got, name, label="", quiet=False):
+    """check_reference on arrays: `got` against a Reference of the same block."""
+    assert ref.margin_violations() == 0, f"{name}: choose another seed"
+    tol = ref.tolerance()
     assert got.dtype == np.float32 and got.shape == ref.kin.shape
     nan = np.isnan(ref.kin)
-    assert np.array_equal(np.isnan(got), nan)
+    assert np.array_equal(np.isnan(got), nan), np.argwhere(np.isnan(got) != nan)[:5]
     ratio = (np.abs(got - ref.kin)[~nan] / tol[~nan]).max() if (~nan).any() else 0.0
-    print(f"{case.name} {label}: largest tolerance {tol[~nan].max() if (~nan).any() else 0:.3g}, "
-          f"largest error / tolerance {ratio:.3g}")
-    assert ratio <= 1.0
+    if not quiet:
+        print(f"{name} {label}: largest tolerance {tol[~nan].max() if (~nan).any() else 0:.3g}, "
+              f"largest error / tolerance {ratio:.3g}")
+    assert ratio <= 1.0, (name, label, ratio)
     return ratio
 
 
 def check_twin(case: Case, device_backend, host_backend):
     """Device against host twin: identical NaN positions, the accumulation bound."""
-    ref = reference(case)
-    dev, host, tol = device_backend(case), host_backend(case), ref.twin_tolerance()
+    check_twin_of(reference(case), device_backend(case), host_backend(case), case.name)
+
+
+def check_twin_of(ref: Reference, dev, host, name, quiet=False):
+    """check_twin on arrays."""
+    tol = ref.twin_tolerance()
     nan = np.isnan(host)
     assert np.array_equal(np.isnan(dev), nan) and np.array_equal(np.isnan(ref.kin), nan)
     ratio = (np.abs(dev.astype(np.float64) - host)[~nan] / tol[~nan]).max() if (~nan).any() else 0.0
-    print(f"{case.name}: device against host twin, largest error / tolerance {ratio:.3g}")
-    assert ratio <= 1.0
+    if not quiet:
+        print(f"{name}: device against host twin, largest error / tolerance {ratio:.3g}")
+    assert ratio <= 1.0, (name, ratio)
+    return ratio
 
 
 def defect_ratio(case: Case, defect: str) -> float:
     """The largest move of an entry by `defect`, in units of that entry's tolerance (an entry
     that becomes or stops being NaN counts as infinitely far)."""
-    ref, bad = reference(case), reference(case, defect)
+    return defect_ratio_of(reference(case), reference(case, defect))
+
+
+def defect_ratio_of(ref: Reference, bad: Reference) -> float:
+    """defect_ratio on two References of the same arrays and block, `bad` with the defect."""
     tol = ref.tolerance()
     if (np.isnan(ref.kin) != np.isnan(bad.kin)).any():
         return float("inf")

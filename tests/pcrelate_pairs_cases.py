@@ -59,6 +59,24 @@ class Case:
     pad: int = 0
     edge_every: int = 7
     immune: tuple = ()    # the DEFECTS that cannot show on this case, by its construction
+    n: int = N            # samples
+    lo: float = 0.01
+    extra_word: object = None   # as pcrelate_cases.Case
+    pads: object = None
+
+
+def specials(n: int) -> tuple:
+    """SPECIALS for a cohort of n samples: the out-of-range index is n; a special that names a
+    sample the cohort does not have is left out."""
+    kept = []
+    for special in SPECIALS:
+        if special is None:
+            kept.append(None)
+        elif special[0] == N:
+            kept.append((n, 0))
+        elif special[1] == 0xFFFFFFFF or max(special) < n:
+            kept.append(special)
+    return tuple(kept)
 
 
 _NO_F = ("f ignored",)    # f is null: ignoring it changes nothing
@@ -83,6 +101,26 @@ CASES = (
 REAL_CASES = tuple(c for c in CASES if not c.exact)
 EXACT_CASES = tuple(c for c in CASES if c.exact)
 
+# ---- the d ladder (pcrelate_cases.py has the reasons): every d from 1 to 32 at 130 samples and
+# 97 sites (a partial step of 64), a list of 513 pairs (one more than a workgroup's), both
+# strides, with and without f.  LADDER_SEEDS[d] is the smallest seed at which
+# Reference.margin_violations() is 0 -- no element within e of a bound and no pair within its
+# tolerance of the k0 switch --, found on the CPU: seed 1 at every d; check_reference asserts it
+# on every rung, on the CPU in test_pcrelate_pairs_host.py.
+LADDER_SEEDS = {d: 1 for d in range(1, 33)}
+LADDER_FORMS = ((8, False), (8, True), (24, False), (24, True))    # (stride, f)
+
+
+def ladder_case(d: int, stride: int = 8, f: bool = False, seed=None) -> Case:
+    seed = LADDER_SEEDS[d] if seed is None else seed
+    return Case(f"ladder P513 S{pc.LADDER_SITES} d{d} stride {stride}{' f' if f else ''}",
+                WORKGROUP_PAIRS + 1, pc.LADDER_SITES, d, stride=stride, f=f, seed=seed,
+                pad=d % 3, edge_every=7 + d, n=pc.LADDER_N)
+
+
+def ladder(d: int) -> tuple:
+    return tuple(ladder_case(d, stride, f) for stride, f in LADDER_FORMS)
+
 
 @dataclass
 class Inputs:
@@ -99,16 +137,22 @@ class Inputs:
     wps: int
 
 
-@lru_cache(maxsize=None)
-def inputs(case: Case) -> Inputs:
-    base = pc.inputs(pc.Case("pairs " + case.name, N, case.sites, case.d, (0, N, 0, N),
-                             seed=case.seed, exact=case.exact, pad=case.pad,
-                             edge_every=case.edge_every))
+def cohort(case: Case):
+    """(code, bits, x, beta, lo, hi, rng) of a case: the cohort of pcrelate_cases.inputs with
+    genotypes that follow the model and the planted relatives (from 10 samples on); `rng` goes
+    on to draw the list and f."""
+    n = case.n
+    base = pc.inputs(pc.Case("pairs " + case.name, n, case.sites, case.d, (0, n, 0, n),
+                             seed=case.seed, exact=case.exact, pad=case.pad, lo=case.lo,
+                             edge_every=case.edge_every, extra_word=case.extra_word,
+                             pads=case.pads))
     rng = np.random.default_rng(77 * case.seed + case.pairs + 3 * case.sites + 11 * case.d)
     code, x = np.array(base.code), np.array(base.x)
+    planted = n >= 10
     # the planted relatives: 4 duplicates 3, 6 copies 5 with half its sites redrawn; both share
     # the model row of their original
-    x[4], x[6] = x[3], x[5]
+    if planted:
+        x[4], x[6] = x[3], x[5]
 
     def draw():   # codes [N, S]: 5 % missing
         if case.exact:
@@ -122,24 +166,42 @@ def inputs(case: Case) -> Inputs:
 
     if not case.exact:
         code = draw()
-        code[2] = 3                              # the all-missing sample
-    code[4] = code[3]
-    code[6] = np.where(rng.random(case.sites) < 0.5, code[5], draw()[5])
-    bits = pc.pack_codes(code, rng, extra_words=1 if case.sites % 3 == 0 else 0)
-    index = rng.integers(0, N, size=(case.pairs + len(SPECIALS), 2), dtype=np.uint32)
-    for k, special in enumerate(SPECIALS):
-        index[k] = index[len(SPECIALS)] if special is None else special
-    index = np.ascontiguousarray(index[:case.pairs])
-    pairs = index
-    if case.stride == 24:   # records: the other fields hold garbage
-        words = rng.integers(0, 2 ** 32, size=(case.pairs, 6), dtype=np.uint64).astype(np.uint32)
-        pairs = np.ascontiguousarray(words).view(KING_RESULT_DTYPE).reshape(-1)
-        pairs["sample_i"], pairs["sample_j"] = index[:, 0], index[:, 1]
-    f = rng.uniform(-0.1, 0.3, size=N).astype(np.float32) if case.f else None
-    for a in (code, bits, index, pairs):
+        if n > 2:
+            code[2] = 3                          # the all-missing sample
+    if planted:
+        code[4] = code[3]
+        code[6] = np.where(rng.random(case.sites) < 0.5, code[5], draw()[5])
+    extra = case.sites % 3 == 0 if case.extra_word is None else case.extra_word
+    bits = pc.pack_codes(code, rng, extra_words=1 if extra else 0)
+    for a in (code, bits):
         a.setflags(write=False)
-    return Inputs(case, code, bits, pc._padded(x, case.pad), base.beta, f, base.lo, base.hi,
-                  index, pairs, bits.shape[1])
+    return code, bits, pc._padded(x, base.case.pad_of(0)), base.beta, base.lo, base.hi, rng
+
+
+def pair_list(index, stride: int, rng):
+    """What the call takes for `index` uint32 [P, 2]: index itself at stride 8, records whose
+    other fields hold garbage at stride 24."""
+    if stride == 8:
+        return index
+    words = rng.integers(0, 2 ** 32, size=(index.shape[0], 6), dtype=np.uint64).astype(np.uint32)
+    pairs = np.ascontiguousarray(words).view(KING_RESULT_DTYPE).reshape(-1)
+    pairs["sample_i"], pairs["sample_j"] = index[:, 0], index[:, 1]
+    return pairs
+
+
+@lru_cache(maxsize=None)
+def inputs(case: Case) -> Inputs:
+    code, bits, x, beta, lo, hi, rng = cohort(case)
+    n, special = case.n, specials(case.n)
+    index = rng.integers(0, n, size=(case.pairs + len(special), 2), dtype=np.uint32)
+    for k, pair in enumerate(special):
+        index[k] = index[len(special)] if pair is None else pair
+    index = np.ascontiguousarray(index[:case.pairs])
+    pairs = pair_list(index, case.stride, rng)
+    f = rng.uniform(-0.1, 0.3, size=n).astype(np.float32) if case.f else None
+    for a in (index, pairs):
+        a.setflags(write=False)
+    return Inputs(case, code, bits, x, beta, f, lo, hi, index, pairs, bits.shape[1])
 
 
 DEFECTS = ("f ignored", "het dominance not zero", "ibs0 counting het/hom", "switch ignored",
@@ -151,8 +213,10 @@ class Reference:
     """The definition in float64 on the float32 inputs, one row per pair; the tolerances;
     optionally with one of DEFECTS built in."""
 
-    def __init__(self, inp: Inputs, defect=None):
-        case, sites, d = inp.case, inp.case.sites, inp.case.d
+    def __init__(self, inp, defect=None):
+        """`inp`: an Inputs, or anything with its arrays (code, x, beta, f, lo, hi, index): the
+        shape comes from the arrays, as in pcrelate_cases.Reference."""
+        sites, d = inp.code.shape[1], inp.x.shape[1]
         x64 = np.asarray(inp.x, dtype=np.float64)
         beta64 = np.asarray(inp.beta, dtype=np.float64)[:sites]
         code = inp.code.astype(np.int64)
@@ -233,6 +297,13 @@ class Reference:
         self.tol = dict(kin=2.0 * d_kin, k0=2.0 * d_k0, k1=2.0 * d_k1, k2=2.0 * d_k2)
         self.above = above
 
+    @classmethod
+    def of(cls, code, x, beta, f, lo, hi, index, defect=None):
+        """The Reference of bare arrays."""
+        from types import SimpleNamespace
+        return cls(SimpleNamespace(code=code, x=x, beta=beta, f=f, lo=lo, hi=hi, index=index),
+                   defect)
+
     def margin_violations(self):
         """Called elements whose float64 mu lies within e of a bound, plus pairs whose kin lies
         within its tolerance of the switch: there float32 and float64 could take different
@@ -260,11 +331,15 @@ def exact_expected(case: Case) -> np.ndarray:
     the site is invalid.  With n the jointly valid sites: 4 den = n, dden = n / 16, hden = n / 8
     and 16 dnum = (sites of equal zygosity) - (the others), all exact below 2^24, so every
     result is a chain of correctly rounded float32 operations on integers."""
-    inp = inputs(case)
+    return exact_expected_of(inputs(case))
+
+
+def exact_expected_of(inp) -> np.ndarray:
+    """exact_expected on arrays: anything with code, beta and index of the exact construction."""
     f32 = np.float32
-    ok = (inp.index < N).all(axis=1)
+    ok = (inp.index < inp.code.shape[0]).all(axis=1)
     i, j = np.where(ok, inp.index[:, 0], 0), np.where(ok, inp.index[:, 1], 0)
-    site_ok = inp.beta[:, 0] == 1.0
+    site_ok = inp.beta[:inp.code.shape[1], 0] == 1.0
     ci, cj = inp.code[i].astype(np.int64), inp.code[j].astype(np.int64)
     joint = (ci != 3) & (cj != 3) & site_ok[None, :] & ok[:, None]
     n = joint.sum(axis=1)
@@ -273,7 +348,7 @@ def exact_expected(case: Case) -> np.ndarray:
     zyg = same.sum(axis=1) - (joint & ~same).sum(axis=1)
     ibs0 = (joint & ((ci ^ cj) == 2)).sum(axis=1)
     assert n.max() < 2 ** 24
-    out = np.zeros(case.pairs, dtype=PCRELATE_PAIR_DTYPE)
+    out = np.zeros(inp.index.shape[0], dtype=PCRELATE_PAIR_DTYPE)
     with np.errstate(divide="ignore", invalid="ignore"):
         kin = num.astype(f32) / n.astype(f32)
         k2 = zyg.astype(f32) / n.astype(f32)
@@ -334,10 +409,14 @@ def e2e_cohort(seed=2):
 
 
 def check_rows(case: Case, rows):
-    inp = inputs(case)
-    assert rows.dtype == PCRELATE_PAIR_DTYPE and rows.shape == (case.pairs,)
-    assert np.array_equal(rows["sample_i"], inp.index[:, 0])
-    assert np.array_equal(rows["sample_j"], inp.index[:, 1])
+    check_rows_of(inputs(case).index, rows)
+
+
+def check_rows_of(index, rows):
+    """check_rows on arrays: the rows of the list `index`."""
+    assert rows.dtype == PCRELATE_PAIR_DTYPE and rows.shape == (index.shape[0],)
+    assert np.array_equal(rows["sample_i"], index[:, 0])
+    assert np.array_equal(rows["sample_j"], index[:, 1])
     # every NaN is the one quiet NaN
     for name in FLOATS:
         bad = np.isnan(rows[name])
@@ -362,34 +441,44 @@ def check_reference(case: Case, backend, label=""):
     every other value within the reference's tolerance.  Returns the largest error /
     tolerance."""
     ref = reference(case)
-    assert ref.margin_violations() == 0, f"{case.name}: choose another seed"
-    got = backend(case)
-    check_rows(case, got)
-    assert np.array_equal(got["ibs0"], ref.ibs0) and np.array_equal(got["sites"], ref.sites)
-    worst = 0.0
-    for name in FLOATS:
-        want, tol = ref.value[name], ref.tol[name]
-        nan = np.isnan(want)
-        assert np.array_equal(np.isnan(got[name]), nan), name
-        inf = np.isinf(want)
-        assert np.array_equal(got[name][inf], want[inf].astype(np.float32)), name
-        ok = ~nan & ~inf
-        if ok.any():
-            ratio = _in_tolerances(np.abs(got[name].astype(np.float64) - want)[ok], tol[ok])
-            print(f"{case.name} {label}: {name} largest tolerance {tol[ok].max():.3g}, largest "
-                  f"error / tolerance {ratio:.3g}")
-            worst = max(worst, ratio)
-    assert worst <= 1.0
+    worst = check_reference_of(ref, inputs(case).index, backend(case), case.name, label)
     if case.pairs >= len(SPECIALS) and case.sites >= 63:   # both sides of the switch
         below = ~ref.above & np.isfinite(ref.value["kin"])
         assert ref.above[0] and below[len(SPECIALS):].any()
     return worst
 
 
+def check_reference_of(ref: Reference, index, got, name, label="", quiet=False):
+    """check_reference on arrays: the rows `got` of the list `index` against its Reference."""
+    assert ref.margin_violations() == 0, f"{name}: choose another seed"
+    check_rows_of(index, got)
+    assert np.array_equal(got["ibs0"], ref.ibs0) and np.array_equal(got["sites"], ref.sites)
+    worst = 0.0
+    for field in FLOATS:
+        want, tol = ref.value[field], ref.tol[field]
+        nan = np.isnan(want)
+        assert np.array_equal(np.isnan(got[field]), nan), field
+        inf = np.isinf(want)
+        assert np.array_equal(got[field][inf], want[inf].astype(np.float32)), field
+        ok = ~nan & ~inf
+        if ok.any():
+            ratio = _in_tolerances(np.abs(got[field].astype(np.float64) - want)[ok], tol[ok])
+            if not quiet:
+                print(f"{name} {label}: {field} largest tolerance {tol[ok].max():.3g}, largest "
+                      f"error / tolerance {ratio:.3g}")
+            worst = max(worst, ratio)
+    assert worst <= 1.0, (name, label, worst)
+    return worst
+
+
 def defect_ratio(case: Case, defect: str) -> float:
     """The largest move of a value by `defect`, in units of that value's tolerance (a count
     that changes, or a value that becomes or stops being NaN or infinite, is infinitely far)."""
-    ref, bad = reference(case), reference(case, defect)
+    return defect_ratio_of(reference(case), reference(case, defect))
+
+
+def defect_ratio_of(ref: Reference, bad: Reference) -> float:
+    """defect_ratio on two References of the same arrays, `bad` with the defect."""
     if not np.array_equal(ref.ibs0, bad.ibs0) or not np.array_equal(ref.sites, bad.sites):
         return float("inf")
     worst = 0.0
@@ -434,7 +523,7 @@ def raw_arguments(inp: Inputs, pointers: dict, **over):
     """The argument list of cuking_pcrelate_pairs_host / cuking_pcrelate_pairs behind the
     context: `pointers` holds bits, x, beta, f, pairs, out, ldx, ldbeta."""
     case = inp.case
-    a = dict(pointers, num_stored=N, wps=inp.wps, sites=case.sites, d=case.d, lo=inp.lo,
+    a = dict(pointers, num_stored=case.n, wps=inp.wps, sites=case.sites, d=case.d, lo=inp.lo,
              hi=inp.hi, num_pairs=case.pairs, stride=case.stride)
     a.update(over)
     return (a["bits"], a["num_stored"], a["wps"], a["sites"], a["x"], a["ldx"], a["beta"],

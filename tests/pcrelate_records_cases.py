@@ -119,6 +119,28 @@ def check_records(records, block):
     assert len(pair_set(records)) == records.shape[0]
 
 
+def check_records_reference(ref, block, records, name, label="", quiet=False):
+    """The records of a call at -inf against a pcrelate_cases.Reference of the block: what
+    check_reference asks of a matrix, on the block's pairs -- the pairs of the records are the
+    pairs whose reference kinship is not NaN (identical NaN positions), and every kinship is
+    within the reference's tolerance.  Returns the largest error / tolerance."""
+    assert ref.margin_violations() == 0, f"{name}: choose another seed"
+    check_records(records, block)
+    want = pair_mask(block) & ~np.isnan(ref.kin)
+    ii = records["sample_i"].astype(np.int64) - block[0]
+    jj = records["sample_j"].astype(np.int64) - block[2]
+    have = np.zeros_like(want)
+    have[ii, jj] = True
+    assert np.array_equal(have, want), np.argwhere(have != want)[:5]
+    if not records.shape[0]:
+        return 0.0
+    ratio = float((np.abs(records["kin"] - ref.kin[ii, jj]) / ref.tolerance()[ii, jj]).max())
+    if not quiet:
+        print(f"{name} {label}: {records.shape[0]} records, largest error / tolerance {ratio:.3g}")
+    assert ratio <= 1.0, (name, label, ratio)
+    return ratio
+
+
 def same_records(got, want):
     """Both sorted by (sample_i, sample_j): the same pairs and the same kinship bytes."""
     assert got.shape == want.shape, (got.shape, want.shape)

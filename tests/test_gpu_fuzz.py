@@ -44,7 +44,19 @@ PIPELINE_SWEEPS = [(s, c, "small") for s, c in PIPELINE] + \
 # and the numpy expectations are most of it), against the 22 to 30 s of a general sweep
 SITE_ORDER = [(501, 100), (502, 100), (503, 100)]
 # (what tests/test_site_order_cases.py holds to its conditions on the CPU)
-SCALE = float(os.environ.get("CUKING_FUZZ_SCALE", "1"))
+# run_pcrelate (pcrelate_matrix, a sub-block, pcrelate_records at four thresholds and
+# pcrelate_pairs twice, interleaved over one bitset and one model, the host twins on every case),
+# in one session on one MI355X box in which the three run_site_order sweeps took 7, 7 and 6 s:
+# the three sweeps of the class "small" 3, 2 and 2 s, the one on the tile and step edges 1 s,
+# the exact one 1 s (the float64 references and the host twins are most of it)
+PCRELATE = [(601, 60), (602, 60), (603, 60)]
+PCRELATE_TILES = [(611, 40)]
+PCRELATE_EXACT = [(621, 40)]
+# (what tests/test_pcrelate_fuzz_cases.py holds to its conditions on the CPU)
+PCRELATE_SWEEPS = [(s, c, "small") for s, c in PCRELATE] + \
+    [(s, c, "tiles") for s, c in PCRELATE_TILES] + [(s, c, "exact") for s, c in PCRELATE_EXACT]
+PCRELATE_TWIN_EVERY = 1
+SCALE =float(os.environ.get("CUKING_FUZZ_SCALE", "1"))
 
 
 def _log(msg):
@@ -142,6 +154,41 @@ def test_random_site_order_calls_interleaved(ctx, seed, cases):
     assert stats["ordered"] == stats["expected_ordered"] > 0, stats
     assert stats["early_exits"] > 0, stats
     assert stats["gathers"] == sorted(site_order_cases.GATHERS), stats
+
+
+def _pcrelate_sweep(ctx, seed, cases, size_class):
+    """One run_pcrelate sweep: every case drawn was run; every D bucket of every kernel was
+    launched; a launch cap really split calls."""
+    import pcrelate_fuzz_cases as pf
+    t0 = time.time()
+    cases, stats = max(1, int(cases * SCALE)), {}
+    ran = fuzz_cases.run_pcrelate(ctx, seed, cases, log=_log, size_class=size_class, stats=stats,
+                                  twin_every=PCRELATE_TWIN_EVERY)
+    print(f"run_pcrelate seed {seed} ({size_class}): {ran} cases OK in {time.time() - t0:.0f}s, "
+          f"{stats}")
+    assert ran == cases
+    buckets = [4] if size_class == "exact" else [4, 8, 16, 32]
+    assert all(stats["d_seen"][kind] == buckets for kind in pf.KINDS), stats
+    assert stats["split_launches"] > 0, stats
+    return stats
+
+
+@pytest.mark.parametrize("seed,cases", PCRELATE)
+def test_random_pcrelate_calls_interleaved(ctx, seed, cases):
+    """... and at least 90 % of the matrix entries were not NaN: held to a tolerance."""
+    stats = _pcrelate_sweep(ctx, seed, cases, "small")
+    assert stats["entries"] > 0 and stats["compared"] >= 0.9 * stats["entries"], stats
+
+
+@pytest.mark.parametrize("seed,cases", PCRELATE_TILES)
+def test_random_pcrelate_calls_tile_and_step_edges(ctx, seed, cases):
+    stats = _pcrelate_sweep(ctx, seed, cases, "tiles")
+    assert stats["entries"] > 0 and stats["compared"] >= 0.9 * stats["entries"], stats
+
+
+@pytest.mark.parametrize("seed,cases", PCRELATE_EXACT)
+def test_random_pcrelate_calls_exact_on_bytes(ctx, seed, cases):
+    _pcrelate_sweep(ctx, seed, cases, "exact")
 
 
 def test_one_staged_configuration_repeated(ctx):

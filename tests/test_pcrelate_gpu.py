@@ -77,6 +77,22 @@ def test_device_against_float64_reference(case):
     pc.check_reference(case, device_backend, "device")
 
 
+@pytest.mark.parametrize("d", range(1, 33))
+def test_ladder_device_against_float64_reference_and_host_twin(d):
+    """Every d from 1 to 32 -- each instantiation of pcrelate_matrix_kernel at its width, below
+    it and at the first d of the next -- at 130 samples x 97 sites, the whole block and (5, 70,
+    97, 130)."""
+    for block in pc.LADDER_BLOCKS:
+        case = pc.ladder_case(d, block)
+        pc.check_reference(case, device_backend, "device")
+        pc.check_twin(case, device_backend, host_backend)
+    whole = device_backend(pc.ladder_case(d)).view(np.uint32)
+    assert np.array_equal(whole, whole.T)
+    i0, i1, j0, j1 = pc.LADDER_BLOCKS[1]
+    part = device_backend(pc.ladder_case(d, pc.LADDER_BLOCKS[1])).view(np.uint32)
+    assert np.array_equal(part, whole[i0:i1, j0:j1])
+
+
 @pytest.mark.parametrize("case", [c for c in pc.CASES if c.block == (0, c.n, 0, c.n)],
                          ids=lambda c: c.name)
 def test_diagonal_block_is_bytewise_symmetric(case):

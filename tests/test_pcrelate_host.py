@@ -39,6 +39,16 @@ def test_host_twin_against_float64_reference(case):
     pc.check_reference(case, host_backend, "host twin")
 
 
+@pytest.mark.parametrize("d", range(1, 33))
+def test_ladder_host_twin_against_float64_reference(d):
+    """Every d from 1 to 32 at 130 samples x 97 sites, the whole block and (5, 70, 97, 130):
+    the rungs the GPU test climbs, so that a fault of the generator shows without a GPU."""
+    for block in pc.LADDER_BLOCKS:
+        case = pc.ladder_case(d, block)
+        assert pc.reference(case).margin_violations() == 0
+        pc.check_reference(case, host_backend, "host twin")
+
+
 @pytest.mark.parametrize("case", pc.REAL_CASES, ids=lambda c: c.name)
 def test_real_cases_keep_their_distance_from_the_bounds(case):
     ref = pc.reference(case)

@@ -81,6 +81,16 @@ def test_device_against_float64_reference(case):
     pp.check_reference(case, device_backend, "device")
 
 
+@pytest.mark.parametrize("d", range(1, 33))
+def test_ladder_device_against_float64_reference(d):
+    """Every d from 1 to 32 -- each instantiation of pcrelate_pairs_kernel at its width, below
+    it and at the first d of the next -- at 130 samples x 97 sites, 513 pairs, both strides,
+    with and without f; and the host twin's bytes."""
+    for case in pp.ladder(d):
+        pp.check_reference(case, device_backend, "device")
+        assert device_backend(case).tobytes() == host_backend(case).tobytes()
+
+
 def test_the_same_pair_gives_the_same_bytes(ctx):
     import torch
     case = next(c for c in pp.CASES if c.name == "P513 S129 d11")

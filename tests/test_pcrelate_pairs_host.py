@@ -36,6 +36,15 @@ def test_host_twin_against_float64_reference(case):
     pp.check_reference(case, host_backend, "host twin")
 
 
+@pytest.mark.parametrize("d", range(1, 33))
+def test_ladder_host_twin_against_float64_reference(d):
+    """Every d from 1 to 32 at 130 samples x 97 sites, 513 pairs, both strides, with and
+    without f: the rungs the GPU test climbs."""
+    for case in pp.ladder(d):
+        assert pp.reference(case).margin_violations() == 0
+        pp.check_reference(case, host_backend, "host twin")
+
+
 def test_the_case_list_covers_the_kernel_constants():
     text = (ROOT / "cuking_amd" / "csrc" / "king_pcrelate_pairs.hip").read_text()
     assert f"constexpr uint32_t kPairThreads = {pp.WORKGROUP_PAIRS};" in text

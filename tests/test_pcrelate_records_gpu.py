@@ -85,6 +85,27 @@ def test_device_records_equal_the_device_matrix_thresholded(case):
         assert got.shape[0] == int((kin[pairs] > t).sum())
 
 
+@pytest.mark.parametrize("d", range(1, 33))
+def test_ladder_device_records_against_float64_reference(d):
+    """Every d from 1 to 32 -- each instantiation of pcrelate_records_kernel at its width, below
+    it and at the first d of the next -- at 130 samples x 97 sites, the whole block and (5, 70,
+    97, 130): at -inf the records are the reference's pairs of defined kinship, each within
+    tolerance, and the device matrix thresholded on bytes; at the median VALUE of the device
+    matrix, which a pair sits on, the strict comparison decides."""
+    for block in pc.LADDER_BLOCKS:
+        case = pc.ladder_case(d, block)
+        kin = device_matrix(case)
+        got, count = device_records(case, -rc.INF)
+        assert count == got.shape[0]
+        rc.check_records_reference(pc.reference(case), block, got, case.name, "device")
+        rc.same_records(got, rc.threshold_matrix(kin, block, -rc.INF))
+        values = np.sort(kin[rc.pair_mask(block) & ~np.isnan(kin)])
+        t = float(values[values.size // 2])
+        got, count = device_records(case, t)
+        assert count == got.shape[0] < values.size
+        rc.same_records(got, rc.threshold_matrix(kin, block, t))
+
+
 @pytest.mark.parametrize("case", rc.CASES, ids=lambda c: c.name)
 def test_device_set_equals_the_host_twin_at_the_gap_thresholds(case):
     inp = pc.inputs(case)

@@ -45,6 +45,19 @@ def test_host_records_equal_the_host_matrix_thresholded(case):
         rc.same_records(got, want)      # (no sort: the host twin's order IS ascending (i, j))
 
 
+@pytest.mark.parametrize("d", range(1, 33))
+def test_ladder_host_records_against_float64_reference(d):
+    """Every d from 1 to 32 at 130 samples x 97 sites, the whole block and (5, 70, 97, 130):
+    at -inf the records are the reference's pairs of defined kinship, each within tolerance,
+    and the host matrix thresholded; the rungs the GPU test climbs."""
+    for block in pc.LADDER_BLOCKS:
+        case = pc.ladder_case(d, block)
+        got, count = host_records(case, -rc.INF)
+        assert count == got.shape[0]
+        rc.check_records_reference(pc.reference(case), block, got, case.name, "host twin")
+        rc.same_records(got, rc.threshold_matrix(host_matrix(case), block, -rc.INF))
+
+
 @pytest.mark.parametrize("case", rc.CASES, ids=lambda c: c.name)
 def test_gap_thresholds_equal_the_float64_reference(case):
     ref = pc.reference(case)
