@@ -28,5 +28,7 @@ from .roh import (ROH_SAMPLE_DTYPE, ROHSamples, roh_segments_host,  # noqa: F401
                   roh_segments_raw_host)
 from .mendel import (MENDEL_TRIO_DTYPE, NO_PARENT, MendelErrors, candidate_trios,  # noqa: F401
                      mendel_errors_host, mendel_errors_raw_host, trios_from_parents)
+from .pihat import (PiHatModel, PiHatRecords, pi_hat_model_host,  # noqa: F401
+                    pi_hat_of_records, pi_hat_records_device, pi_hat_records_host)
 
 __version__ = "0.1.0"

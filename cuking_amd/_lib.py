@@ -38,6 +38,8 @@ PCRELATE_K0_SWITCH =0.17677669529663689   # (rounded to float32 where it is comp
 
 IBD_MIN_SITES = 64
 
+PIHAT_UNBOUNDED = 1
+
 
 class CKinBins(C.Structure):
     """cuking_kin_bins: the histogram of a kinship summary."""
@@ -47,6 +49,12 @@ class CKinBins(C.Structure):
 class CSiteFilter(C.Structure):
     """cuking_site_filter: the thresholds of the site rule."""
     _fields_ = [("min_call_rate", C.c_float), ("min_maf", C.c_float), ("min_mac", C.c_uint32)]
+
+
+class CPihatModel(C.Structure):
+    """cuking_pihat_model: the expected IBS-state proportions of the PI_HAT estimate."""
+    _fields_ = [("e00", C.c_double), ("e01", C.c_double), ("e02", C.c_double),
+                ("e11", C.c_double), ("e12", C.c_double), ("sites_used", C.c_uint32)]
 
 
 class CukingError(RuntimeError):
@@ -213,6 +221,15 @@ SIGNATURES = {
     "cuking_mendel_site_counts": (_int, [_vp, _vp, _u64, _u32, _vp, _vp]),
     "cuking_hwe_sites_host": (_int, [_vp, _u32, _u32, _vp]),
     "cuking_hwe_sites": (_int, [_vp, _vp, _u32, _u32, _vp, _vp]),
+    "cuking_pihat_model_host": (_int, [_vp, _u32, C.POINTER(CPihatModel)]),
+    "cuking_pihat_records_host": (_int, [_vp, _u64, C.POINTER(CPihatModel), _u32, _vp]),
+    "cuking_compute_pihat_host": (_int, [_SM, _u32, _vp, C.POINTER(CPihatModel), _f32, _u32,
+                                         _u32, _vp, C.POINTER(_u32)]),
+    "cuking_compute_pihat": (_int, [_vp, _SM, _u32, _vp, C.POINTER(CPihatModel), _f32, _u32,
+                                    _u32, _vp, _vp, _vp, _vp]),
+    "cuking_compute_pihat_tiles": (_int, [_vp, _SM, _u32, _vp, _u64, _u64,
+                                          C.POINTER(CPihatModel), _f32, _u32, _u32, _vp, _vp,
+                                          _vp, _vp]),
     "cuking_sort_results": (None, [_vp, _sz]),
     "cuking_timing_enable": (_int, [_vp, _int]),
     "cuking_timing_reset": (_int, [_vp]),

@@ -1310,6 +1310,27 @@ class KingContext:
         return _ibd.ibd_scan_device(self, bits, words_per_sample, num_sites, group, pos,
                                     min_sites, min_length, min_total, block, max_records, stream)
 
+    def pi_hat_records(self, sm: Submatrix, words_per_sample: int, bits, num_sites: int,
+                       min_pi_hat: float = 2 * KING_CUTOFFS[0], counts=None, model=None,
+                       bounded: bool = True, max_results=None, stream=None):
+        """PI_HAT for every pair of a block (cuking_compute_pihat; include/cuking_amd.h "PI_HAT
+        (PLINK --genome)" has the definition): the method-of-moments IBD estimate of PLINK
+        ``--genome`` / ``hl.identity_by_descent``, decided on the matrix cores for every pair
+        and returned as a ``PiHatRecords`` of the pairs with ``(float32)pi_hat > min_pi_hat``
+        (default: the third-degree KING cut-off doubled, a convention).  ``counts``: the
+        ``site_counts`` tensor or array of the rows the allele frequencies come from (founders,
+        an unrelated set); by default the block's own stored samples.  ``model``: an earlier
+        call's or ``pi_hat_model_host``'s instead -- the blocks of a split cohort must share
+        one.  ``bounded=False`` skips the bounding of z0, z1, z2.  Without ``max_results`` the
+        buffer is 16 records per sample of the block, grown once to the exact count; with it an
+        overflow raises ``ResourceExhaustedError`` whose ``num_records`` is the exact count, and
+        ``max_results=0`` counts.  Contexts of the tiled kernel with variant 5, 6 or 7 only.
+        PI_HAT assumes one homogeneous population.  Waits for the device."""
+        from . import pihat as _pihat
+        return _pihat.pi_hat_records_device(self, sm, words_per_sample, bits, num_sites,
+                                            min_pi_hat, counts, model, bounded, max_results,
+                                            stream)
+
     def roh_segments_raw(self, bits, words_per_sample: int, num_sites: int, samples=None,
                          group=None, pos=None, min_sites: int = 512, min_length: int = 0,
                          bridge_sites: int = 0, segments: bool = False, max_segments=None,

@@ -206,7 +206,7 @@ def check_mfma_loops(asm_path: Path, verbose: bool = False):
     import re
 
     def label(f):
-        # (KIN is an int: 0 records, 1 dense matrix, 2 summary, 3 relative counts)
+        # (KIN is an int: 0 records, 1 dense matrix, 2 summary, 3 relative counts, 4 PI_HAT)
         m = re.match(r"_ZN6cuking12_GLOBAL__N_116king_mfma_kernelILb(\d)ELb(\d)ELb(\d)ELi(\d)E", f)
         return (f"king_mfma_kernel<FULL={m.group(1)}, SPLIT={m.group(2)}, N4={m.group(3)}, "
                 f"KIN={m.group(4)}>")

@@ -562,6 +562,9 @@ struct Outputs {
   uint32_t *rel_counts;
   uint32_t rel_num;
   float rel_thr[CUKING_REL_THRESHOLDS_MAX];
+  // PI_HAT records (TiledArgs::pihat): the full form with the PI_HAT decision; the call's
+  // kin_threshold is 0 (every tile, no filter)
+  PihatArgs pihat;
 };
 cuking_status launch_args(cuking_ctx *ctx, hipStream_t stream, const cuking_submatrix &sm,
                           uint32_t words_per_sample, const uint64_t *d_bit_sets,
@@ -597,6 +600,7 @@ cuking_status launch_args(cuking_ctx *ctx, hipStream_t stream, const cuking_subm
     a.rel_num = out.rel_num;
     for (uint32_t t = 0; t < out.rel_num; ++t) a.rel_thr[t] = out.rel_thr[t];
   }
+  a.pihat = out.pihat;
   a.rect_row_stride = 1;
   a.bits = d_bit_sets;
   a.words_per_sample = words_per_sample;
@@ -1008,8 +1012,15 @@ cuking_status run_tiled(cuking_ctx *ctx, const cuking_submatrix &sm,
   if (rel && !is_mfma_variant(kv))
     return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "relative counts: no matrix-core kernel");
   const bool kin_mfma = (kin || sum) && is_mfma_variant(kv);
-  const bool full = !kin_mfma && !rel &&
-                    use_full_counts(ctx, kin_threshold, out.counts != nullptr || kin, words_per_sample);
+  // PI_HAT records: the full form (five sums of every pair: the route of cuking_compute_counts
+  // and of a thresholded call at a non-positive threshold) of the matrix-core kernels with a
+  // PI_HAT epilogue; no filter, whose bound is one on KING kinship.
+  const bool pihat = out.pihat.on != 0;
+  if (pihat && !is_mfma_variant(kv))
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "pi_hat: no matrix-core kernel");
+  const bool full = pihat ||
+                    (!kin_mfma && !rel &&
+                     use_full_counts(ctx, kin_threshold, out.counts != nullptr || kin, words_per_sample));
   const LaunchSwitches sw = launch_switches(ctx, words_per_sample, full, kin_threshold);
   // (where the filter runs the four-product kernel's codes may stay unconverted)
   cuking_status st = prepare(ctx, sm, words_per_sample, d_bit_sets, stream, &geo, &tiles,
@@ -2021,6 +2032,59 @@ cuking_status cuking_compute_relative_counts_tiles(cuking_ctx *ctx, const cuking
 }
 
 // ---- unrelated set and families from the records (king_unrelated.h, king_prune.hip) --------
+
+// What cuking_compute_pihat and cuking_compute_pihat_tiles share: the checks in front of anything
+// that touches a device, then the thresholded call's route at threshold 0 with the PI_HAT form.
+static cuking_status run_pihat(cuking_ctx *ctx, const cuking_submatrix *sm,
+                               uint32_t words_per_sample, const uint64_t *d_bit_sets, bool whole,
+                               uint64_t tile_begin, uint64_t tile_end,
+                               const cuking_pihat_model *model, float min_pi_hat, uint32_t flags,
+                               uint32_t max_results, cuking_result *d_results,
+                               uint32_t *d_result_index, uint32_t *d_result_overflow,
+                               void *stream) {
+  cuking_status st = check_compute_args(sm, words_per_sample, d_bit_sets);
+  if (st != CUKING_OK) return st;
+  st = cuking_check_pihat_args(model, flags);
+  if (st != CUKING_OK) return st;
+  if (!d_result_index || !d_result_overflow || (max_results && !d_results))
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "null result pointer");
+  st = check_reducing_args(ctx, sm, words_per_sample, !whole, tile_begin, tile_end, "pi_hat",
+                           "PI_HAT form");
+  if (st != CUKING_OK) return st;
+  if (sm_num_rows(*sm) == 0 || sm_num_cols(*sm) == 0) return CUKING_OK;
+  BIND_OR_RETURN(ctx);
+  Outputs out = {};
+  out.max_results = max_results;
+  out.results = d_results;
+  out.result_index = d_result_index;
+  out.result_overflow = d_result_overflow;
+  out.pihat = PihatArgs{model->e00, model->e01, model->e02, model->e11, model->e12,
+                        min_pi_hat,  flags,      1u};
+  return run_tiled(ctx, *sm, words_per_sample, d_bit_sets, tile_begin, tile_end, whole, 0.f, out,
+                   (hipStream_t)stream);
+}
+
+cuking_status cuking_compute_pihat(cuking_ctx *ctx, const cuking_submatrix *sm,
+                                   uint32_t words_per_sample, const uint64_t *d_bit_sets,
+                                   const cuking_pihat_model *model, float min_pi_hat,
+                                   uint32_t flags, uint32_t max_results, cuking_result *d_results,
+                                   uint32_t *d_result_index, uint32_t *d_result_overflow,
+                                   void *stream) {
+  return run_pihat(ctx, sm, words_per_sample, d_bit_sets, true, 0, 0, model, min_pi_hat, flags,
+                   max_results, d_results, d_result_index, d_result_overflow, stream);
+}
+
+cuking_status cuking_compute_pihat_tiles(cuking_ctx *ctx, const cuking_submatrix *sm,
+                                         uint32_t words_per_sample, const uint64_t *d_bit_sets,
+                                         uint64_t tile_begin, uint64_t tile_end,
+                                         const cuking_pihat_model *model, float min_pi_hat,
+                                         uint32_t flags, uint32_t max_results,
+                                         cuking_result *d_results, uint32_t *d_result_index,
+                                         uint32_t *d_result_overflow, void *stream) {
+  return run_pihat(ctx, sm, words_per_sample, d_bit_sets, false, tile_begin, tile_end, model,
+                   min_pi_hat, flags, max_results, d_results, d_result_index, d_result_overflow,
+                   stream);
+}
 
 cuking_status cuking_unrelated_set(cuking_ctx *ctx, const cuking_result *d_records,
                                    uint64_t num_records, uint32_t num_samples,

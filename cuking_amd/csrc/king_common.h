@@ -122,6 +122,15 @@ struct TileSpace {
   }
 };
 
+// The PI_HAT form's share of the arguments (TiledArgs::pihat): the model of cuking_pihat_model,
+// the threshold and the flags of the call.
+struct PihatArgs {
+  double e00, e01, e02, e11, e12;
+  float min_pi_hat;
+  uint32_t flags;
+  uint32_t on;
+};
+
 // Arguments of the tiled pair kernel: what the device reads, nothing else.  The context's
 // switches travel beside it (LaunchSwitches, king_launch_plan.h); the launchers turn them
 // into plans and fill the launch's fields here from those.
@@ -312,6 +321,12 @@ struct TiledArgs {
   //  0: launch_filter turns that rotation off.  "filter_site_order" 2, and -1 by
   //  kSiteOrderAutoLap below)
   uint32_t site_lap;
+  // PI_HAT records (cuking_compute_pihat; again at the END): pihat.on != 0 = the matrix-core
+  // kernels' full form with the PI_HAT epilogue (king_mfma.hip emit_pihat_records,
+  // instantiations of their own): a pair is appended iff pihat_of_counts() of its IBS counts
+  // (king_pihat.h; the model by value) > pihat.min_pi_hat, and the record's kin field holds that
+  // float.  kin_threshold is not read.
+  struct PihatArgs pihat;
 };
 
 // Prefix statistics: the k-steps (of 256 sites) a check may sit behind, as shares of the

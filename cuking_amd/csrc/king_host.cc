@@ -26,6 +26,7 @@
 #include "king_ld.h"
 #include "king_mendel.h"
 #include "king_pcrelate.h"
+#include "king_pihat.h"
 #include "king_unrelated.h"
 
 using namespace cuking;
@@ -1419,6 +1420,101 @@ cuking_status cuking_hwe_sites_host(const uint32_t *counts, uint32_t num_sites, 
     const uint32_t *c = counts + (uint64_t)s * 4;
     p[s] = hwe_exact_p(c[0], c[1], c[2], (flags & CUKING_HWE_MIDP) != 0);
   }
+  return CUKING_OK;
+}
+
+}  // extern "C"
+
+// ---- PI_HAT (PLINK --genome) -----------------------------------------------------------------
+cuking_status cuking_check_pihat_args(const cuking_pihat_model *model, uint32_t flags) {
+  if (flags & ~CUKING_PIHAT_UNBOUNDED)
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "pi_hat: unknown flags 0x%x", flags);
+  if (model == nullptr)
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "pi_hat: null model pointer");
+  return CUKING_OK;
+}
+
+extern "C" {
+
+// The sites one at a time, with the functions of king_pihat.h.
+cuking_status cuking_pihat_model_host(const uint32_t *counts, uint32_t num_sites,
+                                      cuking_pihat_model *model) {
+  if (model == nullptr)
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "pi_hat model: null model pointer");
+  if (num_sites != 0 && counts == nullptr)
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "pi_hat model: null counts pointer");
+  uint32_t bad = 0;
+  cuking_pihat_model m = {};
+  if (!pihat_model_of_counts(counts, num_sites, &m, &bad))
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT,
+                       "pi_hat model: site %u counts more than 2^24 people", bad);
+  *model = m;
+  return CUKING_OK;
+}
+
+cuking_status cuking_pihat_records_host(const cuking_result *records, uint64_t num_records,
+                                        const cuking_pihat_model *model, uint32_t flags,
+                                        double *out) {
+  const cuking_status st = cuking_check_pihat_args(model, flags);
+  if (st != CUKING_OK) return st;
+  if (num_records != 0 && (records == nullptr || out == nullptr))
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "pi_hat records: null pointer");
+  for (uint64_t k = 0; k < num_records; ++k)
+    pihat_z_of_counts(model->e00, model->e01, model->e02, model->e11, model->e12,
+                      records[k].ibs0, records[k].ibs1, records[k].ibs2,
+                      (flags & CUKING_PIHAT_UNBOUNDED) == 0, out + 4 * k);
+  return CUKING_OK;
+}
+
+// The pairs of the block in ascending (i, j), each counted with plain popcounts over the words
+// of the two samples (cuking.cu:216-240 for the sums; ibs0/1/2 as a KING record carries them).
+cuking_status cuking_compute_pihat_host(const cuking_submatrix *sm, uint32_t words_per_sample,
+                                        const uint64_t *bit_sets,
+                                        const cuking_pihat_model *model, float min_pi_hat,
+                                        uint32_t flags, uint32_t max_results,
+                                        cuking_result *results, uint32_t *num_results) {
+  if (num_results != nullptr) *num_results = 0;
+  cuking_status st = cuking_check_block(sm, words_per_sample);
+  if (st != CUKING_OK) return st;
+  st = cuking_check_pihat_args(model, flags);
+  if (st != CUKING_OK) return st;
+  if (num_results == nullptr || (max_results != 0 && results == nullptr))
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "pi_hat: null result pointer");
+  if (sm_num_rows(*sm) == 0 || sm_num_cols(*sm) == 0) return CUKING_OK;
+  if (bit_sets == nullptr)
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "pi_hat: null bitset pointer");
+  const bool diag = sm_is_diag(*sm);
+  const uint32_t plane_words = words_per_sample / 2;
+  uint64_t count = 0;
+  for (uint64_t i = sm->i_begin; i < sm->i_end; ++i) {
+    const uint64_t *si = bit_sets + (i - sm->i_begin) * words_per_sample;
+    for (uint64_t j = diag ? i + 1 : sm->j_begin; j < sm->j_end; ++j) {
+      const uint64_t stored_j = diag ? j - sm->j_begin : sm_num_rows(*sm) + (j - sm->j_begin);
+      const uint64_t *sj = bit_sets + stored_j * words_per_sample;
+      uint32_t ibs0 = 0, ibs2 = 0, shared = 0;
+      for (uint32_t w = 0; w < plane_words; ++w) {
+        const uint64_t hi = si[w], ai = si[plane_words + w];
+        const uint64_t hj = sj[w], aj = sj[plane_words + w];
+        const uint64_t ri = ~hi & ~ai, rj = ~hj & ~aj;
+        const uint64_t defined = ~(hi & ai) & ~(hj & aj);
+        ibs0 += (uint32_t)__builtin_popcountll(((ri & aj) | (ai & rj)) & defined);
+        ibs2 += (uint32_t)__builtin_popcountll(((ri & rj) | (ai & aj) | (hi & hj)) & defined);
+        shared += (uint32_t)__builtin_popcountll(defined);
+      }
+      const uint32_t ibs1 = shared - ibs0 - ibs2;
+      const float pi_hat = pihat_of_counts(model->e00, model->e01, model->e02, model->e11,
+                                           model->e12, ibs0, ibs1, ibs2, flags);
+      if (!(pi_hat > min_pi_hat)) continue;
+      if (count < max_results)
+        results[count] = cuking_result{(uint32_t)i, (uint32_t)j, pi_hat, ibs0, ibs1, ibs2};
+      ++count;
+    }
+  }
+  *num_results = (uint32_t)(count > 0xFFFFFFFFull ? 0xFFFFFFFFull : count);
+  if (count > max_results)
+    return cuking_fail(CUKING_ERR_RESOURCE_EXHAUSTED,
+                       "pi_hat: %llu records do not fit %u: retry with that many",
+                       (unsigned long long)count, max_results);
   return CUKING_OK;
 }
 

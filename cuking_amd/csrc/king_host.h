@@ -113,5 +113,7 @@ cuking_status cuking_check_mendel_site_args(const void *error_bits, uint64_t num
 // "Hardy-Weinberg test" lists them); OK says nothing about there being work to do.
 cuking_status cuking_check_hwe_args(const void *counts, uint32_t num_sites, uint32_t flags,
                                     const void *p);
+// What the PI_HAT calls (include/cuking_amd.h "PI_HAT") check of model and flags.
+cuking_status cuking_check_pihat_args(const cuking_pihat_model *model, uint32_t flags);
 
 #endif  // CUKING_AMD_KING_HOST_H_

@@ -41,7 +41,8 @@
 //     five_product_loop  the k loop on the quad layout                           (!N4)
 //     four_product_loop  the k loop on the nibble layout                         (N4)
 //     reduce_parts       park and sum the parts of a cut-up tile                 (SPLIT)
-//     emit_full_records  two-sweep reservation and store         (FULL, no dense_counts)
+//     emit_full_records  two-sweep reservation and store         (FULL, no dense_counts;
+//                        KIN = PI_HAT: decision and record of king_pihat.h, out of line)
 //     store_counts       the six counts of every pair            (FULL, dense_counts)
 //     store_kin          float32 kinship of every pair                    (KIN = matrix)
 //     summarise_kin      histogram and nearest-relative keys of a tile    (KIN = summary)
@@ -54,6 +55,7 @@
 #include "king_common.h"
 #include "king_device.h"
 #include "king_kin_summary.h"
+#include "king_pihat.h"
 
 // The LDS-DMA statements below write M0 and say so in their clobber lists; the
 // compiler notes that it keeps no value of its own there (M0 is reserved).
@@ -196,6 +198,43 @@ __device__ __attribute__((noinline)) void full_store_call(
   rec.ibs0 = opp;
   rec.ibs1 = shared - opp - ibs2;
   rec.ibs2 = ibs2;
+  c.results[slot] = rec;
+}
+
+// PI_HAT form: the decision and the record, both out of line -- the fp64 pair math of
+// king_pihat.h (divides included) is a few hundred instructions, and the kernel around the
+// calls has no registers to spare.  ibs0/1/2 from the five sums as full_store_call has them.
+struct PihatPair {
+  uint32_t ibs0, ibs1, ibs2;
+};
+__device__ __forceinline__ PihatPair pihat_pair(uint32_t het_i, uint32_t het_j, uint32_t both_het,
+                                                uint32_t opp, uint32_t hom_hom) {
+  const uint32_t ibs2 = hom_hom - opp + both_het;
+  const uint32_t shared = het_i + het_j - both_het + hom_hom;
+  return PihatPair{opp, shared - opp - ibs2, ibs2};
+}
+__device__ __attribute__((noinline)) bool pihat_decide_call(const PihatArgs p, uint32_t het_i,
+                                                            uint32_t het_j, uint32_t both_het,
+                                                            uint32_t opp, uint32_t hom_hom) {
+  const PihatPair c = pihat_pair(het_i, het_j, both_het, opp, hom_hom);
+  return pihat_of_counts(p.e00, p.e01, p.e02, p.e11, p.e12, c.ibs0, c.ibs1, c.ibs2, p.flags) >
+         p.min_pi_hat;
+}
+template <class Ctx>
+__device__ __attribute__((noinline)) void pihat_store_call(
+    const Ctx c, const PihatArgs p, uint32_t slot, uint32_t li, uint32_t lj, uint32_t het_i,
+    uint32_t het_j, uint32_t both_het, uint32_t opp, uint32_t hom_hom) {
+  if (slot >= c.max_results) {
+    atomicMax(c.result_overflow, 1u);
+    return;
+  }
+  const PihatPair n = pihat_pair(het_i, het_j, both_het, opp, hom_hom);
+  cuking_result rec;
+  record_pair(c, stored_row(c, li), stored_col(c, lj), &rec.sample_i, &rec.sample_j);
+  rec.kin = pihat_of_counts(p.e00, p.e01, p.e02, p.e11, p.e12, n.ibs0, n.ibs1, n.ibs2, p.flags);
+  rec.ibs0 = n.ibs0;
+  rec.ibs1 = n.ibs1;
+  rec.ibs2 = n.ibs2;
   c.results[slot] = rec;
 }
 
@@ -1262,12 +1301,16 @@ __device__ __forceinline__ void pair_sums(const v16f (&acc)[2][2][kNQ], const v1
 // lane).  The decisions of sweep 0 are kept, one bit per pair.
 // The fifth sum stays where the pass in front of the main loop parked it (five products:
 // this lane's 16-byte slots `park`) and is read block by block.
-template <bool N4>
+// PIHAT (KIN = kPiHat): the same two sweeps with the PI_HAT decision and record
+// (pihat_decide_call(), pihat_store_call(): TiledArgs::pihat instead of kin_threshold).
+template <bool N4, bool PIHAT = false>
 __device__ __forceinline__ void emit_full_records(const TiledArgs &a, const Segment &s,
                                                   const Lanes &l, const float4 *const park,
                                                   const v16f (&acc)[2][2][kNQ],
                                                   const v16f (&hh5)[2][2]) {
   const auto emit_ctx = emit_ctx_of<N4>(a);
+  PihatArgs pihat = {};
+  if constexpr (PIHAT) pihat = a.pihat;
   uint32_t total = 0, base = 0, run = 0;  // wave-uniform
   uint32_t decided[2 * 2] = {};           // bit r of word (bi, bj)
 #pragma nounroll
@@ -1288,8 +1331,11 @@ __device__ __forceinline__ void emit_full_records(const TiledArgs &a, const Segm
             uint32_t het_i, het_j, both_het, opp, hom_hom;
             pair_sums<N4>(acc, hh5, bi, bj, r, hh[r1], &het_i, &het_j, &both_het, &opp, &hom_hom);
             if (pass == 0) {
-              const bool emit = pair_valid(a, li, lj) &&
-                                king_kinship(het_i, het_j, both_het, opp) > a.kin_threshold;
+              bool emit = pair_valid(a, li, lj);
+              if constexpr (PIHAT)
+                emit = emit && pihat_decide_call(pihat, het_i, het_j, both_het, opp, hom_hom);
+              else
+                emit = emit && king_kinship(het_i, het_j, both_het, opp) > a.kin_threshold;
               decided[bi * 2 + bj] |= (emit ? 1u : 0u) << r;
             } else {
               const bool emit = (decided[bi * 2 + bj] >> r) & 1u;
@@ -1299,8 +1345,14 @@ __device__ __forceinline__ void emit_full_records(const TiledArgs &a, const Segm
                     (uint32_t)(b >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b, 0u));
                 const uint32_t slot = base + run + before;
                 run += (uint32_t)__popcll(b);
-                if (emit)
-                  full_store_call(emit_ctx, slot, li, lj, het_i, het_j, both_het, opp, hom_hom);
+                if constexpr (PIHAT) {
+                  if (emit)
+                    pihat_store_call(emit_ctx, pihat, slot, li, lj, het_i, het_j, both_het, opp,
+                                     hom_hom);
+                } else {
+                  if (emit)
+                    full_store_call(emit_ctx, slot, li, lj, het_i, het_j, both_het, opp, hom_hom);
+                }
               }
             }
           }
@@ -1563,10 +1615,13 @@ __device__ __forceinline__ void count_relatives(const TiledArgs &a, const Segmen
 // bitsets from 2^22 sites on.
 // The driver: take work -> per segment: hom_hom pass (FULL) -> k loop -> reduce parts
 // (SPLIT, a partial tile) -> epilogue.
-constexpr int kRecords = 0, kKinMatrix = 1, kKinSummary = 2, kRelCounts = 3;  // KIN
+// kPiHat: the PI_HAT record form (TiledArgs::pihat), the only kind besides kRecords with FULL
+// -- and with FULL only: the full form's two passes and an epilogue that decides on PI_HAT.
+constexpr int kRecords = 0, kKinMatrix = 1, kKinSummary = 2, kRelCounts = 3, kPiHat = 4;  // KIN
 template <bool FULL, bool SPLIT, bool N4 = false, int KIN = kRecords>
 __global__ __launch_bounds__(256, 1) void king_mfma_kernel(const TiledArgs a) {
-  static_assert(KIN == kRecords || !FULL, "the dense-kinship forms are lean ones");
+  static_assert(KIN == kRecords || (KIN == kPiHat ? FULL : !FULL),
+                "the dense-kinship forms are lean ones, the PI_HAT form is a full one");
   extern __shared__ uint4 lds[];  // [NSTAGE][side][k-group][plane | slice][128]
   Work work;
   if (!take_work<SPLIT>(a, lds, &work)) return;  // uniform
@@ -1590,7 +1645,9 @@ __global__ __launch_bounds__(256, 1) void king_mfma_kernel(const TiledArgs a) {
         !reduce_parts<FULL, N4>(a, work.piece, s, l, lds, park, acc, hh5))
       continue;
 
-    if constexpr (FULL) {
+    if constexpr (KIN == kPiHat) {
+      emit_full_records<N4, true>(a, s, l, park, acc, hh5);
+    } else if constexpr (FULL) {
       if (a.dense_counts == nullptr) emit_full_records<N4>(a, s, l, park, acc, hh5);
       else store_counts<N4>(a, s, l, park, acc, hh5);
     } else if constexpr (KIN == kKinMatrix) {
@@ -1659,14 +1716,15 @@ size_t mfma_split_counter_bytes(uint32_t wgs) { return split_counter_bytes(wgs);
 
 namespace {
 // launch_shape<FULL, SPLIT, N4, KIN> by run-time flags (kin: kKinMatrix / kKinSummary /
-// kRelCounts, which are lean)
+// kRelCounts, which are lean; kPiHat, which is full)
 hipError_t launch_form(bool full, bool split, bool nibble, int kin, const TiledArgs &a,
                        const LaunchSwitches &sw, uint64_t blocks, uint32_t lds_bytes,
                        hipStream_t stream) {
-  if (kin < kRecords || kin > kRelCounts || (kin != kRecords && full)) return hipErrorInvalidValue;
+  if (kin < kRecords || kin > kPiHat || (kin != kRecords && full != (kin == kPiHat)))
+    return hipErrorInvalidValue;
   using Launch = hipError_t (*)(const TiledArgs &, const LaunchSwitches &, uint64_t, uint32_t,
                                 hipStream_t);
-  static constexpr Launch kForms[4][2][2][2] = {  // [kin][nibble][split][full]
+  static constexpr Launch kForms[5][2][2][2] = {  // [kin][nibble][split][full]
       {{{launch_shape<false, false, false>, launch_shape<true, false, false>},
         {launch_shape<false, true, false>, launch_shape<true, true, false>}},
        {{launch_shape<false, false, true>, launch_shape<true, false, true>},
@@ -1682,7 +1740,11 @@ hipError_t launch_form(bool full, bool split, bool nibble, int kin, const TiledA
       {{{launch_shape<false, false, false, kRelCounts>, nullptr},
         {launch_shape<false, true, false, kRelCounts>, nullptr}},
        {{launch_shape<false, false, true, kRelCounts>, nullptr},
-        {launch_shape<false, true, true, kRelCounts>, nullptr}}}};
+        {launch_shape<false, true, true, kRelCounts>, nullptr}}},
+      {{{nullptr, launch_shape<true, false, false, kPiHat>},
+        {nullptr, launch_shape<true, true, false, kPiHat>}},
+       {{nullptr, launch_shape<true, false, true, kPiHat>},
+        {nullptr, launch_shape<true, true, true, kPiHat>}}}};
   return kForms[kin][nibble][split][full](a, sw, blocks, lds_bytes, stream);
 }
 
@@ -1692,6 +1754,8 @@ hipError_t launch_form(bool full, bool split, bool nibble, int kin, const TiledA
 // The form a thresholded launch runs: records, or (TiledArgs::rel_counts) relative counts --
 // chosen here, on the host.
 int lean_form_of(const TiledArgs &a) { return a.rel_counts != nullptr ? kRelCounts : kRecords; }
+// ... and a planned one: the PI_HAT form (TiledArgs::pihat) is the full form's.
+int planned_form_of(const TiledArgs &a) { return a.pihat.on != 0 ? kPiHat : lean_form_of(a); }
 bool rel_args_ok(const TiledArgs &a) {
   return a.rel_counts == nullptr || (a.rel_num >= 1 && a.rel_num <= CUKING_REL_THRESHOLDS_MAX);
 }
@@ -1762,7 +1826,10 @@ hipError_t launch_mfma(bool full, bool nibble, const TiledArgs &args, const Laun
                        uint64_t num_tiles, uint32_t lds_bytes, hipStream_t stream) {
   // (a relative-counts call, TiledArgs::rel_counts: the counting form, lean only)
   if (!rel_args_ok(args)) return hipErrorInvalidValue;
-  return launch_planned_form(full, nibble, lean_form_of(args), args, sw, num_tiles, lds_bytes,
+  // (a PI_HAT call, TiledArgs::pihat: the full form only, and neither counts nor a matrix)
+  if (args.pihat.on != 0 && (!full || args.rel_counts != nullptr || args.dense_counts != nullptr))
+    return hipErrorInvalidValue;
+  return launch_planned_form(full, nibble, planned_form_of(args), args, sw, num_tiles, lds_bytes,
                              stream);
 }
 

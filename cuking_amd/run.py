@@ -257,6 +257,18 @@ def parse_args(argv=None):
     flag("mendel-site-counts", action="store_true",
          help="--mendel-uri also writes site_errors, the number of listed trios with an error "
               "at each site, and site_index, the sites' numbers among the input's sites")
+    flag("pihat-uri", default="",
+         help="also scan ALL pairs of the cohort for PI_HAT, the method-of-moments IBD estimate "
+              "of PLINK --genome / hl.identity_by_descent (allele frequencies of the cohort's "
+              "own samples, after site QC and LD pruning), and write the pairs with PI_HAT above "
+              "--pihat-min to this .npz: sample_i, sample_j, pi_hat, z0, z1, z2, ibs0, ibs1, "
+              "ibs2 sorted by pair, samples, the model, min_pi_hat, num_records.  Assumes one "
+              "homogeneous population.  One process and --split-factor 1 only")
+    flag("pihat-min", type=float, default=None,
+         help="the threshold of --pihat-uri: pairs with a PI_HAT strictly above it (default "
+              "0.0884, the third-degree kinship cut-off doubled)")
+    flag("pihat-unbounded", action="store_true",
+         help="--pihat-uri without the bounding of z0, z1, z2 to [0, 1]")
     flag("pcrelate-min-kinship", type=float, default=None,
          help="the threshold of --pcrelate-records-uri: pairs with a kinship strictly above it "
               "(default 0.0442, the third-degree cut-off)")
@@ -484,6 +496,17 @@ def validate(args):  # cuking.cu:437-462
         if not args.mendel_trios and not args.bed_uri:
             raise UsageError("--mendel_uri needs --mendel_trios: only the .fam under --bed_uri "
                              "declares parents")
+    if (args.pihat_min is not None or args.pihat_unbounded) and not args.pihat_uri:
+        raise UsageError("--pihat_min and --pihat_unbounded need --pihat_uri")
+    if args.pihat_uri:
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            raise UsageError("--pihat_uri needs one process (one GPU): the scan is not split "
+                             "across ranks yet")
+        if args.split_factor != 1:
+            raise UsageError("--pihat_uri needs --split_factor 1: it scans the whole cohort's "
+                             "pairs")
+        if args.pihat_min is not None and args.pihat_min != args.pihat_min:
+            raise UsageError("--pihat_min must not be NaN")
     if args.pcrelate_min_kinship is not None and not args.pcrelate_records_uri:
         raise UsageError("--pcrelate_min_kinship needs --pcrelate_records_uri")
     if args.pcrelate_records_uri:
@@ -797,6 +820,26 @@ def write_pcrelate_records(path: Path, ctx, bits, wps: int, num_sites: int, pca,
                  kin_pairs=got.kin, relationship=got.relationship(),
                  samples=np.array(list(sample_ids), dtype=str),
                  min_kinship=np.float32(found.min_kinship),
+                 num_records=np.int64(found.num_records))
+
+
+def write_pihat(path: Path, ctx, sm, bits, wps: int, num_sites: int, min_pi_hat: float,
+                bounded: bool, sample_ids) -> None:
+    """The pairs of the whole cohort whose PI_HAT is above `min_pi_hat` as an .npz: `sample_i`,
+    `sample_j`, `pi_hat` (float32, the records' value), `z0`, `z1`, `z2` (float64), `ibs0`,
+    `ibs1`, `ibs2` sorted by (sample_i, sample_j); `samples`; the model (`model`: e00, e01, e02,
+    e11, e12; `sites_used`) of the cohort's own samples; `min_pi_hat`, `bounded`,
+    `num_records`."""
+    found = ctx.pi_hat_records(sm, wps, bits, num_sites, min_pi_hat, bounded=bounded)
+    rows, z = found.sorted(), found.z()
+    path.parent.mkdir(parents=True, exist_ok=True)
+    with open(path, "wb") as f:   # (np.savez would append .npz to another suffix)
+        np.savez(f, sample_i=rows["sample_i"], sample_j=rows["sample_j"], pi_hat=rows["kin"],
+                 z0=z[:, 0], z1=z[:, 1], z2=z[:, 2], ibs0=rows["ibs0"], ibs1=rows["ibs1"],
+                 ibs2=rows["ibs2"], samples=np.array(list(sample_ids), dtype=str),
+                 model=np.array(found.model.as_tuple()[:5], dtype=np.float64),
+                 sites_used=np.int64(found.model.sites_used),
+                 min_pi_hat=np.float32(found.min_pi_hat), bounded=np.bool_(found.bounded),
                  num_records=np.int64(found.num_records))
 
 
@@ -1186,6 +1229,11 @@ def main(argv=None) -> int:
             if counts_path is not None:
                 write_relative_counts(counts_path, ctx, sm, wps, bits,
                                       relative_thresholds(args.relative_thresholds), sample_ids)
+            if args.pihat_uri:
+                write_pihat(resolve_uri(args.pihat_uri), ctx, sm, bits, wps, num_sites,
+                            cuking_amd.pihat.DEFAULT_MIN_PI_HAT if args.pihat_min is None
+                            else args.pihat_min,
+                            not args.pihat_unbounded, sample_ids)
             unrelated_keep = None
             if unrelated_path is not None:
                 unrelated_keep = write_unrelated(unrelated_path, ctx, recs, sample_ids,

@@ -1533,6 +1533,94 @@ cuking_status cuking_hwe_sites_host(const uint32_t *counts, uint32_t num_sites, 
 cuking_status cuking_hwe_sites(cuking_ctx *ctx, const uint32_t *d_counts, uint32_t num_sites,
                                uint32_t flags, double *d_p, void *stream);
 
+/* PI_HAT (PLINK --genome): the method-of-moments IBD estimate of PLINK --genome and
+ * hl.identity_by_descent -- Z0, Z1, Z2 and PI_HAT of a pair from its IBS0/1/2 counts and the
+ * cohort's allele frequencies -- and a scan of a block that decides on PI_HAT instead of on KING
+ * kinship.  csrc/king_pihat.h holds the definition below as code, shared by kernel, host twins
+ * and tests; only *, /, +, - and comparisons on IEEE doubles in ONE written order with no
+ * contraction, so host, device and a restatement in any language with doubles agree bit for bit.
+ *
+ * Model, from the count rows of cuking_site_counts (hom_ref = r, het = h, hom_var = v of the rows
+ * the frequencies come from: founders, an unrelated set, or the cohort itself): n = r + h + v,
+ * x = h + 2 v, y = h + 2 r, N = x + y.  F(a, k) = a (a - 1) ... (a - k + 1), multiplied left to
+ * right, 0 as soon as a factor is 0.  A site is used iff n >= 2; its terms are the probabilities
+ * of drawing the alleles of two people without replacement (PLINK's finite-sample corrections):
+ *     a00 = (2 (F(x,2) F(y,2))) / F(N,4)
+ *     a01 = (4 (F(x,3) F(y,1) + F(x,1) F(y,3))) / F(N,4)
+ *     a02 = ((F(x,4) + F(y,4)) + 4 (F(x,2) F(y,2))) / F(N,4)
+ *     a11 = (2 (F(x,2) F(y,1) + F(x,1) F(y,2))) / F(N,3)
+ *     a12 = (((F(x,3) + F(y,3)) + F(x,2) F(y,1)) + F(x,1) F(y,2)) / F(N,3)
+ * (a00 + a01 + a02 = 1 and a11 + a12 = 1 in exact arithmetic), and E_uv = (the sum of a_uv over
+ * the used sites, in site order) / sites_used.  With no used site the model holds NaNs and no
+ * pair qualifies.  A row with more than 2^24 people fails the call.
+ *
+ * Pair, with S = ibs0 + ibs1 + ibs2 as doubles:
+ *     z0 = ibs0 / (e00 S)
+ *     z1 = (ibs1 - z0 (e01 S)) / (e11 S)
+ *     z2 = ((ibs2 - z0 (e02 S)) - z1 (e12 S)) / S
+ * Bounded (the default: PLINK without --nudge, Hail's bounded=True), in this order: z0 > 1 ->
+ * (1, 0, 0); z1 > 1 -> (0, 1, 0); z2 > 1 -> (0, 0, 1); z0 < 0 -> z0 = 0 and z1, z2 divided by
+ * z1 + z2; z1 < 0 -> z1 = 0 and z0, z2 divided by z0 + z2; z2 < 0 -> z2 = 0 and z0, z1 divided by
+ * z0 + z1.  CUKING_PIHAT_UNBOUNDED skips the bounding.  pi_hat = z1 / 2 + z2.  A record's `kin`
+ * field holds (float)pi_hat, and a pair qualifies iff (float)pi_hat > min_pi_hat: the strict
+ * float32 comparison of every record of this library, false for NaN.  Where this text and PLINK
+ * or Hail differ at an edge (n < 2; S = 0 or a zero expectation, which take whatever IEEE gives),
+ * this text is the contract; no test compares with a PLINK binary.
+ *
+ * cuking_pihat_model_host: counts uint32 [num_sites][4] (hom_ref, het, hom_var, missing --
+ * ignored), O(sites), on the host like cuking_site_mask_host.  INVALID_ARGUMENT: a null model,
+ * with num_sites != 0 null counts, a row of more than 2^24 people.
+ *
+ * cuking_pihat_records_host: out[k] = z0, z1, z2, pi_hat (doubles) of records[k]'s ibs0/1/2, for
+ * ANY record buffer on the host -- the buffer of cuking_compute_king as well.
+ *
+ * cuking_compute_pihat / _tiles: block, layout, tile ranges, counter and overflow flag exactly
+ * those of cuking_compute_king: *d_result_index ends as the number of qualifying pairs whatever
+ * max_results is, nothing is written past the buffer (the overflow flag is set instead),
+ * max_results = 0 only counts.  Records: sample_i < sample_j, kin = (float)pi_hat, ibs0/1/2 bit
+ * for bit those of a KING record of the pair; device order unspecified (the set is the contract;
+ * cuking_sort_results, cuking_unrelated_set, cuking_pcrelate_pairs, cuking_ibd_pairs take the
+ * buffer as it is).  The matrix-core kernels' full form with a PI_HAT epilogue (king_mfma.hip),
+ * on every tile -- the filter's bound is one on KING kinship and does not apply.  Served by
+ * contexts of the tiled kernel with variant 5, 6 or 7 and bitsets below 2^24 sites; every other
+ * context is refused with INVALID_ARGUMENT, as are a null model, unknown flag bits and the null
+ * pointers cuking_compute_king refuses.  min_pi_hat may be anything (NaN: no pair).
+ * cuking_compute_pihat_host: the same records from host memory in ascending (i, j), plain
+ * popcounts per pair; *num_results is the count, RESOURCE_EXHAUSTED when it exceeds max_results.
+ *
+ * PI_HAT assumes ONE homogeneous population: shared ancestry reads as relatedness (that is what
+ * PC-Relate is for).  Out of scope: a dense PI_HAT matrix; --nudge; Hail's maf= field (pass
+ * counts); per-pair missingness-specific expectations; DST, PPC and RATIO; the C++ `cuking`
+ * binary; several ranks; the VALU and stream kernels. */
+#define CUKING_PIHAT_UNBOUNDED 1u
+typedef struct cuking_pihat_model {
+  double e00, e01, e02, e11, e12;
+  uint32_t sites_used;
+} cuking_pihat_model;
+cuking_status cuking_pihat_model_host(const uint32_t *counts, uint32_t num_sites,
+                                      cuking_pihat_model *model);
+cuking_status cuking_pihat_records_host(const cuking_result *records, uint64_t num_records,
+                                        const cuking_pihat_model *model, uint32_t flags,
+                                        double *out /* [num_records][4] */);
+cuking_status cuking_compute_pihat_host(const cuking_submatrix *sm, uint32_t words_per_sample,
+                                        const uint64_t *bit_sets,
+                                        const cuking_pihat_model *model, float min_pi_hat,
+                                        uint32_t flags, uint32_t max_results,
+                                        cuking_result *results, uint32_t *num_results);
+cuking_status cuking_compute_pihat(cuking_ctx *ctx, const cuking_submatrix *sm,
+                                   uint32_t words_per_sample, const uint64_t *d_bit_sets,
+                                   const cuking_pihat_model *model, float min_pi_hat,
+                                   uint32_t flags, uint32_t max_results, cuking_result *d_results,
+                                   uint32_t *d_result_index, uint32_t *d_result_overflow,
+                                   void *stream);
+cuking_status cuking_compute_pihat_tiles(cuking_ctx *ctx, const cuking_submatrix *sm,
+                                         uint32_t words_per_sample, const uint64_t *d_bit_sets,
+                                         uint64_t tile_begin, uint64_t tile_end,
+                                         const cuking_pihat_model *model, float min_pi_hat,
+                                         uint32_t flags, uint32_t max_results,
+                                         cuking_result *d_results, uint32_t *d_result_index,
+                                         uint32_t *d_result_overflow, void *stream);
+
 /* cuking.cu:761-765 on host memory: sort by (sample_i, sample_j, kin). */
 void cuking_sort_results(cuking_result *results, size_t num_results);
 
