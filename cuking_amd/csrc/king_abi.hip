@@ -292,9 +292,8 @@ TiledVariant plan_variant(const cuking_ctx *ctx, uint32_t words_per_sample) {
 // choice is lean iff kin_threshold > c / sqrt(sites) with c = 1.6 (VALU) or
 // 2.05 (matrix cores: break-even near 0.4 % of the pairs emitted).  Either
 // form gives the same records.
-bool use_full_counts(const cuking_ctx *ctx, float kin_threshold, bool dense,
-                     uint32_t words_per_sample) {
-  if (dense || ctx->counts_mode == 1) return true;
+bool use_full_counts(const cuking_ctx *ctx, float kin_threshold, uint32_t words_per_sample) {
+  if (ctx->counts_mode == 1) return true;
   if (ctx->counts_mode == 0) return false;
   if (!(kin_threshold > 0.0f)) return true;
   const double sites = 32.0 * words_per_sample;
@@ -520,15 +519,17 @@ cuking_status scratch_for(cuking_ctx *ctx, hipStream_t stream, uint64_t tiles,
 // The filter's bound applies to a call (it only helps the lean form with a threshold inside
 // (0, 1/2)): the filter kernel runs (LaunchSwitches::filter_runs), and the four-product
 // kernel's codes may stay unconverted.
-bool filter_runs(const cuking_ctx *ctx, uint32_t words_per_sample, bool full, float kin_threshold) {
-  return effective_variant(ctx, words_per_sample) == kMfmaFilterVariant && !full &&
+bool filter_runs(const cuking_ctx *ctx, uint32_t words_per_sample, CallForm form, bool full,
+                 float kin_threshold) {
+  return kCallForms[form].filter_may_run &&
+         effective_variant(ctx, words_per_sample) == kMfmaFilterVariant && !full &&
          kin_threshold > 0.f && kin_threshold < 0.5f;
 }
 
-// The context's switches for a call that runs the `full` or the lean form: built once per
-// call, in front of the conversion (which asks whether the filter runs).
-LaunchSwitches launch_switches(const cuking_ctx *ctx, uint32_t words_per_sample, bool full,
-                               float kin_threshold) {
+// The context's switches for a call of `form` that runs the `full` or the lean k loop: built
+// once per call, in front of the conversion (which asks whether the filter runs).
+LaunchSwitches launch_switches(const cuking_ctx *ctx, uint32_t words_per_sample, CallForm form,
+                               bool full, float kin_threshold) {
   LaunchSwitches sw;
   sw.xcd_swizzle = (uint32_t)ctx->xcd_swizzle;
   sw.dyn_tail_tiles = ctx->dyn_tail_tiles;
@@ -538,14 +539,18 @@ LaunchSwitches launch_switches(const cuking_ctx *ctx, uint32_t words_per_sample,
   sw.rotate = (uint32_t)ctx->filter_rotate;
   sw.rotate_min_tiles = ctx->filter_rotate_min_tiles;
   sw.split_min_steps = ctx->filter_split_min_steps;
-  sw.filter_runs = filter_runs(ctx, words_per_sample, full, kin_threshold);
+  sw.filter_runs = filter_runs(ctx, words_per_sample, form, full, kin_threshold);
+  sw.form = form;
   return sw;
 }
 
-// The device arguments of the pair kernels for the block `sm` of the prepared workspace
-// (geometry `geo`, enumeration `tiles`; the stream's filter scratch sized for
-// `block_tiles`).  Callers fill in the tile range.
+// What a pair call produces: its form (king_launch_plan.h), named by the entry point, the
+// threshold it runs at, and the outputs of that form (the others stay null).
 struct Outputs {
+  CallForm form;
+  // records: the call's; relative counts: rel_thr[0] (the filter's bound, the layout and the
+  // lean form's cheap test all follow the lowest threshold); every other form: 0
+  float kin_threshold;
   uint32_t max_results;
   cuking_result *results;
   uint32_t *result_index, *result_overflow;
@@ -557,20 +562,33 @@ struct Outputs {
   // kinship summary (TiledArgs::sum_hist / sum_best): every pair's kinship reduced, no records
   uint64_t *sum_hist, *sum_best;
   cuking_kin_bins sum_bins;
-  // relative counts (TiledArgs::rel_counts): the thresholded call without records; the
-  // call's kin_threshold is rel_thr[0]
+  // relative counts (TiledArgs::rel_counts): the thresholded call without records
   uint32_t *rel_counts;
   uint32_t rel_num;
   float rel_thr[CUKING_REL_THRESHOLDS_MAX];
-  // PI_HAT records (TiledArgs::pihat): the full form with the PI_HAT decision; the call's
-  // kin_threshold is 0 (every tile, no filter)
+  // PI_HAT records (TiledArgs::pihat): the full form with the PI_HAT decision
   PihatArgs pihat;
 };
+// A records call's, or with a PI_HAT decision a PI_HAT call's.
+Outputs record_outputs(CallForm form, float kin_threshold, uint32_t max_results,
+                       cuking_result *results, uint32_t *result_index,
+                       uint32_t *result_overflow) {
+  Outputs out = {};
+  out.form = form;
+  out.kin_threshold = kin_threshold;
+  out.max_results = max_results;
+  out.results = results;
+  out.result_index = result_index;
+  out.result_overflow = result_overflow;
+  return out;
+}
+// The device arguments of the pair kernels for the block `sm` of the prepared workspace
+// (geometry `geo`, enumeration `tiles`; the stream's filter scratch sized for
+// `block_tiles`).  Callers fill in the tile range.
 cuking_status launch_args(cuking_ctx *ctx, hipStream_t stream, const cuking_submatrix &sm,
                           uint32_t words_per_sample, const uint64_t *d_bit_sets,
                           const PlaneGeometry &geo, const TileSpace &tiles,
-                          uint64_t block_tiles, float kin_threshold, const Outputs &out,
-                          TiledArgs *args) {
+                          uint64_t block_tiles, const Outputs &out, TiledArgs *args) {
   TiledArgs &a = *args;
   a = {};
   a.planes = ctx->planes;
@@ -579,7 +597,7 @@ cuking_status launch_args(cuking_ctx *ctx, hipStream_t stream, const cuking_subm
   a.band_prefix = ctx->band_prefix;
   a.i_begin = sm.i_begin;
   a.j_begin = sm.j_begin;
-  a.kin_threshold = kin_threshold;
+  a.kin_threshold = out.kin_threshold;
   a.max_results = out.max_results;
   a.results = out.results;
   a.result_index = out.result_index;
@@ -605,9 +623,10 @@ cuking_status launch_args(cuking_ctx *ctx, hipStream_t stream, const cuking_subm
   a.bits = d_bit_sets;
   a.words_per_sample = words_per_sample;
   a.split_wgs = ctx->split_wgs;
-  // the sample order of the workspace's layout, and the lazy-codes word
+  // the sample order of the workspace's layout (none where the form's conversion did not
+  // sort: the identity), and the lazy-codes word
   if (plan_variant(ctx, words_per_sample).layout == kLayoutNibbleStats) {
-    a.perm = plane_perm(ctx->planes, geo);
+    if (!kCallForms[out.form].unsorted) a.perm = plane_perm(ctx->planes, geo);
     if (!ctx->prepared.codes) a.codes_ready = plane_flags(ctx->planes, geo);
   }
   cuking_ctx::StreamScratch *e;
@@ -642,18 +661,13 @@ cuking_status launch_args(cuking_ctx *ctx, hipStream_t stream, const cuking_subm
   return CUKING_OK;
 }
 
-// Enqueues `num_tiles` tiles of the planned geometry: as they are when the
-// kernel's tile edge is the geometry's, as four quadrants each otherwise.
+// Enqueues `num_tiles` tiles of the planned geometry with the kernel variant that runs for
+// this width of bitset.
 hipError_t launch_planned(const cuking_ctx *ctx, uint32_t words_per_sample, bool full,
-                          TiledArgs a, const LaunchSwitches &sw, uint64_t num_tiles,
+                          const TiledArgs &a, const LaunchSwitches &sw, uint64_t num_tiles,
                           hipStream_t stream) {
-  const int kv = effective_variant(ctx, words_per_sample);
-  if (tiled_variant(kv).tile != tiled_variant(ctx->variant).tile) {
-    // (only the filter variant's 256-sample geometry over a 128-tile kernel)
-    if (tiled_variant(kv).tile * 2 != tiled_variant(ctx->variant).tile) return hipErrorInvalidValue;
-    to_quadrants(&a, &num_tiles);
-  }
-  return launch_tiled(kv, full, a, sw, num_tiles, stream);
+  return launch_tiled(effective_variant(ctx, words_per_sample), tiled_variant(ctx->variant).tile,
+                      full, a, sw, num_tiles, stream);
 }
 
 // A pair kernel that reads the workspace has been enqueued on `stream`.
@@ -767,7 +781,6 @@ cuking_status upload_prefix(cuking_ctx *ctx, const TileSpace &tiles, hipStream_t
   return CUKING_OK;
 }
 
-// Builds planes + band prefix for `sm` in the context workspace.
 // The nibble codes (+ het-only copy) of every converted tile of a kLayoutNibbleStats
 // workspace whose last conversion left them out (lazy codes): for calls that run the
 // four-product kernel directly.
@@ -792,12 +805,164 @@ cuking_status convert_codes_now(cuking_ctx *ctx, const PlaneGeometry &geo,
   return CUKING_OK;
 }
 
-cuking_status prepare(cuking_ctx *ctx, const cuking_submatrix &sm,
-                      uint32_t words_per_sample, const uint64_t *d_bit_sets,
-                      hipStream_t stream, PlaneGeometry *geo_out,
-                      TileSpace *tiles_out, bool need_codes, bool dense_order,
-                      uint32_t s_tile_begin = 0, uint32_t s_tile_end = 0xFFFFFFFFu,
-                      bool filter_call = false, float kin_threshold = 0.f) {
+// What prepare() is asked for: plane samples [s_tile_begin, s_tile_end) (units of 64; the end
+// is clamped to the block's) of block `sm` of a bitset, converted on `stream` for a call of
+// `form` (king_launch_plan.h: an unsorted form's layout keeps stored order).  filter_call:
+// the filter runs for the call (LaunchSwitches::filter_runs) at kin_threshold -- the site
+// order may apply, and the four-product kernel's codes may stay unconverted.
+struct PrepareRequest {
+  const cuking_submatrix &sm;
+  uint32_t words_per_sample;
+  const uint64_t *d_bit_sets;
+  hipStream_t stream;
+  uint32_t s_tile_begin, s_tile_end;
+  CallForm form;
+  bool filter_call;
+  float kin_threshold;
+};
+constexpr uint32_t kEveryPlaneTile = 0xFFFFFFFFu;
+
+// Site order ("filter_site_order"), what the host knows in front of the conversion: whether
+// this request's layout is to get its curve built (`wanted`), the scratch that takes, and the
+// gather that would apply the order.
+struct SiteOrderPlan {
+  uint32_t num_stored;
+  SiteOrderScratch layout;
+  bool wanted;
+  int gather;
+};
+// Whole-block conversions for a call the filter runs for.  Automatic: blocks of at least
+// kSiteOrderMinTiles tiles whose bitset is long enough for check points get their curve
+// built; whether the layout then takes the order is decided from the curve
+// (decide_site_order).
+SiteOrderPlan plan_site_order(const cuking_ctx *ctx, const PrepareRequest &rq, const TiledVariant &v,
+                              const PlaneGeometry &geo, const TileSpace &tiles, bool whole) {
+  SiteOrderPlan p = {};
+  p.num_stored = geo.diag ? geo.num_rows : geo.num_rows + geo.num_cols;
+  if (rq.filter_call && !kCallForms[rq.form].unsorted && v.layout == kLayoutNibbleStats &&
+      ctx->filter_site_order != 0 && whole) {
+    p.layout = site_order_scratch(p.num_stored, rq.words_per_sample);
+    p.wanted = p.layout.bytes != 0 &&
+               (ctx->filter_site_order >= 1 ||
+                (total_tiles(tiles) >= ctx->filter_site_order_min_tiles &&
+                 geo.k_words / 8 >= filter_check_min_steps()));
+  }
+  p.gather = site_gather_pick(ctx->filter_site_gather, rq.words_per_sample);
+  return p;
+}
+
+// Site order, the decision for a layout that is about to be converted (*site_order: the
+// layout takes the order): counts, weights, sort and the curve in this stream's scratch, and
+// the host waits for the curve before it decides -- the order takes the layout when the
+// option says 1, or when the curve forecasts the check at least kSiteOrderMinGain 64ths
+// earlier than stored order has it and the launch-wide verdict does not send every tile away
+// first.  The scratch (a second copy of the bitset among it) is allocated here, on first use
+// and again for a larger block -- cuking_ctx_reserve does not know it.  A "no" has cost the
+// counts, the sort and the wait, not the gather, and keeps rotated tiles.
+cuking_status decide_site_order(cuking_ctx *ctx, const PrepareRequest &rq, const PlaneGeometry &geo,
+                                const SiteOrderPlan &plan, bool *site_order) {
+  cuking_ctx::Prepared &pr = ctx->prepared;
+  *site_order = false;
+  // (an automatic "no" is remembered for the block: conversion inside every pass of a
+  //  cohort the order cannot help must not pay the counts, the sort and the wait each time)
+  const bool trust_no = ctx->filter_site_order == -1 && pr.order_no_left != 0 &&
+                        pr.order_thr == rq.kin_threshold;
+  if (trust_no) --pr.order_no_left;
+  if (plan.wanted && !trust_no) {
+    cuking_ctx::StreamScratch *e = stream_entry(ctx, rq.stream);
+    const cuking_status st = grow_on_stream(ctx, rq.stream, &e->site_order, plan.layout.bytes);
+    if (st != CUKING_OK) return st;
+    SiteCurve *d_curve = plane_site_curve(ctx->planes, geo);
+    HIP_TRY(launch_site_order(rq.d_bit_sets, plan.num_stored, rq.words_per_sample, geo,
+                              e->site_order.p, plan.layout, d_curve, rq.stream));
+    SiteCurve curve;
+    HIP_TRY(hipMemcpyAsync(&curve, d_curve, sizeof curve, hipMemcpyDeviceToHost, rq.stream));
+    ++ctx->host_syncs;
+    HIP_TRY(hipStreamSynchronize(rq.stream));
+    const SiteOrderForecast f =
+        site_order_forecast(curve, plan.num_stored, geo.k_words, rq.kin_threshold);
+    ctx->order_forecast = f;
+    ctx->order_sigma = curve.sigma;
+    *site_order = ctx->filter_site_order >= 1 ||
+                  (!f.verdict_first && f.order64 != 0 &&
+                   (f.stored64 == 0 || f.order64 + kSiteOrderMinGain <= f.stored64));
+    pr.order_thr = rq.kin_threshold;
+    pr.order_no_left = *site_order ? 0u : kSiteOrderNoTrust;
+  }
+  pr.site_order = *site_order;
+  return CUKING_OK;
+}
+
+// The filter variant's layout (kLayoutNibbleStats) for plane tiles [rq.s_tile_begin, t_end),
+// step by step: statistics in stored order, the sample order (king_sort.hip), T2 -- and the
+// four-product kernel's codes now, or by a gated launch behind the filter kernel if that
+// turns out to need them (lazy codes: whole blocks only; the ranges of a staged pass are
+// converted in full).
+cuking_status convert_nibble_layout(cuking_ctx *ctx, const PrepareRequest &rq,
+                                    const PlaneGeometry &geo, const SiteOrderPlan &plan,
+                                    uint32_t t_end, bool whole) {
+  cuking_ctx::Prepared &pr = ctx->prepared;
+  hipStream_t stream = rq.stream;
+  const bool codes = !rq.filter_call || !ctx->filter_lazy_codes || !whole;
+  const uint32_t sb = rq.s_tile_begin * 64, se = t_end * 64;
+  if (rq.s_tile_begin == 0)  // a conversion that starts at plane sample 0 starts the cohort's sums afresh
+    HIP_TRY(hipMemsetAsync(const_cast<unsigned long long *>(plane_cohort_sums(ctx->planes, geo)),
+                           0, 64, stream));
+  // (whatever is converted now, the codes of the block as a whole are not "there" unless
+  //  this conversion or convert_codes_now() below says so)
+  HIP_TRY(hipMemsetAsync(plane_flags(ctx->planes, geo), 0, sizeof(uint32_t), stream));
+  // Site order: the bitset with every sample's sites in that order in this stream's scratch
+  // -- what the statistics and T2 are built from, so that both see the SAME order (one extra
+  // write and read of the bitset, against a gather in each of the two kernels).  The codes
+  // stay in stored order, like everything that recounts.
+  bool site_order;
+  cuking_status st = decide_site_order(ctx, rq, geo, plan, &site_order);
+  if (st != CUKING_OK) return st;
+  const uint64_t *layout_bits = rq.d_bit_sets;
+  // The byte-wide gather of a diagonal block (plane sample = stored sample) counts the
+  // statistics on the words it assembles: the separate kernel keeps the padding samples
+  // behind the stored ones, which read nothing.
+  const bool fused_stats = site_order && plan.gather > 0 && geo.diag != 0;
+  if (site_order) {
+    cuking_ctx::StreamScratch *e = stream_entry(ctx, stream);
+    const SiteGatherStats fused = {stats_arrays(geo, ctx->planes), geo, se};
+    HIP_TRY(launch_site_permute(rq.d_bit_sets, plan.num_stored, rq.words_per_sample,
+                                e->site_order.p, plan.layout, plan.gather,
+                                fused_stats ? &fused : nullptr, stream));
+    layout_bits = reinterpret_cast<const uint64_t *>(static_cast<const uint8_t *>(e->site_order.p) +
+                                                     plan.layout.permuted);
+  }
+  HIP_TRY(launch_sample_stats(layout_bits, rq.words_per_sample, geo, ctx->planes,
+                              fused_stats ? plan.num_stored : sb, se, stream));
+  HIP_TRY(launch_sample_order(geo, rq.words_per_sample, ctx->planes, sb, se,
+                              !kCallForms[rq.form].unsorted &&
+                                  (ctx->filter_sort == 2 || (ctx->filter_sort == 1 && whole)),
+                              ctx->sort_temp, ctx->sort_temp_bytes, stream));
+  HIP_TRY(launch_prepare_nibbles(codes && !site_order, true, layout_bits, rq.words_per_sample, geo,
+                                 ctx->planes, plane_perm(ctx->planes, geo), rq.s_tile_begin, t_end,
+                                 nullptr, nullptr, stream));
+  if (codes && site_order)
+    HIP_TRY(launch_prepare_nibbles(true, false, rq.d_bit_sets, rq.words_per_sample, geo,
+                                   ctx->planes, plane_perm(ctx->planes, geo), rq.s_tile_begin,
+                                   t_end, nullptr, nullptr, stream));
+  if (!codes) {
+    pr.codes = false;
+  } else if (!pr.codes) {
+    // earlier tiles of this block were converted without codes: complete them
+    return convert_codes_now(ctx, geo, rq.words_per_sample, rq.d_bit_sets, stream);
+  } else {
+    HIP_TRY(hipMemsetAsync(plane_flags(ctx->planes, geo), 1, sizeof(uint32_t), stream));
+  }
+  return CUKING_OK;
+}
+
+// Builds planes + band prefix for `rq.sm` in the context workspace: the workspace, the
+// "same block?" decision, the ordering against readers, the prefix, then the conversion.
+cuking_status prepare(cuking_ctx *ctx, const PrepareRequest &rq, PlaneGeometry *geo_out,
+                      TileSpace *tiles_out) {
+  const cuking_submatrix &sm = rq.sm;
+  const uint32_t words_per_sample = rq.words_per_sample;
+  hipStream_t stream = rq.stream;
   const int variant = effective_variant(ctx, words_per_sample);
   const TiledVariant v = plan_variant(ctx, words_per_sample);
   const PlaneGeometry geo = make_geometry(sm, words_per_sample, v);
@@ -811,40 +976,28 @@ cuking_status prepare(cuking_ctx *ctx, const cuking_submatrix &sm,
   // other streams that still read what is about to be overwritten -- the planes
   // AND the band prefix below, so this comes before either is touched.
   const uint32_t all_tiles = (geo.s_stride + 63) / 64;
-  const uint32_t t_end = s_tile_end < all_tiles ? s_tile_end : all_tiles;
+  const uint32_t s_tile_begin = rq.s_tile_begin;
+  const uint32_t t_end = rq.s_tile_end < all_tiles ? rq.s_tile_end : all_tiles;
+  const bool whole = s_tile_begin == 0 && t_end == all_tiles;
   cuking_ctx::Prepared &pr = ctx->prepared;
   const bool new_prefix = !same_tile_space(ctx->prefix_for, tiles);
-  // (a layout converted for a dense kinship matrix is unsorted: a call of the other kind
-  //  treats it as another block's, and the other way round)
-  // Site order ("filter_site_order"): whole-block conversions for a call the filter runs for
-  // (`filter_call`).  Automatic: blocks of at least kSiteOrderMinTiles tiles whose bitset is
-  // long enough for check points get their curve built (`order_wanted`); whether the layout
-  // then takes the order is decided from the curve, below.
-  const uint32_t num_stored = geo.diag ? geo.num_rows : geo.num_rows + geo.num_cols;
-  SiteOrderScratch order_layout = {};
-  bool order_wanted = false;
-  if (filter_call && !dense_order && v.layout == kLayoutNibbleStats && ctx->filter_site_order != 0 &&
-      s_tile_begin == 0 && t_end == all_tiles) {
-    order_layout = site_order_scratch(num_stored, words_per_sample);
-    order_wanted = order_layout.bytes != 0 &&
-                 (ctx->filter_site_order >= 1 ||
-                  (total_tiles(tiles) >= ctx->filter_site_order_min_tiles &&
-                   geo.k_words / 8 >= filter_check_min_steps()));
-  }
-  const int site_gather = site_gather_pick(ctx->filter_site_gather, words_per_sample);
-  if (order_wanted && site_gather < 0)
+  const bool dense_order = kCallForms[rq.form].unsorted;
+  const SiteOrderPlan order = plan_site_order(ctx, rq, v, geo, tiles, whole);
+  if (order.wanted && order.gather < 0)
     return cuking_fail(CUKING_ERR_INVALID_ARGUMENT,
                        "filter_site_gather %d: %u words per sample do not fit the gather's LDS",
                        ctx->filter_site_gather, words_per_sample);
-  // (... and a layout converted under another answer to that is another block's as well.  A
-  //  layout that is reused keeps the decision of the call that converted it, whatever
-  //  threshold this one has: its share comes from the curve and this call's threshold.)
-  const bool same = same_block(pr, sm, words_per_sample, variant, v.tile, d_bit_sets) &&
-                    pr.dense_order == dense_order && pr.order_wanted == order_wanted &&
+  // (a layout converted for an unsorted form is unsorted: a call of the other kind treats it
+  //  as another block's, and the other way round ... and a layout converted under another
+  //  answer to "is the curve wanted" is another block's as well.  A layout that is reused
+  //  keeps the decision of the call that converted it, whatever threshold this one has: its
+  //  share comes from the curve and this call's threshold.)
+  const bool same = same_block(pr, sm, words_per_sample, variant, v.tile, rq.d_bit_sets) &&
+                    pr.dense_order == dense_order && pr.order_wanted == order.wanted &&
                     // (the share of an ordered layout comes from its curve at the call's
                     //  threshold and may be "no check at all" at another one, where stored
                     //  order would have had one: such a call decides and converts afresh)
-                    !(pr.site_order && pr.order_thr != kin_threshold);
+                    !(pr.site_order && pr.order_thr != rq.kin_threshold);
   if (ctx->reuse_prepared && same && !new_prefix) {
     // The host has promised that the bitset behind this pointer is unchanged
     // since it was converted (cuking_invalidate otherwise): nothing to do when
@@ -853,8 +1006,8 @@ cuking_status prepare(cuking_ctx *ctx, const cuking_submatrix &sm,
     for (uint32_t t = s_tile_begin; t < t_end && all_there; ++t) all_there = pr.tiles[t] != 0;
     if (all_there) {
       ++ctx->conversions_skipped;
-      if (v.layout == kLayoutNibbleStats && need_codes && !pr.codes)
-        return convert_codes_now(ctx, geo, words_per_sample, d_bit_sets, stream);
+      if (v.layout == kLayoutNibbleStats && !rq.filter_call && !pr.codes)
+        return convert_codes_now(ctx, geo, words_per_sample, rq.d_bit_sets, stream);
       return CUKING_OK;
     }
   }
@@ -871,11 +1024,11 @@ cuking_status prepare(cuking_ctx *ctx, const cuking_submatrix &sm,
     pr.words_per_sample = words_per_sample;
     pr.variant = variant;
     pr.tile = v.tile;
-    pr.bits = d_bit_sets;
+    pr.bits = rq.d_bit_sets;
     pr.tiles.assign(all_tiles, 0);
     pr.codes = true;
     pr.dense_order = dense_order;
-    pr.order_wanted = order_wanted;
+    pr.order_wanted = order.wanted;
     pr.site_order = false;
     pr.order_no_left = 0;
   }
@@ -895,167 +1048,74 @@ cuking_status prepare(cuking_ctx *ctx, const cuking_submatrix &sm,
   EventPair *ev = nullptr;
   if (ctx->timing) HIP_TRY(ctx->prepare_timer.begin(stream, &ev));
   if (v.layout == kLayoutNibbleStats) {
-    // The filter variant's layout, step by step: statistics in stored order, the sample
-    // order (king_sort.hip), T2 -- and the four-product kernel's codes now, or by a gated
-    // launch behind the filter kernel if that turns out to need them (lazy codes: whole
-    // blocks only; the ranges of a staged pass are converted in full).
-    const bool whole = s_tile_begin == 0 && t_end == all_tiles;
-    const bool codes = need_codes || !ctx->filter_lazy_codes || !whole;
-    const uint32_t sb = s_tile_begin * 64, se = t_end * 64;
-    if (s_tile_begin == 0)  // a conversion that starts at plane sample 0 starts the cohort's sums afresh
-      HIP_TRY(hipMemsetAsync(const_cast<unsigned long long *>(plane_cohort_sums(ctx->planes, geo)),
-                             0, 64, stream));
-    // (whatever is converted now, the codes of the block as a whole are not "there" unless
-    //  this conversion or convert_codes_now() below says so)
-    HIP_TRY(hipMemsetAsync(plane_flags(ctx->planes, geo), 0, sizeof(uint32_t), stream));
-    // Site order: counts, weights, sort, and the bitset with every sample's sites in that
-    // order in this stream's scratch -- what the statistics and T2 are built from, so that
-    // both see the SAME order (one extra write and read of the bitset, against a gather in
-    // each of the two kernels).  The codes stay in stored order, like everything that recounts.
-    // The scratch (a second copy of the bitset among it) is allocated here, on first use and
-    // again for a larger block -- cuking_ctx_reserve does not know it --, and the host waits
-    // for the curve before it decides: the order takes the layout when the option says 1, or
-    // when the curve forecasts the check at least kSiteOrderMinGain 64ths earlier than stored
-    // order has it and the launch-wide verdict does not send every tile away first.  A "no"
-    // has cost the counts, the sort and the wait, not the gather, and keeps rotated tiles.
-    const uint64_t *layout_bits = d_bit_sets;
-    bool site_order = false;
-    // (an automatic "no" is remembered for the block: conversion inside every pass of a
-    //  cohort the order cannot help must not pay the counts, the sort and the wait each time)
-    const bool trust_no = ctx->filter_site_order == -1 && pr.order_no_left != 0 &&
-                          pr.order_thr == kin_threshold;
-    if (trust_no) --pr.order_no_left;
-    if (order_wanted && !trust_no) {
-      cuking_ctx::StreamScratch *e = stream_entry(ctx, stream);
-      st = grow_on_stream(ctx, stream, &e->site_order, order_layout.bytes);
-      if (st != CUKING_OK) return st;
-      SiteCurve *d_curve = plane_site_curve(ctx->planes, geo);
-      HIP_TRY(launch_site_order(d_bit_sets, num_stored, words_per_sample, geo, e->site_order.p,
-                                order_layout, d_curve, stream));
-      SiteCurve curve;
-      HIP_TRY(hipMemcpyAsync(&curve, d_curve, sizeof curve, hipMemcpyDeviceToHost, stream));
-      ++ctx->host_syncs;
-      HIP_TRY(hipStreamSynchronize(stream));
-      const SiteOrderForecast f = site_order_forecast(curve, num_stored, geo.k_words, kin_threshold);
-      ctx->order_forecast = f;
-      ctx->order_sigma = curve.sigma;
-      site_order = ctx->filter_site_order >= 1 ||
-                   (!f.verdict_first && f.order64 != 0 &&
-                    (f.stored64 == 0 || f.order64 + kSiteOrderMinGain <= f.stored64));
-      pr.order_thr = kin_threshold;
-      pr.order_no_left = site_order ? 0u : kSiteOrderNoTrust;
-    }
-    pr.site_order = site_order;
-    // The byte-wide gather of a diagonal block (plane sample = stored sample) counts the
-    // statistics on the words it assembles: the separate kernel keeps the padding samples
-    // behind the stored ones, which read nothing.
-    const bool fused_stats = site_order && site_gather > 0 && geo.diag != 0;
-    if (site_order) {
-      cuking_ctx::StreamScratch *e = stream_entry(ctx, stream);
-      const SiteGatherStats fused = {stats_arrays(geo, ctx->planes), geo, se};
-      HIP_TRY(launch_site_permute(d_bit_sets, num_stored, words_per_sample, e->site_order.p,
-                                  order_layout, site_gather, fused_stats ? &fused : nullptr,
-                                  stream));
-      layout_bits = reinterpret_cast<const uint64_t *>(static_cast<const uint8_t *>(e->site_order.p) +
-                                                       order_layout.permuted);
-    }
-    HIP_TRY(launch_sample_stats(layout_bits, words_per_sample, geo, ctx->planes,
-                                fused_stats ? num_stored : sb, se, stream));
-    HIP_TRY(launch_sample_order(geo, words_per_sample, ctx->planes, sb, se,
-                                !dense_order &&
-                                    (ctx->filter_sort == 2 || (ctx->filter_sort == 1 && whole)),
-                                ctx->sort_temp, ctx->sort_temp_bytes, stream));
-    HIP_TRY(launch_prepare_nibbles(codes && !site_order, true, layout_bits, words_per_sample, geo,
-                                   ctx->planes, plane_perm(ctx->planes, geo), s_tile_begin, t_end,
-                                   nullptr, nullptr, stream));
-    if (codes && site_order)
-      HIP_TRY(launch_prepare_nibbles(true, false, d_bit_sets, words_per_sample, geo, ctx->planes,
-                                     plane_perm(ctx->planes, geo), s_tile_begin, t_end, nullptr,
-                                     nullptr, stream));
-    if (!codes) {
-      pr.codes = false;
-    } else if (!pr.codes) {
-      // earlier tiles of this block were converted without codes: complete them
-      st = convert_codes_now(ctx, geo, words_per_sample, d_bit_sets, stream);
-      if (st != CUKING_OK) return st;
-    } else {
-      HIP_TRY(hipMemsetAsync(plane_flags(ctx->planes, geo), 1, sizeof(uint32_t), stream));
-    }
+    st = convert_nibble_layout(ctx, rq, geo, order, t_end, whole);
+    if (st != CUKING_OK) return st;
   } else {
-    HIP_TRY(launch_prepare_planes(v.layout, d_bit_sets, words_per_sample, geo, ctx->planes,
-                                  s_tile_begin, s_tile_end, stream));
+    HIP_TRY(launch_prepare_planes(v.layout, rq.d_bit_sets, words_per_sample, geo, ctx->planes,
+                                  s_tile_begin, rq.s_tile_end, stream));
   }
   if (ev) HIP_TRY(hipEventRecord(ev->stop, stream));
   return CUKING_OK;
 }
 
-cuking_status run_tiled(cuking_ctx *ctx, const cuking_submatrix &sm,
-                        uint32_t words_per_sample, const uint64_t *d_bit_sets,
-                        uint64_t tile_begin, uint64_t tile_end, bool whole,
-                        float kin_threshold, const Outputs &out, hipStream_t stream) {
+// The block a pair call works on, as every entry point receives it.
+struct BlockArgs {
+  cuking_ctx *ctx;
+  const cuking_submatrix *sm;
+  uint32_t words_per_sample;
+  const uint64_t *d_bit_sets;
+  void *stream;
+};
+// Every tile of the block (the only form the stream kernel serves), or tiles [begin, end) of
+// its enumeration.
+struct TileRange {
+  bool whole;
+  uint64_t begin, end;
+};
+constexpr TileRange kEveryTile = {true, 0, 0};
+
+// The tiled kernels for a call of out.form: what the form's rules (king_launch_plan.h
+// kCallForms) say about the k loop, the layout and the filter, then conversion and launch.
+cuking_status run_tiled(const BlockArgs &b, TileRange r, const Outputs &out) {
+  cuking_ctx *ctx = b.ctx;
+  const cuking_submatrix &sm = *b.sm;
+  hipStream_t stream = (hipStream_t)b.stream;
+  const CallFormRules &rules = kCallForms[out.form];
+  const bool mfma = is_mfma_variant(effective_variant(ctx, b.words_per_sample));
+  // (the entry points of these forms have refused every other context)
+  if (!mfma && !rules.valu_serves)
+    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "%s: no matrix-core kernel", rules.name);
+  // (a form that keeps every pair on the lean k loop does so on the matrix cores: the VALU
+  //  kernels store a matrix from their full form)
+  const bool full = rules.k_loop == kLoopEither
+                        ? use_full_counts(ctx, out.kin_threshold, b.words_per_sample)
+                        : rules.k_loop == kLoopFull || !mfma;
+  const LaunchSwitches sw =
+      launch_switches(ctx, b.words_per_sample, out.form, full, out.kin_threshold);
   PlaneGeometry geo;
   TileSpace tiles;
-  // A dense kinship matrix: the matrix-core kernels' lean form with an epilogue of its own
-  // (contexts of variant 6 and 7: the four-product kernel, the latter on the quadrants of
-  // its tiles; variant 5 and wide bitsets: the five-product kernel), on a layout that is
-  // never sorted; the VALU kernels store it from their full form.
-  // A kinship summary: the same, with an epilogue that reduces the float instead of storing
-  // it; matrix-core kernels only (the entry points have refused every other context).
-  const bool sum = out.sum_hist != nullptr || out.sum_best != nullptr;
-  const bool kin = out.kin != nullptr;
-  const int kv = effective_variant(ctx, words_per_sample);
-  if (sum && !is_mfma_variant(kv))
-    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "kinship summary: no matrix-core kernel");
-  // Relative counts: the thresholded call's lean form (sorted layout, the filter where its
-  // bound applies) whose kernels count instead of appending records; matrix-core kernels only.
-  const bool rel = out.rel_counts != nullptr;
-  if (rel && !is_mfma_variant(kv))
-    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "relative counts: no matrix-core kernel");
-  const bool kin_mfma = (kin || sum) && is_mfma_variant(kv);
-  // PI_HAT records: the full form (five sums of every pair: the route of cuking_compute_counts
-  // and of a thresholded call at a non-positive threshold) of the matrix-core kernels with a
-  // PI_HAT epilogue; no filter, whose bound is one on KING kinship.
-  const bool pihat = out.pihat.on != 0;
-  if (pihat && !is_mfma_variant(kv))
-    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "pi_hat: no matrix-core kernel");
-  const bool full = pihat ||
-                    (!kin_mfma && !rel &&
-                     use_full_counts(ctx, kin_threshold, out.counts != nullptr || kin, words_per_sample));
-  const LaunchSwitches sw = launch_switches(ctx, words_per_sample, full, kin_threshold);
-  // (where the filter runs the four-product kernel's codes may stay unconverted)
-  cuking_status st = prepare(ctx, sm, words_per_sample, d_bit_sets, stream, &geo, &tiles,
-                             !sw.filter_runs, kin || sum, 0, 0xFFFFFFFFu, sw.filter_runs,
-                             kin_threshold);
+  cuking_status st = prepare(ctx,
+                             {sm, b.words_per_sample, b.d_bit_sets, stream, 0, kEveryPlaneTile,
+                              out.form, sw.filter_runs, out.kin_threshold},
+                             &geo, &tiles);
   if (st != CUKING_OK) return st;
   const uint64_t n_tiles = total_tiles(tiles);
-  if (whole) {
-    tile_begin = 0;
-    tile_end = n_tiles;
-  }
-  if (tile_begin > tile_end || tile_end > n_tiles)
+  if (r.whole) r = {true, 0, n_tiles};
+  if (r.begin > r.end || r.end > n_tiles)
     return cuking_fail(CUKING_ERR_INVALID_ARGUMENT,
                 "tile range [%llu, %llu) outside [0, %llu)",
-                (unsigned long long)tile_begin, (unsigned long long)tile_end,
+                (unsigned long long)r.begin, (unsigned long long)r.end,
                 (unsigned long long)n_tiles);
-  if (tile_begin == tile_end) return CUKING_OK;
+  if (r.begin == r.end) return CUKING_OK;
 
   TiledArgs a;
-  st = launch_args(ctx, stream, sm, words_per_sample, d_bit_sets, geo, tiles, n_tiles,
-                   kin_threshold, out, &a);
+  st = launch_args(ctx, stream, sm, b.words_per_sample, b.d_bit_sets, geo, tiles, n_tiles, out, &a);
   if (st != CUKING_OK) return st;
-  a.tile_begin = tile_begin;
+  a.tile_begin = r.begin;
 
   EventPair *ev = nullptr;
   if (ctx->timing) HIP_TRY(ctx->king_timer.begin(stream, &ev));
-  if (kin_mfma) {
-    uint64_t units = tile_end - tile_begin;
-    if (tiled_variant(ctx->variant).tile == kFilterTile) to_quadrants(&a, &units);
-    a.perm = nullptr;  // (the identity: prepare() above did not sort)
-    if (sum) HIP_TRY(launch_mfma_summary(kv != kMfmaVariant, a, sw, units, stream));
-    else HIP_TRY(launch_mfma_kin(kv != kMfmaVariant, a, sw, units, stream));
-  } else {
-    HIP_TRY(launch_planned(ctx, words_per_sample, full, a, sw, tile_end - tile_begin, stream));
-  }
+  HIP_TRY(launch_planned(ctx, b.words_per_sample, full, a, sw, r.end - r.begin, stream));
   note_reader(ctx, stream);
   mark_read(ctx, 0, 0xFFFFFFFFu);
   if (a.kin_diag != 0) HIP_TRY(launch_kin_mirror(out.kin, out.kin_ld, geo.num_rows, stream));
@@ -1063,22 +1123,46 @@ cuking_status run_tiled(cuking_ctx *ctx, const cuking_submatrix &sm,
   return CUKING_OK;
 }
 
-cuking_status run_stream(cuking_ctx *ctx, const cuking_submatrix &sm,
-                         uint32_t words_per_sample, const uint64_t *d_bit_sets,
-                         float kin_threshold, uint32_t max_results,
-                         cuking_result *d_results, uint32_t *d_result_index,
-                         uint32_t *d_result_overflow, cuking_counts *d_counts,
-                         hipStream_t stream, float *d_kin = nullptr, uint64_t kin_ld = 0,
-                         uint32_t kin_flags = 0) {
+// The stream kernel, for the whole block and the forms the VALU kernels serve.
+cuking_status run_stream(const BlockArgs &b, const Outputs &out) {
+  cuking_ctx *ctx = b.ctx;
+  hipStream_t stream = (hipStream_t)b.stream;
   EventPair *ev = nullptr;
   if (ctx->timing) HIP_TRY(ctx->king_timer.begin(stream, &ev));
-  const uint32_t kin_diag = (d_kin != nullptr && (kin_flags & CUKING_KIN_SYMMETRIC)) ? 1u : 0u;
-  HIP_TRY(launch_stream(sm, words_per_sample, d_bit_sets, kin_threshold,
-                        max_results, d_results, d_result_index,
-                        d_result_overflow, d_counts, d_kin, kin_ld, kin_diag, stream));
-  if (kin_diag != 0) HIP_TRY(launch_kin_mirror(d_kin, kin_ld, sm_num_rows(sm), stream));
+  const uint32_t kin_diag =
+      (out.kin != nullptr && (out.kin_flags & CUKING_KIN_SYMMETRIC)) ? 1u : 0u;
+  HIP_TRY(launch_stream(*b.sm, b.words_per_sample, b.d_bit_sets, out.kin_threshold,
+                        out.max_results, out.results, out.result_index, out.result_overflow,
+                        out.counts, out.kin, out.kin_ld, kin_diag, stream));
+  if (kin_diag != 0) HIP_TRY(launch_kin_mirror(out.kin, out.kin_ld, sm_num_rows(*b.sm), stream));
   if (ev) HIP_TRY(hipEventRecord(ev->stop, stream));
   return CUKING_OK;
+}
+
+// Where a call binds its context's device, among the steps every call takes.  The calls
+// differ in it (and so in what an invalid call with a null context, or one that meets a
+// device error, reports first); the difference is kept as it was, not decided here.
+enum class BindAt { kFirst, kBehindCheck, kBehindEmptyBlock };
+
+// What the pair calls X and X_tiles share, for every X: the call's own part `check` (its
+// argument checks, then its Outputs), the empty block's rule, the kernel.
+template <class Check>
+cuking_status run_pair_call(const BlockArgs &b, const TileRange &r, BindAt bind_at, Check check) {
+  if (bind_at == BindAt::kFirst) BIND_OR_RETURN(b.ctx);
+  Outputs out = {};
+  const cuking_status st = check(&out);
+  if (st != CUKING_OK) return st;
+  if (bind_at == BindAt::kBehindCheck) BIND_OR_RETURN(b.ctx);
+  if (sm_num_rows(*b.sm) == 0 || sm_num_cols(*b.sm) == 0) {
+    // (the checks of the matrix-core-only forms have refused such a range already, in the
+    //  words of every range outside the block's)
+    if (!r.whole && (r.begin != 0 || r.end != 0))
+      return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "empty block has no tiles");
+    return CUKING_OK;
+  }
+  if (bind_at == BindAt::kBehindEmptyBlock) BIND_OR_RETURN(b.ctx);
+  if (r.whole && b.ctx->kernel == CUKING_KERNEL_STREAM) return run_stream(b, out);
+  return run_tiled(b, r, out);
 }
 
 // ---- options ---------------------------------------------------------------
@@ -1539,32 +1623,20 @@ static cuking_status check_compute_args(const cuking_submatrix *sm,
   return CUKING_OK;
 }
 
-// What cuking_compute_king and cuking_compute_king_tiles share: `whole` = every tile of the
-// block (the only form the stream kernel serves).
-static cuking_status run_king(cuking_ctx *ctx, const cuking_submatrix *sm,
-                              uint32_t words_per_sample, const uint64_t *d_bit_sets, bool whole,
-                              uint64_t tile_begin, uint64_t tile_end, float kin_threshold,
-                              uint32_t max_results, cuking_result *d_results,
-                              uint32_t *d_result_index, uint32_t *d_result_overflow,
-                              void *stream) {
-  BIND_OR_RETURN(ctx);
-  const cuking_status st = check_compute_args(sm, words_per_sample, d_bit_sets);
-  if (st != CUKING_OK) return st;
-  if (!d_result_index || !d_result_overflow || (max_results && !d_results))
-    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "null result pointer");
-  if (sm_num_rows(*sm) == 0 || sm_num_cols(*sm) == 0) {
-    if (!whole && (tile_begin != 0 || tile_end != 0))
-      return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "empty block has no tiles");
+// cuking_compute_king and cuking_compute_king_tiles.  (Binds first: a null context is
+// reported in front of any bad argument.)
+static cuking_status king_call(const BlockArgs &b, const TileRange &r, float kin_threshold,
+                               uint32_t max_results, cuking_result *d_results,
+                               uint32_t *d_result_index, uint32_t *d_result_overflow) {
+  return run_pair_call(b, r, BindAt::kFirst, [&](Outputs *out) {
+    const cuking_status st = check_compute_args(b.sm, b.words_per_sample, b.d_bit_sets);
+    if (st != CUKING_OK) return st;
+    if (!d_result_index || !d_result_overflow || (max_results && !d_results))
+      return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "null result pointer");
+    *out = record_outputs(kFormRecords, kin_threshold, max_results, d_results, d_result_index,
+                          d_result_overflow);
     return CUKING_OK;
-  }
-  if (whole && ctx->kernel == CUKING_KERNEL_STREAM)
-    return run_stream(ctx, *sm, words_per_sample, d_bit_sets, kin_threshold,
-                      max_results, d_results, d_result_index, d_result_overflow,
-                      nullptr, (hipStream_t)stream);
-  return run_tiled(ctx, *sm, words_per_sample, d_bit_sets, tile_begin, tile_end, whole,
-                   kin_threshold,
-                   {max_results, d_results, d_result_index, d_result_overflow, nullptr},
-                   (hipStream_t)stream);
+  });
 }
 
 cuking_status cuking_compute_king(cuking_ctx *ctx, const cuking_submatrix *sm,
@@ -1574,8 +1646,8 @@ cuking_status cuking_compute_king(cuking_ctx *ctx, const cuking_submatrix *sm,
                                   cuking_result *d_results,
                                   uint32_t *d_result_index,
                                   uint32_t *d_result_overflow, void *stream) {
-  return run_king(ctx, sm, words_per_sample, d_bit_sets, true, 0, 0, kin_threshold, max_results,
-                  d_results, d_result_index, d_result_overflow, stream);
+  return king_call({ctx, sm, words_per_sample, d_bit_sets, stream}, kEveryTile, kin_threshold,
+                   max_results, d_results, d_result_index, d_result_overflow);
 }
 
 cuking_status cuking_compute_king_tiles(
@@ -1583,9 +1655,8 @@ cuking_status cuking_compute_king_tiles(
     const uint64_t *d_bit_sets, uint64_t tile_begin, uint64_t tile_end,
     float kin_threshold, uint32_t max_results, cuking_result *d_results,
     uint32_t *d_result_index, uint32_t *d_result_overflow, void *stream) {
-  return run_king(ctx, sm, words_per_sample, d_bit_sets, false, tile_begin, tile_end,
-                  kin_threshold, max_results, d_results, d_result_index, d_result_overflow,
-                  stream);
+  return king_call({ctx, sm, words_per_sample, d_bit_sets, stream}, {false, tile_begin, tile_end},
+                   kin_threshold, max_results, d_results, d_result_index, d_result_overflow);
 }
 
 // Offsets of a sample range inside a diagonal block, in tiles.
@@ -1623,9 +1694,12 @@ cuking_status cuking_prepare_samples(cuking_ctx *ctx, const cuking_submatrix *sm
   if (t0 == t1) return CUKING_OK;
   PlaneGeometry geo;
   TileSpace tiles;
-  // prepare() works in units of 64 plane samples.
-  return prepare(ctx, *sm, words_per_sample, d_bit_sets, (hipStream_t)stream, &geo,
-                 &tiles, true, false, t0 * (tile / 64), t1 * (tile / 64));
+  // prepare() works in units of 64 plane samples.  (For the records of rectangles, whatever
+  // their threshold: sorted, every code converted, no site order.)
+  return prepare(ctx,
+                 {*sm, words_per_sample, d_bit_sets, (hipStream_t)stream, t0 * (tile / 64),
+                  t1 * (tile / 64), kFormRecords, false, 0.f},
+                 &geo, &tiles);
 }
 
 cuking_status cuking_compute_king_rect(
@@ -1692,12 +1766,14 @@ cuking_status cuking_compute_king_rect(
                     sm->i_begin + c * v.tile);
   }
 
-  const bool full = use_full_counts(ctx, kin_threshold, false, words_per_sample);
-  LaunchSwitches sw = launch_switches(ctx, words_per_sample, full, kin_threshold);
+  const bool full = use_full_counts(ctx, kin_threshold, words_per_sample);
+  LaunchSwitches sw = launch_switches(ctx, words_per_sample, kFormRecords, full, kin_threshold);
   TiledArgs a;
   st = launch_args(ctx, (hipStream_t)stream, *sm, words_per_sample, d_bit_sets, geo, tiles,
-                   total_tiles(make_tiles(geo, v, ctx->band_rows)), kin_threshold,
-                   {max_results, d_results, d_result_index, d_result_overflow, nullptr}, &a);
+                   total_tiles(make_tiles(geo, v, ctx->band_rows)),
+                   record_outputs(kFormRecords, kin_threshold, max_results, d_results,
+                                  d_result_index, d_result_overflow),
+                   &a);
   if (st != CUKING_OK) return st;
   a.rect_rows = n_rows;
   a.rect_cols = c1 - c0;
@@ -1796,68 +1872,51 @@ cuking_status cuking_compute_counts(cuking_ctx *ctx, const cuking_submatrix *sm,
   if (sm_num_rows(*sm) == 0 || sm_num_cols(*sm) == 0) return CUKING_OK;
   if (d_counts == nullptr)
     return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "null counts pointer");
-  if (ctx->kernel == CUKING_KERNEL_STREAM)
-    return run_stream(ctx, *sm, words_per_sample, d_bit_sets, 0.f, 0, nullptr,
-                      nullptr, nullptr, d_counts, (hipStream_t)stream);
-  return run_tiled(ctx, *sm, words_per_sample, d_bit_sets, 0, 0, true, 0.f,
-                   {0, nullptr, nullptr, nullptr, d_counts}, (hipStream_t)stream);
+  const BlockArgs b = {ctx, sm, words_per_sample, d_bit_sets, stream};
+  Outputs out = {};
+  out.form = kFormCounts;
+  out.counts = d_counts;
+  return ctx->kernel == CUKING_KERNEL_STREAM ? run_stream(b, out) : run_tiled(b, kEveryTile, out);
 }
 
-// The checks the two dense-kinship entry points share, in front of anything that touches
-// a device.
-static cuking_status check_kin_args(const cuking_ctx *ctx, const cuking_submatrix *sm,
-                                    uint32_t words_per_sample, const uint64_t *d_bit_sets,
-                                    const float *d_kin, uint64_t ld, uint32_t flags,
-                                    bool tile_range) {
-  cuking_status st = check_compute_args(sm, words_per_sample, d_bit_sets);
-  if (st != CUKING_OK) return st;
-  if (flags != CUKING_KIN_UPPER && flags != CUKING_KIN_SYMMETRIC)
-    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "unknown kinship matrix flags 0x%x", flags);
-  if (ld < sm_num_cols(*sm))
-    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT,
-                       "kinship matrix: leading dimension %llu below the block's %u columns",
-                       (unsigned long long)ld, sm_num_cols(*sm));
-  if (flags == CUKING_KIN_SYMMETRIC && !sm_is_diag(*sm))
-    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT,
-                       "a symmetric kinship matrix needs a diagonal block (rows == columns)");
-  if (flags == CUKING_KIN_SYMMETRIC && tile_range)
-    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT,
-                       "a symmetric kinship matrix cannot be computed by tile ranges");
-  if (sm_num_rows(*sm) != 0 && sm_num_cols(*sm) != 0 && d_kin == nullptr)
-    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "null kinship matrix pointer");
-  if (ctx == nullptr) return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "null context");
-  return CUKING_OK;
-}
-
-// What the two entry points share behind their checks: `whole` = every tile of the block
-// (the only form the stream kernel serves).
-static cuking_status run_kin_matrix(cuking_ctx *ctx, const cuking_submatrix *sm,
-                                    uint32_t words_per_sample, const uint64_t *d_bit_sets,
-                                    bool whole, uint64_t tile_begin, uint64_t tile_end,
-                                    float *d_kin, uint64_t ld, uint32_t flags, void *stream) {
-  const cuking_status st =
-      check_kin_args(ctx, sm, words_per_sample, d_bit_sets, d_kin, ld, flags, !whole);
-  if (st != CUKING_OK) return st;
-  BIND_OR_RETURN(ctx);
-  if (sm_num_rows(*sm) == 0 || sm_num_cols(*sm) == 0) {
-    if (!whole && (tile_begin != 0 || tile_end != 0))
-      return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "empty block has no tiles");
+// cuking_compute_kin_matrix and cuking_compute_kin_matrix_tiles.  (Every check in front of
+// anything that touches a device, the null context last among them; then the device is bound,
+// an empty block or not.)
+static cuking_status kin_matrix_call(const BlockArgs &b, const TileRange &r, float *d_kin,
+                                     uint64_t ld, uint32_t flags) {
+  return run_pair_call(b, r, BindAt::kBehindCheck, [&](Outputs *out) {
+    const cuking_submatrix *sm = b.sm;
+    const cuking_status st = check_compute_args(sm, b.words_per_sample, b.d_bit_sets);
+    if (st != CUKING_OK) return st;
+    if (flags != CUKING_KIN_UPPER && flags != CUKING_KIN_SYMMETRIC)
+      return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "unknown kinship matrix flags 0x%x", flags);
+    if (ld < sm_num_cols(*sm))
+      return cuking_fail(CUKING_ERR_INVALID_ARGUMENT,
+                         "kinship matrix: leading dimension %llu below the block's %u columns",
+                         (unsigned long long)ld, sm_num_cols(*sm));
+    if (flags == CUKING_KIN_SYMMETRIC && !sm_is_diag(*sm))
+      return cuking_fail(CUKING_ERR_INVALID_ARGUMENT,
+                         "a symmetric kinship matrix needs a diagonal block (rows == columns)");
+    if (flags == CUKING_KIN_SYMMETRIC && !r.whole)
+      return cuking_fail(CUKING_ERR_INVALID_ARGUMENT,
+                         "a symmetric kinship matrix cannot be computed by tile ranges");
+    if (sm_num_rows(*sm) != 0 && sm_num_cols(*sm) != 0 && d_kin == nullptr)
+      return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "null kinship matrix pointer");
+    if (b.ctx == nullptr) return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "null context");
+    out->form = kFormKinMatrix;
+    out->kin = d_kin;
+    out->kin_ld = ld;
+    out->kin_flags = flags;
     return CUKING_OK;
-  }
-  if (whole && ctx->kernel == CUKING_KERNEL_STREAM)
-    return run_stream(ctx, *sm, words_per_sample, d_bit_sets, 0.f, 0, nullptr, nullptr,
-                      nullptr, nullptr, (hipStream_t)stream, d_kin, ld, flags);
-  return run_tiled(ctx, *sm, words_per_sample, d_bit_sets, tile_begin, tile_end, whole, 0.f,
-                   {0, nullptr, nullptr, nullptr, nullptr, d_kin, ld, flags},
-                   (hipStream_t)stream);
+  });
 }
 
 cuking_status cuking_compute_kin_matrix(cuking_ctx *ctx, const cuking_submatrix *sm,
                                         uint32_t words_per_sample, const uint64_t *d_bit_sets,
                                         float *d_kin, uint64_t ld, uint32_t flags,
                                         void *stream) {
-  return run_kin_matrix(ctx, sm, words_per_sample, d_bit_sets, true, 0, 0, d_kin, ld, flags,
-                        stream);
+  return kin_matrix_call({ctx, sm, words_per_sample, d_bit_sets, stream}, kEveryTile, d_kin, ld,
+                         flags);
 }
 
 cuking_status cuking_compute_kin_matrix_tiles(cuking_ctx *ctx, const cuking_submatrix *sm,
@@ -1865,29 +1924,28 @@ cuking_status cuking_compute_kin_matrix_tiles(cuking_ctx *ctx, const cuking_subm
                                               const uint64_t *d_bit_sets, uint64_t tile_begin,
                                               uint64_t tile_end, float *d_kin, uint64_t ld,
                                               uint32_t flags, void *stream) {
-  return run_kin_matrix(ctx, sm, words_per_sample, d_bit_sets, false, tile_begin, tile_end,
-                        d_kin, ld, flags, stream);
+  return kin_matrix_call({ctx, sm, words_per_sample, d_bit_sets, stream},
+                         {false, tile_begin, tile_end}, d_kin, ld, flags);
 }
 
-// What the checks of the reducing calls (kinship summary, relative counts) end with, in front
-// of anything that touches a device: the tile range, the context and what it can serve.
-// `what` names the call, `form` the kernel form a context may lack.
-static cuking_status check_reducing_args(const cuking_ctx *ctx, const cuking_submatrix *sm,
-                                         uint32_t words_per_sample, bool tile_range,
-                                         uint64_t tile_begin, uint64_t tile_end,
-                                         const char *what, const char *form) {
-  if (tile_range && tile_begin > tile_end)
+// What the checks of the matrix-core-only calls (kinship summary, relative counts, PI_HAT)
+// end with, in front of anything that touches a device: the tile range, the context and what
+// it can serve.  `what` names the call, `form` the kernel form a context may lack.
+static cuking_status check_reducing_args(const BlockArgs &b, const TileRange &r, const char *what,
+                                         const char *form) {
+  const cuking_ctx *ctx = b.ctx;
+  if (!r.whole && r.begin > r.end)
     return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "tile range [%llu, %llu) is reversed",
-                       (unsigned long long)tile_begin, (unsigned long long)tile_end);
+                       (unsigned long long)r.begin, (unsigned long long)r.end);
   if (ctx == nullptr) return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "null context");
   // (run_tiled checks the range as well, but only behind the conversion: this call refuses
   //  a bad range before a device is touched)
-  if (tile_range) {
-    const bool empty = sm_num_rows(*sm) == 0 || sm_num_cols(*sm) == 0;
-    const uint64_t n_tiles = empty ? 0 : cuking_num_tiles(ctx, sm);
-    if (tile_end > n_tiles)
+  if (!r.whole) {
+    const bool empty = sm_num_rows(*b.sm) == 0 || sm_num_cols(*b.sm) == 0;
+    const uint64_t n_tiles = empty ? 0 : cuking_num_tiles(ctx, b.sm);
+    if (r.end > n_tiles)
       return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "tile range [%llu, %llu) outside [0, %llu)",
-                         (unsigned long long)tile_begin, (unsigned long long)tile_end,
+                         (unsigned long long)r.begin, (unsigned long long)r.end,
                          (unsigned long long)n_tiles);
   }
   if (ctx->kernel != CUKING_KERNEL_TILED || !is_mfma_variant(ctx->variant))
@@ -1895,67 +1953,52 @@ static cuking_status check_reducing_args(const cuking_ctx *ctx, const cuking_sub
                        "%s: served by contexts of the tiled kernel with variant 5, 6 or 7 (the "
                        "matrix-core kernels) only; the VALU variants and the stream kernel have "
                        "no %s", what, form);
-  if (!is_mfma_variant(effective_variant(ctx, words_per_sample)))
+  if (!is_mfma_variant(effective_variant(ctx, b.words_per_sample)))
     return cuking_fail(CUKING_ERR_INVALID_ARGUMENT,
                        "%s: bitsets from 2^24 sites on are not served (the matrix-core kernels "
                        "count in float32)", what);
   return CUKING_OK;
 }
 
-// The checks the two kinship-summary entry points share, in front of anything that touches
-// a device.
-static cuking_status check_summary_args(const cuking_ctx *ctx, const cuking_submatrix *sm,
-                                        uint32_t words_per_sample, const uint64_t *d_bit_sets,
-                                        const cuking_kin_bins *bins, const uint64_t *d_hist,
-                                        const uint64_t *d_best, bool tile_range,
-                                        uint64_t tile_begin, uint64_t tile_end) {
-  cuking_status st = check_compute_args(sm, words_per_sample, d_bit_sets);
-  if (st != CUKING_OK) return st;
-  if (d_hist == nullptr && d_best == nullptr)
-    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT,
-                       "kinship summary: both outputs (histogram and nearest relatives) are null");
-  if (d_hist != nullptr) {
-    if (bins == nullptr)
+// cuking_compute_kin_summary and cuking_compute_kin_summary_tiles.  (This call and the two
+// below: every check in front of anything that touches a device; an empty block returns
+// before the device is bound.)
+static cuking_status kin_summary_call(const BlockArgs &b, const TileRange &r,
+                                      const cuking_kin_bins *bins, uint64_t *d_hist,
+                                      uint64_t *d_best) {
+  return run_pair_call(b, r, BindAt::kBehindEmptyBlock, [&](Outputs *out) {
+    const cuking_status st = check_compute_args(b.sm, b.words_per_sample, b.d_bit_sets);
+    if (st != CUKING_OK) return st;
+    if (d_hist == nullptr && d_best == nullptr)
       return cuking_fail(CUKING_ERR_INVALID_ARGUMENT,
-                         "kinship summary: a histogram needs bins (null bins pointer)");
-    if (bins->num_bins == 0 || bins->num_bins > CUKING_KIN_BINS_MAX)
-      return cuking_fail(CUKING_ERR_INVALID_ARGUMENT,
-                         "kinship summary: num_bins %u outside [1, %u]", bins->num_bins,
-                         CUKING_KIN_BINS_MAX);
-    if (!kin_bins_valid(*bins))
-      return cuking_fail(CUKING_ERR_INVALID_ARGUMENT,
-                         "kinship summary: histogram bounds must be finite with lo < hi "
-                         "(lo %g, hi %g)", (double)bins->lo, (double)bins->hi);
-  }
-  return check_reducing_args(ctx, sm, words_per_sample, tile_range, tile_begin, tile_end,
-                             "kinship summary", "summary form");
-}
-
-// What the two entry points share behind their checks: `whole` = every tile of the block.
-static cuking_status run_summary(cuking_ctx *ctx, const cuking_submatrix *sm,
-                                 uint32_t words_per_sample, const uint64_t *d_bit_sets,
-                                 bool whole, uint64_t tile_begin, uint64_t tile_end,
-                                 const cuking_kin_bins *bins, uint64_t *d_hist, uint64_t *d_best,
-                                 void *stream) {
-  cuking_status st = check_summary_args(ctx, sm, words_per_sample, d_bit_sets, bins, d_hist,
-                                        d_best, !whole, tile_begin, tile_end);
-  if (st != CUKING_OK) return st;
-  if (sm_num_rows(*sm) == 0 || sm_num_cols(*sm) == 0) return CUKING_OK;
-  BIND_OR_RETURN(ctx);
-  Outputs out = {};
-  out.sum_hist = d_hist;
-  out.sum_best = d_best;
-  if (d_hist != nullptr) out.sum_bins = *bins;
-  return run_tiled(ctx, *sm, words_per_sample, d_bit_sets, tile_begin, tile_end, whole, 0.f, out,
-                   (hipStream_t)stream);
+                         "kinship summary: both outputs (histogram and nearest relatives) are null");
+    if (d_hist != nullptr) {
+      if (bins == nullptr)
+        return cuking_fail(CUKING_ERR_INVALID_ARGUMENT,
+                           "kinship summary: a histogram needs bins (null bins pointer)");
+      if (bins->num_bins == 0 || bins->num_bins > CUKING_KIN_BINS_MAX)
+        return cuking_fail(CUKING_ERR_INVALID_ARGUMENT,
+                           "kinship summary: num_bins %u outside [1, %u]", bins->num_bins,
+                           CUKING_KIN_BINS_MAX);
+      if (!kin_bins_valid(*bins))
+        return cuking_fail(CUKING_ERR_INVALID_ARGUMENT,
+                           "kinship summary: histogram bounds must be finite with lo < hi "
+                           "(lo %g, hi %g)", (double)bins->lo, (double)bins->hi);
+      out->sum_bins = *bins;
+    }
+    out->form = kFormKinSummary;
+    out->sum_hist = d_hist;
+    out->sum_best = d_best;
+    return check_reducing_args(b, r, "kinship summary", "summary form");
+  });
 }
 
 cuking_status cuking_compute_kin_summary(cuking_ctx *ctx, const cuking_submatrix *sm,
                                          uint32_t words_per_sample, const uint64_t *d_bit_sets,
                                          const cuking_kin_bins *bins, uint64_t *d_hist,
                                          uint64_t *d_best, void *stream) {
-  return run_summary(ctx, sm, words_per_sample, d_bit_sets, true, 0, 0, bins, d_hist, d_best,
-                     stream);
+  return kin_summary_call({ctx, sm, words_per_sample, d_bit_sets, stream}, kEveryTile, bins,
+                          d_hist, d_best);
 }
 
 cuking_status cuking_compute_kin_summary_tiles(cuking_ctx *ctx, const cuking_submatrix *sm,
@@ -1964,52 +2007,35 @@ cuking_status cuking_compute_kin_summary_tiles(cuking_ctx *ctx, const cuking_sub
                                                uint64_t tile_end, const cuking_kin_bins *bins,
                                                uint64_t *d_hist, uint64_t *d_best,
                                                void *stream) {
-  return run_summary(ctx, sm, words_per_sample, d_bit_sets, false, tile_begin, tile_end, bins,
-                     d_hist, d_best, stream);
+  return kin_summary_call({ctx, sm, words_per_sample, d_bit_sets, stream},
+                          {false, tile_begin, tile_end}, bins, d_hist, d_best);
 }
 
-// The checks the two relative-counts entry points share, in front of anything that touches a
-// device.
-static cuking_status check_rel_args(const cuking_ctx *ctx, const cuking_submatrix *sm,
-                                    uint32_t words_per_sample, const uint64_t *d_bit_sets,
-                                    const float *thresholds, uint32_t num_thresholds,
-                                    const uint32_t *d_counts, bool tile_range,
-                                    uint64_t tile_begin, uint64_t tile_end) {
-  cuking_status st = check_compute_args(sm, words_per_sample, d_bit_sets);
-  if (st != CUKING_OK) return st;
-  if (thresholds == nullptr)
-    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "relative counts: null thresholds pointer");
-  if (num_thresholds == 0 || num_thresholds > CUKING_REL_THRESHOLDS_MAX)
-    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT,
-                       "relative counts: num_thresholds %u outside [1, %u]", num_thresholds,
-                       CUKING_REL_THRESHOLDS_MAX);
-  if (!rel_thresholds_valid(thresholds, num_thresholds))
-    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT,
-                       "relative counts: thresholds must be finite and strictly ascending");
-  if (sm_num_samples(*sm) != 0 && d_counts == nullptr)
-    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "relative counts: null counts pointer");
-  return check_reducing_args(ctx, sm, words_per_sample, tile_range, tile_begin, tile_end,
-                             "relative counts", "counting form");
-}
-
-// What the two entry points share behind their checks: `whole` = every tile of the block.
-static cuking_status run_rel(cuking_ctx *ctx, const cuking_submatrix *sm,
-                             uint32_t words_per_sample, const uint64_t *d_bit_sets, bool whole,
-                             uint64_t tile_begin, uint64_t tile_end, const float *thresholds,
-                             uint32_t num_thresholds, uint32_t *d_counts, void *stream) {
-  cuking_status st = check_rel_args(ctx, sm, words_per_sample, d_bit_sets, thresholds,
-                                    num_thresholds, d_counts, !whole, tile_begin, tile_end);
-  if (st != CUKING_OK) return st;
-  if (sm_num_rows(*sm) == 0 || sm_num_cols(*sm) == 0) return CUKING_OK;
-  BIND_OR_RETURN(ctx);
-  Outputs out = {};
-  out.rel_counts = d_counts;
-  out.rel_num = num_thresholds;
-  for (uint32_t t = 0; t < num_thresholds; ++t) out.rel_thr[t] = thresholds[t];
-  // (the thresholded call at the lowest threshold: the filter's bound, the layout, the lean
-  //  form's cheap test all follow it)
-  return run_tiled(ctx, *sm, words_per_sample, d_bit_sets, tile_begin, tile_end, whole,
-                   thresholds[0], out, (hipStream_t)stream);
+// cuking_compute_relative_counts and cuking_compute_relative_counts_tiles.
+static cuking_status relative_counts_call(const BlockArgs &b, const TileRange &r,
+                                          const float *thresholds, uint32_t num_thresholds,
+                                          uint32_t *d_counts) {
+  return run_pair_call(b, r, BindAt::kBehindEmptyBlock, [&](Outputs *out) {
+    const cuking_status st = check_compute_args(b.sm, b.words_per_sample, b.d_bit_sets);
+    if (st != CUKING_OK) return st;
+    if (thresholds == nullptr)
+      return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "relative counts: null thresholds pointer");
+    if (num_thresholds == 0 || num_thresholds > CUKING_REL_THRESHOLDS_MAX)
+      return cuking_fail(CUKING_ERR_INVALID_ARGUMENT,
+                         "relative counts: num_thresholds %u outside [1, %u]", num_thresholds,
+                         CUKING_REL_THRESHOLDS_MAX);
+    if (!rel_thresholds_valid(thresholds, num_thresholds))
+      return cuking_fail(CUKING_ERR_INVALID_ARGUMENT,
+                         "relative counts: thresholds must be finite and strictly ascending");
+    if (sm_num_samples(*b.sm) != 0 && d_counts == nullptr)
+      return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "relative counts: null counts pointer");
+    out->form = kFormRelCounts;
+    out->kin_threshold = thresholds[0];
+    out->rel_counts = d_counts;
+    out->rel_num = num_thresholds;
+    for (uint32_t t = 0; t < num_thresholds; ++t) out->rel_thr[t] = thresholds[t];
+    return check_reducing_args(b, r, "relative counts", "counting form");
+  });
 }
 
 cuking_status cuking_compute_relative_counts(cuking_ctx *ctx, const cuking_submatrix *sm,
@@ -2017,8 +2043,8 @@ cuking_status cuking_compute_relative_counts(cuking_ctx *ctx, const cuking_subma
                                              const uint64_t *d_bit_sets, const float *thresholds,
                                              uint32_t num_thresholds, uint32_t *d_counts,
                                              void *stream) {
-  return run_rel(ctx, sm, words_per_sample, d_bit_sets, true, 0, 0, thresholds, num_thresholds,
-                 d_counts, stream);
+  return relative_counts_call({ctx, sm, words_per_sample, d_bit_sets, stream}, kEveryTile,
+                              thresholds, num_thresholds, d_counts);
 }
 
 cuking_status cuking_compute_relative_counts_tiles(cuking_ctx *ctx, const cuking_submatrix *sm,
@@ -2027,41 +2053,31 @@ cuking_status cuking_compute_relative_counts_tiles(cuking_ctx *ctx, const cuking
                                                    uint64_t tile_end, const float *thresholds,
                                                    uint32_t num_thresholds, uint32_t *d_counts,
                                                    void *stream) {
-  return run_rel(ctx, sm, words_per_sample, d_bit_sets, false, tile_begin, tile_end, thresholds,
-                 num_thresholds, d_counts, stream);
+  return relative_counts_call({ctx, sm, words_per_sample, d_bit_sets, stream},
+                              {false, tile_begin, tile_end}, thresholds, num_thresholds, d_counts);
 }
 
-// ---- unrelated set and families from the records (king_unrelated.h, king_prune.hip) --------
+// ---- PI_HAT records (king_pihat.h) ----------------------------------------------------------
 
-// What cuking_compute_pihat and cuking_compute_pihat_tiles share: the checks in front of anything
-// that touches a device, then the thresholded call's route at threshold 0 with the PI_HAT form.
-static cuking_status run_pihat(cuking_ctx *ctx, const cuking_submatrix *sm,
-                               uint32_t words_per_sample, const uint64_t *d_bit_sets, bool whole,
-                               uint64_t tile_begin, uint64_t tile_end,
-                               const cuking_pihat_model *model, float min_pi_hat, uint32_t flags,
-                               uint32_t max_results, cuking_result *d_results,
-                               uint32_t *d_result_index, uint32_t *d_result_overflow,
-                               void *stream) {
-  cuking_status st = check_compute_args(sm, words_per_sample, d_bit_sets);
-  if (st != CUKING_OK) return st;
-  st = cuking_check_pihat_args(model, flags);
-  if (st != CUKING_OK) return st;
-  if (!d_result_index || !d_result_overflow || (max_results && !d_results))
-    return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "null result pointer");
-  st = check_reducing_args(ctx, sm, words_per_sample, !whole, tile_begin, tile_end, "pi_hat",
-                           "PI_HAT form");
-  if (st != CUKING_OK) return st;
-  if (sm_num_rows(*sm) == 0 || sm_num_cols(*sm) == 0) return CUKING_OK;
-  BIND_OR_RETURN(ctx);
-  Outputs out = {};
-  out.max_results = max_results;
-  out.results = d_results;
-  out.result_index = d_result_index;
-  out.result_overflow = d_result_overflow;
-  out.pihat = PihatArgs{model->e00, model->e01, model->e02, model->e11, model->e12,
-                        min_pi_hat,  flags,      1u};
-  return run_tiled(ctx, *sm, words_per_sample, d_bit_sets, tile_begin, tile_end, whole, 0.f, out,
-                   (hipStream_t)stream);
+// cuking_compute_pihat and cuking_compute_pihat_tiles: the thresholded call's route at
+// threshold 0 (every tile, no filter) with the PI_HAT form.
+static cuking_status pihat_call(const BlockArgs &b, const TileRange &r,
+                                const cuking_pihat_model *model, float min_pi_hat, uint32_t flags,
+                                uint32_t max_results, cuking_result *d_results,
+                                uint32_t *d_result_index, uint32_t *d_result_overflow) {
+  return run_pair_call(b, r, BindAt::kBehindEmptyBlock, [&](Outputs *out) {
+    cuking_status st = check_compute_args(b.sm, b.words_per_sample, b.d_bit_sets);
+    if (st != CUKING_OK) return st;
+    st = cuking_check_pihat_args(model, flags);
+    if (st != CUKING_OK) return st;
+    if (!d_result_index || !d_result_overflow || (max_results && !d_results))
+      return cuking_fail(CUKING_ERR_INVALID_ARGUMENT, "null result pointer");
+    *out = record_outputs(kFormPiHat, 0.f, max_results, d_results, d_result_index,
+                          d_result_overflow);
+    out->pihat = PihatArgs{model->e00, model->e01, model->e02, model->e11, model->e12,
+                           min_pi_hat, flags, 1u};
+    return check_reducing_args(b, r, "pi_hat", "PI_HAT form");
+  });
 }
 
 cuking_status cuking_compute_pihat(cuking_ctx *ctx, const cuking_submatrix *sm,
@@ -2070,8 +2086,8 @@ cuking_status cuking_compute_pihat(cuking_ctx *ctx, const cuking_submatrix *sm,
                                    uint32_t flags, uint32_t max_results, cuking_result *d_results,
                                    uint32_t *d_result_index, uint32_t *d_result_overflow,
                                    void *stream) {
-  return run_pihat(ctx, sm, words_per_sample, d_bit_sets, true, 0, 0, model, min_pi_hat, flags,
-                   max_results, d_results, d_result_index, d_result_overflow, stream);
+  return pihat_call({ctx, sm, words_per_sample, d_bit_sets, stream}, kEveryTile, model,
+                    min_pi_hat, flags, max_results, d_results, d_result_index, d_result_overflow);
 }
 
 cuking_status cuking_compute_pihat_tiles(cuking_ctx *ctx, const cuking_submatrix *sm,
@@ -2081,10 +2097,12 @@ cuking_status cuking_compute_pihat_tiles(cuking_ctx *ctx, const cuking_submatrix
                                          uint32_t flags, uint32_t max_results,
                                          cuking_result *d_results, uint32_t *d_result_index,
                                          uint32_t *d_result_overflow, void *stream) {
-  return run_pihat(ctx, sm, words_per_sample, d_bit_sets, false, tile_begin, tile_end, model,
-                   min_pi_hat, flags, max_results, d_results, d_result_index, d_result_overflow,
-                   stream);
+  return pihat_call({ctx, sm, words_per_sample, d_bit_sets, stream},
+                    {false, tile_begin, tile_end}, model, min_pi_hat, flags, max_results,
+                    d_results, d_result_index, d_result_overflow);
 }
+
+// ---- unrelated set and families from the records (king_unrelated.h, king_prune.hip) --------
 
 cuking_status cuking_unrelated_set(cuking_ctx *ctx, const cuking_result *d_records,
                                    uint64_t num_records, uint32_t num_samples,

@@ -587,50 +587,50 @@ constexpr uint32_t kMfmaLdsBytes = kMfmaStages * 2 * 2 * 2 * 128 * 16;
 constexpr uint32_t kMfmaParkBytes = 4 * 64 * 64 * 4;
 static_assert(kMfmaLdsBytes + kMfmaParkBytes <= 160 * 1024, "LDS of one CU");
 const TiledVariant &tiled_variant(int v);
-// Enqueues tiles [args.tile_begin, args.tile_begin + num_tiles).
+// Enqueues tiles [args.tile_begin, args.tile_begin + num_tiles) of a geometry whose tile
+// edge is `plan_tile`, for the call form sw.form (king_launch_plan.h kCallForms: the form
+// says which kernels can serve it and which k loops; no launcher looks at the output
+// pointers to find out).  `variant`: the kernel variant that runs.  Where its tile edge is
+// half the geometry's -- the filter variant's 256-sample tiles under a 128-tile kernel: a
+// wide bitset, or a call the filter does not run for (sw.filter_runs, king_abi.hip
+// filter_runs: the same answer decides whether the four-product kernel's codes are converted
+// up front) -- the tiles go out as their quadrants; this is the one place that says so.
 // full = accumulate all five sums for every pair (needed for the diagnostic
 // counts; chosen when nearly every pair is expected to pass the threshold);
 // otherwise the lean form: four sums in the main loop, IBS2 recounted for
 // emitted pairs only.  Same records either way.
 // `args`: the call's base arguments (no launch mode set: whole tiles in plain order);
-// every launcher fills the fields of its own modes from its plan.  The filter variant
-// runs its filter kernel iff sw.filter_runs (king_abi.hip filter_runs: the same answer
-// decides whether the four-product kernel's codes are converted up front).
-hipError_t launch_tiled(int variant, bool full, const TiledArgs &args, const LaunchSwitches &sw,
-                        uint64_t num_tiles, hipStream_t stream);
-// The matrix-core kernel (king_mfma.hip); reached through launch_tiled.
+// every launcher fills the fields of its own modes from its plan.
+hipError_t launch_tiled(int variant, uint32_t plan_tile, bool full, const TiledArgs &args,
+                        const LaunchSwitches &sw, uint64_t num_tiles, hipStream_t stream);
+// The matrix-core kernels (king_mfma.hip), every form of them, reached through launch_tiled:
+// the k loop of the four-product (nibble) or the five-product kernel and the epilogue of
+// sw.form -- records, counts, a stored or a reduced float32 kinship of every pair, relative
+// counts, PI_HAT records -- under one launch plan (chunking, XCD order, dynamic tail,
+// remainder split).  Refuses a form with the k loop it does not have (kernel_form) and
+// device arguments that lack what the form's epilogue reads.  lds_bytes: the variant
+// table's figure, which only the five-product full form goes by.
 hipError_t launch_mfma(bool full, bool nibble, const TiledArgs &args, const LaunchSwitches &sw,
                        uint64_t num_tiles, uint32_t lds_bytes, hipStream_t stream);
-// The matrix-core kernels' dense-kinship form (TiledArgs::dense_kin; king_mfma.hip, KIN):
-// the lean k loop of the four-product (nibble) or the five-product kernel, and an epilogue
-// that stores the float32 kinship of every pair.  Same launch plan as launch_mfma
-// (chunking, XCD order, dynamic tail, remainder split).
-hipError_t launch_mfma_kin(bool nibble, const TiledArgs &args, const LaunchSwitches &sw,
-                           uint64_t num_tiles, hipStream_t stream);
-// The matrix-core kernels' kinship-summary form (TiledArgs::sum_hist / sum_best; king_mfma.hip,
-// summarise_kin): the same lean k loops and launch plan, and an epilogue that reduces the
-// kinship of a tile's pairs in LDS instead of storing it.
-hipError_t launch_mfma_summary(bool nibble, const TiledArgs &args, const LaunchSwitches &sw,
-                               uint64_t num_tiles, hipStream_t stream);
-// (The relative-counts form, TiledArgs::rel_counts, has no launcher of its own: it IS the
-// thresholded call, so launch_mfma, launch_mfma_list, launch_mfma_gated and launch_filter pick
-// their counting kernels on the host when args.rel_counts is set; lean forms only.)
 // Symmetric fill of an n x n kinship matrix whose upper triangle (and diagonal) is there:
 // kin[j * ld + i] = kin[i * ld + j] for i < j, tile-wise through LDS, reads and writes
 // coalesced.  Runs behind the pair kernel on the same stream.
 hipError_t launch_kin_mirror(float *d_kin, uint64_t ld, uint32_t n, hipStream_t stream);
 // The four-product kernel, lean form, over the first min(*count, cap) entries of the device
-// list `list` (TiledArgs::tile_list) with `grid` workgroups.
-hipError_t launch_mfma_list(const TiledArgs &args, const uint2 *list, const uint32_t *count,
-                            uint32_t cap, uint32_t grid, hipStream_t stream);
+// list `list` (TiledArgs::tile_list) with `grid` workgroups.  This and the next one run
+// behind the filter kernel, for the forms it serves: `form` is records or relative counts.
+hipError_t launch_mfma_list(CallForm form, const TiledArgs &args, const uint2 *list,
+                            const uint32_t *count, uint32_t cap, uint32_t grid,
+                            hipStream_t stream);
 // The four-product kernel, lean form, persistent mode (TiledArgs::gate): `grid`
 // workgroups walk num_units units from args.tile_begin on, if *gate != 0, skipping the
 // quadrants of tiles with skip_tiles[tile - skip_base] != 0.
-hipError_t launch_mfma_gated(const TiledArgs &args, uint64_t num_units, const uint32_t *gate,
-                             const uint8_t *skip_tiles, uint64_t skip_base, uint32_t grid,
-                             hipStream_t stream);
+hipError_t launch_mfma_gated(CallForm form, const TiledArgs &args, uint64_t num_units,
+                             const uint32_t *gate, const uint8_t *skip_tiles, uint64_t skip_base,
+                             uint32_t grid, hipStream_t stream);
 // The filter variant (king_filter.hip): num_tiles 256-sample tiles from
-// args.tile_begin; needs args.filter_ctrl etc. (king_abi.hip: filter scratch).
+// args.tile_begin; needs args.filter_ctrl etc. (king_abi.hip: filter scratch).  sw.form says
+// whether its exact kernels append records or count relatives.
 hipError_t launch_filter(const TiledArgs &args, const LaunchSwitches &sw, uint64_t num_tiles,
                          hipStream_t stream);
 // Quadrant mode (TiledArgs::quad): the launch of *num_units 256-sample tiles from

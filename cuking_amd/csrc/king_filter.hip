@@ -1394,7 +1394,10 @@ hipError_t launch_filter(const TiledArgs &args, const LaunchSwitches &switches, 
   if ((uint64_t)args.geo.k_words * 32 > kMfmaN4MaxSites || args.filter_ctrl == nullptr ||
       args.cand_list == nullptr || args.dense_list == nullptr || args.sample_stats == nullptr)
     return hipErrorInvalidValue;
-  if (args.rel_counts != nullptr && (args.rel_num == 0 || args.rel_num > CUKING_REL_THRESHOLDS_MAX))
+  const bool count = switches.form == kFormRelCounts;  // the counting form of the exact kernels
+  if (!count && switches.form != kFormRecords) return hipErrorInvalidValue;
+  if (count && (args.rel_counts == nullptr || args.rel_num == 0 ||
+                args.rel_num > CUKING_REL_THRESHOLDS_MAX))
     return hipErrorInvalidValue;
   hipError_t e = allow_dynamic_lds<king_filter_kernel>(kFilterLdsBytes);
   if (e != hipSuccess) return e;
@@ -1445,7 +1448,7 @@ hipError_t launch_filter(const TiledArgs &args, const LaunchSwitches &switches, 
     e = hipGetLastError();
     if (e != hipSuccess) return e;
     // (a relative-counts call: the counting form; so do the two launches below)
-    if (a.rel_counts != nullptr) king_refine_count_kernel<<<dim3(wgs * 4), dim3(256), 0, stream>>>(a);
+    if (count) king_refine_count_kernel<<<dim3(wgs * 4), dim3(256), 0, stream>>>(a);
     else king_refine_kernel<<<dim3(wgs * 4), dim3(256), 0, stream>>>(a);
     e = hipGetLastError();
     if (e != hipSuccess) return e;
@@ -1460,8 +1463,8 @@ hipError_t launch_filter(const TiledArgs &args, const LaunchSwitches &switches, 
       if (e != hipSuccess) return e;
     }
     // the quadrants that went dense
-    e = launch_mfma_list(chunk, args.dense_list, args.filter_ctrl + kCtrlDense, args.dense_cap,
-                         wgs, stream);
+    e = launch_mfma_list(sw.form, chunk, args.dense_list, args.filter_ctrl + kCtrlDense,
+                         args.dense_cap, wgs, stream);
     if (e != hipSuccess) return e;
     if (checks) {
       // The fallback: every tile of the chunk that has not set its flag (it left at
@@ -1470,7 +1473,7 @@ hipError_t launch_filter(const TiledArgs &args, const LaunchSwitches &switches, 
       TiledArgs f = chunk;
       uint64_t units = p.n;
       to_quadrants(&f, &units);
-      e = launch_mfma_gated(f, units, args.filter_ctrl + kCtrlGate, args.tile_done,
+      e = launch_mfma_gated(sw.form, f, units, args.filter_ctrl + kCtrlGate, args.tile_done,
                             chunk.tile_begin, wgs, stream);
       if (e != hipSuccess) return e;
     }

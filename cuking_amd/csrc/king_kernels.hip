@@ -727,9 +727,22 @@ uint64_t max_blocks_per_launch(uint32_t threads) {
 
 const TiledVariant &tiled_variant(int v) { return kVariants[v]; }
 
-hipError_t launch_tiled(int variant, bool full, const TiledArgs &args, const LaunchSwitches &sw,
-                        uint64_t num_tiles, hipStream_t stream) {
+hipError_t launch_tiled(int variant, uint32_t plan_tile, bool full, const TiledArgs &base,
+                        const LaunchSwitches &sw, uint64_t num_tiles, hipStream_t stream) {
+  if (variant < 0 || variant >= kNumTiledVariants || sw.form < 0 || sw.form >= kNumCallForms ||
+      (!is_mfma_variant(variant) && !kCallForms[sw.form].valu_serves))
+    return hipErrorInvalidValue;
   if (num_tiles == 0) return hipSuccess;
+  if (variant == kMfmaFilterVariant && sw.filter_runs) return launch_filter(base, sw, num_tiles, stream);
+  // Where the bound does not help (LaunchSwitches::filter_runs) the filter variant is the
+  // four-product kernel ...
+  if (variant == kMfmaFilterVariant) variant = kMfmaN4Variant;
+  // ... and a kernel of half the geometry's tile edge runs on the quadrants of its tiles.
+  TiledArgs args = base;
+  if (kVariants[variant].tile != plan_tile) {
+    if (kVariants[variant].tile * 2 != plan_tile) return hipErrorInvalidValue;
+    to_quadrants(&args, &num_tiles);
+  }
   const uint32_t lds = kVariants[variant].lds_bytes;
 #define CUKING_SHAPE(...)                                                      \
   (full ? launch_variant<__VA_ARGS__, true>(args, num_tiles, lds, stream)      \
@@ -744,14 +757,6 @@ hipError_t launch_tiled(int variant, bool full, const TiledArgs &args, const Lau
     case 4: return CUKING_SHAPE(16, 16, 4, 4, 16, 2, 4);
     case kMfmaVariant: return launch_mfma(full, false, args, sw, num_tiles, lds, stream);
     case kMfmaN4Variant: return launch_mfma(full, true, args, sw, num_tiles, lds, stream);
-    case kMfmaFilterVariant: {
-      // Where the bound does not help (LaunchSwitches::filter_runs) the four-product
-      // kernel runs on the quadrants of the same 256-sample tiles.
-      if (sw.filter_runs) return launch_filter(args, sw, num_tiles, stream);
-      TiledArgs a = args;
-      to_quadrants(&a, &num_tiles);
-      return launch_mfma(full, true, a, sw, num_tiles, kMfmaN4LdsBytes, stream);
-    }
     default: return hipErrorInvalidValue;
   }
 #undef CUKING_SHAPE

@@ -12,7 +12,58 @@
 
 namespace cuking {
 
-// The context's switches for one call (king_abi.hip launch_args): host side only, the
+// The pair calls, by what they produce.  The entry point (king_abi.hip) names its form once;
+// every layer below reads the rules of that form from kCallForms and works nothing out from
+// the output pointers.  Host side only: the kernels read the pointers of TiledArgs.
+enum CallForm : int {
+  kFormRecords,     // records of the pairs above a kinship threshold
+  kFormCounts,      // the five sums of every pair (cuking_compute_counts)
+  kFormKinMatrix,   // float32 kinship of every pair, stored
+  kFormKinSummary,  // float32 kinship of every pair, reduced: histogram, nearest relative
+  kFormRelCounts,   // the thresholded call counted per sample, no records
+  kFormPiHat,       // records of the pairs above a PI_HAT threshold
+  kNumCallForms
+};
+// The k loop a form runs: the full one (five sums of every pair), the lean one (four sums,
+// the fifth recounted where it is needed), or whichever the threshold makes cheaper.
+enum KLoop : int { kLoopEither, kLoopFull, kLoopLean };
+// KIN of king_mfma_kernel (king_mfma.hip): the epilogue behind the k loop.
+constexpr int kRecords = 0, kKinMatrix = 1, kKinSummary = 2, kRelCounts = 3, kPiHat = 4;
+
+struct CallFormRules {
+  const char *name;  // as the messages say it
+  KLoop k_loop;
+  // The layout keeps the samples in stored order (no sort, TiledArgs::perm null): the form
+  // writes per pair by position, or gains nothing from the filter's order.
+  bool unsorted;
+  // The filter's bound (one on KING kinship against a threshold) may apply; whether it does
+  // depends on the variant and the threshold as well (king_abi.hip filter_runs).
+  bool filter_may_run;
+  // The VALU variants and the stream kernel can serve it (they store a matrix from their
+  // full form); otherwise the matrix-core kernels only.
+  bool valu_serves;
+  int kin;  // the matrix-core kernel's KIN
+};
+constexpr CallFormRules kCallForms[kNumCallForms] = {
+    {"records", kLoopEither, false, true, true, kRecords},
+    {"counts", kLoopFull, false, false, true, kRecords},
+    {"kinship matrix", kLoopLean, true, false, true, kKinMatrix},
+    {"kinship summary", kLoopLean, true, false, false, kKinSummary},
+    {"relative counts", kLoopLean, false, true, false, kRelCounts},
+    {"pi_hat", kLoopFull, false, false, false, kPiHat},
+};
+static_assert(kCallForms[kNumCallForms - 1].name != nullptr, "a row for every form");
+// The instantiations of king_mfma_kernel by <KIN, FULL>: the records kind has both k loops,
+// every other kind one.  -1: the form does not run with that k loop.
+constexpr int kNumKernelForms = 6;
+constexpr int kernel_form(CallForm form, bool full) {
+  if (form < 0 || form >= kNumCallForms) return -1;
+  const CallFormRules &r = kCallForms[form];
+  if (r.k_loop != kLoopEither && full != (r.k_loop == kLoopFull)) return -1;
+  return r.kin == kRecords ? (full ? 1 : 0) : r.kin + 1;
+}
+
+// The context's switches for one call (king_abi.hip launch_switches): host side only, the
 // kernels never see them.
 struct LaunchSwitches {
   // Matrix-core kernels, whole-tile launches: XCD-aware order 0 off / 1 one contiguous
@@ -29,6 +80,8 @@ struct LaunchSwitches {
   // (0, 1/2)): the filter kernel runs, and the four-product kernel's codes may stay
   // unconverted until it asks for them.
   bool filter_runs;
+  // The call's form: which kernels a launcher picks.
+  CallForm form;
 };
 
 // One whole-tile launch: workgroup b < launch_tiles (plus padding) takes a tile by its

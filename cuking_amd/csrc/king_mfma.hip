@@ -1617,7 +1617,7 @@ __device__ __forceinline__ void count_relatives(const TiledArgs &a, const Segmen
 // (SPLIT, a partial tile) -> epilogue.
 // kPiHat: the PI_HAT record form (TiledArgs::pihat), the only kind besides kRecords with FULL
 // -- and with FULL only: the full form's two passes and an epilogue that decides on PI_HAT.
-constexpr int kRecords = 0, kKinMatrix = 1, kKinSummary = 2, kRelCounts = 3, kPiHat = 4;  // KIN
+// (The kinds' values: king_launch_plan.h.)
 template <bool FULL, bool SPLIT, bool N4 = false, int KIN = kRecords>
 __global__ __launch_bounds__(256, 1) void king_mfma_kernel(const TiledArgs a) {
   static_assert(KIN == kRecords || (KIN == kPiHat ? FULL : !FULL),
@@ -1715,50 +1715,46 @@ size_t mfma_split_scratch_bytes(uint32_t wgs) {
 size_t mfma_split_counter_bytes(uint32_t wgs) { return split_counter_bytes(wgs); }
 
 namespace {
-// launch_shape<FULL, SPLIT, N4, KIN> by run-time flags (kin: kKinMatrix / kKinSummary /
-// kRelCounts, which are lean; kPiHat, which is full)
-hipError_t launch_form(bool full, bool split, bool nibble, int kin, const TiledArgs &a,
-                       const LaunchSwitches &sw, uint64_t blocks, uint32_t lds_bytes,
-                       hipStream_t stream) {
-  if (kin < kRecords || kin > kPiHat || (kin != kRecords && full != (kin == kPiHat)))
-    return hipErrorInvalidValue;
-  using Launch = hipError_t (*)(const TiledArgs &, const LaunchSwitches &, uint64_t, uint32_t,
-                                hipStream_t);
-  static constexpr Launch kForms[5][2][2][2] = {  // [kin][nibble][split][full]
-      {{{launch_shape<false, false, false>, launch_shape<true, false, false>},
-        {launch_shape<false, true, false>, launch_shape<true, true, false>}},
-       {{launch_shape<false, false, true>, launch_shape<true, false, true>},
-        {launch_shape<false, true, true>, launch_shape<true, true, true>}}},
-      {{{launch_shape<false, false, false, kKinMatrix>, nullptr},
-        {launch_shape<false, true, false, kKinMatrix>, nullptr}},
-       {{launch_shape<false, false, true, kKinMatrix>, nullptr},
-        {launch_shape<false, true, true, kKinMatrix>, nullptr}}},
-      {{{launch_shape<false, false, false, kKinSummary>, nullptr},
-        {launch_shape<false, true, false, kKinSummary>, nullptr}},
-       {{launch_shape<false, false, true, kKinSummary>, nullptr},
-        {launch_shape<false, true, true, kKinSummary>, nullptr}}},
-      {{{launch_shape<false, false, false, kRelCounts>, nullptr},
-        {launch_shape<false, true, false, kRelCounts>, nullptr}},
-       {{launch_shape<false, false, true, kRelCounts>, nullptr},
-        {launch_shape<false, true, true, kRelCounts>, nullptr}}},
-      {{{nullptr, launch_shape<true, false, false, kPiHat>},
-        {nullptr, launch_shape<true, true, false, kPiHat>}},
-       {{nullptr, launch_shape<true, false, true, kPiHat>},
-        {nullptr, launch_shape<true, true, true, kPiHat>}}}};
-  return kForms[kin][nibble][split][full](a, sw, blocks, lds_bytes, stream);
+using Launch = hipError_t (*)(const TiledArgs &, const LaunchSwitches &, uint64_t, uint32_t,
+                              hipStream_t);
+// launch_shape<FULL, SPLIT, N4, KIN> by run-time flags, for the six kernel forms of
+// kernel_form() (king_launch_plan.h): the records kind, which has both k loops, ...
+constexpr Launch kRecordForms[2][2][2] = {  // [nibble][split][full]
+    {{launch_shape<false, false, false>, launch_shape<true, false, false>},
+     {launch_shape<false, true, false>, launch_shape<true, true, false>}},
+    {{launch_shape<false, false, true>, launch_shape<true, false, true>},
+     {launch_shape<false, true, true>, launch_shape<true, true, true>}}};
+// ... and every other kind, which has one.
+#define CUKING_KIND(FULL, KIN)                                                       \
+  {{launch_shape<FULL, false, false, KIN>, launch_shape<FULL, true, false, KIN>},    \
+   {launch_shape<FULL, false, true, KIN>, launch_shape<FULL, true, true, KIN>}}
+constexpr Launch kKindForms[kNumKernelForms - 2][2][2] = {  // [kernel form - 2][nibble][split]
+    CUKING_KIND(false, kKinMatrix), CUKING_KIND(false, kKinSummary),
+    CUKING_KIND(false, kRelCounts), CUKING_KIND(true, kPiHat)};
+#undef CUKING_KIND
+static_assert(kKindForms[kNumKernelForms - 3][1][1] != nullptr, "a row for every kind");
+Launch launch_of(int kernel_form, bool nibble, bool split) {
+  return kernel_form < 2 ? kRecordForms[nibble][split][kernel_form]
+                         : kKindForms[kernel_form - 2][nibble][split];
 }
 
-// ONE launch of the four-product kernel's lean form with `grid` workgroups that stride over
-// a list or a range, whatever the block limit (a test hook may set it below `grid`; a
-// second launch would walk the list again).
-// The form a thresholded launch runs: records, or (TiledArgs::rel_counts) relative counts --
-// chosen here, on the host.
-int lean_form_of(const TiledArgs &a) { return a.rel_counts != nullptr ? kRelCounts : kRecords; }
-// ... and a planned one: the PI_HAT form (TiledArgs::pihat) is the full form's.
-int planned_form_of(const TiledArgs &a) { return a.pihat.on != 0 ? kPiHat : lean_form_of(a); }
-bool rel_args_ok(const TiledArgs &a) {
-  return a.rel_counts == nullptr || (a.rel_num >= 1 && a.rel_num <= CUKING_REL_THRESHOLDS_MAX);
+// What a form's kernels read of the device arguments, checked in front of any launch.
+bool form_args_ok(CallForm form, const TiledArgs &a) {
+  switch (form) {
+    case kFormKinMatrix:  // (stored by position: an unsorted layout)
+      return a.dense_kin != nullptr && a.perm == nullptr;
+    case kFormKinSummary:
+      // (the tile's histogram sits in LDS: kMfmaSummaryLdsBytes)
+      return (a.sum_hist != nullptr || a.sum_best != nullptr) && a.perm == nullptr &&
+             (a.sum_hist == nullptr || (a.sum_bins >= 1 && a.sum_bins <= CUKING_KIN_BINS_MAX));
+    case kFormRelCounts:
+      return a.rel_counts != nullptr && a.rel_num >= 1 && a.rel_num <= CUKING_REL_THRESHOLDS_MAX;
+    case kFormPiHat:  // (records, and neither counts nor a matrix)
+      return a.pihat.on != 0 && a.dense_counts == nullptr;
+    default: return true;
+  }
 }
+
 template <int KIN>
 hipError_t launch_strided_form(const TiledArgs &a, uint32_t grid, hipStream_t stream) {
   constexpr auto kernel = king_mfma_kernel<false, false, true, KIN>;
@@ -1767,18 +1763,25 @@ hipError_t launch_strided_form(const TiledArgs &a, uint32_t grid, hipStream_t st
   kernel<<<dim3(grid), dim3(256), kMfmaN4LdsBytes, stream>>>(a);
   return hipGetLastError();
 }
-hipError_t launch_strided(const TiledArgs &a, uint32_t grid, hipStream_t stream) {
-  if ((uint64_t)a.geo.k_words * 32 > kMfmaN4MaxSites || !rel_args_ok(a)) return hipErrorInvalidValue;
+// ONE launch of the four-product kernel's lean form with `grid` workgroups that stride over
+// a list or a range, whatever the block limit (a test hook may set it below `grid`; a
+// second launch would walk the list again).  Behind the filter kernel only: the forms its
+// bound may apply to.
+hipError_t launch_strided(CallForm form, const TiledArgs &a, uint32_t grid, hipStream_t stream) {
+  if ((uint64_t)a.geo.k_words * 32 > kMfmaN4MaxSites || kernel_form(form, false) < 0 ||
+      !kCallForms[form].filter_may_run || !form_args_ok(form, a))
+    return hipErrorInvalidValue;
   const uint64_t cap = max_blocks_per_launch(256);
   if (grid > cap) grid = (uint32_t)cap;
   if (grid == 0) return hipErrorInvalidValue;
-  return lean_form_of(a) == kRelCounts ? launch_strided_form<kRelCounts>(a, grid, stream)
-                                       : launch_strided_form<kRecords>(a, grid, stream);
+  return form == kFormRelCounts ? launch_strided_form<kRelCounts>(a, grid, stream)
+                                : launch_strided_form<kRecords>(a, grid, stream);
 }
 }  // namespace
 
-hipError_t launch_mfma_list(const TiledArgs &args, const uint2 *list, const uint32_t *count,
-                            uint32_t cap, uint32_t grid, hipStream_t stream) {
+hipError_t launch_mfma_list(CallForm form, const TiledArgs &args, const uint2 *list,
+                            const uint32_t *count, uint32_t cap, uint32_t grid,
+                            hipStream_t stream) {
   if (list == nullptr) return hipErrorInvalidValue;
   TiledArgs a = args;
   a.tile_begin = 0;  // (the entries are tiles of the block, not of a range or a rectangle)
@@ -1786,70 +1789,39 @@ hipError_t launch_mfma_list(const TiledArgs &args, const uint2 *list, const uint
   a.tile_list = list;
   a.tile_list_count = count;
   a.tile_list_cap = cap;
-  return launch_strided(a, grid, stream);
+  return launch_strided(form, a, grid, stream);
 }
 
-hipError_t launch_mfma_gated(const TiledArgs &args, uint64_t num_units, const uint32_t *gate,
-                             const uint8_t *skip_tiles, uint64_t skip_base, uint32_t grid,
-                             hipStream_t stream) {
+hipError_t launch_mfma_gated(CallForm form, const TiledArgs &args, uint64_t num_units,
+                             const uint32_t *gate, const uint8_t *skip_tiles, uint64_t skip_base,
+                             uint32_t grid, hipStream_t stream) {
   if (gate == nullptr || num_units > 0xFFFFFFFFull) return hipErrorInvalidValue;
   TiledArgs a = args;
   a.gate = gate;
   a.gate_count = (uint32_t)num_units;
   a.skip_tiles = skip_tiles;
   a.skip_base = skip_base;
-  return launch_strided(a, grid, stream);
+  return launch_strided(form, a, grid, stream);
 }
 
-namespace {
-hipError_t launch_planned_form(bool full, bool nibble, int kin, const TiledArgs &args,
-                               const LaunchSwitches &sw, uint64_t num_tiles, uint32_t lds_bytes,
-                               hipStream_t stream) {
-  if ((uint64_t)args.geo.k_words * 32 > (nibble ? kMfmaN4MaxSites : kMfmaMaxSites))
+hipError_t launch_mfma(bool full, bool nibble, const TiledArgs &args, const LaunchSwitches &sw,
+                       uint64_t num_tiles, uint32_t lds_bytes, hipStream_t stream) {
+  const int kf = kernel_form(sw.form, full);
+  if (kf < 0 || !form_args_ok(sw.form, args) ||
+      (uint64_t)args.geo.k_words * 32 > (nibble ? kMfmaN4MaxSites : kMfmaMaxSites))
     return hipErrorInvalidValue;
   // Whole tiles first, then ONE launch of whole tiles and the remainder in pieces
   // (king_launch_plan.h mfma_plan).  (Never split without scratch for the pieces.)
   const MfmaPlan p = mfma_plan(num_tiles, args.split_scratch != nullptr ? args.split_wgs : 0,
                                args.geo.k_words / 8, max_blocks_per_launch(256));
-  hipError_t e = launch_form(full, false, nibble, kin, args, sw, p.first, lds_bytes, stream);
+  hipError_t e = launch_of(kf, nibble, false)(args, sw, p.first, lds_bytes, stream);
   if (e != hipSuccess || p.split_tiles == 0) return e;
   TiledArgs a = args;
   a.tile_begin = args.tile_begin + p.first;
   a.split_whole = p.split_whole;
   a.split_tiles = p.split_tiles;
-  return launch_form(full, true, nibble, kin, a, sw, (uint64_t)p.split_whole + args.split_wgs,
-                     lds_bytes, stream);
-}
-}  // namespace
-
-hipError_t launch_mfma(bool full, bool nibble, const TiledArgs &args, const LaunchSwitches &sw,
-                       uint64_t num_tiles, uint32_t lds_bytes, hipStream_t stream) {
-  // (a relative-counts call, TiledArgs::rel_counts: the counting form, lean only)
-  if (!rel_args_ok(args)) return hipErrorInvalidValue;
-  // (a PI_HAT call, TiledArgs::pihat: the full form only, and neither counts nor a matrix)
-  if (args.pihat.on != 0 && (!full || args.rel_counts != nullptr || args.dense_counts != nullptr))
-    return hipErrorInvalidValue;
-  return launch_planned_form(full, nibble, planned_form_of(args), args, sw, num_tiles, lds_bytes,
-                             stream);
-}
-
-hipError_t launch_mfma_kin(bool nibble, const TiledArgs &args, const LaunchSwitches &sw,
-                           uint64_t num_tiles, hipStream_t stream) {
-  if (args.dense_kin == nullptr || args.perm != nullptr) return hipErrorInvalidValue;
-  if (num_tiles == 0) return hipSuccess;
-  // (the lean forms size their LDS themselves: launch_shape)
-  return launch_planned_form(false, nibble, kKinMatrix, args, sw, num_tiles, 0, stream);
-}
-
-hipError_t launch_mfma_summary(bool nibble, const TiledArgs &args, const LaunchSwitches &sw,
-                               uint64_t num_tiles, hipStream_t stream) {
-  if ((args.sum_hist == nullptr && args.sum_best == nullptr) || args.perm != nullptr)
-    return hipErrorInvalidValue;
-  // (the tile's histogram sits in LDS: kMfmaSummaryLdsBytes)
-  if (args.sum_hist != nullptr && (args.sum_bins == 0 || args.sum_bins > CUKING_KIN_BINS_MAX))
-    return hipErrorInvalidValue;
-  if (num_tiles == 0) return hipSuccess;
-  return launch_planned_form(false, nibble, kKinSummary, args, sw, num_tiles, 0, stream);
+  return launch_of(kf, nibble, true)(a, sw, (uint64_t)p.split_whole + args.split_wgs, lds_bytes,
+                                     stream);
 }
 
 // ---- symmetric fill of a dense kinship matrix --------------------------------------------

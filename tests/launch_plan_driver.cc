@@ -136,7 +136,29 @@ static void both(uint64_t t, uint32_t wgs, uint64_t cap, uint32_t steps, int sw)
   filter_line(t, wgs, cap, steps, kFilterCases[sw]);
 }
 
+// "--forms": the rules of the call forms (kCallForms), one line per form:
+//   <form index> <name> | <k loop> <unsorted> <filter_may_run> <valu_serves> | lean <kernel>
+//   full <kernel>        <kernel> = <KIN> <FULL> <kernel_form()>, or "refused"
+static int print_forms() {
+  static const char *const kLoops[] = {"either", "full", "lean"};
+  for (int f = 0; f < kNumCallForms; ++f) {
+    const CallFormRules &r = kCallForms[f];
+    printf("%d %s | %s %d %d %d |", f, r.name, kLoops[r.k_loop], r.unsorted, r.filter_may_run,
+           r.valu_serves);
+    for (int full = 0; full < 2; ++full) {
+      const int kf = kernel_form((CallForm)f, full != 0);
+      if (kf < 0) printf(" %s refused", full ? "full" : "lean");
+      else printf(" %s %d %d %d", full ? "full" : "lean", r.kin, full, kf);
+    }
+    printf("\n");
+  }
+  // (a form outside the table is refused, not read)
+  printf("outside %d %d\n", kernel_form((CallForm)-1, false), kernel_form(kNumCallForms, true));
+  return 0;
+}
+
 int main(int argc, char **argv) {
+  if (argc > 1 && strcmp(argv[1], "--forms") == 0) return print_forms();
   const bool all = argc > 1 && strcmp(argv[1], "--all") == 0;
   // Readable part: every count at the defaults (256 CUs, no block limit, 100k sites), then a
   // few counts with one input changed at a time (a block limit: lines of at most 16 launches).

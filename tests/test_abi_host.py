@@ -362,3 +362,26 @@ def test_default_variant_and_its_tile_geometry_without_a_context():
         assert lib.cuking_tile_samples(None) == 256
         sm = cuking_amd.Submatrix(100_000)
         assert lib.cuking_num_tiles(None, C.byref(sm.c)) == 391 * 392 // 2
+
+
+def test_pair_calls_without_a_context_keep_their_order_of_checks():
+    """What the five X / X_tiles pairs report first when the context is null as well.  The
+    records call binds before it checks anything; the other four check their arguments in
+    front of anything that touches a device and name the null context last -- but in front
+    of the tile range's bounds, which need the context's tile edge."""
+    import pair_call_cases as pcc
+    lib = _lib.load()
+    sm = cuking_amd.Submatrix(10)
+    bits = 1 << 12
+    for tiles in (None, (0, 1)):
+        for name in pcc.CALLS:
+            assert pcc.refused(lib, name, None, sm, bits, tiles) == "null context"
+        assert pcc.refused(lib, "king", None, sm, bits, tiles, out=None) == "null context"
+        assert pcc.refused(lib, "king", None, sm, None, tiles, wps=3) == "null context"
+        for name in pcc.CALLS[1:]:
+            assert pcc.refused(lib, name, None, sm, bits, tiles, out=None) == pcc.NO_RESULT[name]
+    # a reversed range needs no context to be refused; one past the block's tiles does
+    assert pcc.refused(lib, "kin_matrix", None, sm, bits, (2, 1)) == "null context"
+    for name in pcc.MATRIX_CORE_ONLY:
+        assert pcc.refused(lib, name, None, sm, bits, (2, 1)) == "tile range [2, 1) is reversed"
+        assert pcc.refused(lib, name, None, sm, bits, (0, 99)) == "null context"

@@ -1508,3 +1508,42 @@ def test_filter_variant_gives_up_on_a_cohort_its_bound_cannot_thin_out(ctx, orac
         assert dense > 6 * 600
     else:
         assert dense > 0
+
+
+def test_pair_call_argument_errors(ctx):
+    """Status and message of the invalid calls of the five X / X_tiles pairs on a context
+    (tests/test_abi_host.py has the null context): a null result pointer, a reversed and an
+    out-of-range tile range, a tile range on an empty block, and a context without
+    matrix-core kernels for the three forms only they serve.  The records and the matrix call
+    leave the range to the tiled path, which reports both kinds in the same words; the other
+    three refuse it in their checks, an empty block's included."""
+    import pair_call_cases as pcc
+    lib = ctx.lib
+    sm = cuking_amd.Submatrix(10)
+    empty = cuking_amd.Submatrix(5, 4, 3)
+    assert empty.NumRows() == 0 or empty.NumCols() == 0
+    bits = ctx.upload_bitset(np.zeros((10, 2), dtype=np.uint64)).data_ptr()
+    select(ctx, "tiled", 7)
+    assert ctx.num_tiles(sm) == 1
+    for name in pcc.CALLS:
+        for tiles in (None, (0, 1)):
+            assert pcc.refused(lib, name, ctx.handle, sm, bits, tiles, out=None) == \
+                pcc.NO_RESULT[name]
+        served_late = name in ("king", "kin_matrix")
+        assert pcc.refused(lib, name, ctx.handle, sm, bits, (2, 1)) == \
+            ("tile range [2, 1) outside [0, 1)" if served_late else "tile range [2, 1) is reversed")
+        assert pcc.refused(lib, name, ctx.handle, sm, bits, (0, 5)) == \
+            "tile range [0, 5) outside [0, 1)"
+        assert pcc.refused(lib, name, ctx.handle, empty, bits, (0, 1)) == \
+            ("empty block has no tiles" if served_late else "tile range [0, 1) outside [0, 0)")
+    try:
+        for kernel, variant in (("tiled", 2), ("tiled", 0), ("stream", 0)):
+            select(ctx, kernel, variant)
+            for name, (what, form) in pcc.MATRIX_CORE_ONLY.items():
+                for tiles in (None, (0, 1)):
+                    assert pcc.refused(lib, name, ctx.handle, sm, bits, tiles) == \
+                        f"{what}: served by contexts of the tiled kernel with variant 5, 6 or 7 " \
+                        "(the matrix-core kernels) only; the VALU variants and the stream " \
+                        f"kernel have no {form}"
+    finally:
+        select(ctx, "tiled", 7)

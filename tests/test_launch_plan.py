@@ -19,11 +19,11 @@ HEADER = CSRC / "king_launch_plan.h"
 GOLDEN = ROOT / "tests" / "golden" / "launch_plans.txt"
 
 
-def _plans(tmp_path):
+def _plans(tmp_path, *args):
     exe = tmp_path / "launch_plan_driver"
     subprocess.run(["g++", "-std=c++17", "-O2", "-Wall", "-Werror", "-pedantic", f"-I{CSRC}",
                     str(ROOT / "tests" / "launch_plan_driver.cc"), "-o", str(exe)], check=True)
-    return subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout
+    return subprocess.run([str(exe), *args], check=True, capture_output=True, text=True).stdout
 
 
 def test_header_needs_no_hip():
@@ -57,3 +57,48 @@ def test_hand_derived_rows():
     # four-product kernel, configs[1] (3,160 tiles of 128 samples): one split launch of
     # 3,072 whole tiles in patches and 88 tiles in 256 pieces taken by 384 workgroups
     assert rows["m 3160 256 0 391 2 16384"] == "s 0 3072 88 3072 1 256 384 3456"
+
+
+def test_call_form_table(tmp_path):
+    """The rules of the six call forms (kCallForms), row by row and column by column, as the
+    host path had them when every layer still worked them out from the output pointers
+    (king_abi.hip run_tiled and check_reducing_args, king_mfma.hip launch_form):
+    k loop | layout unsorted | filter's bound may apply | VALU variants and stream kernel serve
+    it | the matrix-core kernel's <KIN, FULL> and its slot for the lean and the full k loop."""
+    got = _plans(tmp_path, "--forms").splitlines()
+    assert got == [
+        # records: lean or full by the threshold; KIN kRecords (0) has both k loops
+        "0 records | either 0 1 1 | lean 0 0 0 full 0 1 1",
+        # counts: the records kind's full k loop, with a counts pointer
+        "1 counts | full 0 0 1 | lean refused full 0 1 1",
+        # matrix (KIN 1) and summary (KIN 2): lean, on a layout that is never sorted
+        "2 kinship matrix | lean 1 0 1 | lean 1 0 2 full refused",
+        "3 kinship summary | lean 1 0 0 | lean 2 0 3 full refused",
+        # relative counts (KIN 3): the thresholded call's lean form, sorted, filter and all
+        "4 relative counts | lean 0 1 0 | lean 3 0 4 full refused",
+        # PI_HAT (KIN 4): full only, no filter (its bound is one on KING kinship)
+        "5 pi_hat | full 0 0 0 | lean refused full 4 1 5",
+        "outside -1 -1",
+    ]
+    # every allowed (form, k loop) has a <KIN, FULL> of its own -- except counts, which IS the
+    # records kind's full form (the kernel tells them apart by TiledArgs::dense_counts) -- and
+    # the slots are 0 .. 5 without a gap: a table of 6 x nibble x split has no empty entry
+    kernels, slots = {}, set()
+    for line in got[:6]:
+        form = int(line.split()[0])
+        words = line.split(" | ")[2].split()
+        i = 0
+        while i < len(words):
+            if words[i + 1] == "refused":
+                i += 2
+                continue
+            kin, full, slot = (int(w) for w in words[i + 1:i + 4])
+            assert full == (words[i] == "full")
+            kernels.setdefault((kin, full), []).append(form)
+            slots.add(slot)
+            assert slot == (full if kin == 0 else kin + 1)
+            i += 4
+    assert slots == set(range(6))
+    shared = {k: f for k, f in kernels.items() if len(f) > 1}
+    assert shared == {(0, 1): [0, 1]}
+    assert len(kernels) == 6
