@@ -10,7 +10,9 @@ SEED CASES FIRST_CASE [SIZE_CLASS]`, the size class being the tag's `sweep`; run
 `python tools/fuzz_pipeline.py SEED CASES --first-case K --size-class CLASS`; run_site_order:
 `python tools/fuzz_site_order.py SEED CASES FIRST_CASE`; run_pcrelate, whose checkers are the
 float64 references of tests/pcrelate_cases.py and tests/pcrelate_pairs_cases.py and the host
-twins: `python tools/fuzz_pcrelate.py SEED CASES FIRST_CASE SIZE_CLASS`).
+twins: `python tools/fuzz_pcrelate.py SEED CASES FIRST_CASE SIZE_CLASS`; run_pihat, whose checker
+besides the oracle is the numpy restatement of tests/pihat_cases.py: `python tools/fuzz_pihat.py
+SEED CASES FIRST_CASE SIZE_CLASS`).
 The checker is the CPU oracle (oracle/pyoracle.py); everything checked goes
 through the C ABI."""
 from __future__ import annotations
@@ -344,6 +346,154 @@ def reducing_compared_share(seed: int, cases: int, size_class=None):
     return pairs, compared
 
 
+def reducing_calls(ctx, tag, geno, sm, wps, d_bits, stream, exp, records, stats, fail) -> dict:
+    """The record call and the three reducing calls of one case, each as a closure that issues
+    the call on `stream` and checks what it gives against `exp` (reducing_cases.expect_all of
+    tag["bins"] and tag["thresholds"]) and `records` (the oracle's at tag["thresholds"][0]):
+    {"run", "kin_matrix", "kin_summary", "relative_counts"}.  `fail(what, detail)` raises the
+    runner's FuzzMismatch.  Shared by run_reducing and run_pihat."""
+    import torch
+    import reducing_cases as rc
+    from cuking_amd.dist import tile_partition
+    from test_gpu_kin_matrix import symmetric_expectation
+
+    dev = f"cuda:{ctx.device}"
+    sentinel = float(rc.SENTINEL)
+    thresholds, bins, w = tag["thresholds"], tag["bins"], tag["tile_ranges"]
+    block = sm.as_tuple()
+    kin = exp.pairs[2]
+    above = int((kin > np.float32(thresholds[0])).sum())
+    suffix = exp.bands[:, ::-1].astype(np.uint64).cumsum(axis=1)[:, ::-1]
+    rows, cols, stored = sm.NumRows(), sm.NumCols(), sm.NumSamples()
+    symmetric = tag["symmetric"] and block[0] == block[2]
+
+    def host(t):
+        """After ONE wait for the case's stream, nothing else."""
+        stream.synchronize()
+        return t.cpu().numpy()
+
+    def select(variant):
+        if variant == "stream":
+            ctx.set_kernel("stream")
+        else:
+            ctx.set_kernel("tiled")
+            ctx.set_option("variant", variant)
+
+    def ranges():
+        tiles = ctx.num_tiles(sm) if rows and cols else 0
+        return tile_partition(tiles, w) if tiles >= 2 else []
+
+    def matrix_into():
+        """(the prefilled buffer, its [rows, cols] view with a row pitch of its own)"""
+        buf = torch.full((rows, cols + tag["out_pad"]), sentinel, dtype=torch.float32,
+                         device=dev)
+        return buf, buf[:, :cols]
+
+    def check_matrix(buf, want, what):
+        got = host(buf)
+        try:
+            rc.assert_same(np.ascontiguousarray(got[:, :cols]), want, what)
+        except AssertionError as e:
+            fail(what, str(e))
+        if not (got[:, cols:] == rc.SENTINEL).all():
+            fail(what, "the padding columns of the strided output were written")
+
+    def call_run():
+        select(tag["variant"])
+        for rep in range(2 if tag["reuse_prepared"] else 1):   # the second call reuses the layout
+            got = ctx.run(sm, wps, d_bits, thresholds[0])
+            if got.tobytes() != records.tobytes():
+                fail(f"run (rep {rep})", _diff(got, records))
+
+    def call_kin_matrix():
+        select(tag["matrix_variant"])
+        buf, out = matrix_into()
+        ctx.kin_matrix(sm, wps, d_bits, out=out, symmetric=symmetric, stream=stream)
+        want = exp.matrix
+        if symmetric:
+            want = symmetric_expectation(exp.matrix, geno[block[0]:block[1]])
+        check_matrix(buf, want, f"kin_matrix (symmetric {symmetric})")
+        if tag["matrix_variant"] != "stream" and ranges():
+            buf, out = matrix_into()
+            for r in ranges():
+                ctx.kin_matrix(sm, wps, d_bits, out=out, tile_range=r, stream=stream)
+            check_matrix(buf, exp.matrix, f"kin_matrix, {w} tile ranges")
+
+    def check_summary(summary, pattern, times, what):
+        hist = host(summary.hist).view(np.uint64)
+        keys = host(summary.best).view(np.uint64)
+        added = hist - pattern
+        if not np.array_equal(added, times * exp.hist):
+            fail(what, f"histogram differs at slots "
+                       f"{np.flatnonzero(added != times * exp.hist)[:8]}")
+        if int(added.sum()) != times * kin.size:
+            fail(what, f"{int(added.sum())} pairs counted, the block has {kin.size}")
+        if not np.array_equal(keys, exp.keys):
+            fail(what, f"keys differ at samples {np.flatnonzero(keys != exp.keys)[:8]}")
+        best_kin, partner = rc.decode_keys(keys)
+        nan = np.isnan(exp.best_kin)
+        if not (np.array_equal(partner, exp.best_partner) and np.isnan(best_kin[nan]).all()
+                and np.array_equal(best_kin.view(np.uint32)[~nan],
+                                   exp.best_kin.view(np.uint32)[~nan])):
+            fail(what, "nearest relatives differ")
+        api_kin, api_partner = summary.nearest()
+        if not (np.array_equal(api_partner, partner) and
+                np.array_equal(api_kin.view(np.uint32), best_kin.view(np.uint32))):
+            fail(what, "KinSummary.nearest() decodes the keys differently")
+
+    def call_kin_summary():
+        select(tag["variant"])
+        pattern = (np.arange(bins[2] + 3, dtype=np.uint64) * np.uint64(7) + np.uint64(3))
+        kw = dict(lo=bins[0], hi=bins[1], bins=bins[2], stream=stream)
+
+        def outputs():
+            return (torch.from_numpy(pattern.view(np.int64).copy()).to(dev),
+                    torch.zeros(stored, dtype=torch.int64, device=dev))
+        hist, best = outputs()
+        summary = ctx.kin_summary(sm, wps, d_bits, hist=hist, best=best, **kw)
+        check_summary(summary, pattern, 1, "kin_summary")
+        if ranges():
+            hist, best = outputs()
+            for r in ranges():
+                summary = ctx.kin_summary(sm, wps, d_bits, hist=hist, best=best,
+                                          tile_range=r, **kw)
+            check_summary(summary, pattern, 1, f"kin_summary, {w} tile ranges")
+
+    def check_counts(counts, times, what):
+        got = host(counts.counts).view(np.uint32).reshape(stored, len(thresholds))
+        if not np.array_equal(got, np.uint32(times) * exp.bands):
+            fail(what, f"counts differ at (sample, band) "
+                       f"{np.argwhere(got != np.uint32(times) * exp.bands)[:8].tolist()}")
+        if not np.array_equal(counts.at_least(), np.uint64(times) * suffix):
+            fail(what, "suffix sums differ")
+        if counts.num_records(0) != times * above:
+            fail(what, f"num_records(0) {counts.num_records(0)}, the oracle has "
+                       f"{above} pairs above {thresholds[0]}")
+
+    def call_relative_counts():
+        select(tag["variant"])
+        giveup = tag["size_class"] == "giveup"
+        before = ctx.get_option("filter_dense_quadrants") if giveup else 0
+        out = torch.zeros((stored, len(thresholds)), dtype=torch.int32, device=dev)
+        counts = ctx.relative_counts(sm, wps, d_bits, thresholds=thresholds, out=out,
+                                     stream=stream)
+        check_counts(counts, 1, "relative_counts")
+        if giveup:
+            stats["giveup_dense_quadrants"] += \
+                ctx.get_option("filter_dense_quadrants") - before
+        ctx.relative_counts(sm, wps, d_bits, thresholds=thresholds, out=out, stream=stream)
+        check_counts(counts, 2, "relative_counts, a second call into the same tensor")
+        if ranges():
+            out = torch.zeros((stored, len(thresholds)), dtype=torch.int32, device=dev)
+            for r in ranges():
+                counts = ctx.relative_counts(sm, wps, d_bits, thresholds=thresholds,
+                                             out=out, tile_range=r, stream=stream)
+            check_counts(counts, 1, f"relative_counts, {w} tile ranges")
+
+    return dict(run=call_run, kin_matrix=call_kin_matrix, kin_summary=call_kin_summary,
+                relative_counts=call_relative_counts)
+
+
 def run_reducing(ctx, seed: int, cases: int, first_case: int = 0, log=None, size_class=None,
                  stats=None) -> int:
     """The three reducing calls and the record call, interleaved in a random order over one
@@ -358,24 +508,21 @@ def run_reducing(ctx, seed: int, cases: int, first_case: int = 0, log=None, size
     import torch
     import cuking_amd
     import reducing_cases as rc
-    from cuking_amd.dist import tile_partition
     from oracle import pyoracle
-    from test_gpu_kin_matrix import symmetric_expectation
 
     stats = stats if stats is not None else {}
     for key in ("pairs", "compared", "giveup_dense_quadrants"):
         stats.setdefault(key, 0)
     dev = f"cuda:{ctx.device}"
-    sentinel = float(rc.SENTINEL)
     t0, ran = time.time(), 0
     try:
         for tag, geno in reducing_cases(seed, cases, first_case, size_class):
             n, m, k, shard = tag["n"], tag["m"], tag["split_factor"], tag["shard"]
-            thresholds, bins, w = tag["thresholds"], tag["bins"], tag["tile_ranges"]
+            thresholds, bins = tag["thresholds"], tag["bins"]
             osm, bits, all_pairs = reducing_oracle(tag, geno)
             block = osm.as_tuple()
             exp = rc.expect_all(block, all_pairs, bins, thresholds)
-            oi, oj, kin = exp.pairs
+            kin = exp.pairs[2]
             stats["pairs"] += kin.size
             stats["compared"] += int((~np.isnan(kin)).sum())
             records, _, _ = pyoracle.compute(osm, bits, thresholds[0], threads=8)
@@ -383,12 +530,8 @@ def run_reducing(ctx, seed: int, cases: int, first_case: int = 0, log=None, size
             if above != len(records):
                 raise FuzzMismatch(f"the oracle disagrees with itself: {above} pairs above "
                                    f"{thresholds[0]}, {len(records)} records; {tag}")
-            suffix = exp.bands[:, ::-1].astype(np.uint64).cumsum(axis=1)[:, ::-1]
             sm = cuking_amd.Submatrix(n, k, shard)
             assert sm.as_tuple() == block
-            rows, cols, stored = sm.NumRows(), sm.NumCols(), sm.NumSamples()
-            diag = block[0] == block[2]
-            symmetric = tag["symmetric"] and diag
 
             for key in SHIPPED:
                 if key != "variant":
@@ -405,131 +548,8 @@ def run_reducing(ctx, seed: int, cases: int, first_case: int = 0, log=None, size
                 raise FuzzMismatch(f"{what}: {detail}; reproduce with {tag} (tools/fuzz_reducing.py "
                                    f"{seed} {tag['case'] + 1} {tag['case']} {tag['sweep']})")
 
-            def host(t):
-                """After ONE wait for the case's stream, nothing else."""
-                stream.synchronize()
-                return t.cpu().numpy()
-
-            def select(variant):
-                if variant == "stream":
-                    ctx.set_kernel("stream")
-                else:
-                    ctx.set_kernel("tiled")
-                    ctx.set_option("variant", variant)
-
-            def ranges():
-                tiles = ctx.num_tiles(sm) if rows and cols else 0
-                return tile_partition(tiles, w) if tiles >= 2 else []
-
-            def matrix_into():
-                """(the prefilled buffer, its [rows, cols] view with a row pitch of its own)"""
-                buf = torch.full((rows, cols + tag["out_pad"]), sentinel, dtype=torch.float32,
-                                 device=dev)
-                return buf, buf[:, :cols]
-
-            def check_matrix(buf, want, what):
-                got = host(buf)
-                try:
-                    rc.assert_same(np.ascontiguousarray(got[:, :cols]), want, what)
-                except AssertionError as e:
-                    fail(what, str(e))
-                if not (got[:, cols:] == rc.SENTINEL).all():
-                    fail(what, "the padding columns of the strided output were written")
-
-            def call_run():
-                select(tag["variant"])
-                for rep in range(2 if tag["reuse_prepared"] else 1):   # the second call reuses the layout
-                    got = ctx.run(sm, wps, d_bits, thresholds[0])
-                    if got.tobytes() != records.tobytes():
-                        fail(f"run (rep {rep})", _diff(got, records))
-
-            def call_kin_matrix():
-                select(tag["matrix_variant"])
-                buf, out = matrix_into()
-                ctx.kin_matrix(sm, wps, d_bits, out=out, symmetric=symmetric, stream=stream)
-                want = exp.matrix
-                if symmetric:
-                    want = symmetric_expectation(exp.matrix, geno[block[0]:block[1]])
-                check_matrix(buf, want, f"kin_matrix (symmetric {symmetric})")
-                if tag["matrix_variant"] != "stream" and ranges():
-                    buf, out = matrix_into()
-                    for r in ranges():
-                        ctx.kin_matrix(sm, wps, d_bits, out=out, tile_range=r, stream=stream)
-                    check_matrix(buf, exp.matrix, f"kin_matrix, {w} tile ranges")
-
-            def check_summary(summary, pattern, times, what):
-                hist = host(summary.hist).view(np.uint64)
-                keys = host(summary.best).view(np.uint64)
-                added = hist - pattern
-                if not np.array_equal(added, times * exp.hist):
-                    fail(what, f"histogram differs at slots "
-                               f"{np.flatnonzero(added != times * exp.hist)[:8]}")
-                if int(added.sum()) != times * kin.size:
-                    fail(what, f"{int(added.sum())} pairs counted, the block has {kin.size}")
-                if not np.array_equal(keys, exp.keys):
-                    fail(what, f"keys differ at samples {np.flatnonzero(keys != exp.keys)[:8]}")
-                best_kin, partner = rc.decode_keys(keys)
-                nan = np.isnan(exp.best_kin)
-                if not (np.array_equal(partner, exp.best_partner) and np.isnan(best_kin[nan]).all()
-                        and np.array_equal(best_kin.view(np.uint32)[~nan],
-                                           exp.best_kin.view(np.uint32)[~nan])):
-                    fail(what, "nearest relatives differ")
-                api_kin, api_partner = summary.nearest()
-                if not (np.array_equal(api_partner, partner) and
-                        np.array_equal(api_kin.view(np.uint32), best_kin.view(np.uint32))):
-                    fail(what, "KinSummary.nearest() decodes the keys differently")
-
-            def call_kin_summary():
-                select(tag["variant"])
-                pattern = (np.arange(bins[2] + 3, dtype=np.uint64) * np.uint64(7) + np.uint64(3))
-                kw = dict(lo=bins[0], hi=bins[1], bins=bins[2], stream=stream)
-
-                def outputs():
-                    return (torch.from_numpy(pattern.view(np.int64).copy()).to(dev),
-                            torch.zeros(stored, dtype=torch.int64, device=dev))
-                hist, best = outputs()
-                summary = ctx.kin_summary(sm, wps, d_bits, hist=hist, best=best, **kw)
-                check_summary(summary, pattern, 1, "kin_summary")
-                if ranges():
-                    hist, best = outputs()
-                    for r in ranges():
-                        summary = ctx.kin_summary(sm, wps, d_bits, hist=hist, best=best,
-                                                  tile_range=r, **kw)
-                    check_summary(summary, pattern, 1, f"kin_summary, {w} tile ranges")
-
-            def check_counts(counts, times, what):
-                got = host(counts.counts).view(np.uint32).reshape(stored, len(thresholds))
-                if not np.array_equal(got, np.uint32(times) * exp.bands):
-                    fail(what, f"counts differ at (sample, band) "
-                               f"{np.argwhere(got != np.uint32(times) * exp.bands)[:8].tolist()}")
-                if not np.array_equal(counts.at_least(), np.uint64(times) * suffix):
-                    fail(what, "suffix sums differ")
-                if counts.num_records(0) != times * above:
-                    fail(what, f"num_records(0) {counts.num_records(0)}, the oracle has "
-                               f"{above} pairs above {thresholds[0]}")
-
-            def call_relative_counts():
-                select(tag["variant"])
-                giveup = tag["size_class"] == "giveup"
-                before = ctx.get_option("filter_dense_quadrants") if giveup else 0
-                out = torch.zeros((stored, len(thresholds)), dtype=torch.int32, device=dev)
-                counts = ctx.relative_counts(sm, wps, d_bits, thresholds=thresholds, out=out,
-                                             stream=stream)
-                check_counts(counts, 1, "relative_counts")
-                if giveup:
-                    stats["giveup_dense_quadrants"] += \
-                        ctx.get_option("filter_dense_quadrants") - before
-                ctx.relative_counts(sm, wps, d_bits, thresholds=thresholds, out=out, stream=stream)
-                check_counts(counts, 2, "relative_counts, a second call into the same tensor")
-                if ranges():
-                    out = torch.zeros((stored, len(thresholds)), dtype=torch.int32, device=dev)
-                    for r in ranges():
-                        counts = ctx.relative_counts(sm, wps, d_bits, thresholds=thresholds,
-                                                     out=out, tile_range=r, stream=stream)
-                    check_counts(counts, 1, f"relative_counts, {w} tile ranges")
-
-            calls = dict(run=call_run, kin_matrix=call_kin_matrix, kin_summary=call_kin_summary,
-                         relative_counts=call_relative_counts)
+            calls = reducing_calls(ctx, tag, geno, sm, wps, d_bits, stream, exp, records, stats,
+                                   fail)
             with torch.cuda.stream(stream):
                 for name in tag["order"]:
                     calls[name]()
@@ -928,6 +948,209 @@ def run_pcrelate(ctx, seed: int, cases: int, first_case: int = 0, log=None, size
                 log(f"run_pcrelate seed {seed} case {tag['case']} ok ({time.time() - t0:.0f}s)")
     finally:
         ctx.set_option("max_launch_blocks", 0)
+        ctx.invalidate()
+    return ran
+
+
+# ---- PI_HAT among the pair calls ----------------------------------------------------------------
+def run_pihat(ctx, seed: int, cases: int, first_case: int = 0, log=None, size_class=None,
+              stats=None, twin_every: int = 1) -> int:
+    """The PI_HAT scan among the other pair calls (tests/pihat_fuzz_cases.py has the cases and
+    the size classes "small", "edges" and "tiles"): per case one bitset, uploaded once, and on the
+    case's stream, in the drawn order -- pi_hat_records at the case's threshold, model and
+    `bounded`; the other setting of `bounded` at -1.0 (every pair that is not NaN is a record);
+    the raw tile-range entry point over tile_partition, each range into a buffer of its own; the
+    count alone (capacity 0); a buffer one record short; compute_counts; the KING records; and
+    kin_matrix or relative_counts (reducing_calls), which leave another layout and other codes in
+    the workspace between the PI_HAT calls.  Everything is compared on bytes with what ONE
+    pyoracle.all_pairs call gives: the oracle's sums, and the numpy restatement of the pair math
+    over their IBS counts (pihat_cases.records_np); every `twin_every`-th case the host twin is
+    held to the same bytes (tools/fuzz_pihat.py).  Returns the number of cases run; `stats`, a
+    dict, gains `pairs`, `records` (of the thresholded call), `twins`, `branches` (the bounding
+    steps of pihat_cases.BRANCHES that pairs of the blocks took), `models`, `variants`,
+    `split_launches` (PI_HAT launches whose plan by king_launch_plan.h has remainder pieces) and
+    `ties` (per threshold value, the pairs whose float32 PI_HAT equals it: the strict > decides)."""
+    import torch
+    import cuking_amd
+    import pihat_cases as pc
+    import pihat_fuzz_cases as pf
+    import reducing_cases as rc
+    from cuking_amd import _lib
+    from cuking_amd.dist import tile_partition
+    from oracle import pyoracle
+
+    stats = stats if stats is not None else {}
+    for key in ("pairs", "records", "twins", "split_launches"):
+        stats.setdefault(key, 0)
+    for key in ("branches", "models", "variants"):
+        stats.setdefault(key, [])
+    stats.setdefault("ties", {})
+    dev = f"cuda:{ctx.device}"
+    t0, ran = time.time(), 0
+
+    def seen(key, value):
+        if value not in stats[key]:
+            stats[key] = sorted(stats[key] + [value], key=str)
+
+    try:
+        for tag, geno, spec in pf.cases(seed, cases, first_case, size_class):
+            n, m, k, shard = tag["n"], tag["m"], tag["split_factor"], tag["shard"]
+            thr, bounded, w = tag["thr"], tag["bounded"], tag["tile_ranges"]
+            model = pf.model_of(tag, geno)
+            ref = pf.reference(tag, geno, model)
+            osm, bits = ref.osm, ref.bits
+            block = osm.as_tuple()
+            oi, oj, oc, _ = ref.all_pairs
+            want, other = ref.records[(thr, bounded)], ref.records[(-1.0, not bounded)]
+            listed = {r.tobytes() for r in want}
+            exp = rc.expect_all(block, ref.all_pairs, tag["bins"], tag["thresholds"])
+            records, _, _ = pyoracle.compute(osm, bits, tag["thresholds"][0], threads=8)
+            sm = cuking_amd.Submatrix(n, k, shard)
+            assert sm.as_tuple() == block and bits.shape[0] == sm.NumSamples() >= 2
+            if pf.planted_pairs(tag)["all_missing"] and not len(other) < sm.NumPairs():
+                raise FuzzMismatch(f"the reference lists a pair of the all-missing sample; {tag}")
+
+            ctx.set_kernel("tiled")
+            for key in SHIPPED:
+                if key in tag:
+                    ctx.set_option(key, tag[key])
+            # (a new bitset may land on a recycled pointer: tell the library)
+            ctx.invalidate()
+            d_bits = ctx.upload_bitset(bits)
+            d_founders = ctx.upload_bitset(pf.host_bits(pf.model_rows(tag, geno))) \
+                if spec == "founders" else None
+            wps = cuking_amd.words_per_sample(m)
+            stream = torch.cuda.Stream(dev) if tag["side_stream"] else torch.cuda.current_stream()
+            stream.wait_stream(torch.cuda.current_stream())
+
+            def fail(what, detail=""):
+                raise FuzzMismatch(f"{what}: {detail}; reproduce with {tag} (tools/fuzz_pihat.py "
+                                   f"{seed} {tag['case'] + 1} {tag['case']} {tag['size_class']})")
+
+            def use():
+                """The case's variant (the lean call may have left another kernel selected)."""
+                ctx.set_kernel("tiled")
+                ctx.set_option("variant", tag["variant"])
+
+            def model_args():
+                if spec == "block":
+                    return {}
+                if spec == "founders":
+                    return dict(counts=ctx.site_counts(d_founders, wps, stream=stream))
+                return dict(model=model)
+
+            def scan(min_pi_hat, bound, expect, what):
+                use()
+                got = ctx.pi_hat_records(sm, wps, d_bits, m, min_pi_hat, bounded=bound,
+                                         stream=stream, **model_args())
+                rows = got.sorted()
+                if got.num_records != len(expect) or rows.tobytes() != expect.tobytes():
+                    fail(what, _diff(rows, expect))
+                if spec in ("block", "founders") and not (
+                        got.model.sites_used == model.sites_used and np.array_equal(
+                            pc.bits(got.model.as_tuple()[:5]), pc.bits(model.as_tuple()[:5]))):
+                    fail(what, f"model {got.model}, pi_hat_model_host of the same rows {model}")
+
+            def raw(capacity, tile_range=None):
+                use()
+                return pc.raw_call(ctx, sm, wps, d_bits, model, capacity, tile_range,
+                                   stream=stream, min_pi_hat=float(np.float32(thr)),
+                                   flags=0 if bounded else _lib.PIHAT_UNBOUNDED)
+
+            def untouched(behind, what):
+                if not (behind == 0x55555555).all():
+                    fail(what, "the rows behind the buffer were written")
+
+            def call_tiles():
+                use()
+                tiles = ctx.num_tiles(sm)
+                if tiles != pf.num_tiles(tag):
+                    fail("pi_hat tiles", f"{tiles} tiles, pihat_fuzz_cases.num_tiles says "
+                                         f"{pf.num_tiles(tag)}")
+                parts = [raw(max(len(want), 1), r) for r in tile_partition(tiles, w)]
+                if sum(count for _, count, _, _ in parts) != len(want):
+                    fail(f"pi_hat, {w} tile ranges", f"the counts "
+                         f"{[count for _, count, _, _ in parts]} do not add up to {len(want)}")
+                if any(overflow for _, _, overflow, _ in parts):
+                    fail(f"pi_hat, {w} tile ranges", "an overflow flag is set")
+                for _, _, _, behind in parts:
+                    untouched(behind, f"pi_hat, {w} tile ranges")
+                merged = cuking_amd.sort_results(np.ascontiguousarray(
+                    np.concatenate([rows for rows, _, _, _ in parts])))
+                if merged.tobytes() != want.tobytes():
+                    fail(f"pi_hat, {w} tile ranges", _diff(merged, want))
+
+            def call_count():
+                rows, count, overflow, behind = raw(0)
+                if (len(rows), count, overflow) != (0, len(want), int(len(want) > 0)):
+                    fail("pi_hat count", f"capacity 0 gives count {count}, flag {overflow}; the "
+                                         f"reference has {len(want)} records")
+                untouched(behind, "pi_hat count")
+
+            def call_one_short():
+                total = len(want)
+                if total == 0:
+                    return
+                rows, count, overflow, behind = raw(total - 1)
+                if (count, overflow) != (total, 1):
+                    fail("pi_hat one short", f"count {count}, flag {overflow}; the reference has "
+                                             f"{total} records")
+                untouched(behind, "pi_hat one short")
+                stored = [r.tobytes() for r in rows]
+                if len(stored) != total - 1 or len(set(stored)) != len(stored) or \
+                        not all(r in listed for r in stored):
+                    fail("pi_hat one short", "a stored row is not one of the reference's, or is "
+                                             "stored twice")
+
+            def call_counts():
+                use()
+                got = ctx.compute_counts(sm, wps, d_bits, stream=stream)
+                sel = got[oi - sm.i_begin, oj - sm.j_begin]
+                for field in oc.dtype.names:
+                    if not np.array_equal(sel[field], oc[field]):
+                        at = np.flatnonzero(sel[field] != oc[field])[:5]
+                        fail("counts", f"{field} differs at pairs "
+                                       f"{[(int(oi[a]), int(oj[a])) for a in at]}")
+
+            shared = reducing_calls(ctx, tag, geno, sm, wps, d_bits, stream, exp, records, stats,
+                                    fail)
+            calls = {"pi_hat": lambda: scan(thr, bounded, want, "pi_hat"),
+                     "pi_hat unbounded or bounded":
+                         lambda: scan(-1.0, not bounded, other,
+                                      f"pi_hat at -1.0, bounded {not bounded}"),
+                     "pi_hat tiles": call_tiles, "pi_hat count": call_count,
+                     "pi_hat one short": call_one_short, "counts": call_counts,
+                     "run": shared["run"], "lean": shared[tag["lean"]]}
+            with torch.cuda.stream(stream):
+                for name in tag["order"]:
+                    calls[name]()
+            stream.synchronize()
+
+            if tag["case"] % twin_every == 0:
+                stats["twins"] += 1
+                for t, b in ((thr, bounded), (-1.0, not bounded)):
+                    twin = cuking_amd.pi_hat_records_host(sm, wps, bits, m, t, model=model,
+                                                          bounded=b).records
+                    if twin.tobytes() != ref.records[(t, b)].tobytes():
+                        fail(f"the host twin at {t}, bounded {b}",
+                             _diff(twin, ref.records[(t, b)]))
+            stats["pairs"] += len(oi)
+            stats["records"] += len(want)
+            stats["split_launches"] += pf.split_launches([tag])[0]
+            seen("models", spec)
+            seen("variants", tag["variant"])
+            for step in pc.BRANCHES:
+                if ref.taken.get(step):
+                    seen("branches", step)
+            if ref.ties:
+                stats["ties"][thr] = stats["ties"].get(thr, 0) + ref.ties
+            ran += 1
+            if log and tag["case"] % 10 == 0:
+                log(f"run_pihat seed {seed} case {tag['case']} ok ({time.time() - t0:.0f}s)")
+    finally:
+        ctx.set_kernel("tiled")
+        for key, value in SHIPPED.items():
+            ctx.set_option(key, value)
         ctx.invalidate()
     return ran
 

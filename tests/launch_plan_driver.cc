@@ -8,11 +8,14 @@
 //       s <begin> <split_whole> <split_tiles> <shape> whole tiles + remainder pieces
 //   f <tiles> <wgs> <cap> <steps> <switch set> | launch chunks of the filter kernel:
 //       c <n> <check0> <check1> <rotate> <rest> <parts> <shape> <fsplit_tile0> <fsplit_first> <grid>
+//   "--mfma <tiles> <wgs> <cap> <steps> ..." prints mfma_plan alone for the inputs given
+//   (tests/pihat_fuzz_cases.py asks which calls of a sweep launch remainder pieces).
 //   <shape> = <launch_tiles> <xcd_chunk> <dyn_tiles> <dyn_wgs> <grid>; launch_tiles prints as
 //   "-" where no kernel reads it (plain order, no dynamic tail).
 #include <stdarg.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include <string.h>
 
 #include <string>
@@ -157,8 +160,23 @@ static int print_forms() {
   return 0;
 }
 
+// "--mfma <tiles> <wgs> <cap> <steps> ...": mfma_plan for each group of four numbers (cap 0 =
+// the hardware limit only), one line per group: <first> <split_whole> <split_tiles>
+static int print_mfma(int count, char **words) {
+  if (count % 4 != 0) return 2;
+  for (int k = 0; k < count; k += 4) {
+    const uint64_t tiles = strtoull(words[k], nullptr, 10), cap = strtoull(words[k + 2], nullptr, 10);
+    const uint32_t wgs = (uint32_t)strtoul(words[k + 1], nullptr, 10);
+    const uint32_t steps = (uint32_t)strtoul(words[k + 3], nullptr, 10);
+    const MfmaPlan p = mfma_plan(tiles, wgs, steps, cap != 0 ? cap : kHwBlocks);
+    printf("%llu %u %u\n", (unsigned long long)p.first, p.split_whole, p.split_tiles);
+  }
+  return 0;
+}
+
 int main(int argc, char **argv) {
   if (argc > 1 && strcmp(argv[1], "--forms") == 0) return print_forms();
+  if (argc > 1 && strcmp(argv[1], "--mfma") == 0) return print_mfma(argc - 2, argv + 2);
   const bool all = argc > 1 && strcmp(argv[1], "--all") == 0;
   // Readable part: every count at the defaults (256 CUs, no block limit, 100k sites), then a
   // few counts with one input changed at a time (a block limit: lines of at most 16 launches).

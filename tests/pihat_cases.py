@@ -2,7 +2,11 @@
 the definition once more in Python floats, in the order csrc/king_pihat.h writes it, so that the
 host twin, the kernel and this file must agree bit for bit; the same terms in exact rationals; a
 per-site numpy walk that derives IBS0/1/2 from the genotypes; seeded count rows and IBS triples;
-and the smoke() cohort with its planted pairs."""
+the smoke() cohort with its planted pairs; the pair math once more for arrays of counts
+(z_of_counts_np, records_np: what the sweep of tests/pihat_fuzz_cases.py is judged by), the IBS
+counts of the oracle's sums (ibs_of_counts), the models made by hand (MODELS) and the bare ABI
+call the GPU tests share (raw_call)."""
+import ctypes as C
 import random
 from fractions import Fraction
 from functools import lru_cache
@@ -98,6 +102,124 @@ def bits(a) -> np.ndarray:
     payload of an invalid operation's result to the implementation: x86 gives -NaN for 0 / 0)."""
     a = np.ascontiguousarray(a, dtype=np.float64)
     return np.where(np.isnan(a), np.float64("nan"), a).view(np.uint64)
+
+
+# ---- the restatement once more, vectorised (numpy float64: the same IEEE operations) -----------
+# The bounding steps in the order of csrc/king_pihat.h, and "nan": a pair whose PI_HAT is NaN.
+STEPS = ("z0 > 1", "z1 > 1", "z2 > 1", "z0 < 0", "z1 < 0", "z2 < 0")
+BRANCHES = STEPS + ("nan",)
+# Subtly wrong restatements (tests/test_pihat_fuzz_cases.py: the sweeps' inputs tell each from
+# the right one): what z_of_counts_np, records_np and ibs_of_counts do under `defect=`.
+DEFECTS = ("threshold >=", "no z2 < 0 step", "z1 > 1 step last", "ibs1 = shared - ibs2",
+           "no float32 rounding", "bounded ignored")
+
+
+def z_of_counts_np(model, ibs0, ibs1, ibs2, bounded: bool = True, taken=None, defect=None):
+    """z_of_counts for arrays of counts: (z0, z1, z2, pi_hat) as float64 arrays, the same
+    operations in the same order, the branches as np.where steps in the order of the header; x / 0
+    and 0 / 0 give what IEEE gives.  `taken`, a dict, gains per step of STEPS the number of pairs
+    that took it (a step runs on what the steps before it left) and under "nan" the pairs whose
+    pi_hat is NaN."""
+    e00, e01, e02, e11, e12 = (np.float64(e) for e in model[:5])
+    a0, a1, a2 = (np.asarray(a).astype(np.float64) for a in (ibs0, ibs1, ibs2))
+    if defect == "bounded ignored":
+        bounded = True
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore", under="ignore"):
+        s = (a0 + a1) + a2
+        z0 = a0 / (e00 * s)
+        z1 = (a1 - z0 * (e01 * s)) / (e11 * s)
+        z2 = ((a2 - z0 * (e02 * s)) - z1 * (e12 * s)) / s
+        z = [z0, z1, z2]
+
+        def note(name, c):
+            if taken is not None:
+                taken[name] = taken.get(name, 0) + int(np.count_nonzero(c))
+
+        def above_one(k):
+            c = z[k] > 1.0
+            note(STEPS[k], c)
+            for q in range(3):
+                z[q] = np.where(c, 1.0 if q == k else 0.0, z[q])
+
+        def below_zero(k):
+            c = z[k] < 0.0
+            note(STEPS[3 + k], c)
+            a, b = (q for q in range(3) if q != k)
+            t = z[a] + z[b]
+            z[k] = np.where(c, 0.0, z[k])
+            z[a], z[b] = np.where(c, z[a] / t, z[a]), np.where(c, z[b] / t, z[b])
+
+        if bounded:
+            above_one(0)
+            if defect != "z1 > 1 step last":
+                above_one(1)
+            above_one(2)
+            below_zero(0)
+            below_zero(1)
+            if defect != "no z2 < 0 step":
+                below_zero(2)
+            if defect == "z1 > 1 step last":
+                above_one(1)
+        pi_hat = z[1] / 2.0 + z[2]
+    if taken is not None:
+        taken["nan"] = taken.get("nan", 0) + int(np.isnan(pi_hat).sum())
+    return z[0], z[1], z[2], pi_hat
+
+
+def records_of_pi_hat(i, j, ibs0, ibs1, ibs2, pi_hat, min_pi_hat, defect=None) -> np.ndarray:
+    """The pairs with float32(pi_hat) > float32(min_pi_hat) as records in ascending (i, j)."""
+    thr = np.float32(min_pi_hat)
+    with np.errstate(invalid="ignore", over="ignore", under="ignore"):
+        kin = np.asarray(pi_hat, dtype=np.float64).astype(np.float32)
+        if defect == "threshold >=":
+            keep = kin >= thr
+        elif defect == "no float32 rounding":
+            keep = np.asarray(pi_hat, dtype=np.float64) > np.float64(thr)
+        else:
+            keep = kin > thr
+    i, j = np.asarray(i), np.asarray(j)
+    keep = np.flatnonzero(keep)
+    keep = keep[np.lexsort((j[keep], i[keep]))]
+    out = np.zeros(keep.size, dtype=KING_RESULT_DTYPE)
+    out["sample_i"], out["sample_j"], out["kin"] = i[keep], j[keep], kin[keep]
+    out["ibs0"], out["ibs1"], out["ibs2"] = (np.asarray(a)[keep] for a in (ibs0, ibs1, ibs2))
+    return out
+
+
+def records_np(sm, i, j, ibs0, ibs1, ibs2, model, min_pi_hat, bounded: bool = True,
+               defect=None) -> np.ndarray:
+    """What the scan returns for block `sm` (a cuking_amd.Submatrix) whose pairs (i, j) have
+    the counts ibs0/1/2: KING_RESULT_DTYPE rows in ascending (i, j), the pairs with
+    float32(pi_hat) > float32(min_pi_hat)."""
+    i, j = np.asarray(i), np.asarray(j)
+    assert ((i >= sm.i_begin) & (i < sm.i_end) & (j >= sm.j_begin) & (j < sm.j_end)).all()
+    pi_hat = z_of_counts_np(model, ibs0, ibs1, ibs2, bounded, defect=defect)[3]
+    return records_of_pi_hat(i, j, ibs0, ibs1, ibs2, pi_hat, min_pi_hat, defect)
+
+
+def ibs_of_counts(oc, defect=None):
+    """(ibs0, ibs1, ibs2) uint32 of the COUNTS_DTYPE rows of pyoracle.all_pairs, as the oracle's
+    own records have them (tests/test_pihat_fuzz_cases.py holds this to the ibs fields of
+    pyoracle.compute): opposite homozygotes; what is left; the same genotype."""
+    ibs0 = oc["opposing_hom"].astype(np.uint32)
+    ibs2 = (oc["concordant_hom"] + oc["both_het"]).astype(np.uint32)
+    if defect == "ibs1 = shared - ibs2":
+        return ibs0, (oc["shared"] - ibs2).astype(np.uint32), ibs2
+    return ibs0, (oc["shared"] - ibs0 - ibs2).astype(np.uint32), ibs2
+
+
+# ---- models ------------------------------------------------------------------------------------
+MODELS = {
+    "seeded rows": lambda: model_of_rows(seeded_count_rows()),
+    "333 x 5000": lambda: model_of_rows([(150, 140, 40), (300, 30, 1), (100, 160, 70)] * 50),
+    "zero e00": lambda: model_of_rows([(40, 0, 0), (0, 0, 7)]),
+    "zero e00 and e11": lambda: (0.0, 0.0, 1.0, 0.0, 1.0, 3),
+    "tiny e00": lambda: (1e-300, 0.4, 0.6, 0.36, 0.64, 9),
+    "NaN": lambda: model_of_rows([]),
+    # (no count row gives a negative expectation: z0 = ibs0 / (e00 S) >= 0 under every model of
+    #  counts, so the z0 < 0 step can only be driven by a model made by hand)
+    "negative e00": lambda: (-0.1, 0.4, 0.5, 0.4, 0.6, 3),
+}
 
 
 # ---- exact rationals ---------------------------------------------------------------------------
@@ -253,3 +375,33 @@ def smoke_cohort():
     host = np.ascontiguousarray(host).view(np.uint64).reshape(n, wps)
     host.setflags(write=False)
     return cohort, host, wps
+
+
+# ---- the bare ABI call on the device -----------------------------------------------------------
+def raw_call(ctx, sm, wps, d_bits, model, capacity, tile_range=None, stream=None,
+             min_pi_hat=0.05, sentinel_rows=4, flags=0):
+    """The bare ABI call into a buffer of `capacity` records followed by `sentinel_rows` rows
+    of 0x55 bytes: (records written as host rows, count, overflow flag, the rows behind)."""
+    import torch
+    import cuking_amd
+    from cuking_amd import _lib
+    dev = f"cuda:{ctx.device}"
+    buf = torch.full((capacity + sentinel_rows, 6), 0x55555555, dtype=torch.int32, device=dev)
+    words = torch.zeros(2, dtype=torch.int32, device=dev)
+    head = (ctx.handle, C.byref(sm.c), wps, d_bits.data_ptr())
+    tail = (C.byref(model.c), min_pi_hat, flags, capacity, buf.data_ptr() if capacity else None,
+            words[0:1].data_ptr(), words[1:2].data_ptr(),
+            stream.cuda_stream if stream is not None else None)
+    if stream is not None:
+        stream.wait_stream(torch.cuda.current_stream())
+    if tile_range is None:
+        _lib.check(ctx.lib.cuking_compute_pihat(*head, *tail))
+    else:
+        _lib.check(ctx.lib.cuking_compute_pihat_tiles(*head, *tile_range, *tail))
+    if stream is not None:
+        stream.synchronize()
+    torch.cuda.synchronize(ctx.device)
+    count, overflow = (int(x) & 0xFFFFFFFF for x in words.tolist())
+    host = buf.cpu().numpy()
+    rows = np.ascontiguousarray(host[:min(count, capacity)]).view(cuking_amd.KING_RESULT_DTYPE)
+    return rows.reshape(-1), count, overflow, host[capacity:]

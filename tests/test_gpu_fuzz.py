@@ -56,6 +56,21 @@ PCRELATE_EXACT = [(621, 40)]
 PCRELATE_SWEEPS = [(s, c, "small") for s, c in PCRELATE] + \
     [(s, c, "tiles") for s, c in PCRELATE_TILES] + [(s, c, "exact") for s, c in PCRELATE_EXACT]
 PCRELATE_TWIN_EVERY = 1
+# run_pihat (the PI_HAT scan at two thresholds, over tile ranges, counting and into a short
+# buffer, compute_counts, the KING records and kin_matrix or relative_counts, interleaved over
+# one bitset), in one session on one MI355X box in which the three mixed run_reducing sweeps took
+# 19, 11 and 9 s and the one of launches of >= 64 tiles 11 s: the three sweeps of the class
+# "small" 5, 3 and 5 s, the one on the tile and step edges 2 s, the one of launches of >= 64
+# tiles 14 s (17.8 million pairs; the oracle's all_pairs and the numpy references are most of it.
+# Nine cases are the fewest that draw every model once; the host twin runs on every third of them
+# and on every case of the other classes, and is not what dominates: 14 s with it on every case too)
+PIHAT = [(701, 40), (702, 40), (704, 40)]
+PIHAT_EDGES = [(711, 30)]
+PIHAT_TILES = [(727, 9)]
+# (what tests/test_pihat_fuzz_cases.py holds to its conditions on the CPU)
+PIHAT_SWEEPS = [(s, c, "small") for s, c in PIHAT] + \
+    [(s, c, "edges") for s, c in PIHAT_EDGES] + [(s, c, "tiles") for s, c in PIHAT_TILES]
+PIHAT_TWIN_EVERY = {"small": 1, "edges": 1, "tiles": 3}
 SCALE =float(os.environ.get("CUKING_FUZZ_SCALE", "1"))
 
 
@@ -189,6 +204,44 @@ def test_random_pcrelate_calls_tile_and_step_edges(ctx, seed, cases):
 @pytest.mark.parametrize("seed,cases", PCRELATE_EXACT)
 def test_random_pcrelate_calls_exact_on_bytes(ctx, seed, cases):
     _pcrelate_sweep(ctx, seed, cases, "exact")
+
+
+def _pihat_sweep(ctx, seed, cases, size_class):
+    """One run_pihat sweep: every case drawn was run; on what ran, pairs took every bounding step
+    and the NaN exit, every model spec and every variant was drawn, and pairs sat exactly ON a
+    threshold of 0.0, of 0.5 and of 1.0."""
+    import pihat_cases
+    import pihat_fuzz_cases as pf
+    t0 = time.time()
+    cases, stats = max(1, int(cases * SCALE)), {}
+    ran = fuzz_cases.run_pihat(ctx, seed, cases, log=_log, size_class=size_class, stats=stats,
+                               twin_every=PIHAT_TWIN_EVERY[size_class])
+    print(f"run_pihat seed {seed} ({size_class}): {ran} cases OK in {time.time() - t0:.0f}s, "
+          f"{stats}")
+    assert ran == cases
+    assert set(stats["branches"]) == set(pihat_cases.BRANCHES), stats
+    assert set(stats["models"]) == set(pf.SPECS), stats
+    assert set(stats["variants"]) == set(pf.VARIANTS), stats
+    assert all(stats["ties"].get(t, 0) > 0 for t in pf.TIE_THRESHOLDS), stats
+    assert 0 < stats["records"] < stats["pairs"], stats
+    return stats
+
+
+@pytest.mark.parametrize("seed,cases", PIHAT)
+def test_random_pihat_among_the_pair_calls(ctx, seed, cases):
+    """... and PI_HAT launches had remainder pieces: the SPLIT instantiations ran."""
+    stats = _pihat_sweep(ctx, seed, cases, "small")
+    assert stats["split_launches"] > 0, stats
+
+
+@pytest.mark.parametrize("seed,cases", PIHAT_EDGES)
+def test_random_pihat_tile_and_step_edges(ctx, seed, cases):
+    _pihat_sweep(ctx, seed, cases, "edges")
+
+
+@pytest.mark.parametrize("seed,cases", PIHAT_TILES)
+def test_random_pihat_launches_of_64_tiles(ctx, seed, cases):
+    _pihat_sweep(ctx, seed, cases, "tiles")
 
 
 def test_one_staged_configuration_repeated(ctx):

@@ -15,6 +15,7 @@ import cuking_amd
 from cuking_amd import _lib
 
 import pihat_cases as pc
+from pihat_cases import raw_call   # (tests/test_gpu_call_forms.py takes it from here)
 
 pytestmark = pytest.mark.gpu
 
@@ -150,33 +151,6 @@ def test_launch_shapes(restored):
         restored.set_option("split_wgs", 256)
         restored.set_option("dyn_tail_tiles", 16384)
         restored.set_option("xcd_swizzle", 2)
-
-
-def raw_call(ctx, sm, wps, d_bits, model, capacity, tile_range=None, stream=None,
-             min_pi_hat=MIN_PI_HAT, sentinel_rows=4):
-    """The bare ABI call into a buffer of `capacity` records followed by `sentinel_rows` rows
-    of 0x55 bytes: (records written as host rows, count, overflow flag, the rows behind)."""
-    import torch
-    dev = f"cuda:{ctx.device}"
-    buf = torch.full((capacity + sentinel_rows, 6), 0x55555555, dtype=torch.int32, device=dev)
-    words = torch.zeros(2, dtype=torch.int32, device=dev)
-    head = (ctx.handle, C.byref(sm.c), wps, d_bits.data_ptr())
-    tail = (C.byref(model.c), min_pi_hat, 0, capacity, buf.data_ptr() if capacity else None,
-            words[0:1].data_ptr(), words[1:2].data_ptr(),
-            stream.cuda_stream if stream is not None else None)
-    if stream is not None:
-        stream.wait_stream(torch.cuda.current_stream())
-    if tile_range is None:
-        _lib.check(ctx.lib.cuking_compute_pihat(*head, *tail))
-    else:
-        _lib.check(ctx.lib.cuking_compute_pihat_tiles(*head, *tile_range, *tail))
-    if stream is not None:
-        stream.synchronize()
-    torch.cuda.synchronize(ctx.device)
-    count, overflow = (int(x) & 0xFFFFFFFF for x in words.tolist())
-    host = buf.cpu().numpy()
-    rows = np.ascontiguousarray(host[:min(count, capacity)]).view(cuking_amd.KING_RESULT_DTYPE)
-    return rows.reshape(-1), count, overflow, host[capacity:]
 
 
 @pytest.mark.parametrize("variant", VARIANTS)

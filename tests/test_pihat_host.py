@@ -82,17 +82,7 @@ def test_model_host_equals_restatement_bitwise():
     assert cuking_amd.pi_hat_model_host(pc.counts_array([(pc.MAX_PEOPLE, 0, 0)]), 1).sites_used == 1
 
 
-MODELS = {
-    "seeded rows": lambda: pc.model_of_rows(pc.seeded_count_rows()),
-    "333 x 5000": lambda: pc.model_of_rows([(150, 140, 40), (300, 30, 1), (100, 160, 70)] * 50),
-    "zero e00": lambda: pc.model_of_rows([(40, 0, 0), (0, 0, 7)]),
-    "zero e00 and e11": lambda: (0.0, 0.0, 1.0, 0.0, 1.0, 3),
-    "tiny e00": lambda: (1e-300, 0.4, 0.6, 0.36, 0.64, 9),
-    "NaN": lambda: pc.model_of_rows([]),
-    # (no count row gives a negative expectation: z0 = ibs0 / (e00 S) >= 0 under every model of
-    #  counts, so the z0 < 0 step can only be driven by a model made by hand)
-    "negative e00": lambda: (-0.1, 0.4, 0.5, 0.4, 0.6, 3),
-}
+MODELS = pc.MODELS
 
 
 @pytest.mark.parametrize("name", sorted(MODELS))
